@@ -21,7 +21,9 @@ full replica of the sketches.
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same arguments>` as a CHILD process,
 before anything in this process has touched the GPU, and exits with the child's code.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with the extra objects
+A plain run sets up, warms up, times --steps steps and prints ONE JSON line on rank 0 (metric, value, unit, ms_per_step,
+config, ...); --dump-outputs DIR also writes the selected pairs of the last timed step (write_outputs).  --full adds the
+extra objects
   roofline          the binding resource of the kernel that is the LONGEST of the step by measured duration (the all-pairs signature
                     join, or stage 2a's union histograms): vector-instruction issue, `frac` against the mix-weighted peak plus the
                     same rate against the guide's raw issue rate and the measured mixed rate, the model count beside PMC's SQ_INSTS_VALU;
@@ -85,6 +87,11 @@ def parse():
                     help="gloo = rehearsal of the multi-rank logic on a box with fewer GPUs than ranks (records staged through the host)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="target CPU time of each baseline sample")
     ap.add_argument("--param", action="append", default=[], metavar="NAME=VALUE", help="selhip_ctx_set_param (development A/B runs), repeatable")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: per-kernel times, rooflines, stream_kernel, harder_workload, CPU baselines and the "
+                         "PCIe-inclusive pass (--no-cpu-baseline / --no-extras trim this)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the selected pairs of the last timed step (sorted by (i, k)) as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -287,12 +294,18 @@ def main():
     dom_pass_ms = sel.kernel_ms(timed_key)                       # all launches of one pass (a pipelined pass: one per row chunk)
     dom_launches = max(1.0, sel.kernel_launches(timed_key))
     dom_span_ms = sel.kernel_ms("join_span") if (used_sig and not timed_hist) else -1.0   # first start -> last end of the pass's join launches (chunk lanes overlap them)
-    sel.timing(1)                                                # outside the timed region: every kernel scope, a few passes
-    for _ in range(5):
-        step()
-    torch.cuda.synchronize(dev)
-    detail_ms = {k: sel.kernel_ms(k) for k in ("prep", "sigbuild", "join", "verify", "stage1", "aux", "group", "hist", "select", "total")}
-    stage1_launches = max(1.0, sel.kernel_launches(dom_key))
+    # the last timed step's frame (the gathered one when the collectives run), taken before any further pass reuses the buffers
+    last_frame = None
+    if args.dump_outputs and rank == 0:
+        last_frame = (state["recv"][state["last"]] if dist_on else state["send"][state["last"]]).cpu().numpy()
+    detail_ms, stage1_launches = {}, 1.0
+    if args.full:
+        sel.timing(1)                                            # outside the timed region: every kernel scope, a few passes
+        for _ in range(5):
+            step()
+        torch.cuda.synchronize(dev)
+        detail_ms = {k: sel.kernel_ms(k) for k in ("prep", "sigbuild", "join", "verify", "stage1", "aux", "group", "hist", "select", "total")}
+        stage1_launches = max(1.0, sel.kernel_launches(dom_key))
     sel.timing(0)
 
     t_max = torch.tensor([dt], dtype=torch.float64, device=cdev)
@@ -329,8 +342,6 @@ def main():
         wkey = args.workload + ("hard" if args.hard else "")
         kernels = {k: v for k, v in detail_ms.items() if v > 0}
         kernels[timed_key + "_in_timed_region"] = dom_pass_ms
-        stage1_ms = detail_ms["join"] if used_sig else detail_ms["stage1"]
-        achieved_hbm = alg_bytes / (stage1_ms / launches * 1e-3) / 1e9 if stage1_ms > 0 else None
         out = {
             "metric": "sketch pair-comparisons/sec (N genomes x m buckets)",
             "value": value, "unit": "pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -348,6 +359,14 @@ def main():
             "bucket_pair_comparisons_per_s_nominal": value * cfg.m,
             "kernel_ms": kernels,
         }
+        if n_degenerate:
+            out["config"]["degenerate_genomes"] = n_degenerate
+        if last_frame is not None:
+            write_outputs(Path(args.dump_outputs), last_frame, (pairs_per_step, int(totals[1].item()), int(totals[2].item())))
+
+    if rank == 0 and args.full:
+        stage1_ms = detail_ms["join"] if used_sig else detail_ms["stage1"]
+        achieved_hbm = alg_bytes / (stage1_ms / launches * 1e-3) / 1e9 if stage1_ms > 0 else None
         # ---- rooflines: one per stage; `roofline` = that of the kernel that is the longest of the step (durations of the passes
         # with every kernel timed, outside the timed region; the one chosen for the timed region's events is stated)
         r1 = None
@@ -388,10 +407,8 @@ def main():
                                   "note": "SURVEY.md 8(d) nominal: one candidate sketch streamed per pair-comparison.  NOT a bound of this design: "
                                           "both stage-1 kernels reuse every byte they load against a tile of queries, so the ratio exceeds 1; "
                                           "measured HBM traffic per launch is `traffic` of the stage-1 roofline"}
-        if n_degenerate:
-            out["config"]["degenerate_genomes"] = n_degenerate
 
-    extras = rank == 0 and world == 1 and not args.no_extras
+    extras = rank == 0 and world == 1 and args.full and not args.no_extras
     # ---- the literal north_star kernel (ALGO_STREAM: query tile staged in LDS, candidates streamed row-major, lane-mask
     # reduction) measured beside the default algorithm, outside the timed region (rank 0, N=1, same inputs)
     if extras and args.algo == "auto" and not two_stage:
@@ -453,7 +470,7 @@ def main():
         del aux_h
 
     # ---- CPU baseline: the oracle (OpenMP port of selection.cpp:270-291 / time_smh.cpp:229-257) on a bounded sample
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         sys.path.insert(0, str(ROOT / "tests"))
         import oracle_py
         orc = oracle_py.Oracle()
@@ -520,7 +537,7 @@ def main():
                                                       f"{times[0]:.2f} s and {times[1]:.2f} s wall, difference = {dp} pairs (CB+smh_a mode, the program's only mode)"}
             except Exception as e:                     # the reference binary is optional equipment
                 out["cpu_reference"] = {"error": str(e)[:200]}
-    if rank == 0 and world == 1 and (args.pcie or not args.no_extras):
+    if rank == 0 and world == 1 and (args.pcie or (args.full and not args.no_extras)):
         # PCIe-inclusive variant (never `value`): the boundary handed HOST buffers (selhip_ctx_upload: copies, bit planes of the HLL
         # registers, cardinalities given), then one pass.  First call = with the context's allocations; second = the same context again.
         h = hll_t.cpu().numpy(); a = aux_t.cpu().numpy().view(np.uint64)
@@ -547,6 +564,28 @@ def main():
     sel.close()
     if dist_on:
         dist.destroy_process_group()
+
+
+DUMP_MAX_PAIRS = 2_000_000        # three float64 arrays of this length: 48 MB
+
+
+def write_outputs(out_dir, frame, counts):
+    """--dump-outputs: the selected pairs of the last timed step as a caller of the pass receives them (row ranks i < k in
+    ascending-cardinality order and the Jaccard estimate), sorted by (i, k) so that two builds compare element for element;
+    a longer list is thinned to a fixed seeded sample of DUMP_MAX_PAIRS.  stats = pairs evaluated, stage-1 survivors, selected."""
+    import numpy as np
+    from cuda_selection_criteria_amd.selection import PAIR_DTYPE
+    frames = frame.reshape(-1, frame.shape[-2], 2)             # one frame per rank: record 0 = {count, 0}, then the records
+    pairs = np.concatenate([f[1:1 + int(f[0, 0])].reshape(-1).view(PAIR_DTYPE) for f in frames])
+    assert len(pairs) == counts[2], (len(pairs), counts)
+    pairs = pairs[np.lexsort((pairs["k"], pairs["i"]))]
+    if len(pairs) > DUMP_MAX_PAIRS:
+        pairs = pairs[np.sort(np.random.default_rng(0x5EED).choice(len(pairs), DUMP_MAX_PAIRS, replace=False))]
+    out_dir.mkdir(parents=True, exist_ok=True)
+    np.save(out_dir / "pair_i.npy", pairs["i"].astype(np.float64))
+    np.save(out_dir / "pair_k.npy", pairs["k"].astype(np.float64))
+    np.save(out_dir / "jaccard.npy", pairs["jaccard"].astype(np.float64))
+    np.save(out_dir / "stats.npy", np.array(counts, dtype=np.float64))
 
 
 def _json(path):

@@ -12,7 +12,7 @@ python scripts/bench_build.py > gpurun_out/bench_build_$TAG.json 2> gpurun_out/b
 python -c "
 import json; d=json.load(open('gpurun_out/bench_build_$TAG.json')); print('build: gpu %.3g kmers/s (%.2f ms), ref cpu %s' % (d['gpu_kmers_per_s'], d['gpu_ms'], d.get('cpu_reference')))"
 i=0
-for A in "--steps 20 --warmup 3 --no-cpu-baseline" "$@"; do
+for A in "--full --steps 20 --warmup 3 --no-cpu-baseline" "$@"; do
   i=$((i+1))
   timeout -k 10 900 python bench.py $A > gpurun_out/bench_${TAG}_$i.json 2> gpurun_out/bench_${TAG}_$i.err || { tail -30 gpurun_out/bench_${TAG}_$i.err; exit 1; }
   python - <<PY

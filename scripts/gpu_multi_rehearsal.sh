@@ -13,4 +13,4 @@ d=json.loads(open("gpurun_out/bench_gloo_$N.json").read().strip().splitlines()[-
 print("ranks=$N", "value=%.4g"%d["value"], "ms/step=%.3f"%d["ms_per_step"], d["config"]["n_genomes"], d["config"]["pairs_per_step"], d["config"]["selected_pairs"], d["scaling"])
 PY
 done
-timeout -k 10 300 python bench.py --steps 10 --warmup 2 --no-cpu-baseline | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('single', '%.4g'%d['value'], '%.3f'%d['ms_per_step'], d['roofline']['traffic'])"
+timeout -k 10 300 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('single', '%.4g'%d['value'], '%.3f'%d['ms_per_step'], d['roofline']['traffic'])"

@@ -9,7 +9,7 @@ timeout -k 10 900 python -m pytest tests/test_gpu_parity.py -x -q -m gpu -k "bit
 tail -2 $O/pytest_a.log
 for A in "hist_algo=0" "hist_algo=1"; do
   for H in "" "--hard"; do
-    timeout -k 10 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras --param $A $H > $O/bench_${A}_${H#--}.json 2> $O/bench_${A}_${H#--}.err || { tail -20 $O/bench_${A}_${H#--}.err; exit 1; }
+    timeout -k 10 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extras --param $A $H > $O/bench_${A}_${H#--}.json 2> $O/bench_${A}_${H#--}.err || { tail -20 $O/bench_${A}_${H#--}.err; exit 1; }
     python - <<PY
 import json
 d=json.load(open("$O/bench_${A}_${H#--}.json"))

@@ -5,7 +5,7 @@ cd ${GRAFT_REPO_ROOT:-$(pwd)}
 O=gpurun_out/r03; mkdir -p $O
 run() {  # tag, args...
   T=$1; shift
-  timeout -k 10 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras "$@" > $O/sw_$T.json 2> $O/sw_$T.err || { tail -20 $O/sw_$T.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extras "$@" > $O/sw_$T.json 2> $O/sw_$T.err || { tail -20 $O/sw_$T.err; exit 1; }
   python - <<PY
 import json
 d=json.load(open("$O/sw_$T.json"))

@@ -8,7 +8,7 @@ timeout -k 10 900 python -m pytest tests/test_gpu_parity.py -x -q -m gpu -k "bit
 tail -1 $O/pytest_$T.log
 run() {
   TT=$1; shift
-  timeout -k 10 300 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-extras "$@" > $O/c_$TT.json 2> $O/c_$TT.err || { tail -20 $O/c_$TT.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-extras "$@" > $O/c_$TT.json 2> $O/c_$TT.err || { tail -20 $O/c_$TT.err; exit 1; }
   python - <<PY
 import json
 d=json.load(open("$O/c_$TT.json"))

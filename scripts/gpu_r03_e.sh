@@ -4,7 +4,7 @@ cd ${GRAFT_REPO_ROOT:-$(pwd)}
 O=gpurun_out/r03; mkdir -p $O
 run() {
   TT=$1; shift
-  timeout -k 10 300 python bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-extras "$@" > $O/e_$TT.json 2> $O/e_$TT.err || { tail -20 $O/e_$TT.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-extras "$@" > $O/e_$TT.json 2> $O/e_$TT.err || { tail -20 $O/e_$TT.err; exit 1; }
   python - <<PY
 import json
 d=json.load(open("$O/e_$TT.json"))

@@ -6,7 +6,7 @@ timeout -k 10 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_rando
 tail -1 $O/pytest_g.log
 run() {
   TT=$1; shift
-  timeout -k 10 300 python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-extras "$@" > $O/g_$TT.json 2> $O/g_$TT.err || { tail -20 $O/g_$TT.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-extras "$@" > $O/g_$TT.json 2> $O/g_$TT.err || { tail -20 $O/g_$TT.err; exit 1; }
   python - <<PY
 import json
 d=json.load(open("$O/g_$TT.json"))

@@ -6,7 +6,7 @@ timeout -k 10 600 python -m pytest tests/test_gpu_parity.py -x -q -m gpu -k "sma
 tail -1 $O/pytest_i.log
 run() {
   TT=$1; shift
-  timeout -k 10 300 python bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-extras "$@" > $O/i_$TT.json 2> $O/i_$TT.err || { tail -20 $O/i_$TT.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-extras "$@" > $O/i_$TT.json 2> $O/i_$TT.err || { tail -20 $O/i_$TT.err; exit 1; }
   python - <<PY
 import json
 d=json.load(open("$O/i_$TT.json"))

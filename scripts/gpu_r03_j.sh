@@ -7,7 +7,7 @@ tail -1 $O/pytest_j.log
 SELHIP_LIB=scripts/microbench/libselhip_trace.so timeout -k 10 200 python scripts/small_trace.py > $O/small_trace_j.txt 2>&1 && cat $O/small_trace_j.txt
 run() {
   TT=$1; shift
-  timeout -k 10 300 python bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-extras "$@" > $O/j_$TT.json 2> $O/j_$TT.err || { tail -20 $O/j_$TT.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-extras "$@" > $O/j_$TT.json 2> $O/j_$TT.err || { tail -20 $O/j_$TT.err; exit 1; }
   python - <<PY
 import json
 d=json.load(open("$O/j_$TT.json"))

@@ -8,7 +8,7 @@ tail -1 $O/pytest_k.log
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2
 run() {
   TT=$1; shift
-  timeout -k 10 400 python bench.py "$@" > $O/k_$TT.json 2> $O/k_$TT.err || { tail -20 $O/k_$TT.err; exit 1; }
+  timeout -k 10 400 python bench.py --full "$@" > $O/k_$TT.json 2> $O/k_$TT.err || { tail -20 $O/k_$TT.err; exit 1; }
   python - <<PY
 import json
 d=json.load(open("$O/k_$TT.json"))

@@ -7,7 +7,7 @@ timeout -k 10 900 python -m pytest tests/test_gpu_parity.py -x -q -m gpu -k "bit
 tail -1 $O/pytest_m.log
 run() {
   TT=$1; shift
-  timeout -k 10 400 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-extras "$@" > $O/m_$TT.json 2> $O/m_$TT.err || { tail -20 $O/m_$TT.err; exit 1; }
+  timeout -k 10 400 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-extras "$@" > $O/m_$TT.json 2> $O/m_$TT.err || { tail -20 $O/m_$TT.err; exit 1; }
   python - <<PY
 import json
 d=json.load(open("$O/m_$TT.json"))

@@ -8,7 +8,7 @@ tail -1 $O/pytest_o.log
 for W in "--workload cfg3" "--workload cfg3 --genomes 28280" "--workload cfg4"; do
   for G in 8 16 32; do
     T=$(echo "$W" | tr -d ' -')_$G
-    timeout -k 10 300 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-extras $W --param sig_tile_g=$G > $O/o_$T.json 2> $O/o_$T.err || { tail -20 $O/o_$T.err; exit 1; }
+    timeout -k 10 300 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-extras $W --param sig_tile_g=$G > $O/o_$T.json 2> $O/o_$T.err || { tail -20 $O/o_$T.err; exit 1; }
     python - <<PY
 import json
 d=json.load(open("$O/o_$T.json"))

@@ -7,7 +7,7 @@ for W in "--workload cfg3" "--workload cfg3 --genomes 28280" "--workload cfg4"; 
   for L in 4 8 16; do
     T=$(echo "$W" | tr -d ' -')_L$L
     if [ $L = 4 ]; then unset SELHIP_LIB; else export SELHIP_LIB=scripts/microbench/libselhip_sig$L.so; fi
-    timeout -k 10 300 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-extras $W > $O/p_$T.json 2> $O/p_$T.err || { tail -20 $O/p_$T.err; exit 1; }
+    timeout -k 10 300 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-extras $W > $O/p_$T.json 2> $O/p_$T.err || { tail -20 $O/p_$T.err; exit 1; }
     python - <<PY
 import json
 d=json.load(open("$O/p_$T.json"))

@@ -8,7 +8,7 @@ tail -1 $O/pytest_r.log
 for W in 2 8; do timeout -k 10 200 python scripts/il_breakdown.py $W 2>&1 | grep -v amdgpu.ids; done
 run() {
   TT=$1; shift
-  timeout -k 10 400 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-extras "$@" > $O/r_$TT.json 2> $O/r_$TT.err || { tail -20 $O/r_$TT.err; exit 1; }
+  timeout -k 10 400 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-extras "$@" > $O/r_$TT.json 2> $O/r_$TT.err || { tail -20 $O/r_$TT.err; exit 1; }
   python - <<PY
 import json
 d=json.load(open("$O/r_$TT.json"))

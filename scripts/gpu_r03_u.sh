@@ -5,7 +5,7 @@ cd ${GRAFT_REPO_ROOT:-$(pwd)}
 O=gpurun_out/r03; mkdir -p $O
 for Q in 16 32 48 64 80 96; do
   for W in 4 8; do
-    timeout -k 10 300 python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-extras --param join_qt=$Q --param join_wpb=$W > $O/u_${Q}_$W.json 2> $O/u_${Q}_$W.err || { tail -20 $O/u_${Q}_$W.err; exit 1; }
+    timeout -k 10 300 python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-extras --param join_qt=$Q --param join_wpb=$W > $O/u_${Q}_$W.json 2> $O/u_${Q}_$W.err || { tail -20 $O/u_${Q}_$W.err; exit 1; }
     python - <<PY
 import json
 d=json.load(open("$O/u_${Q}_$W.json"))
