@@ -89,6 +89,9 @@ HIP_SYMBOLS = {
     "selhip_ooc_select": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i64, _i, _i, _i, _i, _i, C.c_float, _i, _i, _i64, _i,
                                _vp, _i64, C.POINTER(_i64), C.POINTER(_i64)]),
     "selhip_ctx_set_candidate_begin": (_i, [_vp, _i64]),
+    "selhip_ctx_upload_queries": (_i, [_vp, _vp, _vp, _vp, _i64]),
+    "selhip_ctx_attach_queries": (_i, [_vp, _vp, _vp, _vp, _i64]),
+    "selhip_ctx_run_queries": (_i, [_vp, _i, _i, C.c_float, _i, _i]),
     "selhip_smh_a_pairs": (_i, [_vp, _i, _i, _i, _vp, _i64, _vp, _vp]),
     "selhip_hll_union_hist": (_i, [_vp, _i, _vp, _i64, _vp, _vp]),
     "selhip_hll_bitslice": (_i, [_vp, _i64, _vp, _vp, _vp, _vp]),

@@ -53,6 +53,7 @@ void selhip_ctx_destroy(selhip_ctx* c) {
     c->hj_keys_in.release(); c->hj_keys_out.release(); c->hj_vals_in.release(); c->hj_vals_out.release(); c->hj_tmp.release();
     c->csr_cnt.release(); c->csr_start.release(); c->grouped.release(); c->scan_tmp.release();
     c->hll_bs.release(); c->hll_bs_max.release(); c->hll_gmax.release(); c->small_bar.release();
+    release_queries(c);
     if (c->h_pc) (void)hipHostFree(c->h_pc);
     if (c->st_stage1) {
         (void)hipStreamDestroy(c->st_stage1);
@@ -97,6 +98,7 @@ int selhip_ctx_set_row_interleave(selhip_ctx* c, int block_rows, int n_parts, in
 //   "small_pass" = 3   the one-launch pass with NO patience at its grid barrier (the bounded wait running out -> regular path)
 //   "sig_tile_g"       genomes per tile of the tiled signature build (8 / 16 / 32; 16 is the measured optimum)
 //   "hist_pad"         extra LDS bytes per block of the byte-row stage-2a kernel (lowers the resident waves per CU)
+//   "query_join_tile"  queries per block of the query passes' signature join (16, the default, or 32)
 int selhip_ctx_set_param(selhip_ctx* c, const char* name, int value) {
     if (!c || !name) return SELHIP_E_BADARG;
     if (!std::strcmp(name, "join_qt")) {
@@ -162,6 +164,11 @@ int selhip_ctx_set_param(selhip_ctx* c, const char* name, int value) {
         c->hist_pad = value;
         return SELHIP_OK;
     }
+    if (!std::strcmp(name, "query_join_tile")) {
+        if (value != 16 && value != 32) { set_err(&c->err, "query_join_tile must be 16 or 32"); return SELHIP_E_BADARG; }
+        c->query_join_tile = value;
+        return SELHIP_OK;
+    }
     if (!std::strcmp(name, "timed_kernel")) {
         if (value < 0 || value > 1) { set_err(&c->err, "timed_kernel must be 0 (stage-1 kernel) or 1 (stage 2a)"); return SELHIP_E_BADARG; }
         c->timed_kernel = value;
@@ -201,6 +208,7 @@ int selhip_ctx_get_param(const selhip_ctx* c, const char* name, int* value) {
     if (!std::strcmp(name, "join_tile_rows"))   { *value = join_tile_rows(c); return SELHIP_OK; }
     if (!std::strcmp(name, "chunks"))           { *value = c->n_chunks_last; return SELHIP_OK; }
     if (!std::strcmp(name, "small_pass_used"))  { *value = c->small_used ? 1 : 0; return SELHIP_OK; }
+    if (!std::strcmp(name, "query_db_sig_builds")) { *value = c->q.db_sig_builds; return SELHIP_OK; }   // database signature builds of the query passes
     return SELHIP_E_BADARG;
 }
 
@@ -304,6 +312,7 @@ int selhip_ctx_upload(selhip_ctx* c, const uint8_t* h_hll, const uint64_t* h_aux
     }
     c->d_hll = c->own_hll.p; c->d_aux = (const u64*)c->own_aux.p; c->owns_sketches = true;
     c->d_aux_hll = nullptr; c->p_aux = 0;
+    drop_queries(c);
     return after_sketches(c, h_cards, true);
 }
 
@@ -318,6 +327,7 @@ int selhip_ctx_attach(selhip_ctx* c, const uint8_t* d_hll, const uint64_t* d_aux
     c->n = n; c->m = m; c->p = p_hll; c->have_run = false; c->pending = false; c->cand_begin = 0; c->sig_key = 0; c->small_pass_failed = false;
     c->d_hll = d_hll; c->d_aux = (const u64*)d_aux; c->owns_sketches = false;
     c->d_aux_hll = nullptr; c->p_aux = 0;
+    drop_queries(c);
     return after_sketches(c, d_cards, false);
 }
 
@@ -359,7 +369,7 @@ int selhip_ctx_run_async(selhip_ctx* c, int mode, int algo, float tau_f, int n_r
     HIPCHK(&c->err, hipSetDevice(c->device));
     c->mode = mode; c->algo = algo; c->tau_f = tau_f; c->n_rows = n_rows; c->n_bands = n_bands;
     c->row_begin = row_begin; c->row_end = row_end;
-    c->have_run = false;
+    c->have_run = false; c->last_was_query = false;
     std::memset(&c->last, 0, sizeof c->last);
     if (c->n == 0 || row_begin == row_end) { c->pending = false; c->have_run = true; return SELHIP_OK; }
     size_t surv_cap = std::max<size_t>(c->surv.cap, std::max<size_t>((size_t)1 << 20, (size_t)c->n * 16));
@@ -490,6 +500,7 @@ int selhip_ctx_copy_results_framed(selhip_ctx* c, void* d_dst, int64_t cap_recor
     // frame = one 16-byte header record {u64 count, u64 0} followed by the records; both copies are device-to-device
     if (!c || !d_dst || cap_records < 0) return SELHIP_E_BADARG;
     if (!c->have_run) return SELHIP_E_STATE;
+    if (c->last_was_query) { set_err(&c->err, "framed copies are for all-pairs passes; after a query pass use selhip_ctx_copy_results"); return SELHIP_E_STATE; }
     HIPCHK(&c->err, hipSetDevice(c->device));
     HIPCHK(&c->err, hipMemcpyAsync(d_dst, &c->pcb->n_results, sizeof(u64), hipMemcpyDeviceToDevice, c->stream));
     const int64_t cnt = std::min<int64_t>((int64_t)c->last.n_results, cap_records);
@@ -503,6 +514,7 @@ int selhip_ctx_copy_results_framed_async(selhip_ctx* c, void* d_dst, int64_t cap
     if (!c || !d_dst || cap_records < 0) return SELHIP_E_BADARG;
     if (!c->pending && !c->have_run) return SELHIP_E_STATE;
     if (!c->results.p || !c->pcb) return SELHIP_E_STATE;
+    if (c->last_was_query && !c->pending) { set_err(&c->err, "framed copies are for all-pairs passes; after a query pass use selhip_ctx_copy_results"); return SELHIP_E_STATE; }
     HIPCHK(&c->err, hipSetDevice(c->device));
     if ((uintptr_t)d_dst & 15) { set_err(&c->err, "frame buffer must be 16-byte aligned"); return SELHIP_E_BADARG; }
     static_assert(sizeof(selhip_pair_t) == 16, "frame records are 16 bytes");

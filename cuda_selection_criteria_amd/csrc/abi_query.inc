@@ -1,0 +1,134 @@
+// abi_query.inc -- the C ABI of the query passes (include/selection_hip.h section 2b): upload / attach a query set, run a query pass.
+// Included by selection_kernels.hip.  The results go through selhip_ctx_result_count / _fetch / _stats / _last_attempts.
+
+extern "C" {
+
+static int after_queries(selhip_ctx* c, const double* cards_src, bool cards_on_host) {
+    auto& q = c->q;
+    q.khi = 0;
+    if (q.n == 0) { q.d_cards = nullptr; return SELHIP_OK; }
+    // the registers as bit planes (stage 2a of the query pass), as for the database
+    HIPCHK(&c->err, q.bs.ensure((size_t)q.n * kBsGenomeDwords));
+    HIPCHK(&c->err, q.gmax.ensure((size_t)q.n));
+    HIPCHK(&c->err, q.bs_max.ensure(1));
+    int rc = build_bitslices(&c->err, c->stream, q.d_hll, q.n, q.bs.p, q.gmax.p, q.bs_max.p, &q.khi);
+    if (rc) return rc;
+    if (!cards_src) {
+        HIPCHK(&c->err, q.own_cards.ensure((size_t)q.n));
+        rc = compute_cards(c, q.d_hll, q.n, c->p, q.own_cards.p);
+        if (rc) return rc;
+        q.d_cards = q.own_cards.p;
+    } else if (cards_on_host) {
+        for (int64_t i = 0; i < q.n; ++i) {
+            const double v = cards_src[i];
+            if (!(v >= 0.0) || !(v < 9.2e18)) { set_err(&c->err, "query cards[%lld] = %g is not a finite value in [0, 2^63)", (long long)i, v); return SELHIP_E_BADARG; }
+            if (i && v < cards_src[i - 1]) { set_err(&c->err, "query cards are not in ascending order at rank %lld", (long long)i); return SELHIP_E_BADARG; }
+        }
+        HIPCHK(&c->err, q.own_cards.ensure((size_t)q.n));
+        HIPCHK(&c->err, hipMemcpyAsync(q.own_cards.p, cards_src, (size_t)q.n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        q.d_cards = q.own_cards.p;
+    } else {
+        q.d_cards = cards_src;
+    }
+    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    return SELHIP_OK;
+}
+
+static int check_query_shape(selhip_ctx* c, int64_t n_q) {
+    if (!c->d_aux && c->n) { set_err(&c->err, "upload or attach the database before the queries"); return SELHIP_E_STATE; }
+    if (c->m <= 0) { set_err(&c->err, "upload or attach the database before the queries"); return SELHIP_E_STATE; }
+    if (c->p != 14) { set_err(&c->err, "query passes need p = 14 sketches (the database has p = %d)", c->p); return SELHIP_E_BADARG; }
+    if (c->pending) { set_err(&c->err, "a pass is still pending (selhip_ctx_finish)"); return SELHIP_E_STATE; }
+    if (n_q < 0 || n_q > 0x7FFFFFF0ll) { set_err(&c->err, "n_q %lld out of range", (long long)n_q); return SELHIP_E_BADARG; }
+    return SELHIP_OK;
+}
+
+int selhip_ctx_upload_queries(selhip_ctx* c, const uint8_t* h_hll, const uint64_t* h_aux, const double* h_cards, int64_t n_q) {
+    if (!c) return SELHIP_E_BADARG;
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    int rc = check_query_shape(c, n_q);
+    if (rc) return rc;
+    if (n_q > 0 && (!h_hll || !h_aux)) { set_err(&c->err, "null query sketch pointer"); return SELHIP_E_BADARG; }
+    auto& q = c->q;
+    q.n = -1;
+    if (n_q > 0) {
+        HIPCHK(&c->err, q.own_hll.ensure((size_t)n_q << 14));
+        HIPCHK(&c->err, q.own_aux.ensure((size_t)n_q * c->m));
+        HIPCHK(&c->err, hipMemcpyAsync(q.own_hll.p, h_hll, (size_t)n_q << 14, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(&c->err, hipMemcpyAsync(q.own_aux.p, h_aux, (size_t)n_q * c->m * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    q.d_hll = q.own_hll.p; q.d_aux = q.own_aux.p;
+    q.n = n_q;
+    rc = after_queries(c, h_cards, true);
+    if (rc) q.n = -1;
+    return rc;
+}
+
+int selhip_ctx_attach_queries(selhip_ctx* c, const uint8_t* d_hll, const uint64_t* d_aux, const double* d_cards, int64_t n_q) {
+    if (!c) return SELHIP_E_BADARG;
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    int rc = check_query_shape(c, n_q);
+    if (rc) return rc;
+    if (n_q > 0 && (!d_hll || !d_aux)) { set_err(&c->err, "null query sketch pointer"); return SELHIP_E_BADARG; }
+    if (((uintptr_t)d_hll & 15) || ((uintptr_t)d_aux & 15)) { set_err(&c->err, "query sketch pointers must be 16-byte aligned"); return SELHIP_E_BADARG; }
+    auto& q = c->q;
+    q.d_hll = d_hll; q.d_aux = (const u64*)d_aux;
+    q.n = n_q;
+    rc = after_queries(c, d_cards, false);
+    if (rc) q.n = -1;
+    return rc;
+}
+
+int selhip_ctx_run_queries(selhip_ctx* c, int mode, int algo, float tau_f, int n_rows, int n_bands) {
+    if (!c) return SELHIP_E_BADARG;
+    auto& q = c->q;
+    if (q.n < 0) { set_err(&c->err, "run_queries before upload / attach of the queries"); return SELHIP_E_STATE; }
+    if (c->pending) { set_err(&c->err, "a pass is still pending (selhip_ctx_finish)"); return SELHIP_E_STATE; }
+    if (mode != SELHIP_MODE_SMH && mode != SELHIP_MODE_CB_SMH) { set_err(&c->err, "bad mode %d", mode); return SELHIP_E_BADARG; }
+    if (c->criterion != SELHIP_CRIT_SMH_A) { set_err(&c->err, "query passes support the criterion smh_a only (criterion %d is set)", c->criterion); return SELHIP_E_BADARG; }
+    if (algo == SELHIP_ALGO_HASHJOIN) { set_err(&c->err, "query passes have no ALGO_HASHJOIN; use AUTO, SIG or STREAM"); return SELHIP_E_BADARG; }
+    if (algo != SELHIP_ALGO_AUTO && algo != SELHIP_ALGO_STREAM && algo != SELHIP_ALGO_SIG) { set_err(&c->err, "bad algo %d", algo); return SELHIP_E_BADARG; }
+    if (n_rows <= 0 || n_bands <= 0 || (long long)n_rows * n_bands != c->m) {
+        set_err(&c->err, "n_rows*n_bands (%d*%d) != m (%d)", n_rows, n_bands, c->m);
+        return SELHIP_E_BADARG;
+    }
+    const bool sig_ok = sig_supported(c->m, n_rows, n_bands);
+    if (algo == SELHIP_ALGO_SIG && !sig_ok) {
+        set_err(&c->err, "ALGO_SIG needs power-of-two rows and 8..128 bands (got %d x %d)", n_rows, n_bands);
+        return SELHIP_E_BADARG;
+    }
+    const bool use_sig = algo != SELHIP_ALGO_STREAM && sig_ok;
+    if (!use_sig && query_stream_tile(c->m) == 0) { set_err(&c->err, "ALGO_STREAM of a query pass holds m <= 4096 buckets (m = %d)", c->m); return SELHIP_E_BADARG; }
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    c->mode = mode; c->algo = algo; c->tau_f = tau_f; c->n_rows = n_rows; c->n_bands = n_bands;
+    c->have_run = false;
+    std::memset(&c->last, 0, sizeof c->last);
+    c->last_was_query = true;
+    if (q.n == 0 || c->n == 0) { c->have_run = true; c->last_attempts = 1; return SELHIP_OK; }
+    size_t cap = std::max<size_t>(q.surv.cap, std::max<size_t>((size_t)1 << 16, (size_t)q.n * 16));
+    if (c->init_cap > 0) cap = std::max<size_t>(q.surv.cap, (size_t)c->init_cap);       // test hook: start small, grow on overflow
+    size_t res_cap = std::max<size_t>(c->results.cap, cap);
+    const double tau = (double)tau_f;                 // float threshold widened, selection.cpp:81,164
+    for (int attempt = 0; attempt < 8; ++attempt) {
+        int rc = ensure_query_scratch(c, cap, res_cap);
+        if (!rc) rc = enqueue_query_pass(c, use_sig, tau);
+        if (rc) return rc;
+        HIPCHK(&c->err, wait_stream(c->stream));
+        const PassCounters pc = *q.h_pc;
+        if (pc.unsorted) { set_err(&c->err, "database or query cards are not in ascending order"); return SELHIP_E_BADARG; }
+        bool grow = false;
+        // (n_pre: the join's list; n_survivors: the survivor list)
+        const u64 worst = std::max(pc.n_pre, pc.n_survivors);
+        if (worst > q.surv.cap || worst > q.cand.cap) { cap = std::max(cap, (size_t)(worst + worst / 8 + 1024)); grow = true; }
+        if (pc.n_results > c->results.cap) { res_cap = (size_t)(pc.n_results + pc.n_results / 8 + 1024); grow = true; }
+        if (!grow) {
+            c->last = pc; c->have_run = true; c->last_attempts = attempt + 1; c->last_was_query = true;
+            return SELHIP_OK;
+        }
+        res_cap = std::max(res_cap, cap);               // an internal list was too small: counts are exact, grow once and repeat
+    }
+    set_err(&c->err, "output buffers kept overflowing");
+    return SELHIP_E_OVERFLOW;
+}
+
+}  // extern "C"

@@ -19,6 +19,9 @@
 //   -o <file>   write the result as a binary result file (include/selection_host.h: "SELR" format: records + name table)
 //               instead of text on stdout
 //   -r <file>   no selection: print the text form of a result file written with -o (needs no GPU)
+//   -q <file>   query-vs-database selection: -q lists the query genomes, -l the database; prints "query_path db_path J" per
+//               selected pair (one member in each list) in (query rank, database rank) order (selhip_ctx_run_queries; criterion
+//               smh_a, one device -- not combinable with -g, -B, -o, -r or -c hll_a / hll_an)
 //   -x          usage
 #include <unistd.h>
 
@@ -32,6 +35,52 @@
 #include "../../../include/selection_hip.h"
 #include "../../../include/selection_host.h"
 
+// -q: the query list against the database list (-l), both loaded and sorted by cardinality; text on stdout
+static int run_queries(const std::string& query_file, const std::string& db_file, float threshold, int aux_bytes, int mode, int algo,
+                       int fp_mode, int threads) {
+    const unsigned m = (unsigned)aux_bytes / 8;
+    selhost_dataset* db = nullptr;
+    selhost_dataset* qs = nullptr;
+    if (selhost_dataset_load(&db, db_file.c_str(), m, 0, fp_mode, threads)) { std::cerr << selhost_last_error() << "\n"; return 1; }
+    if (selhost_dataset_load(&qs, query_file.c_str(), m, 0, fp_mode, threads)) {
+        std::cerr << selhost_last_error() << "\n";
+        selhost_dataset_free(db);
+        return 1;
+    }
+    int n_rows = 1, n_bands = 1;
+    selhost_banding(m, threshold, SELHOST_BANDING_CPU, &n_rows, &n_bands);
+    std::vector<selhip_pair_t> pairs;
+    selhip_ctx* ctx = nullptr;
+    int r = selhip_device_count() > 0 ? selhip_ctx_create(&ctx, 0) : SELHIP_E_NODEVICE;
+    if (r) {
+        std::cerr << "selection: no MI355X (gfx950) device available: " << selhip_last_error(nullptr) << "\n";
+        selhost_dataset_free(db); selhost_dataset_free(qs);
+        return 3;
+    }
+    selhip_ctx_set_fp_mode(ctx, fp_mode);
+    r = selhip_ctx_upload(ctx, selhost_dataset_hll(db), selhost_dataset_aux(db), selhost_dataset_cards(db), selhost_dataset_size(db), (int)m, 14);
+    if (!r) r = selhip_ctx_upload_queries(ctx, selhost_dataset_hll(qs), selhost_dataset_aux(qs), selhost_dataset_cards(qs), selhost_dataset_size(qs));
+    if (!r) r = selhip_ctx_run_queries(ctx, mode, algo, threshold, n_rows, n_bands);
+    if (!r) {
+        pairs.resize((size_t)selhip_ctx_result_count(ctx));
+        r = selhip_ctx_fetch(ctx, pairs.data(), (int64_t)pairs.size());
+    }
+    if (r) std::cerr << "selection: " << selhip_last_error(ctx) << "\n";
+    selhip_ctx_destroy(ctx);
+    if (!r) {
+        std::string out;
+        char line[8192];
+        for (const selhip_pair_t& pr : pairs) {
+            const int w = selhost_format_line(selhost_dataset_name(qs, pr.i), selhost_dataset_name(db, pr.k), pr.jaccard, line, sizeof line);
+            if (w > 0) out.append(line, (size_t)w);
+        }
+        std::cout << out;
+    }
+    selhost_dataset_free(db);
+    selhost_dataset_free(qs);
+    return r ? 4 : 0;
+}
+
 int main(int argc, char* argv[]) {
     std::string list_file = "";
     float threshold = 0.9f;              // selection_cuda.cpp:62
@@ -39,11 +88,14 @@ int main(int argc, char* argv[]) {
     std::string criterion = "smh_a";
     int threads = 8, n_gpus = 1, mode = SELHIP_MODE_CB_SMH, algo = SELHIP_ALGO_AUTO, fp_mode = SELHIP_FP_FMA;
     long long ooc_block = 0;
-    std::string out_file = "", dump_file = "";
+    std::string out_file = "", dump_file = "", query_file = "";
+    bool gpus_given = false;
     int c;
-    while ((c = getopt(argc, argv, "xl:b:a:h:c:t:g:nA:F:B:o:r:")) != -1) {
+    while ((c = getopt(argc, argv, "xl:b:a:h:c:t:g:nA:F:B:o:r:q:")) != -1) {
         switch (c) {
-            case 'x': std::cout << "Usage: -l -h -a -b [-c smh_a] [-t threads] [-g gpus] [-n] [-A auto|stream|sig] [-F 0|1] [-B block] [-o file] | -r file\n"; return 0;
+            case 'x': std::cout << "Usage: -l -h -a -b [-c smh_a] [-t threads] [-g gpus] [-n] [-A auto|stream|sig] [-F 0|1] [-B block] [-o file] | -r file\n"
+                                   "       -l db_list -q query_list -h -a [-n] [-A auto|stream|sig] [-F 0|1]   (query-vs-database selection)\n"; return 0;
+            case 'q': query_file = optarg; break;
             case 'B': ooc_block = std::stoll(optarg); break;
             case 'o': out_file = optarg; break;
             case 'r': dump_file = optarg; break;
@@ -53,12 +105,24 @@ int main(int argc, char* argv[]) {
             case 'h': threshold = std::stof(optarg); break;
             case 'c': criterion = optarg; break;
             case 't': threads = std::stoi(optarg); break;
-            case 'g': n_gpus = std::stoi(optarg); break;
+            case 'g': n_gpus = std::stoi(optarg); gpus_given = true; break;
             case 'n': mode = SELHIP_MODE_SMH; break;
             case 'A': algo = !strcmp(optarg, "stream") ? SELHIP_ALGO_STREAM : !strcmp(optarg, "sig") ? SELHIP_ALGO_SIG : !strcmp(optarg, "hashjoin") ? SELHIP_ALGO_HASHJOIN : SELHIP_ALGO_AUTO; break;
             case 'F': fp_mode = std::stoi(optarg) ? SELHIP_FP_FMA : SELHIP_FP_STRICT; break;
             default: break;
         }
+    }
+    if (!query_file.empty()) {
+        // checked before any file is read or device opened
+        const char* clash = gpus_given ? "-g" : ooc_block != 0 ? "-B" : !out_file.empty() ? "-o" : !dump_file.empty() ? "-r"
+                          : (criterion == "hll_a" || criterion == "hll_an") ? "-c hll_a / hll_an" : criterion != "smh_a" ? "-c" : nullptr;
+        if (clash) {
+            std::cerr << "selection: -q (query-vs-database selection) cannot be combined with " << clash
+                      << "; it runs criterion smh_a on one device and prints text\n";
+            return 2;
+        }
+        if (list_file.empty()) { std::cerr << "selection: -q needs the database list (-l)\n"; return 2; }
+        return run_queries(query_file, list_file, threshold, aux_bytes, mode, algo, fp_mode, threads);
     }
     if (!dump_file.empty()) {
         selhost_results* res = nullptr;

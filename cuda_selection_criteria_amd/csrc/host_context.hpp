@@ -163,6 +163,40 @@ struct selhip_ctx {
     int64_t row_begin = 0, row_end = 0;
     PassCounters last{};
 
+    // query passes (abi_query.inc, host_query.hpp): a second sketch set Q, in its own buffers, matched against the sketches above (D)
+    struct QuerySet {
+        int64_t n = -1;                             // -1 = no queries loaded (uploading / attaching the database drops them)
+        const uint8_t* d_hll = nullptr;
+        const u64* d_aux = nullptr;
+        const double* d_cards = nullptr;
+        DevBuf<uint8_t> own_hll;
+        DevBuf<u64> own_aux;
+        DevBuf<double> own_cards;
+        DevBuf<uint32_t> bs;                        // Q's bit planes [n][6][512], written at upload / attach
+        DevBuf<uint8_t> gmax;
+        DevBuf<int> bs_max;
+        int khi = 0;
+        DevBuf<int> lo, hi;                         // CB window of every query in D
+        DevBuf<u64> ecard;                          // truncated cards, combined index space: [0, n) = Q, [n, n + n_D) = D
+        DevBuf<uint32_t> sigQ, sigT, sigP, sigG;    // Q's band signatures (sigQ is read; the builder writes all four layouts)
+        DevBuf<uint32_t> db_sigQ, db_sigT, db_sigP, db_sigG;   // D's band signatures, kept across query passes
+        long long db_sig_key = 0;                   // (n_rows, n_bands, database generation) they were built for; 0 = none
+        int db_sig_builds = 0;                      // builds of D's signatures since the database was loaded ("query_db_sig_builds")
+        DevBuf<uint32_t> db_bs;                     // D's bit planes, only if the all-pairs path keeps none (hist_algo 0)
+        DevBuf<uint8_t> db_gmax;
+        long long db_bs_gen = -1;
+        int db_khi = 0;
+        DevBuf<selhip_int2_t> cand, surv;
+        DevBuf<uint32_t> counts;
+        DevBuf<PassCounters> pc;                    // two counter sets: pass k uses set k & 1, its first kernel clears the other
+        int pc_flip = 0;
+        bool pc_dirty = true;                       // clear both sets before the next pass (a pass did not get to the end of its enqueue)
+        PassCounters* h_pc = nullptr;
+    } q;
+    long long db_gen = 0;               // incremented by every upload / attach of the database
+    int query_join_tile = 16;           // queries per block of the query passes' signature join (16 or 32; "query_join_tile")
+    bool last_was_query = false;        // the results / statistics held are those of a query pass (no framed copies of them)
+
     int timing = 0;                     // 0 off, 1 every kernel scope, 2 dominant stage-1 kernel only
     int dominant_timer = T_STAGE1;
     int timed_kernel = 0;               // timing level 2 keeps the events of: 0 = the stage-1 kernel (join / stream), 1 = stage 2a ("timed_kernel")

@@ -1,0 +1,194 @@
+// host_query.hpp -- the query pass of libselhip.so: a query set Q against the context's database D (kernel_query.cuh), with the
+// overflow / repeat and timing bookkeeping of the all-pairs pass.  It has buffers and counters of its own (selhip_ctx::q): only the
+// result list and the statistics of the last run are shared with the all-pairs pass.
+// Part of the kernel translation unit selection_kernels.hip (included there, after host_pass.hpp); not a stand-alone header.
+#pragma once
+
+namespace {
+
+void drop_queries(selhip_ctx* c) {
+    c->q.n = -1;
+    c->q.db_sig_key = 0;
+    c->q.db_sig_builds = 0;
+    c->db_gen += 1;
+}
+
+void release_queries(selhip_ctx* c) {
+    auto& q = c->q;
+    q.own_hll.release(); q.own_aux.release(); q.own_cards.release(); q.bs.release(); q.gmax.release(); q.bs_max.release();
+    q.lo.release(); q.hi.release(); q.ecard.release();
+    q.sigQ.release(); q.sigT.release(); q.sigP.release(); q.sigG.release();
+    q.db_sigQ.release(); q.db_sigT.release(); q.db_sigP.release(); q.db_sigG.release(); q.db_bs.release(); q.db_gmax.release();
+    q.cand.release(); q.surv.release(); q.counts.release(); q.pc.release();
+    if (q.h_pc) (void)hipHostFree(q.h_pc);
+    q.h_pc = nullptr;
+}
+
+// band signatures of n genomes (sig_build_kernel without its bounds blocks), into the four layouts of the builder
+hipError_t launch_sig_rows(selhip_ctx* c, const u64* aux, int n, int r, int nb, uint32_t* sQ, uint32_t* sT, uint32_t* sP, uint32_t* sG) {
+    if (n <= 0) return hipSuccess;
+    const int n_pad = ((n + kWave - 1) / kWave) * kWave;
+    const bool tile_mode = is_pow2(c->m) && is_pow2(nb) && nb <= 128 && r >= 2 && r <= 32 && c->m >= 4 && c->sig_tile;
+    const long long threads = r <= kWave ? (long long)n * c->m : (long long)n * nb;
+    const int tg = c->sig_tile_g;
+    const unsigned blocks = tile_mode ? (unsigned)((n + tg - 1) / tg) : (unsigned)((threads + kBlock - 1) / kBlock);
+    RowMap rm{0, 0, 1, 1, 0};
+    hipLaunchKernelGGL(sig_build_kernel, dim3(blocks), dim3(kBlock), 0, c->stream, aux, n, c->m, r, nb, n_pad, sQ, sT, sP, sG,
+                       0, (const double*)nullptr, 0.0, 0, rm, (u64*)nullptr, (int*)nullptr, (PassCounters*)nullptr, (int*)nullptr, 0, 0,
+                       (u64*)nullptr, 0, 16, (PassCounters*)nullptr, tile_mode ? tg : 0);
+    return hipGetLastError();
+}
+
+hipError_t ensure_sig_bufs(int n, int nb, DevBuf<uint32_t>& sQ, DevBuf<uint32_t>& sT, DevBuf<uint32_t>& sP, DevBuf<uint32_t>& sG) {
+    const size_t n_pad = (((size_t)n + kWave - 1) / kWave) * kWave, half = (size_t)(nb + 1) / 2;
+    hipError_t e;
+    if ((e = sQ.ensure(std::max<size_t>(1, (size_t)n * nb))) != hipSuccess) return e;
+    if ((e = sT.ensure(std::max<size_t>(1, n_pad * nb))) != hipSuccess) return e;
+    if ((e = sP.ensure(std::max<size_t>(1, n_pad * half))) != hipSuccess) return e;
+    return sG.ensure((n_pad + 2) * half);
+}
+
+hipError_t launch_query_hist(int khi, hipStream_t st, const uint32_t* bs_q, const uint8_t* gmax_q, const uint32_t* bs_d, const uint8_t* gmax_d,
+                             int n_q, const selhip_int2_t* list, const u64* count, u64 cap, uint32_t* counts, u64 off, u64 window) {
+    const unsigned blocks = grid_for(std::min<u64>(cap, window), kWavesPerBlock, 4096);
+#define SELHIP_QH_LAUNCH(NB) hipLaunchKernelGGL((query_union_hist_kernel<NB>), dim3(blocks), dim3(kBlock), 0, st, bs_q, gmax_q, bs_d, gmax_d, n_q, \
+                                                list, count, cap, counts, off, window)
+    if (khi <= 16)      SELHIP_QH_LAUNCH(4);
+    else if (khi <= 32) SELHIP_QH_LAUNCH(5);
+    else                SELHIP_QH_LAUNCH(6);
+#undef SELHIP_QH_LAUNCH
+    return hipGetLastError();
+}
+
+// the largest query tile the stream kernel stages (qt rows of m u64 in at most 32 KiB of LDS); 0 = m too large for it
+int query_stream_tile(int m) {
+    const int qt = 32768 / (m * 8);
+    return qt < 1 ? 0 : std::min(qt, kQStreamMaxQ);
+}
+
+// one query pass on the context's stream; counters land in q.h_pc (the caller waits)
+int enqueue_query_pass(selhip_ctx* c, bool use_sig, double tau) {
+    auto& q = c->q;
+    const int n_q = (int)q.n, n_d = (int)c->n;
+    c->dominant_timer = c->timed_kernel == 1 ? T_HIST : (use_sig ? T_JOIN : T_STAGE1);
+    if (c->timing) c->timed_passes += 1;
+    TimerScope total(c, T_TOTAL);
+    // counter set of this pass (the other one is cleared by this pass's first kernel for the next pass)
+    if (q.pc_dirty) HIPCHK(&c->err, hipMemsetAsync(q.pc.p, 0, 2 * sizeof(PassCounters), c->stream));
+    PassCounters* const pc = q.pc.p + q.pc_flip;
+    PassCounters* const pc_next = q.pc.p + (q.pc_flip ^ 1);
+    q.pc_flip ^= 1;
+    q.pc_dirty = true;                                  // until the pass is enqueued in full
+    const int r = c->n_rows, nb = c->n_bands;
+    const int use_cb = c->mode == SELHIP_MODE_CB_SMH ? 1 : 0;
+    const unsigned win_blocks = (unsigned)((std::max(n_q, n_d) + kBlock - 1) / kBlock);
+    if (use_sig) {
+        // windows + the queries' band signatures in one launch
+        TimerScope t(c, T_PREP);
+        HIPCHK(&c->err, ensure_sig_bufs(n_q, nb, q.sigQ, q.sigT, q.sigP, q.sigG));
+        const bool tile_mode = is_pow2(c->m) && is_pow2(nb) && nb <= 128 && r >= 2 && r <= 32 && c->m >= 4 && c->sig_tile;
+        const long long threads = r <= kWave ? (long long)n_q * c->m : (long long)n_q * nb;
+        const int tg = c->sig_tile_g;
+        const unsigned sig_blocks = tile_mode ? (unsigned)((n_q + tg - 1) / tg) : (unsigned)((threads + kBlock - 1) / kBlock);
+        hipLaunchKernelGGL(query_prep_sig_kernel, dim3(win_blocks + sig_blocks), dim3(kBlock), 0, c->stream, (int)win_blocks,
+                           q.d_cards, n_q, c->d_cards, n_d, tau, use_cb, q.ecard.p, q.lo.p, q.hi.p, pc, pc_next,
+                           q.d_aux, c->m, r, nb, ((n_q + kWave - 1) / kWave) * kWave, q.sigQ.p, q.sigT.p, q.sigP.p, q.sigG.p, tile_mode ? tg : 0);
+        HIPCHK(&c->err, hipGetLastError());
+    } else {
+        TimerScope t(c, T_PREP);
+        hipLaunchKernelGGL(query_windows_kernel, dim3(win_blocks), dim3(kBlock), 0, c->stream,
+                           q.d_cards, n_q, c->d_cards, n_d, tau, use_cb, q.ecard.p, q.lo.p, q.hi.p, pc, pc_next);
+        HIPCHK(&c->err, hipGetLastError());
+    }
+    {
+        TimerScope t(c, T_PREP);
+        // D's bit planes for stage 2a, when the all-pairs path keeps none
+        if (!use_bitslices(c) && q.db_bs_gen != c->db_gen) {
+            HIPCHK(&c->err, q.db_bs.ensure((size_t)n_d * kBsGenomeDwords));
+            HIPCHK(&c->err, q.db_gmax.ensure((size_t)n_d));
+            HIPCHK(&c->err, q.bs_max.ensure(1));
+            const int rc = build_bitslices(&c->err, c->stream, c->d_hll, n_d, q.db_bs.p, q.db_gmax.p, q.bs_max.p, &q.db_khi);
+            if (rc) return rc;
+            q.db_bs_gen = c->db_gen;
+        }
+    }
+    const uint32_t* const bs_d = use_bitslices(c) ? c->hll_bs.p : q.db_bs.p;
+    const uint8_t* const gmax_d = use_bitslices(c) ? c->hll_gmax.p : q.db_gmax.p;
+    const int khi = std::max(q.khi, use_bitslices(c) ? c->hll_khi : q.db_khi);
+    if (use_sig) {
+        const long long key = ((long long)r << 40) | ((long long)nb << 24) | ((c->db_gen & 0xFFFFF) << 1) | 1;
+        if (q.db_sig_key != key) {
+            // D's signatures depend on D and the band shape only: kept for the shape used last (a pass with another shape replaces them)
+            TimerScope t(c, T_SIGBUILD);
+            HIPCHK(&c->err, ensure_sig_bufs(n_d, nb, q.db_sigQ, q.db_sigT, q.db_sigP, q.db_sigG));
+            HIPCHK(&c->err, launch_sig_rows(c, c->d_aux, n_d, r, nb, q.db_sigQ.p, q.db_sigT.p, q.db_sigP.p, q.db_sigG.p));
+            q.db_sig_key = key;
+            q.db_sig_builds += 1;
+        }
+        {
+            TimerScope t(c, T_JOIN);
+            const int n_pad = ((n_d + kWave - 1) / kWave) * kWave;
+            const int qt = c->query_join_tile;
+            const int col_blocks = (n_d + kBlock - 1) / kBlock, tiles = (n_q + qt - 1) / qt;
+            const long long blocks = (long long)tiles * col_blocks;
+            if (blocks > 0x7FFFFFFFll) { set_err(&c->err, "query pass too large for one launch"); return SELHIP_E_BADARG; }
+#define SELHIP_QJ_LAUNCH(QT) hipLaunchKernelGGL((query_sig_join_kernel<QT>), dim3((unsigned)blocks), dim3(kBlock), 0, c->stream, q.sigQ.p, \
+                                                q.db_sigT.p, n_q, n_d, n_pad, nb, q.lo.p, q.hi.p, col_blocks, q.cand.p, (u64)q.cand.cap, pc)
+            if (qt == 16) SELHIP_QJ_LAUNCH(16);
+            else          SELHIP_QJ_LAUNCH(32);
+#undef SELHIP_QJ_LAUNCH
+            HIPCHK(&c->err, hipGetLastError());
+        }
+        {
+            TimerScope t(c, T_VERIFY);
+            hipLaunchKernelGGL(query_verify_kernel, dim3(grid_for((u64)q.cand.cap, kBlock, 2048)), dim3(kBlock), 0, c->stream,
+                               q.d_aux, c->d_aux, c->m, r, nb, n_q, q.sigQ.p, q.db_sigQ.p, q.cand.p, &pc->n_pre, (u64)q.cand.cap,
+                               q.surv.p, (u64)q.surv.cap, pc);
+            HIPCHK(&c->err, hipGetLastError());
+        }
+    } else {
+        TimerScope t(c, T_STAGE1);
+        const int qt = query_stream_tile(c->m);
+        const int col_blocks = (n_d + kQStreamRows - 1) / kQStreamRows, tiles = (n_q + qt - 1) / qt;
+        const long long blocks = (long long)tiles * col_blocks;
+        if (blocks > 0x7FFFFFFFll) { set_err(&c->err, "query pass too large for one launch"); return SELHIP_E_BADARG; }
+        hipLaunchKernelGGL(query_stream_kernel, dim3((unsigned)blocks), dim3(kBlock), (size_t)qt * c->m * 8, c->stream, q.d_aux, c->d_aux, n_q, n_d,
+                           c->m, r, nb, qt, q.lo.p, q.hi.p, col_blocks, q.surv.p, (u64)q.surv.cap, pc);
+        HIPCHK(&c->err, hipGetLastError());
+    }
+    // stage 2 on the combined index space: the all-pairs estimator / select kernel, unchanged
+    const u64 window = (u64)q.counts.cap / 64;
+    for (u64 off = 0; off < (u64)q.surv.cap; off += window) {
+        {
+            TimerScope t(c, T_HIST);
+            HIPCHK(&c->err, launch_query_hist(khi, c->stream, q.bs.p, q.gmax.p, bs_d, gmax_d, n_q, q.surv.p, &pc->n_survivors, (u64)q.surv.cap,
+                                              q.counts.p, off, window));
+        }
+        TimerScope t(c, T_SELECT);
+        HIPCHK(&c->err, launch_select<1>(c->fp_mode == SELHIP_FP_FMA, c->stream, grid_for(std::min<u64>(window, (u64)q.surv.cap), kWave, 4096),
+                                         q.counts.p, &pc->n_survivors, 0, (u64)q.surv.cap, c->p, nullptr, q.surv.p, q.ecard.p, tau,
+                                         c->results.p, (u64)c->results.cap, pc, nullptr, nullptr, off, window));
+    }
+    hipLaunchKernelGGL(query_result_fixup_kernel, dim3(grid_for((u64)c->results.cap, kBlock, 1024)), dim3(kBlock), 0, c->stream,
+                       c->results.p, &pc->n_results, (u64)c->results.cap, n_q);
+    HIPCHK(&c->err, hipGetLastError());
+    HIPCHK(&c->err, hipMemcpyAsync(q.h_pc, pc, sizeof(PassCounters), hipMemcpyDeviceToHost, c->stream));
+    q.pc_dirty = false;
+    return SELHIP_OK;
+}
+
+int ensure_query_scratch(selhip_ctx* c, size_t list_cap, size_t res_cap) {
+    auto& q = c->q;
+    HIPCHK(&c->err, q.lo.ensure((size_t)std::max<int64_t>(1, q.n)));
+    HIPCHK(&c->err, q.hi.ensure((size_t)std::max<int64_t>(1, q.n)));
+    HIPCHK(&c->err, q.ecard.ensure((size_t)std::max<int64_t>(1, q.n + c->n)));
+    if (!q.pc.p) { HIPCHK(&c->err, q.pc.ensure(2)); q.pc_dirty = true; }
+    if (!q.h_pc) HIPCHK(&c->err, hipHostMalloc((void**)&q.h_pc, sizeof(PassCounters), hipHostMallocDefault));
+    HIPCHK(&c->err, q.cand.ensure(list_cap));
+    HIPCHK(&c->err, q.surv.ensure(list_cap));
+    HIPCHK(&c->err, q.counts.ensure(std::min<size_t>(q.surv.cap, (size_t)1 << 22) * 64));
+    HIPCHK(&c->err, c->results.ensure(res_cap));
+    return SELHIP_OK;
+}
+
+}  // namespace

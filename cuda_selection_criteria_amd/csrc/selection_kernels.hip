@@ -18,6 +18,8 @@
 //   kernel_pairlist.cuh explicit pair lists (drop-in launch_kernel_* path, test building blocks)
 //   kernel_sketch.cuh   synth_kernel, sketch_build_kernel (build_sketch on the GPU), permute_rows
 //   kernel_small.cuh    small_pass_kernel: the whole pass of a set of <= 2 048 genomes in one cooperative launch
+//   kernel_query.cuh    query passes (a query set against the database): CB windows, rectangular signature join, verification,
+//                       literal stream kernel for any band shape, stage 2a on two sets' bit planes
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (see csrc/Makefile).
 #include <hip/hip_runtime.h>
@@ -51,9 +53,12 @@
 #include "kernel_pairlist.cuh"
 #include "kernel_sketch.cuh"
 #include "kernel_small.cuh"
+#include "kernel_query.cuh"
 
 #include "host_context.hpp"      // struct selhip_ctx, device buffers, timers, helpers
 #include "host_pass.hpp"         // pass scheduler: dispatch of every stage, chunk lanes, scratch sizing
+#include "host_query.hpp"        // query passes: Q x D (windows, signature join or stream, verification, stage 2)
 #include "abi_context.inc"       // C ABI: context (create, upload / attach, run, results, timing)
+#include "abi_query.inc"         // C ABI: query passes (upload / attach queries, run_queries)
 #include "abi_blocks.inc"        // C ABI: building blocks, synthetic sketches, sketch construction, memory helpers
 #include "abi_compat.inc"        // C ABI: drop-in launch_kernel_smh / launch_kernel_CBsmh

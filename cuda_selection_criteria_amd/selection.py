@@ -183,6 +183,42 @@ class Selector:
         self._keep = (hll_t, aux_t, cards_t)
         self.n, self.m = n, m
 
+    def upload_queries(self, hll: np.ndarray, aux: np.ndarray, cards: Optional[np.ndarray] = None):
+        """query sketches (ascending cardinality, the database's m, p = 14) for run_queries; cards None = computed on the device"""
+        hll = np.ascontiguousarray(hll, dtype=np.uint8)
+        aux = np.ascontiguousarray(aux, dtype=np.uint64)
+        n_q = aux.shape[0]
+        assert aux.shape == (n_q, self.m) and hll.shape == (n_q, 1 << 14), (hll.shape, aux.shape, self.m)
+        cp = None
+        if cards is not None:
+            cards = np.ascontiguousarray(cards, dtype=np.float64)
+            assert cards.shape == (n_q,)
+            cp = cards.ctypes.data
+        check(self._lib.selhip_ctx_upload_queries(self._ctx, hll.ctypes.data if n_q else None, aux.ctypes.data if n_q else None,
+                                                  cp, n_q), self._ctx)
+        self.n_q = n_q
+
+    def attach_queries(self, hll_t, aux_t, cards_t=None):
+        """torch CUDA tensors of the queries (layout as attach); the caller keeps them alive and unchanged"""
+        n_q = aux_t.shape[0]
+        assert hll_t.is_cuda and aux_t.is_cuda and hll_t.is_contiguous() and aux_t.is_contiguous()
+        assert tuple(hll_t.shape) == (n_q, 1 << 14) and tuple(aux_t.shape) == (n_q, self.m) and aux_t.element_size() == 8
+        cp = None
+        if cards_t is not None:
+            assert cards_t.is_cuda and cards_t.is_contiguous() and cards_t.element_size() == 8 and cards_t.shape[0] == n_q
+            cp = cards_t.data_ptr()
+        check(self._lib.selhip_ctx_attach_queries(self._ctx, hll_t.data_ptr(), aux_t.data_ptr(), cp, n_q), self._ctx)
+        self._keep_q = (hll_t, aux_t, cards_t)
+        self.n_q = n_q
+
+    def run_queries(self, tau: float, mode: int = MODE_CB_SMH, n_rows: Optional[int] = None, n_bands: Optional[int] = None,
+                    algo: int = ALGO_AUTO, fetch: bool = True):
+        """one query pass (queries x database): records {i = query rank, k = database rank, jaccard} sorted by (i, k)"""
+        if n_rows is None or n_bands is None:
+            n_rows, n_bands = banding(self.m, tau) if self.m else (1, 1)
+        check(self._lib.selhip_ctx_run_queries(self._ctx, mode, algo, np.float32(tau), n_rows, n_bands), self._ctx)
+        return self.fetch() if fetch else None
+
     def upload_aux_hll(self, aux_hll: np.ndarray, p_aux: int):
         """auxiliary HLL sketches (.hll_<p> files) for the hll_a / hll_an criteria, rank order"""
         aux_hll = np.ascontiguousarray(aux_hll, dtype=np.uint8)
@@ -382,3 +418,26 @@ def ooc_select(hll: np.ndarray, aux: np.ndarray, cards: np.ndarray, tau: float, 
             continue
         check(rc)
         return out[:cnt.value], {"evaluated": st[0], "survivors": st[1], "selected": st[2], "candidates": st[3]}
+
+
+def query_from_filelists(query_list: str, db_list: str, tau: float, aux_bytes: int, mode: int = MODE_CB_SMH, fp_mode: int = FP_FMA,
+                         device: int = 0, algo: int = ALGO_AUTO) -> str:
+    """Query-vs-database selection (criterion smh_a): both lists are loaded and sorted by cardinality (load_dataset); returns one line
+    'query_path db_path J' per selected pair, in (query rank, database rank) order, J formatted as selection.cpp prints it."""
+    m = aux_bytes // 8
+    qs = load_dataset(query_list, m, 0, fp_mode)
+    db = load_dataset(db_list, m, 0, fp_mode)
+    n_rows, n_bands = banding(m, tau)
+    with Selector(device, fp_mode) as sel:
+        sel.upload(db.hll, db.aux, db.cards)
+        sel.upload_queries(qs.hll, qs.aux, qs.cards)
+        pairs = sel.run_queries(tau, mode, n_rows, n_bands, algo)
+    h = host_lib()
+    buf = C.create_string_buffer(16384)
+    out = []
+    for rec in pairs:
+        w = h.selhost_format_line(qs.names[rec["i"]].encode(), db.names[rec["k"]].encode(), float(rec["jaccard"]), buf, len(buf))
+        if w < 0:
+            raise RuntimeError("line too long")
+        out.append(buf.raw[:w].decode())
+    return "".join(out)

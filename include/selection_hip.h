@@ -181,7 +181,8 @@ int selhip_ctx_set_candidate_begin(selhip_ctx* ctx, int64_t k_min);
  * knobs, listed at selhip_ctx_set_param in csrc/selection_kernels.hip.) */
 int selhip_ctx_set_param(selhip_ctx* ctx, const char* name, int value);
 /* what the context decided (read-only): "hll_khi" (largest p = 14 register value + 1; 0 = no bit planes), "hist_bitplanes",
- * "label_order", "join_tile_rows", "chunks" (chunk lanes of the last pass), "small_pass_used" (the last pass was the one-launch small pass) */
+ * "label_order", "join_tile_rows", "chunks" (chunk lanes of the last pass), "small_pass_used" (the last pass was the one-launch small pass),
+ * "query_db_sig_builds" (builds of the database's band signatures by query passes since the database was loaded, section 2b) */
 int selhip_ctx_get_param(const selhip_ctx* ctx, const char* name, int* value);
 /* Stage 2 grouping (default on): the pairs that reach the HLL-14 stage are bucketed by query row (counting sort) so
  * that waves running side by side on one XCD share their query row in L2.  0 = off (same kernel, list as produced). */
@@ -265,7 +266,30 @@ double selhip_ctx_kernel_launches(const selhip_ctx* ctx, const char* name);
 int    selhip_ctx_timing(selhip_ctx* ctx, int enable);
 
 /* ---------------------------------------------------------------------------------------------------
- * 2b. Multi-GPU entry taking a device list: ONE process, one host thread + one context per
+ * 2b. Query passes: a query set Q against the context's sketches (the database D).  Both sets are in ascending-cardinality
+ *     order, with the same m and p = 14.  A pass selects the pairs (q, d) -- q a query rank, d a database rank -- with
+ *     e_hi != 0, [CB mode] (double)e_lo / (double)e_hi >= (double)tau_f, smh_a and J >= tau_f (e_lo / e_hi = the smaller /
+ *     larger of the two truncated cardinalities; same estimator and FP flavour as selhip_ctx_run).  Every term is symmetric,
+ *     so the result is exactly the cross pairs (one member in Q, one in D) of selhip_ctx_run over Q u D, J bit for bit.
+ *     Records {i = query rank, k = database rank, jaccard} are read with selhip_ctx_result_count / _fetch (sorted by (i,k)),
+ *     selhip_ctx_stats (evaluated = cross pairs inside the CB windows with e_hi != 0) and selhip_ctx_last_attempts.
+ *     Criterion smh_a only (SELHIP_E_BADARG otherwise).  algo: SELHIP_ALGO_SIG (power-of-two rows, 8..128 bands: band
+ *     signatures of a query tile in LDS against the database's, which are kept for the band shape used last -- a pass with
+ *     the same shape against the same database does not build them again, one with another shape replaces them;
+ *     get_param "query_db_sig_builds" counts the builds since the database was loaded), SELHIP_ALGO_STREAM (any band shape,
+ *     m <= 4096: full bucket compare), SELHIP_ALGO_AUTO (SIG where it applies, else STREAM); SELHIP_ALGO_HASHJOIN is refused.
+ *     Uploading / attaching the database drops the queries.  Query and all-pairs passes do not affect each other's results.
+ *     After a query pass selhip_ctx_copy_results_framed / _framed_async return SELHIP_E_STATE (use selhip_ctx_copy_results).
+ * --------------------------------------------------------------------------------------------------- */
+/* h_cards / d_cards may be NULL (computed on the device, as selhip_ctx_upload does); n_q == 0 is legal (0 results).  Cards that are
+ * not ascending: SELHIP_E_BADARG (host cards here, device cards at the run).  attach: device pointers owned by the caller. */
+int selhip_ctx_upload_queries(selhip_ctx* ctx, const uint8_t* h_hll, const uint64_t* h_aux, const double* h_cards, int64_t n_q);
+int selhip_ctx_attach_queries(selhip_ctx* ctx, const uint8_t* d_hll, const uint64_t* d_aux, const double* d_cards, int64_t n_q);
+/* One query pass, synchronous like selhip_ctx_run; SELHIP_E_STATE before any queries are loaded. */
+int selhip_ctx_run_queries(selhip_ctx* ctx, int mode, int algo, float tau_f, int n_rows, int n_bands);
+
+/* ---------------------------------------------------------------------------------------------------
+ * 2c. Multi-GPU entry taking a device list: ONE process, one host thread + one context per
  *     device; the pair space is cut into equal-pair row ranges, every device gets a full replica of the (host)
  *     sketches, and the selected-pair lists are gathered -- over RCCL/xGMI (ncclAllGather of framed record buffers on
  *     communicators from ncclCommInitAll; librccl is dlopen'ed on first use) or through the host.
@@ -284,7 +308,7 @@ int selhip_multi_select(const int* devices, int n_devices,
                         int gather, selhip_pair_t* h_out, int64_t cap, int64_t* count_out, int64_t stats_out[4]);
 
 /* ---------------------------------------------------------------------------------------------------
- * 2c. Out-of-core driver: the sketches stay in HOST memory (all n genomes, ascending
+ * 2d. Out-of-core driver: the sketches stay in HOST memory (all n genomes, ascending
  *     cardinality, h_cards required) and only `block_genomes` of them per block are resident on the device at a time.
  *     The pair space is tiled into block pairs (I, J), I <= J: a diagonal block is an ordinary pass over I; an
  *     off-diagonal one uploads I followed by J and runs rows I x candidates J (selhip_ctx_set_candidate_begin), so every
