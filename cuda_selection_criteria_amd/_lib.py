@@ -92,6 +92,8 @@ HIP_SYMBOLS = {
     "selhip_ctx_upload_queries": (_i, [_vp, _vp, _vp, _vp, _i64]),
     "selhip_ctx_attach_queries": (_i, [_vp, _vp, _vp, _vp, _i64]),
     "selhip_ctx_run_queries": (_i, [_vp, _i, _i, C.c_float, _i, _i]),
+    "selhip_ctx_upload_queries_aux_hll": (_i, [_vp, _vp, _i]),
+    "selhip_ctx_attach_queries_aux_hll": (_i, [_vp, _vp, _i]),
     "selhip_smh_a_pairs": (_i, [_vp, _i, _i, _i, _vp, _i64, _vp, _vp]),
     "selhip_hll_union_hist": (_i, [_vp, _i, _vp, _i64, _vp, _vp]),
     "selhip_hll_bitslice": (_i, [_vp, _i64, _vp, _vp, _vp, _vp]),

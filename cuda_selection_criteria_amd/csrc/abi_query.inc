@@ -1,4 +1,5 @@
-// abi_query.inc -- the C ABI of the query passes (include/selection_hip.h section 2b): upload / attach a query set, run a query pass.
+// abi_query.inc -- the C ABI of the query passes (include/selection_hip.h section 2b): upload / attach a query set and its auxiliary
+// HLL sketches, run a query pass (any criterion).
 // Included by selection_kernels.hip.  The results go through selhip_ctx_result_count / _fetch / _stats / _last_attempts.
 
 extern "C" {
@@ -51,6 +52,7 @@ int selhip_ctx_upload_queries(selhip_ctx* c, const uint8_t* h_hll, const uint64_
     if (n_q > 0 && (!h_hll || !h_aux)) { set_err(&c->err, "null query sketch pointer"); return SELHIP_E_BADARG; }
     auto& q = c->q;
     q.n = -1;
+    q.d_aux_hll = nullptr; q.p_aux = 0;                 // a new query set never meets the previous one's auxiliary sketches
     if (n_q > 0) {
         HIPCHK(&c->err, q.own_hll.ensure((size_t)n_q << 14));
         HIPCHK(&c->err, q.own_aux.ensure((size_t)n_q * c->m));
@@ -72,11 +74,48 @@ int selhip_ctx_attach_queries(selhip_ctx* c, const uint8_t* d_hll, const uint64_
     if (n_q > 0 && (!d_hll || !d_aux)) { set_err(&c->err, "null query sketch pointer"); return SELHIP_E_BADARG; }
     if (((uintptr_t)d_hll & 15) || ((uintptr_t)d_aux & 15)) { set_err(&c->err, "query sketch pointers must be 16-byte aligned"); return SELHIP_E_BADARG; }
     auto& q = c->q;
+    q.d_aux_hll = nullptr; q.p_aux = 0;
     q.d_hll = d_hll; q.d_aux = (const u64*)d_aux;
     q.n = n_q;
     rc = after_queries(c, d_cards, false);
     if (rc) q.n = -1;
     return rc;
+}
+
+static int check_query_aux(selhip_ctx* c, const void* p, int p_aux) {
+    if (c->q.n < 0) { set_err(&c->err, "upload or attach the queries before their auxiliary HLL sketches"); return SELHIP_E_STATE; }
+    if (p_aux < 4 || p_aux > kMaxAuxP) { set_err(&c->err, "p_aux %d out of range [4,%d]", p_aux, kMaxAuxP); return SELHIP_E_BADARG; }
+    if (!p && c->q.n > 0) { set_err(&c->err, "null query auxiliary HLL pointer"); return SELHIP_E_BADARG; }
+    return SELHIP_OK;
+}
+
+int selhip_ctx_upload_queries_aux_hll(selhip_ctx* c, const uint8_t* h_aux_hll, int p_aux) {
+    if (!c) return SELHIP_E_BADARG;
+    int rc = check_query_aux(c, h_aux_hll, p_aux);
+    if (rc) return rc;
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    auto& q = c->q;
+    q.d_aux_hll = nullptr; q.p_aux = 0;
+    const size_t bytes = (size_t)q.n << p_aux;
+    HIPCHK(&c->err, q.own_aux_hll.ensure(bytes ? bytes : 1));
+    if (bytes) HIPCHK(&c->err, hipMemcpyAsync(q.own_aux_hll.p, h_aux_hll, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    q.d_aux_hll = q.own_aux_hll.p; q.p_aux = p_aux;
+    return SELHIP_OK;
+}
+
+int selhip_ctx_attach_queries_aux_hll(selhip_ctx* c, const uint8_t* d_aux_hll, int p_aux) {
+    if (!c) return SELHIP_E_BADARG;
+    int rc = check_query_aux(c, d_aux_hll, p_aux);
+    if (rc) return rc;
+    if ((uintptr_t)d_aux_hll & 15) { set_err(&c->err, "query auxiliary HLL pointer must be 16-byte aligned"); return SELHIP_E_BADARG; }
+    auto& q = c->q;
+    if (!d_aux_hll) {                                   // (n_q == 0: nothing to point at)
+        HIPCHK(&c->err, q.own_aux_hll.ensure(1));
+        d_aux_hll = q.own_aux_hll.p;
+    }
+    q.d_aux_hll = d_aux_hll; q.p_aux = p_aux;
+    return SELHIP_OK;
 }
 
 int selhip_ctx_run_queries(selhip_ctx* c, int mode, int algo, float tau_f, int n_rows, int n_bands) {
@@ -85,28 +124,45 @@ int selhip_ctx_run_queries(selhip_ctx* c, int mode, int algo, float tau_f, int n
     if (q.n < 0) { set_err(&c->err, "run_queries before upload / attach of the queries"); return SELHIP_E_STATE; }
     if (c->pending) { set_err(&c->err, "a pass is still pending (selhip_ctx_finish)"); return SELHIP_E_STATE; }
     if (mode != SELHIP_MODE_SMH && mode != SELHIP_MODE_CB_SMH) { set_err(&c->err, "bad mode %d", mode); return SELHIP_E_BADARG; }
-    if (c->criterion != SELHIP_CRIT_SMH_A) { set_err(&c->err, "query passes support the criterion smh_a only (criterion %d is set)", c->criterion); return SELHIP_E_BADARG; }
-    if (algo == SELHIP_ALGO_HASHJOIN) { set_err(&c->err, "query passes have no ALGO_HASHJOIN; use AUTO, SIG or STREAM"); return SELHIP_E_BADARG; }
-    if (algo != SELHIP_ALGO_AUTO && algo != SELHIP_ALGO_STREAM && algo != SELHIP_ALGO_SIG) { set_err(&c->err, "bad algo %d", algo); return SELHIP_E_BADARG; }
-    if (n_rows <= 0 || n_bands <= 0 || (long long)n_rows * n_bands != c->m) {
-        set_err(&c->err, "n_rows*n_bands (%d*%d) != m (%d)", n_rows, n_bands, c->m);
-        return SELHIP_E_BADARG;
+    if (c->criterion != SELHIP_CRIT_SMH_A) {
+        // the auxiliary HLL sketches of both sets, with one precision
+        if ((c->n && !c->d_aux_hll) || (q.n && !q.d_aux_hll)) {
+            set_err(&c->err, "criterion %d needs the auxiliary HLL sketches of the database (selhip_ctx_upload_aux_hll) and of the queries "
+                             "(selhip_ctx_upload_queries_aux_hll)", c->criterion);
+            return SELHIP_E_STATE;
+        }
+        if (c->d_aux_hll && q.d_aux_hll && c->p_aux != q.p_aux) {
+            set_err(&c->err, "auxiliary HLL precision of the queries (%d) != that of the database (%d)", q.p_aux, c->p_aux);
+            return SELHIP_E_BADARG;
+        }
     }
-    const bool sig_ok = sig_supported(c->m, n_rows, n_bands);
-    if (algo == SELHIP_ALGO_SIG && !sig_ok) {
-        set_err(&c->err, "ALGO_SIG needs power-of-two rows and 8..128 bands (got %d x %d)", n_rows, n_bands);
-        return SELHIP_E_BADARG;
+    const bool smh = query_smh_stage(c);
+    if (algo != SELHIP_ALGO_AUTO && algo != SELHIP_ALGO_STREAM && algo != SELHIP_ALGO_SIG && algo != SELHIP_ALGO_HASHJOIN) { set_err(&c->err, "bad algo %d", algo); return SELHIP_E_BADARG; }
+    bool use_sig = false;
+    if (smh) {
+        // (hll_a / hll_an alone read neither n_rows / n_bands nor algo, as in selhip_ctx_run_async)
+        if (algo == SELHIP_ALGO_HASHJOIN) { set_err(&c->err, "query passes have no ALGO_HASHJOIN; use AUTO, SIG or STREAM"); return SELHIP_E_BADARG; }
+        if (n_rows <= 0 || n_bands <= 0 || (long long)n_rows * n_bands != c->m) {
+            set_err(&c->err, "n_rows*n_bands (%d*%d) != m (%d)", n_rows, n_bands, c->m);
+            return SELHIP_E_BADARG;
+        }
+        const bool sig_ok = sig_supported(c->m, n_rows, n_bands);
+        if (algo == SELHIP_ALGO_SIG && !sig_ok) {
+            set_err(&c->err, "ALGO_SIG needs power-of-two rows and 8..128 bands (got %d x %d)", n_rows, n_bands);
+            return SELHIP_E_BADARG;
+        }
+        use_sig = algo != SELHIP_ALGO_STREAM && sig_ok;
+        if (!use_sig && query_stream_tile(c->m) == 0) { set_err(&c->err, "ALGO_STREAM of a query pass holds m <= 4096 buckets (m = %d)", c->m); return SELHIP_E_BADARG; }
     }
-    const bool use_sig = algo != SELHIP_ALGO_STREAM && sig_ok;
-    if (!use_sig && query_stream_tile(c->m) == 0) { set_err(&c->err, "ALGO_STREAM of a query pass holds m <= 4096 buckets (m = %d)", c->m); return SELHIP_E_BADARG; }
     HIPCHK(&c->err, hipSetDevice(c->device));
     c->mode = mode; c->algo = algo; c->tau_f = tau_f; c->n_rows = n_rows; c->n_bands = n_bands;
     c->have_run = false;
     std::memset(&c->last, 0, sizeof c->last);
     c->last_was_query = true;
     if (q.n == 0 || c->n == 0) { c->have_run = true; c->last_attempts = 1; return SELHIP_OK; }
-    size_t cap = std::max<size_t>(q.surv.cap, std::max<size_t>((size_t)1 << 16, (size_t)q.n * 16));
-    if (c->init_cap > 0) cap = std::max<size_t>(q.surv.cap, (size_t)c->init_cap);       // test hook: start small, grow on overflow
+    const size_t have = smh ? q.surv.cap : q.fin.cap;
+    size_t cap = std::max<size_t>(have, std::max<size_t>((size_t)1 << 16, (size_t)q.n * 16));
+    if (c->init_cap > 0) cap = std::max<size_t>(have, (size_t)c->init_cap);             // test hook: start small, grow on overflow
     size_t res_cap = std::max<size_t>(c->results.cap, cap);
     const double tau = (double)tau_f;                 // float threshold widened, selection.cpp:81,164
     for (int attempt = 0; attempt < 8; ++attempt) {
@@ -117,9 +173,12 @@ int selhip_ctx_run_queries(selhip_ctx* c, int mode, int algo, float tau_f, int n
         const PassCounters pc = *q.h_pc;
         if (pc.unsorted) { set_err(&c->err, "database or query cards are not in ascending order"); return SELHIP_E_BADARG; }
         bool grow = false;
-        // (n_pre: the join's list; n_survivors: the survivor list)
-        const u64 worst = std::max(pc.n_pre, pc.n_survivors);
-        if (worst > q.surv.cap || worst > q.cand.cap) { cap = std::max(cap, (size_t)(worst + worst / 8 + 1024)); grow = true; }
+        // (n_pre: the join's list; n_survivors: the survivor list; n_final: what passed the auxiliary criterion)
+        const u64 worst = std::max(std::max(pc.n_pre, pc.n_survivors), c->criterion != SELHIP_CRIT_SMH_A ? pc.n_final : 0);
+        if ((smh && (worst > q.surv.cap || worst > q.cand.cap)) || (c->criterion != SELHIP_CRIT_SMH_A && worst > q.fin.cap)) {
+            cap = std::max(cap, (size_t)(worst + worst / 8 + 1024));
+            grow = true;
+        }
         if (pc.n_results > c->results.cap) { res_cap = (size_t)(pc.n_results + pc.n_results / 8 + 1024); grow = true; }
         if (!grow) {
             c->last = pc; c->have_run = true; c->last_attempts = attempt + 1; c->last_was_query = true;

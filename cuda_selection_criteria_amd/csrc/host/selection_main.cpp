@@ -21,10 +21,12 @@
 //   -r <file>   no selection: print the text form of a result file written with -o (needs no GPU)
 //   -q <file>   query-vs-database selection: -q lists the query genomes, -l the database; prints "query_path db_path J" per
 //               selected pair (one member in each list) in (query rank, database rank) order (selhip_ctx_run_queries; criterion
-//               smh_a, one device -- not combinable with -g, -B, -o, -r or -c hll_a / hll_an)
+//               smh_a, hll_a or hll_an -- for the last two the .hll_<p> files of both lists are read; one device -- not combinable
+//               with -g, -B, -o or -r)
 //   -x          usage
 #include <unistd.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -35,37 +37,55 @@
 #include "../../../include/selection_hip.h"
 #include "../../../include/selection_host.h"
 
-// -q: the query list against the database list (-l), both loaded and sorted by cardinality; text on stdout
-static int run_queries(const std::string& query_file, const std::string& db_file, float threshold, int aux_bytes, int mode, int algo,
-                       int fp_mode, int threads) {
-    const unsigned m = (unsigned)aux_bytes / 8;
+// -q: the query list against the database list (-l), both loaded and sorted by cardinality; text on stdout.  criterion: "smh_a"
+// (m = aux_bytes / 8 buckets) or "hll_a" / "hll_an" (auxiliary HLL p = ctz(aux_bytes), as the all-pairs mode)
+static int run_queries(const std::string& query_file, const std::string& db_file, const std::string& criterion, float threshold,
+                       int aux_bytes, int mode, int algo, int fp_mode, int threads) {
+    const bool smh = criterion == "smh_a";
+    const int crit = smh ? SELHIP_CRIT_SMH_A : criterion == "hll_a" ? SELHIP_CRIT_HLL_A : SELHIP_CRIT_HLL_AN;
+    const unsigned m = smh ? (unsigned)aux_bytes / 8 : 0;
+    const unsigned p_aux = smh ? 0 : (unsigned)__builtin_ctz(aux_bytes ? aux_bytes : 1);
+    // (smh_a keeps the messages it always had; an hll criterion names the mode and the criterion)
+    const std::string what = smh ? "" : "selection: -q -c " + criterion + ": ";
     selhost_dataset* db = nullptr;
     selhost_dataset* qs = nullptr;
-    if (selhost_dataset_load(&db, db_file.c_str(), m, 0, fp_mode, threads)) { std::cerr << selhost_last_error() << "\n"; return 1; }
-    if (selhost_dataset_load(&qs, query_file.c_str(), m, 0, fp_mode, threads)) {
+    if (selhost_dataset_load(&db, db_file.c_str(), m, p_aux, fp_mode, threads)) {
+        if (!smh) std::cerr << what << "cannot read database list '" << db_file << "': ";
+        std::cerr << selhost_last_error() << "\n";
+        return 1;
+    }
+    if (selhost_dataset_load(&qs, query_file.c_str(), m, p_aux, fp_mode, threads)) {
+        if (!smh) std::cerr << what << "cannot read query list '" << query_file << "': ";
         std::cerr << selhost_last_error() << "\n";
         selhost_dataset_free(db);
         return 1;
     }
     int n_rows = 1, n_bands = 1;
-    selhost_banding(m, threshold, SELHOST_BANDING_CPU, &n_rows, &n_bands);
+    if (m) selhost_banding(m, threshold, SELHOST_BANDING_CPU, &n_rows, &n_bands);
+    // hll_a / hll_an do not read SuperMinHash buckets: a one-bucket placeholder keeps the upload calls uniform
+    const int64_t n_db = selhost_dataset_size(db), n_qs = selhost_dataset_size(qs);
+    std::vector<uint64_t> no_smh(m ? 0 : (size_t)std::max<int64_t>(1, std::max(n_db, n_qs)), 0);
     std::vector<selhip_pair_t> pairs;
     selhip_ctx* ctx = nullptr;
     int r = selhip_device_count() > 0 ? selhip_ctx_create(&ctx, 0) : SELHIP_E_NODEVICE;
     if (r) {
-        std::cerr << "selection: no MI355X (gfx950) device available: " << selhip_last_error(nullptr) << "\n";
+        std::cerr << (smh ? "selection: " : what) << "no MI355X (gfx950) device available: " << selhip_last_error(nullptr) << "\n";
         selhost_dataset_free(db); selhost_dataset_free(qs);
         return 3;
     }
     selhip_ctx_set_fp_mode(ctx, fp_mode);
-    r = selhip_ctx_upload(ctx, selhost_dataset_hll(db), selhost_dataset_aux(db), selhost_dataset_cards(db), selhost_dataset_size(db), (int)m, 14);
-    if (!r) r = selhip_ctx_upload_queries(ctx, selhost_dataset_hll(qs), selhost_dataset_aux(qs), selhost_dataset_cards(qs), selhost_dataset_size(qs));
+    r = selhip_ctx_upload(ctx, selhost_dataset_hll(db), m ? selhost_dataset_aux(db) : no_smh.data(), selhost_dataset_cards(db), n_db,
+                          m ? (int)m : 1, 14);
+    if (!r) r = selhip_ctx_upload_queries(ctx, selhost_dataset_hll(qs), m ? selhost_dataset_aux(qs) : no_smh.data(), selhost_dataset_cards(qs), n_qs);
+    if (!r && p_aux) r = selhip_ctx_upload_aux_hll(ctx, selhost_dataset_aux_hll(db), (int)p_aux);
+    if (!r && p_aux) r = selhip_ctx_upload_queries_aux_hll(ctx, selhost_dataset_aux_hll(qs), (int)p_aux);
+    if (!r) r = selhip_ctx_set_criterion(ctx, crit);
     if (!r) r = selhip_ctx_run_queries(ctx, mode, algo, threshold, n_rows, n_bands);
     if (!r) {
         pairs.resize((size_t)selhip_ctx_result_count(ctx));
         r = selhip_ctx_fetch(ctx, pairs.data(), (int64_t)pairs.size());
     }
-    if (r) std::cerr << "selection: " << selhip_last_error(ctx) << "\n";
+    if (r) std::cerr << (smh ? "selection: " : what) << selhip_last_error(ctx) << "\n";
     selhip_ctx_destroy(ctx);
     if (!r) {
         std::string out;
@@ -94,7 +114,7 @@ int main(int argc, char* argv[]) {
     while ((c = getopt(argc, argv, "xl:b:a:h:c:t:g:nA:F:B:o:r:q:")) != -1) {
         switch (c) {
             case 'x': std::cout << "Usage: -l -h -a -b [-c smh_a] [-t threads] [-g gpus] [-n] [-A auto|stream|sig] [-F 0|1] [-B block] [-o file] | -r file\n"
-                                   "       -l db_list -q query_list -h -a [-n] [-A auto|stream|sig] [-F 0|1]   (query-vs-database selection)\n"; return 0;
+                                   "       -l db_list -q query_list -h -a [-c smh_a|hll_a|hll_an] [-n] [-A auto|stream|sig] [-F 0|1]   (query-vs-database selection)\n"; return 0;
             case 'q': query_file = optarg; break;
             case 'B': ooc_block = std::stoll(optarg); break;
             case 'o': out_file = optarg; break;
@@ -114,15 +134,18 @@ int main(int argc, char* argv[]) {
     }
     if (!query_file.empty()) {
         // checked before any file is read or device opened
-        const char* clash = gpus_given ? "-g" : ooc_block != 0 ? "-B" : !out_file.empty() ? "-o" : !dump_file.empty() ? "-r"
-                          : (criterion == "hll_a" || criterion == "hll_an") ? "-c hll_a / hll_an" : criterion != "smh_a" ? "-c" : nullptr;
+        const char* clash = gpus_given ? "-g" : ooc_block != 0 ? "-B" : !out_file.empty() ? "-o" : !dump_file.empty() ? "-r" : nullptr;
         if (clash) {
             std::cerr << "selection: -q (query-vs-database selection) cannot be combined with " << clash
-                      << "; it runs criterion smh_a on one device and prints text\n";
+                      << "; it runs on one device and prints text\n";
+            return 2;
+        }
+        if (criterion != "smh_a" && criterion != "hll_a" && criterion != "hll_an") {
+            std::cerr << "selection: -q -c " << criterion << ": the accepted criteria are hll_a, hll_an and smh_a\n";
             return 2;
         }
         if (list_file.empty()) { std::cerr << "selection: -q needs the database list (-l)\n"; return 2; }
-        return run_queries(query_file, list_file, threshold, aux_bytes, mode, algo, fp_mode, threads);
+        return run_queries(query_file, list_file, criterion, threshold, aux_bytes, mode, algo, fp_mode, threads);
     }
     if (!dump_file.empty()) {
         selhost_results* res = nullptr;

@@ -187,6 +187,10 @@ struct selhip_ctx {
         long long db_bs_gen = -1;
         int db_khi = 0;
         DevBuf<selhip_int2_t> cand, surv;
+        DevBuf<selhip_int2_t> fin;                  // criteria other than smh_a: the pairs that passed hll_a / hll_an (stage 2's list)
+        const uint8_t* d_aux_hll = nullptr;         // Q's auxiliary HLL registers [n][1 << p_aux] (dropped by every upload / attach of Q)
+        DevBuf<uint8_t> own_aux_hll;
+        int p_aux = 0;                              // 0 = none loaded
         DevBuf<uint32_t> counts;
         DevBuf<PassCounters> pc;                    // two counter sets: pass k uses set k & 1, its first kernel clears the other
         int pc_flip = 0;

@@ -8,6 +8,7 @@ namespace {
 
 void drop_queries(selhip_ctx* c) {
     c->q.n = -1;
+    c->q.d_aux_hll = nullptr; c->q.p_aux = 0;
     c->q.db_sig_key = 0;
     c->q.db_sig_builds = 0;
     c->db_gen += 1;
@@ -19,7 +20,7 @@ void release_queries(selhip_ctx* c) {
     q.lo.release(); q.hi.release(); q.ecard.release();
     q.sigQ.release(); q.sigT.release(); q.sigP.release(); q.sigG.release();
     q.db_sigQ.release(); q.db_sigT.release(); q.db_sigP.release(); q.db_sigG.release(); q.db_bs.release(); q.db_gmax.release();
-    q.cand.release(); q.surv.release(); q.counts.release(); q.pc.release();
+    q.cand.release(); q.surv.release(); q.fin.release(); q.own_aux_hll.release(); q.counts.release(); q.pc.release();
     if (q.h_pc) (void)hipHostFree(q.h_pc);
     q.h_pc = nullptr;
 }
@@ -66,11 +67,50 @@ int query_stream_tile(int m) {
     return qt < 1 ? 0 : std::min(qt, kQStreamMaxQ);
 }
 
+bool query_smh_stage(const selhip_ctx* c) { return c->criterion == SELHIP_CRIT_SMH_A || c->criterion == SELHIP_CRIT_HLL_A_SMH_A; }
+
+// the auxiliary-HLL criterion of a query pass (kernel_query_aux.cuh).  zs, S and relerr_scaled come from the code launch_aux_fused
+// uses, so the float / double roundings are those of the all-pairs pass.  list == nullptr: hll_a / hll_an as the first criterion,
+// over every query's CB window; else the hll_a stage of the two-stage criterion over the smh_a survivors in `list`.
+hipError_t launch_query_aux(selhip_ctx* c, const selhip_int2_t* list, const u64* n_list, u64 list_cap, double tau, PassCounters* pc) {
+    auto& q = c->q;
+    const int n_q = (int)q.n, n_d = (int)c->n;
+    const float Z = 1.96f;                                   // z_score, selection.cpp:76
+    const float zs_f = Z * sigma_p_of(c->p_aux);             // float * float (criteria_sketch.hpp:29,40)
+    const double zs = (double)zs_f;
+    const double S_sum = zs;                                 // order_n = 1 (selection.cpp:77): S = Z*sigma_p
+    const double rs = relerr_scaled_for(c->p_aux);
+    const bool fma = c->fp_mode == SELHIP_FP_FMA;
+    if (list) {
+        const unsigned grid = grid_for(list_cap, kWave, 32768);
+#define SELHIP_QAL_LAUNCH(F) hipLaunchKernelGGL((query_aux_list_kernel<F, 1>), dim3(grid), dim3(kWave), 0, c->stream, q.d_aux_hll, c->d_aux_hll, \
+                                                c->p_aux, n_q, list, n_list, list_cap, q.ecard.p, rs, tau, zs, S_sum, q.fin.p, (u64)q.fin.cap, &pc->n_final)
+        if (fma) SELHIP_QAL_LAUNCH(true);
+        else     SELHIP_QAL_LAUNCH(false);
+#undef SELHIP_QAL_LAUNCH
+        return hipGetLastError();
+    }
+    const int col_blocks = (n_d + kBlock - 1) / kBlock;
+    const long long blocks = (long long)n_q * col_blocks;             // (bounded by the caller)
+    const bool qlds = c->p_aux <= kQueryAuxLdsMaxP;
+#define SELHIP_QAW_LAUNCH(F, CRIT, QL) hipLaunchKernelGGL((query_aux_window_kernel<F, CRIT, QL>), dim3((unsigned)blocks), dim3(kBlock), 0, c->stream, \
+                                                          q.d_aux_hll, c->d_aux_hll, c->p_aux, n_q, n_d, q.lo.p, q.hi.p, col_blocks, q.ecard.p, \
+                                                          rs, tau, zs, S_sum, q.fin.p, (u64)q.fin.cap, pc)
+#define SELHIP_QAW_CRIT(F, QL) do { if (c->criterion == SELHIP_CRIT_HLL_AN) SELHIP_QAW_LAUNCH(F, 2, QL); else SELHIP_QAW_LAUNCH(F, 1, QL); } while (0)
+    if (fma) { if (qlds) SELHIP_QAW_CRIT(true, true);  else SELHIP_QAW_CRIT(true, false); }
+    else     { if (qlds) SELHIP_QAW_CRIT(false, true); else SELHIP_QAW_CRIT(false, false); }
+#undef SELHIP_QAW_CRIT
+#undef SELHIP_QAW_LAUNCH
+    return hipGetLastError();
+}
+
 // one query pass on the context's stream; counters land in q.h_pc (the caller waits)
 int enqueue_query_pass(selhip_ctx* c, bool use_sig, double tau) {
     auto& q = c->q;
     const int n_q = (int)q.n, n_d = (int)c->n;
-    c->dominant_timer = c->timed_kernel == 1 ? T_HIST : (use_sig ? T_JOIN : T_STAGE1);
+    const bool smh = query_smh_stage(c);
+    use_sig = use_sig && smh;
+    c->dominant_timer = c->timed_kernel == 1 ? T_HIST : !smh ? T_AUX : (use_sig ? T_JOIN : T_STAGE1);
     if (c->timing) c->timed_passes += 1;
     TimerScope total(c, T_TOTAL);
     // counter set of this pass (the other one is cleared by this pass's first kernel for the next pass)
@@ -115,7 +155,12 @@ int enqueue_query_pass(selhip_ctx* c, bool use_sig, double tau) {
     const uint32_t* const bs_d = use_bitslices(c) ? c->hll_bs.p : q.db_bs.p;
     const uint8_t* const gmax_d = use_bitslices(c) ? c->hll_gmax.p : q.db_gmax.p;
     const int khi = std::max(q.khi, use_bitslices(c) ? c->hll_khi : q.db_khi);
-    if (use_sig) {
+    if (!smh) {
+        // hll_a / hll_an as the first criterion: straight over the windows, no signatures, no join
+        if ((long long)n_q * ((n_d + kBlock - 1) / kBlock) > 0x7FFFFFFFll) { set_err(&c->err, "query pass too large for one launch"); return SELHIP_E_BADARG; }
+        TimerScope t(c, T_AUX);
+        HIPCHK(&c->err, launch_query_aux(c, nullptr, nullptr, 0, tau, pc));
+    } else if (use_sig) {
         const long long key = ((long long)r << 40) | ((long long)nb << 24) | ((c->db_gen & 0xFFFFF) << 1) | 1;
         if (q.db_sig_key != key) {
             // D's signatures depend on D and the band shape only: kept for the shape used last (a pass with another shape replaces them)
@@ -156,17 +201,25 @@ int enqueue_query_pass(selhip_ctx* c, bool use_sig, double tau) {
                            c->m, r, nb, qt, q.lo.p, q.hi.p, col_blocks, q.surv.p, (u64)q.surv.cap, pc);
         HIPCHK(&c->err, hipGetLastError());
     }
+    // the list stage 2 reads: the smh_a survivors, or what passed the auxiliary criterion
+    const selhip_int2_t* fl = q.surv.p;
+    const u64* fcnt = &pc->n_survivors;
+    u64 fcap = (u64)q.surv.cap;
+    if (c->criterion == SELHIP_CRIT_HLL_A_SMH_A) {
+        TimerScope t(c, T_AUX);
+        HIPCHK(&c->err, launch_query_aux(c, q.surv.p, &pc->n_survivors, (u64)q.surv.cap, tau, pc));
+    }
+    if (c->criterion != SELHIP_CRIT_SMH_A) { fl = q.fin.p; fcnt = &pc->n_final; fcap = (u64)q.fin.cap; }
     // stage 2 on the combined index space: the all-pairs estimator / select kernel, unchanged
     const u64 window = (u64)q.counts.cap / 64;
-    for (u64 off = 0; off < (u64)q.surv.cap; off += window) {
+    for (u64 off = 0; off < fcap; off += window) {
         {
             TimerScope t(c, T_HIST);
-            HIPCHK(&c->err, launch_query_hist(khi, c->stream, q.bs.p, q.gmax.p, bs_d, gmax_d, n_q, q.surv.p, &pc->n_survivors, (u64)q.surv.cap,
-                                              q.counts.p, off, window));
+            HIPCHK(&c->err, launch_query_hist(khi, c->stream, q.bs.p, q.gmax.p, bs_d, gmax_d, n_q, fl, fcnt, fcap, q.counts.p, off, window));
         }
         TimerScope t(c, T_SELECT);
-        HIPCHK(&c->err, launch_select<1>(c->fp_mode == SELHIP_FP_FMA, c->stream, grid_for(std::min<u64>(window, (u64)q.surv.cap), kWave, 4096),
-                                         q.counts.p, &pc->n_survivors, 0, (u64)q.surv.cap, c->p, nullptr, q.surv.p, q.ecard.p, tau,
+        HIPCHK(&c->err, launch_select<1>(c->fp_mode == SELHIP_FP_FMA, c->stream, grid_for(std::min<u64>(window, fcap), kWave, 4096),
+                                         q.counts.p, fcnt, 0, fcap, c->p, nullptr, fl, q.ecard.p, tau,
                                          c->results.p, (u64)c->results.cap, pc, nullptr, nullptr, off, window));
     }
     hipLaunchKernelGGL(query_result_fixup_kernel, dim3(grid_for((u64)c->results.cap, kBlock, 1024)), dim3(kBlock), 0, c->stream,
@@ -184,9 +237,17 @@ int ensure_query_scratch(selhip_ctx* c, size_t list_cap, size_t res_cap) {
     HIPCHK(&c->err, q.ecard.ensure((size_t)std::max<int64_t>(1, q.n + c->n)));
     if (!q.pc.p) { HIPCHK(&c->err, q.pc.ensure(2)); q.pc_dirty = true; }
     if (!q.h_pc) HIPCHK(&c->err, hipHostMalloc((void**)&q.h_pc, sizeof(PassCounters), hipHostMallocDefault));
-    HIPCHK(&c->err, q.cand.ensure(list_cap));
-    HIPCHK(&c->err, q.surv.ensure(list_cap));
-    HIPCHK(&c->err, q.counts.ensure(std::min<size_t>(q.surv.cap, (size_t)1 << 22) * 64));
+    size_t final_cap = list_cap;
+    if (query_smh_stage(c)) {
+        HIPCHK(&c->err, q.cand.ensure(list_cap));
+        HIPCHK(&c->err, q.surv.ensure(list_cap));
+        final_cap = q.surv.cap;
+    }
+    if (c->criterion != SELHIP_CRIT_SMH_A) {
+        HIPCHK(&c->err, q.fin.ensure(list_cap));
+        final_cap = q.fin.cap;
+    }
+    HIPCHK(&c->err, q.counts.ensure(std::min<size_t>(final_cap, (size_t)1 << 22) * 64));
     HIPCHK(&c->err, c->results.ensure(res_cap));
     return SELHIP_OK;
 }

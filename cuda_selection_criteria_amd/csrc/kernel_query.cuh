@@ -3,7 +3,8 @@
 //
 // A pair (q, d) is selected iff e_hi != 0, [CB] cb_pred(tau, e_lo, e_hi), smh_a, J >= tau -- with e_lo / e_hi the smaller / larger of the
 // two truncated cardinalities.  Every term is symmetric in q and d, so a query pass returns exactly the cross pairs of an all-pairs pass
-// over Q u D (include/selection_hip.h section 2b).  The kernels:
+// over Q u D (include/selection_hip.h section 2b).  The auxiliary-HLL criteria (hll_a, hll_an, hll_a + smh_a) are in kernel_query_aux.cuh.
+// The kernels:
 //   query_windows_kernel      one lane per query: e_q, the contiguous CB window [lo_q, hi_q] of D (two binary searches on the literal
 //                             predicate), the evaluated-pair count; also the truncated cards of both sets in ONE index space [Q | D]
 //   query_sig_join_kernel     SIG: a tile of queries' band signatures in LDS, one database genome per lane (band-major, coalesced)

@@ -136,6 +136,7 @@ class Selector:
             check(self._lib.selhip_ctx_set_stream(self._ctx, C.c_void_p(stream)), self._ctx)
         self.n = 0
         self.m = 0
+        self.n_q = None             # rows of the loaded query set (None: none; uploading / attaching the database drops it)
         self._keep = None
 
     def close(self):
@@ -168,6 +169,7 @@ class Selector:
             cp = cards.ctypes.data
         check(self._lib.selhip_ctx_upload(self._ctx, hll.ctypes.data, aux.ctypes.data, cp, n, m, p_hll), self._ctx)
         self.n, self.m = n, m
+        self.n_q = None                                                # (the library dropped the queries)
 
     def attach(self, hll_t, aux_t, cards_t=None, p_hll: int = 14):
         """torch CUDA tensors: hll uint8 [n, 1<<p], aux int64 [n, m] (bit pattern of the u64 buckets),
@@ -182,6 +184,7 @@ class Selector:
         check(self._lib.selhip_ctx_attach(self._ctx, hll_t.data_ptr(), aux_t.data_ptr(), cp, n, m, p_hll), self._ctx)
         self._keep = (hll_t, aux_t, cards_t)
         self.n, self.m = n, m
+        self.n_q = None
 
     def upload_queries(self, hll: np.ndarray, aux: np.ndarray, cards: Optional[np.ndarray] = None):
         """query sketches (ascending cardinality, the database's m, p = 14) for run_queries; cards None = computed on the device"""
@@ -211,9 +214,26 @@ class Selector:
         self._keep_q = (hll_t, aux_t, cards_t)
         self.n_q = n_q
 
+    def upload_queries_aux_hll(self, aux_hll: np.ndarray, p_aux: int):
+        """auxiliary HLL sketches of the queries (query rank order) for the criteria other than smh_a; after upload_queries /
+        attach_queries, which drop them"""
+        aux_hll = np.ascontiguousarray(aux_hll, dtype=np.uint8)
+        if self.n_q is not None:                                       # (without a query set the library refuses the call)
+            assert aux_hll.shape == (self.n_q, 1 << p_aux), (aux_hll.shape, self.n_q, p_aux)
+        check(self._lib.selhip_ctx_upload_queries_aux_hll(self._ctx, aux_hll.ctypes.data if aux_hll.size else None, p_aux), self._ctx)
+
+    def attach_queries_aux_hll(self, aux_hll_t, p_aux: int):
+        """a torch CUDA uint8 tensor (n_q, 1 << p_aux); the caller keeps it alive and unchanged"""
+        assert aux_hll_t.is_cuda and aux_hll_t.is_contiguous()
+        if self.n_q is not None:
+            assert tuple(aux_hll_t.shape) == (self.n_q, 1 << p_aux), (tuple(aux_hll_t.shape), self.n_q, p_aux)
+        check(self._lib.selhip_ctx_attach_queries_aux_hll(self._ctx, aux_hll_t.data_ptr() if aux_hll_t.numel() else None, p_aux), self._ctx)
+        self._keep_q_aux = aux_hll_t
+
     def run_queries(self, tau: float, mode: int = MODE_CB_SMH, n_rows: Optional[int] = None, n_bands: Optional[int] = None,
                     algo: int = ALGO_AUTO, fetch: bool = True):
-        """one query pass (queries x database): records {i = query rank, k = database rank, jaccard} sorted by (i, k)"""
+        """one query pass (queries x database) under the criterion of set_criterion: records {i = query rank, k = database rank,
+        jaccard} sorted by (i, k)"""
         if n_rows is None or n_bands is None:
             n_rows, n_bands = banding(self.m, tau) if self.m else (1, 1)
         check(self._lib.selhip_ctx_run_queries(self._ctx, mode, algo, np.float32(tau), n_rows, n_bands), self._ctx)
@@ -421,16 +441,28 @@ def ooc_select(hll: np.ndarray, aux: np.ndarray, cards: np.ndarray, tau: float, 
 
 
 def query_from_filelists(query_list: str, db_list: str, tau: float, aux_bytes: int, mode: int = MODE_CB_SMH, fp_mode: int = FP_FMA,
-                         device: int = 0, algo: int = ALGO_AUTO) -> str:
-    """Query-vs-database selection (criterion smh_a): both lists are loaded and sorted by cardinality (load_dataset); returns one line
-    'query_path db_path J' per selected pair, in (query rank, database rank) order, J formatted as selection.cpp prints it."""
-    m = aux_bytes // 8
-    qs = load_dataset(query_list, m, 0, fp_mode)
-    db = load_dataset(db_list, m, 0, fp_mode)
-    n_rows, n_bands = banding(m, tau)
+                         device: int = 0, algo: int = ALGO_AUTO, criterion: str = "smh_a") -> str:
+    """Query-vs-database selection: both lists are loaded and sorted by cardinality (load_dataset); returns one line
+    'query_path db_path J' per selected pair, in (query rank, database rank) order, J formatted as selection.cpp prints it.
+    criterion "smh_a" (m = aux_bytes / 8 buckets) or "hll_a" / "hll_an" (auxiliary HLL p = ctz(aux_bytes), as select_from_filelist)."""
+    if criterion == "smh_a":
+        m, p_aux, crit = aux_bytes // 8, 0, CRIT_SMH_A
+    elif criterion in ("hll_a", "hll_an"):
+        m, p_aux = 0, (aux_bytes & -aux_bytes).bit_length() - 1               # __builtin_ctz(aux_bytes), selection.cpp:125
+        crit = CRIT_HLL_A if criterion == "hll_a" else CRIT_HLL_AN
+    else:
+        raise ValueError("Option -c invalid. The accepted criteria are hll_a, hll_an and smh_a.")
+    qs = load_dataset(query_list, m, p_aux, fp_mode)
+    db = load_dataset(db_list, m, p_aux, fp_mode)
+    n_rows, n_bands = banding(m, tau) if m else (1, 1)
     with Selector(device, fp_mode) as sel:
-        sel.upload(db.hll, db.aux, db.cards)
-        sel.upload_queries(qs.hll, qs.aux, qs.cards)
+        # (hll_a / hll_an read no SuperMinHash buckets: a one-bucket placeholder, as select_from_filelist uploads)
+        sel.upload(db.hll, db.aux if m else np.zeros((len(db.names), 1), dtype=np.uint64), db.cards)
+        sel.upload_queries(qs.hll, qs.aux if m else np.zeros((len(qs.names), 1), dtype=np.uint64), qs.cards)
+        if p_aux:
+            sel.upload_aux_hll(db.aux_hll, p_aux)
+            sel.upload_queries_aux_hll(qs.aux_hll, p_aux)
+        sel.set_criterion(crit)
         pairs = sel.run_queries(tau, mode, n_rows, n_bands, algo)
     h = host_lib()
     buf = C.create_string_buffer(16384)

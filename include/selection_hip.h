@@ -268,23 +268,38 @@ int    selhip_ctx_timing(selhip_ctx* ctx, int enable);
 /* ---------------------------------------------------------------------------------------------------
  * 2b. Query passes: a query set Q against the context's sketches (the database D).  Both sets are in ascending-cardinality
  *     order, with the same m and p = 14.  A pass selects the pairs (q, d) -- q a query rank, d a database rank -- with
- *     e_hi != 0, [CB mode] (double)e_lo / (double)e_hi >= (double)tau_f, smh_a and J >= tau_f (e_lo / e_hi = the smaller /
- *     larger of the two truncated cardinalities; same estimator and FP flavour as selhip_ctx_run).  Every term is symmetric,
- *     so the result is exactly the cross pairs (one member in Q, one in D) of selhip_ctx_run over Q u D, J bit for bit.
+ *     e_hi != 0, [CB mode] (double)e_lo / (double)e_hi >= (double)tau_f, the criterion set with selhip_ctx_set_criterion and
+ *     J >= tau_f (e_lo / e_hi = the smaller / larger of the two truncated cardinalities; same estimator and FP flavour as
+ *     selhip_ctx_run).  The auxiliary criteria hll_a / hll_an take card_A <= card_B (gamma = e_A / e_B, e_B on its own): a
+ *     query pair passes (e_lo, e_hi) in that order, whichever set each member comes from; every other term is symmetric.  So
+ *     the result is exactly the cross pairs (one member in Q, one in D) of selhip_ctx_run over Q u D, J bit for bit, for
+ *     every criterion: SELHIP_CRIT_SMH_A, _HLL_A, _HLL_AN and the two-stage _HLL_A_SMH_A.
  *     Records {i = query rank, k = database rank, jaccard} are read with selhip_ctx_result_count / _fetch (sorted by (i,k)),
- *     selhip_ctx_stats (evaluated = cross pairs inside the CB windows with e_hi != 0) and selhip_ctx_last_attempts.
- *     Criterion smh_a only (SELHIP_E_BADARG otherwise).  algo: SELHIP_ALGO_SIG (power-of-two rows, 8..128 bands: band
- *     signatures of a query tile in LDS against the database's, which are kept for the band shape used last -- a pass with
- *     the same shape against the same database does not build them again, one with another shape replaces them;
- *     get_param "query_db_sig_builds" counts the builds since the database was loaded), SELHIP_ALGO_STREAM (any band shape,
- *     m <= 4096: full bucket compare), SELHIP_ALGO_AUTO (SIG where it applies, else STREAM); SELHIP_ALGO_HASHJOIN is refused.
- *     Uploading / attaching the database drops the queries.  Query and all-pairs passes do not affect each other's results.
+ *     selhip_ctx_stats (evaluated = cross pairs inside the CB windows with e_hi != 0; survivors = the cross pairs that pass the
+ *     criterion before the J test -- smh_a, hll_a / hll_an, or both for the two-stage criterion, as selhip_ctx_run reports them)
+ *     and selhip_ctx_last_attempts.
+ *     Criteria other than smh_a need the auxiliary HLL sketches of both sets (selhip_ctx_upload_aux_hll for D,
+ *     selhip_ctx_upload_queries_aux_hll for Q; SELHIP_E_STATE without them) with the same p_aux (SELHIP_E_BADARG otherwise).
+ *     Where the smh_a stage runs (smh_a, two-stage) n_rows * n_bands must be m and algo is: SELHIP_ALGO_SIG (power-of-two
+ *     rows, 8..128 bands: band signatures of a query tile in LDS against the database's, which are kept for the band shape
+ *     used last -- a pass with the same shape against the same database does not build them again, one with another shape
+ *     replaces them; get_param "query_db_sig_builds" counts the builds since the database was loaded), SELHIP_ALGO_STREAM
+ *     (any band shape, m <= 4096: full bucket compare), SELHIP_ALGO_AUTO (SIG where it applies, else STREAM);
+ *     SELHIP_ALGO_HASHJOIN is refused.  hll_a / hll_an alone ignore n_rows, n_bands and algo, as selhip_ctx_run does: each
+ *     query's CB window of D is tested directly, without a pair list.  The auxiliary stage is timed as "aux".
+ *     Uploading / attaching the database drops the queries; uploading / attaching the queries drops their auxiliary sketches.
+ *     Query and all-pairs passes do not affect each other's results.
  *     After a query pass selhip_ctx_copy_results_framed / _framed_async return SELHIP_E_STATE (use selhip_ctx_copy_results).
  * --------------------------------------------------------------------------------------------------- */
 /* h_cards / d_cards may be NULL (computed on the device, as selhip_ctx_upload does); n_q == 0 is legal (0 results).  Cards that are
  * not ascending: SELHIP_E_BADARG (host cards here, device cards at the run).  attach: device pointers owned by the caller. */
 int selhip_ctx_upload_queries(selhip_ctx* ctx, const uint8_t* h_hll, const uint64_t* h_aux, const double* h_cards, int64_t n_q);
 int selhip_ctx_attach_queries(selhip_ctx* ctx, const uint8_t* d_hll, const uint64_t* d_aux, const double* d_cards, int64_t n_q);
+/* Auxiliary HLL sketches of the query set, [n_q][1 << p_aux] u8 in query rank order, p_aux in 4..15 (as selhip_ctx_upload_aux_hll); after
+ * selhip_ctx_upload_queries / _attach_queries (SELHIP_E_STATE before).  attach: 16-byte aligned device pointer owned by the caller.
+ * The pointer may be NULL when n_q == 0. */
+int selhip_ctx_upload_queries_aux_hll(selhip_ctx* ctx, const uint8_t* h_aux_hll, int p_aux);
+int selhip_ctx_attach_queries_aux_hll(selhip_ctx* ctx, const uint8_t* d_aux_hll, int p_aux);
 /* One query pass, synchronous like selhip_ctx_run; SELHIP_E_STATE before any queries are loaded. */
 int selhip_ctx_run_queries(selhip_ctx* ctx, int mode, int algo, float tau_f, int n_rows, int n_bands);
 

@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
-"""GPU box: query-vs-database passes (selhip_ctx_run_queries) on the workloads W1..W5 of DESIGN.md section 8.  One seeded set of
+"""GPU box: query-vs-database passes (selhip_ctx_run_queries) on the workloads W1..W8 of DESIGN.md section 8.  One seeded set of
 n_D + n_Q genomes from the synthetic generator, a seeded random n_Q of them as queries (generator clusters span both sides, so real
 cross pairs exist).  Per workload: device ms per query pass (events around the pass, warm, median of >= 20 passes, with min / max), n_Q * n_D per second and
-the per-kernel figures; for W1, W2 and W5 also the union route (an all-pairs pass over Q u D, cut to its cross pairs), timed in the same
-run and compared with the query pass (pairs and J bits) -- any difference makes the script exit non-zero.
-usage: bench_query.py [--out profiles/query_bench.json] [--passes 20] [--only W1,W3]"""
+the per-kernel figures; for W1, W2, W5 and W6..W8 also the union route (an all-pairs pass over Q u D under the same criterion, cut to its
+cross pairs), timed in the same run and compared with the query pass (pairs and J bits) -- any difference makes the script exit non-zero.
+W1..W5 run criterion smh_a, W6 the two-stage hll_a + smh_a of BASELINE configs[4], W7 hll_a and W8 hll_an (auxiliary HLL p = 8);
+--criterion runs the chosen workloads under another criterion (auxiliary HLL p = 8 where the workload has none).
+usage: bench_query.py [--out profiles/query_bench.json] [--passes 20] [--only W1,W3] [--criterion smh_a|hll_a|hll_an|hll_a+smh_a]"""
 import argparse
 import json
 import sys
@@ -18,15 +20,19 @@ import cuda_selection_criteria_amd as pkg  # noqa: E402
 from cuda_selection_criteria_amd import PAIR_DTYPE, SynthConfig  # noqa: E402
 
 C = pkg.SYNTH_CONFIGS
+CRITERIA = {"smh_a": pkg.CRIT_SMH_A, "hll_a": pkg.CRIT_HLL_A, "hll_an": pkg.CRIT_HLL_AN, "hll_a+smh_a": pkg.CRIT_HLL_A_SMH_A}
 WORKLOADS = {
-    #       database  queries  generator  union route
-    "W1": (50_000, 1_000, C["cfg4"], True),
-    "W2": (100_000, 1_000, C["cfg5"], True),
-    "W3": (50_000, 1, C["cfg4"], False),
-    "W4": (10_000, 10_000, C["cfg3"], False),
-    "W5": (50_000, 1_000, C["cfg3-spread"], True),     # CB prunes: most join blocks meet no window and leave at once
+    #       database  queries  generator  union route  criterion  auxiliary HLL p
+    "W1": (50_000, 1_000, C["cfg4"], True, "smh_a", 0),
+    "W2": (100_000, 1_000, C["cfg5"], True, "smh_a", 0),
+    "W3": (50_000, 1, C["cfg4"], False, "smh_a", 0),
+    "W4": (10_000, 10_000, C["cfg3"], False, "smh_a", 0),
+    "W5": (50_000, 1_000, C["cfg3-spread"], True, "smh_a", 0),     # CB prunes: most join blocks meet no window and leave at once
+    "W6": (100_000, 1_000, C["cfg5"], True, "hll_a+smh_a", 8),     # the configs[4] shape
+    "W7": (50_000, 1_000, C["cfg3-spread"], True, "hll_a", 8),
+    "W8": (50_000, 1_000, C["cfg3-spread"], True, "hll_an", 8),
 }
-KERNELS = ("prep", "sigbuild", "join", "verify", "stage1", "hist", "select", "total")
+KERNELS = ("prep", "sigbuild", "join", "verify", "stage1", "aux", "hist", "select", "total")
 
 
 def timed_passes(sel, run, passes):
@@ -50,11 +56,16 @@ def timed_passes(sel, run, passes):
             "kernel_ms": per_kernel}
 
 
-def bench(name, passes):
-    n_d, n_q, gen, union = WORKLOADS[name]
-    cfg = SynthConfig(f"{name}:{gen.name}", n_d + n_q, gen.m, gen.tau, gen.seed ^ 0x0051, cluster_size=gen.cluster_size, mode=gen.mode,
-                      n_sh_lo=gen.n_sh_lo, n_sh_hi=gen.n_sh_hi)
-    hll_t, aux_t, cards_t, _, _ = pkg.synth_device(cfg)                  # ascending cardinality
+def bench(name, passes, criterion=None):
+    n_d, n_q, gen, union, crit_name, p_aux = WORKLOADS[name]
+    if criterion is not None:
+        crit_name = criterion
+        if crit_name != "smh_a" and not p_aux:
+            p_aux = 8
+    crit = CRITERIA[crit_name]
+    cfg = SynthConfig(f"{name}:{gen.name}", n_d + n_q, gen.m, gen.tau, gen.seed ^ 0x0051, p_aux=p_aux, cluster_size=gen.cluster_size,
+                      mode=gen.mode, n_sh_lo=gen.n_sh_lo, n_sh_hi=gen.n_sh_hi)
+    hll_t, aux_t, cards_t, _, ah_t = pkg.synth_device(cfg)               # ascending cardinality
     n = n_d + n_q
     is_q = np.zeros(n, dtype=bool)
     is_q[np.random.default_rng(cfg.seed).choice(n, n_q, replace=False)] = True
@@ -63,10 +74,15 @@ def bench(name, passes):
     d_t = (hll_t[~mq].contiguous(), aux_t[~mq].contiguous(), cards_t[~mq].contiguous())
     r, b = pkg.banding(cfg.m, cfg.tau)
     out = {"workload": name, "n_database": n_d, "n_queries": n_q, "m": cfg.m, "tau": cfg.tau, "n_rows": r, "n_bands": b,
-           "generator": gen.name}
+           "generator": gen.name, "criterion": crit_name, "p_aux": p_aux}
     with pkg.Selector(0) as sel:
+        sel.set_criterion(crit)
         sel.attach(*d_t)
         sel.attach_queries(*q_t)
+        if p_aux:
+            ah_q, ah_d = ah_t[mq].contiguous(), ah_t[~mq].contiguous()
+            sel.attach_aux_hll(ah_d, p_aux)
+            sel.attach_queries_aux_hll(ah_q, p_aux)
         for _ in range(3):
             got = sel.run_queries(cfg.tau, pkg.MODE_CB_SMH, r, b)
         st = sel.stats()
@@ -76,6 +92,8 @@ def bench(name, passes):
         out["query"] = q
         if union:
             sel.attach(hll_t, aux_t, cards_t)
+            if p_aux:
+                sel.attach_aux_hll(ah_t, p_aux)
             allp = sel.run(cfg.tau, pkg.MODE_CB_SMH, r, b)
             u = timed_passes(sel, lambda: sel.run(cfg.tau, pkg.MODE_CB_SMH, r, b, fetch=False), max(5, passes // 4))
             q_rank, d_rank = np.cumsum(is_q) - 1, np.cumsum(~is_q) - 1
@@ -104,11 +122,12 @@ def main():
     ap.add_argument("--out", default=str(ROOT / "profiles" / "query_bench.json"))
     ap.add_argument("--passes", type=int, default=20)
     ap.add_argument("--only", default="W1,W2,W3,W4,W5")
+    ap.add_argument("--criterion", choices=sorted(CRITERIA), default=None, help="run the workloads under this criterion instead of their own")
     a = ap.parse_args()
     res = []
     ok = True
     for name in a.only.split(","):
-        r = bench(name, a.passes)
+        r = bench(name, a.passes, a.criterion)
         print(json.dumps(r), flush=True)
         res.append(r)
         if "union" in r and not r["union"]["identical"]:
