@@ -113,7 +113,16 @@ int selhip_ctx_set_param(selhip_ctx* c, const char* name, int value) {
         c->join_wpb = value;
         return SELHIP_OK;
     }
-    if (!std::strcmp(name, "join_form")) { c->join_form = value != 0; return SELHIP_OK; }
+    if (!std::strcmp(name, "join_form")) {
+        if (value < 0 || value > 2) { set_err(&c->err, "join_form must be 0 (packed minimum), 1 (zero-half) or 2 (bit-sliced)"); return SELHIP_E_BADARG; }
+        c->join_form = value;
+        return SELHIP_OK;
+    }
+    if (!std::strcmp(name, "join_t")) {
+        if (value < 0 || value > 2) { set_err(&c->err, "join_t must be 0 (automatic), 1 or 2"); return SELHIP_E_BADARG; }
+        c->join_t = value;
+        return SELHIP_OK;
+    }
     if (!std::strcmp(name, "join_tri")) { c->join_tri = value != 0; return SELHIP_OK; }
     if (!std::strcmp(name, "join_db")) { c->join_db = value != 0; return SELHIP_OK; }
     if (!std::strcmp(name, "join_q")) { c->join_q = value != 0; return SELHIP_OK; }
@@ -206,6 +215,7 @@ int selhip_ctx_get_param(const selhip_ctx* c, const char* name, int* value) {
     if (!std::strcmp(name, "hist_bitplanes"))   { *value = use_bitslices(c) ? 1 : 0; return SELHIP_OK; }
     if (!std::strcmp(name, "label_order"))      { *value = label_order(c) ? 1 : 0; return SELHIP_OK; }
     if (!std::strcmp(name, "join_tile_rows"))   { *value = join_tile_rows(c); return SELHIP_OK; }
+    if (!std::strcmp(name, "join_form_used"))   { *value = c->join_form_used; return SELHIP_OK; }      // kernel FORM of the last LDS-tile join (3 = bit-sliced)
     if (!std::strcmp(name, "chunks"))           { *value = c->n_chunks_last; return SELHIP_OK; }
     if (!std::strcmp(name, "small_pass_used"))  { *value = c->small_used ? 1 : 0; return SELHIP_OK; }
     if (!std::strcmp(name, "query_db_sig_builds")) { *value = c->q.db_sig_builds; return SELHIP_OK; }   // database signature builds of the query passes

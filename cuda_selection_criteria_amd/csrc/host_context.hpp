@@ -136,7 +136,11 @@ struct selhip_ctx {
     int join_wpb = 4;                   // 16-bit join: waves per block (DPP form: 1 or 4; LDS form: 4 or 8 -- the waves of a block share the staged query tile)
     int join_db = 1;                    // 16-bit join: double-buffered query batches
     int join_tri = 0;                   // LDS-tile join: 1 = launch only the (tile, candidate block) units above the diagonal (measured: no gain, see JoinTriangle); 0 = the rectangle
-    int join_form = 0;                  // 16-bit LDS-tile join, inner loop: 0 = xor + v_pk_min_u16, 1 = zero-half test (xor, sub, v_bitop3_b32; measured slower, see kernel_sigjoin.cuh)
+    // 16-bit LDS-tile join, inner loop: 2 = bit-sliced signatures, one v_bitop3_b32 per dword (where the tiled build takes the band
+    // shape; packed minimum otherwise), 0 = xor + v_pk_min_u16, 1 = zero-half test (xor, sub, v_bitop3_b32; measured slower, see kernel_sigjoin.cuh)
+    int join_form = 2;
+    int join_form_used = -1;            // kernel FORM of the last LDS-tile join launched (launch_joinl), -1 = none yet
+    int join_t = 0;                     // sliced join: candidate groups of 64 per wave, 1 or 2 (2 only for nb <= 64); 0 = automatic (launch_joinl_f)
     int join_bits = 16;                 // signature width of the all-pairs join: 16 (packed min), 15 (LDS form only: flag arithmetic, all plain VOP2) or 32
     int join_q = 1;                     // 16-bit join, query side: 1 = tile staged in LDS, broadcast reads (sigl_join_kernel), 0 = DPP row broadcast (sig16_join_kernel)
     long long enum_pairs = kEnumPairs;  // hll_a / hll_an as first criterion: pairs listed per sub-pass (test hook "enum_pairs")

@@ -64,10 +64,17 @@ hipError_t launch_stage1(selhip_ctx* c, const StageIO& io, int n_rows, int n_ban
 
 unsigned grid_for(u64 items, unsigned per_block, unsigned max_blocks);
 
+// pairs of the all-pairs triangle that this context's passes cover
+double join_pairs_here(const selhip_ctx* c) {
+    return 0.5 * (double)c->n * (double)c->n / std::max(1, c->il_parts);
+}
+
 // tile height of the signature joins: the configured one, or the automatic choice (see selhip_ctx::join_qt)
 int join_tile_rows(const selhip_ctx* c) {
-    const double pairs_here = 0.5 * (double)c->n * (double)c->n / std::max(1, c->il_parts);       // this context's share of the triangle
+    const double pairs_here = join_pairs_here(c);
     // (< 1e8 pairs: 32-row tiles -- twice the work units for the 8 192 wave slots, a shorter tail: cfg3's join 108.5 -> 104.3 us)
+    // (the sliced join kept these heights: cfg3 32 / 64 rows 239.7 / 239.2 us a pass, cfg4 64 / 128 rows 1643 / 1633 us at T = 1,
+    //  profiles/join_sliced_sweep.txt)
     int qt = c->join_qt > 0 ? c->join_qt : (pairs_here >= 4.5e8 ? 128 : pairs_here >= 2e8 ? 64 : 32);      // (one of 8 ranks of cfg4, 1.6e8 pairs: 32 rows 0.450 ms, 64 rows 0.481)
     if (c->il_parts > 1) { qt = std::min(qt, c->il_block); while (c->il_block % qt) qt -= 16; }
     return qt;
@@ -117,7 +124,18 @@ hipError_t launch_join16_w(selhip_ctx* c, const StageIO& io, int n_pad, const Ro
     return hipGetLastError();
 }
 
-template <int ND, int T, int WPB>
+// the tiled signature build (sig_build_tile_body) takes this band shape
+bool sig_tile_mode(const selhip_ctx* c, int n_rows, int n_bands) {
+    return is_pow2(c->m) && is_pow2(n_bands) && n_bands <= 128 && n_rows >= 2 && n_rows <= 32 && c->m >= 4 && c->sig_tile;
+}
+
+// the all-pairs join of this band shape runs on bit-sliced signatures ("join_form" = 2: the LDS-tile 16-bit join, and a tiled build to
+// write the layout; any other shape keeps the packed form 0).  The build and the join both ask, so they always agree on the layout.
+bool join_sliced(const selhip_ctx* c, int n_rows, int n_bands) {
+    return c->join_form == 2 && c->join_bits == 16 && c->join_q && c->algo != SELHIP_ALGO_HASHJOIN && sig_tile_mode(c, n_rows, n_bands);
+}
+
+template <int ND, int T, int WPB, int FORM>
 hipError_t launch_joinl_w(selhip_ctx* c, const StageIO& io, int n_pad, const RowMap& rm) {
     const int n = (int)c->n;
     // tile height: the configured one, capped so that the tile (+ appenders) fits 64 KiB of LDS; a multiple of 16 that divides the
@@ -153,27 +171,40 @@ hipError_t launch_joinl_w(selhip_ctx* c, const StageIO& io, int n_pad, const Row
     if (blocks > 0x7FFFFFFFll) return hipErrorInvalidValue;
     const size_t smem = (size_t)WPB * kAppendCap * sizeof(selhip_int2_t) + (size_t)((qt + 3) & ~3) * 4 + (size_t)(qt + kJoinTilePadRows) * ND * 4;
     if (smem > 64 * 1024) return hipErrorInvalidValue;                                   // join_qt is capped so that this cannot happen
-#define SELHIP_JOINL_LAUNCH(FORM) hipLaunchKernelGGL((sigl_join_kernel<ND, T, WPB, FORM>), dim3((unsigned)blocks), dim3(WPB * kWave), smem, io.st, \
-                           c->sigP.p, c->sigG.p, n, n_pad, c->hi.p, c->pcb, rm, n_tiles, group_base, qt, \
-                           io.cand, io.cap, io.seg_cnt, c->mode == SELHIP_MODE_CB_SMH ? 1 : 0, tri)
-    if (c->join_bits == 15)    SELHIP_JOINL_LAUNCH(1);
-    else if (c->join_form == 0) SELHIP_JOINL_LAUNCH(0);
-    else                        SELHIP_JOINL_LAUNCH(2);
-#undef SELHIP_JOINL_LAUNCH
+    hipLaunchKernelGGL((sigl_join_kernel<ND, T, WPB, FORM>), dim3((unsigned)blocks), dim3(WPB * kWave), smem, io.st,
+                       c->sigP.p, c->sigG.p, n, n_pad, c->hi.p, c->pcb, rm, n_tiles, group_base, qt,
+                       io.cand, io.cap, io.seg_cnt, c->mode == SELHIP_MODE_CB_SMH ? 1 : 0, tri);
     return hipGetLastError();
 }
 
-// (T = 2 groups of candidates per wave -- half the LDS reads -- was measured twice: 130 VGPRs, 3 waves per SIMD, cfg3 157 vs 127 us,
-// cfg4 2.37 vs 2.07 ms; and, after the wait counts left the row loop, capped at 128 VGPRs / 4 waves per SIMD: cfg3 121 vs 101 us, cfg4
-// 2.28 vs 2.02 ms -- the join wants waves, not fewer LDS reads; the template keeps the parameter, only T = 1 is instantiated)
+// (T = 2 groups of candidates per wave -- half the LDS reads -- was measured twice with the packed minimum: 130 VGPRs, 3 waves per SIMD,
+// cfg3 157 vs 127 us, cfg4 2.37 vs 2.07 ms; and, after the wait counts left the row loop, capped at 128 VGPRs / 4 waves per SIMD: cfg3
+// 121 vs 101 us, cfg4 2.28 vs 2.02 ms -- that loop wants waves, not fewer LDS reads.  The sliced loop issues a third of the instructions
+// per row, so it is built with T = 2 as well (nb <= 64, where 2 x ND candidate registers fit in 128 VGPRs).  Measured (three rounds,
+// profiles/join_sliced_sweep.txt): cfg3 T = 2 241.9 vs T = 1 239.7 us a pass, cfg4 1525 vs 1633 us -- at the pass sizes that take
+// 128-row tiles (>= 4.5e8 pairs) the halved LDS reads pay, below they do not: "join_t" = 0 (automatic) picks T by that size.)
+template <int ND, int FORM>
+hipError_t launch_joinl_f(selhip_ctx* c, const StageIO& io, int n_pad, const RowMap& rm) {
+    const int t = c->join_t ? c->join_t : join_pairs_here(c) >= 4.5e8 ? 2 : 1;
+    if constexpr (FORM == 3 && ND <= 32)
+        if (t == 2) return c->join_wpb == 8 ? launch_joinl_w<ND, 2, 8, FORM>(c, io, n_pad, rm) : launch_joinl_w<ND, 2, 4, FORM>(c, io, n_pad, rm);
+    return c->join_wpb == 8 ? launch_joinl_w<ND, 1, 8, FORM>(c, io, n_pad, rm) : launch_joinl_w<ND, 1, 4, FORM>(c, io, n_pad, rm);
+}
+
+// kernel FORM of sigl_join_kernel: 1 = 15-bit flags, 3 = bit-sliced ("join_form" 2), 2 = zero-half ("join_form" 1), 0 = packed minimum
 template <int ND>
 hipError_t launch_joinl(selhip_ctx* c, const StageIO& io, int n_pad, const RowMap& rm) {
-    return c->join_wpb == 8 ? launch_joinl_w<ND, 1, 8>(c, io, n_pad, rm) : launch_joinl_w<ND, 1, 4>(c, io, n_pad, rm);
+    if (c->join_bits == 15) { c->join_form_used = 1; return launch_joinl_f<ND, 1>(c, io, n_pad, rm); }
+    if (join_sliced(c, c->n_rows, c->n_bands)) { c->join_form_used = 3; return launch_joinl_f<ND, 3>(c, io, n_pad, rm); }
+    if (c->join_form == 1) { c->join_form_used = 2; return launch_joinl_f<ND, 2>(c, io, n_pad, rm); }
+    c->join_form_used = 0;
+    return launch_joinl_f<ND, 0>(c, io, n_pad, rm);
 }
 
 template <int ND, bool DB>
 hipError_t launch_join16(selhip_ctx* c, const StageIO& io, int n_pad, const RowMap& rm) {
     if (c->join_q) return launch_joinl<ND>(c, io, n_pad, rm);
+    c->join_form_used = -1;
     return c->join_wpb == 1 ? launch_join16_w<ND, DB, 1>(c, io, n_pad, rm) : launch_join16_w<ND, DB, 4>(c, io, n_pad, rm);
 }
 
@@ -184,12 +215,15 @@ hipError_t launch_sig_build(selhip_ctx* c, int n_rows, int n_bands, bool with_bo
     TimerScope t(c, T_SIGBUILD);
     const int bounds_blocks = with_bounds ? (n + kBlock - 1) / kBlock : 0;
     // tiled build (kSigTileG genomes per block, LDS transpose) for the shapes of the all-pairs joins; the per-bucket form otherwise
-    const bool tile_mode = is_pow2(c->m) && is_pow2(n_bands) && n_bands <= 128 && n_rows >= 2 && n_rows <= 32 && c->m >= 4 && c->sig_tile;
+    const bool tile_mode = sig_tile_mode(c, n_rows, n_bands);
+    const bool slice = join_sliced(c, n_rows, n_bands);                  // sigP / sigG bit-sliced instead of packed
     const long long threads = n_rows <= kWave ? (long long)n * c->m : (long long)n * n_bands;
     // "sig_cache": the signatures depend on the sketches and the band shape only, so a context that runs many passes over the same
     // sketches (the ranks of a strong-scaled job, a threshold sweep) builds them once; upload / attach and any reallocation of the
-    // signature arrays invalidate them.  The bounds blocks still run every pass (they depend on tau, the mode and the rows).
-    const long long sig_key = ((long long)n_rows << 40) | ((long long)n_bands << 20) | ((long long)(c->join_bits == 15) << 2) | (tile_mode ? 2 : 0) | 1;
+    // signature arrays invalidate them.  The bounds blocks still run every pass (they depend on tau, the mode and the rows).  The key
+    // holds the layout of sigP / sigG (15-bit, 16-bit packed or sliced), so a join never reads words written for another.
+    const long long sig_key = ((long long)n_rows << 40) | ((long long)n_bands << 20) | ((long long)slice << 3) | ((long long)(c->join_bits == 15) << 2) |
+                              (tile_mode ? 2 : 0) | 1;
     const bool cached = c->sig_cache && c->sig_key == sig_key && with_bounds;
     const int tg = c->sig_tile_g;                                       // genomes per tile
     const unsigned work_blocks = cached ? 0u : tile_mode ? (unsigned)((n + tg - 1) / tg) : (unsigned)((threads + kBlock - 1) / kBlock);
@@ -200,7 +234,7 @@ hipError_t launch_sig_build(selhip_ctx* c, int n_rows, int n_bands, bool with_bo
                        bounds_blocks, c->d_cards, tau, c->mode == SELHIP_MODE_CB_SMH ? 1 : 0, row_map(c, rb, re), c->ecard.p, c->hi.p, c->pcb,
                        grouping_on(c) ? c->csr_cnt.p : nullptr, grouping_on(c) ? (int)c->csr_cnt.cap : 0, (int)c->cand_begin,
                        with_bounds ? c->seg_cnt.p : nullptr, with_bounds ? (int)c->seg_cnt.cap : 0, c->join_bits == 15 ? 17 : 16,
-                       zero_pc, tile_mode ? tg : 0);
+                       zero_pc, tile_mode ? tg : 0, slice ? 1 : 0);
     return hipGetLastError();
 }
 

@@ -36,7 +36,7 @@ hipError_t launch_sig_rows(selhip_ctx* c, const u64* aux, int n, int r, int nb, 
     RowMap rm{0, 0, 1, 1, 0};
     hipLaunchKernelGGL(sig_build_kernel, dim3(blocks), dim3(kBlock), 0, c->stream, aux, n, c->m, r, nb, n_pad, sQ, sT, sP, sG,
                        0, (const double*)nullptr, 0.0, 0, rm, (u64*)nullptr, (int*)nullptr, (PassCounters*)nullptr, (int*)nullptr, 0, 0,
-                       (u64*)nullptr, 0, 16, (PassCounters*)nullptr, tile_mode ? tg : 0);
+                       (u64*)nullptr, 0, 16, (PassCounters*)nullptr, tile_mode ? tg : 0, 0);
     return hipGetLastError();
 }
 

@@ -102,13 +102,33 @@ constexpr int kSigTileG = 32;             // LDS capacity of a tile; the launch 
 // 16-byte loads a thread has in flight (8 and 16 measured no better: build alone 17.3 / 17.5 / 18.9 us at cfg3, 60.4 / 60.1 / 63.0 at cfg4,
 // gpurun_out/r03/p_*)
 constexpr int kSigLoads = 4;
+// ballots K .. NB/4 - 1 of a genome's bit-sliced words (sig_build_tile_body, `slice`): ballot K takes bits p = 64 K + lane of the stream,
+// band p % NB (the lane's x0, or x1 for the odd ballots when NB = 128) and plane p / NB, a fixed bit of x0 / x1.  Its low half is word 2K
+// (kept by lane 2K), its high half word 2K + 1 (lane 2K + 1).
+template <int NB, int K>
+__device__ __forceinline__ void sig_slice_words(uint32_t& w, uint32_t x0, uint32_t x1, int lane) {
+    if constexpr (K < NB / 4) {
+        constexpr bool odd = NB > kWave && (K & 1);
+        constexpr int bit = NB > kWave ? K >> 1 : K * (kWave / NB);
+        const u64 bits = __ballot(((odd ? x1 : x0) >> bit) & 1u);
+        const uint32_t v = (lane & 1) ? (uint32_t)(bits >> 32) : (uint32_t)bits;
+        w = (lane >> 1) == K ? v : w;
+        sig_slice_words<NB, K + 1>(w, x0, x1, lane);
+    }
+}
+
 template <int CAP>
 __device__ __forceinline__ void sig_build_tile_body(int tile, const u64* __restrict__ aux, int n, int m, int r, int nb, int n_pad,
                                                     uint32_t* __restrict__ sigQ, uint32_t* __restrict__ sigT, uint32_t* __restrict__ sigP,
                                                     uint32_t* __restrict__ sigG, int pk_shift,
-                                                    int tg, bool all_layouts = true) {
+                                                    int tg, bool all_layouts = true, bool slice = false) {
     // (tg <= CAP genomes per tile: the one-launch pass of a small set spreads ITS genomes over all its blocks; it only reads the
     //  32-bit layouts sigQ / sigT and leaves the packed ones alone)
+    // slice: sigP / sigG receive the BIT-SLICED 16-bit signatures of the sliced join (sigl_join_kernel FORM 3) instead of the packed
+    //  ones.  A genome's ND = nb / 2 words are one bit stream: bit p (p = 32 d + t, bit t of word d) = bit 16 + p / nb of the 32-bit
+    //  signature of band p % nb -- plane j (j = 0..15) = "bit 16 + j of every band", nb bits, the 16 planes one after the other (for
+    //  nb >= 32 a plane spans nb / 32 words, for nb < 32 a word holds 32 / nb planes).  Same shapes as the packed words: sigP[d][n_pad]
+    //  (lane = genome), sigG[g][ND].
     __shared__ uint32_t sig_lds[CAP][129];                          // pitch 129: the band-major read-out is conflict-free
     const int g0 = tile * tg;
     const int ng = min(tg, n - g0);
@@ -143,20 +163,47 @@ __device__ __forceinline__ void sig_build_tile_body(int tile, const u64* __restr
     __syncthreads();
     uint16_t* const sigG16 = reinterpret_cast<uint16_t*>(sigG);
     const int ndw = (nb + 1) >> 1;
+    const bool packed = all_layouts && !slice;
     for (int idx = threadIdx.x; idx < ng * nb; idx += kBlock) {            // genome-major: rows contiguous
         const int gl = idx / nb, b = idx - gl * nb;
         const uint32_t sig = sig_lds[gl][b];
         sigQ[(size_t)(g0 + gl) * nb + b] = sig;
-        if (all_layouts) sigG16[(size_t)(g0 + gl) * (2 * ndw) + b] = (uint16_t)(sig >> pk_shift);
+        if (packed) sigG16[(size_t)(g0 + gl) * (2 * ndw) + b] = (uint16_t)(sig >> pk_shift);
     }
     for (int idx = threadIdx.x; idx < nb * tg; idx += kBlock) {            // band-major: tg consecutive genomes per band
         const int b = idx / tg, gl = idx - b * tg;
         if (gl < ng) sigT[(size_t)b * n_pad + g0 + gl] = sig_lds[gl][b];
     }
     if (!all_layouts) return;
+    if (slice) {
+        // one wave per genome: ballot k (k < nb / 4) takes bits p = 64 k + lane of the stream, i.e. words 2k and 2k + 1.  For nb <= 64
+        // band p % nb = lane % nb whatever k, for nb = 128 it is lane or 64 + lane; the plane p / nb picks the bit.  The wave's words
+        // (lane d holds word d) then take the place of the row they were made from, for the band-major write-out below.
+        __syncthreads();                                                  // the reads of the tile above are done
+        const int lane = threadIdx.x & (kWave - 1), lnb = __builtin_ctz((unsigned)nb);
+        for (int gl = (int)(threadIdx.x / kWave); gl < ng; gl += kBlock / kWave) {
+            // this lane's band, shifted to its first plane (for nb = 128 x0 / x1 hold bands lane / 64 + lane from plane 0)
+            const uint32_t x0 = sig_lds[gl][lane & (nb - 1)] >> (16 + (nb > kWave ? 0 : lane >> lnb));
+            const uint32_t x1 = nb > kWave ? sig_lds[gl][kWave + lane] >> 16 : x0;
+            uint32_t w = 0;
+            switch (nb) {
+                case 8: sig_slice_words<8, 0>(w, x0, x1, lane); break;
+                case 16: sig_slice_words<16, 0>(w, x0, x1, lane); break;
+                case 32: sig_slice_words<32, 0>(w, x0, x1, lane); break;
+                case 64: sig_slice_words<64, 0>(w, x0, x1, lane); break;
+                default: sig_slice_words<128, 0>(w, x0, x1, lane); break;
+            }
+            if (lane < ndw) {
+                sigG[(size_t)(g0 + gl) * ndw + lane] = w;
+                sig_lds[gl][lane] = w;
+            }
+        }
+        __syncthreads();
+    }
     for (int idx = threadIdx.x; idx < ndw * tg; idx += kBlock) {
         const int d = idx / tg, gl = idx - d * tg;
         if (gl < ng) {
+            if (slice) { sigP[(size_t)d * n_pad + g0 + gl] = sig_lds[gl][d]; continue; }
             const uint32_t lo = sig_lds[gl][2 * d] >> pk_shift, hi2 = (2 * d + 1 < nb) ? (sig_lds[gl][2 * d + 1] >> pk_shift) : 0u;
             sigP[(size_t)d * n_pad + g0 + gl] = (lo & 0xFFFFu) | (hi2 << 16);
         }
@@ -170,8 +217,8 @@ void sig_build_kernel(const u64* __restrict__ aux, int n, int m, int r, int nb, 
                       uint32_t* __restrict__ sigQ, uint32_t* __restrict__ sigT, uint32_t* __restrict__ sigP, uint32_t* __restrict__ sigG,
                       int bounds_blocks, const double* __restrict__ cards, double tau, int use_cb, RowMap rm,
                       u64* __restrict__ ecard, int* __restrict__ hi, PassCounters* __restrict__ pc, int* __restrict__ csr_zero, int csr_zero_n, int cand_begin,
-                      u64* __restrict__ seg_zero, int seg_zero_n, int pk_shift, PassCounters* __restrict__ zero_pc, int tile_mode) {
-    // (tile_mode = genomes per tile of the tiled build, 0 = the per-bucket form)
+                      u64* __restrict__ seg_zero, int seg_zero_n, int pk_shift, PassCounters* __restrict__ zero_pc, int tile_mode, int slice) {
+    // (tile_mode = genomes per tile of the tiled build, 0 = the per-bucket form; slice = bit-sliced sigP / sigG, tiled form only)
     if ((int)blockIdx.x < bounds_blocks) {
         const int t = (int)(blockIdx.x * kBlock + threadIdx.x);
         zero_next_counters(t, bounds_blocks * kBlock, zero_pc, kCounterBlocks);
@@ -180,7 +227,7 @@ void sig_build_kernel(const u64* __restrict__ aux, int n, int m, int r, int nb, 
         cb_bounds_body(t, cards, n, tau, use_cb, rm, ecard, hi, pc, cand_begin);
         return;
     }
-    if (tile_mode) sig_build_tile_body<kSigTileG>((int)blockIdx.x - bounds_blocks, aux, n, m, r, nb, n_pad, sigQ, sigT, sigP, sigG, pk_shift, tile_mode);
+    if (tile_mode) sig_build_tile_body<kSigTileG>((int)blockIdx.x - bounds_blocks, aux, n, m, r, nb, n_pad, sigQ, sigT, sigP, sigG, pk_shift, tile_mode, true, slice != 0);
     else           sig_build_body((long long)blockIdx.x - bounds_blocks, aux, n, m, r, nb, n_pad, sigQ, sigT, sigP, sigG, pk_shift);
 }
 
@@ -478,6 +525,48 @@ __device__ __forceinline__ void joinl_test_z(const uint32_t (&acc)[T][4], int i,
     }
 }
 
+// Bit-sliced form ("join_form" = 2, the default where the tiled build can write its layout -- see sig_build_tile_body): the same 16
+// bits per band, stored plane by plane, so "some band has all 16 bits equal" is "some bit of the OR over the planes of (q ^ c) is
+// clear".  The loop is ONE v_bitop3_b32 per dword, acc = acc | (q ^ c) (LUT 0xF6), against a v_xor_b32 and a v_pk_min_u16 (4.07
+// cycles, no dual issue) in the packed form; same 16-bit matches, hence the same candidates, survivors and results.  Accumulator a
+// holds the words d = a (mod 4); for nb >= 32 word d carries bands 32 (d % (nb / 32)) .. + 31, so joinl_test_s folds the
+// accumulators of the same band word with OR and the band words with AND; for nb < 32 a word holds 32 / nb planes, folded by shifts.
+// Measured at cfg3 (profiles/join_sliced_*): join 104.0 -> 63.3 us, SQ_INSTS_VALU 0.58x, LDS busy 42 -> 70 %.
+template <int ND, int T, int OFF, int CNT>
+__device__ __forceinline__ void joinl_accum_s(uint32_t (&acc)[T][4], const uint32_t (&c)[T][ND], const uint32_t (&q)[CNT]) {
+#pragma unroll
+    for (int d = 0; d < CNT; d += 4) {
+#pragma unroll
+        for (int t = 0; t < T; ++t)
+#pragma unroll
+            for (int a = 0; a < 4; ++a) acc[t][a] = __builtin_amdgcn_bitop3_b32(acc[t][a], q[d + a], c[t][OFF + d + a], 0xF6);   // a | (b ^ c)
+    }
+}
+
+template <int ND, int T>
+__device__ __forceinline__ void joinl_test_s(const uint32_t (&acc)[T][4], int i, int k0, int lane, int z0, int n,
+                                             const int* hi_rows, int r, WaveAppender& app) {
+    static_assert(ND == 4 || ND == 8 || ND == 16 || ND == 32 || ND == 64, "sliced join: nb in {8, 16, 32, 64, 128}");
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+        uint32_t f;                                                             // a clear bit = a band with no plane differing
+        if constexpr (ND == 64)      f = (acc[t][0] & acc[t][1]) & (acc[t][2] & acc[t][3]);
+        else if constexpr (ND == 32) f = (acc[t][0] | acc[t][2]) & (acc[t][1] | acc[t][3]);
+        else {
+            f = (acc[t][0] | acc[t][1]) | (acc[t][2] | acc[t][3]);
+            if constexpr (ND == 8) f = (f | (f >> 16)) | 0xFFFF0000u;
+            if constexpr (ND == 4) { f |= f >> 16; f = (f | (f >> 8)) | 0xFFFFFF00u; }
+        }
+        const u64 mm = __ballot(f != 0xFFFFFFFFu);
+        if (mm) {
+            const int lo = max(i + 1, z0);
+            const int hk = min(hi_rows[r], n - 1);
+            const int k = k0 + t * kWave;
+            app.push(((mm >> lane) & 1ull) && k >= lo && k <= hk, i, k, lane);
+        }
+    }
+}
+
 template <int T>
 __device__ __forceinline__ void joinl_reset15(uint32_t (&acc)[T][4]) {
 #pragma unroll
@@ -574,9 +663,10 @@ struct JoinTriangle {
     }
 };
 
-// FORM: 0 = packed minimum (v_xor_b32 + v_pk_min_u16), 1 = 15-bit signatures with flag arithmetic, 2 = 16-bit zero-half test
+// FORM: 0 = packed minimum (v_xor_b32 + v_pk_min_u16), 1 = 15-bit signatures with flag arithmetic, 2 = 16-bit zero-half test,
+// 3 = bit-sliced 16-bit signatures (sigP / sigG written with sig_build_tile_body's `slice`)
 template <int ND, int T, int WPB, int FORM>
-__global__ __launch_bounds__(WPB * kWave)
+__global__ __launch_bounds__(WPB * kWave) __attribute__((amdgpu_waves_per_eu(T == 1 ? 1 : 4)))        // T = 2: at most 128 VGPRs
 void sigl_join_kernel(const uint32_t* __restrict__ sigP, const uint32_t* __restrict__ sigG, int n, int n_pad,
                       const int* __restrict__ hi, const PassCounters* __restrict__ pc_in,
                       RowMap rm, int n_tiles, int group_base, int qt,
@@ -652,16 +742,18 @@ void sigl_join_kernel(const uint32_t* __restrict__ sigP, const uint32_t* __restr
         const u64 seg_cap = pre_cap / kAppendSegs;
         app.init(app_lds, wave, pre + (size_t)seg * seg_cap, seg_cap, seg_cnt + seg * kSegStride);
     }
-    constexpr int CH = ND < 16 ? ND : 16;                                      // dwords per chunk (one register set)
+    constexpr int CHM = T == 1 ? 16 : 8;                                       // (T = 2: 8-dword chunks keep the 2 x ND candidates in 128 VGPRs)
+    constexpr int CH = ND < CHM ? ND : CHM;                                    // dwords per chunk (one register set)
     constexpr int NCH = ND / CH;                                               // chunks per row: 1 (<= 32 bands), 2 (64), 4 (128)
+    static_assert(NCH == 1 || NCH == 2 || NCH == 4, "sigl_join_kernel: 1, 2 or 4 chunks per row");
     const int rows = i_hi - i_lo;
     using acc_t = typename std::conditional<FORM != 0, uint32_t, us2_t>::type;
     acc_t acc[T][4];
     uint32_t k7 = FORM == 2 ? 0x00010001u : 0x7FFF7FFFu;
-    asm volatile("" : "+v"(k7));                                               // keep the constant in a VGPR (a literal operand is not a plain VOP2)
-#define SELHIP_JL_RESET()            do { if constexpr (FORM == 2) joinl_reset_z<T>(acc); else if constexpr (FORM == 1) joinl_reset15<T>(acc); else joinl_reset<T>(acc); } while (0)
-#define SELHIP_JL_ACCUM(OFF, Q)      do { if constexpr (FORM == 2) joinl_accum_z<ND, T, OFF, CH>(acc, c, Q, k7); else if constexpr (FORM == 1) joinl_accum15<ND, T, OFF, CH>(acc, c, Q, k7); else joinl_accum<ND, T, OFF, CH>(acc, c, Q); } while (0)
-#define SELHIP_JL_TEST(R)            do { if constexpr (FORM == 2) joinl_test_z<T>(acc, i_lo + (R), k0, lane, z0, n, hi_lds, R, app); else if constexpr (FORM == 1) joinl_test15<T>(acc, i_lo + (R), k0, lane, z0, n, hi_lds, R, app); else joinl_test<T>(acc, i_lo + (R), k0, lane, z0, n, hi_lds, R, app); } while (0)
+    if constexpr (FORM == 1 || FORM == 2) asm volatile("" : "+v"(k7));         // keep the constant in a VGPR (a literal operand is not a plain VOP2)
+#define SELHIP_JL_RESET()            do { if constexpr (FORM == 2 || FORM == 3) joinl_reset_z<T>(acc); else if constexpr (FORM == 1) joinl_reset15<T>(acc); else joinl_reset<T>(acc); } while (0)
+#define SELHIP_JL_ACCUM(OFF, Q)      do { if constexpr (FORM == 3) joinl_accum_s<ND, T, OFF, CH>(acc, c, Q); else if constexpr (FORM == 2) joinl_accum_z<ND, T, OFF, CH>(acc, c, Q, k7); else if constexpr (FORM == 1) joinl_accum15<ND, T, OFF, CH>(acc, c, Q, k7); else joinl_accum<ND, T, OFF, CH>(acc, c, Q); } while (0)
+#define SELHIP_JL_TEST(R)            do { if constexpr (FORM == 3) joinl_test_s<ND, T>(acc, i_lo + (R), k0, lane, z0, n, hi_lds, R, app); else if constexpr (FORM == 2) joinl_test_z<T>(acc, i_lo + (R), k0, lane, z0, n, hi_lds, R, app); else if constexpr (FORM == 1) joinl_test15<T>(acc, i_lo + (R), k0, lane, z0, n, hi_lds, R, app); else joinl_test<T>(acc, i_lo + (R), k0, lane, z0, n, hi_lds, R, app); } while (0)
     uint32_t qa[CH], qb[CH];
     joinl_load<CH>(qa, tile_lds);
     if constexpr (NCH == 1) {

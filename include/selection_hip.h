@@ -147,8 +147,12 @@ int selhip_ctx_set_candidate_begin(selhip_ctx* ctx, int64_t k_min);
  *   "join_bits"   16 (default): all-pairs join on 16-bit band signatures packed two per dword, its matches cut back to the
  *                 32-bit candidate set during verification; 15: the same with 15-bit signatures and flag arithmetic made of
  *                 plain VOP2 instructions only (LDS form); 32: join on the 32-bit signatures directly
- *   "join_form"   inner loop of the 16-bit LDS-tile join: 0 (default) = v_xor_b32 + v_pk_min_u16; 1 = zero-half test, three 2-cycle
- *                 instructions per packed dword (v_xor_b32, v_sub_u32, v_bitop3_b32; measured slower)
+ *   "join_form"   inner loop of the 16-bit LDS-tile join: 2 (default) = bit-sliced signatures (plane j of a genome = bit 16 + j of
+ *                 every band's signature), one v_bitop3_b32 per dword -- for band shapes of the tiled signature build (power-of-two m,
+ *                 2 <= rows per band <= 32, "sig_tile" = 1), the packed form 0 otherwise; 0 = packed dwords, v_xor_b32 + v_pk_min_u16;
+ *                 1 = zero-half test on the packed dwords (v_xor_b32, v_sub_u32, v_bitop3_b32; measured slower)
+ *   "join_t"      sliced join: groups of 64 candidates per wave, 1 or 2 (at most 64 bands; 1 beyond); 0 (default) = automatic (2 from
+ *                 4.5e8 pairs per pass)
  *   "join_tri"    1: the LDS-tile join launches only the (tile, candidate block) units above the diagonal (contiguous rows; measured:
  *                 no gain); 0 (default): the rectangle, whose blocks under the diagonal leave at once
  *   "join_db"     1 (default) / 0: double-buffered query batches in the DPP form of the 16-bit join
@@ -181,7 +185,8 @@ int selhip_ctx_set_candidate_begin(selhip_ctx* ctx, int64_t k_min);
  * knobs, listed at selhip_ctx_set_param in csrc/selection_kernels.hip.) */
 int selhip_ctx_set_param(selhip_ctx* ctx, const char* name, int value);
 /* what the context decided (read-only): "hll_khi" (largest p = 14 register value + 1; 0 = no bit planes), "hist_bitplanes",
- * "label_order", "join_tile_rows", "chunks" (chunk lanes of the last pass), "small_pass_used" (the last pass was the one-launch small pass),
+ * "label_order", "join_tile_rows", "join_form_used" (kernel form of the last LDS-tile join: 0 packed minimum, 1 15-bit, 2 zero-half,
+ * 3 bit-sliced; -1 none or the DPP join), "chunks" (chunk lanes of the last pass), "small_pass_used" (the last pass was the one-launch small pass),
  * "query_db_sig_builds" (builds of the database's band signatures by query passes since the database was loaded, section 2b) */
 int selhip_ctx_get_param(const selhip_ctx* ctx, const char* name, int* value);
 /* Stage 2 grouping (default on): the pairs that reach the HLL-14 stage are bucketed by query row (counting sort) so
