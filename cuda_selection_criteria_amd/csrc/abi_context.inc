@@ -53,6 +53,7 @@ void selhip_ctx_destroy(selhip_ctx* c) {
     c->hj_keys_in.release(); c->hj_keys_out.release(); c->hj_vals_in.release(); c->hj_vals_out.release(); c->hj_tmp.release();
     c->csr_cnt.release(); c->csr_start.release(); c->grouped.release(); c->scan_tmp.release();
     c->hll_bs.release(); c->hll_bs_max.release(); c->hll_gmax.release(); c->small_bar.release();
+    c->hll_sparse.release(); c->hll_sparse_dev_t.release();
     release_queries(c);
     if (c->h_pc) (void)hipHostFree(c->h_pc);
     if (c->st_stage1) {
@@ -190,6 +191,11 @@ int selhip_ctx_set_param(selhip_ctx* c, const char* name, int value) {
         if (value == 0) c->hll_khi = 0;
         return SELHIP_OK;
     }
+    if (!std::strcmp(name, "hist_sparse")) {
+        if (value < -1 || value > 1) { set_err(&c->err, "hist_sparse must be -1 (automatic), 0 (every value from the bit planes) or 1 (values >= the set's threshold from its sparse lists)"); return SELHIP_E_BADARG; }
+        c->hist_sparse = value;
+        return SELHIP_OK;
+    }
     if (!std::strcmp(name, "hist_dense_degree")) {
         if (value < -1 || value > (1 << 20)) { set_err(&c->err, "hist_dense_degree must be in [-1, 2^20] (-1 = never)"); return SELHIP_E_BADARG; }
         c->hist_dense_degree = value;
@@ -213,6 +219,7 @@ int selhip_ctx_get_param(const selhip_ctx* c, const char* name, int* value) {
     if (!c || !name || !value) return SELHIP_E_BADARG;
     if (!std::strcmp(name, "hll_khi"))          { *value = c->hll_khi; return SELHIP_OK; }             // largest p = 14 register value + 1 (0: no bit planes)
     if (!std::strcmp(name, "hist_bitplanes"))   { *value = use_bitslices(c) ? 1 : 0; return SELHIP_OK; }
+    if (!std::strcmp(name, "hist_sparse_t"))    { *value = sparse_t_used(c); return SELHIP_OK; }      // threshold of the all-pairs stage 2a's sparse lists, 0 = off
     if (!std::strcmp(name, "label_order"))      { *value = label_order(c) ? 1 : 0; return SELHIP_OK; }
     if (!std::strcmp(name, "join_tile_rows"))   { *value = join_tile_rows(c); return SELHIP_OK; }
     if (!std::strcmp(name, "join_form_used"))   { *value = c->join_form_used; return SELHIP_OK; }      // kernel FORM of the last LDS-tile join (3 = bit-sliced)
@@ -274,14 +281,19 @@ static int validate_shape(selhip_ctx* c, int64_t n, int m, int p) {
 
 static int after_sketches(selhip_ctx* c, const double* cards_src, bool cards_on_host) {
     // cards: given or computed with the device estimator
-    c->hll_khi = 0;
+    c->hll_khi = 0; c->hll_sparse_t = 0;
     if (c->n == 0) return SELHIP_OK;
     if (c->p == 14 && c->hist_algo != 0) {
         // the registers once more as bit planes: what stage 2a reads (12 KiB per genome; the byte rows stay for report() and the callers)
         HIPCHK(&c->err, c->hll_bs.ensure((size_t)c->n * kBsGenomeDwords));
         HIPCHK(&c->err, c->hll_bs_max.ensure(1));
         HIPCHK(&c->err, c->hll_gmax.ensure((size_t)c->n));
-        const int rc = build_bitslices(&c->err, c->stream, c->d_hll, c->n, c->hll_bs.p, c->hll_gmax.p, c->hll_bs_max.p, &c->hll_khi);
+        int rc = build_bitslices(&c->err, c->stream, c->d_hll, c->n, c->hll_bs.p, c->hll_gmax.p, c->hll_bs_max.p, &c->hll_khi);
+        if (rc) return rc;
+        // the rare high registers once more as sparse lists (512 B per genome), whatever "hist_sparse" is now: it may change before a pass
+        HIPCHK(&c->err, c->hll_sparse.ensure((size_t)c->n * kBsSparseCap));
+        HIPCHK(&c->err, c->hll_sparse_dev_t.ensure(1));
+        rc = build_sparse_lists(&c->err, c->stream, c->hll_bs.p, c->n, c->hll_sparse.p, c->hll_sparse_dev_t.p, &c->hll_sparse_t);
         if (rc) return rc;
     }
     if (!cards_src) {

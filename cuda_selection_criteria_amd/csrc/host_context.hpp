@@ -128,6 +128,12 @@ struct selhip_ctx {
     DevBuf<uint8_t> hll_gmax;           // [n] largest register value of each genome
     DevBuf<int> hll_bs_max;             // largest register value of the set (device side)
     int hll_khi = 0;                    // 0 = no planes; else max register value + 1
+    // sparse lists of every genome's registers >= hll_sparse_t ([n][kBsSparseCap], written with the planes): stage 2a decodes only the
+    // values below the threshold from the planes.  hll_sparse_t = 0: no lists (the set needs a threshold above kBsSparseMaxT)
+    DevBuf<uint32_t> hll_sparse;
+    DevBuf<int> hll_sparse_dev_t;
+    int hll_sparse_t = 0;
+    int hist_sparse = -1;               // "hist_sparse": -1 automatic (sparse_t_used), 1 = use the lists where the set has them, 0 = every value from the planes
     int hist_algo = -1;                 // -1 automatic (bit planes when p = 14), 0 = byte rows + LDS histogram (hll_union_hist_runs_kernel), 1 = bit planes
     int hist_dense_degree = 32;         // bit-plane kernel: survivors per query row from which a grouped list is walked by candidate slice per XCD (-1 = never)
     int hist_bs_blocks = 2048;          // bit-plane kernel: 4-wave blocks (multiple of 8)

@@ -325,15 +325,59 @@ unsigned grid_for(u64 items, unsigned per_block, unsigned max_blocks) {
 }
 
 // ---- stage 2a on bit planes (kernel_hllbs.cuh) -------------------------------------------------
-// the instantiation for a set whose largest register value is khi - 1 = the number of bit planes that can be non-zero
-hipError_t launch_hist_bs(int khi, unsigned blocks, hipStream_t st, const uint32_t* bs, const uint8_t* gmax, const selhip_int2_t* list, const u64* count,
-                          u64 cap, uint32_t* counts, u64 off, u64 window, int run, u64 dense_pairs) {
-#define SELHIP_BS_LAUNCH(NB) hipLaunchKernelGGL((hll_union_hist_bs_kernel<NB>), dim3(blocks), dim3(kBlock), 0, st, bs, gmax, list, count, cap, counts, off, window, run, dense_pairs)
-    if (khi <= 16)      SELHIP_BS_LAUNCH(4);
-    else if (khi <= 32) SELHIP_BS_LAUNCH(5);
-    else                SELHIP_BS_LAUNCH(6);
+// the instantiation for a set whose largest register value is khi - 1 = the number of bit planes that can be non-zero; sparse_t = 0:
+// every value decoded from the planes, else the set's sparse threshold (a multiple of 4 in [4, kBsSparseMaxT]) with its lists
+template <int NB>
+void launch_hist_bs_nb(int g1, unsigned blocks, hipStream_t st, const uint32_t* bs, const uint8_t* gmax, const uint32_t* lists, const selhip_int2_t* list,
+                       const u64* count, u64 cap, uint32_t* counts, u64 off, u64 window, int run, u64 dense_pairs) {
+#define SELHIP_BS_LAUNCH(G1) hipLaunchKernelGGL((hll_union_hist_bs_kernel<NB, G1>), dim3(blocks), dim3(kBlock), 0, st, bs, gmax, lists, list, count, cap, \
+                                                counts, off, window, run, dense_pairs)
+    switch (g1) {
+        case 1: SELHIP_BS_LAUNCH(1); return;
+        case 2: SELHIP_BS_LAUNCH(2); return;
+        case 3: SELHIP_BS_LAUNCH(3); return;
+    }
+    // (four planes hold values < 16: a threshold of 16 or more leaves every list empty.  With five planes G1 = 6 would spill -- 128
+    //  VGPRs and scratch -- where the sparse form saves no more than the full decode's walks above 24: that set keeps the full decode)
+    if constexpr (NB > 4) {
+        switch (g1) {
+            case 4: SELHIP_BS_LAUNCH(4); return;
+            case 5: SELHIP_BS_LAUNCH(5); return;
+        }
+    }
+    if constexpr (NB > 5) {
+        if (g1 == 6) { SELHIP_BS_LAUNCH(6); return; }
+    }
+    SELHIP_BS_LAUNCH(0);
 #undef SELHIP_BS_LAUNCH
+}
+hipError_t launch_hist_bs(int khi, unsigned blocks, hipStream_t st, const uint32_t* bs, const uint8_t* gmax, const selhip_int2_t* list, const u64* count,
+                          u64 cap, uint32_t* counts, u64 off, u64 window, int run, u64 dense_pairs, int sparse_t = 0, const uint32_t* lists = nullptr) {
+    // (a threshold at or above khi leaves every list empty: there the full decode's per-pair walks already stop below it)
+    const int g1 = sparse_t > 0 && sparse_t < khi && lists ? sparse_t / 4 : 0;
+    if (khi <= 16)      launch_hist_bs_nb<4>(g1, blocks, st, bs, gmax, lists, list, count, cap, counts, off, window, run, dense_pairs);
+    else if (khi <= 32) launch_hist_bs_nb<5>(g1, blocks, st, bs, gmax, lists, list, count, cap, counts, off, window, run, dense_pairs);
+    else                launch_hist_bs_nb<6>(g1, blocks, st, bs, gmax, lists, list, count, cap, counts, off, window, run, dense_pairs);
     return hipGetLastError();
+}
+
+// the sparse lists of n genomes from their planes (kernel_hllbs.cuh); *t = the set's threshold, 0 when it would exceed kBsSparseMaxT
+// (nothing written then).  Waits for the stream.
+int build_sparse_lists(std::string* err, hipStream_t st, const uint32_t* d_bs, int64_t n, uint32_t* d_lists, int* d_t, int* t) {
+    *t = 0;
+    if (n <= 0) return SELHIP_OK;
+    HIPCHK(err, hipMemsetAsync(d_t, 0, sizeof(int), st));
+    hipLaunchKernelGGL(hll_sparse_t_kernel, dim3(grid_for((u64)n, kWavesPerBlock, 8192)), dim3(kBlock), 0, st, d_bs, (long long)n, d_t);
+    HIPCHK(err, hipGetLastError());
+    int need = 0;
+    HIPCHK(err, hipMemcpyAsync(&need, d_t, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(err, hipStreamSynchronize(st));
+    if (need < 4 || need > kBsSparseMaxT) return SELHIP_OK;
+    hipLaunchKernelGGL(hll_sparse_list_kernel, dim3(grid_for((u64)n, kWavesPerBlock, 8192)), dim3(kBlock), 0, st, d_bs, (long long)n, need, d_lists);
+    HIPCHK(err, hipGetLastError());
+    HIPCHK(err, hipStreamSynchronize(st));
+    *t = need;
+    return SELHIP_OK;
 }
 
 // writes the bit planes of n genomes and returns max register value + 1 through *khi (waits for the stream)
@@ -349,6 +393,17 @@ int build_bitslices(std::string* err, hipStream_t st, const uint8_t* d_hll, int6
 }
 
 bool use_bitslices(const selhip_ctx* c) { return c->p == 14 && c->hll_khi > 0 && c->hist_algo != 0; }
+// the all-pairs stage 2a's sparse threshold in use (0 = every value from the planes)
+// Automatic ("hist_sparse" = -1): only where the set's planes fit the Infinity Cache.  Beyond it the kernel is bound by its fetches of
+// candidate rows, not by instructions: cfg4 (50 000 genomes, 600 MB of planes) 144.5 -> 146.8 us, its step 1.502 -> 1.515 ms with the
+// lists (profiles/hist_sparse_ab.txt), while cfg3 and --hard gain 6 % and 23 % a step.
+constexpr size_t kSparseMaxPlaneBytes = (size_t)192 << 20;
+int sparse_t_used(const selhip_ctx* c) {
+    if (!use_bitslices(c) || !c->hist_sparse || c->hll_sparse_t >= c->hll_khi) return 0;
+    if (c->hist_sparse < 0 && (size_t)c->n * kBsGenomeDwords * sizeof(uint32_t) > kSparseMaxPlaneBytes) return 0;
+    if (c->hll_sparse_t > 20 && c->hll_khi <= 32) return 0;                                   // (launch_hist_bs_nb: five planes, G1 = 6)
+    return c->hll_sparse_t;
+}
 
 int compute_cards(selhip_ctx* c, const uint8_t* d_hll, int64_t n, int p, double* d_out) {
     if (n <= 0) return SELHIP_OK;
@@ -535,7 +590,8 @@ int enqueue_tail(selhip_ctx* c, const Chain& ch, const selhip_int2_t* final_list
                                                // ("dense" = survivors per QUERY ROW of this chain: a rank's or a lane's share of the rows sees
                                                //  its share of the pairs and all of the candidate rows)
                                                grouped && c->hist_dense_degree >= 0
-                                                   ? (u64)c->hist_dense_degree * (u64)std::max<long long>(1, ((long long)ch.re - ch.rb) / std::max(1, c->il_parts)) : ~0ull));
+                                                   ? (u64)c->hist_dense_degree * (u64)std::max<long long>(1, ((long long)ch.re - ch.rb) / std::max(1, c->il_parts)) : ~0ull,
+                                               sparse_t_used(c), c->hll_sparse.p));
             else if (c->p == 14)
                 hipLaunchKernelGGL(hll_union_hist_runs_kernel, dim3(c->hist_blocks), dim3(kWave), (size_t)c->hist_pad, st,
                                    c->d_hll, final_list, final_count, final_cap, ch.counts, off, ch.window,

@@ -63,6 +63,95 @@ void hll_bitslice_kernel(const uint8_t* __restrict__ hll, long long n, uint32_t*
     if (lane == 0 && mx_all) atomicMax(max_val, (int)mx_all);
 }
 
+// ---- sparse lists of the rare high registers (stage 2a's "hist_sparse") --------------------------------------------------------
+// A set's registers crowd the low values: at cfg3 a genome holds 58-68 of its 16 384 registers at 12 or more, and none above ~20.
+// The bit-parallel decode costs the same for every group of four values however few registers it holds, so the groups from a
+// threshold T up are taken out of it: every genome also keeps its registers >= T as a SORTED list of kBsSparseCap entries
+// (r' << 8 | value, r' = 32 * plane dword + bit: the register's place in the planes; padded with kBsSparseNone), and stage 2a decodes
+// only the values below T bit-parallel.  T = the smallest multiple of 4 at which every genome of the set holds at most
+// kBsSparseCap such registers; above kBsSparseMaxT the set keeps the full decode.
+constexpr int kBsSparseCap = 128;
+constexpr int kBsSparseMaxT = 24;
+constexpr uint32_t kBsSparseNone = 0xFFFFFFFFu;
+
+// registers (one bit each) of a plane dword whose value is >= 4 k, from the planes 2..5 (a borrow chain of (v >> 2) - k; k wave-uniform)
+__device__ __forceinline__ uint32_t bs_ge4k(const uint32_t (&p)[kBsPlanes], int k) {
+    uint32_t borrow = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) borrow = ((k >> i) & 1) ? (~p[2 + i] | borrow) : (~p[2 + i] & borrow);
+    return ~borrow;
+}
+
+// hll_sparse_t_kernel: one wave per genome; *t_need = max over the genomes of the smallest 4 k (1 <= k <= 6) with at most
+// kBsSparseCap registers >= 4 k -- kBsSparseMaxT + 4 where even 24 leaves more.
+__global__ __launch_bounds__(kBlock)
+void hll_sparse_t_kernel(const uint32_t* __restrict__ bs, long long n, int* __restrict__ t_need) {
+    const int lane = threadIdx.x & (kWave - 1);
+    int t_all = 0;
+    for (long long g = (long long)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave; g < n; g += (long long)gridDim.x * kWavesPerBlock) {
+        const uint32_t* src = bs + g * kBsGenomeDwords;
+        int cnt[6] = {0, 0, 0, 0, 0, 0};
+#pragma unroll 1
+        for (int o = 0; o < kBsPlaneDwords / kWave; ++o) {
+            uint32_t p[kBsPlanes];
+#pragma unroll
+            for (int b = 0; b < kBsPlanes; ++b) p[b] = src[b * kBsPlaneDwords + o * kWave + lane];
+#pragma unroll
+            for (int k = 1; k <= 6; ++k) cnt[k - 1] += __popc(bs_ge4k(p, k));
+        }
+        int t = kBsSparseMaxT + 4;
+#pragma unroll
+        for (int k = 6; k >= 1; --k) {
+            int s = cnt[k - 1];
+#pragma unroll
+            for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d, kWave);
+            if (s <= kBsSparseCap) t = 4 * k;
+        }
+        t_all = max(t_all, t);
+    }
+    if (lane == 0 && t_all) atomicMax(t_need, t_all);
+}
+
+// hll_sparse_list_kernel: one wave per genome, its registers >= t (a multiple of 4 in [4, kBsSparseMaxT]) in ascending r', read from
+// the planes 64 dwords at a time: each lane's count, a wave prefix sum for the offsets, the lane's entries in bit order.
+__global__ __launch_bounds__(kBlock)
+void hll_sparse_list_kernel(const uint32_t* __restrict__ bs, long long n, int t, uint32_t* __restrict__ lists) {
+    const int lane = threadIdx.x & (kWave - 1);
+    for (long long g = (long long)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave; g < n; g += (long long)gridDim.x * kWavesPerBlock) {
+        const uint32_t* src = bs + g * kBsGenomeDwords;
+        uint32_t* dst = lists + g * kBsSparseCap;
+        int base = 0;
+#pragma unroll 1
+        for (int o = 0; o < kBsPlaneDwords / kWave; ++o) {
+            const int d = o * kWave + lane;
+            uint32_t p[kBsPlanes];
+#pragma unroll
+            for (int b = 0; b < kBsPlanes; ++b) p[b] = src[b * kBsPlaneDwords + d];
+            uint32_t h = bs_ge4k(p, t >> 2);
+            const int cnt = __popc(h);
+            int incl = cnt;
+#pragma unroll
+            for (int s = 1; s < kWave; s <<= 1) {
+                const int v = __shfl_up(incl, s, kWave);
+                if (lane >= s) incl += v;
+            }
+            int off = base + incl - cnt;
+            while (h) {
+                const int j = __builtin_ctz(h);
+                h &= h - 1;
+                uint32_t v = 0;
+#pragma unroll
+                for (int b = 0; b < kBsPlanes; ++b) v |= ((p[b] >> j) & 1u) << b;
+                if (off < kBsSparseCap) dst[off] = ((uint32_t)(d * 32 + j) << 8) | v;
+                ++off;
+            }
+            base += __shfl(incl, kWave - 1, kWave);
+        }
+        for (int i = lane; i < kBsSparseCap; i += kWave)
+            if (i >= base) dst[i] = kBsSparseNone;
+    }
+}
+
 // the lane's 8 dwords of each of the NB low planes of genome g (two 16-byte loads per plane, 1 KiB per wave instruction)
 template <int NB>
 __device__ __forceinline__ void bs_load(const uint32_t* __restrict__ bs, int g, int lane, uint32_t (&r)[NB][8]) {
@@ -156,23 +245,30 @@ constexpr int kDppRowMirror = 0x140, kDppRowHalfMirror = 0x141, kDppQuad3210 = 0
 // Each step exchanges half of the values a lane still carries for the partner's copies of the other half and adds:
 //   v_permlane32_swap (lanes 32-63 of a <-> lanes 0-31 of b), v_permlane16_swap (odd rows of a <-> even rows of b),
 //   then inside a row of 16 lanes: DPP row_mirror / row_half_mirror / quad_perm with a select per pair of values.
+// NV: only P[0, NV) can be non-zero (the sparse kernel decodes 2 G1 packed values); the steps on values known to be zero are left out.
+template <int NV = 16>
 __device__ __forceinline__ uint32_t bs_reduce16(const uint32_t (&P)[16], int lane) {
     uint32_t Q[8], R[4];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
+        if (2 * j >= NV) { Q[j] = 0u; continue; }
         const auto s = __builtin_amdgcn_permlane32_swap(P[2 * j], P[2 * j + 1], false, false);
         Q[j] = s[0] + s[1];                 // lanes 0-31: P[2j] over {i, i+32}; lanes 32-63: P[2j+1]
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
+        if (4 * j >= NV) { R[j] = 0u; continue; }
         const auto s = __builtin_amdgcn_permlane16_swap(Q[2 * j], Q[2 * j + 1], false, false);
         R[j] = s[0] + s[1];                 // rows 0..3: P[4j], P[4j+2], P[4j+1], P[4j+3], each over 4 source lanes per lane
     }
     const bool h = (lane & 8) != 0, q = (lane & 4) != 0;
-    const uint32_t t0 = R[0] + bs_dpp<kDppRowMirror>(R[0]), t1 = R[1] + bs_dpp<kDppRowMirror>(R[1]);
-    const uint32_t t2 = R[2] + bs_dpp<kDppRowMirror>(R[2]), t3 = R[3] + bs_dpp<kDppRowMirror>(R[3]);
+    const uint32_t t0 = R[0] + bs_dpp<kDppRowMirror>(R[0]);
+    const uint32_t t1 = NV > 4 ? R[1] + bs_dpp<kDppRowMirror>(R[1]) : 0u;
+    const uint32_t t2 = NV > 8 ? R[2] + bs_dpp<kDppRowMirror>(R[2]) : 0u;
+    const uint32_t t3 = NV > 12 ? R[3] + bs_dpp<kDppRowMirror>(R[3]) : 0u;
     const uint32_t S0 = h ? t1 : t0, S1 = h ? t3 : t2;
-    const uint32_t u0 = S0 + bs_dpp<kDppRowHalfMirror>(S0), u1 = S1 + bs_dpp<kDppRowHalfMirror>(S1);
+    const uint32_t u0 = S0 + bs_dpp<kDppRowHalfMirror>(S0);
+    const uint32_t u1 = NV > 8 ? S1 + bs_dpp<kDppRowHalfMirror>(S1) : 0u;
     const uint32_t U = q ? u1 : u0;
     const uint32_t V = U + bs_dpp<kDppQuad3210>(U);
     return V + bs_dpp<kDppQuad1032>(V);
@@ -223,15 +319,84 @@ __device__ __forceinline__ uint32_t bs_pair_hist(const uint32_t (&xa)[NB][8], co
     return tot;
 }
 
-// hll_union_hist_bs_kernel<NB>: same contract as hll_union_hist_runs_kernel (window [chunk_off, chunk_off + chunk_len) of the
+// ---- the values >= T of a pair from the two rows' sparse lists (A = query row x, B = candidate row y) ---------------------------
+// A register r with M_r = max(a_r, b_r) >= T is in A or in B.  The query row's histogram of A (hA: lane L keeps the bin it stores)
+// counts every r of A at a_r; each entry of B then corrects it: r not in A adds b_r; r in A with b_r > a_r moves one count from a_r to
+// b_r; r in A with b_r <= a_r changes nothing.  Membership and a_r come from a wave-private LDS image of A, built once per query row:
+// a bitmap of its r' (512 dwords), the rank of the first entry of every dword that holds one, and the values by rank -- an entry's
+// rank is first[w] + |bits[w] below it|.  Exact (no hashing, so no collisions), two dependent LDS reads per entry of B.
+struct alignas(16) BsSparseLds {
+    uint32_t bits[kBsPlaneDwords];      // A's registers, one bit each at r'
+    uint32_t bins[64];                  // the pair's corrections by value (zero between pairs; the lane storing bin v reads and clears it)
+    uint8_t first[kBsPlaneDwords];      // rank of the first entry of A in each dword of bits that holds one
+    uint8_t val[kBsSparseCap];          // A's values by rank
+};
+
+// the query row x's image in sp and its histogram hA (the bin my_bin); every lane of the wave takes part
+__device__ __forceinline__ uint32_t bs_sparse_row(BsSparseLds* sp, const uint32_t* __restrict__ lists, int x, int lane, int my_bin) {
+    const uint32_t e0 = lists[(size_t)x * kBsSparseCap + lane], e1 = lists[(size_t)x * kBsSparseCap + kWave + lane];
+    uint4* bits4 = reinterpret_cast<uint4*>(sp->bits);
+    bits4[2 * lane] = make_uint4(0u, 0u, 0u, 0u);
+    bits4[2 * lane + 1] = make_uint4(0u, 0u, 0u, 0u);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const uint32_t e = h ? e1 : e0;
+        if (e != kBsSparseNone) {
+            const uint32_t r = e >> 8;
+            atomicOr(&sp->bits[r >> 5], 1u << (r & 31));
+            atomicAdd(&sp->bins[e & 63], 1u);
+            sp->val[h * kWave + lane] = (uint8_t)(e & 63);
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const uint32_t e = h ? e1 : e0;
+        if (e != kBsSparseNone) {
+            const uint32_t r = e >> 8;
+            // every entry of a dword writes the same rank
+            sp->first[r >> 5] = (uint8_t)(h * kWave + lane - __popc(sp->bits[r >> 5] & ((1u << (r & 31)) - 1u)));
+        }
+    }
+    const uint32_t hA = sp->bins[my_bin];
+    sp->bins[my_bin] = 0u;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    return hA;
+}
+
+// one entry of B against the image of A
+__device__ __forceinline__ void bs_sparse_entry(BsSparseLds* sp, uint32_t e) {
+    if (e == kBsSparseNone) return;
+    const uint32_t r = e >> 8, v = e & 63, w = sp->bits[r >> 5], below = w & ((1u << (r & 31)) - 1u);
+    if ((w >> (r & 31)) & 1u) {
+        const uint32_t av = sp->val[sp->first[r >> 5] + __popc(below)];
+        if (v > av) {
+            atomicAdd(&sp->bins[v], 1u);
+            atomicSub(&sp->bins[av], 1u);
+        }
+    } else {
+        atomicAdd(&sp->bins[v], 1u);
+    }
+}
+
+// hll_union_hist_bs_kernel<NB, G1>: same contract as hll_union_hist_runs_kernel (window [chunk_off, chunk_off + chunk_len) of the
 // pair list, counts indexed from the window start, tasks of run_len (at most 64) consecutive pairs, block b works in the (b % 8)-th eighth of
-// the tasks = on XCD b % 8), on the bit planes.  NB = planes that can be non-zero in the SET (4, 5 or 6); how many values are
-// decoded is decided PER PAIR from the two rows' largest register values (gmax, written with the planes).
+// the tasks = on XCD b % 8), on the bit planes.  NB = planes that can be non-zero in the SET (4, 5 or 6).
+// G1 = 0: how many values are decoded is decided PER PAIR from the two rows' largest register values (gmax, written with the planes).
+// G1 > 0 (the set's sparse threshold T = 4 G1, `lists` its sparse lists): the groups [0, G1) are decoded bit-parallel, in one walk,
+// and every value >= T comes from the lists (bs_sparse_row / bs_sparse_entry); gmax is not read.
 // One wave per pair: a lane owns 8 dwords (256 registers) of every plane; the query row's planes stay in registers across a run.
-template <int NB>
+template <int NB, int G1>
 __global__ __launch_bounds__(kBlock, NB <= 5 ? 4 : 2)
-void hll_union_hist_bs_kernel(const uint32_t* __restrict__ bs, const uint8_t* __restrict__ gmax, const selhip_int2_t* __restrict__ pairs,
-                              const u64* __restrict__ n_pairs_dev, u64 cap, uint32_t* __restrict__ counts,
+void hll_union_hist_bs_kernel(const uint32_t* __restrict__ bs, const uint8_t* __restrict__ gmax, const uint32_t* __restrict__ lists,
+                              const selhip_int2_t* __restrict__ pairs, const u64* __restrict__ n_pairs_dev, u64 cap, uint32_t* __restrict__ counts,
                               u64 chunk_off, u64 chunk_len, int run_len, u64 dense_pairs) {
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = threadIdx.x / kWave;
@@ -279,6 +444,13 @@ void hll_union_hist_bs_kernel(const uint32_t* __restrict__ bs, const uint8_t* __
     const u64 t_begin = dense ? 0 : (u64)xcd * tasks_per_xcd, t_end = min(t_begin + tasks_per_xcd, n_tasks);
     int cur_x = -1;
     uint32_t xa[NB][8];
+    BsSparseLds* sp = nullptr;
+    uint32_t hA = 0;                                                      // G1 > 0: the query row's count of bin my_bin over its list
+    if constexpr (G1 > 0) {
+        __shared__ BsSparseLds sp_block[kWavesPerBlock];
+        sp = &sp_block[wave];
+        sp->bins[my_bin] = 0u;
+    }
     for (u64 task = t_begin + (u64)(blockIdx.x >> 3) * kWavesPerBlock + wave; task < t_end; task += stride) {
         const u64 j0 = task * run_len;
         const int cnt = (int)min((u64)run_len, n_pairs - j0);
@@ -291,10 +463,30 @@ void hll_union_hist_bs_kernel(const uint32_t* __restrict__ bs, const uint8_t* __
             const int px = __builtin_amdgcn_readlane(pr.x, src), py = __builtin_amdgcn_readlane(pr.y, src);   // wave-uniform: scalar row addresses
             uint32_t yb[NB][8];
             bs_load<NB>(bs, py, lane, yb);
-            if (px != cur_x) { bs_load<NB>(bs, px, lane, xa); cur_x = px; }
-            const int kp = max((int)gmax[px], (int)gmax[py]) + 1;         // values this pair can hold: [0, kp)
-            const uint32_t tot = bs_pair_hist<NB>(xa, yb, kp, lane);
-            counts[(j0 + src) * 64 + my_bin] = (lane & 1) ? (tot >> 16) : (tot & 0xFFFFu);
+            if constexpr (G1 == 0) {
+                if (px != cur_x) { bs_load<NB>(bs, px, lane, xa); cur_x = px; }
+                const int kp = max((int)gmax[px], (int)gmax[py]) + 1;     // values this pair can hold: [0, kp)
+                const uint32_t tot = bs_pair_hist<NB>(xa, yb, kp, lane);
+                counts[(j0 + src) * 64 + my_bin] = (lane & 1) ? (tot >> 16) : (tot & 0xFFFFu);
+            } else {
+                const uint32_t eb0 = lists[(size_t)py * kBsSparseCap + lane], eb1 = lists[(size_t)py * kBsSparseCap + kWave + lane];
+                if (px != cur_x) { bs_load<NB>(bs, px, lane, xa); hA = bs_sparse_row(sp, lists, px, lane, my_bin); cur_x = px; }
+                uint32_t P[16];
+#pragma unroll
+                for (int v = 0; v < 16; ++v) P[v] = 0u;
+                bs_decode<NB, 0, G1, 16>(xa, yb, P);
+                const uint32_t tot = bs_reduce16<2 * G1>(P, lane);
+                bs_sparse_entry(sp, eb0);
+                bs_sparse_entry(sp, eb1);
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                const uint32_t s = sp->bins[my_bin];
+                sp->bins[my_bin] = 0u;
+                // (bins >= 32 hold nothing dense: the lanes with lane & 2 store the sparse counts alone)
+                const uint32_t dense_cnt = (lane & 2) ? 0u : ((lane & 1) ? (tot >> 16) : (tot & 0xFFFFu));
+                counts[(j0 + src) * 64 + my_bin] = dense_cnt + hA + s;
+            }
         }
     }
 }

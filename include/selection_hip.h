@@ -171,6 +171,12 @@ int selhip_ctx_set_candidate_begin(selhip_ctx* ctx, int64_t k_min);
  *                 candidate rows instead of streaming all of them (a dense survivor graph; bench.py --hard: 6.2 -> 1.5 GB per pass from beyond L2,
  *                 DESIGN.md section 4.3);
  *   "hist_blocks" one-wave blocks of the byte-row kernel, "hist_bs_blocks" four-wave blocks of the bit-plane kernel (multiples of 8);
+ *   "hist_sparse" 1: the all-pairs bit-plane kernel decodes only the values below the set's sparse threshold T from the planes and
+ *                 takes every register >= T from sorted per-genome lists written with the planes (T = the smallest multiple of 4 at which
+ *                 every genome holds at most 128 such registers; none above 24); 0: every value from the planes; -1 (default): 1 for sets
+ *                 whose bit planes take at most 192 MiB (beyond, stage 2a is bound by its row fetches), else 0.  Same counts either way;
+ *                 selhip_ctx_get_param "hist_sparse_t" reports the T in use (0 = off).  Query passes and the one-launch small pass
+ *                 always decode every value from the planes;
  *   "small_pass"  -1 (default) / 1: a set of up to 2 048 genomes with criterion smh_a takes its whole pass in ONE launch
  *                 (small_pass_kernel: bounds + signatures, a grid barrier, then join, verification, union histograms and estimator
  *                 inside each block; the barrier's wait is bounded and a pass that runs out of patience is repeated on the regular path);
@@ -187,7 +193,8 @@ int selhip_ctx_set_param(selhip_ctx* ctx, const char* name, int value);
 /* what the context decided (read-only): "hll_khi" (largest p = 14 register value + 1; 0 = no bit planes), "hist_bitplanes",
  * "label_order", "join_tile_rows", "join_form_used" (kernel form of the last LDS-tile join: 0 packed minimum, 1 15-bit, 2 zero-half,
  * 3 bit-sliced; -1 none or the DPP join), "chunks" (chunk lanes of the last pass), "small_pass_used" (the last pass was the one-launch small pass),
- * "query_db_sig_builds" (builds of the database's band signatures by query passes since the database was loaded, section 2b) */
+ * "query_db_sig_builds" (builds of the database's band signatures by query passes since the database was loaded, section 2b),
+ * "hist_sparse_t" (the sparse threshold the all-pairs stage 2a uses, 0 = every value from the bit planes) */
 int selhip_ctx_get_param(const selhip_ctx* ctx, const char* name, int* value);
 /* Stage 2 grouping (default on): the pairs that reach the HLL-14 stage are bucketed by query row (counting sort) so
  * that waves running side by side on one XCD share their query row in L2.  0 = off (same kernel, list as produced). */
