@@ -100,8 +100,10 @@ int selhip_ctx_set_row_interleave(selhip_ctx* c, int block_rows, int n_parts, in
 //   "sig_tile_g"       genomes per tile of the tiled signature build (8 / 16 / 32; 16 is the measured optimum)
 //   "hist_pad"         extra LDS bytes per block of the byte-row stage-2a kernel (lowers the resident waves per CU)
 //   "query_join_tile"  queries per block of the query passes' signature join (16, the default, or 32)
+//   "query_index_dir"  ALGO_INDEX: 1 (default) the probe starts from the index's bucket directory, 0 it searches the whole band segment
 int selhip_ctx_set_param(selhip_ctx* c, const char* name, int value) {
     if (!c || !name) return SELHIP_E_BADARG;
+    if (!std::strcmp(name, "query_index_dir")) { c->query_index_dir = value != 0; return SELHIP_OK; }
     if (!std::strcmp(name, "join_qt")) {
         if (value != 0 && (value < 16 || value > 4096 || value % 16)) { set_err(&c->err, "join_qt must be 0 (automatic) or a multiple of 16 in [16, 4096]"); return SELHIP_E_BADARG; }
         c->join_qt = value;
@@ -226,6 +228,13 @@ int selhip_ctx_get_param(const selhip_ctx* c, const char* name, int* value) {
     if (!std::strcmp(name, "chunks"))           { *value = c->n_chunks_last; return SELHIP_OK; }
     if (!std::strcmp(name, "small_pass_used"))  { *value = c->small_used ? 1 : 0; return SELHIP_OK; }
     if (!std::strcmp(name, "query_db_sig_builds")) { *value = c->q.db_sig_builds; return SELHIP_OK; }   // database signature builds of the query passes
+    if (!std::strcmp(name, "query_db_index_builds")) { *value = c->q.db_idx_builds; return SELHIP_OK; } // builds of ALGO_INDEX's sorted signature index
+    if (!std::strcmp(name, "query_db_index_kib")) {                                                     // its resident size (0 = none held)
+        const auto& q = c->q;
+        const long long words = !q.db_idx_key ? 0 : (2ll * c->n + query_index_dir_stride(q.db_idx_dir_bits)) * q.db_idx_bands;
+        *value = (int)std::min<long long>(0x7FFFFFFF, (words * 4 + 1023) / 1024);
+        return SELHIP_OK;
+    }
     return SELHIP_E_BADARG;
 }
 

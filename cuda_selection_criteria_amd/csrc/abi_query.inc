@@ -137,11 +137,11 @@ int selhip_ctx_run_queries(selhip_ctx* c, int mode, int algo, float tau_f, int n
         }
     }
     const bool smh = query_smh_stage(c);
-    if (algo != SELHIP_ALGO_AUTO && algo != SELHIP_ALGO_STREAM && algo != SELHIP_ALGO_SIG && algo != SELHIP_ALGO_HASHJOIN) { set_err(&c->err, "bad algo %d", algo); return SELHIP_E_BADARG; }
-    bool use_sig = false;
+    if (algo != SELHIP_ALGO_AUTO && algo != SELHIP_ALGO_STREAM && algo != SELHIP_ALGO_SIG && algo != SELHIP_ALGO_HASHJOIN && algo != SELHIP_ALGO_INDEX) { set_err(&c->err, "bad algo %d", algo); return SELHIP_E_BADARG; }
+    bool use_sig = false, use_index = false;
     if (smh) {
         // (hll_a / hll_an alone read neither n_rows / n_bands nor algo, as in selhip_ctx_run_async)
-        if (algo == SELHIP_ALGO_HASHJOIN) { set_err(&c->err, "query passes have no ALGO_HASHJOIN; use AUTO, SIG or STREAM"); return SELHIP_E_BADARG; }
+        if (algo == SELHIP_ALGO_HASHJOIN) { set_err(&c->err, "query passes have no ALGO_HASHJOIN; use AUTO, SIG, STREAM or INDEX"); return SELHIP_E_BADARG; }
         if (n_rows <= 0 || n_bands <= 0 || (long long)n_rows * n_bands != c->m) {
             set_err(&c->err, "n_rows*n_bands (%d*%d) != m (%d)", n_rows, n_bands, c->m);
             return SELHIP_E_BADARG;
@@ -151,7 +151,12 @@ int selhip_ctx_run_queries(selhip_ctx* c, int mode, int algo, float tau_f, int n
             set_err(&c->err, "ALGO_SIG needs power-of-two rows and 8..128 bands (got %d x %d)", n_rows, n_bands);
             return SELHIP_E_BADARG;
         }
+        if (algo == SELHIP_ALGO_INDEX && !sig_ok) {             // (no fallback: the caller asked for the index)
+            set_err(&c->err, "ALGO_INDEX needs power-of-two rows and 8..128 bands (got %d x %d)", n_rows, n_bands);
+            return SELHIP_E_BADARG;
+        }
         use_sig = algo != SELHIP_ALGO_STREAM && sig_ok;
+        use_index = algo == SELHIP_ALGO_INDEX;
         if (!use_sig && query_stream_tile(c->m) == 0) { set_err(&c->err, "ALGO_STREAM of a query pass holds m <= 4096 buckets (m = %d)", c->m); return SELHIP_E_BADARG; }
     }
     HIPCHK(&c->err, hipSetDevice(c->device));
@@ -167,7 +172,7 @@ int selhip_ctx_run_queries(selhip_ctx* c, int mode, int algo, float tau_f, int n
     const double tau = (double)tau_f;                 // float threshold widened, selection.cpp:81,164
     for (int attempt = 0; attempt < 8; ++attempt) {
         int rc = ensure_query_scratch(c, cap, res_cap);
-        if (!rc) rc = enqueue_query_pass(c, use_sig, tau);
+        if (!rc) rc = enqueue_query_pass(c, use_sig, use_index, tau);
         if (rc) return rc;
         HIPCHK(&c->err, wait_stream(c->stream));
         const PassCounters pc = *q.h_pc;

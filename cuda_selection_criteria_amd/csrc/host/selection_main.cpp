@@ -12,7 +12,8 @@
 //   -t <n>      host threads for loading sketches (selection.cpp:97)
 //   -g <n>      number of GPUs to shard the pair space over (default 1; any criterion); selected pairs gathered over RCCL/xGMI
 //   -n          no CB pruning ("smh_a" mode of experiments/src/time_smh.cpp:229-257)
-//   -A <algo>   stage-1 algorithm: auto | stream | sig | hashjoin (sort-based: same result, sub-quadratic)
+//   -A <algo>   stage-1 algorithm: auto | stream | sig | hashjoin (sort-based: same result, sub-quadratic); with -q also
+//               index (the database's band signatures sorted once, one search per query and band; band shapes of sig)
 //   -F <0|1>    estimator flavour: 1 = FMA (reference Makefile build on FMA hosts, default), 0 = strict
 //   -B <n>      out-of-core: keep the sketches in host memory and process the pair space in blocks of n genomes
 //               (selhip_ooc_select; same output); 0 = everything resident on the device (default)
@@ -114,7 +115,7 @@ int main(int argc, char* argv[]) {
     while ((c = getopt(argc, argv, "xl:b:a:h:c:t:g:nA:F:B:o:r:q:")) != -1) {
         switch (c) {
             case 'x': std::cout << "Usage: -l -h -a -b [-c smh_a] [-t threads] [-g gpus] [-n] [-A auto|stream|sig] [-F 0|1] [-B block] [-o file] | -r file\n"
-                                   "       -l db_list -q query_list -h -a [-c smh_a|hll_a|hll_an] [-n] [-A auto|stream|sig] [-F 0|1]   (query-vs-database selection)\n"; return 0;
+                                   "       -l db_list -q query_list -h -a [-c smh_a|hll_a|hll_an] [-n] [-A auto|stream|sig|index] [-F 0|1]   (query-vs-database selection)\n"; return 0;
             case 'q': query_file = optarg; break;
             case 'B': ooc_block = std::stoll(optarg); break;
             case 'o': out_file = optarg; break;
@@ -127,7 +128,7 @@ int main(int argc, char* argv[]) {
             case 't': threads = std::stoi(optarg); break;
             case 'g': n_gpus = std::stoi(optarg); gpus_given = true; break;
             case 'n': mode = SELHIP_MODE_SMH; break;
-            case 'A': algo = !strcmp(optarg, "stream") ? SELHIP_ALGO_STREAM : !strcmp(optarg, "sig") ? SELHIP_ALGO_SIG : !strcmp(optarg, "hashjoin") ? SELHIP_ALGO_HASHJOIN : SELHIP_ALGO_AUTO; break;
+            case 'A': algo = !strcmp(optarg, "stream") ? SELHIP_ALGO_STREAM : !strcmp(optarg, "sig") ? SELHIP_ALGO_SIG : !strcmp(optarg, "hashjoin") ? SELHIP_ALGO_HASHJOIN : !strcmp(optarg, "index") ? SELHIP_ALGO_INDEX : SELHIP_ALGO_AUTO; break;
             case 'F': fp_mode = std::stoi(optarg) ? SELHIP_FP_FMA : SELHIP_FP_STRICT; break;
             default: break;
         }
@@ -146,6 +147,11 @@ int main(int argc, char* argv[]) {
         }
         if (list_file.empty()) { std::cerr << "selection: -q needs the database list (-l)\n"; return 2; }
         return run_queries(query_file, list_file, criterion, threshold, aux_bytes, mode, algo, fp_mode, threads);
+    }
+    if (algo == SELHIP_ALGO_INDEX) {
+        // checked before any file is read or device opened
+        std::cerr << "selection: -A index is an algorithm of query-vs-database selection: it needs -q (the query list)\n";
+        return 2;
     }
     if (!dump_file.empty()) {
         selhost_results* res = nullptr;

@@ -192,6 +192,14 @@ struct selhip_ctx {
         DevBuf<uint32_t> db_sigQ, db_sigT, db_sigP, db_sigG;   // D's band signatures, kept across query passes
         long long db_sig_key = 0;                   // (n_rows, n_bands, database generation) they were built for; 0 = none
         int db_sig_builds = 0;                      // builds of D's signatures since the database was loaded ("query_db_sig_builds")
+        // ALGO_INDEX (kernel_query_index.cuh): per band, D's signatures sorted ascending and the database ranks they belong to
+        // ([n_bands][n_D] each).  Buffers of its own: an all-pairs ALGO_HASHJOIN pass in between leaves it alone
+        DevBuf<uint32_t> db_idx_sig;
+        DevBuf<int> db_idx_rank;
+        DevBuf<int> db_idx_dir;                     // bucket directory: [n_bands][2^db_idx_dir_bits + 1] offsets into a band's segment
+        int db_idx_dir_bits = 0, db_idx_bands = 0;
+        long long db_idx_key = 0;                   // as db_sig_key; 0 = none
+        int db_idx_builds = 0;                      // index builds since the database was loaded ("query_db_index_builds")
         DevBuf<uint32_t> db_bs;                     // D's bit planes, only if the all-pairs path keeps none (hist_algo 0)
         DevBuf<uint8_t> db_gmax;
         long long db_bs_gen = -1;
@@ -208,6 +216,7 @@ struct selhip_ctx {
         PassCounters* h_pc = nullptr;
     } q;
     long long db_gen = 0;               // incremented by every upload / attach of the database
+    int query_index_dir = 1;            // ALGO_INDEX: the probe starts from the bucket directory (0 = searches the whole band segment; "query_index_dir")
     int query_join_tile = 16;           // queries per block of the query passes' signature join (16 or 32; "query_join_tile")
     bool last_was_query = false;        // the results / statistics held are those of a query pass (no framed copies of them)
 

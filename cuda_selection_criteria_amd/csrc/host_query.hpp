@@ -11,6 +11,8 @@ void drop_queries(selhip_ctx* c) {
     c->q.d_aux_hll = nullptr; c->q.p_aux = 0;
     c->q.db_sig_key = 0;
     c->q.db_sig_builds = 0;
+    c->q.db_idx_key = 0;
+    c->q.db_idx_builds = 0;
     c->db_gen += 1;
 }
 
@@ -20,6 +22,7 @@ void release_queries(selhip_ctx* c) {
     q.lo.release(); q.hi.release(); q.ecard.release();
     q.sigQ.release(); q.sigT.release(); q.sigP.release(); q.sigG.release();
     q.db_sigQ.release(); q.db_sigT.release(); q.db_sigP.release(); q.db_sigG.release(); q.db_bs.release(); q.db_gmax.release();
+    q.db_idx_sig.release(); q.db_idx_rank.release(); q.db_idx_dir.release();
     q.cand.release(); q.surv.release(); q.fin.release(); q.own_aux_hll.release(); q.counts.release(); q.pc.release();
     if (q.h_pc) (void)hipHostFree(q.h_pc);
     q.h_pc = nullptr;
@@ -59,6 +62,51 @@ hipError_t launch_query_hist(int khi, hipStream_t st, const uint32_t* bs_q, cons
     else                SELHIP_QH_LAUNCH(6);
 #undef SELHIP_QH_LAUNCH
     return hipGetLastError();
+}
+
+// ALGO_INDEX: the sorted index of D's band signatures from the band-major q.db_sigT (which must hold the shape (r, nb) of D).  The
+// 64-bit keys, the unsorted ranks and rocPRIM's scratch live only for the build; q.db_idx_sig / q.db_idx_rank (8 B per entry) and the
+// bucket directory (one word per 2 .. 4 entries) stay.
+int build_query_index(selhip_ctx* c, int nb) {
+    auto& q = c->q;
+    const int n_d = (int)c->n;
+    const int n_pad = ((n_d + kWave - 1) / kWave) * kWave;
+    const size_t total = (size_t)n_d * nb;
+    DevBuf<u64> keys_in, keys_out;
+    DevBuf<int> vals_in;
+    DevBuf<char> tmp;
+    int dir_bits = 0;                                          // 2^dir_bits buckets per band: 2 .. 4 entries each on average
+    while ((4ll << dir_bits) < n_d) ++dir_bits;
+    const size_t dir_words = (size_t)query_index_dir_stride(dir_bits) * nb;
+    auto build = [&]() -> int {
+        HIPCHK(&c->err, q.db_idx_dir.ensure(dir_words));
+        HIPCHK(&c->err, q.db_idx_sig.ensure(total));
+        HIPCHK(&c->err, q.db_idx_rank.ensure(total));
+        HIPCHK(&c->err, keys_in.ensure(total));
+        HIPCHK(&c->err, keys_out.ensure(total));
+        HIPCHK(&c->err, vals_in.ensure(total));
+        const unsigned end_bit = 32u + (unsigned)ilog2(nb) + 1u;
+        size_t tmp_bytes = 0;
+        HIPCHK(&c->err, rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys_in.p, keys_out.p, vals_in.p, q.db_idx_rank.p, total, 0u, end_bit, c->stream));
+        HIPCHK(&c->err, tmp.ensure(tmp_bytes + 256));
+        hipLaunchKernelGGL(sigkey_build_kernel, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream,
+                           q.db_sigT.p, n_d, n_pad, nb, keys_in.p, vals_in.p);
+        HIPCHK(&c->err, hipGetLastError());
+        tmp_bytes = tmp.cap;
+        HIPCHK(&c->err, rocprim::radix_sort_pairs(tmp.p, tmp_bytes, keys_in.p, keys_out.p, vals_in.p, q.db_idx_rank.p, total, 0u, end_bit, c->stream));
+        hipLaunchKernelGGL(query_index_pack_kernel, dim3(grid_for((u64)total, kBlock, 8192)), dim3(kBlock), 0, c->stream,
+                           keys_out.p, (long long)total, q.db_idx_sig.p);
+        HIPCHK(&c->err, hipGetLastError());
+        hipLaunchKernelGGL(query_index_dir_kernel, dim3(grid_for((u64)dir_words, kBlock, 8192)), dim3(kBlock), 0, c->stream,
+                           q.db_idx_sig.p, n_d, nb, dir_bits, q.db_idx_dir.p);
+        HIPCHK(&c->err, hipGetLastError());
+        q.db_idx_dir_bits = dir_bits; q.db_idx_bands = nb;
+        HIPCHK(&c->err, hipStreamSynchronize(c->stream));      // the build's own buffers go away below
+        return SELHIP_OK;
+    };
+    const int rc = build();
+    keys_in.release(); keys_out.release(); vals_in.release(); tmp.release();
+    return rc;
 }
 
 // the largest query tile the stream kernel stages (qt rows of m u64 in at most 32 KiB of LDS); 0 = m too large for it
@@ -105,7 +153,8 @@ hipError_t launch_query_aux(selhip_ctx* c, const selhip_int2_t* list, const u64*
 }
 
 // one query pass on the context's stream; counters land in q.h_pc (the caller waits)
-int enqueue_query_pass(selhip_ctx* c, bool use_sig, double tau) {
+// use_index (with use_sig): ALGO_INDEX -- the probe of the sorted index in place of the signature join
+int enqueue_query_pass(selhip_ctx* c, bool use_sig, bool use_index, double tau) {
     auto& q = c->q;
     const int n_q = (int)q.n, n_d = (int)c->n;
     const bool smh = query_smh_stage(c);
@@ -170,7 +219,23 @@ int enqueue_query_pass(selhip_ctx* c, bool use_sig, double tau) {
             q.db_sig_key = key;
             q.db_sig_builds += 1;
         }
-        {
+        if (use_index && q.db_idx_key != key) {
+            // the index depends on D and the band shape only, like D's signatures it is sorted from: same key, same lifetime
+            TimerScope t(c, T_SIGBUILD);
+            q.db_idx_key = 0;
+            const int rc = build_query_index(c, nb);
+            if (rc) return rc;
+            q.db_idx_key = key;
+            q.db_idx_builds += 1;
+        }
+        if (use_index) {
+            TimerScope t(c, T_JOIN);
+            const u64 items = (u64)((n_q + kWave - 1) / kWave) * (u64)nb;          // (band, group of 64 queries), one per wave
+            hipLaunchKernelGGL(query_index_probe_kernel, dim3(grid_for(items, kWavesPerBlock, 8192)), dim3(kBlock), 0, c->stream, q.sigQ.p, q.db_sigQ.p,
+                               q.db_idx_sig.p, q.db_idx_rank.p, c->query_index_dir ? q.db_idx_dir.p : (const int*)nullptr, q.db_idx_dir_bits,
+                               n_q, n_d, nb, q.lo.p, q.hi.p, q.cand.p, (u64)q.cand.cap, pc);
+            HIPCHK(&c->err, hipGetLastError());
+        } else {
             TimerScope t(c, T_JOIN);
             const int n_pad = ((n_d + kWave - 1) / kWave) * kWave;
             const int qt = c->query_join_tile;

@@ -20,13 +20,15 @@
 //   kernel_small.cuh    small_pass_kernel: the whole pass of a set of <= 2 048 genomes in one cooperative launch
 //   kernel_query.cuh    query passes (a query set against the database): CB windows, rectangular signature join, verification,
 //                       literal stream kernel for any band shape, stage 2a on two sets' bit planes
+//   kernel_query_index.cuh ALGO_INDEX of the query passes: the database's band signatures sorted per band (built once, kept), one
+//                       binary search per (query, band) in place of the rectangular join
 //   kernel_query_aux.cuh the auxiliary-HLL criteria of query passes: hll_a / hll_an over each query's CB window, the hll_a stage
 //                       of hll_a + smh_a over the smh_a survivors
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (see csrc/Makefile).
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_scan.hpp>         // exclusive scan of the per-row survivor counts (grouping for stage 2)
-#include <rocprim/device/device_radix_sort.hpp>   // ALGO_HASHJOIN only: the key sort is a library call, everything else is hand-written
+#include <rocprim/device/device_radix_sort.hpp>   // ALGO_HASHJOIN and the query index: the key sort is a library call, everything else is hand-written
 
 #include <algorithm>
 #include <type_traits>
@@ -57,6 +59,7 @@
 #include "kernel_small.cuh"
 #include "kernel_query.cuh"
 #include "kernel_query_aux.cuh"
+#include "kernel_query_index.cuh"
 
 #include "host_context.hpp"      // struct selhip_ctx, device buffers, timers, helpers
 #include "host_pass.hpp"         // pass scheduler: dispatch of every stage, chunk lanes, scratch sizing

@@ -58,6 +58,9 @@ typedef struct { int32_t i, k; double jaccard; } selhip_pair_t;
 #define SELHIP_ALGO_HASHJOIN 3     /* sub-quadratic: (band, signature) keys radix-sorted, candidates read off the runs of equal
                                       keys, exact verify -- same survivors, but pairs are no longer compared one by one
                                       (never chosen by AUTO; not what the pair-comparisons/s metric measures)          */
+#define SELHIP_ALGO_INDEX    4     /* query passes only (section 2b): the database's band signatures sorted per band, built once and
+                                      kept; a pass is one binary search per (query, band) plus the matches -- the records and
+                                      statistics of SIG (never chosen by AUTO; every other entry answers "bad algo 4")   */
 
 /* selection criterion applied before the final HLL-14 Jaccard test (src/selection.cpp -c ...):
  *   SMH_A        src/selection.cpp:228-291   (the north_star path)
@@ -194,6 +197,8 @@ int selhip_ctx_set_param(selhip_ctx* ctx, const char* name, int value);
  * "label_order", "join_tile_rows", "join_form_used" (kernel form of the last LDS-tile join: 0 packed minimum, 1 15-bit, 2 zero-half,
  * 3 bit-sliced; -1 none or the DPP join), "chunks" (chunk lanes of the last pass), "small_pass_used" (the last pass was the one-launch small pass),
  * "query_db_sig_builds" (builds of the database's band signatures by query passes since the database was loaded, section 2b),
+ * "query_db_index_builds" (builds of SELHIP_ALGO_INDEX's sorted signature index since the database was loaded, section 2b),
+ * "query_db_index_kib" (resident size of that index in KiB, 0 = none held),
  * "hist_sparse_t" (the sparse threshold the all-pairs stage 2a uses, 0 = every value from the bit planes) */
 int selhip_ctx_get_param(const selhip_ctx* ctx, const char* name, int* value);
 /* Stage 2 grouping (default on): the pairs that reach the HLL-14 stage are bucketed by query row (counting sort) so
@@ -296,7 +301,16 @@ int    selhip_ctx_timing(selhip_ctx* ctx, int enable);
  *     rows, 8..128 bands: band signatures of a query tile in LDS against the database's, which are kept for the band shape
  *     used last -- a pass with the same shape against the same database does not build them again, one with another shape
  *     replaces them; get_param "query_db_sig_builds" counts the builds since the database was loaded), SELHIP_ALGO_STREAM
- *     (any band shape, m <= 4096: full bucket compare), SELHIP_ALGO_AUTO (SIG where it applies, else STREAM);
+ *     (any band shape, m <= 4096: full bucket compare), SELHIP_ALGO_AUTO (SIG where it applies, else STREAM), or
+ *     SELHIP_ALGO_INDEX (the band shapes of SIG; any other: SELHIP_E_BADARG, no fallback): the database's signatures sorted per
+ *     band with their ranks plus a bucket directory per band, 9 to 10 bytes per (genome, band) (get_param "query_db_index_kib":
+ *     its resident KiB), searched once per (query, band) instead of compared with every query --
+ *     same records (J bit for bit), statistics and selhip_ctx_last_attempts as SIG.  The index is built by the first INDEX pass
+ *     for (database, n_rows, n_bands) and kept: new queries, another tau with the same shape, another mode, and SIG / STREAM /
+ *     all-pairs passes in between neither rebuild nor disturb it; another band shape replaces it; uploading / attaching the
+ *     database drops it (get_param "query_db_index_builds" counts the builds since the database was loaded).  It is sorted from
+ *     the database signatures SIG keeps, so switching between SIG and INDEX with one shape builds those once.  The probe is
+ *     timed as "join", the index build as "sigbuild" (with the database signature build when that runs).
  *     SELHIP_ALGO_HASHJOIN is refused.  hll_a / hll_an alone ignore n_rows, n_bands and algo, as selhip_ctx_run does: each
  *     query's CB window of D is tested directly, without a pair list.  The auxiliary stage is timed as "aux".
  *     Uploading / attaching the database drops the queries; uploading / attaching the queries drops their auxiliary sketches.
