@@ -47,12 +47,12 @@ void selhip_ctx_destroy(selhip_ctx* c) {
     (void)hipStreamSynchronize(c->stream);
     drain_timers(c);
     c->own_hll.release(); c->own_aux.release(); c->own_cards.release();
-    c->ecard.release(); c->hi.release(); c->pc.release(); c->seg_cnt.release(); c->surv.release();
+    c->ecard.release(); c->hi.release(); c->pc.buf.release(); c->seg_cnt.release(); c->surv.release();
     c->counts.release(); c->results.release(); c->self_pairs.release();
-    c->aux_il.release(); c->cand.release(); c->sigQ.release(); c->sigT.release(); c->sigP.release(); c->sigG.release(); c->fin.release(); c->own_aux_hll.release();
+    c->aux_il.release(); c->cand.release(); c->sig.release(); c->fin.release(); c->own_aux_hll.release();
     c->hj_keys_in.release(); c->hj_keys_out.release(); c->hj_vals_in.release(); c->hj_vals_out.release(); c->hj_tmp.release();
     c->csr_cnt.release(); c->csr_start.release(); c->grouped.release(); c->scan_tmp.release();
-    c->hll_bs.release(); c->hll_bs_max.release(); c->hll_gmax.release(); c->small_bar.release();
+    c->planes.release(); c->small_bar.release();
     c->hll_sparse.release(); c->hll_sparse_dev_t.release();
     release_queries(c);
     if (c->h_pc) (void)hipHostFree(c->h_pc);
@@ -65,10 +65,10 @@ void selhip_ctx_destroy(selhip_ctx* c) {
 
 int selhip_ctx_set_stream(selhip_ctx* c, void* hip_stream) {
     if (!c) return SELHIP_E_BADARG;
-    if (c->stream != (hipStream_t)hip_stream && c->pc.p) {
+    if (c->stream != (hipStream_t)hip_stream && c->pc.buf.p) {
         // the counter sets were cleared by work on the old stream, which the new one is not ordered behind
         (void)hipStreamSynchronize(c->stream);
-        c->pc_dirty = true;
+        c->pc.dirty = true;
     }
     c->stream = (hipStream_t)hip_stream;
     return SELHIP_OK;
@@ -190,7 +190,7 @@ int selhip_ctx_set_param(selhip_ctx* c, const char* name, int value) {
         // takes effect at the next selhip_ctx_upload / _attach (the bit planes are written there)
         if (value < -1 || value > 1) { set_err(&c->err, "hist_algo must be -1 (automatic), 0 (byte rows, LDS histogram) or 1 (bit planes)"); return SELHIP_E_BADARG; }
         c->hist_algo = value;
-        if (value == 0) c->hll_khi = 0;
+        if (value == 0) c->planes.khi = 0;
         return SELHIP_OK;
     }
     if (!std::strcmp(name, "hist_sparse")) {
@@ -219,7 +219,7 @@ int selhip_ctx_set_param(selhip_ctx* c, const char* name, int value) {
 
 int selhip_ctx_get_param(const selhip_ctx* c, const char* name, int* value) {
     if (!c || !name || !value) return SELHIP_E_BADARG;
-    if (!std::strcmp(name, "hll_khi"))          { *value = c->hll_khi; return SELHIP_OK; }             // largest p = 14 register value + 1 (0: no bit planes)
+    if (!std::strcmp(name, "hll_khi"))          { *value = c->planes.khi; return SELHIP_OK; }             // largest p = 14 register value + 1 (0: no bit planes)
     if (!std::strcmp(name, "hist_bitplanes"))   { *value = use_bitslices(c) ? 1 : 0; return SELHIP_OK; }
     if (!std::strcmp(name, "hist_sparse_t"))    { *value = sparse_t_used(c); return SELHIP_OK; }      // threshold of the all-pairs stage 2a's sparse lists, 0 = off
     if (!std::strcmp(name, "label_order"))      { *value = label_order(c) ? 1 : 0; return SELHIP_OK; }
@@ -263,16 +263,21 @@ int selhip_ctx_set_criterion(selhip_ctx* c, int criterion) {
     return SELHIP_OK;
 }
 
+// the auxiliary HLL registers [n][1 << p_aux] of a sketch set from the host into the set's own buffer (the arguments were checked)
+static int upload_aux_hll_rows(selhip_ctx* c, const uint8_t* h_aux_hll, int64_t n, int p_aux, DevBuf<uint8_t>& own, const uint8_t** d_aux_hll, int* p_set) {
+    const size_t bytes = (size_t)n << p_aux;
+    HIPCHK(&c->err, own.ensure(bytes ? bytes : 1));
+    if (bytes) HIPCHK(&c->err, hipMemcpyAsync(own.p, h_aux_hll, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    *d_aux_hll = own.p; *p_set = p_aux;
+    return SELHIP_OK;
+}
+
 int selhip_ctx_upload_aux_hll(selhip_ctx* c, const uint8_t* h_aux_hll, int p_aux) {
     if (!c || !h_aux_hll || p_aux < 4 || p_aux > kMaxAuxP) return SELHIP_E_BADARG;     // (aux_fused_kernel's bins are 16 bits wide)
     if (!c->d_hll && c->n) { set_err(&c->err, "upload the primary sketches first"); return SELHIP_E_STATE; }
     HIPCHK(&c->err, hipSetDevice(c->device));
-    const size_t bytes = (size_t)c->n << p_aux;
-    HIPCHK(&c->err, c->own_aux_hll.ensure(bytes ? bytes : 1));
-    if (bytes) HIPCHK(&c->err, hipMemcpyAsync(c->own_aux_hll.p, h_aux_hll, bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
-    c->d_aux_hll = c->own_aux_hll.p; c->p_aux = p_aux;
-    return SELHIP_OK;
+    return upload_aux_hll_rows(c, h_aux_hll, c->n, p_aux, c->own_aux_hll, &c->d_aux_hll, &c->p_aux);
 }
 
 int selhip_ctx_attach_aux_hll(selhip_ctx* c, const uint8_t* d_aux_hll, int p_aux) {
@@ -288,42 +293,45 @@ static int validate_shape(selhip_ctx* c, int64_t n, int m, int p) {
     return SELHIP_OK;
 }
 
+// the cards of a sketch set of n genomes (`noun` names it in the messages): computed with the device estimator from d_hll when none
+// are given, else validated and copied from the host, else the caller's device array as it is
+static int load_cards(selhip_ctx* c, const char* noun, const uint8_t* d_hll, int64_t n, const double* cards_src, bool cards_on_host,
+                      DevBuf<double>& own, const double** d_cards) {
+    if (!cards_src) {
+        HIPCHK(&c->err, own.ensure((size_t)n));
+        const int rc = compute_cards(c, d_hll, n, c->p, own.p);
+        if (rc) return rc;
+        *d_cards = own.p;
+    } else if (cards_on_host) {
+        for (int64_t i = 0; i < n; ++i) {
+            const double v = cards_src[i];
+            if (!(v >= 0.0) || !(v < 9.2e18)) { set_err(&c->err, "%s[%lld] = %g is not a finite value in [0, 2^63)", noun, (long long)i, v); return SELHIP_E_BADARG; }
+            if (i && v < cards_src[i - 1]) { set_err(&c->err, "%s are not in ascending order at rank %lld", noun, (long long)i); return SELHIP_E_BADARG; }
+        }
+        HIPCHK(&c->err, own.ensure((size_t)n));
+        HIPCHK(&c->err, hipMemcpyAsync(own.p, cards_src, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        *d_cards = own.p;
+    } else {
+        *d_cards = cards_src;
+    }
+    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    return SELHIP_OK;
+}
+
 static int after_sketches(selhip_ctx* c, const double* cards_src, bool cards_on_host) {
-    // cards: given or computed with the device estimator
-    c->hll_khi = 0; c->hll_sparse_t = 0;
+    c->planes.khi = 0; c->hll_sparse_t = 0;
     if (c->n == 0) return SELHIP_OK;
     if (c->p == 14 && c->hist_algo != 0) {
-        // the registers once more as bit planes: what stage 2a reads (12 KiB per genome; the byte rows stay for report() and the callers)
-        HIPCHK(&c->err, c->hll_bs.ensure((size_t)c->n * kBsGenomeDwords));
-        HIPCHK(&c->err, c->hll_bs_max.ensure(1));
-        HIPCHK(&c->err, c->hll_gmax.ensure((size_t)c->n));
-        int rc = build_bitslices(&c->err, c->stream, c->d_hll, c->n, c->hll_bs.p, c->hll_gmax.p, c->hll_bs_max.p, &c->hll_khi);
+        // the registers once more as bit planes: what stage 2a reads
+        int rc = c->planes.build(&c->err, c->stream, c->d_hll, c->n);
         if (rc) return rc;
         // the rare high registers once more as sparse lists (512 B per genome), whatever "hist_sparse" is now: it may change before a pass
         HIPCHK(&c->err, c->hll_sparse.ensure((size_t)c->n * kBsSparseCap));
         HIPCHK(&c->err, c->hll_sparse_dev_t.ensure(1));
-        rc = build_sparse_lists(&c->err, c->stream, c->hll_bs.p, c->n, c->hll_sparse.p, c->hll_sparse_dev_t.p, &c->hll_sparse_t);
+        rc = build_sparse_lists(&c->err, c->stream, c->planes.bs.p, c->n, c->hll_sparse.p, c->hll_sparse_dev_t.p, &c->hll_sparse_t);
         if (rc) return rc;
     }
-    if (!cards_src) {
-        HIPCHK(&c->err, c->own_cards.ensure((size_t)c->n));
-        int rc = compute_cards(c, c->d_hll, c->n, c->p, c->own_cards.p);
-        if (rc) return rc;
-        c->d_cards = c->own_cards.p;
-    } else if (cards_on_host) {
-        for (int64_t i = 0; i < c->n; ++i) {
-            double v = cards_src[i];
-            if (!(v >= 0.0) || !(v < 9.2e18)) { set_err(&c->err, "cards[%lld] = %g is not a finite value in [0, 2^63)", (long long)i, v); return SELHIP_E_BADARG; }
-            if (i && v < cards_src[i - 1]) { set_err(&c->err, "cards are not in ascending order at rank %lld", (long long)i); return SELHIP_E_BADARG; }
-        }
-        HIPCHK(&c->err, c->own_cards.ensure((size_t)c->n));
-        HIPCHK(&c->err, hipMemcpyAsync(c->own_cards.p, cards_src, (size_t)c->n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        c->d_cards = c->own_cards.p;
-    } else {
-        c->d_cards = cards_src;
-    }
-    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
-    return SELHIP_OK;
+    return load_cards(c, "cards", c->d_hll, c->n, cards_src, cards_on_host, c->own_cards, &c->d_cards);
 }
 
 int selhip_ctx_upload(selhip_ctx* c, const uint8_t* h_hll, const uint64_t* h_aux, const double* h_cards,
@@ -390,21 +398,21 @@ int selhip_ctx_run_async(selhip_ctx* c, int mode, int algo, float tau_f, int n_r
         set_err(&c->err, "criterion %d needs auxiliary HLL sketches (selhip_ctx_upload_aux_hll)", c->criterion);
         return SELHIP_E_STATE;
     }
-    const bool needs_smh = c->criterion == SELHIP_CRIT_SMH_A || c->criterion == SELHIP_CRIT_HLL_A_SMH_A;
-    if (needs_smh && (n_rows <= 0 || n_bands <= 0 || (long long)n_rows * n_bands != c->m)) {
+    const PassPlan plan = pass_plan(c->criterion, algo, c->m, n_rows, n_bands);
+    if (plan.smh && (n_rows <= 0 || n_bands <= 0 || (long long)n_rows * n_bands != c->m)) {
         // criteria_sketch.hpp:67-70: the reference prints an error and selects nothing; the ABI reports it
         set_err(&c->err, "n_rows*n_bands (%d*%d) != m (%d)", n_rows, n_bands, c->m);
         return SELHIP_E_BADARG;
     }
     if (row_begin < 0 || row_end > c->n || row_begin > row_end) { set_err(&c->err, "bad row range [%lld,%lld)", (long long)row_begin, (long long)row_end); return SELHIP_E_BADARG; }
     HIPCHK(&c->err, hipSetDevice(c->device));
-    c->mode = mode; c->algo = algo; c->tau_f = tau_f; c->n_rows = n_rows; c->n_bands = n_bands;
+    c->mode = mode; c->algo = algo; c->tau_f = tau_f; c->n_rows = n_rows; c->n_bands = n_bands; c->plan = plan;
     c->row_begin = row_begin; c->row_end = row_end;
     c->have_run = false; c->last_was_query = false;
     std::memset(&c->last, 0, sizeof c->last);
     if (c->n == 0 || row_begin == row_end) { c->pending = false; c->have_run = true; return SELHIP_OK; }
     size_t surv_cap = std::max<size_t>(c->surv.cap, std::max<size_t>((size_t)1 << 20, (size_t)c->n * 16));
-    if (needs_smh && c->join_bits <= 16 && algo != SELHIP_ALGO_STREAM && algo != SELHIP_ALGO_HASHJOIN && sig_supported(c->m, n_rows, n_bands)) {
+    if (join16_pass(c)) {
         // the 16-bit join passes ~n_bands * 2^-16 of the pairs it compares on to the 32-bit filter: size the lists for that
         // up front (an overflow would only cost one repeated pass)
         const double expect = (double)pair_bound(c->n, (int)row_begin, (int)row_end) / std::max(1, c->il_parts) * n_bands / (c->join_bits == 15 ? 32768.0 : 65536.0);
@@ -424,7 +432,7 @@ int selhip_ctx_finish(selhip_ctx* c) {
     if (!c) return SELHIP_E_BADARG;
     if (!c->pending) return c->have_run ? SELHIP_OK : SELHIP_E_STATE;
     HIPCHK(&c->err, hipSetDevice(c->device));
-    for (int attempt = 0; attempt < 8; ++attempt) {
+    for (int attempt = 0; attempt < kMaxAttempts; ++attempt) {
         HIPCHK(&c->err, wait_stream(c->stream));
         // block 0 = pass-wide counters; blocks 1..chunks = per-row-chunk list counters (each list slice = cap / chunks)
         PassCounters pc = c->h_pc[0];
@@ -446,12 +454,12 @@ int selhip_ctx_finish(selhip_ctx* c) {
             pc.n_survivors += q.n_survivors; pc.n_candidates += q.n_candidates; pc.n_aux_in += q.n_aux_in; pc.n_final += q.n_final;
             // the 16-bit join's list is kAppendSegs equal slices: it overflows when its fullest slice does
             const u64 worst = std::max(std::max(std::max(q.n_survivors, q.n_candidates), q.n_pre_segmax * (u64)kAppendSegs), c->criterion != SELHIP_CRIT_SMH_A ? q.n_final : 0);
-            if (worst > slice) { surv_cap = std::max(surv_cap, (size_t)((worst + worst / 8 + 1024) * (u64)chunks)); grow = true; }
+            if (worst > slice) { surv_cap = std::max(surv_cap, grown(worst) * (size_t)chunks); grow = true; }
             // (n_aux_in is zeroed before every enumeration sub-pass, so what arrives here is the LAST sub-pass's count only: it proves
             //  nothing about the others.  The guarantee is the host-side bound in enqueue_pass -- every sub-pass lists at most
             //  cand.cap - 1024 pairs by construction -- and enum_pairs_kernel never writes past out_cap.)
         }
-        if (pc.n_results > c->results.cap) { res_cap = (size_t)(pc.n_results + pc.n_results / 8 + 1024); grow = true; }
+        if (results_overflowed(pc.n_results, c->results.cap, &res_cap)) grow = true;
         if (!grow) {
             c->last = pc; c->pending = false; c->have_run = true; c->last_attempts = attempt + 1;
             // (event pairs are read lazily -- selhip_ctx_kernel_ms / _timing / destroy -- so that a timed run does not stall the

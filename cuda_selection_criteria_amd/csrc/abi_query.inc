@@ -6,33 +6,12 @@ extern "C" {
 
 static int after_queries(selhip_ctx* c, const double* cards_src, bool cards_on_host) {
     auto& q = c->q;
-    q.khi = 0;
+    q.planes.khi = 0;
     if (q.n == 0) { q.d_cards = nullptr; return SELHIP_OK; }
     // the registers as bit planes (stage 2a of the query pass), as for the database
-    HIPCHK(&c->err, q.bs.ensure((size_t)q.n * kBsGenomeDwords));
-    HIPCHK(&c->err, q.gmax.ensure((size_t)q.n));
-    HIPCHK(&c->err, q.bs_max.ensure(1));
-    int rc = build_bitslices(&c->err, c->stream, q.d_hll, q.n, q.bs.p, q.gmax.p, q.bs_max.p, &q.khi);
+    const int rc = q.planes.build(&c->err, c->stream, q.d_hll, q.n);
     if (rc) return rc;
-    if (!cards_src) {
-        HIPCHK(&c->err, q.own_cards.ensure((size_t)q.n));
-        rc = compute_cards(c, q.d_hll, q.n, c->p, q.own_cards.p);
-        if (rc) return rc;
-        q.d_cards = q.own_cards.p;
-    } else if (cards_on_host) {
-        for (int64_t i = 0; i < q.n; ++i) {
-            const double v = cards_src[i];
-            if (!(v >= 0.0) || !(v < 9.2e18)) { set_err(&c->err, "query cards[%lld] = %g is not a finite value in [0, 2^63)", (long long)i, v); return SELHIP_E_BADARG; }
-            if (i && v < cards_src[i - 1]) { set_err(&c->err, "query cards are not in ascending order at rank %lld", (long long)i); return SELHIP_E_BADARG; }
-        }
-        HIPCHK(&c->err, q.own_cards.ensure((size_t)q.n));
-        HIPCHK(&c->err, hipMemcpyAsync(q.own_cards.p, cards_src, (size_t)q.n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        q.d_cards = q.own_cards.p;
-    } else {
-        q.d_cards = cards_src;
-    }
-    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
-    return SELHIP_OK;
+    return load_cards(c, "query cards", q.d_hll, q.n, cards_src, cards_on_host, q.own_cards, &q.d_cards);
 }
 
 static int check_query_shape(selhip_ctx* c, int64_t n_q) {
@@ -96,12 +75,7 @@ int selhip_ctx_upload_queries_aux_hll(selhip_ctx* c, const uint8_t* h_aux_hll, i
     HIPCHK(&c->err, hipSetDevice(c->device));
     auto& q = c->q;
     q.d_aux_hll = nullptr; q.p_aux = 0;
-    const size_t bytes = (size_t)q.n << p_aux;
-    HIPCHK(&c->err, q.own_aux_hll.ensure(bytes ? bytes : 1));
-    if (bytes) HIPCHK(&c->err, hipMemcpyAsync(q.own_aux_hll.p, h_aux_hll, bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
-    q.d_aux_hll = q.own_aux_hll.p; q.p_aux = p_aux;
-    return SELHIP_OK;
+    return upload_aux_hll_rows(c, h_aux_hll, q.n, p_aux, q.own_aux_hll, &q.d_aux_hll, &q.p_aux);
 }
 
 int selhip_ctx_attach_queries_aux_hll(selhip_ctx* c, const uint8_t* d_aux_hll, int p_aux) {
@@ -136,9 +110,9 @@ int selhip_ctx_run_queries(selhip_ctx* c, int mode, int algo, float tau_f, int n
             return SELHIP_E_BADARG;
         }
     }
-    const bool smh = query_smh_stage(c);
+    const PassPlan plan = pass_plan(c->criterion, algo, c->m, n_rows, n_bands);
+    const bool smh = plan.smh;
     if (algo != SELHIP_ALGO_AUTO && algo != SELHIP_ALGO_STREAM && algo != SELHIP_ALGO_SIG && algo != SELHIP_ALGO_HASHJOIN && algo != SELHIP_ALGO_INDEX) { set_err(&c->err, "bad algo %d", algo); return SELHIP_E_BADARG; }
-    bool use_sig = false, use_index = false;
     if (smh) {
         // (hll_a / hll_an alone read neither n_rows / n_bands nor algo, as in selhip_ctx_run_async)
         if (algo == SELHIP_ALGO_HASHJOIN) { set_err(&c->err, "query passes have no ALGO_HASHJOIN; use AUTO, SIG, STREAM or INDEX"); return SELHIP_E_BADARG; }
@@ -146,21 +120,11 @@ int selhip_ctx_run_queries(selhip_ctx* c, int mode, int algo, float tau_f, int n
             set_err(&c->err, "n_rows*n_bands (%d*%d) != m (%d)", n_rows, n_bands, c->m);
             return SELHIP_E_BADARG;
         }
-        const bool sig_ok = sig_supported(c->m, n_rows, n_bands);
-        if (algo == SELHIP_ALGO_SIG && !sig_ok) {
-            set_err(&c->err, "ALGO_SIG needs power-of-two rows and 8..128 bands (got %d x %d)", n_rows, n_bands);
-            return SELHIP_E_BADARG;
-        }
-        if (algo == SELHIP_ALGO_INDEX && !sig_ok) {             // (no fallback: the caller asked for the index)
-            set_err(&c->err, "ALGO_INDEX needs power-of-two rows and 8..128 bands (got %d x %d)", n_rows, n_bands);
-            return SELHIP_E_BADARG;
-        }
-        use_sig = algo != SELHIP_ALGO_STREAM && sig_ok;
-        use_index = algo == SELHIP_ALGO_INDEX;
-        if (!use_sig && query_stream_tile(c->m) == 0) { set_err(&c->err, "ALGO_STREAM of a query pass holds m <= 4096 buckets (m = %d)", c->m); return SELHIP_E_BADARG; }
+        if (plan.bad) { set_err(&c->err, plan.bad, n_rows, n_bands); return SELHIP_E_BADARG; }
+        if (!plan.use_sig && query_stream_tile(c->m) == 0) { set_err(&c->err, "ALGO_STREAM of a query pass holds m <= 4096 buckets (m = %d)", c->m); return SELHIP_E_BADARG; }
     }
     HIPCHK(&c->err, hipSetDevice(c->device));
-    c->mode = mode; c->algo = algo; c->tau_f = tau_f; c->n_rows = n_rows; c->n_bands = n_bands;
+    c->mode = mode; c->algo = algo; c->tau_f = tau_f; c->n_rows = n_rows; c->n_bands = n_bands; c->plan = plan;
     c->have_run = false;
     std::memset(&c->last, 0, sizeof c->last);
     c->last_was_query = true;
@@ -170,9 +134,9 @@ int selhip_ctx_run_queries(selhip_ctx* c, int mode, int algo, float tau_f, int n
     if (c->init_cap > 0) cap = std::max<size_t>(have, (size_t)c->init_cap);             // test hook: start small, grow on overflow
     size_t res_cap = std::max<size_t>(c->results.cap, cap);
     const double tau = (double)tau_f;                 // float threshold widened, selection.cpp:81,164
-    for (int attempt = 0; attempt < 8; ++attempt) {
+    for (int attempt = 0; attempt < kMaxAttempts; ++attempt) {
         int rc = ensure_query_scratch(c, cap, res_cap);
-        if (!rc) rc = enqueue_query_pass(c, use_sig, use_index, tau);
+        if (!rc) rc = enqueue_query_pass(c, tau);
         if (rc) return rc;
         HIPCHK(&c->err, wait_stream(c->stream));
         const PassCounters pc = *q.h_pc;
@@ -181,10 +145,10 @@ int selhip_ctx_run_queries(selhip_ctx* c, int mode, int algo, float tau_f, int n
         // (n_pre: the join's list; n_survivors: the survivor list; n_final: what passed the auxiliary criterion)
         const u64 worst = std::max(std::max(pc.n_pre, pc.n_survivors), c->criterion != SELHIP_CRIT_SMH_A ? pc.n_final : 0);
         if ((smh && (worst > q.surv.cap || worst > q.cand.cap)) || (c->criterion != SELHIP_CRIT_SMH_A && worst > q.fin.cap)) {
-            cap = std::max(cap, (size_t)(worst + worst / 8 + 1024));
+            cap = std::max(cap, grown(worst));
             grow = true;
         }
-        if (pc.n_results > c->results.cap) { res_cap = (size_t)(pc.n_results + pc.n_results / 8 + 1024); grow = true; }
+        if (results_overflowed(pc.n_results, c->results.cap, &res_cap)) grow = true;
         if (!grow) {
             c->last = pc; c->have_run = true; c->last_attempts = attempt + 1; c->last_was_query = true;
             return SELHIP_OK;

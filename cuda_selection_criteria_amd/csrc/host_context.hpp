@@ -1,4 +1,5 @@
-// host_context.hpp -- the context of libselhip.so (struct selhip_ctx), its device buffers, kernel timers and small helpers.
+// host_context.hpp -- the context of libselhip.so (struct selhip_ctx), its device buffers (DevBuf; SigSet, BitPlanes and CounterSets, one
+// definition each for the database's, the queries' and the query passes' instances), kernel timers and small helpers.
 // Part of the kernel translation unit selection_kernels.hip (included there, after the kernel headers); not a stand-alone header.
 #pragma once
 
@@ -28,6 +29,11 @@ void set_err(std::string* dst, const char* fmt, ...) {
         }                                                                                      \
     } while (0)
 
+// a run-time flag that a kernel takes as a template argument (the estimator's SELHIP_FP_FMA mode above all): f(std::true_type{}) or
+// f(std::false_type{}), so that the launch is written once -- with_flag(fma, [&](auto F) { ...kernel<decltype(F)::value>... })
+template <typename F>
+auto with_flag(bool flag, F&& f) { return flag ? f(std::true_type{}) : f(std::false_type{}); }
+
 template <typename T>
 struct DevBuf {
     T* p = nullptr;
@@ -40,6 +46,73 @@ struct DevBuf {
         return e;
     }
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+};
+
+// the four layouts the signature builder writes for one sketch set: genome-major / band-major / band-major 16-bit pairs / genome-major
+// 16-bit pairs (Q, T, P, G)
+struct SigSet {
+    DevBuf<uint32_t> Q, T, P, G;
+    // room for n genomes of nb bands.  *moved (if asked for): an array was reallocated, so whatever a cache key says they hold is gone
+    hipError_t ensure(size_t n, size_t nb, bool* moved = nullptr) {
+        const uint32_t* const old[4] = {Q.p, T.p, P.p, G.p};
+        const size_t n_pad = pad_wave(n), half = (nb + 1) / 2;
+        hipError_t e = Q.ensure(std::max<size_t>(1, n * nb));
+        if (e == hipSuccess) e = T.ensure(std::max<size_t>(1, n_pad * nb));
+        if (e == hipSuccess) e = P.ensure(std::max<size_t>(1, n_pad * half));
+        if (e == hipSuccess) e = G.ensure((n_pad + 2) * half);
+        if (moved) *moved = Q.p != old[0] || T.p != old[1] || P.p != old[2] || G.p != old[3];
+        return e;
+    }
+    void release() { Q.release(); T.release(); P.release(); G.release(); }
+};
+
+// writes the bit planes of n genomes and returns max register value + 1 through *khi (waits for the stream)
+int build_bitslices(std::string* err, hipStream_t st, const uint8_t* d_hll, int64_t n, uint32_t* d_bs, uint8_t* d_gmax, int* d_max, int* khi) {
+    HIPCHK(err, hipMemsetAsync(d_max, 0, sizeof(int), st));
+    hipLaunchKernelGGL(hll_bitslice_kernel, dim3(grid_for((u64)n, kWavesPerBlock, 8192)), dim3(kBlock), 0, st, d_hll, (long long)n, d_bs, d_gmax, d_max);
+    HIPCHK(err, hipGetLastError());
+    int mx = 0;
+    HIPCHK(err, hipMemcpyAsync(&mx, d_max, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(err, hipStreamSynchronize(st));
+    *khi = mx + 1;
+    return SELHIP_OK;
+}
+
+// stage 2a on bit planes (kernel_hllbs.cuh): the p = 14 registers of every genome of a sketch set as 6 bit planes (12 KiB per genome;
+// the byte rows stay for report() and the callers)
+struct BitPlanes {
+    DevBuf<uint32_t> bs;                // [n][6][512]
+    DevBuf<uint8_t> gmax;               // [n] largest register value of each genome
+    DevBuf<int> dev_max;                // largest register value of the set (device side)
+    int khi = 0;                        // 0 = no planes; else max register value + 1
+    int build(std::string* err, hipStream_t st, const uint8_t* d_hll, int64_t n) {
+        HIPCHK(err, bs.ensure((size_t)n * kBsGenomeDwords));
+        HIPCHK(err, gmax.ensure((size_t)n));
+        HIPCHK(err, dev_max.ensure(1));
+        return build_bitslices(err, st, d_hll, n, bs.p, gmax.p, dev_max.p, &khi);
+    }
+    void release() { bs.release(); gmax.release(); dev_max.release(); }
+};
+
+// TWO sets of per_set counter blocks: pass k uses set k & 1 and its first kernel clears the other for pass k + 1 -- no memset dispatch
+// on the stream in steady state.  dirty: a pass claimed a set and did not get to the end of its enqueue (its first kernel may never have
+// run), or nothing has cleared the buffer yet, or the stream changed behind the clearing: the next claim clears both sets first, once
+struct CounterSets {
+    DevBuf<PassCounters> buf;
+    int per_set = 1, flip = 0;
+    bool dirty = false;
+    struct Claim { PassCounters* cur; PassCounters* next; };
+    // the set of the pass being enqueued and the one its first kernel clears; the caller resets `dirty` when its enqueue is complete
+    hipError_t claim(hipStream_t st, Claim* out) {
+        if (dirty) {
+            const hipError_t e = hipMemsetAsync(buf.p, 0, sizeof(PassCounters) * 2 * per_set, st);
+            if (e != hipSuccess) return e;
+        }
+        *out = Claim{buf.p + (size_t)flip * per_set, buf.p + (size_t)(flip ^ 1) * per_set};
+        flip ^= 1;
+        dirty = true;
+        return hipSuccess;
+    }
 };
 
 struct KernelTimer {
@@ -86,10 +159,8 @@ struct selhip_ctx {
     // derived / scratch
     DevBuf<u64> ecard;
     DevBuf<int> hi;
-    DevBuf<PassCounters> pc;            // TWO sets of kMaxChunks + 1 counter blocks: pass k uses set k & 1 and its first kernel clears the other
+    CounterSets pc{{}, kMaxChunks + 1}; // kMaxChunks + 1 blocks per set; cleared once at allocation (ensure_scratch), so it starts clean
     PassCounters* pcb = nullptr;        // the set of the pass enqueued last
-    int pc_flip = 0;
-    bool pc_dirty = false;              // a pass claimed a counter set and did not get to the end of its enqueue (or the stream changed): clear both sets first
     int fail_after_flip = 0;            // test hook ("fail_after_flip"): the next enqueue returns an error right after claiming its counter set
     DevBuf<u64> seg_cnt;                // the join's append-segment counters: (kMaxChunks + 1) x kAppendSegs x kSegStride
     DevBuf<selhip_int2_t> surv;
@@ -103,7 +174,7 @@ struct selhip_ctx {
     int p_aux = 0;
     int criterion = 0;
     DevBuf<u64> aux_il;                 // ALGO_STREAM: bucket-interleaved copy of the sketches (kernel_stream.cuh)
-    DevBuf<uint32_t> sigQ, sigT, sigP, sigG;  // ALGO_SIG: band signatures, genome-major / band-major / band-major 16-bit pairs / genome-major 16-bit pairs
+    SigSet sig;                         // ALGO_SIG: band signatures
     DevBuf<u64> hj_keys_in, hj_keys_out;   // ALGO_HASHJOIN: (band << 32 | signature) keys, before / after the sort
     DevBuf<int> hj_vals_in, hj_vals_out;   //                genome ranks carried by the keys
     DevBuf<char> hj_tmp;                   //                rocPRIM temporary storage
@@ -121,13 +192,10 @@ struct selhip_ctx {
     int il_block = 128, il_parts = 1, il_part = 0;    // row interleave (selhip_ctx_set_row_interleave); il_parts 1 = contiguous
     int hist_pad = 0;                   // stage 2a: extra LDS bytes per one-wave block (lowers the number of resident waves per CU)
     int hist_run = 0, hist_blocks = kHistSpanBlocks;   // stage 2a: pairs per task (0 = automatic: 1, or 4 with the label order), one-wave blocks (multiple of 8)
-    // stage 2a on bit planes (kernel_hllbs.cuh): the p = 14 registers of every genome as 6 bit planes, written when the sketches
-    // are uploaded / attached (selhip_ctx_upload / _attach; the caller's arrays must not change behind an attached context)
-    DevBuf<uint32_t> hll_bs;            // [n][6][512]
+    // the database's bit planes, written when the sketches are uploaded / attached (selhip_ctx_upload / _attach; the caller's arrays
+    // must not change behind an attached context)
+    BitPlanes planes;
     DevBuf<u64> small_bar;              // the one-launch pass's barrier: 16 group words, 128 bytes apart
-    DevBuf<uint8_t> hll_gmax;           // [n] largest register value of each genome
-    DevBuf<int> hll_bs_max;             // largest register value of the set (device side)
-    int hll_khi = 0;                    // 0 = no planes; else max register value + 1
     // sparse lists of every genome's registers >= hll_sparse_t ([n][kBsSparseCap], written with the planes): stage 2a decodes only the
     // values below the threshold from the planes.  hll_sparse_t = 0: no lists (the set needs a threshold above kBsSparseMaxT)
     DevBuf<uint32_t> hll_sparse;
@@ -169,6 +237,7 @@ struct selhip_ctx {
     // last run parameters (for overflow re-runs)
     bool have_run = false, pending = false;
     int mode = 0, algo = 0, n_rows = 0, n_bands = 0;
+    PassPlan plan;                      // which stage 1 these parameters and the criterion select (pass_plan; set by run_async / run_queries)
     float tau_f = 0;
     int64_t row_begin = 0, row_end = 0;
     PassCounters last{};
@@ -182,14 +251,11 @@ struct selhip_ctx {
         DevBuf<uint8_t> own_hll;
         DevBuf<u64> own_aux;
         DevBuf<double> own_cards;
-        DevBuf<uint32_t> bs;                        // Q's bit planes [n][6][512], written at upload / attach
-        DevBuf<uint8_t> gmax;
-        DevBuf<int> bs_max;
-        int khi = 0;
+        BitPlanes planes;                           // Q's bit planes, written at upload / attach
         DevBuf<int> lo, hi;                         // CB window of every query in D
         DevBuf<u64> ecard;                          // truncated cards, combined index space: [0, n) = Q, [n, n + n_D) = D
-        DevBuf<uint32_t> sigQ, sigT, sigP, sigG;    // Q's band signatures (sigQ is read; the builder writes all four layouts)
-        DevBuf<uint32_t> db_sigQ, db_sigT, db_sigP, db_sigG;   // D's band signatures, kept across query passes
+        SigSet sig;                                 // Q's band signatures (sig.Q is read; the builder writes all four layouts)
+        SigSet db_sig;                              // D's band signatures, kept across query passes
         long long db_sig_key = 0;                   // (n_rows, n_bands, database generation) they were built for; 0 = none
         int db_sig_builds = 0;                      // builds of D's signatures since the database was loaded ("query_db_sig_builds")
         // ALGO_INDEX (kernel_query_index.cuh): per band, D's signatures sorted ascending and the database ranks they belong to
@@ -200,19 +266,15 @@ struct selhip_ctx {
         int db_idx_dir_bits = 0, db_idx_bands = 0;
         long long db_idx_key = 0;                   // as db_sig_key; 0 = none
         int db_idx_builds = 0;                      // index builds since the database was loaded ("query_db_index_builds")
-        DevBuf<uint32_t> db_bs;                     // D's bit planes, only if the all-pairs path keeps none (hist_algo 0)
-        DevBuf<uint8_t> db_gmax;
+        BitPlanes db_planes;                        // D's bit planes, only if the all-pairs path keeps none (hist_algo 0)
         long long db_bs_gen = -1;
-        int db_khi = 0;
         DevBuf<selhip_int2_t> cand, surv;
         DevBuf<selhip_int2_t> fin;                  // criteria other than smh_a: the pairs that passed hll_a / hll_an (stage 2's list)
         const uint8_t* d_aux_hll = nullptr;         // Q's auxiliary HLL registers [n][1 << p_aux] (dropped by every upload / attach of Q)
         DevBuf<uint8_t> own_aux_hll;
         int p_aux = 0;                              // 0 = none loaded
         DevBuf<uint32_t> counts;
-        DevBuf<PassCounters> pc;                    // two counter sets: pass k uses set k & 1, its first kernel clears the other
-        int pc_flip = 0;
-        bool pc_dirty = true;                       // clear both sets before the next pass (a pass did not get to the end of its enqueue)
+        CounterSets pc{{}, 1, 0, true};             // one block per set; nothing clears it at allocation, so it starts dirty
         PassCounters* h_pc = nullptr;
     } q;
     long long db_gen = 0;               // incremented by every upload / attach of the database
@@ -298,18 +360,10 @@ void drain_timers(selhip_ctx* c) {
     }
 }
 
-double relerr_scaled_for(int p) {
-    // hll.h:662  relerr /= std::sqrt(m), relerr = 1e-2 (hll.h:211 default, :257)
-    return 1e-2 / std::sqrt((double)(1ull << p));
-}
-
 // stage 2 works on a list bucketed by query row (and laid out by label) unless the caller switched that off -- or the set is small:
 // up to group_min_n genomes (2 048) the whole table of bit planes (<= 20 MB) stays in L2 / the Infinity Cache whatever the order, and
 // the two grouping launches are 13 us of a 95 us step (BASELINE configs[1])
 bool grouping_on(const selhip_ctx* c) { return c->p == 14 && c->group_stage2 && c->n > c->group_min_n; }
-
-bool is_pow2(int x) { return x > 0 && (x & (x - 1)) == 0; }
-int ilog2(int x) { int l = 0; while ((1 << l) < x) ++l; return l; }
 
 // RowMap of the query rows [rb, re) under the context's interleave setting (selhip_ctx_set_row_interleave)
 RowMap row_map(const selhip_ctx* c, int rb, int re) {

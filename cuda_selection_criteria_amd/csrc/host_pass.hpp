@@ -33,10 +33,6 @@ hipError_t launch_stream_r(selhip_ctx* c, const StageIO& io, int l, const RowMap
     return hipErrorInvalidValue;
 }
 
-bool stream_supported(int m, int n_rows) {
-    return is_pow2(m) && m >= 128 && m <= 2048 && is_pow2(n_rows) && n_rows <= m;
-}
-
 hipError_t launch_stage1(selhip_ctx* c, const StageIO& io, int n_rows, int n_bands, const RowMap& rm) {
     if (stream_supported(c->m, n_rows)) {
         const int nch = c->m / 128;
@@ -62,8 +58,6 @@ hipError_t launch_stage1(selhip_ctx* c, const StageIO& io, int n_rows, int n_ban
 }
 
 
-unsigned grid_for(u64 items, unsigned per_block, unsigned max_blocks);
-
 // pairs of the all-pairs triangle that this context's passes cover
 double join_pairs_here(const selhip_ctx* c) {
     return 0.5 * (double)c->n * (double)c->n / std::max(1, c->il_parts);
@@ -80,59 +74,50 @@ int join_tile_rows(const selhip_ctx* c) {
     return qt;
 }
 
-bool sig_supported(int m, int n_rows, int n_bands) {
-    (void)m;
-    return is_pow2(n_rows) && (n_bands == 8 || n_bands == 16 || n_bands == 32 || n_bands == 64 || n_bands == 128);
+// the grid of a signature join: tiles of qt query rows x blocks of gpb candidate groups (a group = 64 candidates, one wave's worth),
+// the candidates being k > row_begin, k >= cand_begin.  blocks = 0: nothing to launch.  nd > 0: the join reads nd dwords per genome
+// through 32-bit offsets into a band-major signature array of pitch n_pad, which must therefore stay below 2 GiB
+struct JoinGeometry { int n_tiles, group_base, n_gblocks; long long blocks; };
+hipError_t join_geometry(const selhip_ctx* c, const RowMap& rm, int qt, int gpb, int nd, int n_pad, JoinGeometry* g) {
+    if ((long long)nd * n_pad * 4 >= (1ll << 31)) return hipErrorInvalidValue;
+    const long long n_tiles_ll = rm.n_tiles(qt);
+    if (n_tiles_ll > 0x7FFFFFFFll) return hipErrorInvalidValue;
+    g->n_tiles = (int)n_tiles_ll;
+    g->group_base = (std::max(rm.row_begin + 1, (int)c->cand_begin) / kWave / gpb) * gpb;
+    const int n_groups = ((int)c->n + kWave - 1) / kWave - g->group_base;
+    g->n_gblocks = (n_groups + gpb - 1) / gpb;
+    g->blocks = g->n_tiles <= 0 || g->n_gblocks <= 0 ? 0 : (long long)g->n_tiles * g->n_gblocks;
+    return g->blocks > 0x7FFFFFFFll ? hipErrorInvalidValue : hipSuccess;
 }
 
 template <int NB>
 hipError_t launch_join(selhip_ctx* c, const StageIO& io, int n_pad, const RowMap& rm) {
-    const int n = (int)c->n;
     const int qt = join_tile_rows(c);   // query rows per block (multiple of 16)
-    const long long n_tiles_ll = rm.n_tiles(qt);
-    if (n_tiles_ll > 0x7FFFFFFFll) return hipErrorInvalidValue;
-    const int n_tiles = (int)n_tiles_ll;
-    const int group_base = (std::max(rm.row_begin + 1, (int)c->cand_begin) / kWave / kWavesPerBlock) * kWavesPerBlock;   // candidates k > row_begin, k >= cand_begin
-    const int n_groups = (n + kWave - 1) / kWave - group_base;
-    const int n_gblocks = (n_groups + kWavesPerBlock - 1) / kWavesPerBlock;
-    if (n_tiles <= 0 || n_gblocks <= 0) return hipSuccess;
-    const long long blocks = (long long)n_tiles * n_gblocks;
-    if (blocks > 0x7FFFFFFFll) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((sig_join_kernel<NB>), dim3((unsigned)blocks), dim3(kBlock), 0, io.st,
-                       c->sigT.p, n, n_pad, c->hi.p, c->pcb, rm, n_tiles, group_base, qt,
+    JoinGeometry g;
+    const hipError_t e = join_geometry(c, rm, qt, kWavesPerBlock, 0, n_pad, &g);
+    if (e != hipSuccess || g.blocks == 0) return e;
+    hipLaunchKernelGGL((sig_join_kernel<NB>), dim3((unsigned)g.blocks), dim3(kBlock), 0, io.st,
+                       c->sig.T.p, (int)c->n, n_pad, c->hi.p, c->pcb, rm, g.n_tiles, g.group_base, qt,
                        io.cand, io.cap, io.pc);
     return hipGetLastError();
 }
 
 template <int ND, bool DB, int WPB>
 hipError_t launch_join16_w(selhip_ctx* c, const StageIO& io, int n_pad, const RowMap& rm) {
-    const int n = (int)c->n;
-    if ((long long)ND * n_pad * 4 >= (1ll << 31)) return hipErrorInvalidValue;          // 32-bit offsets into the band-major signature array
     const int qt = join_tile_rows(c);
-    const long long n_tiles_ll = rm.n_tiles(qt);
-    if (n_tiles_ll > 0x7FFFFFFFll) return hipErrorInvalidValue;
-    const int n_tiles = (int)n_tiles_ll;
-    const int group_base = (std::max(rm.row_begin + 1, (int)c->cand_begin) / kWave / WPB) * WPB;   // candidates k > row_begin, k >= cand_begin
-    const int n_groups = (n + kWave - 1) / kWave - group_base;
-    const int n_gblocks = (n_groups + WPB - 1) / WPB;
-    if (n_tiles <= 0 || n_gblocks <= 0) return hipSuccess;
-    const long long blocks = (long long)n_tiles * n_gblocks;
-    if (blocks > 0x7FFFFFFFll) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((sig16_join_kernel<ND, DB, WPB>), dim3((unsigned)blocks), dim3(WPB * kWave), 0, io.st,
-                       c->sigP.p, n, n_pad, c->hi.p, c->pcb, rm, n_tiles, group_base, qt,
+    JoinGeometry g;
+    const hipError_t e = join_geometry(c, rm, qt, WPB, ND, n_pad, &g);
+    if (e != hipSuccess || g.blocks == 0) return e;
+    hipLaunchKernelGGL((sig16_join_kernel<ND, DB, WPB>), dim3((unsigned)g.blocks), dim3(WPB * kWave), 0, io.st,
+                       c->sig.P.p, (int)c->n, n_pad, c->hi.p, c->pcb, rm, g.n_tiles, g.group_base, qt,
                        io.cand, io.cap, io.seg_cnt);
     return hipGetLastError();
-}
-
-// the tiled signature build (sig_build_tile_body) takes this band shape
-bool sig_tile_mode(const selhip_ctx* c, int n_rows, int n_bands) {
-    return is_pow2(c->m) && is_pow2(n_bands) && n_bands <= 128 && n_rows >= 2 && n_rows <= 32 && c->m >= 4 && c->sig_tile;
 }
 
 // the all-pairs join of this band shape runs on bit-sliced signatures ("join_form" = 2: the LDS-tile 16-bit join, and a tiled build to
 // write the layout; any other shape keeps the packed form 0).  The build and the join both ask, so they always agree on the layout.
 bool join_sliced(const selhip_ctx* c, int n_rows, int n_bands) {
-    return c->join_form == 2 && c->join_bits == 16 && c->join_q && c->algo != SELHIP_ALGO_HASHJOIN && sig_tile_mode(c, n_rows, n_bands);
+    return c->join_form == 2 && c->join_bits == 16 && c->join_q && c->algo != SELHIP_ALGO_HASHJOIN && c->sig_tile && sig_tile_shape(c->m, n_rows, n_bands);
 }
 
 template <int ND, int T, int WPB, int FORM>
@@ -142,16 +127,12 @@ hipError_t launch_joinl_w(selhip_ctx* c, const StageIO& io, int n_pad, const Row
     // interleave block when rows are interleaved
     int qt = std::min(join_tile_rows(c), (int)((64 * 1024 - WPB * kAppendCap * sizeof(selhip_int2_t)) / (ND * 4 + 4) - kJoinTilePadRows) / 16 * 16);
     if (c->il_parts > 1) while (c->il_block % qt) qt -= 16;
-    const long long n_tiles_ll = rm.n_tiles(qt);
-    if (n_tiles_ll > 0x7FFFFFFFll) return hipErrorInvalidValue;
-    const int n_tiles = (int)n_tiles_ll;
-    if ((long long)ND * n_pad * 4 >= (1ll << 31)) return hipErrorInvalidValue;          // 32-bit offsets into the band-major signature array
     constexpr int GPB = WPB * T;                                                          // candidate groups per block
-    const int group_base = (std::max(rm.row_begin + 1, (int)c->cand_begin) / kWave / GPB) * GPB;   // candidates k > row_begin, k >= cand_begin
-    const int n_groups = (n + kWave - 1) / kWave - group_base;
-    const int n_gblocks = (n_groups + GPB - 1) / GPB;
-    if (n_tiles <= 0 || n_gblocks <= 0) return hipSuccess;
-    long long blocks = (long long)n_tiles * n_gblocks;
+    JoinGeometry g;
+    const hipError_t e = join_geometry(c, rm, qt, GPB, ND, n_pad, &g);
+    if (e != hipSuccess || g.blocks == 0) return e;
+    const int n_tiles = g.n_tiles, group_base = g.group_base, n_gblocks = g.n_gblocks;
+    long long blocks = g.blocks;
     // only the units above the diagonal (JoinTriangle, kernel_sigjoin.cuh) when the rows are contiguous and the tiles line up with the
     // 256-candidate blocks; otherwise the rectangle, whose blocks under the diagonal leave at once
     JoinTriangle tri{0, 0, 0, 0};
@@ -172,7 +153,7 @@ hipError_t launch_joinl_w(selhip_ctx* c, const StageIO& io, int n_pad, const Row
     const size_t smem = (size_t)WPB * kAppendCap * sizeof(selhip_int2_t) + (size_t)((qt + 3) & ~3) * 4 + (size_t)(qt + kJoinTilePadRows) * ND * 4;
     if (smem > 64 * 1024) return hipErrorInvalidValue;                                   // join_qt is capped so that this cannot happen
     hipLaunchKernelGGL((sigl_join_kernel<ND, T, WPB, FORM>), dim3((unsigned)blocks), dim3(WPB * kWave), smem, io.st,
-                       c->sigP.p, c->sigG.p, n, n_pad, c->hi.p, c->pcb, rm, n_tiles, group_base, qt,
+                       c->sig.P.p, c->sig.G.p, n, n_pad, c->hi.p, c->pcb, rm, n_tiles, group_base, qt,
                        io.cand, io.cap, io.seg_cnt, c->mode == SELHIP_MODE_CB_SMH ? 1 : 0, tri);
     return hipGetLastError();
 }
@@ -208,40 +189,56 @@ hipError_t launch_join16(selhip_ctx* c, const StageIO& io, int n_pad, const RowM
     return c->join_wpb == 1 ? launch_join16_w<ND, DB, 1>(c, io, n_pad, rm) : launch_join16_w<ND, DB, 4>(c, io, n_pad, rm);
 }
 
-// sig_build with the pass's bounds computation riding in its first blocks (with_bounds) or alone
-hipError_t launch_sig_build(selhip_ctx* c, int n_rows, int n_bands, bool with_bounds, double tau, int rb, int re, PassCounters* zero_pc) {
+// what sig_build_kernel takes besides the sketches and the arrays it writes.  The defaults are the build alone: no bounds blocks, 16-bit
+// pairs packed (never sliced) in P / G -- the database's signatures of the query passes, whatever "join_bits" and "join_form" say
+struct SigBuildPass {
+    unsigned work_blocks;
+    int bounds_blocks = 0;
+    const double* cards = nullptr; double tau = 0.0; int use_cb = 0; RowMap rm{0, 0, 1, 1, 0};
+    u64* ecard = nullptr; int* hi = nullptr; PassCounters* pc = nullptr;
+    int* csr_cnt = nullptr; int csr_cap = 0; int cand_begin = 0;
+    u64* seg_cnt = nullptr; int seg_cap = 0;
+    int pk_shift = 16;
+    PassCounters* zero_pc = nullptr;
+    int slice = 0;
+};
+
+// band signatures of the context's sketches in the band shape (n_rows, n_bands) into the four layouts of `s`
+hipError_t launch_sig_kernel(selhip_ctx* c, SigSet& s, int n_rows, int n_bands, const SigBuildShape& sh, const SigBuildPass& a) {
     const int n = (int)c->n;
-    const int n_pad = ((n + kWave - 1) / kWave) * kWave;
+    if (a.work_blocks + (unsigned)a.bounds_blocks == 0) return hipSuccess;
+    hipLaunchKernelGGL(sig_build_kernel, dim3(a.work_blocks + (unsigned)a.bounds_blocks), dim3(kBlock), 0, c->stream,
+                       c->d_aux, n, c->m, n_rows, n_bands, pad_wave(n), s.Q.p, s.T.p, s.P.p, s.G.p,
+                       a.bounds_blocks, a.cards, a.tau, a.use_cb, a.rm, a.ecard, a.hi, a.pc, a.csr_cnt, a.csr_cap, a.cand_begin,
+                       a.seg_cnt, a.seg_cap, a.pk_shift, a.zero_pc, sh.tile_g, a.slice);
+    return hipGetLastError();
+}
+
+// the all-pairs pass's build of the context's own signatures, with the pass's bounds computation riding in its first blocks
+hipError_t launch_sig_build(selhip_ctx* c, int n_rows, int n_bands, double tau, int rb, int re, PassCounters* zero_pc) {
+    const int n = (int)c->n;
     TimerScope t(c, T_SIGBUILD);
-    const int bounds_blocks = with_bounds ? (n + kBlock - 1) / kBlock : 0;
-    // tiled build (kSigTileG genomes per block, LDS transpose) for the shapes of the all-pairs joins; the per-bucket form otherwise
-    const bool tile_mode = sig_tile_mode(c, n_rows, n_bands);
-    const bool slice = join_sliced(c, n_rows, n_bands);                  // sigP / sigG bit-sliced instead of packed
-    const long long threads = n_rows <= kWave ? (long long)n * c->m : (long long)n * n_bands;
+    const SigBuildShape sh = sig_build_shape(c->m, n, n_rows, n_bands, c->sig_tile, c->sig_tile_g);
+    const bool slice = join_sliced(c, n_rows, n_bands);                  // sig.P / sig.G bit-sliced instead of packed
     // "sig_cache": the signatures depend on the sketches and the band shape only, so a context that runs many passes over the same
     // sketches (the ranks of a strong-scaled job, a threshold sweep) builds them once; upload / attach and any reallocation of the
     // signature arrays invalidate them.  The bounds blocks still run every pass (they depend on tau, the mode and the rows).  The key
     // holds the layout of sigP / sigG (15-bit, 16-bit packed or sliced), so a join never reads words written for another.
     const long long sig_key = ((long long)n_rows << 40) | ((long long)n_bands << 20) | ((long long)slice << 3) | ((long long)(c->join_bits == 15) << 2) |
-                              (tile_mode ? 2 : 0) | 1;
-    const bool cached = c->sig_cache && c->sig_key == sig_key && with_bounds;
-    const int tg = c->sig_tile_g;                                       // genomes per tile
-    const unsigned work_blocks = cached ? 0u : tile_mode ? (unsigned)((n + tg - 1) / tg) : (unsigned)((threads + kBlock - 1) / kBlock);
+                              (sh.tile_g ? 2 : 0) | 1;
+    const bool cached = c->sig_cache && c->sig_key == sig_key;
     c->sig_key = c->sig_cache ? sig_key : 0;
-    if (work_blocks + (unsigned)bounds_blocks == 0) return hipSuccess;
-    hipLaunchKernelGGL(sig_build_kernel, dim3(work_blocks + (unsigned)bounds_blocks), dim3(kBlock), 0, c->stream,
-                       c->d_aux, n, c->m, n_rows, n_bands, n_pad, c->sigQ.p, c->sigT.p, c->sigP.p, c->sigG.p,
-                       bounds_blocks, c->d_cards, tau, c->mode == SELHIP_MODE_CB_SMH ? 1 : 0, row_map(c, rb, re), c->ecard.p, c->hi.p, c->pcb,
-                       grouping_on(c) ? c->csr_cnt.p : nullptr, grouping_on(c) ? (int)c->csr_cnt.cap : 0, (int)c->cand_begin,
-                       with_bounds ? c->seg_cnt.p : nullptr, with_bounds ? (int)c->seg_cnt.cap : 0, c->join_bits == 15 ? 17 : 16,
-                       zero_pc, tile_mode ? tg : 0, slice ? 1 : 0);
-    return hipGetLastError();
+    const SigBuildPass a{cached ? 0u : sh.blocks, (n + kBlock - 1) / kBlock,
+                         c->d_cards, tau, c->mode == SELHIP_MODE_CB_SMH ? 1 : 0, row_map(c, rb, re), c->ecard.p, c->hi.p, c->pcb,
+                         grouping_on(c) ? c->csr_cnt.p : nullptr, grouping_on(c) ? (int)c->csr_cnt.cap : 0, (int)c->cand_begin,
+                         c->seg_cnt.p, (int)c->seg_cnt.cap, c->join_bits == 15 ? 17 : 16, zero_pc, slice ? 1 : 0};
+    return launch_sig_kernel(c, c->sig, n_rows, n_bands, sh, a);
 }
 
 // signature join + exact verification of the query rows [rb, re) (sig_build must have run)
 hipError_t launch_stage1_sig(selhip_ctx* c, const StageIO& io, int n_rows, int n_bands, const RowMap& rm) {
     const int n = (int)c->n;
-    const int n_pad = ((n + kWave - 1) / kWave) * kWave;
+    const int n_pad = pad_wave(n);
     hipError_t e = hipSuccess;
     if (c->join_bits == 16 || c->join_bits == 15) {
         {
@@ -259,7 +256,7 @@ hipError_t launch_stage1_sig(selhip_ctx* c, const StageIO& io, int n_rows, int n
         // the 16-bit matches were staged in the candidate list; survivors go to the survivor list as usual
         TimerScope t(c, T_VERIFY, io.st);
         static_assert(1024 % kAppendSegs == 0, "verify16_kernel: the grid is a multiple of the segment count");
-        hipLaunchKernelGGL(verify16_kernel, dim3(1024), dim3(kVerifyBlock), 0, io.st, c->d_aux, c->m, n_rows, n_bands, c->sigQ.p,
+        hipLaunchKernelGGL(verify16_kernel, dim3(1024), dim3(kVerifyBlock), 0, io.st, c->d_aux, c->m, n_rows, n_bands, c->sig.Q.p,
                            io.cand, io.seg_cnt, io.cap, io.surv, io.cap, io.pc, c->verify_fb, io.row_cnt, io.row_lab, n);
         return hipGetLastError();
     } else {
@@ -280,24 +277,29 @@ hipError_t launch_stage1_sig(selhip_ctx* c, const StageIO& io, int n_rows, int n
     return hipGetLastError();
 }
 
+// the keys (band << 32 | signature) and ranks of n genomes from their band-major signatures sigT, then sorted by key (rocPRIM) into
+// keys_out / vals_out; tmp holds tmp_bytes of rocPRIM's temporary storage (sized by a radix_sort_pairs call with a null pointer)
+hipError_t sort_band_keys(hipStream_t st, const uint32_t* sigT, int n, int n_bands, u64* keys_in, u64* keys_out, int* vals_in, int* vals_out,
+                          char* tmp, size_t tmp_bytes) {
+    const size_t total = (size_t)n * n_bands;
+    hipLaunchKernelGGL(sigkey_build_kernel, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+                       sigT, n, pad_wave(n), n_bands, keys_in, vals_in);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return rocprim::radix_sort_pairs(tmp, tmp_bytes, keys_in, keys_out, vals_in, vals_out, total, 0u, band_key_end_bit(n_bands), st);
+}
+
 // sort-based join of the band signatures (sig_build must have run); rows [rb, re)
 hipError_t launch_stage1_hashjoin(selhip_ctx* c, const StageIO& io, int n_rows, int n_bands, const RowMap& rm) {
     const int n = (int)c->n;
-    const int n_pad = ((n + kWave - 1) / kWave) * kWave;
     const long long total = (long long)n * n_bands;
     if (total <= 0) return hipSuccess;
     TimerScope t(c, T_JOIN, io.st);
-    hipLaunchKernelGGL(sigkey_build_kernel, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, io.st,
-                       c->sigT.p, n, n_pad, n_bands, c->hj_keys_in.p, c->hj_vals_in.p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    size_t tmp_bytes = c->hj_tmp.cap;
-    const unsigned end_bit = 32u + (unsigned)ilog2(n_bands) + 1u;
-    e = rocprim::radix_sort_pairs(c->hj_tmp.p, tmp_bytes, c->hj_keys_in.p, c->hj_keys_out.p, c->hj_vals_in.p, c->hj_vals_out.p,
-                                  (size_t)total, 0u, end_bit, io.st);
+    const hipError_t e = sort_band_keys(io.st, c->sig.T.p, n, n_bands, c->hj_keys_in.p, c->hj_keys_out.p, c->hj_vals_in.p, c->hj_vals_out.p,
+                                        c->hj_tmp.p, c->hj_tmp.cap);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(run_emit_kernel, dim3(grid_for((u64)total, kBlock, 8192)), dim3(kBlock), 0, io.st,
-                       c->hj_keys_out.p, c->hj_vals_out.p, total, c->sigQ.p, n_bands, c->d_aux, c->m, n_rows, n_bands,
+                       c->hj_keys_out.p, c->hj_vals_out.p, total, c->sig.Q.p, n_bands, c->d_aux, c->m, n_rows, n_bands,
                        n, c->hi.p, c->pcb, rm, io.surv, io.cap, io.pc);
     return hipGetLastError();
 }
@@ -308,20 +310,11 @@ hipError_t launch_select(bool fma, hipStream_t st, unsigned grid, const uint32_t
                          selhip_pair_t* results, u64 results_cap, PassCounters* pc,
                          selhip_result_t* rf32, int* out_count, u64 chunk_off = 0, u64 chunk_len = ~0ull) {
     const double rs = relerr_scaled_for(p);
-    if (fma)
-        hipLaunchKernelGGL((ertl_select_kernel<true, MODE>), dim3((grid + kWavesPerBlock - 1) / kWavesPerBlock), dim3(kBlock), 0, st, counts, n_dev, n_host, cap,
+    with_flag(fma, [&](auto F) {
+        hipLaunchKernelGGL((ertl_select_kernel<decltype(F)::value, MODE>), dim3((grid + kWavesPerBlock - 1) / kWavesPerBlock), dim3(kBlock), 0, st, counts, n_dev, n_host, cap,
                            p, rs, est, pairs, ecard, tau, results, results_cap, pc, rf32, out_count, chunk_off, chunk_len);
-    else
-        hipLaunchKernelGGL((ertl_select_kernel<false, MODE>), dim3((grid + kWavesPerBlock - 1) / kWavesPerBlock), dim3(kBlock), 0, st, counts, n_dev, n_host, cap,
-                           p, rs, est, pairs, ecard, tau, results, results_cap, pc, rf32, out_count, chunk_off, chunk_len);
+    });
     return hipGetLastError();
-}
-
-unsigned grid_for(u64 items, unsigned per_block, unsigned max_blocks) {
-    u64 b = (items + per_block - 1) / per_block;
-    if (b < 1) b = 1;
-    if (b > max_blocks) b = max_blocks;
-    return (unsigned)b;
 }
 
 // ---- stage 2a on bit planes (kernel_hllbs.cuh) -------------------------------------------------
@@ -355,9 +348,11 @@ hipError_t launch_hist_bs(int khi, unsigned blocks, hipStream_t st, const uint32
                           u64 cap, uint32_t* counts, u64 off, u64 window, int run, u64 dense_pairs, int sparse_t = 0, const uint32_t* lists = nullptr) {
     // (a threshold at or above khi leaves every list empty: there the full decode's per-pair walks already stop below it)
     const int g1 = sparse_t > 0 && sparse_t < khi && lists ? sparse_t / 4 : 0;
-    if (khi <= 16)      launch_hist_bs_nb<4>(g1, blocks, st, bs, gmax, lists, list, count, cap, counts, off, window, run, dense_pairs);
-    else if (khi <= 32) launch_hist_bs_nb<5>(g1, blocks, st, bs, gmax, lists, list, count, cap, counts, off, window, run, dense_pairs);
-    else                launch_hist_bs_nb<6>(g1, blocks, st, bs, gmax, lists, list, count, cap, counts, off, window, run, dense_pairs);
+    switch (bs_planes(khi)) {
+        case 4:  launch_hist_bs_nb<4>(g1, blocks, st, bs, gmax, lists, list, count, cap, counts, off, window, run, dense_pairs); break;
+        case 5:  launch_hist_bs_nb<5>(g1, blocks, st, bs, gmax, lists, list, count, cap, counts, off, window, run, dense_pairs); break;
+        default: launch_hist_bs_nb<6>(g1, blocks, st, bs, gmax, lists, list, count, cap, counts, off, window, run, dense_pairs);
+    }
     return hipGetLastError();
 }
 
@@ -380,28 +375,16 @@ int build_sparse_lists(std::string* err, hipStream_t st, const uint32_t* d_bs, i
     return SELHIP_OK;
 }
 
-// writes the bit planes of n genomes and returns max register value + 1 through *khi (waits for the stream)
-int build_bitslices(std::string* err, hipStream_t st, const uint8_t* d_hll, int64_t n, uint32_t* d_bs, uint8_t* d_gmax, int* d_max, int* khi) {
-    HIPCHK(err, hipMemsetAsync(d_max, 0, sizeof(int), st));
-    hipLaunchKernelGGL(hll_bitslice_kernel, dim3(grid_for((u64)n, kWavesPerBlock, 8192)), dim3(kBlock), 0, st, d_hll, (long long)n, d_bs, d_gmax, d_max);
-    HIPCHK(err, hipGetLastError());
-    int mx = 0;
-    HIPCHK(err, hipMemcpyAsync(&mx, d_max, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(err, hipStreamSynchronize(st));
-    *khi = mx + 1;
-    return SELHIP_OK;
-}
-
-bool use_bitslices(const selhip_ctx* c) { return c->p == 14 && c->hll_khi > 0 && c->hist_algo != 0; }
+bool use_bitslices(const selhip_ctx* c) { return c->p == 14 && c->planes.khi > 0 && c->hist_algo != 0; }
 // the all-pairs stage 2a's sparse threshold in use (0 = every value from the planes)
 // Automatic ("hist_sparse" = -1): only where the set's planes fit the Infinity Cache.  Beyond it the kernel is bound by its fetches of
 // candidate rows, not by instructions: cfg4 (50 000 genomes, 600 MB of planes) 144.5 -> 146.8 us, its step 1.502 -> 1.515 ms with the
 // lists (profiles/hist_sparse_ab.txt), while cfg3 and --hard gain 6 % and 23 % a step.
 constexpr size_t kSparseMaxPlaneBytes = (size_t)192 << 20;
 int sparse_t_used(const selhip_ctx* c) {
-    if (!use_bitslices(c) || !c->hist_sparse || c->hll_sparse_t >= c->hll_khi) return 0;
+    if (!use_bitslices(c) || !c->hist_sparse || c->hll_sparse_t >= c->planes.khi) return 0;
     if (c->hist_sparse < 0 && (size_t)c->n * kBsGenomeDwords * sizeof(uint32_t) > kSparseMaxPlaneBytes) return 0;
-    if (c->hll_sparse_t > 20 && c->hll_khi <= 32) return 0;                                   // (launch_hist_bs_nb: five planes, G1 = 6)
+    if (c->hll_sparse_t > 20 && c->planes.khi <= 32) return 0;                                   // (launch_hist_bs_nb: five planes, G1 = 6)
     return c->hll_sparse_t;
 }
 
@@ -420,17 +403,6 @@ int compute_cards(selhip_ctx* c, const uint8_t* d_hll, int64_t n, int p, double*
     return SELHIP_OK;
 }
 
-// criteria_sketch.hpp:7-20 sigma(p): a double expression narrowed to float by the return type
-float sigma_p_of(int p) {
-    switch (p) {
-        case 4: return (float)(1.106 / std::sqrt((double)(1 << p)));
-        case 5: return (float)(1.07 / std::sqrt((double)(1 << p)));
-        case 6: return (float)(1.054 / std::sqrt((double)(1 << p)));
-        case 7: return (float)(1.046 / std::sqrt((double)(1 << p)));
-    }
-    return (float)(1.039 / std::sqrt((double)(1 << p)));
-}
-
 // upper bound of the pair space of rows [rb, re): the triangle (CB can only shrink it)
 long long pair_bound(long long n, long long rb, long long re) {
     long long cnt = 0;
@@ -443,18 +415,12 @@ long long pair_bound(long long n, long long rb, long long re) {
 template <int CRIT>
 hipError_t launch_aux_fused(selhip_ctx* c, hipStream_t st, const selhip_int2_t* list, const u64* n_dev, u64 cap, u64 bound, double tau,
                             selhip_int2_t* out, u64 out_cap, u64* out_count) {
-    const float Z = 1.96f;                                   // z_score, selection.cpp:76
-    const float zs_f = Z * sigma_p_of(c->p_aux);             // float * float (criteria_sketch.hpp:29,40)
-    const double zs = (double)zs_f;
-    const double S_sum = zs;                                 // order_n = 1 (selection.cpp:77): S = Z*sigma_p
-    const double rs = relerr_scaled_for(c->p_aux);
+    const AuxConsts k = aux_consts(c->p_aux);
     const unsigned grid = grid_for(bound, kWave, 32768);
-    if (c->fp_mode == SELHIP_FP_FMA)
-        hipLaunchKernelGGL((aux_fused_kernel<true, CRIT>), dim3(grid), dim3(kWave), 0, st, c->d_aux_hll, c->p_aux, list, n_dev, cap,
-                           rs, c->ecard.p, tau, zs, S_sum, out, out_cap, out_count);
-    else
-        hipLaunchKernelGGL((aux_fused_kernel<false, CRIT>), dim3(grid), dim3(kWave), 0, st, c->d_aux_hll, c->p_aux, list, n_dev, cap,
-                           rs, c->ecard.p, tau, zs, S_sum, out, out_cap, out_count);
+    with_flag(c->fp_mode == SELHIP_FP_FMA, [&](auto F) {
+        hipLaunchKernelGGL((aux_fused_kernel<decltype(F)::value, CRIT>), dim3(grid), dim3(kWave), 0, st, c->d_aux_hll, c->p_aux, list, n_dev, cap,
+                           k.rs, c->ecard.p, tau, k.zs, k.S_sum, out, out_cap, out_count);
+    });
     return hipGetLastError();
 }
 
@@ -480,15 +446,16 @@ void chunk_rows(long long n, long long rb, long long re, int chunks, long long p
     bnd[chunks] = re;
 }
 
+// the pass joins 16-bit (or 15-bit) signature pairs and verifies what they pass on (launch_stage1_sig's first branch)
+bool join16_pass(const selhip_ctx* c) { return c->plan.use_sig && !c->plan.use_hash && c->join_bits <= 16; }
+
 int pipeline_chunks(const selhip_ctx* c) {
     // Round 1's pipeline (stage 1 of every chunk on one stream, stage 2 on another) lost on every configuration and was replaced
     // by whole-chain lanes (enqueue_pass).  Automatic setting: two chunks for the signature join once a pass is large enough for
     // the second set of tail launches to cost less than the overlap wins (measured: profiles/r02_chunk_lanes.txt).
-    const bool smh = c->criterion == SELHIP_CRIT_SMH_A || c->criterion == SELHIP_CRIT_HLL_A_SMH_A;
-    if (!smh || c->pipeline == 0 || c->pipeline == 1 || c->algo == SELHIP_ALGO_HASHJOIN) return 1;   // (the sort join works on all rows at once)
+    if (!c->plan.smh || c->pipeline == 0 || c->pipeline == 1 || c->plan.use_hash) return 1;   // (the sort join works on all rows at once)
     if (c->pipeline > 1) return std::min(c->pipeline, kMaxChunks);
-    const bool sig = c->algo != SELHIP_ALGO_STREAM && c->join_bits <= 16 && sig_supported(c->m, c->n_rows, c->n_bands);
-    if (!sig || !grouping_on(c)) return 1;
+    if (!join16_pass(c) || !grouping_on(c)) return 1;
     const double pairs = (double)pair_bound(c->n, c->row_begin, c->row_end) / std::max(1, c->il_parts);
     return pairs >= kAutoChunkPairs ? 2 : 1;
 }
@@ -584,7 +551,7 @@ int enqueue_tail(selhip_ctx* c, const Chain& ch, const selhip_int2_t* final_list
         {
             TimerScope t(c, T_HIST, st);
             if (use_bitslices(c))
-                HIPCHK(&c->err, launch_hist_bs(c->hll_khi, (unsigned)c->hist_bs_blocks, st, c->hll_bs.p, c->hll_gmax.p, final_list, final_count, final_cap, ch.counts, off, ch.window,
+                HIPCHK(&c->err, launch_hist_bs(c->planes.khi, (unsigned)c->hist_bs_blocks, st, c->planes.bs.p, c->planes.gmax.p, final_list, final_count, final_cap, ch.counts, off, ch.window,
                                                c->hist_run > 0 ? c->hist_run : (grouped ? 4 : 1),
                                                // a dense survivor graph is walked by candidate-row slice per XCD (query-major list only)
                                                // ("dense" = survivors per QUERY ROW of this chain: a rank's or a lane's share of the rows sees
@@ -642,25 +609,21 @@ int enqueue_chain(selhip_ctx* c, const Chain& ch, int rb, int re, double tau, bo
 bool small_pass_ok(const selhip_ctx* c) {
     if (c->small_pass == 0 || c->small_pass_failed) return false;
     if (c->n < 2 || c->n > kSmallPassMaxN || c->criterion != SELHIP_CRIT_SMH_A || c->il_parts > 1) return false;
-    if (!(c->algo == SELHIP_ALGO_AUTO || c->algo == SELHIP_ALGO_SIG) || !sig_supported(c->m, c->n_rows, c->n_bands)) return false;
-    if (!(is_pow2(c->m) && c->n_rows >= 2 && c->n_rows <= 32 && c->m >= 4)) return false;          // the tiled signature build
+    if (!c->plan.use_sig || c->plan.use_hash) return false;
+    if (!sig_tile_shape(c->m, c->n_rows, c->n_bands)) return false;          // the kernel always builds in tiles, whatever "sig_tile" says
     if ((c->row_end - c->row_begin + 255) / 256 > kSmallRows) return false;                        // rows per block of the 256-block grid
     if (c->dev_cus < 256) return false;                                                            // (a partitioned or masked device: the regular pass)
-    return use_bitslices(c) && c->hll_khi <= 32;                                                   // bit planes, at most five of them non-zero
-}
-
-hipError_t hipModuleLaunchKernel_like(selhip_ctx* c, const void* fn, unsigned grid, void** args) {
-    return hipLaunchKernel(fn, dim3(grid), dim3(kBlock), args, 0, c->stream);
+    return use_bitslices(c) && c->planes.khi <= 32;                                                   // bit planes, at most five of them non-zero
 }
 
 template <bool FMA, int NB>
 hipError_t launch_small_pass(selhip_ctx* c, PassCounters* pc_next, double tau) {
     int n = (int)c->n;
-    int n_pad = ((n + kWave - 1) / kWave) * kWave;
+    int n_pad = pad_wave(n);
     RowMap rm = row_map(c, (int)c->row_begin, (int)c->row_end);
     int m = c->m, r = c->n_rows, nb = c->n_bands, use_cb = c->mode == SELHIP_MODE_CB_SMH ? 1 : 0, cand_begin = (int)c->cand_begin, fb = c->verify_fb;
-    const u64* aux = c->d_aux; const double* cards = c->d_cards; const uint32_t* bs = c->hll_bs.p; const uint8_t* gmax = c->hll_gmax.p;
-    uint32_t *sQ = c->sigQ.p, *sT = c->sigT.p, *sP = c->sigP.p, *sG = c->sigG.p;
+    const u64* aux = c->d_aux; const double* cards = c->d_cards; const uint32_t* bs = c->planes.bs.p; const uint8_t* gmax = c->planes.gmax.p;
+    uint32_t *sQ = c->sig.Q.p, *sT = c->sig.T.p, *sP = c->sig.P.p, *sG = c->sig.G.p;
     u64* ecard = c->ecard.p; int* hi = c->hi.p; PassCounters* pc = c->pcb;
     u64* barrier_word = &c->pcb[kMaxChunks].n_aux_in;                   // a word of this pass's counter set that nothing else uses (cleared by the previous pass)
     if (!c->small_bar.p) {                                               // the barrier's group words: zero between passes (the kernel puts them back)
@@ -680,16 +643,15 @@ hipError_t launch_small_pass(selhip_ctx* c, PassCounters* pc_next, double tau) {
     // by then; nothing another stream runs waits for this kernel); hipLaunchCooperativeKernel ("small_pass" = 2) asks the runtime for
     // that guarantee and costs ~15 us more per launch
     if (c->small_pass == 2) return hipLaunchCooperativeKernel((const void*)small_pass_kernel<FMA, NB>, dim3(grid), dim3(kBlock), args, 0, c->stream);
-    return hipModuleLaunchKernel_like(c, (const void*)small_pass_kernel<FMA, NB>, grid, args);
+    return hipLaunchKernel((const void*)small_pass_kernel<FMA, NB>, dim3(grid), dim3(kBlock), args, 0, c->stream);
 }
 
 int enqueue_small_pass(selhip_ctx* c, PassCounters* pc_next, double tau) {
     TimerScope t(c, T_STAGE1);
-    const bool fma = c->fp_mode == SELHIP_FP_FMA;
     c->sig_key = 0;                                                      // (the kernel rewrites the 32-bit signature layouts only)
-    hipError_t e;
-    if (c->hll_khi <= 16) e = fma ? launch_small_pass<true, 4>(c, pc_next, tau) : launch_small_pass<false, 4>(c, pc_next, tau);
-    else                  e = fma ? launch_small_pass<true, 5>(c, pc_next, tau) : launch_small_pass<false, 5>(c, pc_next, tau);
+    const hipError_t e = with_flag(c->fp_mode == SELHIP_FP_FMA, [&](auto F) {
+        return bs_planes(c->planes.khi) == 4 ? launch_small_pass<decltype(F)::value, 4>(c, pc_next, tau) : launch_small_pass<decltype(F)::value, 5>(c, pc_next, tau);
+    });
     HIPCHK(&c->err, e);
     return SELHIP_OK;
 }
@@ -699,38 +661,19 @@ int enqueue_pass(selhip_ctx* c) {
     const int rb = (int)c->row_begin, re = (int)c->row_end;
     const double tau = (double)c->tau_f;            // float threshold widened, selection.cpp:81,164
     const int crit = c->criterion;
-    {
-        const bool smh = crit == SELHIP_CRIT_SMH_A || crit == SELHIP_CRIT_HLL_A_SMH_A;
-        const bool sig = smh && (c->algo == SELHIP_ALGO_HASHJOIN ||
-                                 ((c->algo == SELHIP_ALGO_SIG || c->algo == SELHIP_ALGO_AUTO) && sig_supported(c->m, c->n_rows, c->n_bands)));
-        c->dominant_timer = c->timed_kernel == 1 ? T_HIST : (sig ? T_JOIN : T_STAGE1);
-        if (c->timing) c->timed_passes += 1;
-    }
+    const PassPlan& plan = c->plan;
+    c->dominant_timer = c->timed_kernel == 1 ? T_HIST : (plan.use_sig ? T_JOIN : T_STAGE1);
+    if (c->timing) c->timed_passes += 1;
     TimerScope total(c, T_TOTAL);
-    const bool smh_crit = crit == SELHIP_CRIT_SMH_A || crit == SELHIP_CRIT_HLL_A_SMH_A;
-    const bool use_hash = smh_crit && c->algo == SELHIP_ALGO_HASHJOIN;
-    const bool use_sig = use_hash || (smh_crit && (c->algo == SELHIP_ALGO_SIG || c->algo == SELHIP_ALGO_AUTO) &&
-                                      sig_supported(c->m, c->n_rows, c->n_bands));
-    if (smh_crit && c->algo == SELHIP_ALGO_SIG && !use_sig) {
-        set_err(&c->err, "ALGO_SIG needs power-of-two rows and 8..128 bands (got %d x %d)", c->n_rows, c->n_bands);
-        return SELHIP_E_BADARG;
-    }
-    if (use_hash && (!is_pow2(c->n_rows) || c->n_bands > 65536)) {
-        set_err(&c->err, "ALGO_HASHJOIN needs power-of-two rows (got %d x %d)", c->n_rows, c->n_bands);
-        return SELHIP_E_BADARG;
-    }
+    const bool smh_crit = plan.smh, use_hash = plan.use_hash, use_sig = plan.use_sig;
+    if (plan.bad) { set_err(&c->err, plan.bad, c->n_rows, c->n_bands); return SELHIP_E_BADARG; }
     // counter set of this pass (block 0: z0, evaluated, results; blocks 1.. : one per row chunk); the other set is cleared by
-    // this pass's first kernel for the next pass -- no memset dispatch on the stream.  (Chosen only now: nothing above launches, and
-    // an argument error must not consume a set that no kernel has cleared.)
-    if (c->pc_dirty) {
-        // the previous enqueue failed after it had claimed its counter set (its first kernel, which clears the other set for this pass,
-        // may never have run), or the stream changed behind the initial memset: clear both sets here, once
-        HIPCHK(&c->err, hipMemsetAsync(c->pc.p, 0, sizeof(PassCounters) * 2 * (kMaxChunks + 1), c->stream));
-    }
-    c->pcb = c->pc.p + (size_t)c->pc_flip * (kMaxChunks + 1);
-    PassCounters* const pc_next = c->pc.p + (size_t)(c->pc_flip ^ 1) * (kMaxChunks + 1);
-    c->pc_flip ^= 1;
-    c->pc_dirty = true;                                  // until this function returns SELHIP_OK
+    // this pass's first kernel for the next pass.  (Claimed only now: nothing above launches, and an argument error must not consume
+    // a set that no kernel has cleared.)  It stays dirty until this function returns SELHIP_OK
+    CounterSets::Claim pcs;
+    HIPCHK(&c->err, c->pc.claim(c->stream, &pcs));
+    c->pcb = pcs.cur;
+    PassCounters* const pc_next = pcs.next;
     PassCounters* pc0 = c->pcb;
     if (c->fail_after_flip) { c->fail_after_flip = 0; set_err(&c->err, "test hook: enqueue failed after the counter flip"); return SELHIP_E_HIP; }
     c->small_used = small_pass_ok(c);
@@ -739,12 +682,12 @@ int enqueue_pass(selhip_ctx* c) {
         const int rc = enqueue_small_pass(c, pc_next, tau);
         if (rc) return rc;
         HIPCHK(&c->err, hipMemcpyAsync(c->h_pc, c->pcb, sizeof(PassCounters) * (kMaxChunks + 1), hipMemcpyDeviceToHost, c->stream));
-        c->pc_dirty = false;
+        c->pc.dirty = false;
         return SELHIP_OK;
     }
     if (use_sig) {
         // bounds (truncated cards, CB cut-offs, z0, evaluated count) ride in the first blocks of the signature build
-        HIPCHK(&c->err, launch_sig_build(c, c->n_rows, c->n_bands, true, tau, rb, re, pc_next));
+        HIPCHK(&c->err, launch_sig_build(c, c->n_rows, c->n_bands, tau, rb, re, pc_next));
     } else {
         TimerScope t(c, T_PREP);
         hipLaunchKernelGGL(cb_bounds_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
@@ -752,7 +695,7 @@ int enqueue_pass(selhip_ctx* c) {
                            grouping_on(c) ? c->csr_cnt.p : nullptr, grouping_on(c) ? (int)c->csr_cnt.cap : 0, (int)c->cand_begin, pc_next,
                            c->seg_cnt.p, (int)c->seg_cnt.cap);
         HIPCHK(&c->err, hipGetLastError());
-        if (smh_crit && stream_supported(c->m, c->n_rows)) {
+        if (plan.il_stream) {
             // ALGO_STREAM: the bucket-interleaved copy of the sketches (lane l = buckets [l*B, (l+1)*B)), rebuilt every pass
             const int nch = c->m / 128;
             const long long total = (long long)c->n * nch * kWave;
@@ -764,7 +707,7 @@ int enqueue_pass(selhip_ctx* c) {
 
     const int chunks = pipeline_chunks(c);
     c->n_chunks_last = chunks;
-    const bool count_in_verify = crit == SELHIP_CRIT_SMH_A && use_sig && !use_hash && c->join_bits <= 16 && grouping_on(c);
+    const bool count_in_verify = crit == SELHIP_CRIT_SMH_A && join16_pass(c) && grouping_on(c);
     // chunk k's slices of the pass's buffers (one chunk = the whole of each)
     auto chain_of = [&](int k, hipStream_t st, long long b, long long e) {
         const u64 slice = (u64)c->surv.cap / (u64)chunks;
@@ -807,7 +750,7 @@ int enqueue_pass(selhip_ctx* c) {
         HIPCHK(&c->err, hipEventRecord(c->ev_end, lane[1]));
         HIPCHK(&c->err, hipStreamWaitEvent(c->stream, c->ev_end, 0));
         HIPCHK(&c->err, hipMemcpyAsync(c->h_pc, c->pcb, sizeof(PassCounters) * (kMaxChunks + 1), hipMemcpyDeviceToHost, c->stream));
-        c->pc_dirty = false;
+        c->pc.dirty = false;
         return SELHIP_OK;
     }
 
@@ -862,17 +805,17 @@ int enqueue_pass(selhip_ctx* c) {
     // (handing the counters to the host from the last block of the final kernel instead of this copy was tried: the 1 024
     // "block done" atomics on one address cost 16 us, the copy dispatch 4)
     HIPCHK(&c->err, hipMemcpyAsync(c->h_pc, c->pcb, sizeof(PassCounters) * (kMaxChunks + 1), hipMemcpyDeviceToHost, c->stream));
-    c->pc_dirty = false;
+    c->pc.dirty = false;
     return SELHIP_OK;
 }
 
 int ensure_scratch(selhip_ctx* c, size_t surv_cap, size_t res_cap) {
     HIPCHK(&c->err, c->ecard.ensure((size_t)c->n));
     HIPCHK(&c->err, c->hi.ensure((size_t)c->n));
-    if (!c->pc.p) {
-        HIPCHK(&c->err, c->pc.ensure(2 * (kMaxChunks + 1)));
-        HIPCHK(&c->err, hipMemsetAsync(c->pc.p, 0, sizeof(PassCounters) * 2 * (kMaxChunks + 1), c->stream));
-        c->pc_flip = 0;
+    if (!c->pc.buf.p) {
+        HIPCHK(&c->err, c->pc.buf.ensure(2 * (kMaxChunks + 1)));
+        HIPCHK(&c->err, hipMemsetAsync(c->pc.buf.p, 0, sizeof(PassCounters) * 2 * (kMaxChunks + 1), c->stream));
+        c->pc.flip = 0;
     }
     HIPCHK(&c->err, c->seg_cnt.ensure(kSegCounterSlots));
     if (!c->st_stage1) {
@@ -893,19 +836,14 @@ int ensure_scratch(selhip_ctx* c, size_t surv_cap, size_t res_cap) {
         HIPCHK(&c->err, c->cand.ensure((size_t)bound + 1024));
     }
     {
-        const size_t n_pad = (((size_t)c->n + kWave - 1) / kWave) * kWave;
         const size_t nb = (size_t)std::max(c->n_bands, 1);
         const bool hash = c->algo == SELHIP_ALGO_HASHJOIN;
-        const bool smh = c->criterion == SELHIP_CRIT_SMH_A || c->criterion == SELHIP_CRIT_HLL_A_SMH_A;
-        const bool sig_path = hash || ((c->algo == SELHIP_ALGO_SIG || c->algo == SELHIP_ALGO_AUTO) && sig_supported(c->m, c->n_rows, c->n_bands));
-        if (smh && !sig_path && stream_supported(c->m, c->n_rows)) HIPCHK(&c->err, c->aux_il.ensure((size_t)c->n * c->m));
+        if (c->plan.il_stream) HIPCHK(&c->err, c->aux_il.ensure((size_t)c->n * c->m));
         if (nb <= 128 || hash) {
-            const uint32_t* const old_sig[4] = {c->sigQ.p, c->sigT.p, c->sigP.p, c->sigG.p};
-            struct SigGuard { selhip_ctx* c; const uint32_t* const* o; ~SigGuard() { if (c->sigQ.p != o[0] || c->sigT.p != o[1] || c->sigP.p != o[2] || c->sigG.p != o[3]) c->sig_key = 0; } } guard{c, old_sig};
-            HIPCHK(&c->err, c->sigQ.ensure((size_t)c->n * nb));
-            HIPCHK(&c->err, c->sigT.ensure(n_pad * nb));
-            HIPCHK(&c->err, c->sigP.ensure(n_pad * (size_t)((nb + 1) / 2)));
-            HIPCHK(&c->err, c->sigG.ensure((n_pad + 2) * (size_t)((nb + 1) / 2)));
+            bool moved = false;
+            const hipError_t e = c->sig.ensure((size_t)c->n, nb, &moved);
+            if (moved) c->sig_key = 0;                                      // the cached signatures went with the arrays
+            HIPCHK(&c->err, e);
         }
         if (hash) {
             const size_t total = (size_t)c->n * nb;

@@ -1,0 +1,114 @@
+// host_plan.hpp -- the decisions of the host side that are plain arithmetic, each written once: padding and grids, the shape of a
+// signature build, the bit-plane count of a register range, which stage 1 a pass runs, the constants of the auxiliary criterion and
+// the growth rule after an overflow.  Nothing here touches the device or the context.
+// Part of the kernel translation unit selection_kernels.hip (included there, before host_context.hpp); not a stand-alone header.
+#pragma once
+
+namespace {
+
+bool is_pow2(int x) { return x > 0 && (x & (x - 1)) == 0; }
+int ilog2(int x) { int l = 0; while ((1 << l) < x) ++l; return l; }
+
+// n rounded up to whole waves: the row pitch of the band-major signature layouts
+template <typename T>
+T pad_wave(T n) { return ((n + kWave - 1) / kWave) * kWave; }
+
+unsigned grid_for(u64 items, unsigned per_block, unsigned max_blocks) {
+    u64 b = (items + per_block - 1) / per_block;
+    if (b < 1) b = 1;
+    if (b > max_blocks) b = max_blocks;
+    return (unsigned)b;
+}
+
+double relerr_scaled_for(int p) {
+    // hll.h:662  relerr /= std::sqrt(m), relerr = 1e-2 (hll.h:211 default, :257)
+    return 1e-2 / std::sqrt((double)(1ull << p));
+}
+
+// criteria_sketch.hpp:7-20 sigma(p): a double expression narrowed to float by the return type
+float sigma_p_of(int p) {
+    switch (p) {
+        case 4: return (float)(1.106 / std::sqrt((double)(1 << p)));
+        case 5: return (float)(1.07 / std::sqrt((double)(1 << p)));
+        case 6: return (float)(1.054 / std::sqrt((double)(1 << p)));
+        case 7: return (float)(1.046 / std::sqrt((double)(1 << p)));
+    }
+    return (float)(1.039 / std::sqrt((double)(1 << p)));
+}
+
+// what the kernels of the auxiliary-HLL criterion take for a precision p_aux.  One function for the all-pairs and the query passes, so
+// the float / double roundings are the same in both
+struct AuxConsts { double zs, S_sum, rs; };
+AuxConsts aux_consts(int p_aux) {
+    const float Z = 1.96f;                                   // z_score, selection.cpp:76
+    const float zs_f = Z * sigma_p_of(p_aux);                // float * float (criteria_sketch.hpp:29,40)
+    const double zs = (double)zs_f;
+    return {zs, zs /* order_n = 1 (selection.cpp:77): S = Z*sigma_p */, relerr_scaled_for(p_aux)};
+}
+
+// ---- band shapes ------------------------------------------------------------------------------
+bool stream_supported(int m, int n_rows) {
+    return is_pow2(m) && m >= 128 && m <= 2048 && is_pow2(n_rows) && n_rows <= m;
+}
+
+bool sig_supported(int n_rows, int n_bands) {
+    return is_pow2(n_rows) && (n_bands == 8 || n_bands == 16 || n_bands == 32 || n_bands == 64 || n_bands == 128);
+}
+
+// the tiled signature build (sig_build_tile_body) takes this band shape
+bool sig_tile_shape(int m, int n_rows, int n_bands) {
+    return is_pow2(m) && is_pow2(n_bands) && n_bands <= 128 && n_rows >= 2 && n_rows <= 32 && m >= 4;
+}
+
+// the grid of one signature build of n genomes: tiled (tile_g genomes per block, LDS transpose) for the shapes of the all-pairs joins
+// unless "sig_tile" is off; one thread per bucket (tile_g = 0) otherwise
+struct SigBuildShape { int tile_g; unsigned blocks; };
+SigBuildShape sig_build_shape(int m, int n, int n_rows, int n_bands, int sig_tile, int sig_tile_g) {
+    if (sig_tile && sig_tile_shape(m, n_rows, n_bands)) return {sig_tile_g, (unsigned)((n + sig_tile_g - 1) / sig_tile_g)};
+    const long long threads = n_rows <= kWave ? (long long)n * m : (long long)n * n_bands;
+    return {0, (unsigned)((threads + kBlock - 1) / kBlock)};
+}
+
+// bit planes that can be non-zero in a set whose largest register value is khi - 1: the NB of the stage-2a kernels
+int bs_planes(int khi) { return khi <= 16 ? 4 : khi <= 32 ? 5 : 6; }
+
+// ---- which stage 1 a pass runs ------------------------------------------------------------------
+// smh: the criterion has an smh_a stage at all (hll_a / hll_an alone read neither the band shape nor the algorithm).  use_sig: band
+// signatures are built and joined (use_hash: by the sort join; use_index: a query pass probes the sorted index instead of joining);
+// il_stream: ALGO_STREAM in its tiled form, which reads the bucket-interleaved copy of the sketches.  bad: the format of the error
+// (it takes n_rows, n_bands) when the caller insisted on an algorithm that does not take the band shape
+struct PassPlan {
+    bool smh = false, use_hash = false, use_sig = false, use_index = false, il_stream = false;
+    const char* bad = nullptr;
+};
+PassPlan pass_plan(int criterion, int algo, int m, int n_rows, int n_bands) {
+    PassPlan p;
+    p.smh = criterion == SELHIP_CRIT_SMH_A || criterion == SELHIP_CRIT_HLL_A_SMH_A;
+    if (!p.smh) return p;
+    const bool sig_ok = sig_supported(n_rows, n_bands);
+    p.use_hash = algo == SELHIP_ALGO_HASHJOIN;
+    p.use_index = algo == SELHIP_ALGO_INDEX;
+    p.use_sig = p.use_hash || (algo != SELHIP_ALGO_STREAM && sig_ok);
+    p.il_stream = !p.use_sig && stream_supported(m, n_rows);
+    if (algo == SELHIP_ALGO_SIG && !sig_ok) p.bad = "ALGO_SIG needs power-of-two rows and 8..128 bands (got %d x %d)";
+    else if (p.use_index && !sig_ok) p.bad = "ALGO_INDEX needs power-of-two rows and 8..128 bands (got %d x %d)";   // (no fallback: the caller asked for the index)
+    else if (p.use_hash && (!is_pow2(n_rows) || n_bands > 65536)) p.bad = "ALGO_HASHJOIN needs power-of-two rows (got %d x %d)";
+    return p;
+}
+
+// ---- after an overflow --------------------------------------------------------------------------
+// The counts a pass reports are exact even when a list was too small, so the list grows once, to the count and an eighth, and the pass
+// repeats; kMaxAttempts enqueues in all
+constexpr int kMaxAttempts = 8;
+size_t grown(u64 worst) { return (size_t)(worst + worst / 8 + 1024); }
+// the result list: true (and its new capacity in *res_cap) when the pass selected more pairs than it holds
+bool results_overflowed(u64 n_results, size_t have, size_t* res_cap) {
+    if (n_results <= have) return false;
+    *res_cap = grown(n_results);
+    return true;
+}
+
+// bit range of the band keys (band << 32 | signature) that the sort join and the query index sort
+unsigned band_key_end_bit(int n_bands) { return 32u + (unsigned)ilog2(n_bands) + 1u; }
+
+}  // namespace

@@ -6,7 +6,7 @@
 // with the RESULT SEMANTICS of the CPU path src/selection.cpp:270-291 (see include/selection_hip.h).
 //
 // This is the kernel translation unit of the library: it only includes.  The kernels live in the kernel_*.cuh headers (all integer
-// except the estimator; no MFMA), the host side in host_context.hpp (context), host_pass.hpp (pass scheduler) and abi_*.inc (C ABI);
+// except the estimator; no MFMA), the host side in host_plan.hpp (decisions), host_context.hpp (context), host_pass.hpp (pass scheduler) and abi_*.inc (C ABI);
 // the multi-GPU and out-of-core drivers are translation units of their own (selhip_multi.hip, selhip_ooc.hip):
 //   common.cuh          launch constants, per-pass counters, WaveAppender (LDS-staged appends, one atomic per flush)
 //   kernel_bounds.cuh   cb_bounds_kernel      e_i = (size_t)card_i, CB cut-off hi(i), first non-zero rank
@@ -61,7 +61,8 @@
 #include "kernel_query_aux.cuh"
 #include "kernel_query_index.cuh"
 
-#include "host_context.hpp"      // struct selhip_ctx, device buffers, timers, helpers
+#include "host_plan.hpp"         // host decisions that are plain arithmetic: build shape, pass plan, criterion constants, overflow rule
+#include "host_context.hpp"      // struct selhip_ctx, device buffers (signature sets, bit planes, counter sets), timers, helpers
 #include "host_pass.hpp"         // pass scheduler: dispatch of every stage, chunk lanes, scratch sizing
 #include "host_query.hpp"        // query passes: Q x D (windows, signature join or stream, verification, stage 2)
 #include "abi_context.inc"       // C ABI: context (create, upload / attach, run, results, timing)
