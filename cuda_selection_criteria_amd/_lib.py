@@ -42,7 +42,7 @@ class Synth(C.Structure):
 MODE_SMH, MODE_CB_SMH = 0, 1
 ALGO_AUTO, ALGO_STREAM, ALGO_SIG, ALGO_HASHJOIN, ALGO_INDEX = 0, 1, 2, 3, 4    # ALGO_INDEX: query passes only
 FP_STRICT, FP_FMA = 0, 1
-CRIT_SMH_A, CRIT_HLL_A, CRIT_HLL_AN, CRIT_HLL_A_SMH_A = 0, 1, 2, 3
+CRIT_SMH_A, CRIT_HLL_A, CRIT_HLL_AN, CRIT_HLL_A_SMH_A, CRIT_NONE = 0, 1, 2, 3, 4
 BANDING_CPU, BANDING_CUDA = 0, 1
 
 _vp, _i, _i64, _d, _sz, _cp = C.c_void_p, C.c_int, C.c_int64, C.c_double, C.c_size_t, C.c_char_p

@@ -198,6 +198,7 @@ int selhip_ctx_set_param(selhip_ctx* c, const char* name, int value) {
         c->hist_sparse = value;
         return SELHIP_OK;
     }
+    if (!std::strcmp(name, "dense_fused")) { c->dense_fused = value != 0; return SELHIP_OK; }
     if (!std::strcmp(name, "hist_dense_degree")) {
         if (value < -1 || value > (1 << 20)) { set_err(&c->err, "hist_dense_degree must be in [-1, 2^20] (-1 = never)"); return SELHIP_E_BADARG; }
         c->hist_dense_degree = value;
@@ -226,6 +227,7 @@ int selhip_ctx_get_param(const selhip_ctx* c, const char* name, int* value) {
     if (!std::strcmp(name, "join_tile_rows"))   { *value = join_tile_rows(c); return SELHIP_OK; }
     if (!std::strcmp(name, "join_form_used"))   { *value = c->join_form_used; return SELHIP_OK; }      // kernel FORM of the last LDS-tile join (3 = bit-sliced)
     if (!std::strcmp(name, "chunks"))           { *value = c->n_chunks_last; return SELHIP_OK; }
+    if (!std::strcmp(name, "dense_route_used")) { *value = c->dense_route_used; return SELHIP_OK; }         // SELHIP_CRIT_NONE: 1 fused kernel, 0 list route, -1 none yet
     if (!std::strcmp(name, "small_pass_used"))  { *value = c->small_used ? 1 : 0; return SELHIP_OK; }
     if (!std::strcmp(name, "query_db_sig_builds")) { *value = c->q.db_sig_builds; return SELHIP_OK; }   // database signature builds of the query passes
     if (!std::strcmp(name, "query_db_index_builds")) { *value = c->q.db_idx_builds; return SELHIP_OK; } // builds of ALGO_INDEX's sorted signature index
@@ -258,7 +260,7 @@ int selhip_ctx_set_pipeline(selhip_ctx* c, int chunks) {
 }
 
 int selhip_ctx_set_criterion(selhip_ctx* c, int criterion) {
-    if (!c || criterion < SELHIP_CRIT_SMH_A || criterion > SELHIP_CRIT_HLL_A_SMH_A) return SELHIP_E_BADARG;
+    if (!c || criterion < SELHIP_CRIT_SMH_A || criterion > SELHIP_CRIT_NONE) return SELHIP_E_BADARG;
     c->criterion = criterion;
     return SELHIP_OK;
 }
@@ -394,10 +396,11 @@ int selhip_ctx_run_async(selhip_ctx* c, int mode, int algo, float tau_f, int n_r
     if (!c->d_aux && c->n) { set_err(&c->err, "run before upload/attach"); return SELHIP_E_STATE; }
     if (mode != SELHIP_MODE_SMH && mode != SELHIP_MODE_CB_SMH) { set_err(&c->err, "bad mode %d", mode); return SELHIP_E_BADARG; }
     if (algo != SELHIP_ALGO_AUTO && algo != SELHIP_ALGO_STREAM && algo != SELHIP_ALGO_SIG && algo != SELHIP_ALGO_HASHJOIN) { set_err(&c->err, "bad algo %d", algo); return SELHIP_E_BADARG; }
-    if (c->criterion != SELHIP_CRIT_SMH_A && !c->d_aux_hll && c->n) {
+    if (aux_criterion(c->criterion) && !c->d_aux_hll && c->n) {
         set_err(&c->err, "criterion %d needs auxiliary HLL sketches (selhip_ctx_upload_aux_hll)", c->criterion);
         return SELHIP_E_STATE;
     }
+    if (c->criterion == SELHIP_CRIT_NONE) { const int rc = accept_dense(c); if (rc) return rc; }
     const PassPlan plan = pass_plan(c->criterion, algo, c->m, n_rows, n_bands);
     if (plan.smh && (n_rows <= 0 || n_bands <= 0 || (long long)n_rows * n_bands != c->m)) {
         // criteria_sketch.hpp:67-70: the reference prints an error and selects nothing; the ABI reports it
@@ -461,6 +464,7 @@ int selhip_ctx_finish(selhip_ctx* c) {
         }
         if (results_overflowed(pc.n_results, c->results.cap, &res_cap)) grow = true;
         if (!grow) {
+            if (c->criterion == SELHIP_CRIT_NONE) dense_stats(&pc);
             c->last = pc; c->pending = false; c->have_run = true; c->last_attempts = attempt + 1;
             // (event pairs are read lazily -- selhip_ctx_kernel_ms / _timing / destroy -- so that a timed run does not stall the
             // host between passes; a pass records at most ~20 of them)

@@ -98,7 +98,8 @@ int selhip_ctx_run_queries(selhip_ctx* c, int mode, int algo, float tau_f, int n
     if (q.n < 0) { set_err(&c->err, "run_queries before upload / attach of the queries"); return SELHIP_E_STATE; }
     if (c->pending) { set_err(&c->err, "a pass is still pending (selhip_ctx_finish)"); return SELHIP_E_STATE; }
     if (mode != SELHIP_MODE_SMH && mode != SELHIP_MODE_CB_SMH) { set_err(&c->err, "bad mode %d", mode); return SELHIP_E_BADARG; }
-    if (c->criterion != SELHIP_CRIT_SMH_A) {
+    if (c->criterion == SELHIP_CRIT_NONE) { const int rc = accept_dense(c); if (rc) return rc; }
+    if (aux_criterion(c->criterion)) {
         // the auxiliary HLL sketches of both sets, with one precision
         if ((c->n && !c->d_aux_hll) || (q.n && !q.d_aux_hll)) {
             set_err(&c->err, "criterion %d needs the auxiliary HLL sketches of the database (selhip_ctx_upload_aux_hll) and of the queries "
@@ -151,6 +152,7 @@ int selhip_ctx_run_queries(selhip_ctx* c, int mode, int algo, float tau_f, int n
         if (results_overflowed(pc.n_results, c->results.cap, &res_cap)) grow = true;
         if (!grow) {
             c->last = pc; c->have_run = true; c->last_attempts = attempt + 1; c->last_was_query = true;
+            if (c->criterion == SELHIP_CRIT_NONE) dense_stats(&c->last);
             return SELHIP_OK;
         }
         res_cap = std::max(res_cap, cap);               // an internal list was too small: counts are exact, grow once and repeat

@@ -8,7 +8,9 @@
 //   -a <bytes>  auxiliary memory per genome; m = bytes/8 SuperMinHash buckets (selection.cpp:231)
 //   -b <n>      accepted for CLI compatibility (CUDA block size in the reference); ignored
 //   -c <crit>   smh_a (default; the only criterion of the reference's GPU driver, selection_cuda.cpp:64), or hll_a /
-//               hll_an as in the CPU program (src/selection.cpp:122-227: auxiliary HLL p = ctz(aux_bytes), file .hll_<p>)
+//               hll_an as in the CPU program (src/selection.cpp:122-227: auxiliary HLL p = ctz(aux_bytes), file .hll_<p>), or
+//               none: no criterion in front of the Jaccard test -- every pair inside the CB bound (with -n: every pair); reads
+//               only the .hll files, -a is not needed (SELHIP_CRIT_NONE: the reference README's "CB criterion" / "no criterion" lines)
 //   -t <n>      host threads for loading sketches (selection.cpp:97)
 //   -g <n>      number of GPUs to shard the pair space over (default 1; any criterion); selected pairs gathered over RCCL/xGMI
 //   -n          no CB pruning ("smh_a" mode of experiments/src/time_smh.cpp:229-257)
@@ -22,7 +24,7 @@
 //   -r <file>   no selection: print the text form of a result file written with -o (needs no GPU)
 //   -q <file>   query-vs-database selection: -q lists the query genomes, -l the database; prints "query_path db_path J" per
 //               selected pair (one member in each list) in (query rank, database rank) order (selhip_ctx_run_queries; criterion
-//               smh_a, hll_a or hll_an -- for the last two the .hll_<p> files of both lists are read; one device -- not combinable
+//               smh_a, hll_a, hll_an or none -- for hll_a / hll_an the .hll_<p> files of both lists are read; one device -- not combinable
 //               with -g, -B, -o or -r)
 //   -x          usage
 #include <unistd.h>
@@ -39,13 +41,14 @@
 #include "../../../include/selection_host.h"
 
 // -q: the query list against the database list (-l), both loaded and sorted by cardinality; text on stdout.  criterion: "smh_a"
-// (m = aux_bytes / 8 buckets) or "hll_a" / "hll_an" (auxiliary HLL p = ctz(aux_bytes), as the all-pairs mode)
+// (m = aux_bytes / 8 buckets), "hll_a" / "hll_an" (auxiliary HLL p = ctz(aux_bytes), as the all-pairs mode) or "none" (.hll files only)
 static int run_queries(const std::string& query_file, const std::string& db_file, const std::string& criterion, float threshold,
                        int aux_bytes, int mode, int algo, int fp_mode, int threads) {
     const bool smh = criterion == "smh_a";
-    const int crit = smh ? SELHIP_CRIT_SMH_A : criterion == "hll_a" ? SELHIP_CRIT_HLL_A : SELHIP_CRIT_HLL_AN;
+    const bool none = criterion == "none";
+    const int crit = smh ? SELHIP_CRIT_SMH_A : none ? SELHIP_CRIT_NONE : criterion == "hll_a" ? SELHIP_CRIT_HLL_A : SELHIP_CRIT_HLL_AN;
     const unsigned m = smh ? (unsigned)aux_bytes / 8 : 0;
-    const unsigned p_aux = smh ? 0 : (unsigned)__builtin_ctz(aux_bytes ? aux_bytes : 1);
+    const unsigned p_aux = smh || none ? 0 : (unsigned)__builtin_ctz(aux_bytes ? aux_bytes : 1);
     // (smh_a keeps the messages it always had; an hll criterion names the mode and the criterion)
     const std::string what = smh ? "" : "selection: -q -c " + criterion + ": ";
     selhost_dataset* db = nullptr;
@@ -114,8 +117,8 @@ int main(int argc, char* argv[]) {
     int c;
     while ((c = getopt(argc, argv, "xl:b:a:h:c:t:g:nA:F:B:o:r:q:")) != -1) {
         switch (c) {
-            case 'x': std::cout << "Usage: -l -h -a -b [-c smh_a] [-t threads] [-g gpus] [-n] [-A auto|stream|sig] [-F 0|1] [-B block] [-o file] | -r file\n"
-                                   "       -l db_list -q query_list -h -a [-c smh_a|hll_a|hll_an] [-n] [-A auto|stream|sig|index] [-F 0|1]   (query-vs-database selection)\n"; return 0;
+            case 'x': std::cout << "Usage: -l -h -a -b [-c smh_a|hll_a|hll_an|none] [-t threads] [-g gpus] [-n] [-A auto|stream|sig] [-F 0|1] [-B block] [-o file] | -r file\n"
+                                   "       -l db_list -q query_list -h -a [-c smh_a|hll_a|hll_an|none] [-n] [-A auto|stream|sig|index] [-F 0|1]   (query-vs-database selection)\n"; return 0;
             case 'q': query_file = optarg; break;
             case 'B': ooc_block = std::stoll(optarg); break;
             case 'o': out_file = optarg; break;
@@ -141,7 +144,7 @@ int main(int argc, char* argv[]) {
                       << "; it runs on one device and prints text\n";
             return 2;
         }
-        if (criterion != "smh_a" && criterion != "hll_a" && criterion != "hll_an") {
+        if (criterion != "smh_a" && criterion != "hll_a" && criterion != "hll_an" && criterion != "none") {
             std::cerr << "selection: -q -c " << criterion << ": the accepted criteria are hll_a, hll_an and smh_a\n";
             return 2;
         }
@@ -168,13 +171,14 @@ int main(int argc, char* argv[]) {
     int crit = SELHIP_CRIT_SMH_A;
     if (criterion == "hll_a") crit = SELHIP_CRIT_HLL_A;
     else if (criterion == "hll_an") crit = SELHIP_CRIT_HLL_AN;
+    else if (criterion == "none") crit = SELHIP_CRIT_NONE;
     else if (criterion != "smh_a") {
         std::cout << "Option -c invalid. The accepted criteria are hll_a, hll_an and smh_a.\n";    // selection.cpp:293
         return 0;
     }
     if (list_file.empty()) { std::cerr << "No input file provided\n"; exit(-1); }   // selection.cpp:40-44
     const unsigned m = crit == SELHIP_CRIT_SMH_A ? (unsigned)aux_bytes / 8 : 0;                      // selection.cpp:231
-    const unsigned p_aux = crit == SELHIP_CRIT_SMH_A ? 0 : (unsigned)__builtin_ctz(aux_bytes ? aux_bytes : 1);   // :125
+    const unsigned p_aux = crit == SELHIP_CRIT_SMH_A || crit == SELHIP_CRIT_NONE ? 0 : (unsigned)__builtin_ctz(aux_bytes ? aux_bytes : 1);   // :125
 
     selhost_dataset* ds = nullptr;
     int rc = selhost_dataset_load(&ds, list_file.c_str(), m, p_aux, fp_mode, threads);

@@ -133,8 +133,8 @@ static_assert(kCounterBlocks == kMaxChunks + 1, "common.cuh: counter blocks per 
 constexpr int kMaxAuxP = SELHIP_MAX_AUX_P;   // auxiliary HLL precision accepted by every entry point: aux_fused_kernel counts in 16-bit bins (a bin holds up to 2^p_aux)
 constexpr long long kEnumPairs = 1ll << 26;    // hll_a / hll_an as first criterion: pairs listed per sub-pass (512 MiB of int2)
 
-enum { T_PREP = 0, T_STAGE1, T_HIST, T_SELECT, T_TOTAL, T_SIGBUILD, T_JOIN, T_VERIFY, T_AUX, T_GROUP, T_COUNT };
-const char* kTimerNames[T_COUNT] = {"prep", "stage1", "hist", "select", "total", "sigbuild", "join", "verify", "aux", "group"};
+enum { T_PREP = 0, T_STAGE1, T_HIST, T_SELECT, T_TOTAL, T_SIGBUILD, T_JOIN, T_VERIFY, T_AUX, T_GROUP, T_DENSE, T_COUNT };
+const char* kTimerNames[T_COUNT] = {"prep", "stage1", "hist", "select", "total", "sigbuild", "join", "verify", "aux", "group", "dense"};
 
 }  // namespace
 
@@ -233,6 +233,10 @@ struct selhip_ctx {
     int small_pass = -1;                // sets of <= 2 048 genomes: the whole pass in one cooperative launch (kernel_small.cuh); -1 automatic, 0 off
     bool small_used = false, small_pass_failed = false;   // the last enqueue took it / a block's survivor list overflowed once: regular passes from then on
     int group_min_n = 2048;             // ... for sets of more than this many genomes ("group_min_n"; see grouping_on)
+    // SELHIP_CRIT_NONE ("dense_fused"): 1 = dense_select_kernel (kernel_dense.cuh), 0 = the list route (enumeration, then the union-histogram
+    // and estimator kernels of the other criteria); dense_route_used = which the last such pass took (-1 = none yet)
+    int dense_fused = 1;
+    int dense_route_used = -1;
 
     // last run parameters (for overflow re-runs)
     bool have_run = false, pending = false;

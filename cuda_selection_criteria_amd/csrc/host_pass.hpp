@@ -498,6 +498,40 @@ bool label_order(const selhip_ctx* c) {
     return (size_t)c->n * 16384 > kLabelOrderBytes && (double)pair_bound(c->n, c->row_begin, c->row_end) / std::max(1, c->il_parts) >= kLabelOrderPairs;
 }
 
+// stage 2 of one chain over a pair list: union histograms, `window` pairs at a time, and the estimator / J test behind each window.
+// grouped: the list is bucketed by query row (runs of a row's pairs; a dense list is walked by candidate slice per XCD)
+int enqueue_hist_select(selhip_ctx* c, const Chain& ch, const selhip_int2_t* final_list, const u64* final_count, u64 final_cap,
+                        bool grouped, double tau, PassCounters* pc0) {
+    hipStream_t st = ch.io.st;
+    for (u64 off = 0; off < final_cap; off += ch.window) {
+        {
+            TimerScope t(c, T_HIST, st);
+            if (use_bitslices(c))
+                HIPCHK(&c->err, launch_hist_bs(c->planes.khi, (unsigned)c->hist_bs_blocks, st, c->planes.bs.p, c->planes.gmax.p, final_list, final_count, final_cap, ch.counts, off, ch.window,
+                                               c->hist_run > 0 ? c->hist_run : (grouped ? 4 : 1),
+                                               // a dense survivor graph is walked by candidate-row slice per XCD (query-major list only)
+                                               // ("dense" = survivors per QUERY ROW of this chain: a rank's or a lane's share of the rows sees
+                                               //  its share of the pairs and all of the candidate rows)
+                                               grouped && c->hist_dense_degree >= 0
+                                                   ? (u64)c->hist_dense_degree * (u64)std::max<long long>(1, ((long long)ch.re - ch.rb) / std::max(1, c->il_parts)) : ~0ull,
+                                               sparse_t_used(c), c->hll_sparse.p));
+            else if (c->p == 14)
+                hipLaunchKernelGGL(hll_union_hist_runs_kernel, dim3(c->hist_blocks), dim3(kWave), (size_t)c->hist_pad, st,
+                                   c->d_hll, final_list, final_count, final_cap, ch.counts, off, ch.window,
+                                   c->hist_run > 0 ? c->hist_run : (grouped && label_order(c) ? 4 : 1));
+            else
+                hipLaunchKernelGGL(hll_union_hist_kernel, dim3(2048), dim3(kBlock), 0, st,
+                                   c->d_hll, c->p, final_list, final_count, (u64)0, final_cap, ch.counts, off, ch.window);
+            HIPCHK(&c->err, hipGetLastError());
+        }
+        TimerScope t(c, T_SELECT, st);
+        HIPCHK(&c->err, launch_select<1>(c->fp_mode == SELHIP_FP_FMA, st, 4096, ch.counts, final_count, 0,
+                                         final_cap, c->p, nullptr, final_list, c->ecard.p, tau,
+                                         c->results.p, (u64)c->results.cap, pc0, nullptr, nullptr, off, ch.window));
+    }
+    return SELHIP_OK;
+}
+
 int enqueue_tail(selhip_ctx* c, const Chain& ch, const selhip_int2_t* final_list, const u64* final_count, u64 final_cap,
                  bool counted, double tau, PassCounters* pc0) {
     const int n = (int)c->n;
@@ -547,33 +581,7 @@ int enqueue_tail(selhip_ctx* c, const Chain& ch, const selhip_int2_t* final_list
         }
         final_list = ch.grouped;
     }
-    for (u64 off = 0; off < final_cap; off += ch.window) {
-        {
-            TimerScope t(c, T_HIST, st);
-            if (use_bitslices(c))
-                HIPCHK(&c->err, launch_hist_bs(c->planes.khi, (unsigned)c->hist_bs_blocks, st, c->planes.bs.p, c->planes.gmax.p, final_list, final_count, final_cap, ch.counts, off, ch.window,
-                                               c->hist_run > 0 ? c->hist_run : (grouped ? 4 : 1),
-                                               // a dense survivor graph is walked by candidate-row slice per XCD (query-major list only)
-                                               // ("dense" = survivors per QUERY ROW of this chain: a rank's or a lane's share of the rows sees
-                                               //  its share of the pairs and all of the candidate rows)
-                                               grouped && c->hist_dense_degree >= 0
-                                                   ? (u64)c->hist_dense_degree * (u64)std::max<long long>(1, ((long long)ch.re - ch.rb) / std::max(1, c->il_parts)) : ~0ull,
-                                               sparse_t_used(c), c->hll_sparse.p));
-            else if (c->p == 14)
-                hipLaunchKernelGGL(hll_union_hist_runs_kernel, dim3(c->hist_blocks), dim3(kWave), (size_t)c->hist_pad, st,
-                                   c->d_hll, final_list, final_count, final_cap, ch.counts, off, ch.window,
-                                   c->hist_run > 0 ? c->hist_run : (grouped && label_order(c) ? 4 : 1));
-            else
-                hipLaunchKernelGGL(hll_union_hist_kernel, dim3(2048), dim3(kBlock), 0, st,
-                                   c->d_hll, c->p, final_list, final_count, (u64)0, final_cap, ch.counts, off, ch.window);
-            HIPCHK(&c->err, hipGetLastError());
-        }
-        TimerScope t(c, T_SELECT, st);
-        HIPCHK(&c->err, launch_select<1>(c->fp_mode == SELHIP_FP_FMA, st, 4096, ch.counts, final_count, 0,
-                                         final_cap, c->p, nullptr, final_list, c->ecard.p, tau,
-                                         c->results.p, (u64)c->results.cap, pc0, nullptr, nullptr, off, ch.window));
-    }
-    return SELHIP_OK;
+    return enqueue_hist_select(c, ch, final_list, final_count, final_cap, grouped, tau, pc0);
 }
 
 // smh_a (alone or before the auxiliary criterion) over the query rows of one chain, then the final criterion.  [rb, re) is the
@@ -656,13 +664,63 @@ int enqueue_small_pass(selhip_ctx* c, PassCounters* pc_next, double tau) {
     return SELHIP_OK;
 }
 
+// ---- criterion "none" (kernel_dense.cuh) ---------------------------------------------------------------------------------------
+// what SELHIP_CRIT_NONE asks of the context: p = 14 sketches with their bit planes resident (there is no byte-row form of the pass).
+// An accepted pass has its route from here on ("dense_route_used"), also one that turns out empty and launches nothing
+int accept_dense(selhip_ctx* c) {
+    if (c->p != 14 || (c->n > 0 && !use_bitslices(c))) {
+        set_err(&c->err, "criterion none (SELHIP_CRIT_NONE) needs p_hll = 14 sketches and their bit planes (p_hll = %d, hist_algo = %d)", c->p, c->hist_algo);
+        return SELHIP_E_BADARG;
+    }
+    c->dense_route_used = c->dense_fused ? 1 : 0;
+    return SELHIP_OK;
+}
+
+// the empty criterion passes every evaluated pair on: survivors = candidates = evaluated
+void dense_stats(PassCounters* pc) { pc->n_survivors = pc->n_final = pc->n_candidates = pc->n_evaluated; }
+
+// dense_select_kernel over the rows of rm against the candidates from first_cand on.  lo == nullptr: an all-pairs pass (X = Y, ranges
+// from hi and pc_in's z0), else a query pass (windows lo / hi).  khi = largest register value + 1 of the two sets
+hipError_t launch_dense(bool fma, hipStream_t st, int khi, const DenseSet& X, const DenseSet& Y, int n_y, const int* lo, const int* hi,
+                        const PassCounters* pc_in, const RowMap& rm, int first_cand, double tau, selhip_pair_t* results, u64 results_cap,
+                        PassCounters* pc) {
+    const long long n_tiles = rm.n_tiles(kWavesPerBlock);
+    const int span_base = first_cand / kDenseSpan;
+    const long long n_spans = ((long long)n_y + kDenseSpan - 1) / kDenseSpan - span_base;
+    if (n_tiles <= 0 || n_spans <= 0) return hipSuccess;
+    if (n_tiles > 0x7FFFFFFFll) return hipErrorInvalidValue;
+    const long long n_units = 8 * n_tiles * ((n_spans + 7) / 8);
+    const unsigned grid = (unsigned)std::min<long long>(n_units, 0x7FFFFFF8ll);              // (a multiple of 8; beyond it blocks take several units)
+    const double rs = relerr_scaled_for(14);
+    with_flag(fma, [&](auto F) {
+#define SELHIP_DENSE_LAUNCH(NB) hipLaunchKernelGGL((dense_select_kernel<NB, decltype(F)::value>), dim3(grid), dim3(kBlock), 0, st, X, Y, n_y, lo, hi, pc_in, rm, \
+                                                   (int)n_tiles, span_base, n_units, tau, rs, results, results_cap, pc)
+        switch (bs_planes(khi)) {
+            case 4:  SELHIP_DENSE_LAUNCH(4); break;
+            case 5:  SELHIP_DENSE_LAUNCH(5); break;
+            default: SELHIP_DENSE_LAUNCH(6);
+        }
+#undef SELHIP_DENSE_LAUNCH
+    });
+    return hipGetLastError();
+}
+
+// the all-pairs pass of SELHIP_CRIT_NONE in one launch behind cb_bounds_kernel
+int enqueue_dense(selhip_ctx* c, int rb, int re, double tau, PassCounters* pc0) {
+    TimerScope t(c, T_DENSE);
+    const DenseSet set{c->planes.bs.p, c->planes.gmax.p, c->ecard.p};
+    HIPCHK(&c->err, launch_dense(c->fp_mode == SELHIP_FP_FMA, c->stream, c->planes.khi, set, set, (int)c->n, nullptr, c->hi.p, pc0, row_map(c, rb, re),
+                                 std::max(rb + 1, (int)c->cand_begin), tau, c->results.p, (u64)c->results.cap, pc0));
+    return SELHIP_OK;
+}
+
 int enqueue_pass(selhip_ctx* c) {
     const int n = (int)c->n;
     const int rb = (int)c->row_begin, re = (int)c->row_end;
     const double tau = (double)c->tau_f;            // float threshold widened, selection.cpp:81,164
     const int crit = c->criterion;
     const PassPlan& plan = c->plan;
-    c->dominant_timer = c->timed_kernel == 1 ? T_HIST : (plan.use_sig ? T_JOIN : T_STAGE1);
+    c->dominant_timer = c->timed_kernel == 1 ? T_HIST : crit == SELHIP_CRIT_NONE ? T_DENSE : (plan.use_sig ? T_JOIN : T_STAGE1);
     if (c->timing) c->timed_passes += 1;
     TimerScope total(c, T_TOTAL);
     const bool smh_crit = plan.smh, use_hash = plan.use_hash, use_sig = plan.use_sig;
@@ -759,6 +817,9 @@ int enqueue_pass(selhip_ctx* c) {
     if (smh_crit) {
         const int rc = enqueue_chain(c, ch, rb, re, tau, use_hash, use_sig, count_in_verify, pc0);
         if (rc) return rc;
+    } else if (crit == SELHIP_CRIT_NONE && c->dense_fused) {
+        const int rc = enqueue_dense(c, rb, re, tau, pc0);
+        if (rc) return rc;
     } else {
         // hll_a / hll_an as FIRST criterion (selection.cpp:152-173, 206-227): the (CB-pruned) pair space of the rows is listed
         // explicitly, kEnumPairs pairs at a time -- row sub-ranges in turn on the stream, each listed into the same buffer and
@@ -793,14 +854,24 @@ int enqueue_pass(selhip_ctx* c) {
                     HIPCHK(&c->err, hipGetLastError());
                 }
             }
-            TimerScope t(c, T_AUX);
             const u64 bound = std::min<u64>((u64)c->cand.cap, (u64)acc);
+            if (crit == SELHIP_CRIT_NONE) {
+                // the list route of criterion none: nothing filters the sub-pass's list, stage 2 takes all of it (a row's pairs are
+                // neighbours in it, like in a grouped list) before the next sub-pass overwrites it
+                const int rc = enqueue_hist_select(c, ch, c->cand.p, &io.pc->n_aux_in, bound, true, tau, pc0);
+                if (rc) return rc;
+                sb = se;
+                continue;
+            }
+            TimerScope t(c, T_AUX);
             if (crit == SELHIP_CRIT_HLL_AN) HIPCHK(&c->err, launch_aux_fused<2>(c, c->stream, c->cand.p, &io.pc->n_aux_in, (u64)c->cand.cap, bound, tau, ch.fin, ch.fin_cap, &io.pc->n_final));
             else                            HIPCHK(&c->err, launch_aux_fused<1>(c, c->stream, c->cand.p, &io.pc->n_aux_in, (u64)c->cand.cap, bound, tau, ch.fin, ch.fin_cap, &io.pc->n_final));
             sb = se;
         }
-        const int rc = enqueue_tail(c, ch, ch.fin, &io.pc->n_final, ch.fin_cap, false, tau, pc0);
-        if (rc) return rc;
+        if (crit != SELHIP_CRIT_NONE) {
+            const int rc = enqueue_tail(c, ch, ch.fin, &io.pc->n_final, ch.fin_cap, false, tau, pc0);
+            if (rc) return rc;
+        }
     }
     // (handing the counters to the host from the last block of the final kernel instead of this copy was tried: the 1 024
     // "block done" atomics on one address cost 16 us, the copy dispatch 4)
@@ -825,8 +896,9 @@ int ensure_scratch(selhip_ctx* c, size_t surv_cap, size_t res_cap) {
     }
     HIPCHK(&c->err, c->surv.ensure(surv_cap));
     HIPCHK(&c->err, c->cand.ensure(surv_cap));
-    if (c->criterion != SELHIP_CRIT_SMH_A) HIPCHK(&c->err, c->fin.ensure(surv_cap));
-    if (c->criterion == SELHIP_CRIT_HLL_A || c->criterion == SELHIP_CRIT_HLL_AN) {
+    if (aux_criterion(c->criterion)) HIPCHK(&c->err, c->fin.ensure(surv_cap));
+    const bool dense_list = c->criterion == SELHIP_CRIT_NONE && !c->dense_fused;       // the list route: the pair space is listed like hll_a's
+    if (c->criterion == SELHIP_CRIT_HLL_A || c->criterion == SELHIP_CRIT_HLL_AN || dense_list) {
         // the explicit pair space is materialised kEnumPairs pairs at a time (8 B per pair); one interleave period of rows is the
         // smallest unit, so the buffer holds at least that
         const long long period = interleave_period(c);
@@ -857,7 +929,8 @@ int ensure_scratch(selhip_ctx* c, size_t surv_cap, size_t res_cap) {
     }
     // histogram scratch: 256 B per pair, at most 4 Mi pairs per window (1 GiB of 288; the lists are sized for the join's 16-bit
     // matches, several times the final list, so a smaller window only adds empty histogram + estimate launches: 6 -> 2 per chain at cfg5)
-    HIPCHK(&c->err, c->counts.ensure(std::min<size_t>(std::max(c->surv.cap, (size_t)c->n), (size_t)1 << 22) * 64));
+    // (the list route of criterion none puts whole sub-passes through it: the full window)
+    HIPCHK(&c->err, c->counts.ensure(std::min<size_t>(std::max(dense_list ? c->cand.cap : c->surv.cap, (size_t)c->n), (size_t)1 << 22) * 64));
     HIPCHK(&c->err, c->results.ensure(res_cap));
     if (grouping_on(c)) {
         const size_t chunks = (size_t)pipeline_chunks(c);               // every chunk lane has its own row counters and scan scratch

@@ -72,6 +72,9 @@ SigBuildShape sig_build_shape(int m, int n, int n_rows, int n_bands, int sig_til
 // bit planes that can be non-zero in a set whose largest register value is khi - 1: the NB of the stage-2a kernels
 int bs_planes(int khi) { return khi <= 16 ? 4 : khi <= 32 ? 5 : 6; }
 
+// the criterion has an auxiliary-HLL stage (hll_a, hll_an, hll_a + smh_a): it needs the auxiliary sketches
+bool aux_criterion(int criterion) { return criterion == SELHIP_CRIT_HLL_A || criterion == SELHIP_CRIT_HLL_AN || criterion == SELHIP_CRIT_HLL_A_SMH_A; }
+
 // ---- which stage 1 a pass runs ------------------------------------------------------------------
 // smh: the criterion has an smh_a stage at all (hll_a / hll_an alone read neither the band shape nor the algorithm).  use_sig: band
 // signatures are built and joined (use_hash: by the sort join; use_index: a query pass probes the sorted index instead of joining);

@@ -121,7 +121,8 @@ int enqueue_query_pass(selhip_ctx* c, double tau) {
     auto& q = c->q;
     const int n_q = (int)q.n, n_d = (int)c->n;
     const bool smh = c->plan.smh, use_sig = c->plan.use_sig, use_index = c->plan.use_index;
-    c->dominant_timer = c->timed_kernel == 1 ? T_HIST : !smh ? T_AUX : (use_sig ? T_JOIN : T_STAGE1);
+    const bool none = c->criterion == SELHIP_CRIT_NONE;
+    c->dominant_timer = c->timed_kernel == 1 ? T_HIST : none ? T_DENSE : !smh ? T_AUX : (use_sig ? T_JOIN : T_STAGE1);
     if (c->timing) c->timed_passes += 1;
     TimerScope total(c, T_TOTAL);
     // counter set of this pass (the other one is cleared by this pass's first kernel for the next pass)
@@ -157,7 +158,27 @@ int enqueue_query_pass(selhip_ctx* c, double tau) {
         }
     }
     const BitPlanes& planes_d = use_bitslices(c) ? c->planes : q.db_planes;
-    if (!smh) {
+    if (none) {
+        if (c->dense_fused) {
+            // criterion none, one launch behind the windows: records carry database ranks, nothing is left for stage 2
+            {
+                TimerScope t(c, T_DENSE);
+                HIPCHK(&c->err, launch_dense(c->fp_mode == SELHIP_FP_FMA, c->stream, std::max(q.planes.khi, planes_d.khi),
+                                             DenseSet{q.planes.bs.p, q.planes.gmax.p, q.ecard.p}, DenseSet{planes_d.bs.p, planes_d.gmax.p, q.ecard.p + n_q},
+                                             n_d, q.lo.p, q.hi.p, pc, RowMap{0, n_q, n_q, 1, 0}, 0, tau, c->results.p, (u64)c->results.cap, pc));
+            }
+            HIPCHK(&c->err, hipMemcpyAsync(q.h_pc, pc, sizeof(PassCounters), hipMemcpyDeviceToHost, c->stream));
+            q.pc.dirty = false;
+            return SELHIP_OK;
+        }
+        // its list route: every pair of the windows listed, then stage 2 as for every criterion
+        const long long blocks = (long long)n_q * ((n_d + kEnumSpan - 1) / kEnumSpan);
+        if (blocks > 0x7FFFFFFFll) { set_err(&c->err, "query pass too large for one launch"); return SELHIP_E_BADARG; }
+        TimerScope t(c, T_STAGE1);
+        hipLaunchKernelGGL(query_enum_windows_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, c->stream, n_q, q.lo.p, q.hi.p,
+                           q.fin.p, (u64)q.fin.cap, &pc->n_final);
+        HIPCHK(&c->err, hipGetLastError());
+    } else if (!smh) {
         // hll_a / hll_an as the first criterion: straight over the windows, no signatures, no join
         if ((long long)n_q * ((n_d + kBlock - 1) / kBlock) > 0x7FFFFFFFll) { set_err(&c->err, "query pass too large for one launch"); return SELHIP_E_BADARG; }
         TimerScope t(c, T_AUX);

@@ -22,6 +22,8 @@
 //                       literal stream kernel for any band shape, stage 2a on two sets' bit planes
 //   kernel_query_index.cuh ALGO_INDEX of the query passes: the database's band signatures sorted per band (built once, kept), one
 //                       binary search per (query, band) in place of the rectangular join
+//   kernel_dense.cuh    dense_select_kernel: criterion "none" -- every pair of the (CB-pruned) pair space to the Jaccard test, union
+//                       histograms into an LDS tile and the estimator in one launch
 //   kernel_query_aux.cuh the auxiliary-HLL criteria of query passes: hll_a / hll_an over each query's CB window, the hll_a stage
 //                       of hll_a + smh_a over the smh_a survivors
 //
@@ -60,6 +62,7 @@
 #include "kernel_query.cuh"
 #include "kernel_query_aux.cuh"
 #include "kernel_query_index.cuh"
+#include "kernel_dense.cuh"
 
 #include "host_plan.hpp"         // host decisions that are plain arithmetic: build shape, pass plan, criterion constants, overflow rule
 #include "host_context.hpp"      // struct selhip_ctx, device buffers (signature sets, bit planes, counter sets), timers, helpers

@@ -11,7 +11,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import (ALGO_AUTO, BANDING_CPU, CRIT_HLL_A, CRIT_HLL_AN, CRIT_HLL_A_SMH_A, CRIT_SMH_A, FP_FMA, MODE_CB_SMH, Pair,
+from ._lib import (ALGO_AUTO, BANDING_CPU, CRIT_HLL_A, CRIT_HLL_AN, CRIT_HLL_A_SMH_A, CRIT_NONE, CRIT_SMH_A, FP_FMA, MODE_CB_SMH, Pair,
                    check, hip_lib, host_lib)
 
 # layout of selhip_pair_t {int32 i, k; double jaccard}
@@ -361,12 +361,15 @@ class Selector:
 def select_from_filelist(list_file: str, tau: float, aux_bytes: int, mode: int = MODE_CB_SMH, device: int = 0,
                          fp_mode: int = FP_FMA, algo: int = ALGO_AUTO, criterion: str = "smh_a") -> str:
     """The whole of selection_cuda.cpp main() (criterion smh_a) -- and of selection.cpp's hll_a / hll_an
-    branches (:122-227): returns the text the CPU reference prints for `-c criterion -a aux_bytes -h tau`."""
+    branches (:122-227): returns the text the CPU reference prints for `-c criterion -a aux_bytes -h tau`.
+    criterion "none": no criterion in front of the Jaccard test (CRIT_NONE; mode MODE_CB_SMH = the CB bound alone, MODE_SMH = every pair)."""
     if criterion == "smh_a":
         m, p_aux, crit = aux_bytes // 8, 0, CRIT_SMH_A                       # selection.cpp:231
     elif criterion in ("hll_a", "hll_an"):
         m, p_aux = 0, (aux_bytes & -aux_bytes).bit_length() - 1               # __builtin_ctz(aux_bytes), selection.cpp:125
         crit = CRIT_HLL_A if criterion == "hll_a" else CRIT_HLL_AN
+    elif criterion == "none":
+        m, p_aux, crit = 0, 0, CRIT_NONE                                      # only the .hll files are read; aux_bytes is ignored
     else:
         raise ValueError("Option -c invalid. The accepted criteria are hll_a, hll_an and smh_a.")
     ds = load_dataset(list_file, m, p_aux, fp_mode)
@@ -386,7 +389,7 @@ def multi_select(devices: Sequence[int], hll: np.ndarray, aux: np.ndarray, cards
                  fp_mode: int = FP_FMA, gather: int = 2, criterion: int = 0, aux_hll: Optional[np.ndarray] = None, p_aux: int = 0):
     """selhip_multi_select: one process, one context per listed device, interleaved row blocks, RCCL (or host) gather.
     gather: 0 host merge, 1 RCCL required, 2 RCCL if available; criterion / aux_hll / p_aux as for Selector (hll_a, hll_an,
-    the two-stage criterion of BASELINE configs[4]).  Returns (pairs sorted by (i,k), stats dict)."""
+    the two-stage criterion of BASELINE configs[4]; CRIT_NONE takes no auxiliary sketches).  Returns (pairs sorted by (i,k), stats dict)."""
     lib = hip_lib()
     hll = np.ascontiguousarray(hll, dtype=np.uint8)
     aux = np.ascontiguousarray(aux, dtype=np.uint64)
@@ -395,7 +398,7 @@ def multi_select(devices: Sequence[int], hll: np.ndarray, aux: np.ndarray, cards
     if n_rows is None or n_bands is None:
         n_rows, n_bands = banding(m, tau)
     devs = (C.c_int * len(devices))(*devices)
-    ah = np.ascontiguousarray(aux_hll, dtype=np.uint8) if aux_hll is not None and criterion != 0 else None
+    ah = np.ascontiguousarray(aux_hll, dtype=np.uint8) if aux_hll is not None and criterion not in (CRIT_SMH_A, CRIT_NONE) else None
     cap = 1 << 16
     while True:
         out = np.zeros(cap, dtype=PAIR_DTYPE)
@@ -424,7 +427,7 @@ def ooc_select(hll: np.ndarray, aux: np.ndarray, cards: np.ndarray, tau: float, 
     n, m = aux.shape
     if n_rows is None or n_bands is None:
         n_rows, n_bands = banding(m, tau)
-    ah = np.ascontiguousarray(aux_hll, dtype=np.uint8) if aux_hll is not None and criterion != 0 else None
+    ah = np.ascontiguousarray(aux_hll, dtype=np.uint8) if aux_hll is not None and criterion not in (CRIT_SMH_A, CRIT_NONE) else None
     cap = 1 << 16
     while True:
         out = np.zeros(cap, dtype=PAIR_DTYPE)
@@ -444,12 +447,15 @@ def query_from_filelists(query_list: str, db_list: str, tau: float, aux_bytes: i
                          device: int = 0, algo: int = ALGO_AUTO, criterion: str = "smh_a") -> str:
     """Query-vs-database selection: both lists are loaded and sorted by cardinality (load_dataset); returns one line
     'query_path db_path J' per selected pair, in (query rank, database rank) order, J formatted as selection.cpp prints it.
-    criterion "smh_a" (m = aux_bytes / 8 buckets) or "hll_a" / "hll_an" (auxiliary HLL p = ctz(aux_bytes), as select_from_filelist)."""
+    criterion "smh_a" (m = aux_bytes / 8 buckets), "hll_a" / "hll_an" (auxiliary HLL p = ctz(aux_bytes), as select_from_filelist) or
+    "none" (every pair of the CB windows -- MODE_SMH: every cross pair -- to the Jaccard test)."""
     if criterion == "smh_a":
         m, p_aux, crit = aux_bytes // 8, 0, CRIT_SMH_A
     elif criterion in ("hll_a", "hll_an"):
         m, p_aux = 0, (aux_bytes & -aux_bytes).bit_length() - 1               # __builtin_ctz(aux_bytes), selection.cpp:125
         crit = CRIT_HLL_A if criterion == "hll_a" else CRIT_HLL_AN
+    elif criterion == "none":
+        m, p_aux, crit = 0, 0, CRIT_NONE                                      # only the .hll files are read; aux_bytes is ignored
     else:
         raise ValueError("Option -c invalid. The accepted criteria are hll_a, hll_an and smh_a.")
     qs = load_dataset(query_list, m, p_aux, fp_mode)

@@ -68,11 +68,18 @@ typedef struct { int32_t i, k; double jaccard; } selhip_pair_t;
  *   HLL_AN       src/selection.cpp:175-227   criteria_sketch.hpp:22-34,52-58 (order_n = 1, Z = 1.96)
  *   HLL_A_SMH_A  both hll_a and smh_a must select the pair (BASELINE.json config 5: "hll_a prefilter +
  *                smh_a two-stage criterion"); evaluated smh_a first, hll_a on its survivors -- the selected
- *                set is the intersection either way */
+ *                set is the intersection either way
+ *   NONE         no criterion at all: every pair that e_k != 0 and (in SELHIP_MODE_CB_SMH) the CB bound leave goes to the
+ *                Jaccard test -- src/selection.cpp:270-291 with the smh_a test removed.  SELHIP_MODE_CB_SMH gives the reference
+ *                README's "CB criterion" line, SELHIP_MODE_SMH its "no criterion (baseline case)": the ground truth the other
+ *                criteria are lossy filters of.  A pair that another criterion selects is selected here with the same record
+ *                (same i, k, J bits): result(c) is a subset of result(NONE) for every c, same mode, tau_f and FP flavour.
+ *                Needs p_hll = 14 (SELHIP_E_BADARG otherwise); reads neither the SuperMinHash nor the auxiliary HLL sketches */
 #define SELHIP_CRIT_SMH_A        0
 #define SELHIP_CRIT_HLL_A        1
 #define SELHIP_CRIT_HLL_AN       2
 #define SELHIP_CRIT_HLL_A_SMH_A  3
+#define SELHIP_CRIT_NONE         4
 
 /* estimator arithmetic flavour (see csrc/ertl_mle.hpp) */
 #define SELHIP_FP_FMA        1     /* = reference built by its Makefile on an FMA-capable x86 host (default) */
@@ -189,6 +196,9 @@ int selhip_ctx_set_candidate_begin(selhip_ctx* ctx, int64_t k_min);
  *   "group_label" stage-2 grouping lays the query-row buckets out by label = a row's smallest partner, so that the pairs of a
  *                 cluster of similar genomes are neighbours in the list and their HLL rows stay in L2 (-1 = automatic: sets
  *                 whose HLL rows exceed 192 MiB and passes of >= 4e8 pairs; 0 off; 1 on);
+ *   "dense_fused" SELHIP_CRIT_NONE: 1 (default) the pass is ONE kernel behind the bounds (dense_select_kernel: union histograms into an
+ *                 LDS tile, estimator and J test in the same wave); 0 the list route -- the pair space listed explicitly in row
+ *                 sub-passes, then the union-histogram and estimator kernels of the other criteria.  Same records and statistics;
  *   "timed_kernel" see selhip_ctx_timing.
  * (The library also answers to a few names that are NOT part of this interface -- hooks of its own test-suite and measurement
  * knobs, listed at selhip_ctx_set_param in csrc/selection_kernels.hip.) */
@@ -199,7 +209,8 @@ int selhip_ctx_set_param(selhip_ctx* ctx, const char* name, int value);
  * "query_db_sig_builds" (builds of the database's band signatures by query passes since the database was loaded, section 2b),
  * "query_db_index_builds" (builds of SELHIP_ALGO_INDEX's sorted signature index since the database was loaded, section 2b),
  * "query_db_index_kib" (resident size of that index in KiB, 0 = none held),
- * "hist_sparse_t" (the sparse threshold the all-pairs stage 2a uses, 0 = every value from the bit planes) */
+ * "hist_sparse_t" (the sparse threshold the all-pairs stage 2a uses, 0 = every value from the bit planes),
+ * "dense_route_used" (SELHIP_CRIT_NONE: the route of the last such pass, 1 = the fused kernel, 0 = the list route; -1 = none yet) */
 int selhip_ctx_get_param(const selhip_ctx* ctx, const char* name, int* value);
 /* Stage 2 grouping (default on): the pairs that reach the HLL-14 stage are bucketed by query row (counting sort) so
  * that waves running side by side on one XCD share their query row in L2.  0 = off (same kernel, list as produced). */
@@ -223,7 +234,7 @@ int selhip_ctx_attach(selhip_ctx* ctx, const uint8_t* d_hll, const uint64_t* d_a
 int selhip_ctx_upload_aux_hll(selhip_ctx* ctx, const uint8_t* h_aux_hll, int p_aux);
 int selhip_ctx_attach_aux_hll(selhip_ctx* ctx, const uint8_t* d_aux_hll, int p_aux);
 /* criterion used by the following selhip_ctx_run* calls (default SELHIP_CRIT_SMH_A); n_rows/n_bands are
- * ignored by HLL_A / HLL_AN */
+ * ignored by HLL_A / HLL_AN / NONE (NONE ignores algo too and needs no auxiliary HLL sketches) */
 int selhip_ctx_set_criterion(selhip_ctx* ctx, int criterion);
 
 /* report() of every genome (Ertl-MLE, hll.h:834-837,862) computed on the device: d_cards_out[n]. */
@@ -246,7 +257,8 @@ int selhip_ctx_finish(selhip_ctx* ctx);
  *   stats[0] pairs evaluated by the smh_a predicate (after e_k==0 / CB pruning)
  *   stats[1] pairs that passed the auxiliary criterion/criteria (smh_a: pairs with a fully equal band)
  *   stats[2] selected pairs (J >= tau)
- *   stats[3] candidates produced by the signature join (ALGO_SIG; = stats[1] for ALGO_STREAM) */
+ *   stats[3] candidates produced by the signature join (ALGO_SIG; = stats[1] for ALGO_STREAM)
+ * SELHIP_CRIT_NONE: the empty criterion passes everything, stats[1] = stats[3] = stats[0]. */
 int selhip_ctx_stats(const selhip_ctx* ctx, int64_t stats[4]);
 int64_t selhip_ctx_result_count(const selhip_ctx* ctx);
 /* copies min(count, cap) records to the host, sorted by (i,k) = the reference's print order */
@@ -271,13 +283,14 @@ int selhip_ctx_last_attempts(const selhip_ctx* ctx);
 
 /* device time (ms, HIP events on the stream each kernel is launched on) of the named kernel PER PASS, averaged over
  * the passes since the last reset (a pipelined pass launches a kernel once per row chunk: the figure is their sum);
- * names: "prep", "sigbuild", "join", "verify", "stage1", "aux", "group", "hist", "select", "total"; "join_span" = first start to
+ * names: "prep", "sigbuild", "join", "verify", "stage1", "aux", "group", "hist", "select", "dense" (the fused kernel of
+ * SELHIP_CRIT_NONE), "total"; "join_span" = first start to
  * last end of the pass's join launches (chunk lanes run them side by side).  <0 if never launched.
  * selhip_ctx_kernel_launches: launches of that kernel per pass. */
 double selhip_ctx_kernel_ms(const selhip_ctx* ctx, const char* name);
 double selhip_ctx_kernel_launches(const selhip_ctx* ctx, const char* name);
 /* enable: 0 = off, 1 = every kernel scope, 2 = only ONE kernel: the stage-1 kernel ("join" for the signature algorithms,
- * "stage1" otherwise) or, after selhip_ctx_set_param(ctx, "timed_kernel", 1), stage 2a ("hist") -- an event pair costs ~10 us of
+ * "stage1" otherwise; "dense" for SELHIP_CRIT_NONE) or, after selhip_ctx_set_param(ctx, "timed_kernel", 1), stage 2a ("hist") -- an event pair costs ~10 us of
  * stream time, so level 2 is what a throughput measurement leaves on, on whichever kernel is the longest of the step.
  * Every call resets the accumulated figures. */
 int    selhip_ctx_timing(selhip_ctx* ctx, int enable);
@@ -290,12 +303,13 @@ int    selhip_ctx_timing(selhip_ctx* ctx, int enable);
  *     selhip_ctx_run).  The auxiliary criteria hll_a / hll_an take card_A <= card_B (gamma = e_A / e_B, e_B on its own): a
  *     query pair passes (e_lo, e_hi) in that order, whichever set each member comes from; every other term is symmetric.  So
  *     the result is exactly the cross pairs (one member in Q, one in D) of selhip_ctx_run over Q u D, J bit for bit, for
- *     every criterion: SELHIP_CRIT_SMH_A, _HLL_A, _HLL_AN and the two-stage _HLL_A_SMH_A.
+ *     every criterion: SELHIP_CRIT_SMH_A, _HLL_A, _HLL_AN, the two-stage _HLL_A_SMH_A and _NONE (every (q, d) with d inside q's
+ *     CB window -- SELHIP_MODE_SMH: every d -- and e_hi != 0 goes to the J test; algo, n_rows and n_bands are ignored).
  *     Records {i = query rank, k = database rank, jaccard} are read with selhip_ctx_result_count / _fetch (sorted by (i,k)),
  *     selhip_ctx_stats (evaluated = cross pairs inside the CB windows with e_hi != 0; survivors = the cross pairs that pass the
  *     criterion before the J test -- smh_a, hll_a / hll_an, or both for the two-stage criterion, as selhip_ctx_run reports them)
  *     and selhip_ctx_last_attempts.
- *     Criteria other than smh_a need the auxiliary HLL sketches of both sets (selhip_ctx_upload_aux_hll for D,
+ *     Criteria other than smh_a and none need the auxiliary HLL sketches of both sets (selhip_ctx_upload_aux_hll for D,
  *     selhip_ctx_upload_queries_aux_hll for Q; SELHIP_E_STATE without them) with the same p_aux (SELHIP_E_BADARG otherwise).
  *     Where the smh_a stage runs (smh_a, two-stage) n_rows * n_bands must be m and algo is: SELHIP_ALGO_SIG (power-of-two
  *     rows, 8..128 bands: band signatures of a query tile in LDS against the database's, which are kept for the band shape
@@ -335,7 +349,7 @@ int selhip_ctx_run_queries(selhip_ctx* ctx, int mode, int algo, float tau_f, int
  *     sketches, and the selected-pair lists are gathered -- over RCCL/xGMI (ncclAllGather of framed record buffers on
  *     communicators from ncclCommInitAll; librccl is dlopen'ed on first use) or through the host.
  *     Any criterion (SELHIP_CRIT_*): h_aux_hll / p_aux carry the auxiliary HLL sketches of hll_a, hll_an and the two-stage
- *     criterion of BASELINE configs[4] (NULL / 0 for smh_a).  Rows are dealt to the devices in interleaved blocks of 128
+ *     criterion of BASELINE configs[4] (NULL / 0 for smh_a and for SELHIP_CRIT_NONE).  Rows are dealt to the devices in interleaved blocks of 128
  *     (selhip_ctx_set_row_interleave).  h_out receives min(count, cap) records sorted by (i,k); stats_out (optional) as
  *     selhip_ctx_stats.
  * --------------------------------------------------------------------------------------------------- */
@@ -356,7 +370,7 @@ int selhip_multi_select(const int* devices, int n_devices,
  *     pair is evaluated exactly once and the result -- pairs, Jaccard values, statistics -- is identical to one in-core
  *     pass over the whole set.  n_streams = 2 runs two block pairs at a time (own buffers, own context, own host thread):
  *     the upload of one overlaps the pass of the other; device memory needed ~ n_streams * 2 * block_genomes sketches.
- *     h_aux_hll/p_aux are only needed for criteria other than SELHIP_CRIT_SMH_A (NULL/0 otherwise).
+ *     h_aux_hll/p_aux are only needed for the criteria with an auxiliary-HLL stage (NULL/0 for SELHIP_CRIT_SMH_A and _NONE).
  *     h_out receives min(count, cap) records with GLOBAL ranks, sorted by (i,k); SELHIP_E_OVERFLOW (count still exact)
  *     if cap was too small.
  * --------------------------------------------------------------------------------------------------- */

@@ -10,6 +10,12 @@
   experiments.py time -l LIST | -N GENOMES [-m BUCKETS ...] [-h TAU] [-R REPS] [-t THREADS] [-o experiment_smh.csv]
       impl,threads,mh_size,rep,criterio,tiempo    rows for cpu (oracle library: the OpenMP loop of selection.cpp:270-291,
       modes smh_a and CB+smh_a of time_smh.cpp) and gpu (bin/time_smh_hip records `list;label;tau;seconds`)
+  experiments.py recall -l LIST [-a AUX_BYTES] | --cfg NAME [-N GENOMES]  [-h TAU ...] [-c CRITERION ...] [--modes cb nocb] [-o recall.csv]
+      what every criterion loses against the pass without one (criterion none: every pair inside the CB bound, or every pair, to the
+      HLL-14 Jaccard test), on the MI355X, for a file list or a synthetic configuration of synth.py:
+          cfg,criterion,aux,tau,mode,selected,exhaustive,missed,recall,ms_criterion,ms_exhaustive
+      "missed" comes from a keyed join of the two record sets; a pair of a criterion that the exhaustive pass does not hold (or
+      holds with another Jaccard value) is an error, not a row.  Criteria: smh_a, hll_a, hll_an, hll_a+smh_a.
 """
 import argparse
 import csv
@@ -106,6 +112,82 @@ def timing(args):
     return 0
 
 
+RECALL_CRITERIA = {"smh_a": 0, "hll_a": 1, "hll_an": 2, "hll_a+smh_a": 3}
+
+
+def recall_rows(sel, cfg_name, n, m, p_aux, taus, criteria, modes):
+    """rows of the recall table for the sketches loaded in `sel` (a Selector; auxiliary HLL sketches loaded if a criterion needs
+    them).  Times: host clock around one synchronous pass (the second of two: the first sizes the lists), results left on the device."""
+    import numpy as np
+    import cuda_selection_criteria_amd as pkg
+
+    def timed(tau, mode, r, b):
+        sel.run(tau, mode, r, b, fetch=False)
+        t0 = time.perf_counter()
+        got = sel.run(tau, mode, r, b)
+        return got, (time.perf_counter() - t0) * 1e3
+
+    rows = []
+    for tau in taus:
+        for mode_name in modes:
+            mode = pkg.MODE_CB_SMH if mode_name == "cb" else pkg.MODE_SMH
+            sel.set_criterion(pkg.CRIT_NONE)
+            full, ms_full = timed(tau, mode, 1, 1)
+            key_full = full["i"].astype(np.int64) * n + full["k"]
+            for name in criteria:
+                smh = name in ("smh_a", "hll_a+smh_a")
+                r, b = pkg.banding(m, tau) if smh else (1, 1)
+                sel.set_criterion(RECALL_CRITERIA[name])
+                got, ms = timed(tau, mode, r, b)
+                key = got["i"].astype(np.int64) * n + got["k"]
+                pos = np.minimum(np.searchsorted(key_full, key), max(len(key_full) - 1, 0))
+                ok = len(key) == 0 or (len(key_full) > 0 and np.array_equal(key_full[pos], key)
+                                       and np.array_equal(full["jaccard"][pos].view(np.uint64), got["jaccard"].view(np.uint64)))
+                if not ok:
+                    raise RuntimeError(f"{cfg_name} {name} tau {tau} {mode_name}: a selected pair is not in the exhaustive result")
+                aux = f"m{m}" if name == "smh_a" else f"p{p_aux}" if not smh else f"p{p_aux}+m{m}"
+                rows.append([cfg_name, name, aux, tau, mode_name, len(got), len(full), len(full) - len(got),
+                             f"{len(got) / len(full):.6f}" if len(full) else "", f"{ms:.3f}", f"{ms_full:.3f}"])
+    return rows
+
+
+RECALL_HEADER = ["cfg", "criterion", "aux", "tau", "mode", "selected", "exhaustive", "missed", "recall", "ms_criterion", "ms_exhaustive"]
+
+
+def recall(args):
+    import numpy as np
+    import cuda_selection_criteria_amd as pkg
+    need_aux = any(c != "smh_a" for c in args.c)
+    need_smh = any(c in ("smh_a", "hll_a+smh_a") for c in args.c)
+    with pkg.Selector(0) as sel:
+        if args.l:
+            m = args.a // 8 if need_smh else 0
+            p_aux = args.p if need_aux else 0
+            ds = pkg.load_dataset(args.l, m, p_aux)
+            n, name = len(ds.names), Path(args.l).name
+            sel.upload(ds.hll, ds.aux if m else np.zeros((n, 1), dtype=np.uint64), ds.cards)
+            if p_aux:
+                sel.upload_aux_hll(ds.aux_hll, p_aux)
+            keep = ds
+        else:
+            base = pkg.SYNTH_CONFIGS[args.cfg]
+            base = base.scaled(args.N) if args.N else base
+            p_aux = (base.p_aux or args.p) if need_aux else 0
+            cfg = pkg.SynthConfig(base.name, base.n_genomes, base.m, base.tau, base.seed, p_aux, base.cluster_size, base.mode, base.n_sh_lo, base.n_sh_hi)
+            keep = pkg.synth_device(cfg, device=0)
+            n, m, name = cfg.n_genomes, cfg.m, args.cfg + (f"@{args.N}" if args.N else "")
+            sel.attach(keep[0], keep[1], keep[2])
+            if p_aux:
+                sel.attach_aux_hll(keep[4], p_aux)
+        rows = recall_rows(sel, name, n, m, p_aux, [float(t) for t in args.tau], args.c, args.modes)
+    with open(args.o, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(RECALL_HEADER)
+        w.writerows(rows)
+    print(f"recall: {len(rows)} rows in '{args.o}'")
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter, add_help=False)
     ap.add_argument("--help", action="help")
@@ -118,10 +200,17 @@ def main():
     t.add_argument("-l", default=""); t.add_argument("-N", type=int, default=0); t.add_argument("-m", type=int, nargs="+", default=[512])
     t.add_argument("-h", dest="tau", default="0.9"); t.add_argument("-R", type=int, default=1); t.add_argument("-t", type=int, default=8)
     t.add_argument("-o", default="experiment_smh_comparative.csv")
+    rc = sub.add_parser("recall", add_help=False)
+    rc.add_argument("-l", default=""); rc.add_argument("--cfg", default=""); rc.add_argument("-N", type=int, default=0)
+    rc.add_argument("-a", type=int, default=2048); rc.add_argument("-p", type=int, default=8)
+    rc.add_argument("-h", dest="tau", nargs="+", default=["0.9"]); rc.add_argument("-c", nargs="+", default=list(RECALL_CRITERIA), choices=list(RECALL_CRITERIA))
+    rc.add_argument("--modes", nargs="+", default=["cb"], choices=["cb", "nocb"]); rc.add_argument("-o", default="recall.csv")
     args = ap.parse_args()
     if args.cmd == "time" and not args.l and not args.N:
         sys.exit("time: give -l LIST or -N GENOMES")
-    sys.exit(compare(args) if args.cmd == "compare" else timing(args))
+    if args.cmd == "recall" and bool(args.l) == bool(args.cfg):
+        sys.exit("recall: give -l LIST or --cfg NAME")
+    sys.exit(compare(args) if args.cmd == "compare" else recall(args) if args.cmd == "recall" else timing(args))
 
 
 if __name__ == "__main__":
