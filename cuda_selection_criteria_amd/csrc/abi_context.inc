@@ -55,6 +55,7 @@ void selhip_ctx_destroy(selhip_ctx* c) {
     c->planes.release(); c->small_bar.release();
     c->hll_sparse.release(); c->hll_sparse_dev_t.release();
     release_queries(c);
+    release_topk(c);
     if (c->h_pc) (void)hipHostFree(c->h_pc);
     if (c->st_stage1) {
         (void)hipStreamDestroy(c->st_stage1);
@@ -229,6 +230,8 @@ int selhip_ctx_get_param(const selhip_ctx* c, const char* name, int* value) {
     if (!std::strcmp(name, "chunks"))           { *value = c->n_chunks_last; return SELHIP_OK; }
     if (!std::strcmp(name, "dense_route_used")) { *value = c->dense_route_used; return SELHIP_OK; }         // SELHIP_CRIT_NONE: 1 fused kernel, 0 list route, -1 none yet
     if (!std::strcmp(name, "small_pass_used"))  { *value = c->small_used ? 1 : 0; return SELHIP_OK; }
+    if (!std::strcmp(name, "query_topk"))       { *value = c->query_topk; return SELHIP_OK; }              // K of the query passes' top-k, 0 = off
+    if (!std::strcmp(name, "query_topk_lds_cap")) { *value = kTopkLdsCap; return SELHIP_OK; }              // longest segment its select kernel stages in LDS
     if (!std::strcmp(name, "query_db_sig_builds")) { *value = c->q.db_sig_builds; return SELHIP_OK; }   // database signature builds of the query passes
     if (!std::strcmp(name, "query_db_index_builds")) { *value = c->q.db_idx_builds; return SELHIP_OK; } // builds of ALGO_INDEX's sorted signature index
     if (!std::strcmp(name, "query_db_index_kib")) {                                                     // its resident size (0 = none held)
@@ -411,7 +414,7 @@ int selhip_ctx_run_async(selhip_ctx* c, int mode, int algo, float tau_f, int n_r
     HIPCHK(&c->err, hipSetDevice(c->device));
     c->mode = mode; c->algo = algo; c->tau_f = tau_f; c->n_rows = n_rows; c->n_bands = n_bands; c->plan = plan;
     c->row_begin = row_begin; c->row_end = row_end;
-    c->have_run = false; c->last_was_query = false;
+    c->have_run = false; c->last_was_query = false; c->topk_applied = false;
     std::memset(&c->last, 0, sizeof c->last);
     if (c->n == 0 || row_begin == row_end) { c->pending = false; c->have_run = true; return SELHIP_OK; }
     size_t surv_cap = std::max<size_t>(c->surv.cap, std::max<size_t>((size_t)1 << 20, (size_t)c->n * 16));
@@ -501,13 +504,13 @@ int selhip_ctx_stats(const selhip_ctx* c, int64_t stats[4]) {
 
 int64_t selhip_ctx_result_count(const selhip_ctx* c) {
     if (!c || !c->have_run) return SELHIP_E_STATE;
-    return (int64_t)c->last.n_results;
+    return result_records(c);
 }
 
 int selhip_ctx_fetch(selhip_ctx* c, selhip_pair_t* h_out, int64_t cap) {
     if (!c || (cap > 0 && !h_out) || cap < 0) return SELHIP_E_BADARG;
     if (!c->have_run) return SELHIP_E_STATE;
-    const int64_t cnt = (int64_t)c->last.n_results;
+    const int64_t cnt = result_records(c);
     if (cnt == 0) return SELHIP_OK;
     HIPCHK(&c->err, hipSetDevice(c->device));
     std::vector<selhip_pair_t> tmp((size_t)cnt);
@@ -524,14 +527,14 @@ int selhip_ctx_result_device(selhip_ctx* c, const selhip_pair_t** d_results, int
     if (!c || !d_results || !count) return SELHIP_E_BADARG;
     if (!c->have_run) return SELHIP_E_STATE;
     *d_results = c->results.p;
-    *count = (int64_t)c->last.n_results;
+    *count = result_records(c);
     return SELHIP_OK;
 }
 
 int selhip_ctx_copy_results(selhip_ctx* c, selhip_pair_t* d_dst, int64_t cap) {
     if (!c || cap < 0 || (cap > 0 && !d_dst)) return SELHIP_E_BADARG;
     if (!c->have_run) return SELHIP_E_STATE;
-    const int64_t cnt = std::min<int64_t>((int64_t)c->last.n_results, cap);
+    const int64_t cnt = std::min<int64_t>(result_records(c), cap);
     if (cnt > 0) {
         HIPCHK(&c->err, hipSetDevice(c->device));
         HIPCHK(&c->err, hipMemcpyAsync(d_dst, c->results.p, (size_t)cnt * sizeof(selhip_pair_t), hipMemcpyDeviceToDevice, c->stream));

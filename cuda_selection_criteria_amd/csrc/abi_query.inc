@@ -1,5 +1,5 @@
 // abi_query.inc -- the C ABI of the query passes (include/selection_hip.h section 2b): upload / attach a query set and its auxiliary
-// HLL sketches, run a query pass (any criterion).
+// HLL sketches, run a query pass (any criterion), the top-k option of the query passes.
 // Included by selection_kernels.hip.  The results go through selhip_ctx_result_count / _fetch / _stats / _last_attempts.
 
 extern "C" {
@@ -129,7 +129,8 @@ int selhip_ctx_run_queries(selhip_ctx* c, int mode, int algo, float tau_f, int n
     c->have_run = false;
     std::memset(&c->last, 0, sizeof c->last);
     c->last_was_query = true;
-    if (q.n == 0 || c->n == 0) { c->have_run = true; c->last_attempts = 1; return SELHIP_OK; }
+    c->topk_applied = false; c->topk_n = 0;
+    if (q.n == 0 || c->n == 0) { c->have_run = true; c->last_attempts = 1; c->topk_applied = c->query_topk > 0; return SELHIP_OK; }
     const size_t have = smh ? q.surv.cap : q.fin.cap;
     size_t cap = std::max<size_t>(have, std::max<size_t>((size_t)1 << 16, (size_t)q.n * 16));
     if (c->init_cap > 0) cap = std::max<size_t>(have, (size_t)c->init_cap);             // test hook: start small, grow on overflow
@@ -153,12 +154,40 @@ int selhip_ctx_run_queries(selhip_ctx* c, int mode, int algo, float tau_f, int n
         if (!grow) {
             c->last = pc; c->have_run = true; c->last_attempts = attempt + 1; c->last_was_query = true;
             if (c->criterion == SELHIP_CRIT_NONE) dense_stats(&c->last);
+            if (c->query_topk > 0) {
+                // the pass is accepted and n_results known: every query keeps its K best, on the same stream
+                rc = reduce_query_topk(c);
+                if (rc) { c->have_run = false; return rc; }
+                c->topk_applied = true;
+            }
             return SELHIP_OK;
         }
         res_cap = std::max(res_cap, cap);               // an internal list was too small: counts are exact, grow once and repeat
     }
     set_err(&c->err, "output buffers kept overflowing");
     return SELHIP_E_OVERFLOW;
+}
+
+int selhip_ctx_set_query_topk(selhip_ctx* c, int k) {
+    if (!c) return SELHIP_E_BADARG;
+    if (k < 0 || k > SELHIP_TOPK_MAX) { set_err(&c->err, "query top-k must be 0 (off) or in [1, %d] (got %d)", SELHIP_TOPK_MAX, k); return SELHIP_E_BADARG; }
+    if (c->pending) { set_err(&c->err, "a pass is still pending (selhip_ctx_finish)"); return SELHIP_E_STATE; }
+    c->query_topk = k;
+    return SELHIP_OK;
+}
+
+int selhip_ctx_fetch_ranked(selhip_ctx* c, selhip_pair_t* h_out, int64_t cap) {
+    if (!c || (cap > 0 && !h_out) || cap < 0) return SELHIP_E_BADARG;
+    if (!c->have_run || !c->last_was_query || !c->topk_applied) {
+        set_err(&c->err, "fetch_ranked needs a finished query pass with top-k on (selhip_ctx_set_query_topk)");
+        return SELHIP_E_STATE;
+    }
+    const int64_t cnt = c->topk_n;
+    if (cnt == 0) return SELHIP_OK;
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    HIPCHK(&c->err, hipMemcpyAsync(h_out, c->results.p, (size_t)std::min(cnt, cap) * sizeof(selhip_pair_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    return cnt > cap ? SELHIP_E_OVERFLOW : SELHIP_OK;
 }
 
 }  // extern "C"

@@ -26,6 +26,9 @@
 //               selected pair (one member in each list) in (query rank, database rank) order (selhip_ctx_run_queries; criterion
 //               smh_a, hll_a, hll_an or none -- for hll_a / hll_an the .hll_<p> files of both lists are read; one device -- not combinable
 //               with -g, -B, -o or -r)
+//   -k <n>      with -q: only every query's n best pairs (1..1024), cut on the device (selhip_ctx_set_query_topk), printed in ranked
+//               order: query rank, then J descending, ties by database rank.  The best among the pairs that pass -c and -h, not an
+//               unconditional nearest-neighbour search (for that: -c none -n and a -h below every J, e.g. -1)
 //   -x          usage
 #include <unistd.h>
 
@@ -43,7 +46,7 @@
 // -q: the query list against the database list (-l), both loaded and sorted by cardinality; text on stdout.  criterion: "smh_a"
 // (m = aux_bytes / 8 buckets), "hll_a" / "hll_an" (auxiliary HLL p = ctz(aux_bytes), as the all-pairs mode) or "none" (.hll files only)
 static int run_queries(const std::string& query_file, const std::string& db_file, const std::string& criterion, float threshold,
-                       int aux_bytes, int mode, int algo, int fp_mode, int threads) {
+                       int aux_bytes, int mode, int algo, int fp_mode, int threads, int top_k) {
     const bool smh = criterion == "smh_a";
     const bool none = criterion == "none";
     const int crit = smh ? SELHIP_CRIT_SMH_A : none ? SELHIP_CRIT_NONE : criterion == "hll_a" ? SELHIP_CRIT_HLL_A : SELHIP_CRIT_HLL_AN;
@@ -84,10 +87,11 @@ static int run_queries(const std::string& query_file, const std::string& db_file
     if (!r && p_aux) r = selhip_ctx_upload_aux_hll(ctx, selhost_dataset_aux_hll(db), (int)p_aux);
     if (!r && p_aux) r = selhip_ctx_upload_queries_aux_hll(ctx, selhost_dataset_aux_hll(qs), (int)p_aux);
     if (!r) r = selhip_ctx_set_criterion(ctx, crit);
+    if (!r && top_k) r = selhip_ctx_set_query_topk(ctx, top_k);
     if (!r) r = selhip_ctx_run_queries(ctx, mode, algo, threshold, n_rows, n_bands);
     if (!r) {
         pairs.resize((size_t)selhip_ctx_result_count(ctx));
-        r = selhip_ctx_fetch(ctx, pairs.data(), (int64_t)pairs.size());
+        r = top_k ? selhip_ctx_fetch_ranked(ctx, pairs.data(), (int64_t)pairs.size()) : selhip_ctx_fetch(ctx, pairs.data(), (int64_t)pairs.size());
     }
     if (r) std::cerr << (smh ? "selection: " : what) << selhip_last_error(ctx) << "\n";
     selhip_ctx_destroy(ctx);
@@ -113,13 +117,15 @@ int main(int argc, char* argv[]) {
     int threads = 8, n_gpus = 1, mode = SELHIP_MODE_CB_SMH, algo = SELHIP_ALGO_AUTO, fp_mode = SELHIP_FP_FMA;
     long long ooc_block = 0;
     std::string out_file = "", dump_file = "", query_file = "";
-    bool gpus_given = false;
+    bool gpus_given = false, topk_given = false;
+    long long top_k = 0;
     int c;
-    while ((c = getopt(argc, argv, "xl:b:a:h:c:t:g:nA:F:B:o:r:q:")) != -1) {
+    while ((c = getopt(argc, argv, "xl:b:a:h:c:t:g:nA:F:B:o:r:q:k:")) != -1) {
         switch (c) {
             case 'x': std::cout << "Usage: -l -h -a -b [-c smh_a|hll_a|hll_an|none] [-t threads] [-g gpus] [-n] [-A auto|stream|sig] [-F 0|1] [-B block] [-o file] | -r file\n"
-                                   "       -l db_list -q query_list -h -a [-c smh_a|hll_a|hll_an|none] [-n] [-A auto|stream|sig|index] [-F 0|1]   (query-vs-database selection)\n"; return 0;
+                                   "       -l db_list -q query_list -h -a [-c smh_a|hll_a|hll_an|none] [-n] [-A auto|stream|sig|index] [-F 0|1] [-k best_per_query]   (query-vs-database selection)\n"; return 0;
             case 'q': query_file = optarg; break;
+            case 'k': top_k = std::strtoll(optarg, nullptr, 10); topk_given = true; break;
             case 'B': ooc_block = std::stoll(optarg); break;
             case 'o': out_file = optarg; break;
             case 'r': dump_file = optarg; break;
@@ -136,6 +142,11 @@ int main(int argc, char* argv[]) {
             default: break;
         }
     }
+    if (topk_given) {
+        // checked before any file is read or device opened
+        if (query_file.empty()) { std::cerr << "selection: -k (the best pairs per query) needs -q (the query list)\n"; return 2; }
+        if (top_k < 1 || top_k > SELHIP_TOPK_MAX) { std::cerr << "selection: -k must be in 1.." << SELHIP_TOPK_MAX << "\n"; return 2; }
+    }
     if (!query_file.empty()) {
         // checked before any file is read or device opened
         const char* clash = gpus_given ? "-g" : ooc_block != 0 ? "-B" : !out_file.empty() ? "-o" : !dump_file.empty() ? "-r" : nullptr;
@@ -149,7 +160,7 @@ int main(int argc, char* argv[]) {
             return 2;
         }
         if (list_file.empty()) { std::cerr << "selection: -q needs the database list (-l)\n"; return 2; }
-        return run_queries(query_file, list_file, criterion, threshold, aux_bytes, mode, algo, fp_mode, threads);
+        return run_queries(query_file, list_file, criterion, threshold, aux_bytes, mode, algo, fp_mode, threads, (int)top_k);
     }
     if (algo == SELHIP_ALGO_INDEX) {
         // checked before any file is read or device opened

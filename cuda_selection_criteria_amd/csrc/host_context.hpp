@@ -133,8 +133,8 @@ static_assert(kCounterBlocks == kMaxChunks + 1, "common.cuh: counter blocks per 
 constexpr int kMaxAuxP = SELHIP_MAX_AUX_P;   // auxiliary HLL precision accepted by every entry point: aux_fused_kernel counts in 16-bit bins (a bin holds up to 2^p_aux)
 constexpr long long kEnumPairs = 1ll << 26;    // hll_a / hll_an as first criterion: pairs listed per sub-pass (512 MiB of int2)
 
-enum { T_PREP = 0, T_STAGE1, T_HIST, T_SELECT, T_TOTAL, T_SIGBUILD, T_JOIN, T_VERIFY, T_AUX, T_GROUP, T_DENSE, T_COUNT };
-const char* kTimerNames[T_COUNT] = {"prep", "stage1", "hist", "select", "total", "sigbuild", "join", "verify", "aux", "group", "dense"};
+enum { T_PREP = 0, T_STAGE1, T_HIST, T_SELECT, T_TOTAL, T_SIGBUILD, T_JOIN, T_VERIFY, T_AUX, T_GROUP, T_DENSE, T_TOPK, T_COUNT };
+const char* kTimerNames[T_COUNT] = {"prep", "stage1", "hist", "select", "total", "sigbuild", "join", "verify", "aux", "group", "dense", "topk"};
 
 }  // namespace
 
@@ -285,6 +285,15 @@ struct selhip_ctx {
     int query_index_dir = 1;            // ALGO_INDEX: the probe starts from the bucket directory (0 = searches the whole band segment; "query_index_dir")
     int query_join_tile = 16;           // queries per block of the query passes' signature join (16 or 32; "query_join_tile")
     bool last_was_query = false;        // the results / statistics held are those of a query pass (no framed copies of them)
+    // top-k of the query passes (selhip_ctx_set_query_topk; kernel_topk.cuh, host_topk.hpp)
+    int query_topk = 0;                 // K: every query keeps its K best records; 0 = off
+    bool topk_applied = false;          // the result list holds topk(S, K) of the last finished query pass, in ranked order ...
+    int64_t topk_n = 0;                 // ... and this many records (last.n_results stays |S|)
+    DevBuf<uint32_t> topk_cnt;          // records per query, then the scatter's fill cursors
+    DevBuf<u64> topk_off;               // scanned: (output start << 32) | segment start, one slot past the last query = the totals
+    DevBuf<u64> topk_key;               // the records grouped by query: key(J) ...
+    DevBuf<uint32_t> topk_val;          // ... and database rank
+    DevBuf<char> topk_tmp;              // rocPRIM scan scratch
 
     int timing = 0;                     // 0 off, 1 every kernel scope, 2 dominant stage-1 kernel only
     int dominant_timer = T_STAGE1;

@@ -24,12 +24,15 @@
 //                       binary search per (query, band) in place of the rectangular join
 //   kernel_dense.cuh    dense_select_kernel: criterion "none" -- every pair of the (CB-pruned) pair space to the Jaccard test, union
 //                       histograms into an LDS tile and the estimator in one launch
+//   kernel_topk.cuh     top-k of a query pass: records grouped by query (count, scan, scatter), radix select of each query's K best,
+//                       bitonic sort of the winners
 //   kernel_query_aux.cuh the auxiliary-HLL criteria of query passes: hll_a / hll_an over each query's CB window, the hll_a stage
 //                       of hll_a + smh_a over the smh_a survivors
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (see csrc/Makefile).
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_scan.hpp>         // exclusive scan of the per-row survivor counts (grouping for stage 2)
+#include <rocprim/iterator/transform_iterator.hpp> // the top-k scan reads the per-query counts packed on the fly
 #include <rocprim/device/device_radix_sort.hpp>   // ALGO_HASHJOIN and the query index: the key sort is a library call, everything else is hand-written
 
 #include <algorithm>
@@ -63,11 +66,13 @@
 #include "kernel_query_aux.cuh"
 #include "kernel_query_index.cuh"
 #include "kernel_dense.cuh"
+#include "kernel_topk.cuh"
 
 #include "host_plan.hpp"         // host decisions that are plain arithmetic: build shape, pass plan, criterion constants, overflow rule
 #include "host_context.hpp"      // struct selhip_ctx, device buffers (signature sets, bit planes, counter sets), timers, helpers
 #include "host_pass.hpp"         // pass scheduler: dispatch of every stage, chunk lanes, scratch sizing
 #include "host_query.hpp"        // query passes: Q x D (windows, signature join or stream, verification, stage 2)
+#include "host_topk.hpp"         // top-k of a query pass: scratch, launches, the count the result accessors expose
 #include "abi_context.inc"       // C ABI: context (create, upload / attach, run, results, timing)
 #include "abi_query.inc"         // C ABI: query passes (upload / attach queries, run_queries)
 #include "abi_blocks.inc"        // C ABI: building blocks, synthetic sketches, sketch construction, memory helpers

@@ -231,13 +231,33 @@ class Selector:
         self._keep_q_aux = aux_hll_t
 
     def run_queries(self, tau: float, mode: int = MODE_CB_SMH, n_rows: Optional[int] = None, n_bands: Optional[int] = None,
-                    algo: int = ALGO_AUTO, fetch: bool = True):
+                    algo: int = ALGO_AUTO, fetch: bool = True, top_k: Optional[int] = None):
         """one query pass (queries x database) under the criterion of set_criterion: records {i = query rank, k = database rank,
-        jaccard} sorted by (i, k)"""
+        jaccard} sorted by (i, k).  top_k given: set_query_topk(top_k) first (the setting stays), and with top_k > 0 the records come
+        in ranked order (fetch_ranked): every query's top_k best, J descending, ties by ascending database rank"""
+        if top_k is not None:
+            self.set_query_topk(top_k)
         if n_rows is None or n_bands is None:
             n_rows, n_bands = banding(self.m, tau) if self.m else (1, 1)
         check(self._lib.selhip_ctx_run_queries(self._ctx, mode, algo, np.float32(tau), n_rows, n_bands), self._ctx)
-        return self.fetch() if fetch else None
+        if not fetch:
+            return None
+        return self.fetch_ranked() if top_k else self.fetch()
+
+    def set_query_topk(self, k: int):
+        """the following query passes keep every query's k best records (J descending in the IEEE total order, ties by ascending
+        database rank), cut and ordered on the device: 1 .. TOPK_MAX; 0 = off (the default).  The best among the pairs that pass
+        the criterion and tau, not an unconditional nearest-neighbour search -- for that: CRIT_NONE, MODE_SMH and a tau below every J
+        (e.g. -1).  stats()["selected"] stays the uncut count"""
+        check(self._lib.selhip_ctx_set_query_topk(self._ctx, int(k)), self._ctx)
+
+    def fetch_ranked(self) -> np.ndarray:
+        """the reduced list of the last query pass as it lies on the device: query rank ascending, within a query best first (no host
+        sort); raises unless that pass ran with top-k on"""
+        cnt = self.result_count()
+        out = np.zeros(cnt, dtype=PAIR_DTYPE)
+        check(self._lib.selhip_ctx_fetch_ranked(self._ctx, out.ctypes.data if cnt else None, cnt), self._ctx)
+        return out
 
     def upload_aux_hll(self, aux_hll: np.ndarray, p_aux: int):
         """auxiliary HLL sketches (.hll_<p> files) for the hll_a / hll_an criteria, rank order"""
@@ -444,9 +464,10 @@ def ooc_select(hll: np.ndarray, aux: np.ndarray, cards: np.ndarray, tau: float, 
 
 
 def query_from_filelists(query_list: str, db_list: str, tau: float, aux_bytes: int, mode: int = MODE_CB_SMH, fp_mode: int = FP_FMA,
-                         device: int = 0, algo: int = ALGO_AUTO, criterion: str = "smh_a") -> str:
+                         device: int = 0, algo: int = ALGO_AUTO, criterion: str = "smh_a", top_k: int = 0) -> str:
     """Query-vs-database selection: both lists are loaded and sorted by cardinality (load_dataset); returns one line
     'query_path db_path J' per selected pair, in (query rank, database rank) order, J formatted as selection.cpp prints it.
+    top_k > 0: only every query's top_k best pairs, in ranked order (query rank, then J descending, ties by database rank).
     criterion "smh_a" (m = aux_bytes / 8 buckets), "hll_a" / "hll_an" (auxiliary HLL p = ctz(aux_bytes), as select_from_filelist) or
     "none" (every pair of the CB windows -- MODE_SMH: every cross pair -- to the Jaccard test)."""
     if criterion == "smh_a":
@@ -469,7 +490,7 @@ def query_from_filelists(query_list: str, db_list: str, tau: float, aux_bytes: i
             sel.upload_aux_hll(db.aux_hll, p_aux)
             sel.upload_queries_aux_hll(qs.aux_hll, p_aux)
         sel.set_criterion(crit)
-        pairs = sel.run_queries(tau, mode, n_rows, n_bands, algo)
+        pairs = sel.run_queries(tau, mode, n_rows, n_bands, algo, top_k=top_k if top_k else None)
     h = host_lib()
     buf = C.create_string_buffer(16384)
     out = []

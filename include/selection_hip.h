@@ -210,7 +210,8 @@ int selhip_ctx_set_param(selhip_ctx* ctx, const char* name, int value);
  * "query_db_index_builds" (builds of SELHIP_ALGO_INDEX's sorted signature index since the database was loaded, section 2b),
  * "query_db_index_kib" (resident size of that index in KiB, 0 = none held),
  * "hist_sparse_t" (the sparse threshold the all-pairs stage 2a uses, 0 = every value from the bit planes),
- * "dense_route_used" (SELHIP_CRIT_NONE: the route of the last such pass, 1 = the fused kernel, 0 = the list route; -1 = none yet) */
+ * "dense_route_used" (SELHIP_CRIT_NONE: the route of the last such pass, 1 = the fused kernel, 0 = the list route; -1 = none yet),
+ * "query_topk", "query_topk_lds_cap" (top-k of the query passes, section 2b) */
 int selhip_ctx_get_param(const selhip_ctx* ctx, const char* name, int* value);
 /* Stage 2 grouping (default on): the pairs that reach the HLL-14 stage are bucketed by query row (counting sort) so
  * that waves running side by side on one XCD share their query row in L2.  0 = off (same kernel, list as produced). */
@@ -284,7 +285,7 @@ int selhip_ctx_last_attempts(const selhip_ctx* ctx);
 /* device time (ms, HIP events on the stream each kernel is launched on) of the named kernel PER PASS, averaged over
  * the passes since the last reset (a pipelined pass launches a kernel once per row chunk: the figure is their sum);
  * names: "prep", "sigbuild", "join", "verify", "stage1", "aux", "group", "hist", "select", "dense" (the fused kernel of
- * SELHIP_CRIT_NONE), "total"; "join_span" = first start to
+ * SELHIP_CRIT_NONE), "topk" (the cut of a query pass with selhip_ctx_set_query_topk, section 2b: its four launches; not part of "total"), "total"; "join_span" = first start to
  * last end of the pass's join launches (chunk lanes run them side by side).  <0 if never launched.
  * selhip_ctx_kernel_launches: launches of that kernel per pass. */
 double selhip_ctx_kernel_ms(const selhip_ctx* ctx, const char* name);
@@ -306,6 +307,7 @@ int    selhip_ctx_timing(selhip_ctx* ctx, int enable);
  *     every criterion: SELHIP_CRIT_SMH_A, _HLL_A, _HLL_AN, the two-stage _HLL_A_SMH_A and _NONE (every (q, d) with d inside q's
  *     CB window -- SELHIP_MODE_SMH: every d -- and e_hi != 0 goes to the J test; algo, n_rows and n_bands are ignored).
  *     Records {i = query rank, k = database rank, jaccard} are read with selhip_ctx_result_count / _fetch (sorted by (i,k)),
+ *     (both of the k best per query when selhip_ctx_set_query_topk is on, see below),
  *     selhip_ctx_stats (evaluated = cross pairs inside the CB windows with e_hi != 0; survivors = the cross pairs that pass the
  *     criterion before the J test -- smh_a, hll_a / hll_an, or both for the two-stage criterion, as selhip_ctx_run reports them)
  *     and selhip_ctx_last_attempts.
@@ -342,6 +344,33 @@ int selhip_ctx_upload_queries_aux_hll(selhip_ctx* ctx, const uint8_t* h_aux_hll,
 int selhip_ctx_attach_queries_aux_hll(selhip_ctx* ctx, const uint8_t* d_aux_hll, int p_aux);
 /* One query pass, synchronous like selhip_ctx_run; SELHIP_E_STATE before any queries are loaded. */
 int selhip_ctx_run_queries(selhip_ctx* ctx, int mode, int algo, float tau_f, int n_rows, int n_bands);
+
+/* Top-k of the query passes: every query keeps only its k best records, cut and ordered on the device behind the pass.
+ *   S = the result of a query pass as described above.  The sort key of a double J with bit pattern b is the u64
+ *   b ^ 0x8000000000000000 if b's sign bit is clear and ~b if it is set: its unsigned order is the IEEE total order (NaN never passes
+ *   J >= tau_f, and -0.0 cannot arise from (e_lo + e_hi - U) / U).  Within one query, record a RANKS BEFORE record b iff
+ *   key(a.J) > key(b.J), or the keys are equal and a.k < b.k -- database ranks are unique within a query, so this is a strict total
+ *   order and the answer is unique.  topk(S, k) keeps, for every query i, the first min(L_i, k) records of that ranking (L_i = the
+ *   records of query i in S).  The RANKED ORDER of a list is i ascending, then ranking order.
+ * The answer is "the k best among the pairs that pass the criterion and tau_f", not an unconditional k-nearest-neighbour search: a
+ * criterion (smh_a, hll_a, ...) or a threshold that drops a pair drops it here too.  For exact nearest neighbours use SELHIP_CRIT_NONE
+ * with SELHIP_MODE_SMH and a tau_f below every J (negative thresholds are legal in query passes; every J is above -1).
+ * selhip_ctx_set_query_topk: k = 0 switches the cut off (the default: a query pass is exactly what it was without this call),
+ * 1 .. SELHIP_TOPK_MAX switches it on; anything else SELHIP_E_BADARG; SELHIP_E_STATE while a pass is pending.  The setting survives
+ * uploads / attaches and is read by selhip_ctx_run_queries only -- all-pairs passes, selhip_multi_select and selhip_ooc_select never cut.
+ * With k > 0 selhip_ctx_run_queries, once the pass is accepted (every list fitted), replaces the context's result list with
+ * topk(S, k) in ranked order, on the context's stream: selhip_ctx_result_count returns the reduced count, selhip_ctx_fetch the
+ * reduced list in (i, k) order, selhip_ctx_result_device / selhip_ctx_copy_results expose it in ranked order; selhip_ctx_stats is
+ * unchanged (stats[2] = |S|: the difference to selhip_ctx_result_count is what was cut), and so is selhip_ctx_last_attempts.
+ * A pass that selected nothing launches nothing more.  If the cut's scratch (12 bytes per record of S) cannot be allocated the
+ * call returns SELHIP_E_HIP and the pass counts as not run.  At most 2^31 - 1 records per pass (SELHIP_E_BADARG beyond).
+ * get_param "query_topk" = the current k, "query_topk_lds_cap" = the longest segment (records of one query) the select kernel stages
+ * in LDS; longer segments are streamed from global memory by every pass of the selection.  The cut is timed as "topk". */
+#define SELHIP_TOPK_MAX 1024
+int selhip_ctx_set_query_topk(selhip_ctx* ctx, int k);
+/* copies min(count, cap) records of the reduced list as it lies -- ranked order, no host sort; SELHIP_E_STATE unless the last
+ * finished pass was a query pass with top-k on; SELHIP_E_OVERFLOW (after copying cap records) if count > cap */
+int selhip_ctx_fetch_ranked(selhip_ctx* ctx, selhip_pair_t* h_out, int64_t cap);
 
 /* ---------------------------------------------------------------------------------------------------
  * 2c. Multi-GPU entry taking a device list: ONE process, one host thread + one context per
