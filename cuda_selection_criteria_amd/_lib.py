@@ -44,7 +44,7 @@ ALGO_AUTO, ALGO_STREAM, ALGO_SIG, ALGO_HASHJOIN, ALGO_INDEX = 0, 1, 2, 3, 4    #
 FP_STRICT, FP_FMA = 0, 1
 CRIT_SMH_A, CRIT_HLL_A, CRIT_HLL_AN, CRIT_HLL_A_SMH_A, CRIT_NONE = 0, 1, 2, 3, 4
 BANDING_CPU, BANDING_CUDA = 0, 1
-TOPK_MAX = 1024                        # SELHIP_TOPK_MAX: largest k of Selector.set_query_topk
+TOPK_MAX = 1024                        # SELHIP_TOPK_MAX: largest k of Selector.set_query_topk and Selector.set_allpairs_topk
 
 _vp, _i, _i64, _d, _sz, _cp = C.c_void_p, C.c_int, C.c_int64, C.c_double, C.c_size_t, C.c_char_p
 
@@ -95,6 +95,7 @@ HIP_SYMBOLS = {
     "selhip_ctx_run_queries": (_i, [_vp, _i, _i, C.c_float, _i, _i]),
     "selhip_ctx_set_query_topk": (_i, [_vp, _i]),
     "selhip_ctx_fetch_ranked": (_i, [_vp, _vp, _i64]),
+    "selhip_ctx_set_allpairs_topk": (_i, [_vp, _i]),
     "selhip_ctx_upload_queries_aux_hll": (_i, [_vp, _vp, _i]),
     "selhip_ctx_attach_queries_aux_hll": (_i, [_vp, _vp, _i]),
     "selhip_smh_a_pairs": (_i, [_vp, _i, _i, _i, _vp, _i64, _vp, _vp]),

@@ -231,6 +231,7 @@ int selhip_ctx_get_param(const selhip_ctx* c, const char* name, int* value) {
     if (!std::strcmp(name, "dense_route_used")) { *value = c->dense_route_used; return SELHIP_OK; }         // SELHIP_CRIT_NONE: 1 fused kernel, 0 list route, -1 none yet
     if (!std::strcmp(name, "small_pass_used"))  { *value = c->small_used ? 1 : 0; return SELHIP_OK; }
     if (!std::strcmp(name, "query_topk"))       { *value = c->query_topk; return SELHIP_OK; }              // K of the query passes' top-k, 0 = off
+    if (!std::strcmp(name, "allpairs_topk"))    { *value = c->allpairs_topk; return SELHIP_OK; }           // K of the all-pairs passes' top-k, 0 = off
     if (!std::strcmp(name, "query_topk_lds_cap")) { *value = kTopkLdsCap; return SELHIP_OK; }              // longest segment its select kernel stages in LDS
     if (!std::strcmp(name, "query_db_sig_builds")) { *value = c->q.db_sig_builds; return SELHIP_OK; }   // database signature builds of the query passes
     if (!std::strcmp(name, "query_db_index_builds")) { *value = c->q.db_idx_builds; return SELHIP_OK; } // builds of ALGO_INDEX's sorted signature index
@@ -414,9 +415,9 @@ int selhip_ctx_run_async(selhip_ctx* c, int mode, int algo, float tau_f, int n_r
     HIPCHK(&c->err, hipSetDevice(c->device));
     c->mode = mode; c->algo = algo; c->tau_f = tau_f; c->n_rows = n_rows; c->n_bands = n_bands; c->plan = plan;
     c->row_begin = row_begin; c->row_end = row_end;
-    c->have_run = false; c->last_was_query = false; c->topk_applied = false;
+    c->have_run = false; c->last_was_query = false; c->topk_applied = false; c->topk_n = 0;
     std::memset(&c->last, 0, sizeof c->last);
-    if (c->n == 0 || row_begin == row_end) { c->pending = false; c->have_run = true; return SELHIP_OK; }
+    if (c->n == 0 || row_begin == row_end) { c->pending = false; c->have_run = true; c->topk_applied = c->allpairs_topk > 0; return SELHIP_OK; }
     size_t surv_cap = std::max<size_t>(c->surv.cap, std::max<size_t>((size_t)1 << 20, (size_t)c->n * 16));
     if (join16_pass(c)) {
         // the 16-bit join passes ~n_bands * 2^-16 of the pairs it compares on to the 32-bit filter: size the lists for that
@@ -471,6 +472,12 @@ int selhip_ctx_finish(selhip_ctx* c) {
             c->last = pc; c->pending = false; c->have_run = true; c->last_attempts = attempt + 1;
             // (event pairs are read lazily -- selhip_ctx_kernel_ms / _timing / destroy -- so that a timed run does not stall the
             // host between passes; a pass records at most ~20 of them)
+            if (c->allpairs_topk > 0) {
+                // the pass is accepted and n_results known: every genome keeps its K best partners, on the same stream
+                const int rc = reduce_allpairs_topk(c);
+                if (rc) { c->have_run = false; return rc; }
+                c->topk_applied = true;
+            }
             return SELHIP_OK;
         }
         // an output list was too small: counts are exact, so grow once and repeat the pass
@@ -483,6 +490,14 @@ int selhip_ctx_finish(selhip_ctx* c) {
     c->pending = false;
     set_err(&c->err, "output buffers kept overflowing");
     return SELHIP_E_OVERFLOW;
+}
+
+int selhip_ctx_set_allpairs_topk(selhip_ctx* c, int k) {
+    if (!c) return SELHIP_E_BADARG;
+    if (k < 0 || k > SELHIP_TOPK_MAX) { set_err(&c->err, "all-pairs top-k must be 0 (off) or in [1, %d] (got %d)", SELHIP_TOPK_MAX, k); return SELHIP_E_BADARG; }
+    if (c->pending) { set_err(&c->err, "a pass is still pending (selhip_ctx_finish)"); return SELHIP_E_STATE; }
+    c->allpairs_topk = k;
+    return SELHIP_OK;
 }
 
 int selhip_ctx_run(selhip_ctx* c, int mode, int algo, float tau_f, int n_rows, int n_bands,
@@ -547,6 +562,7 @@ int selhip_ctx_copy_results_framed(selhip_ctx* c, void* d_dst, int64_t cap_recor
     if (!c || !d_dst || cap_records < 0) return SELHIP_E_BADARG;
     if (!c->have_run) return SELHIP_E_STATE;
     if (c->last_was_query) { set_err(&c->err, "framed copies are for all-pairs passes; after a query pass use selhip_ctx_copy_results"); return SELHIP_E_STATE; }
+    if (c->allpairs_topk > 0) { set_err(&c->err, "framed copies carry the pass's own count; with the all-pairs top-k on (selhip_ctx_set_allpairs_topk) use selhip_ctx_copy_results"); return SELHIP_E_STATE; }
     HIPCHK(&c->err, hipSetDevice(c->device));
     HIPCHK(&c->err, hipMemcpyAsync(d_dst, &c->pcb->n_results, sizeof(u64), hipMemcpyDeviceToDevice, c->stream));
     const int64_t cnt = std::min<int64_t>((int64_t)c->last.n_results, cap_records);
@@ -561,6 +577,7 @@ int selhip_ctx_copy_results_framed_async(selhip_ctx* c, void* d_dst, int64_t cap
     if (!c->pending && !c->have_run) return SELHIP_E_STATE;
     if (!c->results.p || !c->pcb) return SELHIP_E_STATE;
     if (c->last_was_query && !c->pending) { set_err(&c->err, "framed copies are for all-pairs passes; after a query pass use selhip_ctx_copy_results"); return SELHIP_E_STATE; }
+    if (c->allpairs_topk > 0) { set_err(&c->err, "framed copies carry the pass's own count; with the all-pairs top-k on (selhip_ctx_set_allpairs_topk) use selhip_ctx_copy_results"); return SELHIP_E_STATE; }
     HIPCHK(&c->err, hipSetDevice(c->device));
     if ((uintptr_t)d_dst & 15) { set_err(&c->err, "frame buffer must be 16-byte aligned"); return SELHIP_E_BADARG; }
     static_assert(sizeof(selhip_pair_t) == 16, "frame records are 16 bytes");

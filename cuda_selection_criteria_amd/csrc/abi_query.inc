@@ -178,8 +178,9 @@ int selhip_ctx_set_query_topk(selhip_ctx* c, int k) {
 
 int selhip_ctx_fetch_ranked(selhip_ctx* c, selhip_pair_t* h_out, int64_t cap) {
     if (!c || (cap > 0 && !h_out) || cap < 0) return SELHIP_E_BADARG;
-    if (!c->have_run || !c->last_was_query || !c->topk_applied) {
-        set_err(&c->err, "fetch_ranked needs a finished query pass with top-k on (selhip_ctx_set_query_topk)");
+    if (!c->have_run || !c->topk_applied) {
+        set_err(&c->err, "fetch_ranked needs a finished query pass with top-k on (selhip_ctx_set_query_topk) or a finished all-pairs pass "
+                         "with top-k on (selhip_ctx_set_allpairs_topk)");
         return SELHIP_E_STATE;
     }
     const int64_t cnt = c->topk_n;

@@ -29,6 +29,11 @@
 //   -k <n>      with -q: only every query's n best pairs (1..1024), cut on the device (selhip_ctx_set_query_topk), printed in ranked
 //               order: query rank, then J descending, ties by database rank.  The best among the pairs that pass -c and -h, not an
 //               unconditional nearest-neighbour search (for that: -c none -n and a -h below every J, e.g. -1)
+//   -K <n>      all-pairs selection (-l alone): only every genome's n best partners (1..1024), cut on the device
+//               (selhip_ctx_set_allpairs_topk), printed as "owner_path partner_path J" in ranked order: owner rank, then J descending, ties
+//               by partner rank.  A selected pair counts for both of its genomes, so it can be printed twice, once or not at all.  The
+//               best among the pairs that pass -c and -h (every genome's exact nearest neighbours: -c none -n -h -1); one device, text
+//               output -- not combinable with -q (per-query cut: -k), -g, -B, -o or -r
 //   -x          usage
 #include <unistd.h>
 
@@ -109,6 +114,50 @@ static int run_queries(const std::string& query_file, const std::string& db_file
     return r ? 4 : 0;
 }
 
+// -K: one all-pairs pass over the list with the device-side cut on; text on stdout, one line per kept (owner, partner) record
+static int run_neighbours(const std::string& list_file, int crit, float threshold, int aux_bytes, int mode, int algo, int fp_mode,
+                          int threads, int top_k) {
+    const unsigned m = crit == SELHIP_CRIT_SMH_A ? (unsigned)aux_bytes / 8 : 0;
+    const unsigned p_aux = crit == SELHIP_CRIT_SMH_A || crit == SELHIP_CRIT_NONE ? 0 : (unsigned)__builtin_ctz(aux_bytes ? aux_bytes : 1);
+    selhost_dataset* ds = nullptr;
+    if (selhost_dataset_load(&ds, list_file.c_str(), m, p_aux, fp_mode, threads)) { std::cerr << selhost_last_error() << "\n"; return 1; }
+    const int64_t n = selhost_dataset_size(ds);
+    int n_rows = 1, n_bands = 1;
+    if (m) selhost_banding(m, threshold, SELHOST_BANDING_CPU, &n_rows, &n_bands);
+    std::vector<uint64_t> no_smh(m ? 0 : (size_t)(n > 0 ? n : 1), 0);
+    std::vector<selhip_pair_t> pairs;
+    selhip_ctx* ctx = nullptr;
+    int r = selhip_device_count() > 0 ? selhip_ctx_create(&ctx, 0) : SELHIP_E_NODEVICE;
+    if (r) {
+        std::cerr << "selection: no MI355X (gfx950) device available: " << selhip_last_error(nullptr) << "\n";
+        selhost_dataset_free(ds);
+        return 3;
+    }
+    selhip_ctx_set_fp_mode(ctx, fp_mode);
+    r = selhip_ctx_upload(ctx, selhost_dataset_hll(ds), m ? selhost_dataset_aux(ds) : no_smh.data(), selhost_dataset_cards(ds), n, m ? (int)m : 1, 14);
+    if (!r && p_aux) r = selhip_ctx_upload_aux_hll(ctx, selhost_dataset_aux_hll(ds), (int)p_aux);
+    if (!r) r = selhip_ctx_set_criterion(ctx, crit);
+    if (!r) r = selhip_ctx_set_allpairs_topk(ctx, top_k);
+    if (!r) r = selhip_ctx_run(ctx, mode, algo, threshold, n_rows, n_bands, 0, n);
+    if (!r) {
+        pairs.resize((size_t)selhip_ctx_result_count(ctx));
+        r = selhip_ctx_fetch_ranked(ctx, pairs.data(), (int64_t)pairs.size());
+    }
+    if (r) std::cerr << "selection: " << selhip_last_error(ctx) << "\n";
+    selhip_ctx_destroy(ctx);
+    if (!r) {
+        std::string out;
+        char line[8192];
+        for (const selhip_pair_t& pr : pairs) {
+            const int w = selhost_format_line(selhost_dataset_name(ds, pr.i), selhost_dataset_name(ds, pr.k), pr.jaccard, line, sizeof line);
+            if (w > 0) out.append(line, (size_t)w);
+        }
+        std::cout << out;
+    }
+    selhost_dataset_free(ds);
+    return r ? 4 : 0;
+}
+
 int main(int argc, char* argv[]) {
     std::string list_file = "";
     float threshold = 0.9f;              // selection_cuda.cpp:62
@@ -117,15 +166,17 @@ int main(int argc, char* argv[]) {
     int threads = 8, n_gpus = 1, mode = SELHIP_MODE_CB_SMH, algo = SELHIP_ALGO_AUTO, fp_mode = SELHIP_FP_FMA;
     long long ooc_block = 0;
     std::string out_file = "", dump_file = "", query_file = "";
-    bool gpus_given = false, topk_given = false;
-    long long top_k = 0;
+    bool gpus_given = false, topk_given = false, nbr_given = false;
+    long long top_k = 0, nbr_k = 0;
     int c;
-    while ((c = getopt(argc, argv, "xl:b:a:h:c:t:g:nA:F:B:o:r:q:k:")) != -1) {
+    while ((c = getopt(argc, argv, "xl:b:a:h:c:t:g:nA:F:B:o:r:q:k:K:")) != -1) {
         switch (c) {
             case 'x': std::cout << "Usage: -l -h -a -b [-c smh_a|hll_a|hll_an|none] [-t threads] [-g gpus] [-n] [-A auto|stream|sig] [-F 0|1] [-B block] [-o file] | -r file\n"
-                                   "       -l db_list -q query_list -h -a [-c smh_a|hll_a|hll_an|none] [-n] [-A auto|stream|sig|index] [-F 0|1] [-k best_per_query]   (query-vs-database selection)\n"; return 0;
+                                   "       -l db_list -q query_list -h -a [-c smh_a|hll_a|hll_an|none] [-n] [-A auto|stream|sig|index] [-F 0|1] [-k best_per_query]   (query-vs-database selection)\n"
+                                   "       -l -h -a [-c smh_a|hll_a|hll_an|none] [-n] [-A auto|stream|sig|hashjoin] [-F 0|1] -K best_per_genome   (every genome's best partners, both members of a pair)\n"; return 0;
             case 'q': query_file = optarg; break;
             case 'k': top_k = std::strtoll(optarg, nullptr, 10); topk_given = true; break;
+            case 'K': nbr_k = std::strtoll(optarg, nullptr, 10); nbr_given = true; break;
             case 'B': ooc_block = std::stoll(optarg); break;
             case 'o': out_file = optarg; break;
             case 'r': dump_file = optarg; break;
@@ -146,6 +197,20 @@ int main(int argc, char* argv[]) {
         // checked before any file is read or device opened
         if (query_file.empty()) { std::cerr << "selection: -k (the best pairs per query) needs -q (the query list)\n"; return 2; }
         if (top_k < 1 || top_k > SELHIP_TOPK_MAX) { std::cerr << "selection: -k must be in 1.." << SELHIP_TOPK_MAX << "\n"; return 2; }
+    }
+    if (nbr_given) {
+        // checked before any file is read or device opened
+        if (!query_file.empty()) {
+            std::cerr << "selection: -K (the best partners of every genome of one list) cannot be combined with -q; the best pairs per query are -k\n";
+            return 2;
+        }
+        const char* clash = gpus_given ? "-g" : ooc_block != 0 ? "-B" : !out_file.empty() ? "-o" : !dump_file.empty() ? "-r" : nullptr;
+        if (clash) {
+            std::cerr << "selection: -K (the best partners of every genome) cannot be combined with " << clash
+                      << "; it runs on one device and prints text\n";
+            return 2;
+        }
+        if (nbr_k < 1 || nbr_k > SELHIP_TOPK_MAX) { std::cerr << "selection: -K must be in 1.." << SELHIP_TOPK_MAX << "\n"; return 2; }
     }
     if (!query_file.empty()) {
         // checked before any file is read or device opened
@@ -188,6 +253,7 @@ int main(int argc, char* argv[]) {
         return 0;
     }
     if (list_file.empty()) { std::cerr << "No input file provided\n"; exit(-1); }   // selection.cpp:40-44
+    if (nbr_given) return run_neighbours(list_file, crit, threshold, aux_bytes, mode, algo, fp_mode, threads, (int)nbr_k);
     const unsigned m = crit == SELHIP_CRIT_SMH_A ? (unsigned)aux_bytes / 8 : 0;                      // selection.cpp:231
     const unsigned p_aux = crit == SELHIP_CRIT_SMH_A || crit == SELHIP_CRIT_NONE ? 0 : (unsigned)__builtin_ctz(aux_bytes ? aux_bytes : 1);   // :125
 

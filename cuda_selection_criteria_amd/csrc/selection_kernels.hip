@@ -26,6 +26,7 @@
 //                       histograms into an LDS tile and the estimator in one launch
 //   kernel_topk.cuh     top-k of a query pass: records grouped by query (count, scan, scatter), radix select of each query's K best,
 //                       bitonic sort of the winners
+//   kernel_nbr.cuh      top-k of an all-pairs pass: every record counted and scattered for both of its genomes, then the same select
 //   kernel_query_aux.cuh the auxiliary-HLL criteria of query passes: hll_a / hll_an over each query's CB window, the hll_a stage
 //                       of hll_a + smh_a over the smh_a survivors
 //
@@ -67,12 +68,13 @@
 #include "kernel_query_index.cuh"
 #include "kernel_dense.cuh"
 #include "kernel_topk.cuh"
+#include "kernel_nbr.cuh"
 
 #include "host_plan.hpp"         // host decisions that are plain arithmetic: build shape, pass plan, criterion constants, overflow rule
 #include "host_context.hpp"      // struct selhip_ctx, device buffers (signature sets, bit planes, counter sets), timers, helpers
 #include "host_pass.hpp"         // pass scheduler: dispatch of every stage, chunk lanes, scratch sizing
 #include "host_query.hpp"        // query passes: Q x D (windows, signature join or stream, verification, stage 2)
-#include "host_topk.hpp"         // top-k of a query pass: scratch, launches, the count the result accessors expose
+#include "host_topk.hpp"         // top-k of a query pass and of an all-pairs pass: scratch, launches, the count the result accessors expose
 #include "abi_context.inc"       // C ABI: context (create, upload / attach, run, results, timing)
 #include "abi_query.inc"         // C ABI: query passes (upload / attach queries, run_queries)
 #include "abi_blocks.inc"        // C ABI: building blocks, synthetic sketches, sketch construction, memory helpers

@@ -251,9 +251,18 @@ class Selector:
         (e.g. -1).  stats()["selected"] stays the uncut count"""
         check(self._lib.selhip_ctx_set_query_topk(self._ctx, int(k)), self._ctx)
 
+    def set_allpairs_topk(self, k: int):
+        """the following all-pairs passes (run, run_async + finish) keep every genome's k best partners: a selected pair (i, k, J)
+        counts for both of its genomes, records come as {i = owner, k = partner, jaccard}, ranked like a query's (J descending in the
+        IEEE total order, ties by ascending partner rank), cut and ordered on the device: 1 .. TOPK_MAX; 0 = off (the default).  The
+        reduced list can be longer than the pass's own (up to twice).  The best among the pairs that pass the criterion and tau -- for
+        every genome's exact nearest neighbours: CRIT_NONE, MODE_SMH and a tau below every J (e.g. -1).  stats()["selected"] stays the
+        uncut count; query passes ignore the setting"""
+        check(self._lib.selhip_ctx_set_allpairs_topk(self._ctx, int(k)), self._ctx)
+
     def fetch_ranked(self) -> np.ndarray:
-        """the reduced list of the last query pass as it lies on the device: query rank ascending, within a query best first (no host
-        sort); raises unless that pass ran with top-k on"""
+        """the reduced list of the last pass as it lies on the device: query rank (all-pairs: owner rank) ascending, within it best
+        first (no host sort); raises unless that pass ran with its top-k on"""
         cnt = self.result_count()
         out = np.zeros(cnt, dtype=PAIR_DTYPE)
         check(self._lib.selhip_ctx_fetch_ranked(self._ctx, out.ctypes.data if cnt else None, cnt), self._ctx)
@@ -305,12 +314,19 @@ class Selector:
 
     # -- the hot path -------------------------------------------------------------------------------
     def run(self, tau: float, mode: int = MODE_CB_SMH, n_rows: Optional[int] = None, n_bands: Optional[int] = None,
-            rows: Optional[Tuple[int, int]] = None, algo: int = ALGO_AUTO, fetch: bool = True):
+            rows: Optional[Tuple[int, int]] = None, algo: int = ALGO_AUTO, fetch: bool = True, top_k: Optional[int] = None):
+        """one all-pairs pass: records {i, k, jaccard}, i < k, sorted by (i, k).  top_k given: set_allpairs_topk(top_k) first (the
+        setting stays), and with top_k > 0 the records come in ranked order (fetch_ranked): every genome's top_k best partners as
+        {i = owner, k = partner, jaccard}, J descending, ties by ascending partner rank"""
+        if top_k is not None:
+            self.set_allpairs_topk(top_k)
         if n_rows is None or n_bands is None:
             n_rows, n_bands = banding(self.m, tau) if self.m else (1, 1)
         rb, re = rows if rows is not None else (0, self.n)
         check(self._lib.selhip_ctx_run(self._ctx, mode, algo, np.float32(tau), n_rows, n_bands, rb, re), self._ctx)
-        return self.fetch() if fetch else None
+        if not fetch:
+            return None
+        return self.fetch_ranked() if top_k else self.fetch()
 
     def run_async(self, tau: float, mode: int = MODE_CB_SMH, n_rows: Optional[int] = None, n_bands: Optional[int] = None,
                   rows: Optional[Tuple[int, int]] = None, algo: int = ALGO_AUTO):
@@ -379,10 +395,12 @@ class Selector:
 
 
 def select_from_filelist(list_file: str, tau: float, aux_bytes: int, mode: int = MODE_CB_SMH, device: int = 0,
-                         fp_mode: int = FP_FMA, algo: int = ALGO_AUTO, criterion: str = "smh_a") -> str:
+                         fp_mode: int = FP_FMA, algo: int = ALGO_AUTO, criterion: str = "smh_a", top_k: int = 0) -> str:
     """The whole of selection_cuda.cpp main() (criterion smh_a) -- and of selection.cpp's hll_a / hll_an
     branches (:122-227): returns the text the CPU reference prints for `-c criterion -a aux_bytes -h tau`.
-    criterion "none": no criterion in front of the Jaccard test (CRIT_NONE; mode MODE_CB_SMH = the CB bound alone, MODE_SMH = every pair)."""
+    criterion "none": no criterion in front of the Jaccard test (CRIT_NONE; mode MODE_CB_SMH = the CB bound alone, MODE_SMH = every pair).
+    top_k > 0: only every genome's top_k best partners, one line 'owner_path partner_path J' each, in ranked order (owner rank, then J
+    descending, ties by partner rank): a selected pair can be printed twice (once per member), once or not at all."""
     if criterion == "smh_a":
         m, p_aux, crit = aux_bytes // 8, 0, CRIT_SMH_A                       # selection.cpp:231
     elif criterion in ("hll_a", "hll_an"):
@@ -400,7 +418,7 @@ def select_from_filelist(list_file: str, tau: float, aux_bytes: int, mode: int =
         if p_aux:
             sel.upload_aux_hll(ds.aux_hll, p_aux)
         sel.set_criterion(crit)
-        pairs = sel.run(tau, mode, n_rows, n_bands, algo=algo)
+        pairs = sel.run(tau, mode, n_rows, n_bands, algo=algo, top_k=top_k if top_k else None)
     return format_lines(ds.names, pairs)
 
 

@@ -211,7 +211,8 @@ int selhip_ctx_set_param(selhip_ctx* ctx, const char* name, int value);
  * "query_db_index_kib" (resident size of that index in KiB, 0 = none held),
  * "hist_sparse_t" (the sparse threshold the all-pairs stage 2a uses, 0 = every value from the bit planes),
  * "dense_route_used" (SELHIP_CRIT_NONE: the route of the last such pass, 1 = the fused kernel, 0 = the list route; -1 = none yet),
- * "query_topk", "query_topk_lds_cap" (top-k of the query passes, section 2b) */
+ * "query_topk", "query_topk_lds_cap" (top-k of the query passes, section 2b),
+ * "allpairs_topk" (the current k of selhip_ctx_set_allpairs_topk, 0 = off) */
 int selhip_ctx_get_param(const selhip_ctx* ctx, const char* name, int* value);
 /* Stage 2 grouping (default on): the pairs that reach the HLL-14 stage are bucketed by query row (counting sort) so
  * that waves running side by side on one XCD share their query row in L2.  0 = off (same kernel, list as produced). */
@@ -282,11 +283,41 @@ int selhip_ctx_copy_results_framed_async(selhip_ctx* ctx, void* d_dst, int64_t c
 /* number of times the last finished run had to enqueue its pass (1 = no internal list overflowed) */
 int selhip_ctx_last_attempts(const selhip_ctx* ctx);
 
+/* Top-k of the all-pairs passes: every genome keeps only its k best partners, cut and ordered on the device behind the pass.
+ *   S = the result of an all-pairs pass (selhip_ctx_run, or selhip_ctx_run_async + selhip_ctx_finish) as described above: any criterion,
+ *   mode, algorithm, row range, row interleave, candidate begin or chunk count, and the one-launch small pass; records {i, k, J}, i < k.
+ *   The DIRECTED LIST D(S) holds two records for every record (i, k, J) of S: {owner i, partner k, J} and {owner k, partner i, J} -- a
+ *   pair belongs to both genomes' lists.  Within one owner, record a RANKS BEFORE record b iff key(a.J) > key(b.J), or the keys are
+ *   equal and a.partner < b.partner, with the sort key of section 2b (selhip_ctx_set_query_topk); partners are unique within an owner,
+ *   so the order is strict and total.  nbr(S, k) keeps, for every genome g in 0 .. n - 1, the first min(L_g, k) records of that ranking
+ *   (L_g = the records of S with i = g or k = g).  Its RANKED ORDER is owner ascending, then ranking order; its records are
+ *   selhip_pair_t {i = owner, k = partner, jaccard}, J bits unchanged.  The reduced count, the sum of min(L_g, k) over all genomes, can be
+ *   LARGER than |S| (up to 2 |S|): a selected pair appears twice, once or not at all.
+ * As for queries this is the k best among the pairs that pass the criterion and tau_f; for every genome's exact nearest neighbours use
+ * SELHIP_CRIT_NONE with SELHIP_MODE_SMH and a tau_f below every J, e.g. -1 (selhip_ctx_run_async puts no bound on tau_f).
+ * selhip_ctx_set_allpairs_topk: k = 0 switches the cut off (the default: an all-pairs pass issues exactly the launches and returns
+ * exactly the bytes it did without this call), 1 .. SELHIP_TOPK_MAX switches it on; anything else SELHIP_E_BADARG; SELHIP_E_STATE while
+ * a pass is pending.  The setting survives uploads / attaches and is read by the all-pairs passes of this context only: query passes
+ * ignore it as all-pairs passes ignore selhip_ctx_set_query_topk, and selhip_multi_select, selhip_ooc_select and the drop-in launchers
+ * use contexts of their own.
+ * With k > 0 selhip_ctx_finish, once the pass is accepted (every list fitted), replaces the context's result list with nbr(S, k) in
+ * ranked order, on the context's stream: selhip_ctx_result_count returns the reduced count, selhip_ctx_fetch the reduced list sorted by
+ * (i, k), selhip_ctx_fetch_ranked / selhip_ctx_result_device / selhip_ctx_copy_results give it as it lies; selhip_ctx_stats and
+ * selhip_ctx_last_attempts are unchanged (stats[2] stays |S|).  selhip_ctx_copy_results_framed / _framed_async return SELHIP_E_STATE
+ * while the setting is on: their header is the device-side |S| counter.  With the setting off selhip_ctx_fetch_ranked after an all-pairs
+ * pass returns SELHIP_E_STATE as before.
+ * A pass that selected nothing launches nothing more.  At most 2^31 - 1 directed records, 2 |S|, per pass (SELHIP_E_BADARG beyond).  The
+ * cut's scratch is 12 bytes per directed record, and the result buffer grows when the reduced count exceeds it; if either cannot be
+ * allocated the call returns SELHIP_E_HIP and the pass counts as not run.  The cut is timed as "topk" (not part of "total").
+ * SELHIP_TOPK_MAX and selhip_ctx_fetch_ranked are declared in section 2b. */
+int selhip_ctx_set_allpairs_topk(selhip_ctx* ctx, int k);
+
 /* device time (ms, HIP events on the stream each kernel is launched on) of the named kernel PER PASS, averaged over
  * the passes since the last reset (a pipelined pass launches a kernel once per row chunk: the figure is their sum);
  * names: "prep", "sigbuild", "join", "verify", "stage1", "aux", "group", "hist", "select", "dense" (the fused kernel of
  * SELHIP_CRIT_NONE), "topk" (the cut of a query pass with selhip_ctx_set_query_topk, section 2b: its four launches; not part of "total"), "total"; "join_span" = first start to
  * last end of the pass's join launches (chunk lanes run them side by side).  <0 if never launched.
+ * "topk" is also the cut of an all-pairs pass with selhip_ctx_set_allpairs_topk (above), again outside "total".
  * selhip_ctx_kernel_launches: launches of that kernel per pass. */
 double selhip_ctx_kernel_ms(const selhip_ctx* ctx, const char* name);
 double selhip_ctx_kernel_launches(const selhip_ctx* ctx, const char* name);
@@ -369,7 +400,8 @@ int selhip_ctx_run_queries(selhip_ctx* ctx, int mode, int algo, float tau_f, int
 #define SELHIP_TOPK_MAX 1024
 int selhip_ctx_set_query_topk(selhip_ctx* ctx, int k);
 /* copies min(count, cap) records of the reduced list as it lies -- ranked order, no host sort; SELHIP_E_STATE unless the last
- * finished pass was a query pass with top-k on; SELHIP_E_OVERFLOW (after copying cap records) if count > cap */
+ * finished pass was a query pass with top-k on; SELHIP_E_OVERFLOW (after copying cap records) if count > cap.
+ * An all-pairs pass with selhip_ctx_set_allpairs_topk on (section 2) leaves a ranked list too, read the same way. */
 int selhip_ctx_fetch_ranked(selhip_ctx* ctx, selhip_pair_t* h_out, int64_t cap);
 
 /* ---------------------------------------------------------------------------------------------------
