@@ -24,15 +24,16 @@ def smh_vecsize(m_arg: int) -> int:
     return int(host_lib().selhost_smh_vecsize(m_arg))
 
 
-def build_sketches(fasta_paths: Sequence[str], m: int = 0, p_aux: int = 0, device: int = 0, k: int = 31):
-    """returns (hll u8 [n,16384], smh u64 [n, vecsize(m)] or None, aux u8 [n, 1<<p_aux] or None) as numpy arrays"""
+def build_from_codes(codes_list: Sequence[np.ndarray], m: int = 0, p_aux: int = 0, k: int = 31, device: int = 0):
+    """codes_list: one uint8 array per genome, 0..3 = A,C,G,T, 4 = k-mer window reset.  One selhip_build_sketches call.
+    returns (hll u8 [n,16384], smh u64 [n, vecsize(m)] or None, aux u8 [n, 1<<p_aux] or None) as numpy arrays"""
     import torch
 
     lib = hip_lib()
-    codes = [fasta_codes(p) for p in fasta_paths]
+    codes = [np.ascontiguousarray(c, dtype=np.uint8).reshape(-1) for c in codes_list]
     n = len(codes)
     offsets = np.zeros(n + 1, dtype=np.int64)
-    offsets[1:] = np.cumsum([len(c) for c in codes])
+    offsets[1:] = np.cumsum([len(c) for c in codes], dtype=np.int64)
     flat = np.concatenate(codes) if n else np.zeros(0, dtype=np.uint8)
     dev = torch.device("cuda", device)
     mv = smh_vecsize(m) if m else 0
@@ -48,3 +49,8 @@ def build_sketches(fasta_paths: Sequence[str], m: int = 0, p_aux: int = 0, devic
         check(lib.selhip_device_synchronize())
         return (d_hll.cpu().numpy(), d_smh.cpu().numpy().view(np.uint64) if mv else None,
                 d_aux.cpu().numpy() if p_aux else None)
+
+
+def build_sketches(fasta_paths: Sequence[str], m: int = 0, p_aux: int = 0, device: int = 0, k: int = 31):
+    """FASTA(.gz) files -> codes -> build_from_codes; same triple"""
+    return build_from_codes([fasta_codes(p) for p in fasta_paths], m, p_aux, k, device)

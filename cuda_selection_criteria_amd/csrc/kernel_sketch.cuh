@@ -67,10 +67,13 @@ void synth_kernel(selhip::SynthParams sp, long long g_begin, long long g_end,
 // h[bucket] keeps the minimum.  The running bound a_ (largest integer part still present) only SKIPS offers that
 // cannot win.  Hence h = min over all elements and all steps j <= a_final, and it is computed here as
 //   pass 0: every k-mer in parallel offers its step-0 value (bucket k_0) with a 64-bit LDS atomic min;
-//   while a = max_b min(m-1, h[b] >> 32) exceeds the number of steps J offered so far: J = a and every k-mer re-runs
-//   its own chain up to step J (a handful of entries of p, kept in a tiny per-thread map) -- or, when a is large
-//   (few k-mers per bucket: tiny inputs), ONE lane runs the reference's sequential algorithm literally.
-// Either way the bytes equal the reference's (tests/test_build_sketch.py: 128 reference-written files).
+//   then a = max_b min(m-1, h[b] >> 32).  After pass 0 every integer part is 0 or "empty", so a is 0 (done) or m-1:
+//   m <= 16 (a <= kSketchJmaxParallel): J = m-1 and every k-mer re-runs its own chain up to step J (at most 2 (J+1)
+//     entries of p, kept in a per-thread map); the loop is written as `while a > J`, but this re-run executes at most
+//     ONCE, because no later a can exceed m-1 = J;
+//   m >= 32 (few k-mers per bucket: tiny inputs): ONE lane runs the reference's sequential algorithm literally.
+// Either way the bytes equal the reference's (tests/test_build_sketch.py: 170 reference-written files;
+// tests/test_build_sketch_shapes.py: launch shapes, window edges, m = 1..32 and k != 31 against the oracle).
 // ---------------------------------------------------------------------------------------------
 __host__ __device__ __forceinline__ u64 canonical_kmer(u64 kmer, unsigned k) {           // build_sketch.cpp:26-39
     const u64 b_kmer = kmer;
@@ -132,8 +135,8 @@ __device__ __forceinline__ void lds_byte_max(uint32_t* words, uint32_t idx, uint
 constexpr int kSketchJmaxParallel = 15;
 constexpr int kSketchSeg = 64;          // consecutive k-mer end positions rolled by one thread
 
-// visits every valid k-mer of the genome once: thread t owns segments t, t+256, ... of kSketchSeg end positions and
-// rolls the 2-bit window through them (30 warm-up bases per segment)
+// visits every valid k-mer of the genome once: thread t owns segments t, t+blockDim.x, ... of kSketchSeg end positions
+// and rolls the 2-bit window through them (k-1 warm-up bases per segment)
 template <typename F>
 __device__ __forceinline__ void for_each_kmer(const uint8_t* __restrict__ codes, long long L, int k, F&& f) {
     const u64 kmask = k == 32 ? ~0ull : ((1ull << (2 * k)) - 1);

@@ -149,6 +149,10 @@ long long orcb_sketch_file(const char *path, unsigned k, uint8_t *hll14, uint8_t
     gzFile fp = gzopen(path, "rb");
     if (!fp) return -1;
     long long added = 0;
+    /* The reference fixes k = 31 (build_sketch.cpp:190), so its mask is (1 << 62) - 1.  For every other k this file is the
+     * project's statement of the natural extension: the low 2k bits, which at k = 32 is the whole word -- a shift by
+     * 64 is undefined in C, so that case is spelled out (the kernel's kmask, kernel_sketch.cuh for_each_kmer). */
+    const uint64_t kmask = k >= 32 ? ~(uint64_t)0 : ((1ULL << (k << 1)) - 1);
     uint64_t kmer = 0;
     unsigned bases = 0;
     int in_header = 0, at_line_start = 1;
@@ -171,7 +175,7 @@ long long orcb_sketch_file(const char *path, unsigned k, uint8_t *hll14, uint8_t
                 default: two_bit = 0; bases = 0; kmer = 0; break;
             }
             kmer = (kmer << 2) | two_bit;
-            kmer = kmer & ((1ULL << (k << 1)) - 1);
+            kmer = kmer & kmask;
             if (bases == k) {
                 uint64_t canon = orcb_canonical_kmer(kmer, k);
                 if (hll14) orcb_hll_add(hll14, 14, orcb_wang_hash(canon));                    /* hll.h:901-904 addh */

@@ -52,13 +52,18 @@ def main():
                 f.write(text)
             names.append(f"{name}.fna.gz")
         (td / "list.txt").write_text("\n".join(names) + "\n")
-        for a in (32, 512, 2048, 8192):
+        for a in (8, 16, 64, 128, 256, 32, 512, 2048, 8192):           # -a / 8 buckets: .smh1 .smh2 .smh8 .smh16 .smh32 | .smh4 .smh64 .smh256 .smh1024
             subprocess.run([str(REF), "-l", "list.txt", "-t", "2", "-a", str(a), "-c", "smh_a"], cwd=td, check=True, capture_output=True)
-        for a in (16, 256):
+        for a in (32, 4096, 16, 256):                                   # log2(-a) bits: .hll_5 .hll_12 | .hll_4 .hll_8
             subprocess.run([str(REF), "-l", "list.txt", "-t", "2", "-a", str(a), "-c", "hll_a"], cwd=td, check=True, capture_output=True)
         for f in sorted(td.iterdir()):
-            if f.name != "list.txt":
-                shutil.copy(f, OUT / f.name)
+            if f.name == "list.txt":
+                continue
+            old = OUT / f.name
+            if old.exists():                              # gzip headers carry a time stamp: keep a committed file whose content is unchanged
+                assert gzip.open(old, "rb").read() == gzip.open(f, "rb").read(), f"{f.name}: content differs from the committed file"
+                continue
+            shutil.copy(f, old)
     print("wrote", len(list(OUT.iterdir())), "files to", OUT)
 
 
