@@ -75,6 +75,8 @@ HIP_SYMBOLS = {
     "selhip_ctx_run": (_i, [_vp, _i, _i, C.c_float, _i, _i, _i64, _i64]),
     "selhip_ctx_run_async": (_i, [_vp, _i, _i, C.c_float, _i, _i, _i64, _i64]),
     "selhip_ctx_finish": (_i, [_vp]),
+    "selhip_ctx_run_pairs": (_i, [_vp, _vp, _i64, _i, _i, C.c_float, _i, _i]),
+    "selhip_ctx_run_pairs_async": (_i, [_vp, _vp, _i64, _i, _i, C.c_float, _i, _i]),
     "selhip_ctx_stats": (_i, [_vp, C.POINTER(_i64)]),
     "selhip_ctx_result_count": (_i64, [_vp]),
     "selhip_ctx_fetch": (_i, [_vp, _vp, _i64]),
@@ -138,6 +140,7 @@ HOST_SYMBOLS = {
     "selhost_dataset_cards": (_vp, [_vp]),
     "selhost_dataset_name": (_cp, [_vp, _i64]),
     "selhost_format_line": (_i, [_cp, _cp, _d, _vp, _sz]),
+    "selhost_read_pair_list": (_i, [_cp, _vp, _i64, _vp, _i64, C.POINTER(_i64)]),
     "selhost_write_results": (_i, [C.c_char_p, _vp, _i64, _vp, _i64, C.c_float]),
     "selhost_read_results": (_i, [_vp, C.c_char_p]),
     "selhost_results_free": (None, [_vp]),

@@ -68,6 +68,7 @@ int compat_launch(bool use_cb, const uint8_t* main_sketches, const uint64_t* aux
     hipStream_t st = nullptr;                                        // default stream, like the reference
     HIPCHK(nullptr, hipMemsetAsync(out_count, 0, sizeof(CountT), st));  // selection_kernels.cu:137,166
     if (total_pairs == 0) return SELHIP_OK;
+    if (pairs && ((uintptr_t)pairs & 7)) { set_err(nullptr, "the pair list must be 8-byte aligned (an array of int2)"); return SELHIP_E_BADARG; }
     const int p = ilog2(m_hll);
     std::lock_guard<std::mutex> lk(g_ws.mu);
     if (!pairs) {
@@ -99,9 +100,12 @@ int compat_launch(bool use_cb, const uint8_t* main_sketches, const uint64_t* aux
     for (long long off = 0; off < total_pairs; off += chunk) {
         const long long len = std::min(chunk, total_pairs - off);
         HIPCHK(nullptr, hipMemsetAsync(g_ws.surv_count.p, 0, sizeof(u64), st));
-        hipLaunchKernelGGL(pairlist_smh_kernel, dim3((unsigned)((len + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
-                           (const u64*)aux, m_aux, n_rows, n_bands, pairs + off, len, cards, tau, 1, use_cb ? 1 : 0,
-                           (uint8_t*)nullptr, g_ws.surv.p, (u64)g_ws.surv.cap, g_ws.surv_count.p);
+        // stage 1: pairs_direct_kernel in its launcher form (kernel_pairs.cuh) -- 16 lanes per pair on contiguous 128-byte pieces of both
+        // rows, one append per block and batch (it replaced the lane-per-pair pairlist_smh_kernel here)
+        const PairsDirectShape sh = pairs_direct_shape((u64)len);
+        hipLaunchKernelGGL(pairs_direct_kernel<true>, dim3(sh.grid), dim3(kPairsBlock), 0, st,
+                           (const u64*)aux, m_aux, n_rows, n_bands, pairs + off, (u64)len, 0, (const u64*)nullptr, cards, tau, use_cb ? 1 : 0, sh.gpw,
+                           g_ws.surv.p, (u64)g_ws.surv.cap, g_ws.surv_count.p, (PassCounters*)nullptr);
         HIPCHK(nullptr, hipGetLastError());
         hipLaunchKernelGGL(hll_union_hist_kernel, dim3(2048), dim3(kBlock), 0, st, main_sketches, p, g_ws.surv.p,
                            g_ws.surv_count.p, (u64)0, (u64)g_ws.surv.cap, g_ws.counts.p);

@@ -230,6 +230,7 @@ int selhip_ctx_get_param(const selhip_ctx* c, const char* name, int* value) {
     if (!std::strcmp(name, "chunks"))           { *value = c->n_chunks_last; return SELHIP_OK; }
     if (!std::strcmp(name, "dense_route_used")) { *value = c->dense_route_used; return SELHIP_OK; }         // SELHIP_CRIT_NONE: 1 fused kernel, 0 list route, -1 none yet
     if (!std::strcmp(name, "small_pass_used"))  { *value = c->small_used ? 1 : 0; return SELHIP_OK; }
+    if (!std::strcmp(name, "pairs_route_used")) { *value = c->pairs_route_used; return SELHIP_OK; }         // list passes: 1 signature, 0 direct, 2 no smh_a stage, -1 none yet
     if (!std::strcmp(name, "query_topk"))       { *value = c->query_topk; return SELHIP_OK; }              // K of the query passes' top-k, 0 = off
     if (!std::strcmp(name, "allpairs_topk"))    { *value = c->allpairs_topk; return SELHIP_OK; }           // K of the all-pairs passes' top-k, 0 = off
     if (!std::strcmp(name, "query_topk_lds_cap")) { *value = kTopkLdsCap; return SELHIP_OK; }              // longest segment its select kernel stages in LDS
@@ -415,7 +416,7 @@ int selhip_ctx_run_async(selhip_ctx* c, int mode, int algo, float tau_f, int n_r
     HIPCHK(&c->err, hipSetDevice(c->device));
     c->mode = mode; c->algo = algo; c->tau_f = tau_f; c->n_rows = n_rows; c->n_bands = n_bands; c->plan = plan;
     c->row_begin = row_begin; c->row_end = row_end;
-    c->have_run = false; c->last_was_query = false; c->topk_applied = false; c->topk_n = 0;
+    c->have_run = false; c->last_was_query = false; c->topk_applied = false; c->topk_n = 0; c->list_pass = false;
     std::memset(&c->last, 0, sizeof c->last);
     if (c->n == 0 || row_begin == row_end) { c->pending = false; c->have_run = true; c->topk_applied = c->allpairs_topk > 0; return SELHIP_OK; }
     size_t surv_cap = std::max<size_t>(c->surv.cap, std::max<size_t>((size_t)1 << 20, (size_t)c->n * 16));
@@ -453,6 +454,13 @@ int selhip_ctx_finish(selhip_ctx* c) {
             continue;
         }
         if (pc.unsorted) { c->pending = false; set_err(&c->err, "cards are not in ascending order"); return SELHIP_E_BADARG; }
+        if (c->list_pass && pc.n_pre) {
+            // (block 0 of a list pass: n_pre = invalid entries, n_pre_segmax = 1 + the index of one of them)
+            c->pending = false;
+            set_err(&c->err, "the pair list holds %llu invalid entries (x == y, or a rank outside [0, %lld)); entry %llu is one",
+                    pc.n_pre, (long long)c->n, pc.n_pre_segmax - 1);
+            return SELHIP_E_BADARG;
+        }
         bool grow = false;
         size_t surv_cap = c->surv.cap, res_cap = c->results.cap;
         const size_t slice = c->surv.cap / (size_t)chunks;
@@ -484,7 +492,7 @@ int selhip_ctx_finish(selhip_ctx* c) {
         res_cap = std::max(res_cap, surv_cap);
         int rc = ensure_scratch(c, surv_cap, res_cap);
         if (rc) { c->pending = false; return rc; }
-        rc = enqueue_pass(c);
+        rc = c->list_pass ? enqueue_pairs_pass(c) : enqueue_pass(c);
         if (rc) { c->pending = false; return rc; }
     }
     c->pending = false;

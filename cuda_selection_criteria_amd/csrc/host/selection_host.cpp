@@ -12,6 +12,7 @@
 #include <fstream>
 #include <memory>
 #include <string>
+#include <unordered_map>
 #include <utility>
 #include <vector>
 
@@ -297,6 +298,36 @@ int selhost_format_line(const char* fn1, const char* fn2, double jaccard, char* 
 }
 
 // ---- on-disk result format ---------------------------------------------------------------------------------
+int selhost_read_pair_list(const char* path, const char* const* names, int64_t n_names, int32_t* out_xy, int64_t cap, int64_t* count) {
+    if (!path || !count || n_names < 0 || (n_names > 0 && !names) || cap < 0 || (cap > 0 && !out_xy)) return fail(SELHOST_E_BADARG, "null or negative argument");
+    *count = 0;
+    std::ifstream file(path);
+    if (!file.is_open()) return fail(SELHOST_E_IO, "cannot open pair file %s", path);
+    std::unordered_map<std::string, int32_t> rank_of;
+    rank_of.reserve((size_t)n_names * 2);
+    for (int64_t r = 0; r < n_names; ++r) rank_of.emplace(names[r], (int32_t)r);      // (a name listed twice keeps its first rank)
+    const char* const ws = " \t\r\n";
+    std::string line;
+    int64_t entries = 0;
+    for (long long line_no = 1; getline(file, line); ++line_no) {
+        const size_t a0 = line.find_first_not_of(ws);
+        if (a0 == std::string::npos) continue;                                           // an empty line
+        const size_t a1 = std::min(line.find_first_of(ws, a0), line.size());
+        const size_t b0 = line.find_first_not_of(ws, a1);
+        if (b0 == std::string::npos) return fail(SELHOST_E_FORMAT, "%s:%lld: fewer than two fields", path, line_no);
+        const size_t b1 = std::min(line.find_first_of(ws, b0), line.size());
+        const std::string na = line.substr(a0, a1 - a0), nb = line.substr(b0, b1 - b0);
+        if (na == nb) return fail(SELHOST_E_FORMAT, "%s:%lld: the two names are equal (%s)", path, line_no, na.c_str());
+        const auto ia = rank_of.find(na), ib = rank_of.find(nb);
+        if (ia == rank_of.end() || ib == rank_of.end())
+            return fail(SELHOST_E_FORMAT, "%s:%lld: unknown name %s", path, line_no, (ia == rank_of.end() ? na : nb).c_str());
+        if (entries < cap) { out_xy[2 * entries] = ia->second; out_xy[2 * entries + 1] = ib->second; }
+        entries += 1;
+    }
+    *count = entries;
+    return SELHOST_OK;
+}
+
 struct selhost_results {
     std::vector<selhost_pair_t> pairs;
     std::vector<std::string> names;

@@ -34,6 +34,10 @@
 //               by partner rank.  A selected pair counts for both of its genomes, so it can be printed twice, once or not at all.  The
 //               best among the pairs that pass -c and -h (every genome's exact nearest neighbours: -c none -n -h -1); one device, text
 //               output -- not combinable with -q (per-query cut: -k), -g, -B, -o or -r
+//   -p <file>   pair-list selection: only the pairs listed in the file, lines "path1 path2[ anything]" with paths of the -l list in
+//               either order -- the lines this program prints, so one run's output is the next run's pair file
+//               (selhip_ctx_run_pairs: a pair listed twice is printed twice).  With every -c, -n, -F, -o and -A auto|sig|stream; one
+//               device -- not combinable with -q, -k, -K, -B or -g above 1
 //   -x          usage
 #include <unistd.h>
 
@@ -165,16 +169,18 @@ int main(int argc, char* argv[]) {
     std::string criterion = "smh_a";
     int threads = 8, n_gpus = 1, mode = SELHIP_MODE_CB_SMH, algo = SELHIP_ALGO_AUTO, fp_mode = SELHIP_FP_FMA;
     long long ooc_block = 0;
-    std::string out_file = "", dump_file = "", query_file = "";
+    std::string out_file = "", dump_file = "", query_file = "", pair_file = "";
     bool gpus_given = false, topk_given = false, nbr_given = false;
     long long top_k = 0, nbr_k = 0;
     int c;
-    while ((c = getopt(argc, argv, "xl:b:a:h:c:t:g:nA:F:B:o:r:q:k:K:")) != -1) {
+    while ((c = getopt(argc, argv, "xl:b:a:h:c:t:g:nA:F:B:o:r:q:k:K:p:")) != -1) {
         switch (c) {
             case 'x': std::cout << "Usage: -l -h -a -b [-c smh_a|hll_a|hll_an|none] [-t threads] [-g gpus] [-n] [-A auto|stream|sig] [-F 0|1] [-B block] [-o file] | -r file\n"
                                    "       -l db_list -q query_list -h -a [-c smh_a|hll_a|hll_an|none] [-n] [-A auto|stream|sig|index] [-F 0|1] [-k best_per_query]   (query-vs-database selection)\n"
-                                   "       -l -h -a [-c smh_a|hll_a|hll_an|none] [-n] [-A auto|stream|sig|hashjoin] [-F 0|1] -K best_per_genome   (every genome's best partners, both members of a pair)\n"; return 0;
+                                   "       -l -h -a [-c smh_a|hll_a|hll_an|none] [-n] [-A auto|stream|sig|hashjoin] [-F 0|1] -K best_per_genome   (every genome's best partners, both members of a pair)\n"
+                                   "       -l list -p pair_file -h -a [-c smh_a|hll_a|hll_an|none] [-n] [-A auto|stream|sig] [-F 0|1] [-o file]   (only the listed pairs; lines 'path1 path2 ...')\n"; return 0;
             case 'q': query_file = optarg; break;
+            case 'p': pair_file = optarg; break;
             case 'k': top_k = std::strtoll(optarg, nullptr, 10); topk_given = true; break;
             case 'K': nbr_k = std::strtoll(optarg, nullptr, 10); nbr_given = true; break;
             case 'B': ooc_block = std::stoll(optarg); break;
@@ -191,6 +197,15 @@ int main(int argc, char* argv[]) {
             case 'A': algo = !strcmp(optarg, "stream") ? SELHIP_ALGO_STREAM : !strcmp(optarg, "sig") ? SELHIP_ALGO_SIG : !strcmp(optarg, "hashjoin") ? SELHIP_ALGO_HASHJOIN : !strcmp(optarg, "index") ? SELHIP_ALGO_INDEX : SELHIP_ALGO_AUTO; break;
             case 'F': fp_mode = std::stoi(optarg) ? SELHIP_FP_FMA : SELHIP_FP_STRICT; break;
             default: break;
+        }
+    }
+    if (!pair_file.empty()) {
+        // checked before any file is read or device opened
+        const char* clash = !query_file.empty() ? "-q" : topk_given ? "-k" : nbr_given ? "-K" : ooc_block != 0 ? "-B" : gpus_given && n_gpus > 1 ? "-g" : nullptr;
+        if (clash) {
+            std::cerr << "selection: -p (selection over a list of pairs) cannot be combined with " << clash
+                      << "; it runs one pass over the listed pairs on one device\n";
+            return 2;
         }
     }
     if (topk_given) {
@@ -316,7 +331,23 @@ int main(int argc, char* argv[]) {
         r = selhip_ctx_upload(ctx, selhost_dataset_hll(ds), aux_ptr, selhost_dataset_cards(ds), n, m_up, 14);
         if (!r && p_aux) r = selhip_ctx_upload_aux_hll(ctx, selhost_dataset_aux_hll(ds), (int)p_aux);
         if (!r) r = selhip_ctx_set_criterion(ctx, crit);
-        if (!r) r = selhip_ctx_run(ctx, mode, algo, threshold, n_rows, n_bands, 0, n);
+        void* d_list = nullptr;
+        if (!r && !pair_file.empty()) {
+            // the listed pairs as ranks of the sorted list, then one pass over them
+            std::vector<const char*> names((size_t)n);
+            for (int64_t g = 0; g < n; ++g) names[(size_t)g] = selhost_dataset_name(ds, g);
+            std::vector<int32_t> xy;
+            int64_t cnt = 0;
+            int hr = selhost_read_pair_list(pair_file.c_str(), names.data(), n, nullptr, 0, &cnt);
+            if (!hr) { xy.resize((size_t)cnt * 2); hr = selhost_read_pair_list(pair_file.c_str(), names.data(), n, xy.data(), cnt, &cnt); }
+            if (hr) { std::cerr << "selection: " << selhost_last_error() << "\n"; selhip_ctx_destroy(ctx); return 5; }
+            if (cnt > 0x7FFFFFFFll) { std::cerr << "selection: more than 2^31 - 1 pairs in " << pair_file << "\n"; selhip_ctx_destroy(ctx); return 5; }
+            if (cnt) r = selhip_malloc(&d_list, (size_t)cnt * 8);
+            if (!r && cnt) r = selhip_memcpy_h2d(d_list, xy.data(), (size_t)cnt * 8);
+            if (!r) r = selhip_ctx_run_pairs(ctx, static_cast<const selhip_int2_t*>(d_list), cnt, mode, algo, threshold, n_rows, n_bands);
+        } else if (!r) {
+            r = selhip_ctx_run(ctx, mode, algo, threshold, n_rows, n_bands, 0, n);
+        }
         if (!r) {
             int64_t cnt = selhip_ctx_result_count(ctx);
             parts[0].resize((size_t)cnt);
@@ -324,6 +355,7 @@ int main(int argc, char* argv[]) {
         }
         if (r) { std::cerr << "selection: " << selhip_last_error(ctx) << "\n"; selhip_ctx_destroy(ctx); return 4; }
         selhip_ctx_destroy(ctx);
+        if (d_list) selhip_free(d_list);
     }
 
     if (!out_file.empty()) {

@@ -296,6 +296,12 @@ struct selhip_ctx {
     DevBuf<uint32_t> topk_val;          // ... and database rank
     DevBuf<char> topk_tmp;              // rocPRIM scan scratch
 
+    // pair-list passes (selhip_ctx_run_pairs; abi_pairs.inc, host_pairs.hpp): the pending / last pass evaluates a caller's list
+    bool list_pass = false;
+    const selhip_int2_t* list_pairs = nullptr;     // the caller's, alive until selhip_ctx_finish (a pass that outgrows a list reads it again)
+    int64_t list_n = 0;
+    int pairs_route_used = -1;          // stage 1 of the last list pass: 1 signature route, 0 direct route, 2 no smh_a stage, -1 none yet
+
     int timing = 0;                     // 0 off, 1 every kernel scope, 2 dominant stage-1 kernel only
     int dominant_timer = T_STAGE1;
     int timed_kernel = 0;               // timing level 2 keeps the events of: 0 = the stage-1 kernel (join / stream), 1 = stage 2a ("timed_kernel")

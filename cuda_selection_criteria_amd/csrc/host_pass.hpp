@@ -214,6 +214,13 @@ hipError_t launch_sig_kernel(selhip_ctx* c, SigSet& s, int n_rows, int n_bands, 
     return hipGetLastError();
 }
 
+// what the context's signature arrays hold after a build for this band shape under the current settings (never 0): the "sig_cache" key
+long long sig_cache_key(const selhip_ctx* c, int n_rows, int n_bands) {
+    const SigBuildShape sh = sig_build_shape(c->m, (int)c->n, n_rows, n_bands, c->sig_tile, c->sig_tile_g);
+    return ((long long)n_rows << 40) | ((long long)n_bands << 20) | ((long long)join_sliced(c, n_rows, n_bands) << 3) | ((long long)(c->join_bits == 15) << 2) |
+           (sh.tile_g ? 2 : 0) | 1;
+}
+
 // the all-pairs pass's build of the context's own signatures, with the pass's bounds computation riding in its first blocks
 hipError_t launch_sig_build(selhip_ctx* c, int n_rows, int n_bands, double tau, int rb, int re, PassCounters* zero_pc) {
     const int n = (int)c->n;
@@ -224,8 +231,7 @@ hipError_t launch_sig_build(selhip_ctx* c, int n_rows, int n_bands, double tau, 
     // sketches (the ranks of a strong-scaled job, a threshold sweep) builds them once; upload / attach and any reallocation of the
     // signature arrays invalidate them.  The bounds blocks still run every pass (they depend on tau, the mode and the rows).  The key
     // holds the layout of sigP / sigG (15-bit, 16-bit packed or sliced), so a join never reads words written for another.
-    const long long sig_key = ((long long)n_rows << 40) | ((long long)n_bands << 20) | ((long long)slice << 3) | ((long long)(c->join_bits == 15) << 2) |
-                              (sh.tile_g ? 2 : 0) | 1;
+    const long long sig_key = sig_cache_key(c, n_rows, n_bands);
     const bool cached = c->sig_cache && c->sig_key == sig_key;
     c->sig_key = c->sig_cache ? sig_key : 0;
     const SigBuildPass a{cached ? 0u : sh.blocks, (n + kBlock - 1) / kBlock,
@@ -714,6 +720,26 @@ int enqueue_dense(selhip_ctx* c, int rb, int re, double tau, PassCounters* pc0) 
     return SELHIP_OK;
 }
 
+// chunk k's slices of the pass's buffers (one chunk = the whole of each); pc0 = the pass's counter block 0
+Chain chain_slices(selhip_ctx* c, int k, int chunks, hipStream_t st, long long b, long long e, PassCounters* pc0, bool count_in_verify) {
+    const int n = (int)c->n;
+    const u64 slice = (u64)c->surv.cap / (u64)chunks;
+    Chain ch;
+    ch.io = StageIO{st, c->cand.p + (size_t)k * slice, c->surv.p + (size_t)k * slice, slice, pc0 + 1 + k};
+    ch.io.seg_cnt = c->seg_cnt.p + (size_t)(1 + k) * kAppendSegs * kSegStride;
+    ch.rb = (int)b; ch.re = (int)e;
+    ch.fin = c->fin.p ? c->fin.p + (size_t)k * ((u64)c->fin.cap / (u64)chunks) : nullptr;
+    ch.fin_cap = (u64)c->fin.cap / (u64)chunks;
+    ch.csr_cnt = c->csr_cnt.p ? c->csr_cnt.p + (size_t)k * csr_stride(n) : nullptr;
+    ch.csr_start = c->csr_start.p ? c->csr_start.p + (size_t)k * ((size_t)n + 2) : nullptr;
+    ch.scan_tmp = c->scan_tmp.p ? c->scan_tmp.p + (size_t)k * c->scan_tmp_stride : nullptr;
+    ch.grouped = c->grouped.p ? c->grouped.p + (size_t)k * slice : nullptr;
+    ch.window = ((u64)c->counts.cap / 64) / (u64)chunks;
+    ch.counts = c->counts.p + (size_t)k * ch.window * 64;
+    if (count_in_verify) { ch.io.row_cnt = ch.csr_cnt; if (label_order(c)) ch.io.row_lab = ch.csr_cnt + 2 * (size_t)n; }
+    return ch;
+}
+
 int enqueue_pass(selhip_ctx* c) {
     const int n = (int)c->n;
     const int rb = (int)c->row_begin, re = (int)c->row_end;
@@ -766,24 +792,7 @@ int enqueue_pass(selhip_ctx* c) {
     const int chunks = pipeline_chunks(c);
     c->n_chunks_last = chunks;
     const bool count_in_verify = crit == SELHIP_CRIT_SMH_A && join16_pass(c) && grouping_on(c);
-    // chunk k's slices of the pass's buffers (one chunk = the whole of each)
-    auto chain_of = [&](int k, hipStream_t st, long long b, long long e) {
-        const u64 slice = (u64)c->surv.cap / (u64)chunks;
-        Chain ch;
-        ch.io = StageIO{st, c->cand.p + (size_t)k * slice, c->surv.p + (size_t)k * slice, slice, pc0 + 1 + k};
-        ch.io.seg_cnt = c->seg_cnt.p + (size_t)(1 + k) * kAppendSegs * kSegStride;
-        ch.rb = (int)b; ch.re = (int)e;
-        ch.fin = c->fin.p ? c->fin.p + (size_t)k * ((u64)c->fin.cap / (u64)chunks) : nullptr;
-        ch.fin_cap = (u64)c->fin.cap / (u64)chunks;
-        ch.csr_cnt = c->csr_cnt.p ? c->csr_cnt.p + (size_t)k * csr_stride(n) : nullptr;
-        ch.csr_start = c->csr_start.p ? c->csr_start.p + (size_t)k * ((size_t)n + 2) : nullptr;
-        ch.scan_tmp = c->scan_tmp.p ? c->scan_tmp.p + (size_t)k * c->scan_tmp_stride : nullptr;
-        ch.grouped = c->grouped.p ? c->grouped.p + (size_t)k * slice : nullptr;
-        ch.window = ((u64)c->counts.cap / 64) / (u64)chunks;
-        ch.counts = c->counts.p + (size_t)k * ch.window * 64;
-        if (count_in_verify) { ch.io.row_cnt = ch.csr_cnt; if (label_order(c)) ch.io.row_lab = ch.csr_cnt + 2 * (size_t)n; }
-        return ch;
-    };
+    auto chain_of = [&](int k, hipStream_t st, long long b, long long e) { return chain_slices(c, k, chunks, st, b, e, pc0, count_in_verify); };
     if (chunks > 1) {
         // ---- row chunks, each a whole chain (join -> verify -> [auxiliary criterion] -> grouping -> histogram -> estimate) on one of
         // two streams: while one chunk's short tail kernels (tens of microseconds each, far too few waves to fill the chip) run, the

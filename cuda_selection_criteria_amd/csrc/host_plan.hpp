@@ -111,6 +111,15 @@ bool results_overflowed(u64 n_results, size_t have, size_t* res_cap) {
     return true;
 }
 
+// pairs_direct_kernel: groups of four entries per wave and batch, and the grid -- one group per wave until the list has a group for
+// every wave slot of the device (1 024 blocks of 8 waves), then up to 16
+struct PairsDirectShape { int gpw; unsigned grid; };
+PairsDirectShape pairs_direct_shape(u64 n_pairs) {
+    const u64 slots = 1024ull * 8;
+    const int gpw = (int)std::min<u64>(16, std::max<u64>(1, n_pairs / (4 * slots)));
+    return {gpw, grid_for(n_pairs, 32u * (unsigned)gpw, 1024)};
+}
+
 // bit range of the band keys (band << 32 | signature) that the sort join and the query index sort
 unsigned band_key_end_bit(int n_bands) { return 32u + (unsigned)ilog2(n_bands) + 1u; }
 

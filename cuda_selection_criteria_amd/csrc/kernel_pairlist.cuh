@@ -1,11 +1,12 @@
-// kernel_pairlist.cuh -- explicit pair lists: drop-in launcher path and test building blocks.
+// kernel_pairlist.cuh -- explicit pair lists: test building blocks (selhip_smh_a_pairs, selhip_smh_match_counts) and small helpers.
+// (Stage 1 of the pair-list passes and of the drop-in launchers' explicit-list path is kernel_pairs.cuh.)
 // Part of libselhip.so; included by selection_kernels.hip only (one translation unit, anonymous namespace).
 #pragma once
 
 namespace {
 
 // ---------------------------------------------------------------------------------------------
-// explicit pair lists (drop-in launchers and test building blocks): one LANE per pair.
+// explicit pair lists (selhip_smh_a_pairs, a test building block): one LANE per pair.
 //   flags[j] = pair passes [e_y != 0] [CB] smh_a ;  optionally compacts survivors.
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock)

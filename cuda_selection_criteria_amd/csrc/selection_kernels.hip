@@ -15,7 +15,9 @@
 //   kernel_sigjoin.cuh  sig_build / sig_join / verify   stage 1 ALGO_SIG: all-pairs band-signature join (DPP broadcast) + exact verify
 //   kernel_hll.cuh      hll_union_hist_kernel, ertl_select_kernel (stage 2), enum_pairs / aux_fused (hll_a, hll_an)
 //   kernel_hllbs.cuh    hll_bitslice_kernel, hll_union_hist_bs_kernel: stage 2a on bit-sliced registers (bit-serial max, decode tree, v_bcnt)
-//   kernel_pairlist.cuh explicit pair lists (drop-in launch_kernel_* path, test building blocks)
+//   kernel_pairlist.cuh explicit pair lists (test building blocks)
+//   kernel_pairs.cuh    stage 1 of the pair-list passes (a caller's list of pairs under any criterion) and of the drop-in launchers'
+//                       explicit-list path: filter, signature verification, direct band comparison
 //   kernel_sketch.cuh   synth_kernel, sketch_build_kernel (build_sketch on the GPU), permute_rows
 //   kernel_small.cuh    small_pass_kernel: the whole pass of a set of <= 2 048 genomes in one cooperative launch
 //   kernel_query.cuh    query passes (a query set against the database): CB windows, rectangular signature join, verification,
@@ -61,6 +63,7 @@
 #include "kernel_hll.cuh"
 #include "kernel_hllbs.cuh"
 #include "kernel_pairlist.cuh"
+#include "kernel_pairs.cuh"
 #include "kernel_sketch.cuh"
 #include "kernel_small.cuh"
 #include "kernel_query.cuh"
@@ -73,9 +76,11 @@
 #include "host_plan.hpp"         // host decisions that are plain arithmetic: build shape, pass plan, criterion constants, overflow rule
 #include "host_context.hpp"      // struct selhip_ctx, device buffers (signature sets, bit planes, counter sets), timers, helpers
 #include "host_pass.hpp"         // pass scheduler: dispatch of every stage, chunk lanes, scratch sizing
+#include "host_pairs.hpp"        // pair-list passes: the chain behind selhip_ctx_run_pairs
 #include "host_query.hpp"        // query passes: Q x D (windows, signature join or stream, verification, stage 2)
 #include "host_topk.hpp"         // top-k of a query pass and of an all-pairs pass: scratch, launches, the count the result accessors expose
 #include "abi_context.inc"       // C ABI: context (create, upload / attach, run, results, timing)
+#include "abi_pairs.inc"         // C ABI: pair-list passes (run_pairs)
 #include "abi_query.inc"         // C ABI: query passes (upload / attach queries, run_queries)
 #include "abi_blocks.inc"        // C ABI: building blocks, synthetic sketches, sketch construction, memory helpers
 #include "abi_compat.inc"        // C ABI: drop-in launch_kernel_smh / launch_kernel_CBsmh

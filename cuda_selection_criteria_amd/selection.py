@@ -141,8 +141,9 @@ class Selector:
 
     def close(self):
         if self._ctx:
-            self._lib.selhip_ctx_destroy(self._ctx)
+            self._lib.selhip_ctx_destroy(self._ctx)         # (waits for the stream: a pending list pass is over)
             self._ctx = C.c_void_p()
+            self._drop_pairs()
 
     def __del__(self):
         try:
@@ -336,7 +337,60 @@ class Selector:
         check(self._lib.selhip_ctx_run_async(self._ctx, mode, algo, np.float32(tau), n_rows, n_bands, rb, re), self._ctx)
 
     def finish(self):
-        check(self._lib.selhip_ctx_finish(self._ctx), self._ctx)
+        try:
+            check(self._lib.selhip_ctx_finish(self._ctx), self._ctx)
+        finally:
+            self._drop_pairs()
+
+    # -- pair-list passes ---------------------------------------------------------------------------
+    @staticmethod
+    def _release_pairs(lib, held):
+        if held is not None and held[0] == "own" and held[1]:
+            lib.selhip_free(C.c_void_p(held[1]))
+
+    def _drop_pairs(self):
+        """the list of the last list pass is no longer read: free the device copy of a numpy list, release a caller's tensor"""
+        held, self._pairs_held = getattr(self, "_pairs_held", None), None
+        self._release_pairs(self._lib, held)
+
+    def _device_pairs(self, pairs):
+        """-> (what to keep until finish, device pointer, entries) of a list given as a numpy int32 (P, 2) array (copied to the device)
+        or a torch int32 device tensor of that shape (kept referenced: a pass that outgrows a list reads it again)"""
+        if isinstance(pairs, np.ndarray) or not hasattr(pairs, "data_ptr"):
+            arr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+            ptr = C.c_void_p()
+            if len(arr):
+                check(self._lib.selhip_malloc(C.byref(ptr), arr.nbytes))
+                check(self._lib.selhip_memcpy_h2d(ptr, arr.ctypes.data, arr.nbytes))
+            return ("own", ptr.value), ptr.value, len(arr)
+        assert pairs.is_cuda and pairs.is_contiguous() and pairs.element_size() == 4 and pairs.dim() == 2 and pairs.shape[1] == 2, \
+            "pairs: a contiguous int32 device tensor of shape (P, 2)"
+        return ("tensor", pairs), (pairs.data_ptr() if pairs.numel() else None), int(pairs.shape[0])
+
+    def run_pairs_async(self, pairs, tau: float, mode: int = MODE_CB_SMH, n_rows: Optional[int] = None, n_bands: Optional[int] = None,
+                        algo: int = ALGO_AUTO):
+        """enqueue one pair-list pass (see run_pairs); finish() waits for it"""
+        if n_rows is None or n_bands is None:
+            n_rows, n_bands = banding(self.m, tau) if self.m else (1, 1)
+        held, ptr, cnt = self._device_pairs(pairs)
+        try:
+            check(self._lib.selhip_ctx_run_pairs_async(self._ctx, ptr, cnt, mode, algo, np.float32(tau), n_rows, n_bands), self._ctx)
+        except Exception:
+            self._release_pairs(self._lib, held)      # (refused: a pass that is still pending keeps its own list)
+            raise
+        self._drop_pairs()
+        self._pairs_held = held
+
+    def run_pairs(self, pairs, tau: float, mode: int = MODE_CB_SMH, n_rows: Optional[int] = None, n_bands: Optional[int] = None,
+                  algo: int = ALGO_AUTO, fetch: bool = True):
+        """one pass of the criterion of set_criterion over a list of pairs: `pairs` is a numpy int32 (P, 2) array or a torch int32
+        device tensor of ranks {x, y} in either order.  One record {min, max, jaccard} for every entry whose pair an all-pairs pass
+        with the same arguments selects (an entry listed twice comes twice), sorted by (i, k); statistics count entries.  An entry
+        with x == y or a rank outside [0, n) raises (SELHIP_E_BADARG, the message names one).  algo: ALGO_AUTO, ALGO_SIG (signature
+        route) or ALGO_STREAM (direct route, any band shape); get_param("pairs_route_used") tells which ran"""
+        self.run_pairs_async(pairs, tau, mode, n_rows, n_bands, algo)
+        self.finish()
+        return self.fetch() if fetch else None
 
     def result_count(self) -> int:
         return int(check(self._lib.selhip_ctx_result_count(self._ctx), self._ctx))
@@ -419,6 +473,49 @@ def select_from_filelist(list_file: str, tau: float, aux_bytes: int, mode: int =
             sel.upload_aux_hll(ds.aux_hll, p_aux)
         sel.set_criterion(crit)
         pairs = sel.run(tau, mode, n_rows, n_bands, algo=algo, top_k=top_k if top_k else None)
+    return format_lines(ds.names, pairs)
+
+
+def read_pair_list(pair_file: str, names: Sequence[str]) -> np.ndarray:
+    """the lines 'name1 name2[ anything]' of a text file as an int32 (P, 2) array of ranks in `names` (rank order), in the file's
+    order and orientation (selhost_read_pair_list: unknown names, equal names and short lines raise with the line number)"""
+    h = host_lib()
+    enc = [n.encode() for n in names]
+    arr = (C.c_char_p * len(enc))(*enc)
+    cnt = C.c_int64()
+    out = np.zeros((0, 2), dtype=np.int32)
+    for _ in range(2):
+        rc = h.selhost_read_pair_list(str(pair_file).encode(), arr if enc else None, len(enc), out.ctypes.data if len(out) else None, len(out), C.byref(cnt))
+        if rc:
+            raise RuntimeError(f"selhost error {rc}: {h.selhost_last_error().decode()}")
+        if cnt.value <= len(out):
+            break
+        out = np.zeros((cnt.value, 2), dtype=np.int32)
+    return out[:cnt.value]
+
+
+def select_pairs_from_filelist(list_file: str, pair_file: str, tau: float, aux_bytes: int, mode: int = MODE_CB_SMH, device: int = 0,
+                               fp_mode: int = FP_FMA, algo: int = ALGO_AUTO, criterion: str = "smh_a") -> str:
+    """select_from_filelist restricted to the pairs listed in pair_file (lines 'path1 path2[ anything]' with paths of list_file, in
+    either order): the text `selection -l list_file -p pair_file -c criterion -a aux_bytes -h tau` prints"""
+    if criterion == "smh_a":
+        m, p_aux, crit = aux_bytes // 8, 0, CRIT_SMH_A
+    elif criterion in ("hll_a", "hll_an"):
+        m, p_aux = 0, (aux_bytes & -aux_bytes).bit_length() - 1
+        crit = CRIT_HLL_A if criterion == "hll_a" else CRIT_HLL_AN
+    elif criterion == "none":
+        m, p_aux, crit = 0, 0, CRIT_NONE
+    else:
+        raise ValueError("Option -c invalid. The accepted criteria are hll_a, hll_an and smh_a.")
+    ds = load_dataset(list_file, m, p_aux, fp_mode)
+    listed = read_pair_list(pair_file, ds.names)
+    n_rows, n_bands = banding(m, tau) if m else (1, 1)
+    with Selector(device, fp_mode) as sel:
+        sel.upload(ds.hll, ds.aux if m else np.zeros((len(ds.names), 1), dtype=np.uint64), ds.cards)
+        if p_aux:
+            sel.upload_aux_hll(ds.aux_hll, p_aux)
+        sel.set_criterion(crit)
+        pairs = sel.run_pairs(listed, tau, mode, n_rows, n_bands, algo=algo)
     return format_lines(ds.names, pairs)
 
 

@@ -212,7 +212,8 @@ int selhip_ctx_set_param(selhip_ctx* ctx, const char* name, int value);
  * "hist_sparse_t" (the sparse threshold the all-pairs stage 2a uses, 0 = every value from the bit planes),
  * "dense_route_used" (SELHIP_CRIT_NONE: the route of the last such pass, 1 = the fused kernel, 0 = the list route; -1 = none yet),
  * "query_topk", "query_topk_lds_cap" (top-k of the query passes, section 2b),
- * "allpairs_topk" (the current k of selhip_ctx_set_allpairs_topk, 0 = off) */
+ * "allpairs_topk" (the current k of selhip_ctx_set_allpairs_topk, 0 = off),
+ * "pairs_route_used" (stage 1 of the last pair-list pass, section 2e) */
 int selhip_ctx_get_param(const selhip_ctx* ctx, const char* name, int* value);
 /* Stage 2 grouping (default on): the pairs that reach the HLL-14 stage are bucketed by query row (counting sort) so
  * that waves running side by side on one XCD share their query row in L2.  0 = off (same kernel, list as produced). */
@@ -440,6 +441,39 @@ int selhip_ooc_select(int device, const uint8_t* h_hll, const uint64_t* h_aux, c
                       int64_t n, int m, int p_hll, int mode, int algo, int fp_mode, float tau_f, int n_rows, int n_bands,
                       int64_t block_genomes, int n_streams,
                       selhip_pair_t* h_out, int64_t cap, int64_t* count_out, int64_t stats_out[4]);
+
+/* ---------------------------------------------------------------------------------------------------
+ * 2e. Pair-list passes: the context's criterion over a CALLER'S list of pairs instead of the whole triangle -- re-scoring an
+ *     earlier result under another criterion or threshold, candidates from another tool, J of given pairs (SELHIP_CRIT_NONE,
+ *     SELHIP_MODE_SMH, tau_f = -1).
+ *     Let E be the pair space an all-pairs pass over all rows evaluates -- (i, k), i < k, e_k != 0, and in SELHIP_MODE_CB_SMH the CB
+ *     predicate -- and S that pass's result.  d_pairs holds n_pairs entries {x, y} in device memory (8-byte aligned), each naming
+ *     the unordered pair of the ranks x and y; 0 <= n_pairs <= 2^31 - 1.  The result is one record {min, max, J} for every entry
+ *     whose pair is in S, with the J of S bit for bit; an entry listed twice is evaluated and reported twice; selhip_ctx_fetch
+ *     sorts by (i, k) as always.  An entry with x == y or a rank outside [0, n) makes the pass fail: selhip_ctx_finish returns
+ *     SELHIP_E_BADARG, the message gives the number of such entries and the index of one, and the context holds no results
+ *     (selhip_ctx_stats: SELHIP_E_STATE).
+ *     Statistics count ENTRIES: stats[0] entries whose pair is in E, stats[1] entries passing the criterion (meaning per criterion as
+ *     for an all-pairs pass), stats[2] records, stats[3] on the signature route the entries in E with an equal 32-bit band signature,
+ *     = stats[1] otherwise (SELHIP_CRIT_NONE: stats[1] = stats[3] = stats[0]).
+ *     d_pairs stays the caller's: alive and unchanged until selhip_ctx_finish returns (a pass that outgrows one of its lists is
+ *     repeated and reads it again), visible to the context's stream at the call.  n_pairs == 0 is a finished pass without records.
+ *     Arguments are checked as by selhip_ctx_run_async.  algo picks stage 1 of the criteria with an smh_a stage: SELHIP_ALGO_SIG the
+ *     signature route (band signatures built like an all-pairs pass's, then one check per entry; SELHIP_E_BADARG for a band shape
+ *     without signatures), SELHIP_ALGO_STREAM the direct route (the band comparison on the sketches, any band shape),
+ *     SELHIP_ALGO_AUTO the signature route where the shape has one and the signatures are cached ("sig_cache") or n_pairs >= n / 2;
+ *     SELHIP_ALGO_HASHJOIN and _INDEX are joins, not checks of a given pair: SELHIP_E_BADARG.  SELHIP_E_STATE with the all-pairs
+ *     top-k on (selhip_ctx_set_allpairs_topk), a row interleave of more than one part, or a candidate begin above 0: shard a list
+ *     by cutting the list.
+ *     To everything that follows, a list pass is an all-pairs pass: fetch, result_device, copy_results*, last_attempts, kernel_ms
+ *     (its stage-1 kernel is "stage1"); get_param "chunks" = 1, "small_pass_used" = 0, and "pairs_route_used" = 1 signature route,
+ *     0 direct route, 2 criterion without an smh_a stage, -1 no list pass yet.
+ * --------------------------------------------------------------------------------------------------- */
+int selhip_ctx_run_pairs(selhip_ctx* ctx, const selhip_int2_t* d_pairs, int64_t n_pairs,
+                         int mode, int algo, float tau_f, int n_rows, int n_bands);
+/* Asynchronous variant: selhip_ctx_finish() waits, validates and reports invalid entries. */
+int selhip_ctx_run_pairs_async(selhip_ctx* ctx, const selhip_int2_t* d_pairs, int64_t n_pairs,
+                               int mode, int algo, float tau_f, int n_rows, int n_bands);
 
 
 /* ---------------------------------------------------------------------------------------------------

@@ -78,6 +78,15 @@ const char*     selhost_dataset_name(const selhost_dataset* ds, int64_t rank);
 /* "fn1 fn2 0.946107\n" (std::to_string(double) == "%f"); returns bytes written (excluding NUL) or <0 */
 int selhost_format_line(const char* fn1, const char* fn2, double jaccard, char* buf, size_t cap);
 
+/* ---- pair lists as text (the input of a pair-list pass, selhip_ctx_run_pairs) ---------------------
+ * Reads lines "name1 name2[ anything]" -- the lines the selection prints, so one run's output is the next run's pair file.
+ * names[0 .. n_names) are the genome names in rank order (selhost_dataset_name); entry e of the file becomes the ranks
+ * out_xy[2e], out_xy[2e + 1] of its two names, in the file's order and orientation.  Empty lines are skipped.  Only the first `cap`
+ * entries are stored; *count receives the number of entries in the file (call again with a larger buffer).
+ * SELHOST_E_FORMAT with the line number (from 1) in the message: a name that is not in names[], a line with fewer than two
+ * fields, two equal names. */
+int selhost_read_pair_list(const char* path, const char* const* names, int64_t n_names, int32_t* out_xy, int64_t cap, int64_t* count);
+
 /* ---- on-disk result format (the reference only prints text, selection.cpp:297-300) ---------
  * A self-contained binary file: the selected pairs as 16-byte records plus the table of genome names their ranks refer to.
  *   header (40 B, little endian): char magic[4] = "SELR"; u32 version = 1; u64 n_pairs; u64 n_names; u64 names_bytes;
