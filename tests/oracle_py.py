@@ -33,6 +33,14 @@ class Oracle:
         L.orc_std_sort_perm.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
         L.orc_std_sort_perm.restype = None
         L.orc_cb.argtypes = [C.c_double, C.c_double, C.c_double]
+        L.orc_sigma.restype = C.c_float
+        L.orc_sigma.argtypes = [C.c_int]
+        L.orc_kota_mas.restype = C.c_double
+        L.orc_kota_mas.argtypes = [C.c_size_t, C.c_size_t, C.c_double, C.c_int, C.c_float]
+        L.orc_cota_n.restype = C.c_double
+        L.orc_cota_n.argtypes = [C.c_size_t, C.c_size_t, C.c_double, C.c_int, C.c_float, C.c_int]
+        L.orc_hll_a_from_union.argtypes = [C.c_double, C.c_size_t, C.c_size_t, C.c_double, C.c_int, C.c_float]
+        L.orc_hll_an_from_union.argtypes = [C.c_double, C.c_size_t, C.c_size_t, C.c_double, C.c_int, C.c_float, C.c_int]
 
     def set_fma(self, on):
         self.lib.orc_set_fma(1 if on else 0)
@@ -59,6 +67,31 @@ class Oracle:
     def estimate(self, counts, p, fma=1):
         counts = np.ascontiguousarray(counts, dtype=np.uint32)
         return self.lib.orc_ertl_ml_estimate_ex(counts.ctypes.data, p, 64 - p, 1e-2, fma)
+
+    def cb(self, tau, e_lo, e_hi):
+        """orc_cb on two truncated cardinalities (each exactly a double, as (size_t)card of a double card is) and a float tau"""
+        return bool(self.lib.orc_cb(float(np.float32(tau)), float(e_lo), float(e_hi)))
+
+    # the auxiliary-HLL criteria on a given union estimate (selection.cpp:76-77: Z = 1.96f, order_n = 1), in the flavour of set_fma
+    def kota_mas(self, e_lo, e_hi, union_est, p_aux):
+        """K+ of hll_a as orc_hll_a_from_union forms it: t_hat = (size_t)union_est"""
+        return self.lib.orc_kota_mas(int(e_lo), int(e_hi), float(int(union_est)), p_aux, 1.96)
+
+    def hll_a(self, tau, e_lo, e_hi, union_est, p_aux):
+        return bool(self.lib.orc_hll_a_from_union(float(np.float32(tau)), int(e_lo), int(e_hi), union_est, p_aux, 1.96))
+
+    def cota_n(self, e_lo, e_hi, union_est, p_aux):
+        return self.lib.orc_cota_n(int(e_lo), int(e_hi), union_est, p_aux, 1.96, 1)
+
+    def hll_an(self, tau, e_lo, e_hi, union_est, p_aux):
+        return bool(self.lib.orc_hll_an_from_union(float(np.float32(tau)), int(e_lo), int(e_hi), union_est, p_aux, 1.96, 1))
+
+    def jaccard(self, row_a, row_b, card_a, card_b, p=14):
+        """selection.cpp:286-287 on one pair, through orc_select: J of the pair whatever its size (tau = -inf), None if J is a NaN"""
+        hll = np.stack([row_a, row_b])
+        pairs, _ = self.select(hll, np.zeros((2, 1), dtype=np.uint64), np.array([card_a, card_b], dtype=np.float64), -np.inf, 1, 1,
+                               use_cb=False, p=p, threads=1)
+        return float(pairs["jacc"][0]) if len(pairs) else None
 
     def smh_a(self, v1, v2, n_rows, n_bands):
         v1 = np.ascontiguousarray(v1, dtype=np.uint64)
