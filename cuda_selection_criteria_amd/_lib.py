@@ -43,6 +43,8 @@ MODE_SMH, MODE_CB_SMH = 0, 1
 ALGO_AUTO, ALGO_STREAM, ALGO_SIG, ALGO_HASHJOIN, ALGO_INDEX = 0, 1, 2, 3, 4    # ALGO_INDEX: query passes only
 FP_STRICT, FP_FMA = 0, 1
 CRIT_SMH_A, CRIT_HLL_A, CRIT_HLL_AN, CRIT_HLL_A_SMH_A, CRIT_NONE = 0, 1, 2, 3, 4
+MEASURE_JACCARD, MEASURE_UNION = 0, 1  # SELHIP_MEASURE_*: what a dense matrix stores (Selector.matrix)
+F64, F32 = 0, 1                        # SELHIP_F64 / SELHIP_F32: its element type
 BANDING_CPU, BANDING_CUDA = 0, 1
 TOPK_MAX = 1024                        # SELHIP_TOPK_MAX: largest k of Selector.set_query_topk and Selector.set_allpairs_topk
 
@@ -100,6 +102,8 @@ HIP_SYMBOLS = {
     "selhip_ctx_set_allpairs_topk": (_i, [_vp, _i]),
     "selhip_ctx_upload_queries_aux_hll": (_i, [_vp, _vp, _i]),
     "selhip_ctx_attach_queries_aux_hll": (_i, [_vp, _vp, _i]),
+    "selhip_ctx_matrix": (_i, [_vp, _i, _i, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp]),
+    "selhip_ctx_query_matrix": (_i, [_vp, _i, _i, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp]),
     "selhip_smh_a_pairs": (_i, [_vp, _i, _i, _i, _vp, _i64, _vp, _vp]),
     "selhip_hll_union_hist": (_i, [_vp, _i, _vp, _i64, _vp, _vp]),
     "selhip_hll_bitslice": (_i, [_vp, _i64, _vp, _vp, _vp, _vp]),
@@ -139,6 +143,8 @@ HOST_SYMBOLS = {
     "selhost_dataset_aux_hll": (_vp, [_vp]),
     "selhost_dataset_cards": (_vp, [_vp]),
     "selhost_dataset_name": (_cp, [_vp, _i64]),
+    "selhost_dataset_order": (_i64, [_vp, _i64]),
+    "selhost_write_matrix": (_i, [_cp, _vp, _i64, _i64, _i64, _vp, _vp]),
     "selhost_format_line": (_i, [_cp, _cp, _d, _vp, _sz]),
     "selhost_read_pair_list": (_i, [_cp, _vp, _i64, _vp, _i64, C.POINTER(_i64)]),
     "selhost_write_results": (_i, [C.c_char_p, _vp, _i64, _vp, _i64, C.c_float]),

@@ -52,7 +52,7 @@ void selhip_ctx_destroy(selhip_ctx* c) {
     c->aux_il.release(); c->cand.release(); c->sig.release(); c->fin.release(); c->own_aux_hll.release();
     c->hj_keys_in.release(); c->hj_keys_out.release(); c->hj_vals_in.release(); c->hj_vals_out.release(); c->hj_tmp.release();
     c->csr_cnt.release(); c->csr_start.release(); c->grouped.release(); c->scan_tmp.release();
-    c->planes.release(); c->small_bar.release();
+    c->planes.release(); c->small_bar.release(); c->mat_row_pos.release(); c->mat_col_pos.release();
     c->hll_sparse.release(); c->hll_sparse_dev_t.release();
     release_queries(c);
     release_topk(c);
@@ -200,6 +200,7 @@ int selhip_ctx_set_param(selhip_ctx* c, const char* name, int value) {
         return SELHIP_OK;
     }
     if (!std::strcmp(name, "dense_fused")) { c->dense_fused = value != 0; return SELHIP_OK; }
+    if (!std::strcmp(name, "matrix_mirror")) { c->matrix_mirror = value != 0; return SELHIP_OK; }   // measurement switch: 0 = no mirrored stores
     if (!std::strcmp(name, "hist_dense_degree")) {
         if (value < -1 || value > (1 << 20)) { set_err(&c->err, "hist_dense_degree must be in [-1, 2^20] (-1 = never)"); return SELHIP_E_BADARG; }
         c->hist_dense_degree = value;
@@ -229,6 +230,7 @@ int selhip_ctx_get_param(const selhip_ctx* c, const char* name, int* value) {
     if (!std::strcmp(name, "join_form_used"))   { *value = c->join_form_used; return SELHIP_OK; }      // kernel FORM of the last LDS-tile join (3 = bit-sliced)
     if (!std::strcmp(name, "chunks"))           { *value = c->n_chunks_last; return SELHIP_OK; }
     if (!std::strcmp(name, "dense_route_used")) { *value = c->dense_route_used; return SELHIP_OK; }         // SELHIP_CRIT_NONE: 1 fused kernel, 0 list route, -1 none yet
+    if (!std::strcmp(name, "matrix_mirror"))    { *value = c->matrix_mirror; return SELHIP_OK; }
     if (!std::strcmp(name, "small_pass_used"))  { *value = c->small_used ? 1 : 0; return SELHIP_OK; }
     if (!std::strcmp(name, "pairs_route_used")) { *value = c->pairs_route_used; return SELHIP_OK; }         // list passes: 1 signature, 0 direct, 2 no smh_a stage, -1 none yet
     if (!std::strcmp(name, "query_topk"))       { *value = c->query_topk; return SELHIP_OK; }              // K of the query passes' top-k, 0 = off
@@ -603,17 +605,19 @@ int selhip_ctx_timing(selhip_ctx* c, int enable) {
     drain_timers(c);
     for (int t = 0; t < T_COUNT; ++t) { c->timers[t].total_ms = 0; c->timers[t].launches = 0; c->timers[t].span_ms = 0; }
     c->timing = enable == 2 ? 2 : (enable != 0 ? 1 : 0);
-    c->timed_passes = 0;
+    c->timed_passes = 0; c->timed_matrix_calls = 0;
     return SELHIP_OK;
 }
 
 double selhip_ctx_kernel_ms(const selhip_ctx* c, const char* name) {
     if (!c || !name) return -1.0;
     if (!c->pending) drain_timers(const_cast<selhip_ctx*>(c));
-    const long passes = c->timed_passes;
     for (int t = 0; t < T_COUNT; ++t)
-        if (!std::strcmp(name, kTimerNames[t]))
+        if (!std::strcmp(name, kTimerNames[t])) {
+            const long passes = t == T_MATRIX ? c->timed_matrix_calls : c->timed_passes;
             return (c->timers[t].launches && passes) ? c->timers[t].total_ms / (double)passes : -1.0;
+        }
+    const long passes = c->timed_passes;
     if (!std::strcmp(name, "join_span"))
         return (c->timers[T_JOIN].launches && passes) ? c->timers[T_JOIN].span_ms / (double)passes : -1.0;
     return -1.0;
@@ -622,10 +626,11 @@ double selhip_ctx_kernel_ms(const selhip_ctx* c, const char* name) {
 double selhip_ctx_kernel_launches(const selhip_ctx* c, const char* name) {
     if (!c || !name) return -1.0;
     if (!c->pending) drain_timers(const_cast<selhip_ctx*>(c));
-    const long passes = c->timed_passes;
     for (int t = 0; t < T_COUNT; ++t)
-        if (!std::strcmp(name, kTimerNames[t]))
+        if (!std::strcmp(name, kTimerNames[t])) {
+            const long passes = t == T_MATRIX ? c->timed_matrix_calls : c->timed_passes;
             return passes ? (double)c->timers[t].launches / (double)passes : 0.0;
+        }
     return -1.0;
 }
 

@@ -50,6 +50,7 @@ struct selhost_dataset {
     std::vector<uint64_t> aux;
     std::vector<uint8_t> aux_hll;
     std::vector<double> cards;
+    std::vector<int32_t> order;           // rank -> line of the file list (the sort permutation)
 };
 
 extern "C" {
@@ -266,11 +267,12 @@ int selhost_dataset_load(selhost_dataset** out, const char* list_file, unsigned 
     selhost_sort_by_card(cards.data(), n, perm.data());
     auto ds = std::make_unique<selhost_dataset>();
     ds->n = n; ds->m = m; ds->p_aux = p_aux;
-    ds->names.resize((size_t)n);
+    ds->names.resize((size_t)n); ds->order.resize((size_t)n);
     ds->hll.resize((size_t)n * hb); ds->aux.resize((size_t)n * m); ds->aux_hll.resize((size_t)n * ab); ds->cards.resize((size_t)n);
     for (int64_t r = 0; r < n; ++r) {                                  // selection_cuda.cpp:138-143
         const size_t s = (size_t)perm[(size_t)r];
         ds->names[(size_t)r] = files[s];
+        ds->order[(size_t)r] = (int32_t)s;
         std::memcpy(ds->hll.data() + (size_t)r * hb, hll.data() + s * hb, hb);
         if (m) std::memcpy(ds->aux.data() + (size_t)r * m, aux.data() + s * m, (size_t)m * 8);
         if (ab) std::memcpy(ds->aux_hll.data() + (size_t)r * ab, auxh.data() + s * ab, ab);
@@ -291,10 +293,36 @@ const char* selhost_dataset_name(const selhost_dataset* ds, int64_t rank) {
     return ds->names[(size_t)rank].c_str();
 }
 
+int64_t selhost_dataset_order(const selhost_dataset* ds, int64_t rank) {
+    if (!ds || rank < 0 || rank >= ds->n) return -1;
+    return ds->order[(size_t)rank];
+}
+
 int selhost_format_line(const char* fn1, const char* fn2, double jaccard, char* buf, size_t cap) {
     if (!fn1 || !fn2 || !buf) return SELHOST_E_BADARG;
     int w = snprintf(buf, cap, "%s %s %f\n", fn1, fn2, jaccard);       // selection.cpp:288 std::to_string(double)
     return (w < 0 || (size_t)w >= cap) ? SELHOST_E_BADARG : w;
+}
+
+// ---- dense matrices as text ----------------------------------------------------------------------------------
+int selhost_write_matrix(const char* path, const double* values, int64_t n_rows, int64_t n_cols, int64_t ld,
+                         const char* const* row_names, const char* const* col_names) {
+    if (!path || n_rows < 0 || n_cols < 0 || ld < n_cols || (n_rows && n_cols && !values) || (n_rows && !row_names) || (n_cols && !col_names))
+        return fail(SELHOST_E_BADARG, "bad argument");
+    for (int64_t r = 0; r < n_rows; ++r) if (!row_names[r]) return fail(SELHOST_E_BADARG, "null row name");
+    for (int64_t k = 0; k < n_cols; ++k) if (!col_names[k]) return fail(SELHOST_E_BADARG, "null column name");
+    FILE* fp = std::fopen(path, "w");
+    if (!fp) return fail(SELHOST_E_IO, "cannot open %s for writing", path);
+    bool ok = true;
+    for (int64_t k = 0; k < n_cols && ok; ++k) ok = std::fprintf(fp, "\t%s", col_names[k]) >= 0;
+    ok = ok && std::fputc('\n', fp) != EOF;
+    for (int64_t r = 0; r < n_rows && ok; ++r) {
+        ok = std::fputs(row_names[r], fp) != EOF;
+        for (int64_t k = 0; k < n_cols && ok; ++k) ok = std::fprintf(fp, "\t%.17g", values[r * ld + k]) >= 0;
+        ok = ok && std::fputc('\n', fp) != EOF;
+    }
+    ok = (std::fclose(fp) == 0) && ok;
+    return ok ? SELHOST_OK : fail(SELHOST_E_IO, "short write to %s", path);
 }
 
 // ---- on-disk result format ---------------------------------------------------------------------------------

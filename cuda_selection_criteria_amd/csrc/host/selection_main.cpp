@@ -38,6 +38,12 @@
 //               either order -- the lines this program prints, so one run's output is the next run's pair file
 //               (selhip_ctx_run_pairs: a pair listed twice is printed twice).  With every -c, -n, -F, -o and -A auto|sig|stream; one
 //               device -- not combinable with -q, -k, -K, -B or -g above 1
+//   -M <file>   no selection pass: the dense similarity matrix of the -l list (with -q: rows = the -q list, columns = the -l list) as a
+//               tab-separated table in FILE-LIST order (selhip_ctx_matrix / selhip_ctx_query_matrix, selhost_write_matrix): first line a
+//               tab and the column names, then per row its name and the values in %.17g.  Jaccard estimates (1 on the diagonal, nan for
+//               two empty sketches); with -U the union sizes.  Reads only the .hll files (-a and -b are accepted and unused); with -F and
+//               -t -- not combinable with -p, -k, -K, -g, -B, -o, -r, nor with the options of a selection pass -h, -c, -n, -A
+//   -U          with -M: the union estimate U of every pair instead of J
 //   -x          usage
 #include <unistd.h>
 
@@ -162,6 +168,55 @@ static int run_neighbours(const std::string& list_file, int crit, float threshol
     return r ? 4 : 0;
 }
 
+// -M: the dense matrix of one list, or of the query list against the database list, written as text in file-list order
+static int run_matrix(const std::string& list_file, const std::string& query_file, const std::string& out_file, bool union_measure,
+                      int fp_mode, int threads) {
+    selhost_dataset* db = nullptr;
+    selhost_dataset* qs = nullptr;
+    if (selhost_dataset_load(&db, list_file.c_str(), 0, 0, fp_mode, threads)) { std::cerr << "selection: -M: " << selhost_last_error() << "\n"; return 1; }
+    if (!query_file.empty() && selhost_dataset_load(&qs, query_file.c_str(), 0, 0, fp_mode, threads)) {
+        std::cerr << "selection: -M: cannot read query list '" << query_file << "': " << selhost_last_error() << "\n";
+        selhost_dataset_free(db);
+        return 1;
+    }
+    const selhost_dataset* rows = qs ? qs : db;
+    const int64_t n_d = selhost_dataset_size(db), n_r = selhost_dataset_size(rows);
+    // the positions: rank -> line of the file list; the names in file order
+    std::vector<int32_t> col_pos((size_t)n_d), row_pos((size_t)n_r);
+    std::vector<const char*> col_names((size_t)n_d), row_names((size_t)n_r);
+    for (int64_t r = 0; r < n_d; ++r) { col_pos[(size_t)r] = (int32_t)selhost_dataset_order(db, r); col_names[(size_t)col_pos[(size_t)r]] = selhost_dataset_name(db, r); }
+    for (int64_t r = 0; r < n_r; ++r) { row_pos[(size_t)r] = (int32_t)selhost_dataset_order(rows, r); row_names[(size_t)row_pos[(size_t)r]] = selhost_dataset_name(rows, r); }
+    std::vector<double> values((size_t)n_r * (size_t)n_d);
+    std::vector<uint64_t> no_smh((size_t)std::max<int64_t>(1, std::max(n_d, n_r)), 0);
+    selhip_ctx* ctx = nullptr;
+    int r = selhip_device_count() > 0 ? selhip_ctx_create(&ctx, 0) : SELHIP_E_NODEVICE;
+    if (r) {
+        std::cerr << "selection: no MI355X (gfx950) device available: " << selhip_last_error(nullptr) << "\n";
+        selhost_dataset_free(db); selhost_dataset_free(qs);
+        return 3;
+    }
+    void* d_out = nullptr;
+    selhip_ctx_set_fp_mode(ctx, fp_mode);
+    r = selhip_ctx_upload(ctx, selhost_dataset_hll(db), no_smh.data(), selhost_dataset_cards(db), n_d, 1, 14);
+    if (!r && qs) r = selhip_ctx_upload_queries(ctx, selhost_dataset_hll(qs), no_smh.data(), selhost_dataset_cards(qs), n_r);
+    if (!r && !values.empty()) r = selhip_malloc(&d_out, values.size() * sizeof(double));
+    const int measure = union_measure ? SELHIP_MEASURE_UNION : SELHIP_MEASURE_JACCARD;
+    if (!r) r = qs ? selhip_ctx_query_matrix(ctx, measure, SELHIP_F64, 0, n_r, d_out, n_r, n_d, n_d, row_pos.data(), col_pos.data())
+                   : selhip_ctx_matrix(ctx, measure, SELHIP_F64, 0, n_r, d_out, n_r, n_d, n_d, row_pos.data(), col_pos.data());
+    if (!r && !values.empty()) r = selhip_memcpy_d2h(values.data(), d_out, values.size() * sizeof(double));
+    if (r) std::cerr << "selection: " << selhip_last_error(ctx) << "\n";
+    selhip_ctx_destroy(ctx);
+    if (d_out) selhip_free(d_out);
+    int hr = 0;
+    if (!r) {
+        hr = selhost_write_matrix(out_file.c_str(), values.data(), n_r, n_d, n_d, row_names.data(), col_names.data());
+        if (hr) std::cerr << "selection: " << selhost_last_error() << "\n";
+    }
+    selhost_dataset_free(db);
+    selhost_dataset_free(qs);
+    return r ? 4 : hr ? 5 : 0;
+}
+
 int main(int argc, char* argv[]) {
     std::string list_file = "";
     float threshold = 0.9f;              // selection_cuda.cpp:62
@@ -169,18 +224,22 @@ int main(int argc, char* argv[]) {
     std::string criterion = "smh_a";
     int threads = 8, n_gpus = 1, mode = SELHIP_MODE_CB_SMH, algo = SELHIP_ALGO_AUTO, fp_mode = SELHIP_FP_FMA;
     long long ooc_block = 0;
-    std::string out_file = "", dump_file = "", query_file = "", pair_file = "";
-    bool gpus_given = false, topk_given = false, nbr_given = false;
+    std::string out_file = "", dump_file = "", query_file = "", pair_file = "", matrix_file = "";
+    bool gpus_given = false, topk_given = false, nbr_given = false, matrix_given = false, union_measure = false;
+    const char* selection_opt = nullptr;         // the first of -h, -c, -n, -A seen: options of a selection pass, which -M does not run
     long long top_k = 0, nbr_k = 0;
     int c;
-    while ((c = getopt(argc, argv, "xl:b:a:h:c:t:g:nA:F:B:o:r:q:k:K:p:")) != -1) {
+    while ((c = getopt(argc, argv, "xl:b:a:h:c:t:g:nA:F:B:o:r:q:k:K:p:M:U")) != -1) {
         switch (c) {
             case 'x': std::cout << "Usage: -l -h -a -b [-c smh_a|hll_a|hll_an|none] [-t threads] [-g gpus] [-n] [-A auto|stream|sig] [-F 0|1] [-B block] [-o file] | -r file\n"
                                    "       -l db_list -q query_list -h -a [-c smh_a|hll_a|hll_an|none] [-n] [-A auto|stream|sig|index] [-F 0|1] [-k best_per_query]   (query-vs-database selection)\n"
                                    "       -l -h -a [-c smh_a|hll_a|hll_an|none] [-n] [-A auto|stream|sig|hashjoin] [-F 0|1] -K best_per_genome   (every genome's best partners, both members of a pair)\n"
-                                   "       -l list -p pair_file -h -a [-c smh_a|hll_a|hll_an|none] [-n] [-A auto|stream|sig] [-F 0|1] [-o file]   (only the listed pairs; lines 'path1 path2 ...')\n"; return 0;
+                                   "       -l list -p pair_file -h -a [-c smh_a|hll_a|hll_an|none] [-n] [-A auto|stream|sig] [-F 0|1] [-o file]   (only the listed pairs; lines 'path1 path2 ...')\n"
+                                   "       -l list [-q query_list] [-F 0|1] -M out.tsv [-U]   (no selection: the dense Jaccard -- -U: union size -- matrix, file-list order)\n"; return 0;
             case 'q': query_file = optarg; break;
             case 'p': pair_file = optarg; break;
+            case 'M': matrix_file = optarg; matrix_given = true; break;
+            case 'U': union_measure = true; break;
             case 'k': top_k = std::strtoll(optarg, nullptr, 10); topk_given = true; break;
             case 'K': nbr_k = std::strtoll(optarg, nullptr, 10); nbr_given = true; break;
             case 'B': ooc_block = std::stoll(optarg); break;
@@ -189,16 +248,29 @@ int main(int argc, char* argv[]) {
             case 'l': list_file = optarg; break;
             case 'b': break;
             case 'a': aux_bytes = std::stoi(optarg); break;
-            case 'h': threshold = std::stof(optarg); break;
-            case 'c': criterion = optarg; break;
+            case 'h': threshold = std::stof(optarg); if (!selection_opt) selection_opt = "-h"; break;
+            case 'c': criterion = optarg; if (!selection_opt) selection_opt = "-c"; break;
             case 't': threads = std::stoi(optarg); break;
             case 'g': n_gpus = std::stoi(optarg); gpus_given = true; break;
-            case 'n': mode = SELHIP_MODE_SMH; break;
-            case 'A': algo = !strcmp(optarg, "stream") ? SELHIP_ALGO_STREAM : !strcmp(optarg, "sig") ? SELHIP_ALGO_SIG : !strcmp(optarg, "hashjoin") ? SELHIP_ALGO_HASHJOIN : !strcmp(optarg, "index") ? SELHIP_ALGO_INDEX : SELHIP_ALGO_AUTO; break;
+            case 'n': mode = SELHIP_MODE_SMH; if (!selection_opt) selection_opt = "-n"; break;
+            case 'A': if (!selection_opt) selection_opt = "-A"; algo = !strcmp(optarg, "stream") ? SELHIP_ALGO_STREAM : !strcmp(optarg, "sig") ? SELHIP_ALGO_SIG : !strcmp(optarg, "hashjoin") ? SELHIP_ALGO_HASHJOIN : !strcmp(optarg, "index") ? SELHIP_ALGO_INDEX : SELHIP_ALGO_AUTO; break;
             case 'F': fp_mode = std::stoi(optarg) ? SELHIP_FP_FMA : SELHIP_FP_STRICT; break;
             default: break;
         }
     }
+    if (matrix_given) {
+        // checked before any file is read or device opened
+        const char* clash = !pair_file.empty() ? "-p" : topk_given ? "-k" : nbr_given ? "-K" : gpus_given ? "-g" : ooc_block != 0 ? "-B"
+                          : !out_file.empty() ? "-o" : !dump_file.empty() ? "-r" : selection_opt;
+        if (clash) {
+            std::cerr << "selection: -M (the dense similarity matrix) cannot be combined with " << clash
+                      << "; it runs no selection pass (no criterion, threshold, CB bound or algorithm), on one device, and writes a table\n";
+            return 2;
+        }
+        if (list_file.empty()) { std::cerr << "selection: -M needs the list of genomes (-l)\n"; return 2; }
+        return run_matrix(list_file, query_file, matrix_file, union_measure, fp_mode, threads);
+    }
+    if (union_measure) { std::cerr << "selection: -U (union sizes) is an option of -M (the dense similarity matrix)\n"; return 2; }
     if (!pair_file.empty()) {
         // checked before any file is read or device opened
         const char* clash = !query_file.empty() ? "-q" : topk_given ? "-k" : nbr_given ? "-K" : ooc_block != 0 ? "-B" : gpus_given && n_gpus > 1 ? "-g" : nullptr;

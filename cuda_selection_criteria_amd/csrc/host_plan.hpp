@@ -1,6 +1,6 @@
 // host_plan.hpp -- the decisions of the host side that are plain arithmetic, each written once: padding and grids, the shape of a
-// signature build, the bit-plane count of a register range, which stage 1 a pass runs, the constants of the auxiliary criterion and
-// the growth rule after an overflow.  Nothing here touches the device or the context.
+// signature build, the bit-plane count of a register range, which stage 1 a pass runs, the constants of the auxiliary criterion,
+// the growth rule after an overflow and the units, slab and mirror rules of a dense matrix.  Nothing here touches the device or the context.
 // Part of the kernel translation unit selection_kernels.hip (included there, before host_context.hpp); not a stand-alone header.
 #pragma once
 
@@ -119,6 +119,23 @@ PairsDirectShape pairs_direct_shape(u64 n_pairs) {
     const int gpw = (int)std::min<u64>(16, std::max<u64>(1, n_pairs / (4 * slots)));
     return {gpw, grid_for(n_pairs, 32u * (unsigned)gpw, 1024)};
 }
+
+// ---- dense matrices (kernel_matrix.cuh) -----------------------------------------------------------
+// constexpr: the kernel reads the same rules (it is included behind this header).
+// The units of a matrix of n_rows x n_cols cells: row tiles of four rows (one per wave) x spans of 64 columns, the spans dealt to
+// the 8 XCD slots round robin as in dense_select_kernel -- unit u: slot u % 8, j = u / 8 -> row tile j % n_tiles of span 8 (j / n_tiles) + slot
+constexpr int kMatrixSpan = kWave;
+struct MatrixUnits { long long n_tiles, n_spans, n_units; };
+constexpr MatrixUnits matrix_units(long long n_rows, long long n_cols) {
+    const long long n_tiles = (n_rows + kWavesPerBlock - 1) / kWavesPerBlock, n_spans = (n_cols + kMatrixSpan - 1) / kMatrixSpan;
+    return {n_tiles, n_spans, 8 * n_tiles * ((n_spans + 7) / 8)};
+}
+// a self matrix computes every pair once: row i of the slab [r0, r1) computes the columns [0, r0) u [i, n) ...
+constexpr bool matrix_computes(int r0, int i, long long k) { return k < r0 || k >= i; }
+// ... so it leaves out a span [k0, k0 + 64) that lies wholly under the diagonal and inside the slab ...
+constexpr bool matrix_skips_span(int r0, int i, long long k0) { return k0 >= r0 && k0 + kMatrixSpan <= i; }
+// ... and its cell (i, k) is also the cell (k, i) of a row of the same slab: stored twice
+constexpr bool matrix_mirrors(int i, long long k, int r1) { return k > i && k < r1; }
 
 // bit range of the band keys (band << 32 | signature) that the sort join and the query index sort
 unsigned band_key_end_bit(int n_bands) { return 32u + (unsigned)ilog2(n_bands) + 1u; }

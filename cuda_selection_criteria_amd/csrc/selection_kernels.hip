@@ -26,6 +26,8 @@
 //                       binary search per (query, band) in place of the rectangular join
 //   kernel_dense.cuh    dense_select_kernel: criterion "none" -- every pair of the (CB-pruned) pair space to the Jaccard test, union
 //                       histograms into an LDS tile and the estimator in one launch
+//   kernel_matrix.cuh   matrix_kernel: the union size or the Jaccard estimate of every pair as a dense array (the middle of
+//                       dense_select_kernel over a rectangle, typed and mirrored stores; selhip_ctx_matrix / _query_matrix)
 //   kernel_topk.cuh     top-k of a query pass: records grouped by query (count, scan, scatter), radix select of each query's K best,
 //                       bitonic sort of the winners
 //   kernel_nbr.cuh      top-k of an all-pairs pass: every record counted and scattered for both of its genomes, then the same select
@@ -74,6 +76,7 @@
 #include "kernel_nbr.cuh"
 
 #include "host_plan.hpp"         // host decisions that are plain arithmetic: build shape, pass plan, criterion constants, overflow rule
+#include "kernel_matrix.cuh"     // (behind host_plan.hpp: the kernel reads the unit, slab and mirror rules written there)
 #include "host_context.hpp"      // struct selhip_ctx, device buffers (signature sets, bit planes, counter sets), timers, helpers
 #include "host_pass.hpp"         // pass scheduler: dispatch of every stage, chunk lanes, scratch sizing
 #include "host_pairs.hpp"        // pair-list passes: the chain behind selhip_ctx_run_pairs
@@ -82,5 +85,6 @@
 #include "abi_context.inc"       // C ABI: context (create, upload / attach, run, results, timing)
 #include "abi_pairs.inc"         // C ABI: pair-list passes (run_pairs)
 #include "abi_query.inc"         // C ABI: query passes (upload / attach queries, run_queries)
+#include "abi_matrix.inc"        // C ABI: dense matrices (matrix, query_matrix)
 #include "abi_blocks.inc"        // C ABI: building blocks, synthetic sketches, sketch construction, memory helpers
 #include "abi_compat.inc"        // C ABI: drop-in launch_kernel_smh / launch_kernel_CBsmh

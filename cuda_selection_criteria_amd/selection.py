@@ -11,8 +11,8 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import (ALGO_AUTO, BANDING_CPU, CRIT_HLL_A, CRIT_HLL_AN, CRIT_HLL_A_SMH_A, CRIT_NONE, CRIT_SMH_A, FP_FMA, MODE_CB_SMH, Pair,
-                   check, hip_lib, host_lib)
+from ._lib import (ALGO_AUTO, BANDING_CPU, CRIT_HLL_A, CRIT_HLL_AN, CRIT_HLL_A_SMH_A, CRIT_NONE, CRIT_SMH_A, F32, F64, FP_FMA,
+                   MEASURE_JACCARD, MEASURE_UNION, MODE_CB_SMH, Pair, check, hip_lib, host_lib)
 
 # layout of selhip_pair_t {int32 i, k; double jaccard}
 PAIR_DTYPE = np.dtype([("i", "<i4"), ("k", "<i4"), ("jaccard", "<f8")], align=True)
@@ -43,6 +43,7 @@ class Dataset:
     aux: np.ndarray        # [n, m] u64
     aux_hll: np.ndarray    # [n, 1 << p_aux] u8 (empty when p_aux == 0)
     cards: np.ndarray      # [n] f64 ascending
+    order: Optional[np.ndarray] = None   # [n] i32: the line of the file list each rank came from (the sort permutation)
 
 
 def load_dataset(list_file: str, m: int, p_aux: int = 0, fp_mode: int = FP_FMA, threads: int = 8) -> Dataset:
@@ -65,9 +66,10 @@ def load_dataset(list_file: str, m: int, p_aux: int = 0, fp_mode: int = FP_FMA, 
         aux_hll = arr(h.selhost_dataset_aux_hll(ds), (n, (1 << p_aux) if p_aux else 0), np.uint8)
         cards = arr(h.selhost_dataset_cards(ds), (n,), np.float64)
         names = [h.selhost_dataset_name(ds, r).decode() for r in range(n)]
+        order = np.array([h.selhost_dataset_order(ds, r) for r in range(n)], dtype=np.int32)
     finally:
         h.selhost_dataset_free(ds)
-    return Dataset(names, hll, aux, aux_hll, cards)
+    return Dataset(names, hll, aux, aux_hll, cards, order)
 
 
 def format_lines(names: Sequence[str], pairs: np.ndarray) -> str:
@@ -134,6 +136,7 @@ class Selector:
             check(self._lib.selhip_ctx_set_param(self._ctx, name.encode(), int(value)), self._ctx)
         if stream is not None:
             check(self._lib.selhip_ctx_set_stream(self._ctx, C.c_void_p(stream)), self._ctx)
+        self.device = device
         self.n = 0
         self.m = 0
         self.n_q = None             # rows of the loaded query set (None: none; uploading / attaching the database drops it)
@@ -392,6 +395,50 @@ class Selector:
         self.finish()
         return self.fetch() if fetch else None
 
+    # -- dense matrices -----------------------------------------------------------------------------
+    def _matrix(self, query: bool, measure, dtype, rows, row_pos, col_pos, out):
+        import torch
+        code = {"jaccard": MEASURE_JACCARD, "union": MEASURE_UNION}.get(measure, measure)
+        if code not in (MEASURE_JACCARD, MEASURE_UNION):
+            raise ValueError("measure: 'jaccard' or 'union'")
+        if dtype not in (torch.float64, torch.float32):
+            raise ValueError("dtype: torch.float64 or torch.float32")
+        if query and self.n_q is None:
+            check(self._lib.selhip_ctx_query_matrix(self._ctx, code, F64, 0, 0, None, 0, 0, 0, None, None), self._ctx)   # (raises: no queries)
+        r0, r1 = rows if rows is not None else (0, self.n_q if query else self.n)
+        if out is None:
+            n_out_rows = max(r1 - r0, 0) if row_pos is None else int(np.max(row_pos[r0:r1], initial=-1)) + 1
+            n_out_cols = self.n if col_pos is None else int(np.max(col_pos, initial=-1)) + 1
+            out = torch.empty((max(n_out_rows, 0), max(n_out_cols, 0)), dtype=dtype, device=torch.device("cuda", self.device))
+        assert out.is_cuda and out.dim() == 2 and out.dtype == dtype, "out: a 2-D device tensor of the requested dtype"
+        assert out.shape[1] <= 1 or out.stride(1) == 1, "out: stride(1) must be 1"
+        ld = out.stride(0) if out.shape[0] > 1 else max(out.stride(0), out.shape[1])
+        rp = None if row_pos is None else np.ascontiguousarray(row_pos, dtype=np.int32)
+        cp = None if col_pos is None else np.ascontiguousarray(col_pos, dtype=np.int32)
+        if rp is not None:
+            assert rp.ndim == 1 and len(rp) >= r1, "row_pos is indexed by rank: it covers the ranks below rows[1]"
+        if cp is not None:
+            assert cp.shape == (self.n,), "col_pos: one position per column rank"
+        fn = self._lib.selhip_ctx_query_matrix if query else self._lib.selhip_ctx_matrix
+        check(fn(self._ctx, code, F32 if dtype == torch.float32 else F64, r0, r1, out.data_ptr() if out.numel() else None,
+                 out.shape[0], out.shape[1], ld, None if rp is None else rp.ctypes.data, None if cp is None else cp.ctypes.data), self._ctx)
+        return out
+
+    def matrix(self, measure="jaccard", dtype=None, rows: Optional[Tuple[int, int]] = None, row_pos=None, col_pos=None, out=None):
+        """the similarity of every pair of the context's sketches as a torch tensor on the device (selhip_ctx_matrix): measure
+        "jaccard" (J of the passes, bit for bit; exactly 1.0 on the diagonal; NaN for two empty sketches) or "union" (the union
+        estimate U, also on the diagonal), dtype torch.float64 (default) or torch.float32.  rows = (r0, r1): only that slab of rows.
+        row_pos / col_pos: host int32 arrays indexed by rank -- the cell of rank-row i and rank-column k goes to
+        out[row_pos[i], col_pos[k]] (defaults i - r0 and k).  out: a caller's 2-D tensor (stride(1) == 1; stride(0) is its leading
+        dimension), written in place and returned; cells no (row, column) maps to keep their content"""
+        import torch
+        return self._matrix(False, measure, dtype or torch.float64, rows, row_pos, col_pos, out)
+
+    def query_matrix(self, measure="jaccard", dtype=None, rows: Optional[Tuple[int, int]] = None, row_pos=None, col_pos=None, out=None):
+        """as matrix, rows = the attached queries, columns = the database (selhip_ctx_query_matrix): no diagonal, no symmetry"""
+        import torch
+        return self._matrix(True, measure, dtype or torch.float64, rows, row_pos, col_pos, out)
+
     def result_count(self) -> int:
         return int(check(self._lib.selhip_ctx_result_count(self._ctx), self._ctx))
 
@@ -474,6 +521,37 @@ def select_from_filelist(list_file: str, tau: float, aux_bytes: int, mode: int =
         sel.set_criterion(crit)
         pairs = sel.run(tau, mode, n_rows, n_bands, algo=algo, top_k=top_k if top_k else None)
     return format_lines(ds.names, pairs)
+
+
+def _inverse(order: np.ndarray) -> np.ndarray:
+    inv = np.empty(len(order), dtype=np.int32)
+    inv[order] = np.arange(len(order), dtype=np.int32)
+    return inv
+
+
+def matrix_from_filelist(list_file: str, aux_bytes: int = 0, measure="jaccard", dtype=None, fp_mode: int = FP_FMA, device: int = 0):
+    """(names, tensor): the n x n matrix of the genomes of list_file with rows and columns in FILE-LIST order.  The sketches are loaded
+    and sorted as for a selection (only the .hll files are read; aux_bytes is accepted for symmetry with the other front ends), and the
+    ranks' lines in the list go to the library as both position arrays: the matrix is written in place, nothing is gathered afterwards"""
+    ds = load_dataset(list_file, 0, 0, fp_mode)
+    n = len(ds.names)
+    with Selector(device, fp_mode) as sel:
+        sel.upload(ds.hll, np.zeros((n, 1), dtype=np.uint64), ds.cards)
+        m = sel.matrix(measure, dtype, row_pos=ds.order, col_pos=ds.order)
+    names = [ds.names[r] for r in _inverse(ds.order)]
+    return names, m
+
+
+def query_matrix_from_filelists(query_list: str, db_list: str, aux_bytes: int = 0, measure="jaccard", dtype=None, fp_mode: int = FP_FMA,
+                                device: int = 0):
+    """(query names, database names, tensor): the n_Q x n_D matrix of the two lists, rows and columns in the order of their files"""
+    qs = load_dataset(query_list, 0, 0, fp_mode)
+    db = load_dataset(db_list, 0, 0, fp_mode)
+    with Selector(device, fp_mode) as sel:
+        sel.upload(db.hll, np.zeros((len(db.names), 1), dtype=np.uint64), db.cards)
+        sel.upload_queries(qs.hll, np.zeros((len(qs.names), 1), dtype=np.uint64), qs.cards)
+        m = sel.query_matrix(measure, dtype, row_pos=qs.order, col_pos=db.order)
+    return [qs.names[r] for r in _inverse(qs.order)], [db.names[r] for r in _inverse(db.order)], m
 
 
 def read_pair_list(pair_file: str, names: Sequence[str]) -> np.ndarray:

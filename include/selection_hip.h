@@ -199,6 +199,10 @@ int selhip_ctx_set_candidate_begin(selhip_ctx* ctx, int64_t k_min);
  *   "dense_fused" SELHIP_CRIT_NONE: 1 (default) the pass is ONE kernel behind the bounds (dense_select_kernel: union histograms into an
  *                 LDS tile, estimator and J test in the same wave); 0 the list route -- the pair space listed explicitly in row
  *                 sub-passes, then the union-histogram and estimator kernels of the other criteria.  Same records and statistics;
+ *   "matrix_mirror" a MEASUREMENT switch of the dense matrices (section 2f), the one name here that changes what is written: 1 (default) a
+ *                 self matrix stores every computed cell (i, k), i < k < r1, at (k, i) as well; 0 it stores no mirrored cell, so a call
+ *                 writes only the columns [0, r0) and [i, n) of each row i of its slab [r0, r1) and the matrix is INCOMPLETE below the
+ *                 diagonal -- for timing the mirrored stores (scripts/bench_matrix.py), not for use.  selhip_ctx_get_param reads it back;
  *   "timed_kernel" see selhip_ctx_timing.
  * (The library also answers to a few names that are NOT part of this interface -- hooks of its own test-suite and measurement
  * knobs, listed at selhip_ctx_set_param in csrc/selection_kernels.hip.) */
@@ -319,6 +323,8 @@ int selhip_ctx_set_allpairs_topk(selhip_ctx* ctx, int k);
  * SELHIP_CRIT_NONE), "topk" (the cut of a query pass with selhip_ctx_set_query_topk, section 2b: its four launches; not part of "total"), "total"; "join_span" = first start to
  * last end of the pass's join launches (chunk lanes run them side by side).  <0 if never launched.
  * "topk" is also the cut of an all-pairs pass with selhip_ctx_set_allpairs_topk (above), again outside "total".
+ * "matrix" is the kernel of a dense matrix (section 2f), averaged over the MATRIX CALLS since the last reset: they are counted apart
+ * from the passes, so a matrix call changes no other name's per-pass figure.
  * selhip_ctx_kernel_launches: launches of that kernel per pass. */
 double selhip_ctx_kernel_ms(const selhip_ctx* ctx, const char* name);
 double selhip_ctx_kernel_launches(const selhip_ctx* ctx, const char* name);
@@ -474,6 +480,44 @@ int selhip_ctx_run_pairs(selhip_ctx* ctx, const selhip_int2_t* d_pairs, int64_t 
 /* Asynchronous variant: selhip_ctx_finish() waits, validates and reports invalid entries. */
 int selhip_ctx_run_pairs_async(selhip_ctx* ctx, const selhip_int2_t* d_pairs, int64_t n_pairs,
                                int mode, int algo, float tau_f, int n_rows, int n_bands);
+
+/* ---------------------------------------------------------------------------------------------------
+ * 2f. Dense matrices: the similarity of EVERY pair as one array in the caller's device memory (what `mash triangle` / `dashing dist`
+ *     print), no criterion, no threshold, no record list.  The cell of a row genome a and a column genome b:
+ *       U = the Ertl estimate of the register-wise maximum of the two p = 14 sketches, in the context's FP flavour
+ *           (the reference's hll_t::union_size; the arithmetic of the passes' stage 2);
+ *       SELHIP_MEASURE_UNION stores U; SELHIP_MEASURE_JACCARD stores ((double)e_a + (double)e_b - U) / U (selection.cpp:287, e = the
+ *       truncated cardinalities) for every pair without exception: two empty sketches give NaN, and the matrix holds that NaN.
+ *     On the diagonal of a self matrix UNION stores U(i, i), computed like any cell; JACCARD stores exactly 1.0.  dtype SELHIP_F64
+ *     carries the bits the passes' records carry, SELHIP_F32 is (float) of that value.  A self matrix is bit-symmetric.
+ *     selhip_ctx_matrix: rows [r0, r1) of the context's sketches against all n of them; selhip_ctx_query_matrix: rows [r0, r1) of the
+ *     attached queries (section 2b) against the n sketches of the database.  Ranks are those of the sets as uploaded (the cells do
+ *     not depend on the order).
+ *     out_dev: the caller's device buffer of out_rows x ld elements of dtype (aligned to the element), ld >= out_cols counted in
+ *     elements.  row_pos / col_pos are HOST int32 arrays or NULL: the cell of rank-row i and rank-column k goes to
+ *     out[row_pos[i]][col_pos[k]]; row_pos is indexed by rank and read for the ranks in [r0, r1) only, col_pos for all n columns;
+ *     NULL = row_pos[i] = i - r0, col_pos[k] = k.  Passing the inverse of a sort permutation as both gives the matrix in the
+ *     caller's original order without a gather.  Every position (the defaults too) is checked on the host before anything is
+ *     launched -- 0 <= row position < out_rows, 0 <= column position < out_cols, SELHIP_E_BADARG with the first offending index in
+ *     the message -- and only the checked copies reach the device.  Two rows (columns) sent to the same position is not an error:
+ *     which one lands there is unspecified.  Cells of out_dev that no (row, column) of the call maps to are not written.
+ *     SELHIP_E_BADARG also for: ld < out_cols, r0 > r1 or a range outside the set, a NULL or misaligned out_dev with cells to write, an
+ *     unknown measure or dtype, a query matrix without attached queries, and -- the rule of SELHIP_CRIT_NONE -- sketches with
+ *     p_hll != 14 or without resident bit planes ("hist_algo" 0).  n == 0 or r0 == r1: SELHIP_OK, nothing is written
+ *     (the arguments above are checked all the same, except that out_dev may then be NULL and no position is read).
+ *     SELHIP_E_STATE while a pass is pending.
+ *     The call runs on the context's stream and returns when the matrix is complete.  It leaves the result list, result_count, the
+ *     statistics, the top-k settings and the signature cache as they were; a context that never calls it launches what it always did.
+ *     Its one kernel is timed as "matrix" (selhip_ctx_kernel_ms: per matrix call; the passes' per-pass figures are not touched).
+ * --------------------------------------------------------------------------------------------------- */
+#define SELHIP_MEASURE_JACCARD  0
+#define SELHIP_MEASURE_UNION    1
+#define SELHIP_F64              0
+#define SELHIP_F32              1
+int selhip_ctx_matrix(selhip_ctx* ctx, int measure, int dtype, int64_t r0, int64_t r1, void* out_dev,
+                      int64_t out_rows, int64_t out_cols, int64_t ld, const int32_t* row_pos, const int32_t* col_pos);
+int selhip_ctx_query_matrix(selhip_ctx* ctx, int measure, int dtype, int64_t r0, int64_t r1, void* out_dev,
+                            int64_t out_rows, int64_t out_cols, int64_t ld, const int32_t* row_pos, const int32_t* col_pos);
 
 
 /* ---------------------------------------------------------------------------------------------------

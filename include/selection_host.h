@@ -74,6 +74,8 @@ const uint64_t* selhost_dataset_aux(const selhost_dataset* ds);      /* [n][m]  
 const uint8_t*  selhost_dataset_aux_hll(const selhost_dataset* ds);  /* [n][1<<p_aux]   */
 const double*   selhost_dataset_cards(const selhost_dataset* ds);    /* [n] ascending   */
 const char*     selhost_dataset_name(const selhost_dataset* ds, int64_t rank);
+/* the line of the file list (from 0, empty lines not counted) that the genome of this rank came from; -1 outside [0, n) */
+int64_t         selhost_dataset_order(const selhost_dataset* ds, int64_t rank);
 
 /* "fn1 fn2 0.946107\n" (std::to_string(double) == "%f"); returns bytes written (excluding NUL) or <0 */
 int selhost_format_line(const char* fn1, const char* fn2, double jaccard, char* buf, size_t cap);
@@ -86,6 +88,14 @@ int selhost_format_line(const char* fn1, const char* fn2, double jaccard, char* 
  * SELHOST_E_FORMAT with the line number (from 1) in the message: a name that is not in names[], a line with fewer than two
  * fields, two equal names. */
 int selhost_read_pair_list(const char* path, const char* const* names, int64_t n_names, int32_t* out_xy, int64_t cap, int64_t* count);
+
+/* ---- dense matrices as text (the output of selhip_ctx_matrix / selhip_ctx_query_matrix copied to the host) ----------
+ * A tab-separated table: the first line is a tab followed by the tab-separated column names; then one line per row: the row's
+ * name, then its n_cols values in "%.17g" (which round-trips an f64 exactly -- NaN is printed as "nan" or "-nan" -- so two files
+ * can be compared bit for bit), tab-separated.  values[r * ld + k] is the cell of row r and column k; ld >= n_cols, in elements.
+ * SELHOST_E_IO if the file cannot be opened or written. */
+int selhost_write_matrix(const char* path, const double* values, int64_t n_rows, int64_t n_cols, int64_t ld,
+                         const char* const* row_names, const char* const* col_names);
 
 /* ---- on-disk result format (the reference only prints text, selection.cpp:297-300) ---------
  * A self-contained binary file: the selected pairs as 16-byte records plus the table of genome names their ranks refer to.
