@@ -1,4 +1,4 @@
-// common.cuh -- types, launch constants, per-pass counters and the per-wave output appender.
+// common.cuh -- types, launch constants, per-pass counters and the output appenders (per wave, per block).
 // Part of libselhip.so; included by selection_kernels.hip only (one translation unit, anonymous namespace).
 #pragma once
 
@@ -132,5 +132,59 @@ struct WaveAppender {
         if (count >= kWave) flush(lane);
     }
 };
+
+// ---------------------------------------------------------------------------------------------
+// block_append: the per-BLOCK form, for kernels whose blocks of kAppendBlock threads work through one batch of kAppendBlock records
+// at a time.  What a batch passes on is gathered in LDS and appended with one global atomic per block and batch (plus one for
+// `cand`, a tally the caller's waves add to during the batch): a tenth of the atomics of a per-wave append.
+// The count is exact when the output list is too small (stores are clipped).
+// ---------------------------------------------------------------------------------------------
+constexpr int kAppendBlock = 512;
+
+struct BlockAppendLds {
+    selhip_int2_t out[kAppendBlock];
+    u64 base;
+    uint32_t count, cand;                   // this batch: records passed on, the caller's tally
+};
+
+// thread 0, before the block's first barrier
+__device__ __forceinline__ void block_append_reset(BlockAppendLds& s) { s.count = 0; s.cand = 0; }
+
+// block-uniform, blockDim.x == kAppendBlock (one record per thread and batch): the batch's records with `ok` go to out[] behind *out_count; cand_count (if given) takes the batch's s.cand;
+// stored(q) runs once for every record q that was stored (not clipped), on the thread that stored it
+template <class Stored>
+__device__ __forceinline__ void block_append(BlockAppendLds& s, bool ok, selhip_int2_t pr, int lane, selhip_int2_t* __restrict__ out, u64 out_cap,
+                                             u64* __restrict__ out_count, u64* __restrict__ cand_count, Stored stored) {
+    const u64 okb = __ballot(ok);
+    if (okb) {
+        uint32_t wbase = 0;
+        if (lane == 0) wbase = atomicAdd(&s.count, (uint32_t)__popcll(okb));
+        wbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)wbase);
+        if (ok) s.out[wbase + (uint32_t)__popcll(okb & ((1ull << lane) - 1ull))] = pr;
+    }
+    __syncthreads();
+    const uint32_t cnt = s.count;
+    if (threadIdx.x == 0) {
+        if (cnt) s.base = atomicAdd(out_count, (u64)cnt);
+        if (cand_count && s.cand) atomicAdd(cand_count, (u64)s.cand);
+    }
+    __syncthreads();
+    if (threadIdx.x < cnt) {
+        const u64 dst = s.base + threadIdx.x;
+        if (dst < out_cap) {
+            const selhip_int2_t q = s.out[threadIdx.x];
+            out[dst] = q;
+            stored(q);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) block_append_reset(s);
+    __syncthreads();
+}
+
+__device__ __forceinline__ void block_append(BlockAppendLds& s, bool ok, selhip_int2_t pr, int lane, selhip_int2_t* __restrict__ out, u64 out_cap,
+                                             u64* __restrict__ out_count, u64* __restrict__ cand_count) {
+    block_append(s, ok, pr, lane, out, out_cap, out_count, cand_count, [](selhip_int2_t) {});
+}
 
 }  // namespace

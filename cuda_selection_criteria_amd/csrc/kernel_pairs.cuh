@@ -17,20 +17,18 @@ namespace {
 //    returning atomics, ~87 per microsecond chip-wide, so one per wave or per entry would bound the kernel.
 // The counts are exact when the output list is too small (stores are clipped): the host grows it and repeats the pass.
 // =============================================================================================
-constexpr int kPairsBlock = 512;
+constexpr int kPairsBlock = kAppendBlock;
 constexpr unsigned kPairsMaxGrid = 1024;
 constexpr int kPairsSteps = 8;                 // pairs_direct_kernel: 16-bucket steps whose loads are in flight together
 
 struct PairsLds {
-    selhip_int2_t out[kPairsBlock];
-    u64 base;
-    uint32_t count, cand;                   // this batch: entries passed on, entries with an equal band signature
+    BlockAppendLds app;                     // (block_append, common.cuh; app.cand = the batch's entries with an equal band signature)
     uint32_t bad;
     u64 eval, bad_at;                       // the block's tallies, added up when its waves end
 };
 
 __device__ __forceinline__ void pairs_lds_init(PairsLds& s) {
-    if (threadIdx.x == 0) { s.count = 0; s.cand = 0; s.bad = 0; s.eval = 0; s.bad_at = 0; }
+    if (threadIdx.x == 0) { block_append_reset(s.app); s.bad = 0; s.eval = 0; s.bad_at = 0; }
     __syncthreads();
 }
 
@@ -67,32 +65,6 @@ __device__ __forceinline__ selhip_int2_t pairs_entry(const selhip_int2_t* __rest
     return pr;
 }
 
-// block-uniform: the batch's entries with `ok` go to out[] behind *out_count; cand_count (if given) takes the batch's s.cand
-__device__ __forceinline__ void pairs_block_append(PairsLds& s, bool ok, selhip_int2_t pr, int lane, selhip_int2_t* __restrict__ out, u64 out_cap,
-                                                   u64* __restrict__ out_count, u64* __restrict__ cand_count) {
-    const u64 okb = __ballot(ok);
-    if (okb) {
-        uint32_t wbase = 0;
-        if (lane == 0) wbase = atomicAdd(&s.count, (uint32_t)__popcll(okb));
-        wbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)wbase);
-        if (ok) s.out[wbase + (uint32_t)__popcll(okb & ((1ull << lane) - 1ull))] = pr;
-    }
-    __syncthreads();
-    const uint32_t cnt = s.count;
-    if (threadIdx.x == 0) {
-        if (cnt) s.base = atomicAdd(out_count, (u64)cnt);
-        if (cand_count && s.cand) atomicAdd(cand_count, (u64)s.cand);
-    }
-    __syncthreads();
-    if (threadIdx.x < cnt) {
-        const u64 dst = s.base + threadIdx.x;
-        if (dst < out_cap) out[dst] = s.out[threadIdx.x];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) { s.count = 0; s.cand = 0; }
-    __syncthreads();
-}
-
 // the block's tallies into the pass's counter block 0
 __device__ __forceinline__ void pairs_block_tally(PairsLds& s, const PairsTally& tl, int lane, PassCounters* __restrict__ pc0) {
     if (lane == 0) {
@@ -104,11 +76,6 @@ __device__ __forceinline__ void pairs_block_tally(PairsLds& s, const PairsTally&
         if (s.eval) atomicAdd(&pc0->n_evaluated, s.eval);
         if (s.bad) { atomicAdd(&pc0->n_pre, (u64)s.bad); atomicMax(&pc0->n_pre_segmax, s.bad_at); }
     }
-}
-
-// bit q of the result = the ballot's bit of lane 16 q (one bit per quarter-wave), moved up by `sh`
-__device__ __forceinline__ u64 pairs_quarter_bits(u64 m, int sh) {
-    return (((m >> 0) & 1ull) | (((m >> 16) & 1ull) << 1) | (((m >> 32) & 1ull) << 2) | (((m >> 48) & 1ull) << 3)) << sh;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -127,21 +94,16 @@ void pairs_filter_kernel(const selhip_int2_t* __restrict__ list, u64 off, u64 en
         const u64 j = base + threadIdx.x;
         bool live;
         const selhip_int2_t pr = pairs_entry(list, j, j < end, n, ecard, tau, use_cb, tl, &live);
-        pairs_block_append(s, live, pr, lane, out, out_cap, out_count, nullptr);
+        block_append(s.app, live, pr, lane, out, out_cap, out_count, nullptr);
     }
     pairs_block_tally(s, tl, lane, pc0);
 }
 
 // ---------------------------------------------------------------------------------------------
-// pairs_verify_kernel: the signature route.  The body of verify16_kernel (kernel_sigjoin.cuh) with the list, not the join's 64 append
-// segments, as its input: a wave works on its 64 entries four at a time, 16 lanes per entry; the two genomes' 32-bit signature rows
-// come from the genome-major copy sigQ by 16-byte loads and give one bit per band; an entry with a bit set is a CANDIDATE (counted
-// in n_candidates); its first flagged band is compared on the full sketches; equal -> survivor, not equal (a signature collision,
-// or `force_fallback`) -> the literal smh_a_lane decides.
-// A SECOND COPY of that body, on purpose: verify16_kernel is on the path of every all-pairs pass, and handing both kernels one
-// __device__ function was not shown to leave its ISA as it is.  A change of the rule "signature equal, band not equal" belongs in
-// both (and in the four other places DESIGN.md section 4.2b lists).
-// Resources (compiler's report for gfx950, -O3): 73 VGPRs, no scratch, 4 136 B of LDS; occupancy 6 waves per SIMD.
+// pairs_verify_kernel: the signature route.  verify16_kernel with the list, not the join's 64 append segments, as its input: the
+// body is verify16_batch (kernel_verify.cuh) -- an entry with a signature bit set is a CANDIDATE (counted in n_candidates) -- and
+// sig_candidate_ok decides it (`force_fallback`: test hook "verify_fb").
+// Resources (compiler's report for gfx950, -O3): 71 VGPRs, no scratch, 4 136 B of LDS; occupancy 7 waves per SIMD.
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kPairsBlock)
 void pairs_verify_kernel(const u64* __restrict__ aux, int m, int n_rows, int n_bands, const uint32_t* __restrict__ sigQ,
@@ -150,62 +112,18 @@ void pairs_verify_kernel(const u64* __restrict__ aux, int m, int n_rows, int n_b
                          int force_fallback) {
     __shared__ PairsLds s;
     const int lane = threadIdx.x & (kWave - 1);
-    const int sub = lane & 15, quarter = lane >> 4, qshift = quarter * 16;
-    const int nq = n_bands >> 2;                                              // 16-byte groups per genome (n_bands % 8 == 0, <= 32)
     pairs_lds_init(s);
     PairsTally tl;
     for (u64 base = (u64)blockIdx.x * kPairsBlock; base < n_pairs; base += (u64)gridDim.x * kPairsBlock) {
         const u64 j = base + threadIdx.x;
         bool live;
         const selhip_int2_t pr = pairs_entry(list, j, j < n_pairs, n, ecard, tau, use_cb, tl, &live);
-        const u64 live_mask = __ballot(live);
-        u64 has_mask = 0, ok_mask = 0;                                        // bit p: entry p of this wave's 64 (wave-uniform)
-#pragma unroll 1
-        for (int s0 = 0; s0 < 16; s0 += 8) {
-            int px[8], py[8];
-            uint32_t lm[8];           // bit t (0..3): band 4*sub+t equal; bit 4+t: band 4*(sub+16)+t equal
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                const int src = (s0 + t) * 4 + quarter;
-                px[t] = __shfl(pr.x, src, kWave);
-                py[t] = __shfl(pr.y, src, kWave);
-                const uint4* a = reinterpret_cast<const uint4*>(sigQ + (long long)px[t] * n_bands);
-                const uint4* b = reinterpret_cast<const uint4*>(sigQ + (long long)py[t] * n_bands);
-                uint32_t bits = 0;
-                if (sub < nq) {
-                    const uint4 u = a[sub], v = b[sub];
-                    bits |= (u.x == v.x ? 1u : 0u) | (u.y == v.y ? 2u : 0u) | (u.z == v.z ? 4u : 0u) | (u.w == v.w ? 8u : 0u);
-                }
-                if (sub + 16 < nq) {
-                    const uint4 u = a[sub + 16], v = b[sub + 16];
-                    bits |= (u.x == v.x ? 16u : 0u) | (u.y == v.y ? 32u : 0u) | (u.z == v.z ? 64u : 0u) | (u.w == v.w ? 128u : 0u);
-                }
-                lm[t] = ((live_mask >> src) & 1ull) ? bits : 0u;
-            }
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                const uint32_t mine = (uint32_t)(__ballot(lm[t] != 0u) >> qshift) & 0xFFFFu;   // lanes of my quarter with a bit
-                const bool has = mine != 0u;
-                const int src_sub = has ? __builtin_ctz(mine) : 0;
-                const uint32_t lmv = (uint32_t)__shfl((int)lm[t], qshift + src_sub, kWave);
-                const int bt = has ? __builtin_ctz(lmv) : 0;
-                const int band = bt < 4 ? src_sub * 4 + bt : (src_sub + 16) * 4 + (bt - 4);
-                const u64* x = aux + (long long)px[t] * m + (long long)band * n_rows;
-                const u64* y = aux + (long long)py[t] * m + (long long)band * n_rows;
-                bool eq = true;
-                for (int j0 = sub; j0 < n_rows; j0 += 16)
-                    if (has) eq &= x[j0] == y[j0];
-                const bool all_eq = ((uint32_t)(__ballot(eq) >> qshift) & 0xFFFFu) == 0xFFFFu && !force_fallback;
-                const int sh = (s0 + t) * 4;
-                has_mask |= pairs_quarter_bits(__ballot(has && sub == 0), sh);
-                ok_mask |= pairs_quarter_bits(__ballot(has && all_eq && sub == 0), sh);
-            }
-        }
-        const u64 fb_mask = has_mask & ~ok_mask;                              // signature collision: the literal predicate decides
-        bool ok = (ok_mask >> lane) & 1ull;
-        if ((fb_mask >> lane) & 1ull) ok = smh_a_lane(aux + (long long)pr.x * m, aux + (long long)pr.y * m, n_rows, n_bands);
-        if (lane == 0 && has_mask) atomicAdd(&s.cand, (uint32_t)__popcll(has_mask));
-        pairs_block_append(s, ok, pr, lane, surv, surv_cap, &pc->n_survivors, &pc->n_candidates);
+        const Verify16Masks vm = verify16_batch(aux, m, n_rows, n_bands, sigQ, pr, __ballot(live), lane);
+        bool ok = false;
+        if ((vm.has >> lane) & 1ull)
+            ok = sig_candidate_ok((vm.eq >> lane) & 1ull, force_fallback, aux + (long long)pr.x * m, aux + (long long)pr.y * m, n_rows, n_bands);
+        if (lane == 0 && vm.has) atomicAdd(&s.app.cand, (uint32_t)__popcll(vm.has));
+        block_append(s.app, ok, pr, lane, surv, surv_cap, &pc->n_survivors, &pc->n_candidates);
     }
     pairs_block_tally(s, tl, lane, pc0);
 }
@@ -299,7 +217,7 @@ void pairs_direct_kernel(const u64* __restrict__ aux, int m, int n_rows, int n_b
             ok_mask |= pairs_quarter_bits(__ballot(found && sub == 0), t * 4);
         }
         const bool ok = (ok_mask >> lane) & 1ull;
-        pairs_block_append(s, ok, pr, lane, surv, surv_cap, surv_count, nullptr);
+        block_append(s.app, ok, pr, lane, surv, surv_cap, surv_count, nullptr);
     }
     if constexpr (!LAUNCHER) pairs_block_tally(s, tl, lane, pc0);
 }

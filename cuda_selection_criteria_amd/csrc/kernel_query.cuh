@@ -8,7 +8,7 @@
 //   query_windows_kernel      one lane per query: e_q, the contiguous CB window [lo_q, hi_q] of D (two binary searches on the literal
 //                             predicate), the evaluated-pair count; also the truncated cards of both sets in ONE index space [Q | D]
 //   query_sig_join_kernel     SIG: a tile of queries' band signatures in LDS, one database genome per lane (band-major, coalesced)
-//   query_verify_kernel       32-bit signatures, then the full sketches: a signature collision can never produce a pair
+//   query_verify_kernel       32-bit signatures, then the first flagged band on the full sketches (sig_candidate_ok, kernel_verify.cuh)
 //   query_stream_kernel       STREAM: any band shape; a tile of query rows in LDS, database rows streamed coalesced, one row per wave
 //   query_union_hist_kernel   stage 2a on the bit planes of Q and D (the pair-histogram code of kernel_hllbs.cuh with two base pointers)
 // The survivor list carries (q, n_q + d) -- the combined index space -- so that the estimator / select kernel of the all-pairs path runs
@@ -169,9 +169,8 @@ void query_sig_join_kernel(const uint32_t* __restrict__ sig_q, const uint32_t* _
 
 // query_verify_kernel: one lane per match (q, d) of the join (its list counted in n_pre).  (1) The two genomes' 32-bit signature rows
 // (genome-major sigQ, 16-byte loads) give the first band with an equal signature; the pairs that have one are the candidate set,
-// counted in n_candidates.  (2) That band is compared on the full sketches: equal -> the pair survives; not equal (a 32-bit
-// collision) -> the literal smh_a (criteria_sketch.hpp:66-81) on Q's and D's rows decides.  (Against the literal check alone, which
-// walks the bands from the first: W1 verification 31 -> 29 us, W2 135 -> 15 us.)
+// counted in n_candidates.  (2) That band is compared on the full sketches and sig_candidate_ok (kernel_verify.cuh) decides on Q's
+// and D's rows.  (Against the literal check alone, which walks the bands from the first: W1 verification 31 -> 29 us, W2 135 -> 15 us.)
 // Survivors are appended as (q, n_q + d), the combined index space of stage 2.
 __global__ __launch_bounds__(kBlock)
 void query_verify_kernel(const u64* __restrict__ aux_q, const u64* __restrict__ aux_d, int m, int n_rows, int n_bands, int n_q,
@@ -211,7 +210,7 @@ void query_verify_kernel(const u64* __restrict__ aux_q, const u64* __restrict__ 
                 const u64* y = aux_d + (size_t)pr.y * m + (size_t)first * n_rows;
                 int t = 0;
                 while (t < n_rows && x[t] == y[t]) ++t;
-                ok = t == n_rows || smh_a_lane(aux_q + (size_t)pr.x * m, aux_d + (size_t)pr.y * m, n_rows, n_bands);
+                ok = sig_candidate_ok(t == n_rows, 0, aux_q + (size_t)pr.x * m, aux_d + (size_t)pr.y * m, n_rows, n_bands);
             }
         }
         app.push(ok, pr.x, n_q + pr.y, lane);

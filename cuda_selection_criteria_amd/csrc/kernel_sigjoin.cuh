@@ -1,4 +1,5 @@
-// kernel_sigjoin.cuh -- stage 1, ALGO_SIG: band signatures, all-pairs signature join (DPP broadcast), exact verification.
+// kernel_sigjoin.cuh -- stage 1, ALGO_SIG: band signatures, all-pairs signature join (DPP broadcast), hash join.  The exact
+// verification behind them is in kernel_verify.cuh.
 // Part of libselhip.so; included by selection_kernels.hip only (one translation unit, anonymous namespace).
 #pragma once
 
@@ -9,9 +10,8 @@ namespace {
 //   a pair passes smh_a iff SOME band of r buckets is entirely equal (criteria_sketch.hpp:66-81).  Equal bands
 //   have equal 32-bit signatures (a hash of the band's r u64 values), so "some band signature equal" is a
 //   necessary condition; pairs that meet it are CANDIDATES and are verified with the literal predicate on the
-//   full sketches (verify_kernel).  A hash collision only adds a candidate that the verification rejects
-//   (expected n_bands * 2^-32 per pair), it can never drop a pair: the survivor set is identical to the
-//   stream kernel's.  The all-pairs part then costs n_bands 32-bit compares per pair instead of m 64-bit ones.
+//   full sketches (kernel_verify.cuh: expected n_bands * 2^-32 collisions per pair, none of which changes the
+//   survivor set).  The all-pairs part then costs n_bands 32-bit compares per pair instead of m 64-bit ones.
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ u64 mix64(u64 x) {
     x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
@@ -802,154 +802,6 @@ void sigl_join_kernel(const uint32_t* __restrict__ sigP, const uint32_t* __restr
     }
 #endif
     app.flush(lane);
-}
-
-// verify_kernel: the literal smh_a on every candidate (one lane per candidate), survivors compacted.
-__global__ __launch_bounds__(kBlock)
-void verify_kernel(const u64* __restrict__ aux, int m, int n_rows, int n_bands,
-                   const selhip_int2_t* __restrict__ cand, const u64* __restrict__ n_cand_dev, u64 cand_cap,
-                   selhip_int2_t* __restrict__ surv, u64 surv_cap, PassCounters* __restrict__ pc) {
-    u64 n_cand = *n_cand_dev;
-    if (n_cand > cand_cap) n_cand = cand_cap;
-    for (u64 j = (u64)blockIdx.x * kBlock + threadIdx.x; j < n_cand; j += (u64)gridDim.x * kBlock) {
-        const selhip_int2_t pr = cand[j];
-        if (smh_a_lane(aux + (long long)pr.x * m, aux + (long long)pr.y * m, n_rows, n_bands)) {
-            u64 idx = atomicAdd(&pc->n_survivors, 1ull);
-            if (idx < surv_cap) surv[idx] = pr;
-        }
-    }
-}
-
-// (Round 3 built and measured the alternative of verifying INSIDE the join: every wave of sigl_join_kernel checked its own 16-bit matches
-// at its end -- the candidate registers are free there -- and a light kernel compacted the survivors; bit-identical in all 90 parity tests.
-// It lost: cfg3 join 101 -> 128 us for a verification 25 -> 7 us (step 0.250 -> 0.261 ms), cfg2 join 12.5 -> 26.5 us, cfg4 even
-// (gpurun_out/r03/f_jv*).  A wave meets ~8 matches, so its own verification is two or three dependent memory round trips for a
-// handful of pairs -- 6-8 us added to a 45 us wave that holds one of the 8 192 slots the second round of waves is waiting for -- and
-// keeping the row loop at 64 registers beside it cost spills.  The separate kernel stays.)
-// verify16_kernel: verification behind the 16-bit join.  A wave takes 64 pairs of the join's output at a time and works
-// on them four at a time, 16 lanes per pair (step s: quarter-wave q has pair 4s+q).
-//  1. 32-bit signatures: the lanes of a quarter read the two genomes' signature rows from the genome-major copy sigQ
-//     (coalesced 16-B loads, 2 x n_bands*4 bytes per pair, L2-resident) and keep one bit per band "32-bit signature
-//     equal".  Pairs with a bit set are exactly the candidate set of the 32-bit join (counted in n_candidates).
-//  2. A band that is entirely equal has an equal signature, so only bands with a bit set can make smh_a true: the first
-//     such band of each pair is compared on the full sketches (n_rows u64 per genome, 16 lanes).  Equal -> the pair
-//     survives.  Not equal (a 32-bit hash collision, ~2^-32 per band) -> the pair takes the literal smh_a on one lane.
-// All loads of a phase are independent across the steps, so a batch costs a handful of memory round trips instead of the
-// ~n_bands dependent ones of the lane-serial literal check (verify_kernel: 32 us for 45 000 candidates at cfg3).
-// Recorded alternatives: a separate filter kernel appending the passing pairs to a list (58 us at cfg3 -- one
-// single-address atomic per wave, ~85 of those per microsecond); one lane per pair for step 1 (uncoalesced loads: cfg4
-// verification 90 -> 370 us); literal check in place on each batch's few passing lanes (cfg4 355 us) or on lanes packed
-// through LDS (cfg4 205 us, cfg3 60 us).
-// Output: the survivors of a block's 512 pairs (256: 27 us, 512: 24 us, 1024: 26 us at cfg3) are gathered in LDS and appended with ONE global atomic per block and
-// batch (plus one for the candidate tally): appends are single-address atomics, ~85 per microsecond on this part, and a
-// per-wave append (1 500 waves at cfg3) costs more than the whole check (52 us vs 15 us).
-// force_fallback (test hook): treat every first-band comparison as a collision.
-constexpr int kVerifyBlock = 512;
-
-__global__ __launch_bounds__(kVerifyBlock)
-void verify16_kernel(const u64* __restrict__ aux, int m, int n_rows, int n_bands, const uint32_t* __restrict__ sigQ,
-                     const selhip_int2_t* __restrict__ pre_all, const u64* __restrict__ seg_cnt, u64 pre_cap,
-                     selhip_int2_t* __restrict__ surv, u64 surv_cap, PassCounters* __restrict__ pc, int force_fallback,
-                     int* __restrict__ row_cnt, int* __restrict__ row_lab, int n) {
-    __shared__ selhip_int2_t out_lds[kVerifyBlock];
-    __shared__ uint32_t blk_count, blk_cand;
-    __shared__ u64 blk_base;
-    // the join's output comes in kAppendSegs lists; block b works on list b % kAppendSegs (gridDim.x is a multiple of kAppendSegs)
-    const int seg = blockIdx.x % kAppendSegs;
-    const u64 seg_cap = pre_cap / kAppendSegs;
-    const selhip_int2_t* __restrict__ pre = pre_all + (size_t)seg * seg_cap;
-    const u64 n_seg = seg_cnt[seg * kSegStride];
-    if (blockIdx.x < kAppendSegs && threadIdx.x == 0 && n_seg) {             // exact totals for the host (overflow test, statistics)
-        atomicAdd(&pc->n_pre, n_seg);
-        atomicMax(&pc->n_pre_segmax, n_seg);
-    }
-    const u64 n_pre = n_seg > seg_cap ? seg_cap : n_seg;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int sub = lane & 15, quarter = lane >> 4, qshift = quarter * 16;
-    const int nq = n_bands >> 2;                                              // 16-byte groups per genome (n_bands % 8 == 0, <= 32)
-    if (threadIdx.x == 0) { blk_count = 0; blk_cand = 0; }
-    __syncthreads();
-    for (u64 base = (u64)(blockIdx.x / kAppendSegs) * kVerifyBlock; base < n_pre; base += (u64)(gridDim.x / kAppendSegs) * kVerifyBlock) {
-        const u64 j = base + threadIdx.x;
-        const bool live = j < n_pre;
-        selhip_int2_t pr{0, 0};
-        if (live) pr = pre[j];
-        const u64 live_mask = __ballot(live);
-        u64 has_mask = 0, ok_mask = 0, fb_mask = 0;                           // bit p: pair p of this wave's 64 (wave-uniform)
-#pragma unroll 1
-        for (int s0 = 0; s0 < 16; s0 += 8) {
-            int px[8], py[8];
-            uint32_t lm[8];           // bit t (0..3): band 4*sub+t equal; bit 4+t: band 4*(sub+16)+t equal
-#pragma unroll
-            for (int s = 0; s < 8; ++s) {
-                const int src = (s0 + s) * 4 + quarter;
-                px[s] = __shfl(pr.x, src, kWave);
-                py[s] = __shfl(pr.y, src, kWave);
-                const uint4* a = reinterpret_cast<const uint4*>(sigQ + (long long)px[s] * n_bands);
-                const uint4* b = reinterpret_cast<const uint4*>(sigQ + (long long)py[s] * n_bands);
-                uint32_t bits = 0;
-                if (sub < nq) {
-                    const uint4 u = a[sub], v = b[sub];
-                    bits |= (u.x == v.x ? 1u : 0u) | (u.y == v.y ? 2u : 0u) | (u.z == v.z ? 4u : 0u) | (u.w == v.w ? 8u : 0u);
-                }
-                if (sub + 16 < nq) {
-                    const uint4 u = a[sub + 16], v = b[sub + 16];
-                    bits |= (u.x == v.x ? 16u : 0u) | (u.y == v.y ? 32u : 0u) | (u.z == v.z ? 64u : 0u) | (u.w == v.w ? 128u : 0u);
-                }
-                lm[s] = ((live_mask >> src) & 1ull) ? bits : 0u;
-            }
-#pragma unroll
-            for (int s = 0; s < 8; ++s) {
-                const uint32_t mine = (uint32_t)(__ballot(lm[s] != 0u) >> qshift) & 0xFFFFu;   // lanes of my quarter with a bit
-                const bool has = mine != 0u;
-                const int src_sub = has ? __builtin_ctz(mine) : 0;
-                const uint32_t lmv = (uint32_t)__shfl((int)lm[s], qshift + src_sub, kWave);
-                const int t = has ? __builtin_ctz(lmv) : 0;
-                const int band = t < 4 ? src_sub * 4 + t : (src_sub + 16) * 4 + (t - 4);
-                const u64* x = aux + (long long)px[s] * m + (long long)band * n_rows;
-                const u64* y = aux + (long long)py[s] * m + (long long)band * n_rows;
-                bool eq = true;
-                for (int j0 = sub; j0 < n_rows; j0 += 16)
-                    if (has) eq &= x[j0] == y[j0];
-                const bool all_eq = ((uint32_t)(__ballot(eq) >> qshift) & 0xFFFFu) == 0xFFFFu && !force_fallback;
-                // one bit per quarter (lanes 0, 16, 32, 48) -> bits 4(s0+s) .. 4(s0+s)+3 of the pair masks
-                const u64 mh = __ballot(has && sub == 0), mo = __ballot(has && all_eq && sub == 0);
-                const int sh = (s0 + s) * 4;
-                has_mask |= (((mh >> 0) & 1ull) | (((mh >> 16) & 1ull) << 1) | (((mh >> 32) & 1ull) << 2) | (((mh >> 48) & 1ull) << 3)) << sh;
-                ok_mask |= (((mo >> 0) & 1ull) | (((mo >> 16) & 1ull) << 1) | (((mo >> 32) & 1ull) << 2) | (((mo >> 48) & 1ull) << 3)) << sh;
-            }
-        }
-        fb_mask = has_mask & ~ok_mask;                                        // signature collision: the literal predicate decides
-        bool ok = (ok_mask >> lane) & 1ull;
-        if ((fb_mask >> lane) & 1ull) ok = smh_a_lane(aux + (long long)pr.x * m, aux + (long long)pr.y * m, n_rows, n_bands);
-        const u64 okb = __ballot(ok);
-        if (okb) {
-            uint32_t wbase = 0;
-            if (lane == 0) wbase = atomicAdd(&blk_count, (uint32_t)__popcll(okb));
-            wbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)wbase);
-            if (ok) out_lds[wbase + (uint32_t)__popcll(okb & ((1ull << lane) - 1ull))] = pr;
-        }
-        if (lane == 0 && has_mask) atomicAdd(&blk_cand, (uint32_t)__popcll(has_mask));
-        __syncthreads();
-        const uint32_t cnt = blk_count;
-        if (threadIdx.x == 0) {
-            if (cnt) blk_base = atomicAdd(&pc->n_survivors, (u64)cnt);
-            if (blk_cand) atomicAdd(&pc->n_candidates, (u64)blk_cand);
-        }
-        __syncthreads();
-        if (threadIdx.x < cnt) {
-            const u64 dst = blk_base + threadIdx.x;
-            const selhip_int2_t q = out_lds[threadIdx.x];
-            if (dst < surv_cap) {
-                surv[dst] = q;
-                if (row_cnt) atomicAdd(&row_cnt[q.x], 1);                    // stage 2 grouping: survivors per query row, STORED ones only
-                if (row_lab) atomicMax(&row_lab[q.y], n - q.x);              // ... and every row's smallest partner (csr_label_* in kernel_hll.cuh)
-            }                                                                //   (like csr_count_kernel: the offsets must stay inside `grouped`)
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) { blk_count = 0; blk_cand = 0; }
-        __syncthreads();
-    }
 }
 
 // =============================================================================================

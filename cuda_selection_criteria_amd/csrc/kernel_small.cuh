@@ -8,7 +8,7 @@
 //   -------- grid barrier (two levels of arrival counters + a spin: 256 blocks, one per CU, all resident) --------
 //   phase 1  block b owns up to eight query rows (dealt boustrophedon, so the triangle's work is even): lane = candidate, "some band's
 //            32-bit signature equal" over the band-major signatures, matches queued in LDS and verified sixteen lanes to a pair on the
-//            flagged band (the literal smh_a after a 32-bit collision: rare), survivors into the block's LDS list;
+//            flagged band (sig_candidate_ok, kernel_verify.cuh), survivors into the block's LDS list;
 //   phase 2  the block's survivors, 64 at a time: a wave per pair builds the union histogram from the bit planes (bs_pair_hist, the code
 //            of stage 2a) into an LDS tile, then one wave runs the estimator with a lane per pair and appends the selected ones.
 // Nothing after the barrier leaves the block, so the stages of different blocks overlap freely.  Same results as the regular pass
@@ -113,8 +113,8 @@ void small_pass_kernel(const u64* __restrict__ aux, const double* __restrict__ c
     // a time (64 coalesced loads in flight per lane: the loads' round trips, not their bytes, are what this phase costs) and meet all the
     // rows; per row a lane keeps the first band whose 32-bit signatures agree and queues (row, band, candidate) in LDS.  The queue is
     // then verified sixteen lanes to a candidate: the flagged band alone is compared on the full sketches, one bucket per lane, so a
-    // block's few dozen candidates cost ONE round trip.  The literal lane-serial smh_a only decides after a 32-bit collision, as in
-    // verify16_kernel
+    // block's few dozen candidates cost ONE round trip (band_equal16), and sig_candidate_ok (kernel_verify.cuh) decides on lane 0 of
+    // the sixteen.
     const int z0 = pc->z0p1 ? pc->z0p1 - 1 : n;
     const int rows_total = rm.row_end - rm.row_begin;
     auto row_of = [&](int j) {                                               // ascending in j; -1 past the block's last row
@@ -210,17 +210,9 @@ void small_pass_kernel(const u64* __restrict__ aux, const double* __restrict__ c
                 const uint32_t e = live ? scratch_lds[q] : 0u;
                 const int ri = (int)(e >> 18), fb = (int)((e >> 11) & 127u), kk = (int)(e & 2047u);
                 const int i = row_lds[ri];
-                bool eq = true;
-                if (live) {
-                    const u64* x = aux + (long long)i * m + (long long)fb * r;
-                    const u64* y = aux + (long long)kk * m + (long long)fb * r;
-                    for (int j2 = sub; j2 < r; j2 += 16) eq &= x[j2] == y[j2];
-                }
-                const u64 em = __ballot(eq);
-                bool ok = live && !force_fallback && (uint32_t)((em >> (lane & 48)) & 0xFFFFull) == 0xFFFFu;
-                // a 32-bit collision (or the forced fallback): the literal predicate decides
-                if (live && sub == 0 && !ok) ok = smh_a_lane(aux + (long long)i * m, aux + (long long)kk * m, r, nb);
-                ok = ok && sub == 0;
+                const bool band_eq = band_equal16(aux + (long long)i * m + (long long)fb * r, aux + (long long)kk * m + (long long)fb * r, r, live, lane);
+                bool ok = false;
+                if (live && sub == 0) ok = sig_candidate_ok(band_eq, force_fallback, aux + (long long)i * m, aux + (long long)kk * m, r, nb);
                 const u64 om = __ballot(ok);
                 if (om) {
                     int base = 0;

@@ -172,21 +172,6 @@ void smh_stream_kernel(const u64x2* __restrict__ aux, int n,
     app.flush(lane);
 }
 
-// ---------------------------------------------------------------------------------------------
-// smh_a for one pair evaluated by ONE LANE (any m, rows, bands): criteria_sketch.hpp:66-81 literally.
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool smh_a_lane(const u64* __restrict__ v1, const u64* __restrict__ v2,
-                                           int n_rows, int n_bands) {
-    for (int b = 0; b < n_bands; ++b) {
-        const u64* x = v1 + (long long)b * n_rows;
-        const u64* y = v2 + (long long)b * n_rows;
-        int j = 0;
-        while (j < n_rows && x[j] == y[j]) ++j;
-        if (j == n_rows) return true;
-    }
-    return false;
-}
-
 // generic stage 1: block = 256 lanes = 256 candidates of one query row; grid = (chunks, rows)
 __global__ __launch_bounds__(kBlock)
 void smh_generic_kernel(const u64* __restrict__ aux, int n, int m, int n_rows, int n_bands,

@@ -8,11 +8,13 @@
 // This is the kernel translation unit of the library: it only includes.  The kernels live in the kernel_*.cuh headers (all integer
 // except the estimator; no MFMA), the host side in host_plan.hpp (decisions), host_context.hpp (context), host_pass.hpp (pass scheduler) and abi_*.inc (C ABI);
 // the multi-GPU and out-of-core drivers are translation units of their own (selhip_multi.hip, selhip_ooc.hip):
-//   common.cuh          launch constants, per-pass counters, WaveAppender (LDS-staged appends, one atomic per flush)
+//   common.cuh          launch constants, per-pass counters, WaveAppender / block_append (LDS-staged appends, one atomic per flush)
 //   kernel_bounds.cuh   cb_bounds_kernel      e_i = (size_t)card_i, CB cut-off hi(i), first non-zero rank
+//   kernel_verify.cuh   smh_a_lane (the literal predicate), sig_candidate_ok (the one statement of "signature equal, band not equal"),
+//                       verify16_batch (16 lanes per pair), verify_kernel / verify16_kernel: the exact verification behind ALGO_SIG
 //   kernel_stream.cuh   smh_stream_kernel     stage 1 ALGO_STREAM: query tile in LDS/VGPRs, candidates streamed row-major,
 //                                             v_cmp_eq_u64 lane masks folded on the scalar unit; smh_generic_kernel
-//   kernel_sigjoin.cuh  sig_build / sig_join / verify   stage 1 ALGO_SIG: all-pairs band-signature join (DPP broadcast) + exact verify
+//   kernel_sigjoin.cuh  sig_build / sig_join   stage 1 ALGO_SIG: all-pairs band-signature join (DPP broadcast), hash join
 //   kernel_hll.cuh      hll_union_hist_kernel, ertl_select_kernel (stage 2), enum_pairs / aux_fused (hll_a, hll_an)
 //   kernel_hllbs.cuh    hll_bitslice_kernel, hll_union_hist_bs_kernel: stage 2a on bit-sliced registers (bit-serial max, decode tree, v_bcnt)
 //   kernel_pairlist.cuh explicit pair lists (test building blocks)
@@ -60,6 +62,7 @@
 
 #include "common.cuh"
 #include "kernel_bounds.cuh"
+#include "kernel_verify.cuh"
 #include "kernel_stream.cuh"
 #include "kernel_sigjoin.cuh"
 #include "kernel_hll.cuh"
