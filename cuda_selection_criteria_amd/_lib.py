@@ -44,6 +44,7 @@ ALGO_AUTO, ALGO_STREAM, ALGO_SIG, ALGO_HASHJOIN, ALGO_INDEX = 0, 1, 2, 3, 4    #
 FP_STRICT, FP_FMA = 0, 1
 CRIT_SMH_A, CRIT_HLL_A, CRIT_HLL_AN, CRIT_HLL_A_SMH_A, CRIT_NONE = 0, 1, 2, 3, 4
 MEASURE_JACCARD, MEASURE_UNION = 0, 1  # SELHIP_MEASURE_*: what a dense matrix stores (Selector.matrix)
+MEASURE_SMH_MATCHES, MEASURE_SMH_JACCARD = 16, 17   # ... from the SuperMinHash rows: equal buckets of the pair, and that count / m
 F64, F32 = 0, 1                        # SELHIP_F64 / SELHIP_F32: its element type
 BANDING_CPU, BANDING_CUDA = 0, 1
 TOPK_MAX = 1024                        # SELHIP_TOPK_MAX: largest k of Selector.set_query_topk and Selector.set_allpairs_topk

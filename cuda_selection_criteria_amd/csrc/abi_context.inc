@@ -201,6 +201,12 @@ int selhip_ctx_set_param(selhip_ctx* c, const char* name, int value) {
     }
     if (!std::strcmp(name, "dense_fused")) { c->dense_fused = value != 0; return SELHIP_OK; }
     if (!std::strcmp(name, "matrix_mirror")) { c->matrix_mirror = value != 0; return SELHIP_OK; }   // measurement switch: 0 = no mirrored stores
+    // (not part of the documented interface: the measurement switch of scripts/bench_matrix_smh.py -- 1 = a self matrix of the SuperMinHash
+    //  measures computes every pair once and mirrors it, 3 = it computes the whole square; the same matrix either way)
+    if (!std::strcmp(name, "matrix_smh_form")) {
+        if (value != 1 && value != 3) { set_err(&c->err, "matrix_smh_form: 1 (every pair once, mirrored) or 3 (the whole square)"); return SELHIP_E_BADARG; }
+        c->matrix_smh_form = (int)value; return SELHIP_OK;
+    }
     if (!std::strcmp(name, "hist_dense_degree")) {
         if (value < -1 || value > (1 << 20)) { set_err(&c->err, "hist_dense_degree must be in [-1, 2^20] (-1 = never)"); return SELHIP_E_BADARG; }
         c->hist_dense_degree = value;
@@ -231,6 +237,8 @@ int selhip_ctx_get_param(const selhip_ctx* c, const char* name, int* value) {
     if (!std::strcmp(name, "chunks"))           { *value = c->n_chunks_last; return SELHIP_OK; }
     if (!std::strcmp(name, "dense_route_used")) { *value = c->dense_route_used; return SELHIP_OK; }         // SELHIP_CRIT_NONE: 1 fused kernel, 0 list route, -1 none yet
     if (!std::strcmp(name, "matrix_mirror"))    { *value = c->matrix_mirror; return SELHIP_OK; }
+    if (!std::strcmp(name, "matrix_smh_form"))  { *value = c->matrix_smh_form; return SELHIP_OK; }
+    if (!std::strcmp(name, "matrix_smh_path_used")) { *value = c->matrix_smh_path_used; return SELHIP_OK; }   // kernel of the last SuperMinHash matrix: 1 fast, 0 generic
     if (!std::strcmp(name, "small_pass_used"))  { *value = c->small_used ? 1 : 0; return SELHIP_OK; }
     if (!std::strcmp(name, "pairs_route_used")) { *value = c->pairs_route_used; return SELHIP_OK; }         // list passes: 1 signature, 0 direct, 2 no smh_a stage, -1 none yet
     if (!std::strcmp(name, "query_topk"))       { *value = c->query_topk; return SELHIP_OK; }              // K of the query passes' top-k, 0 = off
@@ -605,7 +613,7 @@ int selhip_ctx_timing(selhip_ctx* c, int enable) {
     drain_timers(c);
     for (int t = 0; t < T_COUNT; ++t) { c->timers[t].total_ms = 0; c->timers[t].launches = 0; c->timers[t].span_ms = 0; }
     c->timing = enable == 2 ? 2 : (enable != 0 ? 1 : 0);
-    c->timed_passes = 0; c->timed_matrix_calls = 0;
+    c->timed_passes = 0; c->timed_matrix_calls = 0; c->timed_matrix_smh_calls = 0;
     return SELHIP_OK;
 }
 
@@ -614,7 +622,7 @@ double selhip_ctx_kernel_ms(const selhip_ctx* c, const char* name) {
     if (!c->pending) drain_timers(const_cast<selhip_ctx*>(c));
     for (int t = 0; t < T_COUNT; ++t)
         if (!std::strcmp(name, kTimerNames[t])) {
-            const long passes = t == T_MATRIX ? c->timed_matrix_calls : c->timed_passes;
+            const long passes = t == T_MATRIX ? c->timed_matrix_calls : t == T_MATRIX_SMH ? c->timed_matrix_smh_calls : c->timed_passes;
             return (c->timers[t].launches && passes) ? c->timers[t].total_ms / (double)passes : -1.0;
         }
     const long passes = c->timed_passes;
@@ -628,7 +636,7 @@ double selhip_ctx_kernel_launches(const selhip_ctx* c, const char* name) {
     if (!c->pending) drain_timers(const_cast<selhip_ctx*>(c));
     for (int t = 0; t < T_COUNT; ++t)
         if (!std::strcmp(name, kTimerNames[t])) {
-            const long passes = t == T_MATRIX ? c->timed_matrix_calls : c->timed_passes;
+            const long passes = t == T_MATRIX ? c->timed_matrix_calls : t == T_MATRIX_SMH ? c->timed_matrix_smh_calls : c->timed_passes;
             return passes ? (double)c->timers[t].launches / (double)passes : 0.0;
         }
     return -1.0;

@@ -44,6 +44,9 @@
 //               two empty sketches); with -U the union sizes.  Reads only the .hll files (-a and -b are accepted and unused); with -F and
 //               -t -- not combinable with -p, -k, -K, -g, -B, -o, -r, nor with the options of a selection pass -h, -c, -n, -A
 //   -U          with -M: the union estimate U of every pair instead of J
+//   -E <est>    with -M: the estimator behind the cells.  hll (default): the HyperLogLog values above.  smh: the SuperMinHash estimate of
+//               J, (equal buckets of the pair) / m; smh_matches: that count itself, printed as an integer (SELHIP_MEASURE_SMH_JACCARD /
+//               _SMH_MATCHES).  smh and smh_matches read the .smh<m> files too, m = -a bytes / 8: -a must be given, -U is refused
 //   -x          usage
 #include <unistd.h>
 
@@ -169,12 +172,13 @@ static int run_neighbours(const std::string& list_file, int crit, float threshol
 }
 
 // -M: the dense matrix of one list, or of the query list against the database list, written as text in file-list order
-static int run_matrix(const std::string& list_file, const std::string& query_file, const std::string& out_file, bool union_measure,
+// measure: a SELHIP_MEASURE_* code; m: the SuperMinHash buckets to load for the SMH measures, 0 for the HLL ones (only the .hll files)
+static int run_matrix(const std::string& list_file, const std::string& query_file, const std::string& out_file, int measure, unsigned m,
                       int fp_mode, int threads) {
     selhost_dataset* db = nullptr;
     selhost_dataset* qs = nullptr;
-    if (selhost_dataset_load(&db, list_file.c_str(), 0, 0, fp_mode, threads)) { std::cerr << "selection: -M: " << selhost_last_error() << "\n"; return 1; }
-    if (!query_file.empty() && selhost_dataset_load(&qs, query_file.c_str(), 0, 0, fp_mode, threads)) {
+    if (selhost_dataset_load(&db, list_file.c_str(), m, 0, fp_mode, threads)) { std::cerr << "selection: -M: " << selhost_last_error() << "\n"; return 1; }
+    if (!query_file.empty() && selhost_dataset_load(&qs, query_file.c_str(), m, 0, fp_mode, threads)) {
         std::cerr << "selection: -M: cannot read query list '" << query_file << "': " << selhost_last_error() << "\n";
         selhost_dataset_free(db);
         return 1;
@@ -187,7 +191,7 @@ static int run_matrix(const std::string& list_file, const std::string& query_fil
     for (int64_t r = 0; r < n_d; ++r) { col_pos[(size_t)r] = (int32_t)selhost_dataset_order(db, r); col_names[(size_t)col_pos[(size_t)r]] = selhost_dataset_name(db, r); }
     for (int64_t r = 0; r < n_r; ++r) { row_pos[(size_t)r] = (int32_t)selhost_dataset_order(rows, r); row_names[(size_t)row_pos[(size_t)r]] = selhost_dataset_name(rows, r); }
     std::vector<double> values((size_t)n_r * (size_t)n_d);
-    std::vector<uint64_t> no_smh((size_t)std::max<int64_t>(1, std::max(n_d, n_r)), 0);
+    std::vector<uint64_t> no_smh(m ? 0 : (size_t)std::max<int64_t>(1, std::max(n_d, n_r)), 0);
     selhip_ctx* ctx = nullptr;
     int r = selhip_device_count() > 0 ? selhip_ctx_create(&ctx, 0) : SELHIP_E_NODEVICE;
     if (r) {
@@ -197,10 +201,9 @@ static int run_matrix(const std::string& list_file, const std::string& query_fil
     }
     void* d_out = nullptr;
     selhip_ctx_set_fp_mode(ctx, fp_mode);
-    r = selhip_ctx_upload(ctx, selhost_dataset_hll(db), no_smh.data(), selhost_dataset_cards(db), n_d, 1, 14);
-    if (!r && qs) r = selhip_ctx_upload_queries(ctx, selhost_dataset_hll(qs), no_smh.data(), selhost_dataset_cards(qs), n_r);
+    r = selhip_ctx_upload(ctx, selhost_dataset_hll(db), m ? selhost_dataset_aux(db) : no_smh.data(), selhost_dataset_cards(db), n_d, m ? (int)m : 1, 14);
+    if (!r && qs) r = selhip_ctx_upload_queries(ctx, selhost_dataset_hll(qs), m ? selhost_dataset_aux(qs) : no_smh.data(), selhost_dataset_cards(qs), n_r);
     if (!r && !values.empty()) r = selhip_malloc(&d_out, values.size() * sizeof(double));
-    const int measure = union_measure ? SELHIP_MEASURE_UNION : SELHIP_MEASURE_JACCARD;
     if (!r) r = qs ? selhip_ctx_query_matrix(ctx, measure, SELHIP_F64, 0, n_r, d_out, n_r, n_d, n_d, row_pos.data(), col_pos.data())
                    : selhip_ctx_matrix(ctx, measure, SELHIP_F64, 0, n_r, d_out, n_r, n_d, n_d, row_pos.data(), col_pos.data());
     if (!r && !values.empty()) r = selhip_memcpy_d2h(values.data(), d_out, values.size() * sizeof(double));
@@ -224,22 +227,24 @@ int main(int argc, char* argv[]) {
     std::string criterion = "smh_a";
     int threads = 8, n_gpus = 1, mode = SELHIP_MODE_CB_SMH, algo = SELHIP_ALGO_AUTO, fp_mode = SELHIP_FP_FMA;
     long long ooc_block = 0;
-    std::string out_file = "", dump_file = "", query_file = "", pair_file = "", matrix_file = "";
-    bool gpus_given = false, topk_given = false, nbr_given = false, matrix_given = false, union_measure = false;
+    std::string out_file = "", dump_file = "", query_file = "", pair_file = "", matrix_file = "", estimator = "";
+    bool gpus_given = false, topk_given = false, nbr_given = false, matrix_given = false, union_measure = false, aux_given = false, estimator_given = false;
     const char* selection_opt = nullptr;         // the first of -h, -c, -n, -A seen: options of a selection pass, which -M does not run
     long long top_k = 0, nbr_k = 0;
     int c;
-    while ((c = getopt(argc, argv, "xl:b:a:h:c:t:g:nA:F:B:o:r:q:k:K:p:M:U")) != -1) {
+    while ((c = getopt(argc, argv, "xl:b:a:h:c:t:g:nA:F:B:o:r:q:k:K:p:M:UE:")) != -1) {
         switch (c) {
             case 'x': std::cout << "Usage: -l -h -a -b [-c smh_a|hll_a|hll_an|none] [-t threads] [-g gpus] [-n] [-A auto|stream|sig] [-F 0|1] [-B block] [-o file] | -r file\n"
                                    "       -l db_list -q query_list -h -a [-c smh_a|hll_a|hll_an|none] [-n] [-A auto|stream|sig|index] [-F 0|1] [-k best_per_query]   (query-vs-database selection)\n"
                                    "       -l -h -a [-c smh_a|hll_a|hll_an|none] [-n] [-A auto|stream|sig|hashjoin] [-F 0|1] -K best_per_genome   (every genome's best partners, both members of a pair)\n"
                                    "       -l list -p pair_file -h -a [-c smh_a|hll_a|hll_an|none] [-n] [-A auto|stream|sig] [-F 0|1] [-o file]   (only the listed pairs; lines 'path1 path2 ...')\n"
-                                   "       -l list [-q query_list] [-F 0|1] -M out.tsv [-U]   (no selection: the dense Jaccard -- -U: union size -- matrix, file-list order)\n"; return 0;
+                                   "       -l list [-q query_list] [-F 0|1] -M out.tsv [-U]   (no selection: the dense Jaccard -- -U: union size -- matrix, file-list order)\n"
+                                   "       -l list [-q query_list] -M out.tsv -E smh|smh_matches -a bytes   (the same table from the SuperMinHash sketches: equal buckets / m, or their count)\n"; return 0;
             case 'q': query_file = optarg; break;
             case 'p': pair_file = optarg; break;
             case 'M': matrix_file = optarg; matrix_given = true; break;
             case 'U': union_measure = true; break;
+            case 'E': estimator = optarg; estimator_given = true; break;
             case 'k': top_k = std::strtoll(optarg, nullptr, 10); topk_given = true; break;
             case 'K': nbr_k = std::strtoll(optarg, nullptr, 10); nbr_given = true; break;
             case 'B': ooc_block = std::stoll(optarg); break;
@@ -247,7 +252,7 @@ int main(int argc, char* argv[]) {
             case 'r': dump_file = optarg; break;
             case 'l': list_file = optarg; break;
             case 'b': break;
-            case 'a': aux_bytes = std::stoi(optarg); break;
+            case 'a': aux_bytes = std::stoi(optarg); aux_given = true; break;
             case 'h': threshold = std::stof(optarg); if (!selection_opt) selection_opt = "-h"; break;
             case 'c': criterion = optarg; if (!selection_opt) selection_opt = "-c"; break;
             case 't': threads = std::stoi(optarg); break;
@@ -268,8 +273,24 @@ int main(int argc, char* argv[]) {
             return 2;
         }
         if (list_file.empty()) { std::cerr << "selection: -M needs the list of genomes (-l)\n"; return 2; }
-        return run_matrix(list_file, query_file, matrix_file, union_measure, fp_mode, threads);
+        int measure = union_measure ? SELHIP_MEASURE_UNION : SELHIP_MEASURE_JACCARD;
+        unsigned m_smh = 0;
+        if (estimator_given && estimator != "hll") {
+            if (estimator != "smh" && estimator != "smh_matches") {
+                std::cerr << "selection: -E (the estimator of -M): hll, smh or smh_matches, not '" << estimator << "'\n";
+                return 2;
+            }
+            if (union_measure) { std::cerr << "selection: -U (union sizes) is a value of -E hll; -E " << estimator << " has no union size\n"; return 2; }
+            if (!aux_given || aux_bytes / 8 <= 0) {
+                std::cerr << "selection: -E " << estimator << " reads the .smh<m> files: give their size with -a (bytes, 8 per bucket)\n";
+                return 2;
+            }
+            measure = estimator == "smh" ? SELHIP_MEASURE_SMH_JACCARD : SELHIP_MEASURE_SMH_MATCHES;
+            m_smh = (unsigned)aux_bytes / 8;
+        }
+        return run_matrix(list_file, query_file, matrix_file, measure, m_smh, fp_mode, threads);
     }
+    if (estimator_given) { std::cerr << "selection: -E (hll, smh, smh_matches) is an option of -M (the dense similarity matrix)\n"; return 2; }
     if (union_measure) { std::cerr << "selection: -U (union sizes) is an option of -M (the dense similarity matrix)\n"; return 2; }
     if (!pair_file.empty()) {
         // checked before any file is read or device opened

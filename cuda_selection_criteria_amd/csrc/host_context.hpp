@@ -133,8 +133,8 @@ static_assert(kCounterBlocks == kMaxChunks + 1, "common.cuh: counter blocks per 
 constexpr int kMaxAuxP = SELHIP_MAX_AUX_P;   // auxiliary HLL precision accepted by every entry point: aux_fused_kernel counts in 16-bit bins (a bin holds up to 2^p_aux)
 constexpr long long kEnumPairs = 1ll << 26;    // hll_a / hll_an as first criterion: pairs listed per sub-pass (512 MiB of int2)
 
-enum { T_PREP = 0, T_STAGE1, T_HIST, T_SELECT, T_TOTAL, T_SIGBUILD, T_JOIN, T_VERIFY, T_AUX, T_GROUP, T_DENSE, T_TOPK, T_MATRIX, T_COUNT };
-const char* kTimerNames[T_COUNT] = {"prep", "stage1", "hist", "select", "total", "sigbuild", "join", "verify", "aux", "group", "dense", "topk", "matrix"};
+enum { T_PREP = 0, T_STAGE1, T_HIST, T_SELECT, T_TOTAL, T_SIGBUILD, T_JOIN, T_VERIFY, T_AUX, T_GROUP, T_DENSE, T_TOPK, T_MATRIX, T_MATRIX_SMH, T_COUNT };
+const char* kTimerNames[T_COUNT] = {"prep", "stage1", "hist", "select", "total", "sigbuild", "join", "verify", "aux", "group", "dense", "topk", "matrix", "matrix_smh"};
 
 }  // namespace
 
@@ -305,12 +305,18 @@ struct selhip_ctx {
     // dense matrices (selhip_ctx_matrix / _query_matrix; abi_matrix.inc): the validated copies of the caller's positions
     DevBuf<int> mat_row_pos, mat_col_pos;
     int matrix_mirror = 1;              // test switch ("matrix_mirror"): 0 = a self matrix stores no mirrored cells (upper triangle of a slab only)
+    // the SuperMinHash measures (kernel_matrix_smh.cuh): "matrix_smh_form" 1 = a self matrix computes every pair once and mirrors it,
+    // 3 = it computes the whole square (a measurement switch; "matrix_mirror" = 0 takes the once-per-pair form whatever this says);
+    // matrix_smh_path_used = the kernel of the last such call: 1 the fast path (matrix_smh_fast), 0 the generic one, -1 none yet
+    int matrix_smh_form = 1;
+    int matrix_smh_path_used = -1;
 
     int timing = 0;                     // 0 off, 1 every kernel scope, 2 dominant stage-1 kernel only
     int dominant_timer = T_STAGE1;
     int timed_kernel = 0;               // timing level 2 keeps the events of: 0 = the stage-1 kernel (join / stream), 1 = stage 2a ("timed_kernel")
     long timed_passes = 0;
     long timed_matrix_calls = 0;        // matrix calls under timing: the divisor of "matrix" alone (the passes' per-pass averages are not theirs to dilute)
+    long timed_matrix_smh_calls = 0;    // ... and those of the SuperMinHash measures: the divisor of "matrix_smh"
     int last_attempts = 0;              // enqueues the last finished run needed (1 = nothing overflowed)
     KernelTimer timers[T_COUNT];
 };

@@ -126,8 +126,9 @@ PairsDirectShape pairs_direct_shape(u64 n_pairs) {
 // the 8 XCD slots round robin as in dense_select_kernel -- unit u: slot u % 8, j = u / 8 -> row tile j % n_tiles of span 8 (j / n_tiles) + slot
 constexpr int kMatrixSpan = kWave;
 struct MatrixUnits { long long n_tiles, n_spans, n_units; };
-constexpr MatrixUnits matrix_units(long long n_rows, long long n_cols) {
-    const long long n_tiles = (n_rows + kWavesPerBlock - 1) / kWavesPerBlock, n_spans = (n_cols + kMatrixSpan - 1) / kMatrixSpan;
+// (tile_rows: the rows of a unit -- four, one per wave, for matrix_kernel; 4 Q, Q per wave, for the fast SuperMinHash kernel)
+constexpr MatrixUnits matrix_units(long long n_rows, long long n_cols, int tile_rows = kWavesPerBlock) {
+    const long long n_tiles = (n_rows + tile_rows - 1) / tile_rows, n_spans = (n_cols + kMatrixSpan - 1) / kMatrixSpan;
     return {n_tiles, n_spans, 8 * n_tiles * ((n_spans + 7) / 8)};
 }
 // a self matrix computes every pair once: row i of the slab [r0, r1) computes the columns [0, r0) u [i, n) ...

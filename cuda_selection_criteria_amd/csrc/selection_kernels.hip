@@ -30,6 +30,8 @@
 //                       histograms into an LDS tile and the estimator in one launch
 //   kernel_matrix.cuh   matrix_kernel: the union size or the Jaccard estimate of every pair as a dense array (the middle of
 //                       dense_select_kernel over a rectangle, typed and mirrored stores; selhip_ctx_matrix / _query_matrix)
+//   kernel_matrix_smh.cuh  matrix_smh_kernel / matrix_smh_generic_kernel: the SuperMinHash bucket-match count, or count / m, of every
+//                       pair as a dense array (query rows in VGPRs, candidate rows streamed past them; the same entry points)
 //   kernel_topk.cuh     top-k of a query pass: records grouped by query (count, scan, scatter), radix select of each query's K best,
 //                       bitonic sort of the winners
 //   kernel_nbr.cuh      top-k of an all-pairs pass: every record counted and scattered for both of its genomes, then the same select
@@ -80,6 +82,7 @@
 
 #include "host_plan.hpp"         // host decisions that are plain arithmetic: build shape, pass plan, criterion constants, overflow rule
 #include "kernel_matrix.cuh"     // (behind host_plan.hpp: the kernel reads the unit, slab and mirror rules written there)
+#include "kernel_matrix_smh.cuh" // (behind kernel_matrix.cuh: MatrixOut)
 #include "host_context.hpp"      // struct selhip_ctx, device buffers (signature sets, bit planes, counter sets), timers, helpers
 #include "host_pass.hpp"         // pass scheduler: dispatch of every stage, chunk lanes, scratch sizing
 #include "host_pairs.hpp"        // pair-list passes: the chain behind selhip_ctx_run_pairs

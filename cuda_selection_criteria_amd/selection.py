@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (ALGO_AUTO, BANDING_CPU, CRIT_HLL_A, CRIT_HLL_AN, CRIT_HLL_A_SMH_A, CRIT_NONE, CRIT_SMH_A, F32, F64, FP_FMA,
-                   MEASURE_JACCARD, MEASURE_UNION, MODE_CB_SMH, Pair, check, hip_lib, host_lib)
+                   MEASURE_JACCARD, MEASURE_SMH_JACCARD, MEASURE_SMH_MATCHES, MEASURE_UNION, MODE_CB_SMH, Pair, check, hip_lib, host_lib)
 
 # layout of selhip_pair_t {int32 i, k; double jaccard}
 PAIR_DTYPE = np.dtype([("i", "<i4"), ("k", "<i4"), ("jaccard", "<f8")], align=True)
@@ -398,9 +398,7 @@ class Selector:
     # -- dense matrices -----------------------------------------------------------------------------
     def _matrix(self, query: bool, measure, dtype, rows, row_pos, col_pos, out):
         import torch
-        code = {"jaccard": MEASURE_JACCARD, "union": MEASURE_UNION}.get(measure, measure)
-        if code not in (MEASURE_JACCARD, MEASURE_UNION):
-            raise ValueError("measure: 'jaccard' or 'union'")
+        code = measure_code(measure)
         if dtype not in (torch.float64, torch.float32):
             raise ValueError("dtype: torch.float64 or torch.float32")
         if query and self.n_q is None:
@@ -426,8 +424,9 @@ class Selector:
 
     def matrix(self, measure="jaccard", dtype=None, rows: Optional[Tuple[int, int]] = None, row_pos=None, col_pos=None, out=None):
         """the similarity of every pair of the context's sketches as a torch tensor on the device (selhip_ctx_matrix): measure
-        "jaccard" (J of the passes, bit for bit; exactly 1.0 on the diagonal; NaN for two empty sketches) or "union" (the union
-        estimate U, also on the diagonal), dtype torch.float64 (default) or torch.float32.  rows = (r0, r1): only that slab of rows.
+        "jaccard" (J of the passes, bit for bit; exactly 1.0 on the diagonal; NaN for two empty sketches), "union" (the union
+        estimate U, also on the diagonal), "smh_matches" (the number of equal SuperMinHash buckets of the pair, 0 .. m) or "smh_jaccard"
+        (that count / m: the SuperMinHash estimate of J; both from the bucket rows alone, whatever p_hll), dtype torch.float64 (default) or torch.float32.  rows = (r0, r1): only that slab of rows.
         row_pos / col_pos: host int32 arrays indexed by rank -- the cell of rank-row i and rank-column k goes to
         out[row_pos[i], col_pos[k]] (defaults i - r0 and k).  out: a caller's 2-D tensor (stride(1) == 1; stride(0) is its leading
         dimension), written in place and returned; cells no (row, column) maps to keep their content"""
@@ -523,6 +522,28 @@ def select_from_filelist(list_file: str, tau: float, aux_bytes: int, mode: int =
     return format_lines(ds.names, pairs)
 
 
+MEASURES = {"jaccard": MEASURE_JACCARD, "union": MEASURE_UNION, "smh_matches": MEASURE_SMH_MATCHES, "smh_jaccard": MEASURE_SMH_JACCARD}
+SMH_MEASURES = (MEASURE_SMH_MATCHES, MEASURE_SMH_JACCARD)
+
+
+def measure_code(measure) -> int:
+    """the SELHIP_MEASURE_* code of a measure given by name or by code; ValueError for anything else"""
+    code = MEASURES.get(measure) if isinstance(measure, str) else measure
+    if isinstance(code, bool) or not isinstance(code, (int, np.integer)) or code not in MEASURES.values():
+        raise ValueError("measure: 'jaccard', 'union', 'smh_matches' or 'smh_jaccard'")
+    return int(code)
+
+
+def _matrix_buckets(measure, aux_bytes: int) -> int:
+    """m of the .smh<m> files a matrix of this measure reads: aux_bytes / 8 for the SuperMinHash measures, 0 (none) for the HLL ones"""
+    if measure_code(measure) not in SMH_MEASURES:
+        return 0
+    m = int(aux_bytes) // 8                                                    # 8 bytes per bucket, as `-a` of the selection passes
+    if m <= 0:
+        raise ValueError("measure 'smh_matches' / 'smh_jaccard' reads the .smh<m> files: aux_bytes (8 m) must be given")
+    return m
+
+
 def _inverse(order: np.ndarray) -> np.ndarray:
     inv = np.empty(len(order), dtype=np.int32)
     inv[order] = np.arange(len(order), dtype=np.int32)
@@ -531,12 +552,14 @@ def _inverse(order: np.ndarray) -> np.ndarray:
 
 def matrix_from_filelist(list_file: str, aux_bytes: int = 0, measure="jaccard", dtype=None, fp_mode: int = FP_FMA, device: int = 0):
     """(names, tensor): the n x n matrix of the genomes of list_file with rows and columns in FILE-LIST order.  The sketches are loaded
-    and sorted as for a selection (only the .hll files are read; aux_bytes is accepted for symmetry with the other front ends), and the
-    ranks' lines in the list go to the library as both position arrays: the matrix is written in place, nothing is gathered afterwards"""
-    ds = load_dataset(list_file, 0, 0, fp_mode)
+    and sorted as for a selection, and the ranks' lines in the list go to the library as both position arrays: the matrix is written in
+    place, nothing is gathered afterwards.  The HLL measures read only the .hll files (aux_bytes is accepted for symmetry with the other
+    front ends); "smh_matches" / "smh_jaccard" also read the .smh<m> files, m = aux_bytes // 8 (aux_bytes == 0: ValueError)"""
+    m_smh = _matrix_buckets(measure, aux_bytes)
+    ds = load_dataset(list_file, m_smh, 0, fp_mode)
     n = len(ds.names)
     with Selector(device, fp_mode) as sel:
-        sel.upload(ds.hll, np.zeros((n, 1), dtype=np.uint64), ds.cards)
+        sel.upload(ds.hll, ds.aux if m_smh else np.zeros((n, 1), dtype=np.uint64), ds.cards)
         m = sel.matrix(measure, dtype, row_pos=ds.order, col_pos=ds.order)
     names = [ds.names[r] for r in _inverse(ds.order)]
     return names, m
@@ -544,12 +567,14 @@ def matrix_from_filelist(list_file: str, aux_bytes: int = 0, measure="jaccard", 
 
 def query_matrix_from_filelists(query_list: str, db_list: str, aux_bytes: int = 0, measure="jaccard", dtype=None, fp_mode: int = FP_FMA,
                                 device: int = 0):
-    """(query names, database names, tensor): the n_Q x n_D matrix of the two lists, rows and columns in the order of their files"""
-    qs = load_dataset(query_list, 0, 0, fp_mode)
-    db = load_dataset(db_list, 0, 0, fp_mode)
+    """(query names, database names, tensor): the n_Q x n_D matrix of the two lists, rows and columns in the order of their files
+    (aux_bytes as for matrix_from_filelist)"""
+    m_smh = _matrix_buckets(measure, aux_bytes)
+    qs = load_dataset(query_list, m_smh, 0, fp_mode)
+    db = load_dataset(db_list, m_smh, 0, fp_mode)
     with Selector(device, fp_mode) as sel:
-        sel.upload(db.hll, np.zeros((len(db.names), 1), dtype=np.uint64), db.cards)
-        sel.upload_queries(qs.hll, np.zeros((len(qs.names), 1), dtype=np.uint64), qs.cards)
+        sel.upload(db.hll, db.aux if m_smh else np.zeros((len(db.names), 1), dtype=np.uint64), db.cards)
+        sel.upload_queries(qs.hll, qs.aux if m_smh else np.zeros((len(qs.names), 1), dtype=np.uint64), qs.cards)
         m = sel.query_matrix(measure, dtype, row_pos=qs.order, col_pos=db.order)
     return [qs.names[r] for r in _inverse(qs.order)], [db.names[r] for r in _inverse(db.order)], m
 

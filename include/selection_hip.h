@@ -217,7 +217,9 @@ int selhip_ctx_set_param(selhip_ctx* ctx, const char* name, int value);
  * "dense_route_used" (SELHIP_CRIT_NONE: the route of the last such pass, 1 = the fused kernel, 0 = the list route; -1 = none yet),
  * "query_topk", "query_topk_lds_cap" (top-k of the query passes, section 2b),
  * "allpairs_topk" (the current k of selhip_ctx_set_allpairs_topk, 0 = off),
- * "pairs_route_used" (stage 1 of the last pair-list pass, section 2e) */
+ * "pairs_route_used" (stage 1 of the last pair-list pass, section 2e),
+ * "matrix_smh_path_used" (the kernel of the last matrix call with a SuperMinHash measure, section 2f: 1 = the register-tile kernel
+ * of m = 128, 256, 512 or 1024 buckets, 0 = the generic kernel of every other m; -1 = none yet) */
 int selhip_ctx_get_param(const selhip_ctx* ctx, const char* name, int* value);
 /* Stage 2 grouping (default on): the pairs that reach the HLL-14 stage are bucketed by query row (counting sort) so
  * that waves running side by side on one XCD share their query row in L2.  0 = off (same kernel, list as produced). */
@@ -324,7 +326,8 @@ int selhip_ctx_set_allpairs_topk(selhip_ctx* ctx, int k);
  * last end of the pass's join launches (chunk lanes run them side by side).  <0 if never launched.
  * "topk" is also the cut of an all-pairs pass with selhip_ctx_set_allpairs_topk (above), again outside "total".
  * "matrix" is the kernel of a dense matrix (section 2f), averaged over the MATRIX CALLS since the last reset: they are counted apart
- * from the passes, so a matrix call changes no other name's per-pass figure.
+ * from the passes, so a matrix call changes no other name's per-pass figure.  "matrix_smh" is the kernel of a matrix call with a
+ * SuperMinHash measure, averaged over THOSE calls: "matrix" stays the HLL kernel's figure and count.
  * selhip_ctx_kernel_launches: launches of that kernel per pass. */
 double selhip_ctx_kernel_ms(const selhip_ctx* ctx, const char* name);
 double selhip_ctx_kernel_launches(const selhip_ctx* ctx, const char* name);
@@ -490,6 +493,14 @@ int selhip_ctx_run_pairs_async(selhip_ctx* ctx, const selhip_int2_t* d_pairs, in
  *       truncated cardinalities) for every pair without exception: two empty sketches give NaN, and the matrix holds that NaN.
  *     On the diagonal of a self matrix UNION stores U(i, i), computed like any cell; JACCARD stores exactly 1.0.  dtype SELHIP_F64
  *     carries the bits the passes' records carry, SELHIP_F32 is (float) of that value.  A self matrix is bit-symmetric.
+ *     Two more measures read the OTHER sketch of every genome, its m SuperMinHash buckets (aux, u64 [n][m]; components (j << 32) | r):
+ *       c(a, b) = #{ j < m : aux_a[j] == aux_b[j] }, compared on the full 64 bits -- buckets that differ in one dword only are unequal;
+ *       SELHIP_MEASURE_SMH_MATCHES stores c as a number (0, 1, ..., m); SELHIP_MEASURE_SMH_JACCARD stores (double)c / (double)m, the
+ *       SuperMinHash estimate of J (what `mash triangle` prints from such sketches).  Both are exact in SELHIP_F64 and, for c, in SELHIP_F32.
+ *     No case is special: the diagonal of a self matrix is m (1.0), two empty sketches -- every bucket UINT64_MAX -- give m (1.0) as
+ *     well, and the matrix is bit-symmetric.  These measures need the bucket rows alone (for a query matrix the queries' too, same m):
+ *     any m > 0 and any p_hll that upload / attach accept, bit planes or none; aux is read in place, as uploaded or attached.
+ *     Everything below holds for them unchanged, except the p_hll = 14 rule and the timer name ("matrix_smh").
  *     selhip_ctx_matrix: rows [r0, r1) of the context's sketches against all n of them; selhip_ctx_query_matrix: rows [r0, r1) of the
  *     attached queries (section 2b) against the n sketches of the database.  Ranks are those of the sets as uploaded (the cells do
  *     not depend on the order).
@@ -502,8 +513,8 @@ int selhip_ctx_run_pairs_async(selhip_ctx* ctx, const selhip_int2_t* d_pairs, in
  *     the message -- and only the checked copies reach the device.  Two rows (columns) sent to the same position is not an error:
  *     which one lands there is unspecified.  Cells of out_dev that no (row, column) of the call maps to are not written.
  *     SELHIP_E_BADARG also for: ld < out_cols, r0 > r1 or a range outside the set, a NULL or misaligned out_dev with cells to write, an
- *     unknown measure or dtype, a query matrix without attached queries, and -- the rule of SELHIP_CRIT_NONE -- sketches with
- *     p_hll != 14 or without resident bit planes ("hist_algo" 0).  n == 0 or r0 == r1: SELHIP_OK, nothing is written
+ *     unknown measure or dtype, a query matrix without attached queries, and -- for the two HLL measures, the rule of
+ *     SELHIP_CRIT_NONE -- sketches with p_hll != 14 or without resident bit planes ("hist_algo" 0).  n == 0 or r0 == r1: SELHIP_OK, nothing is written
  *     (the arguments above are checked all the same, except that out_dev may then be NULL and no position is read).
  *     SELHIP_E_STATE while a pass is pending.
  *     The call runs on the context's stream and returns when the matrix is complete.  It leaves the result list, result_count, the
@@ -512,6 +523,8 @@ int selhip_ctx_run_pairs_async(selhip_ctx* ctx, const selhip_int2_t* d_pairs, in
  * --------------------------------------------------------------------------------------------------- */
 #define SELHIP_MEASURE_JACCARD  0
 #define SELHIP_MEASURE_UNION    1
+#define SELHIP_MEASURE_SMH_MATCHES 16
+#define SELHIP_MEASURE_SMH_JACCARD 17
 #define SELHIP_F64              0
 #define SELHIP_F32              1
 int selhip_ctx_matrix(selhip_ctx* ctx, int measure, int dtype, int64_t r0, int64_t r1, void* out_dev,
@@ -538,7 +551,8 @@ int selhip_hll_union_hist_planes(const uint32_t* d_planes, const uint8_t* d_gmax
                                  uint32_t* d_counts, void* hip_stream);
 /* Ertl-MLE of n histograms: d_est[j] = ertl_ml_estimate(d_counts[j], p, 64-p, 1e-2). */
 int selhip_ertl_estimate(const uint32_t* d_counts, int64_t n, int p, int fp_mode, double* d_est, void* hip_stream);
-/* bucket-match counts (the by-product the north_star mentions): d_matches[j] = #{b : aux_x[b]==aux_y[b]} */
+/* bucket-match counts of an explicit pair list, one lane per pair: d_matches[j] = #{b : aux_x[b]==aux_y[b]}.  The same count of EVERY
+ * pair as a dense array is SELHIP_MEASURE_SMH_MATCHES of section 2f; this entry stays as the independent check of it. */
 int selhip_smh_match_counts(const uint64_t* d_aux, int m, const selhip_int2_t* d_pairs, int64_t n_pairs,
                             int32_t* d_matches, void* hip_stream);
 
