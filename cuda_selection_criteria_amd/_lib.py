@@ -42,7 +42,7 @@ class Synth(C.Structure):
 MODE_SMH, MODE_CB_SMH = 0, 1
 ALGO_AUTO, ALGO_STREAM, ALGO_SIG, ALGO_HASHJOIN, ALGO_INDEX = 0, 1, 2, 3, 4    # ALGO_INDEX: query passes only
 FP_STRICT, FP_FMA = 0, 1
-CRIT_SMH_A, CRIT_HLL_A, CRIT_HLL_AN, CRIT_HLL_A_SMH_A, CRIT_NONE = 0, 1, 2, 3, 4
+CRIT_SMH_A, CRIT_HLL_A, CRIT_HLL_AN, CRIT_HLL_A_SMH_A, CRIT_NONE, CRIT_SMH_C = 0, 1, 2, 3, 4, 5
 MEASURE_JACCARD, MEASURE_UNION = 0, 1  # SELHIP_MEASURE_*: what a dense matrix stores (Selector.matrix)
 MEASURE_SMH_MATCHES, MEASURE_SMH_JACCARD = 16, 17   # ... from the SuperMinHash rows: equal buckets of the pair, and that count / m
 F64, F32 = 0, 1                        # SELHIP_F64 / SELHIP_F32: its element type
@@ -73,6 +73,7 @@ HIP_SYMBOLS = {
     "selhip_ctx_upload_aux_hll": (_i, [_vp, _vp, _i]),
     "selhip_ctx_attach_aux_hll": (_i, [_vp, _vp, _i]),
     "selhip_ctx_set_criterion": (_i, [_vp, _i]),
+    "selhip_ctx_set_min_matches": (_i, [_vp, _i]),
     "selhip_hll_cards": (_i, [_vp, _vp, _i64, _i, _vp]),
     "selhip_ctx_get_cards": (_i, [_vp, _vp]),
     "selhip_ctx_run": (_i, [_vp, _i, _i, C.c_float, _i, _i, _i64, _i64]),

@@ -236,6 +236,7 @@ int selhip_ctx_get_param(const selhip_ctx* c, const char* name, int* value) {
     if (!std::strcmp(name, "join_form_used"))   { *value = c->join_form_used; return SELHIP_OK; }      // kernel FORM of the last LDS-tile join (3 = bit-sliced)
     if (!std::strcmp(name, "chunks"))           { *value = c->n_chunks_last; return SELHIP_OK; }
     if (!std::strcmp(name, "dense_route_used")) { *value = c->dense_route_used; return SELHIP_OK; }         // SELHIP_CRIT_NONE: 1 fused kernel, 0 list route, -1 none yet
+    if (!std::strcmp(name, "smhc_path_used"))   { *value = c->smhc_path_used; return SELHIP_OK; }           // SELHIP_CRIT_SMH_C: 1 fast kernel, 0 generic, -1 none yet
     if (!std::strcmp(name, "matrix_mirror"))    { *value = c->matrix_mirror; return SELHIP_OK; }
     if (!std::strcmp(name, "matrix_smh_form"))  { *value = c->matrix_smh_form; return SELHIP_OK; }
     if (!std::strcmp(name, "matrix_smh_path_used")) { *value = c->matrix_smh_path_used; return SELHIP_OK; }   // kernel of the last SuperMinHash matrix: 1 fast, 0 generic
@@ -275,8 +276,15 @@ int selhip_ctx_set_pipeline(selhip_ctx* c, int chunks) {
 }
 
 int selhip_ctx_set_criterion(selhip_ctx* c, int criterion) {
-    if (!c || criterion < SELHIP_CRIT_SMH_A || criterion > SELHIP_CRIT_NONE) return SELHIP_E_BADARG;
+    if (!c || criterion < SELHIP_CRIT_SMH_A || criterion > SELHIP_CRIT_SMH_C) return SELHIP_E_BADARG;
     c->criterion = criterion;
+    return SELHIP_OK;
+}
+
+int selhip_ctx_set_min_matches(selhip_ctx* c, int c_min) {
+    if (!c) return SELHIP_E_BADARG;
+    if (c_min < 1) { set_err(&c->err, "min_matches must be >= 1 (got %d)", c_min); return SELHIP_E_BADARG; }
+    c->min_matches = c_min;
     return SELHIP_OK;
 }
 
@@ -408,6 +416,7 @@ int selhip_ctx_get_cards(selhip_ctx* c, double* h_out) {
 int selhip_ctx_run_async(selhip_ctx* c, int mode, int algo, float tau_f, int n_rows, int n_bands,
                          int64_t row_begin, int64_t row_end) {
     if (!c) return SELHIP_E_BADARG;
+    if (c->criterion == SELHIP_CRIT_SMH_C) { const int rc = accept_count(c); if (rc) return rc; }
     if (!c->d_aux && c->n) { set_err(&c->err, "run before upload/attach"); return SELHIP_E_STATE; }
     if (mode != SELHIP_MODE_SMH && mode != SELHIP_MODE_CB_SMH) { set_err(&c->err, "bad mode %d", mode); return SELHIP_E_BADARG; }
     if (algo != SELHIP_ALGO_AUTO && algo != SELHIP_ALGO_STREAM && algo != SELHIP_ALGO_SIG && algo != SELHIP_ALGO_HASHJOIN) { set_err(&c->err, "bad algo %d", algo); return SELHIP_E_BADARG; }
@@ -417,7 +426,7 @@ int selhip_ctx_run_async(selhip_ctx* c, int mode, int algo, float tau_f, int n_r
     }
     if (c->criterion == SELHIP_CRIT_NONE) { const int rc = accept_dense(c); if (rc) return rc; }
     const PassPlan plan = pass_plan(c->criterion, algo, c->m, n_rows, n_bands);
-    if (plan.smh && (n_rows <= 0 || n_bands <= 0 || (long long)n_rows * n_bands != c->m)) {
+    if (plan.smh && !plan.count && (n_rows <= 0 || n_bands <= 0 || (long long)n_rows * n_bands != c->m)) {
         // criteria_sketch.hpp:67-70: the reference prints an error and selects nothing; the ABI reports it
         set_err(&c->err, "n_rows*n_bands (%d*%d) != m (%d)", n_rows, n_bands, c->m);
         return SELHIP_E_BADARG;
@@ -478,7 +487,7 @@ int selhip_ctx_finish(selhip_ctx* c) {
             const PassCounters& q = c->h_pc[k];
             pc.n_survivors += q.n_survivors; pc.n_candidates += q.n_candidates; pc.n_aux_in += q.n_aux_in; pc.n_final += q.n_final;
             // the 16-bit join's list is kAppendSegs equal slices: it overflows when its fullest slice does
-            const u64 worst = std::max(std::max(std::max(q.n_survivors, q.n_candidates), q.n_pre_segmax * (u64)kAppendSegs), c->criterion != SELHIP_CRIT_SMH_A ? q.n_final : 0);
+            const u64 worst = std::max(std::max(std::max(q.n_survivors, q.n_candidates), q.n_pre_segmax * (u64)kAppendSegs), !survivors_final(c->criterion) ? q.n_final : 0);
             if (worst > slice) { surv_cap = std::max(surv_cap, grown(worst) * (size_t)chunks); grow = true; }
             // (n_aux_in is zeroed before every enumeration sub-pass, so what arrives here is the LAST sub-pass's count only: it proves
             //  nothing about the others.  The guarantee is the host-side bound in enqueue_pass -- every sub-pass lists at most
@@ -529,7 +538,7 @@ int selhip_ctx_stats(const selhip_ctx* c, int64_t stats[4]) {
     if (!c || !stats) return SELHIP_E_BADARG;
     if (!c->have_run) return SELHIP_E_STATE;
     stats[0] = (int64_t)c->last.n_evaluated;
-    stats[1] = (int64_t)(c->criterion == SELHIP_CRIT_SMH_A ? c->last.n_survivors : c->last.n_final);
+    stats[1] = (int64_t)(survivors_final(c->criterion) ? c->last.n_survivors : c->last.n_final);
     stats[2] = (int64_t)c->last.n_results;
     stats[3] = (int64_t)(c->last.n_candidates ? c->last.n_candidates : c->last.n_survivors);
     return SELHIP_OK;

@@ -34,20 +34,22 @@ int selhip_ctx_run_pairs_async(selhip_ctx* c, const selhip_int2_t* d_pairs, int6
         c->dense_route_used = route;
         if (rc) return rc;
     }
+    if (c->criterion == SELHIP_CRIT_SMH_C) { const int rc = accept_count(c); if (rc) return rc; }
+    // (which stage 1 the criterion has: pass_plan's answer; the route below replaces its choice among the smh_a algorithms)
     PassPlan plan;
-    plan.smh = c->criterion == SELHIP_CRIT_SMH_A || c->criterion == SELHIP_CRIT_HLL_A_SMH_A;
-    if (plan.smh && (n_rows <= 0 || n_bands <= 0 || (long long)n_rows * n_bands != c->m)) {
+    { const PassPlan pp = pass_plan(c->criterion, SELHIP_ALGO_STREAM, c->m, n_rows, n_bands); plan.smh = pp.smh; plan.count = pp.count; }
+    if (plan.smh && !plan.count && (n_rows <= 0 || n_bands <= 0 || (long long)n_rows * n_bands != c->m)) {
         set_err(&c->err, "n_rows*n_bands (%d*%d) != m (%d)", n_rows, n_bands, c->m);
         return SELHIP_E_BADARG;
     }
-    if (plan.smh && algo == SELHIP_ALGO_SIG && !sig_supported(n_rows, n_bands)) {
+    if (plan.smh && !plan.count && algo == SELHIP_ALGO_SIG && !sig_supported(n_rows, n_bands)) {
         set_err(&c->err, "ALGO_SIG needs power-of-two rows and 8..128 bands (got %d x %d)", n_rows, n_bands);
         return SELHIP_E_BADARG;
     }
     HIPCHK(&c->err, hipSetDevice(c->device));
     // (the route first: the cache key asks join_sliced, which reads the algorithm of the pass -- SIG and STREAM are alike to it)
     c->algo = SELHIP_ALGO_SIG;
-    const int route = pairs_route(c, plan.smh, algo, n_rows, n_bands, n_pairs);
+    const int route = plan.count ? 0 : pairs_route(c, plan.smh, algo, n_rows, n_bands, n_pairs);      // (the count has the direct route only)
     plan.use_sig = route == 1;
     c->mode = mode; c->algo = route == 1 ? SELHIP_ALGO_SIG : SELHIP_ALGO_STREAM; c->tau_f = tau_f; c->n_rows = n_rows; c->n_bands = n_bands; c->plan = plan;
     c->row_begin = 0; c->row_end = c->n;

@@ -99,6 +99,7 @@ int selhip_ctx_run_queries(selhip_ctx* c, int mode, int algo, float tau_f, int n
     if (c->pending) { set_err(&c->err, "a pass is still pending (selhip_ctx_finish)"); return SELHIP_E_STATE; }
     if (mode != SELHIP_MODE_SMH && mode != SELHIP_MODE_CB_SMH) { set_err(&c->err, "bad mode %d", mode); return SELHIP_E_BADARG; }
     if (c->criterion == SELHIP_CRIT_NONE) { const int rc = accept_dense(c); if (rc) return rc; }
+    if (c->criterion == SELHIP_CRIT_SMH_C) { const int rc = accept_count(c); if (rc) return rc; }
     if (aux_criterion(c->criterion)) {
         // the auxiliary HLL sketches of both sets, with one precision
         if ((c->n && !c->d_aux_hll) || (q.n && !q.d_aux_hll)) {
@@ -114,8 +115,8 @@ int selhip_ctx_run_queries(selhip_ctx* c, int mode, int algo, float tau_f, int n
     const PassPlan plan = pass_plan(c->criterion, algo, c->m, n_rows, n_bands);
     const bool smh = plan.smh;
     if (algo != SELHIP_ALGO_AUTO && algo != SELHIP_ALGO_STREAM && algo != SELHIP_ALGO_SIG && algo != SELHIP_ALGO_HASHJOIN && algo != SELHIP_ALGO_INDEX) { set_err(&c->err, "bad algo %d", algo); return SELHIP_E_BADARG; }
-    if (smh) {
-        // (hll_a / hll_an alone read neither n_rows / n_bands nor algo, as in selhip_ctx_run_async)
+    if (smh && !plan.count) {
+        // (hll_a / hll_an alone and smh_c read neither n_rows / n_bands nor algo, as in selhip_ctx_run_async)
         if (algo == SELHIP_ALGO_HASHJOIN) { set_err(&c->err, "query passes have no ALGO_HASHJOIN; use AUTO, SIG, STREAM or INDEX"); return SELHIP_E_BADARG; }
         if (n_rows <= 0 || n_bands <= 0 || (long long)n_rows * n_bands != c->m) {
             set_err(&c->err, "n_rows*n_bands (%d*%d) != m (%d)", n_rows, n_bands, c->m);
@@ -145,8 +146,8 @@ int selhip_ctx_run_queries(selhip_ctx* c, int mode, int algo, float tau_f, int n
         if (pc.unsorted) { set_err(&c->err, "database or query cards are not in ascending order"); return SELHIP_E_BADARG; }
         bool grow = false;
         // (n_pre: the join's list; n_survivors: the survivor list; n_final: what passed the auxiliary criterion)
-        const u64 worst = std::max(std::max(pc.n_pre, pc.n_survivors), c->criterion != SELHIP_CRIT_SMH_A ? pc.n_final : 0);
-        if ((smh && (worst > q.surv.cap || worst > q.cand.cap)) || (c->criterion != SELHIP_CRIT_SMH_A && worst > q.fin.cap)) {
+        const u64 worst = std::max(std::max(pc.n_pre, pc.n_survivors), !survivors_final(c->criterion) ? pc.n_final : 0);
+        if ((smh && (worst > q.surv.cap || worst > q.cand.cap)) || (!survivors_final(c->criterion) && worst > q.fin.cap)) {
             cap = std::max(cap, grown(worst));
             grow = true;
         }

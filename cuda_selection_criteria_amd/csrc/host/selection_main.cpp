@@ -11,6 +11,9 @@
 //               hll_an as in the CPU program (src/selection.cpp:122-227: auxiliary HLL p = ctz(aux_bytes), file .hll_<p>), or
 //               none: no criterion in front of the Jaccard test -- every pair inside the CB bound (with -n: every pair); reads
 //               only the .hll files, -a is not needed (SELHIP_CRIT_NONE: the reference README's "CB criterion" / "no criterion" lines)
+//               smh_c: at least -C <c_min> of the m = -a bytes / 8 SuperMinHash buckets equal (SELHIP_CRIT_SMH_C: the SuperMinHash
+//               estimate c / m >= c_min / m, exhaustive, no banding); -a and -C must be given; with -l, -q, -p, -k, -K, -n, not with -g or -B
+//   -C <c_min>  the count threshold of -c smh_c (1 .. m), an option of that criterion alone
 //   -t <n>      host threads for loading sketches (selection.cpp:97)
 //   -g <n>      number of GPUs to shard the pair space over (default 1; any criterion); selected pairs gathered over RCCL/xGMI
 //   -n          no CB pruning ("smh_a" mode of experiments/src/time_smh.cpp:229-257)
@@ -64,12 +67,13 @@
 // -q: the query list against the database list (-l), both loaded and sorted by cardinality; text on stdout.  criterion: "smh_a"
 // (m = aux_bytes / 8 buckets), "hll_a" / "hll_an" (auxiliary HLL p = ctz(aux_bytes), as the all-pairs mode) or "none" (.hll files only)
 static int run_queries(const std::string& query_file, const std::string& db_file, const std::string& criterion, float threshold,
-                       int aux_bytes, int mode, int algo, int fp_mode, int threads, int top_k) {
+                       int aux_bytes, int mode, int algo, int fp_mode, int threads, int top_k, int min_matches) {
     const bool smh = criterion == "smh_a";
+    const bool smh_c = criterion == "smh_c";
     const bool none = criterion == "none";
-    const int crit = smh ? SELHIP_CRIT_SMH_A : none ? SELHIP_CRIT_NONE : criterion == "hll_a" ? SELHIP_CRIT_HLL_A : SELHIP_CRIT_HLL_AN;
-    const unsigned m = smh ? (unsigned)aux_bytes / 8 : 0;
-    const unsigned p_aux = smh || none ? 0 : (unsigned)__builtin_ctz(aux_bytes ? aux_bytes : 1);
+    const int crit = smh ? SELHIP_CRIT_SMH_A : smh_c ? SELHIP_CRIT_SMH_C : none ? SELHIP_CRIT_NONE : criterion == "hll_a" ? SELHIP_CRIT_HLL_A : SELHIP_CRIT_HLL_AN;
+    const unsigned m = smh || smh_c ? (unsigned)aux_bytes / 8 : 0;
+    const unsigned p_aux = smh || smh_c || none ? 0 : (unsigned)__builtin_ctz(aux_bytes ? aux_bytes : 1);
     // (smh_a keeps the messages it always had; an hll criterion names the mode and the criterion)
     const std::string what = smh ? "" : "selection: -q -c " + criterion + ": ";
     selhost_dataset* db = nullptr;
@@ -105,6 +109,7 @@ static int run_queries(const std::string& query_file, const std::string& db_file
     if (!r && p_aux) r = selhip_ctx_upload_aux_hll(ctx, selhost_dataset_aux_hll(db), (int)p_aux);
     if (!r && p_aux) r = selhip_ctx_upload_queries_aux_hll(ctx, selhost_dataset_aux_hll(qs), (int)p_aux);
     if (!r) r = selhip_ctx_set_criterion(ctx, crit);
+    if (!r && smh_c) r = selhip_ctx_set_min_matches(ctx, min_matches);
     if (!r && top_k) r = selhip_ctx_set_query_topk(ctx, top_k);
     if (!r) r = selhip_ctx_run_queries(ctx, mode, algo, threshold, n_rows, n_bands);
     if (!r) {
@@ -129,9 +134,10 @@ static int run_queries(const std::string& query_file, const std::string& db_file
 
 // -K: one all-pairs pass over the list with the device-side cut on; text on stdout, one line per kept (owner, partner) record
 static int run_neighbours(const std::string& list_file, int crit, float threshold, int aux_bytes, int mode, int algo, int fp_mode,
-                          int threads, int top_k) {
-    const unsigned m = crit == SELHIP_CRIT_SMH_A ? (unsigned)aux_bytes / 8 : 0;
-    const unsigned p_aux = crit == SELHIP_CRIT_SMH_A || crit == SELHIP_CRIT_NONE ? 0 : (unsigned)__builtin_ctz(aux_bytes ? aux_bytes : 1);
+                          int threads, int top_k, int min_matches) {
+    const bool reads_smh = crit == SELHIP_CRIT_SMH_A || crit == SELHIP_CRIT_SMH_C;
+    const unsigned m = reads_smh ? (unsigned)aux_bytes / 8 : 0;
+    const unsigned p_aux = reads_smh || crit == SELHIP_CRIT_NONE ? 0 : (unsigned)__builtin_ctz(aux_bytes ? aux_bytes : 1);
     selhost_dataset* ds = nullptr;
     if (selhost_dataset_load(&ds, list_file.c_str(), m, p_aux, fp_mode, threads)) { std::cerr << selhost_last_error() << "\n"; return 1; }
     const int64_t n = selhost_dataset_size(ds);
@@ -150,6 +156,7 @@ static int run_neighbours(const std::string& list_file, int crit, float threshol
     r = selhip_ctx_upload(ctx, selhost_dataset_hll(ds), m ? selhost_dataset_aux(ds) : no_smh.data(), selhost_dataset_cards(ds), n, m ? (int)m : 1, 14);
     if (!r && p_aux) r = selhip_ctx_upload_aux_hll(ctx, selhost_dataset_aux_hll(ds), (int)p_aux);
     if (!r) r = selhip_ctx_set_criterion(ctx, crit);
+    if (!r && crit == SELHIP_CRIT_SMH_C) r = selhip_ctx_set_min_matches(ctx, min_matches);
     if (!r) r = selhip_ctx_set_allpairs_topk(ctx, top_k);
     if (!r) r = selhip_ctx_run(ctx, mode, algo, threshold, n_rows, n_bands, 0, n);
     if (!r) {
@@ -230,14 +237,15 @@ int main(int argc, char* argv[]) {
     std::string out_file = "", dump_file = "", query_file = "", pair_file = "", matrix_file = "", estimator = "";
     bool gpus_given = false, topk_given = false, nbr_given = false, matrix_given = false, union_measure = false, aux_given = false, estimator_given = false;
     const char* selection_opt = nullptr;         // the first of -h, -c, -n, -A seen: options of a selection pass, which -M does not run
-    long long top_k = 0, nbr_k = 0;
+    long long top_k = 0, nbr_k = 0, min_matches = 0;
+    bool cmin_given = false;
     int c;
-    while ((c = getopt(argc, argv, "xl:b:a:h:c:t:g:nA:F:B:o:r:q:k:K:p:M:UE:")) != -1) {
+    while ((c = getopt(argc, argv, "xl:b:a:h:c:C:t:g:nA:F:B:o:r:q:k:K:p:M:UE:")) != -1) {
         switch (c) {
-            case 'x': std::cout << "Usage: -l -h -a -b [-c smh_a|hll_a|hll_an|none] [-t threads] [-g gpus] [-n] [-A auto|stream|sig] [-F 0|1] [-B block] [-o file] | -r file\n"
-                                   "       -l db_list -q query_list -h -a [-c smh_a|hll_a|hll_an|none] [-n] [-A auto|stream|sig|index] [-F 0|1] [-k best_per_query]   (query-vs-database selection)\n"
-                                   "       -l -h -a [-c smh_a|hll_a|hll_an|none] [-n] [-A auto|stream|sig|hashjoin] [-F 0|1] -K best_per_genome   (every genome's best partners, both members of a pair)\n"
-                                   "       -l list -p pair_file -h -a [-c smh_a|hll_a|hll_an|none] [-n] [-A auto|stream|sig] [-F 0|1] [-o file]   (only the listed pairs; lines 'path1 path2 ...')\n"
+            case 'x': std::cout << "Usage: -l -h -a -b [-c smh_a|hll_a|hll_an|none|smh_c -C c_min] [-t threads] [-g gpus] [-n] [-A auto|stream|sig] [-F 0|1] [-B block] [-o file] | -r file\n"
+                                   "       -l db_list -q query_list -h -a [-c smh_a|hll_a|hll_an|none|smh_c -C c_min] [-n] [-A auto|stream|sig|index] [-F 0|1] [-k best_per_query]   (query-vs-database selection)\n"
+                                   "       -l -h -a [-c smh_a|hll_a|hll_an|none|smh_c -C c_min] [-n] [-A auto|stream|sig|hashjoin] [-F 0|1] -K best_per_genome   (every genome's best partners, both members of a pair)\n"
+                                   "       -l list -p pair_file -h -a [-c smh_a|hll_a|hll_an|none|smh_c -C c_min] [-n] [-A auto|stream|sig] [-F 0|1] [-o file]   (only the listed pairs; lines 'path1 path2 ...')\n"
                                    "       -l list [-q query_list] [-F 0|1] -M out.tsv [-U]   (no selection: the dense Jaccard -- -U: union size -- matrix, file-list order)\n"
                                    "       -l list [-q query_list] -M out.tsv -E smh|smh_matches -a bytes   (the same table from the SuperMinHash sketches: equal buckets / m, or their count)\n"; return 0;
             case 'q': query_file = optarg; break;
@@ -255,6 +263,7 @@ int main(int argc, char* argv[]) {
             case 'a': aux_bytes = std::stoi(optarg); aux_given = true; break;
             case 'h': threshold = std::stof(optarg); if (!selection_opt) selection_opt = "-h"; break;
             case 'c': criterion = optarg; if (!selection_opt) selection_opt = "-c"; break;
+            case 'C': min_matches = std::strtoll(optarg, nullptr, 10); cmin_given = true; if (!selection_opt) selection_opt = "-C"; break;
             case 't': threads = std::stoi(optarg); break;
             case 'g': n_gpus = std::stoi(optarg); gpus_given = true; break;
             case 'n': mode = SELHIP_MODE_SMH; if (!selection_opt) selection_opt = "-n"; break;
@@ -292,6 +301,18 @@ int main(int argc, char* argv[]) {
     }
     if (estimator_given) { std::cerr << "selection: -E (hll, smh, smh_matches) is an option of -M (the dense similarity matrix)\n"; return 2; }
     if (union_measure) { std::cerr << "selection: -U (union sizes) is an option of -M (the dense similarity matrix)\n"; return 2; }
+    // -c smh_c and its -C: checked before any file is read or device opened
+    if (cmin_given && criterion != "smh_c") { std::cerr << "selection: -C (the count threshold) is an option of -c smh_c\n"; return 2; }
+    if (criterion == "smh_c") {
+        if (!cmin_given) { std::cerr << "selection: -c smh_c needs its count threshold: -C c_min (at least c_min equal buckets)\n"; return 2; }
+        if (!aux_given || aux_bytes / 8 <= 0) { std::cerr << "selection: -c smh_c reads the .smh<m> files: give their size with -a (bytes, 8 per bucket)\n"; return 2; }
+        const char* clash = gpus_given ? "-g" : ooc_block != 0 ? "-B" : nullptr;
+        if (clash) {
+            std::cerr << "selection: -c smh_c cannot be combined with " << clash << "; the multi-GPU and out-of-core drivers carry no count threshold\n";
+            return 2;
+        }
+        if (min_matches < 1 || min_matches > aux_bytes / 8) { std::cerr << "selection: -C must be in 1.." << aux_bytes / 8 << " (the m = -a / 8 buckets)\n"; return 2; }
+    }
     if (!pair_file.empty()) {
         // checked before any file is read or device opened
         const char* clash = !query_file.empty() ? "-q" : topk_given ? "-k" : nbr_given ? "-K" : ooc_block != 0 ? "-B" : gpus_given && n_gpus > 1 ? "-g" : nullptr;
@@ -328,12 +349,12 @@ int main(int argc, char* argv[]) {
                       << "; it runs on one device and prints text\n";
             return 2;
         }
-        if (criterion != "smh_a" && criterion != "hll_a" && criterion != "hll_an" && criterion != "none") {
+        if (criterion != "smh_a" && criterion != "hll_a" && criterion != "hll_an" && criterion != "none" && criterion != "smh_c") {
             std::cerr << "selection: -q -c " << criterion << ": the accepted criteria are hll_a, hll_an and smh_a\n";
             return 2;
         }
         if (list_file.empty()) { std::cerr << "selection: -q needs the database list (-l)\n"; return 2; }
-        return run_queries(query_file, list_file, criterion, threshold, aux_bytes, mode, algo, fp_mode, threads, (int)top_k);
+        return run_queries(query_file, list_file, criterion, threshold, aux_bytes, mode, algo, fp_mode, threads, (int)top_k, (int)min_matches);
     }
     if (algo == SELHIP_ALGO_INDEX) {
         // checked before any file is read or device opened
@@ -356,14 +377,16 @@ int main(int argc, char* argv[]) {
     if (criterion == "hll_a") crit = SELHIP_CRIT_HLL_A;
     else if (criterion == "hll_an") crit = SELHIP_CRIT_HLL_AN;
     else if (criterion == "none") crit = SELHIP_CRIT_NONE;
+    else if (criterion == "smh_c") crit = SELHIP_CRIT_SMH_C;
     else if (criterion != "smh_a") {
         std::cout << "Option -c invalid. The accepted criteria are hll_a, hll_an and smh_a.\n";    // selection.cpp:293
         return 0;
     }
     if (list_file.empty()) { std::cerr << "No input file provided\n"; exit(-1); }   // selection.cpp:40-44
-    if (nbr_given) return run_neighbours(list_file, crit, threshold, aux_bytes, mode, algo, fp_mode, threads, (int)nbr_k);
-    const unsigned m = crit == SELHIP_CRIT_SMH_A ? (unsigned)aux_bytes / 8 : 0;                      // selection.cpp:231
-    const unsigned p_aux = crit == SELHIP_CRIT_SMH_A || crit == SELHIP_CRIT_NONE ? 0 : (unsigned)__builtin_ctz(aux_bytes ? aux_bytes : 1);   // :125
+    if (nbr_given) return run_neighbours(list_file, crit, threshold, aux_bytes, mode, algo, fp_mode, threads, (int)nbr_k, (int)min_matches);
+    const bool reads_smh = crit == SELHIP_CRIT_SMH_A || crit == SELHIP_CRIT_SMH_C;
+    const unsigned m = reads_smh ? (unsigned)aux_bytes / 8 : 0;                                      // selection.cpp:231
+    const unsigned p_aux = reads_smh || crit == SELHIP_CRIT_NONE ? 0 : (unsigned)__builtin_ctz(aux_bytes ? aux_bytes : 1);   // :125
 
     selhost_dataset* ds = nullptr;
     int rc = selhost_dataset_load(&ds, list_file.c_str(), m, p_aux, fp_mode, threads);
@@ -424,6 +447,7 @@ int main(int argc, char* argv[]) {
         r = selhip_ctx_upload(ctx, selhost_dataset_hll(ds), aux_ptr, selhost_dataset_cards(ds), n, m_up, 14);
         if (!r && p_aux) r = selhip_ctx_upload_aux_hll(ctx, selhost_dataset_aux_hll(ds), (int)p_aux);
         if (!r) r = selhip_ctx_set_criterion(ctx, crit);
+        if (!r && crit == SELHIP_CRIT_SMH_C) r = selhip_ctx_set_min_matches(ctx, (int)min_matches);
         void* d_list = nullptr;
         if (!r && !pair_file.empty()) {
             // the listed pairs as ranks of the sorted list, then one pass over them

@@ -237,6 +237,10 @@ struct selhip_ctx {
     // and estimator kernels of the other criteria); dense_route_used = which the last such pass took (-1 = none yet)
     int dense_fused = 1;
     int dense_route_used = -1;
+    // SELHIP_CRIT_SMH_C (kernel_smhc.cuh): the count threshold (selhip_ctx_set_min_matches; 0 = never set) and the stage-1 kernel of the
+    // last such pass (1 the fast path, 0 the generic one, -1 none yet)
+    int min_matches = 0;
+    int smhc_path_used = -1;
 
     // last run parameters (for overflow re-runs)
     bool have_run = false, pending = false;

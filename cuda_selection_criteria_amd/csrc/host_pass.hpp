@@ -57,6 +57,58 @@ hipError_t launch_stage1(selhip_ctx* c, const StageIO& io, int n_rows, int n_ban
     return hipGetLastError();
 }
 
+// ---- stage 1 of criterion smh_c (kernel_smhc.cuh) -----------------------------------------------
+// what SELHIP_CRIT_SMH_C asks of the context, checked by every entry before it claims a counter set
+int accept_count(selhip_ctx* c) {
+    if (c->m <= 0 || (!c->d_aux && c->n)) { set_err(&c->err, "criterion smh_c (SELHIP_CRIT_SMH_C) needs SuperMinHash rows: the context holds none"); return SELHIP_E_BADARG; }
+    if (c->min_matches < 1) { set_err(&c->err, "criterion smh_c (SELHIP_CRIT_SMH_C) needs a count threshold: selhip_ctx_set_min_matches first"); return SELHIP_E_BADARG; }
+    if (c->min_matches > c->m) { set_err(&c->err, "criterion smh_c (SELHIP_CRIT_SMH_C): c_min = %d exceeds the m = %d buckets of a row", c->min_matches, c->m); return SELHIP_E_BADARG; }
+    return SELHIP_OK;
+}
+
+// the rows of X (owned rows of rm) against the candidates of Y from first_cand on.  QUERY = false: X = Y = the context's rows, windows
+// from hi and pc_in's z0; QUERY = true: the queries against the database, windows lo / hi
+struct CountSets { const u64* X; const u64* Y; int n_x, n_y; const int* lo; const int* hi; const PassCounters* pc_in; };
+template <bool QUERY>
+hipError_t launch_count(selhip_ctx* c, hipStream_t st, const CountSets& a, const RowMap& rm, int first_cand,
+                        selhip_int2_t* surv, u64 cap, PassCounters* pc) {
+    const int m = c->m, c_min = c->min_matches;
+    c->smhc_path_used = smhc_fast(m) ? 1 : 0;
+    if (smhc_fast(m)) {
+        const int nch = m / 128;
+        const long long n_tiles = rm.n_tiles(smhc_q(nch));
+        if (n_tiles > 0x7FFFFFFFll) return hipErrorInvalidValue;
+        const int chunk_base = (first_cand / kChunk) * kChunk;
+        const int n_chunks = (a.n_y - chunk_base + kChunk - 1) / kChunk;
+        if (n_tiles <= 0 || n_chunks <= 0) return hipSuccess;
+        const long long blocks = n_tiles * n_chunks;
+        if (blocks > 0x7FFFFFFFll) return hipErrorInvalidValue;
+#define SELHIP_SMHC_LAUNCH(NCH) hipLaunchKernelGGL((smh_count_kernel<NCH, QUERY>), dim3((unsigned)blocks), dim3(kBlock), 0, st, (const u64x2*)a.X, (const u64x2*)a.Y, \
+                                                   a.n_x, a.n_y, a.lo, a.hi, a.pc_in, rm, (int)n_tiles, chunk_base, c_min, surv, cap, pc)
+        switch (nch) {
+            case 1: SELHIP_SMHC_LAUNCH(1); break;
+            case 2: SELHIP_SMHC_LAUNCH(2); break;
+            case 4: SELHIP_SMHC_LAUNCH(4); break;
+            default: SELHIP_SMHC_LAUNCH(8);
+        }
+#undef SELHIP_SMHC_LAUNCH
+        return hipGetLastError();
+    }
+    const long long rows = rm.n_tiles(1);
+    const long long blocks = rows * ((a.n_y + kBlock - 1) / kBlock);
+    if (blocks <= 0) return hipSuccess;
+    if (rows > 0x7FFFFFFFll || blocks > 0x7FFFFFFFll) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((smh_count_generic_kernel<QUERY>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a.X, a.Y, a.n_x, a.n_y, m, a.lo, a.hi, a.pc_in,
+                       rm, (int)rows, c_min, surv, cap, pc);
+    return hipGetLastError();
+}
+
+// the all-pairs form behind cb_bounds_kernel: candidates k > row_begin, as in launch_stage1
+hipError_t launch_stage1_count(selhip_ctx* c, const StageIO& io, const RowMap& rm) {
+    const int n = (int)c->n;
+    return launch_count<false>(c, io.st, CountSets{c->d_aux, c->d_aux, n, n, nullptr, c->hi.p, c->pcb}, rm, rm.row_begin + 1, io.surv, io.cap, io.pc);
+}
+
 
 // pairs of the all-pairs triangle that this context's passes cover
 double join_pairs_here(const selhip_ctx* c) {
@@ -590,7 +642,7 @@ int enqueue_tail(selhip_ctx* c, const Chain& ch, const selhip_int2_t* final_list
     return enqueue_hist_select(c, ch, final_list, final_count, final_cap, grouped, tau, pc0);
 }
 
-// smh_a (alone or before the auxiliary criterion) over the query rows of one chain, then the final criterion.  [rb, re) is the
+// smh_a (alone or before the auxiliary criterion) or the count of smh_c over the query rows of one chain, then the final criterion.  [rb, re) is the
 // pass's whole row range (row ownership under the interleave is counted from its first row)
 int enqueue_chain(selhip_ctx* c, const Chain& ch, int rb, int re, double tau, bool use_hash, bool use_sig, bool count_in_verify,
                   PassCounters* pc0) {
@@ -600,7 +652,8 @@ int enqueue_chain(selhip_ctx* c, const Chain& ch, int rb, int re, double tau, bo
     else { rm.row_begin = ch.rb; rm.row_end = ch.re; }          // ch.rb - rb is a multiple of the interleave period
     {
         TimerScope t(c, T_STAGE1, io.st);
-        if (use_hash)     HIPCHK(&c->err, launch_stage1_hashjoin(c, io, c->n_rows, c->n_bands, rm));
+        if (c->plan.count) HIPCHK(&c->err, launch_stage1_count(c, io, rm));
+        else if (use_hash) HIPCHK(&c->err, launch_stage1_hashjoin(c, io, c->n_rows, c->n_bands, rm));
         else if (use_sig) HIPCHK(&c->err, launch_stage1_sig(c, io, c->n_rows, c->n_bands, rm));
         else              HIPCHK(&c->err, launch_stage1(c, io, c->n_rows, c->n_bands, rm));
     }

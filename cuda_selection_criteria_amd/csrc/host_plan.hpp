@@ -74,20 +74,25 @@ int bs_planes(int khi) { return khi <= 16 ? 4 : khi <= 32 ? 5 : 6; }
 
 // the criterion has an auxiliary-HLL stage (hll_a, hll_an, hll_a + smh_a): it needs the auxiliary sketches
 bool aux_criterion(int criterion) { return criterion == SELHIP_CRIT_HLL_A || criterion == SELHIP_CRIT_HLL_AN || criterion == SELHIP_CRIT_HLL_A_SMH_A; }
+// stage 1's survivor list is the list stage 2 reads (smh_a, smh_c): nothing filters it again, and the survivors are the statistic
+bool survivors_final(int criterion) { return criterion == SELHIP_CRIT_SMH_A || criterion == SELHIP_CRIT_SMH_C; }
 
 // ---- which stage 1 a pass runs ------------------------------------------------------------------
-// smh: the criterion has an smh_a stage at all (hll_a / hll_an alone read neither the band shape nor the algorithm).  use_sig: band
+// smh: the criterion has a stage 1 on the SuperMinHash rows that fills a survivor list -- smh_a alone or before hll_a, or the count of
+// smh_c (hll_a / hll_an alone read neither the band shape nor the algorithm).  count: that stage is the count test of smh_c
+// (kernel_smhc.cuh), which reads neither the band shape nor the algorithm either: none of the fields below is set.  use_sig: band
 // signatures are built and joined (use_hash: by the sort join; use_index: a query pass probes the sorted index instead of joining);
 // il_stream: ALGO_STREAM in its tiled form, which reads the bucket-interleaved copy of the sketches.  bad: the format of the error
 // (it takes n_rows, n_bands) when the caller insisted on an algorithm that does not take the band shape
 struct PassPlan {
-    bool smh = false, use_hash = false, use_sig = false, use_index = false, il_stream = false;
+    bool smh = false, count = false, use_hash = false, use_sig = false, use_index = false, il_stream = false;
     const char* bad = nullptr;
 };
 PassPlan pass_plan(int criterion, int algo, int m, int n_rows, int n_bands) {
     PassPlan p;
-    p.smh = criterion == SELHIP_CRIT_SMH_A || criterion == SELHIP_CRIT_HLL_A_SMH_A;
-    if (!p.smh) return p;
+    p.count = criterion == SELHIP_CRIT_SMH_C;
+    p.smh = p.count || criterion == SELHIP_CRIT_SMH_A || criterion == SELHIP_CRIT_HLL_A_SMH_A;
+    if (!p.smh || p.count) return p;
     const bool sig_ok = sig_supported(n_rows, n_bands);
     p.use_hash = algo == SELHIP_ALGO_HASHJOIN;
     p.use_index = algo == SELHIP_ALGO_INDEX;

@@ -183,6 +183,11 @@ int enqueue_query_pass(selhip_ctx* c, double tau) {
         if ((long long)n_q * ((n_d + kBlock - 1) / kBlock) > 0x7FFFFFFFll) { set_err(&c->err, "query pass too large for one launch"); return SELHIP_E_BADARG; }
         TimerScope t(c, T_AUX);
         HIPCHK(&c->err, launch_query_aux(c, nullptr, nullptr, 0, tau, pc));
+    } else if (c->plan.count) {
+        // smh_c: the count kernel of the all-pairs pass over the rectangle, every query's window [lo, hi] in place of the triangle's
+        TimerScope t(c, T_STAGE1);
+        HIPCHK(&c->err, launch_count<true>(c, c->stream, CountSets{q.d_aux, c->d_aux, n_q, n_d, q.lo.p, q.hi.p, pc}, RowMap{0, n_q, n_q, 1, 0}, 0,
+                                           q.surv.p, (u64)q.surv.cap, pc));
     } else if (use_sig) {
         const long long key = ((long long)r << 40) | ((long long)nb << 24) | ((c->db_gen & 0xFFFFF) << 1) | 1;
         if (q.db_sig_key != key) {
@@ -249,7 +254,7 @@ int enqueue_query_pass(selhip_ctx* c, double tau) {
         TimerScope t(c, T_AUX);
         HIPCHK(&c->err, launch_query_aux(c, q.surv.p, &pc->n_survivors, (u64)q.surv.cap, tau, pc));
     }
-    if (c->criterion != SELHIP_CRIT_SMH_A) { fl = q.fin.p; fcnt = &pc->n_final; fcap = (u64)q.fin.cap; }
+    if (!survivors_final(c->criterion)) { fl = q.fin.p; fcnt = &pc->n_final; fcap = (u64)q.fin.cap; }
     // stage 2 on the combined index space: the all-pairs estimator / select kernel, unchanged
     const u64 window = (u64)q.counts.cap / 64;
     for (u64 off = 0; off < fcap; off += window) {
@@ -283,7 +288,7 @@ int ensure_query_scratch(selhip_ctx* c, size_t list_cap, size_t res_cap) {
         HIPCHK(&c->err, q.surv.ensure(list_cap));
         final_cap = q.surv.cap;
     }
-    if (c->criterion != SELHIP_CRIT_SMH_A) {
+    if (!survivors_final(c->criterion)) {
         HIPCHK(&c->err, q.fin.ensure(list_cap));
         final_cap = q.fin.cap;
     }

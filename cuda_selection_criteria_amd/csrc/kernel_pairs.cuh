@@ -6,7 +6,7 @@
 namespace {
 
 // =============================================================================================
-// What the three kernels share.  A block takes kPairsBlock consecutive entries per batch:
+// What the kernels share.  A block takes kPairsBlock consecutive entries per batch:
 //  * every thread reads ONE entry with an 8-byte load (a wave reads 512 contiguous bytes), puts the smaller rank first and decides
 //        valid = 0 <= x, y < n and x != y            live = valid && e_hi != 0 && (!use_cb || CB(tau, e_lo, e_hi))
 //    from the truncated cards the pass's first kernel wrote (`live` is the entry's membership of the all-pairs pair space E);
@@ -220,6 +220,61 @@ void pairs_direct_kernel(const u64* __restrict__ aux, int m, int n_rows, int n_b
         block_append(s.app, ok, pr, lane, surv, surv_cap, surv_count, nullptr);
     }
     if constexpr (!LAUNCHER) pairs_block_tally(s, tl, lane, pc0);
+}
+
+// ---------------------------------------------------------------------------------------------
+// pairs_count_kernel: stage 1 of criterion smh_c (kernel_smhc.cuh) over a list.  pairs_direct_kernel's shape -- 16 lanes per entry,
+// groups of four entries, gpw groups per wave and batch, kPairsSteps 16-bucket steps' loads in flight together -- with the count over
+// ALL m buckets in place of the band test: every step adds the population count of the quarter-wave's 16-bit equality mask, and
+// smhc_selects decides the entry when its row is through.  Nothing stops early: a count needs every bucket.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kPairsBlock)
+void pairs_count_kernel(const u64* __restrict__ aux, int m, int c_min,
+                        const selhip_int2_t* __restrict__ list, u64 n_pairs, int n, const u64* __restrict__ ecard, double tau, int use_cb, int gpw,
+                        selhip_int2_t* __restrict__ surv, u64 surv_cap, u64* __restrict__ surv_count, PassCounters* __restrict__ pc0) {
+    __shared__ PairsLds s;
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    const int sub = lane & 15, quarter = lane >> 4, qshift = quarter * 16;
+    const int per_wave = 4 * gpw;                                             // entries a wave takes per batch: its first per_wave lanes hold one each
+    const u64 per_block = (u64)(kPairsBlock / kWave) * per_wave;
+    pairs_lds_init(s);
+    PairsTally tl;
+    for (u64 base = (u64)blockIdx.x * per_block; base < n_pairs; base += (u64)gridDim.x * per_block) {
+        const u64 j = base + (u64)(wave * per_wave + lane);
+        const bool in = lane < per_wave && j < n_pairs;
+        bool live;
+        const selhip_int2_t pr = pairs_entry(list, j, in, n, ecard, tau, use_cb, tl, &live);
+        const u64 live_mask = __ballot(live);
+        u64 ok_mask = 0;
+#pragma unroll 1
+        for (int t = 0; t < gpw; ++t) {
+            if (((live_mask >> (t * 4)) & 0xFull) == 0) continue;             // none of this group's four entries is live
+            const int src = t * 4 + quarter;
+            const int px = __shfl(pr.x, src, kWave), py = __shfl(pr.y, src, kWave);       // (entries that are not live: {0, 0}, inside the arrays)
+            const u64* __restrict__ a = aux + (long long)px * m;
+            const u64* __restrict__ b = aux + (long long)py * m;
+            const bool open = (live_mask >> src) & 1ull;
+            int cnt = 0;                                                      // my quarter's count
+#pragma unroll 1
+            for (int p0 = 0; p0 < m; p0 += 16 * kPairsSteps) {
+                u64 va[kPairsSteps], vb[kPairsSteps];
+#pragma unroll
+                for (int u = 0; u < kPairsSteps; ++u) {
+                    const int idx = p0 + u * 16 + sub;
+                    const bool ld = open && idx < m;
+                    va[u] = ld ? a[idx] : 0ull;
+                    vb[u] = ld ? b[idx] : 1ull;
+                }
+#pragma unroll
+                for (int u = 0; u < kPairsSteps; ++u)
+                    cnt += __popc((uint32_t)(__ballot(va[u] == vb[u]) >> qshift) & 0xFFFFu);
+            }
+            ok_mask |= pairs_quarter_bits(__ballot(open && sub == 0 && smhc_selects(cnt, c_min)), t * 4);
+        }
+        const bool ok = (ok_mask >> lane) & 1ull;
+        block_append(s.app, ok, pr, lane, surv, surv_cap, surv_count, nullptr);
+    }
+    pairs_block_tally(s, tl, lane, pc0);
 }
 
 }  // namespace

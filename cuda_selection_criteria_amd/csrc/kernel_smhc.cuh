@@ -1,0 +1,177 @@
+// kernel_smhc.cuh -- stage 1 of criterion smh_c (SELHIP_CRIT_SMH_C): a pair of the pass's pair space survives iff
+//     c(i, k) = #{ j < m : aux_i[j] == aux_k[j] }  >=  c_min            (the full 64 bits of a bucket are compared)
+// i.e. the SuperMinHash Jaccard estimate c / m is at least c_min / m.  The count is the cell of kernel_matrix_smh.cuh; here it never leaves
+// the scalar unit: no lane write, no dense store, one scalar compare per pair and an append for the few pairs that pass.
+// Part of libselhip.so; included by selection_kernels.hip only (one translation unit, anonymous namespace).  All kernels read `aux`
+// row-major, as uploaded or attached: for a count any lane <-> bucket map does, as long as both rows of a pair use the same one
+// (DESIGN.md section 14), so there is no interleaved copy as in ALGO_STREAM.
+//   smh_count_kernel<NCH, QUERY>        m = 128 * NCH buckets, NCH in {1, 2, 4, 8} (smhc_fast): smh_stream_kernel's block shape and enumeration
+//   smh_count_generic_kernel<QUERY>     every other m > 0: smh_generic_kernel's unit, lane = candidate, a serial loop over the buckets
+// QUERY = false: the all-pairs pass (rows and candidates from one set, the window of row i is [max(i + 1, z0), hi[i]], records (i, k));
+// QUERY = true: the query pass (rows from Q, candidates from D, the window of query i is [lo[i], hi[i]] of query_windows_kernel, records
+// (i, n_q + k) in the combined index space of stage 2).  The pair-list form is pairs_count_kernel (kernel_pairs.cuh).
+// Every kernel decides with smhc_selects: THE threshold step, written once.
+#pragma once
+
+namespace {
+
+constexpr bool smhc_fast(int m) { return m == 128 || m == 256 || m == 512 || m == 1024; }
+// query rows a wave of the fast path keeps in VGPRs: the stream kernel's budget, at most 12 rows (24 rows at m = 128 unrolled into more
+// lane masks in flight than the wave has SGPRs: 25 spilled in the all-pairs form, 6 in the query form -- the matrix kernel's finding)
+constexpr int smhc_q(int nch) { return kQueryVgprBudget / nch < 12 ? kQueryVgprBudget / nch : 12; }
+
+// the threshold step of every smh_c kernel
+__device__ __forceinline__ bool smhc_selects(int count, int c_min) { return count >= c_min; }
+
+// the count of the fast path: 2 NCH v_cmp_eq_u64 lane masks, one s_bcnt1_i32_b64 each, scalar adds (wave-uniform result)
+template <int NCH>
+__device__ __forceinline__ int smhc_count(const u64x2 (&cand)[NCH], const u64x2 (&q)[NCH]) {
+    int cnt = 0;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c)
+        cnt += __popcll(__ballot(cand[c].x == q[c].x)) + __popcll(__ballot(cand[c].y == q[c].y));
+    return cnt;
+}
+
+// the count of the lane-serial kernels: one lane walks both rows
+__device__ __forceinline__ int smhc_count_lane(const u64* __restrict__ x, const u64* __restrict__ y, int m) {
+    int cnt = 0;
+    for (int b = 0; b < m; ++b) cnt += x[b] == y[b] ? 1 : 0;
+    return cnt;
+}
+
+// the pair space of both kernels: the window of row i, and the record of (i, k)
+template <bool QUERY>
+struct SmhcSpace {
+    const int* __restrict__ lo;     // QUERY: first candidate of every query's window; else unused
+    const int* __restrict__ hi;     // last candidate of every row's window
+    int z0;                         // !QUERY: first candidate rank of the pass (first rank with e != 0, raised to cand_begin)
+    int n_x;                        // rows of X (QUERY: n_q, the offset of D in the combined index space)
+    __device__ __forceinline__ int first(int i) const { return QUERY ? lo[i] : max(i + 1, z0); }
+    __device__ __forceinline__ bool holds(int i, int k) const { return k >= first(i) && k <= hi[i]; }
+    __device__ __forceinline__ int partner(int k) const { return QUERY ? n_x + k : k; }
+};
+
+// ---------------------------------------------------------------------------------------------
+// smh_count_kernel<NCH, QUERY>
+//   block  = 4 waves; one block = (tile of Q = smhc_q(NCH) rows of X) x (chunk of kChunk candidates of Y), blockIdx.x -> (tile =
+//            b % n_tiles, chunk = b / n_tiles) as in smh_stream_kernel: the blocks of a chunk share it through their XCD's L2
+//   rows   = every wave holds the tile's Q rows in VGPRs, loaded coalesced (load c of a row hands lane l the buckets 128 c + 2 l, + 1)
+//   stream = the wave walks its candidates (stride 4), NCH x global_load_dwordx4 per candidate, kStreamAhead candidates ahead in a ring
+//            of register sets addressed statically
+//   pair   = smhc_count, ONE scalar compare against c_min, app.push_uniform for a pair that passes and lies in the row's window
+// The count is never cut short (no "count + remaining buckets < c_min" exit): the test would be a scalar compare and branch per
+// ballot on the path every pair takes, where the whole count costs one s_bcnt1 and one s_add per ballot.
+// No LDS tile and no block barrier: a wave that has no candidate leaves on its own.
+// ---------------------------------------------------------------------------------------------
+template <int NCH, bool QUERY>
+__global__ __launch_bounds__(kBlock, (NCH <= 4 ? 3 : 2))
+void smh_count_kernel(const u64x2* __restrict__ X, const u64x2* __restrict__ Y, int n_x, int n_y,
+                      const int* __restrict__ lo, const int* __restrict__ hi, const PassCounters* __restrict__ pc_in,
+                      RowMap rm, int n_tiles, int chunk_base, int c_min,
+                      selhip_int2_t* __restrict__ surv, u64 surv_cap, PassCounters* __restrict__ pc) {
+    constexpr int Q = smhc_q(NCH);
+    constexpr int ROWV = NCH * kWave;                 // u64x2 per sketch row
+    __shared__ selhip_int2_t app_lds[kWavesPerBlock * kAppendCap];
+
+    const int tile = blockIdx.x % n_tiles;
+    const int chunk = blockIdx.x / n_tiles;
+    int i0, i_end;
+    rm.tile_rows(tile, Q, &i0, &i_end);
+    if (i0 >= i_end) return;
+    const int i_last = i_end - 1;
+    SmhcSpace<QUERY> sp{lo, hi, 0, n_x};
+    int kmin, kmax;
+    if constexpr (QUERY) {
+        kmin = 0x7FFFFFFF; kmax = -1;
+        for (int i = i0; i < i_end; ++i) {            // uniform loads; an empty window (hi < lo) takes no part
+            const int l = lo[i], h = hi[i];
+            if (h >= l) { kmin = min(kmin, l); kmax = max(kmax, h); }
+        }
+    } else {
+        sp.z0 = pc_in->z0p1 ? pc_in->z0p1 - 1 : n_y;
+        kmin = max(i0 + 1, sp.z0);
+        kmax = hi[i_last];                            // hi is non-decreasing in i
+    }
+    const int k0 = chunk_base + chunk * kChunk;
+    if (k0 > kmax || k0 + kChunk - 1 < kmin) return;
+
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);     // wave-uniform -> SGPR loop counter
+    const int k_end = min(min(k0 + kChunk, n_y), kmax + 1);
+    int k = max(k0, kmin) + wave;
+    if (k >= k_end) return;
+
+    u64x2 q[Q][NCH];
+#pragma unroll
+    for (int a = 0; a < Q; ++a) {
+        const u64x2* row = X + (long long)min(i0 + a, n_x - 1) * ROWV + lane;        // rows past the end: a valid row, never a record
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) q[a][c] = row[c * kWave];
+    }
+
+    WaveAppender app;
+    app.init(app_lds, wave, surv, surv_cap, &pc->n_survivors);
+    constexpr int AHEAD = NCH <= 4 ? kStreamAhead : 1;                         // (m = 1024: the registers allow one row ahead)
+    constexpr int RING = AHEAD + 1;
+    u64x2 ring[RING][NCH];
+    auto load_row = [&](u64x2 (&dst)[NCH], int kk) {
+        const int kc = min(kk, k_end - 1);                                    // clamped: prefetches past the end re-read a valid row
+        const u64x2* row = Y + (long long)kc * ROWV + lane;
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) dst[c] = row[c * kWave];
+    };
+    auto compare_row = [&](const u64x2 (&cand)[NCH], int kk) {
+#pragma unroll
+        for (int a = 0; a < Q; ++a) {
+            if (smhc_selects(smhc_count<NCH>(cand, q[a]), c_min)) {
+                // (the empty volatile asm pins the branch on the count alone, as in smh_stream_kernel: the window tests stay off the
+                //  path of the pairs that fail it)
+                asm volatile("");
+                const int i = i0 + a;
+                if (i < i_end && sp.holds(i, kk)) app.push_uniform(i, sp.partner(kk), lane);
+            }
+        }
+    };
+#pragma unroll
+    for (int s = 0; s < AHEAD; ++s) load_row(ring[s], k + s * kWavesPerBlock);
+    for (; k < k_end; k += RING * kWavesPerBlock) {
+#pragma unroll
+        for (int s = 0; s < RING; ++s) {
+            const int kk = k + s * kWavesPerBlock;
+            if (kk >= k_end) break;
+            load_row(ring[(s + AHEAD) % RING], kk + AHEAD * kWavesPerBlock);
+            compare_row(ring[s], kk);
+        }
+    }
+    app.flush(lane);
+}
+
+// generic stage 1: block = 256 lanes = 256 candidates of one row; grid = (chunks, rows)
+template <bool QUERY>
+__global__ __launch_bounds__(kBlock)
+void smh_count_generic_kernel(const u64* __restrict__ X, const u64* __restrict__ Y, int n_x, int n_y, int m,
+                              const int* __restrict__ lo, const int* __restrict__ hi, const PassCounters* __restrict__ pc_in,
+                              RowMap rm, int n_rows_grid, int c_min,
+                              selhip_int2_t* __restrict__ surv, u64 surv_cap, PassCounters* __restrict__ pc) {
+    __shared__ selhip_int2_t app_lds[kWavesPerBlock * kAppendCap];
+    int i, i_e;
+    rm.tile_rows((int)(blockIdx.x % n_rows_grid), 1, &i, &i_e);
+    const int chunk = blockIdx.x / n_rows_grid;
+    if (i >= i_e) return;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+    SmhcSpace<QUERY> sp{lo, hi, 0, n_x};
+    if constexpr (!QUERY) sp.z0 = pc_in->z0p1 ? pc_in->z0p1 - 1 : n_y;
+    const int kmax = hi[i];
+    const long long kl = (long long)sp.first(i) + (long long)chunk * kBlock + (int)threadIdx.x;
+    const bool in_range = kl <= kmax && kl < n_y;
+    const int k = in_range ? (int)kl : 0;
+    const bool ok = in_range && smhc_selects(smhc_count_lane(X + (long long)i * m, Y + (long long)k * m, m), c_min);
+    WaveAppender app;
+    app.init(app_lds, wave, surv, surv_cap, &pc->n_survivors);
+    app.push(ok, i, sp.partner(k), lane);
+    app.flush(lane);
+}
+
+}  // namespace

@@ -14,6 +14,9 @@
 //                       verify16_batch (16 lanes per pair), verify_kernel / verify16_kernel: the exact verification behind ALGO_SIG
 //   kernel_stream.cuh   smh_stream_kernel     stage 1 ALGO_STREAM: query tile in LDS/VGPRs, candidates streamed row-major,
 //                                             v_cmp_eq_u64 lane masks folded on the scalar unit; smh_generic_kernel
+//   kernel_smhc.cuh     smh_count_kernel      stage 1 of criterion smh_c: at least c_min equal buckets -- the stream kernel's enumeration with a
+//                                             count (v_cmp_eq_u64, s_bcnt1, scalar adds, one compare) in place of the band fold, over the
+//                                             triangle or a query rectangle; smh_count_generic_kernel for every other m
 //   kernel_sigjoin.cuh  sig_build / sig_join   stage 1 ALGO_SIG: all-pairs band-signature join (DPP broadcast), hash join
 //   kernel_hll.cuh      hll_union_hist_kernel, ertl_select_kernel (stage 2), enum_pairs / aux_fused (hll_a, hll_an)
 //   kernel_hllbs.cuh    hll_bitslice_kernel, hll_union_hist_bs_kernel: stage 2a on bit-sliced registers (bit-serial max, decode tree, v_bcnt)
@@ -66,6 +69,7 @@
 #include "kernel_bounds.cuh"
 #include "kernel_verify.cuh"
 #include "kernel_stream.cuh"
+#include "kernel_smhc.cuh"
 #include "kernel_sigjoin.cuh"
 #include "kernel_hll.cuh"
 #include "kernel_hllbs.cuh"

@@ -70,7 +70,8 @@ extern "C" int selhip_multi_select(const int* devices, int n_devices,
                                    int64_t n, int m, int p_hll, int mode, int algo, int fp_mode, float tau_f, int n_rows, int n_bands,
                                    int gather, selhip_pair_t* h_out, int64_t cap, int64_t* count_out, int64_t stats_out[4]) {
     if (!devices || n_devices < 1 || n_devices > 64 || !count_out || cap < 0 || (cap && !h_out)) { selhip_internal_set_error("bad argument"); return SELHIP_E_BADARG; }
-    if (criterion < SELHIP_CRIT_SMH_A || criterion > SELHIP_CRIT_NONE) { selhip_internal_set_error("bad criterion %d", criterion); return SELHIP_E_BADARG; }
+    if (criterion < SELHIP_CRIT_SMH_A || criterion > SELHIP_CRIT_SMH_C) { selhip_internal_set_error("bad criterion %d", criterion); return SELHIP_E_BADARG; }
+    if (criterion == SELHIP_CRIT_SMH_C) { selhip_internal_set_error("criterion smh_c (SELHIP_CRIT_SMH_C) needs a count threshold that this entry has no argument for: run it through selhip_ctx_set_min_matches and the context passes"); return SELHIP_E_BADARG; }
     const bool need_aux = criterion != SELHIP_CRIT_SMH_A && criterion != SELHIP_CRIT_NONE && n > 0;
     if (need_aux && (!h_aux_hll || p_aux < 4 || p_aux > SELHIP_MAX_AUX_P)) { selhip_internal_set_error("criterion %d needs auxiliary HLL sketches (h_aux_hll, p_aux in [4,15])", criterion); return SELHIP_E_BADARG; }
     if (gather < SELHIP_GATHER_HOST || gather > SELHIP_GATHER_RCCL_OR_HOST) { selhip_internal_set_error("bad gather mode"); return SELHIP_E_BADARG; }

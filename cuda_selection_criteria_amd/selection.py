@@ -11,7 +11,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import (ALGO_AUTO, BANDING_CPU, CRIT_HLL_A, CRIT_HLL_AN, CRIT_HLL_A_SMH_A, CRIT_NONE, CRIT_SMH_A, F32, F64, FP_FMA,
+from ._lib import (ALGO_AUTO, BANDING_CPU, CRIT_HLL_A, CRIT_HLL_AN, CRIT_HLL_A_SMH_A, CRIT_NONE, CRIT_SMH_A, CRIT_SMH_C, F32, F64, FP_FMA,
                    MEASURE_JACCARD, MEASURE_SMH_JACCARD, MEASURE_SMH_MATCHES, MEASURE_UNION, MODE_CB_SMH, Pair, check, hip_lib, host_lib)
 
 # layout of selhip_pair_t {int32 i, k; double jaccard}
@@ -311,6 +311,11 @@ class Selector:
         check(self._lib.selhip_ctx_set_criterion(self._ctx, criterion), self._ctx)
         self.criterion = criterion
 
+    def set_min_matches(self, c: int):
+        """the count threshold of criterion smh_c (CRIT_SMH_C): a pair survives stage 1 iff at least c of its m SuperMinHash buckets
+        are equal (c >= 1; a pass refuses c > m).  min_matches(m, j) gives the c of a SuperMinHash Jaccard estimate j"""
+        check(self._lib.selhip_ctx_set_min_matches(self._ctx, int(c)), self._ctx)
+
     def cards(self) -> np.ndarray:
         out = np.empty(self.n, dtype=np.float64)
         check(self._lib.selhip_ctx_get_cards(self._ctx, out.ctypes.data), self._ctx)
@@ -494,22 +499,53 @@ class Selector:
         return float(self._lib.selhip_ctx_kernel_launches(self._ctx, name.encode()))
 
 
+def min_matches(m: int, j: float) -> int:
+    """the smallest integer c in [1, m] with c / m >= j in float64: the count threshold of criterion smh_c (Selector.set_min_matches)
+    that keeps exactly the pairs whose SuperMinHash estimate c / m reaches j.  ValueError for j > 1 (no count reaches it), for a NaN
+    and for m < 1"""
+    m, j = int(m), float(j)
+    if m < 1:
+        raise ValueError("min_matches: m must be >= 1")
+    if not j <= 1.0:
+        raise ValueError("min_matches: no count c <= m has c / m >= j for j > 1 (or NaN)")
+    c = min(m, max(1, int(np.ceil(j * m))))
+    while c > 1 and (c - 1) / m >= j:             # (j * m is rounded: settle on the exact boundary of the float64 quotient)
+        c -= 1
+    while c / m < j:
+        c += 1
+    return c
+
+
+def _criterion_files(criterion: str, aux_bytes: int, min_matches: Optional[int] = None) -> Tuple[int, int, int]:
+    """(m, p_aux, CRIT_*) of a criterion name and `-a aux_bytes`, for the file-list front ends: m buckets of the .smh<m> files to read
+    (0 = none), precision of the auxiliary .hll_<p> files (0 = none).  min_matches goes with "smh_c" and with nothing else"""
+    if min_matches is not None and criterion != "smh_c":
+        raise ValueError("min_matches is the count threshold of criterion smh_c")
+    if criterion == "smh_a":
+        return aux_bytes // 8, 0, CRIT_SMH_A                                   # selection.cpp:231
+    if criterion == "smh_c":
+        if min_matches is None:
+            raise ValueError("criterion smh_c needs min_matches (the count threshold c_min)")
+        if aux_bytes // 8 < 1:
+            raise ValueError("criterion smh_c reads the .smh<m> files: aux_bytes (8 m) must be given")
+        return aux_bytes // 8, 0, CRIT_SMH_C
+    if criterion in ("hll_a", "hll_an"):
+        return 0, (aux_bytes & -aux_bytes).bit_length() - 1, CRIT_HLL_A if criterion == "hll_a" else CRIT_HLL_AN   # __builtin_ctz(aux_bytes), selection.cpp:125
+    if criterion == "none":
+        return 0, 0, CRIT_NONE                                                 # only the .hll files are read; aux_bytes is ignored
+    raise ValueError("Option -c invalid. The accepted criteria are hll_a, hll_an and smh_a.")
+
+
 def select_from_filelist(list_file: str, tau: float, aux_bytes: int, mode: int = MODE_CB_SMH, device: int = 0,
-                         fp_mode: int = FP_FMA, algo: int = ALGO_AUTO, criterion: str = "smh_a", top_k: int = 0) -> str:
+                         fp_mode: int = FP_FMA, algo: int = ALGO_AUTO, criterion: str = "smh_a", top_k: int = 0,
+                         min_matches: Optional[int] = None) -> str:
     """The whole of selection_cuda.cpp main() (criterion smh_a) -- and of selection.cpp's hll_a / hll_an
     branches (:122-227): returns the text the CPU reference prints for `-c criterion -a aux_bytes -h tau`.
     criterion "none": no criterion in front of the Jaccard test (CRIT_NONE; mode MODE_CB_SMH = the CB bound alone, MODE_SMH = every pair).
+    criterion "smh_c" with min_matches = c: at least c of the m = aux_bytes / 8 SuperMinHash buckets equal (CRIT_SMH_C; `-c smh_c -C c`).
     top_k > 0: only every genome's top_k best partners, one line 'owner_path partner_path J' each, in ranked order (owner rank, then J
     descending, ties by partner rank): a selected pair can be printed twice (once per member), once or not at all."""
-    if criterion == "smh_a":
-        m, p_aux, crit = aux_bytes // 8, 0, CRIT_SMH_A                       # selection.cpp:231
-    elif criterion in ("hll_a", "hll_an"):
-        m, p_aux = 0, (aux_bytes & -aux_bytes).bit_length() - 1               # __builtin_ctz(aux_bytes), selection.cpp:125
-        crit = CRIT_HLL_A if criterion == "hll_a" else CRIT_HLL_AN
-    elif criterion == "none":
-        m, p_aux, crit = 0, 0, CRIT_NONE                                      # only the .hll files are read; aux_bytes is ignored
-    else:
-        raise ValueError("Option -c invalid. The accepted criteria are hll_a, hll_an and smh_a.")
+    m, p_aux, crit = _criterion_files(criterion, aux_bytes, min_matches)
     ds = load_dataset(list_file, m, p_aux, fp_mode)
     n_rows, n_bands = banding(m, tau) if m else (1, 1)
     with Selector(device, fp_mode) as sel:
@@ -518,6 +554,8 @@ def select_from_filelist(list_file: str, tau: float, aux_bytes: int, mode: int =
         if p_aux:
             sel.upload_aux_hll(ds.aux_hll, p_aux)
         sel.set_criterion(crit)
+        if crit == CRIT_SMH_C:
+            sel.set_min_matches(min_matches)
         pairs = sel.run(tau, mode, n_rows, n_bands, algo=algo, top_k=top_k if top_k else None)
     return format_lines(ds.names, pairs)
 
@@ -598,18 +636,11 @@ def read_pair_list(pair_file: str, names: Sequence[str]) -> np.ndarray:
 
 
 def select_pairs_from_filelist(list_file: str, pair_file: str, tau: float, aux_bytes: int, mode: int = MODE_CB_SMH, device: int = 0,
-                               fp_mode: int = FP_FMA, algo: int = ALGO_AUTO, criterion: str = "smh_a") -> str:
+                               fp_mode: int = FP_FMA, algo: int = ALGO_AUTO, criterion: str = "smh_a",
+                               min_matches: Optional[int] = None) -> str:
     """select_from_filelist restricted to the pairs listed in pair_file (lines 'path1 path2[ anything]' with paths of list_file, in
     either order): the text `selection -l list_file -p pair_file -c criterion -a aux_bytes -h tau` prints"""
-    if criterion == "smh_a":
-        m, p_aux, crit = aux_bytes // 8, 0, CRIT_SMH_A
-    elif criterion in ("hll_a", "hll_an"):
-        m, p_aux = 0, (aux_bytes & -aux_bytes).bit_length() - 1
-        crit = CRIT_HLL_A if criterion == "hll_a" else CRIT_HLL_AN
-    elif criterion == "none":
-        m, p_aux, crit = 0, 0, CRIT_NONE
-    else:
-        raise ValueError("Option -c invalid. The accepted criteria are hll_a, hll_an and smh_a.")
+    m, p_aux, crit = _criterion_files(criterion, aux_bytes, min_matches)
     ds = load_dataset(list_file, m, p_aux, fp_mode)
     listed = read_pair_list(pair_file, ds.names)
     n_rows, n_bands = banding(m, tau) if m else (1, 1)
@@ -618,6 +649,8 @@ def select_pairs_from_filelist(list_file: str, pair_file: str, tau: float, aux_b
         if p_aux:
             sel.upload_aux_hll(ds.aux_hll, p_aux)
         sel.set_criterion(crit)
+        if crit == CRIT_SMH_C:
+            sel.set_min_matches(min_matches)
         pairs = sel.run_pairs(listed, tau, mode, n_rows, n_bands, algo=algo)
     return format_lines(ds.names, pairs)
 
@@ -682,21 +715,15 @@ def ooc_select(hll: np.ndarray, aux: np.ndarray, cards: np.ndarray, tau: float, 
 
 
 def query_from_filelists(query_list: str, db_list: str, tau: float, aux_bytes: int, mode: int = MODE_CB_SMH, fp_mode: int = FP_FMA,
-                         device: int = 0, algo: int = ALGO_AUTO, criterion: str = "smh_a", top_k: int = 0) -> str:
+                         device: int = 0, algo: int = ALGO_AUTO, criterion: str = "smh_a", top_k: int = 0,
+                         min_matches: Optional[int] = None) -> str:
     """Query-vs-database selection: both lists are loaded and sorted by cardinality (load_dataset); returns one line
     'query_path db_path J' per selected pair, in (query rank, database rank) order, J formatted as selection.cpp prints it.
     top_k > 0: only every query's top_k best pairs, in ranked order (query rank, then J descending, ties by database rank).
     criterion "smh_a" (m = aux_bytes / 8 buckets), "hll_a" / "hll_an" (auxiliary HLL p = ctz(aux_bytes), as select_from_filelist) or
-    "none" (every pair of the CB windows -- MODE_SMH: every cross pair -- to the Jaccard test)."""
-    if criterion == "smh_a":
-        m, p_aux, crit = aux_bytes // 8, 0, CRIT_SMH_A
-    elif criterion in ("hll_a", "hll_an"):
-        m, p_aux = 0, (aux_bytes & -aux_bytes).bit_length() - 1               # __builtin_ctz(aux_bytes), selection.cpp:125
-        crit = CRIT_HLL_A if criterion == "hll_a" else CRIT_HLL_AN
-    elif criterion == "none":
-        m, p_aux, crit = 0, 0, CRIT_NONE                                      # only the .hll files are read; aux_bytes is ignored
-    else:
-        raise ValueError("Option -c invalid. The accepted criteria are hll_a, hll_an and smh_a.")
+    "none" (every pair of the CB windows -- MODE_SMH: every cross pair -- to the Jaccard test) or "smh_c" with min_matches = c (at least
+    c of the m = aux_bytes / 8 buckets equal)."""
+    m, p_aux, crit = _criterion_files(criterion, aux_bytes, min_matches)
     qs = load_dataset(query_list, m, p_aux, fp_mode)
     db = load_dataset(db_list, m, p_aux, fp_mode)
     n_rows, n_bands = banding(m, tau) if m else (1, 1)
@@ -708,6 +735,8 @@ def query_from_filelists(query_list: str, db_list: str, tau: float, aux_bytes: i
             sel.upload_aux_hll(db.aux_hll, p_aux)
             sel.upload_queries_aux_hll(qs.aux_hll, p_aux)
         sel.set_criterion(crit)
+        if crit == CRIT_SMH_C:
+            sel.set_min_matches(min_matches)
         pairs = sel.run_queries(tau, mode, n_rows, n_bands, algo, top_k=top_k if top_k else None)
     h = host_lib()
     buf = C.create_string_buffer(16384)

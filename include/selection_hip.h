@@ -80,6 +80,9 @@ typedef struct { int32_t i, k; double jaccard; } selhip_pair_t;
 #define SELHIP_CRIT_HLL_AN       2
 #define SELHIP_CRIT_HLL_A_SMH_A  3
 #define SELHIP_CRIT_NONE         4
+/* smh_c: at least c_min of the m SuperMinHash buckets equal (selhip_ctx_set_min_matches), i.e. the SuperMinHash Jaccard estimate
+ * c / m >= c_min / m -- exhaustive over the pass's pair space, no banding loss; n_rows, n_bands and algo are ignored */
+#define SELHIP_CRIT_SMH_C        5
 
 /* estimator arithmetic flavour (see csrc/ertl_mle.hpp) */
 #define SELHIP_FP_FMA        1     /* = reference built by its Makefile on an FMA-capable x86 host (default) */
@@ -245,6 +248,15 @@ int selhip_ctx_attach_aux_hll(selhip_ctx* ctx, const uint8_t* d_aux_hll, int p_a
 /* criterion used by the following selhip_ctx_run* calls (default SELHIP_CRIT_SMH_A); n_rows/n_bands are
  * ignored by HLL_A / HLL_AN / NONE (NONE ignores algo too and needs no auxiliary HLL sketches) */
 int selhip_ctx_set_criterion(selhip_ctx* ctx, int criterion);
+/* SELHIP_CRIT_SMH_C: a pair of the pass's pair space survives stage 1 iff c(i,k) = #{ j < m : aux_i[j] == aux_k[j] } >= c_min, compared
+ * on the full 64 bits (two empty SuperMinHash rows count m); survivors go to the J test of every other criterion and records carry
+ * the same J bits.  c_min < 1 is refused here (SELHIP_E_BADARG); a run under the criterion answers SELHIP_E_BADARG, naming it, when
+ * c_min was never set, when c_min > m and when the context holds no SuperMinHash rows.  The value survives uploads / attaches.
+ * stats[1] = stats[3] = the pairs of the pair space with c >= c_min.  All-pairs passes (row ranges, row interleave, candidate begin,
+ * pipeline, all-pairs top-k), query passes and pair-list passes take the criterion; selhip_multi_select and selhip_ooc_select, whose
+ * signatures carry no c_min, refuse it.  get_param "smhc_path_used": the stage-1 kernel of the last such pass, 1 = the fast path
+ * (m = 128, 256, 512, 1024), 0 = the generic one, -1 = none yet.  The stage is timed as "stage1". */
+int selhip_ctx_set_min_matches(selhip_ctx* ctx, int c_min);
 
 /* report() of every genome (Ertl-MLE, hll.h:834-837,862) computed on the device: d_cards_out[n]. */
 int selhip_hll_cards(selhip_ctx* ctx, const uint8_t* d_hll, int64_t n_genomes, int p, double* d_cards_out);
