@@ -45,6 +45,9 @@ FP_STRICT, FP_FMA = 0, 1
 CRIT_SMH_A, CRIT_HLL_A, CRIT_HLL_AN, CRIT_HLL_A_SMH_A, CRIT_NONE, CRIT_SMH_C = 0, 1, 2, 3, 4, 5
 MEASURE_JACCARD, MEASURE_UNION = 0, 1  # SELHIP_MEASURE_*: what a dense matrix stores (Selector.matrix)
 MEASURE_SMH_MATCHES, MEASURE_SMH_JACCARD = 16, 17   # ... from the SuperMinHash rows: equal buckets of the pair, and that count / m
+# ... from the HLL sketches again: the intersection estimate I = e_a + e_b - U, I / e_row and I / min(e_row, e_col); MAX_CONTAINMENT is
+# also a measure of the passes (Selector.set_measure)
+MEASURE_INTERSECTION, MEASURE_CONTAINMENT, MEASURE_MAX_CONTAINMENT = 32, 33, 34
 F64, F32 = 0, 1                        # SELHIP_F64 / SELHIP_F32: its element type
 BANDING_CPU, BANDING_CUDA = 0, 1
 TOPK_MAX = 1024                        # SELHIP_TOPK_MAX: largest k of Selector.set_query_topk and Selector.set_allpairs_topk
@@ -74,6 +77,7 @@ HIP_SYMBOLS = {
     "selhip_ctx_attach_aux_hll": (_i, [_vp, _vp, _i]),
     "selhip_ctx_set_criterion": (_i, [_vp, _i]),
     "selhip_ctx_set_min_matches": (_i, [_vp, _i]),
+    "selhip_ctx_set_measure": (_i, [_vp, _i]),
     "selhip_hll_cards": (_i, [_vp, _vp, _i64, _i, _vp]),
     "selhip_ctx_get_cards": (_i, [_vp, _vp]),
     "selhip_ctx_run": (_i, [_vp, _i, _i, C.c_float, _i, _i, _i64, _i64]),

@@ -281,6 +281,18 @@ int selhip_ctx_set_criterion(selhip_ctx* c, int criterion) {
     return SELHIP_OK;
 }
 
+int selhip_ctx_set_measure(selhip_ctx* c, int measure) {
+    if (!c) return SELHIP_E_BADARG;
+    if (measure != SELHIP_MEASURE_JACCARD && measure != SELHIP_MEASURE_MAX_CONTAINMENT) {
+        set_err(&c->err, "the measure of a pass is SELHIP_MEASURE_JACCARD (%d) or SELHIP_MEASURE_MAX_CONTAINMENT (%d) (got %d)",
+                SELHIP_MEASURE_JACCARD, SELHIP_MEASURE_MAX_CONTAINMENT, measure);
+        return SELHIP_E_BADARG;
+    }
+    if (c->pending) { set_err(&c->err, "a pass is still pending (selhip_ctx_finish)"); return SELHIP_E_STATE; }
+    c->measure = measure;
+    return SELHIP_OK;
+}
+
 int selhip_ctx_set_min_matches(selhip_ctx* c, int c_min) {
     if (!c) return SELHIP_E_BADARG;
     if (c_min < 1) { set_err(&c->err, "min_matches must be >= 1 (got %d)", c_min); return SELHIP_E_BADARG; }
@@ -416,6 +428,7 @@ int selhip_ctx_get_cards(selhip_ctx* c, double* h_out) {
 int selhip_ctx_run_async(selhip_ctx* c, int mode, int algo, float tau_f, int n_rows, int n_bands,
                          int64_t row_begin, int64_t row_end) {
     if (!c) return SELHIP_E_BADARG;
+    { const int rc = accept_measure(c, mode); if (rc) return rc; }
     if (c->criterion == SELHIP_CRIT_SMH_C) { const int rc = accept_count(c); if (rc) return rc; }
     if (!c->d_aux && c->n) { set_err(&c->err, "run before upload/attach"); return SELHIP_E_STATE; }
     if (mode != SELHIP_MODE_SMH && mode != SELHIP_MODE_CB_SMH) { set_err(&c->err, "bad mode %d", mode); return SELHIP_E_BADARG; }

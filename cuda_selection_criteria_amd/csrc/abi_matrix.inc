@@ -72,7 +72,8 @@ int matrix_call(selhip_ctx* c, bool query, int measure, int dtype, int64_t r0, i
     const char* const what = query ? "selhip_ctx_query_matrix" : "selhip_ctx_matrix";
     if (c->pending) { set_err(&c->err, "%s: a pass is still pending (selhip_ctx_finish)", what); return SELHIP_E_STATE; }
     const bool smh = measure == SELHIP_MEASURE_SMH_MATCHES || measure == SELHIP_MEASURE_SMH_JACCARD;
-    if (measure != SELHIP_MEASURE_JACCARD && measure != SELHIP_MEASURE_UNION && !smh) { set_err(&c->err, "%s: bad measure %d", what, measure); return SELHIP_E_BADARG; }
+    const bool share = measure == SELHIP_MEASURE_INTERSECTION || measure == SELHIP_MEASURE_CONTAINMENT || measure == SELHIP_MEASURE_MAX_CONTAINMENT;
+    if (measure != SELHIP_MEASURE_JACCARD && measure != SELHIP_MEASURE_UNION && !share && !smh) { set_err(&c->err, "%s: bad measure %d", what, measure); return SELHIP_E_BADARG; }
     if (dtype != SELHIP_F64 && dtype != SELHIP_F32) { set_err(&c->err, "%s: bad dtype %d", what, dtype); return SELHIP_E_BADARG; }
     if (query && c->q.n < 0) { set_err(&c->err, "%s: no queries attached (selhip_ctx_upload_queries / _attach_queries)", what); return SELHIP_E_BADARG; }
     const int64_t n_x = query ? c->q.n : c->n, n_y = c->n;

@@ -13,6 +13,7 @@ int selhip_ctx_run_pairs_async(selhip_ctx* c, const selhip_int2_t* d_pairs, int6
     if ((uintptr_t)d_pairs & 7) { set_err(&c->err, "the pair list must be 8-byte aligned"); return SELHIP_E_BADARG; }
     if (!c->d_aux && (c->n || n_pairs)) { set_err(&c->err, "run before upload/attach"); return SELHIP_E_STATE; }
     if (mode != SELHIP_MODE_SMH && mode != SELHIP_MODE_CB_SMH) { set_err(&c->err, "bad mode %d", mode); return SELHIP_E_BADARG; }
+    { const int rc = accept_measure(c, mode); if (rc) return rc; }
     if (algo == SELHIP_ALGO_HASHJOIN || algo == SELHIP_ALGO_INDEX) {
         set_err(&c->err, "a pair-list pass takes SELHIP_ALGO_AUTO, _SIG or _STREAM: algo %d is a join, not a check of a given pair", algo);
         return SELHIP_E_BADARG;

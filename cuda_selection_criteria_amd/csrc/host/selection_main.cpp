@@ -50,6 +50,13 @@
 //   -E <est>    with -M: the estimator behind the cells.  hll (default): the HyperLogLog values above.  smh: the SuperMinHash estimate of
 //               J, (equal buckets of the pair) / m; smh_matches: that count itself, printed as an integer (SELHIP_MEASURE_SMH_JACCARD /
 //               _SMH_MATCHES).  smh and smh_matches read the .smh<m> files too, m = -a bytes / 8: -a must be given, -U is refused
+//   -S <name>   the measure.  Of a selection pass (-l, -q, -p, -k, -K; -c smh_a | none | smh_c): jaccard (default) or max_containment --
+//               the pairs whose intersection estimate I = e_1 + e_2 - U is at least -h of the SMALLER genome, I / min(e_1, e_2),
+//               printed in J's place (selhip_ctx_set_measure): a plasmid, phage or fragment inside a genome.  max_containment needs -n
+//               (the CB bound is a bound on J) and takes no -c hll_a | hll_an (bounds on J), no -g, -B (the drivers carry no measure)
+//               and no -o (the result file records no measure).  With -M: intersection (I), containment (I / e_row: the share of the
+//               row genome found in the column genome, with -q the query inside the database genome) or max_containment (jaccard: the
+//               default table); a value of -E hll -- not with -U or -E smh | smh_matches
 //   -x          usage
 #include <unistd.h>
 
@@ -67,7 +74,7 @@
 // -q: the query list against the database list (-l), both loaded and sorted by cardinality; text on stdout.  criterion: "smh_a"
 // (m = aux_bytes / 8 buckets), "hll_a" / "hll_an" (auxiliary HLL p = ctz(aux_bytes), as the all-pairs mode) or "none" (.hll files only)
 static int run_queries(const std::string& query_file, const std::string& db_file, const std::string& criterion, float threshold,
-                       int aux_bytes, int mode, int algo, int fp_mode, int threads, int top_k, int min_matches) {
+                       int aux_bytes, int mode, int algo, int fp_mode, int threads, int top_k, int min_matches, int measure) {
     const bool smh = criterion == "smh_a";
     const bool smh_c = criterion == "smh_c";
     const bool none = criterion == "none";
@@ -110,6 +117,7 @@ static int run_queries(const std::string& query_file, const std::string& db_file
     if (!r && p_aux) r = selhip_ctx_upload_queries_aux_hll(ctx, selhost_dataset_aux_hll(qs), (int)p_aux);
     if (!r) r = selhip_ctx_set_criterion(ctx, crit);
     if (!r && smh_c) r = selhip_ctx_set_min_matches(ctx, min_matches);
+    if (!r) r = selhip_ctx_set_measure(ctx, measure);
     if (!r && top_k) r = selhip_ctx_set_query_topk(ctx, top_k);
     if (!r) r = selhip_ctx_run_queries(ctx, mode, algo, threshold, n_rows, n_bands);
     if (!r) {
@@ -134,7 +142,7 @@ static int run_queries(const std::string& query_file, const std::string& db_file
 
 // -K: one all-pairs pass over the list with the device-side cut on; text on stdout, one line per kept (owner, partner) record
 static int run_neighbours(const std::string& list_file, int crit, float threshold, int aux_bytes, int mode, int algo, int fp_mode,
-                          int threads, int top_k, int min_matches) {
+                          int threads, int top_k, int min_matches, int measure) {
     const bool reads_smh = crit == SELHIP_CRIT_SMH_A || crit == SELHIP_CRIT_SMH_C;
     const unsigned m = reads_smh ? (unsigned)aux_bytes / 8 : 0;
     const unsigned p_aux = reads_smh || crit == SELHIP_CRIT_NONE ? 0 : (unsigned)__builtin_ctz(aux_bytes ? aux_bytes : 1);
@@ -157,6 +165,7 @@ static int run_neighbours(const std::string& list_file, int crit, float threshol
     if (!r && p_aux) r = selhip_ctx_upload_aux_hll(ctx, selhost_dataset_aux_hll(ds), (int)p_aux);
     if (!r) r = selhip_ctx_set_criterion(ctx, crit);
     if (!r && crit == SELHIP_CRIT_SMH_C) r = selhip_ctx_set_min_matches(ctx, min_matches);
+    if (!r) r = selhip_ctx_set_measure(ctx, measure);
     if (!r) r = selhip_ctx_set_allpairs_topk(ctx, top_k);
     if (!r) r = selhip_ctx_run(ctx, mode, algo, threshold, n_rows, n_bands, 0, n);
     if (!r) {
@@ -234,25 +243,29 @@ int main(int argc, char* argv[]) {
     std::string criterion = "smh_a";
     int threads = 8, n_gpus = 1, mode = SELHIP_MODE_CB_SMH, algo = SELHIP_ALGO_AUTO, fp_mode = SELHIP_FP_FMA;
     long long ooc_block = 0;
-    std::string out_file = "", dump_file = "", query_file = "", pair_file = "", matrix_file = "", estimator = "";
+    std::string out_file = "", dump_file = "", query_file = "", pair_file = "", matrix_file = "", estimator = "", measure_name = "";
+    bool measure_given = false;
     bool gpus_given = false, topk_given = false, nbr_given = false, matrix_given = false, union_measure = false, aux_given = false, estimator_given = false;
     const char* selection_opt = nullptr;         // the first of -h, -c, -n, -A seen: options of a selection pass, which -M does not run
     long long top_k = 0, nbr_k = 0, min_matches = 0;
     bool cmin_given = false;
     int c;
-    while ((c = getopt(argc, argv, "xl:b:a:h:c:C:t:g:nA:F:B:o:r:q:k:K:p:M:UE:")) != -1) {
+    while ((c = getopt(argc, argv, "xl:b:a:h:c:C:t:g:nA:F:B:o:r:q:k:K:p:M:UE:S:")) != -1) {
         switch (c) {
             case 'x': std::cout << "Usage: -l -h -a -b [-c smh_a|hll_a|hll_an|none|smh_c -C c_min] [-t threads] [-g gpus] [-n] [-A auto|stream|sig] [-F 0|1] [-B block] [-o file] | -r file\n"
                                    "       -l db_list -q query_list -h -a [-c smh_a|hll_a|hll_an|none|smh_c -C c_min] [-n] [-A auto|stream|sig|index] [-F 0|1] [-k best_per_query]   (query-vs-database selection)\n"
                                    "       -l -h -a [-c smh_a|hll_a|hll_an|none|smh_c -C c_min] [-n] [-A auto|stream|sig|hashjoin] [-F 0|1] -K best_per_genome   (every genome's best partners, both members of a pair)\n"
                                    "       -l list -p pair_file -h -a [-c smh_a|hll_a|hll_an|none|smh_c -C c_min] [-n] [-A auto|stream|sig] [-F 0|1] [-o file]   (only the listed pairs; lines 'path1 path2 ...')\n"
                                    "       -l list [-q query_list] [-F 0|1] -M out.tsv [-U]   (no selection: the dense Jaccard -- -U: union size -- matrix, file-list order)\n"
-                                   "       -l list [-q query_list] -M out.tsv -E smh|smh_matches -a bytes   (the same table from the SuperMinHash sketches: equal buckets / m, or their count)\n"; return 0;
+                                   "       -l list [-q query_list] -M out.tsv -E smh|smh_matches -a bytes   (the same table from the SuperMinHash sketches: equal buckets / m, or their count)\n"
+                                   "       ... -n -S max_containment [-c smh_a|none|smh_c]   (with -l, -q, -p, -k, -K: select and print I / min(e1, e2), the share of the smaller genome found in the larger)\n"
+                                   "       -l list [-q query_list] -M out.tsv -S intersection|containment|max_containment   (the table of I = e1 + e2 - U, I / e_row or I / min(e_row, e_col))\n"; return 0;
             case 'q': query_file = optarg; break;
             case 'p': pair_file = optarg; break;
             case 'M': matrix_file = optarg; matrix_given = true; break;
             case 'U': union_measure = true; break;
             case 'E': estimator = optarg; estimator_given = true; break;
+            case 'S': measure_name = optarg; measure_given = true; break;
             case 'k': top_k = std::strtoll(optarg, nullptr, 10); topk_given = true; break;
             case 'K': nbr_k = std::strtoll(optarg, nullptr, 10); nbr_given = true; break;
             case 'B': ooc_block = std::stoll(optarg); break;
@@ -272,6 +285,43 @@ int main(int argc, char* argv[]) {
             default: break;
         }
     }
+    // -S: checked before any file is read or device opened
+    int pass_measure = SELHIP_MEASURE_JACCARD, matrix_measure = SELHIP_MEASURE_JACCARD;
+    if (measure_given) {
+        const bool matrix_only = measure_name == "intersection" || measure_name == "containment";
+        if (measure_name != "jaccard" && measure_name != "max_containment" && !matrix_only) {
+            std::cerr << "selection: -S (the measure): jaccard or max_containment, with -M also intersection or containment, not '" << measure_name << "'\n";
+            return 2;
+        }
+        if (matrix_only && !matrix_given) {
+            std::cerr << "selection: -S " << measure_name << " is a measure of -M (the dense similarity matrix); a selection pass takes -S jaccard or -S max_containment\n";
+            return 2;
+        }
+        matrix_measure = measure_name == "intersection" ? SELHIP_MEASURE_INTERSECTION : measure_name == "containment" ? SELHIP_MEASURE_CONTAINMENT
+                       : measure_name == "max_containment" ? SELHIP_MEASURE_MAX_CONTAINMENT : SELHIP_MEASURE_JACCARD;
+        if (union_measure) { std::cerr << "selection: -S (the measure) cannot be combined with -U: the union size is a measure of its own\n"; return 2; }
+        if (estimator_given && estimator != "hll") {
+            std::cerr << "selection: -S (a measure from the HyperLogLog sketches) cannot be combined with -E " << estimator << "\n";
+            return 2;
+        }
+        if (!matrix_given && measure_name == "max_containment") {
+            pass_measure = SELHIP_MEASURE_MAX_CONTAINMENT;
+            if (mode != SELHIP_MODE_SMH) {
+                std::cerr << "selection: -S max_containment needs -n: the CB bound is a bound on J and cuts the pairs of unequal size the measure exists for\n";
+                return 2;
+            }
+            if (criterion == "hll_a" || criterion == "hll_an") {
+                std::cerr << "selection: -S max_containment cannot be combined with -c " << criterion << ": its bound is derived for J (use -c smh_a, none or smh_c)\n";
+                return 2;
+            }
+            const char* clash = gpus_given ? "-g" : ooc_block != 0 ? "-B" : !out_file.empty() ? "-o" : nullptr;
+            if (clash) {
+                std::cerr << "selection: -S max_containment cannot be combined with " << clash
+                          << "; the multi-GPU and out-of-core drivers carry no measure and the result file records none\n";
+                return 2;
+            }
+        }
+    }
     if (matrix_given) {
         // checked before any file is read or device opened
         const char* clash = !pair_file.empty() ? "-p" : topk_given ? "-k" : nbr_given ? "-K" : gpus_given ? "-g" : ooc_block != 0 ? "-B"
@@ -282,7 +332,7 @@ int main(int argc, char* argv[]) {
             return 2;
         }
         if (list_file.empty()) { std::cerr << "selection: -M needs the list of genomes (-l)\n"; return 2; }
-        int measure = union_measure ? SELHIP_MEASURE_UNION : SELHIP_MEASURE_JACCARD;
+        int measure = union_measure ? SELHIP_MEASURE_UNION : matrix_measure;
         unsigned m_smh = 0;
         if (estimator_given && estimator != "hll") {
             if (estimator != "smh" && estimator != "smh_matches") {
@@ -354,7 +404,7 @@ int main(int argc, char* argv[]) {
             return 2;
         }
         if (list_file.empty()) { std::cerr << "selection: -q needs the database list (-l)\n"; return 2; }
-        return run_queries(query_file, list_file, criterion, threshold, aux_bytes, mode, algo, fp_mode, threads, (int)top_k, (int)min_matches);
+        return run_queries(query_file, list_file, criterion, threshold, aux_bytes, mode, algo, fp_mode, threads, (int)top_k, (int)min_matches, pass_measure);
     }
     if (algo == SELHIP_ALGO_INDEX) {
         // checked before any file is read or device opened
@@ -383,7 +433,7 @@ int main(int argc, char* argv[]) {
         return 0;
     }
     if (list_file.empty()) { std::cerr << "No input file provided\n"; exit(-1); }   // selection.cpp:40-44
-    if (nbr_given) return run_neighbours(list_file, crit, threshold, aux_bytes, mode, algo, fp_mode, threads, (int)nbr_k, (int)min_matches);
+    if (nbr_given) return run_neighbours(list_file, crit, threshold, aux_bytes, mode, algo, fp_mode, threads, (int)nbr_k, (int)min_matches, pass_measure);
     const bool reads_smh = crit == SELHIP_CRIT_SMH_A || crit == SELHIP_CRIT_SMH_C;
     const unsigned m = reads_smh ? (unsigned)aux_bytes / 8 : 0;                                      // selection.cpp:231
     const unsigned p_aux = reads_smh || crit == SELHIP_CRIT_NONE ? 0 : (unsigned)__builtin_ctz(aux_bytes ? aux_bytes : 1);   // :125
@@ -448,6 +498,7 @@ int main(int argc, char* argv[]) {
         if (!r && p_aux) r = selhip_ctx_upload_aux_hll(ctx, selhost_dataset_aux_hll(ds), (int)p_aux);
         if (!r) r = selhip_ctx_set_criterion(ctx, crit);
         if (!r && crit == SELHIP_CRIT_SMH_C) r = selhip_ctx_set_min_matches(ctx, (int)min_matches);
+        if (!r) r = selhip_ctx_set_measure(ctx, pass_measure);
         void* d_list = nullptr;
         if (!r && !pair_file.empty()) {
             // the listed pairs as ranks of the sorted list, then one pass over them

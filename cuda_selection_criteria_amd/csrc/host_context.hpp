@@ -241,6 +241,8 @@ struct selhip_ctx {
     // last such pass (1 the fast path, 0 the generic one, -1 none yet)
     int min_matches = 0;
     int smhc_path_used = -1;
+    // what stage 2 of every pass tests against tau and records (selhip_ctx_set_measure): SELHIP_MEASURE_JACCARD or _MAX_CONTAINMENT
+    int measure = SELHIP_MEASURE_JACCARD;
 
     // last run parameters (for overflow re-runs)
     bool have_run = false, pending = false;

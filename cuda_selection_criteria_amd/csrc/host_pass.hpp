@@ -66,6 +66,25 @@ int accept_count(selhip_ctx* c) {
     return SELHIP_OK;
 }
 
+// ---- the measure of the passes (selhip_ctx_set_measure) ------------------------------------------
+// what SELHIP_MEASURE_MAX_CONTAINMENT refuses, checked by every entry before it claims a counter set: the CB bound and the auxiliary-HLL
+// criteria are bounds on J -- e_small / e_large >= tau is necessary for J >= tau, not for I / e_small >= tau -- and would silently drop
+// the pairs of unequal size that the measure exists for.  (smh_a and smh_c test bucket equality, not J: the caller's choice.)
+int accept_measure(selhip_ctx* c, int mode) {
+    if (c->measure == SELHIP_MEASURE_JACCARD) return SELHIP_OK;
+    if (mode == SELHIP_MODE_CB_SMH) {
+        set_err(&c->err, "measure max_containment (SELHIP_MEASURE_MAX_CONTAINMENT) takes no SELHIP_MODE_CB_SMH: the CB bound is a bound on J and "
+                         "cuts pairs of unequal size; pass SELHIP_MODE_SMH");
+        return SELHIP_E_BADARG;
+    }
+    if (aux_criterion(c->criterion)) {
+        set_err(&c->err, "measure max_containment (SELHIP_MEASURE_MAX_CONTAINMENT) takes no auxiliary-HLL criterion (criterion %d: hll_a, hll_an "
+                         "and hll_a + smh_a bound J); use smh_a, smh_c or none", c->criterion);
+        return SELHIP_E_BADARG;
+    }
+    return SELHIP_OK;
+}
+
 // the rows of X (owned rows of rm) against the candidates of Y from first_cand on.  QUERY = false: X = Y = the context's rows, windows
 // from hi and pc_in's z0; QUERY = true: the queries against the database, windows lo / hi
 struct CountSets { const u64* X; const u64* Y; int n_x, n_y; const int* lo; const int* hi; const PassCounters* pc_in; };
@@ -366,11 +385,18 @@ template <int MODE>
 hipError_t launch_select(bool fma, hipStream_t st, unsigned grid, const uint32_t* counts, const u64* n_dev, u64 n_host,
                          u64 cap, int p, double* est, const selhip_int2_t* pairs, const u64* ecard, double tau,
                          selhip_pair_t* results, u64 results_cap, PassCounters* pc,
-                         selhip_result_t* rf32, int* out_count, u64 chunk_off = 0, u64 chunk_len = ~0ull) {
+                         selhip_result_t* rf32, int* out_count, u64 chunk_off = 0, u64 chunk_len = ~0ull, int measure = SELHIP_MEASURE_JACCARD) {
     const double rs = relerr_scaled_for(p);
+    // (the measure of a pass is a template argument: under J the kernel is the one it always was)
     with_flag(fma, [&](auto F) {
-        hipLaunchKernelGGL((ertl_select_kernel<decltype(F)::value, MODE>), dim3((grid + kWavesPerBlock - 1) / kWavesPerBlock), dim3(kBlock), 0, st, counts, n_dev, n_host, cap,
-                           p, rs, est, pairs, ecard, tau, results, results_cap, pc, rf32, out_count, chunk_off, chunk_len);
+        auto launch = [&](auto M) {
+            hipLaunchKernelGGL((ertl_select_kernel<decltype(F)::value, MODE, decltype(M)::value>), dim3((grid + kWavesPerBlock - 1) / kWavesPerBlock), dim3(kBlock), 0, st, counts, n_dev, n_host, cap,
+                               p, rs, est, pairs, ecard, tau, results, results_cap, pc, rf32, out_count, chunk_off, chunk_len);
+        };
+        if constexpr (MODE == 1) {                                           // (the selecting form alone has a measure)
+            if (measure == SELHIP_MEASURE_MAX_CONTAINMENT) { launch(std::integral_constant<int, SELHIP_MEASURE_MAX_CONTAINMENT>{}); return; }
+        }
+        launch(std::integral_constant<int, SELHIP_MEASURE_JACCARD>{});
     });
     return hipGetLastError();
 }
@@ -585,7 +611,7 @@ int enqueue_hist_select(selhip_ctx* c, const Chain& ch, const selhip_int2_t* fin
         TimerScope t(c, T_SELECT, st);
         HIPCHK(&c->err, launch_select<1>(c->fp_mode == SELHIP_FP_FMA, st, 4096, ch.counts, final_count, 0,
                                          final_cap, c->p, nullptr, final_list, c->ecard.p, tau,
-                                         c->results.p, (u64)c->results.cap, pc0, nullptr, nullptr, off, ch.window));
+                                         c->results.p, (u64)c->results.cap, pc0, nullptr, nullptr, off, ch.window, c->measure));
     }
     return SELHIP_OK;
 }
@@ -676,6 +702,7 @@ int enqueue_chain(selhip_ctx* c, const Chain& ch, int rb, int re, double tau, bo
 bool small_pass_ok(const selhip_ctx* c) {
     if (c->small_pass == 0 || c->small_pass_failed) return false;
     if (c->n < 2 || c->n > kSmallPassMaxN || c->criterion != SELHIP_CRIT_SMH_A || c->il_parts > 1) return false;
+    if (c->measure != SELHIP_MEASURE_JACCARD) return false;                  // (the kernel's stage 2 is the J test alone)
     if (!c->plan.use_sig || c->plan.use_hash) return false;
     if (!sig_tile_shape(c->m, c->n_rows, c->n_bands)) return false;          // the kernel always builds in tiles, whatever "sig_tile" says
     if ((c->row_end - c->row_begin + 255) / 256 > kSmallRows) return false;                        // rows per block of the 256-block grid
@@ -742,7 +769,7 @@ void dense_stats(PassCounters* pc) { pc->n_survivors = pc->n_final = pc->n_candi
 // from hi and pc_in's z0), else a query pass (windows lo / hi).  khi = largest register value + 1 of the two sets
 hipError_t launch_dense(bool fma, hipStream_t st, int khi, const DenseSet& X, const DenseSet& Y, int n_y, const int* lo, const int* hi,
                         const PassCounters* pc_in, const RowMap& rm, int first_cand, double tau, selhip_pair_t* results, u64 results_cap,
-                        PassCounters* pc) {
+                        PassCounters* pc, int measure) {
     const long long n_tiles = rm.n_tiles(kWavesPerBlock);
     const int span_base = first_cand / kDenseSpan;
     const long long n_spans = ((long long)n_y + kDenseSpan - 1) / kDenseSpan - span_base;
@@ -751,8 +778,9 @@ hipError_t launch_dense(bool fma, hipStream_t st, int khi, const DenseSet& X, co
     const long long n_units = 8 * n_tiles * ((n_spans + 7) / 8);
     const unsigned grid = (unsigned)std::min<long long>(n_units, 0x7FFFFFF8ll);              // (a multiple of 8; beyond it blocks take several units)
     const double rs = relerr_scaled_for(14);
-    with_flag(fma, [&](auto F) {
-#define SELHIP_DENSE_LAUNCH(NB) hipLaunchKernelGGL((dense_select_kernel<NB, decltype(F)::value>), dim3(grid), dim3(kBlock), 0, st, X, Y, n_y, lo, hi, pc_in, rm, \
+    with_flag(fma, [&](auto F) { with_flag(measure == SELHIP_MEASURE_MAX_CONTAINMENT, [&](auto C) {
+        constexpr int MEAS = decltype(C)::value ? SELHIP_MEASURE_MAX_CONTAINMENT : SELHIP_MEASURE_JACCARD;
+#define SELHIP_DENSE_LAUNCH(NB) hipLaunchKernelGGL((dense_select_kernel<NB, decltype(F)::value, MEAS>), dim3(grid), dim3(kBlock), 0, st, X, Y, n_y, lo, hi, pc_in, rm, \
                                                    (int)n_tiles, span_base, n_units, tau, rs, results, results_cap, pc)
         switch (bs_planes(khi)) {
             case 4:  SELHIP_DENSE_LAUNCH(4); break;
@@ -760,7 +788,7 @@ hipError_t launch_dense(bool fma, hipStream_t st, int khi, const DenseSet& X, co
             default: SELHIP_DENSE_LAUNCH(6);
         }
 #undef SELHIP_DENSE_LAUNCH
-    });
+    }); });
     return hipGetLastError();
 }
 
@@ -769,7 +797,7 @@ int enqueue_dense(selhip_ctx* c, int rb, int re, double tau, PassCounters* pc0) 
     TimerScope t(c, T_DENSE);
     const DenseSet set{c->planes.bs.p, c->planes.gmax.p, c->ecard.p};
     HIPCHK(&c->err, launch_dense(c->fp_mode == SELHIP_FP_FMA, c->stream, c->planes.khi, set, set, (int)c->n, nullptr, c->hi.p, pc0, row_map(c, rb, re),
-                                 std::max(rb + 1, (int)c->cand_begin), tau, c->results.p, (u64)c->results.cap, pc0));
+                                 std::max(rb + 1, (int)c->cand_begin), tau, c->results.p, (u64)c->results.cap, pc0, c->measure));
     return SELHIP_OK;
 }
 

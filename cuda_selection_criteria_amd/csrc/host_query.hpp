@@ -165,7 +165,7 @@ int enqueue_query_pass(selhip_ctx* c, double tau) {
                 TimerScope t(c, T_DENSE);
                 HIPCHK(&c->err, launch_dense(c->fp_mode == SELHIP_FP_FMA, c->stream, std::max(q.planes.khi, planes_d.khi),
                                              DenseSet{q.planes.bs.p, q.planes.gmax.p, q.ecard.p}, DenseSet{planes_d.bs.p, planes_d.gmax.p, q.ecard.p + n_q},
-                                             n_d, q.lo.p, q.hi.p, pc, RowMap{0, n_q, n_q, 1, 0}, 0, tau, c->results.p, (u64)c->results.cap, pc));
+                                             n_d, q.lo.p, q.hi.p, pc, RowMap{0, n_q, n_q, 1, 0}, 0, tau, c->results.p, (u64)c->results.cap, pc, c->measure));
             }
             HIPCHK(&c->err, hipMemcpyAsync(q.h_pc, pc, sizeof(PassCounters), hipMemcpyDeviceToHost, c->stream));
             q.pc.dirty = false;
@@ -265,7 +265,7 @@ int enqueue_query_pass(selhip_ctx* c, double tau) {
         TimerScope t(c, T_SELECT);
         HIPCHK(&c->err, launch_select<1>(c->fp_mode == SELHIP_FP_FMA, c->stream, grid_for(std::min<u64>(window, fcap), kWave, 4096),
                                          q.counts.p, fcnt, 0, fcap, c->p, nullptr, fl, q.ecard.p, tau,
-                                         c->results.p, (u64)c->results.cap, pc, nullptr, nullptr, off, window));
+                                         c->results.p, (u64)c->results.cap, pc, nullptr, nullptr, off, window, c->measure));
     }
     hipLaunchKernelGGL(query_result_fixup_kernel, dim3(grid_for((u64)c->results.cap, kBlock, 1024)), dim3(kBlock), 0, c->stream,
                        c->results.p, &pc->n_results, (u64)c->results.cap, n_q);

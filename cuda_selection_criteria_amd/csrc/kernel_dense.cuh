@@ -50,8 +50,9 @@ __device__ __attribute__((noinline)) double dense_estimate(const uint32_t* col, 
 // lo == nullptr: all-pairs -- row i takes k in [max(i + 1, z0), min(hi[i], n_y - 1)], z0 from pc_in (cb_bounds_kernel: first rank with
 // e != 0, raised to the pass's candidate_begin); else a query pass -- row q takes d in [lo[q], hi[q]] (query_windows_kernel).
 // Block b of the n_units = 8 x n_tiles x (groups of 8 spans): XCD slot x = b % 8, j = b / 8 -> row tile j % n_tiles of span
-// span_base + 8 (j / n_tiles) + x.  Records: {row, candidate, J} with the ranks of their own sets.
-template <int NB, bool FMA>
+// span_base + 8 (j / n_tiles) + x.  Records: {row, candidate, value} with the ranks of their own sets; value = J, or under
+// MEAS = SELHIP_MEASURE_MAX_CONTAINMENT (selhip_ctx_set_measure) I / min(e_row, e_candidate) -- selhip::pair_value either way.
+template <int NB, bool FMA, int MEAS>
 __global__ __launch_bounds__(kBlock, NB <= 5 ? 4 : 2)
 void dense_select_kernel(DenseSet X, DenseSet Y, int n_y, const int* __restrict__ lo, const int* __restrict__ hi,
                          const PassCounters* __restrict__ pc_in, RowMap rm, int n_tiles, int span_base, long long n_units,
@@ -98,7 +99,7 @@ void dense_select_kernel(DenseSet X, DenseSet Y, int n_y, const int* __restrict_
         const bool live = ky >= kb && ky < ke;
         const double t = dense_estimate<FMA>(tile + lane, relerr_scaled);
         const double e1 = (double)X.ecard[i], e2 = live ? (double)Y.ecard[ky] : 0.0;
-        const double jacc = (e1 + e2 - t) / t;                               // selection.cpp:287
+        const double jacc = selhip::pair_value(MEAS, e1, e2, t);             // selection.cpp:287 (pair_value.hpp)
         const bool keep = live && jacc >= tau;                               // selection.cpp:288
         const u64 km = __ballot(keep);
         if (km) {

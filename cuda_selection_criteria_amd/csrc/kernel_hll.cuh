@@ -400,6 +400,8 @@ void frame_results_kernel(const selhip_pair_t* __restrict__ results, const u64* 
 // (pitch 65 -> conflict-free) because the estimator indexes them with run-time k.
 //   MODE 0: est[j] = estimate                                     (selhip_ertl_estimate, cards)
 //   MODE 1: t = estimate; J = ((double)e_x + (double)e_y - t)/t; if (J >= tau) append   (selection.cpp:286-288)
+//           MEAS = the pass's measure (selhip_ctx_set_measure): SELHIP_MEASURE_JACCARD is the line above, instruction for instruction;
+//           SELHIP_MEASURE_MAX_CONTAINMENT tests and records V = selhip::pair_value's I / min(e_x, e_y) in J's place
 //   MODE 2: like 1 but writes selhip_result_t{x,y,(float)J} (drop-in launchers)
 // ---------------------------------------------------------------------------------------------
 struct LdsCounts {
@@ -407,7 +409,7 @@ struct LdsCounts {
     __device__ __forceinline__ uint32_t operator[](int k) const { return base[k * 65]; }
 };
 
-template <bool FMA, int MODE>
+template <bool FMA, int MODE, int MEAS = SELHIP_MEASURE_JACCARD>
 __global__ __launch_bounds__(kBlock)
 void ertl_select_kernel(const uint32_t* __restrict__ counts, const u64* __restrict__ n_dev, u64 n_host, u64 cap,
                         int p, double relerr_scaled,
@@ -462,7 +464,7 @@ void ertl_select_kernel(const uint32_t* __restrict__ counts, const u64* __restri
             if (j < n) est[j] = t;
         } else {
             const double e1 = (double)ec1, e2 = (double)ec2;
-            const double jacc = (e1 + e2 - t) / t;                           // selection.cpp:287
+            const double jacc = selhip::pair_value(MEAS, e1, e2, t);         // selection.cpp:287 (pair_value.hpp)
             const bool keep = j < n && jacc >= tau;                          // selection.cpp:288
             // one global append per block: a wave reserves its slots in the block's tally (LDS), thread 0 reserves the block's
             // range in the output list

@@ -10,7 +10,10 @@
 // A self matrix (X = Y) computes every pair once: row i of the slab [r0, r1) takes the columns [0, r0) u [i, n) (matrix_computes) and
 // stores the cells i < k < r1 a second time at (k, i) (matrix_mirrors).  The cell is bit-symmetric -- e_a + e_b commutes, the
 // histogram is that of a register-wise maximum, kp = max(gmax_a, gmax_b) + 1 -- so the mirror is a saving, not a definition.
-// The diagonal is computed like any cell (U(i, i)); the Jaccard measure stores exactly 1.0 there.
+// The diagonal is computed like any cell (U(i, i), I(i, i)); the Jaccard measure and the two containments store exactly 1.0 there.
+// Measures: U itself, or selhip::pair_value (pair_value.hpp) of U and the two truncated cardinalities -- J, the intersection estimate I,
+// the containment I / e_row (not symmetric: the mirrored store at (k, i) writes I / e_k from the same U) and the max containment
+// I / min(e_row, e_col); a containment with an empty sketch in its denominator is NaN.
 // Positions: row_pos (indexed by rank - r0) / col_pos (indexed by rank) are the HOST-VALIDATED copies of the caller's arrays, nullptr =
 // the defaults rank - r0 / rank; every store address is 64-bit arithmetic on validated values.
 #pragma once
@@ -77,17 +80,19 @@ void matrix_kernel(MatrixSet X, MatrixSet Y, int r0, int r1, int n_y, int n_tile
         const bool live = ky < ke && (!o.self || matrix_computes(r0, i, ky));
         const double t = dense_estimate<FMA>(tile + lane, relerr_scaled);
         if (live) {
-            double v = t;
-            if (o.measure == SELHIP_MEASURE_JACCARD) {
+            double v = t, vm = t;                                            // the cell and its mirror image (k, i)
+            if (o.measure != SELHIP_MEASURE_UNION) {
                 const double e1 = (double)selhip::trunc_card(X.cards[i]), e2 = (double)selhip::trunc_card(Y.cards[ky]);
-                v = (e1 + e2 - t) / t;                                       // selection.cpp:287
-                if (o.self && ky == i) v = 1.0;
+                v = vm = selhip::pair_value(o.measure, e1, e2, t);           // selection.cpp:287 (pair_value.hpp)
+                // the one measure that is not symmetric: the mirrored cell is the share of genome k, from the same U
+                if (o.measure == SELHIP_MEASURE_CONTAINMENT) vm = selhip::pair_value(SELHIP_MEASURE_CONTAINMENT, e2, e1, t);
+                if (o.self && ky == i && o.measure != SELHIP_MEASURE_INTERSECTION) v = 1.0;
             }
             const size_t pos_r = (size_t)(o.row_pos ? o.row_pos[i - r0] : i - r0), pos_c = (size_t)(o.col_pos ? o.col_pos[ky] : ky);
             out[pos_r * (size_t)o.ld + pos_c] = (OutT)v;
             if (o.self && o.mirror && matrix_mirrors(i, ky, r1)) {
                 const size_t m_r = (size_t)(o.row_pos ? o.row_pos[ky - r0] : ky - r0), m_c = (size_t)(o.col_pos ? o.col_pos[i] : i);
-                out[m_r * (size_t)o.ld + m_c] = (OutT)v;
+                out[m_r * (size_t)o.ld + m_c] = (OutT)vm;
             }
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");               // the next unit's stores come after these reads

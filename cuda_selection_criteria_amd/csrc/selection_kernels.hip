@@ -8,6 +8,8 @@
 // This is the kernel translation unit of the library: it only includes.  The kernels live in the kernel_*.cuh headers (all integer
 // except the estimator; no MFMA), the host side in host_plan.hpp (decisions), host_context.hpp (context), host_pass.hpp (pass scheduler) and abi_*.inc (C ABI);
 // the multi-GPU and out-of-core drivers are translation units of their own (selhip_multi.hip, selhip_ooc.hip):
+//   pair_value.hpp      selhip::pair_value: what a pair's value is under J, the intersection estimate and the two containments -- the one
+//                       definition that stage 2 (kernel_hll.cuh, kernel_dense.cuh) and kernel_matrix.cuh call
 //   common.cuh          launch constants, per-pass counters, WaveAppender / block_append (LDS-staged appends, one atomic per flush)
 //   kernel_bounds.cuh   cb_bounds_kernel      e_i = (size_t)card_i, CB cut-off hi(i), first non-zero rank
 //   kernel_verify.cuh   smh_a_lane (the literal predicate), sig_candidate_ok (the one statement of "signature equal, band not equal"),
@@ -31,7 +33,7 @@
 //                       binary search per (query, band) in place of the rectangular join
 //   kernel_dense.cuh    dense_select_kernel: criterion "none" -- every pair of the (CB-pruned) pair space to the Jaccard test, union
 //                       histograms into an LDS tile and the estimator in one launch
-//   kernel_matrix.cuh   matrix_kernel: the union size or the Jaccard estimate of every pair as a dense array (the middle of
+//   kernel_matrix.cuh   matrix_kernel: the union size, the Jaccard estimate, the intersection estimate or a containment of every pair as a dense array (the middle of
 //                       dense_select_kernel over a rectangle, typed and mirrored stores; selhip_ctx_matrix / _query_matrix)
 //   kernel_matrix_smh.cuh  matrix_smh_kernel / matrix_smh_generic_kernel: the SuperMinHash bucket-match count, or count / m, of every
 //                       pair as a dense array (query rows in VGPRs, candidate rows streamed past them; the same entry points)
@@ -63,6 +65,7 @@
 #include "../../include/selection_hip.h"
 #include "selhip_internal.h"
 #include "ertl_mle.hpp"
+#include "pair_value.hpp"      // the value of a pair under every HLL measure (J, intersection, containments): one definition
 #include "synth.hpp"
 
 #include "common.cuh"

@@ -12,7 +12,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import (ALGO_AUTO, BANDING_CPU, CRIT_HLL_A, CRIT_HLL_AN, CRIT_HLL_A_SMH_A, CRIT_NONE, CRIT_SMH_A, CRIT_SMH_C, F32, F64, FP_FMA,
-                   MEASURE_JACCARD, MEASURE_SMH_JACCARD, MEASURE_SMH_MATCHES, MEASURE_UNION, MODE_CB_SMH, Pair, check, hip_lib, host_lib)
+                   MEASURE_CONTAINMENT, MEASURE_INTERSECTION, MEASURE_JACCARD, MEASURE_MAX_CONTAINMENT, MEASURE_SMH_JACCARD,
+                   MEASURE_SMH_MATCHES, MEASURE_UNION, MODE_CB_SMH, Pair, check, hip_lib, host_lib)
 
 # layout of selhip_pair_t {int32 i, k; double jaccard}
 PAIR_DTYPE = np.dtype([("i", "<i4"), ("k", "<i4"), ("jaccard", "<f8")], align=True)
@@ -316,6 +317,16 @@ class Selector:
         are equal (c >= 1; a pass refuses c > m).  min_matches(m, j) gives the c of a SuperMinHash Jaccard estimate j"""
         check(self._lib.selhip_ctx_set_min_matches(self._ctx, int(c)), self._ctx)
 
+    def set_measure(self, measure):
+        """what stage 2 of the following passes (run, run_queries, run_pairs and their top-ks) tests against tau and records in the
+        `jaccard` field: "jaccard" (the default) or "max_containment" -- I / min(e_i, e_k) with I = e_i + e_k - U, the share of the
+        smaller genome found in the larger one -- or the MEASURE_* code of either.  Sticky, like the criterion.  Under
+        "max_containment" a pass refuses MODE_CB_SMH and the hll_a / hll_an / two-stage criteria (bounds on J): MODE_SMH with
+        CRIT_NONE, CRIT_SMH_A or CRIT_SMH_C"""
+        code = measure_code(measure)
+        check(self._lib.selhip_ctx_set_measure(self._ctx, code), self._ctx)
+        self.measure = code
+
     def cards(self) -> np.ndarray:
         out = np.empty(self.n, dtype=np.float64)
         check(self._lib.selhip_ctx_get_cards(self._ctx, out.ctypes.data), self._ctx)
@@ -430,7 +441,9 @@ class Selector:
     def matrix(self, measure="jaccard", dtype=None, rows: Optional[Tuple[int, int]] = None, row_pos=None, col_pos=None, out=None):
         """the similarity of every pair of the context's sketches as a torch tensor on the device (selhip_ctx_matrix): measure
         "jaccard" (J of the passes, bit for bit; exactly 1.0 on the diagonal; NaN for two empty sketches), "union" (the union
-        estimate U, also on the diagonal), "smh_matches" (the number of equal SuperMinHash buckets of the pair, 0 .. m) or "smh_jaccard"
+        estimate U, also on the diagonal), "intersection" (I = e_row + e_col - U, also on the diagonal), "containment" (I / e_row, the
+        share of the row genome found in the column genome: not symmetric, NaN for an empty row sketch, 1.0 on the diagonal),
+        "max_containment" (I / min(e_row, e_col), the value of the passes under set_measure; 1.0 on the diagonal), "smh_matches" (the number of equal SuperMinHash buckets of the pair, 0 .. m) or "smh_jaccard"
         (that count / m: the SuperMinHash estimate of J; both from the bucket rows alone, whatever p_hll), dtype torch.float64 (default) or torch.float32.  rows = (r0, r1): only that slab of rows.
         row_pos / col_pos: host int32 arrays indexed by rank -- the cell of rank-row i and rank-column k goes to
         out[row_pos[i], col_pos[k]] (defaults i - r0 and k).  out: a caller's 2-D tensor (stride(1) == 1; stride(0) is its leading
@@ -538,13 +551,16 @@ def _criterion_files(criterion: str, aux_bytes: int, min_matches: Optional[int] 
 
 def select_from_filelist(list_file: str, tau: float, aux_bytes: int, mode: int = MODE_CB_SMH, device: int = 0,
                          fp_mode: int = FP_FMA, algo: int = ALGO_AUTO, criterion: str = "smh_a", top_k: int = 0,
-                         min_matches: Optional[int] = None) -> str:
+                         min_matches: Optional[int] = None, measure="jaccard") -> str:
     """The whole of selection_cuda.cpp main() (criterion smh_a) -- and of selection.cpp's hll_a / hll_an
     branches (:122-227): returns the text the CPU reference prints for `-c criterion -a aux_bytes -h tau`.
     criterion "none": no criterion in front of the Jaccard test (CRIT_NONE; mode MODE_CB_SMH = the CB bound alone, MODE_SMH = every pair).
     criterion "smh_c" with min_matches = c: at least c of the m = aux_bytes / 8 SuperMinHash buckets equal (CRIT_SMH_C; `-c smh_c -C c`).
     top_k > 0: only every genome's top_k best partners, one line 'owner_path partner_path J' each, in ranked order (owner rank, then J
-    descending, ties by partner rank): a selected pair can be printed twice (once per member), once or not at all."""
+    descending, ties by partner rank): a selected pair can be printed twice (once per member), once or not at all.
+    measure "max_containment": the pairs with I / min(e_i, e_k) >= tau, that value printed in J's place (Selector.set_measure;
+    ValueError with mode=MODE_CB_SMH or an hll_* criterion)."""
+    meas = _pass_measure(measure, mode, criterion)
     m, p_aux, crit = _criterion_files(criterion, aux_bytes, min_matches)
     ds = load_dataset(list_file, m, p_aux, fp_mode)
     n_rows, n_bands = banding(m, tau) if m else (1, 1)
@@ -556,20 +572,37 @@ def select_from_filelist(list_file: str, tau: float, aux_bytes: int, mode: int =
         sel.set_criterion(crit)
         if crit == CRIT_SMH_C:
             sel.set_min_matches(min_matches)
+        sel.set_measure(meas)
         pairs = sel.run(tau, mode, n_rows, n_bands, algo=algo, top_k=top_k if top_k else None)
     return format_lines(ds.names, pairs)
 
 
-MEASURES = {"jaccard": MEASURE_JACCARD, "union": MEASURE_UNION, "smh_matches": MEASURE_SMH_MATCHES, "smh_jaccard": MEASURE_SMH_JACCARD}
+MEASURES = {"jaccard": MEASURE_JACCARD, "union": MEASURE_UNION, "smh_matches": MEASURE_SMH_MATCHES, "smh_jaccard": MEASURE_SMH_JACCARD,
+            "intersection": MEASURE_INTERSECTION, "containment": MEASURE_CONTAINMENT, "max_containment": MEASURE_MAX_CONTAINMENT}
 SMH_MEASURES = (MEASURE_SMH_MATCHES, MEASURE_SMH_JACCARD)
+PASS_MEASURES = ("jaccard", "max_containment")          # what Selector.set_measure and the `measure=` of the file-list helpers take
 
 
 def measure_code(measure) -> int:
     """the SELHIP_MEASURE_* code of a measure given by name or by code; ValueError for anything else"""
     code = MEASURES.get(measure) if isinstance(measure, str) else measure
     if isinstance(code, bool) or not isinstance(code, (int, np.integer)) or code not in MEASURES.values():
-        raise ValueError("measure: 'jaccard', 'union', 'smh_matches' or 'smh_jaccard'")
+        raise ValueError("measure: 'jaccard', 'union', 'intersection', 'containment', 'max_containment', 'smh_matches' or 'smh_jaccard'")
     return int(code)
+
+
+def _pass_measure(measure, mode: int, criterion: str) -> int:
+    """the code of a pass's measure for the file-list helpers; ValueError for a matrix-only measure and for what max containment
+    refuses -- MODE_CB_SMH and the hll_* criteria are bounds on J -- before any file is read"""
+    code = measure_code(measure)
+    if code not in (MEASURE_JACCARD, MEASURE_MAX_CONTAINMENT):
+        raise ValueError("measure of a pass: 'jaccard' or 'max_containment' (the other measures are matrix measures)")
+    if code == MEASURE_MAX_CONTAINMENT:
+        if mode == MODE_CB_SMH:
+            raise ValueError("measure 'max_containment' takes no MODE_CB_SMH: the CB bound is a bound on J and cuts pairs of unequal size; pass mode=MODE_SMH")
+        if criterion in ("hll_a", "hll_an"):
+            raise ValueError(f"measure 'max_containment' takes no criterion {criterion}: its bound is derived for J; use smh_a, smh_c or none")
+    return code
 
 
 def _matrix_buckets(measure, aux_bytes: int) -> int:
@@ -637,9 +670,10 @@ def read_pair_list(pair_file: str, names: Sequence[str]) -> np.ndarray:
 
 def select_pairs_from_filelist(list_file: str, pair_file: str, tau: float, aux_bytes: int, mode: int = MODE_CB_SMH, device: int = 0,
                                fp_mode: int = FP_FMA, algo: int = ALGO_AUTO, criterion: str = "smh_a",
-                               min_matches: Optional[int] = None) -> str:
+                               min_matches: Optional[int] = None, measure="jaccard") -> str:
     """select_from_filelist restricted to the pairs listed in pair_file (lines 'path1 path2[ anything]' with paths of list_file, in
-    either order): the text `selection -l list_file -p pair_file -c criterion -a aux_bytes -h tau` prints"""
+    either order): the text `selection -l list_file -p pair_file -c criterion -a aux_bytes -h tau` prints (measure as there: `-S`)"""
+    meas = _pass_measure(measure, mode, criterion)
     m, p_aux, crit = _criterion_files(criterion, aux_bytes, min_matches)
     ds = load_dataset(list_file, m, p_aux, fp_mode)
     listed = read_pair_list(pair_file, ds.names)
@@ -651,6 +685,7 @@ def select_pairs_from_filelist(list_file: str, pair_file: str, tau: float, aux_b
         sel.set_criterion(crit)
         if crit == CRIT_SMH_C:
             sel.set_min_matches(min_matches)
+        sel.set_measure(meas)
         pairs = sel.run_pairs(listed, tau, mode, n_rows, n_bands, algo=algo)
     return format_lines(ds.names, pairs)
 
@@ -716,13 +751,15 @@ def ooc_select(hll: np.ndarray, aux: np.ndarray, cards: np.ndarray, tau: float, 
 
 def query_from_filelists(query_list: str, db_list: str, tau: float, aux_bytes: int, mode: int = MODE_CB_SMH, fp_mode: int = FP_FMA,
                          device: int = 0, algo: int = ALGO_AUTO, criterion: str = "smh_a", top_k: int = 0,
-                         min_matches: Optional[int] = None) -> str:
+                         min_matches: Optional[int] = None, measure="jaccard") -> str:
     """Query-vs-database selection: both lists are loaded and sorted by cardinality (load_dataset); returns one line
     'query_path db_path J' per selected pair, in (query rank, database rank) order, J formatted as selection.cpp prints it.
     top_k > 0: only every query's top_k best pairs, in ranked order (query rank, then J descending, ties by database rank).
     criterion "smh_a" (m = aux_bytes / 8 buckets), "hll_a" / "hll_an" (auxiliary HLL p = ctz(aux_bytes), as select_from_filelist) or
     "none" (every pair of the CB windows -- MODE_SMH: every cross pair -- to the Jaccard test) or "smh_c" with min_matches = c (at least
-    c of the m = aux_bytes / 8 buckets equal)."""
+    c of the m = aux_bytes / 8 buckets equal).  measure "max_containment": the value tested and printed is I / min(e_q, e_d)
+    (Selector.set_measure; ValueError with mode=MODE_CB_SMH or an hll_* criterion)."""
+    meas = _pass_measure(measure, mode, criterion)
     m, p_aux, crit = _criterion_files(criterion, aux_bytes, min_matches)
     qs = load_dataset(query_list, m, p_aux, fp_mode)
     db = load_dataset(db_list, m, p_aux, fp_mode)
@@ -737,6 +774,7 @@ def query_from_filelists(query_list: str, db_list: str, tau: float, aux_bytes: i
         sel.set_criterion(crit)
         if crit == CRIT_SMH_C:
             sel.set_min_matches(min_matches)
+        sel.set_measure(meas)
         pairs = sel.run_queries(tau, mode, n_rows, n_bands, algo, top_k=top_k if top_k else None)
     h = host_lib()
     buf = C.create_string_buffer(16384)

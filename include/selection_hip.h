@@ -45,6 +45,7 @@ typedef struct { int32_t x, y; float sim; } selhip_result_t;
 /* == CUDA int2 used for the pair list (wrapper.hpp:16) */
 typedef struct { int32_t x, y; } selhip_int2_t;
 /* full-precision output record of the context API: the CPU path prints J with std::to_string(double) */
+/* (`jaccard` carries the value of the pass's MEASURE: J by default, the max containment after selhip_ctx_set_measure) */
 typedef struct { int32_t i, k; double jaccard; } selhip_pair_t;
 
 /* modes, after the two timed regions of experiments/src/time_smh.cpp:229-257 / :261-292 */
@@ -257,6 +258,27 @@ int selhip_ctx_set_criterion(selhip_ctx* ctx, int criterion);
  * signatures carry no c_min, refuse it.  get_param "smhc_path_used": the stage-1 kernel of the last such pass, 1 = the fast path
  * (m = 128, 256, 512, 1024), 0 = the generic one, -1 = none yet.  The stage is timed as "stage1". */
 int selhip_ctx_set_min_matches(selhip_ctx* ctx, int c_min);
+/* The MEASURE that stage 2 of the following passes tests against tau_f and records (sticky like the criterion; survives uploads):
+ *   SELHIP_MEASURE_JACCARD (default)    J = I / U with I = (double)e_i + (double)e_k - U      (selection.cpp:287; nothing changes)
+ *   SELHIP_MEASURE_MAX_CONTAINMENT      V = I / d, d = min(e_i, e_k): the share of the SMALLER genome found in the larger one -- the
+ *                                       measure for pairs of unequal size (a plasmid, phage or fragment inside a genome, a draft inside
+ *                                       its complete assembly), whose J can never exceed e_small / e_large.
+ * I is J's numerator as the kernels spell it (left to right, f64, no fused operation), so J and I / U share their bits; no clamp and
+ * no abs, as for J: estimator noise may give V < 0 or V > 1.  A pair that reaches stage 2 is selected iff d != 0 && V >= (double)tau_f
+ * and its record is {i, k, V}: the `jaccard` field of selhip_pair_t carries the measure.  The pair spaces stay as they are and so do
+ * stats[0..3]; a pair with d == 0 counts as evaluated and as a survivor and is never selected.  The measure is symmetric, so the
+ * invariant of the query passes holds (records = the cross pairs of the all-pairs result over Q u D) and the order of an entry's
+ * ranks in a pair list does not matter.  Taken by selhip_ctx_run / _run_async (row ranges, row interleave, candidate begin, pipeline),
+ * selhip_ctx_run_queries, selhip_ctx_run_pairs / _async and the two top-ks behind them (which rank by the record's value, ties as
+ * before), under SELHIP_CRIT_NONE, _SMH_C and _SMH_A with every algorithm.  smh_a and smh_c are prefilters on bucket equality, tuned
+ * for J: in front of the containment test they cost recall on pairs of unequal size -- the caller's choice.
+ * Refused with SELHIP_E_BADARG and a message naming the measure, before anything is enqueued (the context stays fully usable):
+ *   SELHIP_MODE_CB_SMH -- the CB bound e_small / e_large >= tau is a bound on J and would cut exactly the pairs this measure exists
+ *   for: pass SELHIP_MODE_SMH --, and SELHIP_CRIT_HLL_A, _HLL_AN, _HLL_A_SMH_A, whose bounds are derived for J.
+ * Any other measure code: SELHIP_E_BADARG.  SELHIP_E_STATE while a pass is pending.  The one-launch pass of a small set has the J
+ * test only: under max containment the regular pass runs (get_param "small_pass_used" reads 0).  The drop-in launchers,
+ * selhip_multi_select and selhip_ooc_select carry no measure: J.  A context that never calls this launches what it always did. */
+int selhip_ctx_set_measure(selhip_ctx* ctx, int measure);
 
 /* report() of every genome (Ertl-MLE, hll.h:834-837,862) computed on the device: d_cards_out[n]. */
 int selhip_hll_cards(selhip_ctx* ctx, const uint8_t* d_hll, int64_t n_genomes, int p, double* d_cards_out);
@@ -505,6 +527,15 @@ int selhip_ctx_run_pairs_async(selhip_ctx* ctx, const selhip_int2_t* d_pairs, in
  *       truncated cardinalities) for every pair without exception: two empty sketches give NaN, and the matrix holds that NaN.
  *     On the diagonal of a self matrix UNION stores U(i, i), computed like any cell; JACCARD stores exactly 1.0.  dtype SELHIP_F64
  *     carries the bits the passes' records carry, SELHIP_F32 is (float) of that value.  A self matrix is bit-symmetric.
+ *     Three more measures come from the same U and the same numerator I = (double)e_a + (double)e_b - U (csrc/pair_value.hpp):
+ *       SELHIP_MEASURE_INTERSECTION stores I, the inclusion-exclusion estimate of |A n B|; its diagonal is computed like any cell;
+ *       SELHIP_MEASURE_CONTAINMENT stores I / e_a, the share of the ROW genome found in the column genome -- in a query matrix the
+ *       query inside the database genome, the question of `mash screen`.  It is NOT symmetric; it is NaN when e_a == 0; on the
+ *       diagonal of a self matrix it is exactly 1.0.  A self matrix still computes each pair once: the mirrored store at (b, a)
+ *       writes I / e_b from the same U, bit-equal to that cell computed on its own (IEEE addition commutes);
+ *       SELHIP_MEASURE_MAX_CONTAINMENT stores I / min(e_a, e_b), the value the passes record after selhip_ctx_set_measure: symmetric,
+ *       NaN when min(e_a, e_b) == 0, exactly 1.0 on the diagonal of a self matrix.
+ *     No clamp: estimator noise may put a containment below 0 or above 1.  These three work and are refused wherever JACCARD is.
  *     Two more measures read the OTHER sketch of every genome, its m SuperMinHash buckets (aux, u64 [n][m]; components (j << 32) | r):
  *       c(a, b) = #{ j < m : aux_a[j] == aux_b[j] }, compared on the full 64 bits -- buckets that differ in one dword only are unequal;
  *       SELHIP_MEASURE_SMH_MATCHES stores c as a number (0, 1, ..., m); SELHIP_MEASURE_SMH_JACCARD stores (double)c / (double)m, the
@@ -525,7 +556,7 @@ int selhip_ctx_run_pairs_async(selhip_ctx* ctx, const selhip_int2_t* d_pairs, in
  *     the message -- and only the checked copies reach the device.  Two rows (columns) sent to the same position is not an error:
  *     which one lands there is unspecified.  Cells of out_dev that no (row, column) of the call maps to are not written.
  *     SELHIP_E_BADARG also for: ld < out_cols, r0 > r1 or a range outside the set, a NULL or misaligned out_dev with cells to write, an
- *     unknown measure or dtype, a query matrix without attached queries, and -- for the two HLL measures, the rule of
+ *     unknown measure or dtype, a query matrix without attached queries, and -- for the HLL measures, the rule of
  *     SELHIP_CRIT_NONE -- sketches with p_hll != 14 or without resident bit planes ("hist_algo" 0).  n == 0 or r0 == r1: SELHIP_OK, nothing is written
  *     (the arguments above are checked all the same, except that out_dev may then be NULL and no position is read).
  *     SELHIP_E_STATE while a pass is pending.
@@ -537,6 +568,9 @@ int selhip_ctx_run_pairs_async(selhip_ctx* ctx, const selhip_int2_t* d_pairs, in
 #define SELHIP_MEASURE_UNION    1
 #define SELHIP_MEASURE_SMH_MATCHES 16
 #define SELHIP_MEASURE_SMH_JACCARD 17
+#define SELHIP_MEASURE_INTERSECTION    32
+#define SELHIP_MEASURE_CONTAINMENT     33
+#define SELHIP_MEASURE_MAX_CONTAINMENT 34   /* also a measure of the passes: selhip_ctx_set_measure */
 #define SELHIP_F64              0
 #define SELHIP_F32              1
 int selhip_ctx_matrix(selhip_ctx* ctx, int measure, int dtype, int64_t r0, int64_t r1, void* out_dev,
