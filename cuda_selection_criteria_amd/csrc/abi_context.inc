@@ -514,7 +514,7 @@ int selhip_ctx_finish(selhip_ctx* c) {
             // host between passes; a pass records at most ~20 of them)
             if (c->allpairs_topk > 0) {
                 // the pass is accepted and n_results known: every genome keeps its K best partners, on the same stream
-                const int rc = reduce_allpairs_topk(c);
+                const int rc = reduce_topk(c, {c->allpairs_topk, c->n, true, "genome", "genomes"});
                 if (rc) { c->have_run = false; return rc; }
                 c->topk_applied = true;
             }

@@ -158,7 +158,7 @@ int selhip_ctx_run_queries(selhip_ctx* c, int mode, int algo, float tau_f, int n
             if (c->criterion == SELHIP_CRIT_NONE) dense_stats(&c->last);
             if (c->query_topk > 0) {
                 // the pass is accepted and n_results known: every query keeps its K best, on the same stream
-                rc = reduce_query_topk(c);
+                rc = reduce_topk(c, {c->query_topk, c->q.n, false, "query", "queries"});
                 if (rc) { c->have_run = false; return rc; }
                 c->topk_applied = true;
             }

@@ -293,7 +293,7 @@ struct selhip_ctx {
     bool last_was_query = false;        // the results / statistics held are those of a query pass (no framed copies of them)
     // top-k of the query passes (selhip_ctx_set_query_topk; kernel_topk.cuh, host_topk.hpp)
     int query_topk = 0;                 // K: every query keeps its K best records; 0 = off
-    int allpairs_topk = 0;              // K of the all-pairs passes (selhip_ctx_set_allpairs_topk; kernel_nbr.cuh): every genome keeps its K best partners; 0 = off
+    int allpairs_topk = 0;              // K of the all-pairs passes (selhip_ctx_set_allpairs_topk; kernel_topk.cuh, BOTH): every genome keeps its K best partners; 0 = off
     bool topk_applied = false;          // the result list holds topk(S, K) of the last finished query pass -- or nbr(S, K) of the last all-pairs pass --, in ranked order ...
     int64_t topk_n = 0;                 // ... and this many records (last.n_results stays |S|)
     DevBuf<uint32_t> topk_cnt;          // records per query, then the scatter's fill cursors

@@ -1,16 +1,24 @@
-// kernel_topk.cuh -- top-k of a query pass (include/selection_hip.h section 2b, selhip_ctx_set_query_topk): of the records
-// {i = query rank, k = database rank, J} a pass selected, every query keeps its K best, ranked by (J descending in the IEEE total order,
-// k ascending), and the list comes out in ranked order: i ascending, then that ranking.
-//   topk_count_kernel    records per query
-//   (rocprim::exclusive_scan of the packed counts: low word = a query's segment start, high word = its output start)
-//   topk_scatter_kernel  (key(J), k) of every record into its query's segment: 12 bytes per record in two arrays
+// kernel_topk.cuh -- the device-side top-k of a pass: every owner keeps its K best records, ranked by (J descending in the IEEE total
+// order, partner ascending), and the list comes out in ranked order: owner ascending, then that ranking.  Two forms of one machinery:
+//   query pass (include/selection_hip.h section 2b, selhip_ctx_set_query_topk): of the records {i = query rank, k = database rank, J}
+//     every query i keeps its K best k -- one owner per record (BOTH = false);
+//   all-pairs pass (section 2, selhip_ctx_set_allpairs_topk): every record {i, k, J}, i < k, belongs to BOTH genomes' lists --
+//     {owner i, partner k, J} and {owner k, partner i, J} -- and every genome keeps its K best partners (BOTH = true).
+//   topk_count_kernel    records per owner (BOTH: directed records, one count for a record's i, one for its k)
+//   (rocprim::exclusive_scan of the packed counts, TopkPack: low word = an owner's segment start, high word = its output start)
+//   topk_scatter_kernel  (key(J), partner) of every (directed) record into its owner's segment: 12 bytes each in two arrays
 //   topk_select_kernel   one block per segment: MSB-first radix select of the K best, bitonic sort of the winners, records written
 // key(J): bits ^ 2^63 for a clear sign bit, ~bits for a set one -- a u64 whose unsigned order is the IEEE total order; its inverse is the
 // same two cases told apart by the key's top bit, so the J bits come back exactly.
-// The two grouping kernels never issue one atomic per record on a hot query's counter (a returning atomic on one address sustains
-// ~87 operations/us chip-wide): a wave takes kTopkTile * 64 consecutive records and adds everything that
-// belongs to the query of its first record with ONE atomic; the passes emit records clustered by query, so only the records behind a
-// boundary inside a tile fall back to an atomic of their own.
+// The tile rule.  The i side arrives clustered by i (a query pass by query; an all-pairs pass bucketed by row where stage 2 groups, row
+// by row from the dense kernel), and the two grouping kernels never issue one atomic per record on a hot owner's counter (a returning
+// atomic on one address sustains ~87 operations/us chip-wide): a wave takes kTopkTile * 64 consecutive records
+// and covers everything that carries the i of its first record with ONE atomic -- ballots give each step's mask of such lanes, the
+// population counts add up to the run's length, and in the scatter a record's slot is the returned cursor plus the population count
+// of the lanes below it; only the records behind a boundary inside a tile fall back to an atomic of their own.
+// The k side of an all-pairs pass arrives in no order; it takes one atomic per record (no return value in the count kernel, a returned
+// cursor in the scatter kernel).  Along a row the k are ascending, mostly consecutive, so a wave's 64 atomics fall on few cache
+// lines; only a genome that is the larger member of very many pairs (a hub fed from the k side) makes one word hot.
 #pragma once
 
 namespace {
@@ -34,8 +42,10 @@ struct TopkPack {
     __host__ __device__ u64 operator()(uint32_t c) const { return ((u64)(c < k ? c : k) << 32) | (u64)c; }
 };
 
+// cnt[n_own]: records per owner, zero on entry
+template <bool BOTH>
 __global__ __launch_bounds__(kBlock)
-void topk_count_kernel(const selhip_pair_t* __restrict__ res, u64 n, int n_q, uint32_t* __restrict__ cnt) {
+void topk_count_kernel(const selhip_pair_t* __restrict__ res, u64 n, int n_own, uint32_t* __restrict__ cnt) {
     const int lane = threadIdx.x & (kWave - 1);
     const u64 wave = ((u64)blockIdx.x * kBlock + threadIdx.x) / kWave, waves = (u64)gridDim.x * kWavesPerBlock;
     constexpr u64 tile = (u64)kTopkTile * kWave;
@@ -46,18 +56,34 @@ void topk_count_kernel(const selhip_pair_t* __restrict__ res, u64 n, int n_q, ui
         for (int t = 0; t < kTopkTile; ++t) {
             const u64 j = base + (u64)t * kWave + lane;
             const int i = j < n ? res[j].i : -1;
+            const int k = BOTH && j < n ? res[j].k : -1;            // loaded with i, ahead of the atomics
             const bool same = i == i0;
             n0 += (uint32_t)__popcll(__ballot(same));
-            if (!same && (unsigned)i < (unsigned)n_q) atomicAdd(&cnt[i], 1u);
+            if (!same && (unsigned)i < (unsigned)n_own) atomicAdd(&cnt[i], 1u);
+            if constexpr (BOTH) {
+                if ((unsigned)k < (unsigned)n_own) atomicAdd(&cnt[k], 1u);
+            }
         }
-        if (lane == 0 && (unsigned)i0 < (unsigned)n_q) atomicAdd(&cnt[i0], n0);
+        if (lane == 0 && (unsigned)i0 < (unsigned)n_own) atomicAdd(&cnt[i0], n0);
     }
 }
 
-// cur[n_q]: fill cursors, zero on entry.  off[i] low word = start of query i's segment
+// one slot of owner o's segment, drawn from its fill cursor
+__device__ __forceinline__ u64 topk_slot(const u64* __restrict__ off, uint32_t* __restrict__ cur, int o) {
+    return (u64)(uint32_t)off[o] + (u64)atomicAdd(&cur[o], 1u);
+}
+
+// the one clip: a position at or past seg_cap (a record without an owner in range, a cursor gone wrong) stores nothing
+__device__ __forceinline__ void topk_put(u64* __restrict__ seg_key, uint32_t* __restrict__ seg_val, u64 seg_cap, u64 pos, u64 key, uint32_t val) {
+    if (pos < seg_cap) { seg_key[pos] = key; seg_val[pos] = val; }
+}
+
+// cur[n_own]: fill cursors, zero on entry (one per owner: with BOTH, both sides draw from it).  off[o] low word = start of owner o's
+// segment; seg_key / seg_val hold seg_cap entries (n, with BOTH 2 n), and seg_cap is also the position of a record that is not stored
+template <bool BOTH>
 __global__ __launch_bounds__(kBlock)
-void topk_scatter_kernel(const selhip_pair_t* __restrict__ res, u64 n, int n_q, const u64* __restrict__ off, uint32_t* __restrict__ cur,
-                         u64* __restrict__ seg_key, uint32_t* __restrict__ seg_val) {
+void topk_scatter_kernel(const selhip_pair_t* __restrict__ res, u64 n, int n_own, const u64* __restrict__ off, uint32_t* __restrict__ cur,
+                         u64* __restrict__ seg_key, uint32_t* __restrict__ seg_val, u64 seg_cap) {
     const int lane = threadIdx.x & (kWave - 1);
     const u64 wave = ((u64)blockIdx.x * kBlock + threadIdx.x) / kWave, waves = (u64)gridDim.x * kWavesPerBlock;
     constexpr u64 tile = (u64)kTopkTile * kWave;
@@ -71,28 +97,31 @@ void topk_scatter_kernel(const selhip_pair_t* __restrict__ res, u64 n, int n_q, 
 #pragma unroll
         for (int t = 0; t < kTopkTile; ++t) {
             const u64 j = base + (u64)t * kWave + lane;
-            rec[t] = j < n ? res4[j] : make_uint4(0xFFFFFFFFu, 0, 0, 0);
+            rec[t] = j < n ? res4[j] : make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0, 0);        // past the end: no owner on either side
             same_mask[t] = __ballot((int)rec[t].x == i0);
             n0 += (uint32_t)__popcll(same_mask[t]);
         }
-        const bool ok0 = (unsigned)i0 < (unsigned)n_q;
+        const bool ok0 = (unsigned)i0 < (unsigned)n_own;
         uint32_t at0 = 0;
         if (lane == 0 && ok0) at0 = atomicAdd(&cur[i0], n0);
         at0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)at0);
         if (ok0) at0 += (uint32_t)off[i0];
 #pragma unroll
         for (int t = 0; t < kTopkTile; ++t) {
-            const int i = (int)rec[t].x;
-            u64 pos = n;
+            const int i = (int)rec[t].x, k = (int)rec[t].y;
+            const u64 key = topk_key((u64)rec[t].z | ((u64)rec[t].w << 32));
+            // owner i, partner k
+            u64 pos = seg_cap;
             if (i == i0) {
                 if (ok0) pos = (u64)at0 + (u64)__popcll(same_mask[t] & ((1ull << lane) - 1ull));
-            } else if ((unsigned)i < (unsigned)n_q) {
-                pos = (u64)(uint32_t)off[i] + (u64)atomicAdd(&cur[i], 1u);
+            } else if ((unsigned)i < (unsigned)n_own) {
+                pos = topk_slot(off, cur, i);
             }
             at0 += (uint32_t)__popcll(same_mask[t]);
-            if (pos < n) {
-                seg_key[pos] = topk_key((u64)rec[t].z | ((u64)rec[t].w << 32));
-                seg_val[pos] = rec[t].y;
+            topk_put(seg_key, seg_val, seg_cap, pos, key, (uint32_t)k);
+            if constexpr (BOTH) {
+                // owner k, partner i
+                if ((unsigned)k < (unsigned)n_own) topk_put(seg_key, seg_val, seg_cap, topk_slot(off, cur, k), key, (uint32_t)i);
             }
         }
     }

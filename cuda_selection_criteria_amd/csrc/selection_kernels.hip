@@ -37,9 +37,8 @@
 //                       dense_select_kernel over a rectangle, typed and mirrored stores; selhip_ctx_matrix / _query_matrix)
 //   kernel_matrix_smh.cuh  matrix_smh_kernel / matrix_smh_generic_kernel: the SuperMinHash bucket-match count, or count / m, of every
 //                       pair as a dense array (query rows in VGPRs, candidate rows streamed past them; the same entry points)
-//   kernel_topk.cuh     top-k of a query pass: records grouped by query (count, scan, scatter), radix select of each query's K best,
-//                       bitonic sort of the winners
-//   kernel_nbr.cuh      top-k of an all-pairs pass: every record counted and scattered for both of its genomes, then the same select
+//   kernel_topk.cuh     top-k of a pass: records grouped by owner (count, scan, scatter) -- a query pass's by query, an all-pairs
+//                       pass's for both of their genomes --, radix select of each owner's K best, bitonic sort of the winners
 //   kernel_query_aux.cuh the auxiliary-HLL criteria of query passes: hll_a / hll_an over each query's CB window, the hll_a stage
 //                       of hll_a + smh_a over the smh_a survivors
 //
@@ -85,7 +84,6 @@
 #include "kernel_query_index.cuh"
 #include "kernel_dense.cuh"
 #include "kernel_topk.cuh"
-#include "kernel_nbr.cuh"
 
 #include "host_plan.hpp"         // host decisions that are plain arithmetic: build shape, pass plan, criterion constants, overflow rule
 #include "kernel_matrix.cuh"     // (behind host_plan.hpp: the kernel reads the unit, slab and mirror rules written there)

@@ -11,7 +11,7 @@ from conftest import GOLDEN, ROOT
 from test_allpairs_topk_host import nbr_reference
 from test_exhaustive_gpu import assert_same, ranked
 from test_gpu_parity import assert_same_pairs, sorted_set
-from test_query_topk_gpu import big_set, cfg2_split
+from test_query_topk_gpu import big_set, by_ik, cfg2_split, check_topk, lds_cap
 import test_query_aux_gpu as aux_t
 
 import cuda_selection_criteria_amd as pkg
@@ -23,32 +23,13 @@ pytestmark = pytest.mark.gpu
 BIN = ROOT / "cuda_selection_criteria_amd" / "bin"
 
 
-def by_ik(recs):
-    return recs[np.lexsort((recs["k"], recs["i"]))]
-
-
-def check_nbr(sel, S, K, run):
-    """run() = the all-pairs pass; with the setting at K it must leave nbr_reference(S, K) behind"""
-    sel.set_allpairs_topk(K)
-    assert sel.get_param("allpairs_topk") == K
-    run()
-    want = nbr_reference(S, K)
-    got = sel.fetch_ranked()
-    print(f"K={K}: |S|={len(S)} reduced {len(got)} (want {len(want)}), attempts {sel.last_attempts()}")
-    assert_same(got, want)
-    assert sel.result_count() == len(want) and sel.stats()["selected"] == len(S)
-    assert_same(sel.fetch(), by_ik(want))
-    return got
+# run() = the all-pairs pass; with the setting at K it must leave nbr_reference(S, K) behind
+check_nbr = functools.partial(check_topk, setting="allpairs_topk", reference=nbr_reference)
 
 
 def owned(S, n):
     """L_g: records of S with i = g or k = g"""
     return np.bincount(S["i"], minlength=n) + np.bincount(S["k"], minlength=n)
-
-
-def lds_cap():
-    with Selector(0) as sel:
-        return sel.get_param("query_topk_lds_cap")
 
 
 def first_genomes(oracle, n):
@@ -292,6 +273,33 @@ def test_life_cycle(oracle):
         assert lib.selhip_ctx_copy_results_framed(sel._ctx, frame.data_ptr(), len(S)) == 0
         torch.cuda.synchronize()
         assert int(frame[:8].view(torch.int64).item()) == len(S)
+
+
+def test_query_and_allpairs_cuts_share_a_context(oracle):
+    """the two cuts are one reduction over one scratch set: a query pass, an all-pairs pass over the same database and the query pass
+    again, all cut, on one context -- then the same round with the cfg2 ranked set as the all-pairs pass's database (other owner
+    counts and record counts through the same buffers).  Every list bit for bit its reference, the repeated query lists equal"""
+    Q, D = cfg2_split()
+    with Selector(0) as sel:
+        def split():                                                       # an upload drops the queries
+            sel.upload(D[0], D[1], D[2])
+            sel.upload_queries(Q[0], Q[1], Q[2])
+        query = lambda: sel.run_queries(0.5, fetch=False)
+        allpairs = lambda: sel.run(0.5, fetch=False)
+        split()
+        S_q, S_d = sel.run_queries(0.5), sel.run(0.5)
+        sel.upload(*cfg2_ranked())
+        S_all = sel.run(0.5)
+        assert len(S_q) > 0 and len(S_d) > 0 and len(S_all) > len(S_d)
+        split()
+        first = check_topk(sel, S_q, 3, query)                             # both settings stay on once set
+        assert 0 < len(first) < len(S_q)
+        assert 0 < len(check_nbr(sel, S_d, 3, allpairs)) < 2 * len(S_d)
+        assert_same(check_topk(sel, S_q, 3, query), first)
+        sel.upload(*cfg2_ranked())
+        assert 0 < len(check_nbr(sel, S_all, 3, allpairs)) < 2 * len(S_all)
+        split()
+        assert_same(check_topk(sel, S_q, 3, query), first)
 
 
 @pytest.mark.parametrize("n", [0, 1])

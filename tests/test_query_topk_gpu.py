@@ -26,12 +26,12 @@ def by_ik(recs):
     return recs[np.lexsort((recs["k"], recs["i"]))]
 
 
-def check_topk(sel, S, K, run):
-    """run() = the query pass; with top-k K it must leave topk_reference(S, K) behind"""
-    sel.set_query_topk(K)
-    assert sel.get_param("query_topk") == K
+def check_topk(sel, S, K, run, setting="query_topk", reference=topk_reference):
+    """run() = the pass; with the setting at K it must leave reference(S, K) behind"""
+    getattr(sel, "set_" + setting)(K)
+    assert sel.get_param(setting) == K
     run()
-    want = topk_reference(S, K)
+    want = reference(S, K)
     got = sel.fetch_ranked()
     print(f"K={K}: |S|={len(S)} reduced {len(got)} (want {len(want)}), attempts {sel.last_attempts()}")
     assert_same(got, want)
