@@ -77,6 +77,8 @@ HIP_SYMBOLS = {
     "selhip_ctx_attach_aux_hll": (_i, [_vp, _vp, _i]),
     "selhip_ctx_set_criterion": (_i, [_vp, _i]),
     "selhip_ctx_set_min_matches": (_i, [_vp, _i]),
+    "selhip_ctx_set_min_containment": (_i, [_vp, _d]),
+    "selhip_smhc_threshold": (_i, [_i, _d, C.c_uint64, C.c_uint64]),
     "selhip_ctx_set_measure": (_i, [_vp, _i]),
     "selhip_hll_cards": (_i, [_vp, _vp, _i64, _i, _vp]),
     "selhip_ctx_get_cards": (_i, [_vp, _vp]),

@@ -237,6 +237,7 @@ int selhip_ctx_get_param(const selhip_ctx* c, const char* name, int* value) {
     if (!std::strcmp(name, "chunks"))           { *value = c->n_chunks_last; return SELHIP_OK; }
     if (!std::strcmp(name, "dense_route_used")) { *value = c->dense_route_used; return SELHIP_OK; }         // SELHIP_CRIT_NONE: 1 fused kernel, 0 list route, -1 none yet
     if (!std::strcmp(name, "smhc_path_used"))   { *value = c->smhc_path_used; return SELHIP_OK; }           // SELHIP_CRIT_SMH_C: 1 fast kernel, 0 generic, -1 none yet
+    if (!std::strcmp(name, "smhc_rule_used"))   { *value = c->smhc_rule_used; return SELHIP_OK; }           // its threshold rule: 0 fixed c_min, 1 containment, -1 none yet
     if (!std::strcmp(name, "matrix_mirror"))    { *value = c->matrix_mirror; return SELHIP_OK; }
     if (!std::strcmp(name, "matrix_smh_form"))  { *value = c->matrix_smh_form; return SELHIP_OK; }
     if (!std::strcmp(name, "matrix_smh_path_used")) { *value = c->matrix_smh_path_used; return SELHIP_OK; }   // kernel of the last SuperMinHash matrix: 1 fast, 0 generic
@@ -299,6 +300,16 @@ int selhip_ctx_set_min_matches(selhip_ctx* c, int c_min) {
     c->min_matches = c_min;
     return SELHIP_OK;
 }
+
+int selhip_ctx_set_min_containment(selhip_ctx* c, double gamma) {
+    if (!c) return SELHIP_E_BADARG;
+    if (std::isinf(gamma)) { set_err(&c->err, "min_containment must be finite, or NaN to clear it (got %g)", gamma); return SELHIP_E_BADARG; }
+    if (c->pending) { set_err(&c->err, "a pass is still pending (selhip_ctx_finish)"); return SELHIP_E_STATE; }
+    c->min_containment = gamma;                    // (NaN: the fixed rule again)
+    return SELHIP_OK;
+}
+
+int selhip_smhc_threshold(int m, double gamma, uint64_t e_lo, uint64_t e_hi) { return selhip::smhc_threshold(m, gamma, e_lo, e_hi); }
 
 // the auxiliary HLL registers [n][1 << p_aux] of a sketch set from the host into the set's own buffer (the arguments were checked)
 static int upload_aux_hll_rows(selhip_ctx* c, const uint8_t* h_aux_hll, int64_t n, int p_aux, DevBuf<uint8_t>& own, const uint8_t** d_aux_hll, int* p_set) {

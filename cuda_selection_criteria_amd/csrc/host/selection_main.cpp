@@ -12,8 +12,12 @@
 //               none: no criterion in front of the Jaccard test -- every pair inside the CB bound (with -n: every pair); reads
 //               only the .hll files, -a is not needed (SELHIP_CRIT_NONE: the reference README's "CB criterion" / "no criterion" lines)
 //               smh_c: at least -C <c_min> of the m = -a bytes / 8 SuperMinHash buckets equal (SELHIP_CRIT_SMH_C: the SuperMinHash
-//               estimate c / m >= c_min / m, exhaustive, no banding); -a and -C must be given; with -l, -q, -p, -k, -K, -n, not with -g or -B
+//               estimate c / m >= c_min / m, exhaustive, no banding); -a and -C (or -G) must be given; with -l, -q, -p, -k, -K, -n, not with -g or -B
 //   -C <c_min>  the count threshold of -c smh_c (1 .. m), an option of that criterion alone
+//   -G <gamma>  the minimum containment of -c smh_c, an option of that criterion alone, in -C's place or beside it: a pair passes with
+//               at least ceil(gamma m a / (a + b - gamma a)) equal buckets, a <= b its two cardinalities -- the count at which the
+//               SuperMinHash estimate of the smaller genome's containment is gamma (selhip_ctx_set_min_containment) -- and, with -C,
+//               at least c_min.  The prefilter of -n -S max_containment -h gamma; with -l, -q, -p, -k, -K
 //   -t <n>      host threads for loading sketches (selection.cpp:97)
 //   -g <n>      number of GPUs to shard the pair space over (default 1; any criterion); selected pairs gathered over RCCL/xGMI
 //   -n          no CB pruning ("smh_a" mode of experiments/src/time_smh.cpp:229-257)
@@ -61,6 +65,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -70,6 +75,14 @@
 
 #include "../../../include/selection_hip.h"
 #include "../../../include/selection_host.h"
+
+// -c smh_c: its thresholds onto the context -- -C c_min (0: not given) and -G gamma (NaN: not given)
+static double g_min_containment = std::nan("");
+static int set_count_thresholds(selhip_ctx* ctx, int min_matches) {
+    int r = min_matches > 0 ? selhip_ctx_set_min_matches(ctx, min_matches) : 0;
+    if (!r && !std::isnan(g_min_containment)) r = selhip_ctx_set_min_containment(ctx, g_min_containment);
+    return r;
+}
 
 // -q: the query list against the database list (-l), both loaded and sorted by cardinality; text on stdout.  criterion: "smh_a"
 // (m = aux_bytes / 8 buckets), "hll_a" / "hll_an" (auxiliary HLL p = ctz(aux_bytes), as the all-pairs mode) or "none" (.hll files only)
@@ -116,7 +129,7 @@ static int run_queries(const std::string& query_file, const std::string& db_file
     if (!r && p_aux) r = selhip_ctx_upload_aux_hll(ctx, selhost_dataset_aux_hll(db), (int)p_aux);
     if (!r && p_aux) r = selhip_ctx_upload_queries_aux_hll(ctx, selhost_dataset_aux_hll(qs), (int)p_aux);
     if (!r) r = selhip_ctx_set_criterion(ctx, crit);
-    if (!r && smh_c) r = selhip_ctx_set_min_matches(ctx, min_matches);
+    if (!r && smh_c) r = set_count_thresholds(ctx, min_matches);
     if (!r) r = selhip_ctx_set_measure(ctx, measure);
     if (!r && top_k) r = selhip_ctx_set_query_topk(ctx, top_k);
     if (!r) r = selhip_ctx_run_queries(ctx, mode, algo, threshold, n_rows, n_bands);
@@ -164,7 +177,7 @@ static int run_neighbours(const std::string& list_file, int crit, float threshol
     r = selhip_ctx_upload(ctx, selhost_dataset_hll(ds), m ? selhost_dataset_aux(ds) : no_smh.data(), selhost_dataset_cards(ds), n, m ? (int)m : 1, 14);
     if (!r && p_aux) r = selhip_ctx_upload_aux_hll(ctx, selhost_dataset_aux_hll(ds), (int)p_aux);
     if (!r) r = selhip_ctx_set_criterion(ctx, crit);
-    if (!r && crit == SELHIP_CRIT_SMH_C) r = selhip_ctx_set_min_matches(ctx, min_matches);
+    if (!r && crit == SELHIP_CRIT_SMH_C) r = set_count_thresholds(ctx, min_matches);
     if (!r) r = selhip_ctx_set_measure(ctx, measure);
     if (!r) r = selhip_ctx_set_allpairs_topk(ctx, top_k);
     if (!r) r = selhip_ctx_run(ctx, mode, algo, threshold, n_rows, n_bands, 0, n);
@@ -248,16 +261,17 @@ int main(int argc, char* argv[]) {
     bool gpus_given = false, topk_given = false, nbr_given = false, matrix_given = false, union_measure = false, aux_given = false, estimator_given = false;
     const char* selection_opt = nullptr;         // the first of -h, -c, -n, -A seen: options of a selection pass, which -M does not run
     long long top_k = 0, nbr_k = 0, min_matches = 0;
-    bool cmin_given = false;
+    bool cmin_given = false, gamma_given = false;
     int c;
-    while ((c = getopt(argc, argv, "xl:b:a:h:c:C:t:g:nA:F:B:o:r:q:k:K:p:M:UE:S:")) != -1) {
+    while ((c = getopt(argc, argv, "xl:b:a:h:c:C:G:t:g:nA:F:B:o:r:q:k:K:p:M:UE:S:")) != -1) {
         switch (c) {
-            case 'x': std::cout << "Usage: -l -h -a -b [-c smh_a|hll_a|hll_an|none|smh_c -C c_min] [-t threads] [-g gpus] [-n] [-A auto|stream|sig] [-F 0|1] [-B block] [-o file] | -r file\n"
-                                   "       -l db_list -q query_list -h -a [-c smh_a|hll_a|hll_an|none|smh_c -C c_min] [-n] [-A auto|stream|sig|index] [-F 0|1] [-k best_per_query]   (query-vs-database selection)\n"
-                                   "       -l -h -a [-c smh_a|hll_a|hll_an|none|smh_c -C c_min] [-n] [-A auto|stream|sig|hashjoin] [-F 0|1] -K best_per_genome   (every genome's best partners, both members of a pair)\n"
-                                   "       -l list -p pair_file -h -a [-c smh_a|hll_a|hll_an|none|smh_c -C c_min] [-n] [-A auto|stream|sig] [-F 0|1] [-o file]   (only the listed pairs; lines 'path1 path2 ...')\n"
+            case 'x': std::cout << "Usage: -l -h -a -b [-c smh_a|hll_a|hll_an|none|smh_c -C c_min|-G gamma] [-t threads] [-g gpus] [-n] [-A auto|stream|sig] [-F 0|1] [-B block] [-o file] | -r file\n"
+                                   "       -l db_list -q query_list -h -a [-c smh_a|hll_a|hll_an|none|smh_c -C c_min|-G gamma] [-n] [-A auto|stream|sig|index] [-F 0|1] [-k best_per_query]   (query-vs-database selection)\n"
+                                   "       -l -h -a [-c smh_a|hll_a|hll_an|none|smh_c -C c_min|-G gamma] [-n] [-A auto|stream|sig|hashjoin] [-F 0|1] -K best_per_genome   (every genome's best partners, both members of a pair)\n"
+                                   "       -l list -p pair_file -h -a [-c smh_a|hll_a|hll_an|none|smh_c -C c_min|-G gamma] [-n] [-A auto|stream|sig] [-F 0|1] [-o file]   (only the listed pairs; lines 'path1 path2 ...')\n"
                                    "       -l list [-q query_list] [-F 0|1] -M out.tsv [-U]   (no selection: the dense Jaccard -- -U: union size -- matrix, file-list order)\n"
                                    "       -l list [-q query_list] -M out.tsv -E smh|smh_matches -a bytes   (the same table from the SuperMinHash sketches: equal buckets / m, or their count)\n"
+                                   "       ... -n -S max_containment -h gamma -c smh_c -G gamma -a bytes [-C c_min]   (its prefilter: the count at which the SuperMinHash estimate of the containment is gamma)\n"
                                    "       ... -n -S max_containment [-c smh_a|none|smh_c]   (with -l, -q, -p, -k, -K: select and print I / min(e1, e2), the share of the smaller genome found in the larger)\n"
                                    "       -l list [-q query_list] -M out.tsv -S intersection|containment|max_containment   (the table of I = e1 + e2 - U, I / e_row or I / min(e_row, e_col))\n"; return 0;
             case 'q': query_file = optarg; break;
@@ -277,6 +291,7 @@ int main(int argc, char* argv[]) {
             case 'h': threshold = std::stof(optarg); if (!selection_opt) selection_opt = "-h"; break;
             case 'c': criterion = optarg; if (!selection_opt) selection_opt = "-c"; break;
             case 'C': min_matches = std::strtoll(optarg, nullptr, 10); cmin_given = true; if (!selection_opt) selection_opt = "-C"; break;
+            case 'G': g_min_containment = std::strtod(optarg, nullptr); gamma_given = true; if (!selection_opt) selection_opt = "-G"; break;
             case 't': threads = std::stoi(optarg); break;
             case 'g': n_gpus = std::stoi(optarg); gpus_given = true; break;
             case 'n': mode = SELHIP_MODE_SMH; if (!selection_opt) selection_opt = "-n"; break;
@@ -353,15 +368,17 @@ int main(int argc, char* argv[]) {
     if (union_measure) { std::cerr << "selection: -U (union sizes) is an option of -M (the dense similarity matrix)\n"; return 2; }
     // -c smh_c and its -C: checked before any file is read or device opened
     if (cmin_given && criterion != "smh_c") { std::cerr << "selection: -C (the count threshold) is an option of -c smh_c\n"; return 2; }
+    if (gamma_given && criterion != "smh_c") { std::cerr << "selection: -G (the minimum containment) is an option of -c smh_c\n"; return 2; }
+    if (gamma_given && !std::isfinite(g_min_containment)) { std::cerr << "selection: -G must be a finite number\n"; return 2; }
     if (criterion == "smh_c") {
-        if (!cmin_given) { std::cerr << "selection: -c smh_c needs its count threshold: -C c_min (at least c_min equal buckets)\n"; return 2; }
+        if (!cmin_given && !gamma_given) { std::cerr << "selection: -c smh_c needs its count threshold: -C c_min (at least c_min equal buckets)\n"; return 2; }
         if (!aux_given || aux_bytes / 8 <= 0) { std::cerr << "selection: -c smh_c reads the .smh<m> files: give their size with -a (bytes, 8 per bucket)\n"; return 2; }
         const char* clash = gpus_given ? "-g" : ooc_block != 0 ? "-B" : nullptr;
         if (clash) {
             std::cerr << "selection: -c smh_c cannot be combined with " << clash << "; the multi-GPU and out-of-core drivers carry no count threshold\n";
             return 2;
         }
-        if (min_matches < 1 || min_matches > aux_bytes / 8) { std::cerr << "selection: -C must be in 1.." << aux_bytes / 8 << " (the m = -a / 8 buckets)\n"; return 2; }
+        if (cmin_given && (min_matches < 1 || min_matches > aux_bytes / 8)) { std::cerr << "selection: -C must be in 1.." << aux_bytes / 8 << " (the m = -a / 8 buckets)\n"; return 2; }
     }
     if (!pair_file.empty()) {
         // checked before any file is read or device opened
@@ -497,7 +514,7 @@ int main(int argc, char* argv[]) {
         r = selhip_ctx_upload(ctx, selhost_dataset_hll(ds), aux_ptr, selhost_dataset_cards(ds), n, m_up, 14);
         if (!r && p_aux) r = selhip_ctx_upload_aux_hll(ctx, selhost_dataset_aux_hll(ds), (int)p_aux);
         if (!r) r = selhip_ctx_set_criterion(ctx, crit);
-        if (!r && crit == SELHIP_CRIT_SMH_C) r = selhip_ctx_set_min_matches(ctx, (int)min_matches);
+        if (!r && crit == SELHIP_CRIT_SMH_C) r = set_count_thresholds(ctx, (int)min_matches);
         if (!r) r = selhip_ctx_set_measure(ctx, pass_measure);
         void* d_list = nullptr;
         if (!r && !pair_file.empty()) {

@@ -241,6 +241,10 @@ struct selhip_ctx {
     // last such pass (1 the fast path, 0 the generic one, -1 none yet)
     int min_matches = 0;
     int smhc_path_used = -1;
+    // its per-pair rule (selhip_ctx_set_min_containment; NaN = never set or cleared: the fixed rule) and the rule of the last such pass
+    // (0 fixed, 1 containment, -1 none yet)
+    double min_containment = std::numeric_limits<double>::quiet_NaN();
+    int smhc_rule_used = -1;
     // what stage 2 of every pass tests against tau and records (selhip_ctx_set_measure): SELHIP_MEASURE_JACCARD or _MAX_CONTAINMENT
     int measure = SELHIP_MEASURE_JACCARD;
 

@@ -68,8 +68,13 @@ int enqueue_pairs_pass(selhip_ctx* c) {
             const unsigned grid = grid_for(P, kPairsBlock, kPairsMaxGrid);
             if (c->plan.count) {
                 const PairsDirectShape sh = pairs_direct_shape(P);
-                hipLaunchKernelGGL(pairs_count_kernel, dim3(sh.grid), dim3(kPairsBlock), 0, c->stream, c->d_aux, c->m, c->min_matches,
-                                   c->list_pairs, P, n, c->ecard.p, tau, use_cb, sh.gpw, io.surv, io.cap, &io.pc->n_survivors, pc0);
+                c->smhc_rule_used = smhc_containment(c) ? 1 : 0;
+                if (smhc_containment(c))
+                    hipLaunchKernelGGL(pairs_count_kernel<kSmhcContainment>, dim3(sh.grid), dim3(kPairsBlock), 0, c->stream, c->d_aux, c->m, c->min_matches,
+                                       c->list_pairs, P, n, c->ecard.p, tau, use_cb, sh.gpw, io.surv, io.cap, &io.pc->n_survivors, pc0, c->min_containment);
+                else
+                    hipLaunchKernelGGL(pairs_count_kernel<kSmhcFixed>, dim3(sh.grid), dim3(kPairsBlock), 0, c->stream, c->d_aux, c->m, c->min_matches,
+                                       c->list_pairs, P, n, c->ecard.p, tau, use_cb, sh.gpw, io.surv, io.cap, &io.pc->n_survivors, pc0, c->min_containment);
             } else if (c->pairs_route_used == 1)
                 hipLaunchKernelGGL(pairs_verify_kernel, dim3(grid), dim3(kPairsBlock), 0, c->stream, c->d_aux, c->m, c->n_rows, c->n_bands, c->sig.Q.p,
                                    c->list_pairs, P, n, c->ecard.p, tau, use_cb, io.surv, io.cap, io.pc, pc0, c->verify_fb);

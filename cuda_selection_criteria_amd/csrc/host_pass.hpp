@@ -58,10 +58,12 @@ hipError_t launch_stage1(selhip_ctx* c, const StageIO& io, int n_rows, int n_ban
 }
 
 // ---- stage 1 of criterion smh_c (kernel_smhc.cuh) -----------------------------------------------
+// the passes under the criterion apply the containment rule (selhip_ctx_set_min_containment) on top of c_min
+bool smhc_containment(const selhip_ctx* c) { return !std::isnan(c->min_containment); }
 // what SELHIP_CRIT_SMH_C asks of the context, checked by every entry before it claims a counter set
 int accept_count(selhip_ctx* c) {
     if (c->m <= 0 || (!c->d_aux && c->n)) { set_err(&c->err, "criterion smh_c (SELHIP_CRIT_SMH_C) needs SuperMinHash rows: the context holds none"); return SELHIP_E_BADARG; }
-    if (c->min_matches < 1) { set_err(&c->err, "criterion smh_c (SELHIP_CRIT_SMH_C) needs a count threshold: selhip_ctx_set_min_matches first"); return SELHIP_E_BADARG; }
+    if (c->min_matches < 1 && !smhc_containment(c)) { set_err(&c->err, "criterion smh_c (SELHIP_CRIT_SMH_C) needs a count threshold: selhip_ctx_set_min_matches (a fixed c_min) or selhip_ctx_set_min_containment (a per-pair one) first"); return SELHIP_E_BADARG; }
     if (c->min_matches > c->m) { set_err(&c->err, "criterion smh_c (SELHIP_CRIT_SMH_C): c_min = %d exceeds the m = %d buckets of a row", c->min_matches, c->m); return SELHIP_E_BADARG; }
     return SELHIP_OK;
 }
@@ -87,12 +89,16 @@ int accept_measure(selhip_ctx* c, int mode) {
 
 // the rows of X (owned rows of rm) against the candidates of Y from first_cand on.  QUERY = false: X = Y = the context's rows, windows
 // from hi and pc_in's z0; QUERY = true: the queries against the database, windows lo / hi
-struct CountSets { const u64* X; const u64* Y; int n_x, n_y; const int* lo; const int* hi; const PassCounters* pc_in; };
+// (ex, ey: the truncated cardinalities of the rows and of the candidates, read by the containment rule alone)
+struct CountSets { const u64* X; const u64* Y; int n_x, n_y; const int* lo; const int* hi; const PassCounters* pc_in; const u64* ex; const u64* ey; };
 template <bool QUERY>
 hipError_t launch_count(selhip_ctx* c, hipStream_t st, const CountSets& a, const RowMap& rm, int first_cand,
                         selhip_int2_t* surv, u64 cap, PassCounters* pc) {
     const int m = c->m, c_min = c->min_matches;
     c->smhc_path_used = smhc_fast(m) ? 1 : 0;
+    const bool cont = smhc_containment(c);
+    c->smhc_rule_used = cont ? 1 : 0;
+    const SmhcRule rule{c->min_containment, a.ex, a.ey};
     if (smhc_fast(m)) {
         const int nch = m / 128;
         const long long n_tiles = rm.n_tiles(smhc_q(nch));
@@ -102,8 +108,9 @@ hipError_t launch_count(selhip_ctx* c, hipStream_t st, const CountSets& a, const
         if (n_tiles <= 0 || n_chunks <= 0) return hipSuccess;
         const long long blocks = n_tiles * n_chunks;
         if (blocks > 0x7FFFFFFFll) return hipErrorInvalidValue;
-#define SELHIP_SMHC_LAUNCH(NCH) hipLaunchKernelGGL((smh_count_kernel<NCH, QUERY>), dim3((unsigned)blocks), dim3(kBlock), 0, st, (const u64x2*)a.X, (const u64x2*)a.Y, \
-                                                   a.n_x, a.n_y, a.lo, a.hi, a.pc_in, rm, (int)n_tiles, chunk_base, c_min, surv, cap, pc)
+#define SELHIP_SMHC_LAUNCH_R(NCH, RULE) hipLaunchKernelGGL((smh_count_kernel<NCH, QUERY, RULE>), dim3((unsigned)blocks), dim3(kBlock), 0, st, (const u64x2*)a.X, (const u64x2*)a.Y, \
+                                                   a.n_x, a.n_y, a.lo, a.hi, a.pc_in, rm, (int)n_tiles, chunk_base, c_min, surv, cap, pc, rule)
+#define SELHIP_SMHC_LAUNCH(NCH) do { if (cont) SELHIP_SMHC_LAUNCH_R(NCH, kSmhcContainment); else SELHIP_SMHC_LAUNCH_R(NCH, kSmhcFixed); } while (0)
         switch (nch) {
             case 1: SELHIP_SMHC_LAUNCH(1); break;
             case 2: SELHIP_SMHC_LAUNCH(2); break;
@@ -111,21 +118,26 @@ hipError_t launch_count(selhip_ctx* c, hipStream_t st, const CountSets& a, const
             default: SELHIP_SMHC_LAUNCH(8);
         }
 #undef SELHIP_SMHC_LAUNCH
+#undef SELHIP_SMHC_LAUNCH_R
         return hipGetLastError();
     }
     const long long rows = rm.n_tiles(1);
     const long long blocks = rows * ((a.n_y + kBlock - 1) / kBlock);
     if (blocks <= 0) return hipSuccess;
     if (rows > 0x7FFFFFFFll || blocks > 0x7FFFFFFFll) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((smh_count_generic_kernel<QUERY>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a.X, a.Y, a.n_x, a.n_y, m, a.lo, a.hi, a.pc_in,
-                       rm, (int)rows, c_min, surv, cap, pc);
+    if (cont)
+        hipLaunchKernelGGL((smh_count_generic_kernel<QUERY, kSmhcContainment>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a.X, a.Y, a.n_x, a.n_y, m, a.lo, a.hi, a.pc_in,
+                           rm, (int)rows, c_min, surv, cap, pc, rule);
+    else
+        hipLaunchKernelGGL((smh_count_generic_kernel<QUERY, kSmhcFixed>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a.X, a.Y, a.n_x, a.n_y, m, a.lo, a.hi, a.pc_in,
+                           rm, (int)rows, c_min, surv, cap, pc, rule);
     return hipGetLastError();
 }
 
 // the all-pairs form behind cb_bounds_kernel: candidates k > row_begin, as in launch_stage1
 hipError_t launch_stage1_count(selhip_ctx* c, const StageIO& io, const RowMap& rm) {
     const int n = (int)c->n;
-    return launch_count<false>(c, io.st, CountSets{c->d_aux, c->d_aux, n, n, nullptr, c->hi.p, c->pcb}, rm, rm.row_begin + 1, io.surv, io.cap, io.pc);
+    return launch_count<false>(c, io.st, CountSets{c->d_aux, c->d_aux, n, n, nullptr, c->hi.p, c->pcb, c->ecard.p, c->ecard.p}, rm, rm.row_begin + 1, io.surv, io.cap, io.pc);
 }
 
 

@@ -186,7 +186,7 @@ int enqueue_query_pass(selhip_ctx* c, double tau) {
     } else if (c->plan.count) {
         // smh_c: the count kernel of the all-pairs pass over the rectangle, every query's window [lo, hi] in place of the triangle's
         TimerScope t(c, T_STAGE1);
-        HIPCHK(&c->err, launch_count<true>(c, c->stream, CountSets{q.d_aux, c->d_aux, n_q, n_d, q.lo.p, q.hi.p, pc}, RowMap{0, n_q, n_q, 1, 0}, 0,
+        HIPCHK(&c->err, launch_count<true>(c, c->stream, CountSets{q.d_aux, c->d_aux, n_q, n_d, q.lo.p, q.hi.p, pc, q.ecard.p, q.ecard.p + n_q}, RowMap{0, n_q, n_q, 1, 0}, 0,
                                            q.surv.p, (u64)q.surv.cap, pc));
     } else if (use_sig) {
         const long long key = ((long long)r << 40) | ((long long)nb << 24) | ((c->db_gen & 0xFFFFF) << 1) | 1;

@@ -227,11 +227,13 @@ void pairs_direct_kernel(const u64* __restrict__ aux, int m, int n_rows, int n_b
 // groups of four entries, gpw groups per wave and batch, kPairsSteps 16-bucket steps' loads in flight together -- with the count over
 // ALL m buckets in place of the band test: every step adds the population count of the quarter-wave's 16-bit equality mask, and
 // smhc_selects decides the entry when its row is through.  Nothing stops early: a count needs every bucket.
+// RULE = kSmhcContainment (kernel_smhc.cuh): the entry's own exact threshold in place of c_min, from the cardinalities of its two ranks.
 // ---------------------------------------------------------------------------------------------
+template <int RULE>
 __global__ __launch_bounds__(kPairsBlock)
 void pairs_count_kernel(const u64* __restrict__ aux, int m, int c_min,
                         const selhip_int2_t* __restrict__ list, u64 n_pairs, int n, const u64* __restrict__ ecard, double tau, int use_cb, int gpw,
-                        selhip_int2_t* __restrict__ surv, u64 surv_cap, u64* __restrict__ surv_count, PassCounters* __restrict__ pc0) {
+                        selhip_int2_t* __restrict__ surv, u64 surv_cap, u64* __restrict__ surv_count, PassCounters* __restrict__ pc0, double gamma) {
     __shared__ PairsLds s;
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
     const int sub = lane & 15, quarter = lane >> 4, qshift = quarter * 16;
@@ -269,7 +271,9 @@ void pairs_count_kernel(const u64* __restrict__ aux, int m, int c_min,
                 for (int u = 0; u < kPairsSteps; ++u)
                     cnt += __popc((uint32_t)(__ballot(va[u] == vb[u]) >> qshift) & 0xFFFFu);
             }
-            ok_mask |= pairs_quarter_bits(__ballot(open && sub == 0 && smhc_selects(cnt, c_min)), t * 4);
+            int thr = c_min;
+            if constexpr (RULE == kSmhcContainment) thr = smhc_pair_threshold(m, gamma, ecard[px], ecard[py], c_min);       // ({0, 0} when not live)
+            ok_mask |= pairs_quarter_bits(__ballot(open && sub == 0 && smhc_selects(cnt, thr)), t * 4);
         }
         const bool ok = (ok_mask >> lane) & 1ull;
         block_append(s.app, ok, pr, lane, surv, surv_cap, surv_count, nullptr);

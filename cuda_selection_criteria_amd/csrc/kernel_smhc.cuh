@@ -5,12 +5,16 @@
 // Part of libselhip.so; included by selection_kernels.hip only (one translation unit, anonymous namespace).  All kernels read `aux`
 // row-major, as uploaded or attached: for a count any lane <-> bucket map does, as long as both rows of a pair use the same one
 // (DESIGN.md section 14), so there is no interleaved copy as in ALGO_STREAM.
-//   smh_count_kernel<NCH, QUERY>        m = 128 * NCH buckets, NCH in {1, 2, 4, 8} (smhc_fast): smh_stream_kernel's block shape and enumeration
-//   smh_count_generic_kernel<QUERY>     every other m > 0: smh_generic_kernel's unit, lane = candidate, a serial loop over the buckets
+//   smh_count_kernel<NCH, QUERY, RULE>  m = 128 * NCH buckets, NCH in {1, 2, 4, 8} (smhc_fast): smh_stream_kernel's block shape and enumeration
+//   smh_count_generic_kernel<QUERY, RULE> every other m > 0: smh_generic_kernel's unit, lane = candidate, a serial loop over the buckets
 // QUERY = false: the all-pairs pass (rows and candidates from one set, the window of row i is [max(i + 1, z0), hi[i]], records (i, k));
 // QUERY = true: the query pass (rows from Q, candidates from D, the window of query i is [lo[i], hi[i]] of query_windows_kernel, records
 // (i, n_q + k) in the combined index space of stage 2).  The pair-list form is pairs_count_kernel (kernel_pairs.cuh).
 // Every kernel decides with smhc_selects: THE threshold step, written once.
+// RULE (a template argument of all three count kernels): kSmhcFixed -- the threshold is c_min for every pair, the kernels as they were
+// before the rule existed, instruction for instruction; kSmhcContainment -- the threshold of pair (i, k) is
+//     max(c_min, selhip::smhc_threshold(m, gamma, min(e_i, e_k), max(e_i, e_k)))          (pair_value.hpp; c_min = 0 when never set)
+// the count a minimum containment gamma asks for (selhip_ctx_set_min_containment).
 #pragma once
 
 namespace {
@@ -22,6 +26,15 @@ constexpr int smhc_q(int nch) { return kQueryVgprBudget / nch < 12 ? kQueryVgprB
 
 // the threshold step of every smh_c kernel
 __device__ __forceinline__ bool smhc_selects(int count, int c_min) { return count >= c_min; }
+
+constexpr int kSmhcFixed = 0, kSmhcContainment = 1;
+// what the containment rule reads besides the counts: gamma and the truncated cardinalities of the rows (ex) and the candidates (ey);
+// the same array in the all-pairs pass and in a pair list
+struct SmhcRule { double gamma; const u64* __restrict__ ex; const u64* __restrict__ ey; };
+// the exact threshold of a pair under the containment rule
+__device__ __forceinline__ int smhc_pair_threshold(int m, double gamma, u64 e1, u64 e2, int c_min) {
+    return max(c_min, selhip::smhc_threshold(m, gamma, e1 < e2 ? e1 : e2, e1 < e2 ? e2 : e1));
+}
 
 // the count of the fast path: 2 NCH v_cmp_eq_u64 lane masks, one s_bcnt1_i32_b64 each, scalar adds (wave-uniform result)
 template <int NCH>
@@ -53,23 +66,30 @@ struct SmhcSpace {
 };
 
 // ---------------------------------------------------------------------------------------------
-// smh_count_kernel<NCH, QUERY>
+// smh_count_kernel<NCH, QUERY, RULE>
 //   block  = 4 waves; one block = (tile of Q = smhc_q(NCH) rows of X) x (chunk of kChunk candidates of Y), blockIdx.x -> (tile =
 //            b % n_tiles, chunk = b / n_tiles) as in smh_stream_kernel: the blocks of a chunk share it through their XCD's L2
 //   rows   = every wave holds the tile's Q rows in VGPRs, loaded coalesced (load c of a row hands lane l the buckets 128 c + 2 l, + 1)
 //   stream = the wave walks its candidates (stride 4), NCH x global_load_dwordx4 per candidate, kStreamAhead candidates ahead in a ring
 //            of register sets addressed statically
 //   pair   = smhc_count, ONE scalar compare against c_min, app.push_uniform for a pair that passes and lies in the row's window
+// RULE = kSmhcContainment: the scalar compare of a pair goes against its ROW's coarse threshold, one SGPR per tile row computed at block
+// start: a lower bound of the exact threshold over the block's candidates [max(k0, kmin), k_end), raised to c_min.  The threshold is
+// non-increasing in the larger cardinality and the ranks ascend in cardinality, so in the all-pairs pass (k > i: e_k >= e_i) the bound
+// is the threshold at the range's last candidate; in a query pass the threshold rises while e_k < e_i and falls from there on, so its
+// minimum over the range is at one of the two ends.  (A range end with e = 0 -- threshold m + 1 by definition, outside that shape --
+// gives the bound 0.)  A chunk is kChunk consecutive ranks of a sorted set: the bound is tight.  Only a pair that passes it takes the
+// exact test -- one f64 divide on uniform operands -- behind the pinned branch, beside the window test.
 // The count is never cut short (no "count + remaining buckets < c_min" exit): the test would be a scalar compare and branch per
 // ballot on the path every pair takes, where the whole count costs one s_bcnt1 and one s_add per ballot.
 // No LDS tile and no block barrier: a wave that has no candidate leaves on its own.
 // ---------------------------------------------------------------------------------------------
-template <int NCH, bool QUERY>
+template <int NCH, bool QUERY, int RULE>
 __global__ __launch_bounds__(kBlock, (NCH <= 4 ? 3 : 2))
 void smh_count_kernel(const u64x2* __restrict__ X, const u64x2* __restrict__ Y, int n_x, int n_y,
                       const int* __restrict__ lo, const int* __restrict__ hi, const PassCounters* __restrict__ pc_in,
                       RowMap rm, int n_tiles, int chunk_base, int c_min,
-                      selhip_int2_t* __restrict__ surv, u64 surv_cap, PassCounters* __restrict__ pc) {
+                      selhip_int2_t* __restrict__ surv, u64 surv_cap, PassCounters* __restrict__ pc, SmhcRule rule) {
     constexpr int Q = smhc_q(NCH);
     constexpr int ROWV = NCH * kWave;                 // u64x2 per sketch row
     __shared__ selhip_int2_t app_lds[kWavesPerBlock * kAppendCap];
@@ -102,6 +122,22 @@ void smh_count_kernel(const u64x2* __restrict__ X, const u64x2* __restrict__ Y, 
     int k = max(k0, kmin) + wave;
     if (k >= k_end) return;
 
+    int coarse[Q];                                                            // RULE = kSmhcContainment: wave-uniform, one SGPR per tile row
+    if constexpr (RULE == kSmhcContainment) {
+        const int ks = max(k0, kmin);                                        // ks <= k_end - 1 < n_y
+        const u64 e_first = rule.ey[ks], e_last = rule.ey[k_end - 1];
+#pragma unroll
+        for (int a = 0; a < Q; ++a) {
+            const u64 e_i = rule.ex[min(i0 + a, n_x - 1)];
+            int t = selhip::smhc_threshold(128 * NCH, rule.gamma, min(e_i, e_last), max(e_i, e_last));
+            if constexpr (QUERY) {
+                t = min(t, selhip::smhc_threshold(128 * NCH, rule.gamma, min(e_i, e_first), max(e_i, e_first)));
+                if (e_first == 0 || e_i == 0) t = 0;
+            }
+            coarse[a] = __builtin_amdgcn_readfirstlane(max(t, c_min));
+        }
+    }
+
     u64x2 q[Q][NCH];
 #pragma unroll
     for (int a = 0; a < Q; ++a) {
@@ -124,12 +160,18 @@ void smh_count_kernel(const u64x2* __restrict__ X, const u64x2* __restrict__ Y, 
     auto compare_row = [&](const u64x2 (&cand)[NCH], int kk) {
 #pragma unroll
         for (int a = 0; a < Q; ++a) {
-            if (smhc_selects(smhc_count<NCH>(cand, q[a]), c_min)) {
+            const int cnt = smhc_count<NCH>(cand, q[a]);
+            if (smhc_selects(cnt, RULE == kSmhcContainment ? coarse[a] : c_min)) {
                 // (the empty volatile asm pins the branch on the count alone, as in smh_stream_kernel: the window tests stay off the
                 //  path of the pairs that fail it)
                 asm volatile("");
                 const int i = i0 + a;
-                if (i < i_end && sp.holds(i, kk)) app.push_uniform(i, sp.partner(kk), lane);
+                if (i < i_end && sp.holds(i, kk)) {
+                    bool ok = true;
+                    if constexpr (RULE == kSmhcContainment)
+                        ok = smhc_selects(cnt, smhc_pair_threshold(128 * NCH, rule.gamma, rule.ex[i], rule.ey[kk], c_min));
+                    if (ok) app.push_uniform(i, sp.partner(kk), lane);
+                }
             }
         }
     };
@@ -148,12 +190,12 @@ void smh_count_kernel(const u64x2* __restrict__ X, const u64x2* __restrict__ Y, 
 }
 
 // generic stage 1: block = 256 lanes = 256 candidates of one row; grid = (chunks, rows)
-template <bool QUERY>
+template <bool QUERY, int RULE>
 __global__ __launch_bounds__(kBlock)
 void smh_count_generic_kernel(const u64* __restrict__ X, const u64* __restrict__ Y, int n_x, int n_y, int m,
                               const int* __restrict__ lo, const int* __restrict__ hi, const PassCounters* __restrict__ pc_in,
                               RowMap rm, int n_rows_grid, int c_min,
-                              selhip_int2_t* __restrict__ surv, u64 surv_cap, PassCounters* __restrict__ pc) {
+                              selhip_int2_t* __restrict__ surv, u64 surv_cap, PassCounters* __restrict__ pc, SmhcRule rule) {
     __shared__ selhip_int2_t app_lds[kWavesPerBlock * kAppendCap];
     int i, i_e;
     rm.tile_rows((int)(blockIdx.x % n_rows_grid), 1, &i, &i_e);
@@ -167,7 +209,9 @@ void smh_count_generic_kernel(const u64* __restrict__ X, const u64* __restrict__
     const long long kl = (long long)sp.first(i) + (long long)chunk * kBlock + (int)threadIdx.x;
     const bool in_range = kl <= kmax && kl < n_y;
     const int k = in_range ? (int)kl : 0;
-    const bool ok = in_range && smhc_selects(smhc_count_lane(X + (long long)i * m, Y + (long long)k * m, m), c_min);
+    int t = c_min;
+    if constexpr (RULE == kSmhcContainment) t = smhc_pair_threshold(m, rule.gamma, rule.ex[i], rule.ey[k], c_min);      // (k = 0 out of range: a valid rank)
+    const bool ok = in_range && smhc_selects(smhc_count_lane(X + (long long)i * m, Y + (long long)k * m, m), t);
     WaveAppender app;
     app.init(app_lds, wave, surv, surv_cap, &pc->n_survivors);
     app.push(ok, i, sp.partner(k), lane);

@@ -10,6 +10,10 @@
 //   SELHIP_MEASURE_MAX_CONTAINMENT  I / (e1 < e2 ? e1 : e2)     the share of the smaller genome found in the larger; symmetric
 // No clamp and no abs, as for J: estimator noise may give a value below 0 or above 1.  A containment whose denominator is 0 (an empty
 // sketch) is NaN -- never +-inf -- so `value >= tau` is false for it under every tau: such a pair is never selected.
+// smhc_threshold is the ONE statement of criterion smh_c's per-pair count threshold for a minimum containment gamma
+// (selhip_ctx_set_min_containment): with c / m the SuperMinHash estimate of J, I = J (a + b) / (1 + J) and
+// C^ = I / a = c (a + b) / ((m + c) a), so C^ >= gamma iff c >= gamma m a / (a + b - gamma a).  The count kernels, pairs_count_kernel and
+// selhip_smhc_threshold (the same function on the host) call it, nothing else spells the expression.
 // (e2 + e1 - U has the bits of e1 + e2 - U -- IEEE addition commutes -- so the value of (b, a) may be computed from the operands of (a, b).)
 #pragma once
 
@@ -21,6 +25,19 @@ SELHIP_HD double pair_value(int measure, double e1, double e2, double U) {
     if (measure == SELHIP_MEASURE_INTERSECTION) return I;
     const double d = measure == SELHIP_MEASURE_CONTAINMENT ? e1 : (e1 < e2 ? e1 : e2);
     return d != 0.0 ? I / d : bits2d(0x7FF8000000000000ull);
+}
+
+// the smallest count c in [0, m + 1] of equal buckets with C^ >= gamma for a pair of truncated cardinalities e_lo <= e_hi (m + 1: no
+// count reaches it).  Every operation is rounded on its own, in the order written.
+SELHIP_HD int smhc_threshold(int m, double gamma, unsigned long long e_lo, unsigned long long e_hi) {
+    const double a = (double)e_lo, b = (double)e_hi;
+    if (a == 0.0) return m + 1;                      // stage 2 never selects d = 0 under max containment; two empty rows do not survive
+    const double num = (gamma * (double)m) * a;
+    const double ga = gamma * a;
+    const double den = (a + b) - ga;
+    if (!(den > 0.0)) return m + 1;                  // gamma >= 1 + b / a: no count reaches it
+    const double q = num / den;
+    return q <= 0.0 ? 0 : q > (double)m ? m + 1 : (int)ceil(q);
 }
 
 }  // namespace selhip

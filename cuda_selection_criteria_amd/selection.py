@@ -317,6 +317,13 @@ class Selector:
         are equal (c >= 1; a pass refuses c > m).  min_matches(m, j) gives the c of a SuperMinHash Jaccard estimate j"""
         check(self._lib.selhip_ctx_set_min_matches(self._ctx, int(c)), self._ctx)
 
+    def set_min_containment(self, gamma: Optional[float]):
+        """the per-pair count threshold of criterion smh_c for a minimum containment gamma: a pair survives stage 1 iff its equal
+        buckets c reach containment_matches(m, gamma, min(e_i, e_k), max(e_i, e_k)) -- the count at which the SuperMinHash estimate of
+        the smaller genome's containment is gamma -- and set_min_matches' c, which stays as a floor when set.  Sticky; None (or NaN)
+        clears it; +-inf is refused"""
+        check(self._lib.selhip_ctx_set_min_containment(self._ctx, float("nan") if gamma is None else float(gamma)), self._ctx)
+
     def set_measure(self, measure):
         """what stage 2 of the following passes (run, run_queries, run_pairs and their top-ks) tests against tau and records in the
         `jaccard` field: "jaccard" (the default) or "max_containment" -- I / min(e_i, e_k) with I = e_i + e_k - U, the share of the
@@ -529,15 +536,32 @@ def min_matches(m: int, j: float) -> int:
     return c
 
 
-def _criterion_files(criterion: str, aux_bytes: int, min_matches: Optional[int] = None) -> Tuple[int, int, int]:
+def containment_matches(m, gamma, e_lo, e_hi):
+    """the count of equal SuperMinHash buckets, in [0, m + 1], from which a pair of truncated cardinalities e_lo <= e_hi has a
+    SuperMinHash containment estimate c (e_lo + e_hi) / ((m + c) e_lo) >= gamma (m + 1: no count reaches it): the per-pair threshold of
+    Selector.set_min_containment, computed by the library's own function (selhip_smhc_threshold; no device is touched).  Scalars give
+    an int, arrays broadcast against each other and give an int32 array"""
+    fn = hip_lib().selhip_smhc_threshold
+    args = np.broadcast_arrays(np.asarray(m, dtype=np.int64), np.asarray(gamma, dtype=np.float64), np.asarray(e_lo, dtype=np.uint64), np.asarray(e_hi, dtype=np.uint64))
+    out = np.empty(args[0].shape, dtype=np.int32)
+    flat = out.reshape(-1)
+    for j, (mm, g, a, b) in enumerate(zip(*(x.reshape(-1).tolist() for x in args))):
+        flat[j] = fn(mm, g, a, b)
+    return int(out) if out.ndim == 0 else out
+
+
+def _criterion_files(criterion: str, aux_bytes: int, min_matches: Optional[int] = None, min_containment: Optional[float] = None) -> Tuple[int, int, int]:
     """(m, p_aux, CRIT_*) of a criterion name and `-a aux_bytes`, for the file-list front ends: m buckets of the .smh<m> files to read
-    (0 = none), precision of the auxiliary .hll_<p> files (0 = none).  min_matches goes with "smh_c" and with nothing else"""
+    (0 = none), precision of the auxiliary .hll_<p> files (0 = none).  min_matches and min_containment go with "smh_c" and with nothing
+    else; it needs one of them"""
     if min_matches is not None and criterion != "smh_c":
         raise ValueError("min_matches is the count threshold of criterion smh_c")
+    if min_containment is not None and criterion != "smh_c":
+        raise ValueError("min_containment is the per-pair count threshold of criterion smh_c")
     if criterion == "smh_a":
         return aux_bytes // 8, 0, CRIT_SMH_A                                   # selection.cpp:231
     if criterion == "smh_c":
-        if min_matches is None:
+        if min_matches is None and min_containment is None:
             raise ValueError("criterion smh_c needs min_matches (the count threshold c_min)")
         if aux_bytes // 8 < 1:
             raise ValueError("criterion smh_c reads the .smh<m> files: aux_bytes (8 m) must be given")
@@ -551,17 +575,19 @@ def _criterion_files(criterion: str, aux_bytes: int, min_matches: Optional[int] 
 
 def select_from_filelist(list_file: str, tau: float, aux_bytes: int, mode: int = MODE_CB_SMH, device: int = 0,
                          fp_mode: int = FP_FMA, algo: int = ALGO_AUTO, criterion: str = "smh_a", top_k: int = 0,
-                         min_matches: Optional[int] = None, measure="jaccard") -> str:
+                         min_matches: Optional[int] = None, measure="jaccard", min_containment: Optional[float] = None) -> str:
     """The whole of selection_cuda.cpp main() (criterion smh_a) -- and of selection.cpp's hll_a / hll_an
     branches (:122-227): returns the text the CPU reference prints for `-c criterion -a aux_bytes -h tau`.
     criterion "none": no criterion in front of the Jaccard test (CRIT_NONE; mode MODE_CB_SMH = the CB bound alone, MODE_SMH = every pair).
-    criterion "smh_c" with min_matches = c: at least c of the m = aux_bytes / 8 SuperMinHash buckets equal (CRIT_SMH_C; `-c smh_c -C c`).
+    criterion "smh_c" with min_matches = c: at least c of the m = aux_bytes / 8 SuperMinHash buckets equal (CRIT_SMH_C; `-c smh_c -C c`);
+    with min_containment = gamma (`-G gamma`), with or without min_matches: at least containment_matches(m, gamma, e_small, e_large) of them,
+    the count at which the SuperMinHash estimate of the smaller genome's containment is gamma (Selector.set_min_containment).
     top_k > 0: only every genome's top_k best partners, one line 'owner_path partner_path J' each, in ranked order (owner rank, then J
     descending, ties by partner rank): a selected pair can be printed twice (once per member), once or not at all.
     measure "max_containment": the pairs with I / min(e_i, e_k) >= tau, that value printed in J's place (Selector.set_measure;
     ValueError with mode=MODE_CB_SMH or an hll_* criterion)."""
     meas = _pass_measure(measure, mode, criterion)
-    m, p_aux, crit = _criterion_files(criterion, aux_bytes, min_matches)
+    m, p_aux, crit = _criterion_files(criterion, aux_bytes, min_matches, min_containment)
     ds = load_dataset(list_file, m, p_aux, fp_mode)
     n_rows, n_bands = banding(m, tau) if m else (1, 1)
     with Selector(device, fp_mode) as sel:
@@ -571,7 +597,9 @@ def select_from_filelist(list_file: str, tau: float, aux_bytes: int, mode: int =
             sel.upload_aux_hll(ds.aux_hll, p_aux)
         sel.set_criterion(crit)
         if crit == CRIT_SMH_C:
-            sel.set_min_matches(min_matches)
+            if min_matches is not None:
+                sel.set_min_matches(min_matches)
+            sel.set_min_containment(min_containment)
         sel.set_measure(meas)
         pairs = sel.run(tau, mode, n_rows, n_bands, algo=algo, top_k=top_k if top_k else None)
     return format_lines(ds.names, pairs)
@@ -670,11 +698,11 @@ def read_pair_list(pair_file: str, names: Sequence[str]) -> np.ndarray:
 
 def select_pairs_from_filelist(list_file: str, pair_file: str, tau: float, aux_bytes: int, mode: int = MODE_CB_SMH, device: int = 0,
                                fp_mode: int = FP_FMA, algo: int = ALGO_AUTO, criterion: str = "smh_a",
-                               min_matches: Optional[int] = None, measure="jaccard") -> str:
+                               min_matches: Optional[int] = None, measure="jaccard", min_containment: Optional[float] = None) -> str:
     """select_from_filelist restricted to the pairs listed in pair_file (lines 'path1 path2[ anything]' with paths of list_file, in
     either order): the text `selection -l list_file -p pair_file -c criterion -a aux_bytes -h tau` prints (measure as there: `-S`)"""
     meas = _pass_measure(measure, mode, criterion)
-    m, p_aux, crit = _criterion_files(criterion, aux_bytes, min_matches)
+    m, p_aux, crit = _criterion_files(criterion, aux_bytes, min_matches, min_containment)
     ds = load_dataset(list_file, m, p_aux, fp_mode)
     listed = read_pair_list(pair_file, ds.names)
     n_rows, n_bands = banding(m, tau) if m else (1, 1)
@@ -684,7 +712,9 @@ def select_pairs_from_filelist(list_file: str, pair_file: str, tau: float, aux_b
             sel.upload_aux_hll(ds.aux_hll, p_aux)
         sel.set_criterion(crit)
         if crit == CRIT_SMH_C:
-            sel.set_min_matches(min_matches)
+            if min_matches is not None:
+                sel.set_min_matches(min_matches)
+            sel.set_min_containment(min_containment)
         sel.set_measure(meas)
         pairs = sel.run_pairs(listed, tau, mode, n_rows, n_bands, algo=algo)
     return format_lines(ds.names, pairs)
@@ -751,7 +781,7 @@ def ooc_select(hll: np.ndarray, aux: np.ndarray, cards: np.ndarray, tau: float, 
 
 def query_from_filelists(query_list: str, db_list: str, tau: float, aux_bytes: int, mode: int = MODE_CB_SMH, fp_mode: int = FP_FMA,
                          device: int = 0, algo: int = ALGO_AUTO, criterion: str = "smh_a", top_k: int = 0,
-                         min_matches: Optional[int] = None, measure="jaccard") -> str:
+                         min_matches: Optional[int] = None, measure="jaccard", min_containment: Optional[float] = None) -> str:
     """Query-vs-database selection: both lists are loaded and sorted by cardinality (load_dataset); returns one line
     'query_path db_path J' per selected pair, in (query rank, database rank) order, J formatted as selection.cpp prints it.
     top_k > 0: only every query's top_k best pairs, in ranked order (query rank, then J descending, ties by database rank).
@@ -760,7 +790,7 @@ def query_from_filelists(query_list: str, db_list: str, tau: float, aux_bytes: i
     c of the m = aux_bytes / 8 buckets equal).  measure "max_containment": the value tested and printed is I / min(e_q, e_d)
     (Selector.set_measure; ValueError with mode=MODE_CB_SMH or an hll_* criterion)."""
     meas = _pass_measure(measure, mode, criterion)
-    m, p_aux, crit = _criterion_files(criterion, aux_bytes, min_matches)
+    m, p_aux, crit = _criterion_files(criterion, aux_bytes, min_matches, min_containment)
     qs = load_dataset(query_list, m, p_aux, fp_mode)
     db = load_dataset(db_list, m, p_aux, fp_mode)
     n_rows, n_bands = banding(m, tau) if m else (1, 1)
@@ -773,7 +803,9 @@ def query_from_filelists(query_list: str, db_list: str, tau: float, aux_bytes: i
             sel.upload_queries_aux_hll(qs.aux_hll, p_aux)
         sel.set_criterion(crit)
         if crit == CRIT_SMH_C:
-            sel.set_min_matches(min_matches)
+            if min_matches is not None:
+                sel.set_min_matches(min_matches)
+            sel.set_min_containment(min_containment)
         sel.set_measure(meas)
         pairs = sel.run_queries(tau, mode, n_rows, n_bands, algo, top_k=top_k if top_k else None)
     h = host_lib()

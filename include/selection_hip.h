@@ -258,6 +258,28 @@ int selhip_ctx_set_criterion(selhip_ctx* ctx, int criterion);
  * signatures carry no c_min, refuse it.  get_param "smhc_path_used": the stage-1 kernel of the last such pass, 1 = the fast path
  * (m = 128, 256, 512, 1024), 0 = the generic one, -1 = none yet.  The stage is timed as "stage1". */
 int selhip_ctx_set_min_matches(selhip_ctx* ctx, int c_min);
+/* SELHIP_CRIT_SMH_C with a PER-PAIR count threshold, for a minimum containment gamma.  With c / m the
+ * SuperMinHash estimate of J, I = J (a + b) / (1 + J) and the containment estimate of the smaller genome is
+ * C^ = I / a = c (a + b) / ((m + c) a), so C^ >= gamma iff c >= gamma m a / (a + b - gamma a).  The rule (csrc/pair_value.hpp, every
+ * operation one IEEE-754 double operation, no contraction):
+ *   smhc_threshold(m, gamma, e_lo, e_hi) -> int in [0, m + 1]        e_lo = min, e_hi = max of the pair's truncated cardinalities
+ *       a = (double)e_lo, b = (double)e_hi
+ *       if (a == 0) return m + 1                  (stage 2 never selects d = 0 under max containment; two empty rows do not survive)
+ *       num = (gamma * (double)m) * a
+ *       den = (a + b) - gamma * a
+ *       if (!(den > 0)) return m + 1              (gamma >= 1 + b / a: no count reaches it)
+ *       q = num / den
+ *       return q <= 0 ? 0 : q > m ? m + 1 : (int)ceil(q)
+ * A pair of the pass's pair space survives stage 1 iff c(i,k) >= max(c_min if set else 0, smhc_threshold(m, gamma, min(e_i, e_k),
+ * max(e_i, e_k))): c_min (selhip_ctx_set_min_matches) stays as a floor -- for e_hi >> e_lo the threshold falls to a handful of buckets.
+ * Sticky like set_min_matches and survives uploads; NaN clears it (the fixed rule again); +-inf is SELHIP_E_BADARG; SELHIP_E_STATE
+ * while a pass is pending.  It takes effect under SELHIP_CRIT_SMH_C alone, where a run now needs c_min or gamma; c_min > m is still
+ * refused.  A bucket prefilter, so taken under both measures and both modes (C^ >= gamma is also necessary for J >= gamma), by every
+ * pass that takes the criterion.  stats[1] = stats[3] = the survivors of the exact rule.  get_param "smhc_rule_used": the rule of the
+ * last such pass, 0 = fixed, 1 = containment, -1 = none yet. */
+int selhip_ctx_set_min_containment(selhip_ctx* ctx, double gamma);
+/* the rule above on the host (no device is touched): what the kernels compute for one pair */
+int selhip_smhc_threshold(int m, double gamma, uint64_t e_lo, uint64_t e_hi);
 /* The MEASURE that stage 2 of the following passes tests against tau_f and records (sticky like the criterion; survives uploads):
  *   SELHIP_MEASURE_JACCARD (default)    J = I / U with I = (double)e_i + (double)e_k - U      (selection.cpp:287; nothing changes)
  *   SELHIP_MEASURE_MAX_CONTAINMENT      V = I / d, d = min(e_i, e_k): the share of the SMALLER genome found in the larger one -- the

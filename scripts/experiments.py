@@ -10,14 +10,16 @@
   experiments.py time -l LIST | -N GENOMES [-m BUCKETS ...] [-h TAU] [-R REPS] [-t THREADS] [-o experiment_smh.csv]
       impl,threads,mh_size,rep,criterio,tiempo    rows for cpu (oracle library: the OpenMP loop of selection.cpp:270-291,
       modes smh_a and CB+smh_a of time_smh.cpp) and gpu (bin/time_smh_hip records `list;label;tau;seconds`)
-  experiments.py recall -l LIST [-a AUX_BYTES] | --cfg NAME [-N GENOMES]  [-h TAU ...] [-c CRITERION ...] [--modes cb nocb] [--min-matches C ...] [-o recall.csv]
+  experiments.py recall -l LIST [-a AUX_BYTES] | --cfg NAME [-N GENOMES]  [-h TAU ...] [-c CRITERION ...] [--modes cb nocb] [--min-matches C ...] [--min-containment G ...] [-o recall.csv]
       what every criterion loses against the pass without one (criterion none: every pair inside the CB bound, or every pair, to the
       HLL-14 Jaccard test), on the MI355X, for a file list or a synthetic configuration of synth.py:
           cfg,criterion,aux,tau,mode,selected,exhaustive,missed,recall,ms_criterion,ms_exhaustive
       "missed" comes from a keyed join of the two record sets; a pair of a criterion that the exhaustive pass does not hold (or
       holds with another Jaccard value) is an error, not a row.  Criteria: smh_a, hll_a, hll_an, hll_a+smh_a, smh_c.  smh_c (at least c of
       the m buckets equal) gives one row per count threshold of --min-matches, "aux" = m<m>c<c>; without the option the threshold is
-      min_matches(m, tau), the count at which the SuperMinHash estimate c / m reaches tau.
+      min_matches(m, tau), the count at which the SuperMinHash estimate c / m reaches tau.  --min-containment G ...: smh_c with its
+      per-pair threshold for a minimum containment G (Selector.set_min_containment), one row per G, "aux" = m<m>g<G>; with
+      --min-matches as well, one row per (C, G), C the floor under the per-pair threshold, "aux" = m<m>c<C>g<G>.
 """
 import argparse
 import csv
@@ -117,7 +119,7 @@ def timing(args):
 RECALL_CRITERIA = {"smh_a": 0, "hll_a": 1, "hll_an": 2, "hll_a+smh_a": 3, "smh_c": 5}
 
 
-def recall_rows(sel, cfg_name, n, m, p_aux, taus, criteria, modes, min_matches=()):
+def recall_rows(sel, cfg_name, n, m, p_aux, taus, criteria, modes, min_matches=(), min_containment=()):
     """rows of the recall table for the sketches loaded in `sel` (a Selector; auxiliary HLL sketches loaded if a criterion needs
     them).  Times: host clock around one synchronous pass (the second of two: the first sizes the lists), results left on the device."""
     import numpy as np
@@ -136,13 +138,19 @@ def recall_rows(sel, cfg_name, n, m, p_aux, taus, criteria, modes, min_matches=(
             sel.set_criterion(pkg.CRIT_NONE)
             full, ms_full = timed(tau, mode, 1, 1)
             key_full = full["i"].astype(np.int64) * n + full["k"]
-            # (smh_c: one row per count threshold)
-            for name, c_min in [(c, t) for c in criteria for t in ((list(min_matches) or [pkg.min_matches(m, tau)]) if c == "smh_c" else [None])]:
+            # (smh_c: one row per count threshold -- per minimum containment, or per pair of the two, when those are given)
+            if min_containment:
+                counts = [(c, g) for c in (list(min_matches) or [None]) for g in min_containment]
+            else:
+                counts = [(c, None) for c in (list(min_matches) or [pkg.min_matches(m, tau)])]
+            for name, (c_min, gamma) in [(c, t) for c in criteria for t in (counts if c == "smh_c" else [(None, None)])]:
                 smh = name in ("smh_a", "hll_a+smh_a")
                 r, b = pkg.banding(m, tau) if smh else (1, 1)
                 sel.set_criterion(RECALL_CRITERIA[name])
                 if c_min is not None:
                     sel.set_min_matches(c_min)
+                if name == "smh_c":
+                    sel.set_min_containment(gamma)                       # (None clears it: the fixed rule)
                 got, ms = timed(tau, mode, r, b)
                 key = got["i"].astype(np.int64) * n + got["k"]
                 pos = np.minimum(np.searchsorted(key_full, key), max(len(key_full) - 1, 0))
@@ -150,7 +158,7 @@ def recall_rows(sel, cfg_name, n, m, p_aux, taus, criteria, modes, min_matches=(
                                        and np.array_equal(full["jaccard"][pos].view(np.uint64), got["jaccard"].view(np.uint64)))
                 if not ok:
                     raise RuntimeError(f"{cfg_name} {name} tau {tau} {mode_name}: a selected pair is not in the exhaustive result")
-                aux = f"m{m}" if name == "smh_a" else f"m{m}c{c_min}" if name == "smh_c" else f"p{p_aux}" if not smh else f"p{p_aux}+m{m}"
+                aux = f"m{m}" if name == "smh_a" else f"m{m}" + (f"c{c_min}" if c_min is not None else "") + (f"g{gamma:g}" if gamma is not None else "") if name == "smh_c" else f"p{p_aux}" if not smh else f"p{p_aux}+m{m}"
                 rows.append([cfg_name, name, aux, tau, mode_name, len(got), len(full), len(full) - len(got),
                              f"{len(got) / len(full):.6f}" if len(full) else "", f"{ms:.3f}", f"{ms_full:.3f}"])
     return rows
@@ -184,7 +192,7 @@ def recall(args):
             sel.attach(keep[0], keep[1], keep[2])
             if p_aux:
                 sel.attach_aux_hll(keep[4], p_aux)
-        rows = recall_rows(sel, name, n, m, p_aux, [float(t) for t in args.tau], args.c, args.modes, args.min_matches)
+        rows = recall_rows(sel, name, n, m, p_aux, [float(t) for t in args.tau], args.c, args.modes, args.min_matches, args.min_containment)
     with open(args.o, "w", newline="") as f:
         w = csv.writer(f)
         w.writerow(RECALL_HEADER)
@@ -211,6 +219,7 @@ def main():
     rc.add_argument("-h", dest="tau", nargs="+", default=["0.9"]); rc.add_argument("-c", nargs="+", default=list(RECALL_CRITERIA), choices=list(RECALL_CRITERIA))
     rc.add_argument("--modes", nargs="+", default=["cb"], choices=["cb", "nocb"]); rc.add_argument("-o", default="recall.csv")
     rc.add_argument("--min-matches", dest="min_matches", type=int, nargs="+", default=[])
+    rc.add_argument("--min-containment", dest="min_containment", type=float, nargs="+", default=[])
     args = ap.parse_args()
     if args.cmd == "time" and not args.l and not args.N:
         sys.exit("time: give -l LIST or -N GENOMES")
