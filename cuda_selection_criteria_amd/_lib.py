@@ -48,6 +48,7 @@ MEASURE_SMH_MATCHES, MEASURE_SMH_JACCARD = 16, 17   # ... from the SuperMinHash 
 # ... from the HLL sketches again: the intersection estimate I = e_a + e_b - U, I / e_row and I / min(e_row, e_col); MAX_CONTAINMENT is
 # also a measure of the passes (Selector.set_measure)
 MEASURE_INTERSECTION, MEASURE_CONTAINMENT, MEASURE_MAX_CONTAINMENT = 32, 33, 34
+ESTIMATOR_HLL, ESTIMATOR_SMH = 0, 1    # SELHIP_ESTIMATOR_*: which estimate the records of an smh_c pass carry (Selector.set_estimator)
 F64, F32 = 0, 1                        # SELHIP_F64 / SELHIP_F32: its element type
 BANDING_CPU, BANDING_CUDA = 0, 1
 TOPK_MAX = 1024                        # SELHIP_TOPK_MAX: largest k of Selector.set_query_topk and Selector.set_allpairs_topk
@@ -80,6 +81,8 @@ HIP_SYMBOLS = {
     "selhip_ctx_set_min_containment": (_i, [_vp, _d]),
     "selhip_smhc_threshold": (_i, [_i, _d, C.c_uint64, C.c_uint64]),
     "selhip_ctx_set_measure": (_i, [_vp, _i]),
+    "selhip_ctx_set_estimator": (_i, [_vp, _i]),
+    "selhip_smh_value": (_d, [_i, _i, _i, C.c_uint64, C.c_uint64]),
     "selhip_hll_cards": (_i, [_vp, _vp, _i64, _i, _vp]),
     "selhip_ctx_get_cards": (_i, [_vp, _vp]),
     "selhip_ctx_run": (_i, [_vp, _i, _i, C.c_float, _i, _i, _i64, _i64]),

@@ -294,6 +294,20 @@ int selhip_ctx_set_measure(selhip_ctx* c, int measure) {
     return SELHIP_OK;
 }
 
+int selhip_ctx_set_estimator(selhip_ctx* c, int estimator) {
+    if (!c) return SELHIP_E_BADARG;
+    if (estimator != SELHIP_ESTIMATOR_HLL && estimator != SELHIP_ESTIMATOR_SMH) {
+        set_err(&c->err, "the estimator of a pass is SELHIP_ESTIMATOR_HLL (%d) or SELHIP_ESTIMATOR_SMH (%d) (got %d)",
+                SELHIP_ESTIMATOR_HLL, SELHIP_ESTIMATOR_SMH, estimator);
+        return SELHIP_E_BADARG;
+    }
+    if (c->pending) { set_err(&c->err, "a pass is still pending (selhip_ctx_finish)"); return SELHIP_E_STATE; }
+    c->estimator = estimator;
+    return SELHIP_OK;
+}
+
+double selhip_smh_value(int measure, int m, int c, uint64_t e1, uint64_t e2) { return selhip::smh_value(measure, m, c, e1, e2); }
+
 int selhip_ctx_set_min_matches(selhip_ctx* c, int c_min) {
     if (!c) return SELHIP_E_BADARG;
     if (c_min < 1) { set_err(&c->err, "min_matches must be >= 1 (got %d)", c_min); return SELHIP_E_BADARG; }
@@ -440,6 +454,7 @@ int selhip_ctx_run_async(selhip_ctx* c, int mode, int algo, float tau_f, int n_r
                          int64_t row_begin, int64_t row_end) {
     if (!c) return SELHIP_E_BADARG;
     { const int rc = accept_measure(c, mode); if (rc) return rc; }
+    { const int rc = accept_estimator(c); if (rc) return rc; }
     if (c->criterion == SELHIP_CRIT_SMH_C) { const int rc = accept_count(c); if (rc) return rc; }
     if (!c->d_aux && c->n) { set_err(&c->err, "run before upload/attach"); return SELHIP_E_STATE; }
     if (mode != SELHIP_MODE_SMH && mode != SELHIP_MODE_CB_SMH) { set_err(&c->err, "bad mode %d", mode); return SELHIP_E_BADARG; }
@@ -449,7 +464,7 @@ int selhip_ctx_run_async(selhip_ctx* c, int mode, int algo, float tau_f, int n_r
         return SELHIP_E_STATE;
     }
     if (c->criterion == SELHIP_CRIT_NONE) { const int rc = accept_dense(c); if (rc) return rc; }
-    const PassPlan plan = pass_plan(c->criterion, algo, c->m, n_rows, n_bands);
+    const PassPlan plan = pass_plan(c->criterion, algo, c->m, n_rows, n_bands, c->estimator);
     if (plan.smh && !plan.count && (n_rows <= 0 || n_bands <= 0 || (long long)n_rows * n_bands != c->m)) {
         // criteria_sketch.hpp:67-70: the reference prints an error and selects nothing; the ABI reports it
         set_err(&c->err, "n_rows*n_bands (%d*%d) != m (%d)", n_rows, n_bands, c->m);
@@ -512,7 +527,7 @@ int selhip_ctx_finish(selhip_ctx* c) {
             pc.n_survivors += q.n_survivors; pc.n_candidates += q.n_candidates; pc.n_aux_in += q.n_aux_in; pc.n_final += q.n_final;
             // the 16-bit join's list is kAppendSegs equal slices: it overflows when its fullest slice does
             const u64 worst = std::max(std::max(std::max(q.n_survivors, q.n_candidates), q.n_pre_segmax * (u64)kAppendSegs), !survivors_final(c->criterion) ? q.n_final : 0);
-            if (worst > slice) { surv_cap = std::max(surv_cap, grown(worst) * (size_t)chunks); grow = true; }
+            if (worst > slice && !c->plan.emit) { surv_cap = std::max(surv_cap, grown(worst) * (size_t)chunks); grow = true; }
             // (n_aux_in is zeroed before every enumeration sub-pass, so what arrives here is the LAST sub-pass's count only: it proves
             //  nothing about the others.  The guarantee is the host-side bound in enqueue_pass -- every sub-pass lists at most
             //  cand.cap - 1024 pairs by construction -- and enum_pairs_kernel never writes past out_cap.)

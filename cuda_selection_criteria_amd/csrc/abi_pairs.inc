@@ -14,6 +14,7 @@ int selhip_ctx_run_pairs_async(selhip_ctx* c, const selhip_int2_t* d_pairs, int6
     if (!c->d_aux && (c->n || n_pairs)) { set_err(&c->err, "run before upload/attach"); return SELHIP_E_STATE; }
     if (mode != SELHIP_MODE_SMH && mode != SELHIP_MODE_CB_SMH) { set_err(&c->err, "bad mode %d", mode); return SELHIP_E_BADARG; }
     { const int rc = accept_measure(c, mode); if (rc) return rc; }
+    { const int rc = accept_estimator(c); if (rc) return rc; }
     if (algo == SELHIP_ALGO_HASHJOIN || algo == SELHIP_ALGO_INDEX) {
         set_err(&c->err, "a pair-list pass takes SELHIP_ALGO_AUTO, _SIG or _STREAM: algo %d is a join, not a check of a given pair", algo);
         return SELHIP_E_BADARG;
@@ -38,7 +39,7 @@ int selhip_ctx_run_pairs_async(selhip_ctx* c, const selhip_int2_t* d_pairs, int6
     if (c->criterion == SELHIP_CRIT_SMH_C) { const int rc = accept_count(c); if (rc) return rc; }
     // (which stage 1 the criterion has: pass_plan's answer; the route below replaces its choice among the smh_a algorithms)
     PassPlan plan;
-    { const PassPlan pp = pass_plan(c->criterion, SELHIP_ALGO_STREAM, c->m, n_rows, n_bands); plan.smh = pp.smh; plan.count = pp.count; }
+    { const PassPlan pp = pass_plan(c->criterion, SELHIP_ALGO_STREAM, c->m, n_rows, n_bands); plan.smh = pp.smh; plan.count = pp.count; plan.emit = pp.count && c->estimator == SELHIP_ESTIMATOR_SMH; }
     if (plan.smh && !plan.count && (n_rows <= 0 || n_bands <= 0 || (long long)n_rows * n_bands != c->m)) {
         set_err(&c->err, "n_rows*n_bands (%d*%d) != m (%d)", n_rows, n_bands, c->m);
         return SELHIP_E_BADARG;

@@ -99,6 +99,7 @@ int selhip_ctx_run_queries(selhip_ctx* c, int mode, int algo, float tau_f, int n
     if (c->pending) { set_err(&c->err, "a pass is still pending (selhip_ctx_finish)"); return SELHIP_E_STATE; }
     if (mode != SELHIP_MODE_SMH && mode != SELHIP_MODE_CB_SMH) { set_err(&c->err, "bad mode %d", mode); return SELHIP_E_BADARG; }
     { const int rc = accept_measure(c, mode); if (rc) return rc; }
+    { const int rc = accept_estimator(c); if (rc) return rc; }
     if (c->criterion == SELHIP_CRIT_NONE) { const int rc = accept_dense(c); if (rc) return rc; }
     if (c->criterion == SELHIP_CRIT_SMH_C) { const int rc = accept_count(c); if (rc) return rc; }
     if (aux_criterion(c->criterion)) {
@@ -113,7 +114,7 @@ int selhip_ctx_run_queries(selhip_ctx* c, int mode, int algo, float tau_f, int n
             return SELHIP_E_BADARG;
         }
     }
-    const PassPlan plan = pass_plan(c->criterion, algo, c->m, n_rows, n_bands);
+    const PassPlan plan = pass_plan(c->criterion, algo, c->m, n_rows, n_bands, c->estimator);
     const bool smh = plan.smh;
     if (algo != SELHIP_ALGO_AUTO && algo != SELHIP_ALGO_STREAM && algo != SELHIP_ALGO_SIG && algo != SELHIP_ALGO_HASHJOIN && algo != SELHIP_ALGO_INDEX) { set_err(&c->err, "bad algo %d", algo); return SELHIP_E_BADARG; }
     if (smh && !plan.count) {
@@ -148,7 +149,9 @@ int selhip_ctx_run_queries(selhip_ctx* c, int mode, int algo, float tau_f, int n
         bool grow = false;
         // (n_pre: the join's list; n_survivors: the survivor list; n_final: what passed the auxiliary criterion)
         const u64 worst = std::max(std::max(pc.n_pre, pc.n_survivors), !survivors_final(c->criterion) ? pc.n_final : 0);
-        if ((smh && (worst > q.surv.cap || worst > q.cand.cap)) || (!survivors_final(c->criterion) && worst > q.fin.cap)) {
+        if (plan.emit) {
+            // (stage 1 stored nothing but records: n_survivors is a tally)
+        } else if ((smh && (worst > q.surv.cap || worst > q.cand.cap)) || (!survivors_final(c->criterion) && worst > q.fin.cap)) {
             cap = std::max(cap, grown(worst));
             grow = true;
         }

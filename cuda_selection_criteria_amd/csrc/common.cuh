@@ -93,14 +93,17 @@ constexpr int kCounterBlocks = 9;               // counter blocks per pass: bloc
 constexpr int kAppendSegs = 64;
 constexpr int kSegStride = 16;                 // u64 slots between two segment counters (128 B: one cache line each)
 
-struct WaveAppender {
-    selhip_int2_t* buf;        // this wave's LDS staging area [kAppendCap]
+// Rec = the record type: selhip_int2_t (candidate and survivor lists; WaveAppender) or selhip_pair_t (the result list, for the kernels
+// that emit records themselves; WaveRecordAppender).  One definition for both.
+template <class Rec>
+struct WaveAppenderT {
+    Rec* buf;                  // this wave's LDS staging area [kAppendCap]
     int count;                 // wave-uniform
-    selhip_int2_t* out;
+    Rec* out;
     u64 out_cap;
     u64* out_count;
 
-    __device__ __forceinline__ void init(selhip_int2_t* lds_block, int wave, selhip_int2_t* o, u64 cap, u64* cnt) {
+    __device__ __forceinline__ void init(Rec* lds_block, int wave, Rec* o, u64 cap, u64* cnt) {
         buf = lds_block + wave * kAppendCap; count = 0; out = o; out_cap = cap; out_count = cnt;
     }
     __device__ __forceinline__ void flush(int lane) {
@@ -114,7 +117,21 @@ struct WaveAppender {
             if (base + (u64)t < out_cap) out[base + (u64)t] = buf[t];
         count = 0;
     }
-    // lanes with pred push (x,y); the call must be wave-uniformly reached
+    // lanes with pred push their record; the call must be wave-uniformly reached
+    __device__ __forceinline__ void push_record(bool pred, const Rec& r, int lane) {
+        const u64 m = __ballot(pred);
+        if (m == 0) return;
+        if (pred) buf[count + (int)__popcll(m & ((1ull << lane) - 1ull))] = r;
+        count += (int)__popcll(m);
+        if (count >= kWave) flush(lane);
+    }
+    // wave-uniform single record
+    __device__ __forceinline__ void push_uniform_record(const Rec& r, int lane) {
+        if (lane == 0) buf[count] = r;
+        count += 1;
+        if (count >= kWave) flush(lane);
+    }
+    // the same for a record of two ints
     __device__ __forceinline__ void push(bool pred, int x, int y, int lane) {
         const u64 m = __ballot(pred);
         if (m == 0) return;
@@ -125,13 +142,14 @@ struct WaveAppender {
         count += (int)__popcll(m);
         if (count >= kWave) flush(lane);
     }
-    // wave-uniform single record
     __device__ __forceinline__ void push_uniform(int x, int y, int lane) {
         if (lane == 0) { buf[count].x = x; buf[count].y = y; }
         count += 1;
         if (count >= kWave) flush(lane);
     }
 };
+using WaveAppender = WaveAppenderT<selhip_int2_t>;
+using WaveRecordAppender = WaveAppenderT<selhip_pair_t>;
 
 // ---------------------------------------------------------------------------------------------
 // block_append: the per-BLOCK form, for kernels whose blocks of kAppendBlock threads work through one batch of kAppendBlock records
@@ -141,19 +159,22 @@ struct WaveAppender {
 // ---------------------------------------------------------------------------------------------
 constexpr int kAppendBlock = 512;
 
-struct BlockAppendLds {
-    selhip_int2_t out[kAppendBlock];
+template <class Rec>                        // (Rec as for WaveAppenderT)
+struct BlockAppendLdsT {
+    Rec out[kAppendBlock];
     u64 base;
     uint32_t count, cand;                   // this batch: records passed on, the caller's tally
 };
+using BlockAppendLds = BlockAppendLdsT<selhip_int2_t>;
 
 // thread 0, before the block's first barrier
-__device__ __forceinline__ void block_append_reset(BlockAppendLds& s) { s.count = 0; s.cand = 0; }
+template <class Rec>
+__device__ __forceinline__ void block_append_reset(BlockAppendLdsT<Rec>& s) { s.count = 0; s.cand = 0; }
 
 // block-uniform, blockDim.x == kAppendBlock (one record per thread and batch): the batch's records with `ok` go to out[] behind *out_count; cand_count (if given) takes the batch's s.cand;
 // stored(q) runs once for every record q that was stored (not clipped), on the thread that stored it
-template <class Stored>
-__device__ __forceinline__ void block_append(BlockAppendLds& s, bool ok, selhip_int2_t pr, int lane, selhip_int2_t* __restrict__ out, u64 out_cap,
+template <class Rec, class Stored>
+__device__ __forceinline__ void block_append(BlockAppendLdsT<Rec>& s, bool ok, Rec pr, int lane, Rec* __restrict__ out, u64 out_cap,
                                              u64* __restrict__ out_count, u64* __restrict__ cand_count, Stored stored) {
     const u64 okb = __ballot(ok);
     if (okb) {
@@ -172,7 +193,7 @@ __device__ __forceinline__ void block_append(BlockAppendLds& s, bool ok, selhip_
     if (threadIdx.x < cnt) {
         const u64 dst = s.base + threadIdx.x;
         if (dst < out_cap) {
-            const selhip_int2_t q = s.out[threadIdx.x];
+            const Rec q = s.out[threadIdx.x];
             out[dst] = q;
             stored(q);
         }
@@ -182,9 +203,10 @@ __device__ __forceinline__ void block_append(BlockAppendLds& s, bool ok, selhip_
     __syncthreads();
 }
 
-__device__ __forceinline__ void block_append(BlockAppendLds& s, bool ok, selhip_int2_t pr, int lane, selhip_int2_t* __restrict__ out, u64 out_cap,
+template <class Rec>
+__device__ __forceinline__ void block_append(BlockAppendLdsT<Rec>& s, bool ok, Rec pr, int lane, Rec* __restrict__ out, u64 out_cap,
                                              u64* __restrict__ out_count, u64* __restrict__ cand_count) {
-    block_append(s, ok, pr, lane, out, out_cap, out_count, cand_count, [](selhip_int2_t) {});
+    block_append(s, ok, pr, lane, out, out_cap, out_count, cand_count, [](Rec) {});
 }
 
 }  // namespace

@@ -61,6 +61,12 @@
 //               and no -o (the result file records no measure).  With -M: intersection (I), containment (I / e_row: the share of the
 //               row genome found in the column genome, with -q the query inside the database genome) or max_containment (jaccard: the
 //               default table); a value of -E hll -- not with -U or -E smh | smh_matches
+//   -V <est>    the estimator behind the value that a selection pass under -c smh_c tests against -h and prints (selhip_ctx_set_estimator).
+//               hll (default): the HyperLogLog value, as ever.  smh: the SuperMinHash estimate of the count c the criterion computes
+//               anyway -- c / m, under -S max_containment c (a + b) / ((m + c) a), a <= b the pair's cardinalities -- with no HLL stage
+//               behind the count: a pair is printed when c passes -C / -G AND that value is at least -h.  The sparse list of pairs by
+//               SuperMinHash J, and with -K / -k the nearest neighbours by it (-c smh_c -C 1 -n -h -1 -K 10 -V smh).  With -l, -q, -p,
+//               -k, -K, -n, -S max_containment, -o; -V smh needs -c smh_c and takes no -M (its estimator is -E), -g or -B
 //   -x          usage
 #include <unistd.h>
 
@@ -77,10 +83,13 @@
 #include "../../../include/selection_host.h"
 
 // -c smh_c: its thresholds onto the context -- -C c_min (0: not given) and -G gamma (NaN: not given)
+// and its estimator (-V)
 static double g_min_containment = std::nan("");
+static int g_estimator = SELHIP_ESTIMATOR_HLL;
 static int set_count_thresholds(selhip_ctx* ctx, int min_matches) {
     int r = min_matches > 0 ? selhip_ctx_set_min_matches(ctx, min_matches) : 0;
     if (!r && !std::isnan(g_min_containment)) r = selhip_ctx_set_min_containment(ctx, g_min_containment);
+    if (!r) r = selhip_ctx_set_estimator(ctx, g_estimator);
     return r;
 }
 
@@ -256,14 +265,14 @@ int main(int argc, char* argv[]) {
     std::string criterion = "smh_a";
     int threads = 8, n_gpus = 1, mode = SELHIP_MODE_CB_SMH, algo = SELHIP_ALGO_AUTO, fp_mode = SELHIP_FP_FMA;
     long long ooc_block = 0;
-    std::string out_file = "", dump_file = "", query_file = "", pair_file = "", matrix_file = "", estimator = "", measure_name = "";
+    std::string out_file = "", dump_file = "", query_file = "", pair_file = "", matrix_file = "", estimator = "", measure_name = "", value_estimator = "";
     bool measure_given = false;
     bool gpus_given = false, topk_given = false, nbr_given = false, matrix_given = false, union_measure = false, aux_given = false, estimator_given = false;
     const char* selection_opt = nullptr;         // the first of -h, -c, -n, -A seen: options of a selection pass, which -M does not run
     long long top_k = 0, nbr_k = 0, min_matches = 0;
-    bool cmin_given = false, gamma_given = false;
+    bool cmin_given = false, gamma_given = false, value_given = false;
     int c;
-    while ((c = getopt(argc, argv, "xl:b:a:h:c:C:G:t:g:nA:F:B:o:r:q:k:K:p:M:UE:S:")) != -1) {
+    while ((c = getopt(argc, argv, "xl:b:a:h:c:C:G:t:g:nA:F:B:o:r:q:k:K:p:M:UE:S:V:")) != -1) {
         switch (c) {
             case 'x': std::cout << "Usage: -l -h -a -b [-c smh_a|hll_a|hll_an|none|smh_c -C c_min|-G gamma] [-t threads] [-g gpus] [-n] [-A auto|stream|sig] [-F 0|1] [-B block] [-o file] | -r file\n"
                                    "       -l db_list -q query_list -h -a [-c smh_a|hll_a|hll_an|none|smh_c -C c_min|-G gamma] [-n] [-A auto|stream|sig|index] [-F 0|1] [-k best_per_query]   (query-vs-database selection)\n"
@@ -273,13 +282,15 @@ int main(int argc, char* argv[]) {
                                    "       -l list [-q query_list] -M out.tsv -E smh|smh_matches -a bytes   (the same table from the SuperMinHash sketches: equal buckets / m, or their count)\n"
                                    "       ... -n -S max_containment -h gamma -c smh_c -G gamma -a bytes [-C c_min]   (its prefilter: the count at which the SuperMinHash estimate of the containment is gamma)\n"
                                    "       ... -n -S max_containment [-c smh_a|none|smh_c]   (with -l, -q, -p, -k, -K: select and print I / min(e1, e2), the share of the smaller genome found in the larger)\n"
-                                   "       -l list [-q query_list] -M out.tsv -S intersection|containment|max_containment   (the table of I = e1 + e2 - U, I / e_row or I / min(e_row, e_col))\n"; return 0;
+                                   "       -l list [-q query_list] -M out.tsv -S intersection|containment|max_containment   (the table of I = e1 + e2 - U, I / e_row or I / min(e_row, e_col))\n"
+                                   "       ... -c smh_c -C c_min|-G gamma -a bytes -V smh|hll   (with -l, -q, -p, -k, -K, -n, -S max_containment, -o: -V smh tests and prints the SuperMinHash estimate of the count, c / m, with no HLL stage)\n"; return 0;
             case 'q': query_file = optarg; break;
             case 'p': pair_file = optarg; break;
             case 'M': matrix_file = optarg; matrix_given = true; break;
             case 'U': union_measure = true; break;
             case 'E': estimator = optarg; estimator_given = true; break;
             case 'S': measure_name = optarg; measure_given = true; break;
+            case 'V': value_estimator = optarg; value_given = true; break;
             case 'k': top_k = std::strtoll(optarg, nullptr, 10); topk_given = true; break;
             case 'K': nbr_k = std::strtoll(optarg, nullptr, 10); nbr_given = true; break;
             case 'B': ooc_block = std::stoll(optarg); break;
@@ -298,6 +309,26 @@ int main(int argc, char* argv[]) {
             case 'A': if (!selection_opt) selection_opt = "-A"; algo = !strcmp(optarg, "stream") ? SELHIP_ALGO_STREAM : !strcmp(optarg, "sig") ? SELHIP_ALGO_SIG : !strcmp(optarg, "hashjoin") ? SELHIP_ALGO_HASHJOIN : !strcmp(optarg, "index") ? SELHIP_ALGO_INDEX : SELHIP_ALGO_AUTO; break;
             case 'F': fp_mode = std::stoi(optarg) ? SELHIP_FP_FMA : SELHIP_FP_STRICT; break;
             default: break;
+        }
+    }
+    // -V: checked before any file is read or device opened
+    if (value_given) {
+        if (value_estimator != "hll" && value_estimator != "smh") {
+            std::cerr << "selection: -V (the estimator of a selection pass): hll or smh, not '" << value_estimator << "'\n";
+            return 2;
+        }
+        if (value_estimator == "smh") {
+            if (matrix_given) { std::cerr << "selection: -V smh is an option of a selection pass; the estimator of -M (the dense similarity matrix) is -E\n"; return 2; }
+            if (criterion != "smh_c") {
+                std::cerr << "selection: -V smh needs -c smh_c: the SuperMinHash estimate is computed from the count of equal buckets, which that criterion alone takes\n";
+                return 2;
+            }
+            const char* clash = gpus_given ? "-g" : ooc_block != 0 ? "-B" : nullptr;
+            if (clash) {
+                std::cerr << "selection: -V smh cannot be combined with " << clash << "; the multi-GPU and out-of-core drivers carry no estimator\n";
+                return 2;
+            }
+            g_estimator = SELHIP_ESTIMATOR_SMH;
         }
     }
     // -S: checked before any file is read or device opened

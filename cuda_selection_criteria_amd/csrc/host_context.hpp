@@ -247,6 +247,8 @@ struct selhip_ctx {
     int smhc_rule_used = -1;
     // what stage 2 of every pass tests against tau and records (selhip_ctx_set_measure): SELHIP_MEASURE_JACCARD or _MAX_CONTAINMENT
     int measure = SELHIP_MEASURE_JACCARD;
+    // which estimate the records of an smh_c pass carry (selhip_ctx_set_estimator): SELHIP_ESTIMATOR_HLL, or _SMH -- stage 1 emits them
+    int estimator = SELHIP_ESTIMATOR_HLL;
 
     // last run parameters (for overflow re-runs)
     bool have_run = false, pending = false;

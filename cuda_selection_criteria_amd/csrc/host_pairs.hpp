@@ -53,7 +53,7 @@ int enqueue_pairs_pass(selhip_ctx* c) {
         TimerScope t(c, T_PREP);
         hipLaunchKernelGGL(cb_bounds_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
                            c->d_cards, n, tau, use_cb, row_map(c, 0, 0), c->ecard.p, c->hi.p, pc0,
-                           grouping_on(c) ? c->csr_cnt.p : nullptr, grouping_on(c) ? (int)c->csr_cnt.cap : 0, 0, pcs.next,
+                           grouping_on(c) && !c->plan.emit ? c->csr_cnt.p : nullptr, grouping_on(c) && !c->plan.emit ? (int)c->csr_cnt.cap : 0, 0, pcs.next,
                            c->seg_cnt.p, (int)c->seg_cnt.cap);
         HIPCHK(&c->err, hipGetLastError());
     }
@@ -69,12 +69,17 @@ int enqueue_pairs_pass(selhip_ctx* c) {
             if (c->plan.count) {
                 const PairsDirectShape sh = pairs_direct_shape(P);
                 c->smhc_rule_used = smhc_containment(c) ? 1 : 0;
-                if (smhc_containment(c))
-                    hipLaunchKernelGGL(pairs_count_kernel<kSmhcContainment>, dim3(sh.grid), dim3(kPairsBlock), 0, c->stream, c->d_aux, c->m, c->min_matches,
-                                       c->list_pairs, P, n, c->ecard.p, tau, use_cb, sh.gpw, io.surv, io.cap, &io.pc->n_survivors, pc0, c->min_containment);
-                else
-                    hipLaunchKernelGGL(pairs_count_kernel<kSmhcFixed>, dim3(sh.grid), dim3(kPairsBlock), 0, c->stream, c->d_aux, c->m, c->min_matches,
-                                       c->list_pairs, P, n, c->ecard.p, tau, use_cb, sh.gpw, io.surv, io.cap, &io.pc->n_survivors, pc0, c->min_containment);
+                const PairsGammaEmit gamma_em{c->min_containment, smhc_emit(c, pc0)};
+                with_flag(smhc_containment(c), [&](auto C) {
+                    constexpr int RULE = decltype(C)::value ? kSmhcContainment : kSmhcFixed;
+                    if (c->plan.emit)
+                        hipLaunchKernelGGL((pairs_count_kernel<RULE, true>), dim3(sh.grid), dim3(kPairsBlock), 0, c->stream, c->d_aux, c->m, smhc_floor(c),
+                                           c->list_pairs, P, n, c->ecard.p, tau, use_cb, sh.gpw, c->results.p, (u64)c->results.cap, &io.pc->n_survivors, pc0,
+                                           gamma_em);
+                    else
+                        hipLaunchKernelGGL((pairs_count_kernel<RULE, false>), dim3(sh.grid), dim3(kPairsBlock), 0, c->stream, c->d_aux, c->m, c->min_matches,
+                                           c->list_pairs, P, n, c->ecard.p, tau, use_cb, sh.gpw, io.surv, io.cap, &io.pc->n_survivors, pc0, c->min_containment);
+                });
             } else if (c->pairs_route_used == 1)
                 hipLaunchKernelGGL(pairs_verify_kernel, dim3(grid), dim3(kPairsBlock), 0, c->stream, c->d_aux, c->m, c->n_rows, c->n_bands, c->sig.Q.p,
                                    c->list_pairs, P, n, c->ecard.p, tau, use_cb, io.surv, io.cap, io.pc, pc0, c->verify_fb);
@@ -84,6 +89,12 @@ int enqueue_pairs_pass(selhip_ctx* c) {
                                    c->list_pairs, P, n, c->ecard.p, (const double*)nullptr, tau, use_cb, sh.gpw, io.surv, io.cap, &io.pc->n_survivors, pc0);
             }
             HIPCHK(&c->err, hipGetLastError());
+        }
+        if (c->plan.emit) {
+            // the count kernel wrote the records: nothing is left for a stage 2
+            HIPCHK(&c->err, hipMemcpyAsync(c->h_pc, c->pcb, sizeof(PassCounters) * (kMaxChunks + 1), hipMemcpyDeviceToHost, c->stream));
+            c->pc.dirty = false;
+            return SELHIP_OK;
         }
         if (crit == SELHIP_CRIT_HLL_A_SMH_A) {
             TimerScope t(c, T_AUX);

@@ -87,29 +87,52 @@ int accept_measure(selhip_ctx* c, int mode) {
     return SELHIP_OK;
 }
 
+// ---- the estimator of the records (selhip_ctx_set_estimator) -------------------------------------
+// what SELHIP_ESTIMATOR_SMH refuses, checked by every entry before it claims a counter set: the estimate is a function of the count of
+// equal buckets, which criterion smh_c alone computes for every pair it admits
+int accept_estimator(selhip_ctx* c) {
+    if (c->estimator == SELHIP_ESTIMATOR_HLL || c->criterion == SELHIP_CRIT_SMH_C) return SELHIP_OK;
+    set_err(&c->err, "estimator smh (SELHIP_ESTIMATOR_SMH) records a value computed from the count of criterion smh_c (SELHIP_CRIT_SMH_C) and "
+                     "takes no other criterion (criterion %d); selhip_ctx_set_estimator(ctx, SELHIP_ESTIMATOR_HLL) first", c->criterion);
+    return SELHIP_E_BADARG;
+}
+// what the count kernels of a pass that emits take besides: its records go to the context's result list behind block 0's n_results.
+// (the count floor of such a pass is 1: a pair without an equal bucket has no record)
+SmhcEmit smhc_emit(const selhip_ctx* c, PassCounters* pc0) { return SmhcEmit{(double)c->tau_f, c->measure, pc0}; }
+int smhc_floor(const selhip_ctx* c) { return c->plan.emit ? std::max(c->min_matches, 1) : c->min_matches; }
+
 // the rows of X (owned rows of rm) against the candidates of Y from first_cand on.  QUERY = false: X = Y = the context's rows, windows
 // from hi and pc_in's z0; QUERY = true: the queries against the database, windows lo / hi
 // (ex, ey: the truncated cardinalities of the rows and of the candidates, read by the containment rule alone)
 struct CountSets { const u64* X; const u64* Y; int n_x, n_y; const int* lo; const int* hi; const PassCounters* pc_in; const u64* ex; const u64* ey; };
+// pc0 (a pass that emits, else null): the pass's counter block 0 -- the records go to the context's result list, `surv` is not written
+// and pc->n_survivors takes the tally of the pairs that passed the count test
 template <bool QUERY>
 hipError_t launch_count(selhip_ctx* c, hipStream_t st, const CountSets& a, const RowMap& rm, int first_cand,
-                        selhip_int2_t* surv, u64 cap, PassCounters* pc) {
-    const int m = c->m, c_min = c->min_matches;
+                        selhip_int2_t* surv, u64 cap, PassCounters* pc, PassCounters* pc0 = nullptr) {
+    const int m = c->m, c_min = smhc_floor(c);
+    const bool emit = pc0 != nullptr;
+    selhip_pair_t* const res = c->results.p;
+    const u64 res_cap = (u64)c->results.cap;
     c->smhc_path_used = smhc_fast(m) ? 1 : 0;
     const bool cont = smhc_containment(c);
     c->smhc_rule_used = cont ? 1 : 0;
     const SmhcRule rule{c->min_containment, a.ex, a.ey};
+    const SmhcRuleEmit rule_em{rule, smhc_emit(c, pc0)};
     if (smhc_fast(m)) {
         const int nch = m / 128;
-        const long long n_tiles = rm.n_tiles(smhc_q(nch));
+        const long long n_tiles = rm.n_tiles(smhc_q(nch, emit && cont));
         if (n_tiles > 0x7FFFFFFFll) return hipErrorInvalidValue;
         const int chunk_base = (first_cand / kChunk) * kChunk;
         const int n_chunks = (a.n_y - chunk_base + kChunk - 1) / kChunk;
         if (n_tiles <= 0 || n_chunks <= 0) return hipSuccess;
         const long long blocks = n_tiles * n_chunks;
         if (blocks > 0x7FFFFFFFll) return hipErrorInvalidValue;
-#define SELHIP_SMHC_LAUNCH_R(NCH, RULE) hipLaunchKernelGGL((smh_count_kernel<NCH, QUERY, RULE>), dim3((unsigned)blocks), dim3(kBlock), 0, st, (const u64x2*)a.X, (const u64x2*)a.Y, \
-                                                   a.n_x, a.n_y, a.lo, a.hi, a.pc_in, rm, (int)n_tiles, chunk_base, c_min, surv, cap, pc, rule)
+#define SELHIP_SMHC_LAUNCH_R(NCH, RULE) do { \
+            if (emit) hipLaunchKernelGGL((smh_count_kernel<NCH, QUERY, RULE, true>), dim3((unsigned)blocks), dim3(kBlock), 0, st, (const u64x2*)a.X, (const u64x2*)a.Y, \
+                                         a.n_x, a.n_y, a.lo, a.hi, a.pc_in, rm, (int)n_tiles, chunk_base, c_min, res, res_cap, pc, rule_em); \
+            else hipLaunchKernelGGL((smh_count_kernel<NCH, QUERY, RULE, false>), dim3((unsigned)blocks), dim3(kBlock), 0, st, (const u64x2*)a.X, (const u64x2*)a.Y, \
+                                    a.n_x, a.n_y, a.lo, a.hi, a.pc_in, rm, (int)n_tiles, chunk_base, c_min, surv, cap, pc, rule); } while (0)
 #define SELHIP_SMHC_LAUNCH(NCH) do { if (cont) SELHIP_SMHC_LAUNCH_R(NCH, kSmhcContainment); else SELHIP_SMHC_LAUNCH_R(NCH, kSmhcFixed); } while (0)
         switch (nch) {
             case 1: SELHIP_SMHC_LAUNCH(1); break;
@@ -125,19 +148,23 @@ hipError_t launch_count(selhip_ctx* c, hipStream_t st, const CountSets& a, const
     const long long blocks = rows * ((a.n_y + kBlock - 1) / kBlock);
     if (blocks <= 0) return hipSuccess;
     if (rows > 0x7FFFFFFFll || blocks > 0x7FFFFFFFll) return hipErrorInvalidValue;
-    if (cont)
-        hipLaunchKernelGGL((smh_count_generic_kernel<QUERY, kSmhcContainment>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a.X, a.Y, a.n_x, a.n_y, m, a.lo, a.hi, a.pc_in,
-                           rm, (int)rows, c_min, surv, cap, pc, rule);
-    else
-        hipLaunchKernelGGL((smh_count_generic_kernel<QUERY, kSmhcFixed>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a.X, a.Y, a.n_x, a.n_y, m, a.lo, a.hi, a.pc_in,
-                           rm, (int)rows, c_min, surv, cap, pc, rule);
+    with_flag(cont, [&](auto C) {
+        constexpr int RULE = decltype(C)::value ? kSmhcContainment : kSmhcFixed;
+        if (emit)
+            hipLaunchKernelGGL((smh_count_generic_kernel<QUERY, RULE, true>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a.X, a.Y, a.n_x, a.n_y, m, a.lo, a.hi, a.pc_in,
+                               rm, (int)rows, c_min, res, res_cap, pc, rule_em);
+        else
+            hipLaunchKernelGGL((smh_count_generic_kernel<QUERY, RULE, false>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a.X, a.Y, a.n_x, a.n_y, m, a.lo, a.hi, a.pc_in,
+                               rm, (int)rows, c_min, surv, cap, pc, rule);
+    });
     return hipGetLastError();
 }
 
 // the all-pairs form behind cb_bounds_kernel: candidates k > row_begin, as in launch_stage1
 hipError_t launch_stage1_count(selhip_ctx* c, const StageIO& io, const RowMap& rm) {
     const int n = (int)c->n;
-    return launch_count<false>(c, io.st, CountSets{c->d_aux, c->d_aux, n, n, nullptr, c->hi.p, c->pcb, c->ecard.p, c->ecard.p}, rm, rm.row_begin + 1, io.surv, io.cap, io.pc);
+    return launch_count<false>(c, io.st, CountSets{c->d_aux, c->d_aux, n, n, nullptr, c->hi.p, c->pcb, c->ecard.p, c->ecard.p}, rm, rm.row_begin + 1, io.surv, io.cap, io.pc,
+                               c->plan.emit ? c->pcb : nullptr);
 }
 
 
@@ -695,6 +722,7 @@ int enqueue_chain(selhip_ctx* c, const Chain& ch, int rb, int re, double tau, bo
         else if (use_sig) HIPCHK(&c->err, launch_stage1_sig(c, io, c->n_rows, c->n_bands, rm));
         else              HIPCHK(&c->err, launch_stage1(c, io, c->n_rows, c->n_bands, rm));
     }
+    if (c->plan.emit) return SELHIP_OK;                          // the count kernel wrote the records: nothing is left for a stage 2
     const selhip_int2_t* final_list = io.surv;
     const u64* final_count = &io.pc->n_survivors;
     u64 final_cap = io.cap;
@@ -869,7 +897,7 @@ int enqueue_pass(selhip_ctx* c) {
         TimerScope t(c, T_PREP);
         hipLaunchKernelGGL(cb_bounds_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
                            c->d_cards, n, tau, c->mode == SELHIP_MODE_CB_SMH ? 1 : 0, row_map(c, rb, re), c->ecard.p, c->hi.p, pc0,
-                           grouping_on(c) ? c->csr_cnt.p : nullptr, grouping_on(c) ? (int)c->csr_cnt.cap : 0, (int)c->cand_begin, pc_next,
+                           grouping_on(c) && !plan.emit ? c->csr_cnt.p : nullptr, grouping_on(c) && !plan.emit ? (int)c->csr_cnt.cap : 0, (int)c->cand_begin, pc_next,
                            c->seg_cnt.p, (int)c->seg_cnt.cap);
         HIPCHK(&c->err, hipGetLastError());
         if (plan.il_stream) {

@@ -83,14 +83,17 @@ bool survivors_final(int criterion) { return criterion == SELHIP_CRIT_SMH_A || c
 // (kernel_smhc.cuh), which reads neither the band shape nor the algorithm either: none of the fields below is set.  use_sig: band
 // signatures are built and joined (use_hash: by the sort join; use_index: a query pass probes the sorted index instead of joining);
 // il_stream: ALGO_STREAM in its tiled form, which reads the bucket-interleaved copy of the sketches.  bad: the format of the error
-// (it takes n_rows, n_bands) when the caller insisted on an algorithm that does not take the band shape
+// (it takes n_rows, n_bands) when the caller insisted on an algorithm that does not take the band shape.  emit: stage 1 emits the
+// records -- the count under SELHIP_ESTIMATOR_SMH (selhip_ctx_set_estimator): the pass is its bounds or windows kernel, the count
+// kernel and the counter copy; nothing is grouped, no histogram and no estimate is launched, no survivor list is filled
 struct PassPlan {
-    bool smh = false, count = false, use_hash = false, use_sig = false, use_index = false, il_stream = false;
+    bool smh = false, count = false, emit = false, use_hash = false, use_sig = false, use_index = false, il_stream = false;
     const char* bad = nullptr;
 };
-PassPlan pass_plan(int criterion, int algo, int m, int n_rows, int n_bands) {
+PassPlan pass_plan(int criterion, int algo, int m, int n_rows, int n_bands, int estimator = SELHIP_ESTIMATOR_HLL) {
     PassPlan p;
     p.count = criterion == SELHIP_CRIT_SMH_C;
+    p.emit = p.count && estimator == SELHIP_ESTIMATOR_SMH;
     p.smh = p.count || criterion == SELHIP_CRIT_SMH_A || criterion == SELHIP_CRIT_HLL_A_SMH_A;
     if (!p.smh || p.count) return p;
     const bool sig_ok = sig_supported(n_rows, n_bands);

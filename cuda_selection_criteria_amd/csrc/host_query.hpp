@@ -151,7 +151,7 @@ int enqueue_query_pass(selhip_ctx* c, double tau) {
     {
         TimerScope t(c, T_PREP);
         // D's bit planes for stage 2a, when the all-pairs path keeps none
-        if (!use_bitslices(c) && q.db_bs_gen != c->db_gen) {
+        if (!use_bitslices(c) && q.db_bs_gen != c->db_gen && !c->plan.emit) {
             const int rc = q.db_planes.build(&c->err, c->stream, c->d_hll, n_d);
             if (rc) return rc;
             q.db_bs_gen = c->db_gen;
@@ -187,7 +187,13 @@ int enqueue_query_pass(selhip_ctx* c, double tau) {
         // smh_c: the count kernel of the all-pairs pass over the rectangle, every query's window [lo, hi] in place of the triangle's
         TimerScope t(c, T_STAGE1);
         HIPCHK(&c->err, launch_count<true>(c, c->stream, CountSets{q.d_aux, c->d_aux, n_q, n_d, q.lo.p, q.hi.p, pc, q.ecard.p, q.ecard.p + n_q}, RowMap{0, n_q, n_q, 1, 0}, 0,
-                                           q.surv.p, (u64)q.surv.cap, pc));
+                                           q.surv.p, (u64)q.surv.cap, pc, c->plan.emit ? pc : nullptr));
+        if (c->plan.emit) {
+            // the count kernel wrote the records, database ranks and all: no stage 2 and no fix-up behind it
+            HIPCHK(&c->err, hipMemcpyAsync(q.h_pc, pc, sizeof(PassCounters), hipMemcpyDeviceToHost, c->stream));
+            q.pc.dirty = false;
+            return SELHIP_OK;
+        }
     } else if (use_sig) {
         const long long key = ((long long)r << 40) | ((long long)nb << 24) | ((c->db_gen & 0xFFFFF) << 1) | 1;
         if (q.db_sig_key != key) {

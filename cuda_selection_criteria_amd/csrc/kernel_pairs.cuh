@@ -21,13 +21,16 @@ constexpr int kPairsBlock = kAppendBlock;
 constexpr unsigned kPairsMaxGrid = 1024;
 constexpr int kPairsSteps = 8;                 // pairs_direct_kernel: 16-bucket steps whose loads are in flight together
 
-struct PairsLds {
-    BlockAppendLds app;                     // (block_append, common.cuh; app.cand = the batch's entries with an equal band signature)
+template <class Rec>                        // (the record type of what the kernel passes on, as for BlockAppendLdsT)
+struct PairsLdsT {
+    BlockAppendLdsT<Rec> app;               // (block_append, common.cuh; app.cand = the batch's entries with an equal band signature)
     uint32_t bad;
     u64 eval, bad_at;                       // the block's tallies, added up when its waves end
 };
+using PairsLds = PairsLdsT<selhip_int2_t>;
 
-__device__ __forceinline__ void pairs_lds_init(PairsLds& s) {
+template <class Rec>
+__device__ __forceinline__ void pairs_lds_init(PairsLdsT<Rec>& s) {
     if (threadIdx.x == 0) { block_append_reset(s.app); s.bad = 0; s.eval = 0; s.bad_at = 0; }
     __syncthreads();
 }
@@ -66,7 +69,8 @@ __device__ __forceinline__ selhip_int2_t pairs_entry(const selhip_int2_t* __rest
 }
 
 // the block's tallies into the pass's counter block 0
-__device__ __forceinline__ void pairs_block_tally(PairsLds& s, const PairsTally& tl, int lane, PassCounters* __restrict__ pc0) {
+template <class Rec>
+__device__ __forceinline__ void pairs_block_tally(PairsLdsT<Rec>& s, const PairsTally& tl, int lane, PassCounters* __restrict__ pc0) {
     if (lane == 0) {
         if (tl.eval) atomicAdd(&s.eval, tl.eval);
         if (tl.bad) { atomicAdd(&s.bad, tl.bad); atomicMax(&s.bad_at, tl.bad_at); }
@@ -228,17 +232,28 @@ void pairs_direct_kernel(const u64* __restrict__ aux, int m, int n_rows, int n_b
 // ALL m buckets in place of the band test: every step adds the population count of the quarter-wave's 16-bit equality mask, and
 // smhc_selects decides the entry when its row is through.  Nothing stops early: a count needs every bucket.
 // RULE = kSmhcContainment (kernel_smhc.cuh): the entry's own exact threshold in place of c_min, from the cardinalities of its two ranks.
+// EMIT (kernel_smhc.cuh; false = the kernel as it was, instruction for instruction): every group hands its four counts to the lanes
+// that hold the entries; an entry that passed the count test is tallied in *surv_count -- not stored -- and its record {x, y, V},
+// V = selhip::smh_value(...) >= tau, goes into the result list `surv` behind pc0->n_results through the same block append.
 // ---------------------------------------------------------------------------------------------
-template <int RULE>
+struct PairsGammaEmit { double gamma; SmhcEmit em; };              // (the emit form's last argument: gamma, and SmhcEmit behind it)
+template <bool EMIT> using PairsGammaArg = std::conditional_t<EMIT, PairsGammaEmit, double>;
+__device__ __forceinline__ double pairs_gamma(double g) { return g; }
+__device__ __forceinline__ double pairs_gamma(const PairsGammaEmit& g) { return g.gamma; }
+
+template <int RULE, bool EMIT = false>
 __global__ __launch_bounds__(kPairsBlock)
 void pairs_count_kernel(const u64* __restrict__ aux, int m, int c_min,
                         const selhip_int2_t* __restrict__ list, u64 n_pairs, int n, const u64* __restrict__ ecard, double tau, int use_cb, int gpw,
-                        selhip_int2_t* __restrict__ surv, u64 surv_cap, u64* __restrict__ surv_count, PassCounters* __restrict__ pc0, double gamma) {
-    __shared__ PairsLds s;
+                        SmhcRecord<EMIT>* __restrict__ surv, u64 surv_cap, u64* __restrict__ surv_count, PassCounters* __restrict__ pc0,
+                        PairsGammaArg<EMIT> gamma) {
+    __shared__ PairsLdsT<SmhcRecord<EMIT>> s;
+    __shared__ u64 s_passed;                                                  // EMIT: the block's entries that passed the count test
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
     const int sub = lane & 15, quarter = lane >> 4, qshift = quarter * 16;
     const int per_wave = 4 * gpw;                                             // entries a wave takes per batch: its first per_wave lanes hold one each
     const u64 per_block = (u64)(kPairsBlock / kWave) * per_wave;
+    if constexpr (EMIT) { if (threadIdx.x == 0) s_passed = 0; }               // (before the barrier of pairs_lds_init)
     pairs_lds_init(s);
     PairsTally tl;
     for (u64 base = (u64)blockIdx.x * per_block; base < n_pairs; base += (u64)gridDim.x * per_block) {
@@ -248,6 +263,7 @@ void pairs_count_kernel(const u64* __restrict__ aux, int m, int c_min,
         const selhip_int2_t pr = pairs_entry(list, j, in, n, ecard, tau, use_cb, tl, &live);
         const u64 live_mask = __ballot(live);
         u64 ok_mask = 0;
+        int my_cnt = 0;                                                       // EMIT: the count of the entry this lane holds
 #pragma unroll 1
         for (int t = 0; t < gpw; ++t) {
             if (((live_mask >> (t * 4)) & 0xFull) == 0) continue;             // none of this group's four entries is live
@@ -272,13 +288,28 @@ void pairs_count_kernel(const u64* __restrict__ aux, int m, int c_min,
                     cnt += __popc((uint32_t)(__ballot(va[u] == vb[u]) >> qshift) & 0xFFFFu);
             }
             int thr = c_min;
-            if constexpr (RULE == kSmhcContainment) thr = smhc_pair_threshold(m, gamma, ecard[px], ecard[py], c_min);       // ({0, 0} when not live)
+            if constexpr (RULE == kSmhcContainment) thr = smhc_pair_threshold(m, pairs_gamma(gamma), ecard[px], ecard[py], c_min);       // ({0, 0} when not live)
             ok_mask |= pairs_quarter_bits(__ballot(open && sub == 0 && smhc_selects(cnt, thr)), t * 4);
+            if constexpr (EMIT) {
+                const int c4 = __shfl(cnt, (lane & 3) * 16, kWave);           // lane 4 t + j holds the entry of quarter j
+                if ((lane >> 2) == t) my_cnt = c4;
+            }
         }
         const bool ok = (ok_mask >> lane) & 1ull;
-        block_append(s.app, ok, pr, lane, surv, surv_cap, surv_count, nullptr);
+        if constexpr (EMIT) {
+            bool sel;
+            const selhip_pair_t r = smhc_record(gamma.em, m, my_cnt, ecard[pr.x], ecard[pr.y], pr.x, pr.y, &sel);      // ({0, 0} when not live)
+            const u64 okb = __ballot(ok);
+            if (okb && lane == 0) atomicAdd(&s_passed, (u64)__popcll(okb));
+            block_append(s.app, ok && sel, r, lane, surv, surv_cap, &gamma.em.pc0->n_results, nullptr);
+        } else {
+            block_append(s.app, ok, pr, lane, surv, surv_cap, surv_count, nullptr);
+        }
     }
     pairs_block_tally(s, tl, lane, pc0);
+    if constexpr (EMIT) {                                                     // (behind the tally's barrier)
+        if (threadIdx.x == 0 && s_passed) atomicAdd(surv_count, s_passed);
+    }
 }
 
 }  // namespace

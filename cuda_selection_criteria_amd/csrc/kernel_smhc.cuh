@@ -5,8 +5,8 @@
 // Part of libselhip.so; included by selection_kernels.hip only (one translation unit, anonymous namespace).  All kernels read `aux`
 // row-major, as uploaded or attached: for a count any lane <-> bucket map does, as long as both rows of a pair use the same one
 // (DESIGN.md section 14), so there is no interleaved copy as in ALGO_STREAM.
-//   smh_count_kernel<NCH, QUERY, RULE>  m = 128 * NCH buckets, NCH in {1, 2, 4, 8} (smhc_fast): smh_stream_kernel's block shape and enumeration
-//   smh_count_generic_kernel<QUERY, RULE> every other m > 0: smh_generic_kernel's unit, lane = candidate, a serial loop over the buckets
+//   smh_count_kernel<NCH, QUERY, RULE, EMIT>  m = 128 * NCH buckets, NCH in {1, 2, 4, 8} (smhc_fast): smh_stream_kernel's block shape and enumeration
+//   smh_count_generic_kernel<QUERY, RULE, EMIT> every other m > 0: smh_generic_kernel's unit, lane = candidate, a serial loop over the buckets
 // QUERY = false: the all-pairs pass (rows and candidates from one set, the window of row i is [max(i + 1, z0), hi[i]], records (i, k));
 // QUERY = true: the query pass (rows from Q, candidates from D, the window of query i is [lo[i], hi[i]] of query_windows_kernel, records
 // (i, n_q + k) in the combined index space of stage 2).  The pair-list form is pairs_count_kernel (kernel_pairs.cuh).
@@ -15,6 +15,12 @@
 // before the rule existed, instruction for instruction; kSmhcContainment -- the threshold of pair (i, k) is
 //     max(c_min, selhip::smhc_threshold(m, gamma, min(e_i, e_k), max(e_i, e_k)))          (pair_value.hpp; c_min = 0 when never set)
 // the count a minimum containment gamma asks for (selhip_ctx_set_min_containment).
+// EMIT (the last template argument of all three, false = the kernels as they were before it existed, instruction for instruction): the
+// pass's estimator is SELHIP_ESTIMATOR_SMH (selhip_ctx_set_estimator).  A pair that passes the count test is
+// COUNTED in n_survivors -- nothing is stored for it -- and, at the point where its count is still at hand, takes
+//     V = selhip::smh_value(measure, m, c, e_i, e_k) >= tau                                (pair_value.hpp)
+// and goes as the 16-byte record {i, k, V} into the RESULT list behind n_results: the pass has no stage 2.  Query records carry the
+// database rank k itself (the index space query_result_fixup_kernel restores for the other criteria).
 #pragma once
 
 namespace {
@@ -22,7 +28,12 @@ namespace {
 constexpr bool smhc_fast(int m) { return m == 128 || m == 256 || m == 512 || m == 1024; }
 // query rows a wave of the fast path keeps in VGPRs: the stream kernel's budget, at most 12 rows (24 rows at m = 128 unrolled into more
 // lane masks in flight than the wave has SGPRs: 25 spilled in the all-pairs form, 6 in the query form -- the matrix kernel's finding)
-constexpr int smhc_q(int nch) { return kQueryVgprBudget / nch < 12 ? kQueryVgprBudget / nch : 12; }
+// (tight = the emit form under the containment rule: its threshold, measure, tally and second counter on top of the rule's one SGPR per
+//  row spilled 12 SGPRs in the all-pairs form and 4 in the query form at m = 128 and 256 with 12 rows: 8 rows there)
+constexpr int smhc_q(int nch, bool tight = false) {
+    const int q = kQueryVgprBudget / nch < 12 ? kQueryVgprBudget / nch : 12;
+    return tight && nch <= 2 && q > 8 ? 8 : q;
+}
 
 // the threshold step of every smh_c kernel
 __device__ __forceinline__ bool smhc_selects(int count, int c_min) { return count >= c_min; }
@@ -31,6 +42,23 @@ constexpr int kSmhcFixed = 0, kSmhcContainment = 1;
 // what the containment rule reads besides the counts: gamma and the truncated cardinalities of the rows (ex) and the candidates (ey);
 // the same array in the all-pairs pass and in a pair list
 struct SmhcRule { double gamma; const u64* __restrict__ ex; const u64* __restrict__ ey; };
+// what the emit form reads besides: the threshold and the measure of V, and the pass's counter block 0 (n_results).  It rides behind
+// the rule in the kernels' last argument, so the form that emits nothing keeps its argument list to the byte
+struct SmhcEmit { double tau; int measure; PassCounters* __restrict__ pc0; };
+struct SmhcRuleEmit : SmhcRule { SmhcEmit em; };
+template <bool EMIT> using SmhcRuleArg = std::conditional_t<EMIT, SmhcRuleEmit, SmhcRule>;
+template <bool EMIT> using SmhcRecord = std::conditional_t<EMIT, selhip_pair_t, selhip_int2_t>;
+// the record of a pair under the estimator, or nothing: *sel = V >= tau (false for NaN)
+__device__ __forceinline__ selhip_pair_t smhc_record(const SmhcEmit& em, int m, int cnt, u64 e1, u64 e2, int i, int k, bool* sel) {
+    selhip_pair_t r;
+    r.i = i; r.k = k; r.jaccard = selhip::smh_value(em.measure, m, cnt, e1, e2);
+    *sel = r.jaccard >= em.tau;
+    return r;
+}
+// the wave's tally of pairs that passed the count test: one atomic without a return value, and none for a wave without such a pair
+__device__ __forceinline__ void smhc_tally(u64* __restrict__ n_survivors, int n_pass, int lane) {
+    if (n_pass != 0 && lane == 0) atomicAdd(n_survivors, (u64)n_pass);
+}
 // the exact threshold of a pair under the containment rule
 __device__ __forceinline__ int smhc_pair_threshold(int m, double gamma, u64 e1, u64 e2, int c_min) {
     return max(c_min, selhip::smhc_threshold(m, gamma, e1 < e2 ? e1 : e2, e1 < e2 ? e2 : e1));
@@ -84,15 +112,15 @@ struct SmhcSpace {
 // ballot on the path every pair takes, where the whole count costs one s_bcnt1 and one s_add per ballot.
 // No LDS tile and no block barrier: a wave that has no candidate leaves on its own.
 // ---------------------------------------------------------------------------------------------
-template <int NCH, bool QUERY, int RULE>
+template <int NCH, bool QUERY, int RULE, bool EMIT = false>
 __global__ __launch_bounds__(kBlock, (NCH <= 4 ? 3 : 2))
 void smh_count_kernel(const u64x2* __restrict__ X, const u64x2* __restrict__ Y, int n_x, int n_y,
                       const int* __restrict__ lo, const int* __restrict__ hi, const PassCounters* __restrict__ pc_in,
                       RowMap rm, int n_tiles, int chunk_base, int c_min,
-                      selhip_int2_t* __restrict__ surv, u64 surv_cap, PassCounters* __restrict__ pc, SmhcRule rule) {
-    constexpr int Q = smhc_q(NCH);
+                      SmhcRecord<EMIT>* __restrict__ surv, u64 surv_cap, PassCounters* __restrict__ pc, SmhcRuleArg<EMIT> rule) {
+    constexpr int Q = smhc_q(NCH, EMIT && RULE == kSmhcContainment);
     constexpr int ROWV = NCH * kWave;                 // u64x2 per sketch row
-    __shared__ selhip_int2_t app_lds[kWavesPerBlock * kAppendCap];
+    __shared__ SmhcRecord<EMIT> app_lds[kWavesPerBlock * kAppendCap];
 
     const int tile = blockIdx.x % n_tiles;
     const int chunk = blockIdx.x / n_tiles;
@@ -146,8 +174,10 @@ void smh_count_kernel(const u64x2* __restrict__ X, const u64x2* __restrict__ Y, 
         for (int c = 0; c < NCH; ++c) q[a][c] = row[c * kWave];
     }
 
-    WaveAppender app;
-    app.init(app_lds, wave, surv, surv_cap, &pc->n_survivors);
+    WaveAppenderT<SmhcRecord<EMIT>> app;
+    if constexpr (EMIT) app.init(app_lds, wave, surv, surv_cap, &rule.em.pc0->n_results);
+    else app.init(app_lds, wave, surv, surv_cap, &pc->n_survivors);
+    int n_pass = 0;                                                           // EMIT: pairs that passed the count test (wave-uniform)
     constexpr int AHEAD = NCH <= 4 ? kStreamAhead : 1;                         // (m = 1024: the registers allow one row ahead)
     constexpr int RING = AHEAD + 1;
     u64x2 ring[RING][NCH];
@@ -170,7 +200,16 @@ void smh_count_kernel(const u64x2* __restrict__ X, const u64x2* __restrict__ Y, 
                     bool ok = true;
                     if constexpr (RULE == kSmhcContainment)
                         ok = smhc_selects(cnt, smhc_pair_threshold(128 * NCH, rule.gamma, rule.ex[i], rule.ey[kk], c_min));
-                    if (ok) app.push_uniform(i, sp.partner(kk), lane);
+                    if constexpr (EMIT) {
+                        if (ok) {
+                            n_pass += 1;
+                            bool sel;
+                            const selhip_pair_t r = smhc_record(rule.em, 128 * NCH, cnt, rule.ex[i], rule.ey[kk], i, kk, &sel);
+                            if (sel) app.push_uniform_record(r, lane);
+                        }
+                    } else {
+                        if (ok) app.push_uniform(i, sp.partner(kk), lane);
+                    }
                 }
             }
         }
@@ -187,16 +226,17 @@ void smh_count_kernel(const u64x2* __restrict__ X, const u64x2* __restrict__ Y, 
         }
     }
     app.flush(lane);
+    if constexpr (EMIT) smhc_tally(&pc->n_survivors, n_pass, lane);
 }
 
 // generic stage 1: block = 256 lanes = 256 candidates of one row; grid = (chunks, rows)
-template <bool QUERY, int RULE>
+template <bool QUERY, int RULE, bool EMIT = false>
 __global__ __launch_bounds__(kBlock)
 void smh_count_generic_kernel(const u64* __restrict__ X, const u64* __restrict__ Y, int n_x, int n_y, int m,
                               const int* __restrict__ lo, const int* __restrict__ hi, const PassCounters* __restrict__ pc_in,
                               RowMap rm, int n_rows_grid, int c_min,
-                              selhip_int2_t* __restrict__ surv, u64 surv_cap, PassCounters* __restrict__ pc, SmhcRule rule) {
-    __shared__ selhip_int2_t app_lds[kWavesPerBlock * kAppendCap];
+                              SmhcRecord<EMIT>* __restrict__ surv, u64 surv_cap, PassCounters* __restrict__ pc, SmhcRuleArg<EMIT> rule) {
+    __shared__ SmhcRecord<EMIT> app_lds[kWavesPerBlock * kAppendCap];
     int i, i_e;
     rm.tile_rows((int)(blockIdx.x % n_rows_grid), 1, &i, &i_e);
     const int chunk = blockIdx.x / n_rows_grid;
@@ -211,11 +251,23 @@ void smh_count_generic_kernel(const u64* __restrict__ X, const u64* __restrict__
     const int k = in_range ? (int)kl : 0;
     int t = c_min;
     if constexpr (RULE == kSmhcContainment) t = smhc_pair_threshold(m, rule.gamma, rule.ex[i], rule.ey[k], c_min);      // (k = 0 out of range: a valid rank)
-    const bool ok = in_range && smhc_selects(smhc_count_lane(X + (long long)i * m, Y + (long long)k * m, m), t);
-    WaveAppender app;
-    app.init(app_lds, wave, surv, surv_cap, &pc->n_survivors);
-    app.push(ok, i, sp.partner(k), lane);
-    app.flush(lane);
+    if constexpr (EMIT) {
+        const int cnt = in_range ? smhc_count_lane(X + (long long)i * m, Y + (long long)k * m, m) : 0;
+        const bool ok = in_range && smhc_selects(cnt, t);
+        WaveRecordAppender app;
+        app.init(app_lds, wave, surv, surv_cap, &rule.em.pc0->n_results);
+        bool sel;
+        const selhip_pair_t r = smhc_record(rule.em, m, cnt, rule.ex[i], rule.ey[k], i, k, &sel);       // (k = 0 out of range: a valid rank)
+        app.push_record(ok && sel, r, lane);
+        app.flush(lane);
+        smhc_tally(&pc->n_survivors, (int)__popcll(__ballot(ok)), lane);
+    } else {
+        const bool ok = in_range && smhc_selects(smhc_count_lane(X + (long long)i * m, Y + (long long)k * m, m), t);
+        WaveAppender app;
+        app.init(app_lds, wave, surv, surv_cap, &pc->n_survivors);
+        app.push(ok, i, sp.partner(k), lane);
+        app.flush(lane);
+    }
 }
 
 }  // namespace

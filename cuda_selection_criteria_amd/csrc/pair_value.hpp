@@ -40,4 +40,20 @@ SELHIP_HD int smhc_threshold(int m, double gamma, unsigned long long e_lo, unsig
     return q <= 0.0 ? 0 : q > (double)m ? m + 1 : (int)ceil(q);
 }
 
+// smh_value is the ONE statement of what a pair's value is under the SuperMinHash estimator (selhip_ctx_set_estimator, DESIGN.md
+// section 18): a function of the count c of equal buckets, m and the pair's truncated cardinalities alone -- no HLL register is read.
+//   SELHIP_MEASURE_JACCARD          c / m
+//   SELHIP_MEASURE_MAX_CONTAINMENT  c (a + b) / ((m + c) a), a = min(e1, e2), b = max(e1, e2): the estimate C^ that smhc_threshold inverts
+// Every operation is rounded on its own, in the order written.  No clamp (C^ may exceed 1); a = 0 is NaN explicitly, as in pair_value,
+// and so is any other measure.  The emit forms of the count kernels and selhip_smh_value (the same function on the host) call it.
+SELHIP_HD double smh_value(int measure, int m, int c, unsigned long long e1, unsigned long long e2) {
+    if (measure == SELHIP_MEASURE_JACCARD) return (double)c / (double)m;
+    const unsigned long long e_lo = e1 < e2 ? e1 : e2, e_hi = e1 < e2 ? e2 : e1;
+    if (measure != SELHIP_MEASURE_MAX_CONTAINMENT || e_lo == 0) return bits2d(0x7FF8000000000000ull);
+    const double a = (double)e_lo, b = (double)e_hi;
+    const double num = (double)c * (a + b);
+    const double den = ((double)m + (double)c) * a;
+    return num / den;
+}
+
 }  // namespace selhip

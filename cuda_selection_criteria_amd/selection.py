@@ -11,7 +11,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import (ALGO_AUTO, BANDING_CPU, CRIT_HLL_A, CRIT_HLL_AN, CRIT_HLL_A_SMH_A, CRIT_NONE, CRIT_SMH_A, CRIT_SMH_C, F32, F64, FP_FMA,
+from ._lib import (ALGO_AUTO, BANDING_CPU, CRIT_HLL_A, CRIT_HLL_AN, CRIT_HLL_A_SMH_A, CRIT_NONE, CRIT_SMH_A, CRIT_SMH_C, ESTIMATOR_HLL, ESTIMATOR_SMH, F32, F64, FP_FMA,
                    MEASURE_CONTAINMENT, MEASURE_INTERSECTION, MEASURE_JACCARD, MEASURE_MAX_CONTAINMENT, MEASURE_SMH_JACCARD,
                    MEASURE_SMH_MATCHES, MEASURE_UNION, MODE_CB_SMH, Pair, check, hip_lib, host_lib)
 
@@ -334,6 +334,17 @@ class Selector:
         check(self._lib.selhip_ctx_set_measure(self._ctx, code), self._ctx)
         self.measure = code
 
+    def set_estimator(self, estimator):
+        """which estimate the following passes test against tau and record in the `jaccard` field: "hll" (the default: the HLL
+        estimate of stage 2, nothing changes) or "smh" -- the SuperMinHash estimate smh_value(measure, m, c, e_i, e_k) of the count c
+        that a CRIT_SMH_C pass computes anyway: c / m under "jaccard", c (a + b) / ((m + c) a) under "max_containment" -- or the
+        ESTIMATOR_* code of either.  Sticky, like the measure.  Under "smh" the records leave the count kernel itself (no stage 2, no
+        HLL register read), a pair needs c >= its count threshold AND value >= tau, and a pass of any criterion but CRIT_SMH_C is
+        refused"""
+        code = estimator_code(estimator)
+        check(self._lib.selhip_ctx_set_estimator(self._ctx, code), self._ctx)
+        self.estimator = code
+
     def cards(self) -> np.ndarray:
         out = np.empty(self.n, dtype=np.float64)
         check(self._lib.selhip_ctx_get_cards(self._ctx, out.ctypes.data), self._ctx)
@@ -550,6 +561,42 @@ def containment_matches(m, gamma, e_lo, e_hi):
     return int(out) if out.ndim == 0 else out
 
 
+ESTIMATORS = {"hll": ESTIMATOR_HLL, "smh": ESTIMATOR_SMH}
+
+
+def estimator_code(estimator) -> int:
+    """the SELHIP_ESTIMATOR_* code of an estimator given by name or by code; ValueError for anything else"""
+    code = ESTIMATORS.get(estimator) if isinstance(estimator, str) else estimator
+    if isinstance(code, bool) or not isinstance(code, (int, np.integer)) or code not in ESTIMATORS.values():
+        raise ValueError("estimator: 'hll' or 'smh'")
+    return int(code)
+
+
+def _pass_estimator(estimator, criterion: str) -> int:
+    """the code of a pass's estimator for the file-list helpers; ValueError for what the SuperMinHash estimator refuses"""
+    code = estimator_code(estimator)
+    if code == ESTIMATOR_SMH and criterion != "smh_c":
+        raise ValueError(f"estimator 'smh' records a value computed from the count of criterion smh_c and takes no criterion {criterion}")
+    return code
+
+
+def smh_value(measure, m, c, e1, e2):
+    """the value a pass records under Selector.set_estimator("smh") for a pair with c of m equal SuperMinHash buckets and truncated
+    cardinalities e1, e2, computed by the library's own function (selhip_smh_value; no device is touched): c / m under "jaccard",
+    c (a + b) / ((m + c) a) with a = min(e1, e2), b = max(e1, e2) under "max_containment" (NaN when a = 0; not clamped).  Scalars give a
+    float, arrays broadcast against each other and give a float64 array"""
+    code = measure_code(measure)
+    if code not in (MEASURE_JACCARD, MEASURE_MAX_CONTAINMENT):
+        raise ValueError("measure of a pass: 'jaccard' or 'max_containment' (the other measures are matrix measures)")
+    fn = hip_lib().selhip_smh_value
+    args = np.broadcast_arrays(np.asarray(m, dtype=np.int64), np.asarray(c, dtype=np.int64), np.asarray(e1, dtype=np.uint64), np.asarray(e2, dtype=np.uint64))
+    out = np.empty(args[0].shape, dtype=np.float64)
+    flat = out.reshape(-1)
+    for j, (mm, cc, a, b) in enumerate(zip(*(x.reshape(-1).tolist() for x in args))):
+        flat[j] = fn(code, mm, cc, a, b)
+    return float(out) if out.ndim == 0 else out
+
+
 def _criterion_files(criterion: str, aux_bytes: int, min_matches: Optional[int] = None, min_containment: Optional[float] = None) -> Tuple[int, int, int]:
     """(m, p_aux, CRIT_*) of a criterion name and `-a aux_bytes`, for the file-list front ends: m buckets of the .smh<m> files to read
     (0 = none), precision of the auxiliary .hll_<p> files (0 = none).  min_matches and min_containment go with "smh_c" and with nothing
@@ -575,7 +622,7 @@ def _criterion_files(criterion: str, aux_bytes: int, min_matches: Optional[int] 
 
 def select_from_filelist(list_file: str, tau: float, aux_bytes: int, mode: int = MODE_CB_SMH, device: int = 0,
                          fp_mode: int = FP_FMA, algo: int = ALGO_AUTO, criterion: str = "smh_a", top_k: int = 0,
-                         min_matches: Optional[int] = None, measure="jaccard", min_containment: Optional[float] = None) -> str:
+                         min_matches: Optional[int] = None, measure="jaccard", min_containment: Optional[float] = None, estimator="hll") -> str:
     """The whole of selection_cuda.cpp main() (criterion smh_a) -- and of selection.cpp's hll_a / hll_an
     branches (:122-227): returns the text the CPU reference prints for `-c criterion -a aux_bytes -h tau`.
     criterion "none": no criterion in front of the Jaccard test (CRIT_NONE; mode MODE_CB_SMH = the CB bound alone, MODE_SMH = every pair).
@@ -585,8 +632,11 @@ def select_from_filelist(list_file: str, tau: float, aux_bytes: int, mode: int =
     top_k > 0: only every genome's top_k best partners, one line 'owner_path partner_path J' each, in ranked order (owner rank, then J
     descending, ties by partner rank): a selected pair can be printed twice (once per member), once or not at all.
     measure "max_containment": the pairs with I / min(e_i, e_k) >= tau, that value printed in J's place (Selector.set_measure;
-    ValueError with mode=MODE_CB_SMH or an hll_* criterion)."""
+    ValueError with mode=MODE_CB_SMH or an hll_* criterion).
+    estimator "smh" (`-V smh`, criterion "smh_c" alone): the value tested and printed is the SuperMinHash estimate of the count,
+    smh_value(measure, m, c, e_i, e_k) (Selector.set_estimator), and no HLL stage runs."""
     meas = _pass_measure(measure, mode, criterion)
+    est = _pass_estimator(estimator, criterion)
     m, p_aux, crit = _criterion_files(criterion, aux_bytes, min_matches, min_containment)
     ds = load_dataset(list_file, m, p_aux, fp_mode)
     n_rows, n_bands = banding(m, tau) if m else (1, 1)
@@ -601,6 +651,7 @@ def select_from_filelist(list_file: str, tau: float, aux_bytes: int, mode: int =
                 sel.set_min_matches(min_matches)
             sel.set_min_containment(min_containment)
         sel.set_measure(meas)
+        sel.set_estimator(est)
         pairs = sel.run(tau, mode, n_rows, n_bands, algo=algo, top_k=top_k if top_k else None)
     return format_lines(ds.names, pairs)
 
@@ -698,10 +749,11 @@ def read_pair_list(pair_file: str, names: Sequence[str]) -> np.ndarray:
 
 def select_pairs_from_filelist(list_file: str, pair_file: str, tau: float, aux_bytes: int, mode: int = MODE_CB_SMH, device: int = 0,
                                fp_mode: int = FP_FMA, algo: int = ALGO_AUTO, criterion: str = "smh_a",
-                               min_matches: Optional[int] = None, measure="jaccard", min_containment: Optional[float] = None) -> str:
+                               min_matches: Optional[int] = None, measure="jaccard", min_containment: Optional[float] = None, estimator="hll") -> str:
     """select_from_filelist restricted to the pairs listed in pair_file (lines 'path1 path2[ anything]' with paths of list_file, in
     either order): the text `selection -l list_file -p pair_file -c criterion -a aux_bytes -h tau` prints (measure as there: `-S`)"""
     meas = _pass_measure(measure, mode, criterion)
+    est = _pass_estimator(estimator, criterion)
     m, p_aux, crit = _criterion_files(criterion, aux_bytes, min_matches, min_containment)
     ds = load_dataset(list_file, m, p_aux, fp_mode)
     listed = read_pair_list(pair_file, ds.names)
@@ -716,6 +768,7 @@ def select_pairs_from_filelist(list_file: str, pair_file: str, tau: float, aux_b
                 sel.set_min_matches(min_matches)
             sel.set_min_containment(min_containment)
         sel.set_measure(meas)
+        sel.set_estimator(est)
         pairs = sel.run_pairs(listed, tau, mode, n_rows, n_bands, algo=algo)
     return format_lines(ds.names, pairs)
 
@@ -781,7 +834,7 @@ def ooc_select(hll: np.ndarray, aux: np.ndarray, cards: np.ndarray, tau: float, 
 
 def query_from_filelists(query_list: str, db_list: str, tau: float, aux_bytes: int, mode: int = MODE_CB_SMH, fp_mode: int = FP_FMA,
                          device: int = 0, algo: int = ALGO_AUTO, criterion: str = "smh_a", top_k: int = 0,
-                         min_matches: Optional[int] = None, measure="jaccard", min_containment: Optional[float] = None) -> str:
+                         min_matches: Optional[int] = None, measure="jaccard", min_containment: Optional[float] = None, estimator="hll") -> str:
     """Query-vs-database selection: both lists are loaded and sorted by cardinality (load_dataset); returns one line
     'query_path db_path J' per selected pair, in (query rank, database rank) order, J formatted as selection.cpp prints it.
     top_k > 0: only every query's top_k best pairs, in ranked order (query rank, then J descending, ties by database rank).
@@ -790,6 +843,7 @@ def query_from_filelists(query_list: str, db_list: str, tau: float, aux_bytes: i
     c of the m = aux_bytes / 8 buckets equal).  measure "max_containment": the value tested and printed is I / min(e_q, e_d)
     (Selector.set_measure; ValueError with mode=MODE_CB_SMH or an hll_* criterion)."""
     meas = _pass_measure(measure, mode, criterion)
+    est = _pass_estimator(estimator, criterion)
     m, p_aux, crit = _criterion_files(criterion, aux_bytes, min_matches, min_containment)
     qs = load_dataset(query_list, m, p_aux, fp_mode)
     db = load_dataset(db_list, m, p_aux, fp_mode)
@@ -807,6 +861,7 @@ def query_from_filelists(query_list: str, db_list: str, tau: float, aux_bytes: i
                 sel.set_min_matches(min_matches)
             sel.set_min_containment(min_containment)
         sel.set_measure(meas)
+        sel.set_estimator(est)
         pairs = sel.run_queries(tau, mode, n_rows, n_bands, algo, top_k=top_k if top_k else None)
     h = host_lib()
     buf = C.create_string_buffer(16384)

@@ -301,6 +301,40 @@ int selhip_smhc_threshold(int m, double gamma, uint64_t e_lo, uint64_t e_hi);
  * test only: under max containment the regular pass runs (get_param "small_pass_used" reads 0).  The drop-in launchers,
  * selhip_multi_select and selhip_ooc_select carry no measure: J.  A context that never calls this launches what it always did. */
 int selhip_ctx_set_measure(selhip_ctx* ctx, int measure);
+/* The ESTIMATOR behind the value that the following passes test against tau_f and record (sticky like the
+ * measure; survives uploads):
+ *   SELHIP_ESTIMATOR_HLL (default)   the HLL estimate of stage 2, as described above: nothing changes, the same launches as before
+ *   SELHIP_ESTIMATOR_SMH             the SuperMinHash estimate, a function of the count c(i,k) of equal buckets that a pass of
+ *                                    SELHIP_CRIT_SMH_C already computes for every pair it admits, of m and of the pair's truncated
+ *                                    cardinalities e_i, e_k alone (csrc/pair_value.hpp, every operation one IEEE-754 double operation,
+ *                                    no contraction):
+ *   smh_value(measure, m, c, e1, e2) -> double
+ *       SELHIP_MEASURE_JACCARD          V = (double)c / (double)m
+ *       SELHIP_MEASURE_MAX_CONTAINMENT  a = (double)min(e1, e2), b = (double)max(e1, e2)
+ *                                       V = ((double)c * (a + b)) / (((double)m + (double)c) * a)     -- the estimate C^ behind
+ *                                       selhip_smhc_threshold; min(e1, e2) == 0 gives NaN explicitly (never selected); no clamp: V may
+ *                                       exceed 1, as every containment value of this library may
+ *       any other measure               NaN
+ * Under SELHIP_ESTIMATOR_SMH a pass selects a pair iff (1) it lies in the pass's pair space E -- unchanged: rank order, e_k != 0, the
+ * CB window under SELHIP_MODE_CB_SMH, the own E of query and pair-list passes --, (2) c >= the pass's count threshold -- unchanged:
+ * the fixed c_min, or the per-pair rule of selhip_ctx_set_min_containment with c_min as its floor -- and (3) V >= (double)tau_f.  Its
+ * record is {i, k, V} in the index space of the pass kind.  The count floor of such a pass is 1 whatever the rule gives (c_min >= 1;
+ * a gamma <= 0 without c_min asks for 0): a pair with c < 1 never has a record.  Stage 1 emits the records itself: the pass is its
+ * bounds / windows kernel, the count kernel and the counter copy -- nothing is grouped, no union histogram and no estimate is launched,
+ * no HLL register or bit plane is read.  stats[0] = the evaluated pairs, stats[1] = stats[3] = the pairs with c >= their threshold,
+ * stats[2] = the records.  Row ranges, row interleave, candidate begin, pipeline lanes, the growth of a result list that overflowed,
+ * both top-k cuts (which rank by V; c / m is discrete, so ties -- broken by ascending partner rank as ever -- are common), fetch,
+ * fetch_ranked, copy_results* and get_param "smhc_path_used" / "smhc_rule_used" work as for the criterion under the HLL estimator.
+ * Refused with SELHIP_E_BADARG and a message naming the estimator, by every run entry before anything is enqueued: SELHIP_ESTIMATOR_SMH
+ * with a criterion other than SELHIP_CRIT_SMH_C; besides, everything the criterion and the measure refuse on their own (max containment
+ * still takes no SELHIP_MODE_CB_SMH).  Any other estimator code: SELHIP_E_BADARG with a message, the setting is left alone.
+ * SELHIP_E_STATE while a pass is pending.  selhip_multi_select and selhip_ooc_select refuse smh_c and so carry no estimator; a context
+ * still uploads its HLL rows. */
+#define SELHIP_ESTIMATOR_HLL 0
+#define SELHIP_ESTIMATOR_SMH 1
+int selhip_ctx_set_estimator(selhip_ctx* ctx, int estimator);
+/* smh_value above on the host (no device is touched): what the kernels compute for one pair */
+double selhip_smh_value(int measure, int m, int c, uint64_t e1, uint64_t e2);
 
 /* report() of every genome (Ertl-MLE, hll.h:834-837,862) computed on the device: d_cards_out[n]. */
 int selhip_hll_cards(selhip_ctx* ctx, const uint8_t* d_hll, int64_t n_genomes, int p, double* d_cards_out);
