@@ -51,6 +51,7 @@ MEASURE_INTERSECTION, MEASURE_CONTAINMENT, MEASURE_MAX_CONTAINMENT = 32, 33, 34
 ESTIMATOR_HLL, ESTIMATOR_SMH = 0, 1    # SELHIP_ESTIMATOR_*: which estimate the records of an smh_c pass carry (Selector.set_estimator)
 F64, F32 = 0, 1                        # SELHIP_F64 / SELHIP_F32: its element type
 BANDING_CPU, BANDING_CUDA = 0, 1
+TOPK_ROUNDS_AUTO = -1                  # SELHIP_TOPK_ROUNDS_AUTO: Selector.set_topk_rounds picks the rows per round
 TOPK_MAX = 1024                        # SELHIP_TOPK_MAX: largest k of Selector.set_query_topk and Selector.set_allpairs_topk
 
 _vp, _i, _i64, _d, _sz, _cp = C.c_void_p, C.c_int, C.c_int64, C.c_double, C.c_size_t, C.c_char_p
@@ -111,6 +112,7 @@ HIP_SYMBOLS = {
     "selhip_ctx_set_query_topk": (_i, [_vp, _i]),
     "selhip_ctx_fetch_ranked": (_i, [_vp, _vp, _i64]),
     "selhip_ctx_set_allpairs_topk": (_i, [_vp, _i]),
+    "selhip_ctx_set_topk_rounds": (_i, [_vp, _i64]),
     "selhip_ctx_upload_queries_aux_hll": (_i, [_vp, _vp, _i]),
     "selhip_ctx_attach_queries_aux_hll": (_i, [_vp, _vp, _i]),
     "selhip_ctx_matrix": (_i, [_vp, _i, _i, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp]),

@@ -245,6 +245,10 @@ int selhip_ctx_get_param(const selhip_ctx* c, const char* name, int* value) {
     if (!std::strcmp(name, "pairs_route_used")) { *value = c->pairs_route_used; return SELHIP_OK; }         // list passes: 1 signature, 0 direct, 2 no smh_a stage, -1 none yet
     if (!std::strcmp(name, "query_topk"))       { *value = c->query_topk; return SELHIP_OK; }              // K of the query passes' top-k, 0 = off
     if (!std::strcmp(name, "allpairs_topk"))    { *value = c->allpairs_topk; return SELHIP_OK; }           // K of the all-pairs passes' top-k, 0 = off
+    if (!std::strcmp(name, "topk_rounds"))      { *value = (int)std::min<int64_t>(c->topk_rounds, 0x7FFFFFFF); return SELHIP_OK; }   // selhip_ctx_set_topk_rounds: rows per round, 0 = off, -1 = automatic
+    if (!std::strcmp(name, "topk_rounds_used")) { *value = c->rounds_used; return SELHIP_OK; }             // rounds of the last all-pairs pass (0: it ran in one)
+    if (!std::strcmp(name, "topk_admitted_lo")) { *value = (int)(c->rounds_admitted & 0x7FFFFFFFull); return SELHIP_OK; }            // records its rounds admitted: low ...
+    if (!std::strcmp(name, "topk_admitted_hi")) { *value = (int)((c->rounds_admitted >> 31) & 0x7FFFFFFFull); return SELHIP_OK; }    // ... and high 31 bits
     if (!std::strcmp(name, "query_topk_lds_cap")) { *value = kTopkLdsCap; return SELHIP_OK; }              // longest segment its select kernel stages in LDS
     if (!std::strcmp(name, "query_db_sig_builds")) { *value = c->q.db_sig_builds; return SELHIP_OK; }   // database signature builds of the query passes
     if (!std::strcmp(name, "query_db_index_builds")) { *value = c->q.db_idx_builds; return SELHIP_OK; } // builds of ALGO_INDEX's sorted signature index
@@ -455,6 +459,7 @@ int selhip_ctx_run_async(selhip_ctx* c, int mode, int algo, float tau_f, int n_r
     if (!c) return SELHIP_E_BADARG;
     { const int rc = accept_measure(c, mode); if (rc) return rc; }
     { const int rc = accept_estimator(c); if (rc) return rc; }
+    { const int rc = accept_rounds(c); if (rc) return rc; }
     if (c->criterion == SELHIP_CRIT_SMH_C) { const int rc = accept_count(c); if (rc) return rc; }
     if (!c->d_aux && c->n) { set_err(&c->err, "run before upload/attach"); return SELHIP_E_STATE; }
     if (mode != SELHIP_MODE_SMH && mode != SELHIP_MODE_CB_SMH) { set_err(&c->err, "bad mode %d", mode); return SELHIP_E_BADARG; }
@@ -475,8 +480,20 @@ int selhip_ctx_run_async(selhip_ctx* c, int mode, int algo, float tau_f, int n_r
     c->mode = mode; c->algo = algo; c->tau_f = tau_f; c->n_rows = n_rows; c->n_bands = n_bands; c->plan = plan;
     c->row_begin = row_begin; c->row_end = row_end;
     c->have_run = false; c->last_was_query = false; c->topk_applied = false; c->topk_n = 0; c->list_pass = false;
+    c->rd = selhip_ctx::Rounds{}; c->rounds_used = 0; c->rounds_admitted = 0;
     std::memset(&c->last, 0, sizeof c->last);
     if (c->n == 0 || row_begin == row_end) { c->pending = false; c->have_run = true; c->topk_applied = c->allpairs_topk > 0; return SELHIP_OK; }
+    if (c->topk_rounds != 0) {
+        // row rounds: the first round is enqueued here, selhip_ctx_finish merges it and drives the rest.  Every genome's admission
+        // threshold starts at -inf
+        c->rd.on = true;
+        c->rd.rows = topk_round_rows(c->topk_rounds, c->n, interleave_period(c));
+        c->rd.begin = row_begin; c->rd.end = std::min<int64_t>(row_end, row_begin + c->rd.rows);
+        HIPCHK(&c->err, c->topk_thr.ensure((size_t)c->n));
+        hipLaunchKernelGGL(topk_threshold_kernel, dim3((unsigned)((c->n + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, (const selhip_pair_t*)nullptr, (u64)0,
+                           (const u64*)nullptr, (int)c->n, c->allpairs_topk, c->topk_thr.p);
+        HIPCHK(&c->err, hipGetLastError());
+    }
     size_t surv_cap = std::max<size_t>(c->surv.cap, std::max<size_t>((size_t)1 << 20, (size_t)c->n * 16));
     if (join16_pass(c)) {
         // the 16-bit join passes ~n_bands * 2^-16 of the pairs it compares on to the 32-bit filter: size the lists for that
@@ -535,6 +552,36 @@ int selhip_ctx_finish(selhip_ctx* c) {
         if (results_overflowed(pc.n_results, c->results.cap, &res_cap)) grow = true;
         if (!grow) {
             if (c->criterion == SELHIP_CRIT_NONE) dense_stats(&pc);
+            if (c->rd.on) {
+                // a round of a pass in row rounds is accepted: its counters join the pass's, its records are merged into the carried
+                // list C (which the repeats of a round that overflowed never touched) and raise the thresholds; then the next round
+                // is enqueued and this loop starts over for it
+                selhip_ctx::Rounds& rd = c->rd;
+                rd.acc.n_evaluated += pc.n_evaluated; rd.acc.n_survivors += pc.n_survivors; rd.acc.n_candidates += pc.n_candidates;
+                rd.acc.n_results += pc.n_final;                                  // |S|: the pairs with V >= tau, admitted or not
+                rd.attempts = std::max(rd.attempts, attempt + 1);
+                c->rounds_used += 1; c->rounds_admitted += pc.n_results;
+                c->last = pc;
+                int rc = reduce_topk(c, {c->allpairs_topk, c->n, true, "genome", "genomes", true, rd.n_carry});
+                if (rc) { c->pending = false; rd.on = false; return rc; }
+                rd.n_carry = (u64)c->topk_n;
+                if (rd.end < c->row_end) {
+                    rd.begin = rd.end; rd.end = std::min<int64_t>(c->row_end, rd.begin + rd.rows);
+                    rc = ensure_scratch(c, c->surv.cap, c->results.cap);
+                    if (!rc) rc = enqueue_pass(c);
+                    if (rc) { c->pending = false; rd.on = false; return rc; }
+                    attempt = -1;
+                    continue;
+                }
+                // behind the last round C is nbr(S, K) of the whole pass: it becomes the result list
+                // (copied where it fits -- n K records at most -- so that the result list keeps the capacity the rounds grew it to)
+                if (rd.n_carry && rd.n_carry <= c->results.cap)
+                    HIPCHK(&c->err, hipMemcpyAsync(c->results.p, c->topk_carry.p, (size_t)rd.n_carry * sizeof(selhip_pair_t), hipMemcpyDeviceToDevice, c->stream));
+                else if (rd.n_carry) std::swap(c->results, c->topk_carry);
+                c->last = rd.acc; c->pending = false; c->have_run = true; c->last_attempts = rd.attempts;
+                c->topk_n = (int64_t)rd.n_carry; c->topk_applied = true; rd.on = false;
+                return SELHIP_OK;
+            }
             c->last = pc; c->pending = false; c->have_run = true; c->last_attempts = attempt + 1;
             // (event pairs are read lazily -- selhip_ctx_kernel_ms / _timing / destroy -- so that a timed run does not stall the
             // host between passes; a pass records at most ~20 of them)
@@ -549,11 +596,11 @@ int selhip_ctx_finish(selhip_ctx* c) {
         // an output list was too small: counts are exact, so grow once and repeat the pass
         res_cap = std::max(res_cap, surv_cap);
         int rc = ensure_scratch(c, surv_cap, res_cap);
-        if (rc) { c->pending = false; return rc; }
+        if (rc) { c->pending = false; c->rd.on = false; return rc; }
         rc = c->list_pass ? enqueue_pairs_pass(c) : enqueue_pass(c);
-        if (rc) { c->pending = false; return rc; }
+        if (rc) { c->pending = false; c->rd.on = false; return rc; }
     }
-    c->pending = false;
+    c->pending = false; c->rd.on = false;
     set_err(&c->err, "output buffers kept overflowing");
     return SELHIP_E_OVERFLOW;
 }
@@ -563,6 +610,17 @@ int selhip_ctx_set_allpairs_topk(selhip_ctx* c, int k) {
     if (k < 0 || k > SELHIP_TOPK_MAX) { set_err(&c->err, "all-pairs top-k must be 0 (off) or in [1, %d] (got %d)", SELHIP_TOPK_MAX, k); return SELHIP_E_BADARG; }
     if (c->pending) { set_err(&c->err, "a pass is still pending (selhip_ctx_finish)"); return SELHIP_E_STATE; }
     c->allpairs_topk = k;
+    return SELHIP_OK;
+}
+
+int selhip_ctx_set_topk_rounds(selhip_ctx* c, int64_t rows) {
+    if (!c) return SELHIP_E_BADARG;
+    if (rows < 0 && rows != SELHIP_TOPK_ROUNDS_AUTO) {
+        set_err(&c->err, "top-k rounds: 0 (off), rows per round > 0 or SELHIP_TOPK_ROUNDS_AUTO (%d) (got %lld)", SELHIP_TOPK_ROUNDS_AUTO, (long long)rows);
+        return SELHIP_E_BADARG;
+    }
+    if (c->pending) { set_err(&c->err, "a pass is still pending (selhip_ctx_finish)"); return SELHIP_E_STATE; }
+    c->topk_rounds = rows;
     return SELHIP_OK;
 }
 

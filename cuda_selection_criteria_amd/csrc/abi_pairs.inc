@@ -56,6 +56,7 @@ int selhip_ctx_run_pairs_async(selhip_ctx* c, const selhip_int2_t* d_pairs, int6
     c->mode = mode; c->algo = route == 1 ? SELHIP_ALGO_SIG : SELHIP_ALGO_STREAM; c->tau_f = tau_f; c->n_rows = n_rows; c->n_bands = n_bands; c->plan = plan;
     c->row_begin = 0; c->row_end = c->n;
     c->have_run = false; c->last_was_query = false; c->topk_applied = false; c->topk_n = 0;
+    c->rd.on = false;                                              // (a pair-list pass does not read selhip_ctx_set_topk_rounds)
     c->list_pass = true; c->list_pairs = d_pairs; c->list_n = n_pairs; c->pairs_route_used = route;
     c->small_used = false; c->n_chunks_last = 1;
     std::memset(&c->last, 0, sizeof c->last);

@@ -41,6 +41,10 @@
 //               by partner rank.  A selected pair counts for both of its genomes, so it can be printed twice, once or not at all.  The
 //               best among the pairs that pass -c and -h (every genome's exact nearest neighbours: -c none -n -h -1); one device, text
 //               output -- not combinable with -q (per-query cut: -k), -g, -B, -o or -r
+//   -R <rows>   with -K -c smh_c -V smh: the pass runs in rounds of that many rows (or `auto`: the largest R with R n <= 2^27), each merged
+//               into a carried list of at most n best partners per genome whose n-th values prune the next round at the source
+//               (selhip_ctx_set_topk_rounds): the same text, with memory for n K records and one round instead of every pair that
+//               shares a bucket, and no limit of 2^30 such pairs.  Not combinable with -q, -p, -M, -g or -B; needs -K
 //   -p <file>   pair-list selection: only the pairs listed in the file, lines "path1 path2[ anything]" with paths of the -l list in
 //               either order -- the lines this program prints, so one run's output is the next run's pair file
 //               (selhip_ctx_run_pairs: a pair listed twice is printed twice).  With every -c, -n, -F, -o and -A auto|sig|stream; one
@@ -86,6 +90,7 @@
 // and its estimator (-V)
 static double g_min_containment = std::nan("");
 static int g_estimator = SELHIP_ESTIMATOR_HLL;
+static long long g_topk_rounds = 0;              // -R: rows per round of -K (0: not given, SELHIP_TOPK_ROUNDS_AUTO: auto)
 static int set_count_thresholds(selhip_ctx* ctx, int min_matches) {
     int r = min_matches > 0 ? selhip_ctx_set_min_matches(ctx, min_matches) : 0;
     if (!r && !std::isnan(g_min_containment)) r = selhip_ctx_set_min_containment(ctx, g_min_containment);
@@ -189,6 +194,7 @@ static int run_neighbours(const std::string& list_file, int crit, float threshol
     if (!r && crit == SELHIP_CRIT_SMH_C) r = set_count_thresholds(ctx, min_matches);
     if (!r) r = selhip_ctx_set_measure(ctx, measure);
     if (!r) r = selhip_ctx_set_allpairs_topk(ctx, top_k);
+    if (!r && g_topk_rounds) r = selhip_ctx_set_topk_rounds(ctx, g_topk_rounds);
     if (!r) r = selhip_ctx_run(ctx, mode, algo, threshold, n_rows, n_bands, 0, n);
     if (!r) {
         pairs.resize((size_t)selhip_ctx_result_count(ctx));
@@ -270,9 +276,10 @@ int main(int argc, char* argv[]) {
     bool gpus_given = false, topk_given = false, nbr_given = false, matrix_given = false, union_measure = false, aux_given = false, estimator_given = false;
     const char* selection_opt = nullptr;         // the first of -h, -c, -n, -A seen: options of a selection pass, which -M does not run
     long long top_k = 0, nbr_k = 0, min_matches = 0;
-    bool cmin_given = false, gamma_given = false, value_given = false;
+    bool cmin_given = false, gamma_given = false, value_given = false, rounds_given = false;
+    std::string rounds_arg = "";
     int c;
-    while ((c = getopt(argc, argv, "xl:b:a:h:c:C:G:t:g:nA:F:B:o:r:q:k:K:p:M:UE:S:V:")) != -1) {
+    while ((c = getopt(argc, argv, "xl:b:a:h:c:C:G:t:g:nA:F:B:o:r:q:k:K:p:M:UE:S:V:R:")) != -1) {
         switch (c) {
             case 'x': std::cout << "Usage: -l -h -a -b [-c smh_a|hll_a|hll_an|none|smh_c -C c_min|-G gamma] [-t threads] [-g gpus] [-n] [-A auto|stream|sig] [-F 0|1] [-B block] [-o file] | -r file\n"
                                    "       -l db_list -q query_list -h -a [-c smh_a|hll_a|hll_an|none|smh_c -C c_min|-G gamma] [-n] [-A auto|stream|sig|index] [-F 0|1] [-k best_per_query]   (query-vs-database selection)\n"
@@ -283,7 +290,8 @@ int main(int argc, char* argv[]) {
                                    "       ... -n -S max_containment -h gamma -c smh_c -G gamma -a bytes [-C c_min]   (its prefilter: the count at which the SuperMinHash estimate of the containment is gamma)\n"
                                    "       ... -n -S max_containment [-c smh_a|none|smh_c]   (with -l, -q, -p, -k, -K: select and print I / min(e1, e2), the share of the smaller genome found in the larger)\n"
                                    "       -l list [-q query_list] -M out.tsv -S intersection|containment|max_containment   (the table of I = e1 + e2 - U, I / e_row or I / min(e_row, e_col))\n"
-                                   "       ... -c smh_c -C c_min|-G gamma -a bytes -V smh|hll   (with -l, -q, -p, -k, -K, -n, -S max_containment, -o: -V smh tests and prints the SuperMinHash estimate of the count, c / m, with no HLL stage)\n"; return 0;
+                                   "       ... -c smh_c -C c_min|-G gamma -a bytes -V smh|hll   (with -l, -q, -p, -k, -K, -n, -S max_containment, -o: -V smh tests and prints the SuperMinHash estimate of the count, c / m, with no HLL stage)\n"
+                                   "       -l list -K best_per_genome -c smh_c -C c_min|-G gamma -a bytes -V smh -R rows|auto   (the same list in rounds of rows: memory for n K records and one round, not for every pair that shares a bucket)\n"; return 0;
             case 'q': query_file = optarg; break;
             case 'p': pair_file = optarg; break;
             case 'M': matrix_file = optarg; matrix_given = true; break;
@@ -291,6 +299,7 @@ int main(int argc, char* argv[]) {
             case 'E': estimator = optarg; estimator_given = true; break;
             case 'S': measure_name = optarg; measure_given = true; break;
             case 'V': value_estimator = optarg; value_given = true; break;
+            case 'R': rounds_arg = optarg; rounds_given = true; break;
             case 'k': top_k = std::strtoll(optarg, nullptr, 10); topk_given = true; break;
             case 'K': nbr_k = std::strtoll(optarg, nullptr, 10); nbr_given = true; break;
             case 'B': ooc_block = std::stoll(optarg); break;
@@ -329,6 +338,25 @@ int main(int argc, char* argv[]) {
                 return 2;
             }
             g_estimator = SELHIP_ESTIMATOR_SMH;
+        }
+    }
+    // -R: checked before any file is read or device opened
+    if (rounds_given) {
+        const char* clash = !query_file.empty() ? "-q" : !pair_file.empty() ? "-p" : matrix_given ? "-M" : gpus_given ? "-g" : ooc_block != 0 ? "-B" : nullptr;
+        if (clash) {
+            std::cerr << "selection: -R (the rows per round of -K) cannot be combined with " << clash << "; it cuts one all-pairs pass on one device into rounds\n";
+            return 2;
+        }
+        if (!nbr_given) { std::cerr << "selection: -R (the rows per round) is an option of -K (the best partners of every genome)\n"; return 2; }
+        if (criterion != "smh_c" || g_estimator != SELHIP_ESTIMATOR_SMH) {
+            std::cerr << "selection: -R needs -c smh_c -V smh: the rounds prune with the value the count kernel computes\n";
+            return 2;
+        }
+        char* end = nullptr;
+        g_topk_rounds = rounds_arg == "auto" ? SELHIP_TOPK_ROUNDS_AUTO : std::strtoll(rounds_arg.c_str(), &end, 10);
+        if (rounds_arg != "auto" && (rounds_arg.empty() || *end || g_topk_rounds < 1)) {
+            std::cerr << "selection: -R must be a number of rows >= 1 or auto, not '" << rounds_arg << "'\n";
+            return 2;
         }
     }
     // -S: checked before any file is read or device opened

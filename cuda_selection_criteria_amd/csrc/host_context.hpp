@@ -307,6 +307,20 @@ struct selhip_ctx {
     DevBuf<u64> topk_key;               // the records grouped by query: key(J) ...
     DevBuf<uint32_t> topk_val;          // ... and database rank
     DevBuf<char> topk_tmp;              // rocPRIM scan scratch
+    // all-pairs top-k in row rounds (selhip_ctx_set_topk_rounds): the pass runs as sub-range passes of `rows` rows,
+    // each merged into the carried list C, whose K-th values are the next round's admission thresholds
+    int64_t topk_rounds = 0;            // the setting: 0 = off, > 0 rows per round, SELHIP_TOPK_ROUNDS_AUTO = topk_round_rows' choice
+    int rounds_used = 0;                // rounds of the last such pass ("topk_rounds_used") ...
+    u64 rounds_admitted = 0;            // ... and the records its count kernels appended over all of them ("topk_admitted_lo" / "_hi")
+    struct Rounds {                     // the pending pass
+        bool on = false;                // run_async took the round route: [begin, end) below is the round enqueued, not the pass's rows
+        int64_t rows = 0, begin = 0, end = 0;
+        u64 n_carry = 0;                // |C|
+        PassCounters acc{};             // the counters of the accepted rounds, added up
+        int attempts = 0;               // the most enqueues any round needed
+    } rd;
+    DevBuf<selhip_pair_t> topk_carry;   // C: directed records {owner, partner, V} in ranked order; swapped with the result list behind the last round
+    DevBuf<double> topk_thr;            // thr[n]
 
     // pair-list passes (selhip_ctx_run_pairs; abi_pairs.inc, host_pairs.hpp): the pending / last pass evaluates a caller's list
     bool list_pass = false;

@@ -96,6 +96,16 @@ int accept_estimator(selhip_ctx* c) {
                      "takes no other criterion (criterion %d); selhip_ctx_set_estimator(ctx, SELHIP_ESTIMATOR_HLL) first", c->criterion);
     return SELHIP_E_BADARG;
 }
+// what selhip_ctx_set_topk_rounds asks of an all-pairs pass, checked before it claims a counter set: the rounds prune at the source with
+// the value the count kernel computes, and what they carry is the all-pairs top-k
+int accept_rounds(selhip_ctx* c) {
+    if (c->topk_rounds == 0) return SELHIP_OK;
+    if (c->allpairs_topk > 0 && c->criterion == SELHIP_CRIT_SMH_C && c->estimator == SELHIP_ESTIMATOR_SMH) return SELHIP_OK;
+    set_err(&c->err, "row rounds (selhip_ctx_set_topk_rounds) are for all-pairs top-k passes (selhip_ctx_set_allpairs_topk: %d) of criterion smh_c "
+                     "(SELHIP_CRIT_SMH_C) under the estimator smh (SELHIP_ESTIMATOR_SMH) (criterion %d, estimator %d); "
+                     "selhip_ctx_set_topk_rounds(ctx, 0) first", c->allpairs_topk, c->criterion, c->estimator);
+    return SELHIP_E_BADARG;
+}
 // what the count kernels of a pass that emits take besides: its records go to the context's result list behind block 0's n_results.
 // (the count floor of such a pass is 1: a pair without an equal bucket has no record)
 SmhcEmit smhc_emit(const selhip_ctx* c, PassCounters* pc0) { return SmhcEmit{(double)c->tau_f, c->measure, pc0}; }
@@ -119,9 +129,12 @@ hipError_t launch_count(selhip_ctx* c, hipStream_t st, const CountSets& a, const
     c->smhc_rule_used = cont ? 1 : 0;
     const SmhcRule rule{c->min_containment, a.ex, a.ey};
     const SmhcRuleEmit rule_em{rule, smhc_emit(c, pc0)};
+    // a round of a top-k pass in row rounds: the TOPK form, whose operand rides behind the emit form's
+    const bool topk = !QUERY && emit && c->rd.on;
+    const SmhcRuleEmitTopk rule_tk{rule_em, c->topk_thr.p};
     if (smhc_fast(m)) {
         const int nch = m / 128;
-        const long long n_tiles = rm.n_tiles(smhc_q(nch, emit && cont));
+        const long long n_tiles = rm.n_tiles(smhc_q(nch, smhc_tight(emit, cont, topk)));
         if (n_tiles > 0x7FFFFFFFll) return hipErrorInvalidValue;
         const int chunk_base = (first_cand / kChunk) * kChunk;
         const int n_chunks = (a.n_y - chunk_base + kChunk - 1) / kChunk;
@@ -129,6 +142,10 @@ hipError_t launch_count(selhip_ctx* c, hipStream_t st, const CountSets& a, const
         const long long blocks = n_tiles * n_chunks;
         if (blocks > 0x7FFFFFFFll) return hipErrorInvalidValue;
 #define SELHIP_SMHC_LAUNCH_R(NCH, RULE) do { \
+            if constexpr (!QUERY) if (topk) { \
+                hipLaunchKernelGGL((smh_count_kernel<NCH, false, RULE, true, true>), dim3((unsigned)blocks), dim3(kBlock), 0, st, (const u64x2*)a.X, (const u64x2*)a.Y, \
+                                   a.n_x, a.n_y, a.lo, a.hi, a.pc_in, rm, (int)n_tiles, chunk_base, c_min, res, res_cap, pc, rule_tk); \
+                break; } \
             if (emit) hipLaunchKernelGGL((smh_count_kernel<NCH, QUERY, RULE, true>), dim3((unsigned)blocks), dim3(kBlock), 0, st, (const u64x2*)a.X, (const u64x2*)a.Y, \
                                          a.n_x, a.n_y, a.lo, a.hi, a.pc_in, rm, (int)n_tiles, chunk_base, c_min, res, res_cap, pc, rule_em); \
             else hipLaunchKernelGGL((smh_count_kernel<NCH, QUERY, RULE, false>), dim3((unsigned)blocks), dim3(kBlock), 0, st, (const u64x2*)a.X, (const u64x2*)a.Y, \
@@ -150,6 +167,13 @@ hipError_t launch_count(selhip_ctx* c, hipStream_t st, const CountSets& a, const
     if (rows > 0x7FFFFFFFll || blocks > 0x7FFFFFFFll) return hipErrorInvalidValue;
     with_flag(cont, [&](auto C) {
         constexpr int RULE = decltype(C)::value ? kSmhcContainment : kSmhcFixed;
+        if constexpr (!QUERY) {
+            if (topk) {
+                hipLaunchKernelGGL((smh_count_generic_kernel<false, RULE, true, true>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a.X, a.Y, a.n_x, a.n_y, m, a.lo, a.hi, a.pc_in,
+                                   rm, (int)rows, c_min, res, res_cap, pc, rule_tk);
+                return;
+            }
+        }
         if (emit)
             hipLaunchKernelGGL((smh_count_generic_kernel<QUERY, RULE, true>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a.X, a.Y, a.n_x, a.n_y, m, a.lo, a.hi, a.pc_in,
                                rm, (int)rows, c_min, res, res_cap, pc, rule_em);
@@ -863,12 +887,13 @@ Chain chain_slices(selhip_ctx* c, int k, int chunks, hipStream_t st, long long b
 
 int enqueue_pass(selhip_ctx* c) {
     const int n = (int)c->n;
-    const int rb = (int)c->row_begin, re = (int)c->row_end;
+    // (a pass in row rounds, selhip_ctx_set_topk_rounds: the rows of the round in hand -- a sub-range pass -- instead of the pass's)
+    const int rb = (int)(c->rd.on ? c->rd.begin : c->row_begin), re = (int)(c->rd.on ? c->rd.end : c->row_end);
     const double tau = (double)c->tau_f;            // float threshold widened, selection.cpp:81,164
     const int crit = c->criterion;
     const PassPlan& plan = c->plan;
     c->dominant_timer = c->timed_kernel == 1 ? T_HIST : crit == SELHIP_CRIT_NONE ? T_DENSE : (plan.use_sig ? T_JOIN : T_STAGE1);
-    if (c->timing) c->timed_passes += 1;
+    if (c->timing && !(c->rd.on && c->rd.begin != c->row_begin)) c->timed_passes += 1;       // (the rounds of a pass are one pass)
     TimerScope total(c, T_TOTAL);
     const bool smh_crit = plan.smh, use_hash = plan.use_hash, use_sig = plan.use_sig;
     if (plan.bad) { set_err(&c->err, plan.bad, c->n_rows, c->n_bands); return SELHIP_E_BADARG; }

@@ -119,6 +119,16 @@ bool results_overflowed(u64 n_results, size_t have, size_t* res_cap) {
     return true;
 }
 
+// ---- all-pairs top-k in row rounds (selhip_ctx_set_topk_rounds) ----------------------------------
+// rows per round of a pass over n genomes: the setting itself, or under SELHIP_TOPK_ROUNDS_AUTO the largest R with R n <= 2^27 -- a round
+// admits at most R n records, 2 GiB of them --, one row at least.  `period` (the rows after which the deal of a row interleave
+// repeats, 1 without one): a round is whole periods, so that the rounds' rows are the rows the one-shot pass owns
+constexpr long long kTopkRoundRecords = 1ll << 27;
+long long topk_round_rows(long long setting, long long n, long long period) {
+    long long r = setting > 0 ? setting : std::max<long long>(1, kTopkRoundRecords / std::max<long long>(1, n));
+    return (r + period - 1) / period * period;
+}
+
 // pairs_direct_kernel: groups of four entries per wave and batch, and the grid -- one group per wave until the list has a group for
 // every wave slot of the device (1 024 blocks of 8 waves), then up to 16
 struct PairsDirectShape { int gpw; unsigned grid; };

@@ -5,8 +5,8 @@
 // Part of libselhip.so; included by selection_kernels.hip only (one translation unit, anonymous namespace).  All kernels read `aux`
 // row-major, as uploaded or attached: for a count any lane <-> bucket map does, as long as both rows of a pair use the same one
 // (DESIGN.md section 14), so there is no interleaved copy as in ALGO_STREAM.
-//   smh_count_kernel<NCH, QUERY, RULE, EMIT>  m = 128 * NCH buckets, NCH in {1, 2, 4, 8} (smhc_fast): smh_stream_kernel's block shape and enumeration
-//   smh_count_generic_kernel<QUERY, RULE, EMIT> every other m > 0: smh_generic_kernel's unit, lane = candidate, a serial loop over the buckets
+//   smh_count_kernel<NCH, QUERY, RULE, EMIT, TOPK>  m = 128 * NCH buckets, NCH in {1, 2, 4, 8} (smhc_fast): smh_stream_kernel's block shape and enumeration
+//   smh_count_generic_kernel<QUERY, RULE, EMIT, TOPK> every other m > 0: smh_generic_kernel's unit, lane = candidate, a serial loop over the buckets
 // QUERY = false: the all-pairs pass (rows and candidates from one set, the window of row i is [max(i + 1, z0), hi[i]], records (i, k));
 // QUERY = true: the query pass (rows from Q, candidates from D, the window of query i is [lo[i], hi[i]] of query_windows_kernel, records
 // (i, n_q + k) in the combined index space of stage 2).  The pair-list form is pairs_count_kernel (kernel_pairs.cuh).
@@ -21,6 +21,10 @@
 //     V = selhip::smh_value(measure, m, c, e_i, e_k) >= tau                                (pair_value.hpp)
 // and goes as the 16-byte record {i, k, V} into the RESULT list behind n_results: the pass has no stage 2.  Query records carry the
 // database rank k itself (the index space query_result_fixup_kernel restores for the other criteria).
+// TOPK (the last template argument of the two count kernels, false = the kernels as they were before it existed, instruction for
+// instruction; QUERY = false, EMIT = true only): one round of an all-pairs top-k pass in row rounds (selhip_ctx_set_topk_rounds, DESIGN.md
+// section 19).  A pair with V >= tau is COUNTED in n_final -- the |S| of the one-shot pass -- and its record is appended only if it is
+// ADMITTED: V >= thr[i] || V >= thr[k], thr[g] the value of genome g's K-th best record so far (-inf while it holds fewer than K).
 #pragma once
 
 namespace {
@@ -30,10 +34,15 @@ constexpr bool smhc_fast(int m) { return m == 128 || m == 256 || m == 512 || m =
 // lane masks in flight than the wave has SGPRs: 25 spilled in the all-pairs form, 6 in the query form -- the matrix kernel's finding)
 // (tight = the emit form under the containment rule: its threshold, measure, tally and second counter on top of the rule's one SGPR per
 //  row spilled 12 SGPRs in the all-pairs form and 4 in the query form at m = 128 and 256 with 12 rows: 8 rows there)
-constexpr int smhc_q(int nch, bool tight = false) {
+// (tight = 2, the round form -- TOPK -- of that: the threshold array and the tally of |S| on top spilled 2 SGPRs with 8 rows there: 6 rows;
+//  the round form under the fixed rule takes the 8 rows of tight = 1: 90 SGPRs, nothing spilled)
+constexpr int smhc_q(int nch, int tight = 0) {
     const int q = kQueryVgprBudget / nch < 12 ? kQueryVgprBudget / nch : 12;
-    return tight && nch <= 2 && q > 8 ? 8 : q;
+    const int cap = tight == 2 ? 6 : 8;
+    return tight && nch <= 2 && q > cap ? cap : q;
 }
+// the `tight` of a form
+constexpr int smhc_tight(bool emit, bool containment, bool topk) { return !emit ? 0 : topk ? (containment ? 2 : 1) : containment ? 1 : 0; }
 
 // the threshold step of every smh_c kernel
 __device__ __forceinline__ bool smhc_selects(int count, int c_min) { return count >= c_min; }
@@ -46,7 +55,10 @@ struct SmhcRule { double gamma; const u64* __restrict__ ex; const u64* __restric
 // the rule in the kernels' last argument, so the form that emits nothing keeps its argument list to the byte
 struct SmhcEmit { double tau; int measure; PassCounters* __restrict__ pc0; };
 struct SmhcRuleEmit : SmhcRule { SmhcEmit em; };
-template <bool EMIT> using SmhcRuleArg = std::conditional_t<EMIT, SmhcRuleEmit, SmhcRule>;
+// what a round of a top-k pass in row rounds reads besides: every genome's admission threshold as it stood when the round began.  It
+// rides behind the emit operands in the same way
+struct SmhcRuleEmitTopk : SmhcRuleEmit { const double* __restrict__ thr; };
+template <bool EMIT, bool TOPK = false> using SmhcRuleArg = std::conditional_t<TOPK, SmhcRuleEmitTopk, std::conditional_t<EMIT, SmhcRuleEmit, SmhcRule>>;
 template <bool EMIT> using SmhcRecord = std::conditional_t<EMIT, selhip_pair_t, selhip_int2_t>;
 // the record of a pair under the estimator, or nothing: *sel = V >= tau (false for NaN)
 __device__ __forceinline__ selhip_pair_t smhc_record(const SmhcEmit& em, int m, int cnt, u64 e1, u64 e2, int i, int k, bool* sel) {
@@ -59,6 +71,9 @@ __device__ __forceinline__ selhip_pair_t smhc_record(const SmhcEmit& em, int m, 
 __device__ __forceinline__ void smhc_tally(u64* __restrict__ n_survivors, int n_pass, int lane) {
     if (n_pass != 0 && lane == 0) atomicAdd(n_survivors, (u64)n_pass);
 }
+// THE admission test of a round, written once: non-strict, so that a tie with an owner's K-th value reaches the select, where the
+// partner rank decides.  Two uniform f64 loads and two compares, behind the pinned branch
+__device__ __forceinline__ bool smhc_admits(const double* __restrict__ thr, int i, int k, double v) { return v >= thr[i] || v >= thr[k]; }
 // the exact threshold of a pair under the containment rule
 __device__ __forceinline__ int smhc_pair_threshold(int m, double gamma, u64 e1, u64 e2, int c_min) {
     return max(c_min, selhip::smhc_threshold(m, gamma, e1 < e2 ? e1 : e2, e1 < e2 ? e2 : e1));
@@ -112,13 +127,14 @@ struct SmhcSpace {
 // ballot on the path every pair takes, where the whole count costs one s_bcnt1 and one s_add per ballot.
 // No LDS tile and no block barrier: a wave that has no candidate leaves on its own.
 // ---------------------------------------------------------------------------------------------
-template <int NCH, bool QUERY, int RULE, bool EMIT = false>
+template <int NCH, bool QUERY, int RULE, bool EMIT = false, bool TOPK = false>
 __global__ __launch_bounds__(kBlock, (NCH <= 4 ? 3 : 2))
 void smh_count_kernel(const u64x2* __restrict__ X, const u64x2* __restrict__ Y, int n_x, int n_y,
                       const int* __restrict__ lo, const int* __restrict__ hi, const PassCounters* __restrict__ pc_in,
                       RowMap rm, int n_tiles, int chunk_base, int c_min,
-                      SmhcRecord<EMIT>* __restrict__ surv, u64 surv_cap, PassCounters* __restrict__ pc, SmhcRuleArg<EMIT> rule) {
-    constexpr int Q = smhc_q(NCH, EMIT && RULE == kSmhcContainment);
+                      SmhcRecord<EMIT>* __restrict__ surv, u64 surv_cap, PassCounters* __restrict__ pc, SmhcRuleArg<EMIT, TOPK> rule) {
+    static_assert(!TOPK || (EMIT && !QUERY), "the round form is an all-pairs pass that emits");
+    constexpr int Q = smhc_q(NCH, smhc_tight(EMIT, RULE == kSmhcContainment, TOPK));
     constexpr int ROWV = NCH * kWave;                 // u64x2 per sketch row
     __shared__ SmhcRecord<EMIT> app_lds[kWavesPerBlock * kAppendCap];
 
@@ -178,6 +194,7 @@ void smh_count_kernel(const u64x2* __restrict__ X, const u64x2* __restrict__ Y, 
     if constexpr (EMIT) app.init(app_lds, wave, surv, surv_cap, &rule.em.pc0->n_results);
     else app.init(app_lds, wave, surv, surv_cap, &pc->n_survivors);
     int n_pass = 0;                                                           // EMIT: pairs that passed the count test (wave-uniform)
+    int n_sel = 0;                                                            // TOPK: those of them with V >= tau (wave-uniform)
     constexpr int AHEAD = NCH <= 4 ? kStreamAhead : 1;                         // (m = 1024: the registers allow one row ahead)
     constexpr int RING = AHEAD + 1;
     u64x2 ring[RING][NCH];
@@ -205,7 +222,14 @@ void smh_count_kernel(const u64x2* __restrict__ X, const u64x2* __restrict__ Y, 
                             n_pass += 1;
                             bool sel;
                             const selhip_pair_t r = smhc_record(rule.em, 128 * NCH, cnt, rule.ex[i], rule.ey[kk], i, kk, &sel);
-                            if (sel) app.push_uniform_record(r, lane);
+                            if constexpr (TOPK) {
+                                if (sel) {
+                                    n_sel += 1;
+                                    if (smhc_admits(rule.thr, i, kk, r.jaccard)) app.push_uniform_record(r, lane);
+                                }
+                            } else {
+                                if (sel) app.push_uniform_record(r, lane);
+                            }
                         }
                     } else {
                         if (ok) app.push_uniform(i, sp.partner(kk), lane);
@@ -227,15 +251,17 @@ void smh_count_kernel(const u64x2* __restrict__ X, const u64x2* __restrict__ Y, 
     }
     app.flush(lane);
     if constexpr (EMIT) smhc_tally(&pc->n_survivors, n_pass, lane);
+    if constexpr (TOPK) smhc_tally(&pc->n_final, n_sel, lane);
 }
 
 // generic stage 1: block = 256 lanes = 256 candidates of one row; grid = (chunks, rows)
-template <bool QUERY, int RULE, bool EMIT = false>
+template <bool QUERY, int RULE, bool EMIT = false, bool TOPK = false>
 __global__ __launch_bounds__(kBlock)
 void smh_count_generic_kernel(const u64* __restrict__ X, const u64* __restrict__ Y, int n_x, int n_y, int m,
                               const int* __restrict__ lo, const int* __restrict__ hi, const PassCounters* __restrict__ pc_in,
                               RowMap rm, int n_rows_grid, int c_min,
-                              SmhcRecord<EMIT>* __restrict__ surv, u64 surv_cap, PassCounters* __restrict__ pc, SmhcRuleArg<EMIT> rule) {
+                              SmhcRecord<EMIT>* __restrict__ surv, u64 surv_cap, PassCounters* __restrict__ pc, SmhcRuleArg<EMIT, TOPK> rule) {
+    static_assert(!TOPK || (EMIT && !QUERY), "the round form is an all-pairs pass that emits");
     __shared__ SmhcRecord<EMIT> app_lds[kWavesPerBlock * kAppendCap];
     int i, i_e;
     rm.tile_rows((int)(blockIdx.x % n_rows_grid), 1, &i, &i_e);
@@ -258,9 +284,11 @@ void smh_count_generic_kernel(const u64* __restrict__ X, const u64* __restrict__
         app.init(app_lds, wave, surv, surv_cap, &rule.em.pc0->n_results);
         bool sel;
         const selhip_pair_t r = smhc_record(rule.em, m, cnt, rule.ex[i], rule.ey[k], i, k, &sel);       // (k = 0 out of range: a valid rank)
-        app.push_record(ok && sel, r, lane);
+        if constexpr (TOPK) app.push_record(ok && sel && smhc_admits(rule.thr, i, k, r.jaccard), r, lane);      // (k = 0 out of range: a valid rank)
+        else app.push_record(ok && sel, r, lane);
         app.flush(lane);
         smhc_tally(&pc->n_survivors, (int)__popcll(__ballot(ok)), lane);
+        if constexpr (TOPK) smhc_tally(&pc->n_final, (int)__popcll(__ballot(ok && sel)), lane);
     } else {
         const bool ok = in_range && smhc_selects(smhc_count_lane(X + (long long)i * m, Y + (long long)k * m, m), t);
         WaveAppender app;

@@ -8,6 +8,9 @@
 //   (rocprim::exclusive_scan of the packed counts, TopkPack: low word = an owner's segment start, high word = its output start)
 //   topk_scatter_kernel  (key(J), partner) of every (directed) record into its owner's segment: 12 bytes each in two arrays
 //   topk_select_kernel   one block per segment: MSB-first radix select of the K best, bitonic sort of the winners, records written
+//   topk_threshold_kernel  a pass in row rounds: every owner's admission threshold for the next round
+// Such a pass MERGES: the carried list C (directed records {owner, partner, V}, counted and scattered once, BOTH = false) and the round's
+// new records (BOTH = true) go through the same count array, scan, segments and select.
 // key(J): bits ^ 2^63 for a clear sign bit, ~bits for a set one -- a u64 whose unsigned order is the IEEE total order; its inverse is the
 // same two cases told apart by the key's top bit, so the J bits come back exactly.
 // The tile rule.  The i side arrives clustered by i (a query pass by query; an all-pairs pass bucketed by row where stage 2 groups, row
@@ -279,6 +282,21 @@ void topk_select_kernel(const u64* __restrict__ seg_key, const uint32_t* __restr
         const u64 bits = topk_unkey(skey[t]);
         if (out0 + t < out_cap) out4[out0 + t] = make_uint4((uint32_t)q, sval[t], (uint32_t)bits, (uint32_t)(bits >> 32));
     }
+}
+
+// The admission thresholds of a top-k pass in row rounds (selhip_ctx_set_topk_rounds), behind the select of a round's merge: thr[g] =
+// the value of owner g's K-th record in the reduced list `out` (its records stand at the output starts of `off`, in ranked order), and
+// -inf for an owner that holds fewer than K.  off == nullptr: before the first round, -inf for every owner.
+__global__ __launch_bounds__(kBlock)
+void topk_threshold_kernel(const selhip_pair_t* __restrict__ out, u64 out_cap, const u64* __restrict__ off, int n_own, int K, double* __restrict__ thr) {
+    const int g = (int)(blockIdx.x * kBlock + threadIdx.x);
+    if (g >= n_own) return;
+    double t = -__builtin_inf();
+    if (off) {
+        const u64 o0 = off[g] >> 32, o1 = off[g + 1] >> 32;
+        if (o1 - o0 == (u64)K && o1 <= out_cap) t = out[o1 - 1].jaccard;
+    }
+    thr[g] = t;
 }
 
 }  // namespace

@@ -13,7 +13,7 @@ import numpy as np
 from . import _lib
 from ._lib import (ALGO_AUTO, BANDING_CPU, CRIT_HLL_A, CRIT_HLL_AN, CRIT_HLL_A_SMH_A, CRIT_NONE, CRIT_SMH_A, CRIT_SMH_C, ESTIMATOR_HLL, ESTIMATOR_SMH, F32, F64, FP_FMA,
                    MEASURE_CONTAINMENT, MEASURE_INTERSECTION, MEASURE_JACCARD, MEASURE_MAX_CONTAINMENT, MEASURE_SMH_JACCARD,
-                   MEASURE_SMH_MATCHES, MEASURE_UNION, MODE_CB_SMH, Pair, check, hip_lib, host_lib)
+                   MEASURE_SMH_MATCHES, MEASURE_UNION, MODE_CB_SMH, TOPK_ROUNDS_AUTO, Pair, check, hip_lib, host_lib)
 
 # layout of selhip_pair_t {int32 i, k; double jaccard}
 PAIR_DTYPE = np.dtype([("i", "<i4"), ("k", "<i4"), ("jaccard", "<f8")], align=True)
@@ -265,6 +265,14 @@ class Selector:
         uncut count; query passes ignore the setting"""
         check(self._lib.selhip_ctx_set_allpairs_topk(self._ctx, int(k)), self._ctx)
 
+    def set_topk_rounds(self, rows):
+        """the following all-pairs top-k passes of CRIT_SMH_C under set_estimator("smh") run in rounds of `rows` rows: each round is
+        merged into a carried list of at most k records per genome, whose k-th values are the next round's admission thresholds --
+        the same ranked list, record for record, with n k + one round's admitted records of memory instead of |S|.  0 = off (the
+        default), "auto" (or TOPK_ROUNDS_AUTO) = the largest R with R n <= 2^27.  Sticky; query and pair-list passes ignore it, any
+        other all-pairs pass is refused while it is on.  get_param("topk_rounds_used"), ("topk_admitted_lo"), ("topk_admitted_hi")"""
+        check(self._lib.selhip_ctx_set_topk_rounds(self._ctx, topk_rounds_code(rows)), self._ctx)
+
     def fetch_ranked(self) -> np.ndarray:
         """the reduced list of the last pass as it lies on the device: query rank (all-pairs: owner rank) ascending, within it best
         first (no host sort); raises unless that pass ran with its top-k on"""
@@ -352,12 +360,16 @@ class Selector:
 
     # -- the hot path -------------------------------------------------------------------------------
     def run(self, tau: float, mode: int = MODE_CB_SMH, n_rows: Optional[int] = None, n_bands: Optional[int] = None,
-            rows: Optional[Tuple[int, int]] = None, algo: int = ALGO_AUTO, fetch: bool = True, top_k: Optional[int] = None):
+            rows: Optional[Tuple[int, int]] = None, algo: int = ALGO_AUTO, fetch: bool = True, top_k: Optional[int] = None,
+            rounds=None):
         """one all-pairs pass: records {i, k, jaccard}, i < k, sorted by (i, k).  top_k given: set_allpairs_topk(top_k) first (the
         setting stays), and with top_k > 0 the records come in ranked order (fetch_ranked): every genome's top_k best partners as
-        {i = owner, k = partner, jaccard}, J descending, ties by ascending partner rank"""
+        {i = owner, k = partner, jaccard}, J descending, ties by ascending partner rank.  rounds given: set_topk_rounds(rounds) first
+        (the setting stays)"""
         if top_k is not None:
             self.set_allpairs_topk(top_k)
+        if rounds is not None:
+            self.set_topk_rounds(rounds)
         if n_rows is None or n_bands is None:
             n_rows, n_bands = banding(self.m, tau) if self.m else (1, 1)
         rb, re = rows if rows is not None else (0, self.n)
@@ -622,7 +634,8 @@ def _criterion_files(criterion: str, aux_bytes: int, min_matches: Optional[int] 
 
 def select_from_filelist(list_file: str, tau: float, aux_bytes: int, mode: int = MODE_CB_SMH, device: int = 0,
                          fp_mode: int = FP_FMA, algo: int = ALGO_AUTO, criterion: str = "smh_a", top_k: int = 0,
-                         min_matches: Optional[int] = None, measure="jaccard", min_containment: Optional[float] = None, estimator="hll") -> str:
+                         min_matches: Optional[int] = None, measure="jaccard", min_containment: Optional[float] = None, estimator="hll",
+                         top_k_rounds=0) -> str:
     """The whole of selection_cuda.cpp main() (criterion smh_a) -- and of selection.cpp's hll_a / hll_an
     branches (:122-227): returns the text the CPU reference prints for `-c criterion -a aux_bytes -h tau`.
     criterion "none": no criterion in front of the Jaccard test (CRIT_NONE; mode MODE_CB_SMH = the CB bound alone, MODE_SMH = every pair).
@@ -634,9 +647,14 @@ def select_from_filelist(list_file: str, tau: float, aux_bytes: int, mode: int =
     measure "max_containment": the pairs with I / min(e_i, e_k) >= tau, that value printed in J's place (Selector.set_measure;
     ValueError with mode=MODE_CB_SMH or an hll_* criterion).
     estimator "smh" (`-V smh`, criterion "smh_c" alone): the value tested and printed is the SuperMinHash estimate of the count,
-    smh_value(measure, m, c, e_i, e_k) (Selector.set_estimator), and no HLL stage runs."""
+    smh_value(measure, m, c, e_i, e_k) (Selector.set_estimator), and no HLL stage runs.
+    top_k_rounds (`-R rows`, with top_k > 0, criterion "smh_c" and estimator "smh" alone): the pass runs in rounds of that many rows, or
+    "auto" (Selector.set_topk_rounds): the same text."""
     meas = _pass_measure(measure, mode, criterion)
     est = _pass_estimator(estimator, criterion)
+    rounds = topk_rounds_code(top_k_rounds)
+    if rounds and not (top_k and criterion == "smh_c" and est == ESTIMATOR_SMH):
+        raise ValueError("top_k_rounds takes top_k > 0, criterion 'smh_c' and estimator 'smh'")
     m, p_aux, crit = _criterion_files(criterion, aux_bytes, min_matches, min_containment)
     ds = load_dataset(list_file, m, p_aux, fp_mode)
     n_rows, n_bands = banding(m, tau) if m else (1, 1)
@@ -652,8 +670,17 @@ def select_from_filelist(list_file: str, tau: float, aux_bytes: int, mode: int =
             sel.set_min_containment(min_containment)
         sel.set_measure(meas)
         sel.set_estimator(est)
-        pairs = sel.run(tau, mode, n_rows, n_bands, algo=algo, top_k=top_k if top_k else None)
+        pairs = sel.run(tau, mode, n_rows, n_bands, algo=algo, top_k=top_k if top_k else None, rounds=rounds if rounds else None)
     return format_lines(ds.names, pairs)
+
+
+def topk_rounds_code(rows) -> int:
+    """what selhip_ctx_set_topk_rounds takes for Selector.set_topk_rounds' argument: rows per round >= 0, or "auto" / TOPK_ROUNDS_AUTO"""
+    if rows == "auto":
+        return TOPK_ROUNDS_AUTO
+    if isinstance(rows, bool) or not isinstance(rows, (int, np.integer)) or (rows < 0 and rows != TOPK_ROUNDS_AUTO):
+        raise ValueError("top-k rounds: rows per round (0 = off) or 'auto'")
+    return int(rows)
 
 
 MEASURES = {"jaccard": MEASURE_JACCARD, "union": MEASURE_UNION, "smh_matches": MEASURE_SMH_MATCHES, "smh_jaccard": MEASURE_SMH_JACCARD,

@@ -409,6 +409,32 @@ int selhip_ctx_last_attempts(const selhip_ctx* ctx);
  * SELHIP_TOPK_MAX and selhip_ctx_fetch_ranked are declared in section 2b. */
 int selhip_ctx_set_allpairs_topk(selhip_ctx* ctx, int k);
 
+/* The all-pairs top-k in ROW ROUNDS: nbr(S, k) without ever holding S.  For the all-pairs passes with selhip_ctx_set_allpairs_topk(k > 0),
+ * SELHIP_CRIT_SMH_C and SELHIP_ESTIMATOR_SMH (the passes whose stage 1 emits the records).  The pass's row range is cut into rounds
+ * of `rows` rows; each round runs as the sub-range pass a caller could run, its records are merged into a carried directed list C of at
+ * most k records per genome, and
+ *     thr[g] = -inf while C holds fewer than k records of owner g, else the value of g's k-th record in C
+ * is raised from C.  A pair (i, k') of a later round that passes everything it passes in the one-shot pass (pair space, count threshold,
+ * V >= tau_f) is ADMITTED -- appended and merged -- iff V >= thr[i] || V >= thr[k'], with the thresholds as they stood when its round
+ * began; every other pair is dropped where it is counted.  The test is not strict: a tie with the k-th value can displace it by partner
+ * rank.  The result is nbr(S, k) of the one-shot pass, record for record and bit for bit, in ranked order (a pair rejected for owner g
+ * has k records of g ranking before it, and thresholds only rise); memory is n k records plus one round's admitted records instead
+ * of |S|, and the limit of 2^31 - 1 directed records applies to |C| + 2 (admitted records of one round) instead of 2 |S|.
+ * rows = 0: off (the default: every pass issues exactly the launches and returns exactly the bytes it does without this call);
+ * rows > 0: that many rows per round; SELHIP_TOPK_ROUNDS_AUTO: the largest R with R n <= 2^27 records, one row at least.  Under a row
+ * interleave of more than one part a round is whole periods of the deal (2 block_rows n_parts rows): rows is rounded up to that.
+ * Anything else SELHIP_E_BADARG; SELHIP_E_STATE while a pass is pending.  The setting survives uploads / attaches.  Only all-pairs passes
+ * read it: query passes and pair-list passes ignore it, and an all-pairs pass with rounds on but without the all-pairs top-k, criterion
+ * smh_c or the estimator smh is refused with SELHIP_E_BADARG before anything is launched.
+ * selhip_ctx_run_async enqueues the first round, selhip_ctx_finish drives the rest; a round whose result list overflows grows the list
+ * and repeats alone.  Row interleave, candidate begin and selhip_ctx_set_pipeline apply inside each round.  Afterwards the result
+ * accessors behave as behind any cut pass; selhip_ctx_stats returns what the one-shot pass returns (stats[2] = |S|, the pairs with
+ * V >= tau_f, not the admitted count); selhip_ctx_last_attempts is the largest attempt count of any round.  selhip_ctx_get_param:
+ * "topk_rounds" (the setting), "topk_rounds_used" (rounds of the last all-pairs pass, 0 = it ran in one), "topk_admitted_lo" /
+ * "topk_admitted_hi" (low / high 31 bits of the records admitted over all rounds).  Merge and thresholds are timed as "topk". */
+#define SELHIP_TOPK_ROUNDS_AUTO (-1)
+int selhip_ctx_set_topk_rounds(selhip_ctx* ctx, int64_t rows);
+
 /* device time (ms, HIP events on the stream each kernel is launched on) of the named kernel PER PASS, averaged over
  * the passes since the last reset (a pipelined pass launches a kernel once per row chunk: the figure is their sum);
  * names: "prep", "sigbuild", "join", "verify", "stage1", "aux", "group", "hist", "select", "dense" (the fused kernel of
