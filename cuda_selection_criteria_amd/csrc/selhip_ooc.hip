@@ -32,6 +32,7 @@ extern "C" int selhip_ooc_select(int device, const uint8_t* h_hll, const uint64_
                       selhip_pair_t* h_out, int64_t cap, int64_t* count_out, int64_t stats_out[4]) {
     if (!count_out || cap < 0 || (cap && !h_out) || n < 0 || block_genomes < 1 || n_streams < 1 || n_streams > 4) { selhip_internal_set_error("bad argument"); return SELHIP_E_BADARG; }
     if (n > 0 && (!h_hll || !h_aux || !h_cards)) { selhip_internal_set_error("the out-of-core driver needs host sketches and their cardinalities"); return SELHIP_E_BADARG; }
+    if (p_hll < 4 || p_hll > 20) { selhip_internal_set_error("p_hll %d out of range [4,20]", p_hll); return SELHIP_E_BADARG; }   // (before any buffer is sized by it)
     if (criterion == SELHIP_CRIT_SMH_C) { selhip_internal_set_error("criterion smh_c (SELHIP_CRIT_SMH_C) needs a count threshold that this entry has no argument for: run it through selhip_ctx_set_min_matches and the context passes"); return SELHIP_E_BADARG; }
     const bool need_aux_hll = criterion != SELHIP_CRIT_SMH_A && criterion != SELHIP_CRIT_NONE;
     if (need_aux_hll && (!h_aux_hll || p_aux < 4 || p_aux > SELHIP_MAX_AUX_P)) { selhip_internal_set_error("criterion %d needs auxiliary HLL sketches", criterion); return SELHIP_E_BADARG; }

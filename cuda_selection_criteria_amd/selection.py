@@ -802,15 +802,18 @@ def select_pairs_from_filelist(list_file: str, pair_file: str, tau: float, aux_b
 
 def multi_select(devices: Sequence[int], hll: np.ndarray, aux: np.ndarray, cards: np.ndarray, tau: float,
                  mode: int = MODE_CB_SMH, n_rows: Optional[int] = None, n_bands: Optional[int] = None, algo: int = ALGO_AUTO,
-                 fp_mode: int = FP_FMA, gather: int = 2, criterion: int = 0, aux_hll: Optional[np.ndarray] = None, p_aux: int = 0):
+                 fp_mode: int = FP_FMA, gather: int = 2, criterion: int = 0, aux_hll: Optional[np.ndarray] = None, p_aux: int = 0,
+                 p_hll: int = 14):
     """selhip_multi_select: one process, one context per listed device, interleaved row blocks, RCCL (or host) gather.
     gather: 0 host merge, 1 RCCL required, 2 RCCL if available; criterion / aux_hll / p_aux as for Selector (hll_a, hll_an,
-    the two-stage criterion of BASELINE configs[4]; CRIT_NONE takes no auxiliary sketches).  Returns (pairs sorted by (i,k), stats dict)."""
+    the two-stage criterion of BASELINE configs[4]; CRIT_NONE takes no auxiliary sketches); p_hll: precision of the main sketches
+    (hll is [n, 1 << p_hll]).  Returns (pairs sorted by (i,k), stats dict)."""
     lib = hip_lib()
     hll = np.ascontiguousarray(hll, dtype=np.uint8)
     aux = np.ascontiguousarray(aux, dtype=np.uint64)
     cards = np.ascontiguousarray(cards, dtype=np.float64)
     n, m = aux.shape
+    assert hll.shape == (n, 1 << p_hll), (hll.shape, n, p_hll)
     if n_rows is None or n_bands is None:
         n_rows, n_bands = banding(m, tau)
     devs = (C.c_int * len(devices))(*devices)
@@ -821,7 +824,7 @@ def multi_select(devices: Sequence[int], hll: np.ndarray, aux: np.ndarray, cards
         cnt = C.c_int64()
         st = (C.c_int64 * 4)()
         rc = lib.selhip_multi_select(devs, len(devices), hll.ctypes.data, aux.ctypes.data, cards.ctypes.data,
-                                     ah.ctypes.data if ah is not None else None, p_aux, criterion, n, m, 14, mode, algo,
+                                     ah.ctypes.data if ah is not None else None, p_aux, criterion, n, m, p_hll, mode, algo,
                                      fp_mode, np.float32(tau), n_rows, n_bands, gather, out.ctypes.data, cap, C.byref(cnt), st)
         if rc == -3:
             cap = int(cnt.value)
@@ -833,14 +836,16 @@ def multi_select(devices: Sequence[int], hll: np.ndarray, aux: np.ndarray, cards
 def ooc_select(hll: np.ndarray, aux: np.ndarray, cards: np.ndarray, tau: float, block_genomes: int,
                mode: int = MODE_CB_SMH, n_rows: Optional[int] = None, n_bands: Optional[int] = None, algo: int = ALGO_AUTO,
                fp_mode: int = FP_FMA, n_streams: int = 2, device: int = 0, criterion: int = 0,
-               aux_hll: Optional[np.ndarray] = None, p_aux: int = 0):
+               aux_hll: Optional[np.ndarray] = None, p_aux: int = 0, p_hll: int = 14):
     """selhip_ooc_select: the sketches stay in host memory, at most n_streams * 2 * block_genomes of them are on the device
-    at a time; same result as one in-core pass.  Returns (pairs with global ranks sorted by (i,k), stats dict)."""
+    at a time; same result as one in-core pass.  p_hll: precision of the main sketches (hll is [n, 1 << p_hll]).  Returns (pairs with
+    global ranks sorted by (i,k), stats dict)."""
     lib = hip_lib()
     hll = np.ascontiguousarray(hll, dtype=np.uint8)
     aux = np.ascontiguousarray(aux, dtype=np.uint64)
     cards = np.ascontiguousarray(cards, dtype=np.float64)
     n, m = aux.shape
+    assert hll.shape == (n, 1 << p_hll), (hll.shape, n, p_hll)
     if n_rows is None or n_bands is None:
         n_rows, n_bands = banding(m, tau)
     ah = np.ascontiguousarray(aux_hll, dtype=np.uint8) if aux_hll is not None and criterion not in (CRIT_SMH_A, CRIT_NONE) else None
@@ -850,7 +855,7 @@ def ooc_select(hll: np.ndarray, aux: np.ndarray, cards: np.ndarray, tau: float, 
         cnt = C.c_int64()
         st = (C.c_int64 * 4)()
         rc = lib.selhip_ooc_select(device, hll.ctypes.data, aux.ctypes.data, cards.ctypes.data,
-                                   ah.ctypes.data if ah is not None else None, p_aux, criterion, n, m, 14, mode, algo, fp_mode,
+                                   ah.ctypes.data if ah is not None else None, p_aux, criterion, n, m, p_hll, mode, algo, fp_mode,
                                    np.float32(tau), n_rows, n_bands, block_genomes, n_streams, out.ctypes.data, cap, C.byref(cnt), st)
         if rc == -3:
             cap = int(cnt.value)

@@ -234,7 +234,17 @@ int selhip_ctx_set_fp_mode(selhip_ctx* ctx, int fp_mode);
 /* Host -> device upload of sketches already in ascending-cardinality order
  * (the flatten step of selection_cuda.cpp:131-143 + the H2D copies :167-169).
  *   h_hll [n][1<<p_hll] u8, h_aux [n][m] u64, h_cards [n] f64 (may be NULL: computed on the device
- *   from the registers with the Ertl-MLE estimator, == hll_t::report()). */
+ *   from the registers with the Ertl-MLE estimator, == hll_t::report()).
+ * p_hll is 4 .. 20.  What runs at p_hll != 14 (tests/test_hll_precision_host.py, tests/test_hll_precision_gpu.py: bit for bit
+ * against the oracle at every p):
+ *   entry                                              | at p_hll != 14
+ *   ---------------------------------------------------+--------------------------------------------------------------------------
+ *   upload / attach, selhip_hll_cards                  | no bit planes ("hll_khi" 0); cards from the byte rows
+ *   selhip_ctx_run*, selhip_ctx_run_pairs*, top-k,     | stage 2 on byte rows through hll_union_hist_kernel: no bit-plane stage, no
+ *   selhip_ooc_select, selhip_multi_select,            | grouping, no one-launch small pass ("small_pass_used" 0); same records and
+ *   launch_kernel_*                                    | statistics as the oracle at that p
+ *   selhip_hll_union_hist, selhip_ertl_estimate        | any p in 4 .. 20
+ *   SELHIP_CRIT_NONE, HLL matrices, query passes       | refused: SELHIP_E_BADARG, they need p_hll = 14 */
 int selhip_ctx_upload(selhip_ctx* ctx, const uint8_t* h_hll, const uint64_t* h_aux, const double* h_cards,
                       int64_t n_genomes, int m, int p_hll);
 /* Same, for sketches that already live in device memory (caller keeps ownership and must keep them
