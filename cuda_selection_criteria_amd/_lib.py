@@ -77,6 +77,7 @@ HIP_SYMBOLS = {
     "selhip_ctx_attach": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i]),
     "selhip_ctx_upload_aux_hll": (_i, [_vp, _vp, _i]),
     "selhip_ctx_attach_aux_hll": (_i, [_vp, _vp, _i]),
+    "selhip_ctx_fold_aux_hll": (_i, [_vp, _i]),
     "selhip_ctx_set_criterion": (_i, [_vp, _i]),
     "selhip_ctx_set_min_matches": (_i, [_vp, _i]),
     "selhip_ctx_set_min_containment": (_i, [_vp, _d]),
@@ -115,6 +116,7 @@ HIP_SYMBOLS = {
     "selhip_ctx_set_topk_rounds": (_i, [_vp, _i64]),
     "selhip_ctx_upload_queries_aux_hll": (_i, [_vp, _vp, _i]),
     "selhip_ctx_attach_queries_aux_hll": (_i, [_vp, _vp, _i]),
+    "selhip_ctx_fold_queries_aux_hll": (_i, [_vp, _i]),
     "selhip_ctx_matrix": (_i, [_vp, _i, _i, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp]),
     "selhip_ctx_query_matrix": (_i, [_vp, _i, _i, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp]),
     "selhip_smh_a_pairs": (_i, [_vp, _i, _i, _i, _vp, _i64, _vp, _vp]),
@@ -123,6 +125,7 @@ HIP_SYMBOLS = {
     "selhip_hll_union_hist_planes": (_i, [_vp, _vp, _i, _vp, _i64, _vp, _vp]),
     "selhip_ertl_estimate": (_i, [_vp, _i64, _i, _i, _vp, _vp]),
     "selhip_smh_match_counts": (_i, [_vp, _i, _vp, _i64, _vp, _vp]),
+    "selhip_hll_fold": (_i, [_vp, _i64, _i, _i, _vp, _vp]),
     "selhip_synth_generate": (_i, [C.POINTER(Synth), _i64, _i64, _vp, _vp, _vp, _vp]),
     "selhip_permute_rows": (_i, [_vp, _vp, _vp, _i64, _i64, _vp]),
     "selhip_build_sketches": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp]),
@@ -171,6 +174,7 @@ HOST_SYMBOLS = {
     "selhost_results_text": (_i64, [_vp, _vp, C.c_size_t]),
     "selhost_synth_generate": (_i, [C.POINTER(Synth), _i64, _i64, _vp, _vp, _vp, _i]),
     "selhost_shard_rows": (_i, [_i64, _vp, _i64, _i, _vp]),
+    "selhost_hll_fold": (_i, [_vp, _i64, C.c_uint, C.c_uint, _vp]),
     "selhost_version": (_cp, []),
 }
 

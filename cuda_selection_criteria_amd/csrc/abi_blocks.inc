@@ -72,6 +72,17 @@ int selhip_smh_match_counts(const uint64_t* d_aux, int m, const selhip_int2_t* d
     return SELHIP_OK;
 }
 
+int selhip_hll_fold(const uint8_t* d_hll, int64_t n, int p, int p_aux, uint8_t* d_out, void* hip_stream) {
+    if (n < 0 || p < 4 || p > 20 || p_aux < 4 || p_aux > p || p_aux > kMaxAuxP) {
+        set_err(nullptr, "selhip_hll_fold: p %d, p_aux %d: need 4 <= p <= 20 and 4 <= p_aux <= min(p, %d)", p, p_aux, kMaxAuxP);
+        return SELHIP_E_BADARG;
+    }
+    if (n == 0) return SELHIP_OK;
+    if (!d_hll || !d_out) { set_err(nullptr, "selhip_hll_fold: null pointer"); return SELHIP_E_BADARG; }
+    if (((uintptr_t)d_hll & 15) || ((uintptr_t)d_out & 15)) { set_err(nullptr, "selhip_hll_fold: pointers must be 16-byte aligned"); return SELHIP_E_BADARG; }
+    HIPCHK(nullptr, launch_hll_fold((hipStream_t)hip_stream, d_hll, (u64)n, p, p_aux, d_out));
+    return SELHIP_OK;
+}
 
 // (selhip_multi_select lives in selhip_multi.hip, selhip_ooc_select in selhip_ooc.hip: host-only translation units of this library
 // built on the context API above; what they need beyond it is declared in selhip_internal.h and defined here)

@@ -352,6 +352,34 @@ int selhip_ctx_attach_aux_hll(selhip_ctx* c, const uint8_t* d_aux_hll, int p_aux
     return SELHIP_OK;
 }
 
+// the same registers folded on the device from the set's main sketches d_hll [n][1 << c->p] (hll_fold_kernel): leaves what
+// upload_aux_hll_rows leaves (the arguments were checked)
+static int fold_aux_hll_rows(selhip_ctx* c, const uint8_t* d_hll, int64_t n, int p_aux, DevBuf<uint8_t>& own, const uint8_t** d_aux_hll, int* p_set) {
+    const size_t bytes = (size_t)n << p_aux;
+    HIPCHK(&c->err, own.ensure(bytes ? bytes : 1));
+    if (bytes) HIPCHK(&c->err, launch_hll_fold(c->stream, d_hll, (u64)n, c->p, p_aux, own.p));
+    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    *d_aux_hll = own.p; *p_set = p_aux;
+    return SELHIP_OK;
+}
+
+// range of a fold's p_aux against the main sketches' precision, with a message
+static int check_fold_p(selhip_ctx* c, int p_aux) {
+    const int hi = std::min(c->p, kMaxAuxP);
+    if (p_aux < 4 || p_aux > hi) { set_err(&c->err, "fold: p_aux %d out of range [4,%d] (p_hll = %d)", p_aux, hi, c->p); return SELHIP_E_BADARG; }
+    return SELHIP_OK;
+}
+
+int selhip_ctx_fold_aux_hll(selhip_ctx* c, int p_aux) {
+    if (!c) return SELHIP_E_BADARG;
+    if (c->m <= 0 || (!c->d_hll && c->n)) { set_err(&c->err, "upload or attach the primary sketches before folding them"); return SELHIP_E_STATE; }
+    if (c->pending) { set_err(&c->err, "a pass is still pending (selhip_ctx_finish)"); return SELHIP_E_STATE; }
+    const int rc = check_fold_p(c, p_aux);
+    if (rc) return rc;
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    return fold_aux_hll_rows(c, c->d_hll, c->n, p_aux, c->own_aux_hll, &c->d_aux_hll, &c->p_aux);
+}
+
 static int validate_shape(selhip_ctx* c, int64_t n, int m, int p) {
     if (n < 0 || n > 0x7FFFFFF0ll) { set_err(&c->err, "n_genomes %lld out of range", (long long)n); return SELHIP_E_BADARG; }
     if (m <= 0) { set_err(&c->err, "m must be > 0"); return SELHIP_E_BADARG; }

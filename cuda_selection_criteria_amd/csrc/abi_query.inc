@@ -92,6 +92,19 @@ int selhip_ctx_attach_queries_aux_hll(selhip_ctx* c, const uint8_t* d_aux_hll, i
     return SELHIP_OK;
 }
 
+int selhip_ctx_fold_queries_aux_hll(selhip_ctx* c, int p_aux) {
+    if (!c) return SELHIP_E_BADARG;
+    auto& q = c->q;
+    int rc = check_query_aux(c, q.d_hll, p_aux);           // (the main rows stand in for the pointer: null only for an empty set)
+    if (rc) return rc;
+    if (c->pending) { set_err(&c->err, "a pass is still pending (selhip_ctx_finish)"); return SELHIP_E_STATE; }
+    rc = check_fold_p(c, p_aux);
+    if (rc) return rc;
+    HIPCHK(&c->err, hipSetDevice(c->device));
+    q.d_aux_hll = nullptr; q.p_aux = 0;
+    return fold_aux_hll_rows(c, q.d_hll, q.n, p_aux, q.own_aux_hll, &q.d_aux_hll, &q.p_aux);
+}
+
 int selhip_ctx_run_queries(selhip_ctx* c, int mode, int algo, float tau_f, int n_rows, int n_bands) {
     if (!c) return SELHIP_E_BADARG;
     auto& q = c->q;

@@ -18,6 +18,7 @@
 
 #include "../ertl_mle.hpp"
 #include "../synth.hpp"
+#include "../hll_fold.hpp"
 
 namespace {
 
@@ -516,6 +517,22 @@ int selhost_shard_rows(int64_t n, const int32_t* hi, int64_t z0, int parts, int6
         bounds[part] = b;
     }
     bounds[parts] = n;
+    return SELHOST_OK;
+}
+
+// ---- auxiliary HLL sketches folded from the main ones (host twin of hll_fold_kernel; the rule is ../hll_fold.hpp) ------
+int selhost_hll_fold(const uint8_t* in, int64_t n, unsigned p, unsigned p_aux, uint8_t* out) {
+    if (n < 0 || p < 4 || p > 20 || p_aux < 4 || p_aux > p || p_aux > 15) return fail(SELHOST_E_BADARG, "hll_fold: p %u, p_aux %u: need 4 <= p <= 20 and 4 <= p_aux <= min(p, 15)", p, p_aux);
+    if (n > 0 && (!in || !out)) return fail(SELHOST_E_BADARG, "hll_fold: null pointer");
+    const unsigned d = p - p_aux;
+    const int64_t n_out = n << p_aux;
+#pragma omp parallel for schedule(static) if (n_out >= (1 << 16))
+    for (int64_t g = 0; g < n_out; ++g) {
+        const uint8_t* grp = in + ((size_t)g << d);
+        unsigned v = 0;
+        for (unsigned t = 0; t < (1u << d); ++t) v = selhip::fold_combine(v, selhip::fold_contrib(grp[t], t, d));
+        out[g] = (uint8_t)v;
+    }
     return SELHOST_OK;
 }
 

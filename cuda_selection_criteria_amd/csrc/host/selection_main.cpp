@@ -71,6 +71,11 @@
 //               behind the count: a pair is printed when c passes -C / -G AND that value is at least -h.  The sparse list of pairs by
 //               SuperMinHash J, and with -K / -k the nearest neighbours by it (-c smh_c -C 1 -n -h -1 -K 10 -V smh).  With -l, -q, -p,
 //               -k, -K, -n, -S max_containment, -o; -V smh needs -c smh_c and takes no -M (its estimator is -E), -g or -B
+//   -D          with -c hll_a | hll_an: derive the auxiliary HLL sketches instead of reading them -- no .hll_<p> file is opened; the p =
+//               ctz(-a bytes) sketches are folded on the device from the .hll registers (selhip_ctx_fold_aux_hll: bit for bit the
+//               registers of the files, so the same output), for any p in 4..14.  With -l, -q (both lists), -p, -k, -K; with -g and
+//               -B the host twin (selhost_hll_fold) folds the array handed to the drivers.  Not with -c smh_a | smh_c | none (they
+//               read no auxiliary HLL sketch), -M or -r
 //   -x          usage
 #include <unistd.h>
 
@@ -90,6 +95,7 @@
 // and its estimator (-V)
 static double g_min_containment = std::nan("");
 static int g_estimator = SELHIP_ESTIMATOR_HLL;
+static bool g_fold_aux = false;                  // -D: the auxiliary HLL sketches are folded from the main ones, no .hll_<p> file is read
 static long long g_topk_rounds = 0;              // -R: rows per round of -K (0: not given, SELHIP_TOPK_ROUNDS_AUTO: auto)
 static int set_count_thresholds(selhip_ctx* ctx, int min_matches) {
     int r = min_matches > 0 ? selhip_ctx_set_min_matches(ctx, min_matches) : 0;
@@ -97,6 +103,15 @@ static int set_count_thresholds(selhip_ctx* ctx, int min_matches) {
     if (!r) r = selhip_ctx_set_estimator(ctx, g_estimator);
     return r;
 }
+
+// the auxiliary HLL sketches of the context's database (queries: of its query set): folded on the device under -D, else uploaded
+static int load_aux_hll(selhip_ctx* ctx, const selhost_dataset* ds, unsigned p_aux, bool queries) {
+    if (g_fold_aux) return queries ? selhip_ctx_fold_queries_aux_hll(ctx, (int)p_aux) : selhip_ctx_fold_aux_hll(ctx, (int)p_aux);
+    return queries ? selhip_ctx_upload_queries_aux_hll(ctx, selhost_dataset_aux_hll(ds), (int)p_aux)
+                   : selhip_ctx_upload_aux_hll(ctx, selhost_dataset_aux_hll(ds), (int)p_aux);
+}
+// precision of the .hll_<p> files a run opens: none under -D
+static unsigned aux_files(unsigned p_aux) { return g_fold_aux ? 0 : p_aux; }
 
 // -q: the query list against the database list (-l), both loaded and sorted by cardinality; text on stdout.  criterion: "smh_a"
 // (m = aux_bytes / 8 buckets), "hll_a" / "hll_an" (auxiliary HLL p = ctz(aux_bytes), as the all-pairs mode) or "none" (.hll files only)
@@ -112,12 +127,12 @@ static int run_queries(const std::string& query_file, const std::string& db_file
     const std::string what = smh ? "" : "selection: -q -c " + criterion + ": ";
     selhost_dataset* db = nullptr;
     selhost_dataset* qs = nullptr;
-    if (selhost_dataset_load(&db, db_file.c_str(), m, p_aux, fp_mode, threads)) {
+    if (selhost_dataset_load(&db, db_file.c_str(), m, aux_files(p_aux), fp_mode, threads)) {
         if (!smh) std::cerr << what << "cannot read database list '" << db_file << "': ";
         std::cerr << selhost_last_error() << "\n";
         return 1;
     }
-    if (selhost_dataset_load(&qs, query_file.c_str(), m, p_aux, fp_mode, threads)) {
+    if (selhost_dataset_load(&qs, query_file.c_str(), m, aux_files(p_aux), fp_mode, threads)) {
         if (!smh) std::cerr << what << "cannot read query list '" << query_file << "': ";
         std::cerr << selhost_last_error() << "\n";
         selhost_dataset_free(db);
@@ -140,8 +155,8 @@ static int run_queries(const std::string& query_file, const std::string& db_file
     r = selhip_ctx_upload(ctx, selhost_dataset_hll(db), m ? selhost_dataset_aux(db) : no_smh.data(), selhost_dataset_cards(db), n_db,
                           m ? (int)m : 1, 14);
     if (!r) r = selhip_ctx_upload_queries(ctx, selhost_dataset_hll(qs), m ? selhost_dataset_aux(qs) : no_smh.data(), selhost_dataset_cards(qs), n_qs);
-    if (!r && p_aux) r = selhip_ctx_upload_aux_hll(ctx, selhost_dataset_aux_hll(db), (int)p_aux);
-    if (!r && p_aux) r = selhip_ctx_upload_queries_aux_hll(ctx, selhost_dataset_aux_hll(qs), (int)p_aux);
+    if (!r && p_aux) r = load_aux_hll(ctx, db, p_aux, false);
+    if (!r && p_aux) r = load_aux_hll(ctx, qs, p_aux, true);
     if (!r) r = selhip_ctx_set_criterion(ctx, crit);
     if (!r && smh_c) r = set_count_thresholds(ctx, min_matches);
     if (!r) r = selhip_ctx_set_measure(ctx, measure);
@@ -174,7 +189,7 @@ static int run_neighbours(const std::string& list_file, int crit, float threshol
     const unsigned m = reads_smh ? (unsigned)aux_bytes / 8 : 0;
     const unsigned p_aux = reads_smh || crit == SELHIP_CRIT_NONE ? 0 : (unsigned)__builtin_ctz(aux_bytes ? aux_bytes : 1);
     selhost_dataset* ds = nullptr;
-    if (selhost_dataset_load(&ds, list_file.c_str(), m, p_aux, fp_mode, threads)) { std::cerr << selhost_last_error() << "\n"; return 1; }
+    if (selhost_dataset_load(&ds, list_file.c_str(), m, aux_files(p_aux), fp_mode, threads)) { std::cerr << selhost_last_error() << "\n"; return 1; }
     const int64_t n = selhost_dataset_size(ds);
     int n_rows = 1, n_bands = 1;
     if (m) selhost_banding(m, threshold, SELHOST_BANDING_CPU, &n_rows, &n_bands);
@@ -189,7 +204,7 @@ static int run_neighbours(const std::string& list_file, int crit, float threshol
     }
     selhip_ctx_set_fp_mode(ctx, fp_mode);
     r = selhip_ctx_upload(ctx, selhost_dataset_hll(ds), m ? selhost_dataset_aux(ds) : no_smh.data(), selhost_dataset_cards(ds), n, m ? (int)m : 1, 14);
-    if (!r && p_aux) r = selhip_ctx_upload_aux_hll(ctx, selhost_dataset_aux_hll(ds), (int)p_aux);
+    if (!r && p_aux) r = load_aux_hll(ctx, ds, p_aux, false);
     if (!r) r = selhip_ctx_set_criterion(ctx, crit);
     if (!r && crit == SELHIP_CRIT_SMH_C) r = set_count_thresholds(ctx, min_matches);
     if (!r) r = selhip_ctx_set_measure(ctx, measure);
@@ -279,7 +294,7 @@ int main(int argc, char* argv[]) {
     bool cmin_given = false, gamma_given = false, value_given = false, rounds_given = false;
     std::string rounds_arg = "";
     int c;
-    while ((c = getopt(argc, argv, "xl:b:a:h:c:C:G:t:g:nA:F:B:o:r:q:k:K:p:M:UE:S:V:R:")) != -1) {
+    while ((c = getopt(argc, argv, "xl:b:a:h:c:C:G:t:g:nA:F:B:o:r:q:k:K:p:M:UE:S:V:R:D")) != -1) {
         switch (c) {
             case 'x': std::cout << "Usage: -l -h -a -b [-c smh_a|hll_a|hll_an|none|smh_c -C c_min|-G gamma] [-t threads] [-g gpus] [-n] [-A auto|stream|sig] [-F 0|1] [-B block] [-o file] | -r file\n"
                                    "       -l db_list -q query_list -h -a [-c smh_a|hll_a|hll_an|none|smh_c -C c_min|-G gamma] [-n] [-A auto|stream|sig|index] [-F 0|1] [-k best_per_query]   (query-vs-database selection)\n"
@@ -291,7 +306,8 @@ int main(int argc, char* argv[]) {
                                    "       ... -n -S max_containment [-c smh_a|none|smh_c]   (with -l, -q, -p, -k, -K: select and print I / min(e1, e2), the share of the smaller genome found in the larger)\n"
                                    "       -l list [-q query_list] -M out.tsv -S intersection|containment|max_containment   (the table of I = e1 + e2 - U, I / e_row or I / min(e_row, e_col))\n"
                                    "       ... -c smh_c -C c_min|-G gamma -a bytes -V smh|hll   (with -l, -q, -p, -k, -K, -n, -S max_containment, -o: -V smh tests and prints the SuperMinHash estimate of the count, c / m, with no HLL stage)\n"
-                                   "       -l list -K best_per_genome -c smh_c -C c_min|-G gamma -a bytes -V smh -R rows|auto   (the same list in rounds of rows: memory for n K records and one round, not for every pair that shares a bucket)\n"; return 0;
+                                   "       -l list -K best_per_genome -c smh_c -C c_min|-G gamma -a bytes -V smh -R rows|auto   (the same list in rounds of rows: memory for n K records and one round, not for every pair that shares a bucket)\n"
+                                   "       ... -c hll_a|hll_an -a bytes -D   (with -l, -q, -p, -k, -K, -g, -B: no .hll_<p> file is read, the auxiliary HLL sketches are folded from the .hll registers)\n"; return 0;
             case 'q': query_file = optarg; break;
             case 'p': pair_file = optarg; break;
             case 'M': matrix_file = optarg; matrix_given = true; break;
@@ -300,6 +316,7 @@ int main(int argc, char* argv[]) {
             case 'S': measure_name = optarg; measure_given = true; break;
             case 'V': value_estimator = optarg; value_given = true; break;
             case 'R': rounds_arg = optarg; rounds_given = true; break;
+            case 'D': g_fold_aux = true; break;
             case 'k': top_k = std::strtoll(optarg, nullptr, 10); topk_given = true; break;
             case 'K': nbr_k = std::strtoll(optarg, nullptr, 10); nbr_given = true; break;
             case 'B': ooc_block = std::stoll(optarg); break;
@@ -318,6 +335,20 @@ int main(int argc, char* argv[]) {
             case 'A': if (!selection_opt) selection_opt = "-A"; algo = !strcmp(optarg, "stream") ? SELHIP_ALGO_STREAM : !strcmp(optarg, "sig") ? SELHIP_ALGO_SIG : !strcmp(optarg, "hashjoin") ? SELHIP_ALGO_HASHJOIN : !strcmp(optarg, "index") ? SELHIP_ALGO_INDEX : SELHIP_ALGO_AUTO; break;
             case 'F': fp_mode = std::stoi(optarg) ? SELHIP_FP_FMA : SELHIP_FP_STRICT; break;
             default: break;
+        }
+    }
+    // -D: checked before any file is read or device opened
+    if (g_fold_aux) {
+        if (matrix_given) { std::cerr << "selection: -D (fold the auxiliary HLL sketches) cannot be combined with -M; the dense similarity matrix reads no auxiliary sketch\n"; return 2; }
+        if (!dump_file.empty()) { std::cerr << "selection: -D (fold the auxiliary HLL sketches) cannot be combined with -r; printing a result file reads no sketch\n"; return 2; }
+        if (criterion != "hll_a" && criterion != "hll_an") {
+            std::cerr << "selection: -D folds the auxiliary HLL sketches of -c hll_a | hll_an; -c " << criterion << " reads none\n";
+            return 2;
+        }
+        const int p_fold = __builtin_ctz(aux_bytes ? aux_bytes : 1);
+        if (p_fold < 4 || p_fold > 14) {
+            std::cerr << "selection: -D: the auxiliary precision ctz(-a " << aux_bytes << ") = " << p_fold << " must be in 4..14 (the .hll registers have p = 14)\n";
+            return 2;
         }
     }
     // -V: checked before any file is read or device opened
@@ -515,9 +546,17 @@ int main(int argc, char* argv[]) {
     const unsigned p_aux = reads_smh || crit == SELHIP_CRIT_NONE ? 0 : (unsigned)__builtin_ctz(aux_bytes ? aux_bytes : 1);   // :125
 
     selhost_dataset* ds = nullptr;
-    int rc = selhost_dataset_load(&ds, list_file.c_str(), m, p_aux, fp_mode, threads);
+    int rc = selhost_dataset_load(&ds, list_file.c_str(), m, aux_files(p_aux), fp_mode, threads);
     if (rc) { std::cerr << selhost_last_error() << "\n"; exit(-1); }
     const int64_t n = selhost_dataset_size(ds);
+    // the auxiliary HLL array of the drivers that take host arrays (-B, -g): the files', or under -D the host fold of the .hll registers
+    std::vector<uint8_t> folded;
+    const uint8_t* aux_hll_host = p_aux ? selhost_dataset_aux_hll(ds) : nullptr;
+    if (g_fold_aux && p_aux && (ooc_block > 0 || n_gpus > 1)) {
+        folded.resize(std::max<size_t>(1, (size_t)n << p_aux));
+        if (selhost_hll_fold(selhost_dataset_hll(ds), n, 14, p_aux, folded.data())) { std::cerr << "selection: -D: " << selhost_last_error() << "\n"; return 5; }
+        aux_hll_host = folded.data();
+    }
 
     int n_rows = 1, n_bands = 1;
     if (m) selhost_banding(m, threshold, SELHOST_BANDING_CPU, &n_rows, &n_bands);
@@ -538,7 +577,7 @@ int main(int argc, char* argv[]) {
         for (int attempt = 0; attempt < 2; ++attempt) {
             parts[0].resize((size_t)cap);
             int r = selhip_ooc_select(0, selhost_dataset_hll(ds), aux_ptr, selhost_dataset_cards(ds),
-                                      p_aux ? selhost_dataset_aux_hll(ds) : nullptr, (int)p_aux, crit, n, m_up, 14,
+                                      aux_hll_host, (int)p_aux, crit, n, m_up, 14,
                                       mode, algo, fp_mode, threshold, n_rows, n_bands, ooc_block, 2, parts[0].data(), cap, &cnt, nullptr);
             if (r == SELHIP_E_OVERFLOW && attempt == 0) { cap = cnt; continue; }
             if (r) { std::cerr << "selection: " << selhip_last_error(nullptr) << "\n"; return 4; }
@@ -555,7 +594,7 @@ int main(int argc, char* argv[]) {
         for (int attempt = 0; attempt < 2; ++attempt) {
             parts[0].resize((size_t)cap);
             int r = selhip_multi_select(devs.data(), n_gpus, selhost_dataset_hll(ds), aux_ptr, selhost_dataset_cards(ds),
-                                        p_aux ? selhost_dataset_aux_hll(ds) : nullptr, (int)p_aux, crit, n, m_up, 14,
+                                        aux_hll_host, (int)p_aux, crit, n, m_up, 14,
                                         mode, algo, fp_mode, threshold, n_rows, n_bands, SELHIP_GATHER_RCCL_OR_HOST,
                                         parts[0].data(), cap, &cnt, nullptr);
             if (r == SELHIP_E_OVERFLOW && attempt == 0) { cap = cnt; continue; }
@@ -571,7 +610,7 @@ int main(int argc, char* argv[]) {
         if (r) { std::cerr << "selection: " << selhip_last_error(nullptr) << "\n"; return 4; }
         selhip_ctx_set_fp_mode(ctx, fp_mode);
         r = selhip_ctx_upload(ctx, selhost_dataset_hll(ds), aux_ptr, selhost_dataset_cards(ds), n, m_up, 14);
-        if (!r && p_aux) r = selhip_ctx_upload_aux_hll(ctx, selhost_dataset_aux_hll(ds), (int)p_aux);
+        if (!r && p_aux) r = load_aux_hll(ctx, ds, p_aux, false);
         if (!r) r = selhip_ctx_set_criterion(ctx, crit);
         if (!r && crit == SELHIP_CRIT_SMH_C) r = set_count_thresholds(ctx, (int)min_matches);
         if (!r) r = selhip_ctx_set_measure(ctx, pass_measure);

@@ -41,6 +41,10 @@
 //                       pass's for both of their genomes --, radix select of each owner's K best, bitonic sort of the winners
 //   kernel_query_aux.cuh the auxiliary-HLL criteria of query passes: hll_a / hll_an over each query's CB window, the hll_a stage
 //                       of hll_a + smh_a over the smh_a survivors
+//   hll_fold.hpp        selhip::fold_contrib / fold_combine: how a register of precision p folds into the sketch of a lower precision
+//                       (shared with libselhost.so, like ertl_mle.hpp)
+//   kernel_fold.cuh     hll_fold_kernel: the auxiliary HLL sketches folded from the main registers, one streaming read (in a lane, across
+//                       the lanes of a load, across the loads of a wave)
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (see csrc/Makefile).
 #include <hip/hip_runtime.h>
@@ -67,6 +71,7 @@
 #include "ertl_mle.hpp"
 #include "pair_value.hpp"      // the value of a pair under every HLL measure (J, intersection, containments): one definition
 #include "synth.hpp"
+#include "hll_fold.hpp"        // how a main HLL register folds into the auxiliary sketch of a lower precision: one definition
 
 #include "common.cuh"
 #include "kernel_bounds.cuh"
@@ -85,6 +90,7 @@
 #include "kernel_query_index.cuh"
 #include "kernel_dense.cuh"
 #include "kernel_topk.cuh"
+#include "kernel_fold.cuh"
 
 #include "host_plan.hpp"         // host decisions that are plain arithmetic: build shape, pass plan, criterion constants, overflow rule
 #include "kernel_matrix.cuh"     // (behind host_plan.hpp: the kernel reads the unit, slab and mirror rules written there)

@@ -73,6 +73,20 @@ def load_dataset(list_file: str, m: int, p_aux: int = 0, fp_mode: int = FP_FMA, 
     return Dataset(names, hll, aux, aux_hll, cards, order)
 
 
+def hll_fold(hll: np.ndarray, p_aux: int) -> np.ndarray:
+    """HLL sketches [n, 1 << p] (or one sketch [1 << p]) folded to the lower precision p_aux on the host (selhost_hll_fold): the registers
+    of the .hll_<p_aux> files build_sketch writes beside the .hll files, without reading them.  4 <= p_aux <= min(p, 15)."""
+    hll = np.ascontiguousarray(hll, dtype=np.uint8)
+    rows = hll.reshape(1, -1) if hll.ndim == 1 else hll
+    if rows.ndim != 2 or rows.shape[1] < 16 or rows.shape[1] & (rows.shape[1] - 1):
+        raise ValueError(f"hll must be [n, 1 << p] with p in 4..20, got shape {hll.shape}")
+    p = rows.shape[1].bit_length() - 1
+    out = np.zeros((rows.shape[0], 1 << p_aux) if 0 <= p_aux < 31 else (0, 0), dtype=np.uint8)
+    if host_lib().selhost_hll_fold(rows.ctypes.data, rows.shape[0], p, p_aux, out.ctypes.data) < 0:
+        raise ValueError(host_lib().selhost_last_error().decode())
+    return out[0] if hll.ndim == 1 else out
+
+
 def format_lines(names: Sequence[str], pairs: np.ndarray) -> str:
     """'fn1 fn2 <std::to_string(J)>\\n' per selected pair (selection.cpp:288)."""
     h = host_lib()
@@ -286,6 +300,17 @@ class Selector:
         aux_hll = np.ascontiguousarray(aux_hll, dtype=np.uint8)
         assert aux_hll.shape == (self.n, 1 << p_aux)
         check(self._lib.selhip_ctx_upload_aux_hll(self._ctx, aux_hll.ctypes.data, p_aux), self._ctx)
+
+    def fold_aux_hll(self, p_aux: int):
+        """the auxiliary HLL sketches of upload_aux_hll without their files: folded on the device from the main sketches the context
+        holds, uploaded or attached (selhip_ctx_fold_aux_hll); p_aux in 4 .. min(p_hll, 15).  A snapshot: fold again after new sketches"""
+        check(self._lib.selhip_ctx_fold_aux_hll(self._ctx, p_aux), self._ctx)
+        self._keep_aux = None
+
+    def fold_queries_aux_hll(self, p_aux: int):
+        """the same for the query set (selhip_ctx_fold_queries_aux_hll), in place of upload_queries_aux_hll"""
+        check(self._lib.selhip_ctx_fold_queries_aux_hll(self._ctx, p_aux), self._ctx)
+        self._keep_q_aux = None
 
     def attach_aux_hll(self, aux_hll_t, p_aux: int):
         assert aux_hll_t.is_cuda and aux_hll_t.is_contiguous() and tuple(aux_hll_t.shape) == (self.n, 1 << p_aux)
@@ -632,10 +657,19 @@ def _criterion_files(criterion: str, aux_bytes: int, min_matches: Optional[int] 
     raise ValueError("Option -c invalid. The accepted criteria are hll_a, hll_an and smh_a.")
 
 
+def _aux_files(fold_aux: bool, p_aux: int, criterion: str) -> int:
+    """precision of the .hll_<p> files a front end opens: p_aux, or 0 (none) when the context folds them itself (fold_aux)"""
+    if not fold_aux:
+        return p_aux
+    if not p_aux:
+        raise ValueError(f"fold_aux folds the auxiliary HLL sketches of the criteria hll_a / hll_an; criterion '{criterion}' reads none")
+    return 0
+
+
 def select_from_filelist(list_file: str, tau: float, aux_bytes: int, mode: int = MODE_CB_SMH, device: int = 0,
                          fp_mode: int = FP_FMA, algo: int = ALGO_AUTO, criterion: str = "smh_a", top_k: int = 0,
                          min_matches: Optional[int] = None, measure="jaccard", min_containment: Optional[float] = None, estimator="hll",
-                         top_k_rounds=0) -> str:
+                         top_k_rounds=0, fold_aux: bool = False) -> str:
     """The whole of selection_cuda.cpp main() (criterion smh_a) -- and of selection.cpp's hll_a / hll_an
     branches (:122-227): returns the text the CPU reference prints for `-c criterion -a aux_bytes -h tau`.
     criterion "none": no criterion in front of the Jaccard test (CRIT_NONE; mode MODE_CB_SMH = the CB bound alone, MODE_SMH = every pair).
@@ -649,19 +683,23 @@ def select_from_filelist(list_file: str, tau: float, aux_bytes: int, mode: int =
     estimator "smh" (`-V smh`, criterion "smh_c" alone): the value tested and printed is the SuperMinHash estimate of the count,
     smh_value(measure, m, c, e_i, e_k) (Selector.set_estimator), and no HLL stage runs.
     top_k_rounds (`-R rows`, with top_k > 0, criterion "smh_c" and estimator "smh" alone): the pass runs in rounds of that many rows, or
-    "auto" (Selector.set_topk_rounds): the same text."""
+    "auto" (Selector.set_topk_rounds): the same text.
+    fold_aux (`-D`, criteria "hll_a" / "hll_an" alone): no .hll_<p> file is opened; the context folds the auxiliary sketches from the
+    .hll registers on the device (Selector.fold_aux_hll): the same text."""
     meas = _pass_measure(measure, mode, criterion)
     est = _pass_estimator(estimator, criterion)
     rounds = topk_rounds_code(top_k_rounds)
     if rounds and not (top_k and criterion == "smh_c" and est == ESTIMATOR_SMH):
         raise ValueError("top_k_rounds takes top_k > 0, criterion 'smh_c' and estimator 'smh'")
     m, p_aux, crit = _criterion_files(criterion, aux_bytes, min_matches, min_containment)
-    ds = load_dataset(list_file, m, p_aux, fp_mode)
+    ds = load_dataset(list_file, m, _aux_files(fold_aux, p_aux, criterion), fp_mode)
     n_rows, n_bands = banding(m, tau) if m else (1, 1)
     with Selector(device, fp_mode) as sel:
         aux = ds.aux if m else np.zeros((len(ds.names), 1), dtype=np.uint64)
         sel.upload(ds.hll, aux, ds.cards)
-        if p_aux:
+        if fold_aux:
+            sel.fold_aux_hll(p_aux)
+        elif p_aux:
             sel.upload_aux_hll(ds.aux_hll, p_aux)
         sel.set_criterion(crit)
         if crit == CRIT_SMH_C:
@@ -776,18 +814,22 @@ def read_pair_list(pair_file: str, names: Sequence[str]) -> np.ndarray:
 
 def select_pairs_from_filelist(list_file: str, pair_file: str, tau: float, aux_bytes: int, mode: int = MODE_CB_SMH, device: int = 0,
                                fp_mode: int = FP_FMA, algo: int = ALGO_AUTO, criterion: str = "smh_a",
-                               min_matches: Optional[int] = None, measure="jaccard", min_containment: Optional[float] = None, estimator="hll") -> str:
+                               min_matches: Optional[int] = None, measure="jaccard", min_containment: Optional[float] = None, estimator="hll",
+                               fold_aux: bool = False) -> str:
     """select_from_filelist restricted to the pairs listed in pair_file (lines 'path1 path2[ anything]' with paths of list_file, in
-    either order): the text `selection -l list_file -p pair_file -c criterion -a aux_bytes -h tau` prints (measure as there: `-S`)"""
+    either order): the text `selection -l list_file -p pair_file -c criterion -a aux_bytes -h tau` prints (measure as there: `-S`;
+    fold_aux as there: `-D`)"""
     meas = _pass_measure(measure, mode, criterion)
     est = _pass_estimator(estimator, criterion)
     m, p_aux, crit = _criterion_files(criterion, aux_bytes, min_matches, min_containment)
-    ds = load_dataset(list_file, m, p_aux, fp_mode)
+    ds = load_dataset(list_file, m, _aux_files(fold_aux, p_aux, criterion), fp_mode)
     listed = read_pair_list(pair_file, ds.names)
     n_rows, n_bands = banding(m, tau) if m else (1, 1)
     with Selector(device, fp_mode) as sel:
         sel.upload(ds.hll, ds.aux if m else np.zeros((len(ds.names), 1), dtype=np.uint64), ds.cards)
-        if p_aux:
+        if fold_aux:
+            sel.fold_aux_hll(p_aux)
+        elif p_aux:
             sel.upload_aux_hll(ds.aux_hll, p_aux)
         sel.set_criterion(crit)
         if crit == CRIT_SMH_C:
@@ -866,25 +908,31 @@ def ooc_select(hll: np.ndarray, aux: np.ndarray, cards: np.ndarray, tau: float, 
 
 def query_from_filelists(query_list: str, db_list: str, tau: float, aux_bytes: int, mode: int = MODE_CB_SMH, fp_mode: int = FP_FMA,
                          device: int = 0, algo: int = ALGO_AUTO, criterion: str = "smh_a", top_k: int = 0,
-                         min_matches: Optional[int] = None, measure="jaccard", min_containment: Optional[float] = None, estimator="hll") -> str:
+                         min_matches: Optional[int] = None, measure="jaccard", min_containment: Optional[float] = None, estimator="hll",
+                         fold_aux: bool = False) -> str:
     """Query-vs-database selection: both lists are loaded and sorted by cardinality (load_dataset); returns one line
     'query_path db_path J' per selected pair, in (query rank, database rank) order, J formatted as selection.cpp prints it.
     top_k > 0: only every query's top_k best pairs, in ranked order (query rank, then J descending, ties by database rank).
     criterion "smh_a" (m = aux_bytes / 8 buckets), "hll_a" / "hll_an" (auxiliary HLL p = ctz(aux_bytes), as select_from_filelist) or
     "none" (every pair of the CB windows -- MODE_SMH: every cross pair -- to the Jaccard test) or "smh_c" with min_matches = c (at least
     c of the m = aux_bytes / 8 buckets equal).  measure "max_containment": the value tested and printed is I / min(e_q, e_d)
-    (Selector.set_measure; ValueError with mode=MODE_CB_SMH or an hll_* criterion)."""
+    (Selector.set_measure; ValueError with mode=MODE_CB_SMH or an hll_* criterion).  fold_aux (`-D`): the auxiliary sketches of both
+    sets are folded from their .hll registers on the device, no .hll_<p> file is opened (as select_from_filelist)."""
     meas = _pass_measure(measure, mode, criterion)
     est = _pass_estimator(estimator, criterion)
     m, p_aux, crit = _criterion_files(criterion, aux_bytes, min_matches, min_containment)
-    qs = load_dataset(query_list, m, p_aux, fp_mode)
-    db = load_dataset(db_list, m, p_aux, fp_mode)
+    p_files = _aux_files(fold_aux, p_aux, criterion)
+    qs = load_dataset(query_list, m, p_files, fp_mode)
+    db = load_dataset(db_list, m, p_files, fp_mode)
     n_rows, n_bands = banding(m, tau) if m else (1, 1)
     with Selector(device, fp_mode) as sel:
         # (hll_a / hll_an read no SuperMinHash buckets: a one-bucket placeholder, as select_from_filelist uploads)
         sel.upload(db.hll, db.aux if m else np.zeros((len(db.names), 1), dtype=np.uint64), db.cards)
         sel.upload_queries(qs.hll, qs.aux if m else np.zeros((len(qs.names), 1), dtype=np.uint64), qs.cards)
-        if p_aux:
+        if fold_aux:
+            sel.fold_aux_hll(p_aux)
+            sel.fold_queries_aux_hll(p_aux)
+        elif p_aux:
             sel.upload_aux_hll(db.aux_hll, p_aux)
             sel.upload_queries_aux_hll(qs.aux_hll, p_aux)
         sel.set_criterion(crit)

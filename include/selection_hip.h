@@ -256,6 +256,15 @@ int selhip_ctx_attach(selhip_ctx* ctx, const uint8_t* d_hll, const uint64_t* d_a
  * call after upload/attach of the primary sketches.  attach: device pointer owned by the caller. */
 int selhip_ctx_upload_aux_hll(selhip_ctx* ctx, const uint8_t* h_aux_hll, int p_aux);
 int selhip_ctx_attach_aux_hll(selhip_ctx* ctx, const uint8_t* d_aux_hll, int p_aux);
+/* The same sketches without the .hll_<p> files: the context FOLDS them on the device from the main sketches it holds, uploaded or
+ * attached, into a buffer it owns (hll_fold_kernel, see selhip_hll_fold in section 3: bit for bit the registers build_sketch writes
+ * for p_aux from the same FASTA).  It leaves the context exactly as selhip_ctx_upload_aux_hll with that array would.  p_aux in
+ * 4 .. min(p_hll, 15): SELHIP_E_BADARG with a message outside; SELHIP_E_STATE before upload / attach of the main sketches and while
+ * a pass is pending.  Runs on the context's stream and returns when the sketches are there.  Like an upload it is replaced by the
+ * next upload / attach / fold of auxiliary sketches.  It is a SNAPSHOT of the main sketches at the call and is NOT refreshed: a later
+ * upload / attach of main sketches drops it like any auxiliary array (fold again), and rewriting an attached main buffer in place
+ * leaves it stale, just as the bit planes and cards taken at selhip_ctx_attach are. */
+int selhip_ctx_fold_aux_hll(selhip_ctx* ctx, int p_aux);
 /* criterion used by the following selhip_ctx_run* calls (default SELHIP_CRIT_SMH_A); n_rows/n_bands are
  * ignored by HLL_A / HLL_AN / NONE (NONE ignores algo too and needs no auxiliary HLL sketches) */
 int selhip_ctx_set_criterion(selhip_ctx* ctx, int criterion);
@@ -509,6 +518,10 @@ int selhip_ctx_attach_queries(selhip_ctx* ctx, const uint8_t* d_hll, const uint6
  * The pointer may be NULL when n_q == 0. */
 int selhip_ctx_upload_queries_aux_hll(selhip_ctx* ctx, const uint8_t* h_aux_hll, int p_aux);
 int selhip_ctx_attach_queries_aux_hll(selhip_ctx* ctx, const uint8_t* d_aux_hll, int p_aux);
+/* selhip_ctx_fold_aux_hll for the query set: its auxiliary sketches folded on the device from the queries' main sketches into a buffer
+ * the context owns, under the rules of selhip_ctx_upload_queries_aux_hll (SELHIP_E_STATE before the queries are loaded or while a pass
+ * is pending, SELHIP_E_BADARG with a message for p_aux outside 4..14; dropped by the next upload / attach of queries or database). */
+int selhip_ctx_fold_queries_aux_hll(selhip_ctx* ctx, int p_aux);
 /* One query pass, synchronous like selhip_ctx_run; SELHIP_E_STATE before any queries are loaded. */
 int selhip_ctx_run_queries(selhip_ctx* ctx, int mode, int algo, float tau_f, int n_rows, int n_bands);
 
@@ -693,6 +706,14 @@ int selhip_ertl_estimate(const uint32_t* d_counts, int64_t n, int p, int fp_mode
  * pair as a dense array is SELHIP_MEASURE_SMH_MATCHES of section 2f; this entry stays as the independent check of it. */
 int selhip_smh_match_counts(const uint64_t* d_aux, int m, const selhip_int2_t* d_pairs, int64_t n_pairs,
                             int32_t* d_matches, void* hip_stream);
+/* HLL sketches of precision p folded to the lower precision p_aux: d_out[n][1 << p_aux] u8 from d_hll[n][1 << p] u8 (csrc/hll_fold.hpp,
+ * csrc/kernel_fold.cuh).  With d = p - p_aux,
+ *   out[g] = max over t in [0, 2^d) with r = in[(g << d) | t], r != 0 of ( t == 0 ? d + r : d - floor(log2 t) )      (0 if every r is 0)
+ * which is the sketch the reference's hll_t (hll.h:886-888) builds at p_aux from the same hashes, bit for bit -- the .hll_<p_aux> file
+ * beside a .hll file.  p in 4 .. 20, p_aux in 4 .. min(p, 15) (p_aux == p copies); SELHIP_E_BADARG outside, for a negative n, and with
+ * n > 0 for a null pointer or one that is not 16-byte aligned.  n == 0 launches nothing.  Registers above 64 - p + 1 cannot come from
+ * a sketch builder: what they fold to is unspecified, and nothing validates them.  Asynchronous on hip_stream. */
+int selhip_hll_fold(const uint8_t* d_hll, int64_t n_genomes, int p, int p_aux, uint8_t* d_out, void* hip_stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * 4. Synthetic sketches generated directly in HBM (csrc/synth.hpp; stands in for the FASTA->sketch

@@ -133,6 +133,14 @@ int selhost_synth_generate(const selhost_synth_t* sp, int64_t g_begin, int64_t g
  * bounds[parts+1] receives the row boundaries. */
 int selhost_shard_rows(int64_t n, const int32_t* hi, int64_t z0, int parts, int64_t* bounds);
 
+/* ---- auxiliary HLL sketches without their files (host twin of selhip_hll_fold; the rule is csrc/hll_fold.hpp) ----------
+ * out[n][1 << p_aux] = the sketches in[n][1 << p] folded to the lower precision p_aux: with d = p - p_aux,
+ *   out[g] = max over t in [0, 2^d) with r = in[(g << d) | t], r != 0 of ( t == 0 ? d + r : d - floor(log2 t) )   (0 if every r is 0)
+ * -- bit for bit the registers of the .hll_<p_aux> file build_sketch writes beside a .hll file (hll.h:886-888: register and rank
+ * are functions of the hash alone).  4 <= p <= 20, 4 <= p_aux <= min(p, 15) (p_aux == p copies), SELHOST_E_BADARG otherwise.
+ * For the drivers that take host arrays (selhip_multi_select, selhip_ooc_select) and for use without a GPU. */
+int selhost_hll_fold(const uint8_t* in, int64_t n, unsigned p, unsigned p_aux, uint8_t* out);
+
 const char* selhost_version(void);
 
 #ifdef __cplusplus

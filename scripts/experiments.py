@@ -10,7 +10,7 @@
   experiments.py time -l LIST | -N GENOMES [-m BUCKETS ...] [-h TAU] [-R REPS] [-t THREADS] [-o experiment_smh.csv]
       impl,threads,mh_size,rep,criterio,tiempo    rows for cpu (oracle library: the OpenMP loop of selection.cpp:270-291,
       modes smh_a and CB+smh_a of time_smh.cpp) and gpu (bin/time_smh_hip records `list;label;tau;seconds`)
-  experiments.py recall -l LIST [-a AUX_BYTES] | --cfg NAME [-N GENOMES]  [-h TAU ...] [-c CRITERION ...] [--modes cb nocb] [--min-matches C ...] [--min-containment G ...] [-o recall.csv]
+  experiments.py recall -l LIST [-a AUX_BYTES] | --cfg NAME [-N GENOMES]  [-h TAU ...] [-c CRITERION ...] [--modes cb nocb] [--min-matches C ...] [--min-containment G ...] [-p P_AUX] [--fold -p P_AUX ...] [-o recall.csv]
       what every criterion loses against the pass without one (criterion none: every pair inside the CB bound, or every pair, to the
       HLL-14 Jaccard test), on the MI355X, for a file list or a synthetic configuration of synth.py:
           cfg,criterion,aux,tau,mode,selected,exhaustive,missed,recall,ms_criterion,ms_exhaustive
@@ -20,6 +20,9 @@
       min_matches(m, tau), the count at which the SuperMinHash estimate c / m reaches tau.  --min-containment G ...: smh_c with its
       per-pair threshold for a minimum containment G (Selector.set_min_containment), one row per G, "aux" = m<m>g<G>; with
       --min-matches as well, one row per (C, G), C the floor under the per-pair threshold, "aux" = m<m>c<C>g<G>.
+      --fold: the auxiliary HLL sketches of hll_a, hll_an and hll_a+smh_a are folded on the device from the main registers
+      (Selector.fold_aux_hll) instead of read from .hll_<p> files or generated: their rows are produced for EVERY precision given
+      with -p (4 .. 14), from the .hll files alone; the rows of the other criteria come once.
 """
 import argparse
 import csv
@@ -172,6 +175,10 @@ def recall(args):
     import cuda_selection_criteria_amd as pkg
     need_aux = any(c not in ("smh_a", "smh_c") for c in args.c)
     need_smh = any(c in ("smh_a", "hll_a+smh_a", "smh_c") for c in args.c)
+    if len(args.p) > 1 and not args.fold:
+        sys.exit("recall: several -p precisions need --fold (without it the one precision's .hll_<p> files are read)")
+    fold_ps = args.p if args.fold and need_aux else []
+    args.p = 0 if fold_ps else args.p[0]                                 # (folding: no auxiliary file is read, none is generated)
     with pkg.Selector(0) as sel:
         if args.l:
             m = args.a // 8 if need_smh else 0
@@ -192,7 +199,15 @@ def recall(args):
             sel.attach(keep[0], keep[1], keep[2])
             if p_aux:
                 sel.attach_aux_hll(keep[4], p_aux)
-        rows = recall_rows(sel, name, n, m, p_aux, [float(t) for t in args.tau], args.c, args.modes, args.min_matches, args.min_containment)
+        taus = [float(t) for t in args.tau]
+        if fold_ps:
+            rows = []
+            for idx, p_fold in enumerate(fold_ps):
+                sel.fold_aux_hll(p_fold)
+                crits = [c for c in args.c if idx == 0 or c not in ("smh_a", "smh_c")]
+                rows += recall_rows(sel, name, n, m, p_fold, taus, crits, args.modes, args.min_matches, args.min_containment)
+        else:
+            rows = recall_rows(sel, name, n, m, p_aux, taus, args.c, args.modes, args.min_matches, args.min_containment)
     with open(args.o, "w", newline="") as f:
         w = csv.writer(f)
         w.writerow(RECALL_HEADER)
@@ -215,7 +230,7 @@ def main():
     t.add_argument("-o", default="experiment_smh_comparative.csv")
     rc = sub.add_parser("recall", add_help=False)
     rc.add_argument("-l", default=""); rc.add_argument("--cfg", default=""); rc.add_argument("-N", type=int, default=0)
-    rc.add_argument("-a", type=int, default=2048); rc.add_argument("-p", type=int, default=8)
+    rc.add_argument("-a", type=int, default=2048); rc.add_argument("-p", type=int, nargs="+", default=[8]); rc.add_argument("--fold", action="store_true")
     rc.add_argument("-h", dest="tau", nargs="+", default=["0.9"]); rc.add_argument("-c", nargs="+", default=list(RECALL_CRITERIA), choices=list(RECALL_CRITERIA))
     rc.add_argument("--modes", nargs="+", default=["cb"], choices=["cb", "nocb"]); rc.add_argument("-o", default="recall.csv")
     rc.add_argument("--min-matches", dest="min_matches", type=int, nargs="+", default=[])
