@@ -76,6 +76,16 @@
 //               registers of the files, so the same output), for any p in 4..14.  With -l, -q (both lists), -p, -k, -K; with -g and
 //               -B the host twin (selhost_hll_fold) folds the array handed to the drivers.  Not with -c smh_a | smh_c | none (they
 //               read no auxiliary HLL sketch), -M or -r
+//   -L <file>   behind the selection pass: its single-linkage clusters, computed on the device from the result list (selhip_ctx_cluster)
+//               and written to <file>, one line per genome of the -l list in file-list order:
+//               path <TAB> cluster <TAB> cluster_size <TAB> degree <TAB> representative_path   (cluster: dense id by ascending smallest
+//               rank; degree: records the genome appears in).  Stdout stays byte for byte what it is without -L.  With -l under every
+//               -c, with -p, and with -K (with or without -R: the k-NN graph, directed records as undirected edges); one device -- not
+//               combinable with -q (two index spaces), -M, -g, -B (their lists live on the host) or -r
+//   -T <value>  with -L: only the selected pairs whose printed value is at least this (f64) are edges -- one pass at a low -h can be
+//               clustered at several levels; default: every selected pair
+//   -Y <rule>   with -L: the representative of a cluster: max_degree (default; most records, ties to the smaller rank), min_rank (the
+//               smallest genome) or max_rank (the largest)
 //   -x          usage
 #include <unistd.h>
 
@@ -84,6 +94,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
 #include <iostream>
 #include <string>
 #include <vector>
@@ -97,6 +108,42 @@ static double g_min_containment = std::nan("");
 static int g_estimator = SELHIP_ESTIMATOR_HLL;
 static bool g_fold_aux = false;                  // -D: the auxiliary HLL sketches are folded from the main ones, no .hll_<p> file is read
 static long long g_topk_rounds = 0;              // -R: rows per round of -K (0: not given, SELHIP_TOPK_ROUNDS_AUTO: auto)
+static std::string g_cluster_file = "";         // -L: the cluster table of the pass's result list goes here ("" = none)
+static double g_cluster_min = -INFINITY;         // -T: records below this value are no edges
+static int g_cluster_rep = SELHIP_REP_MAX_DEGREE;   // -Y
+// -L: behind a finished pass of ctx over the n genomes of ds, the clusters of its result list as a table in file-list order
+static int write_clusters(selhip_ctx* ctx, const selhost_dataset* ds, int64_t n) {
+    if (g_cluster_file.empty()) return 0;
+    std::vector<int32_t> cluster((size_t)n), degree((size_t)n), size((size_t)n), rep((size_t)n);
+    selhip_clusters_t out{nullptr, nullptr, nullptr, nullptr, nullptr};
+    void* d = nullptr;
+    int64_t n_clusters = 0;
+    int r = n ? selhip_malloc(&d, (size_t)n * 4 * sizeof(int32_t)) : 0;
+    if (!r && n) {
+        int32_t* base = static_cast<int32_t*>(d);
+        out.d_cluster = base; out.d_degree = base + n; out.d_cluster_size = base + 2 * n; out.d_cluster_rep = base + 3 * n;
+    }
+    if (!r) r = selhip_ctx_cluster(ctx, g_cluster_min, g_cluster_rep, &out, &n_clusters);
+    if (!r && n) r = selhip_memcpy_d2h(cluster.data(), out.d_cluster, (size_t)n * sizeof(int32_t));
+    if (!r && n) r = selhip_memcpy_d2h(degree.data(), out.d_degree, (size_t)n * sizeof(int32_t));
+    if (!r && n_clusters) r = selhip_memcpy_d2h(size.data(), out.d_cluster_size, (size_t)n_clusters * sizeof(int32_t));
+    if (!r && n_clusters) r = selhip_memcpy_d2h(rep.data(), out.d_cluster_rep, (size_t)n_clusters * sizeof(int32_t));
+    if (d) selhip_free(d);
+    if (r) return r;
+    std::vector<int64_t> rank_of_line((size_t)n);
+    for (int64_t g = 0; g < n; ++g) rank_of_line[(size_t)selhost_dataset_order(ds, g)] = g;
+    std::ofstream f(g_cluster_file, std::ios::binary);
+    for (int64_t line = 0; line < n; ++line) {
+        const int64_t g = rank_of_line[(size_t)line];
+        const int32_t c = cluster[(size_t)g];
+        f << selhost_dataset_name(ds, g) << '\t' << c << '\t' << size[(size_t)c] << '\t' << degree[(size_t)g] << '\t'
+          << selhost_dataset_name(ds, rep[(size_t)c]) << '\n';
+    }
+    f.close();
+    if (!f) { std::cerr << "selection: -L: cannot write '" << g_cluster_file << "'\n"; return 5; }
+    return 0;
+}
+
 static int set_count_thresholds(selhip_ctx* ctx, int min_matches) {
     int r = min_matches > 0 ? selhip_ctx_set_min_matches(ctx, min_matches) : 0;
     if (!r && !std::isnan(g_min_containment)) r = selhip_ctx_set_min_containment(ctx, g_min_containment);
@@ -215,6 +262,7 @@ static int run_neighbours(const std::string& list_file, int crit, float threshol
         pairs.resize((size_t)selhip_ctx_result_count(ctx));
         r = selhip_ctx_fetch_ranked(ctx, pairs.data(), (int64_t)pairs.size());
     }
+    if (!r) r = write_clusters(ctx, ds, n);
     if (r) std::cerr << "selection: " << selhip_last_error(ctx) << "\n";
     selhip_ctx_destroy(ctx);
     if (!r) {
@@ -292,9 +340,10 @@ int main(int argc, char* argv[]) {
     const char* selection_opt = nullptr;         // the first of -h, -c, -n, -A seen: options of a selection pass, which -M does not run
     long long top_k = 0, nbr_k = 0, min_matches = 0;
     bool cmin_given = false, gamma_given = false, value_given = false, rounds_given = false;
-    std::string rounds_arg = "";
+    std::string rounds_arg = "", cluster_min_arg = "", cluster_rep_arg = "";
+    bool cluster_given = false, cluster_min_given = false, cluster_rep_given = false;
     int c;
-    while ((c = getopt(argc, argv, "xl:b:a:h:c:C:G:t:g:nA:F:B:o:r:q:k:K:p:M:UE:S:V:R:D")) != -1) {
+    while ((c = getopt(argc, argv, "xl:b:a:h:c:C:G:t:g:nA:F:B:o:r:q:k:K:p:M:UE:S:V:R:DL:T:Y:")) != -1) {
         switch (c) {
             case 'x': std::cout << "Usage: -l -h -a -b [-c smh_a|hll_a|hll_an|none|smh_c -C c_min|-G gamma] [-t threads] [-g gpus] [-n] [-A auto|stream|sig] [-F 0|1] [-B block] [-o file] | -r file\n"
                                    "       -l db_list -q query_list -h -a [-c smh_a|hll_a|hll_an|none|smh_c -C c_min|-G gamma] [-n] [-A auto|stream|sig|index] [-F 0|1] [-k best_per_query]   (query-vs-database selection)\n"
@@ -307,6 +356,7 @@ int main(int argc, char* argv[]) {
                                    "       -l list [-q query_list] -M out.tsv -S intersection|containment|max_containment   (the table of I = e1 + e2 - U, I / e_row or I / min(e_row, e_col))\n"
                                    "       ... -c smh_c -C c_min|-G gamma -a bytes -V smh|hll   (with -l, -q, -p, -k, -K, -n, -S max_containment, -o: -V smh tests and prints the SuperMinHash estimate of the count, c / m, with no HLL stage)\n"
                                    "       -l list -K best_per_genome -c smh_c -C c_min|-G gamma -a bytes -V smh -R rows|auto   (the same list in rounds of rows: memory for n K records and one round, not for every pair that shares a bucket)\n"
+                                   "       -l list [-p pair_file | -K best_per_genome [-R rows]] ... -L clusters.tsv [-T min_value] [-Y max_degree|min_rank|max_rank]   (besides the output: the single-linkage clusters of the selected pairs, one line per genome: path, cluster, size, degree, representative)\n"
                                    "       ... -c hll_a|hll_an -a bytes -D   (with -l, -q, -p, -k, -K, -g, -B: no .hll_<p> file is read, the auxiliary HLL sketches are folded from the .hll registers)\n"; return 0;
             case 'q': query_file = optarg; break;
             case 'p': pair_file = optarg; break;
@@ -317,6 +367,9 @@ int main(int argc, char* argv[]) {
             case 'V': value_estimator = optarg; value_given = true; break;
             case 'R': rounds_arg = optarg; rounds_given = true; break;
             case 'D': g_fold_aux = true; break;
+            case 'L': g_cluster_file = optarg; cluster_given = true; break;
+            case 'T': cluster_min_arg = optarg; cluster_min_given = true; break;
+            case 'Y': cluster_rep_arg = optarg; cluster_rep_given = true; break;
             case 'k': top_k = std::strtoll(optarg, nullptr, 10); topk_given = true; break;
             case 'K': nbr_k = std::strtoll(optarg, nullptr, 10); nbr_given = true; break;
             case 'B': ooc_block = std::stoll(optarg); break;
@@ -335,6 +388,38 @@ int main(int argc, char* argv[]) {
             case 'A': if (!selection_opt) selection_opt = "-A"; algo = !strcmp(optarg, "stream") ? SELHIP_ALGO_STREAM : !strcmp(optarg, "sig") ? SELHIP_ALGO_SIG : !strcmp(optarg, "hashjoin") ? SELHIP_ALGO_HASHJOIN : !strcmp(optarg, "index") ? SELHIP_ALGO_INDEX : SELHIP_ALGO_AUTO; break;
             case 'F': fp_mode = std::stoi(optarg) ? SELHIP_FP_FMA : SELHIP_FP_STRICT; break;
             default: break;
+        }
+    }
+    // -L and its -T, -Y: checked before any file is read or device opened
+    if ((cluster_min_given || cluster_rep_given) && !cluster_given) {
+        std::cerr << "selection: " << (cluster_min_given ? "-T (the smallest value of an edge)" : "-Y (the representative of a cluster)")
+                  << " is an option of -L (the clusters of the selected pairs)\n";
+        return 2;
+    }
+    if (cluster_given) {
+        const char* clash = !query_file.empty() ? "-q" : matrix_given ? "-M" : gpus_given ? "-g" : ooc_block != 0 ? "-B" : !dump_file.empty() ? "-r" : nullptr;
+        if (clash) {
+            std::cerr << "selection: -L (the clusters of the selected pairs) cannot be combined with " << clash
+                      << "; it clusters the result list one all-pairs or pair-list pass leaves on one device\n";
+            return 2;
+        }
+        if (g_cluster_file.empty()) { std::cerr << "selection: -L needs the name of the file to write\n"; return 2; }
+        if (cluster_min_given) {
+            char* end = nullptr;
+            g_cluster_min = std::strtod(cluster_min_arg.c_str(), &end);
+            if (cluster_min_arg.empty() || *end || std::isnan(g_cluster_min)) {
+                std::cerr << "selection: -T (with -L: the smallest value of an edge) must be a number, not '" << cluster_min_arg << "'\n";
+                return 2;
+            }
+        }
+        if (cluster_rep_given) {
+            if (cluster_rep_arg == "max_degree") g_cluster_rep = SELHIP_REP_MAX_DEGREE;
+            else if (cluster_rep_arg == "min_rank") g_cluster_rep = SELHIP_REP_MIN_RANK;
+            else if (cluster_rep_arg == "max_rank") g_cluster_rep = SELHIP_REP_MAX_RANK;
+            else {
+                std::cerr << "selection: -Y (with -L: the representative of a cluster): max_degree, min_rank or max_rank, not '" << cluster_rep_arg << "'\n";
+                return 2;
+            }
         }
     }
     // -D: checked before any file is read or device opened
@@ -636,6 +721,7 @@ int main(int argc, char* argv[]) {
             parts[0].resize((size_t)cnt);
             r = selhip_ctx_fetch(ctx, parts[0].data(), cnt);
         }
+        if (!r) r = write_clusters(ctx, ds, n);
         if (r) { std::cerr << "selection: " << selhip_last_error(ctx) << "\n"; selhip_ctx_destroy(ctx); return 4; }
         selhip_ctx_destroy(ctx);
         if (d_list) selhip_free(d_list);

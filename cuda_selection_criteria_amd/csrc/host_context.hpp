@@ -133,8 +133,8 @@ static_assert(kCounterBlocks == kMaxChunks + 1, "common.cuh: counter blocks per 
 constexpr int kMaxAuxP = SELHIP_MAX_AUX_P;   // auxiliary HLL precision accepted by every entry point: aux_fused_kernel counts in 16-bit bins (a bin holds up to 2^p_aux)
 constexpr long long kEnumPairs = 1ll << 26;    // hll_a / hll_an as first criterion: pairs listed per sub-pass (512 MiB of int2)
 
-enum { T_PREP = 0, T_STAGE1, T_HIST, T_SELECT, T_TOTAL, T_SIGBUILD, T_JOIN, T_VERIFY, T_AUX, T_GROUP, T_DENSE, T_TOPK, T_MATRIX, T_MATRIX_SMH, T_COUNT };
-const char* kTimerNames[T_COUNT] = {"prep", "stage1", "hist", "select", "total", "sigbuild", "join", "verify", "aux", "group", "dense", "topk", "matrix", "matrix_smh"};
+enum { T_PREP = 0, T_STAGE1, T_HIST, T_SELECT, T_TOTAL, T_SIGBUILD, T_JOIN, T_VERIFY, T_AUX, T_GROUP, T_DENSE, T_TOPK, T_MATRIX, T_MATRIX_SMH, T_CLUSTER, T_COUNT };
+const char* kTimerNames[T_COUNT] = {"prep", "stage1", "hist", "select", "total", "sigbuild", "join", "verify", "aux", "group", "dense", "topk", "matrix", "matrix_smh", "cluster"};
 
 }  // namespace
 
@@ -337,12 +337,21 @@ struct selhip_ctx {
     int matrix_smh_form = 1;
     int matrix_smh_path_used = -1;
 
+    // single-linkage clusters of the result list (selhip_ctx_cluster; kernel_cluster.cuh, host_cluster.hpp): scratch the call owns
+    DevBuf<int> cl_parent, cl_label, cl_degree, cl_members;   // the union-find forest; labels, degrees, members per root where the caller takes none
+    DevBuf<uint32_t> cl_flag, cl_ids;   // root flags and their exclusive scan (one slot past the last genome: the number of clusters)
+    DevBuf<u64> cl_key;                 // the representative's key per cluster
+    DevBuf<ClusterBad> cl_bad;          // records the edge kernel refused (none, unless a list is corrupt)
+    DevBuf<char> cl_tmp;                // rocPRIM scan scratch
+    int clusters_last = -1;             // the C of the last call ("clusters_last"), -1 = none yet
+
     int timing = 0;                     // 0 off, 1 every kernel scope, 2 dominant stage-1 kernel only
     int dominant_timer = T_STAGE1;
     int timed_kernel = 0;               // timing level 2 keeps the events of: 0 = the stage-1 kernel (join / stream), 1 = stage 2a ("timed_kernel")
     long timed_passes = 0;
     long timed_matrix_calls = 0;        // matrix calls under timing: the divisor of "matrix" alone (the passes' per-pass averages are not theirs to dilute)
     long timed_matrix_smh_calls = 0;    // ... and those of the SuperMinHash measures: the divisor of "matrix_smh"
+    long timed_cluster_calls = 0;       // cluster calls under timing: the divisor of "cluster"
     int last_attempts = 0;              // enqueues the last finished run needed (1 = nothing overflowed)
     KernelTimer timers[T_COUNT];
 };

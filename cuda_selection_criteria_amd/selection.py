@@ -13,7 +13,8 @@ import numpy as np
 from . import _lib
 from ._lib import (ALGO_AUTO, BANDING_CPU, CRIT_HLL_A, CRIT_HLL_AN, CRIT_HLL_A_SMH_A, CRIT_NONE, CRIT_SMH_A, CRIT_SMH_C, ESTIMATOR_HLL, ESTIMATOR_SMH, F32, F64, FP_FMA,
                    MEASURE_CONTAINMENT, MEASURE_INTERSECTION, MEASURE_JACCARD, MEASURE_MAX_CONTAINMENT, MEASURE_SMH_JACCARD,
-                   MEASURE_SMH_MATCHES, MEASURE_UNION, MODE_CB_SMH, TOPK_ROUNDS_AUTO, Pair, check, hip_lib, host_lib)
+                   MEASURE_SMH_MATCHES, MEASURE_UNION, MODE_CB_SMH, REP_MAX_DEGREE, REP_MAX_RANK, REP_MIN_RANK, TOPK_ROUNDS_AUTO, Clusters, Pair, check, hip_lib,
+                   host_lib)
 
 # layout of selhip_pair_t {int32 i, k; double jaccard}
 PAIR_DTYPE = np.dtype([("i", "<i4"), ("k", "<i4"), ("jaccard", "<f8")], align=True)
@@ -511,6 +512,29 @@ class Selector:
         import torch
         return self._matrix(True, measure, dtype or torch.float64, rows, row_pos, col_pos, out)
 
+    # -- clusters of the result list ------------------------------------------------------------------
+    def cluster(self, min_value: Optional[float] = None, rep="max_degree", to_host: bool = True) -> dict:
+        """the single-linkage clusters of the result list the context holds, computed on the device (selhip_ctx_cluster): the connected
+        components of the graph on the n ranks whose edges are the records with value >= min_value (None: every record).  Behind an
+        all-pairs pass (any criterion; with top_k the directed list is taken as undirected edges) or a pair-list pass; not behind a
+        query pass.  rep picks every cluster's representative: "max_degree" (most records, ties to the smaller rank), "min_rank" (the
+        smallest genome = the label) or "max_rank" (the largest), or a REP_* code.  Returns a dict: "labels" [n] (smallest rank of the
+        component), "clusters" [n] (dense id, by ascending label), "degrees" [n] (records the genome appears in), "sizes" [C],
+        "representatives" [C] -- int32 numpy arrays, or torch tensors on the device with to_host=False -- and "n_clusters" = C"""
+        import torch
+        code = rep_code(rep)
+        mv = float("-inf") if min_value is None else float(min_value)
+        bufs = [torch.empty(self.n, dtype=torch.int32, device=torch.device("cuda", self.device)) for _ in range(5)]
+        out = Clusters(*[b.data_ptr() if self.n else None for b in bufs])
+        cnt = C.c_int64()
+        check(self._lib.selhip_ctx_cluster(self._ctx, mv, code, C.byref(out), C.byref(cnt)), self._ctx)
+        c = int(cnt.value)
+        res = {"labels": bufs[0], "clusters": bufs[1], "degrees": bufs[2], "sizes": bufs[3][:c], "representatives": bufs[4][:c]}
+        if to_host:
+            res = {k: v.cpu().numpy() for k, v in res.items()}
+        res["n_clusters"] = c
+        return res
+
     def result_count(self) -> int:
         return int(check(self._lib.selhip_ctx_result_count(self._ctx), self._ctx))
 
@@ -565,6 +589,46 @@ class Selector:
 
     def kernel_launches(self, name: str) -> float:
         return float(self._lib.selhip_ctx_kernel_launches(self._ctx, name.encode()))
+
+
+REPS = {"max_degree": REP_MAX_DEGREE, "min_rank": REP_MIN_RANK, "max_rank": REP_MAX_RANK}
+
+
+def rep_code(rep) -> int:
+    """the SELHIP_REP_* code of a representative rule given by name or by code; ValueError for anything else"""
+    code = REPS.get(rep) if isinstance(rep, str) else rep
+    if isinstance(code, bool) or not isinstance(code, (int, np.integer)) or code not in REPS.values():
+        raise ValueError("rep: 'max_degree', 'min_rank' or 'max_rank'")
+    return int(code)
+
+
+def components(pairs, n: int, device: int = 0, to_host: bool = True):
+    """labels [n] int32 of the connected components of the undirected graph on the vertices 0 .. n - 1 with one edge per row of `pairs`
+    (a numpy int32 (P, 2) array or a torch int32 device tensor of that shape): labels[g] = the smallest vertex of g's component, computed
+    on the device (selhip_components).  Self-loops and repeated rows are legal; a vertex outside [0, n) raises (SELHIP_E_BADARG, the
+    message names one such row).  A numpy array, or a torch tensor on the device with to_host=False"""
+    import torch
+    lib = hip_lib()
+    dev = torch.device("cuda", device)
+    if isinstance(pairs, np.ndarray) or not hasattr(pairs, "data_ptr"):
+        pairs = torch.from_numpy(np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)).to(dev)
+    assert pairs.is_cuda and pairs.is_contiguous() and pairs.dtype == torch.int32 and pairs.dim() == 2 and pairs.shape[1] == 2, \
+        "pairs: a contiguous int32 tensor of shape (P, 2)"
+    with torch.cuda.device(dev):
+        labels = torch.empty(int(n), dtype=torch.int32, device=dev)
+        check(lib.selhip_components(pairs.data_ptr() if pairs.numel() else None, int(pairs.shape[0]), int(n),
+                                    labels.data_ptr() if n else None, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return labels.cpu().numpy() if to_host else labels
+
+
+def cluster_table(names: Sequence[str], order: np.ndarray, res: dict) -> str:
+    """the text of `selection -L`: one line per genome in FILE-LIST order, 'path<TAB>cluster<TAB>cluster_size<TAB>degree<TAB>
+    representative_path'.  names in rank order, order[rank] = the genome's line in the list, res = Selector.cluster(...) on the host"""
+    out = []
+    for r in np.argsort(np.asarray(order), kind="stable"):
+        c = int(res["clusters"][r])
+        out.append(f"{names[r]}\t{c}\t{int(res['sizes'][c])}\t{int(res['degrees'][r])}\t{names[int(res['representatives'][c])]}\n")
+    return "".join(out)
 
 
 def min_matches(m: int, j: float) -> int:
@@ -666,26 +730,12 @@ def _aux_files(fold_aux: bool, p_aux: int, criterion: str) -> int:
     return 0
 
 
-def select_from_filelist(list_file: str, tau: float, aux_bytes: int, mode: int = MODE_CB_SMH, device: int = 0,
-                         fp_mode: int = FP_FMA, algo: int = ALGO_AUTO, criterion: str = "smh_a", top_k: int = 0,
-                         min_matches: Optional[int] = None, measure="jaccard", min_containment: Optional[float] = None, estimator="hll",
-                         top_k_rounds=0, fold_aux: bool = False) -> str:
-    """The whole of selection_cuda.cpp main() (criterion smh_a) -- and of selection.cpp's hll_a / hll_an
-    branches (:122-227): returns the text the CPU reference prints for `-c criterion -a aux_bytes -h tau`.
-    criterion "none": no criterion in front of the Jaccard test (CRIT_NONE; mode MODE_CB_SMH = the CB bound alone, MODE_SMH = every pair).
-    criterion "smh_c" with min_matches = c: at least c of the m = aux_bytes / 8 SuperMinHash buckets equal (CRIT_SMH_C; `-c smh_c -C c`);
-    with min_containment = gamma (`-G gamma`), with or without min_matches: at least containment_matches(m, gamma, e_small, e_large) of them,
-    the count at which the SuperMinHash estimate of the smaller genome's containment is gamma (Selector.set_min_containment).
-    top_k > 0: only every genome's top_k best partners, one line 'owner_path partner_path J' each, in ranked order (owner rank, then J
-    descending, ties by partner rank): a selected pair can be printed twice (once per member), once or not at all.
-    measure "max_containment": the pairs with I / min(e_i, e_k) >= tau, that value printed in J's place (Selector.set_measure;
-    ValueError with mode=MODE_CB_SMH or an hll_* criterion).
-    estimator "smh" (`-V smh`, criterion "smh_c" alone): the value tested and printed is the SuperMinHash estimate of the count,
-    smh_value(measure, m, c, e_i, e_k) (Selector.set_estimator), and no HLL stage runs.
-    top_k_rounds (`-R rows`, with top_k > 0, criterion "smh_c" and estimator "smh" alone): the pass runs in rounds of that many rows, or
-    "auto" (Selector.set_topk_rounds): the same text.
-    fold_aux (`-D`, criteria "hll_a" / "hll_an" alone): no .hll_<p> file is opened; the context folds the auxiliary sketches from the
-    .hll registers on the device (Selector.fold_aux_hll): the same text."""
+def _filelist_pass(then, list_file: str, tau: float, aux_bytes: int, mode: int = MODE_CB_SMH, device: int = 0,
+                   fp_mode: int = FP_FMA, algo: int = ALGO_AUTO, criterion: str = "smh_a", top_k: int = 0,
+                   min_matches: Optional[int] = None, measure="jaccard", min_containment: Optional[float] = None, estimator="hll",
+                   top_k_rounds=0, fold_aux: bool = False):
+    """the all-pairs pass of select_from_filelist (its arguments); returns then(dataset, selector, fetched records) with the pass's
+    result list still on the device"""
     meas = _pass_measure(measure, mode, criterion)
     est = _pass_estimator(estimator, criterion)
     rounds = topk_rounds_code(top_k_rounds)
@@ -709,7 +759,46 @@ def select_from_filelist(list_file: str, tau: float, aux_bytes: int, mode: int =
         sel.set_measure(meas)
         sel.set_estimator(est)
         pairs = sel.run(tau, mode, n_rows, n_bands, algo=algo, top_k=top_k if top_k else None, rounds=rounds if rounds else None)
-    return format_lines(ds.names, pairs)
+        return then(ds, sel, pairs)
+
+
+def select_from_filelist(list_file: str, tau: float, aux_bytes: int, mode: int = MODE_CB_SMH, device: int = 0,
+                         fp_mode: int = FP_FMA, algo: int = ALGO_AUTO, criterion: str = "smh_a", top_k: int = 0,
+                         min_matches: Optional[int] = None, measure="jaccard", min_containment: Optional[float] = None, estimator="hll",
+                         top_k_rounds=0, fold_aux: bool = False) -> str:
+    """The whole of selection_cuda.cpp main() (criterion smh_a) -- and of selection.cpp's hll_a / hll_an
+    branches (:122-227): returns the text the CPU reference prints for `-c criterion -a aux_bytes -h tau`.
+    criterion "none": no criterion in front of the Jaccard test (CRIT_NONE; mode MODE_CB_SMH = the CB bound alone, MODE_SMH = every pair).
+    criterion "smh_c" with min_matches = c: at least c of the m = aux_bytes / 8 SuperMinHash buckets equal (CRIT_SMH_C; `-c smh_c -C c`);
+    with min_containment = gamma (`-G gamma`), with or without min_matches: at least containment_matches(m, gamma, e_small, e_large) of them,
+    the count at which the SuperMinHash estimate of the smaller genome's containment is gamma (Selector.set_min_containment).
+    top_k > 0: only every genome's top_k best partners, one line 'owner_path partner_path J' each, in ranked order (owner rank, then J
+    descending, ties by partner rank): a selected pair can be printed twice (once per member), once or not at all.
+    measure "max_containment": the pairs with I / min(e_i, e_k) >= tau, that value printed in J's place (Selector.set_measure;
+    ValueError with mode=MODE_CB_SMH or an hll_* criterion).
+    estimator "smh" (`-V smh`, criterion "smh_c" alone): the value tested and printed is the SuperMinHash estimate of the count,
+    smh_value(measure, m, c, e_i, e_k) (Selector.set_estimator), and no HLL stage runs.
+    top_k_rounds (`-R rows`, with top_k > 0, criterion "smh_c" and estimator "smh" alone): the pass runs in rounds of that many rows, or
+    "auto" (Selector.set_topk_rounds): the same text.
+    fold_aux (`-D`, criteria "hll_a" / "hll_an" alone): no .hll_<p> file is opened; the context folds the auxiliary sketches from the
+    .hll registers on the device (Selector.fold_aux_hll): the same text."""
+    return _filelist_pass(lambda ds, sel, pairs: format_lines(ds.names, pairs), list_file, tau, aux_bytes, mode, device, fp_mode, algo, criterion,
+                          top_k, min_matches, measure, min_containment, estimator, top_k_rounds, fold_aux)
+
+
+def cluster_from_filelist(list_file: str, tau: float, aux_bytes: int, mode: int = MODE_CB_SMH, device: int = 0,
+                          fp_mode: int = FP_FMA, algo: int = ALGO_AUTO, criterion: str = "smh_a", top_k: int = 0,
+                          min_matches: Optional[int] = None, measure="jaccard", min_containment: Optional[float] = None, estimator="hll",
+                          top_k_rounds=0, fold_aux: bool = False, cluster_min: Optional[float] = None, rep="max_degree") -> str:
+    """The pass of select_from_filelist (same arguments), clustered on the device instead of printed: the text `selection ... -L file
+    [-T cluster_min] [-Y rep]` writes -- one line per genome in file-list order, 'path<TAB>cluster<TAB>cluster_size<TAB>degree<TAB>
+    representative_path' (Selector.cluster: single-linkage clusters of the selected pairs with value >= cluster_min, None = all of them;
+    rep "max_degree", "min_rank" or "max_rank")"""
+    code = rep_code(rep)
+    if cluster_min is not None and np.isnan(cluster_min):
+        raise ValueError("cluster_min: a number (None takes every selected pair), not NaN")
+    return _filelist_pass(lambda ds, sel, pairs: cluster_table(ds.names, ds.order, sel.cluster(cluster_min, code)), list_file, tau, aux_bytes, mode,
+                          device, fp_mode, algo, criterion, top_k, min_matches, measure, min_containment, estimator, top_k_rounds, fold_aux)
 
 
 def topk_rounds_code(rows) -> int:

@@ -223,7 +223,8 @@ int selhip_ctx_set_param(selhip_ctx* ctx, const char* name, int value);
  * "allpairs_topk" (the current k of selhip_ctx_set_allpairs_topk, 0 = off),
  * "pairs_route_used" (stage 1 of the last pair-list pass, section 2e),
  * "matrix_smh_path_used" (the kernel of the last matrix call with a SuperMinHash measure, section 2f: 1 = the register-tile kernel
- * of m = 128, 256, 512 or 1024 buckets, 0 = the generic kernel of every other m; -1 = none yet) */
+ * of m = 128, 256, 512 or 1024 buckets, 0 = the generic kernel of every other m; -1 = none yet),
+ * "clusters_last" (the number of clusters the last selhip_ctx_cluster call found, section 2g; -1 = none yet) */
 int selhip_ctx_get_param(const selhip_ctx* ctx, const char* name, int* value);
 /* Stage 2 grouping (default on): the pairs that reach the HLL-14 stage are bucketed by query row (counting sort) so
  * that waves running side by side on one XCD share their query row in L2.  0 = off (same kernel, list as produced). */
@@ -463,6 +464,7 @@ int selhip_ctx_set_topk_rounds(selhip_ctx* ctx, int64_t rows);
  * "matrix" is the kernel of a dense matrix (section 2f), averaged over the MATRIX CALLS since the last reset: they are counted apart
  * from the passes, so a matrix call changes no other name's per-pass figure.  "matrix_smh" is the kernel of a matrix call with a
  * SuperMinHash measure, averaged over THOSE calls: "matrix" stays the HLL kernel's figure and count.
+ * "cluster" is the launches of selhip_ctx_cluster (section 2g), averaged over the CLUSTER CALLS since the last reset, counted apart likewise.
  * selhip_ctx_kernel_launches: launches of that kernel per pass. */
 double selhip_ctx_kernel_ms(const selhip_ctx* ctx, const char* name);
 double selhip_ctx_kernel_launches(const selhip_ctx* ctx, const char* name);
@@ -683,6 +685,51 @@ int selhip_ctx_matrix(selhip_ctx* ctx, int measure, int dtype, int64_t r0, int64
 int selhip_ctx_query_matrix(selhip_ctx* ctx, int measure, int dtype, int64_t r0, int64_t r1, void* out_dev,
                             int64_t out_rows, int64_t out_cols, int64_t ld, const int32_t* row_pos, const int32_t* col_pos);
 
+/* ---------------------------------------------------------------------------------------------------
+ * 2g. Single-linkage clusters of the result list: the connected components of the graph whose edges are the records a pass left in
+ *     device memory, with one representative per component -- dereplication ("which genomes are the same thing at J >= 0.95, and
+ *     which one do I keep"), binning, "how many groups are in this collection" -- without fetching the list.
+ *     THE GRAPH: its vertices are the n ranks of the context's set; its edges are the records of the result list the context holds, as
+ *     selhip_ctx_result_device exposes it, whose `jaccard` field (the pass's measure) is >= min_value, compared in f64.  -INFINITY
+ *     takes every record, NaN is SELHIP_E_BADARG, any other value is legal: one pass at a low tau_f can be cut at several levels.
+ *     Accepted lists: all-pairs passes under any criterion, mode, measure or estimator, and the one-launch small pass; the cut lists of
+ *     selhip_ctx_set_allpairs_topk, with or without row rounds (the k-NN graph: its directed records are taken as undirected edges);
+ *     pair-list passes.  SELHIP_E_STATE after a query pass (its ranks live in two index spaces), before any finished pass and while
+ *     a pass is pending.  A matrix call in between changes nothing.
+ *     OUTPUTS, each a pure function of the record list, min_value and rep_rule, bit for bit, whatever order the device worked in:
+ *       d_label[g]         the smallest rank of g's component
+ *       d_cluster[g]       its dense id in 0 .. C-1, the components numbered by ascending label
+ *       d_degree[g]        the RECORDS of the graph in which g appears as i or k -- records, not distinct partners: after a plain
+ *                          all-pairs pass that is the vertex degree; in a directed top-k list a mutual pair counts twice for both of
+ *                          its genomes, and in a pair list an entry listed twice counts twice
+ *       d_cluster_size[c]  members of cluster c          (the first C entries are written)
+ *       d_cluster_rep[c]   its representative's rank      (the first C entries are written), chosen by rep_rule:
+ *           SELHIP_REP_MAX_DEGREE  the member with the most records; ties go to the smaller rank
+ *           SELHIP_REP_MIN_RANK    the label: the smallest genome (ranks ascend with the cardinality)
+ *           SELHIP_REP_MAX_RANK    the largest sketch of the cluster
+ *         a singleton represents itself with degree 0; any other rule: SELHIP_E_BADARG.
+ *     Every array is the caller's device memory of n int32; any of the five pointers may be NULL (that output is not written, and
+ *     nothing else of the caller's is); *n_clusters_out (may be NULL) receives C.  n == 0: C = 0.
+ *     The call reads the list and writes only `out` and scratch the context owns: the list, selhip_ctx_result_count, the statistics,
+ *     selhip_ctx_last_attempts, the top-k settings and the signature cache are as they were, and a context that never calls it launches
+ *     what it always launched.  It runs on the context's stream and returns when the outputs are complete.  A list without records
+ *     (n singletons) is one launch.  Timed as "cluster" in selhip_ctx_kernel_ms: per cluster call, counted apart from the passes as
+ *     "matrix" is.  get_param "clusters_last": the C of the last call, -1 = none yet.
+ *     Not clustered: the host-side lists of selhip_multi_select and selhip_ooc_select (selhip_components takes any edge list).
+ * --------------------------------------------------------------------------------------------------- */
+#define SELHIP_REP_MAX_DEGREE 0
+#define SELHIP_REP_MIN_RANK   1
+#define SELHIP_REP_MAX_RANK   2
+typedef struct {
+    int32_t* d_label;        /* [n]  smallest rank of the genome's component                       */
+    int32_t* d_cluster;      /* [n]  dense id 0 .. C-1, numbered by ascending label                */
+    int32_t* d_degree;       /* [n]  records of the graph in which the genome appears as i or k    */
+    int32_t* d_cluster_size; /* [n]  first C entries written: members of cluster c                 */
+    int32_t* d_cluster_rep;  /* [n]  first C entries written: representative rank of cluster c     */
+} selhip_clusters_t;         /* caller's device memory; any pointer may be NULL (not written)      */
+int selhip_ctx_cluster(selhip_ctx* ctx, double min_value, int rep_rule,
+                       const selhip_clusters_t* out, int64_t* n_clusters_out);
+
 
 /* ---------------------------------------------------------------------------------------------------
  * 3. Building blocks (device pointers), used by the launchers above and exposed for tests.
@@ -714,6 +761,13 @@ int selhip_smh_match_counts(const uint64_t* d_aux, int m, const selhip_int2_t* d
  * n > 0 for a null pointer or one that is not 16-byte aligned.  n == 0 launches nothing.  Registers above 64 - p + 1 cannot come from
  * a sketch builder: what they fold to is unspecified, and nothing validates them.  Asynchronous on hip_stream. */
 int selhip_hll_fold(const uint8_t* d_hll, int64_t n_genomes, int p, int p_aux, uint8_t* d_out, void* hip_stream);
+/* Connected components of an edge list (csrc/kernel_cluster.cuh: a lock-free union-find, one lane per entry): d_label[g] = the smallest
+ * vertex of g's component in the undirected graph on the vertices 0 .. n - 1 with one edge {x, y} per entry of d_pairs (device memory,
+ * 8-byte aligned).  Entries with x == y and entries listed twice are legal and change nothing.  An entry with a vertex outside [0, n)
+ * makes the call return SELHIP_E_BADARG: the message gives the number of such entries and the index of one of them, the labels are not
+ * written, and no kernel reads or writes outside the arrays because of it.  n == 0 and n_pairs == 0 are legal (n_pairs == 0: n
+ * singletons); 0 <= n <= 2^31 - 1, n_pairs any int64 >= 0.  The labels depend on the edge set alone.  Waits for the stream. */
+int selhip_components(const selhip_int2_t* d_pairs, int64_t n_pairs, int64_t n, int32_t* d_label /*[n]*/, void* hip_stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * 4. Synthetic sketches generated directly in HBM (csrc/synth.hpp; stands in for the FASTA->sketch
