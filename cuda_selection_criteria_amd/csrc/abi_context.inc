@@ -57,6 +57,7 @@ void selhip_ctx_destroy(selhip_ctx* c) {
     release_queries(c);
     release_topk(c);
     release_cluster(c);
+    release_greedy(c);
     if (c->h_pc) (void)hipHostFree(c->h_pc);
     if (c->st_stage1) {
         (void)hipStreamDestroy(c->st_stage1);
@@ -224,7 +225,8 @@ int selhip_ctx_set_param(selhip_ctx* c, const char* name, int value) {
         return SELHIP_OK;
     }
     // (a test hook, not part of the documented interface, and PROCESS-wide -- selhip_components has no context: > 0 fixes the grid of
-    //  cluster_edges_kernel for every cluster / components call that follows, 0 = sized from the list; the same clusters either way)
+    //  cluster_edges_kernel for every cluster / components call that follows, 0 = sized from the list; the same clusters either way.
+    //  The record kernels of the greedy clusters, kernel_greedy.cuh, take their grid from the same function and so from this hook)
     if (!std::strcmp(name, "cluster_blocks")) {
         if (value < 0 || value > 65536) { set_err(&c->err, "cluster_blocks must be in [0, 65536] (0 = automatic)"); return SELHIP_E_BADARG; }
         g_cluster_blocks = value;
@@ -251,6 +253,8 @@ int selhip_ctx_get_param(const selhip_ctx* c, const char* name, int* value) {
     if (!std::strcmp(name, "matrix_smh_path_used")) { *value = c->matrix_smh_path_used; return SELHIP_OK; }   // kernel of the last SuperMinHash matrix: 1 fast, 0 generic
     if (!std::strcmp(name, "clusters_last"))    { *value = c->clusters_last; return SELHIP_OK; }            // clusters of the last selhip_ctx_cluster call, -1 = none yet
     if (!std::strcmp(name, "cluster_blocks"))   { *value = g_cluster_blocks; return SELHIP_OK; }
+    if (!std::strcmp(name, "greedy_clusters_last")) { *value = c->greedy_clusters_last; return SELHIP_OK; }  // clusters of the last selhip_ctx_cluster_greedy call, -1 = none yet
+    if (!std::strcmp(name, "greedy_rounds_last"))   { *value = c->greedy_rounds_last; return SELHIP_OK; }    // ... and the rounds its selection took
     if (!std::strcmp(name, "small_pass_used"))  { *value = c->small_used ? 1 : 0; return SELHIP_OK; }
     if (!std::strcmp(name, "pairs_route_used")) { *value = c->pairs_route_used; return SELHIP_OK; }         // list passes: 1 signature, 0 direct, 2 no smh_a stage, -1 none yet
     if (!std::strcmp(name, "query_topk"))       { *value = c->query_topk; return SELHIP_OK; }              // K of the query passes' top-k, 0 = off
@@ -757,7 +761,7 @@ int selhip_ctx_timing(selhip_ctx* c, int enable) {
     drain_timers(c);
     for (int t = 0; t < T_COUNT; ++t) { c->timers[t].total_ms = 0; c->timers[t].launches = 0; c->timers[t].span_ms = 0; }
     c->timing = enable == 2 ? 2 : (enable != 0 ? 1 : 0);
-    c->timed_passes = 0; c->timed_matrix_calls = 0; c->timed_matrix_smh_calls = 0; c->timed_cluster_calls = 0;
+    c->timed_passes = 0; c->timed_matrix_calls = 0; c->timed_matrix_smh_calls = 0; c->timed_cluster_calls = 0; c->timed_greedy_calls = 0;
     return SELHIP_OK;
 }
 
@@ -766,7 +770,7 @@ double selhip_ctx_kernel_ms(const selhip_ctx* c, const char* name) {
     if (!c->pending) drain_timers(const_cast<selhip_ctx*>(c));
     for (int t = 0; t < T_COUNT; ++t)
         if (!std::strcmp(name, kTimerNames[t])) {
-            const long passes = t == T_MATRIX ? c->timed_matrix_calls : t == T_MATRIX_SMH ? c->timed_matrix_smh_calls : t == T_CLUSTER ? c->timed_cluster_calls : c->timed_passes;
+            const long passes = t == T_MATRIX ? c->timed_matrix_calls : t == T_MATRIX_SMH ? c->timed_matrix_smh_calls : t == T_CLUSTER ? c->timed_cluster_calls : t == T_GREEDY ? c->timed_greedy_calls : c->timed_passes;
             return (c->timers[t].launches && passes) ? c->timers[t].total_ms / (double)passes : -1.0;
         }
     const long passes = c->timed_passes;
@@ -780,7 +784,7 @@ double selhip_ctx_kernel_launches(const selhip_ctx* c, const char* name) {
     if (!c->pending) drain_timers(const_cast<selhip_ctx*>(c));
     for (int t = 0; t < T_COUNT; ++t)
         if (!std::strcmp(name, kTimerNames[t])) {
-            const long passes = t == T_MATRIX ? c->timed_matrix_calls : t == T_MATRIX_SMH ? c->timed_matrix_smh_calls : t == T_CLUSTER ? c->timed_cluster_calls : c->timed_passes;
+            const long passes = t == T_MATRIX ? c->timed_matrix_calls : t == T_MATRIX_SMH ? c->timed_matrix_smh_calls : t == T_CLUSTER ? c->timed_cluster_calls : t == T_GREEDY ? c->timed_greedy_calls : c->timed_passes;
             return passes ? (double)c->timers[t].launches / (double)passes : 0.0;
         }
     return -1.0;

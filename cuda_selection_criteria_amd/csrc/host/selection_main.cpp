@@ -86,6 +86,16 @@
 //               clustered at several levels; default: every selected pair
 //   -Y <rule>   with -L: the representative of a cluster: max_degree (default; most records, ties to the smaller rank), min_rank (the
 //               smallest genome) or max_rank (the largest)
+//   -Z <how>    with -L: single (default: the single-linkage clusters above) or greedy: the greedy representative clusters of the selected
+//               pairs (selhip_ctx_cluster_greedy; CD-HIT / UCLUST): the genomes are visited in the order -Y names (max_degree, default: the
+//               most records first; min_rank; max_rank: the largest sketch first) and one becomes a representative unless a selected pair
+//               (with -T: of at least that value) already joins it to one; every other genome goes to the representative it has the
+//               greatest value with.  The table gains a sixth column:
+//               path <TAB> cluster <TAB> cluster_size <TAB> degree <TAB> representative_path <TAB> value_to_representative
+//               (cluster: dense id by ascending representative rank; the value printed as std::to_string does, 1.000000 for a representative)
+//   -W <file>   with -L -Z greedy: the visiting order is a score per genome, the greatest first (ties to the smaller genome): lines of
+//               path <TAB> unsigned score (up to 2^32 - 1), one per genome of the -l list, in any order; read and checked before any
+//               device work.  Not with -Y
 //   -x          usage
 #include <unistd.h>
 
@@ -97,6 +107,7 @@
 #include <fstream>
 #include <iostream>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "../../../include/selection_hip.h"
@@ -111,9 +122,87 @@ static long long g_topk_rounds = 0;              // -R: rows per round of -K (0:
 static std::string g_cluster_file = "";         // -L: the cluster table of the pass's result list goes here ("" = none)
 static double g_cluster_min = -INFINITY;         // -T: records below this value are no edges
 static int g_cluster_rep = SELHIP_REP_MAX_DEGREE;   // -Y
+static bool g_cluster_greedy = false;            // -Z greedy
+static std::string g_priority_file = "";        // -W: the scores that order the greedy clusters ("" = none)
+static std::vector<uint32_t> g_priority;         // ... in rank order, read by load_priorities
+
+// -W: the scores of the n genomes of ds, checked on the host; 0 = fine (or no -W)
+static int load_priorities(const selhost_dataset* ds, int64_t n) {
+    if (g_priority_file.empty()) return 0;
+    std::ifstream f(g_priority_file, std::ios::binary);
+    if (!f) { std::cerr << "selection: -W: cannot read '" << g_priority_file << "'\n"; return 5; }
+    std::unordered_map<std::string, int64_t> rank_of;
+    for (int64_t g = 0; g < n; ++g) rank_of.emplace(selhost_dataset_name(ds, g), g);
+    g_priority.assign((size_t)n, 0);
+    std::vector<char> seen((size_t)n, 0);
+    int64_t n_seen = 0, line_no = 0;
+    std::string line;
+    while (std::getline(f, line)) {
+        ++line_no;
+        if (line.empty()) continue;
+        const size_t tab = line.find('\t');
+        const std::string score = tab == std::string::npos ? "" : line.substr(tab + 1);
+        const auto it = tab == std::string::npos ? rank_of.end() : rank_of.find(line.substr(0, tab));
+        const bool digits = !score.empty() && score.size() <= 10 && score.find_first_not_of("0123456789") == std::string::npos;
+        const unsigned long long v = digits ? std::strtoull(score.c_str(), nullptr, 10) : 0;
+        if (it == rank_of.end() || !digits || v > 0xFFFFFFFFull || seen[(size_t)it->second]) {
+            std::cerr << "selection: -W: line " << line_no << " of '" << g_priority_file
+                      << "' is not 'path<TAB>unsigned score' for a genome of the -l list not scored yet\n";
+            return 5;
+        }
+        seen[(size_t)it->second] = 1;
+        g_priority[(size_t)it->second] = (uint32_t)v;
+        ++n_seen;
+    }
+    if (n_seen != n) { std::cerr << "selection: -W: '" << g_priority_file << "' scores " << n_seen << " of the " << n << " genomes of the -l list\n"; return 5; }
+    return 0;
+}
+
+// -L -Z greedy: the greedy representative clusters of the result list as a table in file-list order
+static int write_greedy(selhip_ctx* ctx, const selhost_dataset* ds, int64_t n) {
+    std::vector<int32_t> rep_of((size_t)n), cluster((size_t)n), degree((size_t)n), size((size_t)n);
+    std::vector<double> value((size_t)n);
+    selhip_greedy_t out{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    void* d = nullptr;
+    int64_t n_clusters = 0;
+    const bool scored = !g_priority_file.empty();
+    // value[n] (f64) first, then rep_of, cluster, degree, cluster_size and the scores: 4-byte words
+    int r = n ? selhip_malloc(&d, (size_t)n * (sizeof(double) + 5 * sizeof(int32_t))) : 0;
+    uint32_t* d_priority = nullptr;
+    if (!r && n) {
+        out.d_value = static_cast<double*>(d);
+        int32_t* base = reinterpret_cast<int32_t*>(out.d_value + n);
+        out.d_rep_of = base; out.d_cluster = base + n; out.d_degree = base + 2 * n; out.d_cluster_size = base + 3 * n;
+        d_priority = reinterpret_cast<uint32_t*>(base + 4 * n);
+        if (scored) r = selhip_memcpy_h2d(d_priority, g_priority.data(), (size_t)n * sizeof(uint32_t));
+    }
+    // (without a genome there is no array to point to: the rule the call accepts with a NULL d_priority)
+    if (!r) r = selhip_ctx_cluster_greedy(ctx, g_cluster_min, scored && n ? SELHIP_REP_PRIORITY : g_cluster_rep, scored && n ? d_priority : nullptr, &out, &n_clusters);
+    if (!r && n) r = selhip_memcpy_d2h(value.data(), out.d_value, (size_t)n * sizeof(double));
+    if (!r && n) r = selhip_memcpy_d2h(rep_of.data(), out.d_rep_of, (size_t)n * sizeof(int32_t));
+    if (!r && n) r = selhip_memcpy_d2h(cluster.data(), out.d_cluster, (size_t)n * sizeof(int32_t));
+    if (!r && n) r = selhip_memcpy_d2h(degree.data(), out.d_degree, (size_t)n * sizeof(int32_t));
+    if (!r && n_clusters) r = selhip_memcpy_d2h(size.data(), out.d_cluster_size, (size_t)n_clusters * sizeof(int32_t));
+    if (d) selhip_free(d);
+    if (r) return r;
+    std::vector<int64_t> rank_of_line((size_t)n);
+    for (int64_t g = 0; g < n; ++g) rank_of_line[(size_t)selhost_dataset_order(ds, g)] = g;
+    std::ofstream f(g_cluster_file, std::ios::binary);
+    for (int64_t line = 0; line < n; ++line) {
+        const int64_t g = rank_of_line[(size_t)line];
+        const int32_t c = cluster[(size_t)g];
+        f << selhost_dataset_name(ds, g) << '\t' << c << '\t' << size[(size_t)c] << '\t' << degree[(size_t)g] << '\t'
+          << selhost_dataset_name(ds, rep_of[(size_t)g]) << '\t' << std::to_string(value[(size_t)g]) << '\n';
+    }
+    f.close();
+    if (!f) { std::cerr << "selection: -L: cannot write '" << g_cluster_file << "'\n"; return 5; }
+    return 0;
+}
+
 // -L: behind a finished pass of ctx over the n genomes of ds, the clusters of its result list as a table in file-list order
 static int write_clusters(selhip_ctx* ctx, const selhost_dataset* ds, int64_t n) {
     if (g_cluster_file.empty()) return 0;
+    if (g_cluster_greedy) return write_greedy(ctx, ds, n);
     std::vector<int32_t> cluster((size_t)n), degree((size_t)n), size((size_t)n), rep((size_t)n);
     selhip_clusters_t out{nullptr, nullptr, nullptr, nullptr, nullptr};
     void* d = nullptr;
@@ -238,6 +327,7 @@ static int run_neighbours(const std::string& list_file, int crit, float threshol
     selhost_dataset* ds = nullptr;
     if (selhost_dataset_load(&ds, list_file.c_str(), m, aux_files(p_aux), fp_mode, threads)) { std::cerr << selhost_last_error() << "\n"; return 1; }
     const int64_t n = selhost_dataset_size(ds);
+    if (const int w = load_priorities(ds, n)) { selhost_dataset_free(ds); return w; }
     int n_rows = 1, n_bands = 1;
     if (m) selhost_banding(m, threshold, SELHOST_BANDING_CPU, &n_rows, &n_bands);
     std::vector<uint64_t> no_smh(m ? 0 : (size_t)(n > 0 ? n : 1), 0);
@@ -341,9 +431,10 @@ int main(int argc, char* argv[]) {
     long long top_k = 0, nbr_k = 0, min_matches = 0;
     bool cmin_given = false, gamma_given = false, value_given = false, rounds_given = false;
     std::string rounds_arg = "", cluster_min_arg = "", cluster_rep_arg = "";
-    bool cluster_given = false, cluster_min_given = false, cluster_rep_given = false;
+    bool cluster_given = false, cluster_min_given = false, cluster_rep_given = false, linkage_given = false, priority_given = false;
+    std::string linkage_arg = "";
     int c;
-    while ((c = getopt(argc, argv, "xl:b:a:h:c:C:G:t:g:nA:F:B:o:r:q:k:K:p:M:UE:S:V:R:DL:T:Y:")) != -1) {
+    while ((c = getopt(argc, argv, "xl:b:a:h:c:C:G:t:g:nA:F:B:o:r:q:k:K:p:M:UE:S:V:R:DL:T:Y:Z:W:")) != -1) {
         switch (c) {
             case 'x': std::cout << "Usage: -l -h -a -b [-c smh_a|hll_a|hll_an|none|smh_c -C c_min|-G gamma] [-t threads] [-g gpus] [-n] [-A auto|stream|sig] [-F 0|1] [-B block] [-o file] | -r file\n"
                                    "       -l db_list -q query_list -h -a [-c smh_a|hll_a|hll_an|none|smh_c -C c_min|-G gamma] [-n] [-A auto|stream|sig|index] [-F 0|1] [-k best_per_query]   (query-vs-database selection)\n"
@@ -357,6 +448,7 @@ int main(int argc, char* argv[]) {
                                    "       ... -c smh_c -C c_min|-G gamma -a bytes -V smh|hll   (with -l, -q, -p, -k, -K, -n, -S max_containment, -o: -V smh tests and prints the SuperMinHash estimate of the count, c / m, with no HLL stage)\n"
                                    "       -l list -K best_per_genome -c smh_c -C c_min|-G gamma -a bytes -V smh -R rows|auto   (the same list in rounds of rows: memory for n K records and one round, not for every pair that shares a bucket)\n"
                                    "       -l list [-p pair_file | -K best_per_genome [-R rows]] ... -L clusters.tsv [-T min_value] [-Y max_degree|min_rank|max_rank]   (besides the output: the single-linkage clusters of the selected pairs, one line per genome: path, cluster, size, degree, representative)\n"
+                                   "       ... -L clusters.tsv -Z single|greedy [-T min_value] [-Y max_degree|min_rank|max_rank | -W scores.tsv]   (-Z greedy: greedy representative clusters, CD-HIT style: genomes visited in the -Y order or by descending score, every other genome to its most similar representative; a sixth column: value to the representative)\n"
                                    "       ... -c hll_a|hll_an -a bytes -D   (with -l, -q, -p, -k, -K, -g, -B: no .hll_<p> file is read, the auxiliary HLL sketches are folded from the .hll registers)\n"; return 0;
             case 'q': query_file = optarg; break;
             case 'p': pair_file = optarg; break;
@@ -370,6 +462,8 @@ int main(int argc, char* argv[]) {
             case 'L': g_cluster_file = optarg; cluster_given = true; break;
             case 'T': cluster_min_arg = optarg; cluster_min_given = true; break;
             case 'Y': cluster_rep_arg = optarg; cluster_rep_given = true; break;
+            case 'Z': linkage_arg = optarg; linkage_given = true; break;
+            case 'W': g_priority_file = optarg; priority_given = true; break;
             case 'k': top_k = std::strtoll(optarg, nullptr, 10); topk_given = true; break;
             case 'K': nbr_k = std::strtoll(optarg, nullptr, 10); nbr_given = true; break;
             case 'B': ooc_block = std::stoll(optarg); break;
@@ -395,6 +489,30 @@ int main(int argc, char* argv[]) {
         std::cerr << "selection: " << (cluster_min_given ? "-T (the smallest value of an edge)" : "-Y (the representative of a cluster)")
                   << " is an option of -L (the clusters of the selected pairs)\n";
         return 2;
+    }
+    // -Z and -W: checked before any file is read or device opened
+    if ((linkage_given || priority_given) && !cluster_given) {
+        std::cerr << "selection: " << (linkage_given ? "-Z (single or greedy clusters)" : "-W (the scores that order the greedy clusters)")
+                  << " is an option of -L (the clusters of the selected pairs)\n";
+        return 2;
+    }
+    if (linkage_given) {
+        if (linkage_arg == "greedy") g_cluster_greedy = true;
+        else if (linkage_arg != "single") {
+            std::cerr << "selection: -Z (with -L: how the selected pairs are clustered): single or greedy, not '" << linkage_arg << "'\n";
+            return 2;
+        }
+    }
+    if (priority_given) {
+        if (!g_cluster_greedy) {
+            std::cerr << "selection: -W (the scores that order the greedy clusters) is an option of -L ... -Z greedy\n";
+            return 2;
+        }
+        if (cluster_rep_given) {
+            std::cerr << "selection: -W (the scores that order the greedy clusters of -L) cannot be combined with -Y; the scores are the order\n";
+            return 2;
+        }
+        if (g_priority_file.empty()) { std::cerr << "selection: -W (with -L -Z greedy) needs the name of the file of scores\n"; return 2; }
     }
     if (cluster_given) {
         const char* clash = !query_file.empty() ? "-q" : matrix_given ? "-M" : gpus_given ? "-g" : ooc_block != 0 ? "-B" : !dump_file.empty() ? "-r" : nullptr;
@@ -634,6 +752,7 @@ int main(int argc, char* argv[]) {
     int rc = selhost_dataset_load(&ds, list_file.c_str(), m, aux_files(p_aux), fp_mode, threads);
     if (rc) { std::cerr << selhost_last_error() << "\n"; exit(-1); }
     const int64_t n = selhost_dataset_size(ds);
+    if (const int w = load_priorities(ds, n)) return w;
     // the auxiliary HLL array of the drivers that take host arrays (-B, -g): the files', or under -D the host fold of the .hll registers
     std::vector<uint8_t> folded;
     const uint8_t* aux_hll_host = p_aux ? selhost_dataset_aux_hll(ds) : nullptr;

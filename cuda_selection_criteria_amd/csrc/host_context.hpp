@@ -133,8 +133,8 @@ static_assert(kCounterBlocks == kMaxChunks + 1, "common.cuh: counter blocks per 
 constexpr int kMaxAuxP = SELHIP_MAX_AUX_P;   // auxiliary HLL precision accepted by every entry point: aux_fused_kernel counts in 16-bit bins (a bin holds up to 2^p_aux)
 constexpr long long kEnumPairs = 1ll << 26;    // hll_a / hll_an as first criterion: pairs listed per sub-pass (512 MiB of int2)
 
-enum { T_PREP = 0, T_STAGE1, T_HIST, T_SELECT, T_TOTAL, T_SIGBUILD, T_JOIN, T_VERIFY, T_AUX, T_GROUP, T_DENSE, T_TOPK, T_MATRIX, T_MATRIX_SMH, T_CLUSTER, T_COUNT };
-const char* kTimerNames[T_COUNT] = {"prep", "stage1", "hist", "select", "total", "sigbuild", "join", "verify", "aux", "group", "dense", "topk", "matrix", "matrix_smh", "cluster"};
+enum { T_PREP = 0, T_STAGE1, T_HIST, T_SELECT, T_TOTAL, T_SIGBUILD, T_JOIN, T_VERIFY, T_AUX, T_GROUP, T_DENSE, T_TOPK, T_MATRIX, T_MATRIX_SMH, T_CLUSTER, T_GREEDY, T_COUNT };
+const char* kTimerNames[T_COUNT] = {"prep", "stage1", "hist", "select", "total", "sigbuild", "join", "verify", "aux", "group", "dense", "topk", "matrix", "matrix_smh", "cluster", "greedy"};
 
 }  // namespace
 
@@ -345,6 +345,14 @@ struct selhip_ctx {
     DevBuf<char> cl_tmp;                // rocPRIM scan scratch
     int clusters_last = -1;             // the C of the last call ("clusters_last"), -1 = none yet
 
+    // greedy representative clusters (selhip_ctx_cluster_greedy; kernel_greedy.cuh, host_greedy.hpp): scratch the call owns, beside what
+    // it shares with the call above (cl_key, cl_degree, cl_members, cl_flag, cl_ids, cl_bad, cl_tmp)
+    DevBuf<int> gr_state, gr_blocked, gr_rep_of;   // UNDECIDED / REP / MEMBER; the last round a vertex was held back; rep_of where the caller takes none
+    DevBuf<u64> gr_best;                // per member, the image of its best edge to a representative
+    DevBuf<uint32_t> gr_count;          // the UNDECIDED counts of a batch of rounds
+    int greedy_clusters_last = -1;      // the C of the last call ("greedy_clusters_last"), -1 = none yet
+    int greedy_rounds_last = -1;        // its rounds ("greedy_rounds_last")
+
     int timing = 0;                     // 0 off, 1 every kernel scope, 2 dominant stage-1 kernel only
     int dominant_timer = T_STAGE1;
     int timed_kernel = 0;               // timing level 2 keeps the events of: 0 = the stage-1 kernel (join / stream), 1 = stage 2a ("timed_kernel")
@@ -352,6 +360,7 @@ struct selhip_ctx {
     long timed_matrix_calls = 0;        // matrix calls under timing: the divisor of "matrix" alone (the passes' per-pass averages are not theirs to dilute)
     long timed_matrix_smh_calls = 0;    // ... and those of the SuperMinHash measures: the divisor of "matrix_smh"
     long timed_cluster_calls = 0;       // cluster calls under timing: the divisor of "cluster"
+    long timed_greedy_calls = 0;        // greedy calls under timing: the divisor of "greedy"
     int last_attempts = 0;              // enqueues the last finished run needed (1 = nothing overflowed)
     KernelTimer timers[T_COUNT];
 };

@@ -13,7 +13,7 @@ import numpy as np
 from . import _lib
 from ._lib import (ALGO_AUTO, BANDING_CPU, CRIT_HLL_A, CRIT_HLL_AN, CRIT_HLL_A_SMH_A, CRIT_NONE, CRIT_SMH_A, CRIT_SMH_C, ESTIMATOR_HLL, ESTIMATOR_SMH, F32, F64, FP_FMA,
                    MEASURE_CONTAINMENT, MEASURE_INTERSECTION, MEASURE_JACCARD, MEASURE_MAX_CONTAINMENT, MEASURE_SMH_JACCARD,
-                   MEASURE_SMH_MATCHES, MEASURE_UNION, MODE_CB_SMH, REP_MAX_DEGREE, REP_MAX_RANK, REP_MIN_RANK, TOPK_ROUNDS_AUTO, Clusters, Pair, check, hip_lib,
+                   MEASURE_SMH_MATCHES, MEASURE_UNION, MODE_CB_SMH, REP_MAX_DEGREE, REP_MAX_RANK, REP_MIN_RANK, REP_PRIORITY, TOPK_ROUNDS_AUTO, Clusters, Greedy, Pair, check, hip_lib,
                    host_lib)
 
 # layout of selhip_pair_t {int32 i, k; double jaccard}
@@ -535,6 +535,47 @@ class Selector:
         res["n_clusters"] = c
         return res
 
+    def cluster_greedy(self, min_value: Optional[float] = None, order="max_degree", priority=None, to_host: bool = True) -> dict:
+        """the greedy representative clusters of the result list the context holds (selhip_ctx_cluster_greedy; CD-HIT / UCLUST): the
+        genomes are visited in `order` -- "max_degree" (most records first, ties to the smaller rank), "min_rank", "max_rank" (the
+        largest sketch first, the CD-HIT order), "priority", or a REP_* code -- and one becomes a representative unless a record with
+        value >= min_value (None: every record) already joins it to one; every other genome belongs to the representative it has the
+        greatest value with (ties to the smaller rank).  priority: n unsigned 32-bit scores, greater first (a numpy array or a torch
+        uint32 / int32 device tensor); it selects the order "priority" and goes with no other.  Behind the passes of Selector.cluster.
+        Returns a dict: "rep_of" [n], "values" [n] float64 (1.0 for a representative), "clusters" [n] (dense id, by ascending
+        representative rank), "degrees" [n], "sizes" [C], "representatives" [C] -- numpy arrays, or torch tensors on the device with
+        to_host=False -- "n_clusters" = C and "rounds" (launch rounds the selection took)"""
+        import torch
+        if priority is not None and order == "max_degree":
+            order = "priority"
+        code = order_code(order)
+        if (code == REP_PRIORITY) != (priority is not None):
+            raise ValueError("priority: the scores of order 'priority', and of no other order")
+        dev = torch.device("cuda", self.device)
+        prio = None
+        if priority is not None:
+            if hasattr(priority, "data_ptr"):
+                prio = priority.to(dev).contiguous()
+                assert prio.dtype in (torch.int32, torch.uint32) and prio.numel() == self.n, "priority: n 32-bit scores"
+            else:
+                host = np.asarray(priority)
+                if host.shape != (self.n,) or host.dtype.kind not in "iu" or (host.size and (host.min() < 0 or host.max() > 0xFFFFFFFF)):
+                    raise ValueError("priority: n unsigned 32-bit scores")
+                prio = torch.from_numpy(host.astype(np.uint32).view(np.int32)).to(dev)
+        mv = float("-inf") if min_value is None else float(min_value)
+        bufs = [torch.empty(self.n, dtype=torch.float64 if j == 1 else torch.int32, device=dev) for j in range(6)]
+        out = Greedy(*[b.data_ptr() if self.n else None for b in bufs])
+        cnt = C.c_int64()
+        check(self._lib.selhip_ctx_cluster_greedy(self._ctx, mv, code, prio.data_ptr() if prio is not None and self.n else None, C.byref(out), C.byref(cnt)),
+              self._ctx)
+        c = int(cnt.value)
+        res = {"rep_of": bufs[0], "values": bufs[1], "clusters": bufs[2], "degrees": bufs[3], "sizes": bufs[4][:c], "representatives": bufs[5][:c]}
+        if to_host:
+            res = {k: v.cpu().numpy() for k, v in res.items()}
+        res["n_clusters"] = c
+        res["rounds"] = self.get_param("greedy_rounds_last")
+        return res
+
     def result_count(self) -> int:
         return int(check(self._lib.selhip_ctx_result_count(self._ctx), self._ctx))
 
@@ -600,6 +641,63 @@ def rep_code(rep) -> int:
     if isinstance(code, bool) or not isinstance(code, (int, np.integer)) or code not in REPS.values():
         raise ValueError("rep: 'max_degree', 'min_rank' or 'max_rank'")
     return int(code)
+
+
+ORDERS = dict(REPS, priority=REP_PRIORITY)
+
+
+def order_code(order) -> int:
+    """the SELHIP_REP_* code of a visiting order of the greedy clusters given by name or by code; ValueError for anything else"""
+    code = ORDERS.get(order) if isinstance(order, str) else order
+    if isinstance(code, bool) or not isinstance(code, (int, np.integer)) or code not in ORDERS.values():
+        raise ValueError("order: 'max_degree', 'min_rank', 'max_rank' or 'priority'")
+    return int(code)
+
+
+def _device_pairs(pairs, dev):
+    import torch
+    if isinstance(pairs, np.ndarray) or not hasattr(pairs, "data_ptr"):
+        pairs = torch.from_numpy(np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)).to(dev)
+    assert pairs.is_cuda and pairs.is_contiguous() and pairs.dtype == torch.int32 and pairs.dim() == 2 and pairs.shape[1] == 2, \
+        "pairs: a contiguous int32 tensor of shape (P, 2)"
+    return pairs
+
+
+def greedy_representatives(pairs, n: int, keys=None, device: int = 0, to_host: bool = True):
+    """(is_rep [n] uint8, rounds): the representatives of the greedy clustering over the undirected graph on the vertices 0 .. n - 1 with
+    one edge per row of `pairs` (a numpy int32 (P, 2) array or a torch int32 device tensor of that shape), computed on the device
+    (selhip_greedy_representatives): visit the vertices by descending keys[g] (n unsigned 64-bit keys, numpy; equal keys: the smaller
+    vertex first; None: key = vertex); a vertex is a representative unless a neighbour already is one.  Self-loops and repeated rows are
+    legal; a vertex outside [0, n) raises (SELHIP_E_BADARG).  rounds: the launch rounds the selection took.  is_rep is a numpy array, or
+    a torch tensor on the device with to_host=False"""
+    import torch
+    lib = hip_lib()
+    dev = torch.device("cuda", device)
+    pairs = _device_pairs(pairs, dev)
+    key = None
+    if keys is not None:
+        host = np.ascontiguousarray(keys, dtype=np.uint64)
+        if host.shape != (int(n),):
+            raise ValueError("keys: n unsigned 64-bit keys")
+        key = torch.from_numpy(host.view(np.int64)).to(dev)
+    rounds = C.c_int64(-1)
+    with torch.cuda.device(dev):
+        is_rep = torch.empty(int(n), dtype=torch.uint8, device=dev)
+        check(lib.selhip_greedy_representatives(pairs.data_ptr() if pairs.numel() else None, int(pairs.shape[0]), int(n),
+                                                key.data_ptr() if key is not None and n else None, is_rep.data_ptr() if n else None,
+                                                C.byref(rounds), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return (is_rep.cpu().numpy() if to_host else is_rep), int(rounds.value)
+
+
+def greedy_table(names: Sequence[str], order: np.ndarray, res: dict) -> str:
+    """the text of `selection -L file -Z greedy`: one line per genome in FILE-LIST order, 'path<TAB>cluster<TAB>cluster_size<TAB>degree
+    <TAB>representative_path<TAB>value_to_representative' (the value with six decimals, as std::to_string prints it).  names in rank
+    order, order[rank] = the genome's line in the list, res = Selector.cluster_greedy(...) on the host"""
+    out = []
+    for r in np.argsort(np.asarray(order), kind="stable"):
+        c = int(res["clusters"][r])
+        out.append(f"{names[r]}\t{c}\t{int(res['sizes'][c])}\t{int(res['degrees'][r])}\t{names[int(res['rep_of'][r])]}\t{float(res['values'][r]):f}\n")
+    return "".join(out)
 
 
 def components(pairs, n: int, device: int = 0, to_host: bool = True):
@@ -799,6 +897,29 @@ def cluster_from_filelist(list_file: str, tau: float, aux_bytes: int, mode: int 
         raise ValueError("cluster_min: a number (None takes every selected pair), not NaN")
     return _filelist_pass(lambda ds, sel, pairs: cluster_table(ds.names, ds.order, sel.cluster(cluster_min, code)), list_file, tau, aux_bytes, mode,
                           device, fp_mode, algo, criterion, top_k, min_matches, measure, min_containment, estimator, top_k_rounds, fold_aux)
+
+
+def greedy_from_filelist(list_file: str, tau: float, aux_bytes: int, mode: int = MODE_CB_SMH, device: int = 0,
+                         fp_mode: int = FP_FMA, algo: int = ALGO_AUTO, criterion: str = "smh_a", top_k: int = 0,
+                         min_matches: Optional[int] = None, measure="jaccard", min_containment: Optional[float] = None, estimator="hll",
+                         top_k_rounds=0, fold_aux: bool = False, cluster_min: Optional[float] = None, order="max_degree", priority=None) -> str:
+    """The pass of select_from_filelist (same arguments), clustered greedily on the device instead of printed: the text `selection ...
+    -L file -Z greedy [-T cluster_min] [-Y order] [-W scores]` writes -- one line per genome in file-list order, 'path<TAB>cluster<TAB>
+    cluster_size<TAB>degree<TAB>representative_path<TAB>value_to_representative' (Selector.cluster_greedy).  priority: one unsigned
+    32-bit score per genome in FILE-LIST order (what -W reads); it selects the order "priority" and goes with no other"""
+    if priority is not None and order == "max_degree":
+        order = "priority"
+    code = order_code(order)
+    if (code == REP_PRIORITY) != (priority is not None):
+        raise ValueError("priority: the scores of order 'priority', and of no other order")
+    if cluster_min is not None and np.isnan(cluster_min):
+        raise ValueError("cluster_min: a number (None takes every selected pair), not NaN")
+
+    def then(ds, sel, pairs):
+        prio = None if priority is None else np.asarray(priority)[np.asarray(ds.order)]          # file-list order -> rank order
+        return greedy_table(ds.names, ds.order, sel.cluster_greedy(cluster_min, code, prio))
+    return _filelist_pass(then, list_file, tau, aux_bytes, mode, device, fp_mode, algo, criterion, top_k, min_matches, measure, min_containment,
+                          estimator, top_k_rounds, fold_aux)
 
 
 def topk_rounds_code(rows) -> int:

@@ -224,7 +224,9 @@ int selhip_ctx_set_param(selhip_ctx* ctx, const char* name, int value);
  * "pairs_route_used" (stage 1 of the last pair-list pass, section 2e),
  * "matrix_smh_path_used" (the kernel of the last matrix call with a SuperMinHash measure, section 2f: 1 = the register-tile kernel
  * of m = 128, 256, 512 or 1024 buckets, 0 = the generic kernel of every other m; -1 = none yet),
- * "clusters_last" (the number of clusters the last selhip_ctx_cluster call found, section 2g; -1 = none yet) */
+ * "clusters_last" (the number of clusters the last selhip_ctx_cluster call found, section 2g; -1 = none yet),
+ * "greedy_clusters_last" and "greedy_rounds_last" (the clusters the last selhip_ctx_cluster_greedy call found and the rounds its
+ * selection took, section 2h; -1 = none yet) */
 int selhip_ctx_get_param(const selhip_ctx* ctx, const char* name, int* value);
 /* Stage 2 grouping (default on): the pairs that reach the HLL-14 stage are bucketed by query row (counting sort) so
  * that waves running side by side on one XCD share their query row in L2.  0 = off (same kernel, list as produced). */
@@ -465,6 +467,7 @@ int selhip_ctx_set_topk_rounds(selhip_ctx* ctx, int64_t rows);
  * from the passes, so a matrix call changes no other name's per-pass figure.  "matrix_smh" is the kernel of a matrix call with a
  * SuperMinHash measure, averaged over THOSE calls: "matrix" stays the HLL kernel's figure and count.
  * "cluster" is the launches of selhip_ctx_cluster (section 2g), averaged over the CLUSTER CALLS since the last reset, counted apart likewise.
+ * "greedy" is the launches of selhip_ctx_cluster_greedy (section 2h), averaged over the GREEDY CALLS since the last reset, counted apart likewise.
  * selhip_ctx_kernel_launches: launches of that kernel per pass. */
 double selhip_ctx_kernel_ms(const selhip_ctx* ctx, const char* name);
 double selhip_ctx_kernel_launches(const selhip_ctx* ctx, const char* name);
@@ -730,6 +733,62 @@ typedef struct {
 int selhip_ctx_cluster(selhip_ctx* ctx, double min_value, int rep_rule,
                        const selhip_clusters_t* out, int64_t* n_clusters_out);
 
+/* ---------------------------------------------------------------------------------------------------
+ * 2h. Greedy representative clusters of the result list: the CD-HIT / UCLUST scheme, the one dereplication tools use to choose
+ *     representatives.  Single linkage (2g) chains: with records A-B and B-C and none for A-C all three share a cluster, whose
+ *     representative may have no record with some member at all.  Here every member is within min_value of ITS OWN representative,
+ *     and no two representatives are within min_value of each other.
+ *     THE GRAPH: the vertices are the n ranks of the context's set; the edges are the records of the result list with
+ *     `jaccard` >= min_value in f64 and i != k.  -INFINITY takes every record, NaN min_value is SELHIP_E_BADARG, a NaN value is never an
+ *     edge.  Repeated records, and the two directed records of a top-k list, are ONE edge; its value is the greatest of theirs.
+ *     THE ORDER: every vertex has a 64-bit key and a greater key is visited first; keys are distinct, each ends in the reversed rank
+ *       SELHIP_REP_MAX_DEGREE  (degree, reversed rank): the best connected first, ties to the smaller rank; degree as d_degree counts
+ *       SELHIP_REP_MIN_RANK    reversed rank: the smallest genome first
+ *       SELHIP_REP_MAX_RANK    rank: the largest sketch first, the CD-HIT order
+ *       SELHIP_REP_PRIORITY    (d_priority[g], reversed rank): d_priority is the caller's uint32_t[n] in device memory, a quality score
+ *                              for example; accepted by this entry only.  d_priority NULL with this rule, or non-NULL with another
+ *                              rule, is SELHIP_E_BADARG; so is any other rule.
+ *     THE REPRESENTATIVES: visit the vertices by descending key; a vertex is a representative if and only if none of its neighbours is
+ *     one already -- the lexicographically first maximal independent set of the graph under the order.  A vertex without an edge is one.
+ *     THE ASSIGNMENT: every other vertex g belongs to the representative r for which the edge {g, r} has the greatest value; values
+ *     compare as f64 (-0.0 equals +0.0), ties go to the smaller rank r.  A member's best edge to a NON-representative assigns nothing.
+ *     OUTPUTS, each a pure function of the record list, min_value, the rule and d_priority, bit for bit, whatever order the device
+ *     worked in:
+ *       d_rep_of[g]        g's representative; a representative has itself
+ *       d_value[g]         the value of the edge {g, d_rep_of[g]} with the record's bits (a zero of either sign is written +0.0);
+ *                          1.0 for a representative
+ *       d_cluster[g]       the dense id in 0 .. C-1 of g's cluster, the clusters numbered by ascending representative rank
+ *       d_degree[g]        the RECORDS with `jaccard` >= min_value in which g appears as i or k, exactly as in 2g -- records, not
+ *                          distinct partners, and a record with i == k counts twice for its genome though it is no edge
+ *       d_cluster_size[c]  members of cluster c, the representative included   (the first C entries are written)
+ *       d_cluster_rep[c]   its representative's rank                           (the first C entries are written)
+ *     Every array is the caller's device memory of n elements; any of the six pointers may be NULL (that output is not written, and the
+ *     launches that only serve it are skipped); *n_clusters_out (may be NULL) receives C.  n == 0: C = 0.
+ *     Accepted lists and SELHIP_E_STATE cases: those of 2g (not after a query pass, not before any finished pass, not while a pass is
+ *     pending).  The call reads the list and writes only `out` and scratch the context owns: the list, selhip_ctx_result_count, the
+ *     statistics, selhip_ctx_last_attempts, the top-k settings, the signature cache and "clusters_last" are as they were, and a context
+ *     that never calls it launches what it always launched.  It runs on the context's stream and returns when the outputs are complete.
+ *     HOW (csrc/kernel_greedy.cuh): rounds of one launch over the records and one over the vertices -- a vertex none of whose earlier
+ *     neighbours is undecided or a representative becomes one, a vertex behind a representative a member -- until a device counter
+ *     reads no undecided vertex; no kernel waits for another lane.  Sparse lists take about ten rounds; a path whose keys ascend along
+ *     it takes one round per vertex (short launches).  get_param "greedy_rounds_last": the first round after which no vertex was
+ *     undecided (a list without records: 1; n == 0: 0); "greedy_clusters_last": C; both -1 = none yet.  Timed as "greedy" in
+ *     selhip_ctx_kernel_ms: per greedy call, counted apart from the passes as "cluster" is.
+ *     Not built: query passes, the host-side lists of selhip_multi_select and selhip_ooc_select (selhip_greedy_representatives takes
+ *     any edge list), average or complete linkage, re-clustering of members around new centroids, distinct-partner degrees.
+ * --------------------------------------------------------------------------------------------------- */
+#define SELHIP_REP_PRIORITY 3
+typedef struct {
+    int32_t* d_rep_of;       /* [n]  the genome's representative (itself for a representative)      */
+    double*  d_value;        /* [n]  value of the edge to it; 1.0 for a representative              */
+    int32_t* d_cluster;      /* [n]  dense id 0 .. C-1, numbered by ascending representative rank   */
+    int32_t* d_degree;       /* [n]  records of the graph in which the genome appears as i or k     */
+    int32_t* d_cluster_size; /* [n]  first C entries written: members of cluster c                  */
+    int32_t* d_cluster_rep;  /* [n]  first C entries written: representative rank of cluster c      */
+} selhip_greedy_t;           /* caller's device memory; any pointer may be NULL (not written)       */
+int selhip_ctx_cluster_greedy(selhip_ctx* ctx, double min_value, int order_rule, const uint32_t* d_priority,
+                              const selhip_greedy_t* out, int64_t* n_clusters_out);
+
 
 /* ---------------------------------------------------------------------------------------------------
  * 3. Building blocks (device pointers), used by the launchers above and exposed for tests.
@@ -768,6 +827,15 @@ int selhip_hll_fold(const uint8_t* d_hll, int64_t n_genomes, int p, int p_aux, u
  * written, and no kernel reads or writes outside the arrays because of it.  n == 0 and n_pairs == 0 are legal (n_pairs == 0: n
  * singletons); 0 <= n <= 2^31 - 1, n_pairs any int64 >= 0.  The labels depend on the edge set alone.  Waits for the stream. */
 int selhip_components(const selhip_int2_t* d_pairs, int64_t n_pairs, int64_t n, int32_t* d_label /*[n]*/, void* hip_stream);
+/* The representatives of the greedy clustering (section 2h; csrc/kernel_greedy.cuh) over an edge list: d_is_rep[g] = 1 where g is in the
+ * lexicographically first maximal independent set of the undirected graph on the vertices 0 .. n - 1 with one edge {x, y} per entry of
+ * d_pairs (device memory, 8-byte aligned), 0 elsewhere.  The vertices are visited by descending d_key[g] (device memory, uint64_t[n]);
+ * equal keys: the smaller vertex goes first; NULL d_key: key = vertex.  Entries with x == y and entries listed twice are legal and change
+ * nothing.  *rounds_out (may be NULL): the rounds the selection took, at most those of the scheme with every read stale
+ * (n_pairs == 0: 1; n == 0: 0).  Arguments, ranges, the SELHIP_E_BADARG of an entry with a vertex outside [0, n) -- d_is_rep is not
+ * written -- and the messages are those of selhip_components.  Waits for the stream. */
+int selhip_greedy_representatives(const selhip_int2_t* d_pairs, int64_t n_pairs, int64_t n, const uint64_t* d_key /* [n] or NULL */,
+                                  uint8_t* d_is_rep /* [n] */, int64_t* rounds_out /* may be NULL */, void* hip_stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * 4. Synthetic sketches generated directly in HBM (csrc/synth.hpp; stands in for the FASTA->sketch
