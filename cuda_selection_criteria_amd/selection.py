@@ -176,6 +176,10 @@ class Selector:
     def __exit__(self, *a):
         self.close()
 
+    def set_stream(self, stream: Optional[int]):
+        """all work of this context runs on `stream` from now on (a hipStream_t as an integer, e.g. torch's Stream.cuda_stream; None = the null stream)"""
+        check(self._lib.selhip_ctx_set_stream(self._ctx, C.c_void_p(stream)), self._ctx)
+
     # -- sketches ---------------------------------------------------------------------------------
     def upload(self, hll: np.ndarray, aux: np.ndarray, cards: Optional[np.ndarray] = None, p_hll: int = 14):
         hll = np.ascontiguousarray(hll, dtype=np.uint8)

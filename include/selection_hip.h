@@ -134,7 +134,16 @@ void selhip_ctx_destroy(selhip_ctx* ctx);
 /* message of the last failure on this context (never NULL); ctx may be NULL for creation errors */
 const char* selhip_last_error(const selhip_ctx* ctx);
 
-/* Run all work of this context on `hip_stream` (a hipStream_t passed as void*; NULL = null stream). */
+/* Run all work of this context on `hip_stream` (a hipStream_t passed as void*; NULL = null stream).
+ * This holds on a NON-BLOCKING stream (hipStreamNonBlocking, e.g. a torch pool stream), which the null stream does not wait for:
+ * every launch, memset, copy and sort of every entry of sections 2 - 2h goes to the stream, the second chunk lane of a pass
+ * (selhip_ctx_set_pipeline) starts behind an event of the stream and is joined by another, and state a context keeps (signature
+ * cache, query index, counter sets) is complete before selhip_ctx_set_stream returns with another stream.  A call on a context whose
+ * buffers are sized neither touches the null stream nor waits for the device (tests/test_streams_gpu.py runs every entry beside a
+ * blocked null stream).  What DOES wait for the whole device is a call that frees device memory (hipFree): a pass that outgrows one
+ * of its lists and repeats; the first SELHIP_ALGO_INDEX pass behind an upload / attach of the database, whose sort scratch goes away
+ * when the index stands; any buffer that grows; and, in section 3, selhip_hll_bitslice, selhip_hll_union_hist_planes,
+ * selhip_components and selhip_greedy_representatives, whose scratch lives for the call. */
 int selhip_ctx_set_stream(selhip_ctx* ctx, void* hip_stream);
 /* Chunk lanes of a pass (smh_a / hll_a+smh_a): the query rows are cut into `chunks` equal-pair chunks and every chunk runs its
  * whole chain (join, verify, [auxiliary criterion], grouping, HLL union histograms, estimate) on one of two internal streams
