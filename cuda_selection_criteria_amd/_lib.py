@@ -44,6 +44,10 @@ class Clusters(C.Structure):          # selhip_clusters_t: the five outputs of s
                 ("d_cluster_rep", C.c_void_p)]
 
 
+class Merged(C.Structure):            # selhip_merged_t: the five outputs of selhip_ctx_merge_groups, device pointers or NULL
+    _fields_ = [("d_hll", C.c_void_p), ("d_aux", C.c_void_p), ("d_aux_hll", C.c_void_p), ("d_cards", C.c_void_p), ("d_size", C.c_void_p)]
+
+
 class Greedy(C.Structure):            # selhip_greedy_t: the six outputs of selhip_ctx_cluster_greedy, device pointers or NULL
     _fields_ = [("d_rep_of", C.c_void_p), ("d_value", C.c_void_p), ("d_cluster", C.c_void_p), ("d_degree", C.c_void_p),
                 ("d_cluster_size", C.c_void_p), ("d_cluster_rep", C.c_void_p)]
@@ -64,6 +68,7 @@ BANDING_CPU, BANDING_CUDA = 0, 1
 TOPK_ROUNDS_AUTO = -1                  # SELHIP_TOPK_ROUNDS_AUTO: Selector.set_topk_rounds picks the rows per round
 REP_MAX_DEGREE, REP_MIN_RANK, REP_MAX_RANK = 0, 1, 2   # SELHIP_REP_*: the representative of a cluster (Selector.cluster)
 REP_PRIORITY = 3                       # SELHIP_REP_PRIORITY: the caller's scores order the greedy clusters (Selector.cluster_greedy alone)
+MERGE_SEGMENT = 64                     # SELHIP_MERGE_SEGMENT: member rows one lane of the merge reduces at most (Selector.merge, merge_sketches)
 TOPK_MAX = 1024                        # SELHIP_TOPK_MAX: largest k of Selector.set_query_topk and Selector.set_allpairs_topk
 
 _vp, _i, _i64, _d, _sz, _cp = C.c_void_p, C.c_int, C.c_int64, C.c_double, C.c_size_t, C.c_char_p
@@ -135,6 +140,8 @@ HIP_SYMBOLS = {
     "selhip_components": (_i, [_vp, _i64, _i64, _vp, _vp]),
     "selhip_ctx_cluster_greedy": (_i, [_vp, _d, _i, _vp, C.POINTER(Greedy), C.POINTER(_i64)]),
     "selhip_greedy_representatives": (_i, [_vp, _i64, _i64, _vp, _vp, C.POINTER(_i64), _vp]),
+    "selhip_ctx_merge_groups": (_i, [_vp, _vp, _i64, C.POINTER(Merged)]),
+    "selhip_merge_sketches": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "selhip_smh_a_pairs": (_i, [_vp, _i, _i, _i, _vp, _i64, _vp, _vp]),
     "selhip_hll_union_hist": (_i, [_vp, _i, _vp, _i64, _vp, _vp]),
     "selhip_hll_bitslice": (_i, [_vp, _i64, _vp, _vp, _vp, _vp]),
@@ -191,6 +198,7 @@ HOST_SYMBOLS = {
     "selhost_synth_generate": (_i, [C.POINTER(Synth), _i64, _i64, _vp, _vp, _vp, _i]),
     "selhost_shard_rows": (_i, [_i64, _vp, _i64, _i, _vp]),
     "selhost_hll_fold": (_i, [_vp, _i64, C.c_uint, C.c_uint, _vp]),
+    "selhost_merge_sketches": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp]),
     "selhost_version": (_cp, []),
 }
 

@@ -58,6 +58,7 @@ void selhip_ctx_destroy(selhip_ctx* c) {
     release_topk(c);
     release_cluster(c);
     release_greedy(c);
+    release_merge(c);
     if (c->h_pc) (void)hipHostFree(c->h_pc);
     if (c->st_stage1) {
         (void)hipStreamDestroy(c->st_stage1);
@@ -761,7 +762,7 @@ int selhip_ctx_timing(selhip_ctx* c, int enable) {
     drain_timers(c);
     for (int t = 0; t < T_COUNT; ++t) { c->timers[t].total_ms = 0; c->timers[t].launches = 0; c->timers[t].span_ms = 0; }
     c->timing = enable == 2 ? 2 : (enable != 0 ? 1 : 0);
-    c->timed_passes = 0; c->timed_matrix_calls = 0; c->timed_matrix_smh_calls = 0; c->timed_cluster_calls = 0; c->timed_greedy_calls = 0;
+    c->timed_passes = 0; c->timed_matrix_calls = 0; c->timed_matrix_smh_calls = 0; c->timed_cluster_calls = 0; c->timed_greedy_calls = 0; c->timed_merge_calls = 0;
     return SELHIP_OK;
 }
 
@@ -770,7 +771,7 @@ double selhip_ctx_kernel_ms(const selhip_ctx* c, const char* name) {
     if (!c->pending) drain_timers(const_cast<selhip_ctx*>(c));
     for (int t = 0; t < T_COUNT; ++t)
         if (!std::strcmp(name, kTimerNames[t])) {
-            const long passes = t == T_MATRIX ? c->timed_matrix_calls : t == T_MATRIX_SMH ? c->timed_matrix_smh_calls : t == T_CLUSTER ? c->timed_cluster_calls : t == T_GREEDY ? c->timed_greedy_calls : c->timed_passes;
+            const long passes = t == T_MATRIX ? c->timed_matrix_calls : t == T_MATRIX_SMH ? c->timed_matrix_smh_calls : t == T_CLUSTER ? c->timed_cluster_calls : t == T_GREEDY ? c->timed_greedy_calls : t == T_MERGE ? c->timed_merge_calls : c->timed_passes;
             return (c->timers[t].launches && passes) ? c->timers[t].total_ms / (double)passes : -1.0;
         }
     const long passes = c->timed_passes;
@@ -784,7 +785,7 @@ double selhip_ctx_kernel_launches(const selhip_ctx* c, const char* name) {
     if (!c->pending) drain_timers(const_cast<selhip_ctx*>(c));
     for (int t = 0; t < T_COUNT; ++t)
         if (!std::strcmp(name, kTimerNames[t])) {
-            const long passes = t == T_MATRIX ? c->timed_matrix_calls : t == T_MATRIX_SMH ? c->timed_matrix_smh_calls : t == T_CLUSTER ? c->timed_cluster_calls : t == T_GREEDY ? c->timed_greedy_calls : c->timed_passes;
+            const long passes = t == T_MATRIX ? c->timed_matrix_calls : t == T_MATRIX_SMH ? c->timed_matrix_smh_calls : t == T_CLUSTER ? c->timed_cluster_calls : t == T_GREEDY ? c->timed_greedy_calls : t == T_MERGE ? c->timed_merge_calls : c->timed_passes;
             return passes ? (double)c->timers[t].launches / (double)passes : 0.0;
         }
     return -1.0;

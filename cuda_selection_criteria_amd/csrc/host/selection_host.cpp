@@ -536,4 +536,38 @@ int selhost_hll_fold(const uint8_t* in, int64_t n, unsigned p, unsigned p_aux, u
     return SELHOST_OK;
 }
 
+// ---- sketches merged by group (host twin of selhip_merge_sketches): maximum of the registers, unsigned minimum of the buckets ------
+int selhost_merge_sketches(const uint8_t* hll, const uint64_t* smh, const uint8_t* aux_hll, int64_t n, int p, int m, int p_aux,
+                           const int32_t* group, int64_t n_groups, uint8_t* hll_out, uint64_t* smh_out, uint8_t* aux_out, int32_t* size_out) {
+    if (!hll != !hll_out || !smh != !smh_out || !aux_hll != !aux_out)
+        return fail(SELHOST_E_BADARG, "merge_sketches: the input and output of a sketch kind must both be given or both be NULL");
+    if (n < 0 || n_groups < 0 || n > 0x7FFFFFFFll || n_groups > 0x7FFFFFFFll) return fail(SELHOST_E_BADARG, "merge_sketches: 0 <= n, n_groups <= 2^31 - 1");
+    if (p < 4 || p > 20) return fail(SELHOST_E_BADARG, "merge_sketches: p %d out of range [4,20]", p);
+    if (smh && m <= 0) return fail(SELHOST_E_BADARG, "merge_sketches: m must be > 0 with SuperMinHash rows");
+    if (aux_hll && (p_aux < 4 || p_aux > 20)) return fail(SELHOST_E_BADARG, "merge_sketches: p_aux %d out of range [4,20]", p_aux);
+    if (n > 0 && !group) return fail(SELHOST_E_BADARG, "merge_sketches: null group array");
+    if (((uintptr_t)smh | (uintptr_t)smh_out) & 7) return fail(SELHOST_E_BADARG, "merge_sketches: smh pointers must be 8-byte aligned");
+    if (((uintptr_t)group | (uintptr_t)size_out) & 3) return fail(SELHOST_E_BADARG, "merge_sketches: group and size arrays must be 4-byte aligned");
+    int64_t bad = 0, bad_at = -1;
+    for (int64_t i = 0; i < n; ++i)
+        if (group[i] < -1 || group[i] >= n_groups) { if (!bad++) bad_at = i; }
+    if (bad)
+        return fail(SELHOST_E_BADARG, "merge_sketches: the group array holds %lld invalid entries (an id outside [-1, %lld)); entry %lld is one",
+                    (long long)bad, (long long)n_groups, (long long)bad_at);
+    const size_t hb = (size_t)1 << p, ab = aux_hll ? (size_t)1 << p_aux : 0, G = (size_t)n_groups;
+    if (hll_out) std::memset(hll_out, 0, G * hb);
+    if (aux_out) std::memset(aux_out, 0, G * ab);
+    if (smh_out) std::memset(smh_out, 0xFF, G * (size_t)m * 8);
+    if (size_out) std::memset(size_out, 0, G * sizeof(int32_t));
+    for (int64_t i = 0; i < n; ++i) {
+        if (group[i] < 0) continue;
+        const size_t g = (size_t)group[i];
+        if (size_out) size_out[g] += 1;
+        if (hll_out) for (size_t j = 0; j < hb; ++j) hll_out[g * hb + j] = std::max(hll_out[g * hb + j], hll[(size_t)i * hb + j]);
+        if (aux_out) for (size_t j = 0; j < ab; ++j) aux_out[g * ab + j] = std::max(aux_out[g * ab + j], aux_hll[(size_t)i * ab + j]);
+        if (smh_out) for (size_t j = 0; j < (size_t)m; ++j) smh_out[g * m + j] = std::min(smh_out[g * m + j], smh[(size_t)i * m + j]);
+    }
+    return SELHOST_OK;
+}
+
 }  // extern "C"

@@ -96,7 +96,21 @@
 //   -W <file>   with -L -Z greedy: the visiting order is a score per genome, the greatest first (ties to the smaller genome): lines of
 //               path <TAB> unsigned score (up to 2^32 - 1), one per genome of the -l list, in any order; read and checked before any
 //               device work.  Not with -Y
+//   -P <dir>    one merged sketch set per group, written into <dir> (created if missing): the union sketch of the group's genomes, merged on
+//               the device (selhip_ctx_merge_groups: the maximum of the HLL registers, the minimum of the SuperMinHash buckets -- bit for
+//               bit the sketches build_sketch would write for the members' records in one FASTA).  <dir>/<name>.hll, <dir>/<name>.smh<m>
+//               where the run reads .smh<m> files (-c smh_a | smh_c), <dir>/<name>.hll_<p> where it reads or folds auxiliary sketches
+//               (-c hll_a | hll_an), and <dir>/filelist.txt, one <dir>/<name> per line in group order: the directory is a database for
+//               selection -l <dir>/filelist.txt [-q ...].  The groups come from -L or from -I:
+//               with -L: the clusters of that run (-Z, -T, -Y, -W as ever); <name> is cluster_<id>, zero-padded to the width of the largest
+//               id.  Stdout and the -L table stay byte for byte what they are without -P.
+//               Not without -L or -I, and not with -q, -M, -g, -B or -r
+//   -I <file>   with -P and without -L: the groups are read from <file>, no pass runs (as with -M): lines path <TAB> group_name, the
+//               groups numbered by first appearance, <name> = group_name (not empty, no '/'); a path that is not in the -l list is a
+//               format error with its line number; a genome of the list that the file does not name is in no group.  -c and -a say which
+//               sketch files are in play, as for a pass.  Not with -L, -p, -k, -K or -o
 //   -x          usage
+#include <sys/stat.h>
 #include <unistd.h>
 
 #include <algorithm>
@@ -125,6 +139,59 @@ static int g_cluster_rep = SELHIP_REP_MAX_DEGREE;   // -Y
 static bool g_cluster_greedy = false;            // -Z greedy
 static std::string g_priority_file = "";        // -W: the scores that order the greedy clusters ("" = none)
 static std::vector<uint32_t> g_priority;         // ... in rank order, read by load_priorities
+static std::string g_merge_dir = "";            // -P: one merged sketch set per group goes into this directory ("" = none)
+static std::string g_groups_file = "";          // -I: the groups of -P, read from this file ("" = the clusters of -L)
+static unsigned g_merge_m = 0, g_merge_p_aux = 0;   // the SuperMinHash buckets and the auxiliary precision in play in the run (0 = none)
+
+// -P: the sketches of the context's set merged by d_group (device, rank order) into n_groups sets named names[], written into g_merge_dir
+static int write_merged(selhip_ctx* ctx, const int32_t* d_group, int64_t n_groups, const std::vector<std::string>& names) {
+    const size_t G = (size_t)n_groups, hb = (size_t)1 << 14, ab = g_merge_p_aux ? (size_t)1 << g_merge_p_aux : 0, m = g_merge_m;
+    std::vector<uint8_t> hll(G * hb), aux_hll(G * ab);
+    std::vector<uint64_t> smh(G * m);
+    selhip_merged_t out{nullptr, nullptr, nullptr, nullptr, nullptr};
+    void* d = nullptr;
+    int r = G ? selhip_malloc(&d, G * (hb + ab + m * 8)) : 0;
+    if (!r && G) {
+        // the byte rows first: both stay 16-byte aligned, the buckets behind them 8-byte aligned
+        out.d_hll = static_cast<uint8_t*>(d);
+        if (ab) out.d_aux_hll = out.d_hll + G * hb;
+        if (m) out.d_aux = reinterpret_cast<uint64_t*>(out.d_hll + G * (hb + ab));
+    }
+    if (!r) r = selhip_ctx_merge_groups(ctx, d_group, n_groups, &out);
+    if (!r && G) r = selhip_memcpy_d2h(hll.data(), out.d_hll, G * hb);
+    if (!r && G && ab) r = selhip_memcpy_d2h(aux_hll.data(), out.d_aux_hll, G * ab);
+    if (!r && G && m) r = selhip_memcpy_d2h(smh.data(), out.d_aux, G * m * 8);
+    if (d) selhip_free(d);
+    if (r) return r;
+    mkdir(g_merge_dir.c_str(), 0777);                                           // (exists already: fine; anything else shows at the first file)
+    std::string list;
+    int hr = 0;
+    for (size_t c = 0; c < G && !hr; ++c) {
+        const std::string base = g_merge_dir + "/" + names[c];
+        hr = selhost_write_hll((base + ".hll").c_str(), hll.data() + c * hb, 14);
+        if (!hr && m) hr = selhost_write_smh((base + ".smh" + std::to_string(m)).c_str(), smh.data() + c * m, (uint32_t)m);
+        if (!hr && ab) hr = selhost_write_hll((base + ".hll_" + std::to_string(g_merge_p_aux)).c_str(), aux_hll.data() + c * ab, g_merge_p_aux);
+        list += base + "\n";
+    }
+    if (hr) { std::cerr << "selection: -P: " << selhost_last_error() << "\n"; return 5; }
+    std::ofstream f(g_merge_dir + "/filelist.txt", std::ios::binary);
+    f << list;
+    f.close();
+    if (!f) { std::cerr << "selection: -P: cannot write '" << g_merge_dir << "/filelist.txt'\n"; return 5; }
+    return 0;
+}
+
+// -L ... -P: the clusters as groups, named cluster_<id> zero-padded to the width of the largest id
+static int write_merged_clusters(selhip_ctx* ctx, const int32_t* d_cluster, int64_t n_clusters) {
+    if (g_merge_dir.empty()) return 0;
+    const size_t width = std::to_string(n_clusters > 0 ? n_clusters - 1 : 0).size();
+    std::vector<std::string> names((size_t)n_clusters);
+    for (int64_t c = 0; c < n_clusters; ++c) {
+        const std::string id = std::to_string(c);
+        names[(size_t)c] = "cluster_" + std::string(width - id.size(), '0') + id;
+    }
+    return write_merged(ctx, d_cluster, n_clusters, names);
+}
 
 // -W: the scores of the n genomes of ds, checked on the host; 0 = fine (or no -W)
 static int load_priorities(const selhost_dataset* ds, int64_t n) {
@@ -183,6 +250,7 @@ static int write_greedy(selhip_ctx* ctx, const selhost_dataset* ds, int64_t n) {
     if (!r && n) r = selhip_memcpy_d2h(cluster.data(), out.d_cluster, (size_t)n * sizeof(int32_t));
     if (!r && n) r = selhip_memcpy_d2h(degree.data(), out.d_degree, (size_t)n * sizeof(int32_t));
     if (!r && n_clusters) r = selhip_memcpy_d2h(size.data(), out.d_cluster_size, (size_t)n_clusters * sizeof(int32_t));
+    if (!r) r = write_merged_clusters(ctx, out.d_cluster, n_clusters);
     if (d) selhip_free(d);
     if (r) return r;
     std::vector<int64_t> rank_of_line((size_t)n);
@@ -217,6 +285,7 @@ static int write_clusters(selhip_ctx* ctx, const selhost_dataset* ds, int64_t n)
     if (!r && n) r = selhip_memcpy_d2h(degree.data(), out.d_degree, (size_t)n * sizeof(int32_t));
     if (!r && n_clusters) r = selhip_memcpy_d2h(size.data(), out.d_cluster_size, (size_t)n_clusters * sizeof(int32_t));
     if (!r && n_clusters) r = selhip_memcpy_d2h(rep.data(), out.d_cluster_rep, (size_t)n_clusters * sizeof(int32_t));
+    if (!r) r = write_merged_clusters(ctx, out.d_cluster, n_clusters);
     if (d) selhip_free(d);
     if (r) return r;
     std::vector<int64_t> rank_of_line((size_t)n);
@@ -324,6 +393,7 @@ static int run_neighbours(const std::string& list_file, int crit, float threshol
     const bool reads_smh = crit == SELHIP_CRIT_SMH_A || crit == SELHIP_CRIT_SMH_C;
     const unsigned m = reads_smh ? (unsigned)aux_bytes / 8 : 0;
     const unsigned p_aux = reads_smh || crit == SELHIP_CRIT_NONE ? 0 : (unsigned)__builtin_ctz(aux_bytes ? aux_bytes : 1);
+    g_merge_m = m; g_merge_p_aux = p_aux;
     selhost_dataset* ds = nullptr;
     if (selhost_dataset_load(&ds, list_file.c_str(), m, aux_files(p_aux), fp_mode, threads)) { std::cerr << selhost_last_error() << "\n"; return 1; }
     const int64_t n = selhost_dataset_size(ds);
@@ -417,6 +487,56 @@ static int run_matrix(const std::string& list_file, const std::string& query_fil
     return r ? 4 : hr ? 5 : 0;
 }
 
+// -I ... -P: no pass; the genomes of the list merged by the groups of g_groups_file.  m, p_aux: the sketch files in play, as for a pass
+static int run_merge_groups(const std::string& list_file, unsigned m, unsigned p_aux, int fp_mode, int threads) {
+    selhost_dataset* ds = nullptr;
+    if (selhost_dataset_load(&ds, list_file.c_str(), m, aux_files(p_aux), fp_mode, threads)) { std::cerr << "selection: -P: " << selhost_last_error() << "\n"; return 1; }
+    const int64_t n = selhost_dataset_size(ds);
+    std::unordered_map<std::string, int64_t> rank_of;
+    for (int64_t g = 0; g < n; ++g) rank_of.emplace(selhost_dataset_name(ds, g), g);
+    std::vector<int32_t> group((size_t)std::max<int64_t>(n, 1), -1);
+    std::vector<std::string> names;
+    std::unordered_map<std::string, int32_t> id_of;
+    std::ifstream f(g_groups_file, std::ios::binary);
+    if (!f) { std::cerr << "selection: -I: cannot read '" << g_groups_file << "'\n"; selhost_dataset_free(ds); return 5; }
+    std::string line;
+    for (int64_t line_no = 1; std::getline(f, line); ++line_no) {
+        if (line.empty()) continue;
+        const size_t tab = line.find('\t');
+        const std::string gname = tab == std::string::npos ? "" : line.substr(tab + 1);
+        const auto it = tab == std::string::npos ? rank_of.end() : rank_of.find(line.substr(0, tab));
+        if (it == rank_of.end() || gname.empty() || gname.find('/') != std::string::npos) {
+            std::cerr << "selection: -I: line " << line_no << " of '" << g_groups_file
+                      << "' is not 'path<TAB>group_name' for a genome of the -l list and a name that is not empty and holds no '/'\n";
+            selhost_dataset_free(ds);
+            return 5;
+        }
+        const auto ins = id_of.emplace(gname, (int32_t)names.size());
+        if (ins.second) names.push_back(gname);
+        group[(size_t)it->second] = ins.first->second;
+    }
+    std::vector<uint64_t> no_smh(m ? 0 : (size_t)(n > 0 ? n : 1), 0);
+    selhip_ctx* ctx = nullptr;
+    int r = selhip_device_count() > 0 ? selhip_ctx_create(&ctx, 0) : SELHIP_E_NODEVICE;
+    if (r) {
+        std::cerr << "selection: no MI355X (gfx950) device available: " << selhip_last_error(nullptr) << "\n";
+        selhost_dataset_free(ds);
+        return 3;
+    }
+    selhip_ctx_set_fp_mode(ctx, fp_mode);
+    void* d_group = nullptr;
+    r = selhip_ctx_upload(ctx, selhost_dataset_hll(ds), m ? selhost_dataset_aux(ds) : no_smh.data(), selhost_dataset_cards(ds), n, m ? (int)m : 1, 14);
+    if (!r && p_aux) r = load_aux_hll(ctx, ds, p_aux, false);
+    if (!r) r = selhip_malloc(&d_group, group.size() * sizeof(int32_t));
+    if (!r) r = selhip_memcpy_h2d(d_group, group.data(), group.size() * sizeof(int32_t));
+    if (!r) r = write_merged(ctx, static_cast<const int32_t*>(d_group), (int64_t)names.size(), names);
+    if (r && r != 5) std::cerr << "selection: " << selhip_last_error(ctx) << "\n";
+    if (d_group) selhip_free(d_group);
+    selhip_ctx_destroy(ctx);
+    selhost_dataset_free(ds);
+    return r == 5 ? 5 : r ? 4 : 0;
+}
+
 int main(int argc, char* argv[]) {
     std::string list_file = "";
     float threshold = 0.9f;              // selection_cuda.cpp:62
@@ -433,8 +553,9 @@ int main(int argc, char* argv[]) {
     std::string rounds_arg = "", cluster_min_arg = "", cluster_rep_arg = "";
     bool cluster_given = false, cluster_min_given = false, cluster_rep_given = false, linkage_given = false, priority_given = false;
     std::string linkage_arg = "";
+    bool merge_given = false, groups_given = false;
     int c;
-    while ((c = getopt(argc, argv, "xl:b:a:h:c:C:G:t:g:nA:F:B:o:r:q:k:K:p:M:UE:S:V:R:DL:T:Y:Z:W:")) != -1) {
+    while ((c = getopt(argc, argv, "xl:b:a:h:c:C:G:t:g:nA:F:B:o:r:q:k:K:p:M:UE:S:V:R:DL:T:Y:Z:W:P:I:")) != -1) {
         switch (c) {
             case 'x': std::cout << "Usage: -l -h -a -b [-c smh_a|hll_a|hll_an|none|smh_c -C c_min|-G gamma] [-t threads] [-g gpus] [-n] [-A auto|stream|sig] [-F 0|1] [-B block] [-o file] | -r file\n"
                                    "       -l db_list -q query_list -h -a [-c smh_a|hll_a|hll_an|none|smh_c -C c_min|-G gamma] [-n] [-A auto|stream|sig|index] [-F 0|1] [-k best_per_query]   (query-vs-database selection)\n"
@@ -449,7 +570,9 @@ int main(int argc, char* argv[]) {
                                    "       -l list -K best_per_genome -c smh_c -C c_min|-G gamma -a bytes -V smh -R rows|auto   (the same list in rounds of rows: memory for n K records and one round, not for every pair that shares a bucket)\n"
                                    "       -l list [-p pair_file | -K best_per_genome [-R rows]] ... -L clusters.tsv [-T min_value] [-Y max_degree|min_rank|max_rank]   (besides the output: the single-linkage clusters of the selected pairs, one line per genome: path, cluster, size, degree, representative)\n"
                                    "       ... -L clusters.tsv -Z single|greedy [-T min_value] [-Y max_degree|min_rank|max_rank | -W scores.tsv]   (-Z greedy: greedy representative clusters, CD-HIT style: genomes visited in the -Y order or by descending score, every other genome to its most similar representative; a sixth column: value to the representative)\n"
-                                   "       ... -c hll_a|hll_an -a bytes -D   (with -l, -q, -p, -k, -K, -g, -B: no .hll_<p> file is read, the auxiliary HLL sketches are folded from the .hll registers)\n"; return 0;
+                                   "       ... -c hll_a|hll_an -a bytes -D   (with -l, -q, -p, -k, -K, -g, -B: no .hll_<p> file is read, the auxiliary HLL sketches are folded from the .hll registers)\n"
+                                   "       ... -L clusters.tsv [-Z ...] -P dir   (besides the output: one merged sketch set per cluster in dir -- cluster_<id>.hll, .smh<m>, .hll_<p> -- and dir/filelist.txt, a database for -l)\n"
+                                   "       -l list [-c ... -a bytes] -I groups.tsv -P dir   (no selection: the genomes merged by the groups of 'path<TAB>group_name' lines, one sketch set per group_name in dir)\n"; return 0;
             case 'q': query_file = optarg; break;
             case 'p': pair_file = optarg; break;
             case 'M': matrix_file = optarg; matrix_given = true; break;
@@ -464,6 +587,8 @@ int main(int argc, char* argv[]) {
             case 'Y': cluster_rep_arg = optarg; cluster_rep_given = true; break;
             case 'Z': linkage_arg = optarg; linkage_given = true; break;
             case 'W': g_priority_file = optarg; priority_given = true; break;
+            case 'P': g_merge_dir = optarg; merge_given = true; break;
+            case 'I': g_groups_file = optarg; groups_given = true; break;
             case 'k': top_k = std::strtoll(optarg, nullptr, 10); topk_given = true; break;
             case 'K': nbr_k = std::strtoll(optarg, nullptr, 10); nbr_given = true; break;
             case 'B': ooc_block = std::stoll(optarg); break;
@@ -513,6 +638,25 @@ int main(int argc, char* argv[]) {
             return 2;
         }
         if (g_priority_file.empty()) { std::cerr << "selection: -W (with -L -Z greedy) needs the name of the file of scores\n"; return 2; }
+    }
+    // -P and -I: checked before any file is read or device opened
+    if (groups_given && !merge_given) { std::cerr << "selection: -I (the groups file) is an option of -P (one merged sketch set per group)\n"; return 2; }
+    if (merge_given) {
+        if (!cluster_given && !groups_given) {
+            std::cerr << "selection: -P (one merged sketch set per group) needs its groups: -L (the clusters of the selected pairs) or -I (a groups file)\n";
+            return 2;
+        }
+        if (cluster_given && groups_given) { std::cerr << "selection: -I (the groups file of -P) cannot be combined with -L; the groups are the one or the other\n"; return 2; }
+        const char* clash = !query_file.empty() ? "-q" : matrix_given ? "-M" : gpus_given ? "-g" : ooc_block != 0 ? "-B" : !dump_file.empty() ? "-r" : nullptr;
+        if (clash) {
+            std::cerr << "selection: -P (one merged sketch set per group) cannot be combined with " << clash
+                      << "; it merges the sketches one context holds on one device\n";
+            return 2;
+        }
+        const char* pass = !groups_given ? nullptr : !pair_file.empty() ? "-p" : topk_given ? "-k" : nbr_given ? "-K" : !out_file.empty() ? "-o" : nullptr;
+        if (pass) { std::cerr << "selection: -I (the groups file of -P) cannot be combined with " << pass << "; it runs no selection pass\n"; return 2; }
+        if (g_merge_dir.empty()) { std::cerr << "selection: -P needs the name of the directory to write\n"; return 2; }
+        if (groups_given && g_groups_file.empty()) { std::cerr << "selection: -I needs the name of the groups file\n"; return 2; }
     }
     if (cluster_given) {
         const char* clash = !query_file.empty() ? "-q" : matrix_given ? "-M" : gpus_given ? "-g" : ooc_block != 0 ? "-B" : !dump_file.empty() ? "-r" : nullptr;
@@ -747,6 +891,8 @@ int main(int argc, char* argv[]) {
     const bool reads_smh = crit == SELHIP_CRIT_SMH_A || crit == SELHIP_CRIT_SMH_C;
     const unsigned m = reads_smh ? (unsigned)aux_bytes / 8 : 0;                                      // selection.cpp:231
     const unsigned p_aux = reads_smh || crit == SELHIP_CRIT_NONE ? 0 : (unsigned)__builtin_ctz(aux_bytes ? aux_bytes : 1);   // :125
+    g_merge_m = m; g_merge_p_aux = p_aux;
+    if (groups_given) return run_merge_groups(list_file, m, p_aux, fp_mode, threads);
 
     selhost_dataset* ds = nullptr;
     int rc = selhost_dataset_load(&ds, list_file.c_str(), m, aux_files(p_aux), fp_mode, threads);

@@ -94,6 +94,20 @@ struct BitPlanes {
     void release() { bs.release(); gmax.release(); dev_max.release(); }
 };
 
+// scratch of a merge by group (kernel_merge.cuh, host_merge.hpp): selhip_ctx_merge_groups keeps one, selhip_merge_sketches owns one per call
+struct MergeScratch {
+    DevBuf<int> cnt, order;             // members per group (the scatter's cursors); the members in group order
+    DevBuf<u64> pk;                     // a level's scan input
+    DevBuf<u64> scan[kMergeMaxLevels];  // per level: member offset << 32 | output-row offset of every group, the totals in slot G
+    DevBuf<char> tmp;                   // rocPRIM scan scratch
+    DevBuf<uint4> part[2];              // partial rows of the levels before the last, ping-pong
+    DevBuf<MergeInfo> info;
+    void release() {
+        cnt.release(); order.release(); pk.release(); tmp.release(); part[0].release(); part[1].release(); info.release();
+        for (auto& s : scan) s.release();
+    }
+};
+
 // TWO sets of per_set counter blocks: pass k uses set k & 1 and its first kernel clears the other for pass k + 1 -- no memset dispatch
 // on the stream in steady state.  dirty: a pass claimed a set and did not get to the end of its enqueue (its first kernel may never have
 // run), or nothing has cleared the buffer yet, or the stream changed behind the clearing: the next claim clears both sets first, once
@@ -133,8 +147,8 @@ static_assert(kCounterBlocks == kMaxChunks + 1, "common.cuh: counter blocks per 
 constexpr int kMaxAuxP = SELHIP_MAX_AUX_P;   // auxiliary HLL precision accepted by every entry point: aux_fused_kernel counts in 16-bit bins (a bin holds up to 2^p_aux)
 constexpr long long kEnumPairs = 1ll << 26;    // hll_a / hll_an as first criterion: pairs listed per sub-pass (512 MiB of int2)
 
-enum { T_PREP = 0, T_STAGE1, T_HIST, T_SELECT, T_TOTAL, T_SIGBUILD, T_JOIN, T_VERIFY, T_AUX, T_GROUP, T_DENSE, T_TOPK, T_MATRIX, T_MATRIX_SMH, T_CLUSTER, T_GREEDY, T_COUNT };
-const char* kTimerNames[T_COUNT] = {"prep", "stage1", "hist", "select", "total", "sigbuild", "join", "verify", "aux", "group", "dense", "topk", "matrix", "matrix_smh", "cluster", "greedy"};
+enum { T_PREP = 0, T_STAGE1, T_HIST, T_SELECT, T_TOTAL, T_SIGBUILD, T_JOIN, T_VERIFY, T_AUX, T_GROUP, T_DENSE, T_TOPK, T_MATRIX, T_MATRIX_SMH, T_CLUSTER, T_GREEDY, T_MERGE, T_COUNT };
+const char* kTimerNames[T_COUNT] = {"prep", "stage1", "hist", "select", "total", "sigbuild", "join", "verify", "aux", "group", "dense", "topk", "matrix", "matrix_smh", "cluster", "greedy", "merge"};
 
 }  // namespace
 
@@ -353,6 +367,10 @@ struct selhip_ctx {
     int greedy_clusters_last = -1;      // the C of the last call ("greedy_clusters_last"), -1 = none yet
     int greedy_rounds_last = -1;        // its rounds ("greedy_rounds_last")
 
+    // sketches merged by group (selhip_ctx_merge_groups; kernel_merge.cuh, host_merge.hpp): scratch the call owns
+    MergeScratch mg;
+    DevBuf<uint8_t> mg_hll;             // the merged main registers where the caller takes the cardinalities without them
+
     int timing = 0;                     // 0 off, 1 every kernel scope, 2 dominant stage-1 kernel only
     int dominant_timer = T_STAGE1;
     int timed_kernel = 0;               // timing level 2 keeps the events of: 0 = the stage-1 kernel (join / stream), 1 = stage 2a ("timed_kernel")
@@ -361,6 +379,7 @@ struct selhip_ctx {
     long timed_matrix_smh_calls = 0;    // ... and those of the SuperMinHash measures: the divisor of "matrix_smh"
     long timed_cluster_calls = 0;       // cluster calls under timing: the divisor of "cluster"
     long timed_greedy_calls = 0;        // greedy calls under timing: the divisor of "greedy"
+    long timed_merge_calls = 0;         // merge calls under timing: the divisor of "merge"
     int last_attempts = 0;              // enqueues the last finished run needed (1 = nothing overflowed)
     KernelTimer timers[T_COUNT];
 };

@@ -49,6 +49,8 @@
 //                       one lane per record), flattened labels, dense ids, degrees, sizes and one representative per cluster
 //   kernel_greedy.cuh   greedy representative clusters of a record list (CD-HIT / UCLUST): the first maximal independent set under a key
 //                       order in rounds of one edge and one vertex launch, then every member to its most similar representative
+//   kernel_merge.cuh    sketches merged by group: a counting sort of the members, then a segmented reduction of the rows (u8 maximum of the
+//                       HLL registers, u64 minimum of the SuperMinHash buckets) in segments of at most SELHIP_MERGE_SEGMENT members per level
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (see csrc/Makefile).
 #include <hip/hip_runtime.h>
@@ -97,6 +99,7 @@
 #include "kernel_fold.cuh"
 #include "kernel_cluster.cuh"
 #include "kernel_greedy.cuh"
+#include "kernel_merge.cuh"
 
 #include "host_plan.hpp"         // host decisions that are plain arithmetic: build shape, pass plan, criterion constants, overflow rule
 #include "kernel_matrix.cuh"     // (behind host_plan.hpp: the kernel reads the unit, slab and mirror rules written there)
@@ -108,11 +111,13 @@
 #include "host_topk.hpp"         // top-k of a query pass and of an all-pairs pass: scratch, launches, the count the result accessors expose
 #include "host_cluster.hpp"      // single-linkage clusters: scratch and launches behind selhip_ctx_cluster / selhip_components
 #include "host_greedy.hpp"       // greedy representative clusters: rounds, scratch and launches behind selhip_ctx_cluster_greedy / selhip_greedy_representatives
+#include "host_merge.hpp"       // sketches merged by group: checks, levels and launches behind selhip_merge_sketches / selhip_ctx_merge_groups
 #include "abi_context.inc"       // C ABI: context (create, upload / attach, run, results, timing)
 #include "abi_pairs.inc"         // C ABI: pair-list passes (run_pairs)
 #include "abi_query.inc"         // C ABI: query passes (upload / attach queries, run_queries)
 #include "abi_matrix.inc"        // C ABI: dense matrices (matrix, query_matrix)
 #include "abi_cluster.inc"       // C ABI: clusters of the result list (cluster) and of a caller's edge list (components)
 #include "abi_greedy.inc"        // C ABI: greedy representative clusters of the result list (cluster_greedy) and of a caller's edge list (greedy_representatives)
+#include "abi_merge.inc"        // C ABI: sketches merged by group (merge_sketches, ctx_merge_groups)
 #include "abi_blocks.inc"        // C ABI: building blocks, synthetic sketches, sketch construction, memory helpers
 #include "abi_compat.inc"        // C ABI: drop-in launch_kernel_smh / launch_kernel_CBsmh

@@ -13,7 +13,7 @@ import numpy as np
 from . import _lib
 from ._lib import (ALGO_AUTO, BANDING_CPU, CRIT_HLL_A, CRIT_HLL_AN, CRIT_HLL_A_SMH_A, CRIT_NONE, CRIT_SMH_A, CRIT_SMH_C, ESTIMATOR_HLL, ESTIMATOR_SMH, F32, F64, FP_FMA,
                    MEASURE_CONTAINMENT, MEASURE_INTERSECTION, MEASURE_JACCARD, MEASURE_MAX_CONTAINMENT, MEASURE_SMH_JACCARD,
-                   MEASURE_SMH_MATCHES, MEASURE_UNION, MODE_CB_SMH, REP_MAX_DEGREE, REP_MAX_RANK, REP_MIN_RANK, REP_PRIORITY, TOPK_ROUNDS_AUTO, Clusters, Greedy, Pair, check, hip_lib,
+                   MEASURE_SMH_MATCHES, MEASURE_UNION, MODE_CB_SMH, REP_MAX_DEGREE, REP_MAX_RANK, REP_MIN_RANK, REP_PRIORITY, TOPK_ROUNDS_AUTO, Clusters, Greedy, Merged, Pair, check, hip_lib,
                    host_lib)
 
 # layout of selhip_pair_t {int32 i, k; double jaccard}
@@ -156,6 +156,8 @@ class Selector:
         self.n = 0
         self.m = 0
         self.n_q = None             # rows of the loaded query set (None: none; uploading / attaching the database drops it)
+        self.p_hll = 14             # precision of the main sketches (upload / attach)
+        self.p_aux = 0              # precision of the auxiliary sketches the context holds (0: none; upload / attach drops them)
         self._keep = None
 
     def close(self):
@@ -193,6 +195,7 @@ class Selector:
             cp = cards.ctypes.data
         check(self._lib.selhip_ctx_upload(self._ctx, hll.ctypes.data, aux.ctypes.data, cp, n, m, p_hll), self._ctx)
         self.n, self.m = n, m
+        self.p_hll, self.p_aux = p_hll, 0
         self.n_q = None                                                # (the library dropped the queries)
 
     def attach(self, hll_t, aux_t, cards_t=None, p_hll: int = 14):
@@ -208,6 +211,7 @@ class Selector:
         check(self._lib.selhip_ctx_attach(self._ctx, hll_t.data_ptr(), aux_t.data_ptr(), cp, n, m, p_hll), self._ctx)
         self._keep = (hll_t, aux_t, cards_t)
         self.n, self.m = n, m
+        self.p_hll, self.p_aux = p_hll, 0
         self.n_q = None
 
     def upload_queries(self, hll: np.ndarray, aux: np.ndarray, cards: Optional[np.ndarray] = None):
@@ -305,12 +309,14 @@ class Selector:
         aux_hll = np.ascontiguousarray(aux_hll, dtype=np.uint8)
         assert aux_hll.shape == (self.n, 1 << p_aux)
         check(self._lib.selhip_ctx_upload_aux_hll(self._ctx, aux_hll.ctypes.data, p_aux), self._ctx)
+        self.p_aux = p_aux
 
     def fold_aux_hll(self, p_aux: int):
         """the auxiliary HLL sketches of upload_aux_hll without their files: folded on the device from the main sketches the context
         holds, uploaded or attached (selhip_ctx_fold_aux_hll); p_aux in 4 .. min(p_hll, 15).  A snapshot: fold again after new sketches"""
         check(self._lib.selhip_ctx_fold_aux_hll(self._ctx, p_aux), self._ctx)
         self._keep_aux = None
+        self.p_aux = p_aux
 
     def fold_queries_aux_hll(self, p_aux: int):
         """the same for the query set (selhip_ctx_fold_queries_aux_hll), in place of upload_queries_aux_hll"""
@@ -321,6 +327,7 @@ class Selector:
         assert aux_hll_t.is_cuda and aux_hll_t.is_contiguous() and tuple(aux_hll_t.shape) == (self.n, 1 << p_aux)
         check(self._lib.selhip_ctx_attach_aux_hll(self._ctx, aux_hll_t.data_ptr(), p_aux), self._ctx)
         self._keep_aux = aux_hll_t
+        self.p_aux = p_aux
 
     def set_pipeline(self, chunks: int):
         """-1 auto, 0 off, 2..8 forced: overlap of stage 1 (next row chunk) with stage 2 (previous chunk)"""
@@ -580,6 +587,43 @@ class Selector:
         res["rounds"] = self.get_param("greedy_rounds_last")
         return res
 
+    # -- sketches merged by group ---------------------------------------------------------------------
+    def merge(self, groups, n_groups: Optional[int] = None, to_host: bool = False) -> dict:
+        """one union sketch per group of the context's set, merged on the device (selhip_ctx_merge_groups): the element-wise maximum of
+        the members' HLL registers and the unsigned minimum of their SuperMinHash buckets -- bit for bit the sketches of the members'
+        records concatenated.  groups: n int32 ids in rank order, -1 .. n_groups - 1 (-1 = in no group; a numpy array or a torch int32
+        device tensor), or the dict Selector.cluster / cluster_greedy returned (its "clusters" and "n_clusters").  n_groups None: the
+        largest id + 1.  Returns a dict, rows in group-id order: "hll" [G, 1 << p_hll] uint8, "aux" [G, m] (int64 view of the u64
+        buckets as a tensor, uint64 as a numpy array), "aux_hll" [G, 1 << p_aux] uint8 or None where the context holds no auxiliary
+        sketches, "cards" [G] float64 (report() of the merged main registers; 0 for an empty group), "sizes" [G] int32 -- torch tensors
+        on the device, or numpy arrays with to_host=True.  An id outside [-1, n_groups) raises (SELHIP_E_BADARG)"""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if isinstance(groups, dict):
+            n_groups = groups["n_clusters"] if n_groups is None else n_groups
+            groups = groups["clusters"]
+        if not hasattr(groups, "data_ptr"):
+            groups = torch.from_numpy(np.ascontiguousarray(groups, dtype=np.int32)).to(dev)
+        groups = groups.to(dev).contiguous()
+        assert groups.dtype == torch.int32 and groups.dim() == 1 and groups.numel() == self.n, "groups: n int32 ids in rank order"
+        if n_groups is None:
+            n_groups = int(groups.max().item()) + 1 if self.n else 0
+        g = int(n_groups)
+        with torch.cuda.device(dev):
+            hll = torch.empty((max(g, 0), 1 << self.p_hll), dtype=torch.uint8, device=dev)
+            aux = torch.empty((max(g, 0), self.m), dtype=torch.int64, device=dev)
+            aux_hll = torch.empty((max(g, 0), 1 << self.p_aux), dtype=torch.uint8, device=dev) if self.p_aux else None
+            cards = torch.empty(max(g, 0), dtype=torch.float64, device=dev)
+            sizes = torch.empty(max(g, 0), dtype=torch.int32, device=dev)
+            ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+            out = Merged(ptr(hll), ptr(aux), ptr(aux_hll), ptr(cards), ptr(sizes))
+            check(self._lib.selhip_ctx_merge_groups(self._ctx, ptr(groups), g, C.byref(out)), self._ctx)
+        res = {"hll": hll, "aux": aux, "aux_hll": aux_hll, "cards": cards, "sizes": sizes}
+        if to_host:
+            res = {k: None if v is None else v.cpu().numpy() for k, v in res.items()}
+            res["aux"] = res["aux"].view(np.uint64)
+        return res
+
     def result_count(self) -> int:
         return int(check(self._lib.selhip_ctx_result_count(self._ctx), self._ctx))
 
@@ -691,6 +735,183 @@ def greedy_representatives(pairs, n: int, keys=None, device: int = 0, to_host: b
                                                 key.data_ptr() if key is not None and n else None, is_rep.data_ptr() if n else None,
                                                 C.byref(rounds), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
     return (is_rep.cpu().numpy() if to_host else is_rep), int(rounds.value)
+
+
+def merge_sketches(hll=None, smh=None, aux_hll=None, groups=None, n_groups: Optional[int] = None, device: Optional[int] = 0):
+    """sketch rows merged by group (selhip_merge_sketches; device=None: the host twin selhost_merge_sketches, no GPU needed): hll [n, 1 << p]
+    uint8, smh [n, m] uint64 and aux_hll [n, 1 << p_aux] uint8 -- numpy arrays, any of them None -- reduced to n_groups rows each by
+    groups [n] (int32, -1 .. n_groups - 1, -1 = in no group; n_groups None: the largest id + 1): maximum of the registers, unsigned minimum of
+    the buckets.  Returns a dict of numpy arrays "hll", "smh", "aux_hll" (None where not given) and "sizes" [n_groups] int32.  An id outside
+    [-1, n_groups) raises and writes nothing"""
+    if groups is None:
+        raise ValueError("groups: one int32 id per row")
+    groups = np.ascontiguousarray(groups, dtype=np.int32)
+    n = groups.shape[0]
+    if n_groups is None:
+        n_groups = int(groups.max()) + 1 if n else 0
+    g = max(int(n_groups), 0)
+    rows = {}
+    for key, arr, dt in (("hll", hll, np.uint8), ("smh", smh, np.uint64), ("aux_hll", aux_hll, np.uint8)):
+        if arr is not None:
+            arr = np.ascontiguousarray(arr, dtype=dt)
+            if arr.ndim != 2 or arr.shape[0] != n:
+                raise ValueError(f"{key}: a 2-D array of {n} rows, got shape {arr.shape}")
+            if dt == np.uint8 and (arr.shape[1] < 16 or arr.shape[1] & (arr.shape[1] - 1)):
+                raise ValueError(f"{key} must be [n, 1 << p] with p in 4..20, got shape {arr.shape}")
+        rows[key] = arr
+    p = rows["hll"].shape[1].bit_length() - 1 if rows["hll"] is not None else 14
+    m = rows["smh"].shape[1] if rows["smh"] is not None else 0
+    p_aux = rows["aux_hll"].shape[1].bit_length() - 1 if rows["aux_hll"] is not None else 0
+    if device is None:
+        outs = {k: None if v is None else np.empty((g, v.shape[1]), dtype=v.dtype) for k, v in rows.items()}
+        sizes = np.empty(g, dtype=np.int32)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        rc = host_lib().selhost_merge_sketches(ptr(rows["hll"]), ptr(rows["smh"]), ptr(rows["aux_hll"]), n, p, m, p_aux, groups.ctypes.data, int(n_groups),
+                                               ptr(outs["hll"]), ptr(outs["smh"]), ptr(outs["aux_hll"]), sizes.ctypes.data)
+        if rc < 0:
+            raise ValueError(host_lib().selhost_last_error().decode())
+        return {**outs, "sizes": sizes}
+    import torch
+    dev = torch.device("cuda", device)
+    def to_dev(a):                                                           # (one spare row: a kind is present by its pointer, n == 0 included)
+        if a is None:
+            return None
+        a = a.view(np.int64) if a.dtype == np.uint64 else a
+        return torch.from_numpy(np.concatenate([a, np.zeros((1, a.shape[1]), dtype=a.dtype)])).to(dev)
+    with torch.cuda.device(dev):
+        d_in = {k: to_dev(v) for k, v in rows.items()}
+        d_out = {k: None if v is None else torch.empty((g + 1, v.shape[1]), dtype=v.dtype, device=dev) for k, v in d_in.items()}
+        d_groups = torch.from_numpy(np.concatenate([groups, np.zeros(1, dtype=np.int32)])).to(dev)
+        d_sizes = torch.empty(g + 1, dtype=torch.int32, device=dev)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        check(hip_lib().selhip_merge_sketches(ptr(d_in["hll"]), ptr(d_in["smh"]), ptr(d_in["aux_hll"]), n, p, m, p_aux, ptr(d_groups), int(n_groups),
+                                              ptr(d_out["hll"]), ptr(d_out["smh"]), ptr(d_out["aux_hll"]), ptr(d_sizes),
+                                              C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    res = {k: None if v is None else v[:g].cpu().numpy() for k, v in d_out.items()}
+    if res["smh"] is not None:
+        res["smh"] = res["smh"].view(np.uint64)
+    res["sizes"] = d_sizes[:g].cpu().numpy()
+    return res
+
+
+def selector_from_rows(hll_t, aux_t, cards_t, aux_hll_t=None, device: int = 0, fp_mode: int = FP_FMA):
+    """(Selector, order): sketch rows that lie on the device in any order -- the rows Selector.merge returns, in group-id order -- as the
+    set of a new Selector: sorted by cards (sort_by_card, the reference's order), gathered with selhip_permute_rows and attached.
+    hll_t uint8 [n, 1 << p], aux_t int64 [n, m], cards_t float64 [n], aux_hll_t uint8 [n, 1 << p_aux] or None; order[rank] = the row the
+    genome of that rank came from"""
+    import torch
+    lib = hip_lib()
+    dev = torch.device("cuda", device)
+    n = int(hll_t.shape[0])
+    order = sort_by_card(cards_t.cpu().numpy())
+    with torch.cuda.device(dev):
+        perm = torch.from_numpy(order).to(dev)
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+        def gather(t):
+            out = torch.empty_like(t)
+            if n and t.shape[1]:
+                check(lib.selhip_permute_rows(t.data_ptr(), out.data_ptr(), perm.data_ptr(), n, t.shape[1] * t.element_size(), st))
+            return out
+        hll_s, aux_s = gather(hll_t.contiguous()), gather(aux_t.contiguous())
+        aux_hll_s = gather(aux_hll_t.contiguous()) if aux_hll_t is not None else None
+        cards_s = cards_t[perm.long()].contiguous()
+        torch.cuda.current_stream(dev).synchronize()
+    sel = Selector(device, fp_mode)
+    sel.attach(hll_s, aux_s, cards_s, p_hll=int(hll_t.shape[1]).bit_length() - 1)
+    if aux_hll_s is not None:
+        sel.attach_aux_hll(aux_hll_s, int(aux_hll_t.shape[1]).bit_length() - 1)
+    return sel, order
+
+
+def read_groups(groups_file: str, names: Sequence[str]):
+    """(groups [n] int32 in the order of `names`, group names): a groups file of lines 'path<TAB>group_name' (what `selection -I` reads);
+    groups are numbered by first appearance, a genome that is not listed belongs to no group (-1).  ValueError with the line number for a
+    path that is not in names, a line without a tab, an empty group name or one containing '/'"""
+    rank = {nm: r for r, nm in enumerate(names)}
+    groups = np.full(len(names), -1, dtype=np.int32)
+    ids: dict = {}
+    with open(groups_file) as f:
+        for ln, line in enumerate(f, 1):
+            line = line.rstrip("\n")
+            if not line:
+                continue
+            path, tab, gname = line.partition("\t")
+            if not tab or path not in rank:
+                raise ValueError(f"{groups_file}:{ln}: expected 'path<TAB>group_name' with a path of the file list")
+            if not gname or "/" in gname:
+                raise ValueError(f"{groups_file}:{ln}: a group name is not empty and holds no '/'")
+            groups[rank[path]] = ids.setdefault(gname, len(ids))
+    return groups, list(ids)
+
+
+def write_merged(out_dir: str, group_names: Sequence[str], merged: dict, m: int, p_aux: int = 0):
+    """writes one sketch set per group of `merged` (Selector.merge(..., to_host=True)) into out_dir the way `selection -P` does:
+    <name>.hll, <name>.smh<m> (m > 0), <name>.hll_<p_aux> (p_aux > 0) through selhost_write_hll / selhost_write_smh, and filelist.txt with one
+    out_dir/<name> per line in group order"""
+    import os
+    h = host_lib()
+    os.makedirs(out_dir, exist_ok=True)
+    hll = np.ascontiguousarray(merged["hll"], dtype=np.uint8)
+    lines = []
+    for c, gname in enumerate(group_names):
+        base = os.path.join(out_dir, gname)
+        rc = h.selhost_write_hll((base + ".hll").encode(), hll[c].ctypes.data, hll.shape[1].bit_length() - 1)
+        if not rc and m:
+            row = np.ascontiguousarray(merged["aux"][c], dtype=np.uint64)
+            rc = h.selhost_write_smh((base + f".smh{m}").encode(), row.ctypes.data, m)
+        if not rc and p_aux:
+            row = np.ascontiguousarray(merged["aux_hll"][c], dtype=np.uint8)
+            rc = h.selhost_write_hll((base + f".hll_{p_aux}").encode(), row.ctypes.data, p_aux)
+        if rc:
+            raise RuntimeError(h.selhost_last_error().decode())
+        lines.append(base + "\n")
+    with open(os.path.join(out_dir, "filelist.txt"), "w") as f:
+        f.writelines(lines)
+
+
+def cluster_names(n_clusters: int) -> list:
+    """the names `selection -L ... -P dir` gives the clusters: cluster_<id>, zero-padded to the width of n_clusters - 1"""
+    width = len(str(max(n_clusters - 1, 0)))
+    return [f"cluster_{c:0{width}d}" for c in range(n_clusters)]
+
+
+def merge_from_filelist(list_file: str, aux_bytes: int, groups_file: Optional[str] = None, out_dir: Optional[str] = None, tau: float = 0.9,
+                        mode: int = MODE_CB_SMH, device: int = 0, fp_mode: int = FP_FMA, algo: int = ALGO_AUTO, criterion: str = "smh_a",
+                        linkage: str = "single", cluster_min: Optional[float] = None, rep="max_degree", fold_aux: bool = False, **pass_args) -> dict:
+    """one merged sketch set per group of the genomes of a file list.  groups_file ('path<TAB>group_name' lines, read_groups; what
+    `selection -I` reads): no pass runs.  Without it the groups are the clusters of the pass of select_from_filelist (tau, criterion and
+    its other arguments), single-linkage (Selector.cluster, rep) or linkage="greedy" (Selector.cluster_greedy, order = rep) at
+    cluster_min -- what `selection -L file [-Z greedy] -P dir` merges.  out_dir: the sets are also written as files (write_merged).
+    Returns Selector.merge's dict on the host plus "names" (the groups' names), "groups" [n] in rank order and "genomes" (the genome names in
+    rank order)"""
+    m_crit, p_aux, _ = _criterion_files(criterion, aux_bytes, pass_args.get("min_matches"), pass_args.get("min_containment"))
+    m = aux_bytes // 8 if criterion in ("smh_a", "smh_c") else m_crit
+
+    def finish(ds, sel, groups, names):
+        res = sel.merge(groups, len(names), to_host=True)
+        if out_dir is not None:
+            write_merged(out_dir, names, res, sel.m if m else 0, sel.p_aux)
+        res.update(names=names, groups=np.asarray(groups), genomes=list(ds.names))
+        return res
+
+    if groups_file is not None:
+        ds = load_dataset(list_file, m, _aux_files(fold_aux, p_aux, criterion) if p_aux else 0, fp_mode)
+        groups, names = read_groups(groups_file, ds.names)
+        with Selector(device, fp_mode) as sel:
+            sel.upload(ds.hll, ds.aux if m else np.zeros((len(ds.names), 1), dtype=np.uint64), ds.cards)
+            if p_aux and fold_aux:
+                sel.fold_aux_hll(p_aux)
+            elif p_aux:
+                sel.upload_aux_hll(ds.aux_hll, p_aux)
+            return finish(ds, sel, groups, names)
+
+    def then(ds, sel, pairs):
+        res = sel.cluster_greedy(cluster_min, rep) if linkage == "greedy" else sel.cluster(cluster_min, rep)
+        return finish(ds, sel, res["clusters"], cluster_names(res["n_clusters"]))
+    if linkage not in ("single", "greedy"):
+        raise ValueError("linkage: 'single' or 'greedy'")
+    return _filelist_pass(then, list_file, tau, aux_bytes, mode, device, fp_mode, algo, criterion, fold_aux=fold_aux, **pass_args)
 
 
 def greedy_table(names: Sequence[str], order: np.ndarray, res: dict) -> str:

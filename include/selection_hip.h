@@ -477,6 +477,7 @@ int selhip_ctx_set_topk_rounds(selhip_ctx* ctx, int64_t rows);
  * SuperMinHash measure, averaged over THOSE calls: "matrix" stays the HLL kernel's figure and count.
  * "cluster" is the launches of selhip_ctx_cluster (section 2g), averaged over the CLUSTER CALLS since the last reset, counted apart likewise.
  * "greedy" is the launches of selhip_ctx_cluster_greedy (section 2h), averaged over the GREEDY CALLS since the last reset, counted apart likewise.
+ * "merge" is the launches of selhip_ctx_merge_groups (section 2i), averaged over the MERGE CALLS since the last reset, counted apart likewise.
  * selhip_ctx_kernel_launches: launches of that kernel per pass. */
 double selhip_ctx_kernel_ms(const selhip_ctx* ctx, const char* name);
 double selhip_ctx_kernel_launches(const selhip_ctx* ctx, const char* name);
@@ -798,6 +799,50 @@ typedef struct {
 int selhip_ctx_cluster_greedy(selhip_ctx* ctx, double min_value, int order_rule, const uint32_t* d_priority,
                               const selhip_greedy_t* out, int64_t* n_clusters_out);
 
+/* ---------------------------------------------------------------------------------------------------
+ * 2i. Sketches merged by group: one union sketch per cluster.  2g and 2h end in a dense cluster id per genome; this turns the ids
+ *     into one sketch set per cluster -- a pan-genome sketch per species cluster, a sketch per metagenome bin, the first level of a
+ *     two-level search -- without the rows leaving the device.
+ *     THE IDENTITIES, both exact: the HLL sketch of a union of k-mer sets is the element-wise MAXIMUM of the registers (index and
+ *     rank are functions of the hash alone; main and auxiliary sketches alike), its SuperMinHash sketch the element-wise unsigned
+ *     MINIMUM of the 64-bit buckets (a bucket is the minimum over all elements and steps; an empty bucket stays ~0).  A merged row is
+ *     bit for bit the row the sketch builder writes for the members' records concatenated.
+ *     d_group[g] (device memory, int32[n], rank order) is the group of genome g, -1 .. n_groups - 1; -1 = in no group.  The d_cluster
+ *     of selhip_ctx_cluster or selhip_ctx_cluster_greedy, with their C as n_groups, is a valid d_group as it is.
+ *     OUTPUTS, n_groups rows in group-id order, each a pure function of the context's set and d_group, whatever order the device worked in:
+ *       d_hll[c]      [1 << p_hll] u8   maximum of the members' main registers           (16-byte aligned)
+ *       d_aux[c]      [m] u64           minimum of the members' SuperMinHash buckets     (8-byte aligned; 16 takes the wide path)
+ *       d_aux_hll[c]  [1 << p_aux] u8   maximum of the members' auxiliary registers      (16-byte aligned); only where the context holds
+ *                                       auxiliary sketches (uploaded, attached or folded): SELHIP_E_STATE otherwise
+ *       d_cards[c]    f64               report() of the merged main registers: the kernels behind selhip_hll_cards, the context's fp mode
+ *       d_size[c]     int32             members of group c
+ *     An empty group: registers 0, buckets ~0, size 0, cardinality 0.  Every array is the caller's device memory; any of the five
+ *     pointers may be NULL (that output is not written).  An id outside [-1, n_groups): SELHIP_E_BADARG, the message gives the number
+ *     of such entries and the index of one of them, no output is written and no kernel reads or writes outside the arrays because of
+ *     it.  n_groups == 0 writes nothing; a set of 0 genomes gives n_groups empty groups.  0 <= n_groups <= 2^31 - 1.
+ *     SELHIP_E_STATE before upload / attach and while a pass is pending.  Allowed after any pass, a query pass included: it merges the
+ *     database set.  The call writes only `out` and scratch the context owns: the result list, the statistics,
+ *     selhip_ctx_last_attempts, the top-k settings, the signature cache and "clusters_last" are as they were.  It runs on the
+ *     context's stream and returns when the outputs are complete.  Timed as "merge" in selhip_ctx_kernel_ms: per merge call, counted
+ *     apart from the passes as "cluster" is.
+ *     HOW (csrc/kernel_merge.cuh): a counting sort of the members by group, then a segmented reduction -- a lane per 16 bytes of an
+ *     output row.  No lane reduces more than SELHIP_MERGE_SEGMENT rows: a longer group is first reduced to partial rows in scratch
+ *     (ceil(size / SELHIP_MERGE_SEGMENT) of them), which the same kernel reduces again.
+ *     Not built: merging query sets, the host-side lists of selhip_multi_select and selhip_ooc_select (selhost_merge_sketches serves
+ *     them), intersections or differences of sketches, re-clustering around the merged rows.
+ * --------------------------------------------------------------------------------------------------- */
+#ifndef SELHIP_MERGE_SEGMENT
+#define SELHIP_MERGE_SEGMENT 64      /* member rows one lane reduces at most (a group beyond it takes one more level per factor) */
+#endif
+typedef struct {
+    uint8_t*  d_hll;         /* [n_groups][1 << p_hll]  merged main registers                        */
+    uint64_t* d_aux;         /* [n_groups][m]           merged SuperMinHash buckets                  */
+    uint8_t*  d_aux_hll;     /* [n_groups][1 << p_aux]  merged auxiliary registers                   */
+    double*   d_cards;       /* [n_groups]              report() of the merged main registers        */
+    int32_t*  d_size;        /* [n_groups]              members of the group                         */
+} selhip_merged_t;           /* caller's device memory; any pointer may be NULL (not written)        */
+int selhip_ctx_merge_groups(selhip_ctx* ctx, const int32_t* d_group, int64_t n_groups, const selhip_merged_t* out);
+
 
 /* ---------------------------------------------------------------------------------------------------
  * 3. Building blocks (device pointers), used by the launchers above and exposed for tests.
@@ -845,6 +890,20 @@ int selhip_components(const selhip_int2_t* d_pairs, int64_t n_pairs, int64_t n, 
  * written -- and the messages are those of selhip_components.  Waits for the stream. */
 int selhip_greedy_representatives(const selhip_int2_t* d_pairs, int64_t n_pairs, int64_t n, const uint64_t* d_key /* [n] or NULL */,
                                   uint8_t* d_is_rep /* [n] */, int64_t* rounds_out /* may be NULL */, void* hip_stream);
+/* Sketches merged by group (section 2i; csrc/kernel_merge.cuh) over a caller's rows: d_hll[n][1 << p] u8, d_smh[n][m] u64 and
+ * d_aux_hll[n][1 << p_aux] u8 reduced to n_groups rows each -- maximum, unsigned minimum, maximum -- by d_group[n] (int32, -1 .. n_groups - 1,
+ * -1 = in no group; ids in any order); d_size_out[n_groups] (int32, may be NULL) receives the members per group.  A sketch kind is
+ * present when its input and its output pointer are both non-NULL and absent when both are NULL; exactly one of the two: SELHIP_E_BADARG.
+ * ALIGNMENT: HLL and auxiliary arrays 16 bytes, SuperMinHash arrays 8 bytes (16-byte aligned arrays with an even m take the 16-byte
+ * path, anything else the 8-byte one: m = 1 and odd m are legal), d_group and d_size_out 4 bytes; SELHIP_E_BADARG otherwise.  Also
+ * SELHIP_E_BADARG: p outside 4 .. 20; with auxiliary rows p_aux outside 4 .. 20; with SuperMinHash rows m < 1; n or n_groups negative or
+ * above 2^31 - 1; and an id outside [-1, n_groups): the message gives the number of such entries and the index of one of them, no output
+ * is written, and no kernel reads or writes outside the arrays because of it.  The maximum is exact for every byte value 0 .. 255,
+ * not only for legal ranks.  An empty group: registers 0, buckets ~0, size 0.  n == 0 writes n_groups empty groups; n_groups == 0
+ * writes nothing.  The call owns its scratch and waits for the stream. */
+int selhip_merge_sketches(const uint8_t* d_hll, const uint64_t* d_smh, const uint8_t* d_aux_hll, int64_t n, int p, int m, int p_aux,
+                          const int32_t* d_group, int64_t n_groups, uint8_t* d_hll_out, uint64_t* d_smh_out, uint8_t* d_aux_out,
+                          int32_t* d_size_out, void* hip_stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * 4. Synthetic sketches generated directly in HBM (csrc/synth.hpp; stands in for the FASTA->sketch

@@ -141,6 +141,18 @@ int selhost_shard_rows(int64_t n, const int32_t* hi, int64_t z0, int parts, int6
  * For the drivers that take host arrays (selhip_multi_select, selhip_ooc_select) and for use without a GPU. */
 int selhost_hll_fold(const uint8_t* in, int64_t n, unsigned p, unsigned p_aux, uint8_t* out);
 
+/* ---- sketches merged by group (host twin of selhip_merge_sketches, selection_hip.h sections 2i and 3), in plain loops ----------
+ * hll[n][1 << p] u8, smh[n][m] u64 and aux_hll[n][1 << p_aux] u8 reduced to n_groups rows each by group[n] (-1 .. n_groups - 1, -1 = in no
+ * group): the element-wise maximum of the registers, the unsigned minimum of the buckets -- the sketches of the unions, bit for bit.
+ * size_out[n_groups] (may be NULL) receives the members per group.  An empty group: registers 0, buckets ~0, size 0.  A sketch kind is
+ * present when its input and output pointers are both non-NULL, absent when both are NULL.  SELHOST_E_BADARG with a message: exactly one
+ * pointer of a kind; p outside 4 .. 20; with auxiliary rows p_aux outside 4 .. 20; with SuperMinHash rows m < 1; n or n_groups negative or
+ * above 2^31 - 1; smh pointers not 8-byte aligned, group / size_out not 4-byte aligned; an id outside [-1, n_groups) -- the message gives
+ * the number of such entries and the index of one of them, and no output is written.  n == 0 writes n_groups empty groups; n_groups == 0
+ * writes nothing.  The independent check of the device kernels, and the route of the drivers whose lists live on the host. */
+int selhost_merge_sketches(const uint8_t* hll, const uint64_t* smh, const uint8_t* aux_hll, int64_t n, int p, int m, int p_aux,
+                           const int32_t* group, int64_t n_groups, uint8_t* hll_out, uint64_t* smh_out, uint8_t* aux_out, int32_t* size_out);
+
 const char* selhost_version(void);
 
 #ifdef __cplusplus
