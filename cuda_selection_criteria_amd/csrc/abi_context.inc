@@ -258,6 +258,8 @@ int selhip_ctx_get_param(const selhip_ctx* c, const char* name, int* value) {
     if (!std::strcmp(name, "greedy_rounds_last"))   { *value = c->greedy_rounds_last; return SELHIP_OK; }    // ... and the rounds its selection took
     if (!std::strcmp(name, "small_pass_used"))  { *value = c->small_used ? 1 : 0; return SELHIP_OK; }
     if (!std::strcmp(name, "pairs_route_used")) { *value = c->pairs_route_used; return SELHIP_OK; }         // list passes: 1 signature, 0 direct, 2 no smh_a stage, -1 none yet
+    if (!std::strcmp(name, "pairs_gpw"))        { *value = c->pairs_gpw_used; return SELHIP_OK; }           // ... its groups of four entries per wave and batch (0: one lane per entry)
+    if (!std::strcmp(name, "pairs_grid"))       { *value = c->pairs_grid_used; return SELHIP_OK; }          // ... and the blocks of its stage-1 kernel
     if (!std::strcmp(name, "query_topk"))       { *value = c->query_topk; return SELHIP_OK; }              // K of the query passes' top-k, 0 = off
     if (!std::strcmp(name, "allpairs_topk"))    { *value = c->allpairs_topk; return SELHIP_OK; }           // K of the all-pairs passes' top-k, 0 = off
     if (!std::strcmp(name, "topk_rounds"))      { *value = (int)std::min<int64_t>(c->topk_rounds, 0x7FFFFFFF); return SELHIP_OK; }   // selhip_ctx_set_topk_rounds: rows per round, 0 = off, -1 = automatic

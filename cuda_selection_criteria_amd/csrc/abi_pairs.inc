@@ -58,6 +58,7 @@ int selhip_ctx_run_pairs_async(selhip_ctx* c, const selhip_int2_t* d_pairs, int6
     c->have_run = false; c->last_was_query = false; c->topk_applied = false; c->topk_n = 0;
     c->rd.on = false;                                              // (a pair-list pass does not read selhip_ctx_set_topk_rounds)
     c->list_pass = true; c->list_pairs = d_pairs; c->list_n = n_pairs; c->pairs_route_used = route;
+    c->pairs_gpw_used = 0; c->pairs_grid_used = 0;                 // (enqueue_pairs_pass sets both; an empty list launches nothing)
     c->small_used = false; c->n_chunks_last = 1;
     std::memset(&c->last, 0, sizeof c->last);
     if (n_pairs == 0) { c->pending = false; c->have_run = true; c->last_attempts = 1; return SELHIP_OK; }

@@ -341,6 +341,8 @@ struct selhip_ctx {
     const selhip_int2_t* list_pairs = nullptr;     // the caller's, alive until selhip_ctx_finish (a pass that outgrows a list reads it again)
     int64_t list_n = 0;
     int pairs_route_used = -1;          // stage 1 of the last list pass: 1 signature route, 0 direct route, 2 no smh_a stage, -1 none yet
+    int pairs_gpw_used = -1;            // ... its groups per wave (pairs_direct_shape; 0: a kernel of one lane per entry), -1 none yet
+    int pairs_grid_used = -1;           // ... and the grid of its stage-1 kernel (criteria that take the list in windows: of the first), -1 none yet
 
     // dense matrices (selhip_ctx_matrix / _query_matrix; abi_matrix.inc): the validated copies of the caller's positions
     DevBuf<int> mat_row_pos, mat_col_pos;

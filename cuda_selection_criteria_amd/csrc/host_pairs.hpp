@@ -23,7 +23,9 @@ int pairs_route(const selhip_ctx* c, bool smh, int algo, int n_rows, int n_bands
 }
 
 hipError_t launch_pairs_filter(selhip_ctx* c, u64 off, u64 end, double tau, selhip_int2_t* out, u64 out_cap, u64* out_count, PassCounters* pc0) {
-    hipLaunchKernelGGL(pairs_filter_kernel, dim3(grid_for(end - off, kPairsBlock, kPairsMaxGrid)), dim3(kPairsBlock), 0, c->stream,
+    const unsigned grid = grid_for(end - off, kPairsBlock, kPairsMaxGrid);
+    if (off == 0) c->pairs_grid_used = (int)grid;                             // ("pairs_grid": of the first window)
+    hipLaunchKernelGGL(pairs_filter_kernel, dim3(grid), dim3(kPairsBlock), 0, c->stream,
                        c->list_pairs, off, end, (int)c->n, c->ecard.p, tau, c->mode == SELHIP_MODE_CB_SMH ? 1 : 0, out, out_cap, out_count, pc0);
     return hipGetLastError();
 }
@@ -66,8 +68,10 @@ int enqueue_pairs_pass(selhip_ctx* c) {
         {
             TimerScope t(c, T_STAGE1);
             const unsigned grid = grid_for(P, kPairsBlock, kPairsMaxGrid);
+            c->pairs_gpw_used = 0; c->pairs_grid_used = (int)grid;            // ("pairs_gpw", "pairs_grid": the signature route's, replaced below)
             if (c->plan.count) {
                 const PairsDirectShape sh = pairs_direct_shape(P);
+                c->pairs_gpw_used = sh.gpw; c->pairs_grid_used = (int)sh.grid;
                 c->smhc_rule_used = smhc_containment(c) ? 1 : 0;
                 const PairsGammaEmit gamma_em{c->min_containment, smhc_emit(c, pc0)};
                 with_flag(smhc_containment(c), [&](auto C) {
@@ -85,6 +89,7 @@ int enqueue_pairs_pass(selhip_ctx* c) {
                                    c->list_pairs, P, n, c->ecard.p, tau, use_cb, io.surv, io.cap, io.pc, pc0, c->verify_fb);
             else {
                 const PairsDirectShape sh = pairs_direct_shape(P);
+                c->pairs_gpw_used = sh.gpw; c->pairs_grid_used = (int)sh.grid;
                 hipLaunchKernelGGL(pairs_direct_kernel<false>, dim3(sh.grid), dim3(kPairsBlock), 0, c->stream, c->d_aux, c->m, c->n_rows, c->n_bands,
                                    c->list_pairs, P, n, c->ecard.p, (const double*)nullptr, tau, use_cb, sh.gpw, io.surv, io.cap, &io.pc->n_survivors, pc0);
             }

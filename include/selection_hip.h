@@ -98,6 +98,14 @@ typedef struct { int32_t i, k; double jaccard; } selhip_pair_t;
  *    materialising the 8 B/pair list: total_pairs must then be n(n-1)/2, which fixes n; cards must be ascending (the
  *    driver's order); this variant runs the all-pairs path of the context API and returns after the pass.
  *    With an explicit list the launchers are asynchronous on the null stream, like the reference.
+ *    An explicit list is taken ENTRY BY ENTRY, in the orientation listed, as the reference's kernels take it: an entry {x, y} is
+ *    evaluated iff (size_t)cards[y] != 0 and, for launch_kernel_CBsmh, (double)(size_t)cards[x] / (double)(size_t)cards[y] >= tau
+ *    -- x's cardinality over y's, whichever is larger, so a reversed entry {larger, smaller} has a ratio >= 1 and is never cut, and an
+ *    entry whose x is an empty sketch is cut at any tau > 0 --; an evaluated entry with an equal band whose J reaches tau gives the
+ *    record {x, y, (float)J} with x and y as listed, once per occurrence of the entry.  Nothing is deduplicated and cards need not
+ *    be ascending.  x == y is no special case: such an entry has every band equal and J = (2 e - t) / t with t the estimate of the
+ *    sketch's own register row.  No rank is checked (the parameter list carries no genome count): a rank outside the arrays is
+ *    the caller's error and reads out of bounds.
  *    m_aux is the number of u64 buckets per sketch, m_hll the number of HLL registers (16384).
  *    launch_kernel_smh evaluates every listed pair; launch_kernel_CBsmh additionally applies CB
  *    (the reference kernel of that name does not, selection_kernels.cu:63-117 -- documented defect).
@@ -231,6 +239,10 @@ int selhip_ctx_set_param(selhip_ctx* ctx, const char* name, int value);
  * "query_topk", "query_topk_lds_cap" (top-k of the query passes, section 2b),
  * "allpairs_topk" (the current k of selhip_ctx_set_allpairs_topk, 0 = off),
  * "pairs_route_used" (stage 1 of the last pair-list pass, section 2e),
+ * "pairs_gpw" and "pairs_grid" (the launch shape of that stage 1: the groups of four entries a wave of the direct route or of the
+ * smh_c count takes per batch, 1 .. 16 by the list's length -- 0 for the kernels of one lane per entry, the signature route and the
+ * criteria without an smh_a stage -- and the kernel's blocks, of the first window where the list goes in windows; both 0 after an
+ * empty list, -1 = no list pass yet),
  * "matrix_smh_path_used" (the kernel of the last matrix call with a SuperMinHash measure, section 2f: 1 = the register-tile kernel
  * of m = 128, 256, 512 or 1024 buckets, 0 = the generic kernel of every other m; -1 = none yet),
  * "clusters_last" (the number of clusters the last selhip_ctx_cluster call found, section 2g; -1 = none yet),
