@@ -107,7 +107,8 @@ void pairs_filter_kernel(const selhip_int2_t* __restrict__ list, u64 off, u64 en
 // pairs_verify_kernel: the signature route.  verify16_kernel with the list, not the join's 64 append segments, as its input: the
 // body is verify16_batch (kernel_verify.cuh) -- an entry with a signature bit set is a CANDIDATE (counted in n_candidates) -- and
 // sig_candidate_ok decides it (`force_fallback`: test hook "verify_fb").
-// Resources (compiler's report for gfx950, -O3): 71 VGPRs, no scratch, 4 136 B of LDS; occupancy 7 waves per SIMD.
+// Resources (compiler's report for gfx950, -O3): 126 VGPRs (verify16_batch keeps 16 signature loads in flight), 94 SGPRs, no scratch,
+// no spills, 4 136 B of LDS; occupancy 4 waves per SIMD.
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kPairsBlock)
 void pairs_verify_kernel(const u64* __restrict__ aux, int m, int n_rows, int n_bands, const uint32_t* __restrict__ sigQ,

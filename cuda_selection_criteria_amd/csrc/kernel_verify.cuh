@@ -39,7 +39,8 @@ __device__ __forceinline__ bool sig_candidate_ok(bool band_equal, int force_fall
 
 // One band of n_rows buckets compared by a quarter-wave (lane's 16-lane group: sub = lane & 15 takes buckets sub, sub + 16, ...);
 // `on` (quarter-uniform) = the quarter has a pair, otherwise nothing is loaded.  Wave-uniformly reached; true on all sixteen lanes
-// iff every bucket is equal.
+// iff every bucket is equal.  The queue check of small_pass_kernel uses it (one band per quarter: nothing to batch); verify16_batch
+// compares eight steps' bands at once, with unguarded loads, in its own loops.
 __device__ __forceinline__ bool band_equal16(const u64* x, const u64* y, int n_rows, bool on, int lane) {
     bool eq = true;
     for (int j0 = lane & 15; j0 < n_rows; j0 += 16)
@@ -54,23 +55,57 @@ __device__ __forceinline__ u64 pairs_quarter_bits(u64 m, int sh) {
 
 // ---------------------------------------------------------------------------------------------
 // verify16_batch: a wave's 64 pairs (lane p holds pair p in `pr`; `live_mask` = the lanes that hold one), four at a time, 16 lanes
-// per pair (step s: quarter-wave q has pair 4s+q).
+// per pair (step s: quarter-wave q has pair 4s+q), in two half-batches of eight steps.
 //  1. 32-bit signatures: the lanes of a quarter read the two genomes' signature rows from the genome-major copy sigQ
 //     (coalesced 16-B loads, 2 x n_bands*4 bytes per pair, L2-resident) and keep one bit per band "32-bit signature
 //     equal".  Pairs with a bit set are exactly the candidate set of the 32-bit join: mask `has`.
 //  2. A band that is entirely equal has an equal signature, so only bands with a bit set can make smh_a true: the first
 //     such band of each pair is compared on the full sketches (n_rows u64 per genome, 16 lanes): mask `eq` (a subset of `has`).
 // Both masks are wave-uniform, bit p = pair p.  The caller hands each pair of `has` to sig_candidate_ok on its own lane.
-// All loads of a phase are independent across the steps (eight steps' loads in flight: the outer loop must not be unrolled, the
-// inner ones must), so a batch costs a handful of memory round trips instead of the ~n_bands dependent ones of the lane-serial
-// literal check (verify_kernel: 32 us for 45 000 candidates at cfg3).
+// EVERY LOAD IS UNCONDITIONAL, at a clamped index, and the lane conditions (sub < nq, the live mask, `has`, sub < n_rows) are applied
+// to the loaded bits: the compiler does not move a load out of a lane-divergent guard that also consumes it, and with the guards
+// every step was a round trip of its own (s_waitcnt vmcnt(0) behind each pair of loads: ~35 dependent round trips a wave).  Now a
+// half-batch issues the 16 signature loads of its eight steps back to back, then -- the bands of all eight steps known, by ballots
+// and shuffles alone -- their 16 sketch loads, each group behind ONE s_waitcnt vmcnt(0) (VERIFY16_ALL_LOADED): 2 round trips a
+// half-batch, 4 a batch (profiles/verify_batch_isa.txt shows the load / wait sequence of the code object before and after).  What
+// makes the unguarded loads valid:
+//  * a lane of a dead pair holds pr = {0, 0} (verify16_kernel, pairs_entry) and reads row 0, which exists whenever a batch runs;
+//  * a lane with sub >= nq re-reads signature group nq - 1 and its bits are dropped; one with sub >= n_rows re-reads bucket
+//    n_rows - 1, a duplicate of lane n_rows - 1's comparison, which cannot change the AND over the sixteen lanes;
+//  * a quarter without a flagged band compares band 0 of row 0 with itself (one cache line for all such quarters, no sketch
+//    traffic for the 16-bit matches that are no candidates) and is masked by `has`.
+// Further round trips, both behind wave-uniform trip counts: 128 bands (nq = 32) take a second batched group of 16 signature loads,
+// bands of more than 16 buckets a remainder loop of batched loads (16 per trip) over the buckets sub + 16, sub + 32, ...
+// Neither the half-batch loop nor the group loop may be unrolled (the 64 registers of 16 signature loads in flight are the budget:
+// 124 VGPRs in verify16_kernel), the loops over the eight steps must.
 // ---------------------------------------------------------------------------------------------
 struct Verify16Masks { u64 has, eq; };
+
+// bits 0..3 of the result: the four signatures of a 16-byte group equal
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ uint32_t sig_group_bits(const u32x4 u, const u32x4 v) {
+    return (u.x == v.x ? 1u : 0u) | (u.y == v.y ? 2u : 0u) | (u.z == v.z ? 4u : 0u) | (u.w == v.w ? 8u : 0u);
+}
+
+// x of the lane K places up in the lane's quarter-wave (a DPP row), rotating inside it
+template <int K>
+__device__ __forceinline__ uint32_t quarter_ror(uint32_t x) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x120 + K, 0xF, 0xF, true);
+}
+
+// An empty statement that takes the 16 loaded values a[0..7], b[0..7] (whole registers: u32x4 or u64) and hands them on: everything
+// computed from them depends on ALL sixteen loads, so the compiler can neither start comparing after the first few and issue the
+// rest behind that wait (it does, to save registers), nor sink one of them into a guard.  One s_waitcnt vmcnt(0) stands in its place.
+#define VERIFY16_ALL_LOADED(a, b)                                                                                                      \
+    asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]),                 \
+                      "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]), "+v"(b[4]), "+v"(b[5]), "+v"(b[6]), "+v"(b[7]))
 
 __device__ __forceinline__ Verify16Masks verify16_batch(const u64* __restrict__ aux, int m, int n_rows, int n_bands, const uint32_t* __restrict__ sigQ,
                                                         selhip_int2_t pr, u64 live_mask, int lane) {
     const int sub = lane & 15, quarter = lane >> 4, qshift = quarter * 16;
     const int nq = n_bands >> 2;                                              // 16-byte groups per genome (n_bands % 8 == 0, <= 32)
+    const int n_groups = nq > 16 ? 2 : 1;                                     // 128 bands: a lane has a second group, sub + 16
+    const int j0 = min(sub, n_rows - 1);                                      // clamped: lanes past the band re-read its last bucket
     Verify16Masks vm{0, 0};
 #pragma unroll 1
     for (int s0 = 0; s0 < 16; s0 += 8) {
@@ -81,33 +116,75 @@ __device__ __forceinline__ Verify16Masks verify16_batch(const u64* __restrict__ 
             const int src = (s0 + s) * 4 + quarter;
             px[s] = __shfl(pr.x, src, kWave);
             py[s] = __shfl(pr.y, src, kWave);
-            const uint4* a = reinterpret_cast<const uint4*>(sigQ + (long long)px[s] * n_bands);
-            const uint4* b = reinterpret_cast<const uint4*>(sigQ + (long long)py[s] * n_bands);
-            uint32_t bits = 0;
-            if (sub < nq) {
-                const uint4 u = a[sub], v = b[sub];
-                bits |= (u.x == v.x ? 1u : 0u) | (u.y == v.y ? 2u : 0u) | (u.z == v.z ? 4u : 0u) | (u.w == v.w ? 8u : 0u);
-            }
-            if (sub + 16 < nq) {
-                const uint4 u = a[sub + 16], v = b[sub + 16];
-                bits |= (u.x == v.x ? 16u : 0u) | (u.y == v.y ? 32u : 0u) | (u.z == v.z ? 64u : 0u) | (u.w == v.w ? 128u : 0u);
-            }
-            lm[s] = ((live_mask >> src) & 1ull) ? bits : 0u;
+            lm[s] = 0u;
         }
+        // ---- phase 1: the signatures of eight steps, all 16 loads of a group before the first comparison.  The trip count is
+        // wave-uniform; only 128 bands take the second trip.
+#pragma unroll 1
+        for (int g = 0; g < n_groups; ++g) {
+            const int gi = min(sub + 16 * g, nq - 1);                         // clamped: lanes past the row re-read its last group
+            // which of the loaded bits count, as an AND mask: a select here becomes a lane-divergent branch, and the compiler sinks
+            // loads into it
+            const uint32_t keep = sub + 16 * g < nq ? 0xFu : 0u;
+            u32x4 u[8], v[8];
+#pragma unroll
+            for (int s = 0; s < 8; ++s) {
+                int x = px[s], y = py[s];
+                asm volatile("" : "+v"(x), "+v"(y));                          // (the row addresses are formed here, not kept across the trips)
+                u[s] = reinterpret_cast<const u32x4*>(sigQ + (long long)x * n_bands)[gi];
+                v[s] = reinterpret_cast<const u32x4*>(sigQ + (long long)y * n_bands)[gi];
+            }
+            VERIFY16_ALL_LOADED(u, v);
+#pragma unroll
+            for (int s = 0; s < 8; ++s) lm[s] |= (sig_group_bits(u[s], v[s]) & keep) << (4 * g);
+        }
+        // ---- phase 2: the first flagged band of every step (ballots and shuffles only), then all their sketch loads
+        uint32_t has_bits = 0, eq_bits = 0;                                   // bit s: step s (has: quarter-uniform; eq: this lane's buckets)
+        long long ox[8], oy[8];                                               // the band's first bucket in aux
 #pragma unroll
         for (int s = 0; s < 8; ++s) {
-            const uint32_t mine = (uint32_t)(__ballot(lm[s] != 0u) >> qshift) & 0xFFFFu;   // lanes of my quarter with a bit
+            const int src = (s0 + s) * 4 + quarter;
+            const uint32_t lms = ((live_mask >> src) & 1ull) ? lm[s] : 0u;
+            const uint32_t mine = (uint32_t)(__ballot(lms != 0u) >> qshift) & 0xFFFFu;     // lanes of my quarter with a bit
             const bool has = mine != 0u;
             const int src_sub = has ? __builtin_ctz(mine) : 0;
-            const uint32_t lmv = (uint32_t)__shfl((int)lm[s], qshift + src_sub, kWave);
+            const uint32_t lmv = (uint32_t)__shfl((int)lms, qshift + src_sub, kWave);
             const int t = has ? __builtin_ctz(lmv) : 0;
             const int band = t < 4 ? src_sub * 4 + t : (src_sub + 16) * 4 + (t - 4);
-            const bool all_eq = band_equal16(aux + (long long)px[s] * m + (long long)band * n_rows,
-                                             aux + (long long)py[s] * m + (long long)band * n_rows, n_rows, has, lane);
-            const int sh = (s0 + s) * 4;
-            vm.has |= pairs_quarter_bits(__ballot(has && sub == 0), sh);
-            vm.eq |= pairs_quarter_bits(__ballot(has && all_eq && sub == 0), sh);
+            has_bits |= has ? 1u << s : 0u;
+            ox[s] = (long long)(has ? px[s] : 0) * m + (long long)band * n_rows;           // (no candidate: band 0 of row 0, twice)
+            oy[s] = (long long)(has ? py[s] : 0) * m + (long long)band * n_rows;
         }
+        {
+            u64 x[8], y[8];
+#pragma unroll
+            for (int s = 0; s < 8; ++s) { x[s] = aux[ox[s] + j0]; y[s] = aux[oy[s] + j0]; }
+            VERIFY16_ALL_LOADED(x, y);
+#pragma unroll
+            for (int s = 0; s < 8; ++s) eq_bits |= x[s] == y[s] ? 1u << s : 0u;
+        }
+        for (int o = 16; o < n_rows; o += 16) {                               // wave-uniform trip count: bands of more than 16 buckets
+            const int j = min(sub + o, n_rows - 1);
+            u64 x[8], y[8];
+#pragma unroll
+            for (int s = 0; s < 8; ++s) { x[s] = aux[ox[s] + j]; y[s] = aux[oy[s] + j]; }
+            VERIFY16_ALL_LOADED(x, y);
+#pragma unroll
+            for (int s = 0; s < 8; ++s) eq_bits &= x[s] == y[s] ? ~0u : ~(1u << s);
+        }
+        // a band is equal iff its sixteen lanes are: AND over the quarter (a DPP row), all eight steps at once
+        uint32_t ok_bits = eq_bits;
+        ok_bits &= quarter_ror<1>(ok_bits);
+        ok_bits &= quarter_ror<2>(ok_bits);
+        ok_bits &= quarter_ror<4>(ok_bits);
+        ok_bits &= quarter_ror<8>(ok_bits);
+        ok_bits &= has_bits;
+        // bit p of the half-batch's masks = pair p = step p >> 2 of quarter p & 3: lane p (< 32) fetches that quarter's word, and a
+        // ballot over its bit p >> 2 lines the 32 pairs up
+        const int from = (lane & 3) * 16, step = (lane >> 2) & 7;
+        const uint32_t has_q = (uint32_t)__shfl((int)has_bits, from, kWave), ok_q = (uint32_t)__shfl((int)ok_bits, from, kWave);
+        vm.has |= (u64)(uint32_t)__ballot(lane < 32 && ((has_q >> step) & 1u)) << (s0 * 4);
+        vm.eq |= (u64)(uint32_t)__ballot(lane < 32 && ((ok_q >> step) & 1u)) << (s0 * 4);
     }
     return vm;
 }
@@ -144,7 +221,10 @@ void verify_kernel(const u64* __restrict__ aux, int m, int n_rows, int n_bands,
 // batch (plus one for the candidate tally; block_append, common.cuh): appends are single-address atomics, ~85 per microsecond on
 // this part, and a per-wave append (1 500 waves at cfg3) costs more than the whole check (52 us vs 15 us).
 // force_fallback (test hook): treat every first-band comparison as a collision.
-// Resources (compiler's report for gfx950, -O3): 71 VGPRs, no scratch, 4 112 B of LDS; occupancy 7 waves per SIMD.
+// Resources (compiler's report for gfx950, -O3): 124 VGPRs (64 of them the 16 signature loads a half-batch keeps in flight), 90 SGPRs,
+// no scratch, no spills, 4 112 B of LDS; occupancy 4 waves per SIMD.  With the guarded loads it had 71 VGPRs and 7 waves, and took
+// 22.6 us a launch at cfg3 against 13.8 us now; cfg4 and cfg5, where it verifies over a million matches and occupancy could matter,
+// are 2 % and 1.5 % faster a step (profiles/verify_batch_ab.txt).
 constexpr int kVerifyBlock = kAppendBlock;
 
 __global__ __launch_bounds__(kVerifyBlock)
