@@ -53,6 +53,11 @@ class Greedy(C.Structure):            # selhip_greedy_t: the six outputs of selh
                 ("d_cluster_size", C.c_void_p), ("d_cluster_rep", C.c_void_p)]
 
 
+class BuildInfo(C.Structure):         # selhip_build_info_t: the plan of selhip_build_sketches_split and what ran
+    _fields_ = [("chunk", C.c_int64), ("items", C.c_int64), ("split_genomes", C.c_int64), ("chunks", C.c_int64),
+                ("fallback_genomes", C.c_int64), ("levels", C.c_int32), ("threads", C.c_int32)]
+
+
 MODE_SMH, MODE_CB_SMH = 0, 1
 ALGO_AUTO, ALGO_STREAM, ALGO_SIG, ALGO_HASHJOIN, ALGO_INDEX = 0, 1, 2, 3, 4    # ALGO_INDEX: query passes only
 FP_STRICT, FP_FMA = 0, 1
@@ -69,6 +74,10 @@ TOPK_ROUNDS_AUTO = -1                  # SELHIP_TOPK_ROUNDS_AUTO: Selector.set_t
 REP_MAX_DEGREE, REP_MIN_RANK, REP_MAX_RANK = 0, 1, 2   # SELHIP_REP_*: the representative of a cluster (Selector.cluster)
 REP_PRIORITY = 3                       # SELHIP_REP_PRIORITY: the caller's scores order the greedy clusters (Selector.cluster_greedy alone)
 MERGE_SEGMENT = 64                     # SELHIP_MERGE_SEGMENT: member rows one lane of the merge reduces at most (Selector.merge, merge_sketches)
+SPLIT_AUTO, SPLIT_OFF = 0, -1          # SELHIP_SPLIT_*: the chunk argument of selhip_build_sketches_split (else: end positions per chunk)
+SPLIT_CHUNK_MIN = 65536                # the shortest chunk SPLIT_AUTO cuts (64 end positions x 1 024 threads)
+SPLIT_SCRATCH_MAX = 1 << 30            # bytes of partial rows a split build may hold
+E_NOMEM = -6                           # SELHIP_E_NOMEM
 TOPK_MAX = 1024                        # SELHIP_TOPK_MAX: largest k of Selector.set_query_topk and Selector.set_allpairs_topk
 
 _vp, _i, _i64, _d, _sz, _cp = C.c_void_p, C.c_int, C.c_int64, C.c_double, C.c_size_t, C.c_char_p
@@ -152,6 +161,8 @@ HIP_SYMBOLS = {
     "selhip_synth_generate": (_i, [C.POINTER(Synth), _i64, _i64, _vp, _vp, _vp, _vp]),
     "selhip_permute_rows": (_i, [_vp, _vp, _vp, _i64, _i64, _vp]),
     "selhip_build_sketches": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "selhip_build_sketches_split": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i64, _vp, _vp, _vp, C.POINTER(BuildInfo), _vp]),
+    "selhip_build_split_plan": (_i, [_vp, _i64, _i, _i, _i, _i64, _i64, _vp, C.POINTER(BuildInfo)]),
     "selhip_malloc": (_i, [C.POINTER(_vp), _sz]),
     "selhip_free": (_i, [_vp]),
     "selhip_memcpy_h2d": (_i, [_vp, _vp, _sz]),

@@ -3,7 +3,8 @@
 // writes <file>.hll (HyperLogLog p=14) and, by criterion, <file>.hll_<p> (hll_a / hll_an, p = ctz(aux_bytes)) or
 // <file>.smh<m> (smh_a, m = aux_bytes/8) -- byte-identical (after gunzip) to what the reference writes.
 // FASTA parsing and file I/O run on host threads; every k-mer of every genome is sketched on the GPU
-// (selhip_build_sketches), genomes batched so that a batch's bases fit a fixed device buffer.
+// (selhip_build_sketches_split), genomes batched so that a batch's bases fit a fixed device buffer.
+// -s auto|off|<end positions>: how long genomes are cut across workgroups (default auto; the files are the same bytes under every -s).
 #include <unistd.h>
 
 #include <cstdio>
@@ -29,18 +30,37 @@ static void load_file_list(std::vector<std::string>& files, const std::string& l
     }
 }
 
+// -s: "auto", "off" or a positive multiple of 64 end positions per chunk; false for anything else
+static bool parse_split(const char* arg, int64_t* chunk) {
+    const std::string s = arg;
+    if (s == "auto") { *chunk = SELHIP_SPLIT_AUTO; return true; }
+    if (s == "off") { *chunk = SELHIP_SPLIT_OFF; return true; }
+    if (s.empty() || s.size() > 18 || s.find_first_not_of("0123456789") != std::string::npos) return false;
+    const long long v = std::stoll(s);
+    if (v <= 0 || v % 64) return false;
+    *chunk = v;
+    return true;
+}
+
 int main(int argc, char* argv[]) {
     std::string list_file = "", criterion = "";
+    int64_t split = SELHIP_SPLIT_AUTO;
     unsigned threads = 8, aux_bytes = 256;
     const int k = 31;                                                           // build_sketch.cpp:190
     int c;
-    while ((c = getopt(argc, argv, "l:t:a:c:x")) != -1) {
+    while ((c = getopt(argc, argv, "l:t:a:c:s:x")) != -1) {
         switch (c) {
             case 'l': list_file = optarg; break;
             case 't': threads = (unsigned)std::stoi(optarg); break;
             case 'a': aux_bytes = (unsigned)std::stoi(optarg); break;
             case 'c': criterion = optarg; break;
-            case 'x': std::cout << "Usage: -l -t -a -c\n"; return 0;
+            case 's':
+                if (!parse_split(optarg, &split)) {
+                    std::cerr << "build_sketch: -s takes auto, off or a positive multiple of 64 end positions per chunk, not '" << optarg << "'\n";
+                    return 2;
+                }
+                break;
+            case 'x': std::cout << "Usage: -l -t -a -c [-s auto|off|<end positions per chunk>]\n"; return 0;
             default: break;
         }
     }
@@ -86,8 +106,8 @@ int main(int argc, char* argv[]) {
         if (!rc && mode == 1) rc = selhip_malloc(&d_aux, aux.size());
         if (!rc) rc = selhip_memcpy_h2d(d_codes, flat.data(), flat.size());
         if (!rc) rc = selhip_memcpy_h2d(d_off, offsets.data(), offsets.size() * 8);
-        if (!rc) rc = selhip_build_sketches((const uint8_t*)d_codes, (const int64_t*)d_off, (int64_t)nb, k, (int)m, p_aux,
-                                            (uint8_t*)d_hll, (uint64_t*)d_smh, (uint8_t*)d_aux, nullptr);
+        if (!rc) rc = selhip_build_sketches_split((const uint8_t*)d_codes, (const int64_t*)d_off, offsets.data(), (int64_t)nb, k, (int)m, p_aux, split,
+                                                  (uint8_t*)d_hll, (uint64_t*)d_smh, (uint8_t*)d_aux, nullptr, nullptr);
         if (!rc) rc = selhip_memcpy_d2h(hll.data(), d_hll, hll.size());
         if (!rc && mode == 2) rc = selhip_memcpy_d2h(smh.data(), d_smh, smh.size() * 8);
         if (!rc && mode == 1) rc = selhip_memcpy_d2h(aux.data(), d_aux, aux.size());

@@ -156,6 +156,68 @@ constexpr bool matrix_skips_span(int r0, int i, long long k0) { return k0 >= r0 
 // ... and its cell (i, k) is also the cell (k, i) of a row of the same slab: stored twice
 constexpr bool matrix_mirrors(int i, long long k, int r1) { return k > i && k < r1; }
 
+// ---- long genomes split across workgroups (selhip_build_sketches_split, kernel_sketch.cuh) ---------
+// The k-mer END positions of a genome of L codes are e in [k-1, L).  With a chunk length C (a positive multiple of kSketchSeg) chunk c
+// owns e in [k-1 + c C, min(k-1 + (c+1) C, L)) and its kernel sees the sub-array codes + c C of length min(C + k-1, L - c C): the k-1
+// warm-up bases of for_each_kmer are the real bases in front of the chunk, so every k-mer belongs to exactly one chunk and a window
+// reset carries across a cut with no special case.  A genome has max(1, ceil((L - (k-1)) / C)) chunks and is split iff it has two.
+constexpr long long kSplitChunkMin = (long long)kSketchSeg * 1024;     // auto never cuts below one stride of a 1 024-thread block
+constexpr unsigned long long kSplitScratchMax = 1ull << 30;            // bytes of partial rows a call may hold (1 GiB)
+// w: the rounds of resident blocks that auto aims at, C = max(kSplitChunkMin, round_up(end positions / (w B), kSplitChunkMin)).
+// Not derivable from the code: chosen from the chunk sweep of scripts/bench_build_split.py (profiles/build_split_chunk_sweep.txt)
+constexpr long long kSplitRounds = 1;
+
+long long split_end_positions(long long L, int k) { return std::max<long long>(0, L - (k - 1)); }
+long long split_chunks_of(long long L, int k, long long C) { return C > 0 ? std::max<long long>(1, (split_end_positions(L, k) + C - 1) / C) : 1; }
+// bytes of partial rows per chunk: the main registers, the buckets, the auxiliary registers
+unsigned long long split_row_bytes(int m, int p_aux) { return 16384ull + 8ull * (unsigned long long)std::max(m, 0) + (p_aux > 0 ? 1ull << p_aux : 0ull); }
+// levels of the segmented reduction over c partial rows: no lane reduces more than SELHIP_MERGE_SEGMENT rows in sequence
+int split_levels_of(long long c) {
+    if (c < 2) return 0;
+    int levels = 1;
+    for (; c > SELHIP_MERGE_SEGMENT; ++levels) c = (c + SELHIP_MERGE_SEGMENT - 1) / SELHIP_MERGE_SEGMENT;
+    return levels;
+}
+
+struct SplitPlan { long long chunk = 0, items = 0, split_genomes = 0, chunks = 0, max_chunks = 0; };
+enum SplitPlanStatus { kSplitPlanOk = 0, kSplitPlanBadChunk, kSplitPlanBadOffsets, kSplitPlanScratch };
+
+// The plan of one call: the chunk length and the chunks of every genome (counts[n], may be NULL).  chunk: SELHIP_SPLIT_OFF (nothing is
+// split, the plan's chunk is 0), SELHIP_SPLIT_AUTO, or a positive multiple of kSketchSeg.  m, p_aux: of the rows asked for (0 = none):
+// they size the scratch.  Auto raises C, doubling, until the partial rows fit kSplitScratchMax; an explicit chunk beyond it is refused.
+SplitPlanStatus split_plan(const int64_t* off, int64_t n, int k, int m, int p_aux, int64_t chunk, int64_t resident_blocks, int64_t* counts, SplitPlan* out) {
+    *out = SplitPlan{};
+    if (chunk != SELHIP_SPLIT_OFF && chunk != SELHIP_SPLIT_AUTO && (chunk < 0 || chunk % kSketchSeg)) return kSplitPlanBadChunk;
+    long long total = 0;
+    for (int64_t g = 0; g < n; ++g) {
+        if (off[g] < 0 || off[g + 1] < off[g]) return kSplitPlanBadOffsets;
+        total += split_end_positions(off[g + 1] - off[g], k);
+    }
+    long long C = chunk == SELHIP_SPLIT_OFF ? 0 : chunk;
+    if (chunk == SELHIP_SPLIT_AUTO) {
+        const long long slots = kSplitRounds * std::max<long long>(1, resident_blocks);
+        const long long per_slot = (total + slots - 1) / slots;
+        C = std::max(kSplitChunkMin, (per_slot + kSplitChunkMin - 1) / kSplitChunkMin * kSplitChunkMin);
+    }
+    const unsigned long long row_bytes = split_row_bytes(m, p_aux);
+    for (;;) {
+        SplitPlan p;
+        p.chunk = C;
+        for (int64_t g = 0; g < n; ++g) {
+            const long long c = split_chunks_of(off[g + 1] - off[g], k, C);
+            if (c >= 2) { p.split_genomes += 1; p.chunks += c; p.items += c; p.max_chunks = std::max(p.max_chunks, c); }
+            else p.items += 1;
+        }
+        if ((unsigned long long)p.chunks * row_bytes <= kSplitScratchMax) {
+            for (int64_t g = 0; counts && g < n; ++g) counts[g] = split_chunks_of(off[g + 1] - off[g], k, C);
+            *out = p;
+            return kSplitPlanOk;
+        }
+        if (chunk != SELHIP_SPLIT_AUTO) return kSplitPlanScratch;
+        C *= 2;
+    }
+}
+
 // bit range of the band keys (band << 32 | signature) that the sort join and the query index sort
 unsigned band_key_end_bit(int n_bands) { return 32u + (unsigned)ilog2(n_bands) + 1u; }
 

@@ -1,4 +1,5 @@
-// kernel_sketch.cuh -- synthetic sketches, sketch construction from k-mers (build_sketch), row permutation.
+// kernel_sketch.cuh -- synthetic sketches, sketch construction from k-mers (build_sketch; one workgroup per genome, or per chunk of a
+// long genome), row permutation.
 // Part of libselhip.so; included by selection_kernels.hip only (one translation unit, anonymous namespace).
 #pragma once
 
@@ -283,6 +284,199 @@ void sketch_build_kernel(const uint8_t* __restrict__ codes_all, const long long*
     for (int t = threadIdx.x; t < 16384 / 4; t += (int)blockDim.x) out32[t] = regs[t];
     for (int t = threadIdx.x; t < n_aux; t += (int)blockDim.x) aux_out[g * n_aux + t] = (uint8_t)(aregs[t >> 2] >> ((t & 3) * 8));
     for (int t = threadIdx.x; t < ms; t += (int)blockDim.x) smh_out[g * (long long)m + t] = h[t];
+}
+
+// ---------------------------------------------------------------------------------------------
+// Long genomes split across workgroups (selhip_build_sketches_split; the plan is split_plan in host_plan.hpp).
+// A work item is a whole genome (direct) or one chunk of a split genome (partial): the chunk's k-mer end positions and the k-1 real bases
+// in front of them, so that for_each_kmer on the sub-array visits exactly the chunk's k-mers.  The sketch of a union of k-mer sets is
+// the bytewise maximum of the HLL registers and, while no k-mer's chain goes beyond step 0, the 64-bit minimum of the buckets
+// (kernel_merge.cuh): a partial item runs pass 0 alone and writes its three rows to scratch, merge_reduce_kernel reduces the rows of a
+// genome, sketch_split_finish_kernel copies them out and computes the loop's own test on the merged buckets (a = 0: pass 0 was final).
+// ---------------------------------------------------------------------------------------------
+enum SketchItemKind { kSketchItemDirect = 0, kSketchItemPartial = 1 };
+struct SketchItem {
+    long long code_off, len, row;       // first code, number of codes, output row (direct: the genome; partial: the row in scratch)
+    int kind, pad;
+};
+
+// One workgroup per item.  The body is sketch_build_kernel's, restated (that kernel's instructions stay as they are): a direct item runs
+// all of it, a partial item ends behind pass 0.  LDS layout and block sizes as there.
+__global__ __launch_bounds__(1024)
+void sketch_build_items_kernel(const uint8_t* __restrict__ codes_all, const SketchItem* __restrict__ items, int k, int m, int p_aux,
+                               uint8_t* __restrict__ hll_out, u64* __restrict__ smh_out, uint8_t* __restrict__ aux_out,
+                               uint8_t* __restrict__ hll_part, u64* __restrict__ smh_part, uint8_t* __restrict__ aux_part) {
+    extern __shared__ unsigned char smem_raw[];
+    // layout: u64 h[m] | u32 regs[16384/4] (byte registers) | u32 aregs[(1<<p_aux)/4] | u32 p[m] | u32 q[m] | i32 b[m] | i32 ctl[4]
+    const int n_aux = (aux_out && p_aux > 0) ? (1 << p_aux) : 0;
+    const int ms = smh_out ? m : 0;
+    u64* h = reinterpret_cast<u64*>(smem_raw);
+    uint32_t* regs = reinterpret_cast<uint32_t*>(smem_raw + (size_t)ms * 8);
+    uint32_t* aregs = regs + 16384 / 4;
+    uint32_t* pp = aregs + (n_aux + 3) / 4;
+    uint32_t* qq = pp + ms;
+    int* bb = reinterpret_cast<int*>(qq + ms);
+    int* ctl = bb + ms;
+
+    const SketchItem it = items[blockIdx.x];
+    const bool partial = it.kind == kSketchItemPartial;
+    const uint8_t* codes = codes_all + it.code_off;
+    const long long L = it.len;
+    const long long g = it.row;
+    const uint32_t mask = (uint32_t)(m - 1);
+
+    for (int t = threadIdx.x; t < ms; t += (int)blockDim.x) h[t] = ~0ull;
+    for (int t = threadIdx.x; t < 16384 / 4; t += (int)blockDim.x) regs[t] = 0;
+    for (int t = threadIdx.x; t < (n_aux + 3) / 4; t += (int)blockDim.x) aregs[t] = 0;
+    if (threadIdx.x == 0) ctl[0] = 0;
+    __syncthreads();
+
+    // pass 0: HLL registers and the step-0 offer of every k-mer
+    for_each_kmer(codes, L, k, [&](u64 kmer) {
+        const u64 canon = canonical_kmer(kmer, (unsigned)k);
+        const u64 hv = wang_hash(canon);
+        uint32_t idx, rank;
+        hll_slot(hv, 14, &idx, &rank);
+        lds_byte_max(regs, idx, rank);
+        if (n_aux) { hll_slot(hv, p_aux, &idx, &rank); lds_byte_max(aregs, idx, rank); }
+        if (ms) {
+            u64 st = canon ? canon : 1337ull;
+            const u64 v = wyhash64_next(st);
+            const u64 offer = v >> 32;
+            u64* slot = &h[(uint32_t)v & mask];
+            if (offer < *(volatile u64*)slot) atomicMin(slot, offer);
+        }
+    });
+    __syncthreads();
+
+    if (ms && !partial) {
+        int J = 0;
+        while (true) {
+            int la = 0;
+            for (int t = threadIdx.x; t < ms; t += (int)blockDim.x) la = max(la, (int)min((u64)(m - 1), h[t] >> 32));
+            atomicMax(&ctl[0], la);
+            __syncthreads();
+            const int a = ctl[0];
+            __syncthreads();
+            if (threadIdx.x == 0) ctl[0] = 0;
+            if (a <= J) break;
+            if (a > kSketchJmaxParallel) {
+                // few k-mers per bucket: the reference's sequential algorithm on one lane, as in sketch_build_kernel
+                for (int t = threadIdx.x; t < ms; t += (int)blockDim.x) { h[t] = ~0ull; qq[t] = 0xFFFFFFFFu; pp[t] = 0; bb[t] = 0; }
+                __syncthreads();
+                if (threadIdx.x == 0) {
+                    bb[m - 1] = m;
+                    u64 aa = (u64)(m - 1), ii = 0;
+                    for (long long i = k - 1; i < L; ++i) {
+                        u64 kmer;
+                        if (!kmer_at(codes, i, k, &kmer)) continue;
+                        const u64 canon = canonical_kmer(kmer, (unsigned)k);
+                        u64 st = canon ? canon : 1337ull;
+                        u64 j = 0;
+                        while (j <= aa) {
+                            const u64 v = wyhash64_next(st);
+                            const uint32_t kk = (uint32_t)v & mask;
+                            if ((u64)qq[j] != ii) { qq[j] = (uint32_t)ii; pp[j] = (uint32_t)j; }
+                            if ((u64)qq[kk] != ii) { qq[kk] = (uint32_t)ii; pp[kk] = kk; }
+                            const uint32_t tmp = pp[kk]; pp[kk] = pp[j]; pp[j] = tmp;
+                            const u64 crj = (j << 32) | (v >> 32);
+                            if (crj < h[pp[j]]) {
+                                const uint32_t jprime = min((uint32_t)(m - 1), (uint32_t)(h[pp[j]] >> 32));
+                                h[pp[j]] = crj;
+                                if (j < jprime) {
+                                    --bb[jprime];
+                                    ++bb[j];
+                                    while (bb[aa] == 0) --aa;
+                                }
+                            }
+                            ++j;
+                        }
+                        ++ii;
+                    }
+                }
+                __syncthreads();
+                break;
+            }
+            J = a;
+            // every k-mer re-runs its chain up to step J
+            for_each_kmer(codes, L, k, [&](u64 kmer) {
+                const u64 canon = canonical_kmer(kmer, (unsigned)k);
+                u64 st = canon ? canon : 1337ull;
+                uint32_t pos[2 * (kSketchJmaxParallel + 1)], val[2 * (kSketchJmaxParallel + 1)];
+                int cnt = 0;
+                for (int j = 0; j <= J; ++j) {
+                    const u64 v = wyhash64_next(st);
+                    const uint32_t kk = (uint32_t)v & mask;
+                    uint32_t pj = (uint32_t)j, pk = kk;
+                    int ij = -1, ik = -1;
+                    for (int t = 0; t < cnt; ++t) {
+                        if (pos[t] == (uint32_t)j) { pj = val[t]; ij = t; }
+                        if (pos[t] == kk) { pk = val[t]; ik = t; }
+                    }
+                    if (ik >= 0) val[ik] = pj; else { pos[cnt] = kk; val[cnt] = pj; ik = cnt++; }
+                    if (kk != (uint32_t)j) {
+                        if (ij >= 0) val[ij] = pk; else { pos[cnt] = (uint32_t)j; val[cnt] = pk; cnt++; }
+                    }
+                    const uint32_t bucket = (kk == (uint32_t)j) ? pj : pk;
+                    atomicMin(&h[bucket], ((u64)j << 32) | (v >> 32));
+                }
+            });
+            __syncthreads();
+        }
+    }
+    __syncthreads();
+    uint8_t* hll_row = (partial ? hll_part : hll_out) + g * 16384;
+    uint8_t* aux_row = (partial ? aux_part : aux_out) + g * n_aux;
+    u64* smh_row = (partial ? smh_part : smh_out) + g * (long long)m;
+    uint32_t* out32 = reinterpret_cast<uint32_t*>(hll_row);
+    for (int t = threadIdx.x; t < 16384 / 4; t += (int)blockDim.x) out32[t] = regs[t];
+    for (int t = threadIdx.x; t < n_aux; t += (int)blockDim.x) aux_row[t] = (uint8_t)(aregs[t >> 2] >> ((t & 3) * 8));
+    for (int t = threadIdx.x; t < ms; t += (int)blockDim.x) smh_row[t] = h[t];
+}
+
+// One block per split genome s: the merged rows (row s of each kind) to output row genome[s], 16 B per lane, and with SuperMinHash rows
+// a = max_b min(m-1, h[b] >> 32) on the merged buckets -- sketch_build_kernel's test behind pass 0.  a > 0 (poly-A, mostly resets, fewer
+// distinct k-mers than buckets): s is appended to the fallback list, which the host rebuilds with direct items.  A block appends at
+// most once, so the list never holds more than gridDim.x entries.  smh_vec: m is even and both bucket arrays are 16-byte aligned.
+__global__ __launch_bounds__(kBlock)
+void sketch_split_finish_kernel(const long long* __restrict__ genome, int m, int n_aux, int smh_vec, const uint4* __restrict__ hll_in,
+                                const u64* __restrict__ smh_in, const uint4* __restrict__ aux_in, uint8_t* __restrict__ hll_out,
+                                u64* __restrict__ smh_out, uint8_t* __restrict__ aux_out, int* __restrict__ fb_count, int* __restrict__ fb_list) {
+    __shared__ int wave_a[kWavesPerBlock];
+    const long long s = blockIdx.x, g = genome[s];
+    uint4* hd = reinterpret_cast<uint4*>(hll_out + g * 16384);
+    for (int t = threadIdx.x; t < 16384 / 16; t += kBlock) hd[t] = hll_in[s * (16384 / 16) + t];
+    if (n_aux) {
+        uint4* ad = reinterpret_cast<uint4*>(aux_out + g * n_aux);
+        for (int t = threadIdx.x; t < n_aux / 16; t += kBlock) ad[t] = aux_in[s * (n_aux / 16) + t];
+    }
+    if (!smh_out) return;
+    int la = 0;
+    const u64* src = smh_in + s * (long long)m;
+    u64* dst = smh_out + g * (long long)m;
+    if (smh_vec) {
+        const uint4* src4 = reinterpret_cast<const uint4*>(src);
+        uint4* dst4 = reinterpret_cast<uint4*>(dst);
+        for (int t = threadIdx.x; t < m / 2; t += kBlock) {
+            const uint4 w = src4[t];
+            la = max(la, (int)min((uint32_t)(m - 1), max(w.y, w.w)));
+            dst4[t] = w;
+        }
+    } else {
+        for (int t = threadIdx.x; t < m; t += kBlock) {
+            const u64 w = src[t];
+            la = max(la, (int)min((u64)(m - 1), w >> 32));
+            dst[t] = w;
+        }
+    }
+    for (int d = kWave / 2; d > 0; d >>= 1) la = max(la, __shfl_xor(la, d, kWave));
+    if ((threadIdx.x & (kWave - 1)) == 0) wave_a[threadIdx.x / kWave] = la;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int a = 0;
+        for (int w = 0; w < kWavesPerBlock; ++w) a = max(a, wave_a[w]);
+        if (a > 0) fb_list[atomicAdd(fb_count, 1)] = (int)s;
+    }
 }
 
 __global__ __launch_bounds__(kBlock)

@@ -25,7 +25,8 @@
 //   kernel_pairlist.cuh explicit pair lists (test building blocks)
 //   kernel_pairs.cuh    stage 1 of the pair-list passes (a caller's list of pairs under any criterion) and of the drop-in launchers'
 //                       explicit-list path: filter, signature verification, direct band comparison
-//   kernel_sketch.cuh   synth_kernel, sketch_build_kernel (build_sketch on the GPU), permute_rows
+//   kernel_sketch.cuh   synth_kernel, sketch_build_kernel (build_sketch on the GPU), sketch_build_items_kernel / sketch_split_finish_kernel
+//                       (the same sketches with long genomes split across workgroups), permute_rows
 //   kernel_small.cuh    small_pass_kernel: the whole pass of a set of <= 2 048 genomes in one cooperative launch
 //   kernel_query.cuh    query passes (a query set against the database): CB windows, rectangular signature join, verification,
 //                       literal stream kernel for any band shape, stage 2a on two sets' bit planes
@@ -112,6 +113,7 @@
 #include "host_cluster.hpp"      // single-linkage clusters: scratch and launches behind selhip_ctx_cluster / selhip_components
 #include "host_greedy.hpp"       // greedy representative clusters: rounds, scratch and launches behind selhip_ctx_cluster_greedy / selhip_greedy_representatives
 #include "host_merge.hpp"       // sketches merged by group: checks, levels and launches behind selhip_merge_sketches / selhip_ctx_merge_groups
+#include "host_build.hpp"       // split sketch builder: items, launches, the reduction through merge_run, the fallback launch
 #include "abi_context.inc"       // C ABI: context (create, upload / attach, run, results, timing)
 #include "abi_pairs.inc"         // C ABI: pair-list passes (run_pairs)
 #include "abi_query.inc"         // C ABI: query passes (upload / attach queries, run_queries)
@@ -119,5 +121,6 @@
 #include "abi_cluster.inc"       // C ABI: clusters of the result list (cluster) and of a caller's edge list (components)
 #include "abi_greedy.inc"        // C ABI: greedy representative clusters of the result list (cluster_greedy) and of a caller's edge list (greedy_representatives)
 #include "abi_merge.inc"        // C ABI: sketches merged by group (merge_sketches, ctx_merge_groups)
+#include "abi_build.inc"        // C ABI: sketch construction with long genomes split across workgroups (build_sketches_split, build_split_plan)
 #include "abi_blocks.inc"        // C ABI: building blocks, synthetic sketches, sketch construction, memory helpers
 #include "abi_compat.inc"        // C ABI: drop-in launch_kernel_smh / launch_kernel_CBsmh

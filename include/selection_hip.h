@@ -39,6 +39,7 @@ extern "C" {
 #define SELHIP_E_OVERFLOW     -3   /* an output buffer was too small; nothing was lost: counts are exact */
 #define SELHIP_E_NODEVICE     -4   /* no usable gfx950 device                                           */
 #define SELHIP_E_STATE        -5   /* call sequence error (e.g. run before upload)                      */
+#define SELHIP_E_NOMEM        -6   /* the call would need more device scratch than it may take          */
 
 /* == struct Result of src/selection_kernels_wrapper.hpp:6-9 (same layout: 12 bytes) */
 typedef struct { int32_t x, y; float sim; } selhip_result_t;
@@ -939,10 +940,43 @@ int selhip_permute_rows(const void* d_src, void* d_dst, const int32_t* d_perm, i
  *     to the files the reference writes.  d_codes: one byte per base (0..3 = A,C,G,T; 4 = window reset: non-ACGT
  *     character or record boundary), genomes concatenated; d_offsets[n_genomes+1] (int64) delimit them
  *     (selhost_fasta_codes produces the codes).  d_smh / d_aux_hll may be NULL.  m must already be rounded up to a
- *     power of two (policy.h:12-19), m <= 2048.  One workgroup per genome.
+ *     power of two (policy.h:12-19), m <= 2048.  One workgroup per genome (selhip_build_sketches) or per chunk of a long
+ *     genome (selhip_build_sketches_split).
  * --------------------------------------------------------------------------------------------------- */
 int selhip_build_sketches(const uint8_t* d_codes, const int64_t* d_offsets, int64_t n_genomes, int k, int m, int p_aux,
                           uint8_t* d_hll, uint64_t* d_smh, uint8_t* d_aux_hll, void* hip_stream);
+/* The same sketches with long genomes SPLIT across workgroups (csrc/kernel_sketch.cuh): byte for byte the rows
+ * selhip_build_sketches writes.  The k-mer end positions of a genome of L codes are [k-1, L); with a chunk length C, chunk c owns the
+ * end positions [k-1 + c C, min(k-1 + (c+1) C, L)); a genome has max(1, ceil((L - (k-1)) / C)) chunks and is split when it has two or
+ * more.  Every chunk of a split genome is sketched by its own workgroup (pass 0: registers and step-0 offers) into scratch, the rows of
+ * a genome are reduced as selhip_merge_sketches reduces a group (no lane reduces more than SELHIP_MERGE_SEGMENT rows in sequence), and a
+ * split genome whose merged buckets show that pass 0 was not final (poly-A, mostly resets, fewer distinct k-mers than buckets) is
+ * rebuilt whole by one more launch; every other genome is one workgroup, longest first.
+ *   chunk: SELHIP_SPLIT_OFF (nothing is split), SELHIP_SPLIT_AUTO, or C itself, a positive multiple of 64.  AUTO never cuts below
+ *     65 536 end positions: C = max(65 536, the call's end positions / (w x resident workgroups) rounded up to 65 536), w = 1, doubled
+ *     until the partial rows (16 384 + 8 m + 2^p_aux bytes per chunk) fit 1 GiB.  An explicit C whose partial rows exceed 1 GiB:
+ *     SELHIP_E_NOMEM with a message, nothing is written.
+ *   h_offsets: the offsets on the host, or NULL: they are copied back from d_offsets once (not with SELHIP_SPLIT_OFF, which never reads them).
+ *   A plan without a split genome (always with SELHIP_SPLIT_OFF; AUTO on short genomes; n_genomes == 0) issues exactly the launch of
+ *   selhip_build_sketches.
+ * SELHIP_E_BADARG before any HIP call, with a message and the outputs untouched: what selhip_build_sketches refuses; a chunk that is
+ * none of the above; unless chunk is SELHIP_SPLIT_OFF, d_hll or d_aux_hll not 16-byte or d_smh not 8-byte aligned.  SELHIP_E_BADARG
+ * before any launch, likewise: offsets (given on the host or copied back) that are negative or descend.  info (may be NULL) receives the plan and what ran: the chunk length (0: off),
+ * the work items of the main launch, the split genomes and their chunks, the genomes rebuilt by the fallback launch, the levels of the
+ * reduction (0 without a split genome) and the threads per workgroup of the main launch.  The call owns its scratch, works on the
+ * caller's stream and waits for it. */
+#define SELHIP_SPLIT_AUTO 0
+#define SELHIP_SPLIT_OFF  (-1)
+typedef struct { int64_t chunk, items, split_genomes, chunks, fallback_genomes; int32_t levels, threads; } selhip_build_info_t;
+int selhip_build_sketches_split(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets /* or NULL: copied back once */,
+                                int64_t n_genomes, int k, int m, int p_aux, int64_t chunk,
+                                uint8_t* d_hll, uint64_t* d_smh, uint8_t* d_aux_hll, selhip_build_info_t* info /* or NULL */, void* hip_stream);
+/* The plan of such a call as plain arithmetic; needs no device.  m, p_aux: of the rows the call would ask for (0: none), they size the
+ * scratch; resident_blocks: the workgroups the device holds at once (what AUTO divides by; the entry above asks the runtime).
+ * chunk_counts[n_genomes] (may be NULL) receives the chunks of every genome; info->chunk, items, split_genomes, chunks, levels and
+ * threads are set, fallback_genomes is 0.  SELHIP_E_BADARG (bad chunk, k outside 1 .. 32, bad offsets) and SELHIP_E_NOMEM as above. */
+int selhip_build_split_plan(const int64_t* h_offsets, int64_t n_genomes, int k, int m, int p_aux, int64_t chunk, int64_t resident_blocks,
+                            int64_t* chunk_counts /* [n_genomes] or NULL */, selhip_build_info_t* info);
 
 /* ---------------------------------------------------------------------------------------------------
  * 5. Plain device-memory helpers so that a host program needs no HIP headers (the reference driver
