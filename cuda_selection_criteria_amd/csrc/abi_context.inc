@@ -404,21 +404,28 @@ static int validate_shape(selhip_ctx* c, int64_t n, int m, int p) {
     return SELHIP_OK;
 }
 
+// host cards of a sketch set (`noun` names it in the messages): finite, in [0, 2^63), ascending.  Touches nothing but the message
+static int check_host_cards(selhip_ctx* c, const char* noun, const double* cards, int64_t n) {
+    for (int64_t i = 0; i < n; ++i) {
+        const double v = cards[i];
+        if (!(v >= 0.0) || !(v < 9.2e18)) { set_err(&c->err, "%s[%lld] = %g is not a finite value in [0, 2^63)", noun, (long long)i, v); return SELHIP_E_BADARG; }
+        if (i && v < cards[i - 1]) { set_err(&c->err, "%s are not in ascending order at rank %lld", noun, (long long)i); return SELHIP_E_BADARG; }
+    }
+    return SELHIP_OK;
+}
+
 // the cards of a sketch set of n genomes (`noun` names it in the messages): computed with the device estimator from d_hll when none
-// are given, else validated and copied from the host, else the caller's device array as it is
+// are given, else validated (unless the caller ran check_host_cards already) and copied from the host, else the caller's device
+// array as it is
 static int load_cards(selhip_ctx* c, const char* noun, const uint8_t* d_hll, int64_t n, const double* cards_src, bool cards_on_host,
-                      DevBuf<double>& own, const double** d_cards) {
+                      DevBuf<double>& own, const double** d_cards, bool host_cards_checked = false) {
     if (!cards_src) {
         HIPCHK(&c->err, own.ensure((size_t)n));
         const int rc = compute_cards(c, d_hll, n, c->p, own.p);
         if (rc) return rc;
         *d_cards = own.p;
     } else if (cards_on_host) {
-        for (int64_t i = 0; i < n; ++i) {
-            const double v = cards_src[i];
-            if (!(v >= 0.0) || !(v < 9.2e18)) { set_err(&c->err, "%s[%lld] = %g is not a finite value in [0, 2^63)", noun, (long long)i, v); return SELHIP_E_BADARG; }
-            if (i && v < cards_src[i - 1]) { set_err(&c->err, "%s are not in ascending order at rank %lld", noun, (long long)i); return SELHIP_E_BADARG; }
-        }
+        if (!host_cards_checked) { const int rc = check_host_cards(c, noun, cards_src, n); if (rc) return rc; }
         HIPCHK(&c->err, own.ensure((size_t)n));
         HIPCHK(&c->err, hipMemcpyAsync(own.p, cards_src, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
         *d_cards = own.p;
@@ -429,6 +436,7 @@ static int load_cards(selhip_ctx* c, const char* noun, const uint8_t* d_hll, int
     return SELHIP_OK;
 }
 
+// the products of the sketches the context was just handed: bit planes, sparse lists, cards (host cards were checked by the caller)
 static int after_sketches(selhip_ctx* c, const double* cards_src, bool cards_on_host) {
     c->planes.khi = 0; c->hll_sparse_t = 0;
     if (c->n == 0) return SELHIP_OK;
@@ -442,7 +450,35 @@ static int after_sketches(selhip_ctx* c, const double* cards_src, bool cards_on_
         rc = build_sparse_lists(&c->err, c->stream, c->planes.bs.p, c->n, c->hll_sparse.p, c->hll_sparse_dev_t.p, &c->hll_sparse_t);
         if (rc) return rc;
     }
-    return load_cards(c, "cards", c->d_hll, c->n, cards_src, cards_on_host, c->own_cards, &c->d_cards);
+    return load_cards(c, "cards", c->d_hll, c->n, cards_src, cards_on_host, c->own_cards, &c->d_cards, true);
+}
+
+// A replacement of the database in two steps.  Everything that can refuse the call on its ARGUMENTS has passed when set_database
+// runs: it is the first statement that changes the context.  What can still fail from there on is a HIP call (an allocation, a copy,
+// a kernel of the plane / list / card builds); the context then holds neither the old set (its buffers may be half overwritten) nor
+// the new one, so no_database leaves it holding none: the next pass selects nothing, queries and auxiliary sketches are gone
+static void set_database(selhip_ctx* c, int64_t n, int m, int p_hll) {
+    c->n = n; c->m = m; c->p = p_hll; c->have_run = false; c->pending = false; c->cand_begin = 0; c->sig_key = 0; c->small_pass_failed = false;
+    c->d_aux_hll = nullptr; c->p_aux = 0;
+    drop_queries(c);
+}
+
+static int no_database(selhip_ctx* c, int rc) {
+    c->n = 0; c->d_hll = nullptr; c->d_aux = nullptr; c->d_cards = nullptr; c->owns_sketches = false;
+    c->planes.khi = 0; c->hll_sparse_t = 0;
+    return rc;
+}
+
+static int upload_rows(selhip_ctx* c, const uint8_t* h_hll, const uint64_t* h_aux, const double* h_cards) {
+    const size_t hb = (size_t)1 << c->p;
+    if (c->n > 0) {
+        HIPCHK(&c->err, c->own_hll.ensure((size_t)c->n * hb));
+        HIPCHK(&c->err, c->own_aux.ensure((size_t)c->n * c->m));
+        HIPCHK(&c->err, hipMemcpyAsync(c->own_hll.p, h_hll, (size_t)c->n * hb, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(&c->err, hipMemcpyAsync(c->own_aux.p, h_aux, (size_t)c->n * c->m * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    c->d_hll = c->own_hll.p; c->d_aux = (const u64*)c->own_aux.p; c->owns_sketches = true;
+    return after_sketches(c, h_cards, true);
 }
 
 int selhip_ctx_upload(selhip_ctx* c, const uint8_t* h_hll, const uint64_t* h_aux, const double* h_cards,
@@ -452,18 +488,10 @@ int selhip_ctx_upload(selhip_ctx* c, const uint8_t* h_hll, const uint64_t* h_aux
     int rc = validate_shape(c, n, m, p_hll);
     if (rc) return rc;
     if (n > 0 && (!h_hll || !h_aux)) { set_err(&c->err, "null sketch pointer"); return SELHIP_E_BADARG; }
-    c->n = n; c->m = m; c->p = p_hll; c->have_run = false; c->pending = false; c->cand_begin = 0; c->sig_key = 0; c->small_pass_failed = false;
-    const size_t hb = (size_t)1 << p_hll;
-    if (n > 0) {
-        HIPCHK(&c->err, c->own_hll.ensure((size_t)n * hb));
-        HIPCHK(&c->err, c->own_aux.ensure((size_t)n * m));
-        HIPCHK(&c->err, hipMemcpyAsync(c->own_hll.p, h_hll, (size_t)n * hb, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(&c->err, hipMemcpyAsync(c->own_aux.p, h_aux, (size_t)n * m * 8, hipMemcpyHostToDevice, c->stream));
-    }
-    c->d_hll = c->own_hll.p; c->d_aux = (const u64*)c->own_aux.p; c->owns_sketches = true;
-    c->d_aux_hll = nullptr; c->p_aux = 0;
-    drop_queries(c);
-    return after_sketches(c, h_cards, true);
+    if (h_cards) { rc = check_host_cards(c, "cards", h_cards, n); if (rc) return rc; }
+    set_database(c, n, m, p_hll);
+    rc = upload_rows(c, h_hll, h_aux, h_cards);
+    return rc ? no_database(c, rc) : SELHIP_OK;
 }
 
 int selhip_ctx_attach(selhip_ctx* c, const uint8_t* d_hll, const uint64_t* d_aux, const double* d_cards,
@@ -474,11 +502,10 @@ int selhip_ctx_attach(selhip_ctx* c, const uint8_t* d_hll, const uint64_t* d_aux
     if (rc) return rc;
     if (n > 0 && (!d_hll || !d_aux)) { set_err(&c->err, "null sketch pointer"); return SELHIP_E_BADARG; }
     if (((uintptr_t)d_hll & 15) || ((uintptr_t)d_aux & 15)) { set_err(&c->err, "sketch pointers must be 16-byte aligned"); return SELHIP_E_BADARG; }
-    c->n = n; c->m = m; c->p = p_hll; c->have_run = false; c->pending = false; c->cand_begin = 0; c->sig_key = 0; c->small_pass_failed = false;
+    set_database(c, n, m, p_hll);
     c->d_hll = d_hll; c->d_aux = (const u64*)d_aux; c->owns_sketches = false;
-    c->d_aux_hll = nullptr; c->p_aux = 0;
-    drop_queries(c);
-    return after_sketches(c, d_cards, false);
+    rc = after_sketches(c, d_cards, false);
+    return rc ? no_database(c, rc) : SELHIP_OK;
 }
 
 int selhip_hll_cards(selhip_ctx* c, const uint8_t* d_hll, int64_t n, int p, double* d_cards_out) {

@@ -121,7 +121,7 @@ int greedy_call(selhip_ctx* c, double min_value, int rule, const uint32_t* d_pri
         set_err(&c->err, "selhip_ctx_cluster_greedy: bad order_rule %d (SELHIP_REP_MAX_DEGREE, _MIN_RANK, _MAX_RANK or _PRIORITY)", rule);
         return SELHIP_E_BADARG;
     }
-    if ((rule == SELHIP_REP_PRIORITY) != (d_priority != nullptr)) {
+    if ((rule == SELHIP_REP_PRIORITY) != (d_priority != nullptr) && !(rule == SELHIP_REP_PRIORITY && c->n == 0)) {      // (no genome, no score to read)
         set_err(&c->err, "selhip_ctx_cluster_greedy: d_priority goes with SELHIP_REP_PRIORITY, and with no other order_rule (rule %d, d_priority %s)", rule,
                 d_priority ? "given" : "NULL");
         return SELHIP_E_BADARG;

@@ -269,7 +269,21 @@ int selhip_ctx_set_fp_mode(selhip_ctx* ctx, int fp_mode);
  *   selhip_ooc_select, selhip_multi_select,            | grouping, no one-launch small pass ("small_pass_used" 0); same records and
  *   launch_kernel_*                                    | statistics as the oracle at that p
  *   selhip_hll_union_hist, selhip_ertl_estimate        | any p in 4 .. 20
- *   SELHIP_CRIT_NONE, HLL matrices, query passes       | refused: SELHIP_E_BADARG, they need p_hll = 14 */
+ *   SELHIP_CRIT_NONE, HLL matrices, query passes       | refused: SELHIP_E_BADARG, they need p_hll = 14
+ *
+ * A context may be given one set after another, of any shape (tests/test_context_reuse_gpu.py).  A successful upload / attach
+ *   RESETS  the results and statistics of the last pass (selhip_ctx_stats / _result_count / _fetch answer SELHIP_E_STATE until the
+ *           next pass), the candidate begin (0), the queries with their auxiliary sketches (query passes: SELHIP_E_STATE until new
+ *           queries are loaded), the database's auxiliary HLL sketches, uploaded, attached or folded (criteria that need them:
+ *           SELHIP_E_STATE), the cached band signatures ("sig_cache"), the query side's database signatures and its index;
+ *   KEEPS   criterion, measure, estimator, min_matches / min_containment, both top-k settings, the row rounds, the row
+ *           interleave, the pipeline, stage-2 grouping, the fp mode, the stream and every selhip_ctx_set_param value.
+ * Failure: every check that can refuse the call on its ARGUMENTS (shape, null or misaligned pointers, host cards that are not
+ * finite, negative or not ascending) runs before the context is touched: after such a SELHIP_E_BADARG the context is exactly what
+ * it was -- a used one still holds its database, queries, auxiliary sketches and results and its next pass gives the old set's
+ * answer, a fresh one is still fresh.  A failure that shows only later (a HIP error while the rows are copied or the bit planes,
+ * sparse lists or cards are built) leaves a context that holds NO database, after upload and attach alike: n = 0, the queries
+ * dropped, a pass selects nothing until the next successful upload / attach. */
 int selhip_ctx_upload(selhip_ctx* ctx, const uint8_t* h_hll, const uint64_t* h_aux, const double* h_cards,
                       int64_t n_genomes, int m, int p_hll);
 /* Same, for sketches that already live in device memory (caller keeps ownership and must keep them
@@ -769,8 +783,9 @@ int selhip_ctx_cluster(selhip_ctx* ctx, double min_value, int rep_rule,
  *       SELHIP_REP_MIN_RANK    reversed rank: the smallest genome first
  *       SELHIP_REP_MAX_RANK    rank: the largest sketch first, the CD-HIT order
  *       SELHIP_REP_PRIORITY    (d_priority[g], reversed rank): d_priority is the caller's uint32_t[n] in device memory, a quality score
- *                              for example; accepted by this entry only.  d_priority NULL with this rule, or non-NULL with another
- *                              rule, is SELHIP_E_BADARG; so is any other rule.
+ *                              for example; accepted by this entry only.  d_priority NULL with this rule (unless the context holds
+ *                              an empty set: there is no score to read), or non-NULL with another rule, is SELHIP_E_BADARG; so is
+ *                              any other rule.
  *     THE REPRESENTATIVES: visit the vertices by descending key; a vertex is a representative if and only if none of its neighbours is
  *     one already -- the lexicographically first maximal independent set of the graph under the order.  A vertex without an edge is one.
  *     THE ASSIGNMENT: every other vertex g belongs to the representative r for which the edge {g, r} has the greatest value; values

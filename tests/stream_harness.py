@@ -77,21 +77,34 @@ def by_ik(rec):
 
 
 class Sets:
-    """one seed's data and every expected value of the cases, each computed once (host only)"""
+    """one seed's data and every expected value of the cases, each computed once (host only).  The shape is an argument (the defaults
+    are the constants above, which tests/test_streams_*.py use): n_d database and n_q query genomes of m buckets, auxiliary sketches
+    of precision p_aux, the threshold tau, the generator's seed (default SEEDS[name]) and forge(hll) -> hll, a step that rewrites
+    registers of the generated sketches before anything is derived from them (tests/context_reuse_model.py)"""
 
-    def __init__(self, oracle, name):
-        self.oracle, self.name, self.seed = oracle, name, SEEDS[name]
-        cfg = SynthConfig("streams-" + name, N_D + N_Q, M, TAU, self.seed, p_aux=P_AUX, mode=1, n_sh_lo=8_000, n_sh_hi=60_000)
+    p_hll = 14
+
+    def __init__(self, oracle, name, n_d=N_D, n_q=N_Q, m=M, p_aux=P_AUX, tau=TAU, seed=None, forge=None):
+        self.oracle, self.name, self.seed = oracle, name, SEEDS[name] if seed is None else seed
+        self.n_d, self.n_q, self.m, self.p_aux, self.tau = n_d, n_q, m, p_aux, tau
+        cfg = SynthConfig("streams-" + name, n_d + n_q, m, tau, self.seed, p_aux=p_aux, mode=1, n_sh_lo=8_000, n_sh_hi=60_000)
         hll, aux, aux_hll = pkg.synth_host(cfg)
+        if forge is not None:
+            hll = forge(hll)
         rng = np.random.default_rng(self.seed)
-        pick = np.zeros(N_D + N_Q, dtype=bool)
-        pick[rng.choice(N_D + N_Q, N_Q, replace=False)] = True
-        self.D, self.Q = self._side(hll[~pick], aux[~pick], aux_hll[~pick]), self._side(hll[pick], aux[pick], aux_hll[pick])
-        self.r, self.b = banding()
+        pick = np.zeros(n_d + n_q, dtype=bool)
+        pick[rng.choice(n_d + n_q, n_q, replace=False)] = True
+        self._finish(self._side(hll[~pick], aux[~pick], aux_hll[~pick]), self._side(hll[pick], aux[pick], aux_hll[pick]), rng)
+
+    def _finish(self, D, Q, rng):
+        """the two sides in rank order, and what is drawn for them"""
+        self.D, self.Q = D, Q
+        self.r, self.b = pkg.banding(self.m, self.tau)
+        self.c_min = C_MIN * self.m // M
         # what no attach snapshots: the priorities of the greedy clusters, the positions of the query matrix
-        self.prio = rng.integers(0, 1 << 20, N_D).astype(np.int32)
-        self.row_pos = rng.permutation(N_Q).astype(np.int32)
-        self.col_pos = rng.permutation(N_D).astype(np.int32)
+        self.prio = rng.integers(0, 1 << 20, self.n_d).astype(np.int32)
+        self.row_pos = rng.permutation(self.n_q).astype(np.int32)
+        self.col_pos = rng.permutation(self.n_d).astype(np.int32)
 
     def _side(self, hll, aux, aux_hll):
         cards = self.oracle.cards(hll)
@@ -100,8 +113,8 @@ class Sets:
 
     def _select(self, crit, aux_hll=None):
         D = self.D
-        return records(self.oracle.select(D.hll, D.aux, D.cards, TAU, self.r, self.b, use_cb=True, criterion=crit,
-                                          aux_hll=D.aux_hll if aux_hll is None else aux_hll, p_aux=P_AUX)[0])
+        return records(self.oracle.select(D.hll, D.aux, D.cards, self.tau, self.r, self.b, use_cb=True, criterion=crit,
+                                          aux_hll=D.aux_hll if aux_hll is None else aux_hll, p=self.p_hll, p_aux=self.p_aux)[0])
 
     # -- all-pairs passes ---------------------------------------------------------------------------
     @functools.cached_property
@@ -114,7 +127,7 @@ class Sets:
 
     @functools.cached_property
     def hll_a_folded(self):
-        return self._select(pkg.CRIT_HLL_A, aux_hll=fold_model.fold(self.D.hll, P_AUX))
+        return self._select(pkg.CRIT_HLL_A, aux_hll=fold_model.fold(self.D.hll, self.p_aux))
 
     @functools.cached_property
     def two_stage(self):
@@ -122,7 +135,7 @@ class Sets:
 
     @functools.cached_property
     def none(self):
-        return flat_oracle_select(self.oracle, self.D.hll, self.D.cards, TAU, True, FP_FMA)[0]
+        return flat_oracle_select(self.oracle, self.D.hll, self.D.cards, self.tau, True, FP_FMA)[0]
 
     @functools.cached_property
     def counts(self):
@@ -130,11 +143,11 @@ class Sets:
 
     @functools.cached_property
     def smh_c(self):
-        return self.none[self.counts[self.none["i"], self.none["k"]] >= C_MIN]
+        return self.none[self.counts[self.none["i"], self.none["k"]] >= self.c_min]
 
     @functools.cached_property
     def smh_c_v(self):
-        return by_ik(smhv_model.expected(self.D.aux, self.D.cards, TAU, use_cb=True, c_min=C_MIN, counts=self.counts)[0])
+        return by_ik(smhv_model.expected(self.D.aux, self.D.cards, self.tau, use_cb=True, c_min=self.c_min, counts=self.counts)[0])
 
     @functools.cached_property
     def topk(self):
@@ -151,12 +164,12 @@ class Sets:
         Q, D = self.Q, self.D
         hll, aux, cards = np.concatenate([Q.hll, D.hll]), np.concatenate([Q.aux, D.aux]), np.concatenate([Q.cards, D.cards])
         perm = pkg.sort_by_card(cards)
-        pairs = self.oracle.select(hll[perm], aux[perm], cards[perm], TAU, self.r, self.b, use_cb=True)[0]
+        pairs = self.oracle.select(hll[perm], aux[perm], cards[perm], self.tau, self.r, self.b, use_cb=True)[0]
         g1, g2 = perm[pairs["i"]], perm[pairs["k"]]
-        cross = (g1 < N_Q) != (g2 < N_Q)
+        cross = (g1 < self.n_q) != (g2 < self.n_q)
         out = np.zeros(int(cross.sum()), dtype=PAIR_DTYPE)
-        out["i"] = np.where(g1 < N_Q, g1, g2)[cross]
-        out["k"] = np.where(g1 < N_Q, g2, g1)[cross] - N_Q
+        out["i"] = np.where(g1 < self.n_q, g1, g2)[cross]
+        out["k"] = np.where(g1 < self.n_q, g2, g1)[cross] - self.n_q
         out["jaccard"] = pairs["jacc"][cross]
         return by_ik(out)
 
@@ -173,8 +186,8 @@ class Sets:
         hit = np.stack([S["i"], S["k"]], axis=1)
         flip = rng.random(len(hit)) < 0.5
         hit[flip] = hit[flip][:, ::-1]
-        x = rng.integers(0, N_D, N_LIST - len(hit))
-        y = (x + rng.integers(1, N_D, len(x))) % N_D
+        x = rng.integers(0, self.n_d, N_LIST - len(hit))
+        y = (x + rng.integers(1, self.n_d, len(x))) % self.n_d
         return rng.permutation(np.concatenate([hit, np.stack([x, y], axis=1)])).astype(np.int32)
 
     @functools.cached_property
@@ -190,8 +203,8 @@ class Sets:
     def matrix_jaccard(self):
         """J of every pair from the oracle's exhaustive loop without a threshold, mirrored, 1.0 on the diagonal"""
         rec = flat_oracle_select(self.oracle, self.D.hll, self.D.cards, -np.inf, False, FP_FMA)[0]
-        assert len(rec) == N_D * (N_D - 1) // 2                       # (no empty sketch in the set: every pair has a record)
-        Jm = np.ones((N_D, N_D))
+        assert len(rec) == self.n_d * (self.n_d - 1) // 2                       # (no empty sketch in the set: every pair has a record)
+        Jm = np.ones((self.n_d, self.n_d))
         Jm[rec["i"], rec["k"]] = rec["jaccard"]
         Jm[rec["k"], rec["i"]] = rec["jaccard"]
         return Jm
@@ -200,7 +213,7 @@ class Sets:
     def dense_aux(self):
         """bucket rows for the SuperMinHash matrix: the generator's unrelated genomes share no bucket, so that both sets' matrices would
         be zero nearly everywhere; these rows share a random part of a base row each (smh_matrix_model.random_rows)"""
-        return smh_matrix_model.random_rows(N_D, M, self.seed + 7)
+        return smh_matrix_model.random_rows(self.n_d, self.m, self.seed + 7)
 
     @functools.cached_property
     def matrix_smh_matches(self):
@@ -218,11 +231,11 @@ class Sets:
     # -- clusters -----------------------------------------------------------------------------------
     @functools.cached_property
     def clusters(self):
-        return cluster_model.clusters(cluster_model.record_edges(self.smh_a), N_D, "max_degree")
+        return cluster_model.clusters(cluster_model.record_edges(self.smh_a), self.n_d, "max_degree")
 
     @functools.cached_property
     def greedy(self):
-        res = greedy_model.clusters(self.smh_a, N_D, rule="priority", priority=self.prio.astype(np.int64))
+        res = greedy_model.clusters(self.smh_a, self.n_d, rule="priority", priority=self.prio.astype(np.int64))
         res.pop("rounds_bound")
         return res
 
@@ -231,7 +244,7 @@ class Sets:
     def block_pairs(self):
         """int32 [N_BLOCK, 2]: a quarter of it pairs of one cluster, the rest random"""
         rng = np.random.default_rng(self.seed + 2)
-        p = np.stack([rng.integers(0, N_D, N_BLOCK), rng.integers(0, N_D, N_BLOCK)], axis=1)
+        p = np.stack([rng.integers(0, self.n_d, N_BLOCK), rng.integers(0, self.n_d, N_BLOCK)], axis=1)
         S = self.none[rng.choice(len(self.none), N_BLOCK // 4)]
         p[: len(S), 0], p[: len(S), 1] = S["k"], S["i"]
         return p.astype(np.int32)
@@ -257,11 +270,11 @@ class Sets:
 
     @functools.cached_property
     def block_fold(self):
-        return fold_model.fold(self.D.hll[:64], P_AUX)
+        return fold_model.fold(self.D.hll[:64], self.p_aux)
 
     @functools.cached_property
     def synth_cfg(self):
-        return SynthConfig("streams-gen-" + self.name, 48, M, TAU, self.seed + 3, p_aux=P_AUX, mode=1, n_sh_lo=2_000, n_sh_hi=30_000)
+        return SynthConfig("streams-gen-" + self.name, 48, self.m, self.tau, self.seed + 3, p_aux=self.p_aux, mode=1, n_sh_lo=2_000, n_sh_hi=30_000)
 
     @functools.cached_property
     def block_synth(self):
@@ -289,13 +302,13 @@ class Sets:
                 path = Path(tmp) / f"g{g}.fna"
                 seq = "".join("ACGTN"[c] for c in codes[off[g]:off[g + 1]])
                 path.write_text(">g%d\n%s\n" % (g, seq))
-                hll, aux, smh, _ = bo.sketch(path, m=64, p_aux=P_AUX)
+                hll, aux, smh, _ = bo.sketch(path, m=64, p_aux=self.p_aux)
                 out["hll"].append(hll), out["smh"].append(smh), out["aux_hll"].append(aux)
         return {k: np.stack(v) for k, v in out.items()}
 
     @functools.cached_property
     def perm(self):
-        return np.random.default_rng(self.seed + 5).permutation(N_D).astype(np.int32)
+        return np.random.default_rng(self.seed + 5).permutation(self.n_d).astype(np.int32)
 
     @functools.cached_property
     def block_permute(self):
@@ -317,15 +330,15 @@ class Sets:
 
     @functools.cached_property
     def components(self):
-        return cluster_model.labels(self.edges, N_D).astype(np.int32)
+        return cluster_model.labels(self.edges, self.n_d).astype(np.int32)
 
     @functools.cached_property
     def keys(self):
-        return np.random.default_rng(self.seed + 6).integers(0, 1 << 40, N_D).astype(np.uint64)
+        return np.random.default_rng(self.seed + 6).integers(0, 1 << 40, self.n_d).astype(np.uint64)
 
     @functools.cached_property
     def greedy_reps(self):
-        return greedy_model.representatives(self.edges, N_D, [int(k) for k in self.keys]).astype(np.uint8)
+        return greedy_model.representatives(self.edges, self.n_d, [int(k) for k in self.keys]).astype(np.uint8)
 
 
 # case id -> (the attribute of Sets that is its expected value, kind): kind "list" = a record list (at least 20 records, the two sets'

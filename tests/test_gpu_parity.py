@@ -994,9 +994,24 @@ def test_event_timing_levels(oracle):
 def test_unsorted_cards_rejected(oracle):
     cfg = SynthConfig("unsorted", 50, 128, 0.9, 5, n_sh_lo=3000, n_sh_hi=3000)
     hll, aux, cards, _, _ = sorted_set(cfg, oracle)
+    r, b = pkg.banding(cfg.m, 0.9)
     with Selector(0) as sel:
         with pytest.raises(pkg.SelhipError):
             sel.upload(hll, aux, cards[::-1].copy())
+        # a refused upload leaves the context what it was (include/selection_hip.h, selhip_ctx_upload): a fresh one stays fresh ...
+        # (no set and no shape: a pass that needs no band shape selects nothing)
+        sel.set_criterion(pkg.CRIT_HLL_A)
+        assert sel.n == 0 and len(sel.run(0.9, MODE_CB_SMH, r, b)) == 0
+        sel.set_criterion(pkg.CRIT_SMH_A)
+        # ... and a used one keeps its set and gives its answer
+        want = oracle.select(hll[:20], aux[:20], cards[:20], 0.9, r, b)[0]
+        sel.upload(hll[:20], aux[:20], cards[:20])
+        with pytest.raises(pkg.SelhipError):
+            sel.upload(hll, aux, cards[::-1].copy())
+        assert sel.n == 20 and np.array_equal(sel.cards().view(np.uint64), cards[:20].view(np.uint64))
+        got = sel.run(0.9, MODE_CB_SMH, r, b)
+        assert np.array_equal(got["i"], want["i"]) and np.array_equal(got["k"], want["k"])
+        assert np.array_equal(got["jaccard"].view(np.uint64), want["jacc"].view(np.uint64))
 
 
 def test_rectangular_pass_and_out_of_core_driver(oracle):
