@@ -53,6 +53,10 @@ class Greedy(C.Structure):            # selhip_greedy_t: the six outputs of selh
                 ("d_cluster_size", C.c_void_p), ("d_cluster_rep", C.c_void_p)]
 
 
+class Forest(C.Structure):            # selhip_forest_t: the two outputs of selhip_ctx_spanning_forest, device pointers or NULL
+    _fields_ = [("d_edges", C.c_void_p), ("d_label", C.c_void_p)]
+
+
 class BuildInfo(C.Structure):         # selhip_build_info_t: the plan of selhip_build_sketches_split and what ran
     _fields_ = [("chunk", C.c_int64), ("items", C.c_int64), ("split_genomes", C.c_int64), ("chunks", C.c_int64),
                 ("fallback_genomes", C.c_int64), ("levels", C.c_int32), ("threads", C.c_int32)]
@@ -149,6 +153,8 @@ HIP_SYMBOLS = {
     "selhip_components": (_i, [_vp, _i64, _i64, _vp, _vp]),
     "selhip_ctx_cluster_greedy": (_i, [_vp, _d, _i, _vp, C.POINTER(Greedy), C.POINTER(_i64)]),
     "selhip_greedy_representatives": (_i, [_vp, _i64, _i64, _vp, _vp, C.POINTER(_i64), _vp]),
+    "selhip_ctx_spanning_forest": (_i, [_vp, _d, C.POINTER(Forest), C.POINTER(_i64)]),
+    "selhip_spanning_forest": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64), _vp]),
     "selhip_ctx_merge_groups": (_i, [_vp, _vp, _i64, C.POINTER(Merged)]),
     "selhip_merge_sketches": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "selhip_smh_a_pairs": (_i, [_vp, _i, _i, _i, _vp, _i64, _vp, _vp]),

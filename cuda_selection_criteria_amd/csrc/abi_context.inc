@@ -58,6 +58,7 @@ void selhip_ctx_destroy(selhip_ctx* c) {
     release_topk(c);
     release_cluster(c);
     release_greedy(c);
+    release_forest(c);
     release_merge(c);
     if (c->h_pc) (void)hipHostFree(c->h_pc);
     if (c->st_stage1) {
@@ -256,6 +257,8 @@ int selhip_ctx_get_param(const selhip_ctx* c, const char* name, int* value) {
     if (!std::strcmp(name, "cluster_blocks"))   { *value = g_cluster_blocks; return SELHIP_OK; }
     if (!std::strcmp(name, "greedy_clusters_last")) { *value = c->greedy_clusters_last; return SELHIP_OK; }  // clusters of the last selhip_ctx_cluster_greedy call, -1 = none yet
     if (!std::strcmp(name, "greedy_rounds_last"))   { *value = c->greedy_rounds_last; return SELHIP_OK; }    // ... and the rounds its selection took
+    if (!std::strcmp(name, "forest_rounds_last"))   { *value = c->forest_rounds_last; return SELHIP_OK; }    // rounds of the last selhip_ctx_spanning_forest call, -1 = none yet
+    if (!std::strcmp(name, "forest_edges_last"))    { *value = c->forest_edges_last; return SELHIP_OK; }     // ... and the edges of its forest
     if (!std::strcmp(name, "small_pass_used"))  { *value = c->small_used ? 1 : 0; return SELHIP_OK; }
     if (!std::strcmp(name, "pairs_route_used")) { *value = c->pairs_route_used; return SELHIP_OK; }         // list passes: 1 signature, 0 direct, 2 no smh_a stage, -1 none yet
     if (!std::strcmp(name, "pairs_gpw"))        { *value = c->pairs_gpw_used; return SELHIP_OK; }           // ... its groups of four entries per wave and batch (0: one lane per entry)
@@ -791,7 +794,7 @@ int selhip_ctx_timing(selhip_ctx* c, int enable) {
     drain_timers(c);
     for (int t = 0; t < T_COUNT; ++t) { c->timers[t].total_ms = 0; c->timers[t].launches = 0; c->timers[t].span_ms = 0; }
     c->timing = enable == 2 ? 2 : (enable != 0 ? 1 : 0);
-    c->timed_passes = 0; c->timed_matrix_calls = 0; c->timed_matrix_smh_calls = 0; c->timed_cluster_calls = 0; c->timed_greedy_calls = 0; c->timed_merge_calls = 0;
+    c->timed_passes = 0; c->timed_matrix_calls = 0; c->timed_matrix_smh_calls = 0; c->timed_cluster_calls = 0; c->timed_greedy_calls = 0; c->timed_merge_calls = 0; c->timed_forest_calls = 0;
     return SELHIP_OK;
 }
 
@@ -800,7 +803,7 @@ double selhip_ctx_kernel_ms(const selhip_ctx* c, const char* name) {
     if (!c->pending) drain_timers(const_cast<selhip_ctx*>(c));
     for (int t = 0; t < T_COUNT; ++t)
         if (!std::strcmp(name, kTimerNames[t])) {
-            const long passes = t == T_MATRIX ? c->timed_matrix_calls : t == T_MATRIX_SMH ? c->timed_matrix_smh_calls : t == T_CLUSTER ? c->timed_cluster_calls : t == T_GREEDY ? c->timed_greedy_calls : t == T_MERGE ? c->timed_merge_calls : c->timed_passes;
+            const long passes = t == T_MATRIX ? c->timed_matrix_calls : t == T_MATRIX_SMH ? c->timed_matrix_smh_calls : t == T_CLUSTER ? c->timed_cluster_calls : t == T_GREEDY ? c->timed_greedy_calls : t == T_MERGE ? c->timed_merge_calls : t == T_FOREST ? c->timed_forest_calls : c->timed_passes;
             return (c->timers[t].launches && passes) ? c->timers[t].total_ms / (double)passes : -1.0;
         }
     const long passes = c->timed_passes;
@@ -814,7 +817,7 @@ double selhip_ctx_kernel_launches(const selhip_ctx* c, const char* name) {
     if (!c->pending) drain_timers(const_cast<selhip_ctx*>(c));
     for (int t = 0; t < T_COUNT; ++t)
         if (!std::strcmp(name, kTimerNames[t])) {
-            const long passes = t == T_MATRIX ? c->timed_matrix_calls : t == T_MATRIX_SMH ? c->timed_matrix_smh_calls : t == T_CLUSTER ? c->timed_cluster_calls : t == T_GREEDY ? c->timed_greedy_calls : t == T_MERGE ? c->timed_merge_calls : c->timed_passes;
+            const long passes = t == T_MATRIX ? c->timed_matrix_calls : t == T_MATRIX_SMH ? c->timed_matrix_smh_calls : t == T_CLUSTER ? c->timed_cluster_calls : t == T_GREEDY ? c->timed_greedy_calls : t == T_MERGE ? c->timed_merge_calls : t == T_FOREST ? c->timed_forest_calls : c->timed_passes;
             return passes ? (double)c->timers[t].launches / (double)passes : 0.0;
         }
     return -1.0;

@@ -141,6 +141,7 @@ static std::string g_priority_file = "";        // -W: the scores that order the
 static std::vector<uint32_t> g_priority;         // ... in rank order, read by load_priorities
 static std::string g_merge_dir = "";            // -P: one merged sketch set per group goes into this directory ("" = none)
 static std::string g_groups_file = "";          // -I: the groups of -P, read from this file ("" = the clusters of -L)
+static std::string g_forest_file = "";         // -H: the maximum spanning forest of the pass's result list goes here ("" = none)
 static unsigned g_merge_m = 0, g_merge_p_aux = 0;   // the SuperMinHash buckets and the auxiliary precision in play in the run (0 = none)
 
 // -P: the sketches of the context's set merged by d_group (device, rank order) into n_groups sets named names[], written into g_merge_dir
@@ -267,8 +268,33 @@ static int write_greedy(selhip_ctx* ctx, const selhost_dataset* ds, int64_t n) {
     return 0;
 }
 
-// -L: behind a finished pass of ctx over the n genomes of ds, the clusters of its result list as a table in file-list order
+// -H: behind a finished pass of ctx over the n genomes of ds, the maximum spanning forest of its result list (the single-linkage
+// dendrogram's merges), one line per edge, best first: path_a<TAB>path_b<TAB>value
+static int write_forest(selhip_ctx* ctx, const selhost_dataset* ds, int64_t n) {
+    if (g_forest_file.empty()) return 0;
+    const size_t cap = n > 1 ? (size_t)(n - 1) : 0;
+    std::vector<selhip_pair_t> edges(cap);
+    selhip_forest_t out{nullptr, nullptr};
+    void* d = nullptr;
+    int64_t n_edges = 0;
+    int r = cap ? selhip_malloc(&d, cap * sizeof(selhip_pair_t)) : 0;
+    if (!r) out.d_edges = static_cast<selhip_pair_t*>(d);
+    if (!r) r = selhip_ctx_spanning_forest(ctx, g_cluster_min, &out, &n_edges);
+    if (!r && n_edges) r = selhip_memcpy_d2h(edges.data(), out.d_edges, (size_t)n_edges * sizeof(selhip_pair_t));
+    if (d) selhip_free(d);
+    if (r) return r;
+    std::ofstream f(g_forest_file, std::ios::binary);
+    for (int64_t e = 0; e < n_edges; ++e)
+        f << selhost_dataset_name(ds, edges[(size_t)e].i) << '\t' << selhost_dataset_name(ds, edges[(size_t)e].k) << '\t'
+          << std::to_string(edges[(size_t)e].jaccard) << '\n';
+    f.close();
+    if (!f) { std::cerr << "selection: -H: cannot write '" << g_forest_file << "'\n"; return 5; }
+    return 0;
+}
+
+// -L (and -H, first): behind a finished pass of ctx over the n genomes of ds, the clusters of its result list as a table in file-list order
 static int write_clusters(selhip_ctx* ctx, const selhost_dataset* ds, int64_t n) {
+    if (const int r = write_forest(ctx, ds, n)) return r;
     if (g_cluster_file.empty()) return 0;
     if (g_cluster_greedy) return write_greedy(ctx, ds, n);
     std::vector<int32_t> cluster((size_t)n), degree((size_t)n), size((size_t)n), rep((size_t)n);
@@ -553,9 +579,9 @@ int main(int argc, char* argv[]) {
     std::string rounds_arg = "", cluster_min_arg = "", cluster_rep_arg = "";
     bool cluster_given = false, cluster_min_given = false, cluster_rep_given = false, linkage_given = false, priority_given = false;
     std::string linkage_arg = "";
-    bool merge_given = false, groups_given = false;
+    bool merge_given = false, groups_given = false, forest_given = false;
     int c;
-    while ((c = getopt(argc, argv, "xl:b:a:h:c:C:G:t:g:nA:F:B:o:r:q:k:K:p:M:UE:S:V:R:DL:T:Y:Z:W:P:I:")) != -1) {
+    while ((c = getopt(argc, argv, "xl:b:a:h:c:C:G:t:g:nA:F:B:o:r:q:k:K:p:M:UE:S:V:R:DL:T:Y:Z:W:P:I:H:")) != -1) {
         switch (c) {
             case 'x': std::cout << "Usage: -l -h -a -b [-c smh_a|hll_a|hll_an|none|smh_c -C c_min|-G gamma] [-t threads] [-g gpus] [-n] [-A auto|stream|sig] [-F 0|1] [-B block] [-o file] | -r file\n"
                                    "       -l db_list -q query_list -h -a [-c smh_a|hll_a|hll_an|none|smh_c -C c_min|-G gamma] [-n] [-A auto|stream|sig|index] [-F 0|1] [-k best_per_query]   (query-vs-database selection)\n"
@@ -570,6 +596,7 @@ int main(int argc, char* argv[]) {
                                    "       -l list -K best_per_genome -c smh_c -C c_min|-G gamma -a bytes -V smh -R rows|auto   (the same list in rounds of rows: memory for n K records and one round, not for every pair that shares a bucket)\n"
                                    "       -l list [-p pair_file | -K best_per_genome [-R rows]] ... -L clusters.tsv [-T min_value] [-Y max_degree|min_rank|max_rank]   (besides the output: the single-linkage clusters of the selected pairs, one line per genome: path, cluster, size, degree, representative)\n"
                                    "       ... -L clusters.tsv -Z single|greedy [-T min_value] [-Y max_degree|min_rank|max_rank | -W scores.tsv]   (-Z greedy: greedy representative clusters, CD-HIT style: genomes visited in the -Y order or by descending score, every other genome to its most similar representative; a sixth column: value to the representative)\n"
+                                   "       -l list [-p pair_file | -K best_per_genome [-R rows]] ... -H forest.tsv [-T min_value]   (besides the output: the maximum spanning forest of the selected pairs = the merges of the single-linkage dendrogram, one line per edge, best first: path_a, path_b, value; may stand beside -L)\n"
                                    "       ... -c hll_a|hll_an -a bytes -D   (with -l, -q, -p, -k, -K, -g, -B: no .hll_<p> file is read, the auxiliary HLL sketches are folded from the .hll registers)\n"
                                    "       ... -L clusters.tsv [-Z ...] -P dir   (besides the output: one merged sketch set per cluster in dir -- cluster_<id>.hll, .smh<m>, .hll_<p> -- and dir/filelist.txt, a database for -l)\n"
                                    "       -l list [-c ... -a bytes] -I groups.tsv -P dir   (no selection: the genomes merged by the groups of 'path<TAB>group_name' lines, one sketch set per group_name in dir)\n"; return 0;
@@ -588,6 +615,7 @@ int main(int argc, char* argv[]) {
             case 'Z': linkage_arg = optarg; linkage_given = true; break;
             case 'W': g_priority_file = optarg; priority_given = true; break;
             case 'P': g_merge_dir = optarg; merge_given = true; break;
+            case 'H': g_forest_file = optarg; forest_given = true; break;
             case 'I': g_groups_file = optarg; groups_given = true; break;
             case 'k': top_k = std::strtoll(optarg, nullptr, 10); topk_given = true; break;
             case 'K': nbr_k = std::strtoll(optarg, nullptr, 10); nbr_given = true; break;
@@ -609,9 +637,27 @@ int main(int argc, char* argv[]) {
             default: break;
         }
     }
+    // -H and its -T: checked before any file is read or device opened
+    if (forest_given) {
+        const char* clash = !query_file.empty() ? "-q" : matrix_given ? "-M" : gpus_given ? "-g" : ooc_block != 0 ? "-B" : !dump_file.empty() ? "-r" : nullptr;
+        if (clash) {
+            std::cerr << "selection: -H (the spanning forest of the selected pairs) cannot be combined with " << clash
+                      << "; it takes the result list one all-pairs or pair-list pass leaves on one device\n";
+            return 2;
+        }
+        if (g_forest_file.empty()) { std::cerr << "selection: -H needs the name of the file to write\n"; return 2; }
+        if (cluster_min_given && !cluster_given) {                       // (beside -L the one -T serves both and is read there)
+            char* end = nullptr;
+            g_cluster_min = std::strtod(cluster_min_arg.c_str(), &end);
+            if (cluster_min_arg.empty() || *end || std::isnan(g_cluster_min)) {
+                std::cerr << "selection: -T (with -H: the smallest value of an edge) must be a number, not '" << cluster_min_arg << "'\n";
+                return 2;
+            }
+        }
+    }
     // -L and its -T, -Y: checked before any file is read or device opened
-    if ((cluster_min_given || cluster_rep_given) && !cluster_given) {
-        std::cerr << "selection: " << (cluster_min_given ? "-T (the smallest value of an edge)" : "-Y (the representative of a cluster)")
+    if (((cluster_min_given && !forest_given) || cluster_rep_given) && !cluster_given) {
+        std::cerr << "selection: " << (cluster_min_given && !forest_given ? "-T (the smallest value of an edge)" : "-Y (the representative of a cluster)")
                   << " is an option of -L (the clusters of the selected pairs)\n";
         return 2;
     }

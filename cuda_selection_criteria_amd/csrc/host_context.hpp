@@ -147,8 +147,8 @@ static_assert(kCounterBlocks == kMaxChunks + 1, "common.cuh: counter blocks per 
 constexpr int kMaxAuxP = SELHIP_MAX_AUX_P;   // auxiliary HLL precision accepted by every entry point: aux_fused_kernel counts in 16-bit bins (a bin holds up to 2^p_aux)
 constexpr long long kEnumPairs = 1ll << 26;    // hll_a / hll_an as first criterion: pairs listed per sub-pass (512 MiB of int2)
 
-enum { T_PREP = 0, T_STAGE1, T_HIST, T_SELECT, T_TOTAL, T_SIGBUILD, T_JOIN, T_VERIFY, T_AUX, T_GROUP, T_DENSE, T_TOPK, T_MATRIX, T_MATRIX_SMH, T_CLUSTER, T_GREEDY, T_MERGE, T_COUNT };
-const char* kTimerNames[T_COUNT] = {"prep", "stage1", "hist", "select", "total", "sigbuild", "join", "verify", "aux", "group", "dense", "topk", "matrix", "matrix_smh", "cluster", "greedy", "merge"};
+enum { T_PREP = 0, T_STAGE1, T_HIST, T_SELECT, T_TOTAL, T_SIGBUILD, T_JOIN, T_VERIFY, T_AUX, T_GROUP, T_DENSE, T_TOPK, T_MATRIX, T_MATRIX_SMH, T_CLUSTER, T_GREEDY, T_MERGE, T_FOREST, T_COUNT };
+const char* kTimerNames[T_COUNT] = {"prep", "stage1", "hist", "select", "total", "sigbuild", "join", "verify", "aux", "group", "dense", "topk", "matrix", "matrix_smh", "cluster", "greedy", "merge", "forest"};
 
 }  // namespace
 
@@ -369,6 +369,12 @@ struct selhip_ctx {
     int greedy_clusters_last = -1;      // the C of the last call ("greedy_clusters_last"), -1 = none yet
     int greedy_rounds_last = -1;        // its rounds ("greedy_rounds_last")
 
+    // maximum spanning forest (selhip_ctx_spanning_forest; kernel_forest.cuh, host_forest.hpp): the emitted records before their sort;
+    // everything else is scratch of the two calls above (cl_parent, cl_label, cl_key, gr_best, gr_count, cl_bad, cl_tmp)
+    DevBuf<ForestEdge> fo_edges;
+    int forest_rounds_last = -1;        // the rounds of the last call, the empty one included ("forest_rounds_last"), -1 = none yet
+    int forest_edges_last = -1;         // its F ("forest_edges_last")
+
     // sketches merged by group (selhip_ctx_merge_groups; kernel_merge.cuh, host_merge.hpp): scratch the call owns
     MergeScratch mg;
     DevBuf<uint8_t> mg_hll;             // the merged main registers where the caller takes the cardinalities without them
@@ -381,6 +387,7 @@ struct selhip_ctx {
     long timed_matrix_smh_calls = 0;    // ... and those of the SuperMinHash measures: the divisor of "matrix_smh"
     long timed_cluster_calls = 0;       // cluster calls under timing: the divisor of "cluster"
     long timed_greedy_calls = 0;        // greedy calls under timing: the divisor of "greedy"
+    long timed_forest_calls = 0;        // forest calls under timing: the divisor of "forest"
     long timed_merge_calls = 0;         // merge calls under timing: the divisor of "merge"
     int last_attempts = 0;              // enqueues the last finished run needed (1 = nothing overflowed)
     KernelTimer timers[T_COUNT];

@@ -50,6 +50,8 @@
 //                       one lane per record), flattened labels, dense ids, degrees, sizes and one representative per cluster
 //   kernel_greedy.cuh   greedy representative clusters of a record list (CD-HIT / UCLUST): the first maximal independent set under a key
 //                       order in rounds of one edge and one vertex launch, then every member to its most similar representative
+//   kernel_forest.cuh   maximum spanning forest of a record list, its single-linkage dendrogram: Boruvka rounds of two record launches (best
+//                       value, then smallest pair among the equal), a hook and a flatten launch over the union-find of kernel_cluster.cuh
 //   kernel_merge.cuh    sketches merged by group: a counting sort of the members, then a segmented reduction of the rows (u8 maximum of the
 //                       HLL registers, u64 minimum of the SuperMinHash buckets) in segments of at most SELHIP_MERGE_SEGMENT members per level
 //
@@ -57,6 +59,7 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_scan.hpp>         // exclusive scan of the per-row survivor counts (grouping for stage 2)
 #include <rocprim/iterator/transform_iterator.hpp> // the top-k scan reads the per-query counts packed on the fly
+#include <rocprim/device/device_merge_sort.hpp>   // the spanning forest's edges into their order: a comparison sort of 16-byte records
 #include <rocprim/device/device_radix_sort.hpp>   // ALGO_HASHJOIN and the query index: the key sort is a library call, everything else is hand-written
 
 #include <algorithm>
@@ -100,6 +103,7 @@
 #include "kernel_fold.cuh"
 #include "kernel_cluster.cuh"
 #include "kernel_greedy.cuh"
+#include "kernel_forest.cuh"
 #include "kernel_merge.cuh"
 
 #include "host_plan.hpp"         // host decisions that are plain arithmetic: build shape, pass plan, criterion constants, overflow rule
@@ -112,6 +116,7 @@
 #include "host_topk.hpp"         // top-k of a query pass and of an all-pairs pass: scratch, launches, the count the result accessors expose
 #include "host_cluster.hpp"      // single-linkage clusters: scratch and launches behind selhip_ctx_cluster / selhip_components
 #include "host_greedy.hpp"       // greedy representative clusters: rounds, scratch and launches behind selhip_ctx_cluster_greedy / selhip_greedy_representatives
+#include "host_forest.hpp"       // maximum spanning forest: rounds, sort and launches behind selhip_ctx_spanning_forest / selhip_spanning_forest
 #include "host_merge.hpp"       // sketches merged by group: checks, levels and launches behind selhip_merge_sketches / selhip_ctx_merge_groups
 #include "host_build.hpp"       // split sketch builder: items, launches, the reduction through merge_run, the fallback launch
 #include "abi_context.inc"       // C ABI: context (create, upload / attach, run, results, timing)
@@ -120,6 +125,7 @@
 #include "abi_matrix.inc"        // C ABI: dense matrices (matrix, query_matrix)
 #include "abi_cluster.inc"       // C ABI: clusters of the result list (cluster) and of a caller's edge list (components)
 #include "abi_greedy.inc"        // C ABI: greedy representative clusters of the result list (cluster_greedy) and of a caller's edge list (greedy_representatives)
+#include "abi_forest.inc"        // C ABI: maximum spanning forest of the result list (ctx_spanning_forest) and of a caller's edge list (spanning_forest)
 #include "abi_merge.inc"        // C ABI: sketches merged by group (merge_sketches, ctx_merge_groups)
 #include "abi_build.inc"        // C ABI: sketch construction with long genomes split across workgroups (build_sketches_split, build_split_plan)
 #include "abi_blocks.inc"        // C ABI: building blocks, synthetic sketches, sketch construction, memory helpers

@@ -13,7 +13,7 @@ import numpy as np
 from . import _lib
 from ._lib import (ALGO_AUTO, BANDING_CPU, CRIT_HLL_A, CRIT_HLL_AN, CRIT_HLL_A_SMH_A, CRIT_NONE, CRIT_SMH_A, CRIT_SMH_C, ESTIMATOR_HLL, ESTIMATOR_SMH, F32, F64, FP_FMA,
                    MEASURE_CONTAINMENT, MEASURE_INTERSECTION, MEASURE_JACCARD, MEASURE_MAX_CONTAINMENT, MEASURE_SMH_JACCARD,
-                   MEASURE_SMH_MATCHES, MEASURE_UNION, MODE_CB_SMH, REP_MAX_DEGREE, REP_MAX_RANK, REP_MIN_RANK, REP_PRIORITY, TOPK_ROUNDS_AUTO, Clusters, Greedy, Merged, Pair, check, hip_lib,
+                   MEASURE_SMH_MATCHES, MEASURE_UNION, MODE_CB_SMH, REP_MAX_DEGREE, REP_MAX_RANK, REP_MIN_RANK, REP_PRIORITY, TOPK_ROUNDS_AUTO, Clusters, Forest, Greedy, Merged, Pair, check, hip_lib,
                    host_lib)
 
 # layout of selhip_pair_t {int32 i, k; double jaccard}
@@ -587,6 +587,31 @@ class Selector:
         res["rounds"] = self.get_param("greedy_rounds_last")
         return res
 
+    def spanning_forest(self, min_value: Optional[float] = None, to_host: bool = True) -> dict:
+        """the maximum spanning forest of the result list the context holds, computed on the device (selhip_ctx_spanning_forest): the
+        single-linkage dendrogram of the graph on the n ranks whose edges are the records with value >= min_value (None: every
+        record).  Its F = n - C edges, best first (greater value first, equal values by ascending (a, b)), are the merges of the
+        hierarchy: the clusters at any threshold t are the components of the edges with value >= t (forest_cut), their number n minus
+        the number of such edges (forest_cluster_counts), and forest_linkage gives SciPy's linkage matrix.  Behind the passes of
+        Selector.cluster.  Returns a dict: "edges" [F] PAIR_DTYPE records {i = a < k = b, jaccard = value}, "labels" [n] int32 (smallest
+        rank of the component: Selector.cluster's labels at the same min_value) -- numpy arrays; with to_host=False torch tensors on the
+        device, the edges as uint8 [F, 16] (the records' bytes) --, "n_edges" = F, "n_clusters" = n - F and "rounds" (launch rounds, the
+        empty last one included)"""
+        import torch
+        mv = float("-inf") if min_value is None else float(min_value)
+        dev = torch.device("cuda", self.device)
+        edges = torch.empty((max(self.n - 1, 0), PAIR_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        labels = torch.empty(self.n, dtype=torch.int32, device=dev)
+        out = Forest(edges.data_ptr() if edges.numel() else None, labels.data_ptr() if self.n else None)
+        cnt = C.c_int64()
+        check(self._lib.selhip_ctx_spanning_forest(self._ctx, mv, C.byref(out), C.byref(cnt)), self._ctx)
+        f = int(cnt.value)
+        res = {"edges": edges[:f], "labels": labels}
+        if to_host:
+            res = {"edges": np.ascontiguousarray(edges[:f].cpu().numpy()).view(PAIR_DTYPE).reshape(-1), "labels": labels.cpu().numpy()}
+        res.update(n_edges=f, n_clusters=self.n - f, rounds=self.get_param("forest_rounds_last"))
+        return res
+
     # -- sketches merged by group ---------------------------------------------------------------------
     def merge(self, groups, n_groups: Optional[int] = None, to_host: bool = False) -> dict:
         """one union sketch per group of the context's set, merged on the device (selhip_ctx_merge_groups): the element-wise maximum of
@@ -944,6 +969,95 @@ def components(pairs, n: int, device: int = 0, to_host: bool = True):
     return labels.cpu().numpy() if to_host else labels
 
 
+def spanning_forest(pairs, n: int, values=None, device: int = 0, to_host: bool = True) -> dict:
+    """the maximum spanning forest of the undirected graph on the vertices 0 .. n - 1 with one edge per row of `pairs` (a numpy int32
+    (P, 2) array or a torch int32 device tensor of that shape) and values[e] as its value (P float64 numbers, numpy or a torch device
+    tensor; None: every value 1.0, the order is then the pair order), computed on the device (selhip_spanning_forest).  A NaN value is
+    no edge; self-loops and repeated rows are legal (a repeated pair counts once, with its greatest value); a vertex outside [0, n)
+    raises (SELHIP_E_BADARG).  The dict of Selector.spanning_forest"""
+    import torch
+    lib = hip_lib()
+    dev = torch.device("cuda", device)
+    pairs = _device_pairs(pairs, dev)
+    vals = None
+    if values is not None:
+        vals = values if hasattr(values, "data_ptr") else torch.from_numpy(np.ascontiguousarray(values, dtype=np.float64)).to(dev)
+        assert vals.is_cuda and vals.is_contiguous() and vals.dtype == torch.float64 and vals.shape == (pairs.shape[0],), "values: P float64 numbers"
+    n = int(n)
+    f, rounds = C.c_int64(-1), C.c_int64(-1)
+    with torch.cuda.device(dev):
+        edges = torch.empty((max(n - 1, 0), PAIR_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        labels = torch.empty(max(n, 0), dtype=torch.int32, device=dev)
+        check(lib.selhip_spanning_forest(pairs.data_ptr() if pairs.numel() else None, vals.data_ptr() if vals is not None and vals.numel() else None,
+                                         int(pairs.shape[0]), n, edges.data_ptr() if edges.numel() else None, labels.data_ptr() if n > 0 else None,
+                                         C.byref(f), C.byref(rounds), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    res = {"edges": edges[:f.value], "labels": labels}
+    if to_host:
+        res = {"edges": np.ascontiguousarray(edges[:f.value].cpu().numpy()).view(PAIR_DTYPE).reshape(-1), "labels": labels.cpu().numpy()}
+    res.update(n_edges=int(f.value), n_clusters=n - int(f.value), rounds=int(rounds.value))
+    return res
+
+
+def forest_cluster_counts(edges, n: int, thresholds) -> np.ndarray:
+    """the number of single-linkage clusters at every threshold t of `thresholds`, from the forest's edges alone (a PAIR_DTYPE array,
+    Selector.spanning_forest's "edges"): n - #{edges with value >= t}, int64"""
+    v = np.asarray(edges["jaccard"], dtype=np.float64)
+    return np.array([int(n) - int(np.count_nonzero(v >= float(t))) for t in np.atleast_1d(np.asarray(thresholds, dtype=np.float64))], dtype=np.int64)
+
+
+def forest_cut(edges, n: int, t: float, device: int = 0) -> np.ndarray:
+    """labels [n] int32 of the single-linkage clusters at threshold t from the forest's edges (a PAIR_DTYPE array in the forest's order):
+    the components (on the device, `components`) of the prefix of edges with value >= t -- Selector.cluster(min_value=t)'s labels"""
+    keep = np.asarray(edges["jaccard"], dtype=np.float64) >= float(t)
+    pairs = np.stack([np.asarray(edges["i"])[keep], np.asarray(edges["k"])[keep]], axis=1).astype(np.int32).reshape(-1, 2)
+    return components(pairs, n, device)
+
+
+def forest_linkage(edges, n: int, distance=lambda v: 1.0 - v, fill: Optional[float] = None) -> np.ndarray:
+    """the linkage matrix Z of scipy.cluster.hierarchy (float64 [n - 1, 4]) from the forest's edges in their order (a PAIR_DTYPE array):
+    row s merges the clusters of the edge's two ends into the new cluster n + s -- columns: the smaller id, the larger id,
+    distance(value), the size of the new cluster; an original observation g has the id g.  A forest of C > 1 components has only
+    n - C merges: ValueError with fill None; otherwise the remaining components are joined in ascending label order (smallest rank),
+    each to the cluster that holds the smallest one, at distance `fill`"""
+    n = int(n)
+    parent, cid, size = list(range(n)), list(range(n)), [1] * n
+
+    def find(x):
+        while parent[x] != x:
+            parent[x] = parent[parent[x]]
+            x = parent[x]
+        return x
+
+    z = []
+
+    def join(a, b, d):
+        ra, rb = find(a), find(b)
+        if ra == rb:
+            raise ValueError("forest_linkage: the edges close a cycle (not a forest)")
+        ia, ib = cid[ra], cid[rb]
+        lo, hi = min(ra, rb), max(ra, rb)
+        parent[hi] = lo
+        size[lo] += size[hi]
+        cid[lo] = n + len(z)
+        z.append([float(min(ia, ib)), float(max(ia, ib)), float(d), float(size[lo])])
+
+    for e in edges:
+        join(int(e["i"]), int(e["k"]), distance(float(e["jaccard"])))
+    roots = sorted({find(g) for g in range(n)})            # (the root is the smallest rank: the label)
+    if len(roots) > 1:
+        if fill is None:
+            raise ValueError(f"forest_linkage: the forest has {len(roots)} components; give fill, the distance at which they are joined")
+        for r in roots[1:]:
+            join(roots[0], r, fill)
+    return np.array(z, dtype=np.float64).reshape(-1, 4)
+
+
+def forest_table(names: Sequence[str], edges) -> str:
+    """the text of `selection -H`: one line per forest edge in the forest's order, 'path_a<TAB>path_b<TAB>value', the value printed as
+    format_lines prints J.  names in rank order, edges = Selector.spanning_forest(...)["edges"] on the host"""
+    return "".join(f"{names[int(e['i'])]}\t{names[int(e['k'])]}\t{float(e['jaccard']):f}\n" for e in edges)
+
+
 def cluster_table(names: Sequence[str], order: np.ndarray, res: dict) -> str:
     """the text of `selection -L`: one line per genome in FILE-LIST order, 'path<TAB>cluster<TAB>cluster_size<TAB>degree<TAB>
     representative_path'.  names in rank order, order[rank] = the genome's line in the list, res = Selector.cluster(...) on the host"""
@@ -1145,6 +1259,19 @@ def greedy_from_filelist(list_file: str, tau: float, aux_bytes: int, mode: int =
         return greedy_table(ds.names, ds.order, sel.cluster_greedy(cluster_min, code, prio))
     return _filelist_pass(then, list_file, tau, aux_bytes, mode, device, fp_mode, algo, criterion, top_k, min_matches, measure, min_containment,
                           estimator, top_k_rounds, fold_aux)
+
+
+def forest_from_filelist(list_file: str, tau: float, aux_bytes: int, mode: int = MODE_CB_SMH, device: int = 0,
+                         fp_mode: int = FP_FMA, algo: int = ALGO_AUTO, criterion: str = "smh_a", top_k: int = 0,
+                         min_matches: Optional[int] = None, measure="jaccard", min_containment: Optional[float] = None, estimator="hll",
+                         top_k_rounds=0, fold_aux: bool = False, cluster_min: Optional[float] = None) -> str:
+    """The pass of select_from_filelist (same arguments), its maximum spanning forest instead of its pairs: the text `selection ...
+    -H file [-T cluster_min]` writes -- one line per forest edge, best first, 'path_a<TAB>path_b<TAB>value' (Selector.spanning_forest
+    over the selected pairs with value >= cluster_min, None = all of them)"""
+    if cluster_min is not None and np.isnan(cluster_min):
+        raise ValueError("cluster_min: a number (None takes every selected pair), not NaN")
+    return _filelist_pass(lambda ds, sel, pairs: forest_table(ds.names, sel.spanning_forest(cluster_min)["edges"]), list_file, tau, aux_bytes, mode,
+                          device, fp_mode, algo, criterion, top_k, min_matches, measure, min_containment, estimator, top_k_rounds, fold_aux)
 
 
 def topk_rounds_code(rows) -> int:

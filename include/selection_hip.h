@@ -152,7 +152,7 @@ const char* selhip_last_error(const selhip_ctx* ctx);
  * blocked null stream).  What DOES wait for the whole device is a call that frees device memory (hipFree): a pass that outgrows one
  * of its lists and repeats; the first SELHIP_ALGO_INDEX pass behind an upload / attach of the database, whose sort scratch goes away
  * when the index stands; any buffer that grows; and, in section 3, selhip_hll_bitslice, selhip_hll_union_hist_planes,
- * selhip_components and selhip_greedy_representatives, whose scratch lives for the call. */
+ * selhip_components, selhip_greedy_representatives and selhip_spanning_forest, whose scratch lives for the call. */
 int selhip_ctx_set_stream(selhip_ctx* ctx, void* hip_stream);
 /* Chunk lanes of a pass (smh_a / hll_a+smh_a): the query rows are cut into `chunks` equal-pair chunks and every chunk runs its
  * whole chain (join, verify, [auxiliary criterion], grouping, HLL union histograms, estimate) on one of two internal streams
@@ -248,7 +248,9 @@ int selhip_ctx_set_param(selhip_ctx* ctx, const char* name, int value);
  * of m = 128, 256, 512 or 1024 buckets, 0 = the generic kernel of every other m; -1 = none yet),
  * "clusters_last" (the number of clusters the last selhip_ctx_cluster call found, section 2g; -1 = none yet),
  * "greedy_clusters_last" and "greedy_rounds_last" (the clusters the last selhip_ctx_cluster_greedy call found and the rounds its
- * selection took, section 2h; -1 = none yet) */
+ * selection took, section 2h; -1 = none yet),
+ * "forest_rounds_last" and "forest_edges_last" (the rounds the last selhip_ctx_spanning_forest call took and the edges F of its
+ * forest, section 2j; -1 = none yet) */
 int selhip_ctx_get_param(const selhip_ctx* ctx, const char* name, int* value);
 /* Stage 2 grouping (default on): the pairs that reach the HLL-14 stage are bucketed by query row (counting sort) so
  * that waves running side by side on one XCD share their query row in L2.  0 = off (same kernel, list as produced). */
@@ -505,6 +507,7 @@ int selhip_ctx_set_topk_rounds(selhip_ctx* ctx, int64_t rows);
  * "cluster" is the launches of selhip_ctx_cluster (section 2g), averaged over the CLUSTER CALLS since the last reset, counted apart likewise.
  * "greedy" is the launches of selhip_ctx_cluster_greedy (section 2h), averaged over the GREEDY CALLS since the last reset, counted apart likewise.
  * "merge" is the launches of selhip_ctx_merge_groups (section 2i), averaged over the MERGE CALLS since the last reset, counted apart likewise.
+ * "forest" is the launches of selhip_ctx_spanning_forest (section 2j), averaged over the FOREST CALLS since the last reset, counted apart likewise.
  * selhip_ctx_kernel_launches: launches of that kernel per pass. */
 double selhip_ctx_kernel_ms(const selhip_ctx* ctx, const char* name);
 double selhip_ctx_kernel_launches(const selhip_ctx* ctx, const char* name);
@@ -871,6 +874,48 @@ typedef struct {
 } selhip_merged_t;           /* caller's device memory; any pointer may be NULL (not written)        */
 int selhip_ctx_merge_groups(selhip_ctx* ctx, const int32_t* d_group, int64_t n_groups, const selhip_merged_t* out);
 
+/* ---------------------------------------------------------------------------------------------------
+ * 2j. Single-linkage hierarchy of the result list: the maximum spanning forest of the record graph.  2g answers one cut per call;
+ *     the forest answers every cut at once.  Its F = n - C edges, best first, are the merge sequence of the single-linkage
+ *     dendrogram; the clusters at any threshold t are the components of the forest edges with value >= t, and their number is n minus
+ *     the number of such edges.  n - 1 records at the most, whatever the length of the list.
+ *     THE GRAPH: the vertices are the n ranks of the context's set.  A record {i, k, value} of the result list is an edge if
+ *     value >= min_value in f64 and i != k.  -INFINITY takes every record, NaN min_value is SELHIP_E_BADARG, a NaN value is never an
+ *     edge.  The edge is the unordered pair {a, b}, a = min(i, k), b = max(i, k).  Repeated records of one pair, and the two directed
+ *     records of a top-k list, are ONE edge; its value is the greatest of theirs, compared through the order-preserving integer image
+ *     of section 2h's values, so -0.0 and +0.0 are one value, written +0.0.
+ *     THE ORDER: edge e goes BEFORE edge f iff image(e.value) > image(f.value), or the images are equal and (e.a, e.b) is
+ *     lexicographically smaller.  Distinct edges have distinct pairs: a strict total order.
+ *     THE FOREST: visit the edges in that order and keep an edge iff its ends are not yet connected by kept edges (Kruskal).  Under a
+ *     strict total order the result is unique.  It has F = n - C edges, C = selhip_ctx_cluster's C at the same min_value.
+ *     OUTPUTS, each a pure function of the record list and min_value, bit for bit, whatever order the device worked in:
+ *       d_edges[0 .. F)   selhip_pair_t {i = a, k = b, jaccard = value} in BEFORE order, best first: the caller's device memory of
+ *                         max(n - 1, 0) records, 16-byte aligned (SELHIP_E_BADARG otherwise); entries from F on are not written
+ *       d_label[g]        the smallest rank of g's component: selhip_ctx_cluster's d_label at the same min_value
+ *       *n_edges_out      F (may be NULL)
+ *     Either pointer may be NULL (not written); the struct may not.  n == 0 writes nothing.
+ *     Accepted lists and SELHIP_E_STATE cases: those of 2g (not after a query pass, not before any finished pass, not while a pass is
+ *     pending).  The call reads the list and writes only `out` and scratch the context owns: the list, selhip_ctx_result_count, the
+ *     statistics, selhip_ctx_last_attempts, the top-k settings, the signature cache, "clusters_last" and "greedy_*_last" are as they
+ *     were, and a context that never calls it launches what it always launched.  It runs on the context's stream and returns when the
+ *     outputs are complete.
+ *     HOW (csrc/kernel_forest.cuh): Boruvka rounds over the union-find of 2g.  A round is two launches over the records -- every
+ *     component's best outgoing value by a 64-bit atomic maximum, then the smallest pair among the records of that value by an atomic
+ *     minimum -- one over the vertices that emits each picked edge once and unites the two components, and one that flattens the
+ *     components and counts the picks; a round that picks nothing ends the call: at most ceil(log2 n) + 1 rounds.  The emitted
+ *     records are then sorted into BEFORE order (rocPRIM).  No kernel waits for another lane.  A list without records is one launch
+ *     (F = 0, the identity labels).  get_param "forest_rounds_last": the rounds, the empty one included (a list without records: 1;
+ *     n == 0: 0); "forest_edges_last": F; both -1 = none yet.  Timed as "forest" in selhip_ctx_kernel_ms: per forest call, counted
+ *     apart from the passes as "cluster" is.
+ *     Not built: Newick output, average or complete linkage, query passes, the host-side lists of selhip_multi_select and
+ *     selhip_ooc_select (selhip_spanning_forest takes any edge list), dropping the records inside one component between the rounds.
+ * --------------------------------------------------------------------------------------------------- */
+typedef struct {
+    selhip_pair_t* d_edges;  /* [max(n-1,0)]  first F written: {a < b, value}, best first           */
+    int32_t*       d_label;  /* [n]  smallest rank of the genome's component                        */
+} selhip_forest_t;           /* caller's device memory; either pointer may be NULL (not written)    */
+int selhip_ctx_spanning_forest(selhip_ctx* ctx, double min_value, const selhip_forest_t* out, int64_t* n_edges_out);
+
 
 /* ---------------------------------------------------------------------------------------------------
  * 3. Building blocks (device pointers), used by the launchers above and exposed for tests.
@@ -918,6 +963,16 @@ int selhip_components(const selhip_int2_t* d_pairs, int64_t n_pairs, int64_t n, 
  * written -- and the messages are those of selhip_components.  Waits for the stream. */
 int selhip_greedy_representatives(const selhip_int2_t* d_pairs, int64_t n_pairs, int64_t n, const uint64_t* d_key /* [n] or NULL */,
                                   uint8_t* d_is_rep /* [n] */, int64_t* rounds_out /* may be NULL */, void* hip_stream);
+/* The maximum spanning forest (section 2j; csrc/kernel_forest.cuh) of an edge list: the undirected graph on the vertices 0 .. n - 1 with
+ * one entry {x, y} of d_pairs (device memory, 8-byte aligned) per record and d_values[e] (device memory, f64) as its value; NULL
+ * d_values = every value 1.0, and the order is then the pair order.  An entry with a NaN value is no edge; entries with x == y and
+ * repeated entries are legal (a repeated pair is one edge with the greatest of its values).  d_edges (max(n - 1, 0) records, 16-byte
+ * aligned), d_label ([n]), *n_edges_out (F) and *rounds_out (the rounds, the empty one included; n_pairs == 0: 1; n == 0: 0) are
+ * section 2j's; each may be NULL.  Ranges, the SELHIP_E_BADARG of an entry with a vertex outside [0, n) -- whatever its value, and
+ * nothing is written -- and its message are those of selhip_components.  The call owns its scratch and waits for the stream. */
+int selhip_spanning_forest(const selhip_int2_t* d_pairs, const double* d_values, int64_t n_pairs, int64_t n,
+                           selhip_pair_t* d_edges /* [max(n-1,0)] */, int32_t* d_label /* [n] */, int64_t* n_edges_out, int64_t* rounds_out,
+                           void* hip_stream);
 /* Sketches merged by group (section 2i; csrc/kernel_merge.cuh) over a caller's rows: d_hll[n][1 << p] u8, d_smh[n][m] u64 and
  * d_aux_hll[n][1 << p_aux] u8 reduced to n_groups rows each -- maximum, unsigned minimum, maximum -- by d_group[n] (int32, -1 .. n_groups - 1,
  * -1 = in no group; ids in any order); d_size_out[n_groups] (int32, may be NULL) receives the members per group.  A sketch kind is
