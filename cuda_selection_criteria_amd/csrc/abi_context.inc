@@ -56,9 +56,7 @@ void selhip_ctx_destroy(selhip_ctx* c) {
     c->hll_sparse.release(); c->hll_sparse_dev_t.release();
     release_queries(c);
     release_topk(c);
-    release_cluster(c);
-    release_greedy(c);
-    release_forest(c);
+    c->gs.release();
     release_merge(c);
     if (c->h_pc) (void)hipHostFree(c->h_pc);
     if (c->st_stage1) {
@@ -794,16 +792,18 @@ int selhip_ctx_timing(selhip_ctx* c, int enable) {
     drain_timers(c);
     for (int t = 0; t < T_COUNT; ++t) { c->timers[t].total_ms = 0; c->timers[t].launches = 0; c->timers[t].span_ms = 0; }
     c->timing = enable == 2 ? 2 : (enable != 0 ? 1 : 0);
-    c->timed_passes = 0; c->timed_matrix_calls = 0; c->timed_matrix_smh_calls = 0; c->timed_cluster_calls = 0; c->timed_greedy_calls = 0; c->timed_merge_calls = 0; c->timed_forest_calls = 0;
+    c->timed_passes = 0;
+    for (long& calls : c->timed_calls) calls = 0;
     return SELHIP_OK;
 }
 
+static long timed_divisor(const selhip_ctx* c, int t) { return t >= T_MATRIX ? c->timed_calls[t] : c->timed_passes; }   // a call timer's (TimedCall) calls, every other's passes
 double selhip_ctx_kernel_ms(const selhip_ctx* c, const char* name) {
     if (!c || !name) return -1.0;
     if (!c->pending) drain_timers(const_cast<selhip_ctx*>(c));
     for (int t = 0; t < T_COUNT; ++t)
         if (!std::strcmp(name, kTimerNames[t])) {
-            const long passes = t == T_MATRIX ? c->timed_matrix_calls : t == T_MATRIX_SMH ? c->timed_matrix_smh_calls : t == T_CLUSTER ? c->timed_cluster_calls : t == T_GREEDY ? c->timed_greedy_calls : t == T_MERGE ? c->timed_merge_calls : t == T_FOREST ? c->timed_forest_calls : c->timed_passes;
+            const long passes = timed_divisor(c, t);
             return (c->timers[t].launches && passes) ? c->timers[t].total_ms / (double)passes : -1.0;
         }
     const long passes = c->timed_passes;
@@ -817,7 +817,7 @@ double selhip_ctx_kernel_launches(const selhip_ctx* c, const char* name) {
     if (!c->pending) drain_timers(const_cast<selhip_ctx*>(c));
     for (int t = 0; t < T_COUNT; ++t)
         if (!std::strcmp(name, kTimerNames[t])) {
-            const long passes = t == T_MATRIX ? c->timed_matrix_calls : t == T_MATRIX_SMH ? c->timed_matrix_smh_calls : t == T_CLUSTER ? c->timed_cluster_calls : t == T_GREEDY ? c->timed_greedy_calls : t == T_MERGE ? c->timed_merge_calls : t == T_FOREST ? c->timed_forest_calls : c->timed_passes;
+            const long passes = timed_divisor(c, t);
             return passes ? (double)c->timers[t].launches / (double)passes : 0.0;
         }
     return -1.0;

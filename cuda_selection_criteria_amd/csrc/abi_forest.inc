@@ -1,6 +1,6 @@
 // abi_forest.inc -- the C ABI of the maximum spanning forest (include/selection_hip.h sections 2j and 3): selhip_ctx_spanning_forest
 // over the result list a context holds, selhip_spanning_forest over a caller's list of edges.  Kernels in kernel_forest.cuh, host side
-// in host_forest.hpp; touches none of the passes' state (result list, counters, statistics, top-k, signature cache) and nothing
+// in host_forest.hpp and host_graph.hpp; touches none of the passes' state (result list, counters, statistics, top-k, signature cache) and nothing
 // selhip_ctx_cluster or selhip_ctx_cluster_greedy report.
 // Included by selection_kernels.hip.
 
@@ -17,9 +17,9 @@ int selhip_spanning_forest(const selhip_int2_t* d_pairs, const double* d_values,
         return SELHIP_E_BADARG;
     }
     if (n == 0) {
-        if (n_pairs == 0) { if (n_edges_out) *n_edges_out = 0; if (rounds_out) *rounds_out = 0; return SELHIP_OK; }
-        set_err(nullptr, "the pair list holds %lld invalid entries (a vertex outside [0, 0)); entry 0 is one", (long long)n_pairs);
-        return SELHIP_E_BADARG;
+        if (n_pairs == 0 && n_edges_out) *n_edges_out = 0;
+        if (n_pairs == 0 && rounds_out) *rounds_out = 0;
+        return graph_no_vertices(n_pairs);
     }
     const hipStream_t st = (hipStream_t)hip_stream;
     if (n_pairs == 0) {
@@ -30,45 +30,33 @@ int selhip_spanning_forest(const selhip_int2_t* d_pairs, const double* d_values,
         if (rounds_out) *rounds_out = 1;
         return SELHIP_OK;
     }
-    // scratch of the call: the emitted records (16 bytes each), best_img[n], best_pair[n] (u64), the tally of invalid entries, then
-    // parent[n], comp[n] and the counters (32-bit words); rocPRIM's scratch once the number of edges is known
-    const size_t slots = (size_t)std::max<int64_t>(n - 1, 1);
-    char* d_scratch = nullptr;
-    void* d_tmp = nullptr;
+    // the emitted records, best_img[n], best_pair[n], the tally of invalid entries, parent[n], comp[n], the counters; rocPRIM's scratch
+    // once the number of edges is known
+    DevBlock<ForestEdge, u64, u64, ClusterBad, int, int, uint32_t> scratch;
+    DevBlock<char> tmp;
     ClusterBad bad{0, ~0ull};
     int64_t rounds = 0, n_edges = 0;
     int rc = SELHIP_OK;
-    hipError_t e = hipMalloc((void**)&d_scratch, slots * sizeof(ForestEdge) + 2 * (size_t)n * sizeof(u64) + sizeof(ClusterBad) +
-                                                     (2 * (size_t)n + kForestWords) * sizeof(int));
+    hipError_t e = scratch.alloc({(size_t)std::max<int64_t>(n - 1, 1), (size_t)n, (size_t)n, 1, (size_t)n, (size_t)n, kForestWords});
     if (e == hipSuccess) {
-        ForestEdge* const edges = reinterpret_cast<ForestEdge*>(d_scratch);
-        u64* const best_img = reinterpret_cast<u64*>(edges + slots);
-        u64* const best_pair = best_img + n;
-        ClusterBad* const d_bad = reinterpret_cast<ClusterBad*>(best_pair + n);
-        int* const parent = reinterpret_cast<int*>(d_bad + 1);
-        int* const comp = parent + n;
-        uint32_t* const words = reinterpret_cast<uint32_t*>(comp + n);
-        rc = forest_rounds(nullptr, st, ForestPairList{d_pairs, d_values}, (u64)n_pairs, n, parent, comp, best_img, best_pair, edges, words, d_bad, &rounds,
-                           &n_edges, &bad);
+        ForestEdge* const edges = scratch.part<0>();
+        int* const comp = scratch.part<5>();
+        rc = forest_rounds(nullptr, st, GraphValuedPairList{d_pairs, d_values}, (u64)n_pairs, n, scratch.part<4>(), comp, scratch.part<1>(), scratch.part<2>(), edges,
+                           scratch.part<6>(), scratch.part<3>(), &rounds, &n_edges, &bad);
         // an invalid entry: nothing is written
         if (!rc && !bad.count) {
             size_t tmp_bytes = 0;
             if (d_edges && n_edges > 0) {
                 e = forest_sort_bytes((size_t)n_edges, &tmp_bytes, st);
-                if (e == hipSuccess) e = hipMalloc(&d_tmp, tmp_bytes + 256);
+                if (e == hipSuccess) e = tmp.alloc({tmp_bytes + 256});
             }
-            if (e == hipSuccess) e = forest_outputs(st, edges, n_edges, comp, n, d_tmp, tmp_bytes, d_edges, d_label);
+            if (e == hipSuccess) e = forest_outputs(st, edges, n_edges, comp, n, tmp.base, tmp_bytes, d_edges, d_label);
             if (e == hipSuccess) e = hipStreamSynchronize(st);
         }
     }
-    if (d_tmp) (void)hipFree(d_tmp);
-    if (d_scratch) (void)hipFree(d_scratch);
     if (rc) return rc;
     HIPCHK(nullptr, e);
-    if (bad.count) {
-        set_err(nullptr, "the pair list holds %llu invalid entries (a vertex outside [0, %lld)); entry %llu is one", bad.count, (long long)n, bad.index);
-        return SELHIP_E_BADARG;
-    }
+    if (bad.count) return graph_bad_entries(bad, n);
     if (n_edges_out) *n_edges_out = n_edges;
     if (rounds_out) *rounds_out = rounds;
     return SELHIP_OK;

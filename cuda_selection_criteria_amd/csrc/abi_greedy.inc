@@ -1,6 +1,6 @@
 // abi_greedy.inc -- the C ABI of the greedy representative clusters (include/selection_hip.h sections 2h and 3):
 // selhip_ctx_cluster_greedy over the result list a context holds, selhip_greedy_representatives over a caller's list of edges.  Kernels
-// in kernel_greedy.cuh, host side in host_greedy.hpp; touches none of the passes' state (result list, counters, statistics, top-k,
+// in kernel_greedy.cuh, host side in host_greedy.hpp and host_graph.hpp; touches none of the passes' state (result list, counters, statistics, top-k,
 // signature cache) and nothing selhip_ctx_cluster reports.
 // Included by selection_kernels.hip.
 
@@ -18,9 +18,8 @@ int selhip_greedy_representatives(const selhip_int2_t* d_pairs, int64_t n_pairs,
         return SELHIP_E_BADARG;
     }
     if (n == 0) {
-        if (n_pairs == 0) { if (rounds_out) *rounds_out = 0; return SELHIP_OK; }
-        set_err(nullptr, "the pair list holds %lld invalid entries (a vertex outside [0, 0)); entry 0 is one", (long long)n_pairs);
-        return SELHIP_E_BADARG;
+        if (n_pairs == 0 && rounds_out) *rounds_out = 0;
+        return graph_no_vertices(n_pairs);
     }
     const hipStream_t st = (hipStream_t)hip_stream;
     if (n_pairs == 0) {
@@ -31,26 +30,23 @@ int selhip_greedy_representatives(const selhip_int2_t* d_pairs, int64_t n_pairs,
         if (rounds_out) *rounds_out = 1;
         return SELHIP_OK;
     }
-    // scratch of the call: key[n] (u64), then state[n], blocked[n], the batch's counts (32-bit words), then the tally of invalid entries
-    char* d_scratch = nullptr;
-    const size_t words = 2 * (size_t)n + kGreedyBatch + ((2 * (size_t)n + kGreedyBatch) & 1);
+    DevBlock<u64, int, int, uint32_t, ClusterBad> scratch;                     // key[n], state[n], blocked[n], the batch's counts, the tally of invalid entries
     ClusterBad bad{0, ~0ull};
     int64_t rounds = 0;
     int rc = SELHIP_OK;
-    hipError_t e = hipMalloc((void**)&d_scratch, (size_t)n * sizeof(u64) + words * sizeof(int) + sizeof(ClusterBad));
+    hipError_t e = scratch.alloc({(size_t)n, (size_t)n, (size_t)n, kGreedyBatch, 1});
     if (e == hipSuccess) {
-        u64* const key = reinterpret_cast<u64*>(d_scratch);
-        int* const state = reinterpret_cast<int*>(key + n);
-        int* const blocked = state + n;
-        uint32_t* const count = reinterpret_cast<uint32_t*>(blocked + n);
-        ClusterBad* const d_bad = reinterpret_cast<ClusterBad*>(state + words);
+        u64* const key = scratch.part<0>();
+        int* const state = scratch.part<1>();
+        int* const blocked = scratch.part<2>();
+        ClusterBad* const d_bad = scratch.part<4>();
         const unsigned vgrid = cluster_vertex_grid(n);
         hipLaunchKernelGGL(greedy_clear_kernel, dim3(vgrid), dim3(kBlock), 0, st, (long long)n, (int*)nullptr, d_bad);
         // NULL d_key: key = vertex, which is SELHIP_REP_MAX_RANK's
         hipLaunchKernelGGL(greedy_key_kernel, dim3(vgrid), dim3(kBlock), 0, st, (long long)n, SELHIP_REP_MAX_RANK, (const int*)nullptr, (const uint32_t*)nullptr,
                            (const u64*)d_key, key, state, blocked, (u64*)nullptr, (int*)nullptr);
         e = hipGetLastError();
-        if (e == hipSuccess) rc = greedy_rounds(nullptr, st, GreedyPairList{d_pairs}, (u64)n_pairs, n, key, state, blocked, count, d_bad, &rounds);
+        if (e == hipSuccess) rc = greedy_rounds(nullptr, st, GraphPairList{d_pairs}, (u64)n_pairs, n, key, state, blocked, scratch.part<3>(), d_bad, &rounds);
         if (e == hipSuccess && !rc) e = hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess && !rc) e = hipStreamSynchronize(st);
         // an invalid entry: the flags are not written
@@ -60,13 +56,9 @@ int selhip_greedy_representatives(const selhip_int2_t* d_pairs, int64_t n_pairs,
             if (e == hipSuccess) e = hipStreamSynchronize(st);
         }
     }
-    if (d_scratch) (void)hipFree(d_scratch);
     if (rc) return rc;
     HIPCHK(nullptr, e);
-    if (bad.count) {
-        set_err(nullptr, "the pair list holds %llu invalid entries (a vertex outside [0, %lld)); entry %llu is one", bad.count, (long long)n, bad.index);
-        return SELHIP_E_BADARG;
-    }
+    if (bad.count) return graph_bad_entries(bad, n);
     if (rounds_out) *rounds_out = rounds;
     return SELHIP_OK;
 }

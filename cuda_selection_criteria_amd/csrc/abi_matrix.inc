@@ -121,15 +121,12 @@ int matrix_call(selhip_ctx* c, bool query, int measure, int dtype, int64_t r0, i
         const int self = !query && (c->matrix_smh_form == 1 || !c->matrix_mirror) ? 1 : 0;
         const MatrixOut o{out_dev, (long long)ld, row_pos ? c->mat_row_pos.p : nullptr, col_pos ? c->mat_col_pos.p : nullptr, measure, self, c->matrix_mirror};
         // timed as "matrix_smh", per call of these measures: "matrix" stays the HLL kernel's
-        const int dominant = c->dominant_timer;
-        c->dominant_timer = T_MATRIX_SMH;
-        if (c->timing) c->timed_matrix_smh_calls += 1;
         hipError_t e;
         {
+            TimedCall call(c, T_MATRIX_SMH);
             TimerScope t(c, T_MATRIX_SMH);
             e = launch_matrix_smh(dtype, c->stream, query ? c->q.d_aux : c->d_aux, c->d_aux, c->m, (int)r0, (int)r1, (int)n_y, o, &c->matrix_smh_path_used);
         }
-        c->dominant_timer = dominant;
         HIPCHK(&c->err, e);
         HIPCHK(&c->err, hipStreamSynchronize(c->stream));
         return SELHIP_OK;
@@ -139,15 +136,12 @@ int matrix_call(selhip_ctx* c, bool query, int measure, int dtype, int64_t r0, i
     const int khi = query ? std::max(c->q.planes.khi, c->planes.khi) : c->planes.khi;
     const MatrixOut o{out_dev, (long long)ld, row_pos ? c->mat_row_pos.p : nullptr, col_pos ? c->mat_col_pos.p : nullptr, measure, query ? 0 : 1, c->matrix_mirror};
     // timed as "matrix", per matrix call: a counter of its own, timed_passes is the passes' (level 2 keeps this kernel's events)
-    const int dominant = c->dominant_timer;
-    c->dominant_timer = T_MATRIX;
-    if (c->timing) c->timed_matrix_calls += 1;
     hipError_t e;
     {
+        TimedCall call(c, T_MATRIX);
         TimerScope t(c, T_MATRIX);
         e = launch_matrix(c->fp_mode == SELHIP_FP_FMA, dtype, c->stream, khi, X, D, (int)r0, (int)r1, (int)n_y, o);
     }
-    c->dominant_timer = dominant;
     HIPCHK(&c->err, e);
     HIPCHK(&c->err, hipStreamSynchronize(c->stream));
     return SELHIP_OK;

@@ -108,6 +108,19 @@ struct MergeScratch {
     }
 };
 
+// scratch of the graph calls over the result list (host_graph.hpp), by role.  No call keeps anything in it: each ensures what it uses and initialises what it reads
+struct GraphScratch {
+    DevBuf<int> parent, label, degree, members;   // the union-find forest; labels, degrees, members per root or representative where the caller takes none
+    DevBuf<int> state, blocked, rep_of; // greedy: UNDECIDED / REP / MEMBER; the last round a vertex was held back; rep_of where the caller takes none
+    DevBuf<uint32_t> flag, ids, words;  // root / representative flags, their exclusive scan (one slot past the last genome: the number of clusters); the counters of a batch of rounds
+    DevBuf<u64> key, best;              // representative key / greedy key / component's best image; a member's best image / a component's best pair
+    DevBuf<ClusterBad> bad;             // records an edge kernel refused (none, unless a list is corrupt)
+    DevBuf<char> tmp;                   // rocPRIM scan / sort scratch
+    DevBuf<ForestEdge> edges;           // the forest's emitted records before their sort
+    void release() { parent.release(); label.release(); degree.release(); members.release(); state.release(); blocked.release(); rep_of.release(); flag.release();
+                     ids.release(); words.release(); key.release(); best.release(); bad.release(); tmp.release(); edges.release(); }
+};
+
 // TWO sets of per_set counter blocks: pass k uses set k & 1 and its first kernel clears the other for pass k + 1 -- no memset dispatch
 // on the stream in steady state.  dirty: a pass claimed a set and did not get to the end of its enqueue (its first kernel may never have
 // run), or nothing has cleared the buffer yet, or the stream changed behind the clearing: the next claim clears both sets first, once
@@ -353,26 +366,11 @@ struct selhip_ctx {
     int matrix_smh_form = 1;
     int matrix_smh_path_used = -1;
 
-    // single-linkage clusters of the result list (selhip_ctx_cluster; kernel_cluster.cuh, host_cluster.hpp): scratch the call owns
-    DevBuf<int> cl_parent, cl_label, cl_degree, cl_members;   // the union-find forest; labels, degrees, members per root where the caller takes none
-    DevBuf<uint32_t> cl_flag, cl_ids;   // root flags and their exclusive scan (one slot past the last genome: the number of clusters)
-    DevBuf<u64> cl_key;                 // the representative's key per cluster
-    DevBuf<ClusterBad> cl_bad;          // records the edge kernel refused (none, unless a list is corrupt)
-    DevBuf<char> cl_tmp;                // rocPRIM scan scratch
-    int clusters_last = -1;             // the C of the last call ("clusters_last"), -1 = none yet
-
-    // greedy representative clusters (selhip_ctx_cluster_greedy; kernel_greedy.cuh, host_greedy.hpp): scratch the call owns, beside what
-    // it shares with the call above (cl_key, cl_degree, cl_members, cl_flag, cl_ids, cl_bad, cl_tmp)
-    DevBuf<int> gr_state, gr_blocked, gr_rep_of;   // UNDECIDED / REP / MEMBER; the last round a vertex was held back; rep_of where the caller takes none
-    DevBuf<u64> gr_best;                // per member, the image of its best edge to a representative
-    DevBuf<uint32_t> gr_count;          // the UNDECIDED counts of a batch of rounds
-    int greedy_clusters_last = -1;      // the C of the last call ("greedy_clusters_last"), -1 = none yet
+    GraphScratch gs;                    // the graph calls over the result list (host_graph.hpp): their scratch; below, what the last call of each kind reports
+    int clusters_last = -1;             // selhip_ctx_cluster: the C of the last call ("clusters_last"), -1 = none yet
+    int greedy_clusters_last = -1;      // selhip_ctx_cluster_greedy: the C of the last call ("greedy_clusters_last"), -1 = none yet
     int greedy_rounds_last = -1;        // its rounds ("greedy_rounds_last")
-
-    // maximum spanning forest (selhip_ctx_spanning_forest; kernel_forest.cuh, host_forest.hpp): the emitted records before their sort;
-    // everything else is scratch of the two calls above (cl_parent, cl_label, cl_key, gr_best, gr_count, cl_bad, cl_tmp)
-    DevBuf<ForestEdge> fo_edges;
-    int forest_rounds_last = -1;        // the rounds of the last call, the empty one included ("forest_rounds_last"), -1 = none yet
+    int forest_rounds_last = -1;        // selhip_ctx_spanning_forest: the rounds of the last call, the empty one included ("forest_rounds_last"), -1 = none yet
     int forest_edges_last = -1;         // its F ("forest_edges_last")
 
     // sketches merged by group (selhip_ctx_merge_groups; kernel_merge.cuh, host_merge.hpp): scratch the call owns
@@ -382,18 +380,20 @@ struct selhip_ctx {
     int timing = 0;                     // 0 off, 1 every kernel scope, 2 dominant stage-1 kernel only
     int dominant_timer = T_STAGE1;
     int timed_kernel = 0;               // timing level 2 keeps the events of: 0 = the stage-1 kernel (join / stream), 1 = stage 2a ("timed_kernel")
-    long timed_passes = 0;
-    long timed_matrix_calls = 0;        // matrix calls under timing: the divisor of "matrix" alone (the passes' per-pass averages are not theirs to dilute)
-    long timed_matrix_smh_calls = 0;    // ... and those of the SuperMinHash measures: the divisor of "matrix_smh"
-    long timed_cluster_calls = 0;       // cluster calls under timing: the divisor of "cluster"
-    long timed_greedy_calls = 0;        // greedy calls under timing: the divisor of "greedy"
-    long timed_forest_calls = 0;        // forest calls under timing: the divisor of "forest"
-    long timed_merge_calls = 0;         // merge calls under timing: the divisor of "merge"
+    long timed_passes = 0;              // passes under timing: the divisor of every pass timer
+    long timed_calls[T_COUNT] = {};     // per call timer (TimedCall), its calls under timing: the divisor of that timer alone (the passes' per-pass averages are not theirs to dilute)
     int last_attempts = 0;              // enqueues the last finished run needed (1 = nothing overflowed)
     KernelTimer timers[T_COUNT];
 };
 
 namespace {
+
+// a call timed per call under a name of its own (T_MATRIX and the ids behind it): its timer is the dominant one while it runs (level 2 keeps its events), its calls are counted apart from the passes
+struct TimedCall {
+    selhip_ctx* c; int before;
+    TimedCall(selhip_ctx* c_, int id) : c(c_), before(c_->dominant_timer) { c->dominant_timer = id; if (c->timing) c->timed_calls[id] += 1; }
+    ~TimedCall() { c->dominant_timer = before; }
+};
 
 int check_device(std::string* err) {
     int cnt = 0;

@@ -1,5 +1,5 @@
 // host_forest.hpp -- host side of the maximum spanning forest (kernel_forest.cuh): the rounds, the sort and the launches behind
-// selhip_spanning_forest and selhip_ctx_spanning_forest, and the context's scratch.
+// selhip_spanning_forest and selhip_ctx_spanning_forest.  Admission, the run of an admitted call and the scratch are host_graph.hpp's.
 // Part of the kernel translation unit selection_kernels.hip (included there, after host_greedy.hpp; the grids -- and so the
 // "cluster_blocks" hook -- are host_cluster.hpp's); not a stand-alone header.
 #pragma once
@@ -10,8 +10,6 @@ namespace {
 // so a batch's trailing rounds cost four empty launches each; a batch costs two small copies and one wait
 constexpr int kForestBatch = 4;
 constexpr int kForestWords = kForestBatch + 1;          // [0] the records emitted so far, [1 + j] the picks of the batch's round j
-
-void release_forest(selhip_ctx* c) { c->fo_edges.release(); }
 
 // the rounds over a list, on st, until one picks nothing: comp[] ends as the labels, edges[0 .. *edges_out) as the forest in the
 // order the device emitted it.  words: kForestWords device words.  *rounds_out = the rounds, the empty one included; *bad_out = what
@@ -72,83 +70,52 @@ hipError_t forest_outputs(hipStream_t st, const ForestEdge* edges, int64_t f, co
     return e;
 }
 
-// the launches of selhip_ctx_spanning_forest behind its checks: n > 0 vertices, cnt > 0 records.
-// (the scratch of selhip_ctx_cluster and selhip_ctx_cluster_greedy serves where it has the type and the size: no call keeps anything in it)
+// the launches of selhip_ctx_spanning_forest behind its checks: n > 0 vertices, cnt > 0 records
 int forest_launches(selhip_ctx* c, double min_value, const selhip_forest_t& out, int64_t cnt, int64_t* rounds, int64_t* n_edges, ClusterBad* bad_out) {
     const int64_t n = c->n;
-    hipError_t e = c->cl_parent.ensure((size_t)n);
-    if (e == hipSuccess) e = c->cl_label.ensure((size_t)n);
-    if (e == hipSuccess) e = c->cl_key.ensure((size_t)n);
-    if (e == hipSuccess) e = c->gr_best.ensure((size_t)n);
-    if (e == hipSuccess) e = c->gr_count.ensure(kForestWords);
-    if (e == hipSuccess) e = c->cl_bad.ensure(1);
-    if (e == hipSuccess) e = c->fo_edges.ensure((size_t)std::max<int64_t>(n - 1, 1));
+    hipError_t e = c->gs.parent.ensure((size_t)n);
+    if (e == hipSuccess) e = c->gs.label.ensure((size_t)n);
+    if (e == hipSuccess) e = c->gs.key.ensure((size_t)n);
+    if (e == hipSuccess) e = c->gs.best.ensure((size_t)n);
+    if (e == hipSuccess) e = c->gs.words.ensure(kForestWords);
+    if (e == hipSuccess) e = c->gs.bad.ensure(1);
+    if (e == hipSuccess) e = c->gs.edges.ensure((size_t)std::max<int64_t>(n - 1, 1));
     if (e != hipSuccess) {
         set_err(&c->err, "selhip_ctx_spanning_forest: scratch for %lld genomes: %s", (long long)n, hipGetErrorString(e));
         return SELHIP_E_HIP;
     }
     {
         TimerScope t(c, T_FOREST);
-        const int rc = forest_rounds(&c->err, c->stream, GreedyRecordList{c->results.p, min_value}, (u64)cnt, n, c->cl_parent.p, c->cl_label.p, c->cl_key.p,
-                                     c->gr_best.p, c->fo_edges.p, c->gr_count.p, c->cl_bad.p, rounds, n_edges, bad_out);
+        const int rc = forest_rounds(&c->err, c->stream, GraphRecordList{c->results.p, min_value}, (u64)cnt, n, c->gs.parent.p, c->gs.label.p, c->gs.key.p,
+                                     c->gs.best.p, c->gs.edges.p, c->gs.words.p, c->gs.bad.p, rounds, n_edges, bad_out);
         if (rc) return rc;
         if (bad_out->count) return SELHIP_OK;                                     // (the caller reports it; nothing is written)
         size_t tmp_bytes = 0;                                                     // (the stream is idle behind the rounds: the scratch may move)
         if (out.d_edges && *n_edges > 0) {
             HIPCHK(&c->err, forest_sort_bytes((size_t)*n_edges, &tmp_bytes, c->stream));
-            HIPCHK(&c->err, c->cl_tmp.ensure(tmp_bytes + 256));
+            HIPCHK(&c->err, c->gs.tmp.ensure(tmp_bytes + 256));
         }
-        HIPCHK(&c->err, forest_outputs(c->stream, c->fo_edges.p, *n_edges, c->cl_label.p, n, c->cl_tmp.p, tmp_bytes, out.d_edges, out.d_label));
+        HIPCHK(&c->err, forest_outputs(c->stream, c->gs.edges.p, *n_edges, c->gs.label.p, n, c->gs.tmp.p, tmp_bytes, out.d_edges, out.d_label));
     }
     HIPCHK(&c->err, hipStreamSynchronize(c->stream));
     return SELHIP_OK;
 }
 
 int forest_call(selhip_ctx* c, double min_value, const selhip_forest_t* out, int64_t* n_edges_out) {
-    if (!c) return SELHIP_E_BADARG;
-    if (c->pending) { set_err(&c->err, "selhip_ctx_spanning_forest: a pass is still pending (selhip_ctx_finish)"); return SELHIP_E_STATE; }
-    if (!c->have_run) { set_err(&c->err, "selhip_ctx_spanning_forest: the context holds no result list (run a pass first)"); return SELHIP_E_STATE; }
-    if (c->last_was_query) {
-        set_err(&c->err, "selhip_ctx_spanning_forest: the result list is a query pass's, whose ranks live in two index spaces; take an all-pairs or pair-list pass");
-        return SELHIP_E_STATE;
-    }
-    if (!out) { set_err(&c->err, "selhip_ctx_spanning_forest: null selhip_forest_t (its members may be null, the struct may not)"); return SELHIP_E_BADARG; }
-    if (std::isnan(min_value)) { set_err(&c->err, "selhip_ctx_spanning_forest: min_value is NaN (-INFINITY takes every record)"); return SELHIP_E_BADARG; }
-    const int64_t n = c->n, cnt = result_records(c);
-    if (n > 0x7FFFFFFFll) { set_err(&c->err, "selhip_ctx_spanning_forest takes up to 2^31 - 1 genomes"); return SELHIP_E_BADARG; }
+    int rc = graph_admit(c, kForestCall, out, min_value, [] { return SELHIP_OK; });
+    if (rc) return rc;
     if (out->d_edges && (reinterpret_cast<uintptr_t>(out->d_edges) & 15)) {
         set_err(&c->err, "selhip_ctx_spanning_forest: d_edges must be 16-byte aligned");
         return SELHIP_E_BADARG;
     }
-    HIPCHK(&c->err, hipSetDevice(c->device));
-    // timed as "forest", per forest call: a counter of its own, like "cluster" (level 2 keeps these launches' events)
-    const int dominant = c->dominant_timer;
-    c->dominant_timer = T_FOREST;
-    if (c->timing) c->timed_forest_calls += 1;
-    int rc = SELHIP_OK;
+    const int64_t n = c->n;
     int64_t rounds = n ? 1 : 0, n_edges = 0;
-    ClusterBad bad{0, ~0ull};
-    if (n == 0) {
-        // nothing to write
-    } else if (cnt == 0) {
-        // no record, no edge: the identity labels, written by the one launch
-        {
-            TimerScope t(c, T_FOREST);
-            hipLaunchKernelGGL(forest_singletons_kernel, dim3(cluster_vertex_grid(n)), dim3(kBlock), 0, c->stream, (long long)n, out->d_label);
-        }
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) { set_err(&c->err, "selhip_ctx_spanning_forest: %s", hipGetErrorString(e)); rc = SELHIP_E_HIP; }
-    } else {
-        rc = forest_launches(c, min_value, *out, cnt, &rounds, &n_edges, &bad);
-    }
-    c->dominant_timer = dominant;
+    rc = graph_run(c, kForestCall,
+                   [&] {   // the identity labels
+                       hipLaunchKernelGGL(forest_singletons_kernel, dim3(cluster_vertex_grid(n)), dim3(kBlock), 0, c->stream, (long long)n, out->d_label);
+                   },
+                   [&](int64_t cnt, ClusterBad* bad) { return forest_launches(c, min_value, *out, cnt, &rounds, &n_edges, bad); });
     if (rc) return rc;
-    if (bad.count) {
-        set_err(&c->err, "selhip_ctx_spanning_forest: %llu records of the result list carry a rank outside [0, %lld); record %llu is one (internal error)",
-                bad.count, (long long)n, bad.index);
-        return SELHIP_E_HIP;
-    }
     c->forest_rounds_last = (int)rounds;
     c->forest_edges_last = (int)n_edges;
     if (n_edges_out) *n_edges_out = n_edges;

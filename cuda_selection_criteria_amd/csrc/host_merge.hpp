@@ -151,17 +151,14 @@ int merge_groups_call(selhip_ctx* c, const int32_t* d_group, int64_t G, const se
     if (out->d_aux) kinds[nk++] = MergeKind{c->d_aux, out->d_aux, (size_t)c->m * 8, kMergeMinU64};
     if (out->d_aux_hll) kinds[nk++] = MergeKind{c->d_aux_hll, out->d_aux_hll, (size_t)1 << c->p_aux, kMergeMaxU8};
     // timed as "merge", per merge call: a counter of its own, like "cluster" (level 2 keeps these launches' events)
-    const int dominant = c->dominant_timer;
-    c->dominant_timer = T_MERGE;
-    if (c->timing) c->timed_merge_calls += 1;
     MergeInfo bad{};
     int rc;
     {
+        TimedCall call(c, T_MERGE);
         TimerScope t(c, T_MERGE);
         rc = merge_run(&c->err, c->stream, c->mg, kinds, G > 0 ? nk : 0, n, d_group, G, out->d_size, &bad);
         if (!rc && !bad.bad_count && out->d_cards && G > 0) rc = compute_cards(c, hll_out, G, c->p, out->d_cards);
     }
-    c->dominant_timer = dominant;
     if (rc) return rc;
     HIPCHK(&c->err, hipStreamSynchronize(c->stream));
     if (bad.bad_count) { merge_bad_message(&c->err, "selhip_ctx_merge_groups", bad, G); return SELHIP_E_BADARG; }

@@ -1,6 +1,6 @@
 // kernel_forest.cuh -- the maximum spanning forest of a record list, which is its single-linkage dendrogram (selhip_spanning_forest,
 // selhip_ctx_spanning_forest; host side in host_forest.hpp).  Part of libselhip.so; included by selection_kernels.hip only, behind
-// kernel_cluster.cuh (cl_load, cl_unite, ClusterBad) and kernel_greedy.cuh (greedy_image, greedy_value, the two kinds of list).
+// kernel_graph.cuh (cl_load, cl_unite, ClusterBad, graph_image, graph_value, the lists).
 //
 // THE DEFINITION.  An edge is an unordered pair {a < b} with the greatest value of its records; edge e goes BEFORE edge f when
 // image(e) > image(f), or the images are equal and (e.a, e.b) is lexicographically smaller: a strict total order.  Kruskal's visit in
@@ -47,7 +47,9 @@ constexpr u64 kForestNoPair = ~0ull;            // best_pair of a component with
 struct alignas(16) ForestEdge { int a, b; double value; };
 static_assert(sizeof(ForestEdge) == sizeof(selhip_pair_t), "a forest edge is a result record");
 
-// the BEFORE order on emitted records (values are no NaN; greedy_image's rule, written out for the sort's host and device sides)
+// the BEFORE order on emitted records (values are no NaN).  image: graph_image's rule (greedy_image, until the graph kernels shared
+// it), written out for the sort's host and device sides -- and for its kernels: through graph_image itself rocPRIM's merge sort
+// compiles to other instructions
 struct ForestBefore {
     __host__ __device__ static u64 image(double v) {
         if (v == 0.0) v = 0.0;
@@ -63,17 +65,6 @@ struct ForestBefore {
 };
 
 __device__ __forceinline__ u64 fo_load(const u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// a caller's entries {x, y} with values[e], or 1.0 where there are none; the records of a pass are GreedyRecordList's
-struct ForestPairList {
-    const selhip_int2_t* p;
-    const double* values;
-    __device__ __forceinline__ bool edge(u64 e, int* u, int* v, double* value) const {
-        const selhip_int2_t r = p[e]; *u = r.x; *v = r.y;
-        *value = values ? values[e] : 1.0;
-        return true;
-    }
-};
 
 // word[c] = max (kMax) or min of itself and val, for every lane with ok; see HOT WORDS above.  Call with the whole wave converged
 template <bool kMax>
@@ -115,13 +106,13 @@ __device__ __forceinline__ bool forest_record(const List& list, u64 e, int n, co
     int u, v;
     double value;
     if (!list.edge(e, &u, &v, &value)) return false;
-    if ((uint32_t)u >= (uint32_t)n || (uint32_t)v >= (uint32_t)n) {
-        if (bad) { atomicAdd(&bad->count, 1ull); atomicMin(&bad->index, e); }
+    if ((uint32_t)u >= (uint32_t)n || (uint32_t)v >= (uint32_t)n) {                 // (graph_edge's check, written out: folded onto it the
+        if (bad) { atomicAdd(&bad->count, 1ull); atomicMin(&bad->index, e); }       // two record kernels compile to other branches)
         return false;
     }
     if (!(value == value) || u == v) return false;
     *a = u < v ? u : v; *b = u < v ? v : u;
-    *img = greedy_image(value);
+    *img = graph_image(value);
     *ca = comp[*a]; *cb = comp[*b];
     return *ca != *cb;
 }
@@ -201,7 +192,7 @@ forest_hook_kernel(long long n, const int* __restrict__ comp, const u64* __restr
             first = (uint32_t)__builtin_amdgcn_readlane((int)first, leader);
             const uint32_t slot = first + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
             if (emits && slot < cap) {
-                const u64 bits = (u64)__double_as_longlong(greedy_value(best_img[g]));
+                const u64 bits = (u64)__double_as_longlong(graph_value(best_img[g]));
                 reinterpret_cast<uint4*>(edges)[slot] = make_uint4((uint32_t)a, (uint32_t)b, (uint32_t)bits, (uint32_t)(bits >> 32));
             }
         }

@@ -1,6 +1,6 @@
 // kernel_greedy.cuh -- greedy representative clusters of a record list (selhip_greedy_representatives, selhip_ctx_cluster_greedy; host
 // side in host_greedy.hpp): the CD-HIT / UCLUST scheme.  Part of libselhip.so; included by selection_kernels.hip only, behind
-// kernel_cluster.cuh, whose ClusterBad, cl_degree_add and cluster_rep_key it reuses.
+// kernel_graph.cuh (the lists, graph_edge, graph_image, cl_degree_add) and kernel_cluster.cuh, whose cluster_rep_key it reuses.
 //
 // THE SEQUENTIAL DEFINITION.  Every vertex has a 64-bit key; a vertex h goes BEFORE a vertex l when key[h] > key[l], or the keys are
 // equal and h < l (greedy_before).  Visit the vertices in that order: a vertex becomes a representative unless one of its neighbours
@@ -35,7 +35,7 @@
 //                          degrees and the rule's arithmetic in every round)
 //   greedy_degree_kernel   the degree tally of cluster_edges_kernel alone (cl_degree_add), launched only where a degree is wanted
 //   greedy_reps_kernel     rep_of[g] = g or none yet, the representatives' flags for the scan
-//   greedy_best_kernel     per member, the greatest value of an edge to a representative: a 64-bit atomic maximum on greedy_image(value)
+//   greedy_best_kernel     per member, the greatest value of an edge to a representative: a 64-bit atomic maximum on graph_image(value)
 //   greedy_assign_kernel   the records whose value is the member's best and whose other end is REP: an atomic minimum on its rank
 //                          (two passes: value and rank do not fit one 64-bit atomic)
 //   (rocprim::exclusive_scan of the flags: the dense ids, numbered by ascending representative)
@@ -50,17 +50,6 @@ constexpr int kGreedyNone = 0x7FFFFFFF;        // rep_of of a member before gree
 
 // h goes before l in the visiting order
 __device__ __forceinline__ bool greedy_before(u64 key_h, int h, u64 key_l, int l) { return key_h > key_l || (key_h == key_l && h < l); }
-
-// the order-preserving integer image of a value that is no NaN: a > b in f64 <=> image(a) > image(b), and -0.0 == +0.0 have one
-// image (canonicalised first).  Every image is > 0, so 0 is "no edge yet"
-__device__ __forceinline__ u64 greedy_image(double v) {
-    if (v == 0.0) v = 0.0;                      // -0.0 -> +0.0
-    const u64 b = (u64)__double_as_longlong(v);
-    return (b >> 63) ? ~b : b | 0x8000000000000000ull;
-}
-__device__ __forceinline__ double greedy_value(u64 image) {
-    return __longlong_as_double((long long)((image >> 63) ? image & 0x7FFFFFFFFFFFFFFFull : ~image));
-}
 
 // key[g]: SELHIP_REP_MAX_DEGREE, _MIN_RANK, _MAX_RANK as cluster_rep_key; SELHIP_REP_PRIORITY (priority[g], reversed rank); the state
 // and the tallies of a call cleared.  Every pointer but state / blocked / key may be null
@@ -87,35 +76,6 @@ greedy_clear_kernel(long long n, int* __restrict__ degree, ClusterBad* __restric
     if (blockIdx.x == 0 && threadIdx.x == 0) { bad->count = 0; bad->index = ~0ull; }
 }
 
-// the two kinds of list, as in kernel_cluster.cuh, with the value of an entry: a caller's entries {x, y}, all of them edges, and a pass's
-// records {i, k, value}, edges where value >= min_value
-struct GreedyPairList {
-    const selhip_int2_t* p;
-    __device__ __forceinline__ bool edge(u64 e, int* u, int* v, double* value) const { const selhip_int2_t r = p[e]; *u = r.x; *v = r.y; *value = 1.0; return true; }
-};
-struct GreedyRecordList {
-    const selhip_pair_t* p;                     // 16-byte records, 16-byte aligned: one dwordx4 per lane, a wave reads 1 KiB in a row
-    double min_value;
-    __device__ __forceinline__ bool edge(u64 e, int* u, int* v, double* value) const {
-        const uint4 w = reinterpret_cast<const uint4*>(p)[e];
-        *u = (int)w.x; *v = (int)w.y;
-        *value = __hiloint2double((int)w.w, (int)w.z);
-        return *value >= min_value;             // NaN never passes, -inf takes everything
-    }
-};
-
-// one record of a list as an edge of the graph: false for a record below the cut and for one with a rank outside [0, n), which is
-// tallied in *bad where the caller passes it (one launch per call does) and touches nothing
-template <class List>
-__device__ __forceinline__ bool greedy_record(const List& list, u64 e, int n, int* u, int* v, double* value, ClusterBad* __restrict__ bad) {
-    if (!list.edge(e, u, v, value)) return false;
-    if ((uint32_t)*u >= (uint32_t)n || (uint32_t)*v >= (uint32_t)n) {
-        if (bad) { atomicAdd(&bad->count, 1ull); atomicMin(&bad->index, e); }
-        return false;
-    }
-    return true;
-}
-
 // every record of the graph adds one to both of its vertices, a record with i == k two to the one: the tally of cluster_edges_kernel
 template <class List>
 __global__ void __launch_bounds__(kBlock)
@@ -124,7 +84,7 @@ greedy_degree_kernel(const List list, u64 n_edges, int n, int* __restrict__ degr
     for (u64 e = (u64)blockIdx.x * kBlock + threadIdx.x; e < n_edges; e += stride) {
         int u, v;
         double value;
-        const bool ok = greedy_record(list, e, n, &u, &v, &value, nullptr);
+        const bool ok = graph_edge<true>(list, e, n, &u, &v, &value, nullptr);
         cl_degree_add(degree, u, ok);
         cl_degree_add(degree, v, ok);
     }
@@ -141,7 +101,7 @@ greedy_edges_kernel(const List list, u64 n_edges, int n, const u64* __restrict__
     for (u64 e = (u64)blockIdx.x * kBlock + threadIdx.x; e < n_edges; e += stride) {
         int u, v;
         double value;
-        if (!greedy_record(list, e, n, &u, &v, &value, bad) || u == v) continue;
+        if (!graph_edge<true>(list, e, n, &u, &v, &value, bad) || u == v) continue;
         const int su = state[u], sv = state[v];
         if (su != kGreedyUndecided && sv != kGreedyUndecided) continue;             // both ends final: most records, after a few rounds
         const bool u_first = greedy_before(key[u], u, key[v], v);
@@ -191,11 +151,11 @@ greedy_best_kernel(const List list, u64 n_edges, int n, const int* __restrict__ 
     for (u64 e = (u64)blockIdx.x * kBlock + threadIdx.x; e < n_edges; e += stride) {
         int u, v;
         double value;
-        if (!greedy_record(list, e, n, &u, &v, &value, nullptr) || u == v) continue;
+        if (!graph_edge<true>(list, e, n, &u, &v, &value, nullptr) || u == v) continue;
         const int su = state[u], sv = state[v];
         if (su == sv) continue;                                                      // (two representatives share no edge)
         const int g = su == kGreedyMember ? u : v;
-        atomicMax(best + g, greedy_image(value));
+        atomicMax(best + g, graph_image(value));
     }
 }
 
@@ -207,11 +167,11 @@ greedy_assign_kernel(const List list, u64 n_edges, int n, const int* __restrict_
     for (u64 e = (u64)blockIdx.x * kBlock + threadIdx.x; e < n_edges; e += stride) {
         int u, v;
         double value;
-        if (!greedy_record(list, e, n, &u, &v, &value, nullptr) || u == v) continue;
+        if (!graph_edge<true>(list, e, n, &u, &v, &value, nullptr) || u == v) continue;
         const int su = state[u], sv = state[v];
         if (su == sv) continue;
         const int g = su == kGreedyMember ? u : v, r = su == kGreedyMember ? v : u;
-        if (best[g] == greedy_image(value)) atomicMin(rep_of + g, r);
+        if (best[g] == graph_image(value)) atomicMin(rep_of + g, r);
     }
 }
 
@@ -222,7 +182,7 @@ greedy_members_kernel(long long n, const int* __restrict__ state, const u64* __r
                       double* __restrict__ value, int* __restrict__ members) {
     const long long stride = (long long)gridDim.x * kBlock;
     for (long long g = (long long)blockIdx.x * kBlock + threadIdx.x; g < n; g += stride) {
-        if (value) value[g] = state[g] == kGreedyRep ? 1.0 : greedy_value(best[g]);
+        if (value) value[g] = state[g] == kGreedyRep ? 1.0 : graph_value(best[g]);
         if (members) {
             const int r = rep_of[g];
             if ((uint32_t)r < (uint32_t)n) atomicAdd(members + r, 1);

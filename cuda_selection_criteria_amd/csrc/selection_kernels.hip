@@ -46,12 +46,14 @@
 //                       (shared with libselhost.so, like ertl_mle.hpp)
 //   kernel_fold.cuh     hll_fold_kernel: the auxiliary HLL sketches folded from the main registers, one streaming read (in a lane, across
 //                       the lanes of a load, across the loads of a wave)
-//   kernel_cluster.cuh  single-linkage clusters of a record list: a lock-free union-find with parent[x] <= x (agent-scope atomic minima,
+//   kernel_graph.cuh    what the three graph kernels below share: the lock-free union-find with parent[x] <= x, the wave-aggregated degree
+//                       tally, the three kinds of edge list, the range check of an entry with its tally, the order-preserving image of a value
+//   kernel_cluster.cuh  single-linkage clusters of a record list: the union-find of kernel_graph.cuh (agent-scope atomic minima,
 //                       one lane per record), flattened labels, dense ids, degrees, sizes and one representative per cluster
 //   kernel_greedy.cuh   greedy representative clusters of a record list (CD-HIT / UCLUST): the first maximal independent set under a key
 //                       order in rounds of one edge and one vertex launch, then every member to its most similar representative
 //   kernel_forest.cuh   maximum spanning forest of a record list, its single-linkage dendrogram: Boruvka rounds of two record launches (best
-//                       value, then smallest pair among the equal), a hook and a flatten launch over the union-find of kernel_cluster.cuh
+//                       value, then smallest pair among the equal), a hook and a flatten launch over the union-find of kernel_graph.cuh
 //   kernel_merge.cuh    sketches merged by group: a counting sort of the members, then a segmented reduction of the rows (u8 maximum of the
 //                       HLL registers, u64 minimum of the SuperMinHash buckets) in segments of at most SELHIP_MERGE_SEGMENT members per level
 //
@@ -74,6 +76,7 @@
 #include <limits>
 #include <mutex>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "../../include/selection_hip.h"
@@ -101,6 +104,7 @@
 #include "kernel_dense.cuh"
 #include "kernel_topk.cuh"
 #include "kernel_fold.cuh"
+#include "kernel_graph.cuh"      // (in front of the three graph kernels: union-find, edge lists, range check, value image)
 #include "kernel_cluster.cuh"
 #include "kernel_greedy.cuh"
 #include "kernel_forest.cuh"
@@ -114,8 +118,9 @@
 #include "host_pairs.hpp"        // pair-list passes: the chain behind selhip_ctx_run_pairs
 #include "host_query.hpp"        // query passes: Q x D (windows, signature join or stream, verification, stage 2)
 #include "host_topk.hpp"         // top-k of a query pass and of an all-pairs pass: scratch, launches, the count the result accessors expose
-#include "host_cluster.hpp"      // single-linkage clusters: scratch and launches behind selhip_ctx_cluster / selhip_components
-#include "host_greedy.hpp"       // greedy representative clusters: rounds, scratch and launches behind selhip_ctx_cluster_greedy / selhip_greedy_representatives
+#include "host_graph.hpp"        // the graph calls' shared front end: admission, the run of an admitted call, reports, the block carver
+#include "host_cluster.hpp"      // single-linkage clusters: grids and launches behind selhip_ctx_cluster / selhip_components
+#include "host_greedy.hpp"       // greedy representative clusters: rounds and launches behind selhip_ctx_cluster_greedy / selhip_greedy_representatives
 #include "host_forest.hpp"       // maximum spanning forest: rounds, sort and launches behind selhip_ctx_spanning_forest / selhip_spanning_forest
 #include "host_merge.hpp"       // sketches merged by group: checks, levels and launches behind selhip_merge_sketches / selhip_ctx_merge_groups
 #include "host_build.hpp"       // split sketch builder: items, launches, the reduction through merge_run, the fallback launch

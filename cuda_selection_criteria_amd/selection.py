@@ -605,12 +605,7 @@ class Selector:
         out = Forest(edges.data_ptr() if edges.numel() else None, labels.data_ptr() if self.n else None)
         cnt = C.c_int64()
         check(self._lib.selhip_ctx_spanning_forest(self._ctx, mv, C.byref(out), C.byref(cnt)), self._ctx)
-        f = int(cnt.value)
-        res = {"edges": edges[:f], "labels": labels}
-        if to_host:
-            res = {"edges": np.ascontiguousarray(edges[:f].cpu().numpy()).view(PAIR_DTYPE).reshape(-1), "labels": labels.cpu().numpy()}
-        res.update(n_edges=f, n_clusters=self.n - f, rounds=self.get_param("forest_rounds_last"))
-        return res
+        return _forest_result(edges, labels, int(cnt.value), self.n, self.get_param("forest_rounds_last"), to_host)
 
     # -- sketches merged by group ---------------------------------------------------------------------
     def merge(self, groups, n_groups: Optional[int] = None, to_host: bool = False) -> dict:
@@ -958,15 +953,21 @@ def components(pairs, n: int, device: int = 0, to_host: bool = True):
     import torch
     lib = hip_lib()
     dev = torch.device("cuda", device)
-    if isinstance(pairs, np.ndarray) or not hasattr(pairs, "data_ptr"):
-        pairs = torch.from_numpy(np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)).to(dev)
-    assert pairs.is_cuda and pairs.is_contiguous() and pairs.dtype == torch.int32 and pairs.dim() == 2 and pairs.shape[1] == 2, \
-        "pairs: a contiguous int32 tensor of shape (P, 2)"
+    pairs = _device_pairs(pairs, dev)
     with torch.cuda.device(dev):
         labels = torch.empty(int(n), dtype=torch.int32, device=dev)
         check(lib.selhip_components(pairs.data_ptr() if pairs.numel() else None, int(pairs.shape[0]), int(n),
                                     labels.data_ptr() if n else None, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
     return labels.cpu().numpy() if to_host else labels
+
+
+def _forest_result(edges, labels, f: int, n: int, rounds: int, to_host: bool) -> dict:
+    """the dict of Selector.spanning_forest / spanning_forest from the device tensors a call filled: its first f edge records and the labels"""
+    res = {"edges": edges[:f], "labels": labels}
+    if to_host:
+        res = {"edges": np.ascontiguousarray(edges[:f].cpu().numpy()).view(PAIR_DTYPE).reshape(-1), "labels": labels.cpu().numpy()}
+    res.update(n_edges=f, n_clusters=n - f, rounds=rounds)
+    return res
 
 
 def spanning_forest(pairs, n: int, values=None, device: int = 0, to_host: bool = True) -> dict:
@@ -991,11 +992,7 @@ def spanning_forest(pairs, n: int, values=None, device: int = 0, to_host: bool =
         check(lib.selhip_spanning_forest(pairs.data_ptr() if pairs.numel() else None, vals.data_ptr() if vals is not None and vals.numel() else None,
                                          int(pairs.shape[0]), n, edges.data_ptr() if edges.numel() else None, labels.data_ptr() if n > 0 else None,
                                          C.byref(f), C.byref(rounds), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-    res = {"edges": edges[:f.value], "labels": labels}
-    if to_host:
-        res = {"edges": np.ascontiguousarray(edges[:f.value].cpu().numpy()).view(PAIR_DTYPE).reshape(-1), "labels": labels.cpu().numpy()}
-    res.update(n_edges=int(f.value), n_clusters=n - int(f.value), rounds=int(rounds.value))
-    return res
+    return _forest_result(edges, labels, int(f.value), n, int(rounds.value), to_host)
 
 
 def forest_cluster_counts(edges, n: int, thresholds) -> np.ndarray:

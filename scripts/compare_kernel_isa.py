@@ -3,12 +3,13 @@
 
     hipcc --offload-arch=gfx950 <HIPFLAGS of csrc/Makefile> --cuda-device-only -S -o old.s selection_kernels.hip     (in the old tree)
     hipcc ... --cuda-device-only -S -o new.s selection_kernels.hip                                                  (in the new tree)
-    scripts/compare_kernel_isa.py old.s new.s [--strip ", false"]
+    scripts/compare_kernel_isa.py old.s new.s [--strip ", false"] [--rename OLD=NEW ...]
 
 Every kernel of old.s must be in new.s with the same instructions (labels renumbered, comments and directives dropped).  A kernel that
 gained a trailing template argument is matched by its demangled name with `--strip` taken off the end of the argument list: the
-count kernels' `EMIT = false` instantiations are `--strip ", false"`.  Prints what differs and the kernels that only new.s has; exit
-status 1 if a kernel of old.s is missing or differs.  Needs no GPU.
+count kernels' `EMIT = false` instantiations are `--strip ", false"`.  A kernel whose template argument was renamed is matched with
+`--rename OLD=NEW` (repeatable), applied as whole words to the demangled names of old.s before matching.  Prints what differs and the
+kernels that only new.s has; exit status 1 if a kernel of old.s is missing or differs.  Needs no GPU.
 """
 import argparse
 import re
@@ -59,9 +60,12 @@ def main():
     ap.add_argument("old")
     ap.add_argument("new")
     ap.add_argument("--strip", default=", false", help="trailing template argument text a kernel may have gained")
+    ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW", help="a name of the old build that the new build spells NEW")
     a = ap.parse_args()
     old, new = kernels(a.old), kernels(a.new)
     d_old, d_new = demangle(list(old)), demangle(list(new))
+    for o, n in (r.split("=", 1) for r in a.rename):
+        d_old = {m: re.sub(rf"\b{re.escape(o)}\b", n, dn) for m, dn in d_old.items()}
     by_name = {}
     for mangled, dn in d_new.items():
         by_name[dn] = mangled

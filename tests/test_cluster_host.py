@@ -101,7 +101,7 @@ def test_header_words():
                  "2g. Single-linkage clusters", "records, not distinct partners", "a mutual pair counts twice", "an entry listed twice counts twice",
                  "ties go to the smaller rank", "two index spaces", '"clusters_last"', '"cluster"', "-INFINITY", "any of the five pointers may be NULL"):
         assert word in header, word
-    kernels = (ROOT / "cuda_selection_criteria_amd" / "csrc" / "kernel_cluster.cuh").read_text()
+    kernels = "".join((ROOT / "cuda_selection_criteria_amd" / "csrc" / name).read_text() for name in ("kernel_graph.cuh", "kernel_cluster.cuh"))
     for word in ("__HIP_MEMORY_SCOPE_AGENT", "__hip_atomic_fetch_min", "__hip_atomic_load", "at most n steps", "No loop waits"):
         assert word in kernels, word
     assert "asm" not in kernels and "cooperative" not in kernels.replace("no cooperative launch", "")
