@@ -7,10 +7,14 @@
 namespace {
 
 // test hook ("cluster_blocks", process-wide: selhip_components has no context): > 0 fixes the grid of cluster_edges_kernel, so that a
-// small list runs the grid-stride loop many times; 0 = sized from the list
-int g_cluster_blocks = 0;
+// small list runs the grid-stride loop many times; 0 = sized from the list.  Atomic (relaxed: the value orders nothing, and the clusters
+// are the same under every grid): one thread may set it through its context while other threads' graph calls read it
+std::atomic<int> g_cluster_blocks{0};
 
-unsigned cluster_edge_grid(u64 n_edges) { return g_cluster_blocks > 0 ? (unsigned)g_cluster_blocks : grid_for(n_edges, kBlock, kClusterMaxBlocks); }
+unsigned cluster_edge_grid(u64 n_edges) {
+    const int blocks = g_cluster_blocks.load(std::memory_order_relaxed);
+    return blocks > 0 ? (unsigned)blocks : grid_for(n_edges, kBlock, kClusterMaxBlocks);
+}
 unsigned cluster_vertex_grid(int64_t n) { return grid_for((u64)n, kBlock, 4096); }
 
 // parent[] initialised (with the tallies the caller wants cleared) and every edge of the list united, on st; nothing is waited for

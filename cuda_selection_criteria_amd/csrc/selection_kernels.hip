@@ -67,6 +67,7 @@
 #include <algorithm>
 #include <type_traits>
 #include <array>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>

@@ -142,6 +142,17 @@ int  selhip_ctx_create(selhip_ctx** out, int device);
 void selhip_ctx_destroy(selhip_ctx* ctx);
 /* message of the last failure on this context (never NULL); ctx may be NULL for creation errors */
 const char* selhip_last_error(const selhip_ctx* ctx);
+/* Host threads.  DIFFERENT contexts may be used from different host threads at the same time, on the same device or on different
+ * ones, and so may the entries that take no context (sections 1, 3, 4, 4b): every context, and every call of a context-free entry,
+ * owns its scratch, its counters and its cached products; nothing of them is shared.  selhip_ooc_select (up to four worker threads on
+ * one device) and selhip_multi_select (one thread per device) rest on this.  ONE context is used by one thread at a time: its calls
+ * are not locked against each other, and the caller orders them (it may hand a context from thread to thread).
+ * selhip_last_error(NULL) is per thread: the message of the last failure of a call made ON THE CALLING THREAD (any context, or none);
+ * selhip_last_error(ctx) is the context's own message, whichever thread reads it.  The one setting that is process-wide is the test
+ * hook "cluster_blocks" of selhip_ctx_set_param: it is set through any context, holds for every graph call of the process (sections 2g, 2h, 2j and their
+ * context-free forms in section 3), may be set while other threads work, and changes no answer.  Calls that free
+ * device memory (below) wait for the whole device and so for the other threads' work; they delay it and do not disturb it.
+ * tests/test_threads_gpu.py runs every entry from several threads at once. */
 
 /* Run all work of this context on `hip_stream` (a hipStream_t passed as void*; NULL = null stream).
  * This holds on a NON-BLOCKING stream (hipStreamNonBlocking, e.g. a torch pool stream), which the null stream does not wait for:
