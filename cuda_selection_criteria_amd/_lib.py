@@ -57,6 +57,10 @@ class Forest(C.Structure):            # selhip_forest_t: the two outputs of selh
     _fields_ = [("d_edges", C.c_void_p), ("d_label", C.c_void_p)]
 
 
+class Linkage(C.Structure):           # selhip_linkage_t: the two outputs of selhip_ctx_linkage, device pointers or NULL
+    _fields_ = [("d_merges", C.c_void_p), ("d_size", C.c_void_p)]
+
+
 class BuildInfo(C.Structure):         # selhip_build_info_t: the plan of selhip_build_sketches_split and what ran
     _fields_ = [("chunk", C.c_int64), ("items", C.c_int64), ("split_genomes", C.c_int64), ("chunks", C.c_int64),
                 ("fallback_genomes", C.c_int64), ("levels", C.c_int32), ("threads", C.c_int32)]
@@ -77,6 +81,7 @@ BANDING_CPU, BANDING_CUDA = 0, 1
 TOPK_ROUNDS_AUTO = -1                  # SELHIP_TOPK_ROUNDS_AUTO: Selector.set_topk_rounds picks the rows per round
 REP_MAX_DEGREE, REP_MIN_RANK, REP_MAX_RANK = 0, 1, 2   # SELHIP_REP_*: the representative of a cluster (Selector.cluster)
 REP_PRIORITY = 3                       # SELHIP_REP_PRIORITY: the caller's scores order the greedy clusters (Selector.cluster_greedy alone)
+LINKAGE_SINGLE, LINKAGE_COMPLETE, LINKAGE_AVERAGE, LINKAGE_WEIGHTED = 0, 1, 2, 3   # SELHIP_LINKAGE_*: the method of Selector.linkage / linkage
 MERGE_SEGMENT = 64                     # SELHIP_MERGE_SEGMENT: member rows one lane of the merge reduces at most (Selector.merge, merge_sketches)
 SPLIT_AUTO, SPLIT_OFF = 0, -1          # SELHIP_SPLIT_*: the chunk argument of selhip_build_sketches_split (else: end positions per chunk)
 SPLIT_CHUNK_MIN = 65536                # the shortest chunk SPLIT_AUTO cuts (64 end positions x 1 024 threads)
@@ -155,6 +160,8 @@ HIP_SYMBOLS = {
     "selhip_greedy_representatives": (_i, [_vp, _i64, _i64, _vp, _vp, C.POINTER(_i64), _vp]),
     "selhip_ctx_spanning_forest": (_i, [_vp, _d, C.POINTER(Forest), C.POINTER(_i64)]),
     "selhip_spanning_forest": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64), _vp]),
+    "selhip_ctx_linkage": (_i, [_vp, _i, _i, _d, C.POINTER(Linkage), C.POINTER(_i64)]),
+    "selhip_linkage": (_i, [_vp, _i64, _i64, _i, _d, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64), _vp]),
     "selhip_ctx_merge_groups": (_i, [_vp, _vp, _i64, C.POINTER(Merged)]),
     "selhip_merge_sketches": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "selhip_smh_a_pairs": (_i, [_vp, _i, _i, _i, _vp, _i64, _vp, _vp]),

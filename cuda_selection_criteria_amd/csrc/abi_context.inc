@@ -256,6 +256,10 @@ int selhip_ctx_get_param(const selhip_ctx* c, const char* name, int* value) {
     if (!std::strcmp(name, "greedy_clusters_last")) { *value = c->greedy_clusters_last; return SELHIP_OK; }  // clusters of the last selhip_ctx_cluster_greedy call, -1 = none yet
     if (!std::strcmp(name, "greedy_rounds_last"))   { *value = c->greedy_rounds_last; return SELHIP_OK; }    // ... and the rounds its selection took
     if (!std::strcmp(name, "forest_rounds_last"))   { *value = c->forest_rounds_last; return SELHIP_OK; }    // rounds of the last selhip_ctx_spanning_forest call, -1 = none yet
+    if (!std::strcmp(name, "linkage_rounds_last"))  { *value = c->linkage_rounds_last; return SELHIP_OK; }   // rounds of the last selhip_ctx_linkage call, -1 = none yet
+    if (!std::strcmp(name, "linkage_merges_last"))  { *value = c->linkage_merges_last; return SELHIP_OK; }   // ... its merges F,
+    if (!std::strcmp(name, "linkage_rowscans_last")) { *value = c->linkage_rowscans_last; return SELHIP_OK; } // ... the rows it scanned
+    if (!std::strcmp(name, "linkage_rescans_last")) { *value = c->linkage_rescans_last; return SELHIP_OK; }  // ... and its rescan rounds
     if (!std::strcmp(name, "forest_edges_last"))    { *value = c->forest_edges_last; return SELHIP_OK; }     // ... and the edges of its forest
     if (!std::strcmp(name, "small_pass_used"))  { *value = c->small_used ? 1 : 0; return SELHIP_OK; }
     if (!std::strcmp(name, "pairs_route_used")) { *value = c->pairs_route_used; return SELHIP_OK; }         // list passes: 1 signature, 0 direct, 2 no smh_a stage, -1 none yet

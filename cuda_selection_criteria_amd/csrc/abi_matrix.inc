@@ -1,4 +1,5 @@
 // abi_matrix.inc -- the C ABI of the dense matrices (include/selection_hip.h section 2f): selhip_ctx_matrix / selhip_ctx_query_matrix.
+// (selhip_ctx_linkage fills its scratch through matrix_call too, under its own timer and name: as_timer, as_what.)
 // One launch of matrix_kernel (kernel_matrix.cuh; the HLL measures) or of a kernel of kernel_matrix_smh.cuh (the SuperMinHash measures)
 // behind the host-side validation of every position; touches none of the passes' state (result list, counters, statistics, top-k,
 // signature cache).
@@ -67,9 +68,9 @@ hipError_t launch_matrix_smh(int dtype, hipStream_t st, const u64* X, const u64*
 }
 
 int matrix_call(selhip_ctx* c, bool query, int measure, int dtype, int64_t r0, int64_t r1, void* out_dev,
-                int64_t out_rows, int64_t out_cols, int64_t ld, const int32_t* row_pos, const int32_t* col_pos) {
+                int64_t out_rows, int64_t out_cols, int64_t ld, const int32_t* row_pos, const int32_t* col_pos, int as_timer = -1, const char* as_what = nullptr) {
     if (!c) return SELHIP_E_BADARG;
-    const char* const what = query ? "selhip_ctx_query_matrix" : "selhip_ctx_matrix";
+    const char* const what = as_what ? as_what : query ? "selhip_ctx_query_matrix" : "selhip_ctx_matrix";
     if (c->pending) { set_err(&c->err, "%s: a pass is still pending (selhip_ctx_finish)", what); return SELHIP_E_STATE; }
     const bool smh = measure == SELHIP_MEASURE_SMH_MATCHES || measure == SELHIP_MEASURE_SMH_JACCARD;
     const bool share = measure == SELHIP_MEASURE_INTERSECTION || measure == SELHIP_MEASURE_CONTAINMENT || measure == SELHIP_MEASURE_MAX_CONTAINMENT;
@@ -123,8 +124,9 @@ int matrix_call(selhip_ctx* c, bool query, int measure, int dtype, int64_t r0, i
         // timed as "matrix_smh", per call of these measures: "matrix" stays the HLL kernel's
         hipError_t e;
         {
-            TimedCall call(c, T_MATRIX_SMH);
-            TimerScope t(c, T_MATRIX_SMH);
+            const int tm = as_timer >= 0 ? as_timer : T_MATRIX_SMH;
+            TimedCall call(c, tm);
+            TimerScope t(c, tm);
             e = launch_matrix_smh(dtype, c->stream, query ? c->q.d_aux : c->d_aux, c->d_aux, c->m, (int)r0, (int)r1, (int)n_y, o, &c->matrix_smh_path_used);
         }
         HIPCHK(&c->err, e);
@@ -138,8 +140,9 @@ int matrix_call(selhip_ctx* c, bool query, int measure, int dtype, int64_t r0, i
     // timed as "matrix", per matrix call: a counter of its own, timed_passes is the passes' (level 2 keeps this kernel's events)
     hipError_t e;
     {
-        TimedCall call(c, T_MATRIX);
-        TimerScope t(c, T_MATRIX);
+        const int tm = as_timer >= 0 ? as_timer : T_MATRIX;
+        TimedCall call(c, tm);
+        TimerScope t(c, tm);
         e = launch_matrix(c->fp_mode == SELHIP_FP_FMA, dtype, c->stream, khi, X, D, (int)r0, (int)r1, (int)n_y, o);
     }
     HIPCHK(&c->err, e);

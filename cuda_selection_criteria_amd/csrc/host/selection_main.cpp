@@ -109,6 +109,16 @@
 //               groups numbered by first appearance, <name> = group_name (not empty, no '/'); a path that is not in the -l list is a
 //               format error with its line number; a genome of the list that the file does not name is in no group.  -c and -a say which
 //               sketch files are in play, as for a pass.  Not with -L, -p, -k, -K or -o
+//   -N <file>   no selection pass (as with -M): the agglomerative hierarchy of the genomes of the -l list, computed on the device from the
+//               dense matrix under the distance 1 - similarity (selhip_ctx_linkage), written to <file> as an ultrametric Newick tree
+//               with the list's paths as leaf names: a node stands at its merge's height, a branch has the length (parent's height -
+//               own height) / 2.  The similarity is that of -M: Jaccard by default, -E smh -a bytes (SuperMinHash), -S max_containment;
+//               not -U, -E smh_matches, -S intersection | containment (no symmetric similarity).  May stand beside -M (both are
+//               written); not with -q, -p, -g, -B, -r, -k, -K, -o, -L, -H, -P, -D or an option of a selection pass
+//   -J <file>   the merges of the same hierarchy, one line each in the order the device emitted them (children before parents):
+//               path_a <TAB> path_b <TAB> height <TAB> size   (the merged cluster lives on under path_a, its smallest rank; the height
+//               printed as std::to_string does).  Alone or beside -N
+//   -X <method> with -N / -J: average (default, UPGMA), complete, weighted (WPGMA) or single
 //   -x          usage
 #include <sys/stat.h>
 #include <unistd.h>
@@ -142,6 +152,7 @@ static std::vector<uint32_t> g_priority;         // ... in rank order, read by l
 static std::string g_merge_dir = "";            // -P: one merged sketch set per group goes into this directory ("" = none)
 static std::string g_groups_file = "";          // -I: the groups of -P, read from this file ("" = the clusters of -L)
 static std::string g_forest_file = "";         // -H: the maximum spanning forest of the pass's result list goes here ("" = none)
+static std::string g_newick_file = "", g_merges_file = "";   // -N, -J: the hierarchy of the dense matrix as a tree / as its merges ("" = none)
 static unsigned g_merge_m = 0, g_merge_p_aux = 0;   // the SuperMinHash buckets and the auxiliary precision in play in the run (0 = none)
 
 // -P: the sketches of the context's set merged by d_group (device, rank order) into n_groups sets named names[], written into g_merge_dir
@@ -513,6 +524,106 @@ static int run_matrix(const std::string& list_file, const std::string& query_fil
     return r ? 4 : hr ? 5 : 0;
 }
 
+// a branch length or height as the shortest of %.15g, %.16g, %.17g that reads back to the same double
+static std::string newick_number(double x) {
+    char buf[64];
+    for (int p = 15; p <= 17; ++p) {
+        std::snprintf(buf, sizeof buf, "%.*g", p, x);
+        if (std::strtod(buf, nullptr) == x) break;
+    }
+    return buf;
+}
+
+// a leaf name: as it is, or in single quotes (a quote doubled) where it is empty or holds a blank or one of ()[]':;,
+static std::string newick_name(const std::string& name) {
+    if (!name.empty() && name.find_first_of(" ()[]':;,\t\n") == std::string::npos) return name;
+    std::string q = "'";
+    for (char ch : name) { q += ch; if (ch == '\'') q += ch; }
+    return q + "'";
+}
+
+// -N / -J: no pass; the hierarchy of the list's dense matrix (selhip_ctx_linkage) as a Newick tree and / or as its merges.
+// measure: a symmetric SELHIP_MEASURE_*; m: the SuperMinHash buckets to load for SMH_JACCARD, 0 for the HLL measures
+static int run_linkage(const std::string& list_file, int measure, int method, unsigned m, int fp_mode, int threads) {
+    selhost_dataset* ds = nullptr;
+    if (selhost_dataset_load(&ds, list_file.c_str(), m, 0, fp_mode, threads)) { std::cerr << "selection: -N / -J: " << selhost_last_error() << "\n"; return 1; }
+    const int64_t n = selhost_dataset_size(ds);
+    const size_t cap = (size_t)std::max<int64_t>(n - 1, 0);
+    std::vector<selhip_pair_t> merges(cap);
+    std::vector<int32_t> sizes(cap);
+    std::vector<uint64_t> no_smh(m ? 0 : (size_t)std::max<int64_t>(1, n), 0);
+    selhip_ctx* ctx = nullptr;
+    int r = selhip_device_count() > 0 ? selhip_ctx_create(&ctx, 0) : SELHIP_E_NODEVICE;
+    if (r) {
+        std::cerr << "selection: no MI355X (gfx950) device available: " << selhip_last_error(nullptr) << "\n";
+        selhost_dataset_free(ds);
+        return 3;
+    }
+    void* d_merges = nullptr;
+    void* d_size = nullptr;
+    int64_t f = 0;
+    selhip_ctx_set_fp_mode(ctx, fp_mode);
+    r = selhip_ctx_upload(ctx, selhost_dataset_hll(ds), m ? selhost_dataset_aux(ds) : no_smh.data(), selhost_dataset_cards(ds), n, m ? (int)m : 1, 14);
+    if (!r && cap) r = selhip_malloc(&d_merges, cap * sizeof(selhip_pair_t));
+    if (!r && cap) r = selhip_malloc(&d_size, cap * sizeof(int32_t));
+    const selhip_linkage_t out{static_cast<selhip_pair_t*>(d_merges), static_cast<int32_t*>(d_size)};
+    if (!r) r = selhip_ctx_linkage(ctx, measure, method, INFINITY, &out, &f);
+    if (!r && f > 0) r = selhip_memcpy_d2h(merges.data(), d_merges, (size_t)f * sizeof(selhip_pair_t));
+    if (!r && f > 0) r = selhip_memcpy_d2h(sizes.data(), d_size, (size_t)f * sizeof(int32_t));
+    if (r) std::cerr << "selection: " << selhip_last_error(ctx) << "\n";
+    selhip_ctx_destroy(ctx);
+    if (d_merges) selhip_free(d_merges);
+    if (d_size) selhip_free(d_size);
+    int hr = 0;
+    if (!r && !g_merges_file.empty()) {
+        std::string text;
+        for (int64_t s = 0; s < f; ++s)
+            text += std::string(selhost_dataset_name(ds, merges[(size_t)s].i)) + "\t" + selhost_dataset_name(ds, merges[(size_t)s].k) + "\t" +
+                    std::to_string(merges[(size_t)s].jaccard) + "\t" + std::to_string(sizes[(size_t)s]) + "\n";
+        std::ofstream o(g_merges_file, std::ios::binary);
+        o << text;
+        o.close();
+        if (!o) { std::cerr << "selection: -J: cannot write '" << g_merges_file << "'\n"; hr = 5; }
+    }
+    if (!r && !hr && !g_newick_file.empty()) {
+        // nodes 0 .. n - 1 the leaves, n + s the cluster merge s made; root_of[slot] = the node that lives in the slot now
+        struct Node { int64_t left, right; double height; };
+        std::vector<Node> node((size_t)n + (size_t)f, Node{-1, -1, 0.0});
+        std::vector<int64_t> root_of((size_t)std::max<int64_t>(n, 1));
+        for (int64_t g = 0; g < n; ++g) root_of[(size_t)g] = g;
+        for (int64_t s = 0; s < f; ++s) {
+            const selhip_pair_t& e = merges[(size_t)s];
+            node[(size_t)(n + s)] = Node{root_of[(size_t)e.i], root_of[(size_t)e.k], e.jaccard};
+            root_of[(size_t)e.i] = n + s;
+        }
+        // written without recursion (a chain is n deep): a stack of nodes to open and of text to emit behind them
+        struct Item { int64_t id; double up; bool has_up; std::string text; };
+        std::string text;
+        std::vector<Item> stack;
+        if (n > 0) stack.push_back(Item{root_of[0], 0.0, false, ""});
+        while (!stack.empty()) {
+            Item it = std::move(stack.back());
+            stack.pop_back();
+            if (it.id < 0) { text += it.text; continue; }
+            const Node& nd = node[(size_t)it.id];
+            const std::string tail = it.has_up ? ":" + newick_number(std::max((it.up - nd.height) / 2.0, 0.0)) : "";
+            if (nd.left < 0) { text += newick_name(selhost_dataset_name(ds, it.id)) + tail; continue; }
+            stack.push_back(Item{-1, 0.0, false, ")" + tail});
+            stack.push_back(Item{nd.right, nd.height, true, ""});
+            stack.push_back(Item{-1, 0.0, false, ","});
+            stack.push_back(Item{nd.left, nd.height, true, ""});
+            text += "(";
+        }
+        text += ";\n";
+        std::ofstream o(g_newick_file, std::ios::binary);
+        o << text;
+        o.close();
+        if (!o) { std::cerr << "selection: -N: cannot write '" << g_newick_file << "'\n"; hr = 5; }
+    }
+    selhost_dataset_free(ds);
+    return r ? 4 : hr;
+}
+
 // -I ... -P: no pass; the genomes of the list merged by the groups of g_groups_file.  m, p_aux: the sketch files in play, as for a pass
 static int run_merge_groups(const std::string& list_file, unsigned m, unsigned p_aux, int fp_mode, int threads) {
     selhost_dataset* ds = nullptr;
@@ -580,8 +691,11 @@ int main(int argc, char* argv[]) {
     bool cluster_given = false, cluster_min_given = false, cluster_rep_given = false, linkage_given = false, priority_given = false;
     std::string linkage_arg = "";
     bool merge_given = false, groups_given = false, forest_given = false;
+    bool newick_given = false, merges_given = false, method_given = false;
+    std::string method_arg = "";
+    int tree_method = SELHIP_LINKAGE_AVERAGE;
     int c;
-    while ((c = getopt(argc, argv, "xl:b:a:h:c:C:G:t:g:nA:F:B:o:r:q:k:K:p:M:UE:S:V:R:DL:T:Y:Z:W:P:I:H:")) != -1) {
+    while ((c = getopt(argc, argv, "xl:b:a:h:c:C:G:t:g:nA:F:B:o:r:q:k:K:p:M:UE:S:V:R:DL:T:Y:Z:W:P:I:H:N:J:X:")) != -1) {
         switch (c) {
             case 'x': std::cout << "Usage: -l -h -a -b [-c smh_a|hll_a|hll_an|none|smh_c -C c_min|-G gamma] [-t threads] [-g gpus] [-n] [-A auto|stream|sig] [-F 0|1] [-B block] [-o file] | -r file\n"
                                    "       -l db_list -q query_list -h -a [-c smh_a|hll_a|hll_an|none|smh_c -C c_min|-G gamma] [-n] [-A auto|stream|sig|index] [-F 0|1] [-k best_per_query]   (query-vs-database selection)\n"
@@ -597,6 +711,7 @@ int main(int argc, char* argv[]) {
                                    "       -l list [-p pair_file | -K best_per_genome [-R rows]] ... -L clusters.tsv [-T min_value] [-Y max_degree|min_rank|max_rank]   (besides the output: the single-linkage clusters of the selected pairs, one line per genome: path, cluster, size, degree, representative)\n"
                                    "       ... -L clusters.tsv -Z single|greedy [-T min_value] [-Y max_degree|min_rank|max_rank | -W scores.tsv]   (-Z greedy: greedy representative clusters, CD-HIT style: genomes visited in the -Y order or by descending score, every other genome to its most similar representative; a sixth column: value to the representative)\n"
                                    "       -l list [-p pair_file | -K best_per_genome [-R rows]] ... -H forest.tsv [-T min_value]   (besides the output: the maximum spanning forest of the selected pairs = the merges of the single-linkage dendrogram, one line per edge, best first: path_a, path_b, value; may stand beside -L)\n"
+                                   "       -l list -N tree.nwk [-J merges.tsv] [-X average|complete|weighted|single] [-E smh -a bytes | -S max_containment] [-M out.tsv]   (no selection: the hierarchy of the dense matrix under 1 - similarity, on the device: a Newick tree and / or one line per merge: path_a, path_b, height, size)\n"
                                    "       ... -c hll_a|hll_an -a bytes -D   (with -l, -q, -p, -k, -K, -g, -B: no .hll_<p> file is read, the auxiliary HLL sketches are folded from the .hll registers)\n"
                                    "       ... -L clusters.tsv [-Z ...] -P dir   (besides the output: one merged sketch set per cluster in dir -- cluster_<id>.hll, .smh<m>, .hll_<p> -- and dir/filelist.txt, a database for -l)\n"
                                    "       -l list [-c ... -a bytes] -I groups.tsv -P dir   (no selection: the genomes merged by the groups of 'path<TAB>group_name' lines, one sketch set per group_name in dir)\n"; return 0;
@@ -616,6 +731,9 @@ int main(int argc, char* argv[]) {
             case 'W': g_priority_file = optarg; priority_given = true; break;
             case 'P': g_merge_dir = optarg; merge_given = true; break;
             case 'H': g_forest_file = optarg; forest_given = true; break;
+            case 'N': g_newick_file = optarg; newick_given = true; break;
+            case 'J': g_merges_file = optarg; merges_given = true; break;
+            case 'X': method_arg = optarg; method_given = true; break;
             case 'I': g_groups_file = optarg; groups_given = true; break;
             case 'k': top_k = std::strtoll(optarg, nullptr, 10); topk_given = true; break;
             case 'K': nbr_k = std::strtoll(optarg, nullptr, 10); nbr_given = true; break;
@@ -636,6 +754,30 @@ int main(int argc, char* argv[]) {
             case 'F': fp_mode = std::stoi(optarg) ? SELHIP_FP_FMA : SELHIP_FP_STRICT; break;
             default: break;
         }
+    }
+    // -N, -J and their -X: checked before any file is read or device opened
+    const bool tree_given = newick_given || merges_given;
+    if (method_given && !tree_given) { std::cerr << "selection: -X (the linkage method) is an option of -N / -J (the hierarchy of the dense matrix)\n"; return 2; }
+    if (tree_given) {
+        const char* clash = !query_file.empty() ? "-q" : !pair_file.empty() ? "-p" : gpus_given ? "-g" : ooc_block != 0 ? "-B" : !dump_file.empty() ? "-r"
+                          : topk_given ? "-k" : nbr_given ? "-K" : !out_file.empty() ? "-o" : cluster_given ? "-L" : forest_given ? "-H" : merge_given ? "-P"
+                          : g_fold_aux ? "-D" : selection_opt;
+        if (clash) {
+            std::cerr << "selection: -N / -J (the hierarchy of the dense matrix) cannot be combined with " << clash
+                      << "; it runs no selection pass, over one list, on one device\n";
+            return 2;
+        }
+        if ((newick_given && g_newick_file.empty()) || (merges_given && g_merges_file.empty())) { std::cerr << "selection: -N / -J need the name of the file to write\n"; return 2; }
+        if (method_given) {
+            tree_method = method_arg == "single" ? SELHIP_LINKAGE_SINGLE : method_arg == "complete" ? SELHIP_LINKAGE_COMPLETE : method_arg == "average" ? SELHIP_LINKAGE_AVERAGE
+                        : method_arg == "weighted" ? SELHIP_LINKAGE_WEIGHTED : -1;
+            if (tree_method < 0) { std::cerr << "selection: -X (the linkage method): average, complete, weighted or single, not '" << method_arg << "'\n"; return 2; }
+        }
+        if (union_measure || (estimator_given && estimator == "smh_matches") || (measure_given && (measure_name == "intersection" || measure_name == "containment"))) {
+            std::cerr << "selection: -N / -J take a symmetric similarity: the default (Jaccard), -E smh or -S max_containment; not -U, -E smh_matches, -S intersection | containment\n";
+            return 2;
+        }
+        if (list_file.empty()) { std::cerr << "selection: -N / -J need the list of genomes (-l)\n"; return 2; }
     }
     // -H and its -T: checked before any file is read or device opened
     if (forest_given) {
@@ -791,7 +933,7 @@ int main(int argc, char* argv[]) {
             std::cerr << "selection: -S (the measure): jaccard or max_containment, with -M also intersection or containment, not '" << measure_name << "'\n";
             return 2;
         }
-        if (matrix_only && !matrix_given) {
+        if (matrix_only && !matrix_given && !tree_given) {
             std::cerr << "selection: -S " << measure_name << " is a measure of -M (the dense similarity matrix); a selection pass takes -S jaccard or -S max_containment\n";
             return 2;
         }
@@ -802,7 +944,7 @@ int main(int argc, char* argv[]) {
             std::cerr << "selection: -S (a measure from the HyperLogLog sketches) cannot be combined with -E " << estimator << "\n";
             return 2;
         }
-        if (!matrix_given && measure_name == "max_containment") {
+        if (!matrix_given && !tree_given && measure_name == "max_containment") {
             pass_measure = SELHIP_MEASURE_MAX_CONTAINMENT;
             if (mode != SELHIP_MODE_SMH) {
                 std::cerr << "selection: -S max_containment needs -n: the CB bound is a bound on J and cuts the pairs of unequal size the measure exists for\n";
@@ -820,9 +962,9 @@ int main(int argc, char* argv[]) {
             }
         }
     }
-    if (matrix_given) {
+    if (matrix_given || tree_given) {
         // checked before any file is read or device opened
-        const char* clash = !pair_file.empty() ? "-p" : topk_given ? "-k" : nbr_given ? "-K" : gpus_given ? "-g" : ooc_block != 0 ? "-B"
+        const char* clash = !matrix_given ? nullptr : !pair_file.empty() ? "-p" : topk_given ? "-k" : nbr_given ? "-K" : gpus_given ? "-g" : ooc_block != 0 ? "-B"
                           : !out_file.empty() ? "-o" : !dump_file.empty() ? "-r" : selection_opt;
         if (clash) {
             std::cerr << "selection: -M (the dense similarity matrix) cannot be combined with " << clash
@@ -845,7 +987,9 @@ int main(int argc, char* argv[]) {
             measure = estimator == "smh" ? SELHIP_MEASURE_SMH_JACCARD : SELHIP_MEASURE_SMH_MATCHES;
             m_smh = (unsigned)aux_bytes / 8;
         }
-        return run_matrix(list_file, query_file, matrix_file, measure, m_smh, fp_mode, threads);
+        int rc = matrix_given ? run_matrix(list_file, query_file, matrix_file, measure, m_smh, fp_mode, threads) : 0;
+        if (!rc && tree_given) rc = run_linkage(list_file, measure, tree_method, m_smh, fp_mode, threads);
+        return rc;
     }
     if (estimator_given) { std::cerr << "selection: -E (hll, smh, smh_matches) is an option of -M (the dense similarity matrix)\n"; return 2; }
     if (union_measure) { std::cerr << "selection: -U (union sizes) is an option of -M (the dense similarity matrix)\n"; return 2; }

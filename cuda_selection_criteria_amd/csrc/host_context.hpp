@@ -160,8 +160,8 @@ static_assert(kCounterBlocks == kMaxChunks + 1, "common.cuh: counter blocks per 
 constexpr int kMaxAuxP = SELHIP_MAX_AUX_P;   // auxiliary HLL precision accepted by every entry point: aux_fused_kernel counts in 16-bit bins (a bin holds up to 2^p_aux)
 constexpr long long kEnumPairs = 1ll << 26;    // hll_a / hll_an as first criterion: pairs listed per sub-pass (512 MiB of int2)
 
-enum { T_PREP = 0, T_STAGE1, T_HIST, T_SELECT, T_TOTAL, T_SIGBUILD, T_JOIN, T_VERIFY, T_AUX, T_GROUP, T_DENSE, T_TOPK, T_MATRIX, T_MATRIX_SMH, T_CLUSTER, T_GREEDY, T_MERGE, T_FOREST, T_COUNT };
-const char* kTimerNames[T_COUNT] = {"prep", "stage1", "hist", "select", "total", "sigbuild", "join", "verify", "aux", "group", "dense", "topk", "matrix", "matrix_smh", "cluster", "greedy", "merge", "forest"};
+enum { T_PREP = 0, T_STAGE1, T_HIST, T_SELECT, T_TOTAL, T_SIGBUILD, T_JOIN, T_VERIFY, T_AUX, T_GROUP, T_DENSE, T_TOPK, T_MATRIX, T_MATRIX_SMH, T_CLUSTER, T_GREEDY, T_MERGE, T_FOREST, T_LINKAGE, T_COUNT };
+const char* kTimerNames[T_COUNT] = {"prep", "stage1", "hist", "select", "total", "sigbuild", "join", "verify", "aux", "group", "dense", "topk", "matrix", "matrix_smh", "cluster", "greedy", "merge", "forest", "linkage"};
 
 }  // namespace
 
@@ -372,6 +372,10 @@ struct selhip_ctx {
     int greedy_rounds_last = -1;        // its rounds ("greedy_rounds_last")
     int forest_rounds_last = -1;        // selhip_ctx_spanning_forest: the rounds of the last call, the empty one included ("forest_rounds_last"), -1 = none yet
     int forest_edges_last = -1;         // its F ("forest_edges_last")
+    int linkage_rounds_last = -1;       // selhip_ctx_linkage: the rounds of the last call, rescan rounds and the empty last one included ("linkage_rounds_last"), -1 = none yet
+    int linkage_merges_last = -1;       // its F ("linkage_merges_last")
+    int linkage_rowscans_last = -1;     // the rows its scan kernel took over all rounds ("linkage_rowscans_last")
+    int linkage_rescans_last = -1;      // its rescan rounds ("linkage_rescans_last")
 
     // sketches merged by group (selhip_ctx_merge_groups; kernel_merge.cuh, host_merge.hpp): scratch the call owns
     MergeScratch mg;
@@ -391,7 +395,7 @@ namespace {
 // a call timed per call under a name of its own (T_MATRIX and the ids behind it): its timer is the dominant one while it runs (level 2 keeps its events), its calls are counted apart from the passes
 struct TimedCall {
     selhip_ctx* c; int before;
-    TimedCall(selhip_ctx* c_, int id) : c(c_), before(c_->dominant_timer) { c->dominant_timer = id; if (c->timing) c->timed_calls[id] += 1; }
+    TimedCall(selhip_ctx* c_, int id, bool count = true) : c(c_), before(c_->dominant_timer) { c->dominant_timer = id; if (c->timing && count) c->timed_calls[id] += 1; }
     ~TimedCall() { c->dominant_timer = before; }
 };
 

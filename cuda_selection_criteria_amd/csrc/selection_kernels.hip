@@ -54,6 +54,8 @@
 //                       order in rounds of one edge and one vertex launch, then every member to its most similar representative
 //   kernel_forest.cuh   maximum spanning forest of a record list, its single-linkage dendrogram: Boruvka rounds of two record launches (best
 //                       value, then smallest pair among the equal), a hook and a flatten launch over the union-find of kernel_graph.cuh
+//   kernel_linkage.cuh  agglomerative hierarchy of a dense f64 distance matrix (single, complete, average, weighted linkage): rounds of
+//                       reciprocal nearest neighbours -- row scans of the dirty rows, ordered pair compaction, Lance-Williams update in place
 //   kernel_merge.cuh    sketches merged by group: a counting sort of the members, then a segmented reduction of the rows (u8 maximum of the
 //                       HLL registers, u64 minimum of the SuperMinHash buckets) in segments of at most SELHIP_MERGE_SEGMENT members per level
 //
@@ -109,6 +111,7 @@
 #include "kernel_cluster.cuh"
 #include "kernel_greedy.cuh"
 #include "kernel_forest.cuh"
+#include "kernel_linkage.cuh"     // (behind kernel_forest.cuh: ClusterBad, ForestEdge)
 #include "kernel_merge.cuh"
 
 #include "host_plan.hpp"         // host decisions that are plain arithmetic: build shape, pass plan, criterion constants, overflow rule
@@ -123,6 +126,7 @@
 #include "host_cluster.hpp"      // single-linkage clusters: grids and launches behind selhip_ctx_cluster / selhip_components
 #include "host_greedy.hpp"       // greedy representative clusters: rounds and launches behind selhip_ctx_cluster_greedy / selhip_greedy_representatives
 #include "host_forest.hpp"       // maximum spanning forest: rounds, sort and launches behind selhip_ctx_spanning_forest / selhip_spanning_forest
+#include "host_linkage.hpp"      // dense-matrix hierarchy: checks, scratch and rounds behind selhip_linkage / selhip_ctx_linkage
 #include "host_merge.hpp"       // sketches merged by group: checks, levels and launches behind selhip_merge_sketches / selhip_ctx_merge_groups
 #include "host_build.hpp"       // split sketch builder: items, launches, the reduction through merge_run, the fallback launch
 #include "abi_context.inc"       // C ABI: context (create, upload / attach, run, results, timing)
@@ -132,6 +136,7 @@
 #include "abi_cluster.inc"       // C ABI: clusters of the result list (cluster) and of a caller's edge list (components)
 #include "abi_greedy.inc"        // C ABI: greedy representative clusters of the result list (cluster_greedy) and of a caller's edge list (greedy_representatives)
 #include "abi_forest.inc"        // C ABI: maximum spanning forest of the result list (ctx_spanning_forest) and of a caller's edge list (spanning_forest)
+#include "abi_linkage.inc"       // C ABI: average / complete / weighted / single linkage of a dense matrix (ctx_linkage, linkage)
 #include "abi_merge.inc"        // C ABI: sketches merged by group (merge_sketches, ctx_merge_groups)
 #include "abi_build.inc"        // C ABI: sketch construction with long genomes split across workgroups (build_sketches_split, build_split_plan)
 #include "abi_blocks.inc"        // C ABI: building blocks, synthetic sketches, sketch construction, memory helpers

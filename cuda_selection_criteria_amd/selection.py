@@ -13,7 +13,7 @@ import numpy as np
 from . import _lib
 from ._lib import (ALGO_AUTO, BANDING_CPU, CRIT_HLL_A, CRIT_HLL_AN, CRIT_HLL_A_SMH_A, CRIT_NONE, CRIT_SMH_A, CRIT_SMH_C, ESTIMATOR_HLL, ESTIMATOR_SMH, F32, F64, FP_FMA,
                    MEASURE_CONTAINMENT, MEASURE_INTERSECTION, MEASURE_JACCARD, MEASURE_MAX_CONTAINMENT, MEASURE_SMH_JACCARD,
-                   MEASURE_SMH_MATCHES, MEASURE_UNION, MODE_CB_SMH, REP_MAX_DEGREE, REP_MAX_RANK, REP_MIN_RANK, REP_PRIORITY, TOPK_ROUNDS_AUTO, Clusters, Forest, Greedy, Merged, Pair, check, hip_lib,
+                   MEASURE_SMH_MATCHES, MEASURE_UNION, MODE_CB_SMH, REP_MAX_DEGREE, REP_MAX_RANK, REP_MIN_RANK, REP_PRIORITY, TOPK_ROUNDS_AUTO, LINKAGE_SINGLE, LINKAGE_COMPLETE, LINKAGE_AVERAGE, LINKAGE_WEIGHTED, Clusters, Forest, Greedy, Linkage, Merged, Pair, check, hip_lib,
                    host_lib)
 
 # layout of selhip_pair_t {int32 i, k; double jaccard}
@@ -607,6 +607,30 @@ class Selector:
         check(self._lib.selhip_ctx_spanning_forest(self._ctx, mv, C.byref(out), C.byref(cnt)), self._ctx)
         return _forest_result(edges, labels, int(cnt.value), self.n, self.get_param("forest_rounds_last"), to_host)
 
+    # -- hierarchy of the dense matrix ------------------------------------------------------------------
+    def linkage(self, measure="jaccard", method="average", max_height: Optional[float] = None, distance=None, to_host: bool = True) -> dict:
+        """the agglomerative hierarchy of the context's set under the distance 1 - measure, computed on the device from the dense
+        matrix (selhip_ctx_linkage): measure "jaccard", "max_containment" or "smh_jaccard" (the symmetric similarities; a NaN cell --
+        two empty sketches -- is distance 1.0), method "single", "complete", "average" (UPGMA) or "weighted" (WPGMA), max_height: no
+        merge above it (None: the whole tree).  distance: a callable applied to the device tensor of Selector.matrix(measure) --
+        `lambda j: -torch.log(2 * j / (1 + j)) / 21` is the Mash distance -- whose result goes to `linkage` in place of 1 - measure
+        (only its strict upper triangle is read; NaN and -inf there raise).  Returns a dict: "merges" [F] PAIR_DTYPE records {i = a <
+        k = b, jaccard = height} in rank indices -- the cluster of a merge lives on as a, the smallest rank among its members --
+        in emitted order (children before parents), "sizes" [F] int32 -- numpy arrays; with to_host=False torch tensors on the device,
+        the merges as uint8 [F, 16] --, "n_merges" = F and "rounds".  linkage_matrix gives SciPy's matrix, linkage_cut the labels at a
+        height (they go into Selector.merge), linkage_newick a tree"""
+        import torch
+        if distance is not None:
+            return linkage(distance(self.matrix(measure)), method, max_height, overwrite=True, device=self.device, to_host=to_host)
+        code, mh = linkage_code(method), _max_height(max_height)
+        dev = torch.device("cuda", self.device)
+        merges = torch.empty((max(self.n - 1, 0), PAIR_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        sizes = torch.empty(max(self.n - 1, 0), dtype=torch.int32, device=dev)
+        out = Linkage(merges.data_ptr() if merges.numel() else None, sizes.data_ptr() if sizes.numel() else None)
+        cnt = C.c_int64()
+        check(self._lib.selhip_ctx_linkage(self._ctx, measure_code(measure), code, mh, C.byref(out), C.byref(cnt)), self._ctx)
+        return _linkage_result(merges, sizes, int(cnt.value), self.get_param("linkage_rounds_last"), to_host)
+
     # -- sketches merged by group ---------------------------------------------------------------------
     def merge(self, groups, n_groups: Optional[int] = None, to_host: bool = False) -> dict:
         """one union sketch per group of the context's set, merged on the device (selhip_ctx_merge_groups): the element-wise maximum of
@@ -1053,6 +1077,196 @@ def forest_table(names: Sequence[str], edges) -> str:
     """the text of `selection -H`: one line per forest edge in the forest's order, 'path_a<TAB>path_b<TAB>value', the value printed as
     format_lines prints J.  names in rank order, edges = Selector.spanning_forest(...)["edges"] on the host"""
     return "".join(f"{names[int(e['i'])]}\t{names[int(e['k'])]}\t{float(e['jaccard']):f}\n" for e in edges)
+
+
+LINKAGES = {"single": LINKAGE_SINGLE, "complete": LINKAGE_COMPLETE, "average": LINKAGE_AVERAGE, "weighted": LINKAGE_WEIGHTED}
+
+
+def linkage_code(method) -> int:
+    """the SELHIP_LINKAGE_* code of a method given by name or by code; ValueError for anything else"""
+    code = LINKAGES.get(method) if isinstance(method, str) else method
+    if isinstance(code, bool) or not isinstance(code, (int, np.integer)) or code not in LINKAGES.values():
+        raise ValueError("method: 'single', 'complete', 'average' or 'weighted'")
+    return int(code)
+
+
+def _max_height(max_height) -> float:
+    mh = float("inf") if max_height is None else float(max_height)
+    if np.isnan(mh):
+        raise ValueError("max_height: a number (None builds the whole hierarchy), not NaN")
+    return mh
+
+
+def _linkage_result(merges, sizes, f: int, rounds: int, to_host: bool) -> dict:
+    """the dict of Selector.linkage / linkage from the device tensors a call filled: their first f entries"""
+    res = {"merges": merges[:f], "sizes": sizes[:f]}
+    if to_host:
+        res = {"merges": np.ascontiguousarray(merges[:f].cpu().numpy()).view(PAIR_DTYPE).reshape(-1), "sizes": sizes[:f].cpu().numpy()}
+    res.update(n_merges=f, rounds=rounds)
+    return res
+
+
+def linkage(dist, method="average", max_height: Optional[float] = None, overwrite: bool = False, device: int = 0, to_host: bool = True) -> dict:
+    """the agglomerative hierarchy of an n x n distance matrix, computed on the device (selhip_linkage): dist a numpy float64 array or
+    a torch float64 tensor (2-D, square, stride(1) == 1; its stride(0) is the leading dimension) of which only the strict upper
+    triangle is read -- a NaN or -inf there raises (SELHIP_E_BADARG), +inf is legal.  The call consumes the matrix it works on: a
+    device tensor is cloned first unless overwrite=True.  method, max_height and the dict: Selector.linkage's"""
+    import torch
+    lib = hip_lib()
+    code, mh = linkage_code(method), _max_height(max_height)
+    dev = torch.device("cuda", device)
+    if hasattr(dist, "data_ptr"):
+        d = dist if dist.is_cuda and overwrite else dist.to(dev, copy=True)
+    else:
+        d = torch.from_numpy(np.ascontiguousarray(dist, dtype=np.float64)).to(dev)
+    assert d.dim() == 2 and d.shape[0] == d.shape[1] and d.dtype == torch.float64, "dist: a square float64 matrix"
+    n = int(d.shape[0])
+    assert n <= 1 or d.stride(1) == 1, "dist: stride(1) must be 1"
+    ld = d.stride(0) if n > 1 else max(n, 1)
+    f, rounds = C.c_int64(-1), C.c_int64(-1)
+    with torch.cuda.device(dev):
+        merges = torch.empty((max(n - 1, 0), PAIR_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        sizes = torch.empty(max(n - 1, 0), dtype=torch.int32, device=dev)
+        check(lib.selhip_linkage(d.data_ptr() if n else None, n, ld, code, mh, merges.data_ptr() if merges.numel() else None,
+                                 sizes.data_ptr() if sizes.numel() else None, C.byref(f), C.byref(rounds),
+                                 C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return _linkage_result(merges, sizes, int(f.value), int(rounds.value), to_host)
+
+
+def _linkage_order(merges) -> list:
+    """the emitted positions of the merges ordered by the key max(own height, children's keys), ties by position: children stay in
+    front of their parents even where rounding makes a parent an ulp lower"""
+    last, key = {}, []
+    for s, e in enumerate(merges):
+        a, b = int(e["i"]), int(e["k"])
+        k = float(e["jaccard"])
+        for c in (last.get(a), last.get(b)):
+            if c is not None and key[c] > k:
+                k = key[c]
+        key.append(k)
+        last[a] = s
+    return sorted(range(len(key)), key=lambda s: (key[s], s))
+
+
+def linkage_matrix(merges, sizes, n: int, fill: Optional[float] = None) -> np.ndarray:
+    """the linkage matrix Z of scipy.cluster.hierarchy (float64 [n - 1, 4]; what fcluster and dendrogram take) from the merges and
+    sizes of Selector.linkage / linkage: row s merges two clusters into the new cluster n + s -- columns: the smaller id, the larger
+    id, the height, the size; an original observation g has the id g.  The rows are ordered by the key max(own height, children's
+    keys), ties by emitted position.  A capped call leaves C > 1 roots: ValueError with fill None; otherwise they are joined in
+    ascending slot order, each to the cluster that holds the smallest one, at height `fill` (as forest_linkage does)"""
+    n = int(n)
+    cid, size = {}, {}
+    z = []
+
+    def join(a, b, h, s):
+        ia, ib = cid.get(a, a), cid.get(b, b)
+        cid[a] = n + len(z)
+        size[a] = s
+        z.append([float(min(ia, ib)), float(max(ia, ib)), float(h), float(s)])
+
+    dead = set()
+    for s in _linkage_order(merges):
+        e = merges[s]
+        join(int(e["i"]), int(e["k"]), float(e["jaccard"]), int(sizes[s]))
+        dead.add(int(e["k"]))
+    roots = [g for g in range(n) if g not in dead]
+    if len(roots) > 1:
+        if fill is None:
+            raise ValueError(f"linkage_matrix: the hierarchy has {len(roots)} roots; give fill, the height at which they are joined")
+        for r in roots[1:]:
+            join(roots[0], r, fill, size.get(roots[0], 1) + size.get(r, 1))
+    return np.array(z, dtype=np.float64).reshape(-1, 4)
+
+
+def linkage_cut(merges, n: int, max_height: float, device: int = 0) -> np.ndarray:
+    """labels [n] int32 (the smallest member) of the clusters of the hierarchy at max_height: the components (on the device,
+    `components`) of the merges with height <= max_height.  They go into Selector.merge as they are"""
+    keep = np.asarray(merges["jaccard"], dtype=np.float64) <= float(max_height)
+    pairs = np.stack([np.asarray(merges["i"])[keep], np.asarray(merges["k"])[keep]], axis=1).astype(np.int32).reshape(-1, 2)
+    return components(pairs, n, device)
+
+
+def _newick_number(x: float) -> str:
+    """the shortest of %.15g, %.16g, %.17g that reads back to the same double (what `selection -N` prints)"""
+    for p in (15, 16, 17):
+        s = "%.*g" % (p, x)
+        if float(s) == x:
+            break
+    return s
+
+
+def _newick_name(name: str) -> str:
+    if name and not any(ch in name for ch in " ()[]':;,\t\n"):
+        return name
+    return "'" + name.replace("'", "''") + "'"
+
+
+def linkage_newick(merges, sizes, names: Sequence[str], fill: Optional[float] = None) -> str:
+    """the hierarchy as an ultrametric Newick tree, one line ending in ';': a node stands at its merge's height (a leaf at 0) and
+    its branch has the length (parent's height - own height) / 2, not below 0; the subtree of a merge's a goes first.  names: the
+    leaves' names in the merges' index space (rank order); a name with a blank or one of ()[]':;, is quoted.  A length is printed as
+    the shortest of %.15g, %.16g, %.17g that reads back to the same double.  A capped hierarchy: fill, as linkage_matrix"""
+    n = len(names)
+    node = {g: (None, None, 0.0, g) for g in range(n)}            # slot -> (left, right, height, leaf)
+    dead = set()
+
+    def join(a, b, h):
+        node[a] = (node[a], node[b], float(h), -1)
+        dead.add(b)
+
+    for e in merges:
+        join(int(e["i"]), int(e["k"]), float(e["jaccard"]))
+    roots = [g for g in range(n) if g not in dead]
+    if len(roots) > 1:
+        if fill is None:
+            raise ValueError(f"linkage_newick: the hierarchy has {len(roots)} roots; give fill, the height at which they are joined")
+        for r in roots[1:]:
+            join(roots[0], r, fill)
+    if n == 0:
+        return ";\n"
+    out, stack = [], [(node[roots[0]], None)]                    # (node, parent's height) or a literal
+    while stack:
+        item = stack.pop()
+        if isinstance(item, str):
+            out.append(item)
+            continue
+        (left, right, h, leaf), up = item
+        tail = "" if up is None else ":" + _newick_number(max((up - h) / 2.0, 0.0))
+        if leaf >= 0:
+            out.append(_newick_name(str(names[leaf])) + tail)
+        else:
+            stack.extend([")" + tail, (right, h), ",", (left, h), "("])
+    return "".join(out) + ";\n"
+
+
+def linkage_table(names: Sequence[str], res: dict) -> str:
+    """the text of `selection -J`: one line per merge in emitted order, 'path_a<TAB>path_b<TAB>height<TAB>size', the height with six
+    decimals as format_lines prints J.  names in rank order, res = Selector.linkage(...) on the host"""
+    return "".join(f"{names[int(e['i'])]}\t{names[int(e['k'])]}\t{float(e['jaccard']):f}\t{int(s)}\n" for e, s in zip(res["merges"], res["sizes"]))
+
+
+def linkage_from_filelist(list_file: str, aux_bytes: int = 0, measure="jaccard", method="average", max_height: Optional[float] = None,
+                          fill: Optional[float] = None, fp_mode: int = FP_FMA, device: int = 0) -> dict:
+    """the hierarchy of the genomes of a file list -- what `selection -l list -N tree.nwk [-J merges.tsv] [-X method]` computes; no pass
+    runs.  The sketches are loaded and sorted as for a selection (the HLL measures read only the .hll files, "smh_jaccard" also the
+    .smh<m> files, m = aux_bytes // 8), Selector.linkage runs in rank order, and the ranks' names are the list's paths.  Returns
+    Selector.linkage's dict on the host plus "names" (rank order), "order" (order[rank] = the genome's line in the list), "table" (the
+    text of -J) and "newick" (the text of -N; None for a capped hierarchy without fill)"""
+    code = measure_code(measure)
+    if code not in (MEASURE_JACCARD, MEASURE_MAX_CONTAINMENT, MEASURE_SMH_JACCARD):
+        raise ValueError("measure of a hierarchy: 'jaccard', 'max_containment' or 'smh_jaccard' (the symmetric similarities)")
+    linkage_code(method)
+    m_smh = _matrix_buckets(measure, aux_bytes)
+    ds = load_dataset(list_file, m_smh, 0, fp_mode)
+    n = len(ds.names)
+    with Selector(device, fp_mode) as sel:
+        sel.upload(ds.hll, ds.aux if m_smh else np.zeros((n, 1), dtype=np.uint64), ds.cards)
+        res = sel.linkage(measure, method, max_height)
+    names = list(ds.names)
+    whole = res["n_merges"] == max(n - 1, 0) or fill is not None
+    res.update(names=names, order=np.asarray(ds.order), table=linkage_table(names, res),
+               newick=linkage_newick(res["merges"], res["sizes"], names, fill) if whole else None)
+    return res
 
 
 def cluster_table(names: Sequence[str], order: np.ndarray, res: dict) -> str:

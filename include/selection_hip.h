@@ -163,7 +163,8 @@ const char* selhip_last_error(const selhip_ctx* ctx);
  * blocked null stream).  What DOES wait for the whole device is a call that frees device memory (hipFree): a pass that outgrows one
  * of its lists and repeats; the first SELHIP_ALGO_INDEX pass behind an upload / attach of the database, whose sort scratch goes away
  * when the index stands; any buffer that grows; and, in section 3, selhip_hll_bitslice, selhip_hll_union_hist_planes,
- * selhip_components, selhip_greedy_representatives and selhip_spanning_forest, whose scratch lives for the call. */
+ * selhip_components, selhip_greedy_representatives, selhip_spanning_forest and selhip_linkage, whose scratch lives for the call
+ * (selhip_ctx_linkage too: its n * n cells of scratch are taken and released in every call). */
 int selhip_ctx_set_stream(selhip_ctx* ctx, void* hip_stream);
 /* Chunk lanes of a pass (smh_a / hll_a+smh_a): the query rows are cut into `chunks` equal-pair chunks and every chunk runs its
  * whole chain (join, verify, [auxiliary criterion], grouping, HLL union histograms, estimate) on one of two internal streams
@@ -261,7 +262,9 @@ int selhip_ctx_set_param(selhip_ctx* ctx, const char* name, int value);
  * "greedy_clusters_last" and "greedy_rounds_last" (the clusters the last selhip_ctx_cluster_greedy call found and the rounds its
  * selection took, section 2h; -1 = none yet),
  * "forest_rounds_last" and "forest_edges_last" (the rounds the last selhip_ctx_spanning_forest call took and the edges F of its
- * forest, section 2j; -1 = none yet) */
+ * forest, section 2j; -1 = none yet),
+ * "linkage_rounds_last", "linkage_merges_last", "linkage_rowscans_last" and "linkage_rescans_last" (the rounds the last
+ * selhip_ctx_linkage call took, its merges F, the rows it scanned and its rescan rounds, section 2k; -1 = none yet) */
 int selhip_ctx_get_param(const selhip_ctx* ctx, const char* name, int* value);
 /* Stage 2 grouping (default on): the pairs that reach the HLL-14 stage are bucketed by query row (counting sort) so
  * that waves running side by side on one XCD share their query row in L2.  0 = off (same kernel, list as produced). */
@@ -519,6 +522,8 @@ int selhip_ctx_set_topk_rounds(selhip_ctx* ctx, int64_t rows);
  * "greedy" is the launches of selhip_ctx_cluster_greedy (section 2h), averaged over the GREEDY CALLS since the last reset, counted apart likewise.
  * "merge" is the launches of selhip_ctx_merge_groups (section 2i), averaged over the MERGE CALLS since the last reset, counted apart likewise.
  * "forest" is the launches of selhip_ctx_spanning_forest (section 2j), averaged over the FOREST CALLS since the last reset, counted apart likewise.
+ * "linkage" is the launches of selhip_ctx_linkage (section 2k: the matrix kernel that fills its scratch, then the rounds), averaged over the
+ * LINKAGE CALLS since the last reset, counted apart likewise; "matrix" and "matrix_smh" do not see that call.
  * selhip_ctx_kernel_launches: launches of that kernel per pass. */
 double selhip_ctx_kernel_ms(const selhip_ctx* ctx, const char* name);
 double selhip_ctx_kernel_launches(const selhip_ctx* ctx, const char* name);
@@ -827,7 +832,8 @@ int selhip_ctx_cluster(selhip_ctx* ctx, double min_value, int rep_rule,
  *     undecided (a list without records: 1; n == 0: 0); "greedy_clusters_last": C; both -1 = none yet.  Timed as "greedy" in
  *     selhip_ctx_kernel_ms: per greedy call, counted apart from the passes as "cluster" is.
  *     Not built: query passes, the host-side lists of selhip_multi_select and selhip_ooc_select (selhip_greedy_representatives takes
- *     any edge list), average or complete linkage, re-clustering of members around new centroids, distinct-partner degrees.
+ *     any edge list), re-clustering of members around new centroids, distinct-partner degrees.  (For average or complete linkage
+ *     see section 2k, over the dense matrix.)
  * --------------------------------------------------------------------------------------------------- */
 #define SELHIP_REP_PRIORITY 3
 typedef struct {
@@ -918,14 +924,70 @@ int selhip_ctx_merge_groups(selhip_ctx* ctx, const int32_t* d_group, int64_t n_g
  *     (F = 0, the identity labels).  get_param "forest_rounds_last": the rounds, the empty one included (a list without records: 1;
  *     n == 0: 0); "forest_edges_last": F; both -1 = none yet.  Timed as "forest" in selhip_ctx_kernel_ms: per forest call, counted
  *     apart from the passes as "cluster" is.
- *     Not built: Newick output, average or complete linkage, query passes, the host-side lists of selhip_multi_select and
+ *     Not built: query passes, the host-side lists of selhip_multi_select and
  *     selhip_ooc_select (selhip_spanning_forest takes any edge list), dropping the records inside one component between the rounds.
+ *     (A Newick tree, and the hierarchy under the other linkages: section 2k.)
  * --------------------------------------------------------------------------------------------------- */
 typedef struct {
     selhip_pair_t* d_edges;  /* [max(n-1,0)]  first F written: {a < b, value}, best first           */
     int32_t*       d_label;  /* [n]  smallest rank of the genome's component                        */
 } selhip_forest_t;           /* caller's device memory; either pointer may be NULL (not written)    */
 int selhip_ctx_spanning_forest(selhip_ctx* ctx, double min_value, const selhip_forest_t* out, int64_t* n_edges_out);
+
+/* ---------------------------------------------------------------------------------------------------
+ * 2k. Agglomerative hierarchy of the DENSE matrix: single, complete, average (UPGMA) and weighted (WPGMA) linkage, on the device.
+ *     2g, 2h and 2j read the sparse record list; this call reads the n x n matrix of section 2f, turned into distances, and gives the
+ *     dendrogram scipy.cluster.hierarchy.linkage gives for it (dRep's primary clustering, a tree from a `mash triangle`).
+ *     THE SCHEME.  All four linkages are reducible -- d(i u j, k) >= min(d(i, k), d(j, k)) -- so every pair of RECIPROCAL NEAREST
+ *     NEIGHBOURS can be merged at once and the dendrogram is the sequential algorithm's.  A round merges many pairs.
+ *     STATE.  D: n x n f64, bit-symmetric; active[s], size[s] per slot s; a cluster lives in the slot of its smallest member; the
+ *     nearest-neighbour cache nn[s], nd[s] and a dirty mark per slot.  At the start every slot is active, of size 1 and dirty.
+ *     INPUT.  Only the strict upper triangle (a < b) is read; it is mirrored into the lower one first and the diagonal is ignored.  A
+ *     NaN or -inf cell there: SELHIP_E_BADARG, the message gives the number of such cells and the indices of one, no output is
+ *     written.  +inf is legal.
+ *     A ROUND.
+ *       1. Scan.  Every active dirty row r: nn[r] = the active slot b != r with the smallest D[r][b] under f64 `<`; equal values,
+ *          -0.0 against +0.0 included, go to the smaller slot; nd[r] = D[r][nn[r]] with its bits.  All dirty marks are cleared.
+ *       2. Pair.  P = {(a, b): a < b, both active, nn[a] == b, nn[b] == a, nd[a] <= max_height}.  P empty and every active row
+ *          scanned in this very round: the call ends.  P empty otherwise (a RESCAN round: caches stale through ties or an ulp of
+ *          rounding): every active row is marked dirty and the next round starts.  At most 2 (n - 1) + 1 rounds.
+ *       3. Update.  LW(x, y, sa, sb) = min(x, y) single | max(x, y) complete | (sa * x + sb * y) / (sa + sb) average |
+ *          0.5 * x + 0.5 * y weighted, in f64 with the sizes as doubles and EVERY product, sum and quotient rounded on its own (no
+ *          fused multiply-add).  For a pair (a, b) of sizes sa, sb and a surviving slot k in no pair: v = LW(D[a][k], D[b][k], sa, sb).
+ *          For two pairs (a, b), (c, d), a < c: v = LW(LW(D[a][c], D[a][d], sc, sd), LW(D[b][c], D[b][d], sc, sd), sa, sb).  v is
+ *          stored at [a][k] and [k][a] (k = c in the second case).  All reads are of the matrix before the round.
+ *       4. Record.  For every pair in ascending a: the merge {i = a, k = b, jaccard = nd[a]} and the size sa + sb are emitted;
+ *          size[a] += size[b], b becomes inactive, a dirty; every active row whose cached nn is an a or a b of the round becomes dirty.
+ *     OUTPUTS, each a pure function of the upper triangle, the method and max_height, bit for bit, whatever order the device worked in:
+ *       d_merges[0 .. F)  the records in round order, ascending a within a round (children before parents): the caller's device
+ *                         memory of max(n - 1, 0) records, 16-byte aligned (SELHIP_E_BADARG otherwise); entries from F on are not written
+ *       d_size[0 .. F)    int32, the members of the cluster each merge made
+ *       *n_merges_out     F <= n - 1; with max_height = INFINITY F = n - 1
+ *     A cut at height h is selhip_components over the merges with value <= h; its labels go into selhip_ctx_merge_groups.
+ *     selhip_ctx_linkage: measure = SELHIP_MEASURE_JACCARD, _MAX_CONTAINMENT or _SMH_JACCARD (the symmetric similarities; any other:
+ *     SELHIP_E_BADARG); method = SELHIP_LINKAGE_*; a NaN max_height: SELHIP_E_BADARG.  The call takes n * n f64 of scratch
+ *     (SELHIP_E_NOMEM if that cannot be had; released before it returns), fills it with the matrix kernels of 2f in rank order, turns
+ *     every cell into the distance 1 - v (a NaN, which two empty sketches give under the HLL measures, into 1.0) and runs the rounds.
+ *     What a matrix call refuses is refused here (p_hll != 14 or no bit planes for the HLL measures, a pending pass), and everything a
+ *     matrix call leaves unchanged is left unchanged.  Timed as "linkage", per linkage call; "matrix" and "matrix_smh" are not touched.
+ *     get_param "linkage_rounds_last" (the rounds, rescan rounds and the empty last one included; n == 1: 1, n == 0: 0),
+ *     "linkage_merges_last" (F), "linkage_rowscans_last" (rows scanned over all rounds), "linkage_rescans_last"; each -1 = none yet.
+ *     HOW (csrc/kernel_linkage.cuh): the dirty rows are a device list; a workgroup per listed row streams it with 16-byte loads and
+ *     reduces (value, slot) in the wave, then across the waves through LDS; one workgroup flags the pairs and compacts them in
+ *     ascending order; one work item per (pair, column) updates in place; one lane per slot books sizes and the next list.  The host
+ *     reads two words per merging round.  No kernel waits for another lane.
+ *     Not built: Ward and centroid linkage, a condensed (triangular) matrix, matrices beyond device memory, query sets, a clusters
+ *     table from the command line (it writes the tree and the merges: selection -N / -J), more than one device.
+ * --------------------------------------------------------------------------------------------------- */
+#define SELHIP_LINKAGE_SINGLE    0
+#define SELHIP_LINKAGE_COMPLETE  1
+#define SELHIP_LINKAGE_AVERAGE   2
+#define SELHIP_LINKAGE_WEIGHTED  3
+typedef struct {
+    selhip_pair_t* d_merges; /* [max(n-1,0)]  first F written: {a < b, height}, in emitted order      */
+    int32_t*       d_size;   /* [max(n-1,0)]  first F written: members of the merged cluster          */
+} selhip_linkage_t;          /* caller's device memory; either pointer may be NULL (not written)    */
+int selhip_ctx_linkage(selhip_ctx* ctx, int measure, int method, double max_height, const selhip_linkage_t* out, int64_t* n_merges_out);
 
 
 /* ---------------------------------------------------------------------------------------------------
@@ -984,6 +1046,15 @@ int selhip_greedy_representatives(const selhip_int2_t* d_pairs, int64_t n_pairs,
 int selhip_spanning_forest(const selhip_int2_t* d_pairs, const double* d_values, int64_t n_pairs, int64_t n,
                            selhip_pair_t* d_edges /* [max(n-1,0)] */, int32_t* d_label /* [n] */, int64_t* n_edges_out, int64_t* rounds_out,
                            void* hip_stream);
+/* The hierarchy of section 2k over a caller's distance matrix d_dist[n][ld] (device memory, f64, 8-byte aligned, ld >= n counted in
+ * elements), which the call works on and CONSUMES: its contents afterwards are unspecified.  With an even ld and a 16-byte aligned
+ * base the row scan takes 16-byte loads, otherwise 8-byte ones; the results are the same.  d_merges (max(n - 1, 0) records, 16-byte
+ * aligned), d_size, *n_merges_out (F) and *rounds_out (the rounds, rescan rounds and the empty last one included; n == 1: 1, n == 0: 0)
+ * are section 2k's; each may be NULL.  SELHIP_E_BADARG: an unknown method, a NaN max_height, n < 0 or > 2^31 - 1, ld < n, a NULL matrix
+ * with n > 1, a misaligned pointer, and a NaN or -inf cell in the strict upper triangle (no output is written).  SELHIP_E_NOMEM: no
+ * room for the per-slot scratch.  The call owns its scratch and waits for the stream. */
+int selhip_linkage(double* d_dist, int64_t n, int64_t ld, int method, double max_height, selhip_pair_t* d_merges /* [max(n-1,0)] */,
+                   int32_t* d_size /* [max(n-1,0)] */, int64_t* n_merges_out, int64_t* rounds_out, void* hip_stream);
 /* Sketches merged by group (section 2i; csrc/kernel_merge.cuh) over a caller's rows: d_hll[n][1 << p] u8, d_smh[n][m] u64 and
  * d_aux_hll[n][1 << p_aux] u8 reduced to n_groups rows each -- maximum, unsigned minimum, maximum -- by d_group[n] (int32, -1 .. n_groups - 1,
  * -1 = in no group; ids in any order); d_size_out[n_groups] (int32, may be NULL) receives the members per group.  A sketch kind is
