@@ -53,7 +53,7 @@ void selhip_ctx_destroy(selhip_ctx* c) {
     c->hj_keys_in.release(); c->hj_keys_out.release(); c->hj_vals_in.release(); c->hj_vals_out.release(); c->hj_tmp.release();
     c->csr_cnt.release(); c->csr_start.release(); c->grouped.release(); c->scan_tmp.release();
     c->planes.release(); c->small_bar.release(); c->mat_row_pos.release(); c->mat_col_pos.release();
-    c->hll_sparse.release(); c->hll_sparse_dev_t.release();
+    c->hll_sparse.release(); c->hll_sparse_dev_t.release(); c->hll_image.release();
     release_queries(c);
     release_topk(c);
     c->gs.release();
@@ -201,6 +201,13 @@ int selhip_ctx_set_param(selhip_ctx* c, const char* name, int value) {
         c->hist_sparse = value;
         return SELHIP_OK;
     }
+    // (not part of the documented interface: 0 = stage 2a reads the six-plane rows even where the set holds a clamped image; -1 and 1 read
+    //  the image wherever it is exact -- with the lists in use at a threshold of 4, 8 or 12; the same counts either way)
+    if (!std::strcmp(name, "hist_image")) {
+        if (value < -1 || value > 1) { set_err(&c->err, "hist_image must be -1 (automatic), 0 (the six-plane rows) or 1 (the clamped image where the set holds one)"); return SELHIP_E_BADARG; }
+        c->hist_image = value;
+        return SELHIP_OK;
+    }
     if (!std::strcmp(name, "dense_fused")) { c->dense_fused = value != 0; return SELHIP_OK; }
     if (!std::strcmp(name, "matrix_mirror")) { c->matrix_mirror = value != 0; return SELHIP_OK; }   // measurement switch: 0 = no mirrored stores
     // (not part of the documented interface: the measurement switch of scripts/bench_matrix_smh.py -- 1 = a self matrix of the SuperMinHash
@@ -241,6 +248,7 @@ int selhip_ctx_get_param(const selhip_ctx* c, const char* name, int* value) {
     if (!std::strcmp(name, "hll_khi"))          { *value = c->planes.khi; return SELHIP_OK; }             // largest p = 14 register value + 1 (0: no bit planes)
     if (!std::strcmp(name, "hist_bitplanes"))   { *value = use_bitslices(c) ? 1 : 0; return SELHIP_OK; }
     if (!std::strcmp(name, "hist_sparse_t"))    { *value = sparse_t_used(c); return SELHIP_OK; }      // threshold of the all-pairs stage 2a's sparse lists, 0 = off
+    if (!std::strcmp(name, "hist_image"))       { *value = c->hist_image_used; return SELHIP_OK; }    // the last all-pairs pass's stage 2a read the clamped image: 1, else 0
     if (!std::strcmp(name, "label_order"))      { *value = label_order(c) ? 1 : 0; return SELHIP_OK; }
     if (!std::strcmp(name, "join_tile_rows"))   { *value = join_tile_rows(c); return SELHIP_OK; }
     if (!std::strcmp(name, "join_form_used"))   { *value = c->join_form_used; return SELHIP_OK; }      // kernel FORM of the last LDS-tile join (3 = bit-sliced)
@@ -443,7 +451,7 @@ static int load_cards(selhip_ctx* c, const char* noun, const uint8_t* d_hll, int
 
 // the products of the sketches the context was just handed: bit planes, sparse lists, cards (host cards were checked by the caller)
 static int after_sketches(selhip_ctx* c, const double* cards_src, bool cards_on_host) {
-    c->planes.khi = 0; c->hll_sparse_t = 0;
+    c->planes.khi = 0; c->hll_sparse_t = 0; c->hll_image_ok = false;
     if (c->n == 0) return SELHIP_OK;
     if (c->p == 14 && c->hist_algo != 0) {
         // the registers once more as bit planes: what stage 2a reads
@@ -452,7 +460,8 @@ static int after_sketches(selhip_ctx* c, const double* cards_src, bool cards_on_
         // the rare high registers once more as sparse lists (512 B per genome), whatever "hist_sparse" is now: it may change before a pass
         HIPCHK(&c->err, c->hll_sparse.ensure((size_t)c->n * kBsSparseCap));
         HIPCHK(&c->err, c->hll_sparse_dev_t.ensure(1));
-        rc = build_sparse_lists(&c->err, c->stream, c->planes.bs.p, c->n, c->hll_sparse.p, c->hll_sparse_dev_t.p, &c->hll_sparse_t);
+        // ... and, where their threshold is 4, 8 or 12, as the clamped image (8 KiB per genome) that stage 2a then reads in place of the planes
+        rc = build_sparse_lists(&c->err, c->stream, c->planes.bs.p, c->n, c->hll_sparse.p, c->hll_sparse_dev_t.p, &c->hll_sparse_t, &c->hll_image, &c->hll_image_ok);
         if (rc) return rc;
     }
     return load_cards(c, "cards", c->d_hll, c->n, cards_src, cards_on_host, c->own_cards, &c->d_cards, true);
@@ -470,7 +479,7 @@ static void set_database(selhip_ctx* c, int64_t n, int m, int p_hll) {
 
 static int no_database(selhip_ctx* c, int rc) {
     c->n = 0; c->d_hll = nullptr; c->d_aux = nullptr; c->d_cards = nullptr; c->owns_sketches = false;
-    c->planes.khi = 0; c->hll_sparse_t = 0;
+    c->planes.khi = 0; c->hll_sparse_t = 0; c->hll_image_ok = false;
     return rc;
 }
 

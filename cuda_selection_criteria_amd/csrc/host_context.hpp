@@ -229,6 +229,13 @@ struct selhip_ctx {
     DevBuf<int> hll_sparse_dev_t;
     int hll_sparse_t = 0;
     int hist_sparse = -1;               // "hist_sparse": -1 automatic (sparse_t_used), 1 = use the lists where the set has them, 0 = every value from the planes
+    // the clamped image of every genome ([n][4][512], min(register, 15) as four planes: kernel_hllbs.cuh), written with the lists where
+    // hll_sparse_t <= kBsImageMaxT (hll_image_ok; every upload / attach clears it and rebuilds the image, a failed one leaves none): what
+    // stage 2a reads in place of the planes wherever it takes the lists at such a threshold
+    DevBuf<uint32_t> hll_image;
+    bool hll_image_ok = false;
+    int hist_image = -1;                // "hist_image": -1 automatic, 1 = the image wherever it is exact (the same today), 0 = the six-plane rows
+    int hist_image_used = 0;            // the last all-pairs pass's stage 2a read the image (get_param "hist_image")
     int hist_algo = -1;                 // -1 automatic (bit planes when p = 14), 0 = byte rows + LDS histogram (hll_union_hist_runs_kernel), 1 = bit planes
     int hist_dense_degree = 32;         // bit-plane kernel: survivors per query row from which a grouped list is walked by candidate slice per XCD (-1 = never)
     int hist_bs_blocks = 2048;          // bit-plane kernel: 4-wave blocks (multiple of 8)

@@ -46,6 +46,7 @@ int enqueue_pairs_pass(selhip_ctx* c) {
     PassCounters* const pc0 = c->pcb;
     if (c->fail_after_flip) { c->fail_after_flip = 0; set_err(&c->err, "test hook: enqueue failed after the counter flip"); return SELHIP_E_HIP; }
     c->small_used = false;
+    c->hist_image_used = 0;
     c->n_chunks_last = 1;
     // the first launch is the all-pairs pass's: truncated cards, the sortedness check, the clearing of the next pass's counters and of
     // the grouping's row counters -- over an EMPTY row range, so that no pair of the triangle is counted as evaluated

@@ -491,10 +491,23 @@ void launch_hist_bs_nb(int g1, unsigned blocks, hipStream_t st, const uint32_t* 
     SELHIP_BS_LAUNCH(0);
 #undef SELHIP_BS_LAUNCH
 }
+// image (with lists, sparse_t <= kBsImageMaxT): the set's clamped image -- the four-plane kernel on its 8 KiB rows, whatever khi is
 hipError_t launch_hist_bs(int khi, unsigned blocks, hipStream_t st, const uint32_t* bs, const uint8_t* gmax, const selhip_int2_t* list, const u64* count,
-                          u64 cap, uint32_t* counts, u64 off, u64 window, int run, u64 dense_pairs, int sparse_t = 0, const uint32_t* lists = nullptr) {
+                          u64 cap, uint32_t* counts, u64 off, u64 window, int run, u64 dense_pairs, int sparse_t = 0, const uint32_t* lists = nullptr,
+                          const uint32_t* image = nullptr) {
     // (a threshold at or above khi leaves every list empty: there the full decode's per-pair walks already stop below it)
     const int g1 = sparse_t > 0 && sparse_t < khi && lists ? sparse_t / 4 : 0;
+    if (image && g1 >= 1 && 4 * g1 <= kBsImageMaxT) {
+#define SELHIP_BS_IMAGE(G1) hipLaunchKernelGGL((hll_union_hist_bs_kernel<kBsImagePlanes, G1, kBsImageDwords>), dim3(blocks), dim3(kBlock), 0, st, image, gmax, lists, \
+                                               list, count, cap, counts, off, window, run, dense_pairs)
+        switch (g1) {
+            case 1:  SELHIP_BS_IMAGE(1); break;
+            case 2:  SELHIP_BS_IMAGE(2); break;
+            default: SELHIP_BS_IMAGE(3);
+        }
+#undef SELHIP_BS_IMAGE
+        return hipGetLastError();
+    }
     switch (bs_planes(khi)) {
         case 4:  launch_hist_bs_nb<4>(g1, blocks, st, bs, gmax, lists, list, count, cap, counts, off, window, run, dense_pairs); break;
         case 5:  launch_hist_bs_nb<5>(g1, blocks, st, bs, gmax, lists, list, count, cap, counts, off, window, run, dense_pairs); break;
@@ -504,9 +517,13 @@ hipError_t launch_hist_bs(int khi, unsigned blocks, hipStream_t st, const uint32
 }
 
 // the sparse lists of n genomes from their planes (kernel_hllbs.cuh); *t = the set's threshold, 0 when it would exceed kBsSparseMaxT
-// (nothing written then).  Waits for the stream.
-int build_sparse_lists(std::string* err, hipStream_t st, const uint32_t* d_bs, int64_t n, uint32_t* d_lists, int* d_t, int* t) {
+// (nothing written then).  image: the set's clamped image, written by the same kernel where the threshold is at most kBsImageMaxT
+// (*image_ok; the threshold is only known here, so the buffer is sized here -- and only ever grown, like every DevBuf: freeing it
+// would make the call wait for the whole device).  Waits for the stream.
+int build_sparse_lists(std::string* err, hipStream_t st, const uint32_t* d_bs, int64_t n, uint32_t* d_lists, int* d_t, int* t, DevBuf<uint32_t>* image,
+                       bool* image_ok) {
     *t = 0;
+    *image_ok = false;
     if (n <= 0) return SELHIP_OK;
     HIPCHK(err, hipMemsetAsync(d_t, 0, sizeof(int), st));
     hipLaunchKernelGGL(hll_sparse_t_kernel, dim3(grid_for((u64)n, kWavesPerBlock, 8192)), dim3(kBlock), 0, st, d_bs, (long long)n, d_t);
@@ -515,25 +532,36 @@ int build_sparse_lists(std::string* err, hipStream_t st, const uint32_t* d_bs, i
     HIPCHK(err, hipMemcpyAsync(&need, d_t, sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(err, hipStreamSynchronize(st));
     if (need < 4 || need > kBsSparseMaxT) return SELHIP_OK;
-    hipLaunchKernelGGL(hll_sparse_list_kernel, dim3(grid_for((u64)n, kWavesPerBlock, 8192)), dim3(kBlock), 0, st, d_bs, (long long)n, need, d_lists);
+    const bool with_image = need <= kBsImageMaxT;
+    if (with_image) HIPCHK(err, image->ensure((size_t)n * kBsImageDwords));
+    hipLaunchKernelGGL(hll_sparse_list_kernel, dim3(grid_for((u64)n, kWavesPerBlock, 8192)), dim3(kBlock), 0, st, d_bs, (long long)n, need, d_lists,
+                       with_image ? image->p : nullptr);
     HIPCHK(err, hipGetLastError());
     HIPCHK(err, hipStreamSynchronize(st));
     *t = need;
+    *image_ok = with_image;
     return SELHIP_OK;
 }
 
 bool use_bitslices(const selhip_ctx* c) { return c->p == 14 && c->planes.khi > 0 && c->hist_algo != 0; }
+// the set holds a clamped image that stage 2a may read with the lists ("hist_image" != 0; the image exists only for thresholds up to kBsImageMaxT)
+bool image_ready(const selhip_ctx* c) { return c->hist_image != 0 && c->hll_image_ok && c->hll_sparse_t >= 4 && c->hll_sparse_t <= kBsImageMaxT; }
 // the all-pairs stage 2a's sparse threshold in use (0 = every value from the planes)
-// Automatic ("hist_sparse" = -1): only where the set's planes fit the Infinity Cache.  Beyond it the kernel is bound by its fetches of
-// candidate rows, not by instructions: cfg4 (50 000 genomes, 600 MB of planes) 144.5 -> 146.8 us, its step 1.502 -> 1.515 ms with the
-// lists (profiles/hist_sparse_ab.txt), while cfg3 and --hard gain 6 % and 23 % a step.
+// Automatic ("hist_sparse" = -1): where the set's planes fit the Infinity Cache, or the lists come with the clamped image.  Beyond the
+// cache the kernel is bound by its fetches of candidate rows, not by instructions, and on the six-plane rows the lists add 512 B to
+// each: cfg4 (50 000 genomes, 600 MB of planes) 144.5 -> 146.8 us, its step 1.502 -> 1.515 ms with them (profiles/hist_sparse_ab.txt).
+// With the image a candidate row is 8.5 KiB where the full decode reads 10, and the sparse form wins there too: cfg4 1.474 -> 1.422 ms
+// a step, cfg5 5.172 -> 5.050 (profiles/hist_image_ab.txt), so the size gate only holds where there is no image (T >= 16, "hist_image" = 0).
 constexpr size_t kSparseMaxPlaneBytes = (size_t)192 << 20;
 int sparse_t_used(const selhip_ctx* c) {
     if (!use_bitslices(c) || !c->hist_sparse || c->hll_sparse_t >= c->planes.khi) return 0;
-    if (c->hist_sparse < 0 && (size_t)c->n * kBsGenomeDwords * sizeof(uint32_t) > kSparseMaxPlaneBytes) return 0;
+    if (c->hist_sparse < 0 && !image_ready(c) && (size_t)c->n * kBsGenomeDwords * sizeof(uint32_t) > kSparseMaxPlaneBytes) return 0;
     if (c->hll_sparse_t > 20 && c->planes.khi <= 32) return 0;                                   // (launch_hist_bs_nb: five planes, G1 = 6)
     return c->hll_sparse_t;
 }
+// ... and whether it reads the image in place of the six-plane rows: wherever it takes the lists and the image is there.  "hist_image"
+// -1 and 1 are the same rule: no size was found at which the shorter rows lose (profiles/hist_image_ab.txt)
+bool image_used(const selhip_ctx* c) { return image_ready(c) && sparse_t_used(c) == c->hll_sparse_t; }
 
 int compute_cards(selhip_ctx* c, const uint8_t* d_hll, int64_t n, int p, double* d_out) {
     if (n <= 0) return SELHIP_OK;
@@ -653,6 +681,7 @@ int enqueue_hist_select(selhip_ctx* c, const Chain& ch, const selhip_int2_t* fin
     for (u64 off = 0; off < final_cap; off += ch.window) {
         {
             TimerScope t(c, T_HIST, st);
+            if (use_bitslices(c)) c->hist_image_used = image_used(c) ? 1 : 0;
             if (use_bitslices(c))
                 HIPCHK(&c->err, launch_hist_bs(c->planes.khi, (unsigned)c->hist_bs_blocks, st, c->planes.bs.p, c->planes.gmax.p, final_list, final_count, final_cap, ch.counts, off, ch.window,
                                                c->hist_run > 0 ? c->hist_run : (grouped ? 4 : 1),
@@ -661,7 +690,7 @@ int enqueue_hist_select(selhip_ctx* c, const Chain& ch, const selhip_int2_t* fin
                                                //  its share of the pairs and all of the candidate rows)
                                                grouped && c->hist_dense_degree >= 0
                                                    ? (u64)c->hist_dense_degree * (u64)std::max<long long>(1, ((long long)ch.re - ch.rb) / std::max(1, c->il_parts)) : ~0ull,
-                                               sparse_t_used(c), c->hll_sparse.p));
+                                               sparse_t_used(c), c->hll_sparse.p, image_used(c) ? c->hll_image.p : nullptr));
             else if (c->p == 14)
                 hipLaunchKernelGGL(hll_union_hist_runs_kernel, dim3(c->hist_blocks), dim3(kWave), (size_t)c->hist_pad, st,
                                    c->d_hll, final_list, final_count, final_cap, ch.counts, off, ch.window,
@@ -907,6 +936,7 @@ int enqueue_pass(selhip_ctx* c) {
     PassCounters* pc0 = c->pcb;
     if (c->fail_after_flip) { c->fail_after_flip = 0; set_err(&c->err, "test hook: enqueue failed after the counter flip"); return SELHIP_E_HIP; }
     c->small_used = small_pass_ok(c);
+    c->hist_image_used = 0;                         // (enqueue_hist_select says otherwise)
     if (c->small_used) {
         c->n_chunks_last = 1;
         const int rc = enqueue_small_pass(c, pc_next, tau);

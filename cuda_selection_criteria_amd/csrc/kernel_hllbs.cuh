@@ -23,6 +23,9 @@ namespace {
 constexpr int kBsPlanes = 6;                                    // register values are < 64 (6 bits)
 constexpr int kBsPlaneDwords = 512;                             // 16 384 registers / 32
 constexpr int kBsGenomeDwords = kBsPlanes * kBsPlaneDwords;     // 12 KiB per genome
+constexpr int kBsImagePlanes = 4;                               // the clamped image of a set with sparse lists (below): values 0..15
+constexpr int kBsImageDwords = kBsImagePlanes * kBsPlaneDwords; // 8 KiB per genome, rows packed at that pitch
+constexpr int kBsImageMaxT = 12;                                // thresholds up to which the image is exact
 
 // hll_bitslice_kernel: one wave per genome.  Register r = 4 * ((8 o + jj) * 64 + lane) + s  (byte s of the dword the lane
 // loads in step 8 o + jj) becomes bit 8 s + jj of dword o * 64 + lane of every plane: which bit a register lands on is
@@ -114,8 +117,13 @@ void hll_sparse_t_kernel(const uint32_t* __restrict__ bs, long long n, int* __re
 
 // hll_sparse_list_kernel: one wave per genome, its registers >= t (a multiple of 4 in [4, kBsSparseMaxT]) in ascending r', read from
 // the planes 64 dwords at a time: each lane's count, a wave prefix sum for the offsets, the lane's entries in bit order.
+// image (t <= kBsImageMaxT; else null): the genome's CLAMPED IMAGE, written from the same plane dwords -- the four planes of
+// a' = min(a, 15), i.e. plane b < 4 = p[b] | p[4] | p[5], same bit placement, rows of kBsImageDwords.  max(a', b') = min(max(a, b), 15), so
+// for T <= 12 the union's value is below T in the image exactly where it is in the full planes, and is then the same value: the
+// decode of the groups below T reads four planes whatever the set's largest register is, and every value >= T comes from the lists.
+// (Not for T >= 16: a 15 and a 16 would both read 15, and 15 is then below T.)
 __global__ __launch_bounds__(kBlock)
-void hll_sparse_list_kernel(const uint32_t* __restrict__ bs, long long n, int t, uint32_t* __restrict__ lists) {
+void hll_sparse_list_kernel(const uint32_t* __restrict__ bs, long long n, int t, uint32_t* __restrict__ lists, uint32_t* __restrict__ image) {
     const int lane = threadIdx.x & (kWave - 1);
     for (long long g = (long long)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave; g < n; g += (long long)gridDim.x * kWavesPerBlock) {
         const uint32_t* src = bs + g * kBsGenomeDwords;
@@ -127,6 +135,11 @@ void hll_sparse_list_kernel(const uint32_t* __restrict__ bs, long long n, int t,
             uint32_t p[kBsPlanes];
 #pragma unroll
             for (int b = 0; b < kBsPlanes; ++b) p[b] = src[b * kBsPlaneDwords + d];
+            if (image) {
+                const uint32_t top = p[4] | p[5];
+#pragma unroll
+                for (int b = 0; b < kBsImagePlanes; ++b) image[g * kBsImageDwords + b * kBsPlaneDwords + d] = p[b] | top;
+            }
             uint32_t h = bs_ge4k(p, t >> 2);
             const int cnt = __popc(h);
             int incl = cnt;
@@ -152,10 +165,12 @@ void hll_sparse_list_kernel(const uint32_t* __restrict__ bs, long long n, int t,
     }
 }
 
-// the lane's 8 dwords of each of the NB low planes of genome g (two 16-byte loads per plane, 1 KiB per wave instruction)
-template <int NB>
+// the lane's 8 dwords of each of the NB low planes of genome g (two 16-byte loads per plane, 1 KiB per wave instruction); PITCH = dwords
+// from one genome's row to the next (kBsGenomeDwords: the six-plane rows, kBsImageDwords: the clamped image)
+template <int NB, int PITCH = kBsGenomeDwords>
 __device__ __forceinline__ void bs_load(const uint32_t* __restrict__ bs, int g, int lane, uint32_t (&r)[NB][8]) {
-    const uint4* p = reinterpret_cast<const uint4*>(bs + (size_t)g * kBsGenomeDwords);
+    static_assert(NB * kBsPlaneDwords <= PITCH, "a row holds the planes read");
+    const uint4* p = reinterpret_cast<const uint4*>(bs + (size_t)g * PITCH);
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
         const uint4 lo = p[b * (kBsPlaneDwords / 4) + lane], hi = p[b * (kBsPlaneDwords / 4) + kWave + lane];
@@ -392,8 +407,10 @@ __device__ __forceinline__ void bs_sparse_entry(BsSparseLds* sp, uint32_t e) {
 // G1 = 0: how many values are decoded is decided PER PAIR from the two rows' largest register values (gmax, written with the planes).
 // G1 > 0 (the set's sparse threshold T = 4 G1, `lists` its sparse lists): the groups [0, G1) are decoded bit-parallel, in one walk,
 // and every value >= T comes from the lists (bs_sparse_row / bs_sparse_entry); gmax is not read.
+// PITCH = dwords per row of `bs`: kBsGenomeDwords, or kBsImageDwords where `bs` is the set's clamped image (NB = 4, G1 <= 3, whatever the
+// set's largest register: hll_sparse_list_kernel).
 // One wave per pair: a lane owns 8 dwords (256 registers) of every plane; the query row's planes stay in registers across a run.
-template <int NB, int G1>
+template <int NB, int G1, int PITCH = kBsGenomeDwords>
 __global__ __launch_bounds__(kBlock, NB <= 5 ? 4 : 2)
 void hll_union_hist_bs_kernel(const uint32_t* __restrict__ bs, const uint8_t* __restrict__ gmax, const uint32_t* __restrict__ lists,
                               const selhip_int2_t* __restrict__ pairs, const u64* __restrict__ n_pairs_dev, u64 cap, uint32_t* __restrict__ counts,
@@ -462,15 +479,15 @@ void hll_union_hist_bs_kernel(const uint32_t* __restrict__ bs, const uint8_t* __
             mine &= mine - 1;
             const int px = __builtin_amdgcn_readlane(pr.x, src), py = __builtin_amdgcn_readlane(pr.y, src);   // wave-uniform: scalar row addresses
             uint32_t yb[NB][8];
-            bs_load<NB>(bs, py, lane, yb);
+            bs_load<NB, PITCH>(bs, py, lane, yb);
             if constexpr (G1 == 0) {
-                if (px != cur_x) { bs_load<NB>(bs, px, lane, xa); cur_x = px; }
+                if (px != cur_x) { bs_load<NB, PITCH>(bs, px, lane, xa); cur_x = px; }
                 const int kp = max((int)gmax[px], (int)gmax[py]) + 1;     // values this pair can hold: [0, kp)
                 const uint32_t tot = bs_pair_hist<NB>(xa, yb, kp, lane);
                 counts[(j0 + src) * 64 + my_bin] = (lane & 1) ? (tot >> 16) : (tot & 0xFFFFu);
             } else {
                 const uint32_t eb0 = lists[(size_t)py * kBsSparseCap + lane], eb1 = lists[(size_t)py * kBsSparseCap + kWave + lane];
-                if (px != cur_x) { bs_load<NB>(bs, px, lane, xa); hA = bs_sparse_row(sp, lists, px, lane, my_bin); cur_x = px; }
+                if (px != cur_x) { bs_load<NB, PITCH>(bs, px, lane, xa); hA = bs_sparse_row(sp, lists, px, lane, my_bin); cur_x = px; }
                 uint32_t P[16];
 #pragma unroll
                 for (int v = 0; v < 16; ++v) P[v] = 0u;
@@ -496,7 +513,18 @@ void hll_union_hist_bs_kernel(const uint32_t* __restrict__ bs, const uint8_t* __
 // the parity suite.  It changed nothing: cfg3 53.7 -> 56.6 us, hard 0.874 -> 0.878 ms, cfg4 / cfg5 equal (gpurun_out/r03/g_pf*).  The PMC
 // pass says why (profiles/r03b_pmc_summary.json): the vector units are ACTIVE for 0.71 of the kernel at cfg3 and 0.83 on the hard set --
 // ~4.1 cycles per instruction: in this mix of dependent chains the boolean instructions do not reach the 2.2 cycles they show alone --
-// so the waves are not waiting for memory, they are waiting for each other's arithmetic.  Dropped; what is left to gain here is
-// instruction count.)
+// so the waves are not waiting for memory, they are waiting for each other's arithmetic.  Dropped.)
+//
+// What bounds the sparse form <NB, 3> (profiles/hist_image_ab.txt, cfg3: 45 000 pairs, T = 12).  Not vector issue alone: 17.5 M
+// wave-instructions (SQ_INSTS_VALU; 389 a pair) on 1 024 SIMDs in 37.8 us is ~5 cycles per instruction, the units ~60 % busy.  Not bytes
+// through the CU alone either: the clamped image takes a fifth of the plane bytes away -- the L2 read requests fall to 0.79 (5.33 M ->
+// 4.19 M, TCP_TCC_READ_REQ_sum), 16 boolean instructions and 16 VGPRs per pair go with the fifth plane (118 -> 102 VGPRs, still 4 waves
+// per SIMD; 5 would spill) -- and the kernel goes from 37.8 to 34.4 us, 9 %, where the bytes fell by 19 %.  The same set clamped at 15 on
+// the six-plane rows had predicted 39.5 -> 36.7 us.  The dense walk of the 25 %-degenerate set, 730 000 pairs whose candidate rows come
+// from one L2, gains the same share (533 -> 489 us), and beyond the Infinity Cache the shorter rows turn the lists from a loss into a
+// gain (host_pass.hpp, sparse_t_used).  So each pair is a chain -- pair record, rows, decode, list entries through LDS, store -- of which
+// the row fetch is one link among several, with four waves per SIMD to hide it; the run length makes no difference (1 / 2 / 4 / 8
+// within the spread).  Sharing a candidate row among the waves of a block through LDS would take most of the remaining row traffic
+// out of L2; not built.
 
 }  // namespace

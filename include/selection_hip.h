@@ -218,7 +218,8 @@ int selhip_ctx_set_candidate_begin(selhip_ctx* ctx, int64_t k_min);
  *   "hist_sparse" 1: the all-pairs bit-plane kernel decodes only the values below the set's sparse threshold T from the planes and
  *                 takes every register >= T from sorted per-genome lists written with the planes (T = the smallest multiple of 4 at which
  *                 every genome holds at most 128 such registers; none above 24); 0: every value from the planes; -1 (default): 1 for sets
- *                 whose bit planes take at most 192 MiB (beyond, stage 2a is bound by its row fetches), else 0.  Same counts either way;
+ *                 whose bit planes take at most 192 MiB, and for larger ones where T <= 12 (stage 2a then reads a four-plane image of
+ *                 min(register, 15), 8 KiB per genome, written with the lists), else 0.  Same counts either way;
  *                 selhip_ctx_get_param "hist_sparse_t" reports the T in use (0 = off).  Query passes and the one-launch small pass
  *                 always decode every value from the planes;
  *   "small_pass"  -1 (default) / 1: a set of up to 2 048 genomes with criterion smh_a takes its whole pass in ONE launch
