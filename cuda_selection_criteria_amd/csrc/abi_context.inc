@@ -567,6 +567,7 @@ int selhip_ctx_run_async(selhip_ctx* c, int mode, int algo, float tau_f, int n_r
     c->row_begin = row_begin; c->row_end = row_end;
     c->have_run = false; c->last_was_query = false; c->topk_applied = false; c->topk_n = 0; c->list_pass = false;
     c->rd = selhip_ctx::Rounds{}; c->rounds_used = 0; c->rounds_admitted = 0;
+    c->hist_image_used = 0;                         // (a pass that launches nothing read no image: not the pass before's report)
     std::memset(&c->last, 0, sizeof c->last);
     if (c->n == 0 || row_begin == row_end) { c->pending = false; c->have_run = true; c->topk_applied = c->allpairs_topk > 0; return SELHIP_OK; }
     if (c->topk_rounds != 0) {

@@ -971,6 +971,12 @@ int selhip_ctx_spanning_forest(selhip_ctx* ctx, double min_value, const selhip_f
  *     every cell into the distance 1 - v (a NaN, which two empty sketches give under the HLL measures, into 1.0) and runs the rounds.
  *     What a matrix call refuses is refused here (p_hll != 14 or no bit planes for the HLL measures, a pending pass), and everything a
  *     matrix call leaves unchanged is left unchanged.  Timed as "linkage", per linkage call; "matrix" and "matrix_smh" are not touched.
+ *     STREAM.  Every launch and copy of the call -- the matrix kernels, the distance kernel, each round's kernels, the small copies
+ *     the host reads between the rounds, the copies into `out` -- runs on the context's stream (selhip_ctx_set_stream), in stream
+ *     order behind whatever the caller put there: `out` may have been written on that stream right before the call.  The host waits
+ *     for the stream after the matrix and twice per merging round, and the call returns when the outputs are complete: they may then
+ *     be read from any stream.  Its scratch is taken and released inside the call, and releasing device memory waits for the whole
+ *     device (see selhip_ctx_set_stream).
  *     get_param "linkage_rounds_last" (the rounds, rescan rounds and the empty last one included; n == 1: 1, n == 0: 0),
  *     "linkage_merges_last" (F), "linkage_rowscans_last" (rows scanned over all rounds), "linkage_rescans_last"; each -1 = none yet.
  *     HOW (csrc/kernel_linkage.cuh): the dirty rows are a device list; a workgroup per listed row streams it with 16-byte loads and
@@ -1053,7 +1059,10 @@ int selhip_spanning_forest(const selhip_int2_t* d_pairs, const double* d_values,
  * aligned), d_size, *n_merges_out (F) and *rounds_out (the rounds, rescan rounds and the empty last one included; n == 1: 1, n == 0: 0)
  * are section 2k's; each may be NULL.  SELHIP_E_BADARG: an unknown method, a NaN max_height, n < 0 or > 2^31 - 1, ld < n, a NULL matrix
  * with n > 1, a misaligned pointer, and a NaN or -inf cell in the strict upper triangle (no output is written).  SELHIP_E_NOMEM: no
- * room for the per-slot scratch.  The call owns its scratch and waits for the stream. */
+ * room for the per-slot scratch.  The call owns its scratch and waits for the stream: every launch and copy runs on hip_stream, in
+ * stream order -- the matrix and the outputs may have been written on that stream right before the call, and are read and overwritten
+ * behind those writes --, the host waits for the stream twice per merging round, and the call returns when the outputs are complete
+ * (they may then be read from any stream).  Releasing the scratch at the end waits for the whole device. */
 int selhip_linkage(double* d_dist, int64_t n, int64_t ld, int method, double max_height, selhip_pair_t* d_merges /* [max(n-1,0)] */,
                    int32_t* d_size /* [max(n-1,0)] */, int64_t* n_merges_out, int64_t* rounds_out, void* hip_stream);
 /* Sketches merged by group (section 2i; csrc/kernel_merge.cuh) over a caller's rows: d_hll[n][1 << p] u8, d_smh[n][m] u64 and

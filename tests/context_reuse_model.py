@@ -134,6 +134,13 @@ class Set(H.Sets):
     def sparse_t(self):
         return bitplane_model.sparse_t(self.D.hll, bitplane_model.khi(self.D.hll)) if self.p_hll == 14 and self.n_d else 0
 
+    def hist_image(self, knobs):
+        """what get_param("hist_image") says behind an all-pairs smh_a pass of the set that went through stage 2a: 1 where the set holds
+        the clamped four-plane image -- its sparse threshold is 4, 8 or 12 -- and the knobs let the pass read it ("hist_image" and
+        "hist_sparse" not 0, bit planes kept), else 0.  knobs: the context's, {name: value}; a knob that is not there is automatic"""
+        allowed = all(knobs.get(k, -1) != 0 for k in ("hist_image", "hist_sparse", "hist_algo"))
+        return int(allowed and self.sparse_t in (4, 8, 12))
+
 
 # operation -> (the attribute of Set that is its expected value, kind): "list" = all-pairs or pair-list records, "qlist" = query records,
 # "matrix", "value".  One per entry of stream_harness.CONTEXT_CASES but the stream-specific ones (NOT_HERE), plus the three below the line
@@ -148,9 +155,12 @@ for _k in NOT_HERE:
 for _k in ("query-sig", "query-stream", "query-index", "query-topk"):
     OPS[_k] = (OPS[_k][0], "qlist")
 OPS.update({"merge_groups": ("merged", "value"), "cards": ("cards", "value")})    # ("fold_aux_hll, then hll_a" is hll_a-folded)
+# (the linkage of an HLL measure is refused as its matrix is; the one over smh_jaccard reads the bucket rows alone and always runs)
+LINKAGE_OPS = tuple(H.LINKAGE_CASES)
+HLL_LINKAGES = {k for k, v in H.LINKAGE_CASES.items() if v[0] != "smh_jaccard"}
 P14_ONLY = {"none-list_route", "none-fused", "matrix-jaccard", "query-sig", "query-stream", "query-index", "query-topk",
-            "query_matrix-containment"}
-NEEDS_PLANES = {"none-list_route", "none-fused", "matrix-jaccard", "query_matrix-containment"}
+            "query_matrix-containment"} | HLL_LINKAGES
+NEEDS_PLANES = {"none-list_route", "none-fused", "matrix-jaccard", "query_matrix-containment"} | HLL_LINKAGES
 QUERY_OPS = {k for k, v in OPS.items() if v[1] == "qlist"} | {"query_matrix-containment"}
 
 
@@ -185,6 +195,10 @@ def expected(S, op, bit_planes=True):
             res = greedy_model.clusters(EMPTY_REC, n, rule="priority", priority=S.prio.astype(np.int64))
             res.pop("rounds_bound")
             return res
+        if op == "forest":
+            return {"edges": EMPTY_REC, "labels": np.arange(n, dtype=np.int32)}
+        if op in H.LINKAGE_CASES:                                 # (no launch: one slot is scanned once and has no neighbour)
+            return {"merges": EMPTY_REC, "sizes": np.zeros(0, dtype=np.int32), "rounds": n}
     return getattr(S, attr)
 
 
@@ -206,7 +220,8 @@ def leaves(value):
 # ---- the sets -----------------------------------------------------------------------------------------------------------------------
 NAMES = ("BIG", "PREFIX", "NARROW", "WIDE", "LOWP", "HIGHREG", "EMPTY", "ONE", "TRIMMED")
 TRANSITIONS = (("BIG", "PREFIX"), ("PREFIX", "BIG"), ("BIG", "NARROW"), ("NARROW", "WIDE"), ("BIG", "LOWP"), ("LOWP", "BIG"),
-               ("HIGHREG", "BIG"), ("BIG", "HIGHREG"), ("BIG", "EMPTY", "PREFIX"), ("BIG", "ONE", "BIG"), ("BIG", "TRIMMED"))
+               ("HIGHREG", "BIG"), ("BIG", "HIGHREG"), ("BIG", "EMPTY", "PREFIX"), ("BIG", "ONE", "BIG"), ("BIG", "TRIMMED"),
+               ("BIG", "HIGHREG", "BIG"))              # (the clamped image on, off -- HIGHREG's threshold is 16 --, and on again)
 # (X, Y, operation) -> reason: the steps X -> Y on which an operation's expected values may be EQUAL, so that the step cannot tell a stale
 # answer from the right one.  No operation may stand here for more than two steps (tests/test_context_reuse_host.py)
 SAME_ANSWER = {}

@@ -24,7 +24,12 @@ race.  Nothing here waits for luck -- every case is arranged so that a wrong str
             instead; afterwards `torch.cuda.default_stream().query()` must still be false -- a synchronous null-stream copy or a
             device-wide wait (hipFree, hipDeviceSynchronize) inside a warmed call ends the delay first.
 
+            The hierarchy entries that free their scratch before they return (ANSWER_UNDER_BLOCKED_NULL) get this run for the answer
+            alone, under a fixed delay that their hipFree waits out.
+
 The delays only size things (each at most 2 s): the conditions are the query() assertions and the answers.
+The linkage cases' expected values take 0.3 s of model time per set at the most (the SuperMinHash case under single linkage, 300 rounds
+of one pair on its plateau), so that case stays single linkage.
 Expected values come from what the suite trusts already: the oracle, tests/*_model.py, numpy."""
 import functools
 import tempfile
@@ -40,7 +45,9 @@ from cuda_selection_criteria_amd import FP_FMA, PAIR_DTYPE, SynthConfig
 import cluster_model
 import containment_model
 import fold_model
+import forest_model
 import greedy_model
+import linkage_model
 import smhv_model
 import topk_rounds_model
 import smh_matrix_model
@@ -74,6 +81,21 @@ def records(pairs):
 
 def by_ik(rec):
     return rec[np.lexsort((rec["k"], rec["i"]))]
+
+
+def distance_of(similarity):
+    """the distance matrix selhip_ctx_linkage builds from a similarity matrix: 1 - v in float64, a NaN cell (two empty sketches) 1.0"""
+    d = 1.0 - np.asarray(similarity, dtype=np.float64)
+    d[np.isnan(d)] = 1.0
+    return d
+
+
+# the context cases of selhip_ctx_linkage: id -> (measure, method, capped at Sets.linkage_cap)
+LINKAGE_CASES = {"linkage-average-jaccard": ("jaccard", "average", False), "linkage-single-smh_jaccard": ("smh_jaccard", "single", False),
+                 "linkage-complete-max_containment-capped": ("max_containment", "complete", True)}
+# the layouts selhip_linkage is handed its matrix in: tag -> (ld - n, offset of the base behind a 16-byte boundary in doubles).  An even ld
+# on a 16-byte base takes lk_scan_kernel<true> (16-byte loads), anything else lk_scan_kernel<false>
+LINKAGE_LAYOUTS = {"wide": (0, 0), "narrow": (3, 1)}
 
 
 class Sets:
@@ -228,6 +250,52 @@ class Sets:
         out[np.ix_(self.row_pos, self.col_pos)] = V
         return out
 
+    @functools.cached_property
+    def matrix_smh_jaccard(self):
+        """the bucket-match counts / m in float64 (smh_matrix_model.expected): of the rows matrix_smh_matches counts"""
+        return self.matrix_smh_matches / np.float64(self.m)
+
+    @functools.cached_property
+    def matrix_max_containment(self):
+        """I / min(e_row, e_col) of every pair from the oracle's union estimates (containment_model), 1.0 on the diagonal"""
+        U = containment_model.union_matrix(self.oracle, self.D.hll, self.D.hll, symmetric=True)
+        return containment_model.matrix_model(U, self.D.cards, self.D.cards, "max_containment", True)
+
+    # -- hierarchies ----------------------------------------------------------------------------------
+    @functools.cached_property
+    def forest(self):
+        """the maximum spanning forest of the smh_a pass's records: forest_model.kruskal, the definition"""
+        edges, labels = forest_model.kruskal(forest_model.records_of_pass(self.smh_a), self.n_d)
+        return {"edges": forest_model.as_records(edges), "labels": np.asarray(labels, dtype=np.int32)}
+
+    def _linkage(self, similarity, method, max_height=np.inf):
+        """{"merges", "sizes", "rounds"} of linkage_model on the distance selhip_ctx_linkage derives: 1 - v, a NaN cell 1.0"""
+        res = linkage_model.linkage_model(distance_of(similarity), method, max_height)
+        return {"merges": res["merges"], "sizes": res["sizes"], "rounds": res["rounds"]}
+
+    @functools.cached_property
+    def linkage_average_jaccard(self):
+        return self._linkage(self.matrix_jaccard, "average")
+
+    @functools.cached_property
+    def linkage_single_smh_jaccard(self):
+        return self._linkage(self.matrix_smh_jaccard, "single")
+
+    @functools.cached_property
+    def linkage_complete_max_containment(self):
+        """the whole tree: what the cap of the capped case is read from"""
+        return self._linkage(self.matrix_max_containment, "complete")
+
+    @functools.cached_property
+    def linkage_cap(self):
+        """max_height of the capped case: the median height of the whole tree"""
+        h = np.sort(self.linkage_complete_max_containment["merges"]["jaccard"])
+        return float(h[len(h) // 2])
+
+    @functools.cached_property
+    def linkage_complete_max_containment_capped(self):
+        return self._linkage(self.matrix_max_containment, "complete", self.linkage_cap)
+
     # -- clusters -----------------------------------------------------------------------------------
     @functools.cached_property
     def clusters(self):
@@ -333,6 +401,29 @@ class Sets:
         return cluster_model.labels(self.edges, self.n_d).astype(np.int32)
 
     @functools.cached_property
+    def forest_values(self):
+        """the values of the edges handed to selhip_spanning_forest: fifty levels, so that many edges tie"""
+        return np.random.default_rng(self.seed + 11).integers(0, 50, len(self.edges)) / 50.0
+
+    @functools.cached_property
+    def block_forest(self):
+        edges, labels = forest_model.kruskal(forest_model.records_of(self.edges, self.forest_values), self.n_d)
+        return {"edges": forest_model.as_records(edges), "labels": np.asarray(labels, dtype=np.int32)}
+
+    @functools.cached_property
+    def linkage_dist(self):
+        """the caller's distance matrix of selhip_linkage: N_D x N_D uniform numbers from the set's seed (whatever the set's own size:
+        the entry takes no context and no sketches); only the strict upper triangle counts"""
+        return np.random.default_rng(self.seed + 12).random((N_D, N_D))
+
+    @functools.cached_property
+    def block_linkage(self):
+        """average linkage of linkage_dist, once per layout of LINKAGE_LAYOUTS: the layouts take the two instantiations of the row
+        scan and must give the same tree"""
+        res = linkage_model.linkage_model(self.linkage_dist, "average")
+        return {f"{k}-{tag}": res[k] for tag in LINKAGE_LAYOUTS for k in ("merges", "sizes", "rounds")}
+
+    @functools.cached_property
     def keys(self):
         return np.random.default_rng(self.seed + 6).integers(0, 1 << 40, self.n_d).astype(np.uint64)
 
@@ -359,6 +450,9 @@ CONTEXT_CASES = {
     "matrix-jaccard": ("matrix_jaccard", "matrix"), "matrix-smh_matches": ("matrix_smh_matches", "matrix"),
     "query_matrix-containment": ("query_matrix_containment", "matrix"),
     "cluster": ("clusters", "value"), "cluster_greedy-priority": ("greedy", "value"),
+    "forest": ("forest", "value"),
+    "linkage-average-jaccard": ("linkage_average_jaccard", "value"), "linkage-single-smh_jaccard": ("linkage_single_smh_jaccard", "value"),
+    "linkage-complete-max_containment-capped": ("linkage_complete_max_containment_capped", "value"),
     "two_contexts": ("smh_a", "list"),                      # (the second context runs smh_c: checked as "smh_c")
     "switch-sig_cache": ("smh_a", "list"), "switch-query_index": ("query", "list"),
 }
@@ -369,6 +463,7 @@ BLOCK_CASES = {
     "selhip_build_sketches": ("block_build", "value"), "selhip_permute_rows": ("block_permute", "value"),
     "selhip_hll_bitslice+union_hist_planes": ("block_hist", "value"),
     "components": ("components", "value"), "greedy_representatives": ("greedy_reps", "value"),
+    "selhip_spanning_forest": ("block_forest", "value"), "selhip_linkage": ("block_linkage", "value"),
 }
 # selhip_permute_rows at the shapes no other test reaches: case id -> (rows, row bytes, byte offset of both pointers).  Row sizes that
 # are no multiple of 16 and 16-byte multiples through pointers that are not 16-byte aligned take permute_bytes_kernel; 70 000 rows
@@ -386,7 +481,13 @@ def expected(S, case_id):
     return getattr(S, CASES[case_id][0])
 # entries that allocate and free device memory in every call -- hipFree waits for the whole device, the blocked null stream included --
 # get run A only (module docstring of tests/test_streams_gpu.py)
-RUN_A_ONLY = {"selhip_hll_bitslice+union_hist_planes", "components", "greedy_representatives", "grown_lists"}
+RUN_A_ONLY = {"selhip_hll_bitslice+union_hist_planes", "components", "greedy_representatives", "grown_lists",
+              "selhip_spanning_forest", "selhip_linkage", *LINKAGE_CASES}
+# ... of which the hierarchy entries still run with the null stream blocked, for the ANSWER alone: their host loops launch round after
+# round from words just read back, and a round left on the null stream shows only while that stream is held.  The hipFree at their end
+# waits the delay out (it is then 300 ms, not sized from the call), so that run does not ask whether the null stream is still blocked
+ANSWER_UNDER_BLOCKED_NULL = {"selhip_spanning_forest", "selhip_linkage", *LINKAGE_CASES}
+BLOCKED_ANSWER_DELAY_MS = 300.0
 
 
 def bits(x):
@@ -620,16 +721,19 @@ def blocked_run(env, body, name, delay_ms, streams=()):
         torch.cuda.synchronize()
 
 
-def run_b(env, body, want, streams=()):
-    """restore the decoy everywhere (timed: the sizing of the delay), then run B: the null stream is blocked"""
+def run_b(env, body, want, streams=(), answer_only=False):
+    """restore the decoy everywhere (timed: the sizing of the delay), then run B: the null stream is blocked.  answer_only: an entry
+    that frees its scratch before it returns (ANSWER_UNDER_BLOCKED_NULL) -- a fixed delay, which the entry waits out, and the answer"""
     t0 = time.perf_counter()
     plain_run(env, body, "decoy", "restore", streams)
     wall_ms = (time.perf_counter() - t0) * 1e3
-    delay_ms = min(MAX_DELAY_MS, 100.0 + 5.0 * wall_ms)
+    delay_ms = BLOCKED_ANSWER_DELAY_MS if answer_only else min(MAX_DELAY_MS, 100.0 + 5.0 * wall_ms)
     env.phase = "B"
     got, blocked = blocked_run(env, body, "real", delay_ms, streams)
     assert same(got, want(env.sets["real"])), "run B (the null stream is blocked): the answer is not the real set's -- the effect of " \
         "something put on the null stream is missing: " + describe(got, want(env.sets["real"]))
+    if answer_only:
+        return
     assert blocked, f"run B: the null stream's delay ({delay_ms:.0f} ms; the same calls took {wall_ms:.1f} ms before) was over when the " \
         "outputs were on the host: the call waited for the null stream or for the whole device"
 
@@ -643,14 +747,15 @@ def runs_beside_null(env, body, streams=()):
     return blocked_run(env, body, "decoy", 150.0, streams)[1]
 
 
-def three_runs(env, body, want, run_b_too=True, streams=(), fresh=None):
+def three_runs(env, body, want, run_b_too=True, streams=(), fresh=None, answer_only=False):
     """warm-up, run A, restore, run B of one case.  body(env) -> the outputs on the host; want(Sets) -> their expected value.
-    streams: the streams the body uses besides the environment's.  fresh: called in front of run A (a case that needs a new context)"""
+    streams: the streams the body uses besides the environment's.  fresh: called in front of run A (a case that needs a new context).
+    answer_only: run B for its answer alone (run_b)"""
     got = plain_run(env, body, "decoy", "warm", streams)
     assert same(got, want(env.sets["decoy"])), "warm-up (decoy, synchronised): " + describe(got, want(env.sets["decoy"]))
     if fresh:
         fresh()
     run_a(env, body, want, streams)
-    if run_b_too:
-        run_b(env, body, want, streams)
+    if run_b_too or answer_only:
+        run_b(env, body, want, streams, answer_only=answer_only and not run_b_too)
 

@@ -11,6 +11,8 @@ the oracle and the models, never from a second context.
   test_walk         60 random steps from a seed: replace the database (upload / attach), replace the queries, flip a route knob that
                     changes no answer, run an operation; the log goes into the assertion message
   test_refused_upload_leaves_the_context_alone, test_settings_survive_a_replacement   the contract of the header"""
+import ctypes as C
+
 import numpy as np
 import pytest
 import torch
@@ -21,6 +23,8 @@ import stream_harness as H
 import cuda_selection_criteria_amd as pkg
 from cuda_selection_criteria_amd import (ALGO_AUTO, ALGO_HASHJOIN, ALGO_INDEX, ALGO_SIG, ALGO_STREAM, CRIT_HLL_A, CRIT_HLL_A_SMH_A,
                                          CRIT_NONE, CRIT_SMH_A, CRIT_SMH_C, MODE_CB_SMH, PAIR_DTYPE, Selector, SelhipError)
+from cuda_selection_criteria_amd._lib import Linkage
+from cuda_selection_criteria_amd._lib import check as lib_check
 
 pytestmark = pytest.mark.gpu
 
@@ -188,6 +192,11 @@ def _smh_a(live, name):
     finally:
         sel.set_param("small_pass", live.knobs["small_pass"])
         sel.set_pipeline(live.knobs.get("pipeline", -1))
+    # which rows stage 2a read: the clamped four-plane image wherever the set holds one and the knobs allow it (the one-launch small pass
+    # has its own stage 2 and reports 0)
+    image = sel.get_param("hist_image")
+    image_want = 0 if sel.get_param("small_pass_used") else S.hist_image(live.knobs)
+    assert image == image_want, f"{name} on {S.name}: get_param('hist_image') {image}, the set (threshold {S.sparse_t}) and the knobs say {image_want}"
     if name == "smh_a-sig":
         # a pad column that is joined and filtered later shows in the statistics alone
         st = sel.stats()
@@ -309,6 +318,48 @@ def _cluster(live, name):
     return res
 
 
+@op("forest")
+def _forest(live, name):
+    """the smh_a signature pass, then its maximum spanning forest: GraphScratch, which cluster and cluster_greedy size too"""
+    live.settle()
+    live.run(ALGO_SIG, fetch=False)
+    res = live.sel.spanning_forest()
+    assert res["n_edges"] == len(res["edges"]) == live.sel.get_param("forest_edges_last")
+    return {"edges": res["edges"], "labels": res["labels"]}
+
+
+def kept_of_the_last_pass(sel):
+    """the result list, its count and the statistics as the context gives them now, or the refusal where it holds no finished pass"""
+    try:
+        return sel.result_count(), sel.fetch().tobytes(), sel.stats()
+    except SelhipError as e:
+        return "refused", e.code
+
+
+@op(*R.LINKAGE_OPS)
+def _linkage(live, name):
+    """selhip_ctx_linkage into poisoned arrays: the merges, the sizes and the rounds; "linkage_merges_last" and "linkage_rounds_last" are
+    the model's, and the result list, stats() and result_count() are what they were before the call"""
+    sel, S = live.sel, live.S
+    measure, method, capped = H.LINKAGE_CASES[name]
+    want = R.expected(S, name, live.knobs.get("hist_algo") != 0)
+    cap = float("inf") if not capped else 0.5 if isinstance(want, int) or S.trivial else S.linkage_cap      # (0.5: a call that is refused)
+    room = max(S.n_d - 1, 0)
+    merges = torch.full((room, PAIR_DTYPE.itemsize), 0xA5, dtype=torch.uint8, device="cuda")
+    sizes = torch.full((room,), int(POISON), dtype=torch.int32, device="cuda")
+    before = kept_of_the_last_pass(sel)
+    out, cnt = Linkage(merges.data_ptr() if room else None, sizes.data_ptr() if room else None), C.c_int64(-5)
+    lib_check(sel._lib.selhip_ctx_linkage(sel._ctx, pkg.measure_code(measure), pkg.linkage_code(method), cap, C.byref(out), C.byref(cnt)), sel._ctx)
+    f = cnt.value
+    m, s = merges.cpu().numpy(), sizes.cpu().numpy()
+    assert 0 <= f <= room and np.all(m[f:] == 0xA5) and np.all(s[f:] == int(POISON)), f"{name} on {S.name}: the entries from F = {f} on were written"
+    got = {"merges": np.ascontiguousarray(m[:f]).reshape(-1).view(PAIR_DTYPE), "sizes": s[:f], "rounds": sel.get_param("linkage_rounds_last")}
+    assert (sel.get_param("linkage_merges_last"), got["rounds"]) == (len(want["merges"]), want["rounds"]), \
+        f"{name} on {S.name}: merges and rounds {sel.get_param('linkage_merges_last'), got['rounds']}, the model's {len(want['merges']), want['rounds']}"
+    assert kept_of_the_last_pass(sel) == before, f"{name} on {S.name}: the call changed the result list, its count or the statistics"
+    return got
+
+
 @op("merge_groups")
 def _merge(live, name):
     S = live.S
@@ -331,9 +382,9 @@ def test_every_operation_has_a_body():
 def want_of(live, name):
     """expected(S, op) for the queries the context holds"""
     S, want = live.S, R.expected(live.S, name, live.knobs.get("hist_algo") != 0)
+    if name == "merge_groups" and S.n_d == 0:                     # (whatever queries the context holds: _merge drops the rows there)
+        want = {k: v for k, v in want.items() if k != "aux_hll"}
     if isinstance(want, int) or live.q_rows is None or live.q_rows == S.n_q:
-        if name == "merge_groups" and S.n_d == 0:
-            want = {k: v for k, v in want.items() if k != "aux_hll"}
         return want
     if R.OPS[name][1] == "qlist":
         return want[want["i"] < live.q_rows]
@@ -408,7 +459,7 @@ def test_transition(lib, names, flavour):
 
 # ---- (b) random walks ----------------------------------------------------------------------------------------------------------------
 KNOB_FLIPS = {"sig_cache": (0, 1), "small_pass": (0, -1), "pipeline": (0, 2), "group_min_n": (0, 2048), "hist_sparse": (-1, 0, 1),
-              "query_index_dir": (0, 1), "join_form": (0, 1, 2)}
+              "hist_image": (-1, 0, 1), "query_index_dir": (0, 1), "join_form": (0, 1, 2)}
 
 
 @pytest.mark.parametrize("seed", [11, 12, 13, 14])

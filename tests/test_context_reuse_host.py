@@ -51,6 +51,57 @@ def test_every_step_changes_every_answer(lib, step):
         assert not H.same(R.expected(X, op), R.expected(Y, op)), f"{op}: {step[0]} and {step[1]} have one answer, the step is blind to it"
 
 
+NEW_OPS = ("forest",) + tuple(H.LINKAGE_CASES)
+
+
+def test_the_hierarchy_operations_need_no_exemption(lib):
+    """the forest and the three linkages tell every step's two sets apart: none of them stands in SAME_ANSWER, and on every step both
+    sets admit they differ (said once more for them alone, beside test_every_step_changes_every_answer)"""
+    assert set(NEW_OPS) <= set(R.OPS) and not any(key[2] in NEW_OPS for key in R.SAME_ANSWER)
+    assert R.HLL_LINKAGES == {"linkage-average-jaccard", "linkage-complete-max_containment-capped"}
+    assert R.HLL_LINKAGES <= R.P14_ONLY and R.HLL_LINKAGES <= R.NEEDS_PLANES
+    for x, y in R.steps():
+        for op in NEW_OPS:
+            if R.refusal(lib[x], op) is None and R.refusal(lib[y], op) is None:
+                assert not H.same(R.expected(lib[x], op), R.expected(lib[y], op)), (x, y, op)
+    L = lib["LOWP"]
+    for op in NEW_OPS:
+        assert R.refusal(L, op) == (R.BADARG if op in R.HLL_LINKAGES else None), op
+        assert R.refusal(lib["BIG"], op, bit_planes=False) == (R.BADARG if op in R.HLL_LINKAGES else None), op
+        assert R.refusal(lib["EMPTY"], op, bit_planes=False) is None
+    for name in ("EMPTY", "ONE"):
+        n = lib[name].n_d
+        for op in R.LINKAGE_OPS:
+            want = R.expected(lib[name], op)
+            assert len(want["merges"]) == len(want["sizes"]) == 0 and want["rounds"] == n
+        want = R.expected(lib[name], "forest")
+        assert len(want["edges"]) == 0 and want["labels"].tolist() == list(range(n))
+    # the capped case cuts on every set of two or more genomes it runs on
+    for name in R.NAMES:
+        S = lib[name]
+        if not S.trivial and S.p_hll == 14:
+            assert 0 < len(S.linkage_complete_max_containment_capped["merges"]) < S.n_d - 1, name
+
+
+def test_the_image_premises(lib):
+    """which sets hold the clamped four-plane image (threshold 4, 8 or 12), and that the steps and sequences are there on which a stale
+    image would be read: a step between two sets that are both on the image with other rows at equal ranks, and a sequence on, off, on"""
+    on = {name: lib[name].hist_image({}) for name in R.NAMES}
+    assert on == {"BIG": 1, "PREFIX": 1, "NARROW": 1, "WIDE": 1, "LOWP": 0, "HIGHREG": 0, "EMPTY": 0, "ONE": 1, "TRIMMED": 1}, on
+    B = lib["BIG"]
+    for knob in ("hist_image", "hist_sparse", "hist_algo"):
+        assert B.hist_image({knob: 0}) == 0 and B.hist_image({knob: 1}) == 1 and B.hist_image({knob: -1}) == 1
+    other_rows = []
+    for x, y in R.steps():
+        X, Y = lib[x], lib[y]
+        k = min(X.n_d, Y.n_d)
+        if on[x] and on[y] and k >= 2 and (X.D.hll[:k] != Y.D.hll[:k]).any(axis=1).all():
+            other_rows.append((x, y))
+    assert ("BIG", "NARROW") in other_rows and ("NARROW", "WIDE") in other_rows and ("BIG", "PREFIX") not in other_rows, other_rows
+    assert any(tuple(on[s] for s in t[j:j + 3]) == (1, 0, 1) for t in R.TRANSITIONS for j in range(len(t) - 2)), "no sequence on, off, on"
+    assert ("BIG", "HIGHREG", "BIG") in R.TRANSITIONS
+
+
 def test_exemptions_are_few():
     for key, reason in R.SAME_ANSWER.items():
         assert reason and (key[0], key[1]) in R.steps() and key[2] in R.OPS

@@ -10,6 +10,11 @@ Known exceptions
   * selhip_hll_bitslice, selhip_hll_union_hist_planes, selhip_components and selhip_greedy_representatives (behind components() and
     greedy_representatives()) allocate and free their scratch in every call; they have no context to keep it in.  hipFree waits for the
     whole device, the blocked null stream included, so they get run A only.
+  * selhip_spanning_forest, selhip_linkage and selhip_ctx_linkage (its n * n cells of scratch) allocate and free in every call too: run A,
+    and run B for its ANSWER alone -- the null stream held by a fixed delay, which the call's hipFree waits out, and no question whether
+    it is still held afterwards.  Their rounds are launched one after the other from words the host has just read back; with the
+    stream idle in between, a launch left on the null stream shows only while that stream is held.  selhip_ctx_spanning_forest keeps
+    its scratch in the context and gets all three runs.
   * A pass that outgrows its lists ("init_cap") frees the old ones and allocates larger ones before it repeats: the same wait.  It
     gets run A only, on a fresh context whose lists are still small.
   * SELHIP_ALGO_INDEX builds its index in the first pass behind an attach of the database, in sort scratch (20 bytes per genome and
@@ -33,7 +38,7 @@ from stream_harness import K, M, N_BLOCK, N_D, N_Q, P_AUX, TAU
 import cuda_selection_criteria_amd as pkg
 from cuda_selection_criteria_amd import (ALGO_AUTO, ALGO_HASHJOIN, ALGO_INDEX, ALGO_SIG, ALGO_STREAM, CRIT_HLL_A, CRIT_HLL_A_SMH_A,
                                          CRIT_NONE, CRIT_SMH_A, CRIT_SMH_C, FP_FMA, MODE_CB_SMH, PAIR_DTYPE, Selector)
-from cuda_selection_criteria_amd._lib import check
+from cuda_selection_criteria_amd._lib import Forest, Linkage, check
 
 pytestmark = pytest.mark.gpu
 
@@ -346,6 +351,66 @@ def _cluster(env, case_id):
     return body
 
 
+def record_outputs(n):
+    """the two caller-owned arrays of a hierarchy call for n vertices (records as bytes, int32 words), poisoned in front of every call"""
+    rec = torch.empty((n - 1, PAIR_DTYPE.itemsize), dtype=torch.uint8, device="cuda")
+    words = torch.empty(n - 1, dtype=torch.int32, device="cuda")
+    return rec, words
+
+
+def first_records(env, rec, f, what):
+    """the first f records of a poisoned record array, read behind a call that returns when they are complete; the entries from f on
+    still hold the poison"""
+    raw = env.host_any_stream(rec)
+    assert 0 <= f <= len(raw) and np.all(raw[f:] == 0xA5), f"{what}: the entries from F = {f} on are not the poison any more"
+    return np.ascontiguousarray(raw[:f]).reshape(-1).view(PAIR_DTYPE)
+
+
+@case("forest")
+def _forest(env, case_id):
+    """the smh_a signature pass, then the maximum spanning forest of its list (scratch the context holds: run B too)"""
+    env.database()
+    sel = selector(env)
+    edges = torch.empty((N_D - 1, PAIR_DTYPE.itemsize), dtype=torch.uint8, device="cuda")
+    labels = torch.empty(N_D, dtype=torch.int32, device="cuda")
+    env.poison(edges, labels)
+
+    def body(env):
+        attach(env, sel)
+        env.stall(late=False)
+        sel.run(TAU, MODE_CB_SMH, R, B, algo=ALGO_SIG, fetch=False)
+        env.stall()                                     # (run A: another delay in front of the forest call)
+        out, cnt = Forest(edges.data_ptr(), labels.data_ptr()), C.c_int64(-5)
+        check(sel._lib.selhip_ctx_spanning_forest(sel._ctx, float("-inf"), C.byref(out), C.byref(cnt)), sel._ctx)
+        assert sel.get_param("forest_edges_last") == cnt.value
+        return {"edges": first_records(env, edges, cnt.value, case_id), "labels": env.host(labels)}
+    return body
+
+
+@case(*H.LINKAGE_CASES)
+def _linkage(env, case_id):
+    """selhip_ctx_linkage: n * n cells of scratch taken and released in the call, the matrix kernels, then up to 2 (n - 1) + 1 rounds
+    whose launch shapes the host reads back from the stream"""
+    measure, method, capped = H.LINKAGE_CASES[case_id]
+    env.database(extra=(lambda S: {"aux": S.dense_aux}) if measure == "smh_jaccard" else None)
+    sel = selector(env)
+    merges, sizes = record_outputs(N_D)
+    env.poison(merges, sizes)
+
+    def body(env):
+        attach(env, sel)
+        env.stall()
+        out, cnt = Linkage(merges.data_ptr(), sizes.data_ptr()), C.c_int64(-5)
+        cap = env.data.linkage_cap if capped else float("inf")
+        check(sel._lib.selhip_ctx_linkage(sel._ctx, pkg.measure_code(measure), pkg.linkage_code(method), cap, C.byref(out), C.byref(cnt)), sel._ctx)
+        f = cnt.value
+        assert sel.get_param("linkage_merges_last") == f
+        got_sizes = env.host(sizes)
+        assert np.all(got_sizes[f:] == -7), f"{case_id}: the sizes from F = {f} on are not the poison any more"
+        return {"merges": first_records(env, merges, f, case_id), "sizes": got_sizes[:f], "rounds": sel.get_param("linkage_rounds_last")}
+    return body
+
+
 @case("two_contexts")
 def _two_contexts(env, case_id):
     """two contexts on two streams over the same attached tensors; both passes are enqueued before either is finished"""
@@ -376,10 +441,10 @@ def _two_contexts(env, case_id):
 
 
 # ---- block launchers and Python helpers ------------------------------------------------------------------------------------------------
-def launcher(env, make, outputs, call, result, asynchronous=True):
+def launcher(env, make, outputs, call, result, asynchronous=True, late=()):
     """a launcher case: make(Sets) -> its input arrays, outputs -> its output tensors (poisoned on the stream in front of every call),
-    call(T, stream pointer), result() -> the outputs on the host"""
-    env.tensors(make)
+    call(T, stream pointer), result() -> the outputs on the host.  late: the inputs written behind run A's second delay"""
+    env.tensors(make, late)
     env.poison(*outputs)
 
     def body(env):
@@ -521,6 +586,51 @@ def _b_greedy(env, case_id):
     return body
 
 
+@case("selhip_spanning_forest")
+def _b_forest(env, case_id):
+    """the edge list and its values are late inputs; the entry owns its scratch and waits for the stream"""
+    edges = torch.empty((N_D - 1, PAIR_DTYPE.itemsize), dtype=torch.uint8, device="cuda")
+    labels = torch.empty(N_D, dtype=torch.int32, device="cuda")
+    f, rounds = C.c_int64(-5), C.c_int64(-5)
+
+    def call(T, st):
+        check(pkg.hip_lib().selhip_spanning_forest(T["edges"].data_ptr(), T["values"].data_ptr(), H.N_EDGES, N_D, edges.data_ptr(), labels.data_ptr(),
+                                                   C.byref(f), C.byref(rounds), st))
+    return launcher(env, lambda S: {"edges": S.edges, "values": S.forest_values}, [edges, labels], call,
+                    lambda: {"edges": first_records(env, edges, f.value, case_id), "labels": env.host(labels)},
+                    asynchronous=False, late=("edges", "values"))
+
+
+@case("selhip_linkage")
+def _b_linkage(env, case_id):
+    """average linkage of a caller's matrix, a late input, in both layouts of H.LINKAGE_LAYOUTS: the matrix is staged on the stream into a
+    buffer of the layout's leading dimension and base (the call consumes it), and each layout has poisoned outputs of its own"""
+    n = N_D
+    lay = {}
+    for tag, (ld_extra, offset) in H.LINKAGE_LAYOUTS.items():
+        ld = n + ld_extra
+        buf = torch.full((n * ld + 2 + offset,), float("nan"), dtype=torch.float64, device="cuda")
+        assert buf.data_ptr() % 16 == 0
+        lay[tag] = (buf[offset:offset + n * ld].view(n, ld), ld, *record_outputs(n), C.c_int64(-5), C.c_int64(-5))
+    assert lay["wide"][1] % 2 == 0 and lay["wide"][0].data_ptr() % 16 == 0 and lay["narrow"][1] % 2 == 1 and lay["narrow"][0].data_ptr() % 16 == 8
+
+    def call(T, st):
+        for view, ld, merges, sizes, f, rounds in lay.values():
+            view[:, :n].copy_(T["dist"], non_blocking=True)
+            check(pkg.hip_lib().selhip_linkage(view.data_ptr(), n, ld, pkg.LINKAGE_AVERAGE, float("inf"), merges.data_ptr(), sizes.data_ptr(),
+                                               C.byref(f), C.byref(rounds), st))
+
+    def result():
+        out = {}
+        for tag, (_, _, merges, sizes, f, rounds) in lay.items():
+            got_sizes = env.host(sizes)
+            assert np.all(got_sizes[f.value:] == -7), (case_id, tag)
+            out.update({f"merges-{tag}": first_records(env, merges, f.value, case_id), f"sizes-{tag}": got_sizes[:f.value], f"rounds-{tag}": rounds.value})
+        return out
+    outputs = [t for v in lay.values() for t in v[2:4]]
+    return launcher(env, lambda S: {"dist": S.linkage_dist}, outputs, call, result, asynchronous=False, late=("dist",))
+
+
 SWITCHES = ("switch-sig_cache", "switch-query_index")
 
 
@@ -533,7 +643,8 @@ def test_late_stream_and_blocked_null_stream(rig, env, case_id):
     env.rig_streams = rig.streams
     made = SETUP[case_id](env)
     body, options = made if isinstance(made, tuple) else (made, {})
-    H.three_runs(env, body, lambda S: H.expected(S, case_id), run_b_too=case_id not in H.RUN_A_ONLY, **options)
+    H.three_runs(env, body, lambda S: H.expected(S, case_id), run_b_too=case_id not in H.RUN_A_ONLY,
+                 answer_only=case_id in H.ANSWER_UNDER_BLOCKED_NULL, **options)
 
 
 @pytest.mark.parametrize("case_id", SWITCHES)

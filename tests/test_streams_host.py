@@ -47,7 +47,7 @@ def test_real_and_decoy_answers_differ(sets, case_id):
 def test_late_inputs_differ(sets):
     """what is written behind run A's second delay differs between the sets too, and the pair lists are valid"""
     a, b = sets["real"], sets["decoy"]
-    for name in ("pair_list", "prio", "row_pos", "col_pos", "block_pairs", "edges", "keys", "perm"):
+    for name in ("pair_list", "prio", "row_pos", "col_pos", "block_pairs", "edges", "keys", "perm", "forest_values", "linkage_dist"):
         assert not np.array_equal(getattr(a, name), getattr(b, name)), name
     for S in (a, b):
         for p in (S.pair_list, S.block_pairs, S.edges):
@@ -58,6 +58,27 @@ def test_late_inputs_differ(sets):
         assert 20 <= len(S.smh_c) < len(S.none) and 20 <= len(S.smh_c_v)
         # the cuts keep fewer records than the directed lists hold: the top-k really cuts
         assert len(S.topk) < 2 * len(S.smh_a) and len(S.query_topk) < len(S.query)
+
+
+def test_hierarchy_premises(sets):
+    """the capped linkage case really cuts (0 < F < n - 1, at the median height of the whole tree), the SuperMinHash case ends in a
+    plateau of equal distances (one pair per round: as many rounds as genomes), the forest is a proper one (0 < F < n - 1: several
+    components of several genomes), selhip_linkage's matrix has the harness's size and both layouts are there"""
+    assert H.ANSWER_UNDER_BLOCKED_NULL <= H.RUN_A_ONLY and set(H.LINKAGE_CASES) <= set(H.CONTEXT_CASES)
+    assert H.LINKAGE_LAYOUTS == {"wide": (0, 0), "narrow": (3, 1)} and (H.N_D + 3) % 2 == 1 and H.N_D % 2 == 0
+    for S in sets.values():
+        n = S.n_d
+        whole, capped = S.linkage_complete_max_containment, S.linkage_complete_max_containment_capped
+        assert len(whole["merges"]) == n - 1 and 0 < len(capped["merges"]) < n - 1
+        assert np.isfinite(S.linkage_cap) and (capped["merges"]["jaccard"] <= S.linkage_cap).all()
+        assert np.sort(whole["merges"]["jaccard"])[(n - 1) // 2] == S.linkage_cap
+        for name in ("linkage_average_jaccard", "linkage_single_smh_jaccard"):
+            assert len(getattr(S, name)["merges"]) == len(getattr(S, name)["sizes"]) == n - 1
+        assert S.linkage_single_smh_jaccard["rounds"] >= n // 2 > 4 * S.linkage_average_jaccard["rounds"] // 3
+        for forest in (S.forest, S.block_forest):
+            assert 0 < len(forest["edges"]) < n - 1 and len(forest["labels"]) == n
+        assert S.linkage_dist.shape == (H.N_D, H.N_D) and len(S.forest_values) == len(S.edges) == H.N_EDGES
+        assert len(S.block_linkage) == 6 and len(S.block_linkage["merges-wide"]) == H.N_D - 1
 
 
 def test_bits_compare_bit_for_bit():

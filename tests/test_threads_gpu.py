@@ -5,7 +5,7 @@ selhip_multi_select rest on that, and until now only the former's narrow path (a
 Each thread owns one context (tests/test_context_reuse_gpu.py's Live) that holds a set of its OWN -- another n, m and seed, so that
 anything crossing between contexts shows as the other set's answer -- on a non-blocking torch pool stream of its own, and makes its torch
 calls under torch.cuda.stream(that stream): the threads' device work can really overlap (ctypes releases the GIL during a library call).
-The sets, the 28 operations and their expected values are tests/context_reuse_model.py's; the context-free entries and theirs are
+The sets, the 32 operations and their expected values are tests/context_reuse_model.py's; the context-free entries and theirs are
 tests/thread_entries.py's.  Every comparison is bit for bit with the oracle and the models (stream_harness.same), never with a second
 context or a serial run.  The threads run in a thread_harness.Crew: a failure in one is re-raised here with every thread's log, breaks the
 barrier and stops the others before their next step; every wait has a time-out; behind a HIP error no test of this file starts another
@@ -45,8 +45,8 @@ pytestmark = pytest.mark.gpu
 
 OPS = tuple(R.OPS)
 # The least share of barrier steps of test_every_operation_beside_every_operation whose two intervals must intersect.  A condition of
-# the test, not a performance figure: half the lowest share of three runs of this file on an MI355X (784 of 784 steps in each: DESIGN.md
-# section 29), never under a quarter
+# the test, not a performance figure: half the lowest share of three runs of this file on an MI355X (784 of 784 steps in each, with the 28 operations of then; the
+# 1 024 steps of the 32 of now are measured in DESIGN.md section 29 too), never under a quarter
 OVERLAP_FLOOR = 0.50
 TALLY = {"cases": 0, "steps": 0, "hits": 0}
 
@@ -82,6 +82,7 @@ def prime(lib, names, ops=OPS):
         for o in ops:
             R.expected(S, o)
         R.stats_expected(S)
+        S.sparse_t
 
 
 class Worker:
@@ -117,7 +118,7 @@ def step(me, key, live, name):
 
 # the operations whose last pass is the all-pairs smh_a pass without a top-k: what the context keeps of it is known
 SMH_A_LAST = ("smh_a-sig", "smh_a-stream", "smh_a-hashjoin", "smh_a-chunks2", "smh_a-small_pass", "run_async-framed-finish", "cluster",
-              "cluster_greedy-priority")
+              "cluster_greedy-priority", "forest")
 
 
 def second_look(live, name):
@@ -318,7 +319,7 @@ def test_walks_in_parallel(lib, streams, seed):
 FREE_SETS = ("BIG", "NARROW", "HIGHREG")
 FREE_ROUNDS = 3
 FREE_VALUES = ("block_flags", "block_hist", "block_estimates", "block_matches", "block_fold", "block_synth", "block_build", "block_permute",
-               "components", "greedy_reps", "edges", "keys", "perm")
+               "components", "greedy_reps", "edges", "keys", "perm", "forest_values", "block_forest", "linkage_dist", "block_linkage")
 
 
 def test_free_standing_entries_in_parallel(lib, streams):
@@ -348,8 +349,9 @@ def test_free_standing_entries_in_parallel(lib, streams):
 
 def test_first_calls_meet_in_a_fresh_process():
     """selhip_synth_generate, selhip_build_sketches and the split builder raise their kernels' LDS limit in a std::call_once at their first
-    call.  In a fresh child process three threads make those first calls at once, on three streams and three inputs, and compare what
-    they get with the generator's host twin and the builder's oracle (a child process: the program of this one is not replaced)"""
+    call.  In a fresh child process three threads make those first calls at once, and the first calls of selhip_linkage, on three streams
+    and three inputs, and compare what they get with the generator's host twin, the builder's oracle and the linkage model (a child
+    process: the program of this one is not replaced)"""
     child = Path(__file__).with_name("threads_child.py")
     r = subprocess.run([sys.executable, str(child)], capture_output=True, text=True, timeout=T.TIMEOUT)
     print(r.stdout[-2000:])
@@ -360,7 +362,8 @@ def test_first_calls_meet_in_a_fresh_process():
 CHURN = 30
 CHURN_SETS = ("PREFIX", "NARROW", "ONE", "TRIMMED", "WIDE")
 WORK_OPS = ("smh_a-sig", "query-index", "cluster", "merge_groups", "allpairs-topk-rounds", "none-fused", "matrix-jaccard", "pairs-direct_route",
-            "hll_a-folded", "smh_a-hashjoin", "run_async-framed-finish", "query_matrix-containment")
+            "hll_a-folded", "smh_a-hashjoin", "run_async-framed-finish", "query_matrix-containment",
+            "linkage-average-jaccard")                    # (a hipMalloc and a hipFree of its own in every call, beside the churn's)
 
 
 def test_context_churn_beside_work(lib, streams):

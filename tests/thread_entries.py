@@ -14,7 +14,6 @@ import cuda_selection_criteria_amd as pkg
 from cuda_selection_criteria_amd import FP_FMA, PAIR_DTYPE
 from cuda_selection_criteria_amd._lib import BuildInfo, check
 
-import forest_model
 import merge_model
 import stream_harness as H
 
@@ -183,18 +182,36 @@ def _greedy(S, st):
     return is_rep, S.greedy_reps
 
 
-def forest_values(S):
-    return np.random.default_rng(S.seed + 11).integers(0, 50, len(S.edges)) / 50.0
-
-
 @entry("selhip_spanning_forest")
 def _forest(S, st):
-    values = forest_values(S)
-    res = pkg.spanning_forest(dev(S.edges), S.n_d, values=values)
-    edges, labels = forest_model.kruskal(forest_model.records_of(S.edges, values), S.n_d)
-    want = forest_model.as_records(edges)
-    assert res["edges"].dtype == PAIR_DTYPE and res["n_edges"] == len(want)
-    return {"edges": res["edges"], "labels": res["labels"]}, {"edges": want, "labels": np.asarray(labels, dtype=np.int32)}
+    res = pkg.spanning_forest(dev(S.edges), S.n_d, values=S.forest_values)
+    want = S.block_forest
+    assert res["edges"].dtype == PAIR_DTYPE and res["n_edges"] == len(want["edges"])
+    return {"edges": res["edges"], "labels": res["labels"]}, want
+
+
+@entry("selhip_linkage")
+def _linkage(S, st):
+    """average linkage of the set's own matrix (Sets.linkage_dist) in both layouts of stream_harness.LINKAGE_LAYOUTS: per-call scratch,
+    and a host loop that launches round after round from words it reads back, beside the other threads' calls"""
+    import torch
+    n = S.linkage_dist.shape[0]
+    src, got = dev(S.linkage_dist), {}
+    for tag, (ld_extra, offset) in H.LINKAGE_LAYOUTS.items():
+        ld = n + ld_extra
+        buf = torch.full((n * ld + 2 + offset,), float("nan"), dtype=torch.float64, device="cuda")
+        view = buf[offset:offset + n * ld].view(n, ld)
+        assert (ld % 2 == 0 and view.data_ptr() % 16 == 0) == (tag == "wide")
+        view[:, :n].copy_(src)
+        merges, sizes = poisoned((n - 1, PAIR_DTYPE.itemsize), torch.uint8), poisoned((n - 1,), torch.int32)
+        f, rounds = C.c_int64(-5), C.c_int64(-5)
+        check(pkg.hip_lib().selhip_linkage(view.data_ptr(), n, ld, pkg.LINKAGE_AVERAGE, float("inf"), merges.data_ptr(), sizes.data_ptr(),
+                                           C.byref(f), C.byref(rounds), ptr(st)))
+        m, s = merges.cpu().numpy(), sizes.cpu().numpy()
+        assert 0 <= f.value <= n - 1 and np.all(m[f.value:] == 0xA5) and np.all(s[f.value:] == -7), (tag, f.value)
+        got.update({f"merges-{tag}": np.ascontiguousarray(m[:f.value]).reshape(-1).view(PAIR_DTYPE), f"sizes-{tag}": s[:f.value],
+                    f"rounds-{tag}": rounds.value})
+    return got, S.block_linkage
 
 
 def merge_groups(S):
@@ -211,3 +228,6 @@ def _merge(S, st):
 # the entries whose first call in a process goes through a std::call_once (csrc/abi_blocks.inc: selhip_synth_generate,
 # selhip_build_sketches; csrc/host_build.hpp: the split builder's main launch)
 CALL_ONCE = ("selhip_synth_generate", "selhip_build_sketches", "selhip_build_sketches_split")
+# what three threads of a fresh process call first (tests/threads_child.py): those, and selhip_linkage, whose first call loads its seven
+# kernels and takes its scratch while the other threads do the same
+FIRST_CALLS = CALL_ONCE + ("selhip_linkage",)
