@@ -239,6 +239,14 @@ int selhip_ctx_set_param(selhip_ctx* c, const char* name, int value) {
         g_cluster_blocks.store(value, std::memory_order_relaxed);
         return SELHIP_OK;
     }
+    // (its sibling, as process-wide and as little part of the documented interface: > 0 fixes the grid of every kernel that takes a lane
+    //  per vertex, row or slot -- whatever cluster_vertex_grid sizes: clusters, greedy, forest, linkage, the merge's row kernels -- so that
+    //  a small n walks their grid-stride loops many times; 0 = sized from n; the same answers either way)
+    if (!std::strcmp(name, "vertex_blocks")) {
+        if (value < 0 || value > 65536) { set_err(&c->err, "vertex_blocks must be in [0, 65536] (0 = automatic)"); return SELHIP_E_BADARG; }
+        g_vertex_blocks.store(value, std::memory_order_relaxed);
+        return SELHIP_OK;
+    }
     set_err(&c->err, "unknown parameter '%s'", name);
     return SELHIP_E_BADARG;
 }
@@ -261,6 +269,7 @@ int selhip_ctx_get_param(const selhip_ctx* c, const char* name, int* value) {
     if (!std::strcmp(name, "matrix_smh_path_used")) { *value = c->matrix_smh_path_used; return SELHIP_OK; }   // kernel of the last SuperMinHash matrix: 1 fast, 0 generic
     if (!std::strcmp(name, "clusters_last"))    { *value = c->clusters_last; return SELHIP_OK; }            // clusters of the last selhip_ctx_cluster call, -1 = none yet
     if (!std::strcmp(name, "cluster_blocks"))   { *value = g_cluster_blocks.load(std::memory_order_relaxed); return SELHIP_OK; }
+    if (!std::strcmp(name, "vertex_blocks"))    { *value = g_vertex_blocks.load(std::memory_order_relaxed); return SELHIP_OK; }
     if (!std::strcmp(name, "greedy_clusters_last")) { *value = c->greedy_clusters_last; return SELHIP_OK; }  // clusters of the last selhip_ctx_cluster_greedy call, -1 = none yet
     if (!std::strcmp(name, "greedy_rounds_last"))   { *value = c->greedy_rounds_last; return SELHIP_OK; }    // ... and the rounds its selection took
     if (!std::strcmp(name, "forest_rounds_last"))   { *value = c->forest_rounds_last; return SELHIP_OK; }    // rounds of the last selhip_ctx_spanning_forest call, -1 = none yet

@@ -10,12 +10,20 @@ namespace {
 // small list runs the grid-stride loop many times; 0 = sized from the list.  Atomic (relaxed: the value orders nothing, and the clusters
 // are the same under every grid): one thread may set it through its context while other threads' graph calls read it
 std::atomic<int> g_cluster_blocks{0};
+// its sibling for the kernels that take a lane per vertex, row or slot ("vertex_blocks", process-wide and atomic for the same reasons):
+// > 0 fixes the result of cluster_vertex_grid, so that a small n walks those kernels' grid-stride loops -- and the ballots, lane reads
+// and per-cluster atomics at the end of each trip -- many times; 0 = sized from n.  It changes no answer: every such kernel strides by
+// its own grid.  The row kernels of the merge by group (host_merge.hpp) take their grid here too
+std::atomic<int> g_vertex_blocks{0};
 
 unsigned cluster_edge_grid(u64 n_edges) {
     const int blocks = g_cluster_blocks.load(std::memory_order_relaxed);
     return blocks > 0 ? (unsigned)blocks : grid_for(n_edges, kBlock, kClusterMaxBlocks);
 }
-unsigned cluster_vertex_grid(int64_t n) { return grid_for((u64)n, kBlock, 4096); }
+unsigned cluster_vertex_grid(int64_t n) {
+    const int blocks = g_vertex_blocks.load(std::memory_order_relaxed);
+    return blocks > 0 ? (unsigned)blocks : grid_for((u64)n, kBlock, 4096);
+}
 
 // parent[] initialised (with the tallies the caller wants cleared) and every edge of the list united, on st; nothing is waited for
 template <class List>

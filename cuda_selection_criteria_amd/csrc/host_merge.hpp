@@ -38,7 +38,7 @@ int merge_run(std::string* err, hipStream_t st, MergeScratch& ms, const MergeKin
     // level 0: members per group, the check of the ids, offsets
     if (G > 0) HIPCHK(err, hipMemsetAsync(ms.cnt.p, 0, (size_t)G * sizeof(int), st));
     HIPCHK(err, hipMemsetAsync(ms.info.p, 0, sizeof(MergeInfo), st));
-    const unsigned ngrid = grid_for((u64)n, kBlock, 4096);
+    const unsigned ngrid = cluster_vertex_grid(n);                             // (so the "vertex_blocks" hook shapes the two row kernels too)
     if (n > 0) {
         hipLaunchKernelGGL(merge_count_kernel, dim3(ngrid), dim3(kBlock), 0, st, d_group, (long long)n, (int)G, ms.cnt.p, ms.info.p);
         HIPCHK(err, hipGetLastError());

@@ -148,9 +148,11 @@ const char* selhip_last_error(const selhip_ctx* ctx);
  * one device) and selhip_multi_select (one thread per device) rest on this.  ONE context is used by one thread at a time: its calls
  * are not locked against each other, and the caller orders them (it may hand a context from thread to thread).
  * selhip_last_error(NULL) is per thread: the message of the last failure of a call made ON THE CALLING THREAD (any context, or none);
- * selhip_last_error(ctx) is the context's own message, whichever thread reads it.  The one setting that is process-wide is the test
- * hook "cluster_blocks" of selhip_ctx_set_param: it is set through any context, holds for every graph call of the process (sections 2g, 2h, 2j and their
- * context-free forms in section 3), may be set while other threads work, and changes no answer.  Calls that free
+ * selhip_last_error(ctx) is the context's own message, whichever thread reads it.  The two settings that are process-wide are the test
+ * hooks "cluster_blocks" and "vertex_blocks" of selhip_ctx_set_param (the grids of the kernels that take a lane per record, and per
+ * vertex, row or slot; 0 = sized from the input): each is set through any context, holds for every graph call of the process (sections
+ * 2g, 2h, 2j, 2k and their context-free forms in section 3; "vertex_blocks" also for the merge by group), may be set while other
+ * threads work, is read back by selhip_ctx_get_param, and changes no answer.  Calls that free
  * device memory (below) wait for the whole device and so for the other threads' work; they delay it and do not disturb it.
  * tests/test_threads_gpu.py runs every entry from several threads at once. */
 

@@ -2,7 +2,9 @@
 equality with tests/cluster_model.py -- a sequential union-find in Python -- run on the same edge list, or on the records fetched from
 the pass.  The graphs of (1) are built to break a concurrent union-find: long parent chains, every hook on one root, one giant
 component, a bridge in the last entry; each runs with the default grid and with the edge kernel's grid forced to 1 and 2 blocks (the
-grid-stride loop then runs many times), twice, and the two runs must be byte-equal."""
+grid-stride loop then runs many times), twice, and the two runs must be byte-equal.  Those record grids are crossed with the vertex
+kernels' grid ("vertex_blocks": sized from n, 1 block, 3 blocks), so that the loops over the vertices come round too (DESIGN.md
+section 32); test_vertex_trips_of_the_context_call does the same for every kernel of selhip_ctx_cluster at 771 genomes."""
 import ctypes as C
 import subprocess
 
@@ -29,10 +31,22 @@ OUTPUTS = ("labels", "clusters", "degrees", "sizes", "representatives")
 
 @pytest.fixture
 def grid_hook():
-    """sets the process-wide grid of the edge kernel (0 = automatic) and puts the default back"""
+    """sets the process-wide grids of the edge kernel and of the vertex kernels (0 = automatic) and puts the defaults back"""
     with Selector(0) as sel:
-        yield lambda blocks: sel.set_param("cluster_blocks", blocks)
-        sel.set_param("cluster_blocks", 0)
+        def set_hooks(blocks, vertex_blocks=0):
+            sel.set_param("cluster_blocks", blocks)
+            sel.set_param("vertex_blocks", vertex_blocks)
+            assert (sel.get_param("cluster_blocks"), sel.get_param("vertex_blocks")) == (blocks, vertex_blocks)
+        yield set_hooks
+        set_hooks(0, 0)
+
+
+VERTEX_BLOCKS = (0, 1, 3)      # the vertex kernels' grid: sized from n, one block, three blocks (strides of 256 and of 768 vertices)
+
+
+def hook_grid(record_blocks):
+    """the ("cluster_blocks", "vertex_blocks") pairs a case runs under: the file's record grids crossed with VERTEX_BLOCKS"""
+    return [(b, v) for v in VERTEX_BLOCKS for b in record_blocks]
 
 
 # ---- 1. + 2. selhip_components on graphs built to break a union-find, every grid, twice ----------------------------------------------------
@@ -76,7 +90,7 @@ def graphs():
          ("path-ascending", 4097, path(4097, "ascending")), ("path-descending", 4097, path(4097, "descending")),
          ("path-shuffled", 4097, path(4097, "shuffled")),
          ("star-centre-highest", 65537, star(65537, 65536)), ("star-centre-0", 65537, star(65537, 0)),
-         ("K300", 300, clique(0, 300)),
+         ("n1000-apart", 1000, np.zeros((0, 2), dtype=np.int64)), ("K300", 300, clique(0, 300)),
          ("two-cliques-bridge-last", 300, np.concatenate([clique(0, 150), clique(150, 300), np.array([[299, 0]])])),
          ("two-cliques-apart", 300, np.concatenate([clique(0, 150), clique(150, 300)])),
          ("sparse-5000", 5000, sparse_random(5000, 2500, 11)),
@@ -97,6 +111,18 @@ def want_labels(name, n, edges):
     return _WANT[name]
 
 
+def components_raw(dev_pairs, n):
+    """selhip_components into a buffer filled with a sentinel, guards on both sides: a vertex the call left unwritten shows (torch.empty
+    would hand a second call the block, and the answer, of the first)"""
+    lib = pkg.hip_lib()
+    buf = torch.full((n + 2 * GUARD,), SENTINEL, dtype=torch.int32, device="cuda")
+    rc = lib.selhip_components(dev_pairs.data_ptr() if dev_pairs.numel() else None, int(dev_pairs.shape[0]), n, buf.data_ptr() + 4 * GUARD, None)
+    assert rc == 0, lib.selhip_last_error(None).decode()
+    out = buf.cpu().numpy()
+    assert np.all(out[:GUARD] == SENTINEL) and np.all(out[GUARD + n:] == SENTINEL)
+    return out[GUARD:GUARD + n].copy()
+
+
 @pytest.mark.parametrize("name,n,edges", GRAPHS, ids=[g[0] for g in GRAPHS])
 def test_components(grid_hook, name, n, edges):
     want = want_labels(name, n, edges)
@@ -108,12 +134,12 @@ def test_components(grid_hook, name, n, edges):
         sizes = np.bincount(want)
         assert sizes.max() > 3 and (sizes == 1).sum() > 100                     # many components of mixed size
     dev = torch.from_numpy(np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 2)).cuda()
-    for blocks in (0, 1, 2):
-        grid_hook(blocks)
-        first = pkg.components(dev, n)
-        again = pkg.components(dev, n)
-        assert first.dtype == np.int32 and first.tobytes() == again.tobytes(), (name, blocks)
-        assert np.array_equal(first, want), (name, blocks, np.flatnonzero(first != want)[:5])
+    for blocks, vblocks in hook_grid((0, 1, 2)):
+        grid_hook(blocks, vblocks)
+        first = components_raw(dev, n)
+        again = components_raw(dev, n)
+        assert first.dtype == np.int32 and first.tobytes() == again.tobytes(), (name, blocks, vblocks)
+        assert np.array_equal(first, want), (name, blocks, vblocks, np.flatnonzero(first != want)[:5])
     grid_hook(0)
     assert np.array_equal(pkg.components(np.asarray(edges), n), want)            # a host list is copied to the device
 
@@ -125,8 +151,8 @@ def test_components_invalid_entry(grid_hook, bad):
     edges[[17, 230]] = bad                                                         # two such entries
     lib = pkg.hip_lib()
     dev = torch.from_numpy(edges).cuda()
-    for blocks in (0, 1):
-        grid_hook(blocks)
+    for blocks, vblocks in hook_grid((0, 1)):
+        grid_hook(blocks, vblocks)
         buf = torch.full((n + 2 * GUARD,), SENTINEL, dtype=torch.int32, device="cuda")
         rc = lib.selhip_components(dev.data_ptr(), len(edges), n, buf.data_ptr() + 4 * GUARD, None)
         msg = lib.selhip_last_error(None).decode()
@@ -134,6 +160,7 @@ def test_components_invalid_entry(grid_hook, bad):
         assert "2 invalid entries" in msg and f"[0, {n})" in msg and ("entry 17 is one" in msg or "entry 230 is one" in msg), msg
         out = buf.cpu().numpy()
         assert np.all(out[:GUARD] == SENTINEL) and np.all(out[GUARD + n:] == SENTINEL)
+    grid_hook(0)
     # the same list without them is fine, and the guards stay
     edges[[17, 230]] = (0, 0)
     buf = torch.full((n + 2 * GUARD,), SENTINEL, dtype=torch.int32, device="cuda")
@@ -216,10 +243,10 @@ def test_cluster_behind_all_pairs(oracle, grid_hook, crit):
             cuts = [-np.inf] + ([float(values[len(values) // 2]), float(values[-1])] if len(values) else [])
             for min_value in cuts:
                 edges = CM.record_edges(rec, min_value)
-                for blocks in (0, 1):
-                    grid_hook(blocks)
-                    want = CM.clusters(edges, n, "max_degree")
-                    assert_same(raw_cluster(sel, min_value, 0), want, (crit, n, min_value, blocks))
+                want = CM.clusters(edges, n, "max_degree")
+                for blocks, vblocks in hook_grid((0, 1)):
+                    grid_hook(blocks, vblocks)
+                    assert_same(raw_cluster(sel, min_value, 0), want, (crit, n, min_value, blocks, vblocks))
                 n_mixed += 1 < want["n_clusters"] < n
             grid_hook(0)
             # every output pointer NULL in turn: the others are still right, nothing else is written
@@ -313,6 +340,30 @@ def test_representative_rules():
             assert err.value.code == -1
         with pytest.raises(ValueError, match="rep"):
             sel.cluster(rep="degree")
+
+
+def test_vertex_trips_of_the_context_call(grid_hook):
+    """771 genomes = three blocks of 256 and three lanes: with the vertex kernels in one block every loop of selhip_ctx_cluster comes
+    round four times and ends in a wave of three lanes; with three blocks it comes round twice.  Every output, each representative
+    rule, two cuts; twice, byte-equal"""
+    from test_greedy_gpu import planted_pass, random_weighted                            # (that module imports this one)
+    n, m = 771, 256
+    with Selector(0) as sel:
+        rec = planted_pass(sel, n, m, random_weighted(n, 771), seed=771)                 # a sparse random graph: components across the trips
+        for min_value in (-np.inf, 8 / m):
+            edges = CM.record_edges(rec, min_value)
+            for rule, code in CM.REP_NAMES.items():
+                want = CM.clusters(edges, n, rule)
+                far = np.flatnonzero(np.arange(n) // 256 != want["labels"] // 256)       # members a trip or more away from their root
+                assert 1 < want["n_clusters"] < n and want["sizes"].max() > 50 and (want["sizes"] == 1).sum() > 20 and len(far) > 100
+                for blocks, vblocks in hook_grid((0, 1)):
+                    grid_hook(blocks, vblocks)
+                    first, again = raw_cluster(sel, min_value, code), raw_cluster(sel, min_value, code)
+                    assert all(first[k].tobytes() == again[k].tobytes() for k in OUTPUTS), (rule, blocks, vblocks)
+                    assert_same(first, want, (min_value, rule, blocks, vblocks))
+        grid_hook(0, 3)
+        assert len(sel.run(2.0, MODE_SMH, 7, 3)) == 0                                   # no record: cluster_singletons_kernel, two trips
+        assert_same(raw_cluster(sel, -np.inf, 0), CM.clusters(np.zeros((0, 2), dtype=np.int64), n), "empty list")
 
 
 # ---- 6. the kinds of list, the refusals, and what the call leaves alone -------------------------------------------------------------------

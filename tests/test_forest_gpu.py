@@ -3,7 +3,9 @@ compared bit for bit with tests/forest_model.py -- Kruskal's visit in the BEFORE
 records fetched from the pass; the rounds with the model of the synchronous Boruvka scheme.  The graphs of (1) are those that break a
 concurrent union-find (tests/test_cluster_gpu.py): hook chains of 4 096, 65 536 picks aimed at one word, one giant component, a bridge
 as the worst and as the best edge; each under four value sets, with the default grid and with the record kernels' grid forced to 1 and 2
-blocks, twice, and the two runs must be byte-equal."""
+blocks, twice, and the two runs must be byte-equal.  The record grids are crossed with the vertex kernels' grid ("vertex_blocks": sized
+from n, 1 block, 3 blocks), so that the loops of the hook, flatten and emit kernels -- a ballot and a lane-ordered scatter at the end
+of every trip -- come round up to 257 times; the round count must equal the model's under every grid."""
 import ctypes as C
 import subprocess
 
@@ -15,7 +17,7 @@ from conftest import GOLDEN, ROOT
 import cluster_model as CM
 import forest_model as FM
 import smhc_model as M
-from test_cluster_gpu import clique, path, sparse_random, star, with_noise
+from test_cluster_gpu import clique, hook_grid, path, sparse_random, star, with_noise
 from test_smhv_gpu import case, configure, zeros_hll
 
 import cuda_selection_criteria_amd as pkg
@@ -30,10 +32,14 @@ SENTINEL = -77
 
 @pytest.fixture
 def grid_hook():
-    """sets the process-wide grid of the record kernels (0 = automatic) and puts the default back"""
+    """sets the process-wide grids of the record kernels and of the vertex kernels (0 = automatic) and puts the defaults back"""
     with Selector(0) as sel:
-        yield lambda blocks: sel.set_param("cluster_blocks", blocks)
-        sel.set_param("cluster_blocks", 0)
+        def set_hooks(blocks, vertex_blocks=0):
+            sel.set_param("cluster_blocks", blocks)
+            sel.set_param("vertex_blocks", vertex_blocks)
+            assert (sel.get_param("cluster_blocks"), sel.get_param("vertex_blocks")) == (blocks, vertex_blocks)
+        yield set_hooks
+        set_hooks(0, 0)
 
 
 # ---- 1. selhip_spanning_forest on graphs built to break a union-find, four value sets, every grid, twice --------------------------------
@@ -41,7 +47,7 @@ def graphs():
     p4097 = path(4097, "ascending")
     g = [("n1", 1, np.zeros((0, 2), dtype=np.int64)), ("n1-loop", 1, np.array([[0, 0]])),
          ("n2-apart", 2, np.zeros((0, 2), dtype=np.int64)), ("n2-edge", 2, np.array([[1, 0]])),
-         ("path-4097", 4097, p4097),
+         ("n1000-apart", 1000, np.zeros((0, 2), dtype=np.int64)), ("path-4097", 4097, p4097),
          ("star-centre-highest", 65537, star(65537, 65536)), ("star-centre-0", 65537, star(65537, 0)),
          ("K300", 300, clique(0, 300)),
          ("two-cliques-bridge", 300, np.concatenate([clique(0, 150), clique(150, 300), np.array([[299, 0]])])),
@@ -116,15 +122,15 @@ def test_spanning_forest(grid_hook, name, n, edges):
         if name.startswith("star") and vname == "null":
             assert len(k) == 65536 and want_rounds == 2
         dvals = None if values is None else torch.from_numpy(np.ascontiguousarray(values, dtype=np.float64)).cuda()
-        for blocks in (0, 1, 2):
-            grid_hook(blocks)
+        for blocks, vblocks in hook_grid((0, 1, 2)):
+            grid_hook(blocks, vblocks)
             first = forest_raw(dev, dvals, n)
             again = forest_raw(dev, dvals, n)
-            assert first[0].tobytes() == again[0].tobytes() and first[1].tobytes() == again[1].tobytes() and first[2:] == again[2:], (name, vname, blocks)
+            assert first[0].tobytes() == again[0].tobytes() and first[1].tobytes() == again[1].tobytes() and first[2:] == again[2:], (name, vname, blocks, vblocks)
             got, got_lab, f, rounds = first
-            assert f == len(k) and got.tobytes() == want.tobytes(), (name, vname, blocks, f, len(k))
-            assert np.array_equal(got_lab, want_lab), (name, vname, blocks)
-            assert rounds == want_rounds, (name, vname, blocks, rounds, want_rounds)
+            assert f == len(k) and got.tobytes() == want.tobytes(), (name, vname, blocks, vblocks, f, len(k))
+            assert np.array_equal(got_lab, want_lab), (name, vname, blocks, vblocks)
+            assert rounds == want_rounds, (name, vname, blocks, vblocks, rounds, want_rounds)
         grid_hook(0)
     # the wrapper: a host list is copied to the device; tensors on the device
     values = value_sets(name, n, edges)["levels"]
@@ -146,8 +152,8 @@ def test_spanning_forest_invalid_entry(grid_hook, bad):
     values[17] = np.nan                                                            # whatever its value
     lib = pkg.hip_lib()
     dev, dvals = torch.from_numpy(edges).cuda(), torch.from_numpy(values).cuda()
-    for blocks in (0, 1):
-        grid_hook(blocks)
+    for blocks, vblocks in hook_grid((0, 1)):
+        grid_hook(blocks, vblocks)
         for vals in (dvals, None):
             ebuf = torch.full(((n - 1 + 2 * GUARD) * 4,), SENTINEL, dtype=torch.int32, device="cuda")
             lbuf = torch.full((n + 2 * GUARD,), SENTINEL, dtype=torch.int32, device="cuda")
@@ -209,11 +215,11 @@ def check_list(sel, rec, cuts, grid_hook, what, every_value=True):
         k, lab = FM.kruskal(recs, n, min_value)
         b, comp, want_rounds = FM.boruvka_rounds(recs, n, min_value)
         assert k == b
-        for blocks in (0, 1):
-            grid_hook(blocks)
+        for blocks, vblocks in hook_grid((0, 1)):
+            grid_hook(blocks, vblocks)
             got = raw_forest(sel, min_value)
-            assert got["n_edges"] == len(k) and got["edges"].tobytes() == FM.as_records(k).tobytes(), (what, min_value, blocks)
-            assert got["labels"].tolist() == lab and got["rounds"] == want_rounds, (what, min_value, blocks, got["rounds"], want_rounds)
+            assert got["n_edges"] == len(k) and got["edges"].tobytes() == FM.as_records(k).tobytes(), (what, min_value, blocks, vblocks)
+            assert got["labels"].tolist() == lab and got["rounds"] == want_rounds, (what, min_value, blocks, vblocks, got["rounds"], want_rounds)
         grid_hook(0)
         clu = sel.cluster(min_value)
         assert np.array_equal(got["labels"], clu["labels"]) and got["n_edges"] == n - clu["n_clusters"], (what, min_value)

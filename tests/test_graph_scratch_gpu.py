@@ -29,8 +29,12 @@ SMALL, LARGE = 70, 300          # more than one wave and less than one 256-threa
 def grid_hook():
     """sets the process-wide grid of the record kernels (0 = automatic) and puts the default back"""
     with Selector(0) as sel:
-        yield lambda blocks: sel.set_param("cluster_blocks", blocks)
-        sel.set_param("cluster_blocks", 0)
+        def set_hooks(blocks, vertex_blocks=0):
+            sel.set_param("cluster_blocks", blocks)
+            sel.set_param("vertex_blocks", vertex_blocks)
+            assert (sel.get_param("cluster_blocks"), sel.get_param("vertex_blocks")) == (blocks, vertex_blocks)
+        yield set_hooks
+        set_hooks(0, 0)
 
 
 def load(sel, oracle, n):

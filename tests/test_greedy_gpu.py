@@ -3,7 +3,9 @@ output is compared for exact equality -- values by their bits -- with tests/gree
 the same edge list or on the records fetched from the pass.  The graphs of (1) are those of test_cluster_gpu.py plus the orders that
 stretch the round scheme: a path whose keys ascend along it (one round per vertex), stars with the centre first and last; each runs
 with the default grid and with the edge kernel's grid forced to 1 and 2 blocks, twice, and the two runs must be byte-equal.  The device's
-round count must lie in [1, rounds of the scheme with every read stale]."""
+round count must lie in [1, rounds of the scheme with every read stale].  The record grids are crossed with the vertex kernels' grid
+("vertex_blocks": sized from n, 1 block, 3 blocks); test_vertex_trips_of_the_context_call does the same for
+every kernel of selhip_ctx_cluster_greedy at 771 genomes."""
 import ctypes as C
 import subprocess
 
@@ -16,7 +18,7 @@ import cluster_model as CM
 import greedy_model as GM
 import smhc_model as M
 import smhv_model as V
-from test_cluster_gpu import clique, path, sparse_random, star, with_noise
+from test_cluster_gpu import clique, hook_grid, path, sparse_random, star, with_noise
 from test_smhv_gpu import case, configure, zeros_hll
 
 import cuda_selection_criteria_amd as pkg
@@ -34,10 +36,14 @@ RULES = {"max_degree": 0, "min_rank": 1, "max_rank": 2, "priority": 3}
 
 @pytest.fixture
 def grid_hook():
-    """sets the process-wide grid of the edge kernels (0 = automatic) and puts the default back"""
+    """sets the process-wide grids of the edge kernels and of the vertex kernels (0 = automatic) and puts the defaults back"""
     with Selector(0) as sel:
-        yield lambda blocks: sel.set_param("cluster_blocks", blocks)
-        sel.set_param("cluster_blocks", 0)
+        def set_hooks(blocks, vertex_blocks=0):
+            sel.set_param("cluster_blocks", blocks)
+            sel.set_param("vertex_blocks", vertex_blocks)
+            assert (sel.get_param("cluster_blocks"), sel.get_param("vertex_blocks")) == (blocks, vertex_blocks)
+        yield set_hooks
+        set_hooks(0, 0)
 
 
 # ---- 1. selhip_greedy_representatives: the graph shapes, the key orders, every grid, twice ------------------------------------------------
@@ -49,6 +55,7 @@ def graphs():
     none = np.zeros((0, 2), dtype=np.int64)
     rev = lambda n: np.arange(n - 1, -1, -1).astype(np.uint64)                       # noqa: E731
     g = [("n1", 1, none, None), ("n1-loop", 1, np.array([[0, 0]]), None), ("n2-apart", 2, none, None), ("n2-edge", 2, np.array([[1, 0]]), None),
+         ("n1000-apart", 1000, none, None),
          ("n2-edge-equal-keys", 2, np.array([[1, 0]]), np.array([9, 9], dtype=np.uint64)),
          ("path-key-vertex", 4097, path(4097, "ascending"), None), ("path-key-reversed", 4097, path(4097, "shuffled"), rev(4097)),
          ("path-key-random", 4097, path(4097, "descending"), random_keys(4097, 3)),
@@ -79,6 +86,21 @@ def want_reps(name, n, edges, keys):
     return _WANT[name]
 
 
+def greedy_raw(dev_pairs, n, keys=None):
+    """selhip_greedy_representatives into a buffer filled with 0xAB, guards on both sides: (flags, rounds).  A vertex the call left
+    unwritten shows (torch.empty would hand a second call the block, and the answer, of the first)"""
+    lib = pkg.hip_lib()
+    buf = torch.full((n + 2 * GUARD,), 0xAB, dtype=torch.uint8, device="cuda")
+    key = None if keys is None else torch.from_numpy(np.ascontiguousarray(keys, dtype=np.uint64).view(np.int64)).cuda()
+    rounds = C.c_int64(-9)
+    rc = lib.selhip_greedy_representatives(dev_pairs.data_ptr() if dev_pairs.numel() else None, int(dev_pairs.shape[0]), n,
+                                           None if key is None else key.data_ptr(), buf.data_ptr() + GUARD, C.byref(rounds), None)
+    assert rc == 0, lib.selhip_last_error(None).decode()
+    out = buf.cpu().numpy()
+    assert np.all(out[:GUARD] == 0xAB) and np.all(out[GUARD + n:] == 0xAB)
+    return out[GUARD:GUARD + n].copy(), rounds.value
+
+
 @pytest.mark.parametrize("name,n,edges,keys", GRAPHS, ids=[g[0] for g in GRAPHS])
 def test_representatives(grid_hook, name, n, edges, keys):
     want, bound = want_reps(name, n, edges, keys)
@@ -98,14 +120,14 @@ def test_representatives(grid_hook, name, n, edges, keys):
         assert want.tolist() == [1, 0]                                                # equal keys: the smaller vertex first
     dev = torch.from_numpy(np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 2)).cuda()
     seen = set()
-    for blocks in (0, 1, 2):
-        grid_hook(blocks)
-        first, rounds = pkg.greedy_representatives(dev, n, keys)
-        again, rounds_again = pkg.greedy_representatives(dev, n, keys)
-        assert first.dtype == np.uint8 and first.tobytes() == again.tobytes(), (name, blocks)
-        assert np.array_equal(first, want), (name, blocks, np.flatnonzero(first != want)[:5])
+    for blocks, vblocks in hook_grid((0, 1, 2)):
+        grid_hook(blocks, vblocks)
+        first, rounds = greedy_raw(dev, n, keys)
+        again, rounds_again = greedy_raw(dev, n, keys)
+        assert first.dtype == np.uint8 and first.tobytes() == again.tobytes(), (name, blocks, vblocks)
+        assert np.array_equal(first, want), (name, blocks, vblocks, np.flatnonzero(first != want)[:5])
         for r in (rounds, rounds_again):
-            assert 1 <= r <= bound, (name, blocks, r, bound)
+            assert 1 <= r <= bound, (name, blocks, vblocks, r, bound)
         seen.add(rounds)
     print(f"{name}: rounds {sorted(seen)} of at most {bound}")
     grid_hook(0)
@@ -123,8 +145,8 @@ def test_representatives_invalid_entry(grid_hook, bad):
     lib = pkg.hip_lib()
     dev = torch.from_numpy(edges).cuda()
     keys = torch.from_numpy(random_keys(n, 2).view(np.int64)).cuda()
-    for blocks, key_ptr in ((0, None), (1, keys.data_ptr())):
-        grid_hook(blocks)
+    for blocks, vblocks, key_ptr in ((0, 0, None), (1, 0, keys.data_ptr()), (0, 1, keys.data_ptr()), (0, 3, None), (1, 1, None)):
+        grid_hook(blocks, vblocks)
         buf = torch.full((n + 2 * GUARD,), 0xAB, dtype=torch.uint8, device="cuda")
         rounds = C.c_int64(-9)
         rc = lib.selhip_greedy_representatives(dev.data_ptr(), len(edges), n, key_ptr, buf.data_ptr() + GUARD, C.byref(rounds), None)
@@ -132,6 +154,7 @@ def test_representatives_invalid_entry(grid_hook, bad):
         assert rc == -1 and rounds.value == -9, (rc, msg)
         assert "2 invalid entries" in msg and f"[0, {n})" in msg and ("entry 17 is one" in msg or "entry 230 is one" in msg), msg
         assert np.all(buf.cpu().numpy() == 0xAB)                                      # nothing written, the guards included
+    grid_hook(0)
     # the same list without them is fine, and the guards stay
     edges[[17, 230]] = (0, 0)
     buf = torch.full((n + 2 * GUARD,), 0xAB, dtype=torch.uint8, device="cuda")
@@ -242,9 +265,9 @@ def test_greedy_behind_planted_pass(grid_hook):
                 for rule, code in RULES.items():
                     p = prio if rule == "priority" else None
                     want = GM.clusters(rec, n, min_value, rule, p)
-                    for blocks in (0, 1):
-                        grid_hook(blocks)
-                        assert_same(raw_greedy(sel, min_value, code, p), want, (n, min_value, rule, blocks))
+                    for blocks, vblocks in hook_grid((0, 1)):
+                        grid_hook(blocks, vblocks)
+                        assert_same(raw_greedy(sel, min_value, code, p), want, (n, min_value, rule, blocks, vblocks))
                     n_mixed += 1 < want["n_clusters"] < n
             grid_hook(0)
             # every output pointer NULL in turn: the others are still right, nothing else is written
@@ -270,6 +293,31 @@ def test_greedy_behind_planted_pass(grid_hook):
         with pytest.raises(ValueError, match="order"):
             sel.cluster_greedy(order="degree")
     assert n_mixed > 0
+
+
+def test_vertex_trips_of_the_context_call(grid_hook):
+    """771 genomes = three blocks of 256 and three lanes: with the vertex kernels in one block every loop of selhip_ctx_cluster_greedy
+    comes round four times and ends in a wave of three lanes; with three blocks it comes round twice.  Every output, each order rule
+    and a caller's priority, two cuts; twice, byte-equal"""
+    n, m = 771, 256
+    with Selector(0) as sel:
+        rec = planted_pass(sel, n, m, random_weighted(n, 771), seed=771)                 # a sparse random graph: clusters across the trips
+        prio = np.random.default_rng(n).integers(0, 4, size=n).astype(np.uint32)         # four levels: ties, broken by the smaller rank
+        prio[n - 1] = 0xFFFFFFFF
+        for min_value in (-np.inf, 8 / m):
+            for rule, code in RULES.items():
+                p = prio if rule == "priority" else None
+                want = GM.clusters(rec, n, min_value, rule, p)
+                far = np.flatnonzero(np.arange(n) // 256 != want["rep_of"] // 256)       # members a trip or more away from their representative
+                assert 1 < want["n_clusters"] < n and want["sizes"].max() > 2 and len(far) > 100, (rule, want["n_clusters"], len(far))
+                for blocks, vblocks in hook_grid((0, 1)):
+                    grid_hook(blocks, vblocks)
+                    first, again = raw_greedy(sel, min_value, code, p), raw_greedy(sel, min_value, code, p)
+                    assert all(first[k].tobytes() == again[k].tobytes() for k in OUTPUTS), (rule, blocks, vblocks)
+                    assert_same(first, want, (min_value, rule, blocks, vblocks))
+        grid_hook(0, 3)
+        assert len(sel.run(2.0, MODE_SMH, 7, 3)) == 0                                   # no record: greedy_singletons_kernel, two trips
+        assert_same(raw_greedy(sel, -np.inf, 0), GM.clusters(rec[:0], n), "empty list")
 
 
 # ---- 3. the chain A - B - C with A - C below the cut ------------------------------------------------------------------------------------------

@@ -1,6 +1,8 @@
 """The dense-matrix hierarchy on the GPU (selhip_linkage, selhip_ctx_linkage; include/selection_hip.h section 2k).
 Every output is compared bit for bit with tests/linkage_model.py, the sequential model in numpy, run on the same matrix; outputs go
-into guarded buffers; every case runs twice and the two runs must be byte-equal."""
+into guarded buffers; every case runs twice and the two runs must be byte-equal.  Section 1b runs the slot kernels (lk_init_kernel,
+lk_all_kernel, lk_book_kernel) under the process-wide grid hook "vertex_blocks", 1c the update kernel's stride over the pairs of a round
+(n = 8 200) and 3b the distance transform's second trip (1 500 genomes): DESIGN.md section 32."""
 import ctypes as C
 import subprocess
 
@@ -25,6 +27,22 @@ METHODS = ("single", "complete", "average", "weighted")
 SCAN_COLS = 512                # kLkScanCols of csrc/kernel_linkage.cuh: the columns one sweep of a row-scan workgroup covers
 SIZES = [1, 2, 3, 63, 64, 65, 255, 256, 257, 511, 512, 513, 2 * SCAN_COLS + 7]
 RESCAN_SEEDS = (4, 36, 48)     # three-level matrices under single linkage whose model takes the rescan branch (asserted below)
+VERTEX_BLOCKS = (1, 3)         # the slot kernels' grid under the hook: strides of 256 and of 768 slots
+PAIR_CAPS = {"average": 200.0, "complete": 300.0, "single": 110.0, "weighted": 200.0}      # max_height for the "pairs" matrices: a few rounds and one rescan
+UPDATE_ROWS = 4096             # the rows of lk_update_kernel's grid at most (host_linkage.hpp): a round of more pairs strides over them
+DISTANCE_CELLS = 8192 * 256    # the cells one trip of lk_distance_kernel's grid covers at most
+
+
+@pytest.fixture
+def vertex_hook():
+    """sets the process-wide grid of the kernels that take a lane per slot (0 = automatic) and puts the default back"""
+    with Selector(0) as sel:
+        def set_hook(vertex_blocks):
+            sel.set_param("vertex_blocks", vertex_blocks)
+            assert sel.get_param("vertex_blocks") == vertex_blocks
+        yield set_hook
+        set_hook(0)
+        sel.set_param("cluster_blocks", 0)
 
 
 def three_levels(seed):
@@ -33,15 +51,20 @@ def three_levels(seed):
     return rng.choice([0.25, 0.5, 0.75], size=(n, n))
 
 
+def pairs_matrix(n, rng):
+    """points on a line in n / 2 close pairs far apart: the first round pairs them all"""
+    gaps = np.repeat(np.cumsum(100.0 + 50.0 * rng.random(n // 2 + 1)), 2)[:n]
+    p = gaps + np.tile([0.0, 1.0], n // 2 + 1)[:n] * (0.5 + 0.4 * rng.random(n))
+    return np.abs(p[:, None] - p[None, :])
+
+
 def matrices(n):
     """{value set: n x n float64}; only the strict upper triangle counts"""
     rng = np.random.default_rng(1000 + n)
     sets = {"distinct": (rng.permutation(n * n).reshape(n, n) + rng.random((n, n)) / 2) / float(max(n * n, 1)),
             "levels": rng.choice([0.25, 0.5, 0.75], size=(n, n)),
             "specials": rng.choice([np.inf, -0.0, 0.0, 5e-324, -1.5, -0.25, 0.25, 1.0, 3.0], size=(n, n))}
-    gaps = np.repeat(np.cumsum(100.0 + 50.0 * rng.random(n // 2 + 1)), 2)[:n]
-    p = gaps + np.tile([0.0, 1.0], n // 2 + 1)[:n] * (0.5 + 0.4 * rng.random(n))
-    sets["pairs"] = np.abs(p[:, None] - p[None, :])
+    sets["pairs"] = pairs_matrix(n, rng)
     if n <= 257:                                                   # (the model rescans every row in each of their n - 1 rounds)
         sets["equal"] = np.full((n, n), 0.5)
         c = np.cumsum(1.5 ** np.arange(n))
@@ -84,6 +107,16 @@ def same(got, want, what):
     assert np.array_equal(sizes, want["sizes"]), what
 
 
+_WANT = {}
+
+
+def model(n, vname, method, dist):
+    """the model's answer for matrices(n)[vname], computed once for the tests that share it"""
+    if (n, vname, method) not in _WANT:
+        _WANT[n, vname, method] = LM.linkage_model(dist, method)
+    return _WANT[n, vname, method]
+
+
 # ---- 1. selhip_linkage: every size, layout, method and value set against the model, twice -----------------------------------------------
 @pytest.mark.parametrize("n", SIZES)
 def test_linkage_against_the_model(n):
@@ -91,7 +124,7 @@ def test_linkage_against_the_model(n):
         for method in METHODS:
             if n >= 511 and method == "single" and vname in ("levels", "specials"):
                 continue                                           # (n - 1 rounds of full rescans: seconds of model time; n <= 257 covers them)
-            want = LM.linkage_model(dist, method)
+            want = model(n, vname, method, dist)
             assert want["n_merges"] == max(n - 1, 0)
             if vname == "equal" and n > 1:
                 assert want["rounds"] == n and want["pairs_per_round"] == [1] * (n - 1) + [0]
@@ -114,6 +147,63 @@ def test_rescan_rounds(seed):
         same(linkage_raw(dist, "single", ld_extra=ld_extra, offset=offset), want, seed)
     for method in METHODS[1:]:
         same(linkage_raw(dist, method), LM.linkage_model(dist, method), (seed, method))
+
+
+# ---- 1b. the slot kernels in 1 and 3 blocks: every trip of lk_init, lk_all and lk_book ends in a ballot and a lane-ordered scatter ----------
+@pytest.mark.parametrize("n", [257, 513, 2 * SCAN_COLS + 7])
+def test_slot_kernels_under_the_vertex_hook(vertex_hook, n):
+    """257, 513 and 1 031 slots in blocks of 256: under one block 2, 3 and 5 trips, the last of 1, 1 and 7 lanes; under three blocks
+    the last trip of 1 031 holds 263.  The capped "pairs" hierarchy ends in a rescan round: lk_all_kernel then lists the active slots
+    with inactive ones in every trip"""
+    sets = matrices(n)
+    for vname in ("distinct", "levels", "pairs"):
+        for method in METHODS:
+            if n >= 511 and method == "single" and vname == "levels":
+                continue                                           # (as above)
+            want = model(n, vname, method, sets[vname])
+            for blocks in VERTEX_BLOCKS:
+                vertex_hook(blocks)
+                first = linkage_raw(sets[vname], method)
+                again = linkage_raw(sets[vname], method)
+                assert all(np.asarray(x).tobytes() == np.asarray(y).tobytes() for x, y in zip(first, again)), (n, vname, method, blocks)
+                same(first, want, (n, vname, method, blocks))
+            same(linkage_raw(sets[vname], method, ld_extra=3, offset=1), want, (n, vname, method, blocks, "8-byte"))
+    for method, cap in PAIR_CAPS.items():
+        want = LM.linkage_model(sets["pairs"], method, cap)
+        assert want["rescans"] == 1 and 0 < want["n_merges"] < n - 1 and want["pairs_per_round"][0] == n // 2
+        for blocks in VERTEX_BLOCKS:
+            vertex_hook(blocks)
+            same(linkage_raw(sets["pairs"], method, cap), want, (n, "pairs, capped", method, blocks))
+
+
+def test_rescan_rounds_under_the_vertex_hook(vertex_hook):
+    """(these matrices have fewer than 48 slots -- one trip of one block; the rescan rounds over several trips are the capped ones above)"""
+    dist = three_levels(RESCAN_SEEDS[0])
+    want = LM.linkage_model(dist, "single")
+    assert want["rescans"] > 0
+    for blocks in VERTEX_BLOCKS:
+        vertex_hook(blocks)
+        same(linkage_raw(dist, "single"), want, (RESCAN_SEEDS[0], blocks))
+
+
+# ---- 1c. more pairs in a round than lk_update_kernel's grid has rows: the stride p += gridDim.y ------------------------------------------------
+@pytest.mark.parametrize("method", METHODS)
+def test_update_kernel_pair_stride(method):
+    """n = 8 200 points in 4 100 close pairs: round 1 pairs them all, so the update of the distances serves the pairs 4 096 .. 4 099 -- the
+    slots 8 192 .. 8 199 -- in a second trip over the grid's rows.  The records of round 1 do not depend on the update; the later merges
+    do, and the model has some among the slots from 8 192 on.  Capped (PAIR_CAPS): the whole hierarchy takes the model minutes"""
+    n = 2 * UPDATE_ROWS + 8
+    dist = pairs_matrix(n, np.random.default_rng(1000 + n))
+    want = LM.linkage_model(dist, method, PAIR_CAPS[method])
+    assert want["pairs_per_round"][0] == n // 2 == 4100 > UPDATE_ROWS and want["rescans"] == 1
+    late = want["merges"][n // 2:]
+    served_late = [(int(a), int(b)) for a, b in zip(late["i"], late["k"]) if max(a, b) >= 2 * UPDATE_ROWS]
+    assert len(served_late) >= 1 and (method == "single" or len(served_late) == 3), served_late
+    print(f"{method}: rounds {want['rounds']}, pairs per round {want['pairs_per_round'][:4]}, merges {want['n_merges']}, late merges of slots >= 8192: {served_late}")
+    for ld_extra, offset in ((0, 0), (3, 1)):                      # the 16-byte path and one 8-byte layout
+        got = linkage_raw(dist, method, PAIR_CAPS[method], ld_extra=ld_extra, offset=offset)
+        torch.cuda.empty_cache()                                   # (538 MB of matrix: gone before the next one)
+        same(got, want, (method, ld_extra, offset))
 
 
 def test_empty_and_wrapper():
@@ -265,6 +355,34 @@ def test_context_synthetic_set(oracle):
         sel.upload(hll, aux, cards)
         assert np.isnan(sel.matrix("jaccard").cpu().numpy()[0, 1])
         check_context(sel, ("jaccard", "max_containment", "smh_jaccard"))
+
+
+# ---- 3b. more cells than one trip of lk_distance_kernel's grid covers ---------------------------------------------------------------------
+def test_context_distance_second_trip():
+    """1 500 genomes, 2 250 000 cells: the distance transform comes round for the cells from 2 097 152 on -- row 1 398, column 304.  Five
+    genomes have empty HLL sketches and J is NaN between them: three in the first rows, two past row 1 398, so NaN cells lie in both
+    trips.  The rows stay in generation order and the device computes the cardinalities: a matrix call asks for no ranking, and ranked
+    rows would have every empty sketch in front"""
+    n = 1500
+    empty = (0, 1, 2, 1450, 1499)
+    hll, aux = synth("cfg2-spread", n)
+    hll = hll.copy()
+    hll[list(empty)] = 0
+    assert n * n > DISTANCE_CELLS
+    with Selector(0) as sel:
+        sel.upload(hll, aux, None)
+        assert np.flatnonzero(sel.cards() == 0).tolist() == list(empty)
+        nan_at = np.flatnonzero(np.isnan(sel.matrix("jaccard").cpu().numpy().reshape(-1)))
+        assert nan_at.min() < DISTANCE_CELLS <= 1450 * n + 1499 and 1450 * n + 1499 in nan_at and 1499 * n + 1450 in nan_at, (nan_at.min(), nan_at.max())
+        dist = distance_of(sel, "jaccard")
+        want = LM.linkage_model(dist, "average")
+        same(raw_ctx_linkage(sel, "jaccard", "average"), want, "average")
+        assert sel.get_param("linkage_rowscans_last") == want["rowscans"] and sel.get_param("linkage_rescans_last") == want["rescans"]
+        h = np.sort(want["merges"]["jaccard"])
+        cap = float(h[len(h) // 2])
+        capped = LM.linkage_model(dist, "complete", cap)
+        assert 0 < capped["n_merges"] < n - 1
+        same(raw_ctx_linkage(sel, "jaccard", "complete", cap), capped, "complete, capped")
 
 
 def test_context_influenza(monkeypatch):

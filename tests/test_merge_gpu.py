@@ -1,6 +1,9 @@
 """Sketches merged by group on the device: selhip_merge_sketches against the numpy model (tests/merge_model.py) at
 the smallest shapes at which its counting sort, its levels and its two row paths can go wrong; the context entry behind both
-clusterings; the merged rows as the set of a second context; and the builder identity.  Every comparison is bit for bit."""
+clusterings; the merged rows as the set of a second context; and the builder identity.  Every comparison is bit for bit.  The two
+kernels that take a lane per member row (the count and the scatter of the counting sort) are grid-stride loops: the primitive and the
+context entry also run with the process-wide hook "vertex_blocks" at 1 and 3 blocks, so that 335 rows take two trips and the 4 102
+rows of test_three_levels seventeen and six."""
 import ctypes as C
 
 import numpy as np
@@ -21,6 +24,19 @@ S = MERGE_SEGMENT
 FILL = 0xEE
 U64_MAX = np.uint64(0xFFFFFFFFFFFFFFFF)
 SIZES = (0, 1, 2, S - 1, S, S + 1, 2 * S + 3)          # one group of each size in one call
+VERTEX_BLOCKS = (0, 1, 3)      # the row kernels' grid: sized from n, one block, three blocks
+
+
+@pytest.fixture
+def vertex_hook():
+    """sets the process-wide grid of the kernels that take a lane per row (0 = automatic) and puts the default back"""
+    with Selector(0) as sel:
+        def set_hook(vertex_blocks):
+            sel.set_param("vertex_blocks", vertex_blocks)
+            assert sel.get_param("vertex_blocks") == vertex_blocks
+        yield set_hook
+        set_hook(0)
+        sel.set_param("cluster_blocks", 0)
 
 
 def edge_groups(seed, sizes=SIZES, loose=9):
@@ -89,13 +105,18 @@ def assert_is_model(out, want, G, what=""):
         assert (out[key][G:].view(np.uint8) == FILL).all(), (what, key, "wrote past its rows")
 
 
-def check_primitive(seed, groups, G, p=None, m=None, p_aux=None, what=""):
+def check_primitive(seed, groups, G, p=None, m=None, p_aux=None, what="", hook=None):
+    """hook: the vertex_hook fixture's setter -- the call then runs under every grid of VERTEX_BLOCKS"""
     n = len(groups)
     hll, smh, aux = random_rows(seed, n, p, m, p_aux)
     want = M.merge_all(hll, smh, aux, groups, G)
-    rc, out = raw_merge(to_dev(hll), to_dev(smh), to_dev(aux), to_dev(groups) if n else torch.zeros(1, dtype=torch.int32, device=DEV), n, G)
-    assert rc == 0, (what, pkg.hip_lib().selhip_last_error(None).decode())
-    assert_is_model(out, want, G, what)
+    rows = to_dev(hll), to_dev(smh), to_dev(aux), to_dev(groups) if n else torch.zeros(1, dtype=torch.int32, device=DEV)
+    for blocks in VERTEX_BLOCKS if hook else (0,):
+        if hook:
+            hook(blocks)
+        rc, out = raw_merge(*rows, n, G)
+        assert rc == 0, (what, blocks, pkg.hip_lib().selhip_last_error(None).decode())
+        assert_is_model(out, want, G, (what, blocks))
     return hll, smh, aux, want
 
 
@@ -106,10 +127,10 @@ SHAPES = [(4, 1, 4), (4, 3, 8), (14, 96, 4), (14, 512, 8), (4, 2048, 4), (14, No
 
 
 @pytest.mark.parametrize("p,m,p_aux", SHAPES)
-def test_primitive_is_the_model(p, m, p_aux):
+def test_primitive_is_the_model(vertex_hook, p, m, p_aux):
     groups, G = edge_groups(17)
     assert list(M.sizes(groups, G)) == list(SIZES) and (groups == -1).sum() == 9
-    hll, smh, aux, want = check_primitive(100 + 7 * (p or 0) + (m or 0) + 3 * (p_aux or 0), groups, G, p, m, p_aux, (p, m, p_aux))
+    hll, smh, aux, want = check_primitive(100 + 7 * (p or 0) + (m or 0) + 3 * (p_aux or 0), groups, G, p, m, p_aux, (p, m, p_aux), hook=vertex_hook)
     if hll is not None:
         assert not want["hll"][0].any() and np.array_equal(want["hll"][1], hll[groups == 1][0])      # empty: zeros; singleton: a copy
         assert p != 14 or (want["hll"][6] == 255).mean() > 0.3                                     # 131 random bytes: the maximum is often 255
@@ -133,17 +154,17 @@ def test_primitive_every_byte_value():
     assert rc == 0 and np.array_equal(out["hll"][:half], want)
 
 
-def test_three_levels():
+def test_three_levels(vertex_hook):
     """one group of S^2 + 1 members: S + 1 partial rows, then 2, then the row (p = 4 and m = 2 keep it to a few hundred KiB)"""
     n = S * S + 1
     groups = np.zeros(n + 5, dtype=np.int32)
     groups[[3, 77, n // 2, n, n + 4]] = -1
-    hll, smh, _, want = check_primitive(33, groups, 1, p=4, m=2, what="three levels")
+    hll, smh, _, want = check_primitive(33, groups, 1, p=4, m=2, what="three levels", hook=vertex_hook)
     assert want["sizes"][0] == n
     # ... and beside other groups, ids interleaved: the partial rows of every group lie in group order
     groups = np.random.default_rng(5).permutation(np.concatenate([np.zeros(3, dtype=np.int32), np.full(n, 1, dtype=np.int32),
                                                                   np.full(S + 1, 3, dtype=np.int32), np.full(4, -1, dtype=np.int32)]))
-    check_primitive(34, groups, 4, p=4, m=3, p_aux=4, what="three levels, four groups")
+    check_primitive(34, groups, 4, p=4, m=3, p_aux=4, what="three levels, four groups", hook=vertex_hook)
 
 
 def test_empty_shapes():
@@ -263,7 +284,7 @@ def assert_context_merge(sel, res, groups, G, hll, aux, aux_hll, what):
 
 
 @pytest.mark.parametrize("linkage", ["single", "greedy"])
-def test_context_merge_behind_a_clustering(synth_set, linkage):
+def test_context_merge_behind_a_clustering(synth_set, vertex_hook, linkage):
     cfg, (hll_t, aux_t, cards_t, ah_t), (hll, aux, aux_hll) = synth_set
     r, b = pkg.banding(cfg.m, cfg.tau)
     with Selector(0) as sel:
@@ -275,9 +296,11 @@ def test_context_merge_behind_a_clustering(synth_set, linkage):
         G = res["n_clusters"]
         assert 1 < G < cfg.n_genomes and res["sizes"].max() > 1
         before = snapshot(sel) + (sel.get_param("greedy_clusters_last"),)
-        merged = sel.merge(res)
-        assert snapshot(sel) + (sel.get_param("greedy_clusters_last"),) == before          # list, statistics, attempts, "clusters_last": as they were
-        got = assert_context_merge(sel, merged, res["clusters"], G, hll, aux, None, linkage)
+        for blocks in VERTEX_BLOCKS[::-1]:                                              # (the default grid last: the calls below run under it)
+            vertex_hook(blocks)
+            merged = sel.merge(res)
+            assert snapshot(sel) + (sel.get_param("greedy_clusters_last"),) == before      # list, statistics, attempts, "clusters_last": as they were
+            got = assert_context_merge(sel, merged, res["clusters"], G, hll, aux, None, (linkage, blocks))
         assert np.array_equal(got["sizes"], res["sizes"])
         # a device tensor of ids, n_groups from the ids, host arrays out
         host = sel.merge(torch.from_numpy(res["clusters"]).to(DEV), to_host=True)
@@ -291,14 +314,16 @@ def test_context_merge_behind_a_clustering(synth_set, linkage):
         assert snapshot(sel) + (sel.get_param("greedy_clusters_last"),) == before
 
 
-def test_context_groups_of_any_kind(synth_set):
+def test_context_groups_of_any_kind(synth_set, vertex_hook):
     """ids that are no clustering: empty groups, genomes in no group, a group longer than the segment"""
     cfg, (hll_t, aux_t, cards_t, _), (hll, aux, _) = synth_set
     n = cfg.n_genomes
     groups = np.random.default_rng(8).permutation(np.concatenate([np.full(S + 5, 2), np.full(3, 0), np.full(n - S - 8 - 10, 4), np.full(10, -1)])).astype(np.int32)
     with Selector(0) as sel:
         sel.attach(hll_t, aux_t, cards_t)
-        got = assert_context_merge(sel, sel.merge(groups, 6), groups, 6, hll, aux, None, "any ids")
+        for blocks in VERTEX_BLOCKS[::-1]:                                              # (the default grid last: the calls below run under it)
+            vertex_hook(blocks)
+            got = assert_context_merge(sel, sel.merge(groups, 6), groups, 6, hll, aux, None, ("any ids", blocks))
         assert list(got["sizes"][[1, 3, 5]]) == [0, 0, 0] and list(got["cards"][[1, 3, 5]]) == [0.0, 0.0, 0.0]
         with pytest.raises(SelhipError, match="invalid entries") as err:
             sel.merge(groups, 4)

@@ -18,7 +18,7 @@ GPU call.
   test_same_shape_side_by_side   two contexts that hold sets of ONE shape (BIG, HIGHREG) and swap them: a cache key or a scratch buffer
                       shared between contexts meets a context in which every index and every key of the other one is valid
   test_walks_in_parallel[seed]   four threads, 60 free-running random steps each as test_walk takes them; one of them toggles the
-                      process-wide grid hook "cluster_blocks" among 0, 1 and 7 between its steps
+                      process-wide grid hooks "cluster_blocks" and "vertex_blocks" among 0, 1 and 7 between its steps
   test_free_standing_entries_in_parallel   the context-free entries from three threads on three sets, and their first calls in a fresh
                       child process (tests/threads_child.py)
   test_context_churn_beside_work   one thread creates, loads, runs and destroys contexts (hipMalloc / hipFree: device-wide waits) while two work
@@ -260,10 +260,12 @@ def test_same_shape_side_by_side(lib, streams):
 # ---- (c) random walks, four at once ------------------------------------------------------------------------------------------------------
 WALK_STARTS = ("BIG", "NARROW", "WIDE", "HIGHREG")
 CLUSTER_BLOCKS = (0, 1, 7)
+VERTEX_BLOCKS = (0, 1, 7)
 
 
 def walk(me, w, rng, steps, toggles, one_launch):
-    """test_walk's steps on one context; toggles: this thread also sets the process-wide "cluster_blocks" between its steps.  one_launch:
+    """test_walk's steps on one context; toggles: this thread also sets the process-wide "cluster_blocks" and "vertex_blocks" between its
+    steps.  one_launch:
     this thread may take the one-launch small pass (the operation smh_a-small_pass, the knob "small_pass").  Two such kernels fit the
     device together (512 block slots for twice 256 blocks); three need not, and the library then answers through the bounded wait of
     the kernel's grid barrier and the regular chain -- rightly, but the operations assert the route they asked for ("small_pass_used")"""
@@ -276,6 +278,9 @@ def walk(me, w, rng, steps, toggles, one_launch):
             value = int(rng.choice(CLUSTER_BLOCKS))
             live.log.append(("cluster_blocks", value))
             live.sel.set_param("cluster_blocks", value)
+            value = int(rng.choice(VERTEX_BLOCKS))
+            live.log.append(("vertex_blocks", value))
+            live.sel.set_param("vertex_blocks", value)
         kind = rng.choice(["db", "queries", "knob", "op", "op", "op"])
         if kind == "db":
             live.replace(str(rng.choice(R.NAMES)), str(rng.choice(["upload", "attach"])))
@@ -312,6 +317,7 @@ def test_walks_in_parallel(lib, streams, seed):
     finally:
         if not T.hip_failed() and made[0] is not None:
             made[0].live.sel.set_param("cluster_blocks", 0)
+            made[0].live.sel.set_param("vertex_blocks", 0)
         close_all(made)
 
 
