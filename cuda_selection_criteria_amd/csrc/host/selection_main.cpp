@@ -118,7 +118,10 @@
 //   -J <file>   the merges of the same hierarchy, one line each in the order the device emitted them (children before parents):
 //               path_a <TAB> path_b <TAB> height <TAB> size   (the merged cluster lives on under path_a, its smallest rank; the height
 //               printed as std::to_string does).  Alone or beside -N
-//   -X <method> with -N / -J: average (default, UPGMA), complete, weighted (WPGMA) or single
+//   -X <method> with -N / -J: average (default, UPGMA), complete, weighted (WPGMA) or single; or nj: the neighbour-joining tree of the same
+//               distances (selhip_ctx_neighbor_joining) in place of a hierarchy -- -N writes the unrooted tree rooted on its last join's
+//               edge, with the joins' own branch lengths (not ultrametric; a length may be negative), -J one line per join:
+//               path_a <TAB> path_b <TAB> len_a <TAB> len_b
 //   -x          usage
 #include <sys/stat.h>
 #include <unistd.h>
@@ -624,6 +627,85 @@ static int run_linkage(const std::string& list_file, int measure, int method, un
     return r ? 4 : hr;
 }
 
+constexpr int kTreeNj = 100;   // -X nj: no SELHIP_LINKAGE_* code
+
+// -N / -J with -X nj: no pass; the neighbour-joining tree of the list's dense matrix (selhip_ctx_neighbor_joining) as a Newick tree
+// and / or as its joins.  measure, m: as for run_linkage
+static int run_nj(const std::string& list_file, int measure, unsigned m, int fp_mode, int threads) {
+    selhost_dataset* ds = nullptr;
+    if (selhost_dataset_load(&ds, list_file.c_str(), m, 0, fp_mode, threads)) { std::cerr << "selection: -N / -J: " << selhost_last_error() << "\n"; return 1; }
+    const int64_t n = selhost_dataset_size(ds);
+    const size_t cap = (size_t)std::max<int64_t>(n - 1, 0);
+    std::vector<selhip_nj_join_t> joins(cap);
+    std::vector<uint64_t> no_smh(m ? 0 : (size_t)std::max<int64_t>(1, n), 0);
+    selhip_ctx* ctx = nullptr;
+    int r = selhip_device_count() > 0 ? selhip_ctx_create(&ctx, 0) : SELHIP_E_NODEVICE;
+    if (r) {
+        std::cerr << "selection: no MI355X (gfx950) device available: " << selhip_last_error(nullptr) << "\n";
+        selhost_dataset_free(ds);
+        return 3;
+    }
+    void* d_joins = nullptr;
+    int64_t f = 0;
+    selhip_ctx_set_fp_mode(ctx, fp_mode);
+    r = selhip_ctx_upload(ctx, selhost_dataset_hll(ds), m ? selhost_dataset_aux(ds) : no_smh.data(), selhost_dataset_cards(ds), n, m ? (int)m : 1, 14);
+    if (!r && cap) r = selhip_malloc(&d_joins, cap * sizeof(selhip_nj_join_t));
+    if (!r) r = selhip_ctx_neighbor_joining(ctx, measure, static_cast<selhip_nj_join_t*>(d_joins), &f);
+    if (!r && f > 0) r = selhip_memcpy_d2h(joins.data(), d_joins, (size_t)f * sizeof(selhip_nj_join_t));
+    if (r) std::cerr << "selection: " << selhip_last_error(ctx) << "\n";
+    selhip_ctx_destroy(ctx);
+    if (d_joins) selhip_free(d_joins);
+    int hr = 0;
+    if (!r && !g_merges_file.empty()) {
+        std::string text;
+        for (int64_t s = 0; s < f; ++s)
+            text += std::string(selhost_dataset_name(ds, joins[(size_t)s].a)) + "\t" + selhost_dataset_name(ds, joins[(size_t)s].b) + "\t" +
+                    std::to_string(joins[(size_t)s].len_a) + "\t" + std::to_string(joins[(size_t)s].len_b) + "\n";
+        std::ofstream o(g_merges_file, std::ios::binary);
+        o << text;
+        o.close();
+        if (!o) { std::cerr << "selection: -J: cannot write '" << g_merges_file << "'\n"; hr = 5; }
+    }
+    if (!r && !hr && !g_newick_file.empty()) {
+        // nodes 0 .. n - 1 the leaves, n + s the node join s made; root_of[slot] = the node that lives in the slot now
+        struct Node { int64_t left, right; double len_left, len_right; };
+        std::vector<Node> node((size_t)n + (size_t)f, Node{-1, -1, 0.0, 0.0});
+        std::vector<int64_t> root_of((size_t)std::max<int64_t>(n, 1));
+        for (int64_t g = 0; g < n; ++g) root_of[(size_t)g] = g;
+        for (int64_t s = 0; s < f; ++s) {
+            const selhip_nj_join_t& e = joins[(size_t)s];
+            node[(size_t)(n + s)] = Node{root_of[(size_t)e.a], root_of[(size_t)e.b], e.len_a, e.len_b};
+            root_of[(size_t)e.a] = n + s;
+        }
+        // written without recursion, as run_linkage writes its tree: the last join's node is the root (the slot that is left is the
+        // smallest of all: a join lives on in its smaller slot)
+        struct Item { int64_t id; double len; bool has_len; std::string text; };
+        std::string text;
+        std::vector<Item> stack;
+        if (n > 0) stack.push_back(Item{root_of[0], 0.0, false, ""});
+        while (!stack.empty()) {
+            Item it = std::move(stack.back());
+            stack.pop_back();
+            if (it.id < 0) { text += it.text; continue; }
+            const Node& nd = node[(size_t)it.id];
+            const std::string tail = it.has_len ? ":" + newick_number(it.len) : "";
+            if (nd.left < 0) { text += newick_name(selhost_dataset_name(ds, it.id)) + tail; continue; }
+            stack.push_back(Item{-1, 0.0, false, ")" + tail});
+            stack.push_back(Item{nd.right, nd.len_right, true, ""});
+            stack.push_back(Item{-1, 0.0, false, ","});
+            stack.push_back(Item{nd.left, nd.len_left, true, ""});
+            text += "(";
+        }
+        text += ";\n";
+        std::ofstream o(g_newick_file, std::ios::binary);
+        o << text;
+        o.close();
+        if (!o) { std::cerr << "selection: -N: cannot write '" << g_newick_file << "'\n"; hr = 5; }
+    }
+    selhost_dataset_free(ds);
+    return r ? 4 : hr;
+}
+
 // -I ... -P: no pass; the genomes of the list merged by the groups of g_groups_file.  m, p_aux: the sketch files in play, as for a pass
 static int run_merge_groups(const std::string& list_file, unsigned m, unsigned p_aux, int fp_mode, int threads) {
     selhost_dataset* ds = nullptr;
@@ -711,7 +793,7 @@ int main(int argc, char* argv[]) {
                                    "       -l list [-p pair_file | -K best_per_genome [-R rows]] ... -L clusters.tsv [-T min_value] [-Y max_degree|min_rank|max_rank]   (besides the output: the single-linkage clusters of the selected pairs, one line per genome: path, cluster, size, degree, representative)\n"
                                    "       ... -L clusters.tsv -Z single|greedy [-T min_value] [-Y max_degree|min_rank|max_rank | -W scores.tsv]   (-Z greedy: greedy representative clusters, CD-HIT style: genomes visited in the -Y order or by descending score, every other genome to its most similar representative; a sixth column: value to the representative)\n"
                                    "       -l list [-p pair_file | -K best_per_genome [-R rows]] ... -H forest.tsv [-T min_value]   (besides the output: the maximum spanning forest of the selected pairs = the merges of the single-linkage dendrogram, one line per edge, best first: path_a, path_b, value; may stand beside -L)\n"
-                                   "       -l list -N tree.nwk [-J merges.tsv] [-X average|complete|weighted|single] [-E smh -a bytes | -S max_containment] [-M out.tsv]   (no selection: the hierarchy of the dense matrix under 1 - similarity, on the device: a Newick tree and / or one line per merge: path_a, path_b, height, size)\n"
+                                   "       -l list -N tree.nwk [-J merges.tsv] [-X average|complete|weighted|single|nj] [-E smh -a bytes | -S max_containment] [-M out.tsv]   (no selection: the hierarchy of the dense matrix under 1 - similarity, on the device: a Newick tree and / or one line per merge: path_a, path_b, height, size; -X nj: the neighbour-joining tree, one line per join: path_a, path_b, len_a, len_b)\n"
                                    "       ... -c hll_a|hll_an -a bytes -D   (with -l, -q, -p, -k, -K, -g, -B: no .hll_<p> file is read, the auxiliary HLL sketches are folded from the .hll registers)\n"
                                    "       ... -L clusters.tsv [-Z ...] -P dir   (besides the output: one merged sketch set per cluster in dir -- cluster_<id>.hll, .smh<m>, .hll_<p> -- and dir/filelist.txt, a database for -l)\n"
                                    "       -l list [-c ... -a bytes] -I groups.tsv -P dir   (no selection: the genomes merged by the groups of 'path<TAB>group_name' lines, one sketch set per group_name in dir)\n"; return 0;
@@ -770,8 +852,11 @@ int main(int argc, char* argv[]) {
         if ((newick_given && g_newick_file.empty()) || (merges_given && g_merges_file.empty())) { std::cerr << "selection: -N / -J need the name of the file to write\n"; return 2; }
         if (method_given) {
             tree_method = method_arg == "single" ? SELHIP_LINKAGE_SINGLE : method_arg == "complete" ? SELHIP_LINKAGE_COMPLETE : method_arg == "average" ? SELHIP_LINKAGE_AVERAGE
-                        : method_arg == "weighted" ? SELHIP_LINKAGE_WEIGHTED : -1;
-            if (tree_method < 0) { std::cerr << "selection: -X (the linkage method): average, complete, weighted or single, not '" << method_arg << "'\n"; return 2; }
+                        : method_arg == "weighted" ? SELHIP_LINKAGE_WEIGHTED : method_arg == "nj" ? kTreeNj : -1;
+            if (tree_method < 0) {
+                std::cerr << "selection: -X (the linkage method): average, complete, weighted or single, not '" << method_arg << "' (or nj: the neighbour-joining tree)\n";
+                return 2;
+            }
         }
         if (union_measure || (estimator_given && estimator == "smh_matches") || (measure_given && (measure_name == "intersection" || measure_name == "containment"))) {
             std::cerr << "selection: -N / -J take a symmetric similarity: the default (Jaccard), -E smh or -S max_containment; not -U, -E smh_matches, -S intersection | containment\n";
@@ -988,7 +1073,7 @@ int main(int argc, char* argv[]) {
             m_smh = (unsigned)aux_bytes / 8;
         }
         int rc = matrix_given ? run_matrix(list_file, query_file, matrix_file, measure, m_smh, fp_mode, threads) : 0;
-        if (!rc && tree_given) rc = run_linkage(list_file, measure, tree_method, m_smh, fp_mode, threads);
+        if (!rc && tree_given) rc = tree_method == kTreeNj ? run_nj(list_file, measure, m_smh, fp_mode, threads) : run_linkage(list_file, measure, tree_method, m_smh, fp_mode, threads);
         return rc;
     }
     if (estimator_given) { std::cerr << "selection: -E (hll, smh, smh_matches) is an option of -M (the dense similarity matrix)\n"; return 2; }

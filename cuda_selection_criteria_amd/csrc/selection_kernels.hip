@@ -56,6 +56,8 @@
 //                       value, then smallest pair among the equal), a hook and a flatten launch over the union-find of kernel_graph.cuh
 //   kernel_linkage.cuh  agglomerative hierarchy of a dense f64 distance matrix (single, complete, average, weighted linkage): rounds of
 //                       reciprocal nearest neighbours -- row scans of the dirty rows, ordered pair compaction, Lance-Williams update in place
+//   kernel_nj.cuh       neighbour-joining tree of a dense f64 distance matrix: per join a fused transform-and-argmin scan of the active
+//                       triangle (several list rows per workgroup, the row-sum vector shared in registers), one pick workgroup, one update
 //   kernel_merge.cuh    sketches merged by group: a counting sort of the members, then a segmented reduction of the rows (u8 maximum of the
 //                       HLL registers, u64 minimum of the SuperMinHash buckets) in segments of at most SELHIP_MERGE_SEGMENT members per level
 //
@@ -112,6 +114,7 @@
 #include "kernel_greedy.cuh"
 #include "kernel_forest.cuh"
 #include "kernel_linkage.cuh"     // (behind kernel_forest.cuh: ClusterBad, ForestEdge)
+#include "kernel_nj.cuh"          // (behind kernel_linkage.cuh: kLkTile, lk_distance_kernel)
 #include "kernel_merge.cuh"
 
 #include "host_plan.hpp"         // host decisions that are plain arithmetic: build shape, pass plan, criterion constants, overflow rule
@@ -127,6 +130,7 @@
 #include "host_greedy.hpp"       // greedy representative clusters: rounds and launches behind selhip_ctx_cluster_greedy / selhip_greedy_representatives
 #include "host_forest.hpp"       // maximum spanning forest: rounds, sort and launches behind selhip_ctx_spanning_forest / selhip_spanning_forest
 #include "host_linkage.hpp"      // dense-matrix hierarchy: checks, scratch and rounds behind selhip_linkage / selhip_ctx_linkage
+#include "host_nj.hpp"           // neighbour-joining tree: checks, scratch and joins behind selhip_neighbor_joining / selhip_ctx_neighbor_joining
 #include "host_merge.hpp"       // sketches merged by group: checks, levels and launches behind selhip_merge_sketches / selhip_ctx_merge_groups
 #include "host_build.hpp"       // split sketch builder: items, launches, the reduction through merge_run, the fallback launch
 #include "abi_context.inc"       // C ABI: context (create, upload / attach, run, results, timing)
@@ -137,6 +141,7 @@
 #include "abi_greedy.inc"        // C ABI: greedy representative clusters of the result list (cluster_greedy) and of a caller's edge list (greedy_representatives)
 #include "abi_forest.inc"        // C ABI: maximum spanning forest of the result list (ctx_spanning_forest) and of a caller's edge list (spanning_forest)
 #include "abi_linkage.inc"       // C ABI: average / complete / weighted / single linkage of a dense matrix (ctx_linkage, linkage)
+#include "abi_nj.inc"            // C ABI: neighbour-joining tree of a dense matrix (ctx_neighbor_joining, neighbor_joining)
 #include "abi_merge.inc"        // C ABI: sketches merged by group (merge_sketches, ctx_merge_groups)
 #include "abi_build.inc"        // C ABI: sketch construction with long genomes split across workgroups (build_sketches_split, build_split_plan)
 #include "abi_blocks.inc"        // C ABI: building blocks, synthetic sketches, sketch construction, memory helpers

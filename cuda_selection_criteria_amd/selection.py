@@ -631,6 +631,24 @@ class Selector:
         check(self._lib.selhip_ctx_linkage(self._ctx, measure_code(measure), code, mh, C.byref(out), C.byref(cnt)), self._ctx)
         return _linkage_result(merges, sizes, int(cnt.value), self.get_param("linkage_rounds_last"), to_host)
 
+    # -- neighbour-joining tree of the dense matrix --------------------------------------------------------
+    def neighbor_joining(self, measure="jaccard", distance=None, to_host: bool = True) -> dict:
+        """the neighbour-joining tree of the context's set under the distance 1 - measure, computed on the device from the dense
+        matrix (selhip_ctx_neighbor_joining; the definition is section 2l of include/selection_hip.h): measure "jaccard",
+        "max_containment" or "smh_jaccard" (a NaN cell -- two empty sketches -- is distance 1.0).  distance: a callable applied to
+        the device tensor of Selector.matrix(measure), as in Selector.linkage -- `lambda j: -torch.log(2 * j / (1 + j)) / 21` is the
+        Mash distance -- whose result goes to `neighbor_joining`; every cell of its upper triangle must be finite: a J of 0 gives
+        +inf there and the call raises, saying so.  Returns a dict: "joins" [n - 1] NJ_DTYPE records {a < b, len_a, len_b} in rank
+        indices and emitted order -- after record s slot a stands for node n + s -- (a numpy array; with to_host=False a torch uint8
+        [n - 1, 24] tensor on the device) and "n_joins".  nj_newick gives the tree, nj_table the text of `selection -X nj -J`"""
+        import torch
+        if distance is not None:
+            return neighbor_joining(distance(self.matrix(measure)), overwrite=True, device=self.device, to_host=to_host)
+        joins = torch.empty((max(self.n - 1, 0), NJ_DTYPE.itemsize), dtype=torch.uint8, device=torch.device("cuda", self.device))
+        cnt = C.c_int64()
+        check(self._lib.selhip_ctx_neighbor_joining(self._ctx, measure_code(measure), joins.data_ptr() if joins.numel() else None, C.byref(cnt)), self._ctx)
+        return _nj_result(joins, int(cnt.value), to_host)
+
     # -- sketches merged by group ---------------------------------------------------------------------
     def merge(self, groups, n_groups: Optional[int] = None, to_host: bool = False) -> dict:
         """one union sketch per group of the context's set, merged on the device (selhip_ctx_merge_groups): the element-wise maximum of
@@ -1266,6 +1284,91 @@ def linkage_from_filelist(list_file: str, aux_bytes: int = 0, measure="jaccard",
     whole = res["n_merges"] == max(n - 1, 0) or fill is not None
     res.update(names=names, order=np.asarray(ds.order), table=linkage_table(names, res),
                newick=linkage_newick(res["merges"], res["sizes"], names, fill) if whole else None)
+    return res
+
+
+NJ_DTYPE = np.dtype([("a", "<i4"), ("b", "<i4"), ("len_a", "<f8"), ("len_b", "<f8")], align=True)   # selhip_nj_join_t
+
+
+def _nj_result(joins, f: int, to_host: bool) -> dict:
+    """the dict of Selector.neighbor_joining / neighbor_joining from the device tensor a call filled: its first f records"""
+    if to_host:
+        return {"joins": np.ascontiguousarray(joins[:f].cpu().numpy()).view(NJ_DTYPE).reshape(-1), "n_joins": f}
+    return {"joins": joins[:f], "n_joins": f}
+
+
+def neighbor_joining(dist, overwrite: bool = False, device: int = 0, to_host: bool = True) -> dict:
+    """the neighbour-joining tree of an n x n distance matrix, computed on the device (selhip_neighbor_joining): dist a numpy float64
+    array or a torch float64 tensor (2-D, square, stride(1) == 1; its stride(0) is the leading dimension) of which only the strict
+    upper triangle is read -- a NaN, +inf or -inf there raises (SELHIP_E_BADARG; the message names one such cell).  The call consumes
+    the matrix it works on: a device tensor is cloned first unless overwrite=True.  The dict: Selector.neighbor_joining's"""
+    import torch
+    lib = hip_lib()
+    dev = torch.device("cuda", device)
+    if hasattr(dist, "data_ptr"):
+        d = dist if dist.is_cuda and overwrite else dist.to(dev, copy=True)
+    else:
+        d = torch.from_numpy(np.ascontiguousarray(dist, dtype=np.float64)).to(dev)
+    assert d.dim() == 2 and d.shape[0] == d.shape[1] and d.dtype == torch.float64, "dist: a square float64 matrix"
+    n = int(d.shape[0])
+    assert n <= 1 or d.stride(1) == 1, "dist: stride(1) must be 1"
+    ld = d.stride(0) if n > 1 else max(n, 1)
+    f = C.c_int64(-1)
+    with torch.cuda.device(dev):
+        joins = torch.empty((max(n - 1, 0), NJ_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        check(lib.selhip_neighbor_joining(d.data_ptr() if n else None, n, ld, joins.data_ptr() if joins.numel() else None, C.byref(f),
+                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return _nj_result(joins, int(f.value), to_host)
+
+
+def nj_newick(joins, names: Sequence[str]) -> str:
+    """the neighbour-joining tree as Newick, one line ending in ';': the unrooted tree rooted on the last record's edge, so the root
+    has two children, each at half that edge.  The subtree of a record's a goes first, with len_a behind it, then b's with len_b;
+    negative lengths are printed as they are.  names: the leaves' names in the records' index space (rank order), quoted and the
+    numbers printed as linkage_newick does"""
+    n = len(names)
+    if n == 0:
+        return ";\n"
+    node = {g: g for g in range(n)}                                # slot -> a leaf, or (left, len_a, right, len_b)
+    for e in joins:
+        a, b = int(e["a"]), int(e["b"])
+        node[a] = (node[a], float(e["len_a"]), node.pop(b), float(e["len_b"]))
+    out, stack = [], [(node[min(node)], None)]                     # (node, the length of its branch) or a literal
+    while stack:
+        item = stack.pop()
+        if isinstance(item, str):
+            out.append(item)
+            continue
+        nd, up = item
+        tail = "" if up is None else ":" + _newick_number(up)
+        if isinstance(nd, tuple):
+            stack.extend([")" + tail, (nd[2], nd[3]), ",", (nd[0], nd[1]), "("])
+        else:
+            out.append(_newick_name(str(names[nd])) + tail)
+    return "".join(out) + ";\n"
+
+
+def nj_table(names: Sequence[str], joins) -> str:
+    """the text of `selection -X nj -J`: one line per join in emitted order, 'path_a<TAB>path_b<TAB>len_a<TAB>len_b', the lengths with
+    six decimals.  names in rank order"""
+    return "".join(f"{names[int(e['a'])]}\t{names[int(e['b'])]}\t{float(e['len_a']):f}\t{float(e['len_b']):f}\n" for e in joins)
+
+
+def nj_from_filelist(list_file: str, aux_bytes: int = 0, measure="jaccard", fp_mode: int = FP_FMA, device: int = 0) -> dict:
+    """the neighbour-joining tree of the genomes of a file list -- what `selection -l list -N tree.nwk [-J joins.tsv] -X nj` computes;
+    no pass runs.  The sketches are loaded and sorted as for linkage_from_filelist.  Returns Selector.neighbor_joining's dict on the
+    host plus "names" (rank order), "order", "table" (the text of -J) and "newick" (the text of -N)"""
+    code = measure_code(measure)
+    if code not in (MEASURE_JACCARD, MEASURE_MAX_CONTAINMENT, MEASURE_SMH_JACCARD):
+        raise ValueError("measure of a tree: 'jaccard', 'max_containment' or 'smh_jaccard' (the symmetric similarities)")
+    m_smh = _matrix_buckets(measure, aux_bytes)
+    ds = load_dataset(list_file, m_smh, 0, fp_mode)
+    n = len(ds.names)
+    with Selector(device, fp_mode) as sel:
+        sel.upload(ds.hll, ds.aux if m_smh else np.zeros((n, 1), dtype=np.uint64), ds.cards)
+        res = sel.neighbor_joining(measure)
+    names = list(ds.names)
+    res.update(names=names, order=np.asarray(ds.order), table=nj_table(names, res["joins"]), newick=nj_newick(res["joins"], names))
     return res
 
 

@@ -998,6 +998,60 @@ typedef struct {
 } selhip_linkage_t;          /* caller's device memory; either pointer may be NULL (not written)    */
 int selhip_ctx_linkage(selhip_ctx* ctx, int measure, int method, double max_height, const selhip_linkage_t* out, int64_t* n_merges_out);
 
+/* ---------------------------------------------------------------------------------------------------
+ * 2l. Neighbour-joining tree of the DENSE matrix (Saitou & Nei 1987; Studier & Keppler 1988), on the device.  Every tree of 2j and
+ *     2k is ultrametric; this is the unrooted, additive tree that is drawn from sketch distances (mashtree: Mash + QuickTree).  The
+ *     number of joins is known (n - 1), so the host reads nothing back while they run.
+ *     THE DEFINITION -- the kernels (csrc/kernel_nj.cuh) and the tests' model follow it; every output is a pure function of the
+ *     strict upper triangle, bit for bit and run to run.
+ *     STATE.  D: n x n f64, symmetric; only the strict upper triangle (a < b) is input, it is mirrored into the lower one first and
+ *     the diagonal is ignored.  A set of r active slots, at the start all n.  R[s] = the sum of D[s][k] over the active k != s.  A
+ *     joined node lives in the smaller of its two slots (2k's convention).
+ *     ONE JOIN, while r > 2.  For active a < b: q(a, b) = ((r - 2) * D[a][b] - R[a]) - R[b]; a q that is NaN (inf - inf, once sums
+ *     have overflowed) counts as +inf.  The join is the pair with the smallest q under f64 `<`; equal q: the lexicographically
+ *     smallest (a, b).  With d = D[a][b]:
+ *       len_a = 0.5 * d + (R[a] - R[b]) / (2 * (r - 2)),   len_b = d - len_a          (the record; negative lengths stay as they are)
+ *       for every other active k:   v = 0.5 * ((D[a][k] + D[b][k]) - d),   R[k] <- ((R[k] - D[a][k]) - D[b][k]) + v,
+ *                                   D[a][k] = D[k][a] = v
+ *       b leaves the active set;   R[a] <- a fresh row sum of the new row.
+ *     Every product, sum, difference and quotient is rounded on its own (no fused multiply-add); r - 2 enters as a double.
+ *     THE LAST JOIN, at r == 2: the two remaining slots a < b with len_a = len_b = 0.5 * D[a][b].
+ *     n - 1 records for n >= 2; none, and no launch, for n <= 1.
+ *     A ROW SUM -- the initial R[s] of every row and the fresh R[a] of a join alike -- has ONE shape, which is part of the contract
+ *     because R feeds q.  1 024 lanes; lane l adds the cells of its columns l, l + 1024, l + 2048, ... in ascending order onto +0.0,
+ *     where an inactive column and the diagonal add nothing.  The 64 lanes of a wave (lanes 64 w .. 64 w + 63) are then summed by a
+ *     butterfly: for the strides 32, 16, 8, 4, 2, 1 in this order every lane replaces its value x by x + (the value of lane
+ *     l XOR stride).  The 16 wave sums are added from wave 0 upwards: ((W0 + W1) + W2) + ... + W15.  No floating-point atomics; the
+ *     shape depends on neither the grid nor on timing.
+ *     RECORDS.  selhip_nj_join_t {a, b, len_a, len_b}, 24 bytes, in emitted order: d_joins is the caller's device memory of
+ *     max(n - 1, 0) records, 8-byte aligned, or NULL (nothing is copied out).  After record s slot a stands for the internal node
+ *     n + s (SciPy's numbering, as `linkage_matrix` of the Python package uses it).
+ *     REFUSAL.  A NaN, +inf or -inf cell of the upper triangle: SELHIP_E_BADARG; the message gives the number of such cells and the
+ *     indices of the smallest one, and no record is written.  (2k takes +inf as data; a neighbour-joining sum cannot.)
+ *     selhip_ctx_neighbor_joining: measure = SELHIP_MEASURE_JACCARD, _MAX_CONTAINMENT or _SMH_JACCARD (any other: SELHIP_E_BADARG).
+ *     The call takes n * n f64 of scratch (SELHIP_E_NOMEM if that cannot be had; released before it returns), fills it with the
+ *     matrix kernels of 2f in rank order, turns every cell into the distance 1 - v (a NaN, which two empty sketches give under the
+ *     HLL measures, into 1.0) and runs the joins.  What a matrix call refuses is refused here (p_hll != 14 or no bit planes for the
+ *     HLL measures, a pending pass), and everything a matrix call leaves unchanged is left unchanged.  Timed as "nj", per call;
+ *     "matrix", "matrix_smh" and "linkage" are not touched.
+ *     STREAM.  Every launch and copy runs on the context's stream, in stream order.  The host waits for the stream after the matrix,
+ *     once for the refusal tally BEFORE the first join, and once behind the last join: never between joins.  The call returns when
+ *     the records are complete.  Its scratch is taken and released inside the call.
+ *     HOW.  At most three plain launches per join, back to back.  Scan: the active slots are an ascending device list; a workgroup
+ *     takes 4 consecutive rows of it and sweeps the columns behind the first of them once -- R[c] and active[c] are read once per
+ *     step (from L2) and serve the 4 matrix loads that go with them (16-byte loads where ld is even and the base 16-byte aligned) --,
+ *     forms q, keeps a (q, b) best per lane and row and reduces it in the wave, then through LDS.  Pick: one workgroup reduces the
+ *     rows' bests under (q, a, b), writes the record, and sums the new row in the shape above from the two old rows.  Update: one
+ *     lane per column writes v, its mirror and R[k], retires b and shifts the list.  No cooperative launch, no graph, no spin.
+ *     Not built: BIONJ's variance weights, rapid-NJ's bounds on q, physical compaction of dead columns, matrices beyond device
+ *     memory, a Mash-distance switch on the command line (the Python package takes a `distance` callable), more than one device.
+ * --------------------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t a, b;            /* the two slots joined, a < b; the new node lives on in a              */
+    double  len_a, len_b;    /* the branch lengths from the new node to what a and b stood for       */
+} selhip_nj_join_t;          /* 24 bytes                                                             */
+int selhip_ctx_neighbor_joining(selhip_ctx* ctx, int measure, selhip_nj_join_t* d_joins /* [max(n-1,0)] or NULL */, int64_t* n_joins_out);
+
 
 /* ---------------------------------------------------------------------------------------------------
  * 3. Building blocks (device pointers), used by the launchers above and exposed for tests.
@@ -1067,6 +1121,15 @@ int selhip_spanning_forest(const selhip_int2_t* d_pairs, const double* d_values,
  * (they may then be read from any stream).  Releasing the scratch at the end waits for the whole device. */
 int selhip_linkage(double* d_dist, int64_t n, int64_t ld, int method, double max_height, selhip_pair_t* d_merges /* [max(n-1,0)] */,
                    int32_t* d_size /* [max(n-1,0)] */, int64_t* n_merges_out, int64_t* rounds_out, void* hip_stream);
+/* The neighbour-joining tree of section 2l over a caller's distance matrix d_dist[n][ld] (device memory, f64, 8-byte aligned, ld >= n
+ * counted in elements), which the call works on and CONSUMES.  With an even ld and a 16-byte aligned base the scan takes 16-byte
+ * loads, otherwise 8-byte ones; the results are the same.  d_joins (max(n - 1, 0) records, 8-byte aligned) and *n_joins_out (n - 1,
+ * or 0 for n <= 1) are section 2l's; each may be NULL.  SELHIP_E_BADARG: n < 0 or > 2^31 - 1, ld < n, a NULL matrix with n > 1, a
+ * misaligned pointer, and a NaN, +inf or -inf cell in the strict upper triangle (no record is written).  SELHIP_E_NOMEM: no room for
+ * the per-slot scratch.  The call owns its scratch; every launch and copy runs on hip_stream, in stream order; the host waits once
+ * before the first join (the refusal tally) and once behind the last, and the call returns when the records are complete. */
+int selhip_neighbor_joining(double* d_dist, int64_t n, int64_t ld, selhip_nj_join_t* d_joins /* [max(n-1,0)] */, int64_t* n_joins_out,
+                            void* hip_stream);
 /* Sketches merged by group (section 2i; csrc/kernel_merge.cuh) over a caller's rows: d_hll[n][1 << p] u8, d_smh[n][m] u64 and
  * d_aux_hll[n][1 << p_aux] u8 reduced to n_groups rows each -- maximum, unsigned minimum, maximum -- by d_group[n] (int32, -1 .. n_groups - 1,
  * -1 = in no group; ids in any order); d_size_out[n_groups] (int32, may be NULL) receives the members per group.  A sketch kind is
