@@ -83,6 +83,10 @@ int nj_ctx_call(selhip_ctx* c, int measure, selhip_nj_join_t* d_joins, int64_t* 
     if (n == 1) {
         // (the refusals of a matrix call still hold for one genome; none has anything to refuse with no genome)
         if (const int rc = matrix_call(c, false, measure, SELHIP_F64, 0, 0, nullptr, 0, 0, 0, nullptr, nullptr, T_NJ, what)) return rc;
+        // (an empty matrix call times nothing; "nj" is per call, so the call is counted here, with an empty scope on the stream)
+        HIPCHK(&c->err, hipSetDevice(c->device));
+        TimedCall call(c, T_NJ);
+        TimerScope t(c, T_NJ);
     } else if (n > 1) {
         HIPCHK(&c->err, hipSetDevice(c->device));
         DevBlock<double> dist;

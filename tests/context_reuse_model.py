@@ -20,6 +20,10 @@ sets are shaped so that the old bytes lie where a missing mask or a stale key wo
            columns; after BIG -> TRIMMED the stride stays and column 322 of every band still holds genome 322 of BIG, a true partner
            of eight live rows: the one column a pad mask that is off by one admits
 
+selhip_ctx_neighbor_joining ("nj-jaccard", "nj-smh_jaccard") is an operation like the linkages: it runs at every station of the
+transitions and the walks against nj_model on that station's set -- the cut query set changes nothing for it, and EMPTY and ONE give
+no record.
+
 Expected values come from what the suite trusts already -- the oracle, tests/*_model.py, numpy -- through stream_harness.Sets, whose
 shape is an argument; never from a second context.  Each is computed once per set."""
 import functools
@@ -34,6 +38,7 @@ import cluster_model
 import fold_model
 import greedy_model
 import merge_model
+import nj_model
 import precision_model
 import sig_model
 import stream_harness as H
@@ -48,6 +53,7 @@ BADARG, STATE = -1, -5                       # SELHIP_E_BADARG, SELHIP_E_STATE
 SEEDS = {"BIG": 0xC0DE0004, "NARROW": 0xC0DE0012, "WIDE": 0xC0DE0023, "HIGHREG": 0xC0DE0031, "LOWP": 211}
 FORGED = (33, 36, 41, 47)                    # HIGHREG: register values written into a few genomes (above 32: a sixth plane)
 EMPTY_REC = np.zeros(0, dtype=PAIR_DTYPE)
+EMPTY_NJ = np.zeros(0, dtype=nj_model.NJ_DTYPE)
 
 
 def forge_high(hll):
@@ -158,9 +164,12 @@ OPS.update({"merge_groups": ("merged", "value"), "cards": ("cards", "value")})  
 # (the linkage of an HLL measure is refused as its matrix is; the one over smh_jaccard reads the bucket rows alone and always runs)
 LINKAGE_OPS = tuple(H.LINKAGE_CASES)
 HLL_LINKAGES = {k for k, v in H.LINKAGE_CASES.items() if v[0] != "smh_jaccard"}
+# (the same for the neighbour-joining tree: what its matrix call refuses is refused)
+NJ_OPS = tuple(H.NJ_CASES)
+HLL_NJ = {k for k, v in H.NJ_CASES.items() if v != "smh_jaccard"}
 P14_ONLY = {"none-list_route", "none-fused", "matrix-jaccard", "query-sig", "query-stream", "query-index", "query-topk",
-            "query_matrix-containment"} | HLL_LINKAGES
-NEEDS_PLANES = {"none-list_route", "none-fused", "matrix-jaccard", "query_matrix-containment"} | HLL_LINKAGES
+            "query_matrix-containment"} | HLL_LINKAGES | HLL_NJ
+NEEDS_PLANES = {"none-list_route", "none-fused", "matrix-jaccard", "query_matrix-containment"} | HLL_LINKAGES | HLL_NJ
 QUERY_OPS = {k for k, v in OPS.items() if v[1] == "qlist"} | {"query_matrix-containment"}
 
 
@@ -199,6 +208,8 @@ def expected(S, op, bit_planes=True):
             return {"edges": EMPTY_REC, "labels": np.arange(n, dtype=np.int32)}
         if op in H.LINKAGE_CASES:                                 # (no launch: one slot is scanned once and has no neighbour)
             return {"merges": EMPTY_REC, "sizes": np.zeros(0, dtype=np.int32), "rounds": n}
+        if op in H.NJ_CASES:                                      # (no join, no launch, nothing written)
+            return EMPTY_NJ
     return getattr(S, attr)
 
 

@@ -1,6 +1,10 @@
 """The neighbour-joining definition of include/selection_hip.h section 2l in numpy: sequential over the joins, vectorised inside one,
 f64 and plain.  It follows the header's row-sum shape (1 024 lanes, wave butterflies, the wave sums from wave 0 upwards), so its
-records are the device's bit for bit.  Also the additive dyadic trees the tests take their truth from."""
+records are the device's bit for bit.  The working matrix is the upper triangle mirrored by COPY, so signed zeros survive as on the
+device; neighbor_joining(dist, first=k) stops behind k records.  Also the additive dyadic trees the tests take their truth from, and
+the value sets tests/test_nj_host.py and tests/test_nj_gpu.py share: the file's seeded matrices (value_sets), the forged pair that
+the pick kernel's later trips decide (forged), tied values at those sizes (tie_sets), signed zeros (zero_sets) and cells whose
+sums overflow (overflow_sets)."""
 import numpy as np
 
 NJ_DTYPE = np.dtype([("a", "<i4"), ("b", "<i4"), ("len_a", "<f8"), ("len_b", "<f8")], align=True)
@@ -25,24 +29,38 @@ def row_sums(cells):
     return total
 
 
-def neighbor_joining(dist):
-    """the n - 1 records of the strict upper triangle of dist [n, n]"""
+def mirrored(dist):
+    """the working matrix: the strict upper triangle of dist COPIED into the lower one, cell by cell (a -0.0 stays -0.0, as section 2l's
+    "is mirrored" says and nj_mirror_kernel does; a sum of two triangles would turn it into +0.0), the diagonal +0.0"""
+    D = np.array(dist, dtype=np.float64)
+    np.fill_diagonal(D, 0.0)
+    lo = np.tril_indices(D.shape[0], -1)
+    D[lo] = D.T[lo]
+    return D
+
+
+def neighbor_joining(dist, first=None):
+    """the n - 1 records of the strict upper triangle of dist [n, n]; first=k: the first min(k, n - 1) of them, and no join behind them
+    is computed (a prefix of a large matrix costs what its joins cost)"""
     n = dist.shape[0]
-    joins = np.zeros(max(n - 1, 0), dtype=NJ_DTYPE)
-    if n < 2:
+    joins = np.zeros(max(n - 1, 0) if first is None else min(max(n - 1, 0), max(int(first), 0)), dtype=NJ_DTYPE)
+    if len(joins) == 0:
         return joins
-    D = np.triu(np.asarray(dist, dtype=np.float64), 1)
-    D = D + D.T
-    R = row_sums(D)
+    D = mirrored(dist)
     act = np.arange(n)
     lower = np.tri(n, dtype=bool)                                            # the diagonal and below: no pair
     with np.errstate(all="ignore"):
-        for s in range(n - 1):
+        R = row_sums(D)
+        for s in range(len(joins)):
             r = len(act)
             rm2 = float(r - 2)
-            q = (rm2 * D[np.ix_(act, act)] - R[act][:, None]) - R[act][None, :]
+            q = D[np.ix_(act, act)]                                                     # (a copy; the three steps in place, each rounded on its own)
+            q *= rm2
+            q -= R[act][:, None]
+            q -= R[act][None, :]
             q[np.isnan(q)] = np.inf
-            best = int(np.argmin(np.where(lower[:r, :r], np.inf, q)))                   # row-major, the first: the smallest (a, b) among the equal
+            q[lower[:r, :r]] = np.inf
+            best = int(np.argmin(q))                                                    # row-major, the first: the smallest (a, b) among the equal
             if best // r >= best % r:                                                   # every q is +inf
                 best = 1
             a, b = int(act[best // r]), int(act[best % r])
@@ -116,3 +134,85 @@ def join_splits(joins, n):
         if 1 < len(side) < n - 1:
             splits.add(frozenset(side))
     return splits
+
+
+# ---- the value sets of tests/test_nj_host.py and tests/test_nj_gpu.py: n x n float64, of which the strict upper triangle counts -----------
+TRIP_SIZES = (LANES + 7, 2 * LANES + 7)      # two and three trips of the 1 024-lane loops (the pick's walk over the rows' bests, the row sums)
+ZERO_SIZES = (2, 3, 5, 65, 257)
+OVERFLOW_SIZES = (5, 65, 130)
+PREFIX = 16                                  # records of the model computed at TRIP_SIZES
+TWIN = (100, 102)                            # the pair that ties with forged_pair(n) in tie_sets(n)["twins"]
+
+
+def first_q(dist):
+    """q of every pair a < b at the first join (+inf elsewhere), as the definition forms it"""
+    n = dist.shape[0]
+    D = mirrored(dist)
+    R = row_sums(D)
+    q = (float(n - 2) * D - R[:, None]) - R[None, :]
+    q[np.tri(n, dtype=bool)] = np.inf
+    return q
+
+
+def value_sets(n):
+    """{value set: matrix} of test_against_the_model, from one seeded generator in this order"""
+    rng = np.random.default_rng(2000 + n)
+    sets = {"distinct": (rng.permutation(n * n).reshape(n, n) + rng.random((n, n)) / 2) / float(max(n * n, 1))}
+    if n <= 513:
+        sets["negative"] = 10.0 * rng.random((n, n)) ** 4                     # far from a metric: negative branch lengths
+        if n >= 3:
+            sets["dyadic"] = dyadic_tree(n, n)[0]
+    if n <= 257:                                                              # ties: the smallest (a, b)
+        sets["levels"] = rng.choice([0.25, 0.5, 0.75], size=(n, n))
+        sets["equal"] = np.full((n, n), 0.5)
+    return sets
+
+
+def forged_pair(n):
+    return n - 4, n - 2
+
+
+def forged(n):
+    """the "distinct" matrix of n with +50 on the rows and columns of forged_pair(n) and 0.001 between the two: both row sums are far
+    above every other, so the first join is that pair -- the row at list position n - 4, which for n = 1 024 j + 7 lies in the pick's
+    last trip, with two columns behind it"""
+    p, q = forged_pair(n)
+    D = value_sets(n)["distinct"].copy()
+    D[[p, q], :] += 50.0
+    D[:, [p, q]] += 50.0
+    D[p, q] = 0.001
+    return D
+
+
+def tie_sets(n):
+    """"equal": every q ties in every join, the answer is (0, 1), (0, 2), ...; "levels": three values, ties by the thousand; "twins":
+    "equal" with 0.25 in the cells TWIN and forged_pair(n) -- every operation is exact, the two cells share the smallest q of the first
+    join, and for n = 1 024 j + 7 the pick kernel meets them in different waves: the row n - 4 in a later trip of a lane of wave 0, the
+    row 100 in wave 1, so only the cross-wave step's comparison of a gives the smaller pair"""
+    twins = np.full((n, n), 0.5)
+    twins[TWIN] = twins[forged_pair(n)] = 0.25
+    return {"equal": np.full((n, n), 0.5), "levels": np.random.default_rng(3000 + n).choice([0.25, 0.5, 0.75], size=(n, n)), "twins": twins}
+
+
+def zero_sets(n):
+    """-0.0 in every cell; in a random half of the cells of an all-zero matrix; in half the zero cells of a "levels" matrix with a fourth
+    level 0.0"""
+    rng = np.random.default_rng(4000 + n)
+    half = np.where(rng.random((n, n)) < 0.5, -0.0, 0.0)
+    levels = rng.choice([0.0, 0.25, 0.5, 0.75], size=(n, n))
+    levels[(levels == 0.0) & (rng.random((n, n)) < 0.5)] = -0.0
+    return {"all": np.full((n, n), -0.0), "half": half, "levels0": levels}
+
+
+def overflow_sets(n):
+    """finite cells whose sums are not: "huge" -- every cell (0.5 + u) * 0.9e308, every sum overflows and every length is NaN --; at
+    n = 65 also "mixed" -- uniform cells, those in the rows or columns 0 .. 7 times 1e307: the sums of those rows overflow, the others
+    do not, and the lengths are +-inf, NaN and finite"""
+    rng = np.random.default_rng(5000 + n)
+    sets = {"huge": (0.5 + rng.random((n, n))) * 0.9e308}
+    if n == 65:
+        mixed = rng.random((n, n))
+        i, j = np.indices((n, n))
+        mixed[(i < 8) | (j < 8)] *= 1e307
+        sets["mixed"] = mixed
+    return sets

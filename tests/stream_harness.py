@@ -28,6 +28,9 @@ race.  Nothing here waits for luck -- every case is arranged so that a wrong str
             alone, under a fixed delay that their hipFree waits out.
 
 The delays only size things (each at most 2 s): the conditions are the query() assertions and the answers.
+The neighbour-joining entries (selhip_neighbor_joining, selhip_ctx_neighbor_joining: a host loop of 3 (n - 1) launches, per-call scratch,
+one tally read back before the first join) are cases like the linkage's; the free-standing one must also REFUSE a second matrix that
+holds a NaN in the real set alone.
 The linkage cases' expected values take 0.3 s of model time per set at the most (the SuperMinHash case under single linkage, 300 rounds
 of one pair on its plateau), so that case stays single linkage.
 Expected values come from what the suite trusts already: the oracle, tests/*_model.py, numpy."""
@@ -48,6 +51,7 @@ import fold_model
 import forest_model
 import greedy_model
 import linkage_model
+import nj_model
 import smhv_model
 import topk_rounds_model
 import smh_matrix_model
@@ -96,6 +100,10 @@ LINKAGE_CASES = {"linkage-average-jaccard": ("jaccard", "average", False), "link
 # the layouts selhip_linkage is handed its matrix in: tag -> (ld - n, offset of the base behind a 16-byte boundary in doubles).  An even ld
 # on a 16-byte base takes lk_scan_kernel<true> (16-byte loads), anything else lk_scan_kernel<false>
 LINKAGE_LAYOUTS = {"wide": (0, 0), "narrow": (3, 1)}
+# the context cases of selhip_ctx_neighbor_joining: id -> measure.  selhip_neighbor_joining takes its matrix in the layouts above too
+# (nj_scan_kernel<true> and <false>)
+NJ_CASES = {"nj-jaccard": "jaccard", "nj-smh_jaccard": "smh_jaccard"}
+NJ_BAD_CELL = (3, 64)                        # the NaN cell of the REAL set's second matrix (Sets.nj_dist_refused)
 
 
 class Sets:
@@ -296,6 +304,15 @@ class Sets:
     def linkage_complete_max_containment_capped(self):
         return self._linkage(self.matrix_max_containment, "complete", self.linkage_cap)
 
+    @functools.cached_property
+    def nj_jaccard(self):
+        """the neighbour-joining records of nj_model on the distance selhip_ctx_neighbor_joining derives: 1 - v, a NaN cell 1.0"""
+        return nj_model.neighbor_joining(distance_of(self.matrix_jaccard))
+
+    @functools.cached_property
+    def nj_smh_jaccard(self):
+        return nj_model.neighbor_joining(distance_of(self.matrix_smh_jaccard))
+
     # -- clusters -----------------------------------------------------------------------------------
     @functools.cached_property
     def clusters(self):
@@ -424,6 +441,32 @@ class Sets:
         return {f"{k}-{tag}": res[k] for tag in LINKAGE_LAYOUTS for k in ("merges", "sizes", "rounds")}
 
     @functools.cached_property
+    def nj_dist(self):
+        """the caller's distance matrix of selhip_neighbor_joining: N_D x N_D uniform numbers of its own from the set's seed"""
+        return np.random.default_rng(self.seed + 13).random((N_D, N_D))
+
+    @functools.cached_property
+    def block_nj(self):
+        """the records of nj_dist, once per layout of LINKAGE_LAYOUTS: both scan instantiations must give the same tree"""
+        joins = nj_model.neighbor_joining(self.nj_dist)
+        return {f"joins-{tag}": joins for tag in LINKAGE_LAYOUTS}
+
+    @functools.cached_property
+    def nj_dist_refused(self):
+        """a second matrix, which the entry must REFUSE for the set named "real" alone: its cell NJ_BAD_CELL is a NaN there.  The tally of
+        such cells is read back before the first join; read on another stream, it is the one of the set before"""
+        d = np.random.default_rng(self.seed + 14).random((N_D, N_D))
+        if self.name == "real":
+            d[NJ_BAD_CELL] = np.nan
+        return d
+
+    @functools.cached_property
+    def block_nj_and_refusal(self):
+        """block_nj, and the return code of the entry on nj_dist_refused: SELHIP_E_BADARG where it holds a NaN, else SELHIP_OK"""
+        bad = np.isnan(self.nj_dist_refused[np.triu_indices(N_D, 1)]).any()
+        return dict(self.block_nj, refusal=np.array([-1 if bad else 0], dtype=np.int32))
+
+    @functools.cached_property
     def keys(self):
         return np.random.default_rng(self.seed + 6).integers(0, 1 << 40, self.n_d).astype(np.uint64)
 
@@ -453,6 +496,7 @@ CONTEXT_CASES = {
     "forest": ("forest", "value"),
     "linkage-average-jaccard": ("linkage_average_jaccard", "value"), "linkage-single-smh_jaccard": ("linkage_single_smh_jaccard", "value"),
     "linkage-complete-max_containment-capped": ("linkage_complete_max_containment_capped", "value"),
+    "nj-jaccard": ("nj_jaccard", "value"), "nj-smh_jaccard": ("nj_smh_jaccard", "value"),
     "two_contexts": ("smh_a", "list"),                      # (the second context runs smh_c: checked as "smh_c")
     "switch-sig_cache": ("smh_a", "list"), "switch-query_index": ("query", "list"),
 }
@@ -464,6 +508,7 @@ BLOCK_CASES = {
     "selhip_hll_bitslice+union_hist_planes": ("block_hist", "value"),
     "components": ("components", "value"), "greedy_representatives": ("greedy_reps", "value"),
     "selhip_spanning_forest": ("block_forest", "value"), "selhip_linkage": ("block_linkage", "value"),
+    "selhip_neighbor_joining": ("block_nj_and_refusal", "value"),
 }
 # selhip_permute_rows at the shapes no other test reaches: case id -> (rows, row bytes, byte offset of both pointers).  Row sizes that
 # are no multiple of 16 and 16-byte multiples through pointers that are not 16-byte aligned take permute_bytes_kernel; 70 000 rows
@@ -482,11 +527,11 @@ def expected(S, case_id):
 # entries that allocate and free device memory in every call -- hipFree waits for the whole device, the blocked null stream included --
 # get run A only (module docstring of tests/test_streams_gpu.py)
 RUN_A_ONLY = {"selhip_hll_bitslice+union_hist_planes", "components", "greedy_representatives", "grown_lists",
-              "selhip_spanning_forest", "selhip_linkage", *LINKAGE_CASES}
+              "selhip_spanning_forest", "selhip_linkage", *LINKAGE_CASES, "selhip_neighbor_joining", *NJ_CASES}
 # ... of which the hierarchy entries still run with the null stream blocked, for the ANSWER alone: their host loops launch round after
 # round from words just read back, and a round left on the null stream shows only while that stream is held.  The hipFree at their end
 # waits the delay out (it is then 300 ms, not sized from the call), so that run does not ask whether the null stream is still blocked
-ANSWER_UNDER_BLOCKED_NULL = {"selhip_spanning_forest", "selhip_linkage", *LINKAGE_CASES}
+ANSWER_UNDER_BLOCKED_NULL = {"selhip_spanning_forest", "selhip_linkage", *LINKAGE_CASES, "selhip_neighbor_joining", *NJ_CASES}
 BLOCKED_ANSWER_DELAY_MS = 300.0
 
 
@@ -498,6 +543,8 @@ def bits(x):
     if isinstance(x, (tuple, list)):
         return [bits(v) for v in x]
     x = np.asarray(x)
+    if x.dtype.names and "len_a" in x.dtype.names:                 # neighbour-joining records
+        return list(zip(x["a"].tolist(), x["b"].tolist(), *(np.ascontiguousarray(x[f]).view(np.uint64).tolist() for f in ("len_a", "len_b"))))
     if x.dtype.names:
         return list(zip(x["i"].tolist(), x["k"].tolist(), np.ascontiguousarray(x["jaccard"], dtype=np.float64).view(np.uint64).tolist()))
     if x.dtype.kind == "f":

@@ -10,7 +10,10 @@ the oracle and the models, never from a second context.
                     queries and auxiliary sketches, every operation on Y against expected(Y, op)
   test_walk         60 random steps from a seed: replace the database (upload / attach), replace the queries, flip a route knob that
                     changes no answer, run an operation; the log goes into the assertion message
-  test_refused_upload_leaves_the_context_alone, test_settings_survive_a_replacement   the contract of the header"""
+  test_refused_upload_leaves_the_context_alone, test_settings_survive_a_replacement   the contract of the header
+
+selhip_ctx_neighbor_joining ("nj-jaccard", "nj-smh_jaccard") is among the operations: at every station, the cut query set and the
+empty set included, against tests/nj_model.py on that station's set."""
 import ctypes as C
 
 import numpy as np
@@ -358,6 +361,22 @@ def _linkage(live, name):
         f"{name} on {S.name}: merges and rounds {sel.get_param('linkage_merges_last'), got['rounds']}, the model's {len(want['merges']), want['rounds']}"
     assert kept_of_the_last_pass(sel) == before, f"{name} on {S.name}: the call changed the result list, its count or the statistics"
     return got
+
+
+@op(*R.NJ_OPS)
+def _nj(live, name):
+    """selhip_ctx_neighbor_joining into a poisoned array with two records of room behind the n - 1: the count, the records, nothing
+    written behind them (EMPTY and ONE: nothing at all), and the result list, stats() and result_count() as before the call"""
+    sel, S = live.sel, live.S
+    room = max(S.n_d - 1, 0)
+    joins = torch.full((room + 2, pkg.NJ_DTYPE.itemsize), 0xA5, dtype=torch.uint8, device="cuda")
+    before = kept_of_the_last_pass(sel)
+    cnt = C.c_int64(-5)
+    lib_check(sel._lib.selhip_ctx_neighbor_joining(sel._ctx, pkg.measure_code(H.NJ_CASES[name]), joins.data_ptr(), C.byref(cnt)), sel._ctx)
+    raw = joins.cpu().numpy()
+    assert cnt.value == room and np.all(raw[room:] == 0xA5), f"{name} on {S.name}: {cnt.value} joins for {room}, or records written behind them"
+    assert kept_of_the_last_pass(sel) == before, f"{name} on {S.name}: the call changed the result list, its count or the statistics"
+    return np.ascontiguousarray(raw[:room]).reshape(-1).view(pkg.NJ_DTYPE)
 
 
 @op("merge_groups")

@@ -83,6 +83,29 @@ def test_the_hierarchy_operations_need_no_exemption(lib):
             assert 0 < len(S.linkage_complete_max_containment_capped["merges"]) < S.n_d - 1, name
 
 
+def test_the_neighbour_joining_operations_need_no_exemption(lib):
+    """selhip_ctx_neighbor_joining tells every step's two sets apart, is refused where its matrix is (an HLL measure on LOWP and without
+    bit planes), and has no record on EMPTY and ONE; every other set gives a whole tree"""
+    assert set(R.NJ_OPS) == set(H.NJ_CASES) <= set(R.OPS) and not any(key[2] in R.NJ_OPS for key in R.SAME_ANSWER)
+    assert R.HLL_NJ == {"nj-jaccard"} and R.HLL_NJ <= R.P14_ONLY and R.HLL_NJ <= R.NEEDS_PLANES
+    for x, y in R.steps():
+        for op in R.NJ_OPS:
+            if R.refusal(lib[x], op) is None and R.refusal(lib[y], op) is None:
+                assert not H.same(R.expected(lib[x], op), R.expected(lib[y], op)), (x, y, op)
+    for op in R.NJ_OPS:
+        assert R.refusal(lib["LOWP"], op) == (R.BADARG if op in R.HLL_NJ else None), op
+        assert R.refusal(lib["BIG"], op, bit_planes=False) == R.refusal(lib["ONE"], op, bit_planes=False) == (R.BADARG if op in R.HLL_NJ else None), op
+        assert R.refusal(lib["EMPTY"], op, bit_planes=False) is None
+        for name in ("EMPTY", "ONE"):
+            want = R.expected(lib[name], op)
+            assert len(want) == 0 and want.dtype == R.nj_model.NJ_DTYPE
+        for name in R.NAMES:
+            S = lib[name]
+            if not S.trivial and R.refusal(S, op) is None:
+                want = R.expected(S, op)
+                assert len(want) == S.n_d - 1 and (want["a"] < want["b"]).all() and want["b"].max() < S.n_d, (name, op)
+
+
 def test_the_image_premises(lib):
     """which sets hold the clamped four-plane image (threshold 4, 8 or 12), and that the steps and sequences are there on which a stale
     image would be read: a step between two sets that are both on the image with other rows at equal ranks, and a sequence on, off, on"""

@@ -1,6 +1,13 @@
 """The neighbour-joining tree on the device (include/selection_hip.h section 2l) against tests/nj_model.py, bit for bit:
 selhip_neighbor_joining into guarded buffers, every case twice and byte-equal, over both scan paths (16-byte and 8-byte loads), the
-slot kernels under the "vertex_blocks" hook, the refusals, the context entry and the command line."""
+slot kernels under the "vertex_blocks" hook, the refusals, the context entry and the command line.
+
+Beyond the well-behaved matrices (the sets are tests/nj_model.py's, their premises tests/test_nj_host.py's):
+  test_later_trips_decide, test_later_trips_under_the_vertex_hook   n = 1 031 and 2 055: the winning row in the last trip of the pick's
+                      walk, three cells per lane of the row sums, ties across trips, waves and sweep steps; the model's first 16 records
+  test_signed_zero_literals, test_signed_zeros   -0.0 cells survive the mirror: two truths worked out by hand, and three kinds of set
+  test_sums_that_overflow   finite cells near 1e308: NaN q counts as +inf; the one comparison that takes a NaN for a NaN
+  test_context_small_sets_and_null_arguments   contexts of 0, 1, 2, 3 and 5 genomes, d_joins NULL, n_joins_out NULL, a pending pass"""
 import ctypes as C
 import functools
 import subprocess
@@ -16,6 +23,7 @@ from test_matrix_gpu import synth
 
 import cuda_selection_criteria_amd as pkg
 from cuda_selection_criteria_amd import FP_FMA, NJ_DTYPE, SelhipError, Selector
+from cuda_selection_criteria_amd._lib import check as lib_check
 
 pytestmark = pytest.mark.gpu
 
@@ -30,16 +38,7 @@ LAYOUTS = [(0, 0), (3, 0), (0, 1), (3, 1)]      # (ld - n, doubles behind a 16-b
 @functools.lru_cache(maxsize=None)
 def matrices(n):
     """{value set: (n x n float64 of which the strict upper triangle counts, the model's records)}, computed once"""
-    rng = np.random.default_rng(2000 + n)
-    sets = {"distinct": (rng.permutation(n * n).reshape(n, n) + rng.random((n, n)) / 2) / float(max(n * n, 1))}
-    if n <= 513:
-        sets["negative"] = 10.0 * rng.random((n, n)) ** 4                     # far from a metric: negative branch lengths
-        if n >= 3:
-            sets["dyadic"] = NM.dyadic_tree(n, n)[0]
-    if n <= 257:                                                              # ties: the smallest (a, b)
-        sets["levels"] = rng.choice([0.25, 0.5, 0.75], size=(n, n))
-        sets["equal"] = np.full((n, n), 0.5)
-    return {k: (v, NM.neighbor_joining(v)) for k, v in sets.items()}
+    return {k: (v, NM.neighbor_joining(v)) for k, v in NM.value_sets(n).items()}
 
 
 def nj_raw(dist, ld_extra=0, offset=0):
@@ -92,6 +91,127 @@ def test_slot_kernels_under_the_vertex_hook(blocks):
             assert nj_raw(dist).tobytes() == want.tobytes() and nj_raw(dist, 3, 1).tobytes() == want.tobytes()
         finally:
             sel.set_param("vertex_blocks", 0)
+
+
+BOTH_SCANS = [(0, 0), (3, 1)]                    # nj_scan_kernel<true> and <false>
+TRIP_SETS = ("forged", "equal", "levels", "twins")
+
+
+@functools.lru_cache(maxsize=None)
+def trip_case(n, vname):
+    """(matrix, the first NM.PREFIX records of the model) of a set whose answer the later trips of the 1 024-lane loops decide"""
+    dist = NM.forged(n) if vname == "forged" else NM.tie_sets(n)[vname]
+    return dist, NM.neighbor_joining(dist, first=NM.PREFIX)
+
+
+def twice_in_both_scans(dist, want, compare=None):
+    """`dist` through both scan instantiations, each twice and byte-equal: the device's first len(want) records are the model's (by
+    bytes, or by compare(got, want)), and whatever lies behind them is the same in all four runs.  Returns the records"""
+    first = None
+    for layout in BOTH_SCANS:
+        got, again = nj_raw(dist, *layout), nj_raw(dist, *layout)
+        head = got[:len(want)]
+        if compare is None:
+            assert head.tobytes() == want.tobytes(), (layout, np.flatnonzero(head != want)[:3], head[:2], want[:2])
+        else:
+            compare(head, want, layout)
+        assert again.tobytes() == got.tobytes(), layout
+        first = got if first is None else first
+        assert got.tobytes() == first.tobytes(), "the two scan paths give different records"
+    return first
+
+
+def check_trip_case(n, vname):
+    dist, want = trip_case(n, vname)
+    got = twice_in_both_scans(dist, want)
+    assert len(got) == n - 1 and np.all(got["a"] < got["b"])
+    if vname == "equal":                                                      # the truth that does not depend on the model: a star
+        assert np.all(got["a"] == 0) and np.array_equal(got["b"], np.arange(1, n))
+        assert np.all(got["len_b"][:-1] == 0.25) and np.all(got["len_a"][1:-1] == 0.0) and got["len_a"][-1] == got["len_b"][-1] == 0.125
+    if vname == "forged":
+        assert (int(got["a"][0]), int(got["b"][0])) == NM.forged_pair(n)
+    if vname == "twins":
+        assert [(int(e["a"]), int(e["b"])) for e in got[:2]] == [NM.TWIN, NM.forged_pair(n)]
+
+
+@pytest.mark.parametrize("vname", TRIP_SETS)
+@pytest.mark.parametrize("n", NM.TRIP_SIZES)
+def test_later_trips_decide(n, vname):
+    """n = 1 024 + 7 and 2 * 1 024 + 7: nj_pick_kernel walks the rows' bests in two and three trips and the winning row lies in the
+    last one ("forged": the pair (n - 4, n - 2), premise pinned by tests/test_nj_host.py); nj_rowsum_kernel adds two and three cells
+    per lane, and the forged columns n - 4 and n - 2 carry most of every row's sum; ties are resolved across the trips of a lane,
+    the waves and the scan workgroups' sweep steps ("equal": every q ties, "twins": the smallest q lies once in wave 1 and once in a
+    later trip of wave 0, "levels").  The model's first 16 records; the rest between the runs and the layouts"""
+    check_trip_case(n, vname)
+
+
+@pytest.mark.parametrize("blocks", (1, 3))
+def test_later_trips_under_the_vertex_hook(blocks):
+    """... and with nj_init_kernel and nj_update_kernel in 5 and 2 trips of their own loops"""
+    with Selector(0) as sel:
+        sel.set_param("vertex_blocks", blocks)
+        try:
+            for vname in TRIP_SETS:
+                check_trip_case(NM.TRIP_SIZES[0], vname)
+        finally:
+            sel.set_param("vertex_blocks", 0)
+
+
+def f64_bits(*values):
+    return np.array(values, dtype=np.float64).view(np.uint64).tolist()
+
+
+def test_signed_zero_literals():
+    """section 2l evaluated by hand (tests/test_nj_host.py holds the model to the same two): the mirror copies a -0.0 cell, so
+    0.5 * -0.0 = -0.0 at n = 2, and five slots of -0.0 give (0, 1, -0.0 + 0.0 / 6 = +0.0, -0.0 - +0.0 = -0.0)"""
+    for layout in BOTH_SCANS:
+        two = nj_raw(np.array([[0.0, -0.0], [0.0, 0.0]]), *layout)
+        assert (int(two["a"][0]), int(two["b"][0])) == (0, 1) and f64_bits(two["len_a"][0], two["len_b"][0]) == f64_bits(-0.0, -0.0), (layout, two)
+        five = nj_raw(np.triu(np.full((5, 5), -0.0), 1), *layout)
+        assert (int(five["a"][0]), int(five["b"][0])) == (0, 1) and f64_bits(five["len_a"][0], five["len_b"][0]) == f64_bits(0.0, -0.0), (layout, five)
+
+
+@functools.lru_cache(maxsize=None)
+def zero_cases(n):
+    return {k: (v, NM.neighbor_joining(v)) for k, v in NM.zero_sets(n).items()}
+
+
+@pytest.mark.parametrize("n", NM.ZERO_SIZES)
+def test_signed_zeros(n):
+    """-0.0 in every cell, in a random half of an all-zero matrix, and among the zeros of a four-level matrix: bytes and all"""
+    for vname, (dist, want) in zero_cases(n).items():
+        got = twice_in_both_scans(dist, want)
+        assert len(got) == n - 1, vname
+
+
+def same_but_for_the_nans(got, want, where):
+    """THE OVERFLOW SETS ONLY.  a and b exactly; a length by its bit pattern where the model's is no NaN, and by being a NaN where it is:
+    inf - inf gives a NaN whose sign and payload differ between x86 (the model: the default NaN with the sign set) and the GPU (its
+    canonical quiet NaN), and section 2l says nothing about them.  No other case of this file may use this comparison"""
+    assert np.array_equal(got["a"], want["a"]) and np.array_equal(got["b"], want["b"]), (where, np.flatnonzero((got["a"] != want["a"]) | (got["b"] != want["b"]))[:3])
+    for field in ("len_a", "len_b"):
+        g, w = got[field], want[field]
+        nan = np.isnan(w)
+        assert np.array_equal(np.isnan(g), nan), (where, field, np.flatnonzero(np.isnan(g) != nan)[:3])
+        assert np.array_equal(g[~nan].view(np.uint64), w[~nan].view(np.uint64)), (where, field)
+
+
+@functools.lru_cache(maxsize=None)
+def overflow_cases(n):
+    return {k: (v, NM.neighbor_joining(v)) for k, v in NM.overflow_sets(n).items()}
+
+
+@pytest.mark.parametrize("n", NM.OVERFLOW_SIZES)
+def test_sums_that_overflow(n):
+    """finite cells near 1e308: the row sums are +inf, q is inf - inf = NaN and counts as +inf; where every q is +inf the first two
+    active slots are joined.  The run-to-run and layout-to-layout comparisons stay by bytes: the device's NaNs are its own, every time"""
+    for vname, (dist, want) in overflow_cases(n).items():
+        got = twice_in_both_scans(dist, want, compare=lambda g, w, layout: same_but_for_the_nans(g, w, (n, vname, layout)))
+        assert len(got) == n - 1 and np.all(got["a"] < got["b"]), vname
+        if vname == "huge" and n >= 65:
+            assert np.isnan(got["len_a"]).all() and np.isnan(got["len_b"]).all()
+        if vname == "mixed":
+            assert np.isinf(got["len_a"]).any() and np.isnan(got["len_a"]).any() and np.isfinite(got["len_a"]).any()
 
 
 @pytest.mark.parametrize("bad", [np.nan, np.inf, -np.inf])
@@ -157,6 +277,58 @@ def test_context_synthetic_set(oracle):
         sel.upload(*ranked(oracle, hll, aux, FP_FMA))
         assert np.isnan(sel.matrix("jaccard").cpu().numpy()[0, 1])
         check_context(sel)
+
+
+def ctx_nj_raw(sel, measure, joins=True, count=True):
+    """selhip_ctx_neighbor_joining into a guarded buffer (joins=False: d_joins NULL; count=False: n_joins_out NULL):
+    (the records, the count or -5 where none was asked for)"""
+    cap = max(sel.n - 1, 0)
+    jbuf = torch.full(((cap + 2 * GUARD) * 6,), SENTINEL, dtype=torch.int32, device="cuda")
+    f = C.c_int64(-5)
+    rc = sel._lib.selhip_ctx_neighbor_joining(sel._ctx, pkg.measure_code(measure), jbuf.data_ptr() + 24 * GUARD if joins else None, C.byref(f) if count else None)
+    j = jbuf.cpu().numpy()
+    if rc != 0 or not joins:
+        assert np.all(j == SENTINEL)                                          # nothing is written
+    lib_check(rc, sel._ctx)
+    assert np.all(j[:6 * GUARD] == SENTINEL) and np.all(j[6 * (GUARD + cap):] == SENTINEL)
+    return j[6 * GUARD:6 * (GUARD + cap)].copy().view(NJ_DTYPE), f.value
+
+
+@pytest.mark.parametrize("n", (0, 1, 2, 3, 5))
+def test_context_small_sets_and_null_arguments(oracle, n):
+    """the first n genomes of test_context_synthetic_set's set (three empty sketches in front): no genome and one genome give no
+    record and write nothing, two give the last join alone; d_joins NULL and n_joins_out NULL; a pending pass refuses"""
+    hll, aux = synth("cfg2-spread", 130)
+    hll = hll[:n].copy()
+    hll[:3] = 0
+    with Selector(0) as sel:
+        sel.upload(*ranked(oracle, hll, aux[:n], FP_FMA))
+        assert sel.n == n
+        if n >= 1:
+            check_context(sel)                                                # (n = 1: "nj" counts the call, the other timers stand)
+        for measure in ("jaccard", "max_containment", "smh_jaccard"):
+            want = NM.neighbor_joining(np.zeros((n, n)))
+            if n >= 2:
+                sim = sel.matrix(measure).cpu().numpy()
+                dist = 1.0 - sim
+                dist[np.isnan(sim)] = 1.0
+                want = NM.neighbor_joining(dist)
+            assert len(want) == max(n - 1, 0)
+            got, f = ctx_nj_raw(sel, measure)
+            assert f == max(n - 1, 0) and got.tobytes() == want.tobytes(), measure
+            got, f = ctx_nj_raw(sel, measure, joins=False)
+            assert f == max(n - 1, 0) and len(got) == max(n - 1, 0), measure
+            got, f = ctx_nj_raw(sel, measure, count=False)
+            assert f == -5 and got.tobytes() == want.tobytes(), measure
+        if n >= 2:
+            sel.run_async(0.5)
+            try:
+                with pytest.raises(SelhipError, match="still pending") as err:
+                    ctx_nj_raw(sel, "jaccard")
+                assert err.value.code == -5                                   # SELHIP_E_STATE
+            finally:
+                sel.finish()
+            assert ctx_nj_raw(sel, "jaccard")[1] == n - 1
 
 
 @pytest.mark.parametrize("args,kw", [([], dict(measure="jaccard")), (["-E", "smh", "-a", "512"], dict(measure="smh_jaccard", aux_bytes=512))], ids=["jaccard", "smh"])

@@ -411,6 +411,37 @@ def _linkage(env, case_id):
     return body
 
 
+def nj_outputs(n):
+    """the caller-owned record array of a neighbour-joining call (24-byte records as bytes), poisoned in front of every call"""
+    return torch.empty((n - 1, pkg.NJ_DTYPE.itemsize), dtype=torch.uint8, device="cuda")
+
+
+def nj_records(env, rec, f, what):
+    raw = env.host_any_stream(rec)
+    assert 0 <= f <= len(raw) and np.all(raw[f:] == 0xA5), f"{what}: the records from {f} on are not the poison any more"
+    return np.ascontiguousarray(raw[:f]).reshape(-1).view(pkg.NJ_DTYPE)
+
+
+@case(*H.NJ_CASES)
+def _nj(env, case_id):
+    """selhip_ctx_neighbor_joining: n * n cells of scratch taken and released in the call, the matrix kernels, the distance transform,
+    the mirror and one tally read back, then 3 (n - 1) launches with nothing read in between and one copy of the records"""
+    measure = H.NJ_CASES[case_id]
+    env.database(extra=(lambda S: {"aux": S.dense_aux}) if measure == "smh_jaccard" else None)
+    sel = selector(env)
+    joins = nj_outputs(N_D)
+    env.poison(joins)
+
+    def body(env):
+        attach(env, sel)
+        env.stall()
+        cnt = C.c_int64(-5)
+        check(sel._lib.selhip_ctx_neighbor_joining(sel._ctx, pkg.measure_code(measure), joins.data_ptr(), C.byref(cnt)), sel._ctx)
+        assert cnt.value == N_D - 1
+        return nj_records(env, joins, cnt.value, case_id)
+    return body
+
+
 @case("two_contexts")
 def _two_contexts(env, case_id):
     """two contexts on two streams over the same attached tensors; both passes are enqueued before either is finished"""
@@ -629,6 +660,44 @@ def _b_linkage(env, case_id):
         return out
     outputs = [t for v in lay.values() for t in v[2:4]]
     return launcher(env, lambda S: {"dist": S.linkage_dist}, outputs, call, result, asynchronous=False, late=("dist",))
+
+
+@case("selhip_neighbor_joining")
+def _b_nj(env, case_id):
+    """the neighbour-joining tree of a caller's matrix, a late input, in both layouts of H.LINKAGE_LAYOUTS (the call consumes the staged
+    copy), each into poisoned records of its own; then a second matrix, which holds a NaN cell in the real set alone: the entry reads
+    its tally of such cells back before the first join, and must refuse the real set's matrix -- writing nothing -- and no other"""
+    n = N_D
+    lay = {}
+    for tag, (ld_extra, offset) in {**H.LINKAGE_LAYOUTS, "refused": (0, 0)}.items():
+        ld = n + ld_extra
+        buf = torch.full((n * ld + 2 + offset,), float("nan"), dtype=torch.float64, device="cuda")
+        assert buf.data_ptr() % 16 == 0
+        lay[tag] = (buf[offset:offset + n * ld].view(n, ld), ld, nj_outputs(n), C.c_int64(-5))
+    codes = {}
+
+    def call(T, st):
+        for tag, (view, ld, joins, f) in lay.items():
+            f.value = -5
+            view[:, :n].copy_(T["dist_refused" if tag == "refused" else "dist"], non_blocking=True)
+            codes[tag] = pkg.hip_lib().selhip_neighbor_joining(view.data_ptr(), n, ld, joins.data_ptr(), C.byref(f), st)
+            if tag != "refused":
+                check(codes[tag])
+
+    def result():
+        out = {f"joins-{tag}": nj_records(env, lay[tag][2], lay[tag][3].value, case_id) for tag in H.LINKAGE_LAYOUTS}
+        _, _, joins, f = lay["refused"]
+        if codes["refused"] != 0:
+            cell = "cell (%d, %d) is one" % H.NJ_BAD_CELL
+            assert cell in pkg.hip_lib().selhip_last_error(None).decode() and f.value == -5
+            assert np.all(env.host(joins) == 0xA5), "a refused call wrote records"
+        else:
+            assert f.value == n - 1
+        out["refusal"] = np.array([codes["refused"]], dtype=np.int32)
+        return out
+    outputs = [v[2] for v in lay.values()]
+    return launcher(env, lambda S: {"dist": S.nj_dist, "dist_refused": S.nj_dist_refused}, outputs, call, result, asynchronous=False,
+                    late=("dist", "dist_refused"))
 
 
 SWITCHES = ("switch-sig_cache", "switch-query_index")

@@ -47,7 +47,7 @@ def test_real_and_decoy_answers_differ(sets, case_id):
 def test_late_inputs_differ(sets):
     """what is written behind run A's second delay differs between the sets too, and the pair lists are valid"""
     a, b = sets["real"], sets["decoy"]
-    for name in ("pair_list", "prio", "row_pos", "col_pos", "block_pairs", "edges", "keys", "perm", "forest_values", "linkage_dist"):
+    for name in ("pair_list", "prio", "row_pos", "col_pos", "block_pairs", "edges", "keys", "perm", "forest_values", "linkage_dist", "nj_dist", "nj_dist_refused"):
         assert not np.array_equal(getattr(a, name), getattr(b, name)), name
     for S in (a, b):
         for p in (S.pair_list, S.block_pairs, S.edges):
@@ -81,8 +81,31 @@ def test_hierarchy_premises(sets):
         assert len(S.block_linkage) == 6 and len(S.block_linkage["merges-wide"]) == H.N_D - 1
 
 
+def test_neighbour_joining_premises(sets):
+    """the three neighbour-joining ids are cases like the linkage's (run A, and run B for the answer alone); every set's trees are whole
+    (n - 1 records) and in both layouts; the second matrix of selhip_neighbor_joining is refused for the real set alone, for one NaN cell
+    of its upper triangle, and differs from the decoy's everywhere else too; no matrix is the linkage's"""
+    ids = {"selhip_neighbor_joining", *H.NJ_CASES}
+    assert ids <= H.RUN_A_ONLY and ids <= H.ANSWER_UNDER_BLOCKED_NULL and set(H.NJ_CASES) <= set(H.CONTEXT_CASES)
+    assert H.NJ_CASES == {"nj-jaccard": "jaccard", "nj-smh_jaccard": "smh_jaccard"} and H.NJ_BAD_CELL[0] < H.NJ_BAD_CELL[1] < H.N_D
+    for name, S in sets.items():
+        for value in (S.nj_jaccard, S.nj_smh_jaccard, S.block_nj["joins-wide"], S.block_nj["joins-narrow"]):
+            assert len(value) == H.N_D - 1 and (value["a"] < value["b"]).all()
+        assert sorted(S.block_nj_and_refusal) == ["joins-narrow", "joins-wide", "refusal"]
+        assert S.block_nj_and_refusal["refusal"].tolist() == [-1 if name == "real" else 0]
+        bad = np.argwhere(np.isnan(S.nj_dist_refused)).tolist()
+        assert bad == ([list(H.NJ_BAD_CELL)] if name == "real" else []) and np.isfinite(S.nj_dist).all()
+        assert S.nj_dist.shape == S.nj_dist_refused.shape == (H.N_D, H.N_D) and not np.array_equal(S.nj_dist, S.linkage_dist)
+    assert not H.same(sets["real"].nj_jaccard, sets["real"].nj_smh_jaccard)
+
+
 def test_bits_compare_bit_for_bit():
     nan = np.array([np.nan, 0.0])
     assert H.same(nan, nan.copy()) and not H.same(np.array([0.0]), np.array([-0.0]))
     assert H.same({"a": np.arange(3, dtype=np.int32)}, {"a": np.arange(3, dtype=np.int64)})
     assert not H.same(np.zeros(3), np.zeros(4))
+    import nj_model
+    a = np.array([(0, 1, 0.0, 0.5), (0, 2, np.nan, 1.0)], dtype=nj_model.NJ_DTYPE)
+    b, c = a.copy(), a.copy()
+    b["len_a"][0], c["b"][1] = -0.0, 3
+    assert H.same(a, a.copy()) and not H.same(a, b) and not H.same(a, c) and not H.same(a, a[:1])

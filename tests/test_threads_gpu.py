@@ -5,7 +5,7 @@ selhip_multi_select rest on that, and until now only the former's narrow path (a
 Each thread owns one context (tests/test_context_reuse_gpu.py's Live) that holds a set of its OWN -- another n, m and seed, so that
 anything crossing between contexts shows as the other set's answer -- on a non-blocking torch pool stream of its own, and makes its torch
 calls under torch.cuda.stream(that stream): the threads' device work can really overlap (ctypes releases the GIL during a library call).
-The sets, the 32 operations and their expected values are tests/context_reuse_model.py's; the context-free entries and theirs are
+The sets, the 34 operations and their expected values are tests/context_reuse_model.py's; the context-free entries and theirs are
 tests/thread_entries.py's.  Every comparison is bit for bit with the oracle and the models (stream_harness.same), never with a second
 context or a serial run.  The threads run in a thread_harness.Crew: a failure in one is re-raised here with every thread's log, breaks the
 barrier and stops the others before their next step; every wait has a time-out; behind a HIP error no test of this file starts another
@@ -19,8 +19,9 @@ GPU call.
                       shared between contexts meets a context in which every index and every key of the other one is valid
   test_walks_in_parallel[seed]   four threads, 60 free-running random steps each as test_walk takes them; one of them toggles the
                       process-wide grid hooks "cluster_blocks" and "vertex_blocks" among 0, 1 and 7 between its steps
-  test_free_standing_entries_in_parallel   the context-free entries from three threads on three sets, and their first calls in a fresh
-                      child process (tests/threads_child.py)
+  test_free_standing_entries_in_parallel   the context-free entries from three threads on three sets -- selhip_neighbor_joining in both
+                      layouts and selhip_ctx_neighbor_joining through a context of the call's own among them --, and their first calls in
+                      a fresh child process (tests/threads_child.py)
   test_context_churn_beside_work   one thread creates, loads, runs and destroys contexts (hipMalloc / hipFree: device-wide waits) while two work
   test_small_passes_side_by_side   two one-launch small passes (a grid barrier under an ordinary launch) and a regular pass, 50 times
   test_errors_stay_with_their_thread   a refusal on one thread, clean work on the other: whose message selhip_last_error gives whom"""
@@ -325,7 +326,7 @@ def test_walks_in_parallel(lib, streams, seed):
 FREE_SETS = ("BIG", "NARROW", "HIGHREG")
 FREE_ROUNDS = 3
 FREE_VALUES = ("block_flags", "block_hist", "block_estimates", "block_matches", "block_fold", "block_synth", "block_build", "block_permute",
-               "components", "greedy_reps", "edges", "keys", "perm", "forest_values", "block_forest", "linkage_dist", "block_linkage")
+               "components", "greedy_reps", "edges", "keys", "perm", "forest_values", "block_forest", "linkage_dist", "block_linkage", "nj_dist", "block_nj", "nj_jaccard")
 
 
 def test_free_standing_entries_in_parallel(lib, streams):
@@ -355,8 +356,9 @@ def test_free_standing_entries_in_parallel(lib, streams):
 
 def test_first_calls_meet_in_a_fresh_process():
     """selhip_synth_generate, selhip_build_sketches and the split builder raise their kernels' LDS limit in a std::call_once at their first
-    call.  In a fresh child process three threads make those first calls at once, and the first calls of selhip_linkage, on three streams
-    and three inputs, and compare what they get with the generator's host twin, the builder's oracle and the linkage model (a child
+    call.  In a fresh child process three threads make those first calls at once, and the first calls of selhip_linkage and of
+    selhip_neighbor_joining, on three streams and three inputs, and compare what they get with the generator's host twin, the builder's
+    oracle, the linkage model and the neighbour-joining model (a child
     process: the program of this one is not replaced)"""
     child = Path(__file__).with_name("threads_child.py")
     r = subprocess.run([sys.executable, str(child)], capture_output=True, text=True, timeout=T.TIMEOUT)

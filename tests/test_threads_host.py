@@ -70,6 +70,22 @@ def test_a_wait_that_ran_out_is_a_failure():
         del T._HIP_FAILED[before:]
 
 
+def test_every_entry_is_listed():
+    """tests/thread_entries.py (host side: the registrations import nothing of the device): every context-free block case of the stream
+    harness that names an entry of the library has a thread entry of that name, the neighbour-joining entries among them, and what the
+    fresh child process calls first are entries"""
+    import stream_harness as H
+    import thread_entries as E
+    for case_id in H.BLOCK_CASES:
+        if case_id.startswith("selhip_"):
+            assert case_id in E.ENTRIES, case_id
+    for name in ("selhip_linkage", "selhip_neighbor_joining", "selhip_ctx_neighbor_joining", "selhip_components", "selhip_greedy_representatives",
+                 "selhip_merge_sketches", "selhip_hll_cards", "selhip_build_sketches_split"):
+        assert name in E.ENTRIES, name
+    assert set(E.CALL_ONCE) <= set(E.FIRST_CALLS) <= set(E.ENTRIES) and len(set(E.FIRST_CALLS)) == len(E.FIRST_CALLS)
+    assert E.FIRST_CALLS[-2:] == ("selhip_linkage", "selhip_neighbor_joining")
+
+
 def test_names_hip_error():
     from cuda_selection_criteria_amd import SelhipError
     assert T.names_hip_error(SelhipError(-2, "hipMemcpyAsync(...) failed: an illegal memory access was encountered"))

@@ -214,6 +214,43 @@ def _linkage(S, st):
     return got, S.block_linkage
 
 
+@entry("selhip_neighbor_joining")
+def _nj(S, st):
+    """the neighbour-joining tree of the set's own matrix (Sets.nj_dist) in both layouts of stream_harness.LINKAGE_LAYOUTS, into output
+    buffers of its own: per-call scratch and 3 (n - 1) launches on the thread's stream, beside the other threads' calls"""
+    import torch
+    n = S.nj_dist.shape[0]
+    src, got = dev(S.nj_dist), {}
+    for tag, (ld_extra, offset) in H.LINKAGE_LAYOUTS.items():
+        ld = n + ld_extra
+        buf = torch.full((n * ld + 2 + offset,), float("nan"), dtype=torch.float64, device="cuda")
+        view = buf[offset:offset + n * ld].view(n, ld)
+        assert (ld % 2 == 0 and view.data_ptr() % 16 == 0) == (tag == "wide")
+        view[:, :n].copy_(src)
+        joins = poisoned((n + 1, pkg.NJ_DTYPE.itemsize), torch.uint8)
+        f = C.c_int64(-5)
+        check(pkg.hip_lib().selhip_neighbor_joining(view.data_ptr(), n, ld, joins.data_ptr(), C.byref(f), ptr(st)))
+        raw = joins.cpu().numpy()
+        assert f.value == n - 1 and np.all(raw[n - 1:] == 0xA5), (tag, f.value)
+        got[f"joins-{tag}"] = np.ascontiguousarray(raw[:n - 1]).reshape(-1).view(pkg.NJ_DTYPE)
+    return got, S.block_nj
+
+
+@entry("selhip_ctx_neighbor_joining")
+def _ctx_nj(S, st):
+    """the tree of the set's Jaccard distances through a context that is made and destroyed around the call, on the thread's stream"""
+    import torch
+    n = S.n_d
+    joins = poisoned((n + 1, pkg.NJ_DTYPE.itemsize), torch.uint8)
+    cnt = C.c_int64(-5)
+    with pkg.Selector(0, stream=st.cuda_stream) as sel:
+        sel.upload(S.D.hll, S.D.aux, S.D.cards)
+        check(sel._lib.selhip_ctx_neighbor_joining(sel._ctx, pkg.measure_code("jaccard"), joins.data_ptr(), C.byref(cnt)), sel._ctx)
+        raw = joins.cpu().numpy()
+    assert cnt.value == n - 1 and np.all(raw[n - 1:] == 0xA5), cnt.value
+    return np.ascontiguousarray(raw[:n - 1]).reshape(-1).view(pkg.NJ_DTYPE), S.nj_jaccard
+
+
 def merge_groups(S):
     return np.random.default_rng(S.seed + 9).integers(-1, N_GROUPS, S.n_d).astype(np.int32)
 
@@ -228,6 +265,6 @@ def _merge(S, st):
 # the entries whose first call in a process goes through a std::call_once (csrc/abi_blocks.inc: selhip_synth_generate,
 # selhip_build_sketches; csrc/host_build.hpp: the split builder's main launch)
 CALL_ONCE = ("selhip_synth_generate", "selhip_build_sketches", "selhip_build_sketches_split")
-# what three threads of a fresh process call first (tests/threads_child.py): those, and selhip_linkage, whose first call loads its seven
-# kernels and takes its scratch while the other threads do the same
-FIRST_CALLS = CALL_ONCE + ("selhip_linkage",)
+# what three threads of a fresh process call first (tests/threads_child.py): those, and selhip_linkage and selhip_neighbor_joining, whose
+# first calls load their kernels and take their scratch while the other threads do the same
+FIRST_CALLS = CALL_ONCE + ("selhip_linkage", "selhip_neighbor_joining")

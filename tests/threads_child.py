@@ -1,9 +1,9 @@
 """Run by tests/test_threads_gpu.py as a fresh child process: the FIRST calls of selhip_synth_generate, selhip_build_sketches,
-selhip_build_sketches_split and selhip_linkage of a process, made by three threads at once.  Each of the first three raises its kernel's
+selhip_build_sketches_split, selhip_linkage and selhip_neighbor_joining of a process, made by three threads at once.  Each of the first three raises its kernel's
 dynamic LDS limit in a std::call_once (csrc/abi_blocks.inc, csrc/host_build.hpp); a thread that got past the flag before the attribute
 stood would launch a kernel that asks for more LDS than it may.  selhip_linkage has no such flag: its first calls load its kernels and
-take their per-call scratch side by side.  Every thread has its own stream and inputs (three seeds); what it gets is compared with the
-generator's host twin, the builder's oracle and the linkage model (tests/thread_entries.py), computed before the first device call.
+take their per-call scratch side by side, and so do selhip_neighbor_joining's.  Every thread has its own stream and inputs (three seeds); what it gets is compared with the
+generator's host twin, the builder's oracle, the linkage model and the neighbour-joining model (tests/thread_entries.py), computed before the first device call.
 
 Prints "threads_child ok" and exits 0, or prints the failure and exits 1.  Not a test module: pytest does not collect it."""
 import sys
@@ -23,7 +23,7 @@ def main():
 
     sets = [E.bare_set(f"child{t}", 0xC41D0000 + 17 * t, m=(64, 128, 256)[t], p_aux=(6, 8, 10)[t]) for t in range(3)]
     for S in sets:                                                   # (host only: the generator's twin, the builder's oracle, the model)
-        S.block_synth, S.block_build, S.block_linkage
+        S.block_synth, S.block_build, S.block_linkage, S.block_nj
     streams = []
     while len(streams) < 3:
         s = torch.cuda.Stream()
