@@ -164,6 +164,8 @@ HIP_SYMBOLS = {
     "selhip_linkage": (_i, [_vp, _i64, _i64, _i, _d, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64), _vp]),
     "selhip_ctx_neighbor_joining": (_i, [_vp, _i, _vp, C.POINTER(_i64)]),
     "selhip_neighbor_joining": (_i, [_vp, _i64, _i64, _vp, C.POINTER(_i64), _vp]),
+    "selhip_ctx_gather": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "selhip_gather": (_i, [_vp, _i64, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "selhip_ctx_merge_groups": (_i, [_vp, _vp, _i64, C.POINTER(Merged)]),
     "selhip_merge_sketches": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "selhip_smh_a_pairs": (_i, [_vp, _i, _i, _i, _vp, _i64, _vp, _vp]),

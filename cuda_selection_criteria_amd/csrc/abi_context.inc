@@ -247,6 +247,13 @@ int selhip_ctx_set_param(selhip_ctx* c, const char* name, int value) {
         g_vertex_blocks.store(value, std::memory_order_relaxed);
         return SELHIP_OK;
     }
+    // (a test hook: bytes of LDS the screen's pick stage may stage a query's segment in, so that small segments take the streamed route;
+    //  0 = what the device reports; the same picks either way)
+    if (!std::strcmp(name, "gather_lds_cap")) {
+        if (value < 0) { set_err(&c->err, "gather_lds_cap must be >= 0 (0 = what the device reports for a workgroup)"); return SELHIP_E_BADARG; }
+        c->gather_lds_cap = value;
+        return SELHIP_OK;
+    }
     set_err(&c->err, "unknown parameter '%s'", name);
     return SELHIP_E_BADARG;
 }
@@ -289,6 +296,12 @@ int selhip_ctx_get_param(const selhip_ctx* c, const char* name, int* value) {
     if (!std::strcmp(name, "topk_admitted_lo")) { *value = (int)(c->rounds_admitted & 0x7FFFFFFFull); return SELHIP_OK; }            // records its rounds admitted: low ...
     if (!std::strcmp(name, "topk_admitted_hi")) { *value = (int)((c->rounds_admitted >> 31) & 0x7FFFFFFFull); return SELHIP_OK; }    // ... and high 31 bits
     if (!std::strcmp(name, "query_topk_lds_cap")) { *value = kTopkLdsCap; return SELHIP_OK; }              // longest segment its select kernel stages in LDS
+    if (!std::strcmp(name, "gather_lds_cap")) {                                                         // bytes of LDS the screen's pick stage stages a segment in
+        int cap = 0;
+        if (hipSetDevice(c->device) != hipSuccess || gather_device_lds(&cap)) return SELHIP_E_HIP;
+        *value = c->gather_lds_cap > 0 ? std::min(cap, c->gather_lds_cap) : cap;
+        return SELHIP_OK;
+    }
     if (!std::strcmp(name, "query_db_sig_builds")) { *value = c->q.db_sig_builds; return SELHIP_OK; }   // database signature builds of the query passes
     if (!std::strcmp(name, "query_db_index_builds")) { *value = c->q.db_idx_builds; return SELHIP_OK; } // builds of ALGO_INDEX's sorted signature index
     if (!std::strcmp(name, "query_db_index_kib")) {                                                     // its resident size (0 = none held)

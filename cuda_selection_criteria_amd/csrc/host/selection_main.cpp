@@ -527,6 +527,63 @@ static int run_matrix(const std::string& list_file, const std::string& query_fil
     return r ? 4 : hr ? 5 : 0;
 }
 
+// -w: no pass; the winner-takes-all screen of the query list against the database list (selhip_ctx_gather), one line per pick:
+// query_path, db_path, unique, matches, unique / m, matches / m -- queries in file-list order, each query's picks in pick order
+static int run_gather(const std::string& list_file, const std::string& query_file, const std::string& out_file, unsigned m, int c_min, int max_picks,
+                      int fp_mode, int threads) {
+    selhost_dataset* db = nullptr;
+    selhost_dataset* qs = nullptr;
+    if (selhost_dataset_load(&db, list_file.c_str(), m, 0, fp_mode, threads)) { std::cerr << "selection: -w: " << selhost_last_error() << "\n"; return 1; }
+    if (selhost_dataset_load(&qs, query_file.c_str(), m, 0, fp_mode, threads)) {
+        std::cerr << "selection: -w: cannot read query list '" << query_file << "': " << selhost_last_error() << "\n";
+        selhost_dataset_free(db);
+        return 1;
+    }
+    const int64_t n_d = selhost_dataset_size(db), n_q = selhost_dataset_size(qs);
+    std::vector<selhip_gather_pick_t> picks((size_t)n_q * (size_t)max_picks);
+    std::vector<int32_t> n_picks((size_t)n_q, 0);
+    selhip_ctx* ctx = nullptr;
+    int r = selhip_device_count() > 0 ? selhip_ctx_create(&ctx, 0) : SELHIP_E_NODEVICE;
+    if (r) {
+        std::cerr << "selection: no MI355X (gfx950) device available: " << selhip_last_error(nullptr) << "\n";
+        selhost_dataset_free(db); selhost_dataset_free(qs);
+        return 3;
+    }
+    void* d_picks = nullptr;
+    void* d_n = nullptr;
+    selhip_ctx_set_fp_mode(ctx, fp_mode);
+    r = selhip_ctx_upload(ctx, selhost_dataset_hll(db), selhost_dataset_aux(db), selhost_dataset_cards(db), n_d, (int)m, 14);
+    if (!r) r = selhip_ctx_upload_queries(ctx, selhost_dataset_hll(qs), selhost_dataset_aux(qs), selhost_dataset_cards(qs), n_q);
+    if (!r && n_q) r = selhip_malloc(&d_picks, picks.size() * sizeof(selhip_gather_pick_t));
+    if (!r && n_q) r = selhip_malloc(&d_n, n_picks.size() * sizeof(int32_t));
+    if (!r) r = selhip_ctx_gather(ctx, c_min, max_picks, static_cast<selhip_gather_pick_t*>(d_picks), static_cast<int32_t*>(d_n), nullptr);
+    if (!r && n_q) r = selhip_memcpy_d2h(n_picks.data(), d_n, n_picks.size() * sizeof(int32_t));
+    if (!r && n_q) r = selhip_memcpy_d2h(picks.data(), d_picks, picks.size() * sizeof(selhip_gather_pick_t));
+    if (r) std::cerr << "selection: " << selhip_last_error(ctx) << "\n";
+    selhip_ctx_destroy(ctx);
+    if (d_picks) selhip_free(d_picks);
+    if (d_n) selhip_free(d_n);
+    int hr = 0;
+    if (!r) {
+        std::vector<int64_t> by_line((size_t)n_q);                         // line of the query list -> rank
+        for (int64_t q = 0; q < n_q; ++q) by_line[(size_t)selhost_dataset_order(qs, q)] = q;
+        FILE* f = std::fopen(out_file.c_str(), "w");
+        if (!f) { std::cerr << "selection: -w: cannot write '" << out_file << "'\n"; hr = 1; }
+        for (int64_t line = 0; f && line < n_q; ++line) {
+            const int64_t q = by_line[(size_t)line];
+            for (int32_t t = 0; t < n_picks[(size_t)q]; ++t) {
+                const selhip_gather_pick_t& p = picks[(size_t)q * (size_t)max_picks + (size_t)t];
+                std::fprintf(f, "%s\t%s\t%d\t%d\t%f\t%f\n", selhost_dataset_name(qs, q), selhost_dataset_name(db, p.d), p.unique, p.matches,
+                             (double)p.unique / (double)m, (double)p.matches / (double)m);
+            }
+        }
+        if (f && std::fclose(f)) { std::cerr << "selection: -w: cannot write '" << out_file << "'\n"; hr = 1; }
+    }
+    selhost_dataset_free(db);
+    selhost_dataset_free(qs);
+    return r ? 4 : hr ? 5 : 0;
+}
+
 // a branch length or height as the shortest of %.15g, %.16g, %.17g that reads back to the same double
 static std::string newick_number(double x) {
     char buf[64];
@@ -774,10 +831,11 @@ int main(int argc, char* argv[]) {
     std::string linkage_arg = "";
     bool merge_given = false, groups_given = false, forest_given = false;
     bool newick_given = false, merges_given = false, method_given = false;
-    std::string method_arg = "";
+    std::string method_arg = "", gather_file = "";
+    bool gather_given = false;
     int tree_method = SELHIP_LINKAGE_AVERAGE;
     int c;
-    while ((c = getopt(argc, argv, "xl:b:a:h:c:C:G:t:g:nA:F:B:o:r:q:k:K:p:M:UE:S:V:R:DL:T:Y:Z:W:P:I:H:N:J:X:")) != -1) {
+    while ((c = getopt(argc, argv, "xl:b:a:h:c:C:G:t:g:nA:F:B:o:r:q:k:K:p:M:UE:S:V:R:DL:T:Y:Z:W:P:I:H:N:J:X:w:")) != -1) {
         switch (c) {
             case 'x': std::cout << "Usage: -l -h -a -b [-c smh_a|hll_a|hll_an|none|smh_c -C c_min|-G gamma] [-t threads] [-g gpus] [-n] [-A auto|stream|sig] [-F 0|1] [-B block] [-o file] | -r file\n"
                                    "       -l db_list -q query_list -h -a [-c smh_a|hll_a|hll_an|none|smh_c -C c_min|-G gamma] [-n] [-A auto|stream|sig|index] [-F 0|1] [-k best_per_query]   (query-vs-database selection)\n"
@@ -794,6 +852,7 @@ int main(int argc, char* argv[]) {
                                    "       ... -L clusters.tsv -Z single|greedy [-T min_value] [-Y max_degree|min_rank|max_rank | -W scores.tsv]   (-Z greedy: greedy representative clusters, CD-HIT style: genomes visited in the -Y order or by descending score, every other genome to its most similar representative; a sixth column: value to the representative)\n"
                                    "       -l list [-p pair_file | -K best_per_genome [-R rows]] ... -H forest.tsv [-T min_value]   (besides the output: the maximum spanning forest of the selected pairs = the merges of the single-linkage dendrogram, one line per edge, best first: path_a, path_b, value; may stand beside -L)\n"
                                    "       -l list -N tree.nwk [-J merges.tsv] [-X average|complete|weighted|single|nj] [-E smh -a bytes | -S max_containment] [-M out.tsv]   (no selection: the hierarchy of the dense matrix under 1 - similarity, on the device: a Newick tree and / or one line per merge: path_a, path_b, height, size; -X nj: the neighbour-joining tree, one line per join: path_a, path_b, len_a, len_b)\n"
+                                   "       -l db_list -q query_list -a bytes -w out.tsv [-C c_min] [-k max_picks]   (no selection: the winner-takes-all screen, every query decomposed greedily into database genomes; one line per pick: query_path, db_path, unique, matches, unique / m, matches / m)\n"
                                    "       ... -c hll_a|hll_an -a bytes -D   (with -l, -q, -p, -k, -K, -g, -B: no .hll_<p> file is read, the auxiliary HLL sketches are folded from the .hll registers)\n"
                                    "       ... -L clusters.tsv [-Z ...] -P dir   (besides the output: one merged sketch set per cluster in dir -- cluster_<id>.hll, .smh<m>, .hll_<p> -- and dir/filelist.txt, a database for -l)\n"
                                    "       -l list [-c ... -a bytes] -I groups.tsv -P dir   (no selection: the genomes merged by the groups of 'path<TAB>group_name' lines, one sketch set per group_name in dir)\n"; return 0;
@@ -816,6 +875,7 @@ int main(int argc, char* argv[]) {
             case 'N': g_newick_file = optarg; newick_given = true; break;
             case 'J': g_merges_file = optarg; merges_given = true; break;
             case 'X': method_arg = optarg; method_given = true; break;
+            case 'w': gather_file = optarg; gather_given = true; break;
             case 'I': g_groups_file = optarg; groups_given = true; break;
             case 'k': top_k = std::strtoll(optarg, nullptr, 10); topk_given = true; break;
             case 'K': nbr_k = std::strtoll(optarg, nullptr, 10); nbr_given = true; break;
@@ -839,6 +899,20 @@ int main(int argc, char* argv[]) {
     }
     // -N, -J and their -X: checked before any file is read or device opened
     const bool tree_given = newick_given || merges_given;
+    if (gather_given) {
+        // -w: the winner-takes-all screen of the queries against the database; no pass runs, so what belongs to one, or to another output, is refused
+        const char* other = !pair_file.empty() ? "-p" : matrix_given ? "-M" : gpus_given ? "-g" : ooc_block ? "-B" : !dump_file.empty() ? "-r" : cluster_given ? "-L"
+                          : forest_given ? "-H" : newick_given ? "-N" : nullptr;
+        if (other) { std::cerr << "selection: -w (the winner-takes-all screen) cannot be combined with " << other << "\n"; return 2; }
+        if (query_file.empty()) { std::cerr << "selection: -w needs the query list (-q) beside the database list (-l)\n"; return 2; }
+        if (gather_file.empty() || list_file.empty()) { std::cerr << "selection: -w needs the name of the file to write and the database list (-l)\n"; return 2; }
+        const int m = aux_bytes / 8;
+        if (!aux_given || m < 1 || m > 4096) { std::cerr << "selection: -w reads the .smh<m> files: give their size with -a (bytes, 8 per bucket, up to 4096 buckets)\n"; return 2; }
+        const long long c_min = cmin_given ? min_matches : 1, picks = topk_given ? top_k : 64;
+        if (c_min < 1 || c_min > m) { std::cerr << "selection: -w: -C must be in 1.." << m << " (the m = -a / 8 buckets)\n"; return 2; }
+        if (picks < 1 || picks > SELHIP_GATHER_MAX_PICKS) { std::cerr << "selection: -w: -k must be in 1.." << SELHIP_GATHER_MAX_PICKS << "\n"; return 2; }
+        return run_gather(list_file, query_file, gather_file, (unsigned)m, (int)c_min, (int)picks, fp_mode, threads);
+    }
     if (method_given && !tree_given) { std::cerr << "selection: -X (the linkage method) is an option of -N / -J (the hierarchy of the dense matrix)\n"; return 2; }
     if (tree_given) {
         const char* clash = !query_file.empty() ? "-q" : !pair_file.empty() ? "-p" : gpus_given ? "-g" : ooc_block != 0 ? "-B" : !dump_file.empty() ? "-r"

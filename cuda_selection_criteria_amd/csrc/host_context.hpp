@@ -160,8 +160,8 @@ static_assert(kCounterBlocks == kMaxChunks + 1, "common.cuh: counter blocks per 
 constexpr int kMaxAuxP = SELHIP_MAX_AUX_P;   // auxiliary HLL precision accepted by every entry point: aux_fused_kernel counts in 16-bit bins (a bin holds up to 2^p_aux)
 constexpr long long kEnumPairs = 1ll << 26;    // hll_a / hll_an as first criterion: pairs listed per sub-pass (512 MiB of int2)
 
-enum { T_PREP = 0, T_STAGE1, T_HIST, T_SELECT, T_TOTAL, T_SIGBUILD, T_JOIN, T_VERIFY, T_AUX, T_GROUP, T_DENSE, T_TOPK, T_MATRIX, T_MATRIX_SMH, T_CLUSTER, T_GREEDY, T_MERGE, T_FOREST, T_LINKAGE, T_NJ, T_COUNT };
-const char* kTimerNames[T_COUNT] = {"prep", "stage1", "hist", "select", "total", "sigbuild", "join", "verify", "aux", "group", "dense", "topk", "matrix", "matrix_smh", "cluster", "greedy", "merge", "forest", "linkage", "nj"};
+enum { T_PREP = 0, T_STAGE1, T_HIST, T_SELECT, T_TOTAL, T_SIGBUILD, T_JOIN, T_VERIFY, T_AUX, T_GROUP, T_DENSE, T_TOPK, T_MATRIX, T_MATRIX_SMH, T_CLUSTER, T_GREEDY, T_MERGE, T_FOREST, T_LINKAGE, T_NJ, T_GATHER_MASK, T_GATHER_PICK, T_COUNT };
+const char* kTimerNames[T_COUNT] = {"prep", "stage1", "hist", "select", "total", "sigbuild", "join", "verify", "aux", "group", "dense", "topk", "matrix", "matrix_smh", "cluster", "greedy", "merge", "forest", "linkage", "nj", "gather_mask", "gather_pick"};
 
 }  // namespace
 
@@ -383,6 +383,10 @@ struct selhip_ctx {
     int linkage_merges_last = -1;       // its F ("linkage_merges_last")
     int linkage_rowscans_last = -1;     // the rows its scan kernel took over all rounds ("linkage_rowscans_last")
     int linkage_rescans_last = -1;      // its rescan rounds ("linkage_rescans_last")
+
+    // the screen (selhip_ctx_gather; kernel_gather.cuh): "gather_lds_cap", bytes of LDS the pick stage may stage a segment in; 0 = what the
+    // device reports for a workgroup (a test hook lowers it, so that small segments take the streamed route)
+    int gather_lds_cap = 0;
 
     // sketches merged by group (selhip_ctx_merge_groups; kernel_merge.cuh, host_merge.hpp): scratch the call owns
     MergeScratch mg;

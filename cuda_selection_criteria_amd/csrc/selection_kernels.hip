@@ -58,6 +58,9 @@
 //                       reciprocal nearest neighbours -- row scans of the dirty rows, ordered pair compaction, Lance-Williams update in place
 //   kernel_nj.cuh       neighbour-joining tree of a dense f64 distance matrix: per join a fused transform-and-argmin scan of the active
 //                       triangle (several list rows per workgroup, the row-sum vector shared in registers), one pick workgroup, one update
+//   kernel_gather.cuh   winner-takes-all screen (greedy decomposition of every query into database rows): the fast SuperMinHash matrix
+//                       enumeration with the v_cmp_eq_u64 ballots kept as per-candidate bucket masks (count, scan, fill), then one workgroup
+//                       per query that runs every pick round in one launch over masks staged word-major in LDS
 //   kernel_merge.cuh    sketches merged by group: a counting sort of the members, then a segmented reduction of the rows (u8 maximum of the
 //                       HLL registers, u64 minimum of the SuperMinHash buckets) in segments of at most SELHIP_MERGE_SEGMENT members per level
 //
@@ -80,6 +83,7 @@
 #include <cstring>
 #include <limits>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <tuple>
 #include <vector>
@@ -120,6 +124,7 @@
 #include "host_plan.hpp"         // host decisions that are plain arithmetic: build shape, pass plan, criterion constants, overflow rule
 #include "kernel_matrix.cuh"     // (behind host_plan.hpp: the kernel reads the unit, slab and mirror rules written there)
 #include "kernel_matrix_smh.cuh" // (behind kernel_matrix.cuh: MatrixOut)
+#include "kernel_gather.cuh"     // (behind kernel_matrix_smh.cuh: the fast path's unit, matrix_smh_q)
 #include "host_context.hpp"      // struct selhip_ctx, device buffers (signature sets, bit planes, counter sets), timers, helpers
 #include "host_pass.hpp"         // pass scheduler: dispatch of every stage, chunk lanes, scratch sizing
 #include "host_pairs.hpp"        // pair-list passes: the chain behind selhip_ctx_run_pairs
@@ -131,6 +136,7 @@
 #include "host_forest.hpp"       // maximum spanning forest: rounds, sort and launches behind selhip_ctx_spanning_forest / selhip_spanning_forest
 #include "host_linkage.hpp"      // dense-matrix hierarchy: checks, scratch and rounds behind selhip_linkage / selhip_ctx_linkage
 #include "host_nj.hpp"           // neighbour-joining tree: checks, scratch and joins behind selhip_neighbor_joining / selhip_ctx_neighbor_joining
+#include "host_gather.hpp"       // winner-takes-all screen: checks, scratch and launches behind selhip_gather / selhip_ctx_gather
 #include "host_merge.hpp"       // sketches merged by group: checks, levels and launches behind selhip_merge_sketches / selhip_ctx_merge_groups
 #include "host_build.hpp"       // split sketch builder: items, launches, the reduction through merge_run, the fallback launch
 #include "abi_context.inc"       // C ABI: context (create, upload / attach, run, results, timing)
@@ -142,6 +148,7 @@
 #include "abi_forest.inc"        // C ABI: maximum spanning forest of the result list (ctx_spanning_forest) and of a caller's edge list (spanning_forest)
 #include "abi_linkage.inc"       // C ABI: average / complete / weighted / single linkage of a dense matrix (ctx_linkage, linkage)
 #include "abi_nj.inc"            // C ABI: neighbour-joining tree of a dense matrix (ctx_neighbor_joining, neighbor_joining)
+#include "abi_gather.inc"        // C ABI: winner-takes-all screen of the queries against the database (ctx_gather, gather)
 #include "abi_merge.inc"        // C ABI: sketches merged by group (merge_sketches, ctx_merge_groups)
 #include "abi_build.inc"        // C ABI: sketch construction with long genomes split across workgroups (build_sketches_split, build_split_plan)
 #include "abi_blocks.inc"        // C ABI: building blocks, synthetic sketches, sketch construction, memory helpers

@@ -649,6 +649,26 @@ class Selector:
         check(self._lib.selhip_ctx_neighbor_joining(self._ctx, measure_code(measure), joins.data_ptr() if joins.numel() else None, C.byref(cnt)), self._ctx)
         return _nj_result(joins, int(cnt.value), to_host)
 
+    # -- winner-takes-all screen of the queries against the database ------------------------------------
+    def gather(self, min_matches: int = 1, max_picks: int = 64, to_host: bool = True) -> dict:
+        """every loaded query decomposed greedily into database genomes, on the device (selhip_ctx_gather; the definition is section
+        2m of include/selection_hip.h): per round the genome that shares most of the query's still unexplained buckets (ties: the
+        smaller rank), until that count falls below min_matches or max_picks picks are made.  Only the SuperMinHash rows are read.
+        Returns a dict: "picks" GATHER_DTYPE records {q, d, unique, matches} compacted, queries ascending, in pick order (a numpy
+        array; with to_host=False a torch int32 [P, 4] tensor on the device), "n_picks" [n_q] and "unexplained" [n_q] int32"""
+        import torch
+        if self.n_q is None:
+            check(self._lib.selhip_ctx_gather(self._ctx, int(min_matches), int(max_picks), None, None, None), self._ctx)   # (raises: no queries)
+        dev = torch.device("cuda", self.device)
+        with torch.cuda.device(dev):
+            picks = torch.empty((self.n_q or 0, int(max_picks), 4), dtype=torch.int32, device=dev)
+            n_picks = torch.zeros(self.n_q or 0, dtype=torch.int32, device=dev)
+            left = torch.zeros(self.n_q or 0, dtype=torch.int32, device=dev)
+            torch.cuda.synchronize(dev)
+            check(self._lib.selhip_ctx_gather(self._ctx, int(min_matches), int(max_picks), picks.data_ptr() if picks.numel() else None,
+                                              n_picks.data_ptr() if self.n_q else None, left.data_ptr() if self.n_q else None), self._ctx)
+        return _gather_result(picks, n_picks, left, to_host)
+
     # -- sketches merged by group ---------------------------------------------------------------------
     def merge(self, groups, n_groups: Optional[int] = None, to_host: bool = False) -> dict:
         """one union sketch per group of the context's set, merged on the device (selhip_ctx_merge_groups): the element-wise maximum of
@@ -1369,6 +1389,80 @@ def nj_from_filelist(list_file: str, aux_bytes: int = 0, measure="jaccard", fp_m
         res = sel.neighbor_joining(measure)
     names = list(ds.names)
     res.update(names=names, order=np.asarray(ds.order), table=nj_table(names, res["joins"]), newick=nj_newick(res["joins"], names))
+    return res
+
+
+GATHER_DTYPE = np.dtype([("q", "<i4"), ("d", "<i4"), ("unique", "<i4"), ("matches", "<i4")])   # selhip_gather_pick_t
+
+
+def _gather_result(picks, n_picks, left, to_host: bool) -> dict:
+    """the dict of Selector.gather / gather from the device tensors a call filled: the first n_picks[q] records of every query's row"""
+    import torch
+    keep = torch.arange(picks.shape[1], device=picks.device)[None, :] < n_picks[:, None]
+    flat = picks[keep]                                              # (row-major: queries ascending, each in pick order)
+    if to_host:
+        return {"picks": np.ascontiguousarray(flat.cpu().numpy()).view(GATHER_DTYPE).reshape(-1), "n_picks": n_picks.cpu().numpy(),
+                "unexplained": left.cpu().numpy()}
+    return {"picks": flat, "n_picks": n_picks, "unexplained": left}
+
+
+def gather(q_smh, db_smh, min_matches: int = 1, max_picks: int = 64, device: int = 0, to_host: bool = True) -> dict:
+    """the winner-takes-all screen of section 2m over bucket rows of the caller's (selhip_gather): q_smh [n_q, m] and db_smh [n_d, m],
+    numpy uint64 arrays or torch int64 tensors (the bit pattern of the u64 buckets; UINT64_MAX = unfilled).  The dict: Selector.gather's"""
+    import torch
+    lib = hip_lib()
+    dev = torch.device("cuda", device)
+
+    def rows(a):
+        if hasattr(a, "data_ptr"):
+            assert a.dim() == 2 and a.element_size() == 8, "bucket rows: a 2-D tensor of 8-byte elements"
+            return a.to(dev).contiguous()
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint64).view(np.int64)).to(dev)
+
+    with torch.cuda.device(dev):
+        q, d = rows(q_smh), rows(db_smh)
+        assert q.shape[1] == d.shape[1], "queries and database: the same number of buckets"
+        n_q, n_d, m = int(q.shape[0]), int(d.shape[0]), int(q.shape[1])
+        picks = torch.empty((n_q, int(max_picks), 4), dtype=torch.int32, device=dev)
+        n_picks = torch.zeros(n_q, dtype=torch.int32, device=dev)
+        left = torch.zeros(n_q, dtype=torch.int32, device=dev)
+        check(lib.selhip_gather(q.data_ptr() if n_q else None, n_q, d.data_ptr() if n_d else None, n_d, m, int(min_matches), int(max_picks),
+                                picks.data_ptr() if picks.numel() else None, n_picks.data_ptr() if n_q else None, left.data_ptr() if n_q else None,
+                                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return _gather_result(picks, n_picks, left, to_host)
+
+
+def gather_table(q_names: Sequence[str], q_order, db_names: Sequence[str], picks, m: int) -> str:
+    """the text of `selection -w`: one line per pick, 'query_path<TAB>db_path<TAB>unique<TAB>matches<TAB>unique/m<TAB>matches/m' (the
+    shares with six decimals), queries in FILE-LIST order, each query's picks in pick order.  Names in rank order, q_order[rank] = the
+    query's line in its list"""
+    by_q = {}
+    for e in picks:
+        by_q.setdefault(int(e["q"]), []).append(e)
+    out = []
+    for r in np.argsort(np.asarray(q_order), kind="stable"):
+        for e in by_q.get(int(r), []):
+            u, c = int(e["unique"]), int(e["matches"])
+            out.append(f"{q_names[r]}\t{db_names[int(e['d'])]}\t{u}\t{c}\t{u / m:f}\t{c / m:f}\n")
+    return "".join(out)
+
+
+def gather_from_filelists(query_list: str, db_list: str, aux_bytes: int, min_matches: int = 1, max_picks: int = 64, fp_mode: int = FP_FMA,
+                          device: int = 0) -> dict:
+    """the screen of the genomes of query_list against those of db_list -- what `selection -l db_list -q query_list -a aux_bytes -w out.tsv
+    [-C min_matches] [-k max_picks]` computes; no pass runs.  The sketches are loaded and sorted as for a selection, m = aux_bytes // 8.
+    Returns Selector.gather's dict on the host plus "query_names" and "db_names" (rank order) and "table" (the text of -w)"""
+    m = aux_bytes // 8
+    if m < 1:
+        raise ValueError("the screen reads the SuperMinHash rows: aux_bytes >= 8")
+    qs = load_dataset(query_list, m, 0, fp_mode)
+    db = load_dataset(db_list, m, 0, fp_mode)
+    with Selector(device, fp_mode) as sel:
+        sel.upload(db.hll, db.aux, db.cards)
+        sel.upload_queries(qs.hll, qs.aux, qs.cards)
+        res = sel.gather(min_matches, max_picks)
+        m_rows = sel.m
+    res.update(query_names=list(qs.names), db_names=list(db.names), table=gather_table(qs.names, qs.order, db.names, res["picks"], m_rows))
     return res
 
 

@@ -1052,6 +1052,61 @@ typedef struct {
 } selhip_nj_join_t;          /* 24 bytes                                                             */
 int selhip_ctx_neighbor_joining(selhip_ctx* ctx, int measure, selhip_nj_join_t* d_joins /* [max(n-1,0)] or NULL */, int64_t* n_joins_out);
 
+/* ---------------------------------------------------------------------------------------------------
+ * 2m. Winner-takes-all screen: every query decomposed greedily into database genomes (`mash screen -w`, `sourmash gather`), on the
+ *     device.  The matrices of 2f and the smh_c passes score every database genome on its own, so fifty strains of one species each
+ *     explain the same buckets of a mixed query and all rank above the second organism present; here a genome is credited only
+ *     with the buckets no earlier pick has explained.  Exact integer work on the SuperMinHash bucket rows of the attached queries
+ *     (2b) and of the database: no HLL register, no estimator, any p_hll, with or without bit planes.
+ *     THE DEFINITION -- the kernels (csrc/kernel_gather.cuh) and the tests' model follow it; every output is a pure function of the
+ *     two bucket sets, c_min and max_picks, bit for bit and run to run.
+ *     INPUTS.  A query bucket row Q[0..m) and the database rows D[d][0..m), u64 buckets as uploaded or attached; UINT64_MAX marks an
+ *     unfilled bucket.
+ *       valid = { j : Q[j] != UINT64_MAX }
+ *       M(d)  = { j in valid : Q[j] == D[d][j] }      compared on all 64 bits: a bucket that differs in one dword is unequal
+ *       L_0   = valid
+ *     ROUND t = 1, 2, ...:
+ *       1. c_t(d) = |M(d) n L_{t-1}| for every database rank d;
+ *       2. d_t = the d with the greatest c_t(d); ties go to the smaller database rank;
+ *       3. the query ends when c_t(d_t) < c_min, or when t - 1 == max_picks picks have already been made;
+ *       4. otherwise the pick {q, d = d_t, unique = c_t(d_t), matches = |M(d_t)|} is emitted and L_t = L_{t-1} \ M(d_t).
+ *     CONSEQUENCES.  c_min >= 1, so a picked genome's remaining count is 0 and it is never picked again: no `used` flag belongs to
+ *     the definition.  unexplained(q) = |L_final|.  An empty query (every bucket UINT64_MAX) has no pick and unexplained 0; an empty
+ *     database row matches nothing.  unique / m is the share of the query this genome alone accounts for given the earlier picks
+ *     (sourmash's f_unique_to_query); matches / m is its plain SuperMinHash share, the SELHIP_MEASURE_SMH_MATCHES cell of 2f (which
+ *     also counts the buckets unfilled on BOTH sides: the two agree wherever the query row is filled).
+ *     OUTPUTS, the caller's device memory, each may be NULL: d_picks[q * max_picks + t] = pick t + 1 of query q, selhip_gather_pick_t
+ *     (four int32, 16 bytes; 16-byte aligned), the records behind a query's last pick are not written; d_n_picks[q] and
+ *     d_unexplained[q], int32.
+ *     REFUSALS.  SELHIP_E_BADARG: c_min outside 1 .. m, max_picks outside 1 .. SELHIP_GATHER_MAX_PICKS, m outside 1 .. 4 096, a
+ *     misaligned pointer.  SELHIP_E_STATE: no queries attached, no database, or a pass pending.  SELHIP_E_NOMEM: no room for the
+ *     scratch (the candidate entries: 8 + 4 ceil(m / 32) bytes for every (query, database row) pair with |M(d)| >= c_min, released
+ *     before the call returns).  No query or no database row: SELHIP_OK, zero picks per query.
+ *     Like the matrix calls, the call leaves the result list, statistics, top-k settings and signature cache untouched.  Timed as
+ *     "gather_mask" and "gather_pick", per call.
+ *     STREAM.  Every launch and copy runs on the context's stream, in stream order.  The host waits once between the count and the
+ *     fill launch of the mask stage (it sizes the candidate scratch from the total) and once behind the pick launch: never between
+ *     rounds.
+ *     HOW.  Mask stage: the rows are streamed twice -- a count launch, two scan launches, a fill launch --, so every query's segment
+ *     of candidate entries {rank, |M(d)|, the m bits of M(d)} is sized exactly and nothing is appended through an atomic.  For
+ *     m = 128, 256, 512, 1 024 (16-byte aligned rows) it is the enumeration of the fast SuperMinHash matrix kernel with the
+ *     v_cmp_eq_u64 ballots kept: ANDed with the query's valid ballots they ARE the mask, stored with vector stores; the lane map of
+ *     the coalesced loads permutes the bits, the same way for every candidate of a query.  Every other m: one lane per pair, masks
+ *     in natural bucket order.  Pick stage: one workgroup per query, every round in ONE launch; a segment that fits the workgroup's
+ *     LDS (what the device reports; get_param "gather_lds_cap", bytes -- set_param lowers it, a test hook, 0 = as reported) is staged
+ *     once word-major, a longer one is read from global memory every round; popcount(mask & live) per candidate with live in scalar
+ *     registers for m <= 1 024, a (count, smaller rank) butterfly in the wave, four waves through LDS, one barrier per round.
+ *     Not built: an all-pairs self mode, the HLL-based measures, more than one device, lazy re-evaluation of stale counts.
+ * --------------------------------------------------------------------------------------------------- */
+#define SELHIP_GATHER_MAX_PICKS 4096
+typedef struct {
+    int32_t q, d;            /* query rank, database rank                                            */
+    int32_t unique;          /* buckets of the query this pick explains that no earlier pick did     */
+    int32_t matches;         /* |M(d)|: every bucket the two share                                   */
+} selhip_gather_pick_t;      /* 16 bytes                                                             */
+int selhip_ctx_gather(selhip_ctx* ctx, int c_min, int max_picks, selhip_gather_pick_t* d_picks /* [n_q * max_picks] */,
+                      int32_t* d_n_picks /* [n_q] */, int32_t* d_unexplained /* [n_q] */);
+
 
 /* ---------------------------------------------------------------------------------------------------
  * 3. Building blocks (device pointers), used by the launchers above and exposed for tests.
@@ -1130,6 +1185,15 @@ int selhip_linkage(double* d_dist, int64_t n, int64_t ld, int method, double max
  * before the first join (the refusal tally) and once behind the last, and the call returns when the records are complete. */
 int selhip_neighbor_joining(double* d_dist, int64_t n, int64_t ld, selhip_nj_join_t* d_joins /* [max(n-1,0)] */, int64_t* n_joins_out,
                             void* hip_stream);
+/* The screen of section 2m over caller-owned bucket rows: d_q_aux[n_q][m] and d_db_aux[n_d][m], u64, device memory, 8-byte aligned
+ * (16-byte aligned rows with m = 128, 256, 512 or 1 024 take the fast mask kernel, anything else the generic one: the same outputs).
+ * d_picks (n_q * max_picks records, 16-byte aligned), d_n_picks and d_unexplained ([n_q] int32) are section 2m's; each may be NULL.
+ * SELHIP_E_BADARG: m outside 1 .. 4 096, c_min outside 1 .. m, max_picks outside 1 .. SELHIP_GATHER_MAX_PICKS, n_q or n_d negative or
+ * above 2^31 - 1, a NULL row array where there is a row to read, a misaligned pointer.  SELHIP_E_NOMEM: no room for the scratch.
+ * n_q == 0 writes nothing; n_d == 0 writes zero picks and unexplained = the filled buckets per query.  The call owns its scratch;
+ * every launch and copy runs on hip_stream, in stream order; the host waits once inside the mask stage and once behind the picks. */
+int selhip_gather(const uint64_t* d_q_aux, int64_t n_q, const uint64_t* d_db_aux, int64_t n_d, int m, int c_min, int max_picks,
+                  selhip_gather_pick_t* d_picks, int32_t* d_n_picks, int32_t* d_unexplained, void* hip_stream);
 /* Sketches merged by group (section 2i; csrc/kernel_merge.cuh) over a caller's rows: d_hll[n][1 << p] u8, d_smh[n][m] u64 and
  * d_aux_hll[n][1 << p_aux] u8 reduced to n_groups rows each -- maximum, unsigned minimum, maximum -- by d_group[n] (int32, -1 .. n_groups - 1,
  * -1 = in no group; ids in any order); d_size_out[n_groups] (int32, may be NULL) receives the members per group.  A sketch kind is
