@@ -216,6 +216,12 @@ int selhip_ctx_set_param(selhip_ctx* c, const char* name, int value) {
         if (value != 1 && value != 3) { set_err(&c->err, "matrix_smh_form: 1 (every pair once, mirrored) or 3 (the whole square)"); return SELHIP_E_BADARG; }
         c->matrix_smh_form = (int)value; return SELHIP_OK;
     }
+    // (a test and measurement hook like "vertex_blocks", but per context: 1 = a matrix of the SuperMinHash measures takes the generic
+    //  kernel whatever m is, 0 = the kernel of matrix_smh_kind; read at the launch; the same matrix either way)
+    if (!std::strcmp(name, "matrix_smh_generic")) {
+        if (value != 0 && value != 1) { set_err(&c->err, "matrix_smh_generic must be 0 (the kernel that fits m) or 1 (the generic kernel)"); return SELHIP_E_BADARG; }
+        c->matrix_smh_generic = (int)value; return SELHIP_OK;
+    }
     if (!std::strcmp(name, "hist_dense_degree")) {
         if (value < -1 || value > (1 << 20)) { set_err(&c->err, "hist_dense_degree must be in [-1, 2^20] (-1 = never)"); return SELHIP_E_BADARG; }
         c->hist_dense_degree = value;
@@ -273,7 +279,9 @@ int selhip_ctx_get_param(const selhip_ctx* c, const char* name, int* value) {
     if (!std::strcmp(name, "smhc_rule_used"))   { *value = c->smhc_rule_used; return SELHIP_OK; }           // its threshold rule: 0 fixed c_min, 1 containment, -1 none yet
     if (!std::strcmp(name, "matrix_mirror"))    { *value = c->matrix_mirror; return SELHIP_OK; }
     if (!std::strcmp(name, "matrix_smh_form"))  { *value = c->matrix_smh_form; return SELHIP_OK; }
-    if (!std::strcmp(name, "matrix_smh_path_used")) { *value = c->matrix_smh_path_used; return SELHIP_OK; }   // kernel of the last SuperMinHash matrix: 1 fast, 0 generic
+    if (!std::strcmp(name, "matrix_smh_path_used")) { *value = c->matrix_smh_path_used; return SELHIP_OK; }   // kernel of the last SuperMinHash matrix: 1 the whole-row register tile, 0 any other
+    if (!std::strcmp(name, "matrix_smh_kernel_used")) { *value = c->matrix_smh_kernel_used; return SELHIP_OK; } // ... which: 0 generic, 1 tile, 2 narrow, 3 wide, -1 none yet
+    if (!std::strcmp(name, "matrix_smh_generic"))   { *value = c->matrix_smh_generic; return SELHIP_OK; }
     if (!std::strcmp(name, "clusters_last"))    { *value = c->clusters_last; return SELHIP_OK; }            // clusters of the last selhip_ctx_cluster call, -1 = none yet
     if (!std::strcmp(name, "cluster_blocks"))   { *value = g_cluster_blocks.load(std::memory_order_relaxed); return SELHIP_OK; }
     if (!std::strcmp(name, "vertex_blocks"))    { *value = g_vertex_blocks.load(std::memory_order_relaxed); return SELHIP_OK; }

@@ -39,22 +39,37 @@ hipError_t launch_matrix(bool fma, int dtype, hipStream_t st, int khi, const Mat
     return hipGetLastError();
 }
 
-// the SuperMinHash measures: the fast kernel where matrix_smh_fast(m), else the generic one; *fast_out = which.  (The fast kernel's
-// 16-byte loads need 16-byte aligned rows: selhip_ctx_attach / _attach_queries refuse other pointers, uploads allocate their own.)  The grid is the unit count (one block per unit, capped as above).
-hipError_t launch_matrix_smh(int dtype, hipStream_t st, const u64* X, const u64* Y, int m, int r0, int r1, int n_y, const MatrixOut& o, int* fast_out) {
-    const bool fast = matrix_smh_fast(m);
-    *fast_out = fast ? 1 : 0;
-    const MatrixUnits mu = matrix_units((long long)r1 - r0, n_y, fast ? matrix_smh_tile_rows(m) : kWavesPerBlock);
+// the SuperMinHash measures: the kernel of matrix_smh_kind(m) -- the register tile, the narrow or the wide kernel, else the generic one,
+// which also takes every m under `force_generic` ("matrix_smh_generic") and any base pointer that is not 16-byte aligned: the other
+// three load 16 bytes per lane (selhip_ctx_attach / _attach_queries refuse such pointers, uploads allocate their own, so that is a
+// guard, not a route).  *kind_out = which.  A unit is matrix_smh_unit_rows(m) rows x a span; the grid is the unit count (one block
+// per unit, capped as above).
+hipError_t launch_matrix_smh(int dtype, hipStream_t st, const u64* X, const u64* Y, int m, int r0, int r1, int n_y, const MatrixOut& o, bool force_generic, int* kind_out) {
+    const bool aligned = !((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y)) & 15);
+    const int kind = force_generic || !aligned ? kMatrixSmhGeneric : matrix_smh_kind(m);
+    *kind_out = kind;
+    const MatrixUnits mu = matrix_units((long long)r1 - r0, n_y, kind == kMatrixSmhGeneric ? kWavesPerBlock : matrix_smh_unit_rows(m));
     if (mu.n_units <= 0) return hipSuccess;
     if (mu.n_tiles > 0x7FFFFFFFll) return hipErrorInvalidValue;
     const unsigned grid = (unsigned)std::min<long long>(mu.n_units, 0x7FFFFFF8ll);
+    const u64x2* const X2 = reinterpret_cast<const u64x2*>(X);
+    const u64x2* const Y2 = reinterpret_cast<const u64x2*>(Y);
     with_flag(dtype == SELHIP_F32, [&](auto F32) {
         using OutT = std::conditional_t<decltype(F32)::value, float, double>;
-        if (!fast) {
+        if (kind == kMatrixSmhGeneric) {
             hipLaunchKernelGGL((matrix_smh_generic_kernel<OutT>), dim3(grid), dim3(kBlock), 0, st, X, Y, m, r0, r1, n_y, (int)mu.n_tiles, mu.n_units, o);
             return;
         }
-#define SELHIP_MATRIX_SMH_LAUNCH(NCH) hipLaunchKernelGGL((matrix_smh_kernel<NCH, OutT>), dim3(grid), dim3(kBlock), 0, st, (const u64x2*)X, (const u64x2*)Y, \
+        if (kind == kMatrixSmhWide) {
+            hipLaunchKernelGGL((matrix_smh_wide_kernel<OutT>), dim3(grid), dim3(kBlock), 0, st, X2, Y2, m / (128 * kMatrixSmhWideNch), r0, r1, n_y, (int)mu.n_tiles, mu.n_units, o);
+            return;
+        }
+        if (kind == kMatrixSmhNarrow) {
+            if (m == 64) hipLaunchKernelGGL((matrix_smh_narrow_kernel<2, OutT>), dim3(grid), dim3(kBlock), 0, st, X2, Y2, r0, r1, n_y, (int)mu.n_tiles, mu.n_units, o);
+            else         hipLaunchKernelGGL((matrix_smh_narrow_kernel<4, OutT>), dim3(grid), dim3(kBlock), 0, st, X2, Y2, r0, r1, n_y, (int)mu.n_tiles, mu.n_units, o);
+            return;
+        }
+#define SELHIP_MATRIX_SMH_LAUNCH(NCH) hipLaunchKernelGGL((matrix_smh_kernel<NCH, OutT>), dim3(grid), dim3(kBlock), 0, st, X2, Y2, \
                                                          r0, r1, n_y, (int)mu.n_tiles, mu.n_units, o)
         switch (m / 128) {
             case 1:  SELHIP_MATRIX_SMH_LAUNCH(1); break;
@@ -127,7 +142,9 @@ int matrix_call(selhip_ctx* c, bool query, int measure, int dtype, int64_t r0, i
             const int tm = as_timer >= 0 ? as_timer : T_MATRIX_SMH;
             TimedCall call(c, tm);
             TimerScope t(c, tm);
-            e = launch_matrix_smh(dtype, c->stream, query ? c->q.d_aux : c->d_aux, c->d_aux, c->m, (int)r0, (int)r1, (int)n_y, o, &c->matrix_smh_path_used);
+            e = launch_matrix_smh(dtype, c->stream, query ? c->q.d_aux : c->d_aux, c->d_aux, c->m, (int)r0, (int)r1, (int)n_y, o, c->matrix_smh_generic != 0,
+                                  &c->matrix_smh_kernel_used);
+            c->matrix_smh_path_used = c->matrix_smh_kernel_used == kMatrixSmhTile ? 1 : 0;
         }
         HIPCHK(&c->err, e);
         HIPCHK(&c->err, hipStreamSynchronize(c->stream));

@@ -369,9 +369,13 @@ struct selhip_ctx {
     int matrix_mirror = 1;              // test switch ("matrix_mirror"): 0 = a self matrix stores no mirrored cells (upper triangle of a slab only)
     // the SuperMinHash measures (kernel_matrix_smh.cuh): "matrix_smh_form" 1 = a self matrix computes every pair once and mirrors it,
     // 3 = it computes the whole square (a measurement switch; "matrix_mirror" = 0 takes the once-per-pair form whatever this says);
-    // matrix_smh_path_used = the kernel of the last such call: 1 the fast path (matrix_smh_fast), 0 the generic one, -1 none yet
+    // matrix_smh_path_used = the kernel of the last such call: 1 the whole-row register tile (matrix_smh_fast), 0 any other, -1 none yet;
+    // matrix_smh_kernel_used = which exactly (matrix_smh_kind: 0 generic, 1 tile, 2 narrow, 3 wide; -1 none yet);
+    // "matrix_smh_generic" 1 = every m takes the generic kernel (a test and measurement hook, read at the launch)
     int matrix_smh_form = 1;
     int matrix_smh_path_used = -1;
+    int matrix_smh_kernel_used = -1;
+    int matrix_smh_generic = 0;
 
     GraphScratch gs;                    // the graph calls over the result list (host_graph.hpp): their scratch; below, what the last call of each kind reports
     int clusters_last = -1;             // selhip_ctx_cluster: the C of the last call ("clusters_last"), -1 = none yet

@@ -36,8 +36,8 @@
 //                       histograms into an LDS tile and the estimator in one launch
 //   kernel_matrix.cuh   matrix_kernel: the union size, the Jaccard estimate, the intersection estimate or a containment of every pair as a dense array (the middle of
 //                       dense_select_kernel over a rectangle, typed and mirrored stores; selhip_ctx_matrix / _query_matrix)
-//   kernel_matrix_smh.cuh  matrix_smh_kernel / matrix_smh_generic_kernel: the SuperMinHash bucket-match count, or count / m, of every
-//                       pair as a dense array (query rows in VGPRs, candidate rows streamed past them; the same entry points)
+//   kernel_matrix_smh.cuh  matrix_smh_kernel / _narrow_kernel / _wide_kernel / _generic_kernel: the SuperMinHash bucket-match count, or
+//                       count / m, of every pair as a dense array (query rows in VGPRs, candidate rows streamed past them; the same entry points)
 //   kernel_topk.cuh     top-k of a pass: records grouped by owner (count, scan, scatter) -- a query pass's by query, an all-pairs
 //                       pass's for both of their genomes --, radix select of each owner's K best, bitonic sort of the winners
 //   kernel_query_aux.cuh the auxiliary-HLL criteria of query passes: hll_a / hll_an over each query's CB window, the hll_a stage

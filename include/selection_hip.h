@@ -259,8 +259,12 @@ int selhip_ctx_set_param(selhip_ctx* ctx, const char* name, int value);
  * smh_c count takes per batch, 1 .. 16 by the list's length -- 0 for the kernels of one lane per entry, the signature route and the
  * criteria without an smh_a stage -- and the kernel's blocks, of the first window where the list goes in windows; both 0 after an
  * empty list, -1 = no list pass yet),
- * "matrix_smh_path_used" (the kernel of the last matrix call with a SuperMinHash measure, section 2f: 1 = the register-tile kernel
- * of m = 128, 256, 512 or 1024 buckets, 0 = the generic kernel of every other m; -1 = none yet),
+ * "matrix_smh_path_used" (the kernel of the last matrix call with a SuperMinHash measure, section 2f: 1 = the whole-row register tile,
+ * 0 = any other kernel; -1 = none yet),
+ * "matrix_smh_kernel_used" (which kernel that was: 0 = generic, 1 = the whole-row register tile of m = 128, 256, 512 or 1024 buckets,
+ * 2 = the narrow kernel of m = 32 or 64, 3 = the wide kernel of every multiple of 1024 from 2048 to 8192; -1 = none yet.
+ * selhip_ctx_set_param "matrix_smh_generic" 1, a test and measurement hook read at each launch, gives every m the generic kernel:
+ * the same matrix, byte for byte; 0 is the default),
  * "clusters_last" (the number of clusters the last selhip_ctx_cluster call found, section 2g; -1 = none yet),
  * "greedy_clusters_last" and "greedy_rounds_last" (the clusters the last selhip_ctx_cluster_greedy call found and the rounds its
  * selection took, section 2h; -1 = none yet),

@@ -19,7 +19,14 @@ Afterwards the kernels alone under selhip_ctx_timing(2) (mean of 10): "matrix_sm
 ALGO_STREAM stage-1 launch over the same pairs ("stage1": the same loads and compares per pair, a band fold in place of the count).
 The condition recorded: smh_f64 (device) <= pairlist_scatter.  The two routes' arrays are compared once.
 
+`--shapes` measures the narrow (m = 32, 64) and the wide (m = 2048, 4096) kernel instead: random rows, a
+10 000 x 10 000 self matrix and a 1 000 x 50 000 query matrix, f64 counts; per m and workload, after 3 warm calls, `--reps` alternating
+rounds of the kernel of m, the generic kernel on the same rows ("matrix_smh_generic" = 1: the route those m took before) and the tile
+kernel at the neighbouring m (128 or 1024) in a second context.  Recorded: the arrays of the first two are identical; the aim
+time(m) <= time(tile) * m / m_tile + the tile run's spread (max - min), met or missed; generic / new.
+
 usage: bench_matrix_smh.py [--out profiles/matrix_smh_bench.json] [--only M1,M2,M3] [--reps 20]
+       bench_matrix_smh.py --shapes all|32,64,2048,4096 [--out profiles/matrix_smh_shapes_bench.json] [--reps 20]
 """
 import argparse
 import json
@@ -172,12 +179,84 @@ def bench(name, reps):
     return out
 
 
+SHAPES = {32: 128, 64: 128, 2048: 1024, 4096: 1024}         # m of the narrow / wide kernel: the tile kernel's neighbouring m
+SHAPE_LOADS = {"self": (10_000, 0), "query": (50_000, 1_000)}
+
+
+def shape_rows(n, m, seed):
+    """n rows of m random buckets on the device, each sharing a random share of them with one base row (counts spread over 0 .. m)"""
+    import torch
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    rnd = torch.randint(0, 1 << 62, (n + 1, m), dtype=torch.int64, device="cuda", generator=g)
+    keep = torch.rand((n, m), device="cuda", generator=g) < torch.rand((n, 1), device="cuda", generator=g)
+    return torch.where(keep, rnd[n:], rnd[:n]).contiguous()
+
+
+def bench_shapes(m, reps):
+    """the kernel of m, the generic kernel on the same rows ("matrix_smh_generic": the route before the narrow and wide kernels) and
+    the tile kernel at the neighbouring m, per workload in alternating rounds after 3 warm calls; f64 counts, device ms"""
+    import torch
+    m_tile = SHAPES[m]
+    out = {"m": m, "tile_m": m_tile, "workloads": {}}
+    for wname, (n_d, n_q) in SHAPE_LOADS.items():
+        with pkg.Selector(0) as sel, pkg.Selector(0) as tile:
+            # (these measures never read the HLL rows: both contexts attach the same empty ones; the arrays live until the contexts close)
+            hll, cards = torch.zeros((n_d + n_q, 16384), dtype=torch.uint8, device="cuda"), torch.zeros(n_d + n_q, dtype=torch.float64, device="cuda")
+            rows = {mm: shape_rows(n_d + n_q, mm, 1000 + mm) for mm in (m, m_tile)}
+            for s, mm in ((sel, m), (tile, m_tile)):
+                s.attach(hll[:n_d], rows[mm][:n_d], cards[:n_d])
+                if n_q:
+                    s.attach_queries(hll[n_d:], rows[mm][n_d:], cards[n_d:])
+            shape = (n_q or n_d, n_d)
+            buf, ref = torch.empty(shape, dtype=torch.float64, device="cuda"), torch.empty(shape, dtype=torch.float64, device="cuda")
+
+            def run(s, generic, dst):
+                s.set_param("matrix_smh_generic", generic)
+                (s.query_matrix if n_q else s.matrix)("smh_matches", out=dst)
+                s.set_param("matrix_smh_generic", 0)
+                return s.get_param("matrix_smh_kernel_used")
+
+            variants = [("new", lambda: run(sel, 0, buf)), ("generic", lambda: run(sel, 1, ref)), ("tile", lambda: run(tile, 0, buf))]
+            kernels = {}
+            for vname, call in variants:
+                for _ in range(3):
+                    kernels[vname] = call()
+            run(sel, 0, buf)
+            identical = bool(torch.equal(buf, ref))
+            samples = {v[0]: [] for v in variants}
+            order_rng = np.random.default_rng(m)
+            for r in range(reps):
+                for vname, call in [variants[j] for j in order_rng.permutation(len(variants))]:
+                    samples[vname].append(timed(call))
+                print(f"  [m={m} {wname}] round {r + 1} of {reps}", file=sys.stderr, flush=True)
+            res = {v: summary(s) for v, s in samples.items()}
+            t = res["tile"]["device_ms"]
+            aim = t["median"] * m / m_tile + (t["max"] - t["min"])
+            new = res["new"]["device_ms"]["median"]
+            out["workloads"][wname] = {"cells": shape[0] * shape[1], "kernel_used": kernels, "identical_to_generic": identical, "variants": res,
+                                       "aim_ms": round(aim, 3), "aim_met": bool(new <= aim), "generic_over_new": round(res["generic"]["device_ms"]["median"] / new, 2),
+                                       "beats_generic": bool(new < res["generic"]["device_ms"]["median"])}
+        torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--out", default="profiles/matrix_smh_bench.json")
+    ap.add_argument("--out", default=None, help="default profiles/matrix_smh_bench.json, with --shapes profiles/matrix_smh_shapes_bench.json")
     ap.add_argument("--only", default="M1,M2,M3")
+    ap.add_argument("--shapes", default=None, help="the narrow / wide kernels instead of the workloads: a list of m out of 32,64,2048,4096, or 'all'")
     ap.add_argument("--reps", type=int, default=20)
     args = ap.parse_args()
+    if args.shapes:
+        path = Path(args.out or "profiles/matrix_smh_shapes_bench.json")
+        results = []
+        for m in (sorted(SHAPES) if args.shapes == "all" else [int(x) for x in args.shapes.split(",")]):
+            results.append(bench_shapes(m, args.reps))
+            print(json.dumps(results[-1]), flush=True)
+            path.parent.mkdir(parents=True, exist_ok=True)
+            path.write_text(json.dumps({"device": "MI355X", "protocol": f"3 warm calls, {args.reps} alternating rounds, device events", "shapes": results}, indent=1) + "\n")
+        return 0
+    args.out = args.out or "profiles/matrix_smh_bench.json"
     results = []
     for name in args.only.split(","):
         r = bench(name, args.reps)
