@@ -222,6 +222,12 @@ int selhip_ctx_set_param(selhip_ctx* c, const char* name, int value) {
         if (value != 0 && value != 1) { set_err(&c->err, "matrix_smh_generic must be 0 (the kernel that fits m) or 1 (the generic kernel)"); return SELHIP_E_BADARG; }
         c->matrix_smh_generic = (int)value; return SELHIP_OK;
     }
+    // (its twin for the count passes of criterion smh_c: 1 = stage 1 takes the generic kernel whatever m is, 0 = the kernel of smhc_kind;
+    //  read at the launch; the same survivors and records either way)
+    if (!std::strcmp(name, "smhc_generic")) {
+        if (value != 0 && value != 1) { set_err(&c->err, "smhc_generic must be 0 (the kernel that fits m) or 1 (the generic kernel)"); return SELHIP_E_BADARG; }
+        c->smhc_generic = (int)value; return SELHIP_OK;
+    }
     if (!std::strcmp(name, "hist_dense_degree")) {
         if (value < -1 || value > (1 << 20)) { set_err(&c->err, "hist_dense_degree must be in [-1, 2^20] (-1 = never)"); return SELHIP_E_BADARG; }
         c->hist_dense_degree = value;
@@ -275,7 +281,9 @@ int selhip_ctx_get_param(const selhip_ctx* c, const char* name, int* value) {
     if (!std::strcmp(name, "join_form_used"))   { *value = c->join_form_used; return SELHIP_OK; }      // kernel FORM of the last LDS-tile join (3 = bit-sliced)
     if (!std::strcmp(name, "chunks"))           { *value = c->n_chunks_last; return SELHIP_OK; }
     if (!std::strcmp(name, "dense_route_used")) { *value = c->dense_route_used; return SELHIP_OK; }         // SELHIP_CRIT_NONE: 1 fused kernel, 0 list route, -1 none yet
-    if (!std::strcmp(name, "smhc_path_used"))   { *value = c->smhc_path_used; return SELHIP_OK; }           // SELHIP_CRIT_SMH_C: 1 fast kernel, 0 generic, -1 none yet
+    if (!std::strcmp(name, "smhc_path_used"))   { *value = c->smhc_path_used; return SELHIP_OK; }           // SELHIP_CRIT_SMH_C: 1 fast (tile) kernel, 0 any other, -1 none yet
+    if (!std::strcmp(name, "smhc_kernel_used")) { *value = c->smhc_kernel_used; return SELHIP_OK; }         // ... which: 0 generic, 1 tile, 2 narrow, 3 wide, -1 none yet
+    if (!std::strcmp(name, "smhc_generic"))     { *value = c->smhc_generic; return SELHIP_OK; }
     if (!std::strcmp(name, "smhc_rule_used"))   { *value = c->smhc_rule_used; return SELHIP_OK; }           // its threshold rule: 0 fixed c_min, 1 containment, -1 none yet
     if (!std::strcmp(name, "matrix_mirror"))    { *value = c->matrix_mirror; return SELHIP_OK; }
     if (!std::strcmp(name, "matrix_smh_form"))  { *value = c->matrix_smh_form; return SELHIP_OK; }

@@ -272,9 +272,13 @@ struct selhip_ctx {
     int dense_fused = 1;
     int dense_route_used = -1;
     // SELHIP_CRIT_SMH_C (kernel_smhc.cuh): the count threshold (selhip_ctx_set_min_matches; 0 = never set) and the stage-1 kernel of the
-    // last such pass (1 the fast path, 0 the generic one, -1 none yet)
+    // last such pass (1 the fast path -- the tile kernel --, 0 any other kernel, -1 none yet)
     int min_matches = 0;
     int smhc_path_used = -1;
+    // smhc_kernel_used = which exactly (smhc_kind: 0 generic, 1 tile, 2 narrow, 3 wide; -1 none yet); "smhc_generic" 1 = every m takes the
+    // generic kernel (a test and measurement hook, read at the launch)
+    int smhc_kernel_used = -1;
+    int smhc_generic = 0;
     // its per-pair rule (selhip_ctx_set_min_containment; NaN = never set or cleared: the fixed rule) and the rule of the last such pass
     // (0 fixed, 1 containment, -1 none yet)
     double min_containment = std::numeric_limits<double>::quiet_NaN();

@@ -124,7 +124,6 @@ hipError_t launch_count(selhip_ctx* c, hipStream_t st, const CountSets& a, const
     const bool emit = pc0 != nullptr;
     selhip_pair_t* const res = c->results.p;
     const u64 res_cap = (u64)c->results.cap;
-    c->smhc_path_used = smhc_fast(m) ? 1 : 0;
     const bool cont = smhc_containment(c);
     c->smhc_rule_used = cont ? 1 : 0;
     const SmhcRule rule{c->min_containment, a.ex, a.ey};
@@ -132,7 +131,44 @@ hipError_t launch_count(selhip_ctx* c, hipStream_t st, const CountSets& a, const
     // a round of a top-k pass in row rounds: the TOPK form, whose operand rides behind the emit form's
     const bool topk = !QUERY && emit && c->rd.on;
     const SmhcRuleEmitTopk rule_tk{rule_em, c->topk_thr.p};
-    if (smhc_fast(m)) {
+    // the kernel of smhc_kind(m); the generic one instead under "smhc_generic", and -- for the narrow and the wide kernel, which have
+    // no round form and load 16 bytes per lane -- in a round of a top-k pass and for a base pointer off the 16-byte grid (attach refuses
+    // such pointers and uploads allocate their own: a guard, not a route)
+    const bool aligned = !((reinterpret_cast<uintptr_t>(a.X) | reinterpret_cast<uintptr_t>(a.Y)) & 15);
+    int kind = c->smhc_generic ? kSmhcGeneric : smhc_kind(m);
+    if ((kind == kSmhcNarrow || kind == kSmhcWide) && (topk || !aligned)) kind = kSmhcGeneric;
+    c->smhc_kernel_used = kind;
+    c->smhc_path_used = kind == kSmhcTile ? 1 : 0;
+    if (kind == kSmhcNarrow || kind == kSmhcWide) {
+        const long long n_tiles = rm.n_tiles(kind == kSmhcNarrow ? smhc_narrow_q(emit, cont) : kWavesPerBlock * kSmhcWideQ);
+        if (n_tiles > 0x7FFFFFFFll) return hipErrorInvalidValue;
+        const int chunk_base = (first_cand / kChunk) * kChunk;
+        const int n_chunks = (a.n_y - chunk_base + kChunk - 1) / kChunk;
+        if (n_tiles <= 0 || n_chunks <= 0) return hipSuccess;
+        const long long blocks = n_tiles * n_chunks;
+        if (blocks > 0x7FFFFFFFll) return hipErrorInvalidValue;
+        const u64x2* const X2 = reinterpret_cast<const u64x2*>(a.X);
+        const u64x2* const Y2 = reinterpret_cast<const u64x2*>(a.Y);
+        with_flag(cont, [&](auto C) { with_flag(emit, [&](auto E) {
+            constexpr int RULE = decltype(C)::value ? kSmhcContainment : kSmhcFixed;
+            constexpr bool EMIT = decltype(E)::value;
+            SmhcRecord<EMIT>* out;
+            SmhcRuleArg<EMIT> arg;
+            u64 out_cap;
+            if constexpr (EMIT) { out = res; out_cap = res_cap; arg = rule_em; } else { out = surv; out_cap = cap; arg = rule; }
+            if (kind == kSmhcWide)
+                hipLaunchKernelGGL((smh_count_wide_kernel<QUERY, RULE, EMIT>), dim3((unsigned)blocks), dim3(kBlock), 0, st, X2, Y2, a.n_x, a.n_y,
+                                   m / (2 * kWave * kSmhcWideNch), a.lo, a.hi, a.pc_in, rm, (int)n_tiles, chunk_base, c_min, out, out_cap, pc, arg);
+            else if (m == 64)
+                hipLaunchKernelGGL((smh_count_narrow_kernel<2, QUERY, RULE, EMIT>), dim3((unsigned)blocks), dim3(kBlock), 0, st, X2, Y2, a.n_x, a.n_y,
+                                   a.lo, a.hi, a.pc_in, rm, (int)n_tiles, chunk_base, c_min, out, out_cap, pc, arg);
+            else
+                hipLaunchKernelGGL((smh_count_narrow_kernel<4, QUERY, RULE, EMIT>), dim3((unsigned)blocks), dim3(kBlock), 0, st, X2, Y2, a.n_x, a.n_y,
+                                   a.lo, a.hi, a.pc_in, rm, (int)n_tiles, chunk_base, c_min, out, out_cap, pc, arg);
+        }); });
+        return hipGetLastError();
+    }
+    if (kind == kSmhcTile) {
         const int nch = m / 128;
         const long long n_tiles = rm.n_tiles(smhc_q(nch, smhc_tight(emit, cont, topk)));
         if (n_tiles > 0x7FFFFFFFll) return hipErrorInvalidValue;

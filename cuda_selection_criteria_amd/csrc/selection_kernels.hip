@@ -18,7 +18,9 @@
 //                                             v_cmp_eq_u64 lane masks folded on the scalar unit; smh_generic_kernel
 //   kernel_smhc.cuh     smh_count_kernel      stage 1 of criterion smh_c: at least c_min equal buckets -- the stream kernel's enumeration with a
 //                                             count (v_cmp_eq_u64, s_bcnt1, scalar adds, one compare) in place of the band fold, over the
-//                                             triangle or a query rectangle; smh_count_generic_kernel for every other m
+//                                             triangle or a query rectangle; smh_count_narrow_kernel (m = 32, 64: G candidate rows per wave
+//                                             load) and smh_count_wide_kernel (m = 2048 .. 8192: 1 024-bucket chunks, running totals per
+//                                             lane) on the same blocks; smh_count_generic_kernel for every other m
 //   kernel_sigjoin.cuh  sig_build / sig_join   stage 1 ALGO_SIG: all-pairs band-signature join (DPP broadcast), hash join
 //   kernel_hll.cuh      hll_union_hist_kernel, ertl_select_kernel (stage 2), enum_pairs / aux_fused (hll_a, hll_an)
 //   kernel_hllbs.cuh    hll_bitslice_kernel, hll_union_hist_bs_kernel: stage 2a on bit-sliced registers (bit-serial max, decode tree, v_bcnt)

@@ -265,6 +265,8 @@ int selhip_ctx_set_param(selhip_ctx* ctx, const char* name, int value);
  * 2 = the narrow kernel of m = 32 or 64, 3 = the wide kernel of every multiple of 1024 from 2048 to 8192; -1 = none yet.
  * selhip_ctx_set_param "matrix_smh_generic" 1, a test and measurement hook read at each launch, gives every m the generic kernel:
  * the same matrix, byte for byte; 0 is the default),
+ * "smhc_path_used", "smhc_kernel_used" and "smhc_generic" (the stage-1 kernel of the last pass under SELHIP_CRIT_SMH_C and the hook
+ * that forces the generic one: selhip_ctx_set_min_matches),
  * "clusters_last" (the number of clusters the last selhip_ctx_cluster call found, section 2g; -1 = none yet),
  * "greedy_clusters_last" and "greedy_rounds_last" (the clusters the last selhip_ctx_cluster_greedy call found and the rounds its
  * selection took, section 2h; -1 = none yet),
@@ -337,7 +339,13 @@ int selhip_ctx_set_criterion(selhip_ctx* ctx, int criterion);
  * stats[1] = stats[3] = the pairs of the pair space with c >= c_min.  All-pairs passes (row ranges, row interleave, candidate begin,
  * pipeline, all-pairs top-k), query passes and pair-list passes take the criterion; selhip_multi_select and selhip_ooc_select, whose
  * signatures carry no c_min, refuse it.  get_param "smhc_path_used": the stage-1 kernel of the last such pass, 1 = the fast path
- * (m = 128, 256, 512, 1024), 0 = the generic one, -1 = none yet.  The stage is timed as "stage1". */
+ * (m = 128, 256, 512, 1024), 0 = any other kernel, -1 = none yet.  get_param "smhc_kernel_used": which kernel that was, 0 = generic,
+ * 1 = the whole-row register tile of m = 128, 256, 512 or 1024 buckets, 2 = the narrow kernel of m = 32 or 64, 3 = the wide kernel of
+ * every multiple of 1024 from 2048 to 8192; -1 = none yet.  The narrow and the wide kernel serve the all-pairs and the query passes
+ * under both rules and both estimators; a round of a top-k pass in row rounds, the pair-list passes and every other m keep the
+ * generic route.  selhip_ctx_set_param "smhc_generic" 1, a test and measurement hook read at each launch, gives every m the generic
+ * kernel: the same survivors and records; 0 is the default, any other value is refused (SELHIP_E_BADARG).  The stage is timed as
+ * "stage1". */
 int selhip_ctx_set_min_matches(selhip_ctx* ctx, int c_min);
 /* SELHIP_CRIT_SMH_C with a PER-PAIR count threshold, for a minimum containment gamma.  With c / m the
  * SuperMinHash estimate of J, I = J (a + b) / (1 + J) and the containment estimate of the smaller genome is

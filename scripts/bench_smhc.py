@@ -15,7 +15,16 @@ The condition recorded: smh_c's median <= none's median.  smh_c's and none_filte
 Afterwards the kernels alone under selhip_ctx_timing(2) (mean of 10): smh_c's "stage1", the match matrix's "matrix_smh" without mirrored
 stores ("matrix_mirror" = 0, self workloads) and, for the self workloads, one ALGO_STREAM stage 1 of smh_a over the same set.
 
-usage: bench_smhc.py [--out profiles/smhc_bench.json] [--only S1,S2,S3] [--reps 20]
+--shapes (a list of m out of 32,64,2048,4096, or 'all'): the narrow and the wide count kernel instead of the
+workloads.  Per m and load -- 10 000 genomes all pairs, 1 000 queries x 50 000 -- on random rows that share a random part of their buckets
+with one base row, under the estimator smh with c_min chosen so that about 0.1 % of the pairs survive: after 3 warm calls, `--reps`
+alternating rounds of
+  new            the pass on the kernel of m
+  generic        the same pass under "smhc_generic" = 1 (the route every such m took before), same context and rows
+  matrix         matrix("smh_matches", f32) of the same rows
+The aim recorded: new's median <= matrix's median + its spread (max - min).  The records of new and generic are compared once.
+
+usage: bench_smhc.py [--out profiles/smhc_bench.json] [--only S1,S2,S3] [--reps 20] [--shapes all]
 """
 import argparse
 import json
@@ -163,12 +172,94 @@ def bench(name, reps):
     return out
 
 
+SHAPES = (32, 64, 2048, 4096)
+SHAPE_LOADS = {"self": (10_000, 0), "query": (50_000, 1_000)}
+
+
+def shape_rows(n, m, seed):
+    """n rows of m random buckets on the device, each sharing a random share of them with one base row (counts spread over 0 .. m)"""
+    import torch
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    rnd = torch.randint(0, 1 << 62, (n + 1, m), dtype=torch.int64, device="cuda", generator=g)
+    keep = torch.rand((n, m), device="cuda", generator=g) < torch.rand((n, 1), device="cuda", generator=g)
+    return torch.where(keep, rnd[n:], rnd[:n]).contiguous()
+
+
+def bench_shapes(m, reps):
+    import torch
+    out = {"m": m, "workloads": {}}
+    for wname, (n_d, n_q) in SHAPE_LOADS.items():
+        with pkg.Selector(0) as sel:
+            # (the estimator smh never reads the HLL rows; ascending cardinalities, none of them 0: every pair is in the pair space)
+            hll = torch.zeros((max(n_d, n_q), 16384), dtype=torch.uint8, device="cuda")
+            cards = torch.arange(1000, 1000 + n_d, dtype=torch.float64, device="cuda")
+            rows = shape_rows(n_d + n_q, m, 1000 + m)
+            sel.attach(hll[:n_d], rows[:n_d], cards)
+            if n_q:
+                sel.attach_queries(hll[:n_q], rows[n_d:], cards[:n_q].contiguous())
+            cells = torch.empty((n_q or n_d, n_d), dtype=torch.float32, device="cuda")
+            matrix = lambda: (sel.query_matrix if n_q else sel.matrix)("smh_matches", dtype=torch.float32, out=cells)   # noqa: E731
+            matrix()
+            hist = torch.bincount(cells.flatten().long(), minlength=m + 1).cpu().numpy().astype(np.int64)
+            if not n_q:                                                                              # every pair twice, and the diagonal
+                hist[m] -= n_d
+                hist //= 2
+            pairs = int(hist.sum())
+            above = np.cumsum(hist[::-1])[::-1]                                                      # above[c] = pairs with count >= c
+            c_min = max(1, int(np.argmin(np.abs(above[1:] - pairs / 1000.0))) + 1)
+            sel.set_criterion(pkg.CRIT_SMH_C)
+            sel.set_estimator("smh")
+            sel.set_min_matches(c_min)
+
+            def count_pass(generic, fetch=False):
+                sel.set_param("smhc_generic", generic)
+                rec = (sel.run_queries if n_q else sel.run)(0.0, pkg.MODE_SMH, 1, 1, fetch=fetch)
+                sel.set_param("smhc_generic", 0)
+                return rec
+
+            variants = [("new", lambda: count_pass(0)), ("generic", lambda: count_pass(1)), ("matrix", matrix)]
+            kernels = {}
+            for vname, call in variants:
+                for _ in range(3):
+                    call()
+                kernels[vname] = sel.get_param("matrix_smh_kernel_used" if vname == "matrix" else "smhc_kernel_used")
+            direct, st = sorted_records(count_pass(0, fetch=True)), sel.stats()
+            via = sorted_records(count_pass(1, fetch=True))
+            assert st["survivors"] == int(above[c_min]) == sel.stats()["survivors"], (st, int(above[c_min]))
+            samples = {v[0]: [] for v in variants}
+            order_rng = np.random.default_rng(m)
+            for r in range(reps):
+                for vname, call in [variants[j] for j in order_rng.permutation(len(variants))]:
+                    samples[vname].append(timed(call))
+                print(f"  [m={m} {wname}] round {r + 1} of {reps}", file=sys.stderr, flush=True)
+            res = {v: summary(s) for v, s in samples.items()}
+            t, new = res["matrix"]["device_ms"], res["new"]["device_ms"]["median"]
+            aim = t["median"] + (t["max"] - t["min"])
+            out["workloads"][wname] = {"pairs": pairs, "c_min": c_min, "survivors": st["survivors"], "records": st["selected"], "kernel_used": kernels,
+                                       "identical_to_generic": bool(direct.tobytes() == via.tobytes()), "variants": res, "aim_ms": round(aim, 3),
+                                       "aim_met": bool(new <= aim), "generic_over_new": round(res["generic"]["device_ms"]["median"] / new, 2)}
+        del hll, cards, rows, cells
+        torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--out", default="profiles/smhc_bench.json")
+    ap.add_argument("--out", default=None, help="default profiles/smhc_bench.json, with --shapes profiles/smhc_shapes_bench.json")
+    ap.add_argument("--shapes", default=None, help="the narrow / wide count kernels instead of the workloads: a list of m out of 32,64,2048,4096, or 'all'")
     ap.add_argument("--only", default="S1,S2,S3")
     ap.add_argument("--reps", type=int, default=20)
     args = ap.parse_args()
+    if args.shapes:
+        path = Path(args.out or "profiles/smhc_shapes_bench.json")
+        results = []
+        for m in (SHAPES if args.shapes == "all" else [int(x) for x in args.shapes.split(",")]):
+            results.append(bench_shapes(m, args.reps))
+            print(json.dumps(results[-1]), flush=True)
+            path.parent.mkdir(parents=True, exist_ok=True)
+            path.write_text(json.dumps({"device": "MI355X", "protocol": f"3 warm calls, {args.reps} alternating rounds, device events", "shapes": results}, indent=1) + "\n")
+        return 0
+    args.out = args.out or "profiles/smhc_bench.json"
     results = []
     for name in args.only.split(","):
         r = bench(name, args.reps)
