@@ -266,6 +266,12 @@ int selhip_ctx_set_param(selhip_ctx* c, const char* name, int value) {
         c->gather_lds_cap = value;
         return SELHIP_OK;
     }
+    // (the twin of "matrix_smh_generic" and "smhc_generic" for the screen's mask stage: 1 = every m that is not a tile m takes the generic
+    //  mask kernel, 0 = the kernel of matrix_smh_kind; read at the call; the same picks either way)
+    if (!std::strcmp(name, "gather_generic")) {
+        if (value != 0 && value != 1) { set_err(&c->err, "gather_generic must be 0 (the kernel that fits m) or 1 (the generic kernel)"); return SELHIP_E_BADARG; }
+        c->gather_generic = (int)value; return SELHIP_OK;
+    }
     set_err(&c->err, "unknown parameter '%s'", name);
     return SELHIP_E_BADARG;
 }
@@ -312,6 +318,8 @@ int selhip_ctx_get_param(const selhip_ctx* c, const char* name, int* value) {
     if (!std::strcmp(name, "topk_admitted_lo")) { *value = (int)(c->rounds_admitted & 0x7FFFFFFFull); return SELHIP_OK; }            // records its rounds admitted: low ...
     if (!std::strcmp(name, "topk_admitted_hi")) { *value = (int)((c->rounds_admitted >> 31) & 0x7FFFFFFFull); return SELHIP_OK; }    // ... and high 31 bits
     if (!std::strcmp(name, "query_topk_lds_cap")) { *value = kTopkLdsCap; return SELHIP_OK; }              // longest segment its select kernel stages in LDS
+    if (!std::strcmp(name, "gather_mask_kernel_used")) { *value = c->gather_mask_kernel_used; return SELHIP_OK; } // mask kernel of the last screen: 0 generic, 1 tile, 2 narrow, 3 wide, -1 none yet
+    if (!std::strcmp(name, "gather_generic"))   { *value = c->gather_generic; return SELHIP_OK; }
     if (!std::strcmp(name, "gather_lds_cap")) {                                                         // bytes of LDS the screen's pick stage stages a segment in
         int cap = 0;
         if (hipSetDevice(c->device) != hipSuccess || gather_device_lds(&cap)) return SELHIP_E_HIP;

@@ -19,10 +19,10 @@ int selhip_gather(const uint64_t* d_q_aux, int64_t n_q, const uint64_t* d_db_aux
         return SELHIP_E_BADARG;
     }
     if (n_q == 0) return SELHIP_OK;
-    int cap = 0;
+    int cap = 0, kind = 0;
     if (gather_device_lds(&cap)) { set_err(nullptr, "%s: the device reports no LDS size", what); return SELHIP_E_HIP; }
     return gather_run(nullptr, nullptr, what, (hipStream_t)hip_stream, reinterpret_cast<const u64*>(d_q_aux), n_q, reinterpret_cast<const u64*>(d_db_aux), n_d, m,
-                      c_min, max_picks, cap, GatherOut{d_picks, d_n_picks, d_unexplained});
+                      c_min, max_picks, cap, GatherOut{d_picks, d_n_picks, d_unexplained}, false, &kind);
 }
 
 }  // extern "C"

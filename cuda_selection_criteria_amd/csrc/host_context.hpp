@@ -395,6 +395,10 @@ struct selhip_ctx {
     // the screen (selhip_ctx_gather; kernel_gather.cuh): "gather_lds_cap", bytes of LDS the pick stage may stage a segment in; 0 = what the
     // device reports for a workgroup (a test hook lowers it, so that small segments take the streamed route)
     int gather_lds_cap = 0;
+    // gather_mask_kernel_used = the mask kernel of the last screen (matrix_smh_kind: 0 generic, 1 tile, 2 narrow, 3 wide; -1 none yet);
+    // "gather_generic" 1 = every m that is not a tile m takes the generic mask kernel (a test and measurement hook, read at the call)
+    int gather_mask_kernel_used = -1;
+    int gather_generic = 0;
 
     // sketches merged by group (selhip_ctx_merge_groups; kernel_merge.cuh, host_merge.hpp): scratch the call owns
     MergeScratch mg;

@@ -48,12 +48,16 @@ int gather_check(std::string* err, const char* what, int m, int c_min, int max_p
 
 // the screen of n_q >= 1 query rows against n_d >= 0 database rows on st; arguments checked (gather_check).  tc: the context whose
 // "gather_mask" / "gather_pick" timers the two stages run under, or null; lds_cap: bytes of LDS for a staged segment.  Waits for the
-// stream once inside the mask stage and once behind the picks
+// stream once inside the mask stage and once behind the picks.  The mask kernel is that of matrix_smh_kind(m) -- tile, narrow, wide (m <=
+// kGatherMaxM), else generic --; the generic one also takes any base pointer off the 16-byte grid (the others load 16 bytes per lane)
+// and, under force_generic ("gather_generic"), every m that is not a tile m.  *kind_out = which
 int gather_run(selhip_ctx* tc, std::string* err, const char* what, hipStream_t st, const u64* Q, int64_t n_q, const u64* D, int64_t n_d, int m, int c_min,
-               int max_picks, int lds_cap, const GatherOut& o) {
+               int max_picks, int lds_cap, const GatherOut& o, bool force_generic, int* kind_out) {
     const int W = gather_words(m);
-    const bool fast = matrix_smh_fast(m) && !((reinterpret_cast<uintptr_t>(Q) | reinterpret_cast<uintptr_t>(D)) & 15);
-    const MatrixUnits mu = matrix_units(n_q, n_d, fast ? matrix_smh_tile_rows(m) : kWavesPerBlock);
+    const bool aligned = !((reinterpret_cast<uintptr_t>(Q) | reinterpret_cast<uintptr_t>(D)) & 15);
+    const int kind = !aligned || (force_generic && !matrix_smh_fast(m)) ? kMatrixSmhGeneric : matrix_smh_kind(m);
+    *kind_out = kind;
+    const MatrixUnits mu = matrix_units(n_q, n_d, kind == kMatrixSmhGeneric ? kWavesPerBlock : matrix_smh_unit_rows(m));
     const long long n_spans = std::max<long long>(mu.n_spans, 1);
     if (mu.n_tiles > 0x7FFFFFFFll) { set_err(err, "%s: too many queries for one launch", what); return SELHIP_E_BADARG; }
     GatherScratch s;
@@ -75,11 +79,24 @@ int gather_run(selhip_ctx* tc, std::string* err, const char* what, hipStream_t s
     auto mask_launch = [&](bool fill, GatherCand* cand, uint32_t* masks) {
         with_flag(fill, [&](auto F) {
             constexpr bool FILL = decltype(F)::value;
-            if (!fast) {
+            if (kind == kMatrixSmhGeneric) {
                 hipLaunchKernelGGL((gather_mask_generic_kernel<FILL>), dim3(grid), dim3(kBlock), 0, st, Q, D, m, (int)n_q, (int)n_d, (int)mu.n_tiles, mu.n_units,
                                    c_min, n_spans, span_cnt, (const u64*)qstart, cand, masks);
                 return;
             }
+            if (kind == kMatrixSmhWide) {
+                hipLaunchKernelGGL((gather_mask_wide_kernel<FILL>), dim3(grid), dim3(kBlock), 0, st, (const u64x2*)Q, (const u64x2*)D, m / (128 * kMatrixSmhWideNch),
+                                   (int)n_q, (int)n_d, (int)mu.n_tiles, mu.n_units, c_min, n_spans, span_cnt, (const u64*)qstart, cand, masks);
+                return;
+            }
+#define SELHIP_GATHER_NARROW_LAUNCH(G) hipLaunchKernelGGL((gather_mask_narrow_kernel<G, FILL>), dim3(grid), dim3(kBlock), 0, st, (const u64x2*)Q, (const u64x2*)D, \
+                                                          (int)n_q, (int)n_d, (int)mu.n_tiles, mu.n_units, c_min, n_spans, span_cnt, (const u64*)qstart, cand, masks)
+            if (kind == kMatrixSmhNarrow) {
+                if (m == 64) SELHIP_GATHER_NARROW_LAUNCH(2);
+                else         SELHIP_GATHER_NARROW_LAUNCH(4);
+                return;
+            }
+#undef SELHIP_GATHER_NARROW_LAUNCH
 #define SELHIP_GATHER_MASK_LAUNCH(NCH) hipLaunchKernelGGL((gather_mask_kernel<NCH, FILL>), dim3(grid), dim3(kBlock), 0, st, (const u64x2*)Q, (const u64x2*)D, \
                                                           (int)n_q, (int)n_d, (int)mu.n_tiles, mu.n_units, c_min, n_spans, span_cnt, (const u64*)qstart, cand, masks)
             switch (m / 128) {
@@ -94,7 +111,16 @@ int gather_run(selhip_ctx* tc, std::string* err, const char* what, hipStream_t s
     auto valid_launch = [&]() {
         const unsigned vgrid = grid_for((u64)n_q, kWavesPerBlock, 65536);
 #define SELHIP_GATHER_VALID_LAUNCH(NCH) hipLaunchKernelGGL((gather_valid_kernel<NCH>), dim3(vgrid), dim3(kBlock), 0, st, Q, m, (int)n_q, valid)
-        switch (fast ? m / 128 : 0) {
+        if (kind == kMatrixSmhWide) {
+            hipLaunchKernelGGL(gather_valid_wide_kernel, dim3(vgrid), dim3(kBlock), 0, st, (const u64x2*)Q, m / (128 * kMatrixSmhWideNch), (int)n_q, valid);
+            return;
+        }
+        if (kind == kMatrixSmhNarrow) {
+            if (m == 64) hipLaunchKernelGGL((gather_valid_narrow_kernel<2>), dim3(vgrid), dim3(kBlock), 0, st, (const u64x2*)Q, (int)n_q, valid);
+            else         hipLaunchKernelGGL((gather_valid_narrow_kernel<4>), dim3(vgrid), dim3(kBlock), 0, st, (const u64x2*)Q, (int)n_q, valid);
+            return;
+        }
+        switch (kind == kMatrixSmhTile ? m / 128 : 0) {
             case 0:  SELHIP_GATHER_VALID_LAUNCH(0); break;
             case 1:  SELHIP_GATHER_VALID_LAUNCH(1); break;
             case 2:  SELHIP_GATHER_VALID_LAUNCH(2); break;
@@ -164,7 +190,8 @@ int gather_ctx_call(selhip_ctx* c, int c_min, int max_picks, selhip_gather_pick_
     int cap = 0;
     if (gather_device_lds(&cap)) { set_err(&c->err, "%s: the device reports no LDS size", what); return SELHIP_E_HIP; }
     if (c->gather_lds_cap > 0) cap = std::min(cap, c->gather_lds_cap);
-    return gather_run(c, &c->err, what, c->stream, c->q.d_aux, c->q.n, c->d_aux, c->n, c->m, c_min, max_picks, cap, GatherOut{d_picks, d_n_picks, d_unexplained});
+    return gather_run(c, &c->err, what, c->stream, c->q.d_aux, c->q.n, c->d_aux, c->n, c->m, c_min, max_picks, cap, GatherOut{d_picks, d_n_picks, d_unexplained},
+                      c->gather_generic != 0, &c->gather_mask_kernel_used);
 }
 
 }  // namespace

@@ -12,8 +12,24 @@
 //       survivor's ballots are its mask -- lane l < 2 NCH selects ballot l and stores it with one 8-byte vector store.  The lane map of
 //       the coalesced loads permutes the bits: ballot 2 c + h, bit l = bucket 128 c + 2 l + h.  Every candidate of a query, and the
 //       query's own valid mask (gather_valid_kernel), use that one map.  FILL = false tallies the survivors per (query, span).
-//     gather_mask_generic_kernel<FILL>   every other m <= 4 096, and rows that are not 16-byte aligned: one query row per wave, lane =
-//       column of the span, masks in natural bucket order (word w, bit b = bucket 32 w + b; padding bits zero).
+//     gather_mask_narrow_kernel<G, FILL>   m = 128 / G, G in {2, 4}: matrix_smh_narrow_kernel's enumeration (Q = 12 query rows per wave,
+//       one u64x2 each, replicated over the G lane groups; a wave load = G consecutive candidate rows through the same ring).  The two
+//       ballots of a (row, load) hold G fields of 64 / G bits; matrix_smh_narrow_counts splits the raw counts, and a (row, group) that
+//       reaches c_min ANDs its fields with the query row's `bucket filled` fields and counts again.  A survivor's fields are its mask.
+//     gather_mask_wide_kernel<FILL>   m = 1 024 C, C in {2, 3, 4}: two phases per (wave, span).  Phase 1 is matrix_smh_wide_kernel's walk
+//       (Q = 3 rows, chunk-major, ring of two): lane l ends with the RAW count of column k0 + l.  Phase 2 takes the columns whose raw
+//       count reaches c_min in ascending order on the scalar unit and walks the C chunks of that one pair again (both rows in L2 by
+//       then): 16 ballots per chunk, ANDed with the query chunk's `bucket filled` ballots, the masked count added up, and the ballots
+//       PARKED -- lane l < 16 keeps ballot l of chunk c in one u64 register -- because only the last chunk decides.  A survivor's parked
+//       words are stored, C 8-byte stores per lane; nothing is stored for a pair that fails (its slot belongs to the next cell).
+//     gather_mask_generic_kernel<FILL>   every other m <= 4 096, rows that are not 16-byte aligned, and every non-tile m under
+//       "gather_generic": one query row per wave, lane = column of the span.
+//     THE BIT MAPS of a mask (one per kernel; a query's valid mask, gather_valid_*_kernel, and all of its candidates' masks share it, and
+//     no output depends on which):
+//       tile     u64 word 2 c + h, bit l = bucket 128 c + 2 l + h                              (c < NCH, h = 0 for .x, 1 for .y)
+//       wide     u64 word 16 c' + 2 c + h, bit l = bucket 1 024 c' + 128 c + 2 l + h           (the tile map of NCH = 8 per chunk c' < C)
+//       narrow   m = 64: dword h, bit l = bucket 2 l + h;  m = 32: ONE dword, bit l = bucket 2 l, bit 16 + l = bucket 2 l + 1 (l < 16)
+//       generic  natural order: dword w, bit b = bucket 32 w + b; padding bits zero
 //     gather_scan_rows_kernel / gather_scan_queries_kernel   the tallies of a query's spans into exclusive offsets in place and a total,
 //       the totals into 64-bit segment starts, the number of candidates and the longest segment.
 //   PICK STAGE -- gather_pick_kernel<WT>: one workgroup per query, all rounds in one launch.  A segment that fits the LDS the launch was
@@ -67,6 +83,43 @@ void gather_valid_kernel(const u64* __restrict__ X, int m, int n_q, uint32_t* __
                 for (int b = 0; b < 32 && 32 * w + b < m; ++b) word |= (x[32 * w + b] != kGatherEmpty ? 1u : 0u) << b;
                 valid[i * W + w] = word;
             }
+        }
+    }
+}
+
+// the narrow form: a wave load is G query rows, lane group g holds row i + g; lane g < G stores the fields of its row
+template <int G>
+__global__ __launch_bounds__(kBlock)
+void gather_valid_narrow_kernel(const u64x2* __restrict__ X, int n_q, uint32_t* __restrict__ valid) {
+    constexpr int LPR = kWave / G;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int sub = lane & (LPR - 1), grp = lane / LPR;
+    for (long long i = ((long long)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave) * G; i < n_q; i += (long long)gridDim.x * kWavesPerBlock * G) {
+        const u64x2 v = X[min(i + grp, (long long)n_q - 1) * LPR + sub];      // groups past the set re-read the last row, never stored
+        const u64 bx = __ballot(v.x != kGatherEmpty), by = __ballot(v.y != kGatherEmpty);
+        if (lane < G && i + lane < n_q) {
+            if constexpr (G == 2) reinterpret_cast<u64*>(valid)[i + lane] = (u64)(uint32_t)(bx >> (32 * lane)) | ((by >> (32 * lane)) << 32);
+            else valid[i + lane] = ((uint32_t)(bx >> (16 * lane)) & 0xFFFFu) | ((uint32_t)(by >> (16 * lane)) << 16);
+        }
+    }
+}
+
+// the wide form: n_chunks chunks of the NCH = 8 map
+__global__ __launch_bounds__(kBlock)
+void gather_valid_wide_kernel(const u64x2* __restrict__ X, int n_chunks, int n_q, uint32_t* __restrict__ valid) {
+    constexpr int NCH = kMatrixSmhWideNch;
+    const int lane = threadIdx.x & (kWave - 1);
+    for (long long i = (long long)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave; i < n_q; i += (long long)gridDim.x * kWavesPerBlock) {
+        for (int c = 0; c < n_chunks; ++c) {
+            const u64x2* row = X + (i * n_chunks + c) * (NCH * kWave) + lane;
+            u64 b[2 * NCH];
+#pragma unroll
+            for (int h = 0; h < NCH; ++h) {
+                const u64x2 v = row[h * kWave];
+                b[2 * h] = __ballot(v.x != kGatherEmpty);
+                b[2 * h + 1] = __ballot(v.y != kGatherEmpty);
+            }
+            gather_store_ballots<2 * NCH>(reinterpret_cast<u64*>(valid + (i * n_chunks + c) * (4 * NCH)), b, lane);
         }
     }
 }
@@ -151,6 +204,228 @@ void gather_mask_kernel(const u64x2* __restrict__ X, const u64x2* __restrict__ Y
                 if (kk >= ke) break;
                 load_row(ring[(s + AHEAD) % RING], kk + AHEAD);
                 compare_row(ring[s], kk);
+            }
+        }
+        if constexpr (!FILL) {
+            int mine = 0;
+#pragma unroll
+            for (int a = 0; a < Q; ++a) mine = lane == a ? ns[a] : mine;
+            if (lane < Q && i0 + lane < n_q) span_cnt[(long long)(i0 + lane) * n_spans + span] = (uint32_t)mine;
+        }
+    }
+}
+
+// ---- narrow rows: m = 32 and m = 64 -----------------------------------------------------------------------------------------------
+// the mask stage of m = 128 / G: the tile kernel's survivor counting over matrix_smh_narrow_kernel's loads.  A cell's survivors come in
+// ascending rank in both launches: the loads ascend, and within a load g ascends
+template <int G, bool FILL>
+__global__ __launch_bounds__(kBlock, 3)
+void gather_mask_narrow_kernel(const u64x2* __restrict__ X, const u64x2* __restrict__ Y, int n_q, int n_y, int n_tiles, long long n_units, int c_min,
+                               long long n_spans, uint32_t* __restrict__ span_cnt, const u64* __restrict__ qstart, GatherCand* __restrict__ cand,
+                               uint32_t* __restrict__ masks) {
+    constexpr int Q = kMatrixSmhNarrowQ;
+    constexpr int LPR = kWave / G;                     // u64x2 (lanes) per sketch row = bits of a ballot field: m = 2 LPR
+    constexpr int AHEAD = kStreamAhead;
+    constexpr int RING = AHEAD + 1;
+    static_assert(kMatrixSpan % G == 0, "a span is whole wave loads");
+    static_assert(Q <= kWave, "one lane per query row holds its segment position");
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x / kWave);
+    const int sub = lane & (LPR - 1), grp = lane / LPR;
+    for (long long u = blockIdx.x; u < n_units; u += gridDim.x) {
+        const long long j = u >> 3;
+        const long long span = 8 * (j / n_tiles) + (u & 7);
+        const long long k0l = span * kMatrixSpan;
+        if (k0l >= n_y) continue;
+        const long long i0l = ((j % n_tiles) * kWavesPerBlock + wave) * Q;
+        if (i0l >= n_q) continue;                                            // wave-uniform; the kernel has no block barrier
+        const int i0 = (int)i0l, k0 = (int)k0l;
+        const int ke = (int)min((long long)n_y, k0l + kMatrixSpan);
+        u64x2 q[Q];
+#pragma unroll
+        for (int a = 0; a < Q; ++a) q[a] = X[(long long)min(i0 + a, n_q - 1) * LPR + sub];     // every lane group holds the whole row; rows past the set: a valid row, never stored
+        // lane a = survivors of (row a, this span) so far.  Wave-uniform per row, but kept in ONE VGPR and touched only when a pair
+        // survives: twelve scalar counters on top of the ballots were more than the SGPR file holds
+        int ns = 0;
+        u64 vbase = 0;                                                       // FILL: lane a = where row a's survivors of this span start
+        if (FILL && lane < Q && i0 + lane < n_q) vbase = qstart[i0 + lane] + span_cnt[(long long)(i0 + lane) * n_spans + span];
+        u64x2 ring[RING];
+        auto load_rows = [&](u64x2& dst, int kk) { dst = Y[(long long)min(kk + grp, ke - 1) * LPR + sub]; };     // a group past the span re-reads row ke - 1
+        auto compare_rows = [&](const u64x2& cd, int kk) {
+#pragma unroll
+            for (int a = 0; a < Q; ++a) {
+                const u64 bx = __ballot(cd.x == q[a].x), by = __ballot(cd.y == q[a].y);      // (the two ballots matrix_smh_narrow_counts forms: one pair of compares)
+                int raw[G];
+                matrix_smh_narrow_counts<G>(q[a], cd, raw);
+                bool any = false;
+#pragma unroll
+                for (int g = 0; g < G; ++g) any = any || (raw[g] >= c_min && kk + g < ke);
+                if (!any || i0 + a >= n_q) continue;                         // (the raw count bounds the masked one from above)
+                // the query row's `bucket filled` fields, formed only now: field 0 of each ballot (every group holds the row)
+                // (behind an empty asm on the constant, so that the compiler does not hoist the 2 Q loop-invariant ballots into SGPRs it lacks)
+                u64 empty = kGatherEmpty;
+                asm volatile("" : "+s"(empty));
+                const uint32_t vx = (uint32_t)__ballot(q[a].x != empty), vy = (uint32_t)__ballot(q[a].y != empty);
+#pragma unroll
+                for (int g = 0; g < G; ++g) {
+                    if (raw[g] < c_min || kk + g >= ke) continue;
+                    uint32_t w0, w1 = 0;
+                    if constexpr (G == 2) {
+                        w0 = (uint32_t)(bx >> (LPR * g)) & vx;
+                        w1 = (uint32_t)(by >> (LPR * g)) & vy;
+                    } else {
+                        w0 = (((uint32_t)(bx >> (LPR * g)) & 0xFFFFu) | ((uint32_t)(by >> (LPR * g)) << 16)) & ((vx & 0xFFFFu) | (vy << 16));
+                    }
+                    const int cnt = __popc(w0) + __popc(w1);
+                    if (cnt < c_min) continue;
+                    if constexpr (FILL) {
+                        const u64 base = ((u64)(uint32_t)__builtin_amdgcn_readlane((int)(vbase >> 32), a) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)vbase, a);
+                        const u64 slot = base + (u64)(uint32_t)__builtin_amdgcn_readlane(ns, a);
+                        if (lane == 0) {
+                            cand[slot] = GatherCand{kk + g, cnt};
+                            if constexpr (G == 2) *reinterpret_cast<u64*>(masks + slot * 2) = (u64)w0 | ((u64)w1 << 32);
+                            else masks[slot] = w0;
+                        }
+                    }
+                    ns = matrix_smh_writelane(__builtin_amdgcn_readlane(ns, a) + 1, a, ns);
+                }
+            }
+        };
+#pragma unroll
+        for (int s = 0; s < AHEAD; ++s) load_rows(ring[s], k0 + s * G);
+        for (int k = k0; k < ke; k += RING * G) {
+#pragma unroll
+            for (int s = 0; s < RING; ++s) {
+                const int kk = k + s * G;
+                if (kk >= ke) break;
+                load_rows(ring[(s + AHEAD) % RING], kk + AHEAD * G);
+                compare_rows(ring[s], kk);
+            }
+        }
+        if constexpr (!FILL) {
+            if (lane < Q && i0 + lane < n_q) span_cnt[(long long)(i0 + lane) * n_spans + span] = (uint32_t)ns;
+        }
+    }
+}
+
+// ---- wide rows: m = 1024 C, C = 2 .. 4 ------------------------------------------------------------------------------------------------
+template <bool FILL>
+__global__ __launch_bounds__(kBlock, 2)
+void gather_mask_wide_kernel(const u64x2* __restrict__ X, const u64x2* __restrict__ Y, int n_chunks, int n_q, int n_y, int n_tiles, long long n_units, int c_min,
+                             long long n_spans, uint32_t* __restrict__ span_cnt, const u64* __restrict__ qstart, GatherCand* __restrict__ cand,
+                             uint32_t* __restrict__ masks) {
+    constexpr int NCH = kMatrixSmhWideNch;
+    constexpr int Q = matrix_smh_q(NCH);
+    constexpr int CHV = NCH * kWave;                   // u64x2 per chunk of a row
+    constexpr int NB = 2 * NCH;                        // ballots per (pair, chunk) = u64 words of a chunk's mask
+    constexpr int MAXC = kGatherMaxM / (2 * CHV);      // the parking registers: one u64 per chunk
+    const long long pitch = (long long)n_chunks * CHV; // u64x2 per sketch row
+    const u64 W = (u64)(2 * NB) * (u64)n_chunks;       // dwords of a mask
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x / kWave);
+    for (long long u = blockIdx.x; u < n_units; u += gridDim.x) {
+        const long long j = u >> 3;
+        const long long span = 8 * (j / n_tiles) + (u & 7);
+        const long long k0l = span * kMatrixSpan;
+        if (k0l >= n_y) continue;
+        const long long i0l = ((j % n_tiles) * kWavesPerBlock + wave) * Q;
+        if (i0l >= n_q) continue;                                            // wave-uniform; the kernel has no block barrier
+        const int i0 = (int)i0l, k0 = (int)k0l;
+        const int ke = (int)min((long long)n_y, k0l + kMatrixSpan);
+        int acc[Q];                                                          // lane l: the running RAW count of column k0 + l
+#pragma unroll
+        for (int a = 0; a < Q; ++a) acc[a] = 0;
+        {
+            // phase 1, matrix_smh_wide_kernel's walk: ONE stream of (chunk, candidate row) steps, chunk-major, through a ring of two
+            u64x2 q[Q][NCH];
+            auto load_queries = [&](int c) {
+#pragma unroll
+                for (int a = 0; a < Q; ++a) {
+                    const u64x2* row = X + (long long)min(i0 + a, n_q - 1) * pitch + (long long)c * CHV + lane;      // rows past the set: a valid row, never stored
+#pragma unroll
+                    for (int h = 0; h < NCH; ++h) q[a][h] = row[h * kWave];
+                }
+            };
+            u64x2 ring[2][NCH];
+            int pc = 0, pk = k0;                                             // the step to fetch next (wave-uniform)
+            auto prefetch = [&](u64x2 (&dst)[NCH]) {
+                const u64x2* row = Y + (long long)pk * pitch + (long long)pc * CHV + lane;
+#pragma unroll
+                for (int h = 0; h < NCH; ++h) dst[h] = row[h * kWave];
+                if (pk + 1 < ke) ++pk;
+                else if (pc + 1 < n_chunks) { pk = k0; ++pc; }               // (behind the last step: that step again)
+            };
+            int cc = 0, ck = k0;                                             // the step to compare next
+            auto compare_row = [&](const u64x2 (&cd)[NCH]) {
+                const int col = ck - k0;
+#pragma unroll
+                for (int a = 0; a < Q; ++a) {
+                    const int cnt = matrix_smh_chunk_count<NCH>(q[a], cd) + __builtin_amdgcn_readlane(acc[a], col);
+                    acc[a] = matrix_smh_writelane(cnt, col, acc[a]);
+                }
+                if (++ck == ke) {
+                    ck = k0;
+                    if (++cc < n_chunks) load_queries(cc);
+                }
+            };
+            const int steps = n_chunks * (ke - k0);
+            prefetch(ring[0]);
+            load_queries(0);
+            for (int t = 0; t < steps; t += 2) {
+                prefetch(ring[1]);
+                compare_row(ring[0]);
+                if (t + 1 >= steps) break;
+                prefetch(ring[0]);
+                compare_row(ring[1]);
+            }
+        }
+        // phase 2: the pairs whose raw count reaches c_min, one at a time in ascending rank; the phase-1 registers are dead
+        int ns[Q];                                                           // survivors of (row a, this span) so far; wave-uniform
+#pragma unroll
+        for (int a = 0; a < Q; ++a) ns[a] = 0;
+        u64 vbase = 0;                                                       // FILL: lane a = where row a's survivors of this span start
+        if (FILL && lane < Q && i0 + lane < n_q) vbase = qstart[i0 + lane] + span_cnt[(long long)(i0 + lane) * n_spans + span];
+#pragma unroll
+        for (int a = 0; a < Q; ++a) {
+            u64 todo = __ballot(acc[a] >= c_min && k0 + lane < ke);
+            if (i0 + a >= n_q) todo = 0;
+            const u64x2* const qrow = X + (long long)min(i0 + a, n_q - 1) * pitch + lane;
+            while (todo) {
+                const int col = __builtin_ctzll(todo);
+                todo &= todo - 1;
+                const u64x2* const crow = Y + (long long)(k0 + col) * pitch + lane;
+                u64 park[MAXC];
+                int cnt = 0;
+#pragma unroll
+                for (int c = 0; c < MAXC; ++c) {
+                    park[c] = 0;
+                    if (c >= n_chunks) continue;
+                    u64x2 qc[NCH], cd[NCH];
+#pragma unroll
+                    for (int h = 0; h < NCH; ++h) { qc[h] = qrow[c * CHV + h * kWave]; cd[h] = crow[c * CHV + h * kWave]; }
+                    u64 v = 0;
+#pragma unroll
+                    for (int h = 0; h < NCH; ++h) {
+                        const u64 bx = __ballot(cd[h].x == qc[h].x) & __ballot(qc[h].x != kGatherEmpty);
+                        const u64 by = __ballot(cd[h].y == qc[h].y) & __ballot(qc[h].y != kGatherEmpty);
+                        cnt += __popcll(bx) + __popcll(by);
+                        v = lane == 2 * h ? bx : lane == 2 * h + 1 ? by : v;  // (the select chain of gather_store_ballots)
+                    }
+                    park[c] = v;
+                }
+                if (cnt < c_min) continue;
+                if constexpr (FILL) {
+                    const u64 base = ((u64)(uint32_t)__builtin_amdgcn_readlane((int)(vbase >> 32), a) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)vbase, a);
+                    const u64 slot = base + (u64)ns[a];
+                    if (lane == 0) cand[slot] = GatherCand{k0 + col, cnt};
+                    if (lane < NB) {
+                        u64* const dst = reinterpret_cast<u64*>(masks + slot * W) + lane;
+#pragma unroll
+                        for (int c = 0; c < MAXC; ++c)
+                            if (c < n_chunks) dst[c * NB] = park[c];
+                    }
+                }
+                ns[a] += 1;
             }
         }
         if constexpr (!FILL) {

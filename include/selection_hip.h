@@ -1109,6 +1109,13 @@ int selhip_ctx_neighbor_joining(selhip_ctx* ctx, int measure, selhip_nj_join_t* 
  *     once word-major, a longer one is read from global memory every round; popcount(mask & live) per candidate with live in scalar
  *     registers for m <= 1 024, a (count, smaller rank) butterfly in the wave, four waves through LDS, one barrier per round.
  *     Not built: an all-pairs self mode, the HLL-based measures, more than one device, lazy re-evaluation of stale counts.
+ *     KERNELS OF THE MASK STAGE.  m = 32 and 64 take a narrow kernel (a wave load holds 4 or 2 candidate rows, the counts and masks
+ *     split from two ballots) and m = 2 048, 3 072, 4 096 a wide one (raw totals per chunk of 1 024 buckets first, then the masked
+ *     count and the mask of the pairs that reach c_min), of the "every other m" above.  get_param "gather_mask_kernel_used": the
+ *     mask kernel of the context's last screen, 0 = generic, 1 = the tile kernel of m = 128 ... 1 024, 2 = the narrow kernel of
+ *     m = 32 or 64, 3 = the wide kernel, -1 = none yet.  set_param "gather_generic" 1: every m that is not a tile m takes the generic
+ *     kernel (0 = the kernel that fits m, the default; any other value is refused, SELHIP_E_BADARG); per context, read at the call,
+ *     the same picks either way -- a test and measurement hook, the twin of "matrix_smh_generic" and "smhc_generic".
  * --------------------------------------------------------------------------------------------------- */
 #define SELHIP_GATHER_MAX_PICKS 4096
 typedef struct {

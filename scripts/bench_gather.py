@@ -15,9 +15,16 @@ code: it streams the rows twice (count, then fill), so twice the yardstick's med
 host route runs `--host-reps` times over the first 16 queries: both bucket arrays copied to the host plus tests/gather_model.py; its picks
 are compared with the device's byte for byte.
 
+`--shapes` measures the mask stage's narrow (m = 32, 64) and wide (m = 2048, 4096) kernels instead: the screen and
+the mixture workload rebuilt at that m (cfg4's generator with m replaced), c_min = 3.  Three warm calls, then `--reps` rounds that
+alternate the kernel of m, the same context under "gather_generic" = 1 (the route those m took before) and the matrix call; the aim is
+the same rule, and the picks of the two routes are compared byte for byte.
+
 usage: bench_gather.py [--out profiles/gather_bench.json] [--only screen:1,...] [--reps 20] [--host-reps 3] [--limit seconds]
+       bench_gather.py --shapes all|32,64,2048,4096 [--out profiles/gather_shapes_bench.json] [--reps 20] [--limit seconds]
 """
 import argparse
+import dataclasses
 import json
 import subprocess
 import sys
@@ -38,11 +45,16 @@ MAX_PICKS = 64
 HOST_QUERIES = 16
 
 
-def sets(kind):
-    """(hll, aux, cards) of the database and the queries' bucket rows, device tensors"""
+SHAPES = (32, 64, 2048, 4096)
+SHAPE_C_MIN = 3
+
+
+def sets(kind, m=None):
+    """(hll, aux, cards) of the database and the queries' bucket rows, device tensors; m: cfg4's generator at another row width"""
     import torch
     import cuda_selection_criteria_amd as pkg
-    hll, aux, cards, _, _ = pkg.synth_device(pkg.SYNTH_CONFIGS["cfg4"], device=0)
+    cfg = pkg.SYNTH_CONFIGS["cfg4"]
+    hll, aux, cards, _, _ = pkg.synth_device(cfg if m is None else dataclasses.replace(cfg, m=m), device=0)
     if kind == "screen":
         return hll, aux, cards, aux[::50].contiguous()
     if kind == "mixture":
@@ -122,9 +134,69 @@ def bench(kind, c_min, reps, host_reps):
     return out
 
 
+def bench_shape(kind, m, reps):
+    """one workload at one m: the mask and pick timers under the kernel of m and under "gather_generic" = 1, and the matrix call"""
+    import torch
+    import cuda_selection_criteria_amd as pkg
+    hll, aux, cards, q_aux = sets(kind, m)
+    n_q, n_d, c_min = q_aux.shape[0], aux.shape[0], SHAPE_C_MIN
+    out = {"workload": f"{kind}:{c_min}", "n_q": n_q, "n_d": n_d, "m": m, "c_min": c_min, "max_picks": MAX_PICKS}
+    with pkg.Selector(0) as sel:
+        sel.attach(hll, aux, cards)
+        sel.attach_queries(torch.zeros((n_q, 1 << 14), dtype=torch.uint8, device=aux.device), q_aux, torch.zeros(n_q, dtype=torch.float64, device=aux.device))
+        kept = sel.query_matrix("smh_matches", torch.float32)
+        out["candidates_per_query"] = float((kept >= c_min).sum().item()) / n_q
+        picks, used = {}, {}
+        for generic in (0, 1):
+            sel.set_param("gather_generic", generic)
+            picks[generic] = sel.gather(c_min, MAX_PICKS)
+            used[generic] = sel.get_param("gather_mask_kernel_used")
+        out["mask_kernel_used"] = {"new": used[0], "generic": used[1]}
+        out["picks_per_query"] = float(picks[0]["n_picks"].mean())
+        out["picks_identical_to_generic"] = bool(all(picks[0][k].tobytes() == picks[1][k].tobytes() for k in ("picks", "n_picks", "unexplained")))
+
+        def gather_ms(generic):
+            sel.set_param("gather_generic", generic)
+            sel.timing(1)
+            sel.gather(c_min, MAX_PICKS, to_host=False)
+            t = sel.kernel_ms("gather_mask"), sel.kernel_ms("gather_pick")
+            sel.timing(0)
+            return t
+
+        def matrix_ms():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            sel.query_matrix("smh_matches", torch.float32, out=kept)
+            b.record()
+            torch.cuda.synchronize()
+            return a.elapsed_time(b)
+
+        calls = {"new": lambda: gather_ms(0), "generic": lambda: gather_ms(1), "matrix": matrix_ms}
+        for _ in range(3):
+            for call in calls.values():
+                call()
+        samples = {"new_mask": [], "new_pick": [], "generic_mask": [], "generic_pick": [], "matrix": []}
+        names = list(calls)
+        for r in range(reps):
+            for name in names[r % 3:] + names[:r % 3]:
+                t = calls[name]()
+                if name == "matrix":
+                    samples["matrix"].append(t)
+                else:
+                    samples[name + "_mask"].append(t[0])
+                    samples[name + "_pick"].append(t[1])
+        sel.set_param("gather_generic", 0)
+        out.update({k + "_ms": med(v) for k, v in samples.items()})
+        out["mask_aim_ms"] = round(2 * out["matrix_ms"]["median"] + (out["matrix_ms"]["max"] - out["matrix_ms"]["min"]), 4)
+        out["mask_within_the_aim"] = bool(out["new_mask_ms"]["median"] <= out["mask_aim_ms"])
+        out["generic_over_new"] = round(out["generic_mask_ms"]["median"] / out["new_mask_ms"]["median"], 2)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--out", default="profiles/gather_bench.json")
+    ap.add_argument("--out", default=None, help="default profiles/gather_bench.json, with --shapes profiles/gather_shapes_bench.json")
+    ap.add_argument("--shapes", default=None, help="the narrow / wide mask kernels instead of the workloads: a list of m out of 32,64,2048,4096, or 'all'")
     ap.add_argument("--only", default=",".join(WORKLOADS))
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--host-reps", type=int, default=3)
@@ -133,9 +205,31 @@ def main():
     args = ap.parse_args()
     if args.worker:
         kind, c_min = args.worker.split(":")
-        print("RESULT " + json.dumps(bench(kind, int(c_min), args.reps, args.host_reps)), flush=True)
+        res = bench_shape(kind, int(c_min), args.reps) if args.shapes else bench(kind, int(c_min), args.reps, args.host_reps)
+        print("RESULT " + json.dumps(res), flush=True)
         return 0
     results = []
+    if args.shapes:
+        shapes = SHAPES if args.shapes == "all" else tuple(int(x) for x in args.shapes.split(","))
+        out_path = Path(args.out or "profiles/gather_shapes_bench.json")
+        for m in shapes:
+            for kind in ("screen", "mixture"):
+                # (the worker's second field is m here) a fresh child process per line, under its own time limit; nothing more after a failure
+                child = subprocess.run(["timeout", "-k", "10", str(args.limit), sys.executable, __file__, "--shapes", "1", "--worker", f"{kind}:{m}", "--reps",
+                                        str(args.reps)], stdout=subprocess.PIPE, text=True)
+                line = next((ln for ln in child.stdout.splitlines() if ln.startswith("RESULT ")), None)
+                if child.returncode != 0 or line is None:
+                    print(f"m = {m} {kind} ended with status {child.returncode}: stopping", file=sys.stderr, flush=True)
+                    return 1
+                r = json.loads(line[len("RESULT "):])
+                results.append(r)
+                print(f"m={m} {r['workload']}: mask {r['new_mask_ms']['median']} ms, generic {r['generic_mask_ms']['median']} ms ({r['generic_over_new']}x), aim "
+                      f"{r['mask_aim_ms']}, within the aim: {'yes' if r['mask_within_the_aim'] else '**no**'}; pick {r['new_pick_ms']['median']} ms; matrix "
+                      f"{r['matrix_ms']['median']} ms; picks identical: {r['picks_identical_to_generic']}", flush=True)
+                out_path.parent.mkdir(parents=True, exist_ok=True)
+                out_path.write_text(json.dumps({"device": "MI355X", "protocol": f"3 warm calls, {args.reps} alternating rounds", "lines": results}, indent=1) + "\n")
+        return 0
+    args.out = args.out or "profiles/gather_bench.json"
     for name in args.only.split(","):
         # a fresh child process per workload, under its own time limit; nothing more is started after one that failed
         child = subprocess.run(["timeout", "-k", "10", str(args.limit), sys.executable, __file__, "--worker", name, "--reps", str(args.reps),
