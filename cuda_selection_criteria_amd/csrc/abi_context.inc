@@ -57,6 +57,7 @@ void selhip_ctx_destroy(selhip_ctx* c) {
     release_queries(c);
     release_topk(c);
     c->gs.release();
+    c->adj.release();
     release_merge(c);
     if (c->h_pc) (void)hipHostFree(c->h_pc);
     if (c->st_stage1) {
@@ -307,6 +308,11 @@ int selhip_ctx_get_param(const selhip_ctx* c, const char* name, int* value) {
     if (!std::strcmp(name, "linkage_rowscans_last")) { *value = c->linkage_rowscans_last; return SELHIP_OK; } // ... the rows it scanned
     if (!std::strcmp(name, "linkage_rescans_last")) { *value = c->linkage_rescans_last; return SELHIP_OK; }  // ... and its rescan rounds
     if (!std::strcmp(name, "forest_edges_last"))    { *value = c->forest_edges_last; return SELHIP_OK; }     // ... and the edges of its forest
+    if (!std::strcmp(name, "adjacency_nnz_last"))       { *value = c->adjacency_nnz_last; return SELHIP_OK; }       // entries of the last selhip_ctx_adjacency call (clipped to 2^31 - 1), -1 = none yet
+    if (!std::strcmp(name, "adjacency_mid_rows_last"))  { *value = c->adjacency_mid_rows_last; return SELHIP_OK; }  // ... the rows its one-workgroup kernel sorted in LDS
+    if (!std::strcmp(name, "adjacency_long_rows_last")) { *value = c->adjacency_long_rows_last; return SELHIP_OK; } // ... and the rows that took the long route
+    if (!std::strcmp(name, "last_was_query"))           { *value = c->have_run && c->last_was_query ? 1 : 0; return SELHIP_OK; }   // the result list held is a query pass's (n_q x n_d ranks)
+    if (!std::strcmp(name, "adjacency_lds_cap"))        { *value = kAdjLdsCap; return SELHIP_OK; }                  // longest segment sorted in LDS
     if (!std::strcmp(name, "small_pass_used"))  { *value = c->small_used ? 1 : 0; return SELHIP_OK; }
     if (!std::strcmp(name, "pairs_route_used")) { *value = c->pairs_route_used; return SELHIP_OK; }         // list passes: 1 signature, 0 direct, 2 no smh_a stage, -1 none yet
     if (!std::strcmp(name, "pairs_gpw"))        { *value = c->pairs_gpw_used; return SELHIP_OK; }           // ... its groups of four entries per wave and batch (0: one lane per entry)

@@ -121,6 +121,18 @@ struct GraphScratch {
                      ids.release(); words.release(); key.release(); best.release(); bad.release(); tmp.release(); edges.release(); }
 };
 
+// scratch of the sparse adjacency (kernel_adjacency.cuh, host_adjacency.hpp): selhip_ctx_adjacency keeps one, selhip_adjacency owns one per call
+struct AdjScratch {
+    DevBuf<uint32_t> words;             // with slots = n_rows + 1: entries per row, fill cursors, kept counts (slots each), the two class counters, the two class lists (n_rows each)
+    DevBuf<u64> off;                    // scanned: every row's segment start, the total in slot n_rows
+    DevBuf<u64> key, key2;              // the entries grouped by row: key(value) ..., and the long rows' second segment
+    DevBuf<uint32_t> col, col2;         // ... and column
+    DevBuf<char> tmp;                   // rocPRIM scan scratch
+    DevBuf<ClusterBad> bad;             // what the count and the scatter kernel refused
+    hipError_t ensure(size_t n_rows, size_t entries, size_t tmp_bytes, bool twin);
+    void release() { words.release(); off.release(); key.release(); key2.release(); col.release(); col2.release(); tmp.release(); bad.release(); }
+};
+
 // TWO sets of per_set counter blocks: pass k uses set k & 1 and its first kernel clears the other for pass k + 1 -- no memset dispatch
 // on the stream in steady state.  dirty: a pass claimed a set and did not get to the end of its enqueue (its first kernel may never have
 // run), or nothing has cleared the buffer yet, or the stream changed behind the clearing: the next claim clears both sets first, once
@@ -160,8 +172,8 @@ static_assert(kCounterBlocks == kMaxChunks + 1, "common.cuh: counter blocks per 
 constexpr int kMaxAuxP = SELHIP_MAX_AUX_P;   // auxiliary HLL precision accepted by every entry point: aux_fused_kernel counts in 16-bit bins (a bin holds up to 2^p_aux)
 constexpr long long kEnumPairs = 1ll << 26;    // hll_a / hll_an as first criterion: pairs listed per sub-pass (512 MiB of int2)
 
-enum { T_PREP = 0, T_STAGE1, T_HIST, T_SELECT, T_TOTAL, T_SIGBUILD, T_JOIN, T_VERIFY, T_AUX, T_GROUP, T_DENSE, T_TOPK, T_MATRIX, T_MATRIX_SMH, T_CLUSTER, T_GREEDY, T_MERGE, T_FOREST, T_LINKAGE, T_NJ, T_GATHER_MASK, T_GATHER_PICK, T_COUNT };
-const char* kTimerNames[T_COUNT] = {"prep", "stage1", "hist", "select", "total", "sigbuild", "join", "verify", "aux", "group", "dense", "topk", "matrix", "matrix_smh", "cluster", "greedy", "merge", "forest", "linkage", "nj", "gather_mask", "gather_pick"};
+enum { T_PREP = 0, T_STAGE1, T_HIST, T_SELECT, T_TOTAL, T_SIGBUILD, T_JOIN, T_VERIFY, T_AUX, T_GROUP, T_DENSE, T_TOPK, T_MATRIX, T_MATRIX_SMH, T_CLUSTER, T_GREEDY, T_MERGE, T_FOREST, T_LINKAGE, T_NJ, T_GATHER_MASK, T_GATHER_PICK, T_ADJACENCY, T_COUNT };
+const char* kTimerNames[T_COUNT] = {"prep", "stage1", "hist", "select", "total", "sigbuild", "join", "verify", "aux", "group", "dense", "topk", "matrix", "matrix_smh", "cluster", "greedy", "merge", "forest", "linkage", "nj", "gather_mask", "gather_pick", "adjacency"};
 
 }  // namespace
 
@@ -399,6 +411,11 @@ struct selhip_ctx {
     // "gather_generic" 1 = every m that is not a tile m takes the generic mask kernel (a test and measurement hook, read at the call)
     int gather_mask_kernel_used = -1;
     int gather_generic = 0;
+
+    // the sparse adjacency (selhip_ctx_adjacency; kernel_adjacency.cuh, host_adjacency.hpp): its scratch, and of the last call the entries
+    // ("adjacency_nnz_last", clipped to 2^31 - 1) and the rows its block and long kernels took ("adjacency_mid_rows_last" / "_long_rows_last"); -1 = none yet
+    AdjScratch adj;
+    int adjacency_nnz_last = -1, adjacency_mid_rows_last = -1, adjacency_long_rows_last = -1;
 
     // sketches merged by group (selhip_ctx_merge_groups; kernel_merge.cuh, host_merge.hpp): scratch the call owns
     MergeScratch mg;

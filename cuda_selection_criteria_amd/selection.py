@@ -13,7 +13,7 @@ import numpy as np
 from . import _lib
 from ._lib import (ALGO_AUTO, BANDING_CPU, CRIT_HLL_A, CRIT_HLL_AN, CRIT_HLL_A_SMH_A, CRIT_NONE, CRIT_SMH_A, CRIT_SMH_C, ESTIMATOR_HLL, ESTIMATOR_SMH, F32, F64, FP_FMA,
                    MEASURE_CONTAINMENT, MEASURE_INTERSECTION, MEASURE_JACCARD, MEASURE_MAX_CONTAINMENT, MEASURE_SMH_JACCARD,
-                   MEASURE_SMH_MATCHES, MEASURE_UNION, MODE_CB_SMH, REP_MAX_DEGREE, REP_MAX_RANK, REP_MIN_RANK, REP_PRIORITY, TOPK_ROUNDS_AUTO, LINKAGE_SINGLE, LINKAGE_COMPLETE, LINKAGE_AVERAGE, LINKAGE_WEIGHTED, Clusters, Forest, Greedy, Linkage, Merged, Pair, check, hip_lib,
+                   MEASURE_SMH_MATCHES, MEASURE_UNION, MODE_CB_SMH, REP_MAX_DEGREE, REP_MAX_RANK, REP_MIN_RANK, REP_PRIORITY, TOPK_ROUNDS_AUTO, LINKAGE_SINGLE, LINKAGE_COMPLETE, LINKAGE_AVERAGE, LINKAGE_WEIGHTED, ADJ_DIRECTED, ADJ_SYMMETRIC, Clusters, Csr, Forest, Greedy, Linkage, Merged, Pair, check, hip_lib,
                    host_lib)
 
 # layout of selhip_pair_t {int32 i, k; double jaccard}
@@ -607,6 +607,28 @@ class Selector:
         check(self._lib.selhip_ctx_spanning_forest(self._ctx, mv, C.byref(out), C.byref(cnt)), self._ctx)
         return _forest_result(edges, labels, int(cnt.value), self.n, self.get_param("forest_rounds_last"), to_host)
 
+    def adjacency(self, form="symmetric", min_value: Optional[float] = None, values: bool = True, to_torch: bool = True):
+        """the result list the context holds as a sparse CSR matrix on the device (selhip_ctx_adjacency): a record {i, k, v} with
+        v >= min_value (None: every record; a NaN v never) is the entry (row i, column k, v) -- form "directed" -- and with form
+        "symmetric" also (row k, column i, v) where i != k; entries with the same (row, column) are one entry with the greatest of their
+        values; columns ascending inside each row.  n x n behind an all-pairs or pair-list pass; behind a query pass the directed form
+        alone, n_q x n_d.  Returns a torch.sparse_csr_tensor on the device (crow / col indices int32 while nnz < 2^31, else int64;
+        values float64 -- 1.0 each with values=False, which spares the value array on the device); with to_torch=False the dict
+        {"row_ptr" int64 [n_rows + 1], "col" int32 [nnz], "val" float64 [nnz] or None, "nnz"} of device tensors"""
+        import torch
+        dev = torch.device("cuda", self.device)
+        code = adjacency_form_code(form)
+        n_rows = self.n_q if self.get_param("last_was_query") == 1 and self.n_q is not None else self.n
+        bound = self.result_count() * (2 if code == ADJ_SYMMETRIC else 1)
+        row_ptr = torch.empty(n_rows + 1, dtype=torch.int64, device=dev)
+        col = torch.empty(bound, dtype=torch.int32, device=dev)
+        val = torch.empty(bound, dtype=torch.float64, device=dev) if values else None
+        out = Csr(row_ptr.data_ptr(), col.data_ptr() if bound else None, val.data_ptr() if values and bound else None)
+        nnz = C.c_int64(-1)
+        check(self._lib.selhip_ctx_adjacency(self._ctx, code, float("-inf") if min_value is None else float(min_value), C.byref(out), bound, C.byref(nnz)),
+              self._ctx)
+        return _adjacency_result(row_ptr, col, val, int(nnz.value), (n_rows, self.n), to_torch, {})
+
     # -- hierarchy of the dense matrix ------------------------------------------------------------------
     def linkage(self, measure="jaccard", method="average", max_height: Optional[float] = None, distance=None, to_host: bool = True) -> dict:
         """the agglomerative hierarchy of the context's set under the distance 1 - measure, computed on the device from the dense
@@ -1055,6 +1077,59 @@ def spanning_forest(pairs, n: int, values=None, device: int = 0, to_host: bool =
                                          int(pairs.shape[0]), n, edges.data_ptr() if edges.numel() else None, labels.data_ptr() if n > 0 else None,
                                          C.byref(f), C.byref(rounds), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
     return _forest_result(edges, labels, int(f.value), n, int(rounds.value), to_host)
+
+
+def adjacency_form_code(form) -> int:
+    """SELHIP_ADJ_* of "directed" / "symmetric" (or of the code itself)"""
+    codes = {"directed": ADJ_DIRECTED, "symmetric": ADJ_SYMMETRIC, ADJ_DIRECTED: ADJ_DIRECTED, ADJ_SYMMETRIC: ADJ_SYMMETRIC}
+    if form not in codes:
+        raise ValueError("form: 'directed' or 'symmetric'")
+    return codes[form]
+
+
+def _adjacency_result(row_ptr, col, val, nnz: int, shape, to_torch: bool, extra: dict):
+    """what Selector.adjacency / adjacency return from the device tensors a call filled: the arrays narrowed to nnz entries"""
+    import torch
+    col = col[:nnz]
+    val = None if val is None else val[:nnz]
+    if not to_torch:
+        return dict({"row_ptr": row_ptr, "col": col, "val": val, "nnz": nnz}, **extra)
+    if nnz < 2 ** 31:
+        row_ptr = row_ptr.to(torch.int32)
+    else:
+        col = col.to(torch.int64)
+    return torch.sparse_csr_tensor(row_ptr, col, torch.ones(nnz, dtype=torch.float64, device=col.device) if val is None else val, size=tuple(shape))
+
+
+def adjacency(pairs, n_rows: int, n_cols: Optional[int] = None, values=None, form="symmetric", min_value: Optional[float] = None, device: int = 0,
+              to_torch: bool = True):
+    """the sparse CSR matrix of Selector.adjacency over a caller's entries, computed on the device (selhip_adjacency): one record
+    {x, y, values[e]} per row of `pairs` (a numpy int32 (P, 2) array or a torch int32 device tensor of that shape; values: P float64
+    numbers, numpy or a torch device tensor, None: 1.0 each), x a row in [0, n_rows), y a column in [0, n_cols) (None: n_rows; the
+    symmetric form needs a square).  A rank out of range raises (SELHIP_E_BADARG).  Returns the tensor, or with to_torch=False the dict of
+    Selector.adjacency with "long_rows": the rows whose segment took the column-range split"""
+    import torch
+    lib = hip_lib()
+    dev = torch.device("cuda", device)
+    pairs = _device_pairs(pairs, dev)
+    vals = None
+    if values is not None:
+        vals = values if hasattr(values, "data_ptr") else torch.from_numpy(np.ascontiguousarray(values, dtype=np.float64)).to(dev)
+        assert vals.is_cuda and vals.is_contiguous() and vals.dtype == torch.float64 and vals.shape == (pairs.shape[0],), "values: P float64 numbers"
+    code = adjacency_form_code(form)
+    n_rows = int(n_rows)
+    n_cols = n_rows if n_cols is None else int(n_cols)
+    bound = int(pairs.shape[0]) * (2 if code == ADJ_SYMMETRIC else 1)
+    nnz, long_rows = C.c_int64(-1), C.c_int64(0)
+    with torch.cuda.device(dev):
+        row_ptr = torch.empty(max(n_rows, 0) + 1, dtype=torch.int64, device=dev)
+        col = torch.empty(bound, dtype=torch.int32, device=dev)
+        val = torch.empty(bound, dtype=torch.float64, device=dev)
+        out = Csr(row_ptr.data_ptr(), col.data_ptr() if bound else None, val.data_ptr() if bound else None)
+        check(lib.selhip_adjacency(pairs.data_ptr() if pairs.numel() else None, vals.data_ptr() if vals is not None and vals.numel() else None,
+                                   int(pairs.shape[0]), n_rows, n_cols, code, float("-inf") if min_value is None else float(min_value), C.byref(out), bound,
+                                   C.byref(nnz), C.byref(long_rows), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return _adjacency_result(row_ptr, col, val, int(nnz.value), (n_rows, n_cols), to_torch, {"long_rows": int(long_rows.value)})
 
 
 def forest_cluster_counts(edges, n: int, thresholds) -> np.ndarray:

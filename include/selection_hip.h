@@ -1128,6 +1128,56 @@ int selhip_ctx_gather(selhip_ctx* ctx, int c_min, int max_picks, selhip_gather_p
 
 
 /* ---------------------------------------------------------------------------------------------------
+ * 2n. Sparse adjacency: the result list as a CSR matrix in the caller's device memory, built on the device -- row offsets, the
+ *     columns ascending inside each row, the values, duplicates merged.  What torch.sparse_csr_tensor / scipy.sparse.csr_matrix,
+ *     a spectral or label-propagation clustering, a GNN or the k-NN graph of a top-k pass take; in the directed form also the
+ *     (i, k)-sorted list of selhip_ctx_fetch in structure-of-arrays form, without the host sort.
+ *     THE DEFINITION -- the kernels (csrc/kernel_adjacency.cuh) and the tests' model follow it.
+ *     ENTRIES.  A record {i, k, v} is an entry iff v >= min_value in f64: -INFINITY takes every record, a NaN v is never an entry, a
+ *     NaN min_value is SELHIP_E_BADARG.  SELHIP_ADJ_DIRECTED: the record gives the entry (row i, column k, v).
+ *     SELHIP_ADJ_SYMMETRIC: it also gives (row k, column i, v) when i != k.
+ *     DUPLICATES.  Entries with the same (row, column) are ONE entry -- a pair listed twice in a pair-list pass, the two directed
+ *     records of mutual neighbours in a top-k list.  Its value is the greatest of theirs under the order of key(J) of
+ *     csrc/kernel_topk.cuh (the IEEE total order: -0.0 below +0.0), so the stored bits are those of one of the records.
+ *     OUTPUTS, the caller's device memory, in selhip_csr_t: d_row_ptr[n_rows + 1] int64, d_col[cap] int32, d_val[cap] f64 (may be
+ *     NULL: not written); *nnz_out = the entries.  Row r owns [d_row_ptr[r], d_row_ptr[r + 1]); columns strictly ascending inside a
+ *     row.  Every output is a pure function of the multiset of records, min_value and the form, bit for bit, whatever order the
+ *     device worked in.  nnz > cap: SELHIP_E_OVERFLOW with *nnz_out and d_row_ptr complete, d_col / d_val unspecified.  nnz never
+ *     exceeds the record count (directed) or twice the record count (symmetric): a caller who allocates that bound needs one call.
+ *     ACCEPTED LISTS.  All-pairs passes under every criterion, measure and estimator (n x n); the all-pairs top-k with or without row
+ *     rounds; pair-list passes; a QUERY pass in the directed form only, n_rows = n_q and n_cols = n_d -- the symmetric form after a
+ *     query pass is SELHIP_E_STATE.  SELHIP_E_STATE also before any finished pass and while a pass is pending.  SELHIP_E_BADARG: a null
+ *     struct or d_row_ptr, a null d_col with cap > 0, cap < 0, an unknown form, a misaligned pointer (8 / 4 / 8 bytes), more than
+ *     2^31 - 1 rows, columns or records.  SELHIP_E_NOMEM: no room for the scratch.
+ *     SIDE EFFECTS.  The call reads the list and writes only `out` and scratch the context owns (12 bytes per possible entry, twice
+ *     that from 4 097 possible entries on; kept for the next call, released with the context).  The list, the counts, the
+ *     statistics, the top-k settings and the caches are as they were; a context that never calls it launches what it always did.
+ *     STREAM.  Every launch and copy runs on the context's stream, in stream order; the host waits once for nnz and once for the end.
+ *     get_param "adjacency_nnz_last": nnz of the last call (clipped to 2^31 - 1); "adjacency_long_rows_last" / "adjacency_mid_rows_last":
+ *     the rows that took the long route / the one-workgroup route; all -1 = none yet; "adjacency_lds_cap": 4 096; "last_was_query": 1
+ *     while the list held is a query pass's.  Timed as "adjacency"
+ *     in selhip_ctx_kernel_ms: per adjacency call, counted apart from the passes, as "cluster" is.
+ *     HOW.  Count per row, scan, scatter of (column, key(v)), 12 bytes, into row segments -- one atomic per run of equal i inside a
+ *     wave's tile, per-record atomics on the k side only.  Then every segment is sorted by (column ascending, key descending), an
+ *     entry is kept iff its column differs from its predecessor's, and the row's kept count is written -- by length L: L <= 64 one
+ *     wave per row, a sorting network in registers with cross-lane moves; L <= 4 096 one workgroup per row, staged once in LDS
+ *     (48 KiB); longer rows one workgroup that splits the segment into 256 column ranges through a histogram in LDS and a second
+ *     scratch segment and sorts runs of ranges in LDS (a single range beyond 4 096 entries: a sort through global memory, for
+ *     correctness only).  A scan of the kept counts gives d_row_ptr, one lane per kept entry writes d_col / d_val.
+ *     Not built: a command-line flag; rows and columns in file-list (position) order; selhip_ctx_fetch through this sort; the host-side
+ *     lists of selhip_multi_select / selhip_ooc_select (selhip_adjacency takes any list); a host twin.
+ * --------------------------------------------------------------------------------------------------- */
+#define SELHIP_ADJ_DIRECTED  0
+#define SELHIP_ADJ_SYMMETRIC 1
+typedef struct {
+    int64_t* d_row_ptr;      /* [n_rows + 1]                                                         */
+    int32_t* d_col;          /* [cap]                                                                */
+    double*  d_val;          /* [cap], or NULL                                                       */
+} selhip_csr_t;              /* caller's device memory                                               */
+int selhip_ctx_adjacency(selhip_ctx* ctx, int form, double min_value, const selhip_csr_t* out, int64_t cap, int64_t* nnz_out);
+
+
+/* ---------------------------------------------------------------------------------------------------
  * 3. Building blocks (device pointers), used by the launchers above and exposed for tests.
  * --------------------------------------------------------------------------------------------------- */
 /* smh_a on an explicit pair list: d_flags[j] = 1 iff pair j has a fully equal band. */
@@ -1183,6 +1233,15 @@ int selhip_greedy_representatives(const selhip_int2_t* d_pairs, int64_t n_pairs,
 int selhip_spanning_forest(const selhip_int2_t* d_pairs, const double* d_values, int64_t n_pairs, int64_t n,
                            selhip_pair_t* d_edges /* [max(n-1,0)] */, int32_t* d_label /* [n] */, int64_t* n_edges_out, int64_t* rounds_out,
                            void* hip_stream);
+/* The sparse adjacency (section 2n; csrc/kernel_adjacency.cuh) of an entry list: one record {x, y, d_values[e]} per entry of d_pairs
+ * (device memory, 8-byte aligned; NULL d_values = every value 1.0), x a row in [0, n_rows), y a column in [0, n_cols); the symmetric
+ * form needs n_rows == n_cols.  Entries, duplicates, outputs, cap and SELHIP_E_OVERFLOW are section 2n's; *long_rows_out (may be NULL):
+ * the rows that took the long route.  An entry with a row or column out of range -- whatever its value -- makes the call return
+ * SELHIP_E_BADARG with the number of such entries and the index of one; the outputs are then unspecified, and no kernel reads or
+ * writes outside the arrays because of it.  0 <= n_rows, n_cols, n_pairs <= 2^31 - 1; n_rows == 0 or n_pairs == 0 writes d_row_ptr
+ * only.  The call owns its scratch and waits for the stream. */
+int selhip_adjacency(const selhip_int2_t* d_pairs, const double* d_values, int64_t n_pairs, int64_t n_rows, int64_t n_cols, int form,
+                     double min_value, const selhip_csr_t* out, int64_t cap, int64_t* nnz_out, int64_t* long_rows_out, void* hip_stream);
 /* The hierarchy of section 2k over a caller's distance matrix d_dist[n][ld] (device memory, f64, 8-byte aligned, ld >= n counted in
  * elements), which the call works on and CONSUMES: its contents afterwards are unspecified.  With an even ld and a 16-byte aligned
  * base the row scan takes 16-byte loads, otherwise 8-byte ones; the results are the same.  d_merges (max(n - 1, 0) records, 16-byte
