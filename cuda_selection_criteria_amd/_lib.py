@@ -61,6 +61,15 @@ class Csr(C.Structure):               # selhip_csr_t: the three outputs of selhi
     _fields_ = [("d_row_ptr", C.c_void_p), ("d_col", C.c_void_p), ("d_val", C.c_void_p)]
 
 
+class MclParams(C.Structure):         # selhip_mcl_params_t: a field of 0 takes its default (inflation 2.0, prune 1e-4, chaos_tol 1e-3, K 32, 64 iterations)
+    _fields_ = [("inflation", C.c_double), ("prune", C.c_double), ("chaos_tol", C.c_double), ("max_entries", C.c_int32), ("max_iters", C.c_int32)]
+
+
+class Mcl(C.Structure):               # selhip_mcl_t: two device arrays (d_cluster may be NULL) and three host pointers (each may be NULL)
+    _fields_ = [("d_label", C.c_void_p), ("d_cluster", C.c_void_p), ("n_clusters", C.POINTER(C.c_int64)), ("iters", C.POINTER(C.c_int64)),
+                ("chaos", C.POINTER(C.c_double))]
+
+
 class Linkage(C.Structure):           # selhip_linkage_t: the two outputs of selhip_ctx_linkage, device pointers or NULL
     _fields_ = [("d_merges", C.c_void_p), ("d_size", C.c_void_p)]
 
@@ -167,6 +176,8 @@ HIP_SYMBOLS = {
     "selhip_spanning_forest": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64), _vp]),
     "selhip_ctx_adjacency": (_i, [_vp, _i, _d, C.POINTER(Csr), _i64, C.POINTER(_i64)]),
     "selhip_adjacency": (_i, [_vp, _vp, _i64, _i64, _i64, _i, _d, C.POINTER(Csr), _i64, C.POINTER(_i64), C.POINTER(_i64), _vp]),
+    "selhip_ctx_mcl": (_i, [_vp, _d, C.POINTER(MclParams), C.POINTER(Mcl)]),
+    "selhip_mcl": (_i, [C.POINTER(Csr), _i64, _i64, C.POINTER(MclParams), C.POINTER(Mcl), _vp]),
     "selhip_ctx_linkage": (_i, [_vp, _i, _i, _d, C.POINTER(Linkage), C.POINTER(_i64)]),
     "selhip_linkage": (_i, [_vp, _i64, _i64, _i, _d, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64), _vp]),
     "selhip_ctx_neighbor_joining": (_i, [_vp, _i, _vp, C.POINTER(_i64)]),

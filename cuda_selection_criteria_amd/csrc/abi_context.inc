@@ -58,6 +58,7 @@ void selhip_ctx_destroy(selhip_ctx* c) {
     release_topk(c);
     c->gs.release();
     c->adj.release();
+    c->mcl.release();
     release_merge(c);
     if (c->h_pc) (void)hipHostFree(c->h_pc);
     if (c->st_stage1) {
@@ -312,6 +313,9 @@ int selhip_ctx_get_param(const selhip_ctx* c, const char* name, int* value) {
     if (!std::strcmp(name, "adjacency_mid_rows_last"))  { *value = c->adjacency_mid_rows_last; return SELHIP_OK; }  // ... the rows its one-workgroup kernel sorted in LDS
     if (!std::strcmp(name, "adjacency_long_rows_last")) { *value = c->adjacency_long_rows_last; return SELHIP_OK; } // ... and the rows that took the long route
     if (!std::strcmp(name, "last_was_query"))           { *value = c->have_run && c->last_was_query ? 1 : 0; return SELHIP_OK; }   // the result list held is a query pass's (n_q x n_d ranks)
+    if (!std::strcmp(name, "mcl_iters_last"))           { *value = c->mcl_iters_last; return SELHIP_OK; }           // iterations of the last selhip_ctx_mcl call, -1 = none yet
+    if (!std::strcmp(name, "mcl_clusters_last"))        { *value = c->mcl_clusters_last; return SELHIP_OK; }        // ... its clusters
+    if (!std::strcmp(name, "mcl_kclass_last"))          { *value = c->mcl_kclass_last; return SELHIP_OK; }          // ... the class of its step kernel: 0 (K <= 8), 1 (K <= 32), 2 (K <= 64)
     if (!std::strcmp(name, "adjacency_lds_cap"))        { *value = kAdjLdsCap; return SELHIP_OK; }                  // longest segment sorted in LDS
     if (!std::strcmp(name, "small_pass_used"))  { *value = c->small_used ? 1 : 0; return SELHIP_OK; }
     if (!std::strcmp(name, "pairs_route_used")) { *value = c->pairs_route_used; return SELHIP_OK; }         // list passes: 1 signature, 0 direct, 2 no smh_a stage, -1 none yet

@@ -133,6 +133,25 @@ struct AdjScratch {
     void release() { words.release(); off.release(); key.release(); key2.release(); col.release(); col2.release(); tmp.release(); bad.release(); }
 };
 
+// scratch of the Markov clustering (kernel_mcl.cuh, host_mcl.hpp): selhip_ctx_mcl keeps one, selhip_mcl owns one per call
+struct MclScratch {
+    DevBuf<int> row[2], cnt[2];         // the two flow buffers: [n * K] rows ascending inside a column, [n] entries in use
+    DevBuf<double> val[2];              // ... [n * K] values
+    DevBuf<u64> chaos;                  // the chaos image of the iteration in flight and of the next: two slots, taken in turn
+    DevBuf<ClusterBad> bad;             // what the input check refused: entries, rows
+    DevBuf<int> parent, label;          // the union-find forest of the final matrix; the labels where the caller takes none
+    DevBuf<uint32_t> flag, ids;         // root flags, their exclusive scan (one slot past the last vertex: the number of clusters)
+    DevBuf<char> tmp;                   // rocPRIM scan scratch
+    DevBuf<int64_t> csr_row;            // selhip_ctx_mcl: the symmetric adjacency of the list held
+    DevBuf<int32_t> csr_col;
+    DevBuf<double> csr_val;
+    void release() {
+        for (int b = 0; b < 2; ++b) { row[b].release(); cnt[b].release(); val[b].release(); }
+        chaos.release(); bad.release(); parent.release(); label.release(); flag.release(); ids.release(); tmp.release();
+        csr_row.release(); csr_col.release(); csr_val.release();
+    }
+};
+
 // TWO sets of per_set counter blocks: pass k uses set k & 1 and its first kernel clears the other for pass k + 1 -- no memset dispatch
 // on the stream in steady state.  dirty: a pass claimed a set and did not get to the end of its enqueue (its first kernel may never have
 // run), or nothing has cleared the buffer yet, or the stream changed behind the clearing: the next claim clears both sets first, once
@@ -172,8 +191,8 @@ static_assert(kCounterBlocks == kMaxChunks + 1, "common.cuh: counter blocks per 
 constexpr int kMaxAuxP = SELHIP_MAX_AUX_P;   // auxiliary HLL precision accepted by every entry point: aux_fused_kernel counts in 16-bit bins (a bin holds up to 2^p_aux)
 constexpr long long kEnumPairs = 1ll << 26;    // hll_a / hll_an as first criterion: pairs listed per sub-pass (512 MiB of int2)
 
-enum { T_PREP = 0, T_STAGE1, T_HIST, T_SELECT, T_TOTAL, T_SIGBUILD, T_JOIN, T_VERIFY, T_AUX, T_GROUP, T_DENSE, T_TOPK, T_MATRIX, T_MATRIX_SMH, T_CLUSTER, T_GREEDY, T_MERGE, T_FOREST, T_LINKAGE, T_NJ, T_GATHER_MASK, T_GATHER_PICK, T_ADJACENCY, T_COUNT };
-const char* kTimerNames[T_COUNT] = {"prep", "stage1", "hist", "select", "total", "sigbuild", "join", "verify", "aux", "group", "dense", "topk", "matrix", "matrix_smh", "cluster", "greedy", "merge", "forest", "linkage", "nj", "gather_mask", "gather_pick", "adjacency"};
+enum { T_PREP = 0, T_STAGE1, T_HIST, T_SELECT, T_TOTAL, T_SIGBUILD, T_JOIN, T_VERIFY, T_AUX, T_GROUP, T_DENSE, T_TOPK, T_MATRIX, T_MATRIX_SMH, T_CLUSTER, T_GREEDY, T_MERGE, T_FOREST, T_LINKAGE, T_NJ, T_GATHER_MASK, T_GATHER_PICK, T_ADJACENCY, T_MCL, T_COUNT };
+const char* kTimerNames[T_COUNT] = {"prep", "stage1", "hist", "select", "total", "sigbuild", "join", "verify", "aux", "group", "dense", "topk", "matrix", "matrix_smh", "cluster", "greedy", "merge", "forest", "linkage", "nj", "gather_mask", "gather_pick", "adjacency", "mcl"};
 
 }  // namespace
 
@@ -416,6 +435,11 @@ struct selhip_ctx {
     // ("adjacency_nnz_last", clipped to 2^31 - 1) and the rows its block and long kernels took ("adjacency_mid_rows_last" / "_long_rows_last"); -1 = none yet
     AdjScratch adj;
     int adjacency_nnz_last = -1, adjacency_mid_rows_last = -1, adjacency_long_rows_last = -1;
+
+    // the Markov clustering (selhip_ctx_mcl; kernel_mcl.cuh, host_mcl.hpp): its scratch, and of the last call the iterations, the clusters
+    // and the kernel class ("mcl_iters_last" / "mcl_clusters_last" / "mcl_kclass_last"); -1 = none yet
+    MclScratch mcl;
+    int mcl_iters_last = -1, mcl_clusters_last = -1, mcl_kclass_last = -1;
 
     // sketches merged by group (selhip_ctx_merge_groups; kernel_merge.cuh, host_merge.hpp): scratch the call owns
     MergeScratch mg;

@@ -65,6 +65,9 @@
 //                       per query that runs every pick round in one launch over masks staged word-major in LDS
 //   kernel_adjacency.cuh sparse adjacency (CSR) of a record list: entries grouped by row (count, scan, scatter), every row's segment sorted by
 //                       column with duplicates merged -- one wave, one workgroup in LDS, or a column-range split by segment length --, compaction
+//   kernel_mcl.cuh      Markov clustering of a symmetric CSR graph: the flow matrix in an ELL layout of K slots per column, one launch per iteration --
+//                       per column the products sorted by (row, source), run sums in source order, inflation, pruning, the K best, normalisation
+//                       and chaos -- by K one wave in registers or one workgroup in LDS; the labels through the union-find of kernel_graph.cuh
 //   kernel_merge.cuh    sketches merged by group: a counting sort of the members, then a segmented reduction of the rows (u8 maximum of the
 //                       HLL registers, u64 minimum of the SuperMinHash buckets) in segments of at most SELHIP_MERGE_SEGMENT members per level
 //
@@ -125,6 +128,7 @@
 #include "kernel_nj.cuh"          // (behind kernel_linkage.cuh: kLkTile, lk_distance_kernel)
 #include "kernel_merge.cuh"
 #include "kernel_adjacency.cuh"   // (behind kernel_topk.cuh and kernel_graph.cuh: key(J), the tile size, ClusterBad)
+#include "kernel_mcl.cuh"         // (behind kernel_graph.cuh and kernel_adjacency.cuh: ClusterBad, graph_image, adj_init_kernel)
 
 #include "host_plan.hpp"         // host decisions that are plain arithmetic: build shape, pass plan, criterion constants, overflow rule
 #include "kernel_matrix.cuh"     // (behind host_plan.hpp: the kernel reads the unit, slab and mirror rules written there)
@@ -140,6 +144,7 @@
 #include "host_greedy.hpp"       // greedy representative clusters: rounds and launches behind selhip_ctx_cluster_greedy / selhip_greedy_representatives
 #include "host_forest.hpp"       // maximum spanning forest: rounds, sort and launches behind selhip_ctx_spanning_forest / selhip_spanning_forest
 #include "host_adjacency.hpp"    // sparse adjacency: scratch, the chain of launches and the checks behind selhip_ctx_adjacency / selhip_adjacency
+#include "host_mcl.hpp"          // Markov clustering: parameters, scratch, the iteration loop and the labels behind selhip_ctx_mcl / selhip_mcl
 #include "host_linkage.hpp"      // dense-matrix hierarchy: checks, scratch and rounds behind selhip_linkage / selhip_ctx_linkage
 #include "host_nj.hpp"           // neighbour-joining tree: checks, scratch and joins behind selhip_neighbor_joining / selhip_ctx_neighbor_joining
 #include "host_gather.hpp"       // winner-takes-all screen: checks, scratch and launches behind selhip_gather / selhip_ctx_gather
@@ -153,6 +158,7 @@
 #include "abi_greedy.inc"        // C ABI: greedy representative clusters of the result list (cluster_greedy) and of a caller's edge list (greedy_representatives)
 #include "abi_forest.inc"        // C ABI: maximum spanning forest of the result list (ctx_spanning_forest) and of a caller's edge list (spanning_forest)
 #include "abi_adjacency.inc"     // C ABI: sparse adjacency (CSR) of the result list (ctx_adjacency) and of a caller's entry list (adjacency)
+#include "abi_mcl.inc"           // C ABI: Markov clustering of the result list (ctx_mcl) and of a caller's CSR matrix (mcl)
 #include "abi_linkage.inc"       // C ABI: average / complete / weighted / single linkage of a dense matrix (ctx_linkage, linkage)
 #include "abi_nj.inc"            // C ABI: neighbour-joining tree of a dense matrix (ctx_neighbor_joining, neighbor_joining)
 #include "abi_gather.inc"        // C ABI: winner-takes-all screen of the queries against the database (ctx_gather, gather)

@@ -13,7 +13,7 @@ import numpy as np
 from . import _lib
 from ._lib import (ALGO_AUTO, BANDING_CPU, CRIT_HLL_A, CRIT_HLL_AN, CRIT_HLL_A_SMH_A, CRIT_NONE, CRIT_SMH_A, CRIT_SMH_C, ESTIMATOR_HLL, ESTIMATOR_SMH, F32, F64, FP_FMA,
                    MEASURE_CONTAINMENT, MEASURE_INTERSECTION, MEASURE_JACCARD, MEASURE_MAX_CONTAINMENT, MEASURE_SMH_JACCARD,
-                   MEASURE_SMH_MATCHES, MEASURE_UNION, MODE_CB_SMH, REP_MAX_DEGREE, REP_MAX_RANK, REP_MIN_RANK, REP_PRIORITY, TOPK_ROUNDS_AUTO, LINKAGE_SINGLE, LINKAGE_COMPLETE, LINKAGE_AVERAGE, LINKAGE_WEIGHTED, ADJ_DIRECTED, ADJ_SYMMETRIC, Clusters, Csr, Forest, Greedy, Linkage, Merged, Pair, check, hip_lib,
+                   MEASURE_SMH_MATCHES, MEASURE_UNION, MODE_CB_SMH, REP_MAX_DEGREE, REP_MAX_RANK, REP_MIN_RANK, REP_PRIORITY, TOPK_ROUNDS_AUTO, LINKAGE_SINGLE, LINKAGE_COMPLETE, LINKAGE_AVERAGE, LINKAGE_WEIGHTED, ADJ_DIRECTED, ADJ_SYMMETRIC, Clusters, Csr, Forest, Greedy, Linkage, Mcl, MclParams, Merged, Pair, check, hip_lib,
                    host_lib)
 
 # layout of selhip_pair_t {int32 i, k; double jaccard}
@@ -629,6 +629,23 @@ class Selector:
               self._ctx)
         return _adjacency_result(row_ptr, col, val, int(nnz.value), (n_rows, self.n), to_torch, {})
 
+    def mcl(self, min_value: Optional[float] = None, inflation: float = 2.0, max_entries: int = 32, prune: float = 1e-4, max_iters: int = 64,
+            chaos_tol: float = 1e-3, to_host: bool = True) -> dict:
+        """Markov clustering (MCL) of the result list the context holds, computed on the device (selhip_ctx_mcl): the symmetric adjacency
+        of the records with value >= min_value (None: every record) is the similarity graph; expansion, inflation by `inflation`,
+        pruning below `prune` times a column's largest value and a cut to the `max_entries` (1 .. 64) best entries per column, until
+        the chaos falls to `chaos_tol` or for `max_iters` iterations (include/selection_hip.h section 2o is the definition).  Unlike
+        Selector.cluster it does not chain through a weak bridge record.  Returns a dict: "label" [n] int32 (smallest rank of the
+        cluster) and "cluster" [n] int32 (dense id by ascending label) -- numpy arrays, with to_host=False torch tensors on the device --,
+        "n_clusters", "iters" and "chaos" (of the last iteration)"""
+        import torch
+        dev = torch.device("cuda", self.device)
+        label = torch.empty(self.n, dtype=torch.int32, device=dev)
+        cluster = torch.empty(self.n, dtype=torch.int32, device=dev)
+        params, out, scalars = _mcl_arguments(label, cluster, inflation, max_entries, prune, max_iters, chaos_tol)
+        check(self._lib.selhip_ctx_mcl(self._ctx, float("-inf") if min_value is None else float(min_value), C.byref(params), C.byref(out)), self._ctx)
+        return _mcl_result(label, cluster, scalars, to_host)
+
     # -- hierarchy of the dense matrix ------------------------------------------------------------------
     def linkage(self, measure="jaccard", method="average", max_height: Optional[float] = None, distance=None, to_host: bool = True) -> dict:
         """the agglomerative hierarchy of the context's set under the distance 1 - measure, computed on the device from the dense
@@ -1130,6 +1147,50 @@ def adjacency(pairs, n_rows: int, n_cols: Optional[int] = None, values=None, for
                                    int(pairs.shape[0]), n_rows, n_cols, code, float("-inf") if min_value is None else float(min_value), C.byref(out), bound,
                                    C.byref(nnz), C.byref(long_rows), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
     return _adjacency_result(row_ptr, col, val, int(nnz.value), (n_rows, n_cols), to_torch, {"long_rows": int(long_rows.value)})
+
+
+def _mcl_arguments(label, cluster, inflation, max_entries, prune, max_iters, chaos_tol):
+    """the two structs of selhip_ctx_mcl / selhip_mcl over the device tensors `label` and `cluster`, and the three host scalars they fill"""
+    scalars = (C.c_int64(0), C.c_int64(0), C.c_double(0.0))
+    params = MclParams(float(inflation), float(prune), float(chaos_tol), int(max_entries), int(max_iters))
+    out = Mcl(label.data_ptr() if label.numel() else None, cluster.data_ptr() if cluster.numel() else None, C.pointer(scalars[0]), C.pointer(scalars[1]),
+              C.pointer(scalars[2]))
+    return params, out, scalars
+
+
+def _mcl_result(label, cluster, scalars, to_host: bool) -> dict:
+    res = {"label": label, "cluster": cluster}
+    if to_host:
+        res = {k: v.cpu().numpy() for k, v in res.items()}
+    res.update(n_clusters=int(scalars[0].value), iters=int(scalars[1].value), chaos=float(scalars[2].value))
+    return res
+
+
+def mcl(row_ptr, col, val, n: int, inflation: float = 2.0, max_entries: int = 32, prune: float = 1e-4, max_iters: int = 64, chaos_tol: float = 1e-3,
+        device: int = 0, to_host: bool = True) -> dict:
+    """Markov clustering of Selector.mcl over a caller's symmetric n x n CSR matrix, computed on the device (selhip_mcl): row_ptr [n + 1]
+    int64, col [nnz] int32 strictly ascending per row, val [nnz] float64, finite and >= 0 -- numpy arrays or torch device tensors, the
+    form adjacency(..., form="symmetric", to_torch=False) returns.  A negative or non-finite value or a column out of range raises
+    (SELHIP_E_BADARG) and nothing is computed.  Returns the dict of Selector.mcl"""
+    import torch
+    lib = hip_lib()
+    dev = torch.device("cuda", device)
+
+    def on_device(a, dtype, np_dtype):
+        t = a if hasattr(a, "data_ptr") else torch.from_numpy(np.ascontiguousarray(a, dtype=np_dtype)).to(dev)
+        assert t.is_cuda and t.is_contiguous() and t.dtype == dtype and t.dim() == 1, "row_ptr int64, col int32, val float64: flat arrays"
+        return t
+    n = int(n)
+    row_ptr, col, val = on_device(row_ptr, torch.int64, np.int64), on_device(col, torch.int32, np.int32), on_device(val, torch.float64, np.float64)
+    assert row_ptr.numel() == max(n, 0) + 1 and col.numel() == val.numel(), "row_ptr: n + 1 offsets; col and val: nnz entries each"
+    nnz = int(col.numel())
+    with torch.cuda.device(dev):
+        label = torch.empty(max(n, 0), dtype=torch.int32, device=dev)
+        cluster = torch.empty(max(n, 0), dtype=torch.int32, device=dev)
+        params, out, scalars = _mcl_arguments(label, cluster, inflation, max_entries, prune, max_iters, chaos_tol)
+        csr = Csr(row_ptr.data_ptr(), col.data_ptr() if nnz else None, val.data_ptr() if nnz else None)
+        check(lib.selhip_mcl(C.byref(csr), n, nnz, C.byref(params), C.byref(out), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return _mcl_result(label, cluster, scalars, to_host)
 
 
 def forest_cluster_counts(edges, n: int, thresholds) -> np.ndarray:

@@ -1178,6 +1178,79 @@ int selhip_ctx_adjacency(selhip_ctx* ctx, int form, double min_value, const selh
 
 
 /* ---------------------------------------------------------------------------------------------------
+ * 2o. Markov clustering (van Dongen's MCL: expansion, inflation, pruning) of the similarity graph, on the device: the consumer of 2n's
+ *     symmetric matrix.  Single linkage (2g, 2j) chains through one weak bridge record; MCL is the standard answer to that, the default
+ *     for protein families (OrthoMCL, TribeMCL) and common for genome and plasmid dereplication.
+ *     THE DEFINITION -- the kernels (csrc/kernel_mcl.cuh) and the tests' model (tests/mcl_model.py) follow it.
+ *     INPUT.  An n x n CSR matrix in the form SELHIP_ADJ_SYMMETRIC produces: row_ptr int64, col int32 strictly ascending per row, val
+ *     f64 (required).  It is symmetric, so row j is column j of the flow matrix.  Every value must be finite and >= 0, every column in
+ *     [0, n) and above its predecessor's in the row, the offsets ascending from 0 to nnz: otherwise SELHIP_E_BADARG with the number of
+ *     bad entries (or rows) and the index of one, nothing is written and nothing outside the arrays is touched -- checked on the
+ *     device (an entry that fails two of these is counted twice).  Symmetry itself is not checked: the flow of an asymmetric matrix is
+ *     that of its rows read as columns.  Entries of value 0 and diagonal entries are ignored.
+ *     PARAMETERS, selhip_mcl_params_t; a field of 0, or a NULL struct, takes the default -- part of the definition, not measurements:
+ *     inflation r, f64 > 1 and finite (2.0); max_entries K, 1 .. SELHIP_MCL_MAX_ENTRIES = 64 (32); prune, f64 in [0, 1) (1e-4);
+ *     max_iters >= 1 (64); chaos_tol > 0 (1e-3).  Anything else, a NaN included, is SELHIP_E_BADARG.
+ *     BEST.  Of two entries of a column the one with the greater value; equal values: the one in the smaller row.
+ *     START.  Column j = the entries of input row j plus the self loop (j, the largest value of that row; 1.0 for a row without
+ *     entries), cut to its K best and normalised (below).
+ *     ONE ITERATION, column j with the entries (k_s, w_s), s ascending with k:
+ *       expansion       x_i = sum over s of M[i, k_s] * w_s: each product rounded on its own, the products added one after the other in
+ *                       ascending s (no fused multiply-add, no other grouping)
+ *       inflation       x * x when r == 2.0 exactly, pow(x, r) otherwise
+ *       pruning         entries below prune * (the column's largest inflated value) are dropped; the largest always stays
+ *       cut             the K best stay
+ *       normalisation   s = the sum in ascending row order, one addition after the other; every entry becomes x / s
+ *     STOPPING.  The chaos of a column is max_i x_i - sum_i x_i * x_i (the sum in ascending row order), the chaos of the matrix the
+ *     maximum over its columns.  The loop stops behind the first iteration whose chaos is <= chaos_tol, or behind max_iters.
+ *     RESULT, selhip_mcl_t.  The clusters are the connected components of the undirected graph with an edge {i, j} for every stored
+ *     entry (i, j) of the final matrix (attractors with what they attract, overlaps merged).  d_label[n] int32 (device): the smallest
+ *     vertex of the component; d_cluster[n] int32 (device, may be NULL): the dense id by ascending label; n_clusters, iters, chaos
+ *     (HOST pointers, each may be NULL): the clusters, the iterations run and the last iteration's chaos.  With r == 2.0 every output is
+ *     a pure function of the input, bit for bit, whatever order the device worked in; with another r up to the platform's pow.
+ *     selhip_ctx_mcl takes the symmetric adjacency of the list the context holds at min_value -- through 2n's code, its scratch and
+ *     CSR arrays the context keeps -- and runs the same loop: it accepts and refuses the lists the symmetric form of
+ *     selhip_ctx_adjacency does (SELHIP_E_STATE behind a query pass, before any pass, while one is pending; a NaN min_value is
+ *     SELHIP_E_BADARG; a list with a negative value, as an intersection estimate can be, is SELHIP_E_BADARG).  The list, the
+ *     statistics, the settings, 2n's "adjacency_*_last" and the caches are as they were; a context that never calls it launches what
+ *     it always did.  selhip_mcl (section 3) takes a caller's matrix and owns its scratch.
+ *     STREAM.  Every launch and copy runs on the stream, in stream order.  The host waits once for the input check, reads the 8-byte
+ *     chaos once per iteration (that read decides whether another iteration is enqueued), and waits once behind the labels.
+ *     get_param "mcl_iters_last" / "mcl_clusters_last": of the last selhip_ctx_mcl call; "mcl_kclass_last": the class of the step kernel it
+ *     ran, 0 / 1 / 2, -1 where it ran none (a context without genomes); all -1 = no call yet.  Timed as "mcl" in selhip_ctx_kernel_ms: per call, adjacency included, counted apart from the passes.
+ *     HOW.  The flow matrix is an ELL array of K slots per column, (int32 row, f64 value) with the rows ascending, and a count per
+ *     column; two such buffers alternate (24 n K bytes), nothing is allocated or counted ahead inside the loop.  One launch is one
+ *     whole iteration.  Per column the at most K * K products get the key (row, source slot, entry) and are sorted by it -- a sort,
+ *     not a K-way merge: its cost follows the products there are, and its order is the order of the additions --, the lane at the head
+ *     of a run of equal rows adds its run, inflates, and a second sort by "best" leaves the survivors of pruning and cut in front;
+ *     they are ranked by row, added, divided and written with the column's chaos, whose maximum is an integer atomic over an
+ *     order-preserving image.  By K: K <= 8 one wave per column, 64 products in registers, cross-lane moves, no LDS; K <= 32 one
+ *     workgroup of 256, 1 024 products, 14 092 bytes of LDS; K <= 64 one workgroup of 512, 4 096 products, 50 956 bytes of LDS (12 bytes
+ *     per product and 1 804 for the column).  The start orders a row of up to 4 095 entries in LDS (50 956 bytes); a longer row takes
+ *     K rounds of two passes over global memory, which is there for correctness only.  The labels: the final entries as edges through
+ *     the union-find of 2g, the dense ids from its scan.
+ *     Not built: a command-line flag; a host twin; query passes; more than one device; K above 64; overlapping-cluster output; MCL's
+ *     recovery and selection resource schemes; entries in the stream, reuse and thread harnesses of the test-suite.
+ * --------------------------------------------------------------------------------------------------- */
+#define SELHIP_MCL_MAX_ENTRIES 64
+typedef struct {
+    double  inflation;       /* r; 0 = 2.0                                                           */
+    double  prune;           /* 0 = 1e-4                                                             */
+    double  chaos_tol;       /* 0 = 1e-3                                                             */
+    int32_t max_entries;     /* K; 0 = 32                                                            */
+    int32_t max_iters;       /* 0 = 64                                                               */
+} selhip_mcl_params_t;
+typedef struct {
+    int32_t* d_label;        /* [n], device                                                          */
+    int32_t* d_cluster;      /* [n], device, or NULL                                                 */
+    int64_t* n_clusters;     /* host, or NULL                                                        */
+    int64_t* iters;          /* host, or NULL                                                        */
+    double*  chaos;          /* host, or NULL                                                        */
+} selhip_mcl_t;
+int selhip_ctx_mcl(selhip_ctx* ctx, double min_value, const selhip_mcl_params_t* params, const selhip_mcl_t* out);
+
+
+/* ---------------------------------------------------------------------------------------------------
  * 3. Building blocks (device pointers), used by the launchers above and exposed for tests.
  * --------------------------------------------------------------------------------------------------- */
 /* smh_a on an explicit pair list: d_flags[j] = 1 iff pair j has a fully equal band. */
@@ -1242,6 +1315,12 @@ int selhip_spanning_forest(const selhip_int2_t* d_pairs, const double* d_values,
  * only.  The call owns its scratch and waits for the stream. */
 int selhip_adjacency(const selhip_int2_t* d_pairs, const double* d_values, int64_t n_pairs, int64_t n_rows, int64_t n_cols, int form,
                      double min_value, const selhip_csr_t* out, int64_t cap, int64_t* nnz_out, int64_t* long_rows_out, void* hip_stream);
+/* Markov clustering (section 2o; csrc/kernel_mcl.cuh) of a caller's symmetric CSR matrix in device memory: adj->d_row_ptr[n + 1],
+ * adj->d_col[nnz], adj->d_val[nnz] (8 / 4 / 8-byte aligned; d_col and d_val may be NULL where nnz == 0).  Input, parameters, result and
+ * SELHIP_E_BADARG are section 2o's; 0 <= n <= 2^31 - 1, 0 <= nnz.  n == 0 writes n_clusters = iters = 0 and chaos = 0.0; nnz == 0 gives
+ * n singletons behind one iteration.  SELHIP_E_NOMEM: no room for the two flow buffers (24 n K bytes).  The call owns its scratch, works
+ * in stream order on hip_stream, reads the 8-byte chaos once per iteration and returns when the outputs are complete. */
+int selhip_mcl(const selhip_csr_t* adj, int64_t n, int64_t nnz, const selhip_mcl_params_t* params, const selhip_mcl_t* out, void* hip_stream);
 /* The hierarchy of section 2k over a caller's distance matrix d_dist[n][ld] (device memory, f64, 8-byte aligned, ld >= n counted in
  * elements), which the call works on and CONSUMES: its contents afterwards are unspecified.  With an even ld and a 16-byte aligned
  * base the row scan takes 16-byte loads, otherwise 8-byte ones; the results are the same.  d_merges (max(n - 1, 0) records, 16-byte
