@@ -131,16 +131,17 @@ hipError_t launch_count(selhip_ctx* c, hipStream_t st, const CountSets& a, const
     // a round of a top-k pass in row rounds: the TOPK form, whose operand rides behind the emit form's
     const bool topk = !QUERY && emit && c->rd.on;
     const SmhcRuleEmitTopk rule_tk{rule_em, c->topk_thr.p};
-    // the kernel of smhc_kind(m); the generic one instead under "smhc_generic", and -- for the narrow and the wide kernel, which have
-    // no round form and load 16 bytes per lane -- in a round of a top-k pass and for a base pointer off the 16-byte grid (attach refuses
-    // such pointers and uploads allocate their own: a guard, not a route)
+    // the kernel of smhc_kind(m), a round of a top-k pass included; the generic one instead under "smhc_generic", and -- for the narrow
+    // and the wide kernel, which load 16 bytes per lane -- for a base pointer off the 16-byte grid (attach refuses such pointers and
+    // uploads allocate their own: a guard, not a route)
     const bool aligned = !((reinterpret_cast<uintptr_t>(a.X) | reinterpret_cast<uintptr_t>(a.Y)) & 15);
     int kind = c->smhc_generic ? kSmhcGeneric : smhc_kind(m);
-    if ((kind == kSmhcNarrow || kind == kSmhcWide) && (topk || !aligned)) kind = kSmhcGeneric;
+    if ((kind == kSmhcNarrow || kind == kSmhcWide) && !aligned) kind = kSmhcGeneric;
     c->smhc_kernel_used = kind;
     c->smhc_path_used = kind == kSmhcTile ? 1 : 0;
     if (kind == kSmhcNarrow || kind == kSmhcWide) {
-        const long long n_tiles = rm.n_tiles(kind == kSmhcNarrow ? smhc_narrow_q(emit, cont) : kWavesPerBlock * kSmhcWideQ);
+        // (the round form of the narrow kernel holds fewer rows: its tiles are sized with that Q)
+        const long long n_tiles = rm.n_tiles(kind == kSmhcNarrow ? smhc_narrow_q(emit, cont, topk) : kWavesPerBlock * kSmhcWideQ);
         if (n_tiles > 0x7FFFFFFFll) return hipErrorInvalidValue;
         const int chunk_base = (first_cand / kChunk) * kChunk;
         const int n_chunks = (a.n_y - chunk_base + kChunk - 1) / kChunk;
@@ -149,6 +150,23 @@ hipError_t launch_count(selhip_ctx* c, hipStream_t st, const CountSets& a, const
         if (blocks > 0x7FFFFFFFll) return hipErrorInvalidValue;
         const u64x2* const X2 = reinterpret_cast<const u64x2*>(a.X);
         const u64x2* const Y2 = reinterpret_cast<const u64x2*>(a.Y);
+        if constexpr (!QUERY) {
+            if (topk) {                                // a round: the TOPK forms, the records into the result list, thr behind the emit operands
+                with_flag(cont, [&](auto C) {
+                    constexpr int RULE = decltype(C)::value ? kSmhcContainment : kSmhcFixed;
+                    if (kind == kSmhcWide)
+                        hipLaunchKernelGGL((smh_count_wide_kernel<false, RULE, true, true>), dim3((unsigned)blocks), dim3(kBlock), 0, st, X2, Y2, a.n_x, a.n_y,
+                                           m / (2 * kWave * kSmhcWideNch), a.lo, a.hi, a.pc_in, rm, (int)n_tiles, chunk_base, c_min, res, res_cap, pc, rule_tk);
+                    else if (m == 64)
+                        hipLaunchKernelGGL((smh_count_narrow_kernel<2, false, RULE, true, true>), dim3((unsigned)blocks), dim3(kBlock), 0, st, X2, Y2, a.n_x, a.n_y,
+                                           a.lo, a.hi, a.pc_in, rm, (int)n_tiles, chunk_base, c_min, res, res_cap, pc, rule_tk);
+                    else
+                        hipLaunchKernelGGL((smh_count_narrow_kernel<4, false, RULE, true, true>), dim3((unsigned)blocks), dim3(kBlock), 0, st, X2, Y2, a.n_x, a.n_y,
+                                           a.lo, a.hi, a.pc_in, rm, (int)n_tiles, chunk_base, c_min, res, res_cap, pc, rule_tk);
+                });
+                return hipGetLastError();
+            }
+        }
         with_flag(cont, [&](auto C) { with_flag(emit, [&](auto E) {
             constexpr int RULE = decltype(C)::value ? kSmhcContainment : kSmhcFixed;
             constexpr bool EMIT = decltype(E)::value;

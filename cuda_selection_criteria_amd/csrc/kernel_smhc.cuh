@@ -6,12 +6,12 @@
 // row-major, as uploaded or attached: for a count any lane <-> bucket map does, as long as both rows of a pair use the same one
 // (DESIGN.md section 14), so there is no interleaved copy as in ALGO_STREAM.
 //   smh_count_kernel<NCH, QUERY, RULE, EMIT, TOPK>  m = 128 * NCH buckets, NCH in {1, 2, 4, 8} (smhc_fast): smh_stream_kernel's block shape and enumeration
-//   smh_count_narrow_kernel<G, QUERY, RULE, EMIT>   m = 128 / G buckets, G in {2, 4}: the same block and enumeration, a wave load = G consecutive
+//   smh_count_narrow_kernel<G, QUERY, RULE, EMIT, TOPK> m = 128 / G buckets, G in {2, 4}: the same block and enumeration, a wave load = G consecutive
 //                                                    candidate rows, the G counts split from two ballots on the scalar unit
-//   smh_count_wide_kernel<QUERY, RULE, EMIT>        m = 1024 C buckets, C = 2 .. 8: the same block, the chunk walked in spans of 64 candidates, the
+//   smh_count_wide_kernel<QUERY, RULE, EMIT, TOPK>  m = 1024 C buckets, C = 2 .. 8: the same block, the chunk walked in spans of 64 candidates, the
 //                                                    buckets in C chunks of 1 024 with a running total per (row, lane = candidate) (section 37)
 //   smh_count_generic_kernel<QUERY, RULE, EMIT, TOPK> every other m > 0: smh_generic_kernel's unit, lane = candidate, a serial loop over the buckets;
-//                                                    also every m under "smhc_generic", and the round form (TOPK) of the narrow and wide m
+//                                                    also every m under "smhc_generic"
 // (smhc_kind(m) says which; the narrow and the wide kernel count with matrix_smh_narrow_counts / matrix_smh_chunk_count of kernel_matrix_smh.cuh)
 // QUERY = false: the all-pairs pass (rows and candidates from one set, the window of row i is [max(i + 1, z0), hi[i]], records (i, k));
 // QUERY = true: the query pass (rows from Q, candidates from D, the window of query i is [lo[i], hi[i]] of query_windows_kernel, records
@@ -27,10 +27,13 @@
 //     V = selhip::smh_value(measure, m, c, e_i, e_k) >= tau                                (pair_value.hpp)
 // and goes as the 16-byte record {i, k, V} into the RESULT list behind n_results: the pass has no stage 2.  Query records carry the
 // database rank k itself (the index space query_result_fixup_kernel restores for the other criteria).
-// TOPK (the last template argument of the two count kernels, false = the kernels as they were before it existed, instruction for
+// TOPK (the last template argument of all four count kernels, false = the kernels as they were before it existed, instruction for
 // instruction; QUERY = false, EMIT = true only): one round of an all-pairs top-k pass in row rounds (selhip_ctx_set_topk_rounds, DESIGN.md
 // section 19).  A pair with V >= tau is COUNTED in n_final -- the |S| of the one-shot pass -- and its record is appended only if it is
 // ADMITTED: V >= thr[i] || V >= thr[k], thr[g] the value of genome g's K-th best record so far (-inf while it holds fewer than K).
+// Where the thresholds live: the tile and the generic kernel read both behind the branch; the narrow kernel keeps thr[i] of its tile rows
+// in SGPR pairs from block start and reads thr[k] behind the branch; the wide kernel, whose lanes are candidates, keeps thr[i] of a
+// wave's rows in SGPR pairs and fetches thr[k] per lane, one coalesced load a span.
 #pragma once
 
 // v_writelane_b32 for the wide kernel's running totals: kernel_matrix_smh.cuh's declaration, word for word (that header comes later in
@@ -100,6 +103,12 @@ __device__ __forceinline__ void smhc_tally(u64* __restrict__ n_survivors, int n_
 // THE admission test of a round, written once: non-strict, so that a tie with an owner's K-th value reaches the select, where the
 // partner rank decides.  Two uniform f64 loads and two compares, behind the pinned branch
 __device__ __forceinline__ bool smhc_admits(const double* __restrict__ thr, int i, int k, double v) { return v >= thr[i] || v >= thr[k]; }
+// the same test for a kernel that holds the two thresholds in registers already (narrow: thr[i] in an SGPR pair; wide: thr[k] per lane):
+// smhc_admits on a local pair, which the compiler dissolves into the two compares
+__device__ __forceinline__ bool smhc_admits_held(double thr_i, double thr_k, double v) {
+    const double held[2] = {thr_i, thr_k};
+    return smhc_admits(held, 0, 1, v);
+}
 // the exact threshold of a pair under the containment rule
 __device__ __forceinline__ int smhc_pair_threshold(int m, double gamma, u64 e1, u64 e2, int c_min) {
     return max(c_min, selhip::smhc_threshold(m, gamma, e1 < e2 ? e1 : e2, e1 < e2 ? e2 : e1));
@@ -341,15 +350,19 @@ void smh_count_generic_kernel(const u64* __restrict__ X, const u64* __restrict__
 // row on top of the G counts in flight, and 12 rows spilled SGPRs (to VGPR lanes, no scratch): 1 (m = 64) and 2 (m = 32) in the all-pairs
 // form, 14 and 15 in its emit form, 6 in the query pass's emit form -- so, as smhc_q's `tight` does, 10 rows there and 8 where the pass
 // emits as well (resource lines: DESIGN.md section 37).
+// The round form (TOPK) keeps thr[i] of every tile row in an SGPR pair on top of that, so that the admission test behind the branch reads
+// thr[k] alone.  With the emit form's rows it spilled 23 SGPRs under the fixed rule (12 rows; 9 / 10 with 10 rows, 3 / 5 with 9) and 13 / 15
+// under the containment rule (8 rows; 0 / 2 with 6): 8 rows and 5 rows there, nothing spilled.
 // ---------------------------------------------------------------------------------------------
-constexpr int smhc_narrow_q(bool emit, bool containment) { return !containment ? 12 : emit ? 8 : 10; }
-template <int G, bool QUERY, int RULE, bool EMIT = false>
+constexpr int smhc_narrow_q(bool emit, bool containment, bool topk = false) { return topk ? (containment ? 5 : 8) : !containment ? 12 : emit ? 8 : 10; }
+template <int G, bool QUERY, int RULE, bool EMIT = false, bool TOPK = false>
 __global__ __launch_bounds__(kBlock, 3)
 void smh_count_narrow_kernel(const u64x2* __restrict__ X, const u64x2* __restrict__ Y, int n_x, int n_y,
                              const int* __restrict__ lo, const int* __restrict__ hi, const PassCounters* __restrict__ pc_in,
                              RowMap rm, int n_tiles, int chunk_base, int c_min,
-                             SmhcRecord<EMIT>* __restrict__ surv, u64 surv_cap, PassCounters* __restrict__ pc, SmhcRuleArg<EMIT> rule) {
-    constexpr int Q = smhc_narrow_q(EMIT, RULE == kSmhcContainment);
+                             SmhcRecord<EMIT>* __restrict__ surv, u64 surv_cap, PassCounters* __restrict__ pc, SmhcRuleArg<EMIT, TOPK> rule) {
+    static_assert(!TOPK || (EMIT && !QUERY), "the round form is an all-pairs pass that emits");
+    constexpr int Q = smhc_narrow_q(EMIT, RULE == kSmhcContainment, TOPK);
     constexpr int LPR = kWave / G;                    // u64x2 (lanes) per sketch row: m = 2 LPR
     constexpr int M = 2 * LPR;
     __shared__ SmhcRecord<EMIT> app_lds[kWavesPerBlock * kAppendCap];
@@ -399,6 +412,12 @@ void smh_count_narrow_kernel(const u64x2* __restrict__ X, const u64x2* __restric
         }
     }
 
+    double thr_i[Q];                                                          // TOPK: the tile rows' thresholds, wave-uniform, one SGPR pair per row
+    if constexpr (TOPK) {
+#pragma unroll
+        for (int a = 0; a < Q; ++a) thr_i[a] = rule.thr[min(i0 + a, n_x - 1)];                // (uniform address: a scalar load; rows past the end as below)
+    }
+
     u64x2 q[Q];
 #pragma unroll
     for (int a = 0; a < Q; ++a) q[a] = X[(long long)min(i0 + a, n_x - 1) * LPR + sub];      // rows past the end: a valid row, never a record
@@ -407,6 +426,7 @@ void smh_count_narrow_kernel(const u64x2* __restrict__ X, const u64x2* __restric
     if constexpr (EMIT) app.init(app_lds, wave, surv, surv_cap, &rule.em.pc0->n_results);
     else app.init(app_lds, wave, surv, surv_cap, &pc->n_survivors);
     int n_pass = 0;                                                           // EMIT: pairs that passed the count test (wave-uniform)
+    int n_sel = 0;                                                            // TOPK: those of them with V >= tau (wave-uniform)
     constexpr int AHEAD = kStreamAhead;
     constexpr int RING = AHEAD + 1;
     constexpr int STEP = kWavesPerBlock * G;                                  // candidates between two loads of a wave
@@ -432,7 +452,14 @@ void smh_count_narrow_kernel(const u64x2* __restrict__ X, const u64x2* __restric
                                 n_pass += 1;
                                 bool sel;
                                 const selhip_pair_t r = smhc_record(rule.em, M, cnt[g], rule.ex[i], rule.ey[kg], i, kg, &sel);
-                                if (sel) app.push_uniform_record(r, lane);
+                                if constexpr (TOPK) {
+                                    if (sel) {
+                                        n_sel += 1;
+                                        if (smhc_admits_held(thr_i[a], rule.thr[kg], r.jaccard)) app.push_uniform_record(r, lane);
+                                    }
+                                } else {
+                                    if (sel) app.push_uniform_record(r, lane);
+                                }
                             }
                         } else {
                             if (ok) app.push_uniform(i, sp.partner(kg), lane);
@@ -455,10 +482,11 @@ void smh_count_narrow_kernel(const u64x2* __restrict__ X, const u64x2* __restric
     }
     app.flush(lane);
     if constexpr (EMIT) smhc_tally(&pc->n_survivors, n_pass, lane);
+    if constexpr (TOPK) smhc_tally(&pc->n_final, n_sel, lane);
 }
 
 // ---------------------------------------------------------------------------------------------
-// smh_count_wide_kernel<QUERY, RULE, EMIT>      m = 1024 C buckets, C = 2 .. 8 (a kernel argument): the buckets are split, not the rows
+// smh_count_wide_kernel<QUERY, RULE, EMIT, TOPK>    m = 1024 C buckets, C = 2 .. 8 (a kernel argument): the buckets are split, not the rows
 //   block  = (tile of 12 rows of X: 4 waves x Q = 3 rows) x (chunk of kChunk candidates of Y), blockIdx.x -> (tile, chunk) as above.  A
 //            wave cuts the chunk to the windows of ITS three rows and walks what is left in spans of 64 candidates
 //   span   = matrix_smh_wide_kernel's: per bucket chunk c the wave's 3 query chunks in 96 VGPRs, the span's candidate chunks streamed past
@@ -474,12 +502,13 @@ void smh_count_narrow_kernel(const u64x2* __restrict__ X, const u64x2* __restric
 // ---------------------------------------------------------------------------------------------
 constexpr int kSmhcWideNch = 8;                        // wave loads per bucket chunk: 1 024 buckets, the tile kernel's widest row
 constexpr int kSmhcWideQ = 3;                          // rows a wave keeps (one bucket chunk each): 96 VGPRs
-template <bool QUERY, int RULE, bool EMIT = false>
+template <bool QUERY, int RULE, bool EMIT = false, bool TOPK = false>
 __global__ __launch_bounds__(kBlock, 2)
 void smh_count_wide_kernel(const u64x2* __restrict__ X, const u64x2* __restrict__ Y, int n_x, int n_y, int n_bch,
                            const int* __restrict__ lo, const int* __restrict__ hi, const PassCounters* __restrict__ pc_in,
                            RowMap rm, int n_tiles, int chunk_base, int c_min,
-                           SmhcRecord<EMIT>* __restrict__ surv, u64 surv_cap, PassCounters* __restrict__ pc, SmhcRuleArg<EMIT> rule) {
+                           SmhcRecord<EMIT>* __restrict__ surv, u64 surv_cap, PassCounters* __restrict__ pc, SmhcRuleArg<EMIT, TOPK> rule) {
+    static_assert(!TOPK || (EMIT && !QUERY), "the round form is an all-pairs pass that emits");
     constexpr int NCH = kSmhcWideNch;
     constexpr int Q = kSmhcWideQ;
     constexpr int CHV = NCH * kWave;                   // u64x2 per bucket chunk of a row
@@ -516,9 +545,19 @@ void smh_count_wide_kernel(const u64x2* __restrict__ X, const u64x2* __restrict_
     if constexpr (EMIT) app.init(app_lds, wave, surv, surv_cap, &rule.em.pc0->n_results);
     else app.init(app_lds, wave, surv, surv_cap, &pc->n_survivors);
     int n_pass = 0;                                                           // EMIT: pairs that passed the count test (wave-uniform)
+    int n_sel = 0;                                                            // TOPK: those of them with V >= tau (wave-uniform)
+    double thr_i[Q];                                                          // TOPK: the wave's rows' thresholds, wave-uniform, one SGPR pair per row
+    if constexpr (TOPK) {
+#pragma unroll
+        for (int a = 0; a < Q; ++a) thr_i[a] = rule.thr[min(i0 + a, n_x - 1)];                // (uniform address: a scalar load)
+    }
 
     for (int s0 = max(k0, kmin); s0 < k_end; s0 += kWave) {                   // the span [s0, se): lane l <-> candidate s0 + l
         const int se = min(s0 + kWave, k_end);
+        // TOPK: the candidates' thresholds, lane l <-> thr[s0 + l] (lanes past the span: thr[se - 1], never a record): ONE coalesced f64
+        // load, issued in front of the span's first chunk and first read in the tail, n_bch (se - s0) steps later
+        double thr_k = 0.0;
+        if constexpr (TOPK) thr_k = rule.thr[min(s0 + lane, se - 1)];
         u64x2 q[Q][NCH];
         auto load_queries = [&](int c) {
 #pragma unroll
@@ -580,7 +619,13 @@ void smh_count_wide_kernel(const u64x2* __restrict__ X, const u64x2* __restrict_
             if constexpr (EMIT) {
                 bool sel;
                 const selhip_pair_t r = smhc_record(rule.em, m, cnt, rule.ex[i], rule.ey[kc], i, kl, &sel);
-                app.push_record(ok && sel, r, lane);
+                if constexpr (TOPK) {
+                    // the vector form of the admission test: thr[i] uniform, thr[k] and V per lane; only selected AND admitted lanes append
+                    app.push_record(ok && sel && smhc_admits_held(thr_i[a], thr_k, r.jaccard), r, lane);
+                    n_sel += (int)__popcll(__ballot(ok && sel));
+                } else {
+                    app.push_record(ok && sel, r, lane);
+                }
                 n_pass += (int)__popcll(__ballot(ok));
             } else {
                 app.push(ok, i, sp.partner(kl), lane);
@@ -589,6 +634,7 @@ void smh_count_wide_kernel(const u64x2* __restrict__ X, const u64x2* __restrict_
     }
     app.flush(lane);
     if constexpr (EMIT) smhc_tally(&pc->n_survivors, n_pass, lane);
+    if constexpr (TOPK) smhc_tally(&pc->n_final, n_sel, lane);
 }
 
 }  // namespace

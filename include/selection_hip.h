@@ -342,8 +342,8 @@ int selhip_ctx_set_criterion(selhip_ctx* ctx, int criterion);
  * (m = 128, 256, 512, 1024), 0 = any other kernel, -1 = none yet.  get_param "smhc_kernel_used": which kernel that was, 0 = generic,
  * 1 = the whole-row register tile of m = 128, 256, 512 or 1024 buckets, 2 = the narrow kernel of m = 32 or 64, 3 = the wide kernel of
  * every multiple of 1024 from 2048 to 8192; -1 = none yet.  The narrow and the wide kernel serve the all-pairs and the query passes
- * under both rules and both estimators; a round of a top-k pass in row rounds, the pair-list passes and every other m keep the
- * generic route.  selhip_ctx_set_param "smhc_generic" 1, a test and measurement hook read at each launch, gives every m the generic
+ * under both rules and both estimators, and every round of a top-k pass in row rounds (selhip_ctx_set_topk_rounds: 2 / 3 is read
+ * back behind such a pass); the pair-list passes and every other m keep the generic route.  selhip_ctx_set_param "smhc_generic" 1, a test and measurement hook read at each launch, gives every m the generic
  * kernel: the same survivors and records; 0 is the default, any other value is refused (SELHIP_E_BADARG).  The stage is timed as
  * "stage1". */
 int selhip_ctx_set_min_matches(selhip_ctx* ctx, int c_min);
@@ -520,7 +520,10 @@ int selhip_ctx_set_allpairs_topk(selhip_ctx* ctx, int k);
  * accessors behave as behind any cut pass; selhip_ctx_stats returns what the one-shot pass returns (stats[2] = |S|, the pairs with
  * V >= tau_f, not the admitted count); selhip_ctx_last_attempts is the largest attempt count of any round.  selhip_ctx_get_param:
  * "topk_rounds" (the setting), "topk_rounds_used" (rounds of the last all-pairs pass, 0 = it ran in one), "topk_admitted_lo" /
- * "topk_admitted_hi" (low / high 31 bits of the records admitted over all rounds).  Merge and thresholds are timed as "topk". */
+ * "topk_admitted_hi" (low / high 31 bits of the records admitted over all rounds).  Merge and thresholds are timed as "topk".
+ * Every round counts with the kernel of m that the one-shot pass takes ("smhc_kernel_used" behind the pass): the register tile at
+ * m = 128 ... 1024, the narrow kernel at m = 32 and 64, the wide kernel at every multiple of 1024 from 2048 to 8192, the generic
+ * kernel at every other m and under "smhc_generic" 1. */
 #define SELHIP_TOPK_ROUNDS_AUTO (-1)
 int selhip_ctx_set_topk_rounds(selhip_ctx* ctx, int64_t rows);
 

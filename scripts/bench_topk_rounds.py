@@ -13,7 +13,15 @@ the device after its warm-up (free device memory before the context minus after)
 call, median (min ... max); the ranked list of every variant is compared with the one-shot's (D46: with -R auto's) in every round.
 Also: |S|, the records admitted, the rounds, the records kept, and "stage1" / "topk" under the context's own timer (mean of 3).
 
+`--shapes all`: the rounds at the narrow and the wide rows.  The same generator at n = 16 384, K = 10,
+m = 32, 64, 2048, 4096 and R = n (one round: everything is admitted) and 1 024; one child process per (m, R).  One context, three routes:
+the pass in rounds on the kernel of m ("new"), the same pass under "smhc_generic" = 1 (the route these m took before) and the one-shot
+pass, which runs the emit form of the same kernel.  3 warm calls each, then 20 alternating rounds in a fresh seeded order, device ms as
+median (min ... max); the ranked lists of the three must be the same bytes in every round.  The aim of a line at R = n is the one-shot's
+median plus its spread (max - min); at R = 1 024 the line records generic / new.  Writes profiles/topk_rounds_shapes_bench.json.
+
 usage: bench_topk_rounds.py [--out profiles/topk_rounds_bench.json] [--only D4,D16,D46] [--reps 7] [--limit seconds per workload]
+       bench_topk_rounds.py --shapes all [--out profiles/topk_rounds_shapes_bench.json] [--reps 20] [--limit seconds per line]
 """
 import argparse
 import hashlib
@@ -149,6 +157,66 @@ def bench(name, reps):
     return out
 
 
+SHAPES_N = 16_384
+SHAPES = [(m, r) for m in (32, 64, 2048, 4096) for r in (SHAPES_N, 1024)]
+
+
+def bench_shape(m, rows, reps):
+    """one line of `--shapes all`: the three routes on one context"""
+    import torch
+    import cuda_selection_criteria_amd as pkg
+    n = SHAPES_N
+    hll_t, aux_t, cards_t = dense_set(n, m, 19)
+    sel = pkg.Selector(0)
+    sel.attach(hll_t, aux_t, cards_t)
+    sel.set_criterion(pkg.CRIT_SMH_C)
+    sel.set_min_matches(1)
+    sel.set_estimator("smh")
+    sel.set_allpairs_topk(K)
+    routes = {"new": (rows, 0), "generic": (rows, 1), "one_shot": (0, 0)}          # (rows per round, "smhc_generic")
+
+    def go(route):
+        per_round, generic = routes[route]
+        sel.set_topk_rounds(per_round)
+        sel.set_param("smhc_generic", generic)
+        sel.run(-1.0, pkg.MODE_SMH, 1, 1, fetch=False)
+        sel.set_param("smhc_generic", 0)
+
+    out = {"m": m, "n_genomes": n, "top_k": K, "rows_per_round": rows, "routes": {}}
+    for route in routes:
+        for _ in range(3):
+            go(route)
+        st = sel.stats()
+        adm = sel.get_param("topk_admitted_lo") + (sel.get_param("topk_admitted_hi") << 31)
+        out["routes"][route] = {"kernel_used": sel.get_param("smhc_kernel_used"), "rounds": sel.get_param("topk_rounds_used"), "selected": st["selected"],
+                                "admitted": adm if routes[route][0] else st["selected"], "kept": sel.result_count()}
+    samples = {route: [] for route in routes}
+    order_rng = np.random.default_rng(1)
+    for r in range(reps):
+        digest = {}
+        for route in [list(routes)[j] for j in order_rng.permutation(len(routes))]:
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            a.record()
+            go(route)
+            b.record()
+            torch.cuda.synchronize()
+            samples[route].append(a.elapsed_time(b))
+            digest[route] = hashlib.sha256(sel.fetch_ranked().tobytes()).hexdigest()
+        assert len(set(digest.values())) == 1, (r, digest)                                  # the same ranked list, byte for byte, every round
+        print(f"  [m = {m}, R = {rows}] round {r + 1} of {reps}", file=sys.stderr, flush=True)
+    for route in routes:
+        out["routes"][route]["device_ms"] = med(samples[route])
+    ms = {route: out["routes"][route]["device_ms"] for route in routes}
+    out["generic_over_new"] = round(ms["generic"]["median"] / ms["new"]["median"], 2)
+    out["lists_identical"] = True
+    if rows == n:
+        out["aim_ms"] = round(ms["one_shot"]["median"] + ms["one_shot"]["max"] - ms["one_shot"]["min"], 3)
+        out["aim_met"] = ms["new"]["median"] <= out["aim_ms"]
+    sel.close()
+    return out
+
+
 def report(r):
     print(json.dumps({k: r[k] for k in ("workload", "n_genomes", "m", "top_k", "pairs")}), flush=True)
     for v, d in r["variants"].items():
@@ -157,19 +225,41 @@ def report(r):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--out", default="profiles/topk_rounds_bench.json")
+    ap.add_argument("--out", default=None, help="profiles/topk_rounds_bench.json, with --shapes profiles/topk_rounds_shapes_bench.json")
     ap.add_argument("--only", default="D4,D16,D46")
-    ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--limit", type=int, default=240, help="seconds a workload's child process may take")
+    ap.add_argument("--shapes", choices=["all"], default=None, help="the rounds at m = 32, 64, 2048, 4096 instead of the workloads")
+    ap.add_argument("--reps", type=int, default=None, help="alternating rounds: 7, with --shapes 20")
+    ap.add_argument("--limit", type=int, default=None, help="seconds a workload's child process may take: 240, a line of --shapes 400")
     ap.add_argument("--worker", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    reps = args.reps or (20 if args.shapes else 7)
+    limit = args.limit or (400 if args.shapes else 240)
+    out_path = Path(args.out or ("profiles/topk_rounds_shapes_bench.json" if args.shapes else "profiles/topk_rounds_bench.json"))
+    if args.worker and args.shapes:
+        m, rows = (int(x) for x in args.worker.split(":"))
+        print("RESULT " + json.dumps(bench_shape(m, rows, reps)), flush=True)
+        return 0
     if args.worker:
-        print("RESULT " + json.dumps(bench(args.worker, args.reps)), flush=True)
+        print("RESULT " + json.dumps(bench(args.worker, reps)), flush=True)
         return 0
     results = []
+    if args.shapes:
+        for m, rows in SHAPES:
+            # a fresh child process per line, under its own time limit; nothing more is started after one that failed
+            child = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, __file__, "--shapes", "all", "--worker", f"{m}:{rows}", "--reps", str(reps)],
+                                   stdout=subprocess.PIPE, text=True)
+            line = next((ln for ln in child.stdout.splitlines() if ln.startswith("RESULT ")), None)
+            if child.returncode != 0 or line is None:
+                print(f"line m = {m}, R = {rows} ended with status {child.returncode}: stopping", file=sys.stderr, flush=True)
+                return 1
+            results.append(json.loads(line[len("RESULT "):]))
+            print(json.dumps(results[-1]), flush=True)
+            out_path.parent.mkdir(parents=True, exist_ok=True)
+            out_path.write_text(json.dumps({"device": "MI355X", "lines": results}, indent=1) + "\n")
+        return 0
     for name in args.only.split(","):
         # a fresh child process per workload, under its own time limit; nothing more is started after one that failed
-        child = subprocess.run(["timeout", "-k", "10", str(args.limit), sys.executable, __file__, "--worker", name, "--reps", str(args.reps)],
+        child = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, __file__, "--worker", name, "--reps", str(reps)],
                                stdout=subprocess.PIPE, text=True)
         line = next((ln for ln in child.stdout.splitlines() if ln.startswith("RESULT ")), None)
         if child.returncode != 0 or line is None:
@@ -178,8 +268,8 @@ def main():
         r = json.loads(line[len("RESULT "):])
         results.append(r)
         report(r)
-        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-        Path(args.out).write_text(json.dumps({"device": "MI355X", "workloads": results}, indent=1) + "\n")
+        out_path.parent.mkdir(parents=True, exist_ok=True)
+        out_path.write_text(json.dumps({"device": "MI355X", "workloads": results}, indent=1) + "\n")
     return 0
 
 
